@@ -4,6 +4,11 @@
 Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N>1 it is launched through
 torch.distributed.run, one rank per GPU.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times --steps headline steps, checks the last step's round trip and prints the headline
+(metric, value, unit, ms_per_step, ratio, config).  --full adds "container_assembly" and everything below from "roofline"
+on; --no-cpu, --no-legs, --no-e2e and --legs-only select parts of it.  --dump-outputs DIR writes what the last timed step computed (rank 0's batch):
+the unit stream offsets in full and fixed seeded samples of the packed streams and of the decoded frames, as .npy (dump_outputs).
+
 Headline (BASELINE.json configs[1]): a batch of DISTINCT synthetic XR-like frames of the reference's XR shape (cols 2577 x
 rows 2048, fseu16_test.go:32), noise tuned so that PICS-8 codes them at the reference's published XR ratio (~1.755), each coded
 as PICS with 8 strips (CompressParallelStrips(..., numStrips=8)).  One step = encode the whole batch, then decode it again, with
@@ -536,6 +541,29 @@ def leg_end_to_end(mic, torch, d_px, W, H, S, maxv, dev, devices=None):
     return out
 
 
+DUMP_SAMPLES = 6 << 20      # per sampled array: 24 MB as float32, so a dump stays under 64 MB
+
+
+def dump_outputs(path, mic, torch, dev, d_out, d_blobs, offs):
+    """What a caller of the timed path holds after the last step, as float arrays: the offset table of the packed unit streams
+    (every entry; float64 is exact for offsets below 2^53), and fixed seeded samples of the packed streams (bytes as float32) and of
+    the decoded frames (u16 pixels as float32).  The pixel positions depend only on the batch's shape, so two builds compare
+    sample for sample; the stream positions depend on the stream length as well, which equal streams share."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stream_offsets.npy"), offs.astype(np.float64))
+    total = int(offs[-1])
+    streams = torch.empty(total, dtype=torch.uint8, device=dev)
+    mic.device_copy(streams.data_ptr(), d_blobs, total)
+    torch.cuda.synchronize()
+    idx = np.sort(np.random.default_rng([20261015, 1]).integers(0, total, min(total, DUMP_SAMPLES)))
+    np.save(os.path.join(path, "streams_sample.npy"), streams[torch.from_numpy(idx).to(dev)].float().cpu().numpy())
+    del streams
+    flat = d_out.view(-1)
+    idx = np.sort(np.random.default_rng([20261015, 2]).integers(0, flat.numel(), min(flat.numel(), DUMP_SAMPLES)))
+    px = flat[torch.from_numpy(idx).to(dev)].to(torch.int32) & 0xFFFF                 # int16 storage of u16 pixels
+    np.save(os.path.join(path, "pixels_sample.npy"), px.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -548,11 +576,20 @@ def main():
     ap.add_argument("--cols", type=int, default=2577)
     ap.add_argument("--rows", type=int, default=2048)
     ap.add_argument("--noise", type=float, default=None, help="xr_like noise (default: the level that codes at the published XR ratio 1.755)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip configs 3-5 and the batch sweep")
-    ap.add_argument("--legs-only", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (PCIe-inclusive) figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the determinism check, per-kernel times and roofline, container assembly (N > 1), the host-buffer figure, "
+                         "the batch sweep, configs 3-5 and the CPU baseline; without it only the headline steps run")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="(--full) skip configs 3-5 and the batch sweep")
+    ap.add_argument("--legs-only", action="store_true", help="(--full) only configs 3-5 and the batch sweep")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the host-buffer (PCIe-inclusive) figure")
     args = ap.parse_args()
+    if not args.full and (args.no_cpu or args.no_legs or args.legs_only or args.no_e2e):
+        ap.error("--no-cpu, --no-legs, --legs-only and --no-e2e select parts of --full")
+    if args.legs_only and args.dump_outputs:
+        ap.error("--legs-only runs no headline steps: nothing to dump")
 
     # stdout carries ONE line, the result.  Native libraries write there too (RCCL prints a version banner when a process group comes
     # up): while the bench runs, file descriptor 1 points at stderr; it is put back for the line.
@@ -628,6 +665,23 @@ def main():
 
         assert torch.equal(d_out, d_px), "round trip differs"             # lossless check of the last step (outside the timed region)
         comp_bytes = int(offs[-1])
+        raw_bytes = d_px.numel() * 2
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, mic, torch, dev, d_out, d_blobs, offs)
+        ms_step = elapsed / args.steps * 1e3
+        value = raw_bytes * world / (elapsed / args.steps) / 1e9
+        out = {
+            "metric": "PICS-8 encode+decode throughput over raw u16 bytes (XR-shaped frames), lossless",
+            "value": round(value, 4), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u16", "data": "synthetic",
+            "config": {"workload": f"PICS-{S} encode+decode, {B} distinct XR-like {W}x{H} {args.depth}-bit synthetic frames ({n_units} strips) per GPU per step, "
+                                   f"noise tuned to the published XR PICS-8 ratio",
+                       "frames_per_gpu": B, "strips_per_frame": S, "width": W, "height": H, "max_value": maxv, "noise": noise,
+                       "fse": "2-state (CompressParallelStrips default)", "parallelism": f"{world} x independent batches"},
+            "ratio": round(raw_bytes / comp_bytes, 4),
+        }
+    if args.full and not args.legs_only:
         # consecutive steps, byte for byte: a lossless codec's stream is a pure function of its input (fse2state.go:122-199,
         # fsecompressu16.go:81-187) -- every unit's bytes and every offset of the next steps equal this one's (outside the timed region)
         first = torch.empty(comp_bytes, dtype=torch.uint8, device=dev)
@@ -643,7 +697,6 @@ def main():
         assert same_all, "the encoder produced different bytes for the same input in consecutive steps"
         determinism = {"steps_compared": 3, "units": n_units, "bytes": comp_bytes, "identical": True}
         del first
-        raw_bytes = d_px.numel() * 2
         kmean = mean_timings([step(True)[2] for _ in range(3)])           # per-kernel device times, separate instrumented steps
         dom = max(kmean, key=kmean.get)
         # HBM bytes of the dominant kernel: the committed PMC passes of this same command (tools/profile_bench.sh) -- used only when
@@ -660,8 +713,6 @@ def main():
                 traffic_source = {"file": "profiles/r04_traffic.json", "used": True, "csrc_sha16": meta.get("csrc_sha16")}
         except Exception:
             traffic = None
-        ms_step = elapsed / args.steps * 1e3
-        value = raw_bytes * world / (elapsed / args.steps) / 1e9
         enc_ms = sum(v for k, v in kmean.items() if k.startswith("k_enc") or k.startswith("k_scan"))
         dec_ms = sum(v for k, v in kmean.items() if k.startswith("k_dec"))
 
@@ -680,16 +731,7 @@ def main():
                         "bytes_on_rank0": int(alloffs[-1]) if rank == 0 else None,
                         "what": "all_gather of per-unit sizes + send/recv of the packed device blobs to rank 0 (RCCL over xGMI)"}
 
-        out = {
-            "metric": "PICS-8 encode+decode throughput over raw u16 bytes (XR-shaped frames), lossless",
-            "value": round(value, 4), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u16", "data": "synthetic",
-            "config": {"workload": f"PICS-{S} encode+decode, {B} distinct XR-like {W}x{H} {args.depth}-bit synthetic frames ({n_units} strips) per GPU per step, "
-                                   f"noise tuned to the published XR PICS-8 ratio",
-                       "frames_per_gpu": B, "strips_per_frame": S, "width": W, "height": H, "max_value": maxv, "noise": noise,
-                       "fse": "2-state (CompressParallelStrips default)", "parallelism": f"{world} x independent batches"},
-            "ratio": round(raw_bytes / comp_bytes, 4),
+        out.update({
             "encode_GBps_kernels": round(raw_bytes / (enc_ms * 1e-3) / 1e9, 4) if enc_ms else None,
             "decode_GBps_kernels": round(raw_bytes / (dec_ms * 1e-3) / 1e9, 4) if dec_ms else None,
             "kernel_ms": {k: round(v, 4) for k, v in kmean.items() if v >= 0.02},
@@ -699,30 +741,30 @@ def main():
             "container_assembly": assembly,
             "workspace": {"session_bytes": sess.workspace_bytes()[0], "tier2": sess.workspace_bytes()[1],
                           "x_input": round(sess.workspace_bytes()[0] / raw_bytes, 2)},
-        }
+        })
     sess.close()
 
-    if world == 1 and os.environ.get("MIC_BENCH_REHEARSE_MULTI"):       # the N > 1 legs on one rank (nccl, world size 1): a rehearsal of the code path
+    if args.full and world == 1 and os.environ.get("MIC_BENCH_REHEARSE_MULTI"):       # the N > 1 legs on one rank (nccl, world size 1): a rehearsal of the code path
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29511")
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
         out["legs_multi_gpu_rehearsal"] = legs_multi_gpu(mic, torch, synth, par, dist, dev, 0, 1, steps=2)
         dist.destroy_process_group()
         dist = None
-    if world > 1 and not args.no_legs:
+    if args.full and world > 1 and not args.no_legs:
         try:
             out["legs_multi_gpu"] = legs_multi_gpu(mic, torch, synth, par, dist, dev, rank, world)
         except Exception as e:  # noqa: BLE001 -- the headline line must come out whatever a leg does
             out["legs_multi_gpu"] = {"error": repr(e)}
         torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_e2e and not args.legs_only:
+    if args.full and world == 1 and not args.no_e2e and not args.legs_only:
         try:
             out["end_to_end"] = leg_end_to_end(mic, torch, d_px, W, H, S, maxv, dev)
         except Exception as e:  # noqa: BLE001 -- the headline line must come out whatever a leg does
             out["end_to_end"] = {"error": repr(e)}
         torch.cuda.empty_cache()
-    if world > 1 and not args.no_e2e and not args.legs_only:
+    if args.full and world > 1 and not args.no_e2e and not args.legs_only:
         # ONE process, all N devices (what a Go host does): rank 0 drives every GPU of the job through mic_hip_set_devices while the
         # other ranks wait at the barrier below with their sessions closed
         torch.cuda.empty_cache()
@@ -735,7 +777,7 @@ def main():
         dist.barrier()
         torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_legs:
+    if args.full and world == 1 and not args.no_legs:
         # B in {1, 64, 288, 512}: kernel time of one encode+decode per batch size (report B = 1 honestly)
         sweep = []
         for b in (1, 4, 16, 64, 288, 512):
@@ -775,7 +817,7 @@ def main():
         if "roofline" in out:
             out["roofline_fracs"] = {"config2_pics8_xr": out["roofline"]["frac"], **{k: (v.get("roofline") or {}).get("frac") for k, v in legs.items()}}
 
-    if rank == 0 and not args.no_cpu and not args.legs_only:
+    if rank == 0 and args.full and not args.no_cpu and not args.legs_only:
         from oracle import mico
         mico.lib()
         ref = load_reference_codec()
@@ -792,7 +834,7 @@ def main():
         else:
             out["cpu_baseline"] = port
         out["cpu_baseline"]["host"] = host_info()
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None
     if rank == 0 and out.get("cpu_baseline") and out.get("batch_sweep"):
         # smallest batch at which the device (frames resident in HBM) outruns this box's host cores on the same frames

@@ -28,6 +28,18 @@ def load_package():
     return mod
 
 
+def nema_image(mico, name):
+    """One of the reference's NEMA test images (testdata/compsamples_refanddir/IMAGES/REF/<name>_UNC), kept here as the reference
+    C codec's two-state stream of it, tests/golden/<name>_<width>_<height>_2state.mic (tests/golden/make_golden.py).  Its pixels
+    must hash to what golden.json recorded of the original file's."""
+    import json
+    rec = json.load(open(os.path.join(GOLDEN, "golden.json")))["streams"][f"{name}/2"]
+    w, h = rec["width"], rec["height"]
+    rc, px = mico.decompress_single_frame(open(os.path.join(GOLDEN, f"{name}_{w}_{h}_2state.mic"), "rb").read(), w, h)
+    assert rc == 0 and f"{mico.fnv1a64(px.tobytes()):016x}" == rec["pixels_fnv1a64"], name
+    return px
+
+
 @pytest.fixture(scope="session")
 def mic():
     return load_package()

@@ -828,100 +828,93 @@ def test_wavelet_batch_matches_single_calls(mic, mico, synth, gpu_ready):
     assert np.array_equal(back[0], frames[0]) and np.array_equal(back[3], frames[3])
 
 
-# ---- the reference's own C codec, where its in-place build travelled with the repo (oracle/_ref, test infrastructure) -----------
-def _ref_codec():
-    import ctypes as C
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libmic_ref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libmic_ref.so not built (needs /root/reference at build time)")
-    L = C.CDLL(path)
-    for name in ("two", "four", "eight"):
-        getattr(L, f"mic_compress_{name}_state").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        getattr(L, f"mic_decompress_{name}_state").argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
-    return L
+# ---- the reference's own C codec on the inputs below: tests/golden/make_golden.py ran it (oracle/_ref, built in place from the
+# ---- reference) and recorded the bytes it wrote and the files its readers took back (golden.json, "reference_c") ---------------
+def ref_codec_frames(synth):
+    """full-size XR / CT / MR shaped frames and odd ones, for CompressSingleFrame{,4State,8State}"""
+    return [synth.xr_like(cols=2577, rows=2048, depth=12, seed=31), synth.xr_like(cols=2577, rows=256, depth=12, seed=32),
+            synth.ct_stack(frames=1, size=512, depth=12, seed=5)[0], synth.xr_like(cols=333, rows=77, depth=10, seed=33), _ct()]
 
 
-def test_bitstreams_equal_the_reference_c_codec(mic, synth, gpu_ready):
-    """Same inputs, same bytes: mic_compress_{two,four,eight}_state (ojph/mic_compress_c.c, maxValue = the frame's own maximum) against
-    the library, full-size XR / CT / MR shaped frames and odd ones; each side decodes the other's stream."""
-    import ctypes as C
-    L = _ref_codec()
-    frames = [synth.xr_like(cols=2577, rows=2048, depth=12, seed=31), synth.xr_like(cols=2577, rows=256, depth=12, seed=32),
-              synth.ct_stack(frames=1, size=512, depth=12, seed=5)[0], synth.xr_like(cols=333, rows=77, depth=10, seed=33),
-              np.fromfile(os.path.join(GOLDEN, "CT_512_512_image.bin"), dtype="<u2").reshape(512, 512)]
-    for k, img in enumerate(frames):
+def ref_reader_cases(synth):
+    """(images with their maxValue, (strips, nstates) of each PICS file) that the reference's C reader was given"""
+    return ([(synth.xr_like(cols=2577, rows=2048, depth=12, seed=41), 4095), (synth.xr_like(cols=301, rows=203, depth=12, seed=42), 4095)],
+            [(8, 2), (8, 4), (5, 2), (1, 4), (16, 2)])
+
+
+def ref_payload_inputs(synth):
+    """a 2577 x 2048 image with one pixel at the global maximum in each of its 8 strips, and 12 CT-like frames that all hold the
+    stack's maximum"""
+    img = synth.xr_like(cols=2577, rows=2048, depth=12, seed=51).copy()
+    img[np.arange(0, 2048, 256) + 100, 1000] = 4095
+    stack = synth.ct_stack(frames=12, size=512, depth=12, seed=9).copy()
+    stack[:, 7, 7] = int(stack.max())
+    return img, stack
+
+
+def _same_bytes(mico, b, rec):
+    return len(b) == rec["size"] and f"{mico.fnv1a64(b):016x}" == rec["fnv1a64"]
+
+
+def test_bitstreams_equal_the_reference_c_codec(mic, mico, synth, gpu_ready):
+    """Same inputs, same bytes: the library against what mic_compress_{two,four,eight}_state (ojph/mic_compress_c.c, maxValue = the
+    frame's own maximum) wrote for full-size XR / CT / MR shaped frames and odd ones; the reference's own decoders read those streams
+    back when they were recorded, and the library decodes them."""
+    frames = ref_codec_frames(synth)
+    assert len(frames) == len(GOLD["reference_c"]["frames"])
+    for k, (img, rec) in enumerate(zip(frames, GOLD["reference_c"]["frames"])):
         img = np.ascontiguousarray(img)
         h, w = img.shape
+        assert [h, w] == rec["shape"] and f"{mico.fnv1a64(img.tobytes()):016x}" == rec["pixels_fnv1a64"], k
         mx = int(img.max())
-        for name, ns in (("two", 2), ("four", 4), ("eight", 8)):
-            out = np.empty(img.size * 4 + 135168, dtype=np.uint8)
-            n = C.c_size_t(0)
-            rc = getattr(L, f"mic_compress_{name}_state")(img.ctypes.data, w, h, out.ctypes.data, out.size, C.byref(n))
-            assert rc == 0, (k, name)
-            want = out[: n.value].tobytes()
+        for ns in (2, 4, 8):
             got = mic.compress_single_frame(img, w, h, mx, ns)
-            assert got == want, (k, name, len(got), len(want))
-            assert np.array_equal(mic.decompress_single_frame(want, w, h), img), (k, name)
-            back = np.empty_like(img)
-            g = np.frombuffer(got, dtype=np.uint8)
-            assert getattr(L, f"mic_decompress_{name}_state")(g.ctypes.data, g.size, back.ctypes.data, w, h) == 0 and np.array_equal(back, img), (k, name)
+            assert _same_bytes(mico, got, rec["streams"][str(ns)]), (k, ns, len(got))
+            assert np.array_equal(mic.decompress_single_frame(got, w, h), img), (k, ns)
 
 
 def test_pics_files_decode_with_the_reference_c_decoder(mic, mico, synth, gpu_ready):
-    """mic_decompress_parallel (ojph/mic_parallel.c:49, the reference's own C reader of PICS files, two- and four-state strips) reads
-    the PICS files the library writes, scalar and SIMD inner decoders, any thread count."""
-    import ctypes as C
-    L = _ref_codec()
-    for fn in ("mic_decompress_parallel", "mic_decompress_parallel_scalar"):
-        getattr(L, fn).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    for img, mx in ((synth.xr_like(cols=2577, rows=2048, depth=12, seed=41), 4095), (synth.xr_like(cols=301, rows=203, depth=12, seed=42), 4095)):
+    """mic_decompress_parallel (ojph/mic_parallel.c:49, the reference's own C reader of PICS files, two- and four-state strips) read
+    back the PICS files recorded here, scalar and SIMD inner decoders, several thread counts; the library writes those same files."""
+    images, cases = ref_reader_cases(synth)
+    assert len(images) == len(GOLD["reference_c"]["pics_reader"])
+    for (img, mx), recs in zip(images, GOLD["reference_c"]["pics_reader"]):
         h, w = img.shape
-        for strips, ns in ((8, 2), (8, 4), (5, 2), (1, 4), (16, 2)):
+        assert len(recs) == len(cases)
+        for (strips, ns), rec in zip(cases, recs):
+            assert (strips, ns) == (rec["strips"], rec["nstates"])
             rc, want = mico.pics_compress(img, mx, strips, ns)
-            if rc != 0:                                                  # strips too short for their alphabet: the reference fails too
+            assert rc == rec["rc"], (strips, ns)
+            if rc != 0:                                                  # strips too short for their alphabet
                 with pytest.raises(mic.MicError) as e:
                     mic.compress_parallel_strips(img, w, h, mx, strips, ns)
                 assert e.value.code == rc
                 continue
-            blob = np.frombuffer(mic.compress_parallel_strips(img, w, h, mx, strips, ns), dtype=np.uint8)
-            assert blob.tobytes() == want
-            for fn, threads in (("mic_decompress_parallel", 0), ("mic_decompress_parallel", 3), ("mic_decompress_parallel_scalar", 8)):
-                back = np.zeros_like(img)
-                assert getattr(L, fn)(blob.ctypes.data, blob.size, back.ctypes.data, w, h, threads) == 0, (strips, ns, fn)
-                assert np.array_equal(back, img), (strips, ns, fn)
+            assert _same_bytes(mico, want, rec), (strips, ns)
+            assert mic.compress_parallel_strips(img, w, h, mx, strips, ns) == want, (strips, ns)
 
 
-def test_pics_and_mic2_payloads_are_reference_written_bytes_when_every_unit_holds_max_value(mic, synth, gpu_ready):
+def test_pics_and_mic2_payloads_are_reference_written_bytes_when_every_unit_holds_max_value(mic, mico, synth, gpu_ready):
     """PICS strips and MIC2 frames are CompressSingleFrame(unit, GLOBAL maxValue) (parallelstrips.go:88, multiframecompress.go:201);
     the reference's C encoder derives maxValue from the unit it is given (ojph/mic_compress_c.c:774-775).  Where every unit holds a
     pixel equal to the global maximum the two agree, and the container payloads -- not only their readers -- are pinned to bytes the
     reference wrote: strip s of the PICS file == mic_compress_two_state(strip s), frame i of the MIC2 file likewise."""
-    import ctypes as C
-    L = _ref_codec()
-
-    def ref_two_state(px):
-        px = np.ascontiguousarray(px)
-        out = np.empty(px.size * 4 + 135168, dtype=np.uint8)
-        n = C.c_size_t(0)
-        assert L.mic_compress_two_state(px.ctypes.data, px.shape[1], px.shape[0], out.ctypes.data, out.size, C.byref(n)) == 0
-        return out[: n.value].tobytes()
-
-    img = synth.xr_like(cols=2577, rows=2048, depth=12, seed=51).copy()
-    img[np.arange(0, 2048, 256) + 100, 1000] = 4095                              # one pixel at the global maximum in each of the 8 strips
+    img, stack = ref_payload_inputs(synth)
+    recs = GOLD["reference_c"]["payloads"]
     assert int(img.max()) == 4095
     pics = mic.compress_parallel_strips(img, 2577, 2048, 4095, 8)
     tab = np.frombuffer(pics, dtype="<u4", count=16, offset=20).reshape(8, 2)
+    assert len(recs["pics_strips"]) == 8
     for s_ in range(8):
         a = 20 + 64 + int(tab[s_, 0])
-        assert pics[a: a + int(tab[s_, 1])] == ref_two_state(img[s_ * 256:(s_ + 1) * 256]), s_
-    stack = synth.ct_stack(frames=12, size=512, depth=12, seed=9).copy()
+        assert _same_bytes(mico, pics[a: a + int(tab[s_, 1])], recs["pics_strips"][s_]), s_
     mx = int(stack.max())
-    stack[:, 7, 7] = mx                                                           # every frame holds the stack's maximum
     mic2 = mic.compress_multi_frame(stack, 512, 512, mx)
     ft = np.frombuffer(mic2, dtype="<u4", count=24, offset=20).reshape(12, 2)
+    assert len(recs["mic2_frames"]) == 12
     for i in range(12):
         a = 20 + 96 + int(ft[i, 0])
-        assert mic2[a: a + int(ft[i, 1])] == ref_two_state(stack[i]), i
+        assert _same_bytes(mico, mic2[a: a + int(ft[i, 1])], recs["mic2_frames"][i]), i
 
 
 def test_sub_batch_loops(gpu_ready):
