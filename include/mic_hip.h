@@ -216,6 +216,27 @@ int mic_hip_compress_frame_grad(const uint16_t *pixels, int width, int height, u
 int mic_hip_decompress_frame_grad(const uint8_t *compressed, size_t compressed_len,
                                   uint16_t *pixels_out, int width, int height);
 
+/* ---- gap removal: the unit codec with a compact alphabet ------------------------------------------- */
+/* Replaces CompressSingleFrameGapRemoval / DecompressSingleFrameGapRemoval (gapremovalcompressu16.go:52-176, :178-282): the
+ * Delta+RLE tokens of CompressSingleFrame; when few of the values below the largest one occur (:104-111), the tokens are coded as
+ * indices into the sorted list of the values used, and the list goes in front of the FSE stream as a raw list (mode 0x01) or a
+ * delta list (0x03); otherwise the file is 0x00 || CompressSingleFrame's bytes.  The decoder also reads the bitmap form (0x02) the
+ * reference's encoder never chooses.  nstates = 2 is the reference's encoder byte for byte (two-state FSE, then one-state,
+ * :328-339); 4 and 8 apply the chains of CompressSingleFrame4State / 8State (multiframecompress.go:38-95) to the compact tokens --
+ * the reference's decoder reads those too (FSEDecompressU16Auto); anything else is MIC_ERR_ARGS.
+ * out_cap >= MIC_HIP_GAP_FRAME_BOUND(width*height) is always sufficient: a chosen map is never larger than the bitmap, at most
+ * 3 + 8192 bytes.  A malformed map, an empty input and a decoded compact symbol >= numSymbols (:270-273: only a symbol the payload
+ * emits counts, not one its NCount merely weights) are MIC_ERR_CORRUPT.  A gap-removal unit of the session API takes a map slab of
+ * 24 KiB beside the unit codec's (136 KiB in a session whose slabs are the worst-case ones). */
+#define MIC_HIP_GAP_FRAME_BOUND(npx) (MIC_HIP_FRAME_BOUND(npx) + 8195)
+int mic_hip_compress_frame_gap(const uint16_t *pixels, int width, int height, uint16_t max_value, int nstates,
+                               uint8_t *out, size_t out_cap, size_t *out_len);
+int mic_hip_decompress_frame_gap(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height);
+/* Many frames in one call, through the same pipeline as mic_hip_compress_batch / _decompress_batch (sub-batches, pinned staging,
+ * mic_hip_set_devices shards); per-job status and nstates_used as there.  Every job's bytes equal the single-frame call's. */
+int mic_hip_compress_batch_gap(mic_hip_enc_job *jobs, int njobs);
+int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs);
+
 /* ---- PICA container: content-adaptive strips, per-strip predictor choice ------------------------ */
 /* Replaces CompressParallelStripsAdaptive (parallelstripsadaptive.go:54): strip boundaries by equal-cost partition of the rows'
  * summed |vertical delta| (adaptiveStripBoundaries, :222-289, float64 like the reference), every strip coded with both the avg
@@ -348,12 +369,15 @@ typedef struct mic_hip_unit {
     uint64_t px_offset;     /* first pixel of the unit, in u16 elements from d_pixels */
     int32_t  width, height;
     uint16_t max_value;
-    uint16_t nstates;       /* 2 / 4 / 8, optionally | MIC_HIP_PRED_GRAD */
+    uint16_t nstates;       /* 2 / 4 / 8, optionally | MIC_HIP_PRED_GRAD or | MIC_HIP_GAP_REMOVAL */
 } mic_hip_unit;
 /* OR'ed into mic_hip_unit.nstates: the unit uses the gradient-adaptive predictor of CompressSingleFrameGrad /
  * DecompressSingleFrameGrad (multiframecompress.go:111-142, deltagradrlecompressu16.go) instead of avg(left, top).  The
  * stream does not record its predictor (PICA keeps it in the strip's flags word), so decode units must carry it too. */
 #define MIC_HIP_PRED_GRAD 0x200
+/* OR'ed into mic_hip_unit.nstates: the unit is a gap-removal stream (mic_hip_compress_frame_gap's bytes).  Decode units must carry it
+ * too; with MIC_HIP_PRED_GRAD it is MIC_ERR_ARGS (the reference has no such codec). */
+#define MIC_HIP_GAP_REMOVAL 0x800
 
 /* Encode n units.  Compressed blobs are left in the session; *d_blobs receives the device
  * address of a packed buffer holding them back to back, h_offsets[n+1] (host) their byte

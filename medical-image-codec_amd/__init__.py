@@ -31,6 +31,7 @@ MIC_ERR_INTERNAL = -8
 MIC_ERR_UNSUPPORTED = -9
 MIC_HIP_PRED_GRAD = 0x200          # OR'ed into a session unit's nstates: gradient-adaptive predictor (include/mic_hip.h)
 MIC_ERR_INCOMPRESSIBLE = -10
+MIC_HIP_GAP_REMOVAL = 0x800        # OR'ed into a session unit's nstates: a gap-removal stream (include/mic_hip.h)
 
 _ERR_NAMES = {
     MIC_ERR_ARGS: "bad arguments", MIC_ERR_NOMEM: "out of memory",
@@ -105,6 +106,7 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_compress", "mic_hip_mic2_compress_temporal", "mic_hip_mic2_info", "mic_hip_mic2_decompress",
     "mic_hip_mic2_decompress_frame",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
+    "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
     "mic_hip_compress_frame_grad", "mic_hip_decompress_frame_grad", "mic_hip_pica_compress", "mic_hip_pica_info", "mic_hip_pica_decompress",
     "mic_hip_rgb_compress", "mic_hip_rgb_decompress", "mic_hip_micr_compress", "mic_hip_micr_info", "mic_hip_micr_decompress",
     "mic_hip_mic1_compress", "mic_hip_mic1_info", "mic_hip_mic1_decompress",
@@ -200,12 +202,17 @@ def lib() -> C.CDLL:
     L.mic_hip_compress_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int,
                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_decompress_frame.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+    L.mic_hip_compress_frame_gap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mic_hip_decompress_frame_gap.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     L.mic_hip_fse_compress_u16.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_fse_decompress_u16_auto.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_fse_compress_u16_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_fse_decompress_u16_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_compress_batch.argtypes = [C.POINTER(EncJob), C.c_int]
     L.mic_hip_decompress_batch.argtypes = [C.POINTER(DecJob), C.c_int]
+    L.mic_hip_compress_batch_gap.argtypes = [C.POINTER(EncJob), C.c_int]
+    L.mic_hip_decompress_batch_gap.argtypes = [C.POINTER(DecJob), C.c_int]
     L.mic_hip_pics_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_int,
                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_pics_compress_ex.argtypes = L.mic_hip_pics_compress.argtypes + [C.POINTER(C.c_int)]
@@ -372,6 +379,72 @@ def decompress_batch(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]]) ->
     rc = lib().mic_hip_decompress_batch(jobs, n)
     if rc:
         _raise(rc, "decompress_batch")
+    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0]) if jobs[i].status == 0 else None) for i in range(n)]
+
+
+# ------------------------------------------------------------------ gap removal
+def _gap_frame_bound(npx: int) -> int:
+    """MIC_HIP_GAP_FRAME_BOUND (include/mic_hip.h)"""
+    return _frame_bound(npx) + 8195
+
+
+def compress_single_frame_gap_removal(pixels, width: int, height: int, max_value: int, nstates: int = 2) -> bytes:
+    """CompressSingleFrameGapRemoval (gapremovalcompressu16.go:52); nstates 4 / 8 code the compact tokens with the
+    CompressSingleFrame4State / 8State chains (the reference's decoder reads them)."""
+    px = _u16(pixels).reshape(-1)
+    if px.size != width * height:
+        raise MicError(MIC_ERR_ARGS, "compress_single_frame_gap_removal")
+    cap = _gap_frame_bound(px.size)
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().mic_hip_compress_frame_gap(px.ctypes.data, width, height, max_value, nstates, out.ctypes.data, cap, C.byref(n))
+    if rc:
+        _raise(rc, "compress_single_frame_gap_removal")
+    return out[: n.value].tobytes()
+
+
+def decompress_single_frame_gap_removal(compressed, width: int, height: int) -> np.ndarray:
+    """DecompressSingleFrameGapRemoval (gapremovalcompressu16.go:178); MicError(MIC_ERR_CORRUPT) for a malformed map or a decoded
+    compact symbol >= numSymbols (only one the payload emits, as :270-273)."""
+    c = _bytes_arr(compressed)
+    out = np.empty(width * height, dtype=np.uint16)
+    rc = lib().mic_hip_decompress_frame_gap(c.ctypes.data, c.size, out.ctypes.data, width, height)
+    if rc:
+        _raise(rc, "decompress_single_frame_gap_removal")
+    return out.reshape(height, width)
+
+
+def compress_batch_gap_removal(frames: Sequence[np.ndarray], max_values: Sequence[int], nstates: int = 2
+                               ) -> List[Tuple[int, bytes, int]]:
+    """compress_single_frame_gap_removal over many frames in one call; returns [(status, blob, nstates_used)]."""
+    n = len(frames)
+    arrs = [_u16(f) for f in frames]
+    outs = [np.empty(_gap_frame_bound(a.size), dtype=np.uint8) for a in arrs]
+    jobs = (EncJob * n)()
+    for i, a in enumerate(arrs):
+        h, w = a.shape
+        jobs[i].pixels = a.ctypes.data; jobs[i].width = w; jobs[i].height = h
+        jobs[i].max_value = int(max_values[i]); jobs[i].nstates = nstates
+        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
+    rc = lib().mic_hip_compress_batch_gap(jobs, n)
+    if rc:
+        _raise(rc, "compress_batch_gap_removal")
+    return [(jobs[i].status, outs[i][: jobs[i].out_len].tobytes() if jobs[i].status == 0 else b"", jobs[i].nstates_used)
+            for i in range(n)]
+
+
+def decompress_batch_gap_removal(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]]) -> List[Tuple[int, Optional[np.ndarray]]]:
+    """decompress_single_frame_gap_removal over many streams in one call; returns [(status, pixels or None)]."""
+    n = len(blobs)
+    cs = [_bytes_arr(b) for b in blobs]
+    outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
+    jobs = (DecJob * n)()
+    for i in range(n):
+        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
+        jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
+    rc = lib().mic_hip_decompress_batch_gap(jobs, n)
+    if rc:
+        _raise(rc, "decompress_batch_gap_removal")
     return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0]) if jobs[i].status == 0 else None) for i in range(n)]
 
 

@@ -129,7 +129,9 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
     int rc = s->ensure(n, max_px, tier);
     if (rc) return rc;
     { const int arc = s->h_units.assign((size_t)n, MicUnit{}); if (arc) return arc; }
-    bool any_grad = false, narrow = true;
+    bool any_grad = false, narrow = true, any_gap = false;
+    for (int i = 0; i < n; i++) any_gap |= (units[i].nstates & MIC_HIP_GAP_REMOVAL) != 0;
+    if (any_gap && (rc = s->gap.reserve((size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)n))) return rc;
     for (int i = 0; i < n; i++) {
         MicUnit &u = s->h_units[(size_t)i];
         narrow &= (units[i].nstates & 0xFF) <= 2;
@@ -137,6 +139,7 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         u.w = units[i].width; u.h = units[i].height;
         u.max_value = units[i].max_value; u.nstates = units[i].nstates & 0xFF;
         u.pred = (units[i].nstates & MIC_HIP_PRED_GRAD) ? 1u : 0u; any_grad |= u.pred != 0;
+        if (units[i].nstates & MIC_HIP_GAP_REMOVAL) { u.gap = 1; u.gap_buf = (uint8_t *)s->gap.p + (size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)i; }
         s->fill_workspace(u, i);
         u.tok_cap = (uint32_t)tok_cap_tier((size_t)u.w * (size_t)u.h, tier);
     }
@@ -152,7 +155,8 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         if ((size_t)units[i].width * (size_t)units[i].height <= 131072u) enc_hint |= MIC_ENC_CLS_SMALL12 | MIC_ENC_CLS_SMALL13;
         if (units[i].max_value >= 2048u) enc_hint |= MIC_ENC_CLS_TL14 | MIC_ENC_CLS_TL15 | MIC_ENC_CLS_TL16;
     }
-    mic_launch_encode((MicUnit *)s->units.p, n, s->stream, s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0), &s->timer,
+    mic_launch_encode((MicUnit *)s->units.p, n, s->stream, s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0) |
+                      (any_gap ? MIC_VARIANT_GAP : 0), &s->timer,
                       s->enc_classes.mask() | enc_hint);
     if (hipGetLastError() != hipSuccess) { s->hist_unknown(); return MIC_ERR_DEVICE; }
     s->begin_chain(n);
@@ -185,7 +189,8 @@ int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const m
         if (units[i].width <= 0 || units[i].height <= 0) return MIC_ERR_ARGS;
         max_px = std::max(max_px, (size_t)units[i].width * (size_t)units[i].height);
         const int ns = units[i].nstates & 0xFF;
-        if (!(ns == 2 || ns == 4 || ns == 8) || (units[i].nstates & ~(0xFF | MIC_HIP_PRED_GRAD))) return MIC_ERR_ARGS;
+        if (!(ns == 2 || ns == 4 || ns == 8) || (units[i].nstates & ~(0xFF | MIC_HIP_PRED_GRAD | MIC_HIP_GAP_REMOVAL))) return MIC_ERR_ARGS;
+        if ((units[i].nstates & MIC_HIP_PRED_GRAD) && (units[i].nstates & MIC_HIP_GAP_REMOVAL)) return MIC_ERR_ARGS;   // (no such codec in the reference)
         deep |= units[i].max_value >= (1u << 13);                        // depth 14+: tokens reach past 8192
     }
     if (max_px > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
@@ -305,9 +310,12 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
     if (n <= 0) return MIC_ERR_ARGS;
     if (n > 65535) return MIC_ERR_UNSUPPORTED;
     size_t max_px = 0;
+    bool any_gap = false;
     for (int i = 0; i < n; i++) {
         if (units[i].width <= 0 || units[i].height <= 0) return MIC_ERR_ARGS;
         max_px = std::max(max_px, (size_t)units[i].width * (size_t)units[i].height);
+        if ((units[i].nstates & MIC_HIP_PRED_GRAD) && (units[i].nstates & MIC_HIP_GAP_REMOVAL)) return MIC_ERR_ARGS;
+        any_gap |= (units[i].nstates & MIC_HIP_GAP_REMOVAL) != 0;
     }
     if (max_px > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
     for (int i = 0; i < n; i++) if (ends[i] < begins[i] || ends[i] - begins[i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
@@ -321,6 +329,7 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
     } else if (s->retry.kind != 0 && begins != s->retry.begins.data()) s->retry.kind = 0;
     int rc = s->ensure(n, max_px, tier);
     if (rc) return rc;
+    if (any_gap && (rc = s->gap.reserve((size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)n))) return rc;
     { const int arc = s->h_units.assign((size_t)n, MicUnit{}); if (arc) return arc; }
     bool any_grad = false;
     uint32_t rows_kmask = 0;                                             // predictor classes (by width) this batch holds
@@ -332,6 +341,7 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
         u.px_out = d_pixels_out + units[i].px_offset;
         u.w = units[i].width; u.h = units[i].height;
         u.pred = (units[i].nstates & MIC_HIP_PRED_GRAD) ? 1u : 0u; any_grad |= u.pred != 0;
+        if (units[i].nstates & MIC_HIP_GAP_REMOVAL) { u.gap = 1; u.gap_buf = (uint8_t *)s->gap.p + (size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)i; }
         s->fill_workspace(u, i);
         u.tok_cap = (uint32_t)tok_cap_tier((size_t)u.w * (size_t)u.h, tier);
         u.sym_cap = (uint32_t)std::min<size_t>(tok_cap_for((size_t)u.w * (size_t)u.h) + 64, 0xFFFFFFF0u);   // (a bound on the symbols a frame can use, not a slab size: the symbol slab is idle on this side)
@@ -339,7 +349,7 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
     { const int urc = s->h_units.upload(s->units.p, (size_t)n, s->stream); if (urc) return urc; }
     HIP_TRY(hipMemsetAsync(s->flags.p, 0, s->flag_stride * (size_t)n, s->stream));
     s->timer.reset(s->stream);
-    mic_launch_decode((MicUnit *)s->units.p, n, s->stream, s->variant | (any_grad ? MIC_VARIANT_GRAD : 0), &s->timer, (int *)s->cls.p, rows_kmask,
+    mic_launch_decode((MicUnit *)s->units.p, n, s->stream, s->variant | (any_grad ? MIC_VARIANT_GRAD : 0) | (any_gap ? MIC_VARIANT_GAP : 0), &s->timer, (int *)s->cls.p, rows_kmask,
                       s->dec_classes.mask());
     HIP_TRY(hipGetLastError());
     s->begin_chain(n);
@@ -450,6 +460,29 @@ int mic_hip_decompress_frame(const uint8_t *compressed, size_t compressed_len, u
     mic_hip_dec_job j{};
     j.compressed = compressed; j.compressed_len = compressed_len; j.pixels_out = pixels_out; j.width = width; j.height = height;
     int rc = mic_hip_decompress_batch(&j, 1);
+    if (rc) return rc;
+    return j.status;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+// ---- gap removal (gapremovalcompressu16.go:52-282): the unit codec with MIC_HIP_GAP_REMOVAL, through the batch pipeline
+int mic_hip_compress_frame_gap(const uint16_t *pixels, int width, int height, uint16_t max_value, int nstates,
+                               uint8_t *out, size_t out_cap, size_t *out_len) try {
+    if (!pixels || !out || !out_len || width <= 0 || height <= 0) return MIC_ERR_ARGS;
+    if (!(nstates == 2 || nstates == 4 || nstates == 8)) return MIC_ERR_ARGS;
+    mic_hip_enc_job j{};
+    j.pixels = pixels; j.width = width; j.height = height; j.max_value = max_value; j.nstates = (uint16_t)nstates;
+    j.out = out; j.out_cap = out_cap;
+    int rc = mic_hip_compress_batch_gap(&j, 1);
+    if (rc) return rc;
+    if (j.status == MIC_OK) *out_len = j.out_len;
+    return j.status;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+int mic_hip_decompress_frame_gap(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height) try {
+    if (!compressed || !pixels_out || width <= 0 || height <= 0) return MIC_ERR_ARGS;
+    mic_hip_dec_job j{};
+    j.compressed = compressed; j.compressed_len = compressed_len; j.pixels_out = pixels_out; j.width = width; j.height = height;
+    int rc = mic_hip_decompress_batch_gap(&j, 1);
     if (rc) return rc;
     return j.status;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)

@@ -38,11 +38,8 @@ struct BitR {
     }
 };
 
-// v0: one lane decodes the stream.  grid = units, block = 64.
-__global__ void __launch_bounds__(64) k_dec_tans_serial(MicUnit *units) {
-    MicUnit &u = units[blockIdx.x];
-    if (threadIdx.x != 0 || u.status != MICD_OK) return;
-    if (u.ntok != 0) return;                                           // a fast variant already decoded it
+// v0: one lane decodes the stream (the caller's lane 0; u.status == MICD_OK, u.ntok == 0): u.tok[0, u.ntok) or an error status.
+__device__ __noinline__ void dec_tans_serial_body(MicUnit &u) {
     const uint32_t tl = u.table_log;
     const uint32_t *dt = u.tt_nb;
     const uint16_t *ds = u.tab_sym;
@@ -84,6 +81,38 @@ __global__ void __launch_bounds__(64) k_dec_tans_serial(MicUnit *units) {
         st[k] = (e & 0xFFFF) + low;
     }
     u.ntok = count;
+}
+// grid = units, block = 64
+__global__ void __launch_bounds__(64) k_dec_tans_serial(MicUnit *units) {
+    MicUnit &u = units[blockIdx.x];
+    if (threadIdx.x != 0 || u.status != MICD_OK) return;
+    if (u.ntok != 0) return;                                           // a fast variant already decoded it
+    dec_tans_serial_body(u);
+}
+
+// Gap removal's checking path (mic_gap.hip: k_dec_gap_expand parks a unit whose table gives weight to a compact symbol >= numSymbols
+// in MICD_GAP_CHECK, its tab_sym left compact, so that no other decoder takes it): lane 0 decodes the compact symbols serially,
+// then the wave expands them through the map -- MIC_ERR_CORRUPT exactly when one of them is out of range, as
+// gapremovalcompressu16.go:270-273 fails.  The pixel kernels behind take the tokens as they take a one-state stream's.
+__global__ void __launch_bounds__(64) k_dec_gap_check(MicUnit *units) {
+    MicUnit &u = units[blockIdx.x];
+    if (u.status != MICD_GAP_CHECK) return;
+    const uint32_t lane = threadIdx.x;
+    int st = 0; uint32_t ntok = 0;
+    if (lane == 0) { u.status = MICD_OK; u.ntok = 0; dec_tans_serial_body(u); st = u.status; ntok = u.ntok; }
+    MIC_GROUP_HANDOFF();                                               // (lane 0's token stores, then every lane reads them)
+    st = __shfl(st, 0, 64); ntok = (uint32_t)__shfl((int)ntok, 0, 64);
+    if (st != MICD_OK) return;
+    const uint32_t lim = min(u.gap_nsym, u.tab_cap);                   // (the expand table holds the map's first tab_cap entries)
+    mic_gp<uint16_t> tok = mic_g(u.tok);
+    const mic_gp<const uint16_t> ex = mic_g((const uint16_t *)u.gap_buf);
+    bool bad = false;
+    for (uint32_t i = lane; i < ntok; i += 64) {
+        const uint32_t c = tok[i];
+        if (c >= lim) bad = true;
+        else tok[i] = ex[c];
+    }
+    if (__any(bad) && lane == 0) u.status = MICD_ERR_CORRUPT;
 }
 
 
@@ -272,9 +301,11 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
 
 
 void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant, MicTimer *t, int *d_cls, uint32_t pred_mask, uint32_t cls_mask) {
-    const bool any_grad = (variant & MIC_VARIANT_GRAD) != 0;
+    const bool any_grad = (variant & MIC_VARIANT_GRAD) != 0, gap = (variant & MIC_VARIANT_GAP) != 0;
+    if (gap) mic_launch_dec_gap_map(d_units, n, stream, t);
     if (t) t->mark("k_dec_tables_wg");
     mic_launch_dec_tables(d_units, n, stream);
+    if (gap) mic_launch_dec_gap_expand(d_units, n, stream, t);
     // lane-per-state kernels over compacted per-class lists (mic_decode_ls.hip): every table size has its class; what they leave
     // (a tableLog-16 table with 0-bit entries, 1-state streams) falls through to the kernels below, which skip decoded units
     mic_launch_dec_tans_ls(d_units, n, d_cls + MIC_CLS_HEAD, d_cls, stream, t, cls_mask);
@@ -283,6 +314,7 @@ void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant,
     if (t) t->mark("k_dec_tans_gl<4,8>");
     hipLaunchKernelGGL(k_dec_tans_gl<4>, dim3(n), dim3(64), 0, stream, d_units);
     hipLaunchKernelGGL(k_dec_tans_gl<8>, dim3(n), dim3(64), 0, stream, d_units);
+    if (gap) { if (t) t->mark("k_dec_gap_check"); hipLaunchKernelGGL(k_dec_gap_check, dim3(n), dim3(64), 0, stream, d_units); }
     if (t) t->mark("k_dec_tans_serial");
     hipLaunchKernelGGL(k_dec_tans_serial, dim3(n), dim3(64), 0, stream, d_units);
     mic_launch_decode_pixels(d_units, n, stream, t, any_grad, pred_mask);

@@ -12,6 +12,11 @@
 #define MIC_MIN_TABLELOG  5      // fseu16.go:26
 #define MIC_MAX_TABLELOG  16     // fseu16.go:23
 #define MIC_DEF_TABLELOG  11     // fseu16.go:25
+#define MIC_GAP_HDR_MAX   8195u      // 3 + 8192: the bitmap of a 65536-symbol alphabet bounds every map the encoder chooses
+// MicUnit.gap_buf: tab_cap u16 (enc: compact index per token value, dec: the map's first tab_cap entries), then the encoder's
+// mode || map bytes; mic_gap_stride(tab_cap) bytes per unit
+__host__ __device__ inline uint32_t mic_gap_map_off(uint32_t tab_cap) { return 2u * tab_cap; }
+__host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2u * tab_cap + MIC_GAP_HDR_MAX + 255u) & ~255u; }
 
 // status codes: keep in sync with include/mic_hip.h
 #define MICD_OK                  0
@@ -23,6 +28,7 @@
 #define MICD_ERR_UNSUPPORTED    -9
 #define MICD_ERR_INCOMPRESSIBLE -10
 #define MICD_INT_GROW           -21    // internal: a tier-1 slab would overflow; the host runs the batch again in tier 2 (never surfaces)
+#define MICD_GAP_CHECK          -22    // internal: a gap-removal unit for k_dec_gap_check, the checking decode path (never surfaces)
 
 struct MicUnit {
     // ---- inputs ------------------------------------------------------------------
@@ -66,6 +72,11 @@ struct MicUnit {
     uint32_t  wv_slow;        // WaveletV2: this frame takes the one-group kernels (escape words in its stream, or a stream the walker refused)
     uint32_t  wv_zmax;        // WaveletV2 encode: largest zigzag symbol of the frame
     uint32_t  hist_hi;        // encode: every token the tokeniser counted is below this (0: unknown -- all 65536 bins are scanned)
+    // gap removal (CompressSingleFrameGapRemoval / DecompressSingleFrameGapRemoval, gapremovalcompressu16.go; mic_gap.hip)
+    uint32_t  gap;            // 0: plain unit; 1: a gap-removal unit; 2: its tokens use the compact alphabet behind a map
+    uint32_t  gap_hdr_len;    // encode: bytes of mode || map written in front of the FSE stream; decode: bytes skipped
+    uint32_t  gap_nsym;       // decode: numSymbols of the map
+    uint8_t  *gap_buf;        // mic_gap_stride(tab_cap) bytes: enc compact-index table / dec expand table, then enc mode || map
     // ---- results -----------------------------------------------------------------
     uint32_t ntok;            // number of u16 in tok
     uint32_t blob_len;

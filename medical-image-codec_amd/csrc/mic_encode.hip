@@ -1320,11 +1320,18 @@ __global__ void __launch_bounds__(256) k_enc_pack(const MicUnit *units, const ui
     if (u.status != MICD_OK) return;
     if (dst_off[n] + 16 > cap) return;                                   // (the batch does not fit: the host packs it again into a larger buffer)
     const mic_gp<const uint8_t> src = mic_g((const uint8_t *)u.blob) + (u.nstates_used == 1 ? 6 : 0);
-    const mic_gp<uint8_t> d = mic_g(dst) + dst_off[blockIdx.y];
+    mic_gp<uint8_t> d = mic_g(dst) + dst_off[blockIdx.y];
+    // a gap-removal unit: mode || map first (mic_gap.hip; blob_len counts them)
+    const uint32_t ghdr = u.gap ? u.gap_hdr_len : 0u;
+    if (ghdr) {
+        const mic_gp<const uint8_t> m = mic_g((const uint8_t *)u.gap_buf + mic_gap_map_off(u.tab_cap));
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ghdr; i += gridDim.x * blockDim.x) d[i] = m[i];
+        d += ghdr;
+    }
     // 16 bytes per thread and step; neither side is aligned (gfx950 runs vector memory in unaligned mode)
     typedef uint32_t pk_v4 __attribute__((ext_vector_type(4)));
     typedef pk_v4 PkQ __attribute__((aligned(1)));
-    const uint32_t len = u.blob_len, nvec = len / 16;
+    const uint32_t len = u.blob_len - ghdr, nvec = len / 16;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += gridDim.x * blockDim.x)
         *(mic_gp<PkQ>)(d + (size_t)i * 16) = *(mic_gp<const PkQ>)(src + (size_t)i * 16);
     if (blockIdx.x == 0 && threadIdx.x < (len & 15u)) d[nvec * 16 + threadIdx.x] = src[nvec * 16 + threadIdx.x];
@@ -1372,8 +1379,11 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
     hipLaunchKernelGGL(k_enc_tokens_wg<0>, dim3(n), dim3(TK_THREADS), 0, stream, d_units);
     if (!frames) hipLaunchKernelGGL(k_enc_tokens_wg<1>, dim3(n), dim3(TK_THREADS), 0, stream, d_units);
     if (any_grad) hipLaunchKernelGGL((k_enc_tokens_wg<0, 1>), dim3(n), dim3(TK_THREADS), 0, stream, d_units);
+    const bool gap = (variant & MIC_VARIANT_GAP) != 0;
+    if (gap) mic_launch_enc_gap(d_units, n, stream, t);
     if (t) t->mark("k_enc_tables_wg");
     mic_launch_enc_tables(d_units, n, stream);
+    if (gap) mic_launch_enc_gap_remap(d_units, n, stream, t);
     static MicPerDeviceOnce once;
     once.run([] {
         (void)hipFuncSetAttribute((const void *)k_enc_tans_wg<13, TE_THREADS, TE_TT_SYMS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
@@ -1397,6 +1407,7 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
     if (enc_mask & MIC_ENC_CLS_TL16) hipLaunchKernelGGL((k_enc_tans_wg<16, TE_THREADS16, TE_TT_SYMS>), dim3(n), dim3(TE_THREADS16), (2u << 16) + TE_THREADS16 * (unsigned)es * 2u, stream, d_units, es);
     if (t) t->mark("k_enc_tans_serial");
     hipLaunchKernelGGL(k_enc_tans_serial, dim3(n), dim3(64), 0, stream, d_units);
+    if (gap) mic_launch_enc_gap_len(d_units, n, stream);
     if (t) t->mark("k_enc_hist_clean");
     hipLaunchKernelGGL(k_enc_hist_clean, dim3(n), dim3(256), 0, stream, d_units);
     if (t) t->mark("end");

@@ -200,17 +200,22 @@ struct DecUnit {
     int32_t status = MIC_OK;
 };
 
+inline bool unit_gap(const EncUnit &u) { return (u.nstates & MIC_HIP_GAP_REMOVAL) != 0; }
+inline bool unit_gap(const DecUnit &u) { return (u.flags & MIC_HIP_GAP_REMOVAL) != 0; }
 // units [i0, i1) of the next sub-batch: under the workspace ceiling, and -- when the call is large enough to be worth a pipeline --
 // about `target` units (the kernels want a couple of thousand units per launch: the tANS decode chain takes as long for ten
 // streams as for 2304)
 template <class U>
 int next_cut(const std::vector<U> &units, int i0, size_t target) {
     const int n = (int)units.size();
-    size_t max_px = 0, cap = 0; int i1 = i0;
+    size_t max_px = 0, cap = 0, gap_x = 0; int i1 = i0;
     while (i1 < n) {
         const size_t px = (size_t)units[(size_t)i1].w * (size_t)units[(size_t)i1].h;
         const size_t mp = std::max(max_px, px);
-        if (mp != max_px || cap == 0) cap = batch_units_for(mp, 1, 12 * mp);   // (+ the staging: two halves each of the pixels, the streams, the packed buffer)
+        // (a gap-removal unit holds a map slab beside the others: the tier-2 one is counted)
+        const size_t gx = std::max(gap_x, unit_gap(units[(size_t)i1]) ? (size_t)mic_gap_stride(65536u) : (size_t)0);
+        if (mp != max_px || gx != gap_x || cap == 0) cap = batch_units_for(mp, 1, 12 * mp + gx);   // (+ the staging: two halves each of the pixels, the streams, the packed buffer)
+        gap_x = gx;
         if (i1 > i0 && ((size_t)(i1 - i0 + 1) > cap || (size_t)(i1 - i0) >= target || i1 - i0 >= 65535)) break;
         max_px = mp; i1++;
     }
@@ -516,7 +521,8 @@ void *mic_hip_host_alloc(size_t bytes) {
 }
 void mic_hip_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
-int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
+// flags: OR-ed into every unit's nstates (MIC_HIP_GAP_REMOVAL for the _gap entry points)
+static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
@@ -528,7 +534,7 @@ int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
         if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || (size_t)j.width * (size_t)j.height > ((size_t)1 << 28) ||
             !(j.nstates == 2 || j.nstates == 4 || j.nstates == 8)) { j.status = MIC_ERR_ARGS; continue; }
         G.push_back(EncGroup{ j.pixels, j.out, j.out_cap, 0, (int)U.size(), 1 });
-        U.push_back(EncUnit{ 0, j.width, j.height, j.max_value, j.nstates, (int)G.size() - 1 });
+        U.push_back(EncUnit{ 0, j.width, j.height, j.max_value, (uint16_t)(j.nstates | flags), (int)G.size() - 1 });
         job_of.push_back(i);
     }
     if ((rc = encode_sharded(G, U))) return rc;
@@ -538,9 +544,15 @@ int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
         j.out_len = G[k].status == MIC_OK ? G[k].written : 0;
     }
     return MIC_OK;
+}
+int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
+    return compress_jobs(jobs, njobs, 0);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+int mic_hip_compress_batch_gap(mic_hip_enc_job *jobs, int njobs) try {
+    return compress_jobs(jobs, njobs, MIC_HIP_GAP_REMOVAL);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
-int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs) try {
+static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
@@ -553,12 +565,18 @@ int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs) try {
             j.status = (j.compressed && j.compressed_len == 0) ? MIC_ERR_CORRUPT : MIC_ERR_ARGS; continue;
         }
         G.push_back(DecGroup{ j.compressed, j.pixels_out, (int)U.size(), 1 });
-        U.push_back(DecUnit{ 0, j.compressed_len, 0, j.width, j.height, 0, (int)G.size() - 1 });
+        U.push_back(DecUnit{ 0, j.compressed_len, 0, j.width, j.height, flags, (int)G.size() - 1 });
         job_of.push_back(i);
     }
     if ((rc = decode_sharded(G, U))) return rc;
     for (size_t k = 0; k < G.size(); k++) jobs[job_of[k]].status = G[k].status;
     return MIC_OK;
+}
+int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs) try {
+    return decompress_jobs(jobs, njobs, 0);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs) try {
+    return decompress_jobs(jobs, njobs, MIC_HIP_GAP_REMOVAL);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // ---- PICS (parallelstrips.go) ----------------------------------------------------------------

@@ -50,6 +50,7 @@ struct MicTimer {
 #define MIC_VARIANT_GRAD 0x1000
 #define MIC_VARIANT_NARROW 0x2000       // encode: no unit of the batch asks for more than two states (sizes k_enc_tans_wg's end-state area)
 #define MIC_VARIANT_FRAMES 0x4000       // encode: every unit is a frame (mode 0, avg or gradient predictor): the symbol-unit kernels are not launched
+#define MIC_VARIANT_GAP 0x8000         // some unit is a gap-removal one (mic_gap.hip): its map kernels are only launched then
 // Launch masks.  Most kernels of a chain come in classes (table size, flavour, frame width) and a homogeneous batch uses one or two
 // of them; a launch of a class without units is an empty grid that still costs ~5 us of the device's time (~45 of them per encode +
 // decode of a PICS batch, 0.2 ms).  What the HOST knows (widths, modes) it says outright; what only the streams know (flavour,
@@ -104,4 +105,11 @@ __host__ __device__ inline int mic_dec_cls(uint32_t flavour, uint32_t tl, uint32
     return (tl <= 12 ? 4 : (int)tl - 13) * 6 + (ns == 2 ? 0 : ns == 4 ? 2 : 4) + (zero_bits ? 1 : 0);
 }
 void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream);
+// gap removal (mic_gap.hip): encode -- map and compact histogram behind the tokeniser, token remap in front of the tANS encoder, the
+// header's bytes added to blob_len behind it; decode -- map parse in front of k_dec_parse, expansion of tab_sym behind the tables
+void mic_launch_enc_gap(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
+void mic_launch_enc_gap_remap(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
+void mic_launch_enc_gap_len(MicUnit *d_units, int n, hipStream_t stream);
+void mic_launch_dec_gap_map(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
+void mic_launch_dec_gap_expand(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
 void mic_launch_dec_tables(MicUnit *d_units, int n, hipStream_t stream);

@@ -146,6 +146,7 @@ struct mic_hip_session {
     // devices: every public call makes the session's device the calling thread's current one first.
     int activate() { return hipSetDevice(device) == hipSuccess ? MIC_OK : MIC_ERR_DEVICE; }
     DevBuf units, cls, tok, hist, norm, tt_nb, tt_find, state_tab, tab_sym, cumul, blob, packed, offsets, seg, sym, flags;
+    DevBuf gap;                            // gap-removal units' map slabs (mic_gap_stride(tab_syms) each), reserved by the first batch that has one
     DevBuf io_px, io_comp;                 // staging for the host-pointer entry points
     DevBuf io_px2, io_comp2, packed2;      // their second halves: sub-batch k + 1 comes up while k is coded and k - 1 goes down (mic_host_io.hip)
     DevBuf wv_a, wv_b;                     // WaveletV2 coefficient planes (int32, two per frame of the batch)
@@ -262,13 +263,13 @@ struct mic_hip_session {
         u.flags = (uint32_t *)((char *)flags.p + flag_stride * (size_t)i);
     }
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
