@@ -128,6 +128,15 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
     for (int i = 0; i < n; i++) max_px = std::max(max_px, (size_t)units[i].width * (size_t)units[i].height);
     int rc = s->ensure(n, max_px, tier);
     if (rc) return rc;
+    // The packed buffer is sized from what the session's last batch needed; it is reserved here, in front of the chain (a reallocation
+    // behind it would wait for the queued chain to drain).
+    {
+        size_t raw = 0;
+        for (int i = 0; i < n; i++) raw += (size_t)units[i].width * (size_t)units[i].height * 2;
+        const size_t want = std::max(s->pack_hint + s->pack_hint / 8, raw / 3) + ((size_t)64 << 10);
+        if ((rc = s->packed.reserve(want))) return rc;
+        if ((rc = s->pin_off.reserve((size_t)n + 1))) return rc;
+    }
     { const int arc = s->h_units.assign((size_t)n, MicUnit{}); if (arc) return arc; }
     bool any_grad = false, narrow = true, any_gap = false;
     for (int i = 0; i < n; i++) any_gap |= (units[i].nstates & MIC_HIP_GAP_REMOVAL) != 0;
@@ -163,14 +172,9 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
     s->learn_encode = true;                                              // (behind begin_chain, which clears it: the masks were never learned)
     // Compaction and the read-back of the results ride behind the chain, so that session_encode_finish is ONE synchronisation (round 3:
     // descriptors down, a synchronisation, sizes summed on the host, scan + pack launched, a second synchronisation -- 86 us of idle
-    // device between the chain and the pack of every call).  The packed buffer is sized from what the session's last batch needed;
-    // k_enc_pack leaves a batch that does not fit alone and finish packs it again into a buffer of the right size.
+    // device between the chain and the pack of every call).  The pack kernels leave a batch that does not fit the packed buffer alone
+    // and finish packs it again into a buffer of the right size.
     {
-        size_t raw = 0;
-        for (int i = 0; i < n; i++) raw += (size_t)units[i].width * (size_t)units[i].height * 2;
-        const size_t want = std::max(s->pack_hint + s->pack_hint / 8, raw / 3) + ((size_t)64 << 10);
-        if ((rc = s->packed.reserve(want))) return rc;
-        if ((rc = s->pin_off.reserve((size_t)n + 1))) return rc;
         mic_launch_pack((const MicUnit *)s->units.p, n, (uint64_t *)s->offsets.p, (uint8_t *)s->packed.p, (uint64_t)s->packed.cap, s->stream, &s->timer);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(s->h_units.data(), s->units.p, sizeof(MicUnit) * (size_t)n, hipMemcpyDeviceToHost, s->stream));

@@ -90,6 +90,7 @@ struct MicUnit {
     uint32_t bits_off;        // decode: offset of the bitstream inside comp_in
     uint32_t count;           // decode: symbol count from the 6-byte prefix
     uint32_t flavour;         // decode: 1/2/4/8, 108 = rANS-8
+    uint32_t packed_direct;   // encode: 1 = the bitstream goes straight to the packed buffer (k_enc_tans_pack); the blob holds only the framing
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
 };
 

@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (u.mode != (SRC ? 2u : 0u)) return;                    // bare-FSE units (mode 1) bring their own tokens
     if (SRC && u.status != MICD_OK) return;                   // the symbol producer already failed
-    if (tid == 0) { u.status = MICD_OK; u.ntok = 0; u.blob_len = 0; u.nstates_used = 0; s_ovf = 0; s_last[0] = s_last[1] = 0; s_tmaxall = 0; s_frun = 0; }
+    if (tid == 0) { u.status = MICD_OK; u.ntok = 0; u.blob_len = 0; u.nstates_used = 0; u.packed_direct = 0; s_ovf = 0; s_last[0] = s_last[1] = 0; s_tmaxall = 0; s_frun = 0; }
     const int depth = mic_len16(u.max_value);
     if (!SRC && (u.w <= 0 || u.h <= 0)) { if (tid == 0) u.status = MICD_ERR_ARGS; return; }
     if (depth < 4) { if (tid == 0) u.status = MICD_ERR_UNSUPPORTED; return; }   // see k_enc_tokens_serial
@@ -665,7 +665,7 @@ __global__ void __launch_bounds__(256) k_enc_symbols(MicUnit *units) {
     // (a caller's symbols may be anything up to 65535: bare FSE units run on tier-2 slabs only -- every caller lays them out so)
     const bool fits = n <= u.tok_cap && u.tier != 1;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        u.status = fits ? MICD_OK : (u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CAPACITY); u.ntok = fits ? n : 0; u.blob_len = 0; u.nstates_used = 0;
+        u.status = fits ? MICD_OK : (u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CAPACITY); u.ntok = fits ? n : 0; u.blob_len = 0; u.nstates_used = 0; u.packed_direct = 0;
     }
     if (!fits) return;
     const uint16_t *src = u.px_in; uint16_t *tok = u.tok; uint32_t *hist = u.hist;
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(64) k_enc_tans_serial(MicUnit *units) {
                 u.blob[4] = (uint8_t)(n >> 16); u.blob[5] = (uint8_t)(n >> 24);
             }
             // 1-state streams have no prefix: the blob starts at u.blob + 6
-            u.blob_len = out_len; u.nstates_used = lanes; u.status = MICD_OK;
+            u.blob_len = out_len; u.nstates_used = lanes; u.packed_direct = 0; u.status = MICD_OK;
             return;
         }
         u.status = rc;                                                  // error of the last attempt
@@ -837,7 +837,164 @@ __device__ __forceinline__ void te_set(TeBlkT<B> &b, int j, uint32_t x) {
 #else
 #define TE_SYNC() __syncthreads()
 #endif
-template <int N, bool RANS, bool TTL, int T, bool FS>   // FS: the LDS state table holds whole states (they fit 16 bits up to tableLog 15)
+// Phase 4 of the walk below, and the trailer: thread t packs its blocks [b_lo, b_hi) from the true start states stp into the bit grid
+// `words` from grid bit gstart on; thread 0 then writes the final states fin (fse2state.go:194-197) and the end mark at grid bit pos.
+// BOUND (k_enc_tans_pack: the grid is the final buffer, where the unit's neighbours live): the 64-bit word holding the first grid byte
+// `lead` when that is not 8-aligned, and the one holding the last, end_b - 1, when that does not end a word, are shared with the
+// neighbours, which another group (on another XCD, behind another L2) writes at the same time.  Nothing of this group touches them in
+// HBM: every store and OR into them goes to s_edge[2] in LDS (zeroed by the caller), and thread 0 stores their own bytes at the end.
+// Returns the bits packed (TE_CHECK builds compare them with the walk's).
+#ifndef TE_RING
+#define TE_RING 4                 // units of a store group (a power of two): 4 = 32 bytes, a memory sector
+#endif
+template <int N, int BLK, bool BOUND, class Step>
+__device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> src, mic_gp<uint32_t> words, uint64_t gstart,
+                                            uint32_t b_lo, uint32_t b_hi, uint32_t n, uint32_t (&stp)[N], uint32_t mybits,
+                                            uint64_t pos, const uint32_t (&fin)[N], uint32_t tl, uint64_t lead, uint64_t end_b,
+                                            unsigned long long *s_edge) {
+    typedef TeBlkT<BLK> TeBlk;
+    const uint32_t tid = threadIdx.x;
+    // 64-bit units, stored in aligned PAIRS (16 bytes): the memory counters charge every store instruction a 32-byte write whatever
+    // its width or its neighbours (1.74 GB of output as dword stores = 435 M x 32 bytes = 13.9 GB of WRITE_SIZE, measured in two
+    // orders of the same stores; as 64-bit stores 8.3 GB and 6.4 -> 5.2 ms), so the pass makes a quarter as many.  A unit is stored by
+    // the thread owning its first bit; the threads that only reach into it OR their bits in after a barrier.
+    const mic_gp<unsigned long long> words64 = (mic_gp<unsigned long long>)words;
+    const mic_gp<uint8_t> bytes = (mic_gp<uint8_t>)words;
+    const uint32_t first_q = (uint32_t)(gstart >> 6);
+    const bool own_first = (gstart & 63) == 0;
+    uint32_t q = first_q;
+    uint64_t acc = 0; uint32_t filled = (uint32_t)(gstart & 63);
+    uint64_t lead_val = 0; bool have_lead = false;
+    typedef unsigned long long te_u2 __attribute__((ext_vector_type(2)));
+    uint64_t abl_chk = 0;
+    const uint64_t qh = (BOUND && (lead & 7)) ? lead >> 3 : ~0ull, qt = (BOUND && (end_b & 7)) ? (end_b - 1) >> 3 : ~0ull;
+    auto edge = [&](uint64_t qi) -> int { return !BOUND ? -1 : qi == qh ? 0 : qi == qt ? 1 : -1; };   // s_edge slot of a shared word
+    auto or_edge = [&](int e, uint64_t v) { (void)__hip_atomic_fetch_or(&s_edge[e], (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+    auto put1 = [&](uint32_t qi, uint64_t v) {                             // one unit
+        const int e = edge(qi);
+        if (e >= 0) or_edge(e, v); else words64[qi] = v;
+    };
+    uint64_t rg[TE_RING]; uint32_t rmask = 0;                            // the units of the current group that are waiting (the last slot: the one that completes it)
+#pragma unroll
+    for (int i = 0; i < TE_RING; i++) rg[i] = 0;
+    auto flush4 = [&](uint32_t base, uint64_t vlast, bool have_last) {    // base: the group's first unit (a multiple of TE_RING)
+        const uint32_t m = rmask | (have_last ? 1u << (TE_RING - 1) : 0u);
+        rg[TE_RING - 1] = vlast;
+#pragma unroll
+        for (int i = 0; i < TE_RING; i += 2) {
+            const uint32_t mm = (m >> i) & 3u;
+            if (mm == 3u) {
+                if (edge(base + i) >= 0 || edge(base + i + 1) >= 0) { put1(base + i, rg[i]); put1(base + i + 1, rg[i + 1]); }
+                else { te_u2 pr; pr.x = rg[i]; pr.y = rg[i + 1]; *(mic_gp<te_u2>)(words64 + base + i) = pr; }
+            }
+            else if (mm & 1u) put1(base + i, rg[i]);
+            else if (mm & 2u) put1(base + i + 1, rg[i + 1]);
+        }
+    };
+    auto emit = [&](uint64_t v) {                                          // unit q is complete (or the thread's last, partial one)
+        if (TE_ABL & 2) { q++; return; }
+        if (TE_ABL & 4) { abl_chk ^= v; q++; return; }                          // (timing only: the pass without its stores)
+        if (q == first_q && !own_first) { lead_val = v; have_lead = true; }
+        // Units leave in aligned groups of FOUR (32 bytes, two 16-byte stores back to back): the memory side writes 32-byte sectors,
+        // and a lone 16-byte store 1.4 KiB from its lane neighbours' left a sector half written when its line was evicted -- the
+        // counters showed the stream written 2.75 times.
+        else if ((q & (TE_RING - 1u)) == TE_RING - 1u) { flush4(q - (TE_RING - 1u), v, true); rmask = 0; }
+        else {
+            const uint32_t k = q & (TE_RING - 1u);
+#pragma unroll
+            for (int i = 0; i < TE_RING - 1; i++) rg[i] = k == (uint32_t)i ? v : rg[i];
+            rmask |= 1u << k;
+        }
+        q++;
+    };
+    uint32_t pbits = 0;
+    // Four tokens (<= 64 bits) are gathered branch-free before they meet the accumulator: the test "does a 64-bit unit fill up"
+    // is a divergent branch that some lane takes at almost every token, so it is made once per four of them.
+    for (uint32_t b = b_hi; b > b_lo; b--) {
+        const uint32_t base = (b - 1) * BLK;
+        const TeBlk tk = te_load<BLK>(src + base);
+        const bool whole = base + BLK <= n;
+#pragma unroll
+        for (int j4 = BLK / 4 - 1; j4 >= 0; j4--) {
+            uint64_t t4 = 0; uint32_t f4 = 0;
+#pragma unroll
+            for (int jj = 3; jj >= 0; jj--) {
+                const int j = j4 * 4 + jj;
+                if (whole || base + (uint32_t)j < n) {
+                    const int k = j & (N - 1);
+                    const uint32_t stt = stp[k];
+                    uint32_t nb;
+                    stp[k] = step(stt, te_get(tk, j), nb);
+                    const uint32_t bv = __builtin_amdgcn_ubfe(stt, 0u, nb);   // nb <= 16
+                    t4 |= (uint64_t)bv << f4;                                // f4 <= 48 here
+                    f4 += nb;
+                }
+            }
+#ifdef TE_CHECK
+            pbits += f4;
+#endif
+            acc |= t4 << filled;                                             // filled < 64
+            const uint32_t nf = filled + f4;
+            if (nf >= 64) {
+                emit(acc);
+                acc = filled ? (t4 >> (64u - filled)) : 0ull;                // what did not fit
+                filled = nf - 64;
+            } else filled = nf;
+        }
+    }
+    if (mybits > 0 && filled > 0) emit(acc);                             // the thread's last, partial unit
+    if ((TE_ABL & 4) && abl_chk == 0x1234567ull) words64[first_q] = abl_chk;
+    if (rmask) flush4((q - 1u) & ~(TE_RING - 1u), 0ull, false);           // (a group the next thread completes)
+#ifdef TE_NO_HANDOFF    // diagnostic: the barrier round 3 had here before MIC_GROUP_HANDOFF
+    __threadfence_block(); __syncthreads();
+#else
+    MIC_GROUP_HANDOFF();                                   // (every unit is in L2 before anything is OR-ed into it)
+#endif
+    if (have_lead && lead_val) {
+        if (edge(first_q) >= 0) or_edge(edge(first_q), lead_val);
+        else (void)__hip_atomic_fetch_or(&words64[first_q], (unsigned long long)lead_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __threadfence_block();
+    TE_SYNC();
+    if (tid == 0) {
+        // final states, last lane first (fse2state.go:194-197), then the end mark.  The word the symbols' last bit lies in is shared
+        // with the atomic ORs other threads have just made (executed at L2, nothing here waits for them): the trailer ORs its bits in
+        // the same way instead of reading the word back; the words wholly behind that bit are zeroed first and the zeroes are
+        // acknowledged before the first OR.
+        const uint64_t end = pos + (uint64_t)N * tl + 1;
+        for (uint64_t ww = (pos + 31) >> 5; ww <= ((end - 1) >> 5); ww++) if (edge(ww >> 1) < 0) words[ww] = 0;   // (s_edge starts at zero)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef TE_OLD_TRAILER   // diagnostic: round 3's trailer, a plain read-modify-write of the shared word
+        auto or32 = [&](uint32_t wi, uint32_t bits) { words[wi] |= bits; };
+#else
+        auto or32 = [&](uint32_t wi, uint32_t bits) {
+            if (!bits) return;
+            if (edge(wi >> 1) >= 0) or_edge(edge(wi >> 1), (uint64_t)bits << (32 * (wi & 1)));
+            else (void)__hip_atomic_fetch_or(&words[wi], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        };
+#endif
+        for (int k = N - 1; k >= 0; k--) {
+            const uint64_t v = (uint64_t)fin[k] & (((uint64_t)1 << tl) - 1);  // addBits32NC(state, tl)
+            const uint32_t wi = (uint32_t)(pos >> 5), sh = (uint32_t)(pos & 31);
+            or32(wi, (uint32_t)(v << sh));
+            if (sh + tl > 32) or32(wi + 1, (uint32_t)(v >> (32 - sh)));
+            pos += tl;
+        }
+        or32((uint32_t)(pos >> 5), 1u << (pos & 31));                   // bitwriter.go:162-168
+        if (BOUND) {                                                    // the shared words: this unit's bytes of them, nothing else
+            for (int e = 0; e < 2; e++) {
+                const uint64_t qe = e ? qt : qh;
+                if (qe == ~0ull || (e && qt == qh)) continue;
+                const uint64_t v = s_edge[e];
+                for (uint64_t b = max(8 * qe, lead); b < min(8 * qe + 8, end_b); b++) bytes[b] = (uint8_t)(v >> (8 * (b - 8 * qe)));
+            }
+        }
+    }
+    return pbits;
+}
+
+template <int N, bool RANS, bool TTL, int T, bool FS, bool DEFER = false>   // FS: the LDS state table holds whole states (they fit 16 bits up to tableLog 15);
+                                                                       // DEFER: stop after phase 3 (the records are what k_enc_tans_pack starts from)
 __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *s_tt,
                           uint16_t *s_E, uint32_t *s_scan, int &rc_out, uint32_t &total_bytes_out) {   // s_E: T x N end states
     // tokens per block: the two-state walk (the usual flavour) reads a whole 128-byte line at a time (two 64-byte halves read apart were two
@@ -1062,94 +1219,18 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
     if (rc != MICD_OK) return;
 #endif
     MIC_STAMP_AT(u, 10);
+    if (DEFER) return;                                   // (the records hold the true states: k_enc_tans_pack packs into the final buffer)
     // ---- 4. pack -------------------------------------------------------------------------------------
-    // 64-bit units, stored in aligned PAIRS (16 bytes): the memory counters charge every store instruction a 32-byte write whatever
-    // its width or its neighbours (1.74 GB of output as dword stores = 435 M x 32 bytes = 13.9 GB of WRITE_SIZE, measured in two
-    // orders of the same stores; as 64-bit stores 8.3 GB and 6.4 -> 5.2 ms), so the pass makes a quarter as many.  A unit is stored by
-    // the thread owning its first bit; the threads that only reach into it OR their bits in after a barrier.
-    const mic_gp<unsigned long long> words64 = (mic_gp<unsigned long long>)words;
-    const uint32_t first_q = (uint32_t)(gstart >> 6);
-    const bool own_first = (gstart & 63) == 0;
-    uint32_t q = first_q;
-    uint64_t acc = 0; uint32_t filled = (uint32_t)(gstart & 63);
-    uint64_t lead_val = 0; bool have_lead = false;
-    typedef unsigned long long te_u2 __attribute__((ext_vector_type(2)));
-    uint64_t abl_chk = 0;
-#ifndef TE_RING
-#define TE_RING 4                 // units of a store group (a power of two): 4 = 32 bytes, a memory sector
-#endif
-    uint64_t rg[TE_RING]; uint32_t rmask = 0;                            // the units of the current group that are waiting (the last slot: the one that completes it)
-#pragma unroll
-    for (int i = 0; i < TE_RING; i++) rg[i] = 0;
-    auto flush4 = [&](uint32_t base, uint64_t vlast, bool have_last) {    // base: the group's first unit (a multiple of TE_RING)
-        const uint32_t m = rmask | (have_last ? 1u << (TE_RING - 1) : 0u);
-        rg[TE_RING - 1] = vlast;
-#pragma unroll
-        for (int i = 0; i < TE_RING; i += 2) {
-            const uint32_t mm = (m >> i) & 3u;
-            if (mm == 3u) { te_u2 pr; pr.x = rg[i]; pr.y = rg[i + 1]; *(mic_gp<te_u2>)(words64 + base + i) = pr; }
-            else if (mm & 1u) words64[base + i] = rg[i];
-            else if (mm & 2u) words64[base + i + 1] = rg[i + 1];
-        }
-    };
-    auto emit = [&](uint64_t v) {                                          // unit q is complete (or the thread's last, partial one)
-        if (TE_ABL & 2) { q++; return; }
-        if (TE_ABL & 4) { abl_chk ^= v; q++; return; }                          // (timing only: the pass without its stores)
-        if (q == first_q && !own_first) { lead_val = v; have_lead = true; }
-        // Units leave in aligned groups of FOUR (32 bytes, two 16-byte stores back to back): the memory side writes 32-byte sectors,
-        // and a lone 16-byte store 1.4 KiB from its lane neighbours' left a sector half written when its line was evicted -- the
-        // counters showed the stream written 2.75 times.
-        else if ((q & (TE_RING - 1u)) == TE_RING - 1u) { flush4(q - (TE_RING - 1u), v, true); rmask = 0; }
-        else {
-            const uint32_t k = q & (TE_RING - 1u);
-#pragma unroll
-            for (int i = 0; i < TE_RING - 1; i++) rg[i] = k == (uint32_t)i ? v : rg[i];
-            rmask |= 1u << k;
-        }
-        q++;
-    };
-#ifdef TE_CHECK
-    uint32_t pbits = 0;
-#endif
     {
-        uint32_t stp[N];
         const uint32_t lastown = (nblk + per - 1) / per;   // threads 0 .. lastown-1 own tokens; s_E[T-1] was overwritten for the trailer
+        uint32_t stp[N], fin[N];
 #pragma unroll
-        for (int k = 0; k < N; k++) stp[k] = (tid > 0 && tid < lastown) ? (uint32_t)s_E[(tid - 1) * N + k] + size : size;
-        // Four tokens (<= 64 bits) are gathered branch-free before they meet the accumulator: the test "does a 64-bit unit fill up"
-        // is a divergent branch that some lane takes at almost every token, so it is made once per four of them.
-        for (uint32_t b = b_hi; b > b_lo; b--) {
-            const uint32_t base = (b - 1) * BLK;
-            const TeBlk tk = te_load<BLK>(src + base);
-            const bool whole = base + BLK <= n;
-#pragma unroll
-            for (int j4 = BLK / 4 - 1; j4 >= 0; j4--) {
-                uint64_t t4 = 0; uint32_t f4 = 0;
-#pragma unroll
-                for (int jj = 3; jj >= 0; jj--) {
-                    const int j = j4 * 4 + jj;
-                    if (whole || base + (uint32_t)j < n) {
-                        const int k = j & (N - 1);
-                        const uint32_t stt = stp[k];
-                        uint32_t nb;
-                        stp[k] = step(stt, te_get(tk, j), nb);
-                        const uint32_t bv = __builtin_amdgcn_ubfe(stt, 0u, nb);   // nb <= 16
-                        t4 |= (uint64_t)bv << f4;                                // f4 <= 48 here
-                        f4 += nb;
-                    }
-                }
-#ifdef TE_CHECK
-                pbits += f4;
-#endif
-                acc |= t4 << filled;                                             // filled < 64
-                const uint32_t nf = filled + f4;
-                if (nf >= 64) {
-                    emit(acc);
-                    acc = filled ? (t4 >> (64u - filled)) : 0ull;                // what did not fit
-                    filled = nf - 64;
-                } else filled = nf;
-            }
+        for (int k = 0; k < N; k++) {
+            stp[k] = (tid > 0 && tid < lastown) ? (uint32_t)s_E[(tid - 1) * N + k] + size : size;
+            fin[k] = (uint32_t)s_E[(T - 1) * N + k] + size;
         }
+        const uint32_t pbits = te_pack<N, BLK, false>(step, src, words, gstart, b_lo, b_hi, n, stp, mybits, 8ull * lead + sym_bits, fin, tl, lead, 0, nullptr);
+        (void)pbits;
 #ifdef TE_CHECK
         {
             uint32_t bad = pbits != mybits ? 2u : 0u;
@@ -1157,40 +1238,6 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
             if (bad) { atomicOr(&u.dbg[15], bad); atomicMin(&u.dbg[13], tid | 0x10000u); }
         }
 #endif
-    }
-    if (mybits > 0 && filled > 0) emit(acc);                             // the thread's last, partial unit
-    if ((TE_ABL & 4) && abl_chk == 0x1234567ull) words64[first_q] = abl_chk;
-    if (rmask) flush4((q - 1u) & ~(TE_RING - 1u), 0ull, false);           // (a group the next thread completes)
-#ifdef TE_NO_HANDOFF    // diagnostic: the barrier round 3 had here before MIC_GROUP_HANDOFF
-    __threadfence_block(); __syncthreads();
-#else
-    MIC_GROUP_HANDOFF();                                   // (every unit is in L2 before anything is OR-ed into it)
-#endif
-    if (have_lead && lead_val) (void)__hip_atomic_fetch_or(&words64[first_q], (unsigned long long)lead_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence_block();
-    TE_SYNC();
-    if (tid == 0) {
-        // final states, last lane first (fse2state.go:194-197), then the end mark.  The word the symbols' last bit lies in is shared
-        // with the atomic ORs other threads have just made (executed at L2, nothing here waits for them): the trailer ORs its bits in
-        // the same way instead of reading the word back; the words wholly behind that bit are zeroed first and the zeroes are
-        // acknowledged before the first OR.
-        uint64_t pos = 8ull * lead + sym_bits;
-        const uint64_t end = pos + (uint64_t)N * tl + 1;
-        for (uint64_t ww = (pos + 31) >> 5; ww <= ((end - 1) >> 5); ww++) words[ww] = 0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef TE_OLD_TRAILER   // diagnostic: round 3's trailer, a plain read-modify-write of the shared word
-        auto or32 = [&](uint32_t wi, uint32_t bits) { words[wi] |= bits; };
-#else
-        auto or32 = [&](uint32_t wi, uint32_t bits) { if (bits) (void)__hip_atomic_fetch_or(&words[wi], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-#endif
-        for (int k = N - 1; k >= 0; k--) {
-            const uint64_t v = (uint64_t)((uint32_t)s_E[(T - 1) * N + k] + size) & (((uint64_t)1 << tl) - 1);  // addBits32NC(state, tl)
-            const uint32_t wi = (uint32_t)(pos >> 5), sh = (uint32_t)(pos & 31);
-            or32(wi, (uint32_t)(v << sh));
-            if (sh + tl > 32) or32(wi + 1, (uint32_t)(v >> (32 - sh)));
-            pos += tl;
-        }
-        or32((uint32_t)(pos >> 5), 1u << (pos & 31));                   // bitwriter.go:162-168
     }
 #ifdef MIC_GATE_REG2
     total_bytes_out = total_bytes; rc_out = rc_reg;
@@ -1266,7 +1313,7 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
                 if (WIDTH != 1 && rans) te_encode<8, true, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
                 else if (WIDTH != 1 && lanes == 8) te_encode<8, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
                 else if (WIDTH != 1 && lanes == 4) te_encode<4, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
-                else if (lanes == 2) te_encode<2, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
+                else if (lanes == 2) te_encode<2, false, true, T, (TLHI <= 15), (WIDTH == 1)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
 #ifndef TE_COMBINED
                 else if (WIDTH == 1) rc = MICD_ERR_INTERNAL;                            // (not reached: the two-state instance hands its fall-backs over)
 #endif
@@ -1298,6 +1345,7 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
                 }
                 u.blob_len = ((lanes == 1) ? 0 : 6) + hdr_len + total_bytes;      // 1-state blob starts at blob + 6
                 u.nstates_used = (int32_t)lanes;
+                u.packed_direct = (WIDTH == 1 && lanes == 2) ? 1u : 0u;           // (its bitstream is k_enc_tans_pack's to write)
                 u.status = MICD_OK;
             }
             return;
@@ -1312,12 +1360,89 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
     }
 }
 
+// Phase 4 of the two-state 512-thread instance (k_enc_tans_wg<13, 512, .., 1>), run after k_scan_lens: every unit that instance coded
+// (packed_direct) is packed straight to dst + dst_off[unit], framing first -- gap-removal mode || map, the 6-byte prefix and the NCount
+// from the blob -- so k_enc_pack copies none of its bytes.  The walk left in u.sym one record per 128 tokens with the true states
+// behind it and the bits it emits: a thread's bit count is the sum of its records, its start state its predecessor's last record, the
+// final states the last record of the last thread that owns tokens.  The grid is laid on 32-byte boundaries of dst itself, so the
+// store groups are whole sectors; the unit's first and last words are shared with its neighbours: they are put together in LDS and
+// only the unit's own bytes of them are stored (te_pack<.., BOUND>).  grid = units, block = 512, dynamic LDS = 2 << 13 + TTS x 8 bytes.
+template <int T, int TTS>
+__global__ void __launch_bounds__(T, TE_NARROW_WPS) k_enc_tans_pack(const MicUnit *units, const uint64_t *dst_off, uint8_t *dst, uint64_t cap, int nu) {
+    constexpr int N = 2, BLK = TE_BLK2;
+    constexpr uint32_t RGRP = 128 / BLK;
+    extern __shared__ __attribute__((aligned(16))) uint16_t s_stab[];
+    __shared__ uint32_t s_scan[T / 64];
+    __shared__ unsigned long long s_edge[2];                           // the unit's two words shared with its neighbours (te_pack)
+    const MicUnit &u = units[blockIdx.x];
+    if (u.status != MICD_OK || !u.packed_direct) return;
+    if (dst_off[nu] + 16 > cap) return;                                  // (the batch does not fit: the host packs it again into a larger buffer)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n = u.ntok, tl = u.table_log, size = 1u << tl;
+    if (tid < 2) s_edge[tid] = 0;
+    {
+        const mic_gp<const uint32_t> gst = mic_g((const uint32_t *)u.state_tab);
+        for (uint32_t i = tid; i < size; i += T) s_stab[i] = (uint16_t)gst[i];
+    }
+    uint2 *s_tt = (uint2 *)(s_stab + (1u << 13));
+    {
+        const mic_gp<const uint32_t> gnb = mic_g((const uint32_t *)u.tt_nb); const mic_gp<const int32_t> gfi = mic_g((const int32_t *)u.tt_find);
+        for (uint32_t i = tid; i < u.symbol_len; i += T) s_tt[i] = make_uint2(gnb[i], (uint32_t)gfi[i]);
+    }
+    // framing
+    const uint32_t ghdr = u.gap ? u.gap_hdr_len : 0u, hdr = 6u + u.hdr_len;
+    const mic_gp<uint8_t> d = mic_g(dst) + dst_off[blockIdx.x];
+    if (ghdr) {
+        const mic_gp<const uint8_t> m = mic_g((const uint8_t *)u.gap_buf + mic_gap_map_off(u.tab_cap));
+        for (uint32_t i = tid; i < ghdr; i += T) d[i] = m[i];
+    }
+    { const mic_gp<const uint8_t> b = mic_g((const uint8_t *)u.blob); for (uint32_t i = tid; i < hdr; i += T) d[ghdr + i] = b[i]; }
+    // the thread's blocks, records, bits and start state (the walk's partition: te_encode)
+    const uint32_t nblk = (n + BLK - 1) / BLK, per = (nblk + T - 1) / T, gper = (per + RGRP - 1) / RGRP;
+    const uint32_t b_hi = (tid * per < nblk) ? nblk - tid * per : 0;
+    const uint32_t b_lo = (b_hi > per) ? b_hi - per : 0;
+    const uint32_t lastown = (nblk + per - 1) / per;
+    const mic_gp<const uint32_t> rec = mic_g((const uint32_t *)u.sym);   // record g of thread t: words 2 (t gper + g) (both states) and + 1 (bits)
+    uint32_t mybits = 0;
+    for (uint32_t g = 0; g < (b_hi - b_lo + RGRP - 1) / RGRP; g++) mybits += rec[2 * ((size_t)tid * gper + g) + 1] & 0xFFFFu;
+    uint32_t stp[N], fin[N];
+    {
+        const uint32_t w = (tid > 0 && tid < lastown) ? rec[2 * ((size_t)tid * gper - 1)] : 0u;   // (threads before the last owner hold per blocks)
+        const uint32_t l_hi = nblk - (lastown - 1) * per, l_lo = (l_hi > per) ? l_hi - per : 0;
+        const uint32_t wf = rec[2 * ((size_t)(lastown - 1) * gper + (l_hi - l_lo + RGRP - 1) / RGRP - 1)];
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            stp[k] = (tid > 0 && tid < lastown) ? ((w >> (16 * k)) & 0xFFFFu) + size : size;
+            fin[k] = ((wf >> (16 * k)) & 0xFFFFu) + size;
+        }
+    }
+    const uint32_t incl = tk_wave_incl_add(mybits, lane);
+    if (lane == 63) s_scan[wave] = incl;
+    __syncthreads();
+    uint32_t woff = 0, sym_bits = 0;
+#pragma unroll
+    for (int wv = 0; wv < (T / 64); wv++) { const uint32_t v = s_scan[wv]; if ((uint32_t)wv < wave) woff += v; sym_bits += v; }
+    const mic_gp<uint8_t> bits_base = d + ghdr + hdr;
+    const uint32_t lead = (uint32_t)((uintptr_t)bits_base & 31);
+    const mic_gp<uint32_t> words = (mic_gp<uint32_t>)(bits_base - lead);
+    const uint64_t total_bits = (uint64_t)sym_bits + (uint64_t)N * tl + 1;
+    const uint64_t end_b = lead + ((total_bits + 7) >> 3);              // grid bytes of the unit (the blob_len the walk reported, less the framing)
+    auto step = [&](uint32_t state, uint32_t sy, uint32_t &nb_out) -> uint32_t {   // te_encode's tANS step, whole states in LDS
+        const uint2 r = s_tt[sy];
+        const uint32_t nb = (state + r.x) >> 16;
+        nb_out = nb;
+        return s_stab[(int32_t)(state >> nb) + (int32_t)r.y];
+    };
+    (void)te_pack<N, BLK, true>(step, mic_g((const uint16_t *)u.tok), words, 8ull * lead + woff + incl - mybits, b_lo, b_hi, n, stp, mybits,
+                                8ull * lead + sym_bits, fin, tl, lead, end_b, s_edge);
+}
+
 // ------------------------------------------------------------------------------------------
 // Compaction: copy every unit's staging blob to its final offset.  grid = (chunks, units).
 // dst_off[i] = byte offset of unit i in `dst` (exclusive scan of blob_len, done by k_scan_lens).
 __global__ void __launch_bounds__(256) k_enc_pack(const MicUnit *units, const uint64_t *dst_off, uint8_t *dst, uint64_t cap, int n) {
     const MicUnit &u = units[blockIdx.y];
-    if (u.status != MICD_OK) return;
+    if (u.status != MICD_OK || u.packed_direct) return;                 // (k_enc_tans_pack has written that one)
     if (dst_off[n] + 16 > cap) return;                                   // (the batch does not fit: the host packs it again into a larger buffer)
     const mic_gp<const uint8_t> src = mic_g((const uint8_t *)u.blob) + (u.nstates_used == 1 ? 6 : 0);
     mic_gp<uint8_t> d = mic_g(dst) + dst_off[blockIdx.y];
@@ -1415,6 +1540,8 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
 void mic_launch_pack(const MicUnit *d_units, int n, uint64_t *d_off, uint8_t *d_dst, uint64_t d_cap, hipStream_t stream, MicTimer *t) {
     if (t) t->mark("k_scan_lens");
     hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, stream, d_units, n, d_off);
+    if (t) t->mark("k_enc_tans_pack");
+    hipLaunchKernelGGL((k_enc_tans_pack<TE_THREADS, TE_TT_SYMS>), dim3(n), dim3(TE_THREADS), (2u << 13) + TE_TT_SYMS * 8, stream, d_units, d_off, d_dst, d_cap, n);
     if (t) t->mark("k_enc_pack");
     hipLaunchKernelGGL(k_enc_pack, dim3(32, n), dim3(256), 0, stream, d_units, d_off, d_dst, d_cap, n);
     if (t) t->mark("end");
