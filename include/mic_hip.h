@@ -54,7 +54,9 @@ extern "C" {
  * one session per device with mic_hip_session_create_on and uses the session entry points. */
 int mic_hip_set_device(int device);
 /* SEVERAL devices for the batch entry points below (mic_hip_compress_batch / _decompress_batch, mic_hip_pics_compress_batch /
- * _decompress_batch, mic_hip_mic2_compress / _decompress): a call's jobs are cut into one contiguous shard per listed device,
+ * _decompress_batch, mic_hip_mic2_compress / _decompress, mic_hip_wavelet_v2_compress_batch / _decompress_batch) and for the MIC3
+ * calls mic_hip_wsi_compress / _compress_ex (bands of tile rows, see there), mic_hip_wsi_decompress_level and
+ * mic_hip_wsi_decompress_region (tile rows; a region of two tile rows or more): a call's jobs are cut into one contiguous shard per listed device,
  * balanced by pixels -- the static assignment of the reference's fan-outs (parallelstrips.go:77-93, multiframecompress.go:186-209,
  * wsicompress.go:126-145) -- and the shards run side by side, each on a session of its device's pool with its own sub-batch
  * pipeline and transfer streams; results are written straight into the caller's buffers (no gather: the caller's memory is the
@@ -68,6 +70,10 @@ int mic_hip_get_devices(int *devices, int cap);
  * `shards` contiguous shards -- item i belongs to shard k iff first[k] <= i < first[k + 1]; first has shards + 1 entries.
  * Needs no device. */
 int mic_hip_shard_plan(const uint64_t *weights, int n, int shards, int *first);
+/* The bands mic_hip_wsi_compress_ex cuts a slide into over `shards` devices (arguments as there: tile sizes 0 = 256, levels <= 0 =
+ * automatic).  *k_out = K, the top level every band codes itself; band b is the rows row_first[b] .. row_first[b + 1] - 1 (row_first
+ * has shards + 1 entries; a band may be empty).  Needs no device. */
+int mic_hip_wsi_band_plan(int width, int height, int tile_w, int tile_h, int levels, int shards, int *k_out, int *row_first);
 /* "gfx950 <n CUs> ..." style description of the active device; "" if none. */
 const char *mic_hip_device_name(void);
 const char *mic_hip_version(void);
@@ -305,7 +311,14 @@ int mic_hip_wsi_compress(const uint8_t *rgb, int width, int height, int tile_w, 
 /* CompressWSI(pixels, width, height, channels, bitsPerSample, opts) with the reference's full signature: channels 3 /
  * 8 bits is the call above; channels 1 with 8 or 16 bits per sample (16-bit samples little-endian, bytesToUint16Slice,
  * wsicompress.go:573-587) is the greyscale path -- Downsample2xGrey (wsipyramid.go:34-55), one plane per tile and the tile blob is
- * that plane's blob (compressGreyTileBlob, :366-370), no colour-transform flag.  Other combinations: MIC_ERR_UNSUPPORTED. */
+ * that plane's blob (compressGreyTileBlob, :366-370), no colour-transform flag.  Other combinations: MIC_ERR_UNSUPPORTED.
+ * Several devices (mic_hip_set_devices; not in a nested call) -- the tile worker pool of wsicompress.go:126-145 over GPUs: the slide
+ * is cut into one band of tile rows per device (mic_hip_wsi_band_plan).  Every band but the last is a multiple of tile_h << K rows,
+ * so it holds whole tiles of levels 0..K and the 2x2 box filter never crosses its edge: each device uploads only its rows and codes
+ * levels 0..K of its band as a slide of its own.  The bands' rows of level K + 1 (of level K for an odd tile_h) are staged through
+ * pinned host memory to devices[0], which codes levels K + 1 .. L - 1.  All tile lengths are gathered first; out_cap is checked
+ * before any byte of `out` is written; each device's tiles are then copied to their final offsets.  The file is byte-identical
+ * to the one-device file.  One device, or fewer than two non-empty bands: the one-device path. */
 int mic_hip_wsi_compress_ex(const uint8_t *pixels, int width, int height, int channels, int bits_per_sample,
                             int tile_w, int tile_h, int levels, uint8_t *out, size_t out_cap, size_t *out_len);
 /* WSIHeader.Channels / BitsPerSample / ColorTransform (wsiformat.go:169-227).  The decompress calls below write

@@ -97,7 +97,7 @@ class Unit(C.Structure):
 
 # every symbol include/mic_hip.h declares (tests/test_abi.py checks the .so exports them all)
 ABI_SYMBOLS = [
-    "mic_hip_set_device", "mic_hip_set_devices", "mic_hip_get_devices", "mic_hip_shard_plan", "mic_hip_device_name", "mic_hip_version",
+    "mic_hip_set_device", "mic_hip_set_devices", "mic_hip_get_devices", "mic_hip_shard_plan", "mic_hip_wsi_band_plan", "mic_hip_device_name", "mic_hip_version",
     "mic_hip_compress_frame", "mic_hip_decompress_frame",
     "mic_hip_fse_compress_u16", "mic_hip_fse_decompress_u16_auto", "mic_hip_fse_compress_u16_ex", "mic_hip_fse_decompress_u16_ex",
     "mic_hip_compress_batch", "mic_hip_decompress_batch", "mic_hip_host_alloc", "mic_hip_host_free",
@@ -220,6 +220,7 @@ def lib() -> C.CDLL:
     L.mic_hip_set_devices.argtypes = [C.POINTER(C.c_int), C.c_int]
     L.mic_hip_get_devices.argtypes = [C.POINTER(C.c_int), C.c_int]
     L.mic_hip_shard_plan.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.mic_hip_wsi_band_plan.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mic_hip_pics_compress_batch.argtypes = [C.POINTER(PicsEncJob), C.c_int]
     L.mic_hip_pics_decompress_batch.argtypes = [C.POINTER(PicsDecJob), C.c_int]
     L.mic_hip_host_alloc.argtypes = [C.c_size_t]
@@ -490,6 +491,16 @@ def shard_plan(weights: Sequence[int], shards: int) -> List[int]:
     if rc:
         _raise(rc, "shard_plan")
     return list(first)
+
+
+def wsi_band_plan(width: int, height: int, tile_w: int = 0, tile_h: int = 0, levels: int = 0, shards: int = 1) -> Tuple[int, List[int]]:
+    """mic_hip_wsi_band_plan: (K, row_first[0..shards]) -- the bands of tile rows compress_wsi codes one per device of set_devices."""
+    k = C.c_int(0)
+    first = (C.c_int * (max(shards, 0) + 1))()
+    rc = lib().mic_hip_wsi_band_plan(width, height, tile_w, tile_h, levels, shards, C.byref(k), first)
+    if rc:
+        _raise(rc, "wsi_band_plan")
+    return k.value, list(first)
 
 
 def pics_bound(width: int, height: int, num_strips: int) -> int:

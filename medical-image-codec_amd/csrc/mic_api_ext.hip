@@ -377,9 +377,220 @@ int compress_level_tiles(mic_hip_session *s, const void *d_img, const Level &L, 
     return rc;
 }
 
+// one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
+void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
+    if (fmt.planes() == 3)
+        hipLaunchKernelGGL(k_wsi_downsample, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
+    else if (fmt.bps == 16)
+        hipLaunchKernelGGL(k_wsi_downsample_grey<uint16_t>, dim3(1024), dim3(256), 0, st, (const uint16_t *)src, sw, (uint16_t *)dst, dw, dh);
+    else
+        hipLaunchKernelGGL(k_wsi_downsample_grey<uint8_t>, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
+}
+
+// WriteMIC3 (wsiformat.go:99-165) without the blobs: header, level table, tile index for blobs of the given lengths back to back
+void put_mic3_index(uint8_t *out, int width, int height, int tile_w, int tile_h, const Mic3 &fmt, const std::vector<Level> &lv,
+                    size_t total_tiles, const size_t *lens) {
+    const int nlev = (int)lv.size();
+    memset(out, 0, 48 + 20 * (size_t)nlev);
+    memcpy(out, "MIC3", 4); put_u32(out + 4, 1); put_u32(out + 8, (uint32_t)width); put_u32(out + 12, (uint32_t)height);
+    put_u32(out + 16, (uint32_t)tile_w); put_u32(out + 20, (uint32_t)tile_h);
+    out[24] = (uint8_t)fmt.channels; out[25] = 0; out[26] = (uint8_t)fmt.bps; out[27] = (uint8_t)fmt.flags;
+    out[28] = (uint8_t)nlev; out[29] = (uint8_t)(nlev >> 8);
+    put_u64(out + 32, (uint64_t)total_tiles);
+    for (int i = 0; i < nlev; i++) {
+        uint8_t *ld = out + 48 + 20 * (size_t)i;
+        put_u32(ld, (uint32_t)lv[(size_t)i].w); put_u32(ld + 4, (uint32_t)lv[(size_t)i].h); put_u32(ld + 8, (uint32_t)lv[(size_t)i].tx);
+        put_u32(ld + 12, (uint32_t)lv[(size_t)i].ty); put_u32(ld + 16, (uint32_t)lv[(size_t)i].first);
+    }
+    size_t off = 0;
+    for (size_t t = 0; t < total_tiles; t++) {
+        uint8_t *e = out + 48 + 20 * (size_t)nlev + 16 * t;
+        put_u64(e, (uint64_t)off); put_u64(e + 8, (uint64_t)lens[t]);
+        off += lens[t];
+    }
+}
+
+// ---- MIC3 over the devices of mic_hip_set_devices: the slide in bands of tile rows (parallel.wsi_band_plan) ----------------------
+// A level-k tile covers 2^k tile rows of level 0, so a band of a multiple of tile_h << K rows holds whole tiles of levels 0..K and
+// the 2x2 box filter never reaches across its edge: each band is coded as a slide of its own up to level K.  K is the largest level
+// whose blocks of tile_h << K rows still give every shard one; shard b takes blocks [nb * b / shards, nb * (b + 1) / shards)
+// (shard_range), clipped to the slide.  Returns K; row_first[0 .. shards] are the bands' first rows.
+int band_plan(int height, int tile_h, int nlev, int shards, int *row_first) {
+    auto blocks = [&](int k) { const int64_t a = (int64_t)tile_h << k; return ((int64_t)height + a - 1) / a; };
+    int k = nlev - 1;
+    while (k > 0 && blocks(k) < shards) k--;
+    const int64_t a = (int64_t)tile_h << k, nb = blocks(k);
+    for (int b = 0; b <= shards; b++) row_first[b] = (int)std::min<int64_t>(height, nb * b / shards * a);
+    return k;
+}
+
+struct PinnedHost {                                  // staging for the rows that go from the bands to devices[0]
+    void *p = nullptr;
+    ~PinnedHost() { if (p) (void)hipHostFree(p); }
+};
+
+// mic_hip_wsi_compress_ex with shard b coding rows [row_first[b], row_first[b + 1]) on devs[b]: levels 0..K of its band, each
+// tile with the single-device tile path; devs[0] codes levels K + 1 .. L - 1 from the bands' rows of level K + 1 (of level K when
+// tile_h is odd: a band of an odd number of level-K rows does not end on a row pair).  Within a level the tiles of band b are one
+// contiguous run of the tile table, so the lengths scan into the file's offsets and each shard writes its own run of `out`.
+int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt, int tile_w, int tile_h, const std::vector<Level> &lv,
+                       int K, const std::vector<int> &row_first, const std::vector<int> &devs, uint8_t *out, size_t out_cap, size_t *out_len) {
+    const int nlev = (int)lv.size(), shards = (int)devs.size();
+    const size_t bpp = fmt.bpp();
+    size_t total_tiles = 0;
+    for (const Level &l : lv) total_tiles += (size_t)l.tx * l.ty;
+    const size_t hdr = 48 + 20 * (size_t)nlev + 16 * total_tiles;
+    if (out_cap < hdr) return MIC_ERR_CAPACITY;
+    int rc = ensure_device();
+    if (rc) return rc;
+    // the level devs[0] starts the top of the pyramid from: -1 none, 0 the caller's slide itself, else rows gathered from the bands
+    const int top = nlev > K + 1 ? ((tile_h & 1) ? K : K + 1) : -1;
+    PinnedHost stage;
+    if (top > 0 && hipHostMalloc(&stage.p, (size_t)lv[(size_t)top].w * lv[(size_t)top].h * bpp + 64, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); return MIC_ERR_NOMEM;
+    }
+    struct Band { std::vector<std::vector<uint8_t>> blobs; std::vector<size_t> first, count; };   // per level k <= K: global first tile, tiles
+    std::vector<Band> B((size_t)shards);
+    rc = run_parallel(shards, [&](int b) -> int {
+        const int y0 = row_first[(size_t)b], rows = row_first[(size_t)b + 1] - y0;
+        if (rows <= 0) return MIC_OK;
+        Band &band = B[(size_t)b];
+        std::vector<Level> bl;                                                  // the band's levels 0..K, tile indices local to the band
+        size_t nt = 0;
+        for (int k = 0; k <= K; k++) {
+            const int h = rows >> k;
+            bl.push_back(Level{ lv[(size_t)k].w, h, lv[(size_t)k].tx, (h + tile_h - 1) / tile_h, (int)nt });
+            band.first.push_back((size_t)lv[(size_t)k].first + (size_t)((y0 >> k) / tile_h) * lv[(size_t)k].tx);
+            band.count.push_back((size_t)bl.back().tx * bl.back().ty);
+            nt += band.count.back();
+        }
+        band.blobs.resize(nt);
+        DefaultLease lease;
+        int r = lease.acquire(devs[(size_t)b]);
+        if (r) return r;
+        mic_hip_session *s = lease.s;
+        if ((r = s->ensure(1, (size_t)tile_w * tile_h))) return r;
+        struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;   // freed on every return path
+        std::vector<DevBuf> &img = bufs.img;
+        img.resize((size_t)K + 2);
+        if ((r = img[0].reserve((size_t)width * rows * bpp + 64))) return r;
+        HIP_TRY(hipMemcpyAsync(img[0].p, px + (size_t)y0 * width * bpp, (size_t)width * rows * bpp, hipMemcpyHostToDevice, s->stream));
+        for (int k = 1; k <= K; k++) {
+            if ((r = img[(size_t)k].reserve((size_t)bl[(size_t)k].w * bl[(size_t)k].h * bpp + 64))) return r;
+            launch_downsample(s->stream, fmt, img[(size_t)k - 1].p, bl[(size_t)k - 1].w, img[(size_t)k].p, bl[(size_t)k].w, bl[(size_t)k].h);
+        }
+        HIP_TRY(hipGetLastError());
+        if (top > 0) {                                                          // this band's rows of level `top`, to their place in the stage
+            const int th = rows >> top, tw = lv[(size_t)top].w;
+            if (top == K + 1) {
+                if ((r = img[(size_t)K + 1].reserve((size_t)tw * th * bpp + 64))) return r;
+                launch_downsample(s->stream, fmt, img[(size_t)K].p, bl[(size_t)K].w, img[(size_t)K + 1].p, tw, th);
+                HIP_TRY(hipGetLastError());
+            }
+            if (th > 0)
+                HIP_TRY(hipMemcpyAsync((uint8_t *)stage.p + (size_t)(y0 >> top) * tw * bpp, img[(size_t)top].p, (size_t)tw * th * bpp,
+                                       hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+        }
+        for (int k = 0; k <= K && r == MIC_OK; k++)
+            r = compress_level_tiles(s, img[(size_t)k].p, bl[(size_t)k], tile_w, tile_h, fmt, band.blobs.data() + bl[(size_t)k].first);
+        return r;
+    });
+    if (rc) return rc;
+    // the top of the pyramid on devs[0]
+    std::vector<std::vector<uint8_t>> top_blobs;
+    const size_t top_first = top >= 0 ? (size_t)lv[(size_t)K + 1].first : total_tiles;
+    if (top >= 0) {
+        top_blobs.resize(total_tiles - top_first);
+        DefaultLease lease;
+        if ((rc = lease.acquire(devs[0]))) return rc;
+        mic_hip_session *s = lease.s;
+        if ((rc = s->ensure(1, (size_t)tile_w * tile_h))) return rc;
+        struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;
+        std::vector<DevBuf> &img = bufs.img;
+        img.resize((size_t)nlev);
+        const Level &T = lv[(size_t)top];
+        if ((rc = img[(size_t)top].reserve((size_t)T.w * T.h * bpp + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(img[(size_t)top].p, top ? (const uint8_t *)stage.p : px, (size_t)T.w * T.h * bpp, hipMemcpyHostToDevice, s->stream));
+        for (int i = top + 1; i < nlev; i++) {
+            if ((rc = img[(size_t)i].reserve((size_t)lv[(size_t)i].w * lv[(size_t)i].h * bpp + 64))) return rc;
+            launch_downsample(s->stream, fmt, img[(size_t)i - 1].p, lv[(size_t)i - 1].w, img[(size_t)i].p, lv[(size_t)i].w, lv[(size_t)i].h);
+        }
+        HIP_TRY(hipGetLastError());
+        for (int i = K + 1; i < nlev && rc == MIC_OK; i++)
+            rc = compress_level_tiles(s, img[(size_t)i].p, lv[(size_t)i], tile_w, tile_h, fmt, top_blobs.data() + (lv[(size_t)i].first - top_first));
+        if (rc) return rc;
+    }
+    // the container: every tile's length, the capacity check, the offsets; then each shard copies its runs to their place
+    std::vector<size_t> lens(total_tiles, 0);
+    for (const Band &band : B)
+        for (size_t k = 0, j = 0; k < band.first.size(); j += band.count[k], k++)
+            for (size_t t = 0; t < band.count[k]; t++) lens[band.first[k] + t] = band.blobs[j + t].size();
+    for (size_t t = 0; t < top_blobs.size(); t++) lens[top_first + t] = top_blobs[t].size();
+    std::vector<size_t> off(total_tiles + 1, 0);
+    for (size_t t = 0; t < total_tiles; t++) off[t + 1] = off[t] + lens[t];
+    if (out_cap < hdr + off[total_tiles]) return MIC_ERR_CAPACITY;
+    put_mic3_index(out, width, height, tile_w, tile_h, fmt, lv, total_tiles, lens.data());
+    uint8_t *body = out + hdr;
+    rc = run_parallel(shards, [&](int b) -> int {
+        const Band &band = B[(size_t)b];
+        for (size_t k = 0, j = 0; k < band.first.size(); j += band.count[k], k++)
+            for (size_t t = 0; t < band.count[k]; t++) memcpy(body + off[band.first[k] + t], band.blobs[j + t].data(), band.blobs[j + t].size());
+        if (b == 0)
+            for (size_t t = 0; t < top_blobs.size(); t++) memcpy(body + off[top_first + t], top_blobs[t].data(), top_blobs[t].size());
+        return MIC_OK;
+    });
+    if (rc) return rc;
+    *out_len = hdr + off[total_tiles];
+    return MIC_OK;
+}
+
+// Tiles [tx0, tx1] x [ty0, ty1] of level L into dst, an image of bw x bh pixels whose corner is the level's (bx, by = ty0 * th).
+// One device, or -- when the box spans two tile rows or more, several devices are listed and the call is not nested -- one
+// contiguous range of tile rows per device (shard_plan, weighted by pixels), each decoded into its own rows of dst.
+int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
+               uint8_t *dst) {
+    const int by = ty0 * m.th;
+    auto rows = [&](int r0, int r1, int device) -> int {                        // tile rows r0 .. r1 - 1
+        const int ys = r0 * m.th, hs = std::min(r1 * m.th, by + bh) - ys;
+        std::vector<size_t> tiles; std::vector<int4> place;
+        for (int ty = r0; ty < r1; ty++) for (int tx = tx0; tx <= tx1; tx++) {
+            const int aw = std::min(m.tw, L.w - tx * m.tw), ah = std::min(m.th, L.h - ty * m.th);
+            if (aw <= 0 || ah <= 0) continue;
+            tiles.push_back((size_t)L.first + (size_t)ty * L.tx + tx);
+            place.push_back(make_int4(tx * m.tw - bx, ty * m.th - ys, aw, ah));
+        }
+        DefaultLease lease;
+        const int rc = lease.acquire(device);
+        if (rc) return rc;
+        return decode_tiles(c, len, m, tiles, place, dst + (size_t)(ys - by) * bw * m.bpp(), bw, hs);
+    };
+    const int nrows = ty1 - ty0 + 1;
+    const std::vector<int> devs = default_devices();
+    const int shards = cur_default() ? 1 : (int)std::min<size_t>(devs.size(), (size_t)nrows);
+    if (shards <= 1) return rows(ty0, ty1 + 1, -1);
+    std::vector<uint64_t> w((size_t)nrows);
+    for (int r = 0; r < nrows; r++) w[(size_t)r] = (uint64_t)bw * (uint64_t)std::min(m.th, by + bh - (ty0 + r) * m.th);
+    std::vector<int> first((size_t)shards + 1);
+    plan_shards(w.data(), nrows, shards, first.data());
+    return run_parallel(shards, [&](int k) {
+        const int r0 = ty0 + first[(size_t)k], r1 = ty0 + first[(size_t)k + 1];
+        return r0 < r1 ? rows(r0, r1, devs[(size_t)k]) : MIC_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+// parallel.wsi_band_plan behind the band path of mic_hip_wsi_compress_ex (band_plan); no device needed
+int mic_hip_wsi_band_plan(int width, int height, int tile_w, int tile_h, int levels, int shards, int *k_out, int *row_first) try {
+    if (!k_out || !row_first || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0 || levels > 32 || shards <= 0) return MIC_ERR_ARGS;
+    if (tile_w == 0) tile_w = 256;
+    if (tile_h == 0) tile_h = 256;
+    *k_out = band_plan(height, tile_h, (int)plan_levels(width, height, tile_w, tile_h, levels).size(), shards, row_first);
+    return MIC_OK;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // CompressWSI (wsicompress.go:27-171): 8-bit RGB (channels 3) or 8/16-bit greyscale (channels 1, little-endian samples)
 int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int channels, int bits_per_sample, int tile_w, int tile_h,
@@ -387,10 +598,21 @@ int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int chann
     if (!rgb || !out || !out_len || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0) return MIC_ERR_ARGS;
     Mic3 fmt; fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);   // defaults(), wsiformat.go:86-96
     if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
-    const size_t P = (size_t)fmt.planes(), bpp = fmt.bpp();
+    const size_t bpp = fmt.bpp();
     if (tile_w == 0) tile_w = 256;                                                          // WSIOptions.defaults, wsiformat.go:86-96
     if (tile_h == 0) tile_h = 256;
     if ((size_t)tile_w * tile_h > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
+    if (!cur_default()) {                                                                   // several devices: bands of tile rows
+        const std::vector<int> devs = default_devices();
+        if (devs.size() > 1) {
+            const std::vector<Level> lv = plan_levels(width, height, tile_w, tile_h, levels);
+            std::vector<int> row_first(devs.size() + 1);
+            const int K = band_plan(height, tile_h, (int)lv.size(), (int)devs.size(), row_first.data());
+            int bands = 0;
+            for (size_t b = 0; b < devs.size(); b++) bands += row_first[b + 1] > row_first[b];
+            if (bands >= 2) return wsi_compress_bands(rgb, width, height, fmt, tile_w, tile_h, lv, K, row_first, devs, out, out_cap, out_len);
+        }
+    }
     DefaultLease lease;
     int rc = lease.acquire();
     if (rc) return rc;
@@ -409,15 +631,7 @@ int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int chann
     if (hipMemcpyAsync(img[0].p, rgb, (size_t)width * height * bpp, hipMemcpyHostToDevice, s->stream) != hipSuccess) { cleanup(); return MIC_ERR_DEVICE; }
     for (int i = 1; i < nlev; i++) {
         if ((rc = img[(size_t)i].reserve((size_t)lv[i].w * lv[i].h * bpp + 64))) { cleanup(); return rc; }
-        if (P == 3)
-            hipLaunchKernelGGL(k_wsi_downsample, dim3(1024), dim3(256), 0, s->stream, (const uint8_t *)img[(size_t)i - 1].p, lv[i - 1].w,
-                               (uint8_t *)img[(size_t)i].p, lv[i].w, lv[i].h);
-        else if (bits_per_sample == 16)
-            hipLaunchKernelGGL(k_wsi_downsample_grey<uint16_t>, dim3(1024), dim3(256), 0, s->stream, (const uint16_t *)img[(size_t)i - 1].p,
-                               lv[i - 1].w, (uint16_t *)img[(size_t)i].p, lv[i].w, lv[i].h);
-        else
-            hipLaunchKernelGGL(k_wsi_downsample_grey<uint8_t>, dim3(1024), dim3(256), 0, s->stream, (const uint8_t *)img[(size_t)i - 1].p,
-                               lv[i - 1].w, (uint8_t *)img[(size_t)i].p, lv[i].w, lv[i].h);
+        launch_downsample(s->stream, fmt, img[(size_t)i - 1].p, lv[i - 1].w, img[(size_t)i].p, lv[i].w, lv[i].h);
     }
     std::vector<std::vector<uint8_t>> tile_blobs(total_tiles);
     for (int li = 0; li < nlev && rc == MIC_OK; li++)
@@ -427,21 +641,11 @@ int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int chann
     size_t total = 0;
     for (const auto &tb : tile_blobs) total += tb.size();
     if (out_cap < hdr + total) return MIC_ERR_CAPACITY;
-    memset(out, 0, hdr);                                                                    // WriteMIC3, wsiformat.go:99-165
-    memcpy(out, "MIC3", 4); put_u32(out + 4, 1); put_u32(out + 8, (uint32_t)width); put_u32(out + 12, (uint32_t)height);
-    put_u32(out + 16, (uint32_t)tile_w); put_u32(out + 20, (uint32_t)tile_h);
-    out[24] = (uint8_t)channels; out[25] = 0; out[26] = (uint8_t)bits_per_sample; out[27] = (uint8_t)fmt.flags;
-    out[28] = (uint8_t)nlev; out[29] = (uint8_t)(nlev >> 8);
-    put_u64(out + 32, (uint64_t)total_tiles);
-    for (int i = 0; i < nlev; i++) {
-        uint8_t *ld = out + 48 + 20 * (size_t)i;
-        put_u32(ld, (uint32_t)lv[(size_t)i].w); put_u32(ld + 4, (uint32_t)lv[(size_t)i].h); put_u32(ld + 8, (uint32_t)lv[(size_t)i].tx);
-        put_u32(ld + 12, (uint32_t)lv[(size_t)i].ty); put_u32(ld + 16, (uint32_t)lv[(size_t)i].first);
-    }
+    std::vector<size_t> lens(total_tiles);
+    for (size_t t = 0; t < total_tiles; t++) lens[t] = tile_blobs[t].size();
+    put_mic3_index(out, width, height, tile_w, tile_h, fmt, lv, total_tiles, lens.data());    // WriteMIC3, wsiformat.go:99-165
     size_t off = 0;
     for (size_t t = 0; t < total_tiles; t++) {
-        uint8_t *e = out + 48 + 20 * (size_t)nlev + 16 * t;
-        put_u64(e, (uint64_t)off); put_u64(e + 8, (uint64_t)tile_blobs[t].size());
         memcpy(out + hdr + off, tile_blobs[t].data(), tile_blobs[t].size());
         off += tile_blobs[t].size();
     }
@@ -604,16 +808,7 @@ int mic_hip_wsi_decompress_level(const uint8_t *c, size_t len, int level, uint8_
     if (!m.supported()) return MIC_ERR_UNSUPPORTED;
     if (L.w <= 0 || L.h <= 0 || (size_t)L.w * L.h * m.bpp() > out_cap) return (L.w <= 0 || L.h <= 0) ? MIC_ERR_CORRUPT : MIC_ERR_CAPACITY;
     if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
-    std::vector<size_t> tiles; std::vector<int4> place;
-    for (int ty = 0; ty < L.ty; ty++) for (int tx = 0; tx < L.tx; tx++) {
-        const int aw = std::min(m.tw, L.w - tx * m.tw), ah = std::min(m.th, L.h - ty * m.th);
-        if (aw <= 0 || ah <= 0) continue;
-        tiles.push_back((size_t)L.first + (size_t)ty * L.tx + tx);
-        place.push_back(make_int4(tx * m.tw, ty * m.th, aw, ah));
-    }
-    DefaultLease lease;
-    if ((rc = lease.acquire())) return rc;
-    return decode_tiles(c, len, m, tiles, place, rgb_out, L.w, L.h);
+    return decode_box(c, len, m, L, 0, L.tx - 1, 0, L.ty - 1, 0, L.w, L.h, rgb_out);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // DecompressWSIRegion (wsicompress.go:219-297): the tiles that overlap the rectangle are decoded in one batch into
@@ -636,19 +831,8 @@ int mic_hip_wsi_decompress_region(const uint8_t *c, size_t len, int level, int x
     const int tx0 = x / m.tw, ty0 = y / m.th, tx1 = (x + w - 1) / m.tw, ty1 = (y + h - 1) / m.th;
     const int bx = tx0 * m.tw, by = ty0 * m.th;
     const int bw = std::min((tx1 + 1) * m.tw, L.w) - bx, bh = std::min((ty1 + 1) * m.th, L.h) - by;
-    std::vector<size_t> tiles; std::vector<int4> place;
-    for (int ty = ty0; ty <= ty1; ty++) for (int tx = tx0; tx <= tx1; tx++) {
-        const int aw = std::min(m.tw, L.w - tx * m.tw), ah = std::min(m.th, L.h - ty * m.th);
-        if (aw <= 0 || ah <= 0) continue;
-        tiles.push_back((size_t)L.first + (size_t)ty * L.tx + tx);
-        place.push_back(make_int4(tx * m.tw - bx, ty * m.th - by, aw, ah));
-    }
     std::vector<uint8_t> box((size_t)bw * bh * bpp);
-    {
-        DefaultLease lease;
-        if ((rc = lease.acquire())) return rc;
-        if ((rc = decode_tiles(c, len, m, tiles, place, box.data(), bw, bh))) return rc;
-    }
+    if ((rc = decode_box(c, len, m, L, tx0, tx1, ty0, ty1, bx, bw, bh, box.data()))) return rc;
     for (int r = 0; r < h; r++)
         memcpy(rgb_out + (size_t)r * w * bpp, box.data() + ((size_t)(y - by + r) * bw + (size_t)(x - bx)) * bpp, (size_t)w * bpp);
     if (out_w) *out_w = w;

@@ -448,25 +448,14 @@ int run_shards(std::vector<Grp> &G, std::vector<Unt> &U, Run run_one) {
         for (Grp &g : S[(size_t)k].G) g.first -= u0;
         for (Unt &u : S[(size_t)k].U) u.group -= g0;
     }
-    auto work = [&](int k) {
-        if (S[(size_t)k].G.empty()) return;
+    int rc = run_parallel(shards, [&](int k) {
+        if (S[(size_t)k].G.empty()) return MIC_OK;
         DefaultLease lease;
-        int rc = lease.acquire(devs[(size_t)k]);
-        if (rc == MIC_OK) rc = run_one(lease.s, S[(size_t)k].G, S[(size_t)k].U);
-        S[(size_t)k].rc = rc;
-    };
-    std::vector<std::thread> th;
-    int started = 1;                                  // shards 1 .. started - 1 have a thread; what could not get one runs here, one after the other
-    try {
-        th.reserve((size_t)shards);
-        for (; started < shards; started++) th.emplace_back(work, started);
-    } catch (...) { }                                 // (no exception crosses the C ABI: a thread the system refuses costs overlap, not the call)
-    work(0);
-    for (int k = started; k < shards; k++) work(k);
-    for (auto &t : th) t.join();
-    int rc = MIC_OK;
+        int r = lease.acquire(devs[(size_t)k]);
+        if (r == MIC_OK) r = run_one(lease.s, S[(size_t)k].G, S[(size_t)k].U);
+        return S[(size_t)k].rc = r;
+    });
     for (int k = 0; k < shards; k++) {
-        if (S[(size_t)k].rc != MIC_OK && rc == MIC_OK) rc = S[(size_t)k].rc;
         const int g0 = first[(size_t)k];
         if (S[(size_t)k].G.empty()) continue;
         const int u0 = G[(size_t)g0].first;
@@ -497,6 +486,25 @@ int host_copy(int device, void *dev, void *host, size_t bytes, bool to_device) {
     const int rc = io_submit(req, device, dev, host, bytes, to_device);
     const int r2 = req.wait();
     return rc ? rc : r2;
+}
+void plan_shards(const uint64_t *w, int n, int shards, int *first) { shard_plan(w, n, shards, first); }
+int run_parallel(int n, const std::function<int(int)> &work) {
+    std::vector<int> rcs((size_t)std::max(n, 0), MIC_OK);
+    auto one = [&](int k) {
+        try { rcs[(size_t)k] = work(k); }
+        catch (const std::bad_alloc &) { rcs[(size_t)k] = MIC_ERR_NOMEM; } catch (...) { rcs[(size_t)k] = MIC_ERR_INTERNAL; }
+    };
+    std::vector<std::thread> th;
+    int started = 1;                                  // 1 .. started - 1 have a thread; what could not get one runs here, one after the other
+    try {
+        th.reserve((size_t)std::max(n, 1));
+        for (; started < n; started++) th.emplace_back(one, started);
+    } catch (...) { }                                 // (no exception crosses the C ABI: a thread the system refuses costs overlap, not the call)
+    if (n > 0) one(0);
+    for (int k = started; k < n; k++) one(k);
+    for (auto &t : th) t.join();
+    for (int r : rcs) if (r != MIC_OK) return r;
+    return MIC_OK;
 }
 }  // namespace micapi
 

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -315,5 +316,10 @@ size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // one blocking host <-> device copy through the transfer engine of mic_host_io.hip (pinned host memory: DMA in place; ordinary
 // memory: staged through pinned slots by the worker threads).  The device side must be ready / is complete on return.
 int host_copy(int device, void *dev, void *host, size_t bytes, bool to_device);
+// the cut of n weighted items into `shards` contiguous shards (mic_hip_shard_plan; first has shards + 1 entries)
+void plan_shards(const uint64_t *w, int n, int shards, int *first);
+// work(0 .. n - 1) side by side, each on a thread of its own (work(0) on the calling thread); returns the code of the first
+// (lowest) k that failed.  An exception inside work(k) is that k's MIC_ERR_NOMEM / MIC_ERR_INTERNAL.
+int run_parallel(int n, const std::function<int(int)> &work);
 #define kWorkspaceBudget (micapi::workspace_budget())
 }  // namespace micapi

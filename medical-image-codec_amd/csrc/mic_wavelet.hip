@@ -895,6 +895,20 @@ void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int app
 
 size_t wv_frames_per_batch(size_t n) { return std::max<size_t>(1, kWorkspaceBudget / (unit_ws_bytes(2 * n + 16) + 8 * n)); }
 
+// range(f0, f1, device) over frames [0, nframes) of rows x cols pixels: one call on the default device, or -- several devices listed,
+// the call not nested -- one contiguous shard per device (shard_plan), side by side; the first failing shard's code
+int wv_sharded(int nframes, size_t n, const std::function<int(size_t, size_t, int)> &range) {
+    const std::vector<int> devs = default_devices();
+    const int shards = cur_default() ? 1 : (int)std::min<size_t>(devs.size(), (size_t)nframes);
+    if (shards <= 1) return range(0, (size_t)nframes, -1);
+    std::vector<uint64_t> w((size_t)nframes, (uint64_t)n);
+    std::vector<int> first((size_t)shards + 1);
+    plan_shards(w.data(), nframes, shards, first.data());
+    return run_parallel(shards, [&](int k) {
+        return first[(size_t)k] < first[(size_t)k + 1] ? range((size_t)first[(size_t)k], (size_t)first[(size_t)k + 1], devs[(size_t)k]) : MIC_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -913,29 +927,31 @@ int mic_hip_wavelet_v2_compress_batch(const uint16_t *frames, int nframes, int r
     if (levels > 8) levels = 8;
     int applied = 0;
     { int r = rows, c = cols; for (; applied < levels; applied++) { if (r < 2 || c < 2) break; r = (r + 1) / 2; c = (c + 1) / 2; } }   // :321-330
-    DefaultLease lease;
-    int rc = lease.acquire();
-    if (rc) return rc;
-    mic_hip_session *s = cur_default();
-    const size_t per = wv_frames_per_batch(n);
-    for (size_t f0 = 0; f0 < (size_t)nframes; f0 += per) {
-        const int nf = (int)std::min(per, (size_t)nframes - f0);
-        if ((rc = s->ensure(nf, 2 * n + 16))) return rc;
-        if ((rc = s->io_px.reserve(n * 2 * (size_t)nf + 64))) return rc;
-        HIP_TRY(hipMemcpyAsync(s->io_px.p, frames + f0 * n, n * 2 * (size_t)nf, hipMemcpyHostToDevice, s->stream));
-        std::vector<std::vector<uint8_t>> blobs; std::vector<int32_t> st;
-        if ((rc = wv_compress_frames(s, (const uint16_t *)s->io_px.p, nf, rows, cols, applied, &blobs, st))) return rc;
-        for (int i = 0; i < nf; i++) {
-            uint8_t *o = out + (f0 + (size_t)i) * out_stride;
-            status[f0 + (size_t)i] = st[(size_t)i]; out_lens[f0 + (size_t)i] = 0;
-            if (st[(size_t)i] != MIC_OK) continue;
-            if (11 + blobs[(size_t)i].size() > out_stride) { status[f0 + (size_t)i] = MIC_ERR_CAPACITY; continue; }
-            wv_put_header(o, rows, cols, max_value, applied);
-            memcpy(o + 11, blobs[(size_t)i].data(), blobs[(size_t)i].size());
-            out_lens[f0 + (size_t)i] = 11 + blobs[(size_t)i].size();
+    return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session
+        DefaultLease lease;
+        int rc = lease.acquire(device);
+        if (rc) return rc;
+        mic_hip_session *s = cur_default();
+        const size_t per = wv_frames_per_batch(n);
+        for (size_t f0 = fa; f0 < fb; f0 += per) {
+            const int nf = (int)std::min(per, fb - f0);
+            if ((rc = s->ensure(nf, 2 * n + 16))) return rc;
+            if ((rc = s->io_px.reserve(n * 2 * (size_t)nf + 64))) return rc;
+            HIP_TRY(hipMemcpyAsync(s->io_px.p, frames + f0 * n, n * 2 * (size_t)nf, hipMemcpyHostToDevice, s->stream));
+            std::vector<std::vector<uint8_t>> blobs; std::vector<int32_t> st;
+            if ((rc = wv_compress_frames(s, (const uint16_t *)s->io_px.p, nf, rows, cols, applied, &blobs, st))) return rc;
+            for (int i = 0; i < nf; i++) {
+                uint8_t *o = out + (f0 + (size_t)i) * out_stride;
+                status[f0 + (size_t)i] = st[(size_t)i]; out_lens[f0 + (size_t)i] = 0;
+                if (st[(size_t)i] != MIC_OK) continue;
+                if (11 + blobs[(size_t)i].size() > out_stride) { status[f0 + (size_t)i] = MIC_ERR_CAPACITY; continue; }
+                wv_put_header(o, rows, cols, max_value, applied);
+                memcpy(o + 11, blobs[(size_t)i].data(), blobs[(size_t)i].size());
+                out_lens[f0 + (size_t)i] = 11 + blobs[(size_t)i].size();
+            }
         }
-    }
-    return MIC_OK;
+        return MIC_OK;
+    });
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // WaveletV2RLEFSECompressU16 / WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303, :374)
@@ -973,40 +989,43 @@ int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_
     const size_t n = (size_t)rows * (size_t)cols;
     if (n > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
     if (n * (size_t)nframes > out_cap_px) return MIC_ERR_CAPACITY;
-    DefaultLease lease;
-    if ((rc = lease.acquire())) return rc;
-    mic_hip_session *s = cur_default();
-    const size_t per = wv_frames_per_batch(n);
-    for (size_t f0 = 0; f0 < (size_t)nframes; f0 += per) {
-        const int nf = (int)std::min(per, (size_t)nframes - f0);
-        std::vector<int> slot((size_t)nf, -1); std::vector<uint64_t> offs(1, 0); int good = 0;   // streams packed back to back
-        for (int i = 0; i < nf; i++) {
-            const uint8_t *c = files[f0 + (size_t)i]; const size_t len = lens[f0 + (size_t)i];
-            int r2, c2, m2, l2;
-            status[f0 + (size_t)i] = MIC_OK;
-            if (!c) { status[f0 + (size_t)i] = MIC_ERR_ARGS; continue; }
-            if (mic_hip_wavelet_v2_info(c, len, &r2, &c2, &m2, &l2) != MIC_OK) { status[f0 + (size_t)i] = MIC_ERR_CORRUPT; continue; }
-            if (r2 != rows || c2 != cols || l2 != levels) { status[f0 + (size_t)i] = MIC_ERR_ARGS; continue; }
-            if (len < 13 || c[11] != 0xFF || c[12] != 0x04 || len - 11 > 0xFFFFFFF0ull) { status[f0 + (size_t)i] = MIC_ERR_CORRUPT; continue; }   // FSEDecompressU16FourState only, :503
-            slot[(size_t)i] = good++; offs.push_back(offs.back() + (len - 11));
+    return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session; shape: files[0]'s
+        DefaultLease lease;
+        int rc = lease.acquire(device);
+        if (rc) return rc;
+        mic_hip_session *s = cur_default();
+        const size_t per = wv_frames_per_batch(n);
+        for (size_t f0 = fa; f0 < fb; f0 += per) {
+            const int nf = (int)std::min(per, fb - f0);
+            std::vector<int> slot((size_t)nf, -1); std::vector<uint64_t> offs(1, 0); int good = 0;   // streams packed back to back
+            for (int i = 0; i < nf; i++) {
+                const uint8_t *c = files[f0 + (size_t)i]; const size_t len = lens[f0 + (size_t)i];
+                int r2, c2, m2, l2;
+                status[f0 + (size_t)i] = MIC_OK;
+                if (!c) { status[f0 + (size_t)i] = MIC_ERR_ARGS; continue; }
+                if (mic_hip_wavelet_v2_info(c, len, &r2, &c2, &m2, &l2) != MIC_OK) { status[f0 + (size_t)i] = MIC_ERR_CORRUPT; continue; }
+                if (r2 != rows || c2 != cols || l2 != levels) { status[f0 + (size_t)i] = MIC_ERR_ARGS; continue; }
+                if (len < 13 || c[11] != 0xFF || c[12] != 0x04 || len - 11 > 0xFFFFFFF0ull) { status[f0 + (size_t)i] = MIC_ERR_CORRUPT; continue; }   // FSEDecompressU16FourState only, :503
+                slot[(size_t)i] = good++; offs.push_back(offs.back() + (len - 11));
+            }
+            if (!good) continue;
+            if ((rc = s->ensure(good, 2 * n + 16))) return rc;
+            if ((rc = s->io_comp.reserve((size_t)offs.back() + 64)) || (rc = s->io_px.reserve(n * 2 * (size_t)good + 64))) return rc;
+            for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0)
+                HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + offs[(size_t)slot[(size_t)i]], files[f0 + (size_t)i] + 11, lens[f0 + (size_t)i] - 11,
+                                       hipMemcpyHostToDevice, s->stream));
+            std::vector<int32_t> st;
+            if ((rc = wv_decompress_frames(s, (const uint8_t *)s->io_comp.p, (uint16_t *)s->io_px.p, good, offs.data(), rows, cols, levels, st))) return rc;
+            for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0) {
+                const size_t k = (size_t)slot[(size_t)i];
+                status[f0 + (size_t)i] = st[k];
+                if (st[k] == MIC_OK)
+                    HIP_TRY(hipMemcpyAsync(pixels_out + (f0 + (size_t)i) * n, (uint16_t *)s->io_px.p + k * n, n * 2, hipMemcpyDeviceToHost, s->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(s->stream));
         }
-        if (!good) continue;
-        if ((rc = s->ensure(good, 2 * n + 16))) return rc;
-        if ((rc = s->io_comp.reserve((size_t)offs.back() + 64)) || (rc = s->io_px.reserve(n * 2 * (size_t)good + 64))) return rc;
-        for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0)
-            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + offs[(size_t)slot[(size_t)i]], files[f0 + (size_t)i] + 11, lens[f0 + (size_t)i] - 11,
-                                   hipMemcpyHostToDevice, s->stream));
-        std::vector<int32_t> st;
-        if ((rc = wv_decompress_frames(s, (const uint8_t *)s->io_comp.p, (uint16_t *)s->io_px.p, good, offs.data(), rows, cols, levels, st))) return rc;
-        for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0) {
-            const size_t k = (size_t)slot[(size_t)i];
-            status[f0 + (size_t)i] = st[k];
-            if (st[k] == MIC_OK)
-                HIP_TRY(hipMemcpyAsync(pixels_out + (f0 + (size_t)i) * n, (uint16_t *)s->io_px.p + k * n, n * 2, hipMemcpyDeviceToHost, s->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    return MIC_OK;
+        return MIC_OK;
+    });
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // WaveletV2RLEFSEDecompressU16 / WaveletV2SIMDRLEFSEDecompressU16 (:380-425, :493-534)
