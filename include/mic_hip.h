@@ -39,6 +39,7 @@ extern "C" {
 #define MIC_ERR_INTERNAL        -8
 #define MIC_ERR_UNSUPPORTED     -9
 #define MIC_ERR_INCOMPRESSIBLE -10   /* Go ErrIncompressible, fseu16.go:33; C: -4 / -10 */
+#define MIC_ERR_IO             -11   /* a read or write callback of the MIC3 streaming calls returned non-zero */
 
 /* FSE flavour requested from an encoder: the entry of the reference's fallback chain
  * (multiframecompress.go:15-93).  2 -> CompressSingleFrame (2-state, then 1-state),
@@ -341,6 +342,50 @@ int mic_hip_wsi_decompress_level(const uint8_t *compressed, size_t compressed_le
 int mic_hip_wsi_decompress_region(const uint8_t *compressed, size_t compressed_len, int level,
                                   int x, int y, int w, int h,
                                   uint8_t *rgb_out, size_t out_cap, int *out_w, int *out_h);
+
+/* ---- MIC3 streaming: a row-push writer and a random-access reader ------------------------------- */
+/* For slides too large for one host buffer (the reference's "WSI streaming API" roadmap item, io.ReaderAt / io.WriteSeeker).
+ * pwrite-like sink: write len bytes at an absolute offset, 0 = success.  The ranges of one file never overlap.
+ * pread-like source (io.ReaderAt): fill dst with exactly len bytes from offset, 0 = success.
+ * A callback that returns non-zero makes the call MIC_ERR_IO. */
+typedef int (*mic_hip_write_fn)(void *user, uint64_t offset, const uint8_t *data, size_t len);
+typedef int (*mic_hip_read_fn)(void *user, uint64_t offset, uint8_t *dst, size_t len);
+typedef struct mic_hip_wsi_writer mic_hip_wsi_writer;
+typedef struct mic_hip_wsi_reader mic_hip_wsi_reader;
+/* Writer.  Formats, defaults and MIC_ERR_UNSUPPORTED cases are mic_hip_wsi_compress_ex's, checked before a device is touched.
+ * The sink receives the file mic_hip_wsi_compress_ex writes for the same slide, byte for byte, whatever the push schedule and
+ * band_tile_rows.  The slide is coded in bands of band_tile_rows tile rows (0 = automatic: one band fills a sub-batch of the unit
+ * codec, capped at 256 MiB of level-0 pixels; never a function of height).  Each level keeps its current band plus one carried row
+ * on the device; one kernel per band makes every level's new rows.  Level-0 tile blobs go to the sink as soon as their band is
+ * coded (the file's blobs start with level 0); blobs of levels >= 1 are held in host memory and written at finish, then the header,
+ * level table and tile index at offset 0.  Host memory: the upper levels' blobs, 16 bytes per tile and one band of staging.
+ * Device memory (mic_hip_wsi_writer_device_bytes, at open) depends on width, tile size, band_tile_rows and format only.
+ * push_rows takes the next nrows >= 1 rows, top to bottom (width * bytes per pixel each, 16-bit samples little-endian); rows past
+ * height are MIC_ERR_ARGS and consume nothing.  finish before all rows are pushed is MIC_ERR_ARGS.  A sink or device error is
+ * sticky: later pushes and finish return it.  close always frees; an unfinished file is abandoned.
+ * The writer owns a session on the default device (devices[0] of mic_hip_set_devices: a stream is not spread over several GPUs)
+ * and holds no default-pool session between calls.  Calls on one handle are serialised; different handles may run in parallel.
+ * stats: bands coded, rows of level 0 per band, device time of the band pyramid kernel summed over them (ms), peak host bytes held. */
+int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sample, int tile_w, int tile_h, int levels,
+                            int band_tile_rows, mic_hip_write_fn write, void *user, mic_hip_wsi_writer **w);
+int mic_hip_wsi_writer_push_rows(mic_hip_wsi_writer *w, const uint8_t *rows, int nrows);
+int mic_hip_wsi_writer_finish(mic_hip_wsi_writer *w, uint64_t *file_len);
+int mic_hip_wsi_writer_device_bytes(const mic_hip_wsi_writer *w, uint64_t *bytes);
+int mic_hip_wsi_writer_stats(const mic_hip_wsi_writer *w, uint64_t *bands, int *band_rows, double *pyramid_ms, uint64_t *host_bytes_peak);
+void mic_hip_wsi_writer_close(mic_hip_wsi_writer *w);
+/* Reader.  open reads the header, level table and tile index (48 + 20 * levels + 16 * tiles bytes) through the callback and
+ * validates them as the flat-buffer calls do; open and info need no device.  Tile and region decodes read only the blobs of the
+ * tiles they cover (contiguous blobs of one tile row in one read) and return the pixels mic_hip_wsi_decompress_tile / _region
+ * return for the whole file.  A blob outside file_len is MIC_ERR_CORRUPT.  Calls on one handle are serialised, and so are its
+ * callbacks. */
+int mic_hip_wsi_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len, mic_hip_wsi_reader **r);
+int mic_hip_wsi_reader_info(const mic_hip_wsi_reader *r, int *width, int *height, int *tile_w, int *tile_h, int *levels,
+                            int *channels, int *bits_per_sample);
+int mic_hip_wsi_reader_decompress_tile(mic_hip_wsi_reader *r, int level, int tile_x, int tile_y,
+                                       uint8_t *out, size_t out_cap, int *out_w, int *out_h);
+int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x, int y, int w, int h,
+                                         uint8_t *out, size_t out_cap, int *out_w, int *out_h);
+void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r);
 
 /* ---- single-frame RGB and the CLI's single-frame files ------------------------------------------ */
 /* Replaces CompressRGB / DecompressRGB (rgbcompress.go:25-33): YCoCg-R, then the three planes as in a WSI tile blob

@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+import threading
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -31,6 +32,7 @@ MIC_ERR_INTERNAL = -8
 MIC_ERR_UNSUPPORTED = -9
 MIC_HIP_PRED_GRAD = 0x200          # OR'ed into a session unit's nstates: gradient-adaptive predictor (include/mic_hip.h)
 MIC_ERR_INCOMPRESSIBLE = -10
+MIC_ERR_IO = -11                   # a read / write callback of the MIC3 streaming calls failed
 MIC_HIP_GAP_REMOVAL = 0x800        # OR'ed into a session unit's nstates: a gap-removal stream (include/mic_hip.h)
 
 _ERR_NAMES = {
@@ -39,6 +41,7 @@ _ERR_NAMES = {
     MIC_ERR_CAPACITY: "output buffer too small", MIC_ERR_CORRUPT: "corrupt stream",
     MIC_ERR_DEVICE: "no usable gfx950 device / HIP error", MIC_ERR_INTERNAL: "internal error",
     MIC_ERR_UNSUPPORTED: "unsupported", MIC_ERR_INCOMPRESSIBLE: "input is not compressible",  # fseu16.go:33
+    MIC_ERR_IO: "read / write callback failed",
 }
 
 
@@ -112,6 +115,10 @@ ABI_SYMBOLS = [
     "mic_hip_mic1_compress", "mic_hip_mic1_info", "mic_hip_mic1_decompress",
     "mic_hip_wsi_compress", "mic_hip_wsi_compress_ex", "mic_hip_wsi_format", "mic_hip_wsi_info", "mic_hip_wsi_level_info",
     "mic_hip_wsi_decompress_tile", "mic_hip_wsi_decompress_level", "mic_hip_wsi_decompress_region",
+    "mic_hip_wsi_writer_open", "mic_hip_wsi_writer_push_rows", "mic_hip_wsi_writer_finish", "mic_hip_wsi_writer_device_bytes",
+    "mic_hip_wsi_writer_stats", "mic_hip_wsi_writer_close",
+    "mic_hip_wsi_reader_open", "mic_hip_wsi_reader_info", "mic_hip_wsi_reader_decompress_tile", "mic_hip_wsi_reader_decompress_region",
+    "mic_hip_wsi_reader_close",
     "mic_hip_session_create", "mic_hip_session_create_on", "mic_hip_session_device", "mic_hip_session_workspace_bytes", "mic_hip_session_destroy", "mic_hip_session_stream",
     "mic_hip_device_copy",
     "mic_hip_session_wavelet_v2_encode", "mic_hip_session_wavelet_v2_decode",
@@ -123,6 +130,9 @@ ABI_SYMBOLS = [
 ]
 
 _lib: Optional[C.CDLL] = None
+# mic_hip_write_fn / mic_hip_read_fn (include/mic_hip.h)
+_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint8), C.c_size_t)
+_READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint8), C.c_size_t)
 
 
 def _share_torch_hip_runtime():
@@ -198,6 +208,21 @@ def lib() -> C.CDLL:
     L.mic_hip_session_wsi_decode_level.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.mic_hip_session_wsi_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     L.mic_hip_session_destroy.argtypes = [C.c_void_p]
+    L.mic_hip_wsi_writer_open.argtypes = [C.c_int] * 8 + [_WRITE_FN, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mic_hip_wsi_writer_push_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.mic_hip_wsi_writer_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mic_hip_wsi_writer_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mic_hip_wsi_writer_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.mic_hip_wsi_writer_close.argtypes = [C.c_void_p]
+    L.mic_hip_wsi_writer_close.restype = None
+    L.mic_hip_wsi_reader_open.argtypes = [_READ_FN, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mic_hip_wsi_reader_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 7
+    L.mic_hip_wsi_reader_decompress_tile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mic_hip_wsi_reader_decompress_region.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mic_hip_wsi_reader_close.argtypes = [C.c_void_p]
+    L.mic_hip_wsi_reader_close.restype = None
     L.mic_hip_session_destroy.restype = None
     L.mic_hip_compress_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int,
                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -788,6 +813,169 @@ def decompress_wsi_level(compressed, level: int = 0) -> np.ndarray:
     if rc:
         _raise(rc, "decompress_wsi_level")
     return _wsi_shape(hdr, out, lv["width"], lv["height"])
+
+
+class _Callback:
+    """A ctypes callback that never lets an exception pass as success: the first exception it meets is kept, the callback
+    returns non-zero (the library then reports MIC_ERR_IO), and the caller re-raises it once the C call has returned.
+    fn returning None or 0 is success, any other value a failure (the C convention)."""
+
+    def __init__(self, fn, cfunctype):
+        self.exc = None
+        self._lock = threading.Lock()
+
+        def tramp(user, offset, ptr, n):
+            try:
+                return 0 if fn(int(offset), ptr, int(n)) in (None, 0) else 1
+            except BaseException as e:     # (ctypes would print it and return 0)
+                with self._lock:
+                    if self.exc is None:
+                        self.exc = e
+                return 1
+        self.c = cfunctype(tramp)
+
+    def check(self, rc: int, where: str):
+        if self.exc is not None:
+            e, self.exc = self.exc, None
+            raise e
+        if rc:
+            _raise(rc, where)
+
+
+class WsiWriter:
+    """MIC3 streaming writer (mic_hip_wsi_writer_*): rows go in with push(), top to bottom, in pieces of any size; the sink
+    receives the file compress_wsi writes for the same slide, byte for byte.  sink: a binary file object (seek + write) or a
+    callable (offset, memoryview).  Level-0 tiles reach the sink as their band is coded; the rest of the file at finish()."""
+
+    def __init__(self, sink, width: int, height: int, channels: int = 3, bits_per_sample: int = 8, tile_w: int = 0,
+                 tile_h: int = 0, levels: int = 0, band_tile_rows: int = 0):
+        if hasattr(sink, "seek") and hasattr(sink, "write"):
+            def put(offset, data):
+                sink.seek(offset)
+                sink.write(data)
+        else:
+            put = sink
+        self.width, self.height, self.bpp = width, height, channels * (2 if bits_per_sample == 16 else 1)
+        self._cb = _Callback(lambda off, ptr, n: put(off, memoryview((C.c_uint8 * n).from_address(C.addressof(ptr.contents))).cast("B")),
+                             _WRITE_FN)
+        self._h = C.c_void_p()
+        rc = lib().mic_hip_wsi_writer_open(width, height, channels, bits_per_sample, tile_w, tile_h, levels, band_tile_rows,
+                                           self._cb.c, None, C.byref(self._h))
+        self._cb.check(rc, "WsiWriter")
+
+    def push(self, rows) -> None:
+        """The next rows of the slide: (n, width, 3) / (n, width) arrays, or raw bytes of whole rows."""
+        arr = np.asarray(rows)
+        if arr.dtype == np.uint16:
+            arr = arr.astype("<u2", copy=False)
+        px = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+        if px.size == 0 or px.size % (self.width * self.bpp):
+            raise MicError(MIC_ERR_ARGS, "WsiWriter.push: whole rows")
+        self._cb.check(lib().mic_hip_wsi_writer_push_rows(self._h, px.ctypes.data, px.size // (self.width * self.bpp)), "WsiWriter.push")
+
+    def finish(self) -> int:
+        """Writes the upper levels, the header and the tile index; returns the file's length."""
+        n = C.c_uint64(0)
+        self._cb.check(lib().mic_hip_wsi_writer_finish(self._h, C.byref(n)), "WsiWriter.finish")
+        return n.value
+
+    @property
+    def device_bytes(self) -> int:
+        n = C.c_uint64(0)
+        self._cb.check(lib().mic_hip_wsi_writer_device_bytes(self._h, C.byref(n)), "WsiWriter.device_bytes")
+        return n.value
+
+    @property
+    def stats(self):
+        """dict(bands, band_rows, pyramid_ms, host_bytes_peak): bands coded, level-0 rows per band, device time of the band
+        pyramid kernel over them, peak host bytes the writer held."""
+        b, r, hp, ms = C.c_uint64(0), C.c_int(0), C.c_uint64(0), C.c_double(0)
+        self._cb.check(lib().mic_hip_wsi_writer_stats(self._h, C.byref(b), C.byref(r), C.byref(ms), C.byref(hp)), "WsiWriter.stats")
+        return dict(bands=b.value, band_rows=r.value, pyramid_ms=ms.value, host_bytes_peak=hp.value)
+
+    def close(self) -> None:
+        if self._h:
+            lib().mic_hip_wsi_writer_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WsiReader:
+    """MIC3 random-access reader (mic_hip_wsi_reader_*): reads the header and tile index at open, then only the blobs of the
+    tiles a tile() or region() covers.  source: a binary file object (seek + read), bytes, or a callable (offset, n) -> bytes."""
+
+    def __init__(self, source, file_len: Optional[int] = None):
+        if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = memoryview(source).cast("B")
+            get = lambda off, n: buf[off: off + n]
+            file_len = len(buf) if file_len is None else file_len
+        elif hasattr(source, "seek") and hasattr(source, "read"):
+            def get(off, n):
+                source.seek(off)
+                return source.read(n)
+            if file_len is None:
+                file_len = source.seek(0, os.SEEK_END)
+        else:
+            get = source
+        if file_len is None:
+            raise MicError(MIC_ERR_ARGS, "WsiReader: file_len")
+
+        def fill(off, ptr, n):
+            data = get(off, n)
+            if len(data) != n:
+                raise EOFError(f"WsiReader: {len(data)} of {n} bytes at {off}")
+            C.memmove(ptr, bytes(data), n)
+        self._cb = _Callback(fill, _READ_FN)
+        self._h = C.c_void_p()
+        self._cb.check(lib().mic_hip_wsi_reader_open(self._cb.c, None, int(file_len), C.byref(self._h)), "WsiReader")
+        v = [C.c_int() for _ in range(7)]
+        lib().mic_hip_wsi_reader_info(self._h, *[C.byref(x) for x in v])
+        w, h, tw, th, nl, ch, bps = (x.value for x in v)
+        self.info = dict(width=w, height=h, tile_width=tw, tile_height=th, levels=nl, channels=ch, bits_per_sample=bps)
+
+    def tile(self, level: int, tile_x: int, tile_y: int) -> np.ndarray:
+        """as decompress_wsi_tile on the whole file"""
+        out = np.empty(self.info["tile_width"] * self.info["tile_height"] * _wsi_bpp(self.info), dtype=np.uint8)
+        ow, oh = C.c_int(), C.c_int()
+        self._cb.check(lib().mic_hip_wsi_reader_decompress_tile(self._h, level, tile_x, tile_y, out.ctypes.data, out.size,
+                                                                C.byref(ow), C.byref(oh)), "WsiReader.tile")
+        return _wsi_shape(self.info, out, ow.value, oh.value).copy()
+
+    def region(self, level: int, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """as decompress_wsi_region on the whole file"""
+        out = np.empty(max(w, 0) * max(h, 0) * _wsi_bpp(self.info), dtype=np.uint8)
+        ow, oh = C.c_int(), C.c_int()
+        self._cb.check(lib().mic_hip_wsi_reader_decompress_region(self._h, level, x, y, w, h, out.ctypes.data, out.size,
+                                                                  C.byref(ow), C.byref(oh)), "WsiReader.region")
+        return _wsi_shape(self.info, out, ow.value, oh.value)
+
+    def close(self) -> None:
+        if self._h:
+            lib().mic_hip_wsi_reader_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------------------ gradient predictor, PICA

@@ -10,6 +10,8 @@
 // the requested tiles, then inverse transform + crop on the device.
 #include "mic_session.h"
 
+#include <memory>
+
 static constexpr size_t kMaxGridX = 0x7FFFFFFF;
 static constexpr size_t kMaxGridY = 65535;   // HIP grid limit in y and z: launches that put tiles there take at most this many per sub-batch
 
@@ -174,19 +176,25 @@ struct Mic3 {
     int planes() const { return rgb() ? 3 : 1; }
     size_t bpp() const { return (size_t)channels * (bps == 16 ? 2 : 1); }  // bytesPerPixel, wsicompress.go:530-533
 };
-int parse_mic3(const uint8_t *c, size_t len, Mic3 &m) {                       // ReadMIC3Header, wsiformat.go:169-227
+// ReadMIC3Header (wsiformat.go:169-227) in two steps, so that a reader that pulls the file through a callback can check the fixed
+// 48 bytes against the file's length before it reads the level table and tile index: parse_mic3_fixed sees c[0 .. 48) only,
+// parse_mic3_levels c[48 .. 48 + 20 * nlev).  len is the whole file's length either way.
+int parse_mic3_fixed(const uint8_t *c, size_t len, Mic3 &m) {
     if (len < 48 || memcmp(c, "MIC3", 4) != 0) return MIC_ERR_CORRUPT;
     if (get_u32(c + 4) != 1) return MIC_ERR_CORRUPT;
     m.w = (int)get_u32(c + 8); m.h = (int)get_u32(c + 12); m.tw = (int)get_u32(c + 16); m.th = (int)get_u32(c + 20);
     m.channels = c[24] | (c[25] << 8); m.bps = c[26]; m.flags = c[27]; m.nlev = c[28] | (c[29] << 8); m.total = get_u64(c + 32);
     if (len < 48 + 20 * (size_t)m.nlev) return MIC_ERR_CORRUPT;
     if (m.total > (len - 48 - 20 * (size_t)m.nlev) / 16) return MIC_ERR_CORRUPT;
+    m.data_off = 48 + 20 * (size_t)m.nlev + 16 * (size_t)m.total;
+    return MIC_OK;
+}
+int parse_mic3_levels(const uint8_t *c, Mic3 &m) {
     m.lv.clear();
     for (int i = 0; i < m.nlev; i++) {
         const uint8_t *p = c + 48 + 20 * (size_t)i;
         m.lv.push_back(Level{ (int)get_u32(p), (int)get_u32(p + 4), (int)get_u32(p + 8), (int)get_u32(p + 12), (int)get_u32(p + 16) });
     }
-    m.data_off = 48 + 20 * (size_t)m.nlev + 16 * (size_t)m.total;
     if (m.tw <= 0 || m.th <= 0 || (size_t)m.tw * m.th > ((size_t)1 << 26)) return MIC_ERR_CORRUPT;
     // the level table must be what computeLevels writes (wsiformat.go:244-271): positive dimensions, tile counts that are the
     // ceilings of dimension / tile size, tile ranges inside the tile table.  The decoders walk tx * ty tiles of a level, so a
@@ -197,6 +205,10 @@ int parse_mic3(const uint8_t *c, size_t len, Mic3 &m) {                       //
         if ((uint64_t)l.first + (uint64_t)l.tx * (uint64_t)l.ty > m.total) return MIC_ERR_CORRUPT;
     }
     return MIC_OK;
+}
+int parse_mic3(const uint8_t *c, size_t len, Mic3 &m) {
+    const int rc = parse_mic3_fixed(c, len, m);
+    return rc ? rc : parse_mic3_levels(c, m);
 }
 
 // decode the given tiles (global indices) of one level into dst (an image of dst_w x dst_h pixels of the slide's format);
@@ -282,28 +294,46 @@ int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::v
     return rc;
 }
 
-// the given tiles (global indices) of a MIC3 container: ExtractTileBlob (wsiformat.go:230-241), then decode_blobs
+// ExtractTileBlob (wsiformat.go:230-241) for the given tiles (global indices): a flat file in memory, or a streaming reader's callback
+// (its bytes then live in `keep`).  decode_box asks one source from several threads at once.
+typedef std::function<int(const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep)> BlobSource;
+BlobSource flat_source(const uint8_t *c, size_t len, const Mic3 &m) {
+    return [c, len, &m](const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &) -> int {
+        for (size_t gi : tiles) {
+            if (gi >= m.total) return MIC_ERR_CORRUPT;
+            const uint8_t *e = c + 48 + 20 * (size_t)m.nlev + 16 * gi;
+            const uint64_t bo = get_u64(e), bl = get_u64(e + 8);
+            if (bo > len || bl > len || m.data_off + bo + bl > len) return MIC_ERR_CORRUPT;
+            blobs.push_back(TileBlob{ c + m.data_off + bo, (size_t)bl });
+        }
+        return MIC_OK;
+    };
+}
+
+// the given tiles (global indices) of a MIC3 container, then decode_blobs
+int decode_tiles(const BlobSource &src, const Mic3 &m, const std::vector<size_t> &tiles, const std::vector<int4> &place,
+                 uint8_t *rgb_out, int dst_w, int dst_h) {
+    std::vector<TileBlob> blobs; std::vector<uint8_t> keep;
+    const int rc = src(tiles, blobs, keep);
+    if (rc) return rc;
+    return decode_blobs(m, blobs, place, rgb_out, dst_w, dst_h);
+}
 int decode_tiles(const uint8_t *c, size_t len, const Mic3 &m, const std::vector<size_t> &tiles, const std::vector<int4> &place,
                  uint8_t *rgb_out, int dst_w, int dst_h) {
-    std::vector<TileBlob> blobs;
-    for (size_t gi : tiles) {
-        if (gi >= m.total) return MIC_ERR_CORRUPT;
-        const uint8_t *e = c + 48 + 20 * (size_t)m.nlev + 16 * gi;
-        const uint64_t bo = get_u64(e), bl = get_u64(e + 8);
-        if (bo > len || bl > len || m.data_off + bo + bl > len) return MIC_ERR_CORRUPT;
-        blobs.push_back(TileBlob{ c + m.data_off + bo, (size_t)bl });
-    }
-    return decode_blobs(m, blobs, place, rgb_out, dst_w, dst_h);
+    return decode_tiles(flat_source(c, len, m), m, tiles, place, rgb_out, dst_w, dst_h);
 }
 
 // every tile of one pyramid level (image d_img on the device): extraction + transform + plane statistics, the unit codec over all
 // non-constant planes in slabs that keep planes + unit workspace bounded, then the tile blobs (compressTileBlob, wsicompress.go:312-370)
+// keep: planes / stats buffers the caller holds across calls and the tiles per sub-batch (the streaming writer); null: per call.
+struct TileBufs { DevBuf *planes, *stats; size_t per; };
 int compress_level_tiles(mic_hip_session *s, const void *d_img, const Level &L, int tile_w, int tile_h, const Mic3 &fmt,
-                         std::vector<uint8_t> *blobs_out) {
+                         std::vector<uint8_t> *blobs_out, const TileBufs *keep = nullptr) {
     const size_t P = (size_t)fmt.planes();
     const size_t npx = (size_t)tile_w * tile_h;
-    const size_t per = std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), ((size_t)8 << 30) / (P * npx * 2))));
-    DevBuf planes, stats;
+    const size_t per = keep ? keep->per : std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), ((size_t)8 << 30) / (P * npx * 2))));
+    DevBuf own_planes, own_stats;
+    DevBuf &planes = keep ? *keep->planes : own_planes, &stats = keep ? *keep->stats : own_stats;
     int rc = MIC_OK;
     const size_t ntl = (size_t)L.tx * L.ty;
     for (size_t t0 = 0; t0 < ntl && rc == MIC_OK; t0 += per) {
@@ -373,7 +403,7 @@ int compress_level_tiles(mic_hip_session *s, const void *d_img, const Level &L, 
             }
         }
     }
-    planes.release(); stats.release();
+    own_planes.release(); own_stats.release();
     return rc;
 }
 
@@ -548,7 +578,7 @@ int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt
 // Tiles [tx0, tx1] x [ty0, ty1] of level L into dst, an image of bw x bh pixels whose corner is the level's (bx, by = ty0 * th).
 // One device, or -- when the box spans two tile rows or more, several devices are listed and the call is not nested -- one
 // contiguous range of tile rows per device (shard_plan, weighted by pixels), each decoded into its own rows of dst.
-int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
+int decode_box(const BlobSource &src, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
                uint8_t *dst) {
     const int by = ty0 * m.th;
     auto rows = [&](int r0, int r1, int device) -> int {                        // tile rows r0 .. r1 - 1
@@ -563,7 +593,7 @@ int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int 
         DefaultLease lease;
         const int rc = lease.acquire(device);
         if (rc) return rc;
-        return decode_tiles(c, len, m, tiles, place, dst + (size_t)(ys - by) * bw * m.bpp(), bw, hs);
+        return decode_tiles(src, m, tiles, place, dst + (size_t)(ys - by) * bw * m.bpp(), bw, hs);
     };
     const int nrows = ty1 - ty0 + 1;
     const std::vector<int> devs = default_devices();
@@ -578,7 +608,54 @@ int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int 
         return r0 < r1 ? rows(r0, r1, devs[(size_t)k]) : MIC_OK;
     });
 }
+int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
+               uint8_t *dst) {
+    return decode_box(flat_source(c, len, m), m, L, tx0, tx1, ty0, ty1, bx, bw, bh, dst);
+}
 
+// DecompressWSITile on a parsed header, the blobs from `src` (mic_hip_wsi_decompress_tile: the flat file; the streaming reader)
+int wsi_tile(const BlobSource &src, const Mic3 &m, int level, int tile_x, int tile_y, uint8_t *rgb_out, size_t out_cap, int *out_w, int *out_h) {
+    int rc;
+    if (level < 0 || level >= m.nlev) return MIC_ERR_ARGS;
+    const Level &L = m.lv[(size_t)level];
+    if (tile_x < 0 || tile_x >= L.tx || tile_y < 0 || tile_y >= L.ty) return MIC_ERR_ARGS;
+    const int aw = std::min(m.tw, L.w - tile_x * m.tw), ah = std::min(m.th, L.h - tile_y * m.th);
+    if (aw <= 0 || ah <= 0) return MIC_ERR_CORRUPT;
+    if (!m.supported()) return MIC_ERR_UNSUPPORTED;
+    if ((size_t)aw * ah * m.bpp() > out_cap) return MIC_ERR_CAPACITY;
+    if (out_w) *out_w = aw; if (out_h) *out_h = ah;
+    DefaultLease lease;
+    if ((rc = lease.acquire())) return rc;
+    std::vector<size_t> tiles(1, (size_t)L.first + (size_t)tile_y * L.tx + tile_x);
+    std::vector<int4> place(1, make_int4(0, 0, aw, ah));
+    return decode_tiles(src, m, tiles, place, rgb_out, aw, ah);
+}
+
+// DecompressWSIRegion on a parsed header, the blobs from `src`
+int wsi_region(const BlobSource &src, const Mic3 &m, int level, int x, int y, int w, int h, uint8_t *rgb_out, size_t out_cap,
+               int *out_w, int *out_h) {
+    int rc;
+    if (level < 0 || level >= m.nlev || x < 0 || y < 0) return MIC_ERR_ARGS;
+    const Level &L = m.lv[(size_t)level];
+    if (L.w <= 0 || L.h <= 0 || m.tw <= 0 || m.th <= 0) return MIC_ERR_CORRUPT;
+    if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
+    if ((int64_t)x + w > L.w) w = L.w - x;                                                  // :232-237
+    if ((int64_t)y + h > L.h) h = L.h - y;
+    if (w <= 0 || h <= 0) return MIC_ERR_ARGS;                                              // "MIC3: empty region"
+    if (!m.supported()) return MIC_ERR_UNSUPPORTED;
+    const size_t bpp = m.bpp();
+    if ((size_t)w * h * bpp > out_cap) return MIC_ERR_CAPACITY;
+    const int tx0 = x / m.tw, ty0 = y / m.th, tx1 = (x + w - 1) / m.tw, ty1 = (y + h - 1) / m.th;
+    const int bx = tx0 * m.tw, by = ty0 * m.th;
+    const int bw = std::min((tx1 + 1) * m.tw, L.w) - bx, bh = std::min((ty1 + 1) * m.th, L.h) - by;
+    std::vector<uint8_t> box((size_t)bw * bh * bpp);
+    if ((rc = decode_box(src, m, L, tx0, tx1, ty0, ty1, bx, bw, bh, box.data()))) return rc;
+    for (int r = 0; r < h; r++)
+        memcpy(rgb_out + (size_t)r * w * bpp, box.data() + ((size_t)(y - by + r) * bw + (size_t)(x - bx)) * bpp, (size_t)w * bpp);
+    if (out_w) *out_w = w;
+    if (out_h) *out_h = h;
+    return MIC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -783,19 +860,7 @@ int mic_hip_wsi_decompress_tile(const uint8_t *c, size_t len, int level, int til
     if (!c || !rgb_out) return MIC_ERR_ARGS;
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
-    if (level < 0 || level >= m.nlev) return MIC_ERR_ARGS;
-    const Level &L = m.lv[(size_t)level];
-    if (tile_x < 0 || tile_x >= L.tx || tile_y < 0 || tile_y >= L.ty) return MIC_ERR_ARGS;
-    const int aw = std::min(m.tw, L.w - tile_x * m.tw), ah = std::min(m.th, L.h - tile_y * m.th);
-    if (aw <= 0 || ah <= 0) return MIC_ERR_CORRUPT;
-    if (!m.supported()) return MIC_ERR_UNSUPPORTED;
-    if ((size_t)aw * ah * m.bpp() > out_cap) return MIC_ERR_CAPACITY;
-    if (out_w) *out_w = aw; if (out_h) *out_h = ah;
-    DefaultLease lease;
-    if ((rc = lease.acquire())) return rc;
-    std::vector<size_t> tiles(1, (size_t)L.first + (size_t)tile_y * L.tx + tile_x);
-    std::vector<int4> place(1, make_int4(0, 0, aw, ah));
-    return decode_tiles(c, len, m, tiles, place, rgb_out, aw, ah);
+    return wsi_tile(flat_source(c, len, m), m, level, tile_x, tile_y, rgb_out, out_cap, out_w, out_h);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // Whole pyramid level in one batch: every tile of the level, stitched (viewer / bench path)
@@ -818,26 +883,7 @@ int mic_hip_wsi_decompress_region(const uint8_t *c, size_t len, int level, int x
     if (!c || !rgb_out) return MIC_ERR_ARGS;
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
-    if (level < 0 || level >= m.nlev || x < 0 || y < 0) return MIC_ERR_ARGS;
-    const Level &L = m.lv[(size_t)level];
-    if (L.w <= 0 || L.h <= 0 || m.tw <= 0 || m.th <= 0) return MIC_ERR_CORRUPT;
-    if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
-    if ((int64_t)x + w > L.w) w = L.w - x;                                                  // :232-237
-    if ((int64_t)y + h > L.h) h = L.h - y;
-    if (w <= 0 || h <= 0) return MIC_ERR_ARGS;                                              // "MIC3: empty region"
-    if (!m.supported()) return MIC_ERR_UNSUPPORTED;
-    const size_t bpp = m.bpp();
-    if ((size_t)w * h * bpp > out_cap) return MIC_ERR_CAPACITY;
-    const int tx0 = x / m.tw, ty0 = y / m.th, tx1 = (x + w - 1) / m.tw, ty1 = (y + h - 1) / m.th;
-    const int bx = tx0 * m.tw, by = ty0 * m.th;
-    const int bw = std::min((tx1 + 1) * m.tw, L.w) - bx, bh = std::min((ty1 + 1) * m.th, L.h) - by;
-    std::vector<uint8_t> box((size_t)bw * bh * bpp);
-    if ((rc = decode_box(c, len, m, L, tx0, tx1, ty0, ty1, bx, bw, bh, box.data()))) return rc;
-    for (int r = 0; r < h; r++)
-        memcpy(rgb_out + (size_t)r * w * bpp, box.data() + ((size_t)(y - by + r) * bw + (size_t)(x - bx)) * bpp, (size_t)w * bpp);
-    if (out_w) *out_w = w;
-    if (out_h) *out_h = h;
-    return MIC_OK;
+    return wsi_region(flat_source(c, len, m), m, level, x, y, w, h, rgb_out, out_cap, out_w, out_h);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 
@@ -1174,5 +1220,393 @@ int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int
     for (int i = 0; i < *levels && i < cap; i++) { if (widths) widths[i] = s->wsi->lv[(size_t)i].w; if (heights) heights[i] = s->wsi->lv[(size_t)i].h; }
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+}  // extern "C"
+
+// ==========================================================================================
+// MIC3 streaming.  The writer takes a slide's rows in pushes of any size and codes it in bands of B tile rows (R = B * tile_h rows
+// of level 0).  Every level k keeps, on the device, the rows it has made but not yet coded, behind one carried row: slot 0 of the
+// level's buffer holds its row `base`, slot i row base + i.  Level k + 1 row y is the 2x2 box of level-k rows 2y and 2y + 1
+// (Downsample2xRGB / Downsample2xGrey, wsipyramid.go:10-55, the odd last row and column dropped), so the row a level carries over
+// a coded band edge is the one that still waits for its partner.  A level codes its rows once it holds B whole tile rows, or all of
+// its rows: only its last tile row is ever padded, as in the one-shot file.
+namespace {
+
+// one level of a band: rows [lo, hi) are new in this band; buf = slot 0 (global row `base`); w = the level's width
+struct BandLevel { uint8_t *buf; int w, base, lo, hi; };
+struct BandPyr { BandLevel L[33]; int nlev, strip; };   // strip: level-0 columns per workgroup, a power of two >= 2^(nlev - 1)
+
+typedef uint32_t bp_u32x4 __attribute__((ext_vector_type(4)));
+typedef bp_u32x4 bp_u32x4_u __attribute__((aligned(1)));    // (rows are packed: a row starts at any byte)
+
+// VP output pixels of one row from 2 * VP pixels of two source rows: 16-byte loads of each row, 16-byte stores.
+// u8 (RGB or grey): VP = 16; u16 grey: VP = 8.  Each output sample is (a + b + c + d + 2) / 4 of its 2x2 source samples.
+template <typename T, int C>
+__device__ __forceinline__ void band_pyr_chunk(const uint8_t *ra, const uint8_t *rb, uint8_t *o) {
+    constexpr int VP = sizeof(T) == 1 ? 16 : 8, NI = 2 * VP * C * (int)sizeof(T) / 16, NO = NI / 2;
+    uint32_t a[4 * NI], b[4 * NI], r[4 * NO];
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        const bp_u32x4 va = *(const bp_u32x4_u *)(ra + 16 * i), vb = *(const bp_u32x4_u *)(rb + 16 * i);
+        a[4 * i] = va.x; a[4 * i + 1] = va.y; a[4 * i + 2] = va.z; a[4 * i + 3] = va.w;
+        b[4 * i] = vb.x; b[4 * i + 1] = vb.y; b[4 * i + 2] = vb.z; b[4 * i + 3] = vb.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4 * NO; i++) r[i] = 0;
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int j = 0; j < VP; j++) {                         // word j of a row pair = source samples 2j, 2j + 1
+            const uint32_t v = ((a[j] & 0xFFFFu) + (a[j] >> 16) + (b[j] & 0xFFFFu) + (b[j] >> 16) + 2) >> 2;
+            r[j >> 1] |= v << (16 * (j & 1));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < VP * C; j++) {                     // output byte j = channel j % C of pixel j / C
+            const int i1 = 2 * (j / C) * C + j % C, i2 = i1 + C;
+            const uint32_t v = (((a[i1 >> 2] >> (8 * (i1 & 3))) & 0xFFu) + ((a[i2 >> 2] >> (8 * (i2 & 3))) & 0xFFu) +
+                                ((b[i1 >> 2] >> (8 * (i1 & 3))) & 0xFFu) + ((b[i2 >> 2] >> (8 * (i2 & 3))) & 0xFFu) + 2) >> 2;
+            r[j >> 2] |= v << (8 * (j & 3));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NO; i++) *(bp_u32x4_u *)(o + 16 * i) = bp_u32x4{ r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3] };
+}
+
+// Every level's new rows of one band in one launch.  Workgroup g owns level-0 columns [g * strip, (g + 1) * strip) and so columns
+// [g * strip >> k, (g + 1) * strip >> k) of level k: what it reads of level k - 1 it wrote itself (or an earlier launch did), so the
+// levels follow each other behind a workgroup barrier and no workgroup waits for another.  A lane makes VP pixels of a row from
+// 16-byte loads of the row pair; a chunk cut by the strip's or the row's end goes sample by sample.  32-bit index arithmetic only.
+template <typename T, int C>
+__global__ void __launch_bounds__(256) k_wsi_band_pyramid(BandPyr P) {
+    constexpr int VP = sizeof(T) == 1 ? 16 : 8, BPP = C * (int)sizeof(T);
+    const int g = blockIdx.x;
+    for (int k = 1; k < P.nlev; k++) {
+        const BandLevel D = P.L[k], S = P.L[k - 1];
+        const int sk = P.strip >> k, x0 = g * sk, x1 = min(D.w, x0 + sk);
+        if (D.lo < D.hi && x0 < x1) {
+            const int nch = (x1 - x0 + VP - 1) / VP, items = nch * (D.hi - D.lo);
+            const size_t srow = (size_t)S.w * BPP, drow = (size_t)D.w * BPP;
+            for (int i = threadIdx.x; i < items; i += blockDim.x) {
+                const int yr = i / nch, ch = i - yr * nch;
+                const int y = D.lo + yr, px0 = x0 + ch * VP, n = min(VP, x1 - px0);
+                const uint8_t *ra = S.buf + (size_t)(2 * y - S.base) * srow + (size_t)px0 * 2 * BPP, *rb = ra + srow;
+                uint8_t *o = D.buf + (size_t)(y - D.base) * drow + (size_t)px0 * BPP;
+                if (n == VP) { band_pyr_chunk<T, C>(ra, rb, o); continue; }
+                const T *ta = (const T *)ra, *tb = (const T *)rb;
+                T *to = (T *)o;
+                for (int p = 0; p < n; p++)
+#pragma unroll
+                    for (int c = 0; c < C; c++)
+                        to[p * C + c] = (T)(((uint32_t)ta[2 * p * C + c] + ta[2 * p * C + C + c] + tb[2 * p * C + c] + tb[2 * p * C + C + c] + 2) / 4);
+            }
+        }
+        __syncthreads();                                        // level k is complete in this strip before level k + 1 reads it
+    }
+}
+
+}  // namespace
+
+struct mic_hip_wsi_writer {
+    std::mutex mu;
+    mic_hip_write_fn write = nullptr; void *user = nullptr;
+    Mic3 fmt; int width = 0, height = 0, tw = 0, th = 0;
+    std::vector<Level> lv; size_t total_tiles = 0, hdr = 0;
+    int B = 0, R = 0, strip = 0, nbuf = 0;        // band tile rows, band rows, columns per workgroup, levels the buffers hold
+    mic_hip_session *s = nullptr;
+    DevBuf pyr, planes, stats;
+    TileBufs bufs{ nullptr, nullptr, 1 };
+    std::vector<size_t> lvoff; std::vector<int> cap;   // per level: byte offset of its buffer in pyr, its slots
+    std::vector<int> base, made, coded;                // per level: row in slot 0, rows made, rows coded
+    std::vector<uint64_t> lens;                        // every tile's blob length (level 0's as they are coded)
+    uint64_t l0_bytes = 0;                             // level-0 blob bytes written so far
+    std::vector<std::vector<uint8_t>> upper;           // blobs of levels >= 1, held until finish
+    size_t upper_bytes = 0, host_peak = 0;
+    std::vector<uint8_t> staging;
+    uint64_t device_bytes = 0, bands = 0;
+    double pyr_ms = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int err = MIC_OK; bool done = false;
+    ~mic_hip_wsi_writer() {
+        if (s) {
+            (void)s->activate();
+            pyr.release(); planes.release(); stats.release();
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            mic_hip_session_destroy(s);
+        }
+    }
+    size_t row_bytes(int k) const { return (size_t)(width >> k) * fmt.bpp(); }
+    uint8_t *slot(int k, int row) { return (uint8_t *)pyr.p + lvoff[(size_t)k] + (size_t)(row - base[(size_t)k]) * row_bytes(k); }
+    int sink(uint64_t off, const uint8_t *p, size_t n) { return n == 0 || write(user, off, p, n) == 0 ? MIC_OK : MIC_ERR_IO; }
+    void note_host() { host_peak = std::max(host_peak, upper_bytes + lens.size() * 16 + staging.capacity()); }
+
+    // level k codes `rows` rows from `coded` on (whole tile rows, or the rest of the level); level 0's blobs go to the sink
+    int code_rows(int k, int rows) {
+        const Level &G = lv[(size_t)k];
+        const int ntr = (rows + th - 1) / th;
+        const Level band{ G.w, rows, G.tx, ntr, 0 };
+        std::vector<std::vector<uint8_t>> blobs((size_t)ntr * G.tx);
+        int rc = compress_level_tiles(s, slot(k, coded[(size_t)k]), band, tw, th, fmt, blobs.data(), &bufs);
+        if (rc) return rc;
+        const size_t first = (size_t)G.first + (size_t)(coded[(size_t)k] / th) * G.tx;
+        for (size_t t = 0; t < blobs.size(); t++) lens[first + t] = blobs[t].size();
+        if (k == 0) {
+            staging.clear();
+            for (auto &b : blobs) staging.insert(staging.end(), b.begin(), b.end());
+            note_host();
+            if ((rc = sink(hdr + l0_bytes, staging.data(), staging.size()))) return rc;
+            l0_bytes += staging.size();
+        } else {
+            for (size_t t = 0; t < blobs.size(); t++) { upper_bytes += blobs[t].size(); upper[first - lv[1].first + t].swap(blobs[t]); }
+            note_host();
+        }
+        coded[(size_t)k] += rows;
+        // keep the rows not coded yet and the one before them at the front of the buffer (they never overlap what they replace:
+        // at least one tile row was coded, at most tile_h - 1 rows are left behind)
+        const int keep_from = coded[(size_t)k] - 1, n = made[(size_t)k] - keep_from;
+        if (n > 0 && keep_from > base[(size_t)k])
+            HIP_TRY(hipMemcpyAsync(slot(k, base[(size_t)k]), slot(k, keep_from), (size_t)n * row_bytes(k), hipMemcpyDeviceToDevice, s->stream));
+        base[(size_t)k] = keep_from;
+        return MIC_OK;
+    }
+
+    // level 0 holds a full band, or the slide's last rows: the other levels' new rows, then every level that has enough to code
+    int band() {
+        const int nlev = (int)lv.size();
+        BandPyr P{};
+        P.nlev = nlev; P.strip = strip;
+        bool any = false;
+        for (int k = 0; k < nlev; k++) {
+            BandLevel &L = P.L[k];
+            L.buf = (uint8_t *)pyr.p + lvoff[(size_t)k]; L.w = lv[(size_t)k].w; L.base = base[(size_t)k];
+            L.lo = L.hi = made[(size_t)k];
+            if (k > 0) {
+                L.hi = std::min(lv[(size_t)k].h, made[(size_t)k - 1] / 2);
+                if (L.hi - L.base > cap[(size_t)k] || 2 * L.lo < P.L[k - 1].base) return MIC_ERR_INTERNAL;   // (the slot bound of open)
+                made[(size_t)k] = L.hi;
+                any |= L.hi > L.lo;
+            }
+        }
+        if (any) {
+            const unsigned grid = (unsigned)((width + strip - 1) / strip);
+            HIP_TRY(hipEventRecord(ev0, s->stream));
+            if (fmt.planes() == 3) hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 3>), dim3(grid), dim3(256), 0, s->stream, P);
+            else if (fmt.bps == 16) hipLaunchKernelGGL((k_wsi_band_pyramid<uint16_t, 1>), dim3(grid), dim3(256), 0, s->stream, P);
+            else hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 1>), dim3(grid), dim3(256), 0, s->stream, P);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev1, s->stream));
+        }
+        for (int k = 0; k < nlev; k++) {
+            const int pending = made[(size_t)k] - coded[(size_t)k];
+            if (pending <= 0) continue;
+            int rc = MIC_OK;
+            if (made[(size_t)k] == lv[(size_t)k].h) rc = code_rows(k, pending);
+            else if (pending / th >= B) rc = code_rows(k, pending / th * th);
+            if (rc) return rc;
+        }
+        if (any) {
+            float ms = 0;
+            HIP_TRY(hipEventSynchronize(ev1));
+            if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) pyr_ms += ms;
+        }
+        bands++;
+        return MIC_OK;
+    }
+};
+
+struct mic_hip_wsi_reader {
+    std::mutex mu, io;                      // mu: one call at a time; io: one callback at a time (decode_box asks from several threads)
+    mic_hip_read_fn read = nullptr; void *user = nullptr;
+    uint64_t file_len = 0;
+    Mic3 m;
+    std::vector<uint8_t> head;              // header, level table, tile index
+    // the blobs of `tiles` through the callback: every entry checked against file_len first, then one read per run of contiguous blobs
+    int fetch(const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
+        std::vector<uint64_t> off(tiles.size()), len(tiles.size());
+        size_t total = 0;
+        for (size_t i = 0; i < tiles.size(); i++) {
+            if (tiles[i] >= m.total) return MIC_ERR_CORRUPT;
+            const uint8_t *e = head.data() + 48 + 20 * (size_t)m.nlev + 16 * tiles[i];
+            const uint64_t bo = get_u64(e), bl = get_u64(e + 8);
+            if (bo > file_len || bl > file_len || m.data_off + bo + bl > file_len) return MIC_ERR_CORRUPT;
+            off[i] = m.data_off + bo; len[i] = bl; total += (size_t)bl;
+        }
+        keep.resize(total + 1);
+        std::lock_guard<std::mutex> lk(io);
+        size_t pos = 0;
+        for (size_t i = 0; i < tiles.size();) {
+            size_t j = i + 1, n = (size_t)len[i];
+            while (j < tiles.size() && off[j] == off[j - 1] + len[j - 1]) n += (size_t)len[j++];
+            if (n && read(user, off[i], keep.data() + pos, n) != 0) return MIC_ERR_IO;
+            for (; i < j; i++) { blobs.push_back(TileBlob{ keep.data() + pos, (size_t)len[i] }); pos += (size_t)len[i]; }
+        }
+        return MIC_OK;
+    }
+    BlobSource source() {
+        return [this](const std::vector<size_t> &t, std::vector<TileBlob> &b, std::vector<uint8_t> &k) { return fetch(t, b, k); };
+    }
+};
+
+extern "C" {
+
+int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sample, int tile_w, int tile_h, int levels,
+                            int band_tile_rows, mic_hip_write_fn write, void *user, mic_hip_wsi_writer **out) try {
+    if (!write || !out || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0 || band_tile_rows < 0) return MIC_ERR_ARGS;
+    *out = nullptr;
+    Mic3 fmt; fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);   // as mic_hip_wsi_compress_ex
+    if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
+    if (tile_w == 0) tile_w = 256;
+    if (tile_h == 0) tile_h = 256;
+    if ((size_t)tile_w * tile_h > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
+    const size_t bpp = fmt.bpp(), P = (size_t)fmt.planes(), npx = (size_t)tile_w * tile_h;
+    const size_t tiles_x = ((size_t)width + tile_w - 1) / tile_w;
+    if ((size_t)width * bpp * tile_h > ((size_t)1 << 31)) return MIC_ERR_UNSUPPORTED;    // one tile row of level 0 under 2 GiB
+    std::unique_ptr<mic_hip_wsi_writer> w(new mic_hip_wsi_writer());
+    w->write = write; w->user = user; w->fmt = fmt;
+    w->width = width; w->height = height; w->tw = tile_w; w->th = tile_h;
+    w->lv = plan_levels(width, height, tile_w, tile_h, levels);
+    for (const Level &l : w->lv) w->total_tiles += (size_t)l.tx * l.ty;
+    w->hdr = 48 + 20 * w->lv.size() + 16 * w->total_tiles;
+    int dev = default_devices()[0];
+    int rc = check_device(dev);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(dev));
+    // B: one band fills a sub-batch of the unit codec, at most 256 MiB of level-0 pixels
+    size_t B = (size_t)band_tile_rows;
+    if (B == 0) {
+        const size_t fill = std::max<size_t>(1, std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)) / tiles_x);
+        B = std::max<size_t>(1, std::min(fill, ((size_t)256 << 20) / ((size_t)width * bpp * tile_h)));
+    }
+    if (B * tile_h > (size_t)1 << 28) return MIC_ERR_UNSUPPORTED;
+    w->B = (int)B; w->R = (int)B * tile_h;
+    // the buffers hold every level the width allows (the level count follows the height): level 0 a band and the carried row,
+    // level k >= 1 up to B tile rows not yet coded + a band's new rows (R / 2 + 1) + the carried row
+    int nbuf = 0;
+    while (nbuf < 33 && (width >> nbuf) >= 1) nbuf++;
+    w->nbuf = nbuf;
+    size_t bytes = 0;
+    for (int k = 0; k < nbuf; k++) {
+        const int c = k == 0 ? w->R + 1 : w->R + w->R / 2 + 2;
+        w->lvoff.push_back(bytes); w->cap.push_back(c);
+        bytes += ((size_t)c * w->row_bytes(k) + 255) & ~(size_t)255;
+    }
+    w->strip = 64;                                                  // (the kernel's workgroups: no memory hangs on it)
+    while (w->strip < (1 << std::min((int)w->lv.size() - 1, 30)) || (width + w->strip - 1) / w->strip > 1024) w->strip *= 2;
+    const size_t per = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kMaxGridY / P, B * tiles_x), ((size_t)8 << 30) / (P * npx * 2)));
+    if ((rc = mic_hip_session_create_on(dev, &w->s, (int)(per * P), npx))) return rc;
+    mic_hip_session *s = w->s;
+    if ((rc = w->pyr.reserve(bytes + 64))) return rc;
+    if ((rc = w->planes.reserve(per * P * npx * 2 + 64))) return rc;
+    if ((rc = w->stats.reserve(per * P * 8 + 64))) return rc;
+    w->bufs = TileBufs{ &w->planes, &w->stats, per };
+    HIP_TRY(hipEventCreate(&w->ev0));
+    HIP_TRY(hipEventCreate(&w->ev1));
+    const size_t nl = w->lv.size();
+    w->base.assign(nl, -1); w->made.assign(nl, 0); w->coded.assign(nl, 0);
+    w->lens.assign(w->total_tiles, 0);
+    if (nl > 1) w->upper.resize(w->total_tiles - (size_t)w->lv[1].first);
+    w->device_bytes = w->pyr.cap + w->planes.cap + w->stats.cap + s->reserved_bytes();
+    w->note_host();
+    *out = w.release();
+    return MIC_OK;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+int mic_hip_wsi_writer_push_rows(mic_hip_wsi_writer *w, const uint8_t *rows, int nrows) try {
+    if (!w) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(w->mu);
+    if (w->err) return w->err;
+    if (!rows || nrows <= 0 || w->done || (int64_t)w->made[0] + nrows > w->height) return MIC_ERR_ARGS;
+    int rc = w->s->activate();
+    const size_t rb = w->row_bytes(0);
+    while (rc == MIC_OK && nrows > 0) {
+        const int n = std::min(nrows, w->R - (w->made[0] - w->coded[0]));
+        if (hipMemcpyAsync(w->slot(0, w->made[0]), rows, (size_t)n * rb, hipMemcpyHostToDevice, w->s->stream) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
+        w->made[0] += n; rows += (size_t)n * rb; nrows -= n;
+        if (w->made[0] - w->coded[0] == w->R || w->made[0] == w->height) rc = w->band();
+    }
+    if (rc == MIC_OK && hipStreamSynchronize(w->s->stream) != hipSuccess) rc = MIC_ERR_DEVICE;   // the caller's rows are consumed
+    if (rc) w->err = rc;
+    return rc;
+} catch (const std::bad_alloc &) { w->err = MIC_ERR_NOMEM; return MIC_ERR_NOMEM; } catch (...) { w->err = MIC_ERR_INTERNAL; return MIC_ERR_INTERNAL; }
+
+int mic_hip_wsi_writer_finish(mic_hip_wsi_writer *w, uint64_t *file_len) try {
+    if (!w) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(w->mu);
+    if (w->err) return w->err;
+    if (w->done || w->made[0] != w->height) return MIC_ERR_ARGS;
+    for (size_t k = 0; k < w->lv.size(); k++) if (w->coded[k] != w->lv[k].h) { w->err = MIC_ERR_INTERNAL; return w->err; }
+    // the upper levels' blobs behind level 0's, then header, level table and tile index (WriteMIC3, wsiformat.go:99-165) at 0
+    uint64_t off = w->hdr + w->l0_bytes;
+    int rc = MIC_OK;
+    for (size_t t = 0; t < w->upper.size() && rc == MIC_OK; t++) { rc = w->sink(off, w->upper[t].data(), w->upper[t].size()); off += w->upper[t].size(); }
+    if (rc == MIC_OK) {
+        std::vector<size_t> lens(w->lens.begin(), w->lens.end());
+        std::vector<uint8_t> head(w->hdr);
+        put_mic3_index(head.data(), w->width, w->height, w->tw, w->th, w->fmt, w->lv, w->total_tiles, lens.data());
+        rc = w->sink(0, head.data(), head.size());
+    }
+    if (rc) { w->err = rc; return rc; }
+    w->done = true;
+    if (file_len) *file_len = off;
+    return MIC_OK;
+} catch (const std::bad_alloc &) { w->err = MIC_ERR_NOMEM; return MIC_ERR_NOMEM; } catch (...) { w->err = MIC_ERR_INTERNAL; return MIC_ERR_INTERNAL; }
+
+int mic_hip_wsi_writer_device_bytes(const mic_hip_wsi_writer *w, uint64_t *bytes) {
+    if (!w || !bytes) return MIC_ERR_ARGS;
+    *bytes = w->device_bytes;
+    return MIC_OK;
+}
+
+int mic_hip_wsi_writer_stats(const mic_hip_wsi_writer *w, uint64_t *bands, int *band_rows, double *pyramid_ms, uint64_t *host_bytes_peak) {
+    if (!w) return MIC_ERR_ARGS;
+    if (bands) *bands = w->bands;
+    if (band_rows) *band_rows = w->R;
+    if (pyramid_ms) *pyramid_ms = w->pyr_ms;
+    if (host_bytes_peak) *host_bytes_peak = w->host_peak;
+    return MIC_OK;
+}
+
+void mic_hip_wsi_writer_close(mic_hip_wsi_writer *w) { delete w; }
+
+int mic_hip_wsi_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len, mic_hip_wsi_reader **out) try {
+    if (!read || !out) return MIC_ERR_ARGS;
+    *out = nullptr;
+    std::unique_ptr<mic_hip_wsi_reader> r(new mic_hip_wsi_reader());
+    r->read = read; r->user = user; r->file_len = file_len;
+    if (file_len < 48) return MIC_ERR_CORRUPT;
+    r->head.resize(48);
+    if (read(user, 0, r->head.data(), 48) != 0) return MIC_ERR_IO;
+    int rc = parse_mic3_fixed(r->head.data(), (size_t)file_len, r->m);
+    if (rc) return rc;
+    r->head.resize(r->m.data_off);
+    if (r->m.data_off > 48 && read(user, 48, r->head.data() + 48, r->m.data_off - 48) != 0) return MIC_ERR_IO;
+    if ((rc = parse_mic3_levels(r->head.data(), r->m))) return rc;
+    *out = r.release();
+    return MIC_OK;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+int mic_hip_wsi_reader_info(const mic_hip_wsi_reader *r, int *width, int *height, int *tile_w, int *tile_h, int *levels,
+                            int *channels, int *bits_per_sample) {
+    if (!r) return MIC_ERR_ARGS;
+    if (width) *width = r->m.w; if (height) *height = r->m.h; if (tile_w) *tile_w = r->m.tw; if (tile_h) *tile_h = r->m.th;
+    if (levels) *levels = r->m.nlev; if (channels) *channels = r->m.channels; if (bits_per_sample) *bits_per_sample = r->m.bps;
+    return MIC_OK;
+}
+
+int mic_hip_wsi_reader_decompress_tile(mic_hip_wsi_reader *r, int level, int tile_x, int tile_y,
+                                       uint8_t *out, size_t out_cap, int *out_w, int *out_h) try {
+    if (!r || !out) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    return wsi_tile(r->source(), r->m, level, tile_x, tile_y, out, out_cap, out_w, out_h);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x, int y, int w, int h,
+                                         uint8_t *out, size_t out_cap, int *out_w, int *out_h) try {
+    if (!r || !out) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    return wsi_region(r->source(), r->m, level, x, y, w, h, out, out_cap, out_w, out_h);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
 
 }  // extern "C"
