@@ -660,6 +660,9 @@ __global__ void __launch_bounds__(256) k_rle_walk_compact(MicUnit *units) {
     const uint32_t nsym = u.nsym;
     auto put = [&](uint32_t idx, uint32_t x, uint32_t o, uint32_t len) {
         u.seg[idx] = make_uint2(x, o);
+        // the literal chunk that holds the stream's last symbol must lie inside the tokens: k_wv_scatter reads only the first n
+        // symbols, Go reads all of them (rledecompressu16.go:87-97: index panic).  Such a frame is k_wv_expand's, which reports it.
+        if (!(x >> 31) && o < nsym && nsym - o <= len && x + (nsym - 1 - o) >= u.ntok) u.wv_slow = 1;
         if (((o + len - 1) >> 13) != ((o - 1) >> 13))
             for (uint32_t kk = (o + (WS_T - 1)) >> 13; (kk << 13) < o + len && (kk << 13) < nsym; kk++) tidx[kk] = idx;
     };
@@ -760,6 +763,10 @@ __global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, int32_t *a,
 
 int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
 
+// The most symbols a WaveletV2 stream of n pixels may announce: every coefficient escaped (3 words), + 8.  Go has no ceiling
+// (rledecompressu16.go:87-97 allocates what the stream announces); a stream above this one is MIC_ERR_CORRUPT here and in the oracle.
+inline size_t wv_sym_ceiling(size_t n) { return 3 * n + 8; }
+
 }  // namespace
 
 void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter) {
@@ -851,6 +858,7 @@ int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_
         MicUnit &u = s->h_units[(size_t)i];
         u.comp_in = d_comp + offs[(size_t)i]; u.comp_len = (uint32_t)(offs[(size_t)i + 1] - offs[(size_t)i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
         s->fill_workspace(u, i);
+        u.sym_cap = (uint32_t)std::min<size_t>(u.sym_cap, wv_sym_ceiling(n));   // the oracle's ceiling: DESIGN.md section 4, WaveletV2
     }
     if (s->h_units.upload(s->units.p, (size_t)nf, s->stream) != MIC_OK) return done(MIC_ERR_DEVICE);
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;

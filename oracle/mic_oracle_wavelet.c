@@ -202,6 +202,9 @@ int mico_wavelet_v2_decompress(const uint8_t *in, size_t len, uint16_t *px, size
     if (tok && enc && ord && data) {
         size_t tn = 0, m = 0;
         rc = mico_fse_decompress_auto(in + 11, len - 11, tok, 6 * n + 32, &tn);
+        /* more than 3 n + 8 symbols announced (every coefficient escaped, + 8): corrupt, as on the device (csrc/mic_wavelet.hip:
+         * wv_sym_ceiling).  Go has no ceiling (rledecompressu16.go:87-97 allocates what the stream announces). */
+        if (rc == MICO_OK && tn >= 3 && (((uint32_t)tok[1] << 16) + tok[2]) > 3 * n + 8) rc = MICO_ERR_CORRUPT;
         if (rc == MICO_OK) rc = mico_rle_decompress(tok, tn, enc, 3 * n + 8, &m);
         if (rc == MICO_OK) {
             size_t i = 0, k = 0;                                      /* u16ToWaveletCoeffs, :43-58 */

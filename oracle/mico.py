@@ -221,6 +221,15 @@ def rle_compress(sym: np.ndarray, max_value: int) -> np.ndarray:
     return out[: n.value].copy()
 
 
+def rle_decompress(tok: np.ndarray, cap: int):
+    """RleDecompressU16.Decompress (rledecompressu16.go:87-97): returns (rc, symbols)"""
+    tok = np.ascontiguousarray(tok, dtype=np.uint16)
+    out = np.empty(max(cap, 1), dtype=np.uint16)
+    n = C.c_size_t()
+    rc = lib().mico_rle_decompress(_p(tok), C.c_size_t(tok.size), _p(out), C.c_size_t(cap), C.byref(n))
+    return rc, (out[: n.value].copy() if rc == 0 else None)
+
+
 def wt53_forward(data: np.ndarray, levels: int):
     """in-place multi-level forward transform of an int32 (rows, cols) array; returns levels applied"""
     assert data.dtype == np.int32 and data.flags.c_contiguous
