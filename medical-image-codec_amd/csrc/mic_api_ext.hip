@@ -15,6 +15,11 @@
 static constexpr size_t kMaxGridX = 0x7FFFFFFF;
 static constexpr size_t kMaxGridY = 65535;   // HIP grid limit in y and z: launches that put tiles there take at most this many per sub-batch
 
+// One coded plane of a tile (compressWSIPlane, wsicompress.go:373-421): mode 0 constant zero, 1 constant `value`, 2 a unit-codec
+// stream, 3 raw pixels; the bytes of modes 2 / 3 are `len` bytes at base + off on the device, the base being whatever buffer the
+// records describe (the session's store, a slab of uploaded blobs; 0 -- absolute addresses -- for a slab just encoded).
+struct WsiPlane { uint8_t mode; uint16_t value; uint64_t off, len; };
+
 namespace {
 
 void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
@@ -139,10 +144,6 @@ __global__ void __launch_bounds__(256) k_wsi_plane_to_grey(const uint16_t *plane
     }
 }
 
-__global__ void __launch_bounds__(256) k_fill_u16(uint16_t *p, size_t n, uint16_t v) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
 // constant planes of a slab in one launch: grid = (chunks, planes); fill[k] = {plane index, value}
 __global__ void __launch_bounds__(256) k_fill_planes(uint16_t *planes, size_t npx, const uint2 *fill) {
     const uint2 f = fill[blockIdx.y];
@@ -211,8 +212,174 @@ int parse_mic3(const uint8_t *c, size_t len, Mic3 &m) {
     return rc ? rc : parse_mic3_levels(c, m);
 }
 
+// The slide formats compressTileBlob codes (wsicompress.go:312-317) with WSIOptions.defaults (wsiformat.go:86-96): fmt of a
+// width x height slide, tile_w / tile_h 0 = 256.  What every MIC3 encode entry point checks first.
+int wsi_options(int width, int height, int channels, int bits_per_sample, int tile_w, int tile_h, int levels, Mic3 &fmt) {
+    fmt = Mic3();
+    fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);
+    if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
+    fmt.w = width; fmt.h = height; fmt.tw = tile_w ? tile_w : 256; fmt.th = tile_h ? tile_h : 256;
+    if ((size_t)fmt.tw * fmt.th > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
+    return MIC_OK;
+}
+
+// ---- the kernels by slide format: each helper is the one place that picks the instantiation ------------------------------------
+// tiles t0 .. t0 + nt - 1 of level L (image img) -> planes [nt][P][tw * th] and their {min, max} stats
+void launch_tile_planes(hipStream_t st, const Mic3 &fmt, const void *img, const Level &L, size_t t0, size_t nt, uint16_t *planes, uint32_t *stats) {
+    const dim3 grid(8, (unsigned)nt), block(256);
+    if (fmt.planes() == 3)
+        hipLaunchKernelGGL(k_wsi_tile_planes, grid, block, 0, st, (const uint8_t *)img, L.w, L.h, fmt.tw, fmt.th, L.tx, (int)t0, planes, stats);
+    else if (fmt.bps == 16)
+        hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint16_t>, grid, block, 0, st, (const uint16_t *)img, L.w, L.h, fmt.tw, fmt.th, L.tx, (int)t0, planes, stats);
+    else
+        hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint8_t>, grid, block, 0, st, (const uint8_t *)img, L.w, L.h, fmt.tw, fmt.th, L.tx, (int)t0, planes, stats);
+}
+// planes of nt tiles -> dst (dst_w pixels across) at place[k] (device)
+void launch_planes_to_pixels(hipStream_t st, const Mic3 &m, const uint16_t *planes, const int4 *place, size_t nt, void *dst, int dst_w) {
+    const dim3 grid(16, (unsigned)nt), block(256);
+    if (m.planes() == 3)
+        hipLaunchKernelGGL(k_wsi_planes_to_rgb, grid, block, 0, st, planes, m.tw, m.th, place, (uint8_t *)dst, dst_w);
+    else if (m.bps == 16)
+        hipLaunchKernelGGL(k_wsi_plane_to_grey<uint16_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint16_t *)dst, dst_w);
+    else
+        hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint8_t *)dst, dst_w);
+}
+// one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
+void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
+    if (fmt.planes() == 3)
+        hipLaunchKernelGGL(k_wsi_downsample, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
+    else if (fmt.bps == 16)
+        hipLaunchKernelGGL(k_wsi_downsample_grey<uint16_t>, dim3(1024), dim3(256), 0, st, (const uint16_t *)src, sw, (uint16_t *)dst, dw, dh);
+    else
+        hipLaunchKernelGGL(k_wsi_downsample_grey<uint8_t>, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
+}
+
+// ---- tile blobs ------------------------------------------------------------------------------------------------------------------
+// Bytes of one plane in a tile blob: the mode byte, then the constant (mode 1) or the stream / raw pixels (modes 2, 3)
+uint64_t plane_bytes(const WsiPlane &p) { return p.mode == 0 ? 1 : p.mode == 1 ? 3 : 1 + p.len; }
+
+// compressTileBlob (wsicompress.go:334-364) on the device: tile blockIdx.x's planes, each with its mode byte in front (and its
+// constant), to their places in the payload; for RGB the tile's three plane lengths in front of them.  src is a device address.
+struct WsiRec { uint64_t src, dst; uint32_t len; uint32_t mode_value; };          // mode_value = mode | value << 8
+__global__ void __launch_bounds__(256) k_wsi_assemble(const WsiRec *recs, int P, uint8_t *payload) {
+    const size_t t = blockIdx.x;
+    typedef uint32_t wv4 __attribute__((ext_vector_type(4)));
+    typedef wv4 WQ __attribute__((aligned(1)));
+    for (int p = 0; p < P; p++) {
+        const WsiRec r = recs[t * (size_t)P + (size_t)p];
+        const uint32_t mode = r.mode_value & 0xFFu, value = r.mode_value >> 8;
+        uint8_t *d = payload + r.dst;
+        const uint32_t plen = mode == 0 ? 1u : mode == 1 ? 3u : 1u + r.len;
+        if (threadIdx.x == 0) {
+            d[0] = (uint8_t)mode;
+            if (mode == 1) { d[1] = (uint8_t)value; d[2] = (uint8_t)(value >> 8); }
+            if (P == 3) {                                                               // [Y_len][Co_len][Cg_len], u32 LE, in front of the tile's planes
+                uint8_t *h = payload + recs[t * 3].dst - 12 + 4 * p;
+                h[0] = (uint8_t)plen; h[1] = (uint8_t)(plen >> 8); h[2] = (uint8_t)(plen >> 16); h[3] = (uint8_t)(plen >> 24);
+            }
+        }
+        if (mode >= 2) {
+            const uint8_t *sp = (const uint8_t *)(uintptr_t)r.src; uint8_t *dp = d + 1;
+            const uint32_t nv = r.len / 16;
+            for (uint32_t i = threadIdx.x; i < nv; i += 256) *(WQ *)(dp + (size_t)i * 16) = *(const WQ *)(sp + (size_t)i * 16);
+            if (threadIdx.x < (r.len & 15u)) dp[(size_t)nv * 16 + threadIdx.x] = sp[(size_t)nv * 16 + threadIdx.x];
+        }
+    }
+}
+
+// The blobs of n tiles (P plane records each, bytes at base + off) back to back in `payload` on the device: the host lays them
+// out from the records, one k_wsi_assemble launch writes them.  tlen[t] = bytes of tile t, *total = their sum.
+int assemble_tiles(mic_hip_session *s, const WsiPlane *pl, size_t n, size_t P, uint64_t base, DevBuf &payload, DevBuf &d_recs,
+                   uint64_t *tlen, uint64_t *total) {
+    std::vector<WsiRec> recs(n * P);
+    uint64_t off = 0;
+    for (size_t t = 0; t < n; t++) {
+        const uint64_t t0 = off;
+        if (P == 3) off += 12;
+        for (size_t p = 0; p < P; p++) {
+            const WsiPlane &wp = pl[t * P + p];
+            recs[t * P + p] = WsiRec{ base + wp.off, off, wp.mode >= 2 ? (uint32_t)wp.len : 0u, (uint32_t)wp.mode | ((uint32_t)wp.value << 8) };
+            off += plane_bytes(wp);
+        }
+        tlen[t] = off - t0;
+    }
+    *total = off;
+    int rc;
+    if ((rc = payload.reserve((size_t)off + 64)) || (rc = d_recs.reserve(recs.size() * sizeof(WsiRec) + 64))) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(WsiRec), hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_wsi_assemble, dim3((unsigned)n), dim3(256), 0, s->stream, (const WsiRec *)d_recs.p, (int)P, (uint8_t *)payload.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s->stream));                                       // (recs is a stack-scope vector)
+    }
+    return MIC_OK;
+}
+
+// WriteMIC3 (wsiformat.go:99-165) without the blobs: header, level table, tile index for blobs of the given lengths back to back
+void put_mic3_index(uint8_t *out, const Mic3 &fmt, const std::vector<Level> &lv, const std::vector<uint64_t> &lens) {
+    const int nlev = (int)lv.size();
+    memset(out, 0, 48 + 20 * (size_t)nlev);
+    memcpy(out, "MIC3", 4); put_u32(out + 4, 1); put_u32(out + 8, (uint32_t)fmt.w); put_u32(out + 12, (uint32_t)fmt.h);
+    put_u32(out + 16, (uint32_t)fmt.tw); put_u32(out + 20, (uint32_t)fmt.th);
+    out[24] = (uint8_t)fmt.channels; out[25] = 0; out[26] = (uint8_t)fmt.bps; out[27] = (uint8_t)fmt.flags;
+    out[28] = (uint8_t)nlev; out[29] = (uint8_t)(nlev >> 8);
+    put_u64(out + 32, (uint64_t)lens.size());
+    for (int i = 0; i < nlev; i++) {
+        uint8_t *ld = out + 48 + 20 * (size_t)i;
+        put_u32(ld, (uint32_t)lv[(size_t)i].w); put_u32(ld + 4, (uint32_t)lv[(size_t)i].h); put_u32(ld + 8, (uint32_t)lv[(size_t)i].tx);
+        put_u32(ld + 12, (uint32_t)lv[(size_t)i].ty); put_u32(ld + 16, (uint32_t)lv[(size_t)i].first);
+    }
+    uint64_t off = 0;
+    for (size_t t = 0; t < lens.size(); t++) {
+        uint8_t *e = out + 48 + 20 * (size_t)nlev + 16 * t;
+        put_u64(e, off); put_u64(e + 8, lens[t]);
+        off += lens[t];
+    }
+}
+
+// ---- decode ----------------------------------------------------------------------------------------------------------------------
+// decompressTileBlob (wsicompress.go:424-527) for nt tiles from their plane records (bytes at base + off on the device): constant
+// planes filled, streams through the unit codec, raw planes copied; then YCoCg-R inverse / uint16ToBytes + crop into dst (dst_w
+// pixels across), tile k at place[k] (host).  planes holds the nt * P planes, aux the place rectangles and the fill list.
+int decode_planes(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, const int4 *place,
+                  DevBuf &planes, DevBuf &aux, void *dst, int dst_w) {
+    const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
+    int rc;
+    if ((rc = planes.reserve(nt * P * npx * 2 + 64))) return rc;
+    uint16_t *dp = (uint16_t *)planes.p;
+    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<uint2> fills;
+    for (size_t q = 0; q < nt * P; q++) {
+        const WsiPlane &wp = pl[q];
+        if (wp.mode <= 1) fills.push_back(make_uint2((uint32_t)q, wp.mode ? wp.value : 0u));
+        else if (wp.mode == 2) { units.push_back(mic_hip_unit{ q * npx, m.tw, m.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); }
+        else HIP_TRY(hipMemcpyAsync(dp + q * npx, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
+    }
+    if ((rc = aux.reserve(fills.size() * sizeof(uint2) + nt * sizeof(int4) + 64))) return rc;
+    int4 *d_place = (int4 *)aux.p; uint2 *d_fill = (uint2 *)((char *)aux.p + nt * sizeof(int4));
+    HIP_TRY(hipMemcpyAsync(d_place, place, nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
+    if (!fills.empty()) {
+        HIP_TRY(hipMemcpyAsync(d_fill, fills.data(), fills.size() * sizeof(uint2), hipMemcpyHostToDevice, s->stream));
+        s->timer.reset(s->stream); s->timer.mark("k_fill_planes");
+        for (size_t f0 = 0; f0 < fills.size(); f0 += 65535)
+            hipLaunchKernelGGL(k_fill_planes, dim3(4, (unsigned)std::min<size_t>(65535, fills.size() - f0)), dim3(256), 0, s->stream, dp, npx, (const uint2 *)d_fill + f0);
+    }
+    if (!units.empty()) {
+        if ((rc = session_decode_enqueue_spans(s, base, begins.data(), ends.data(), units.data(), (int)units.size(), dp))) return rc;
+        std::vector<int32_t> st(units.size());
+        if ((rc = session_decode_finish(s, st.data()))) return rc;
+        for (int32_t v : st) if (v != MIC_OK) return v;
+    }
+    s->timer.reset(s->stream); s->timer.mark("k_wsi_planes_to_pixels");
+    launch_planes_to_pixels(s->stream, m, dp, d_place, nt, dst, dst_w);
+    s->timer.mark("end");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return MIC_OK;
+}
+
 // decode the given tiles (global indices) of one level into dst (an image of dst_w x dst_h pixels of the slide's format);
-// place[k] = where tile k goes and how much of it is kept
+// place[k] = where tile k goes and how much of it is kept.  Slab by slab: the blobs are checked on the host, their planes' bytes
+// go up in one copy, decode_planes does the rest.
 struct TileBlob { const uint8_t *p; size_t len; };
 int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::vector<int4> &place,
                  uint8_t *rgb_out, int dst_w, int dst_h) {
@@ -223,19 +390,14 @@ int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::v
     const size_t P = (size_t)m.planes(), bpp = m.bpp();
     // per-tile chunking keeps the unit workspace bounded
     const size_t per = std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P));   // (tiles are a launch's grid y)
-    struct Bufs { DevBuf planes, d_place, d_out; ~Bufs() { planes.release(); d_place.release(); d_out.release(); } } bufs;   // freed on every return path
-    DevBuf &planes = bufs.planes, &d_place = bufs.d_place, &d_out = bufs.d_out;
+    struct Bufs { DevBuf planes, aux, d_out; ~Bufs() { planes.release(); aux.release(); d_out.release(); } } bufs;   // freed on every return path
     int rc;
-    if ((rc = d_out.reserve((size_t)dst_w * dst_h * bpp + 64))) return rc;
-    if (tiles.empty()) HIP_TRY(hipMemsetAsync(d_out.p, 0, (size_t)dst_w * dst_h * bpp, s->stream));   // nothing will write it
+    if ((rc = bufs.d_out.reserve((size_t)dst_w * dst_h * bpp + 64))) return rc;
+    if (tiles.empty()) HIP_TRY(hipMemsetAsync(bufs.d_out.p, 0, (size_t)dst_w * dst_h * bpp, s->stream));   // nothing will write it
+    std::vector<WsiPlane> pl; std::vector<uint8_t> bytes;
     for (size_t t0 = 0; t0 < ntile && rc == MIC_OK; t0 += per) {
         const size_t nt = std::min(per, ntile - t0);
-        if ((rc = planes.reserve(nt * P * npx * 2 + 64))) break;
-        if ((rc = d_place.reserve(nt * sizeof(int4) + 64))) break;
-        if ((rc = s->ensure(1, npx))) break;
-        std::vector<mic_hip_unit> units; std::vector<uint64_t> offs(1, 0); std::vector<uint8_t> comp;
-        struct Fill { size_t plane; int mode; uint16_t val; const uint8_t *raw; };
-        std::vector<Fill> fills;
+        pl.clear(); bytes.clear();
         for (size_t k = 0; k < nt && rc == MIC_OK; k++) {
             const uint8_t *blob = tiles[t0 + k].p; const size_t bl = tiles[t0 + k].len;
             size_t pl_off[3] = { 0, 0, 0 }, pl_len[3] = { (size_t)bl, 0, 0 };              // greyscale: the blob is the plane, :477-484
@@ -247,48 +409,24 @@ int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::v
             }
             for (size_t p = 0; p < P; p++) {                                               // decompressWSIPlane, :487-527
                 const uint8_t *d = blob + pl_off[p]; const size_t dl = pl_len[p];
-                const size_t plane = k * P + p;
                 if (dl == 0) { rc = MIC_ERR_CORRUPT; break; }
-                if (d[0] == 0) fills.push_back(Fill{ plane, 0, 0, nullptr });
-                else if (d[0] == 1) { if (dl < 3) { rc = MIC_ERR_CORRUPT; break; } fills.push_back(Fill{ plane, 1, (uint16_t)(d[1] | (d[2] << 8)), nullptr }); }
-                else if (d[0] == 2) {
-                    units.push_back(mic_hip_unit{ plane * npx, m.tw, m.th, 0, 0 });
-                    comp.insert(comp.end(), d + 1, d + dl);
-                    offs.push_back(comp.size());
-                } else if (d[0] == 3) { if (dl < 1 + 2 * npx) { rc = MIC_ERR_CORRUPT; break; } fills.push_back(Fill{ plane, 3, 0, d + 1 }); }
+                WsiPlane wp{ d[0], 0, bytes.size(), 0 };
+                if (d[0] == 0) { }
+                else if (d[0] == 1) { if (dl < 3) { rc = MIC_ERR_CORRUPT; break; } wp.value = (uint16_t)(d[1] | (d[2] << 8)); }
+                else if (d[0] == 2) wp.len = dl - 1;
+                else if (d[0] == 3) { if (dl < 1 + 2 * npx) { rc = MIC_ERR_CORRUPT; break; } wp.len = 2 * npx; }
                 else { rc = MIC_ERR_CORRUPT; break; }
+                if (wp.mode >= 2) bytes.insert(bytes.end(), d + 1, d + 1 + wp.len);
+                pl.push_back(wp);
             }
         }
         if (rc) break;
-        uint16_t *dp = (uint16_t *)planes.p;
-        for (const Fill &f : fills) {
-            if (f.mode == 3) HIP_TRY(hipMemcpyAsync(dp + f.plane * npx, f.raw, npx * 2, hipMemcpyHostToDevice, s->stream));
-            else hipLaunchKernelGGL(k_fill_u16, dim3(64), dim3(256), 0, s->stream, dp + f.plane * npx, npx, f.val);
-        }
-        if (!units.empty()) {
-            if ((rc = s->io_comp.reserve(comp.size() + 64))) break;
-            HIP_TRY(hipMemcpyAsync(s->io_comp.p, comp.data(), comp.size(), hipMemcpyHostToDevice, s->stream));
-            if ((rc = session_decode_enqueue(s, (const uint8_t *)s->io_comp.p, offs.data(), units.data(), (int)units.size(), dp))) break;
-            std::vector<int32_t> st(units.size());
-            if ((rc = session_decode_finish(s, st.data()))) break;
-            for (int32_t v : st) if (v != MIC_OK) { rc = v; break; }
-            if (rc) break;
-        }
-        HIP_TRY(hipMemcpyAsync(d_place.p, place.data() + t0, nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
-        if (P == 3)
-            hipLaunchKernelGGL(k_wsi_planes_to_rgb, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th, (const int4 *)d_place.p,
-                               (uint8_t *)d_out.p, dst_w);
-        else if (m.bps == 16)
-            hipLaunchKernelGGL(k_wsi_plane_to_grey<uint16_t>, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th,
-                               (const int4 *)d_place.p, (uint16_t *)d_out.p, dst_w);
-        else
-            hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th,
-                               (const int4 *)d_place.p, (uint8_t *)d_out.p, dst_w);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        if ((rc = s->ensure(1, npx)) || (rc = s->io_comp.reserve(bytes.size() + 64))) break;
+        if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
+        rc = decode_planes(s, m, (const uint8_t *)s->io_comp.p, pl.data(), nt, place.data() + t0, bufs.planes, bufs.aux, bufs.d_out.p, dst_w);
     }
     if (rc == MIC_OK) {
-        hipError_t e = hipMemcpy(rgb_out, d_out.p, (size_t)dst_w * dst_h * bpp, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(rgb_out, bufs.d_out.p, (size_t)dst_w * dst_h * bpp, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = MIC_ERR_DEVICE;
     }
     return rc;
@@ -318,126 +456,86 @@ int decode_tiles(const BlobSource &src, const Mic3 &m, const std::vector<size_t>
     if (rc) return rc;
     return decode_blobs(m, blobs, place, rgb_out, dst_w, dst_h);
 }
-int decode_tiles(const uint8_t *c, size_t len, const Mic3 &m, const std::vector<size_t> &tiles, const std::vector<int4> &place,
-                 uint8_t *rgb_out, int dst_w, int dst_h) {
-    return decode_tiles(flat_source(c, len, m), m, tiles, place, rgb_out, dst_w, dst_h);
+
+// ---- encode ----------------------------------------------------------------------------------------------------------------------
+// tiles per slab: within the grid's y limit, a sub-batch of the unit codec, at most `cap` bytes of planes
+size_t slab_tiles(const Mic3 &fmt, size_t cap) {
+    const size_t P = (size_t)fmt.planes(), npx = (size_t)fmt.tw * fmt.th;
+    return std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), cap / (P * npx * 2))));
 }
 
-// every tile of one pyramid level (image d_img on the device): extraction + transform + plane statistics, the unit codec over all
-// non-constant planes in slabs that keep planes + unit workspace bounded, then the tile blobs (compressTileBlob, wsicompress.go:312-370)
-// keep: planes / stats buffers the caller holds across calls and the tiles per sub-batch (the streaming writer); null: per call.
-struct TileBufs { DevBuf *planes, *stats; size_t per; };
-int compress_level_tiles(mic_hip_session *s, const void *d_img, const Level &L, int tile_w, int tile_h, const Mic3 &fmt,
-                         std::vector<uint8_t> *blobs_out, const TileBufs *keep = nullptr) {
-    const size_t P = (size_t)fmt.planes();
-    const size_t npx = (size_t)tile_w * tile_h;
-    const size_t per = keep ? keep->per : std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), ((size_t)8 << 30) / (P * npx * 2))));
-    DevBuf own_planes, own_stats;
-    DevBuf &planes = keep ? *keep->planes : own_planes, &stats = keep ? *keep->stats : own_stats;
-    int rc = MIC_OK;
+// One coded slab of tiles t0 .. t0 + nt - 1: P plane records per tile at absolute addresses -- a stream inside the slab's packed
+// streams [streams, streams + stream_bytes), a raw plane inside the slab's plane buffer.  Valid until the next slab.
+struct Slab { size_t t0, nt; std::vector<WsiPlane> planes; const uint8_t *streams; uint64_t stream_bytes; };
+
+// every tile of level L (image d_img on the device) in slabs of `per` tiles: the tile extraction fused with the colour transform and
+// the plane statistics, the plane modes (compressWSIPlane, wsicompress.go:373-421), the unit codec over the non-constant planes;
+// then sink(slab).  planes / stats: the caller's buffers for a slab's planes and their {min, max}.
+int encode_level(mic_hip_session *s, const Mic3 &fmt, const void *d_img, const Level &L, DevBuf &planes, DevBuf &stats, size_t per,
+                 const std::function<int(const Slab &)> &sink) {
+    const size_t P = (size_t)fmt.planes(), npx = (size_t)fmt.tw * fmt.th;
     const size_t ntl = (size_t)L.tx * L.ty;
-    for (size_t t0 = 0; t0 < ntl && rc == MIC_OK; t0 += per) {
+    Slab sl;
+    int rc;
+    for (size_t t0 = 0; t0 < ntl; t0 += per) {
         const size_t nt = std::min(per, ntl - t0);
-        if ((rc = planes.reserve(nt * P * npx * 2 + 64))) break;
-        if ((rc = stats.reserve(nt * P * 8 + 64))) break;
+        if ((rc = planes.reserve(nt * P * npx * 2 + 64)) || (rc = stats.reserve(nt * P * 8 + 64))) return rc;
         std::vector<uint32_t> st(nt * P * 2);
         for (size_t k = 0; k < nt * P; k++) { st[2 * k] = 0xFFFFFFFFu; st[2 * k + 1] = 0; }
-        if (hipMemcpyAsync(stats.p, st.data(), st.size() * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
-        if (P == 3)
-            hipLaunchKernelGGL(k_wsi_tile_planes, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint8_t *)d_img, L.w, L.h,
-                               tile_w, tile_h, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        else if (fmt.bps == 16)
-            hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint16_t>, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint16_t *)d_img,
-                               L.w, L.h, tile_w, tile_h, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        else
-            hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint8_t>, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint8_t *)d_img,
-                               L.w, L.h, tile_w, tile_h, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        if (hipGetLastError() != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
-        if (hipMemcpyAsync(st.data(), stats.p, st.size() * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
-        if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
-        // plane modes (compressWSIPlane, wsicompress.go:373-421)
-        std::vector<mic_hip_unit> units; std::vector<size_t> unit_plane;
-        for (size_t p = 0; p < nt * P; p++) {
-            const uint32_t mn = st[2 * p], mx = st[2 * p + 1];
-            if (mn == mx) continue;                                                    // constant plane
-            units.push_back(mic_hip_unit{ p * npx, tile_w, tile_h, (uint16_t)std::max<uint32_t>(mx, 255u), 2 });   // :398-402
-            unit_plane.push_back(p);
-        }
+        HIP_TRY(hipMemcpyAsync(stats.p, st.data(), st.size() * 4, hipMemcpyHostToDevice, s->stream));
+        s->timer.reset(s->stream); s->timer.mark("k_wsi_tile_planes");
+        launch_tile_planes(s->stream, fmt, d_img, L, t0, nt, (uint16_t *)planes.p, (uint32_t *)stats.p);
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(st.data(), stats.p, st.size() * 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        std::vector<mic_hip_unit> units;                                               // a unit per non-constant plane
+        for (size_t p = 0; p < nt * P; p++)
+            if (st[2 * p] != st[2 * p + 1]) units.push_back(mic_hip_unit{ p * npx, fmt.tw, fmt.th, (uint16_t)std::max<uint32_t>(st[2 * p + 1], 255u), 2 });   // :398-402
         std::vector<uint64_t> offs(units.size() + 1, 0); std::vector<int32_t> ust(units.size()), uns(units.size());
-        std::vector<uint8_t> packed;
+        sl.streams = nullptr;
         if (!units.empty()) {
-            if ((rc = session_encode_enqueue(s, (const uint16_t *)planes.p, units.data(), (int)units.size()))) break;
-            const uint8_t *d_blobs = nullptr;
-            if ((rc = session_encode_finish(s, &d_blobs, offs.data(), ust.data(), uns.data()))) break;
-            packed.resize((size_t)offs.back() + 16);
-            if (offs.back() && hipMemcpy(packed.data(), d_blobs, (size_t)offs.back(), hipMemcpyDeviceToHost) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
+            if ((rc = session_encode_enqueue(s, (const uint16_t *)planes.p, units.data(), (int)units.size()))) return rc;
+            if ((rc = session_encode_finish(s, &sl.streams, offs.data(), ust.data(), uns.data()))) return rc;
         }
-        std::vector<long> unit_of(nt * P, -1);
-        for (size_t k = 0; k < units.size(); k++) unit_of[unit_plane[k]] = (long)k;
-        std::vector<uint16_t> rawbuf;
-        for (size_t k = 0; k < nt && rc == MIC_OK; k++) {
-            std::vector<uint8_t> &tb = blobs_out[t0 + k];
-            tb.assign(P == 3 ? 12 : 0, 0);                                             // RGB: three plane lengths, :341-363; grey: bare plane, :366-370
-            for (size_t p = 0; p < P; p++) {
-                const size_t pi = k * P + p;
-                const size_t before = tb.size();
-                const uint32_t mn = st[2 * pi], mx = st[2 * pi + 1];
-                if (mn == mx) {
-                    if (mn == 0) tb.push_back(0);                                      // planeConstantZero
-                    else { tb.push_back(1); tb.push_back((uint8_t)mn); tb.push_back((uint8_t)(mn >> 8)); }
-                } else {
-                    const long ui = unit_of[pi];
-                    const int32_t ustat = ust[(size_t)ui];
-                    if (ustat == MIC_OK) {
-                        tb.push_back(2);
-                        tb.insert(tb.end(), packed.begin() + (long)offs[(size_t)ui], packed.begin() + (long)offs[(size_t)ui + 1]);
-                    } else if (ustat == MIC_ERR_USE_RLE || ustat == MIC_ERR_INCOMPRESSIBLE) {      // raw fallback, :403-414
-                        rawbuf.resize(npx);
-                        if (hipMemcpy(rawbuf.data(), (uint16_t *)planes.p + pi * npx, npx * 2, hipMemcpyDeviceToHost) != hipSuccess) { rc = MIC_ERR_DEVICE; break; }
-                        tb.push_back(3);
-                        const uint8_t *rb = (const uint8_t *)rawbuf.data();
-                        tb.insert(tb.end(), rb, rb + npx * 2);
-                    } else { rc = ustat; break; }
-                }
-                if (P == 3) put_u32(tb.data() + 4 * p, (uint32_t)(tb.size() - before));
-            }
+        sl.t0 = t0; sl.nt = nt; sl.stream_bytes = offs.back();
+        sl.planes.resize(nt * P);
+        for (size_t p = 0, u = 0; p < nt * P; p++) {
+            const uint32_t mn = st[2 * p], mx = st[2 * p + 1];
+            WsiPlane &wp = sl.planes[p];
+            if (mn == mx) { wp = WsiPlane{ (uint8_t)(mn == 0 ? 0 : 1), (uint16_t)mn, 0, 0 }; continue; }
+            if (ust[u] == MIC_OK) wp = WsiPlane{ 2, 0, (uint64_t)(uintptr_t)sl.streams + offs[u], offs[u + 1] - offs[u] };
+            else if (ust[u] == MIC_ERR_USE_RLE || ust[u] == MIC_ERR_INCOMPRESSIBLE)                   // raw fallback, :403-414
+                wp = WsiPlane{ 3, 0, (uint64_t)(uintptr_t)((const uint16_t *)planes.p + p * npx), npx * 2 };
+            else return ust[u];
+            u++;
         }
+        if ((rc = sink(sl))) return rc;
     }
-    own_planes.release(); own_stats.release();
-    return rc;
+    return MIC_OK;
 }
 
-// one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
-void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
-    if (fmt.planes() == 3)
-        hipLaunchKernelGGL(k_wsi_downsample, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
-    else if (fmt.bps == 16)
-        hipLaunchKernelGGL(k_wsi_downsample_grey<uint16_t>, dim3(1024), dim3(256), 0, st, (const uint16_t *)src, sw, (uint16_t *)dst, dw, dh);
-    else
-        hipLaunchKernelGGL(k_wsi_downsample_grey<uint8_t>, dim3(1024), dim3(256), 0, st, (const uint8_t *)src, sw, (uint8_t *)dst, dw, dh);
-}
+// Tile blobs of one level that lie back to back in the file: tile `first` (global index) and the lens.size() tiles after it
+struct TileRun { size_t first = 0; std::vector<uint8_t> bytes; std::vector<uint64_t> lens; };
+struct SlabBufs {                                    // a slab's planes and stats, its assembled blobs and their records
+    DevBuf planes, stats, payload, recs;
+    void release() { planes.release(); stats.release(); payload.release(); recs.release(); }
+    ~SlabBufs() { release(); }
+};
 
-// WriteMIC3 (wsiformat.go:99-165) without the blobs: header, level table, tile index for blobs of the given lengths back to back
-void put_mic3_index(uint8_t *out, int width, int height, int tile_w, int tile_h, const Mic3 &fmt, const std::vector<Level> &lv,
-                    size_t total_tiles, const size_t *lens) {
-    const int nlev = (int)lv.size();
-    memset(out, 0, 48 + 20 * (size_t)nlev);
-    memcpy(out, "MIC3", 4); put_u32(out + 4, 1); put_u32(out + 8, (uint32_t)width); put_u32(out + 12, (uint32_t)height);
-    put_u32(out + 16, (uint32_t)tile_w); put_u32(out + 20, (uint32_t)tile_h);
-    out[24] = (uint8_t)fmt.channels; out[25] = 0; out[26] = (uint8_t)fmt.bps; out[27] = (uint8_t)fmt.flags;
-    out[28] = (uint8_t)nlev; out[29] = (uint8_t)(nlev >> 8);
-    put_u64(out + 32, (uint64_t)total_tiles);
-    for (int i = 0; i < nlev; i++) {
-        uint8_t *ld = out + 48 + 20 * (size_t)i;
-        put_u32(ld, (uint32_t)lv[(size_t)i].w); put_u32(ld + 4, (uint32_t)lv[(size_t)i].h); put_u32(ld + 8, (uint32_t)lv[(size_t)i].tx);
-        put_u32(ld + 12, (uint32_t)lv[(size_t)i].ty); put_u32(ld + 16, (uint32_t)lv[(size_t)i].first);
-    }
-    size_t off = 0;
-    for (size_t t = 0; t < total_tiles; t++) {
-        uint8_t *e = out + 48 + 20 * (size_t)nlev + 16 * t;
-        put_u64(e, (uint64_t)off); put_u64(e + 8, (uint64_t)lens[t]);
-        off += lens[t];
-    }
+// every tile of level L appended to `run` (the host-bound paths): each slab's blobs are assembled on the device and come to the
+// host in one copy
+int code_level(mic_hip_session *s, const Mic3 &fmt, const void *d_img, const Level &L, SlabBufs &b, size_t per, TileRun &run) {
+    return encode_level(s, fmt, d_img, L, b.planes, b.stats, per, [&](const Slab &sl) -> int {
+        const size_t n0 = run.lens.size(), b0 = run.bytes.size();
+        uint64_t total = 0;
+        run.lens.resize(n0 + sl.nt);
+        int rc = assemble_tiles(s, sl.planes.data(), sl.nt, (size_t)fmt.planes(), 0, b.payload, b.recs, run.lens.data() + n0, &total);
+        if (rc) return rc;
+        run.bytes.resize(b0 + (size_t)total);
+        if (total) HIP_TRY(hipMemcpy(run.bytes.data() + b0, b.payload.p, (size_t)total, hipMemcpyDeviceToHost));
+        return MIC_OK;
+    });
 }
 
 // ---- MIC3 over the devices of mic_hip_set_devices: the slide in bands of tile rows (parallel.wsi_band_plan) ----------------------
@@ -462,10 +560,11 @@ struct PinnedHost {                                  // staging for the rows tha
 // mic_hip_wsi_compress_ex with shard b coding rows [row_first[b], row_first[b + 1]) on devs[b]: levels 0..K of its band, each
 // tile with the single-device tile path; devs[0] codes levels K + 1 .. L - 1 from the bands' rows of level K + 1 (of level K when
 // tile_h is odd: a band of an odd number of level-K rows does not end on a row pair).  Within a level the tiles of band b are one
-// contiguous run of the tile table, so the lengths scan into the file's offsets and each shard writes its own run of `out`.
-int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt, int tile_w, int tile_h, const std::vector<Level> &lv,
-                       int K, const std::vector<int> &row_first, const std::vector<int> &devs, uint8_t *out, size_t out_cap, size_t *out_len) {
-    const int nlev = (int)lv.size(), shards = (int)devs.size();
+// contiguous run of the tile table, so the lengths scan into the file's offsets and each shard writes its own runs of `out`.
+// One band (band_plan with one shard: K = L - 1) is the one-device slide.
+int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Level> &lv, int K, const std::vector<int> &row_first,
+                       const std::vector<int> &devs, uint8_t *out, size_t out_cap, size_t *out_len) {
+    const int nlev = (int)lv.size(), shards = (int)devs.size(), width = fmt.w, tile_h = fmt.th;
     const size_t bpp = fmt.bpp();
     size_t total_tiles = 0;
     for (const Level &l : lv) total_tiles += (size_t)l.tx * l.ty;
@@ -479,27 +578,27 @@ int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt
     if (top > 0 && hipHostMalloc(&stage.p, (size_t)lv[(size_t)top].w * lv[(size_t)top].h * bpp + 64, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError(); return MIC_ERR_NOMEM;
     }
-    struct Band { std::vector<std::vector<uint8_t>> blobs; std::vector<size_t> first, count; };   // per level k <= K: global first tile, tiles
-    std::vector<Band> B((size_t)shards);
+    std::vector<std::vector<TileRun>> runs((size_t)shards);                   // shard b's runs: levels 0..K of its band (devs[0]: + the top)
+    // level L of an image on the device as one more run of `rs` (L.first: the level's first tile in the file)
+    auto code_run = [&](mic_hip_session *s, const void *d_img, const Level &L, std::vector<TileRun> &rs) -> int {
+        SlabBufs bufs;                                                          // (freed behind each level)
+        rs.emplace_back();
+        rs.back().first = (size_t)L.first;
+        return code_level(s, fmt, d_img, L, bufs, slab_tiles(fmt, (size_t)8 << 30), rs.back());
+    };
     rc = run_parallel(shards, [&](int b) -> int {
         const int y0 = row_first[(size_t)b], rows = row_first[(size_t)b + 1] - y0;
         if (rows <= 0) return MIC_OK;
-        Band &band = B[(size_t)b];
-        std::vector<Level> bl;                                                  // the band's levels 0..K, tile indices local to the band
-        size_t nt = 0;
+        std::vector<Level> bl;                                                  // the band's levels 0..K; first: global tile index
         for (int k = 0; k <= K; k++) {
             const int h = rows >> k;
-            bl.push_back(Level{ lv[(size_t)k].w, h, lv[(size_t)k].tx, (h + tile_h - 1) / tile_h, (int)nt });
-            band.first.push_back((size_t)lv[(size_t)k].first + (size_t)((y0 >> k) / tile_h) * lv[(size_t)k].tx);
-            band.count.push_back((size_t)bl.back().tx * bl.back().ty);
-            nt += band.count.back();
+            bl.push_back(Level{ lv[(size_t)k].w, h, lv[(size_t)k].tx, (h + tile_h - 1) / tile_h, lv[(size_t)k].first + (y0 >> k) / tile_h * lv[(size_t)k].tx });
         }
-        band.blobs.resize(nt);
         DefaultLease lease;
         int r = lease.acquire(devs[(size_t)b]);
         if (r) return r;
         mic_hip_session *s = lease.s;
-        if ((r = s->ensure(1, (size_t)tile_w * tile_h))) return r;
+        if ((r = s->ensure(1, (size_t)fmt.tw * fmt.th))) return r;
         struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;   // freed on every return path
         std::vector<DevBuf> &img = bufs.img;
         img.resize((size_t)K + 2);
@@ -514,7 +613,7 @@ int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt
             const int th = rows >> top, tw = lv[(size_t)top].w;
             if (top == K + 1) {
                 if ((r = img[(size_t)K + 1].reserve((size_t)tw * th * bpp + 64))) return r;
-                launch_downsample(s->stream, fmt, img[(size_t)K].p, bl[(size_t)K].w, img[(size_t)K + 1].p, tw, th);
+                launch_downsample(s->stream, fmt, img[(size_t)K].p, lv[(size_t)K].w, img[(size_t)K + 1].p, tw, th);
                 HIP_TRY(hipGetLastError());
             }
             if (th > 0)
@@ -522,20 +621,15 @@ int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt
                                        hipMemcpyDeviceToHost, s->stream));
             HIP_TRY(hipStreamSynchronize(s->stream));
         }
-        for (int k = 0; k <= K && r == MIC_OK; k++)
-            r = compress_level_tiles(s, img[(size_t)k].p, bl[(size_t)k], tile_w, tile_h, fmt, band.blobs.data() + bl[(size_t)k].first);
+        for (int k = 0; k <= K && r == MIC_OK; k++) r = code_run(s, img[(size_t)k].p, bl[(size_t)k], runs[(size_t)b]);
         return r;
     });
     if (rc) return rc;
-    // the top of the pyramid on devs[0]
-    std::vector<std::vector<uint8_t>> top_blobs;
-    const size_t top_first = top >= 0 ? (size_t)lv[(size_t)K + 1].first : total_tiles;
-    if (top >= 0) {
-        top_blobs.resize(total_tiles - top_first);
+    if (top >= 0) {                                                             // the top of the pyramid on devs[0]
         DefaultLease lease;
         if ((rc = lease.acquire(devs[0]))) return rc;
         mic_hip_session *s = lease.s;
-        if ((rc = s->ensure(1, (size_t)tile_w * tile_h))) return rc;
+        if ((rc = s->ensure(1, (size_t)fmt.tw * fmt.th))) return rc;
         struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;
         std::vector<DevBuf> &img = bufs.img;
         img.resize((size_t)nlev);
@@ -547,31 +641,24 @@ int wsi_compress_bands(const uint8_t *px, int width, int height, const Mic3 &fmt
             launch_downsample(s->stream, fmt, img[(size_t)i - 1].p, lv[(size_t)i - 1].w, img[(size_t)i].p, lv[(size_t)i].w, lv[(size_t)i].h);
         }
         HIP_TRY(hipGetLastError());
-        for (int i = K + 1; i < nlev && rc == MIC_OK; i++)
-            rc = compress_level_tiles(s, img[(size_t)i].p, lv[(size_t)i], tile_w, tile_h, fmt, top_blobs.data() + (lv[(size_t)i].first - top_first));
+        for (int i = K + 1; i < nlev && rc == MIC_OK; i++) rc = code_run(s, img[(size_t)i].p, lv[(size_t)i], runs[0]);
         if (rc) return rc;
     }
     // the container: every tile's length, the capacity check, the offsets; then each shard copies its runs to their place
-    std::vector<size_t> lens(total_tiles, 0);
-    for (const Band &band : B)
-        for (size_t k = 0, j = 0; k < band.first.size(); j += band.count[k], k++)
-            for (size_t t = 0; t < band.count[k]; t++) lens[band.first[k] + t] = band.blobs[j + t].size();
-    for (size_t t = 0; t < top_blobs.size(); t++) lens[top_first + t] = top_blobs[t].size();
-    std::vector<size_t> off(total_tiles + 1, 0);
+    std::vector<uint64_t> lens(total_tiles, 0);
+    for (const auto &rs : runs)
+        for (const TileRun &run : rs) std::copy(run.lens.begin(), run.lens.end(), lens.begin() + (long)run.first);
+    std::vector<uint64_t> off(total_tiles + 1, 0);
     for (size_t t = 0; t < total_tiles; t++) off[t + 1] = off[t] + lens[t];
     if (out_cap < hdr + off[total_tiles]) return MIC_ERR_CAPACITY;
-    put_mic3_index(out, width, height, tile_w, tile_h, fmt, lv, total_tiles, lens.data());
+    put_mic3_index(out, fmt, lv, lens);
     uint8_t *body = out + hdr;
     rc = run_parallel(shards, [&](int b) -> int {
-        const Band &band = B[(size_t)b];
-        for (size_t k = 0, j = 0; k < band.first.size(); j += band.count[k], k++)
-            for (size_t t = 0; t < band.count[k]; t++) memcpy(body + off[band.first[k] + t], band.blobs[j + t].data(), band.blobs[j + t].size());
-        if (b == 0)
-            for (size_t t = 0; t < top_blobs.size(); t++) memcpy(body + off[top_first + t], top_blobs[t].data(), top_blobs[t].size());
+        for (const TileRun &run : runs[(size_t)b]) memcpy(body + off[run.first], run.bytes.data(), run.bytes.size());
         return MIC_OK;
     });
     if (rc) return rc;
-    *out_len = hdr + off[total_tiles];
+    *out_len = hdr + (size_t)off[total_tiles];
     return MIC_OK;
 }
 
@@ -669,87 +756,48 @@ int mic_hip_wsi_band_plan(int width, int height, int tile_w, int tile_h, int lev
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
-// CompressWSI (wsicompress.go:27-171): 8-bit RGB (channels 3) or 8/16-bit greyscale (channels 1, little-endian samples)
+// CompressWSI (wsicompress.go:27-171): 8-bit RGB (channels 3) or 8/16-bit greyscale (channels 1, little-endian samples).
+// Bands of tile rows over the devices of mic_hip_set_devices when that gives two or more (and the call is not nested), else one band.
 int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int channels, int bits_per_sample, int tile_w, int tile_h,
                             int levels, uint8_t *out, size_t out_cap, size_t *out_len) try {
     if (!rgb || !out || !out_len || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0) return MIC_ERR_ARGS;
-    Mic3 fmt; fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);   // defaults(), wsiformat.go:86-96
-    if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
-    const size_t bpp = fmt.bpp();
-    if (tile_w == 0) tile_w = 256;                                                          // WSIOptions.defaults, wsiformat.go:86-96
-    if (tile_h == 0) tile_h = 256;
-    if ((size_t)tile_w * tile_h > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
+    Mic3 fmt;
+    int rc = wsi_options(width, height, channels, bits_per_sample, tile_w, tile_h, levels, fmt);
+    if (rc) return rc;
+    const std::vector<Level> lv = plan_levels(width, height, fmt.tw, fmt.th, levels);
     if (!cur_default()) {                                                                   // several devices: bands of tile rows
         const std::vector<int> devs = default_devices();
         if (devs.size() > 1) {
-            const std::vector<Level> lv = plan_levels(width, height, tile_w, tile_h, levels);
             std::vector<int> row_first(devs.size() + 1);
-            const int K = band_plan(height, tile_h, (int)lv.size(), (int)devs.size(), row_first.data());
+            const int K = band_plan(height, fmt.th, (int)lv.size(), (int)devs.size(), row_first.data());
             int bands = 0;
             for (size_t b = 0; b < devs.size(); b++) bands += row_first[b + 1] > row_first[b];
-            if (bands >= 2) return wsi_compress_bands(rgb, width, height, fmt, tile_w, tile_h, lv, K, row_first, devs, out, out_cap, out_len);
+            if (bands >= 2) return wsi_compress_bands(rgb, fmt, lv, K, row_first, devs, out, out_cap, out_len);
         }
     }
-    DefaultLease lease;
-    int rc = lease.acquire();
-    if (rc) return rc;
-    mic_hip_session *s = cur_default();
-    if ((rc = s->ensure(1, (size_t)tile_w * tile_h))) return rc;
-    const std::vector<Level> lv = plan_levels(width, height, tile_w, tile_h, levels);
-    const int nlev = (int)lv.size();
-    size_t total_tiles = 0;
-    for (const Level &l : lv) total_tiles += (size_t)l.tx * l.ty;
-    const size_t hdr = 48 + 20 * (size_t)nlev + 16 * total_tiles;
-    if (out_cap < hdr) return MIC_ERR_CAPACITY;
-    // pyramid on the device
-    std::vector<DevBuf> img((size_t)nlev);
-    auto cleanup = [&]() { for (auto &b : img) b.release(); };
-    if ((rc = img[0].reserve((size_t)width * height * bpp + 64))) { cleanup(); return rc; }
-    if (hipMemcpyAsync(img[0].p, rgb, (size_t)width * height * bpp, hipMemcpyHostToDevice, s->stream) != hipSuccess) { cleanup(); return MIC_ERR_DEVICE; }
-    for (int i = 1; i < nlev; i++) {
-        if ((rc = img[(size_t)i].reserve((size_t)lv[i].w * lv[i].h * bpp + 64))) { cleanup(); return rc; }
-        launch_downsample(s->stream, fmt, img[(size_t)i - 1].p, lv[i - 1].w, img[(size_t)i].p, lv[i].w, lv[i].h);
-    }
-    std::vector<std::vector<uint8_t>> tile_blobs(total_tiles);
-    for (int li = 0; li < nlev && rc == MIC_OK; li++)
-        rc = compress_level_tiles(s, img[(size_t)li].p, lv[(size_t)li], tile_w, tile_h, fmt, tile_blobs.data() + lv[(size_t)li].first);
-    cleanup();
-    if (rc) return rc;
-    size_t total = 0;
-    for (const auto &tb : tile_blobs) total += tb.size();
-    if (out_cap < hdr + total) return MIC_ERR_CAPACITY;
-    std::vector<size_t> lens(total_tiles);
-    for (size_t t = 0; t < total_tiles; t++) lens[t] = tile_blobs[t].size();
-    put_mic3_index(out, width, height, tile_w, tile_h, fmt, lv, total_tiles, lens.data());    // WriteMIC3, wsiformat.go:99-165
-    size_t off = 0;
-    for (size_t t = 0; t < total_tiles; t++) {
-        memcpy(out + hdr + off, tile_blobs[t].data(), tile_blobs[t].size());
-        off += tile_blobs[t].size();
-    }
-    *out_len = hdr + total;
-    return MIC_OK;
+    std::vector<int> row_first(2);                                                          // the default device, or the session held
+    const int K = band_plan(height, fmt.th, (int)lv.size(), 1, row_first.data());
+    return wsi_compress_bands(rgb, fmt, lv, K, row_first, std::vector<int>(1, -1), out, out_cap, out_len);
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // CompressRGB (rgbcompress.go:25-27) = compressRGBTileBlob on the whole image: one "tile" of width x height
 int mic_hip_rgb_compress(const uint8_t *rgb, int width, int height, uint8_t *out, size_t out_cap, size_t *out_len) try {
     if (!rgb || !out || !out_len || width <= 0 || height <= 0) return MIC_ERR_ARGS;
     if ((size_t)width * height > ((size_t)1 << 26)) return MIC_ERR_UNSUPPORTED;
-    Mic3 fmt; fmt.channels = 3; fmt.bps = 8; fmt.flags = 0x03;
+    Mic3 fmt; fmt.channels = 3; fmt.bps = 8; fmt.flags = 0x03; fmt.tw = width; fmt.th = height;
     DefaultLease lease;
     int rc = lease.acquire();
     if (rc) return rc;
     mic_hip_session *s = cur_default();
     if ((rc = s->ensure(1, (size_t)width * height))) return rc;
-    DevBuf img;
-    if ((rc = img.reserve((size_t)width * height * 3 + 64))) return rc;
-    if (hipMemcpyAsync(img.p, rgb, (size_t)width * height * 3, hipMemcpyHostToDevice, s->stream) != hipSuccess) { img.release(); return MIC_ERR_DEVICE; }
-    std::vector<uint8_t> blob;
-    rc = compress_level_tiles(s, img.p, Level{ width, height, 1, 1, 0 }, width, height, fmt, &blob);
-    img.release();
-    if (rc) return rc;
-    if (blob.size() > out_cap) return MIC_ERR_CAPACITY;
-    memcpy(out, blob.data(), blob.size());
-    *out_len = blob.size();
+    struct Bufs : SlabBufs { DevBuf img; ~Bufs() { img.release(); } } bufs;                // freed on every return path
+    if ((rc = bufs.img.reserve((size_t)width * height * 3 + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(bufs.img.p, rgb, (size_t)width * height * 3, hipMemcpyHostToDevice, s->stream));
+    TileRun blob;
+    if ((rc = code_level(s, fmt, bufs.img.p, Level{ width, height, 1, 1, 0 }, bufs, slab_tiles(fmt, (size_t)8 << 30), blob))) return rc;
+    if (blob.bytes.size() > out_cap) return MIC_ERR_CAPACITY;
+    memcpy(out, blob.bytes.data(), blob.bytes.size());
+    *out_len = blob.bytes.size();
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
@@ -890,15 +938,14 @@ int mic_hip_wsi_decompress_region(const uint8_t *c, size_t len, int level, int x
 }  // extern "C"
 
 // ==========================================================================================
-// MIC3 on a device-resident slide (what bench.py times for BASELINE config 5).  mic_hip_session_wsi_encode runs the pyramid, the
-// tile extraction + YCoCg-R + plane statistics and the unit codec exactly as mic_hip_wsi_compress_ex does, but the coded planes
-// never leave the device: they are appended to a store the session owns (device bytes + one host record per plane).
-// mic_hip_session_wsi_write turns the store into the MIC3 file (WriteMIC3, wsiformat.go:99-165: the only step that needs the
-// bytes on the host); mic_hip_session_wsi_decode_level decodes every tile of a level from the store into a device image.
-struct WsiPlane { uint8_t mode; uint16_t value; uint64_t off; uint32_t len; };          // mode 0 / 1: no bytes; 2: stream; 3: raw pixels
+// MIC3 on a device-resident slide (what bench.py times for BASELINE config 5).  mic_hip_session_wsi_encode runs the pyramid and the
+// tile path of mic_hip_wsi_compress_ex (encode_level), but the coded planes never leave the device: they are appended to a store
+// the session owns (device bytes + one host record per plane).  mic_hip_session_wsi_write turns the store into the MIC3 file
+// (WriteMIC3, wsiformat.go:99-165: the only step that needs the bytes on the host); mic_hip_session_wsi_decode_level decodes every
+// tile of a level from the store into a device image.
 struct mic_hip_wsi_store {
     Mic3 fmt; std::vector<Level> lv; size_t total_tiles = 0;
-    std::vector<WsiPlane> planes;                                                       // total_tiles * fmt.planes(), tile-major
+    std::vector<WsiPlane> planes;                                                       // total_tiles * fmt.planes(), tile-major; off: into bytes
     DevBuf bytes; size_t used = 0;
     int append(hipStream_t st, const void *d_src, size_t n, uint64_t *off) {            // grows by copying (rare: starts at the raw size / 2)
         if (used + n > bytes.cap) {
@@ -919,66 +966,16 @@ void mic_wsi_store_free(mic_hip_wsi_store *w) { if (w) { w->bytes.release(); del
 
 namespace {
 
-// one pyramid level into the store: as compress_level_tiles up to the unit codec, then device-to-device appends
-int store_level_tiles(mic_hip_session *s, mic_hip_wsi_store &W, const void *d_img, const Level &L) {
-    const Mic3 &fmt = W.fmt;
-    const size_t P = (size_t)fmt.planes(), npx = (size_t)fmt.tw * fmt.th;
-    const size_t per = std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), ((size_t)16 << 30) / (P * npx * 2))));
-    DevBuf &planes = s->wsi_planes, &stats = s->wsi_stats;
-    const size_t ntl = (size_t)L.tx * L.ty;
-    int rc;
-    for (size_t t0 = 0; t0 < ntl; t0 += per) {
-        const size_t nt = std::min(per, ntl - t0);
-        if ((rc = planes.reserve(nt * P * npx * 2 + 64)) || (rc = stats.reserve(nt * P * 8 + 64))) return rc;
-        std::vector<uint32_t> st(nt * P * 2);
-        for (size_t k = 0; k < nt * P; k++) { st[2 * k] = 0xFFFFFFFFu; st[2 * k + 1] = 0; }
-        HIP_TRY(hipMemcpyAsync(stats.p, st.data(), st.size() * 4, hipMemcpyHostToDevice, s->stream));
-        s->timer.reset(s->stream); s->timer.mark("k_wsi_tile_planes");
-        if (P == 3)
-            hipLaunchKernelGGL(k_wsi_tile_planes, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint8_t *)d_img, L.w, L.h,
-                               fmt.tw, fmt.th, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        else if (fmt.bps == 16)
-            hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint16_t>, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint16_t *)d_img,
-                               L.w, L.h, fmt.tw, fmt.th, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        else
-            hipLaunchKernelGGL(k_wsi_tile_plane_grey<uint8_t>, dim3(8, (unsigned)nt), dim3(256), 0, s->stream, (const uint8_t *)d_img,
-                               L.w, L.h, fmt.tw, fmt.th, L.tx, (int)t0, (uint16_t *)planes.p, (uint32_t *)stats.p);
-        s->timer.mark("end");
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(st.data(), stats.p, st.size() * 4, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        std::vector<mic_hip_unit> units; std::vector<size_t> unit_plane;
-        for (size_t p = 0; p < nt * P; p++) {
-            const uint32_t mn = st[2 * p], mx = st[2 * p + 1];
-            if (mn == mx) continue;
-            units.push_back(mic_hip_unit{ p * npx, fmt.tw, fmt.th, (uint16_t)std::max<uint32_t>(mx, 255u), 2 });   // wsicompress.go:398-402
-            unit_plane.push_back(p);
-        }
-        std::vector<uint64_t> offs(units.size() + 1, 0); std::vector<int32_t> ust(units.size()), uns(units.size());
-        const uint8_t *d_blobs = nullptr; uint64_t base = 0;
-        if (!units.empty()) {
-            if ((rc = session_encode_enqueue(s, (const uint16_t *)planes.p, units.data(), (int)units.size()))) return rc;
-            if ((rc = session_encode_finish(s, &d_blobs, offs.data(), ust.data(), uns.data()))) return rc;
-            if ((rc = W.append(s->stream, d_blobs, (size_t)offs.back(), &base))) return rc;          // every stream of the slab in one copy
-        }
-        std::vector<long> unit_of(nt * P, -1);
-        for (size_t k = 0; k < units.size(); k++) unit_of[unit_plane[k]] = (long)k;
-        for (size_t p = 0; p < nt * P; p++) {
-            WsiPlane &wp = W.planes[((size_t)L.first + t0) * P + p];
-            const uint32_t mn = st[2 * p], mx = st[2 * p + 1];
-            if (mn == mx) { wp = WsiPlane{ (uint8_t)(mn == 0 ? 0 : 1), (uint16_t)mn, 0, 0 }; continue; }
-            const long ui = unit_of[p];
-            const int32_t ustat = ust[(size_t)ui];
-            if (ustat == MIC_OK) wp = WsiPlane{ 2, 0, base + offs[(size_t)ui], (uint32_t)(offs[(size_t)ui + 1] - offs[(size_t)ui]) };
-            else if (ustat == MIC_ERR_USE_RLE || ustat == MIC_ERR_INCOMPRESSIBLE) {                     // raw fallback, :403-414
-                uint64_t o = 0;
-                if ((rc = W.append(s->stream, (uint16_t *)planes.p + p * npx, npx * 2, &o))) return rc;
-                wp = WsiPlane{ 3, 0, o, (uint32_t)(npx * 2) };
-            } else return ustat;
-        }
-        HIP_TRY(hipStreamSynchronize(s->stream));                                                    // the slab's planes are reused by the next one
-    }
-    return MIC_OK;
+// tiles per slab of the session's slide (encode and decode)
+size_t session_slab_tiles(const Mic3 &fmt) { return slab_tiles(fmt, (size_t)16 << 30); }
+
+// The store as the container's payload (compressTileBlob, wsicompress.go:334-364, for every tile in container order), built on the
+// device in s->wsi_payload: WriteMIC3 then is one transfer of it behind the header and the tile index; a multi-GPU writer gathers
+// it device to device.  tlen[t] = bytes of tile t (total_tiles entries), *total = their sum.
+int wsi_assemble(mic_hip_session *s, uint64_t *tlen, uint64_t *total) {
+    mic_hip_wsi_store &W = *s->wsi;
+    return assemble_tiles(s, W.planes.data(), W.total_tiles, (size_t)W.fmt.planes(), (uint64_t)(uintptr_t)W.bytes.p, s->wsi_payload,
+                          s->wsi_recs, tlen, total);
 }
 
 }  // namespace
@@ -988,123 +985,61 @@ extern "C" {
 int mic_hip_session_wsi_encode(mic_hip_session *s, const uint8_t *d_pixels, int width, int height, int channels, int bits_per_sample,
                                int tile_w, int tile_h, int levels, uint64_t *total_tiles, uint64_t *compressed_bytes) try {
     if (!s || !d_pixels || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0) return MIC_ERR_ARGS;
-    Mic3 fmt; fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);
-    if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
-    if (tile_w == 0) tile_w = 256;
-    if (tile_h == 0) tile_h = 256;
-    if ((size_t)tile_w * tile_h > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
-    int rc = s->activate();
+    Mic3 fmt;
+    int rc = wsi_options(width, height, channels, bits_per_sample, tile_w, tile_h, levels, fmt);
     if (rc) return rc;
-    if ((rc = s->ensure(1, (size_t)tile_w * tile_h))) return rc;
+    if ((rc = s->activate())) return rc;
+    if ((rc = s->ensure(1, (size_t)fmt.tw * fmt.th))) return rc;
     if (!s->wsi) s->wsi = new mic_hip_wsi_store();
     mic_hip_wsi_store &W = *s->wsi;
-    fmt.w = width; fmt.h = height; fmt.tw = tile_w; fmt.th = tile_h;
-    W.fmt = fmt; W.lv = plan_levels(width, height, tile_w, tile_h, levels);
+    W.fmt = fmt; W.lv = plan_levels(width, height, fmt.tw, fmt.th, levels);
     W.fmt.nlev = (int)W.lv.size();
     W.total_tiles = 0;
     for (const Level &l : W.lv) W.total_tiles += (size_t)l.tx * l.ty;
     W.fmt.total = W.total_tiles;
-    W.planes.assign(W.total_tiles * (size_t)fmt.planes(), WsiPlane{ 0, 0, 0, 0 });
+    const size_t P = (size_t)fmt.planes();
+    W.planes.assign(W.total_tiles * P, WsiPlane{ 0, 0, 0, 0 });
     W.used = 0;
     const size_t bpp = fmt.bpp();
     if ((rc = W.bytes.reserve((size_t)width * height * bpp / 2 + (1 << 20)))) return rc;
     // pyramid on the device (Downsample2xRGB / Downsample2xGrey, wsipyramid.go:10-55); level 0 is the caller's buffer
     std::vector<DevBuf> &img = s->wsi_pyr;
     if (img.size() < W.lv.size()) img.resize(W.lv.size());
-    const void *prev = d_pixels;
+    std::vector<const void *> lvl(W.lv.size(), d_pixels);
     for (size_t i = 1; i < W.lv.size(); i++) if ((rc = img[i].reserve((size_t)W.lv[i].w * W.lv[i].h * bpp + 64))) return rc;
     s->timer.reset(s->stream); s->timer.mark("k_wsi_downsample");
     for (size_t i = 1; i < W.lv.size(); i++) {
-        if (channels == 3)
-            hipLaunchKernelGGL(k_wsi_downsample, dim3(1024), dim3(256), 0, s->stream, (const uint8_t *)prev, W.lv[i - 1].w, (uint8_t *)img[i].p, W.lv[i].w, W.lv[i].h);
-        else if (bits_per_sample == 16)
-            hipLaunchKernelGGL(k_wsi_downsample_grey<uint16_t>, dim3(1024), dim3(256), 0, s->stream, (const uint16_t *)prev, W.lv[i - 1].w, (uint16_t *)img[i].p, W.lv[i].w, W.lv[i].h);
-        else
-            hipLaunchKernelGGL(k_wsi_downsample_grey<uint8_t>, dim3(1024), dim3(256), 0, s->stream, (const uint8_t *)prev, W.lv[i - 1].w, (uint8_t *)img[i].p, W.lv[i].w, W.lv[i].h);
-        prev = img[i].p;
+        launch_downsample(s->stream, fmt, lvl[i - 1], W.lv[i - 1].w, img[i].p, W.lv[i].w, W.lv[i].h);
+        lvl[i] = img[i].p;
     }
     s->timer.mark("end");
     HIP_TRY(hipGetLastError());
-    for (size_t i = 0; i < W.lv.size(); i++)
-        if ((rc = store_level_tiles(s, W, i == 0 ? (const void *)d_pixels : (const void *)img[i].p, W.lv[i]))) return rc;
+    // each slab's streams go into the store in one copy, its raw planes one by one; the records then point into the store
+    for (size_t i = 0; i < W.lv.size(); i++) {
+        const Level &L = W.lv[i];
+        rc = encode_level(s, fmt, lvl[i], L, s->wsi_planes, s->wsi_stats, session_slab_tiles(fmt), [&](const Slab &sl) -> int {
+            uint64_t base = 0;
+            int r;
+            if (sl.stream_bytes && (r = W.append(s->stream, sl.streams, (size_t)sl.stream_bytes, &base))) return r;
+            for (size_t p = 0; p < sl.planes.size(); p++) {
+                WsiPlane wp = sl.planes[p];
+                if (wp.mode == 2) wp.off = base + (wp.off - (uint64_t)(uintptr_t)sl.streams);
+                else if (wp.mode == 3 && (r = W.append(s->stream, (const void *)(uintptr_t)wp.off, (size_t)wp.len, &wp.off))) return r;
+                W.planes[((size_t)L.first + sl.t0) * P + p] = wp;
+            }
+            HIP_TRY(hipStreamSynchronize(s->stream));                                                    // the slab's planes are reused by the next one
+            return MIC_OK;
+        });
+        if (rc) return rc;
+    }
     if (total_tiles) *total_tiles = W.total_tiles;
     if (compressed_bytes) {                                                     // size of the file mic_hip_session_wsi_write would produce
-        uint64_t n = 48 + 20 * (uint64_t)W.lv.size() + 16 * (uint64_t)W.total_tiles;
-        const size_t P = (size_t)fmt.planes();
-        for (size_t t = 0; t < W.total_tiles; t++) {
-            if (P == 3) n += 12;
-            for (size_t p = 0; p < P; p++) { const WsiPlane &wp = W.planes[t * P + p]; n += wp.mode == 0 ? 1 : wp.mode == 1 ? 3 : 1 + (uint64_t)wp.len; }
-        }
+        uint64_t n = 48 + 20 * (uint64_t)W.lv.size() + 16 * (uint64_t)W.total_tiles + (P == 3 ? 12 * (uint64_t)W.total_tiles : 0);
+        for (const WsiPlane &wp : W.planes) n += plane_bytes(wp);
         *compressed_bytes = n;
     }
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
-
-// WriteMIC3 (wsiformat.go:99-165) around the store: header, level table, tile table, tile blobs ([Ylen][Colen][Cglen] + planes,
-// wsicompress.go:341-363; grey: the bare plane).  One device-to-host copy of the store's bytes.
-// The container's payload -- every tile blob, in container order -- is put together on the DEVICE: the plane records are host
-// data (mode, constant, offset and length of each coded plane), so the host lays the tiles out (a prefix sum over 16 bytes per
-// plane) and one kernel copies every plane's bytes from the store to its place, with the mode byte in front and, for RGB, the
-// tile's three plane lengths (compressTileBlob, wsicompress.go:334-364).  WriteMIC3 then is one transfer of the payload straight
-// into the caller's buffer behind the header and the tile index; a multi-GPU writer gathers the payload device to device.
-struct WsiRec { uint64_t src, dst; uint32_t len; uint32_t mode_value; };          // mode_value = mode | value << 8
-__global__ void __launch_bounds__(256) k_wsi_assemble(const WsiRec *recs, int P, const uint8_t *store, uint8_t *payload) {
-    const size_t t = blockIdx.x;
-    typedef uint32_t wv4 __attribute__((ext_vector_type(4)));
-    typedef wv4 WQ __attribute__((aligned(1)));
-    for (int p = 0; p < P; p++) {
-        const WsiRec r = recs[t * (size_t)P + (size_t)p];
-        const uint32_t mode = r.mode_value & 0xFFu, value = r.mode_value >> 8;
-        uint8_t *d = payload + r.dst;
-        const uint32_t plen = mode == 0 ? 1u : mode == 1 ? 3u : 1u + r.len;
-        if (threadIdx.x == 0) {
-            d[0] = (uint8_t)mode;
-            if (mode == 1) { d[1] = (uint8_t)value; d[2] = (uint8_t)(value >> 8); }
-            if (P == 3) {                                                               // [Y_len][Co_len][Cg_len], u32 LE, in front of the tile's planes
-                uint8_t *h = payload + recs[t * 3].dst - 12 + 4 * p;
-                h[0] = (uint8_t)plen; h[1] = (uint8_t)(plen >> 8); h[2] = (uint8_t)(plen >> 16); h[3] = (uint8_t)(plen >> 24);
-            }
-        }
-        if (mode >= 2) {
-            const uint8_t *sp = store + r.src; uint8_t *dp = d + 1;
-            const uint32_t nv = r.len / 16;
-            for (uint32_t i = threadIdx.x; i < nv; i += 256) *(WQ *)(dp + (size_t)i * 16) = *(const WQ *)(sp + (size_t)i * 16);
-            if (threadIdx.x < (r.len & 15u)) dp[(size_t)nv * 16 + threadIdx.x] = sp[(size_t)nv * 16 + threadIdx.x];
-        }
-    }
-}
-
-// lays the payload out and builds it in s->wsi_payload; tlen[t] = bytes of tile t, *total = their sum
-static int wsi_assemble(mic_hip_session *s, std::vector<uint64_t> &tlen, uint64_t *total_out) {
-    mic_hip_wsi_store &W = *s->wsi;
-    const size_t P = (size_t)W.fmt.planes();
-    std::vector<WsiRec> recs(W.total_tiles * P);
-    tlen.assign(W.total_tiles, 0);
-    uint64_t off = 0;
-    for (size_t t = 0; t < W.total_tiles; t++) {
-        const uint64_t t0 = off;
-        if (P == 3) off += 12;
-        for (size_t p = 0; p < P; p++) {
-            const WsiPlane &wp = W.planes[t * P + p];
-            const uint64_t n = wp.mode == 0 ? 1 : wp.mode == 1 ? 3 : 1 + (uint64_t)wp.len;
-            recs[t * P + p] = WsiRec{ wp.off, off, wp.mode >= 2 ? wp.len : 0u, (uint32_t)wp.mode | ((uint32_t)wp.value << 8) };
-            off += n;
-        }
-        tlen[t] = off - t0;
-    }
-    *total_out = off;
-    int rc;
-    if ((rc = s->wsi_payload.reserve((size_t)off + 64))) return rc;
-    if ((rc = s->wsi_recs.reserve(recs.size() * sizeof(WsiRec) + 64))) return rc;
-    if (!recs.empty()) {
-        HIP_TRY(hipMemcpyAsync(s->wsi_recs.p, recs.data(), recs.size() * sizeof(WsiRec), hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(k_wsi_assemble, dim3((unsigned)W.total_tiles), dim3(256), 0, s->stream, (const WsiRec *)s->wsi_recs.p, (int)P,
-                           (const uint8_t *)W.bytes.p, (uint8_t *)s->wsi_payload.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));                                       // (recs is a stack-scope vector)
-    }
-    return MIC_OK;
-}
 
 // The store as the container's payload, on the device: *d_payload (valid until the session's next wsi call), its size, and the
 // byte length of every tile in container order (tile_lens[cap >= total tiles], host).  What a multi-GPU writer gathers.
@@ -1114,42 +1049,25 @@ int mic_hip_session_wsi_payload(mic_hip_session *s, const uint8_t **d_payload, u
     if (rc) return rc;
     if (cap < s->wsi->total_tiles) return MIC_ERR_CAPACITY;
     if ((size_t)kMaxGridX < s->wsi->total_tiles) return MIC_ERR_UNSUPPORTED;
-    std::vector<uint64_t> tlen; uint64_t total = 0;
-    if ((rc = wsi_assemble(s, tlen, &total))) return rc;
-    for (size_t t = 0; t < tlen.size(); t++) tile_lens[t] = tlen[t];
-    *d_payload = (const uint8_t *)s->wsi_payload.p; *payload_bytes = total;
+    if ((rc = wsi_assemble(s, tile_lens, payload_bytes))) return rc;
+    *d_payload = (const uint8_t *)s->wsi_payload.p;
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
+// WriteMIC3 (wsiformat.go:99-165) around the store: one device-to-host copy of the assembled payload, then header, level table and
+// tile index in front of it
 int mic_hip_session_wsi_write(mic_hip_session *s, uint8_t *out, size_t out_cap, size_t *out_len) try {
     if (!s || !out || !out_len || !s->wsi) return MIC_ERR_ARGS;
     int rc = s->activate();
     if (rc) return rc;
     mic_hip_wsi_store &W = *s->wsi;
     if ((size_t)kMaxGridX < W.total_tiles) return MIC_ERR_UNSUPPORTED;
-    const size_t nlev = W.lv.size();
-    const size_t hdr = 48 + 20 * nlev + 16 * W.total_tiles;
-    std::vector<uint64_t> tlen; uint64_t total = 0;
-    if ((rc = wsi_assemble(s, tlen, &total))) return rc;
+    const size_t hdr = 48 + 20 * W.lv.size() + 16 * W.total_tiles;
+    std::vector<uint64_t> tlen(W.total_tiles); uint64_t total = 0;
+    if ((rc = wsi_assemble(s, tlen.data(), &total))) return rc;
     if (out_cap < hdr + total) return MIC_ERR_CAPACITY;
-    if ((rc = micapi::host_copy(s->device, s->wsi_payload.p, out + hdr, (size_t)total, false))) return rc;   // (the header is written meanwhile? no: after -- it is 0.4 MB)
-    memset(out, 0, hdr);
-    memcpy(out, "MIC3", 4); put_u32(out + 4, 1); put_u32(out + 8, (uint32_t)W.fmt.w); put_u32(out + 12, (uint32_t)W.fmt.h);
-    put_u32(out + 16, (uint32_t)W.fmt.tw); put_u32(out + 20, (uint32_t)W.fmt.th);
-    out[24] = (uint8_t)W.fmt.channels; out[25] = 0; out[26] = (uint8_t)W.fmt.bps; out[27] = (uint8_t)W.fmt.flags;
-    out[28] = (uint8_t)nlev; out[29] = (uint8_t)(nlev >> 8);
-    put_u64(out + 32, (uint64_t)W.total_tiles);
-    for (size_t i = 0; i < nlev; i++) {
-        uint8_t *ld = out + 48 + 20 * i;
-        put_u32(ld, (uint32_t)W.lv[i].w); put_u32(ld + 4, (uint32_t)W.lv[i].h); put_u32(ld + 8, (uint32_t)W.lv[i].tx);
-        put_u32(ld + 12, (uint32_t)W.lv[i].ty); put_u32(ld + 16, (uint32_t)W.lv[i].first);
-    }
-    uint64_t off = 0;
-    for (size_t t = 0; t < W.total_tiles; t++) {
-        uint8_t *e = out + 48 + 20 * nlev + 16 * t;
-        put_u64(e, off); put_u64(e + 8, tlen[t]);
-        off += tlen[t];
-    }
+    if ((rc = micapi::host_copy(s->device, s->wsi_payload.p, out + hdr, (size_t)total, false))) return rc;
+    put_mic3_index(out, W.fmt, W.lv, tlen);
     *out_len = hdr + (size_t)total;
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
@@ -1163,53 +1081,18 @@ int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_p
     if (level < 0 || level >= (int)W.lv.size()) return MIC_ERR_ARGS;
     const Mic3 &m = W.fmt;
     const Level &L = W.lv[(size_t)level];
-    const size_t P = (size_t)m.planes(), bpp = m.bpp(), npx = (size_t)m.tw * m.th;
-    if ((size_t)L.w * L.h * bpp > out_cap) return MIC_ERR_CAPACITY;
-    const size_t ntl = (size_t)L.tx * L.ty;
-    const size_t per = std::min<size_t>(kMaxGridY / P, std::max<size_t>(1, std::min<size_t>(batch_units_for(npx, P), ((size_t)16 << 30) / (P * npx * 2))));
-    DevBuf &planes = s->wsi_planes, &aux = s->wsi_stats;
+    const size_t P = (size_t)m.planes();
+    if ((size_t)L.w * L.h * m.bpp() > out_cap) return MIC_ERR_CAPACITY;
+    const size_t ntl = (size_t)L.tx * L.ty, per = session_slab_tiles(m);
     for (size_t t0 = 0; t0 < ntl; t0 += per) {
         const size_t nt = std::min(per, ntl - t0);
-        if ((rc = planes.reserve(nt * P * npx * 2 + 64))) return rc;
-        std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<uint2> fills; std::vector<int4> place(nt);
-        uint16_t *dp = (uint16_t *)planes.p;
+        std::vector<int4> place(nt);
         for (size_t k = 0; k < nt; k++) {
-            const size_t t = t0 + k; const int tx = (int)(t % (size_t)L.tx), ty = (int)(t / (size_t)L.tx);
+            const int tx = (int)((t0 + k) % (size_t)L.tx), ty = (int)((t0 + k) / (size_t)L.tx);
             place[k] = make_int4(tx * m.tw, ty * m.th, std::min(m.tw, L.w - tx * m.tw), std::min(m.th, L.h - ty * m.th));
-            for (size_t p = 0; p < P; p++) {
-                const WsiPlane &wp = W.planes[((size_t)L.first + t) * P + p];
-                const size_t plane = k * P + p;
-                if (wp.mode <= 1) fills.push_back(make_uint2((uint32_t)plane, wp.mode ? wp.value : 0u));
-                else if (wp.mode == 2) { units.push_back(mic_hip_unit{ plane * npx, m.tw, m.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); }
-                else HIP_TRY(hipMemcpyAsync(dp + plane * npx, (const char *)W.bytes.p + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
-            }
         }
-        const size_t aux_bytes = fills.size() * sizeof(uint2) + nt * sizeof(int4) + 64;
-        if ((rc = aux.reserve(aux_bytes))) return rc;
-        int4 *d_place = (int4 *)aux.p; uint2 *d_fill = (uint2 *)((char *)aux.p + nt * sizeof(int4));
-        HIP_TRY(hipMemcpyAsync(d_place, place.data(), nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
-        if (!fills.empty()) {
-            HIP_TRY(hipMemcpyAsync(d_fill, fills.data(), fills.size() * sizeof(uint2), hipMemcpyHostToDevice, s->stream));
-            s->timer.reset(s->stream); s->timer.mark("k_fill_planes");
-            for (size_t f0 = 0; f0 < fills.size(); f0 += 65535)
-                hipLaunchKernelGGL(k_fill_planes, dim3(4, (unsigned)std::min<size_t>(65535, fills.size() - f0)), dim3(256), 0, s->stream, dp, npx, (const uint2 *)d_fill + f0);
-        }
-        if (!units.empty()) {
-            if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)W.bytes.p, begins.data(), ends.data(), units.data(), (int)units.size(), dp))) return rc;
-            std::vector<int32_t> st(units.size());
-            if ((rc = session_decode_finish(s, st.data()))) return rc;
-            for (int32_t v : st) if (v != MIC_OK) return v;
-        }
-        s->timer.reset(s->stream); s->timer.mark("k_wsi_planes_to_pixels");
-        if (P == 3)
-            hipLaunchKernelGGL(k_wsi_planes_to_rgb, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th, (const int4 *)d_place, d_pixels_out, L.w);
-        else if (m.bps == 16)
-            hipLaunchKernelGGL(k_wsi_plane_to_grey<uint16_t>, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th, (const int4 *)d_place, (uint16_t *)d_pixels_out, L.w);
-        else
-            hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, dim3(16, (unsigned)nt), dim3(256), 0, s->stream, dp, m.tw, m.th, (const int4 *)d_place, d_pixels_out, L.w);
-        s->timer.mark("end");
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        if ((rc = decode_planes(s, m, (const uint8_t *)W.bytes.p, W.planes.data() + ((size_t)L.first + t0) * P, nt, place.data(),
+                                s->wsi_planes, s->wsi_stats, d_pixels_out, L.w))) return rc;
     }
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
@@ -1303,6 +1186,11 @@ __global__ void __launch_bounds__(256) k_wsi_band_pyramid(BandPyr P) {
         __syncthreads();                                        // level k is complete in this strip before level k + 1 reads it
     }
 }
+void launch_band_pyramid(hipStream_t st, const Mic3 &fmt, unsigned grid, const BandPyr &P) {
+    if (fmt.planes() == 3) hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 3>), dim3(grid), dim3(256), 0, st, P);
+    else if (fmt.bps == 16) hipLaunchKernelGGL((k_wsi_band_pyramid<uint16_t, 1>), dim3(grid), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 1>), dim3(grid), dim3(256), 0, st, P);
+}
 
 }  // namespace
 
@@ -1313,15 +1201,15 @@ struct mic_hip_wsi_writer {
     std::vector<Level> lv; size_t total_tiles = 0, hdr = 0;
     int B = 0, R = 0, strip = 0, nbuf = 0;        // band tile rows, band rows, columns per workgroup, levels the buffers hold
     mic_hip_session *s = nullptr;
-    DevBuf pyr, planes, stats;
-    TileBufs bufs{ nullptr, nullptr, 1 };
+    DevBuf pyr;
+    SlabBufs bufs; size_t per = 1;                     // the tile path's buffers, tiles per slab
     std::vector<size_t> lvoff; std::vector<int> cap;   // per level: byte offset of its buffer in pyr, its slots
     std::vector<int> base, made, coded;                // per level: row in slot 0, rows made, rows coded
     std::vector<uint64_t> lens;                        // every tile's blob length (level 0's as they are coded)
     uint64_t l0_bytes = 0;                             // level-0 blob bytes written so far
-    std::vector<std::vector<uint8_t>> upper;           // blobs of levels >= 1, held until finish
+    TileRun l0;                                        // the band's level-0 blobs on their way to the sink
+    std::vector<TileRun> upper;                        // blobs of levels >= 1, held until finish
     size_t upper_bytes = 0, host_peak = 0;
-    std::vector<uint8_t> staging;
     uint64_t device_bytes = 0, bands = 0;
     double pyr_ms = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1329,7 +1217,7 @@ struct mic_hip_wsi_writer {
     ~mic_hip_wsi_writer() {
         if (s) {
             (void)s->activate();
-            pyr.release(); planes.release(); stats.release();
+            pyr.release(); bufs.release();
             if (ev0) (void)hipEventDestroy(ev0);
             if (ev1) (void)hipEventDestroy(ev1);
             mic_hip_session_destroy(s);
@@ -1338,26 +1226,24 @@ struct mic_hip_wsi_writer {
     size_t row_bytes(int k) const { return (size_t)(width >> k) * fmt.bpp(); }
     uint8_t *slot(int k, int row) { return (uint8_t *)pyr.p + lvoff[(size_t)k] + (size_t)(row - base[(size_t)k]) * row_bytes(k); }
     int sink(uint64_t off, const uint8_t *p, size_t n) { return n == 0 || write(user, off, p, n) == 0 ? MIC_OK : MIC_ERR_IO; }
-    void note_host() { host_peak = std::max(host_peak, upper_bytes + lens.size() * 16 + staging.capacity()); }
+    void note_host() { host_peak = std::max(host_peak, upper_bytes + lens.size() * 16 + l0.bytes.capacity()); }
 
     // level k codes `rows` rows from `coded` on (whole tile rows, or the rest of the level); level 0's blobs go to the sink
     int code_rows(int k, int rows) {
         const Level &G = lv[(size_t)k];
-        const int ntr = (rows + th - 1) / th;
-        const Level band{ G.w, rows, G.tx, ntr, 0 };
-        std::vector<std::vector<uint8_t>> blobs((size_t)ntr * G.tx);
-        int rc = compress_level_tiles(s, slot(k, coded[(size_t)k]), band, tw, th, fmt, blobs.data(), &bufs);
+        const Level band{ G.w, rows, G.tx, (rows + th - 1) / th, 0 };
+        TileRun up, &run = k == 0 ? l0 : up;
+        run.first = (size_t)G.first + (size_t)(coded[(size_t)k] / th) * G.tx; run.bytes.clear(); run.lens.clear();
+        int rc = code_level(s, fmt, slot(k, coded[(size_t)k]), band, bufs, per, run);
         if (rc) return rc;
-        const size_t first = (size_t)G.first + (size_t)(coded[(size_t)k] / th) * G.tx;
-        for (size_t t = 0; t < blobs.size(); t++) lens[first + t] = blobs[t].size();
+        std::copy(run.lens.begin(), run.lens.end(), lens.begin() + (long)run.first);
         if (k == 0) {
-            staging.clear();
-            for (auto &b : blobs) staging.insert(staging.end(), b.begin(), b.end());
             note_host();
-            if ((rc = sink(hdr + l0_bytes, staging.data(), staging.size()))) return rc;
-            l0_bytes += staging.size();
+            if ((rc = sink(hdr + l0_bytes, l0.bytes.data(), l0.bytes.size()))) return rc;
+            l0_bytes += l0.bytes.size();
         } else {
-            for (size_t t = 0; t < blobs.size(); t++) { upper_bytes += blobs[t].size(); upper[first - lv[1].first + t].swap(blobs[t]); }
+            upper_bytes += up.bytes.size();
+            upper.push_back(std::move(up));
             note_host();
         }
         coded[(size_t)k] += rows;
@@ -1390,9 +1276,7 @@ struct mic_hip_wsi_writer {
         if (any) {
             const unsigned grid = (unsigned)((width + strip - 1) / strip);
             HIP_TRY(hipEventRecord(ev0, s->stream));
-            if (fmt.planes() == 3) hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 3>), dim3(grid), dim3(256), 0, s->stream, P);
-            else if (fmt.bps == 16) hipLaunchKernelGGL((k_wsi_band_pyramid<uint16_t, 1>), dim3(grid), dim3(256), 0, s->stream, P);
-            else hipLaunchKernelGGL((k_wsi_band_pyramid<uint8_t, 1>), dim3(grid), dim3(256), 0, s->stream, P);
+            launch_band_pyramid(s->stream, fmt, grid, P);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ev1, s->stream));
         }
@@ -1453,11 +1337,10 @@ int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sa
                             int band_tile_rows, mic_hip_write_fn write, void *user, mic_hip_wsi_writer **out) try {
     if (!write || !out || width <= 0 || height <= 0 || tile_w < 0 || tile_h < 0 || band_tile_rows < 0) return MIC_ERR_ARGS;
     *out = nullptr;
-    Mic3 fmt; fmt.channels = channels; fmt.bps = bits_per_sample; fmt.flags = 0x01 | (channels == 3 ? 0x02 : 0);   // as mic_hip_wsi_compress_ex
-    if (!fmt.supported()) return MIC_ERR_UNSUPPORTED;
-    if (tile_w == 0) tile_w = 256;
-    if (tile_h == 0) tile_h = 256;
-    if ((size_t)tile_w * tile_h > ((size_t)1 << 26) || levels > 32) return MIC_ERR_UNSUPPORTED;
+    Mic3 fmt;
+    int rc = wsi_options(width, height, channels, bits_per_sample, tile_w, tile_h, levels, fmt);
+    if (rc) return rc;
+    tile_w = fmt.tw; tile_h = fmt.th;
     const size_t bpp = fmt.bpp(), P = (size_t)fmt.planes(), npx = (size_t)tile_w * tile_h;
     const size_t tiles_x = ((size_t)width + tile_w - 1) / tile_w;
     if ((size_t)width * bpp * tile_h > ((size_t)1 << 31)) return MIC_ERR_UNSUPPORTED;    // one tile row of level 0 under 2 GiB
@@ -1468,7 +1351,7 @@ int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sa
     for (const Level &l : w->lv) w->total_tiles += (size_t)l.tx * l.ty;
     w->hdr = 48 + 20 * w->lv.size() + 16 * w->total_tiles;
     int dev = default_devices()[0];
-    int rc = check_device(dev);
+    rc = check_device(dev);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(dev));
     // B: one band fills a sub-batch of the unit codec, at most 256 MiB of level-0 pixels
@@ -1496,16 +1379,15 @@ int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sa
     if ((rc = mic_hip_session_create_on(dev, &w->s, (int)(per * P), npx))) return rc;
     mic_hip_session *s = w->s;
     if ((rc = w->pyr.reserve(bytes + 64))) return rc;
-    if ((rc = w->planes.reserve(per * P * npx * 2 + 64))) return rc;
-    if ((rc = w->stats.reserve(per * P * 8 + 64))) return rc;
-    w->bufs = TileBufs{ &w->planes, &w->stats, per };
+    if ((rc = w->bufs.planes.reserve(per * P * npx * 2 + 64))) return rc;
+    if ((rc = w->bufs.stats.reserve(per * P * 8 + 64))) return rc;
+    w->per = per;
     HIP_TRY(hipEventCreate(&w->ev0));
     HIP_TRY(hipEventCreate(&w->ev1));
     const size_t nl = w->lv.size();
     w->base.assign(nl, -1); w->made.assign(nl, 0); w->coded.assign(nl, 0);
     w->lens.assign(w->total_tiles, 0);
-    if (nl > 1) w->upper.resize(w->total_tiles - (size_t)w->lv[1].first);
-    w->device_bytes = w->pyr.cap + w->planes.cap + w->stats.cap + s->reserved_bytes();
+    w->device_bytes = w->pyr.cap + w->bufs.planes.cap + w->bufs.stats.cap + s->reserved_bytes();
     w->note_host();
     *out = w.release();
     return MIC_OK;
@@ -1535,14 +1417,15 @@ int mic_hip_wsi_writer_finish(mic_hip_wsi_writer *w, uint64_t *file_len) try {
     if (w->err) return w->err;
     if (w->done || w->made[0] != w->height) return MIC_ERR_ARGS;
     for (size_t k = 0; k < w->lv.size(); k++) if (w->coded[k] != w->lv[k].h) { w->err = MIC_ERR_INTERNAL; return w->err; }
-    // the upper levels' blobs behind level 0's, then header, level table and tile index (WriteMIC3, wsiformat.go:99-165) at 0
+    // the upper levels' blobs behind level 0's in file order, then header, level table and tile index (WriteMIC3,
+    // wsiformat.go:99-165) at 0
+    std::sort(w->upper.begin(), w->upper.end(), [](const TileRun &a, const TileRun &b) { return a.first < b.first; });
     uint64_t off = w->hdr + w->l0_bytes;
     int rc = MIC_OK;
-    for (size_t t = 0; t < w->upper.size() && rc == MIC_OK; t++) { rc = w->sink(off, w->upper[t].data(), w->upper[t].size()); off += w->upper[t].size(); }
+    for (size_t r = 0; r < w->upper.size() && rc == MIC_OK; r++) { rc = w->sink(off, w->upper[r].bytes.data(), w->upper[r].bytes.size()); off += w->upper[r].bytes.size(); }
     if (rc == MIC_OK) {
-        std::vector<size_t> lens(w->lens.begin(), w->lens.end());
         std::vector<uint8_t> head(w->hdr);
-        put_mic3_index(head.data(), w->width, w->height, w->tw, w->th, w->fmt, w->lv, w->total_tiles, lens.data());
+        put_mic3_index(head.data(), w->fmt, w->lv, w->lens);
         rc = w->sink(0, head.data(), head.size());
     }
     if (rc) { w->err = rc; return rc; }

@@ -66,10 +66,10 @@ def test_config5_wsi_8192_matches_oracle(mic, mico, synth, gpu_ready):
 
 
 def _box2(a):
-    """Downsample2xRGB (wsipyramid.go:10-32)"""
+    """Downsample2xRGB / Downsample2xGrey (wsipyramid.go:10-55)"""
     h, w = a.shape[0] // 2 * 2, a.shape[1] // 2 * 2
-    b = a[:h, :w].astype(np.uint16)
-    return ((b[0::2, 0::2] + b[0::2, 1::2] + b[1::2, 0::2] + b[1::2, 1::2] + 2) // 4).astype(np.uint8)
+    b = a[:h, :w].astype(np.uint32)
+    return ((b[0::2, 0::2] + b[0::2, 1::2] + b[1::2, 0::2] + b[1::2, 1::2] + 2) // 4).astype(a.dtype)
 
 
 def test_config5_wsi_32768_slide(mic, mico, synth, gpu_ready):
@@ -157,6 +157,54 @@ def test_session_wsi_device_resident(mic, mico, synth, gpu_ready):
         d_out = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
         sess.wsi_decode_level(k, d_out.data_ptr(), d_out.numel())
         assert np.array_equal(d_out.cpu().numpy(), img), f"level {k}"
+        img = _box2(img)
+    sess.close()
+
+
+def _plane_modes(c):
+    """the mode byte of every plane of a MIC3 file (compressTileBlob, wsicompress.go:334-370), counted: [zero, constant, stream, raw]"""
+    nl, total, ch = c[28] | (c[29] << 8), int.from_bytes(c[32:40], "little"), c[24]
+    data_off = 48 + 20 * nl + 16 * total
+    modes = []
+    for t in range(total):
+        e = 48 + 20 * nl + 16 * t
+        b = c[data_off + int.from_bytes(c[e:e + 8], "little"):]
+        if ch == 1:
+            modes.append(b[0])
+        else:
+            l0, l1 = int.from_bytes(b[0:4], "little"), int.from_bytes(b[4:8], "little")
+            modes += [b[12], b[12 + l0], b[12 + l0 + l1]]
+    return np.bincount(modes, minlength=4).tolist()
+
+
+@pytest.mark.parametrize("case", ["grey8", "grey16", "grey16_raw"])
+def test_session_wsi_greyscale_and_raw_planes(mic, mico, synth, gpu_ready, case):
+    """The session path beside the RGB slide above: 8- and 16-bit greyscale, and a 16-bit slide with ramp tiles that the unit codec
+    declines (raw planes, wsicompress.go:403-414).  Store, container and level decode against the oracle and compress_wsi."""
+    torch = pytest.importorskip("torch")
+    from test_oracle_wavelet_wsi import _grey_slide
+    W, H, bits = 1100, 700, 8 if case == "grey8" else 16
+    slide = _grey_slide(synth, W, H, bits, seed=21)
+    if case == "grey16_raw":
+        yy, xx = np.mgrid[0:256, 0:256]
+        slide[0:256, 256:512] = slide[256:512, 768:1024] = (yy * 256 + xx + 1).astype(np.uint16)
+    rc, want = mico.wsi_compress_grey(slide)
+    assert rc == 0
+    modes = _plane_modes(want)
+    assert modes[2] > 0 and (modes[3] >= 2 if case == "grey16_raw" else modes[3] == 0), modes
+    d_px = torch.from_numpy(slide.view(np.int16 if bits == 16 else np.uint8).copy()).cuda()
+    sess = mic.Session(1, 256 * 256)
+    tiles, nbytes = sess.wsi_encode(d_px.data_ptr(), W, H, channels=1, bits_per_sample=bits)
+    assert nbytes == len(want)
+    assert sess.wsi_write() == want
+    assert mic.compress_wsi(slide, W, H, channels=1, bits_per_sample=bits) == want
+    lv = sess.wsi_levels()
+    assert lv[0] == (W, H) and tiles == sum(((w + 255) // 256) * ((h + 255) // 256) for w, h in lv)
+    img = slide
+    for k, (w, h) in enumerate(lv):
+        d_out = torch.zeros((h, w), dtype=torch.int16 if bits == 16 else torch.uint8, device="cuda")
+        sess.wsi_decode_level(k, d_out.data_ptr(), d_out.numel() * d_out.element_size())
+        assert np.array_equal(d_out.cpu().numpy().view(slide.dtype), img), f"level {k}"
         img = _box2(img)
     sess.close()
 
