@@ -55,7 +55,7 @@ extern "C" {
  * one session per device with mic_hip_session_create_on and uses the session entry points. */
 int mic_hip_set_device(int device);
 /* SEVERAL devices for the batch entry points below (mic_hip_compress_batch / _decompress_batch, mic_hip_pics_compress_batch /
- * _decompress_batch, mic_hip_mic2_compress / _decompress, mic_hip_wavelet_v2_compress_batch / _decompress_batch) and for the MIC3
+ * _decompress_batch, mic_hip_mic2_compress / _decompress, mic_hip_wavelet_v2_compress_batch / _decompress_batch / _decompress_level_batch) and for the MIC3
  * calls mic_hip_wsi_compress / _compress_ex (bands of tile rows, see there), mic_hip_wsi_decompress_level and
  * mic_hip_wsi_decompress_region (tile rows; a region of two tile rows or more): a call's jobs are cut into one contiguous shard per listed device,
  * balanced by pixels -- the static assignment of the reference's fan-outs (parallelstrips.go:77-93, multiframecompress.go:186-209,
@@ -301,6 +301,21 @@ int mic_hip_wavelet_v2_compress_batch(const uint16_t *frames, int nframes, int r
 int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_t *lens, int nframes,
                                         uint16_t *pixels_out, size_t out_cap_px, int32_t *status);
 
+/* At reduced resolution (no reference counterpart; the subband scan makes the format resolution-scalable).  For 0 <= level <= levels
+ * (the header's level count): nr[0] = rows, nr[l + 1] = (nr[l] + 1) / 2, nc alike; the image at `level` is the nr[level] x nc[level]
+ * LL band the forward transform holds after `level` levels, saturated to [0, 65535] (level 0: the decoded image, byte for byte).
+ * It needs only the first nr[level] * nc[level] coefficients of the subband scan, so the serial tANS chain stops early: about 1/4^level
+ * of the work.  A preview validates only the part of the stream it decodes.
+ * level_info (host only): the band's size.  level < 0 or > levels: MIC_ERR_ARGS; a header shorter than 11 bytes: MIC_ERR_CORRUPT.
+ * decompress_level_batch: the shape rules of decompress_batch; frame i's band goes to pixels_out + i * nr[level] * nc[level]
+ * (capacity checked against that size); symbols_decoded (nullable): the tANS symbols the chain decoded per frame -- a frame whose
+ * prefix fell short (escape-heavy 16-bit content) is decoded again whole, and both passes count. */
+int mic_hip_wavelet_v2_level_info(const uint8_t *compressed, size_t compressed_len, int level, int *out_rows, int *out_cols);
+int mic_hip_wavelet_v2_decompress_level(const uint8_t *compressed, size_t compressed_len, int level,
+                                        uint16_t *pixels_out, size_t out_cap_px);
+int mic_hip_wavelet_v2_decompress_level_batch(const uint8_t *const *files, const size_t *lens, int nframes, int level,
+                                              uint16_t *pixels_out, size_t out_cap_px, int32_t *status, uint64_t *symbols_decoded);
+
 /* ---- MIC3 container: tiled RGB whole-slide images ---------------------------------------------- */
 /* Replaces CompressWSI (wsicompress.go:27) + WriteMIC3 (wsiformat.go:99) for 8-bit RGB with the
  * YCoCg-R colour transform (forced on for RGB, wsiformat.go:93-95).  tile_w / tile_h = 0 select the
@@ -474,6 +489,11 @@ int mic_hip_session_wavelet_v2_encode(mic_hip_session *s, const uint16_t *d_fram
                                       const uint8_t **d_streams, uint64_t *h_offsets, int32_t *h_status, int *levels_applied);
 int mic_hip_session_wavelet_v2_decode(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
                                       int rows, int cols, int levels, uint16_t *d_pixels_out, int32_t *h_status);
+/* decode at reduced resolution (mic_hip_wavelet_v2_decompress_level_batch): frame i's band to d_pixels_out + i * nr[level] * nc[level];
+ * h_symbols_decoded (nullable): tANS symbols decoded per frame. */
+int mic_hip_session_wavelet_v2_decode_level(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
+                                            int rows, int cols, int levels, int level, uint16_t *d_pixels_out,
+                                            int32_t *h_status, uint64_t *h_symbols_decoded);
 /* MIC3 on a device-resident slide (BASELINE config 5 as bench.py times it).  encode = CompressWSI (wsicompress.go:27-171) up
  * to, but without, the container: pyramid, tiles, YCoCg-R, plane modes and every plane's CompressSingleFrame on the device, the
  * coded planes kept in a store the session owns (device bytes + one host record per plane); *compressed_bytes = the size of the

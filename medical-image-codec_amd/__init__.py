@@ -109,6 +109,7 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_compress", "mic_hip_mic2_compress_temporal", "mic_hip_mic2_info", "mic_hip_mic2_decompress",
     "mic_hip_mic2_decompress_frame",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
+    "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
     "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
     "mic_hip_compress_frame_grad", "mic_hip_decompress_frame_grad", "mic_hip_pica_compress", "mic_hip_pica_info", "mic_hip_pica_decompress",
     "mic_hip_rgb_compress", "mic_hip_rgb_decompress", "mic_hip_micr_compress", "mic_hip_micr_info", "mic_hip_micr_decompress",
@@ -121,7 +122,7 @@ ABI_SYMBOLS = [
     "mic_hip_wsi_reader_close",
     "mic_hip_session_create", "mic_hip_session_create_on", "mic_hip_session_device", "mic_hip_session_workspace_bytes", "mic_hip_session_destroy", "mic_hip_session_stream",
     "mic_hip_device_copy",
-    "mic_hip_session_wavelet_v2_encode", "mic_hip_session_wavelet_v2_decode",
+    "mic_hip_session_wavelet_v2_encode", "mic_hip_session_wavelet_v2_decode", "mic_hip_session_wavelet_v2_decode_level",
     "mic_hip_session_wsi_encode", "mic_hip_session_wsi_write", "mic_hip_session_wsi_payload", "mic_hip_session_wsi_decode_level", "mic_hip_session_wsi_levels",
     "mic_hip_session_encode", "mic_hip_session_decode",
     "mic_hip_session_encode_enqueue", "mic_hip_session_encode_finish",
@@ -202,6 +203,8 @@ def lib() -> C.CDLL:
                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int)]
     L.mic_hip_session_wavelet_v2_decode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_void_p, C.POINTER(C.c_int32)]
+    L.mic_hip_session_wavelet_v2_decode_level.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     L.mic_hip_session_wsi_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mic_hip_session_wsi_write.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_session_wsi_payload.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
@@ -266,6 +269,10 @@ def lib() -> C.CDLL:
     L.mic_hip_wavelet_v2_decompress_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
     L.mic_hip_wavelet_v2_info.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 4
     L.mic_hip_wavelet_v2_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.mic_hip_wavelet_v2_level_info.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mic_hip_wavelet_v2_decompress_level.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+    L.mic_hip_wavelet_v2_decompress_level_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p,
+                                                            C.c_size_t, C.POINTER(C.c_int32), C.c_void_p]
     L.mic_hip_wsi_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_compress_frame_grad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_decompress_frame_grad.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
@@ -722,6 +729,47 @@ def wavelet_v2_decompress(compressed) -> Tuple[np.ndarray, int, int]:
     if rc:
         _raise(rc, "wavelet_v2_decompress")
     return out.reshape(r.value, cc.value), r.value, cc.value
+
+
+def wavelet_v2_level_info(compressed, level: int) -> Tuple[int, int]:
+    """(rows, cols) of the image at resolution `level` of a WaveletV2 file: nr[0] = rows, nr[l + 1] = (nr[l] + 1) // 2, cols alike;
+    0 <= level <= the header's level count (else MicError MIC_ERR_ARGS).  Host only."""
+    c = _bytes_arr(compressed)
+    r, cc = C.c_int(), C.c_int()
+    rc = lib().mic_hip_wavelet_v2_level_info(c.ctypes.data, c.size, int(level), C.byref(r), C.byref(cc))
+    if rc:
+        _raise(rc, "wavelet_v2_level_info")
+    return r.value, cc.value
+
+
+def wavelet_v2_decompress_level(compressed, level: int) -> np.ndarray:
+    """The image at resolution `level` (wavelet_v2_level_info): the LL band the forward transform holds after `level` levels,
+    saturated to uint16 -- level 0 is wavelet_v2_decompress's image.  The tANS chain stops after the symbols that band needs, so a
+    preview validates only the part of the stream it decodes."""
+    c = _bytes_arr(compressed)
+    r, cc = wavelet_v2_level_info(c, level)
+    out = np.empty(r * cc, dtype=np.uint16)
+    rc = lib().mic_hip_wavelet_v2_decompress_level(c.ctypes.data, c.size, int(level), out.ctypes.data, out.size)
+    if rc:
+        _raise(rc, "wavelet_v2_decompress_level")
+    return out.reshape(r, cc)
+
+
+def wavelet_v2_decompress_level_batch(files: Sequence[bytes], level: int, counts: bool = False):
+    """files of ONE shape at resolution `level` -> ([status], nframes x nr x nc uint16), and with counts=True also the tANS symbols
+    the chain decoded per frame (uint64; a frame decoded twice -- escape-heavy content -- counts both passes)."""
+    cs = [_bytes_arr(b) for b in files]
+    nf = len(cs)
+    r, cc = wavelet_v2_level_info(cs[0], level)
+    out = np.zeros((nf, r, cc), dtype=np.uint16)
+    ptrs = (C.c_void_p * nf)(*[c.ctypes.data for c in cs]); lens = (C.c_size_t * nf)(*[c.size for c in cs]); st = (C.c_int32 * nf)()
+    syms = np.zeros(nf, dtype=np.uint64)
+    rc = lib().mic_hip_wavelet_v2_decompress_level_batch(ptrs, lens, nf, int(level), out.ctypes.data, out.size, st, syms.ctypes.data)
+    if rc:
+        _raise(rc, "wavelet_v2_decompress_level_batch")
+    if counts:
+        return [int(v) for v in st], out, syms
+    return [int(v) for v in st], out
 
 
 # ------------------------------------------------------------------ MIC3 / WSI
@@ -1196,6 +1244,18 @@ class Session:
         if rc:
             _raise(rc, "session_wavelet_v2_decode")
         return np.array(st[:], dtype=np.int32)
+
+    def wavelet_v2_decode_level(self, d_streams: int, offsets: np.ndarray, nframes: int, rows: int, cols: int, levels: int, level: int,
+                                d_pixels_out: int):
+        """wavelet_v2_decode at resolution `level`: frame i's nr x nc band (wavelet_v2_level_info) to d_pixels_out + i * nr * nc u16.
+        -> (status[nframes], tANS symbols decoded per frame)"""
+        offs = (C.c_uint64 * len(offsets))(*[int(v) for v in offsets]); st = (C.c_int32 * nframes)()
+        syms = np.zeros(nframes, dtype=np.uint64)
+        rc = lib().mic_hip_session_wavelet_v2_decode_level(self._h, d_streams, offs, nframes, rows, cols, levels, int(level), d_pixels_out, st,
+                                                           syms.ctypes.data)
+        if rc:
+            _raise(rc, "session_wavelet_v2_decode_level")
+        return np.array(st[:], dtype=np.int32), syms
 
     # ---- MIC3 on a device-resident slide (wsicompress.go:27-171) ---------------------------------------------------------------
     def wsi_encode(self, d_pixels: int, width: int, height: int, channels: int = 3, bits_per_sample: int = 8,

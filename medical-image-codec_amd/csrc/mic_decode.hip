@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
     typedef __attribute__((address_space(1))) uint32_t *gu32;
     const gcu32 tabg = (gcu32)u.tt_nb;
     const gcu16 symg = (gcu16)u.tab_sym;
-    const uint32_t count = u.count;
+    const uint32_t count = mic_sym_ceiling(u, u.count);                 // (a ceiling is a multiple of 128: no tail behind it)
     const gu16 out = (gu16)u.tok;
     const uint8_t *bs = u.comp_in + u.bits_off;
     const uint32_t last = bs[len - 1];
@@ -291,7 +291,7 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
         walk(count, [&](uint32_t pos) -> uint32_t { return __builtin_amdgcn_readlane(tv0, pos - done); });
     }
     if (lane == 0) {
-        if (q + 32 - (int32_t)(8u * sb) < 0) u.status = MICD_ERR_CORRUPT;   // bitreader.go:113-120
+        if (count == u.count && q + 32 - (int32_t)(8u * sb) < 0) u.status = MICD_ERR_CORRUPT;   // bitreader.go:113-120 (a prefix reads less)
         else {
             u.ntok = count;
             if (u.mode == 0 && u.seg != nullptr && !w_err) { u.nseg = w_nseg; u.nsym = min(w_out, w_symcap); u.walk_ok = 1; }

@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     const uint32_t gs = have ? g : 0;                                       // absent streams run on stream 0's table (every access in range)
     const MicUnit &u = units[list[slot0 + (int)gs]];
     const uint32_t tl = u.table_log, size = 1u << tl;
-    const uint32_t count = have ? u.count : 0u;
+    const uint32_t count = have ? mic_sym_ceiling(u, u.count) : 0u;          // (a ceiling is a multiple of 128: no tail behind it)
     const uint32_t bits_off = u.bits_off, len = u.comp_len - bits_off;
     const uint32_t sbase = (wv * LS_SPW + g) * LS_STREAM_BYTES;             // own ring / stage (also for an absent stream)
     const uint32_t tbase = (wv * LS_SPW + gs) * LS_STREAM_BYTES + LS_TAB;
@@ -494,7 +494,8 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     // ---- results: one lane per stream -------------------------------------------------------------------------------
     if (have && lane % LS_LS == 0 && lane < LS_SPW * LS_LS) {
         MicUnit &uo = units[list[slot0 + (int)g]];
-        if (q + 32 - (int32_t)(8u * sb) < 0) uo.status = MICD_ERR_CORRUPT;  // bitreader.go:113-120: more bits taken than the stream holds
+        // bitreader.go:113-120: more bits taken than the stream holds -- a prefix has read only the bits behind its own symbols
+        if (count == uo.count && q + 32 - (int32_t)(8u * sb) < 0) uo.status = MICD_ERR_CORRUPT;
         else { uo.ntok = count; uo.walk_ok = 2; }                           // tok holds STATES: k_dec_translate turns them into symbols
     }
 }

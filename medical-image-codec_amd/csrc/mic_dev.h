@@ -92,7 +92,19 @@ struct MicUnit {
     uint32_t flavour;         // decode: 1/2/4/8, 108 = rANS-8
     uint32_t packed_direct;   // encode: 1 = the bitstream goes straight to the packed buffer (k_enc_tans_pack); the blob holds only the framing
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
+    // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------
+    uint32_t sym_limit;       // 0: the whole stream.  Else the chain kernels that honour it decode only the first
+                              // round_up(sym_limit, 128) symbols (whole 128-symbol chunks) and leave ntok < count: a PREFIX unit,
+                              // whose bits behind the prefix are never read (no over-read check)
 };
+// a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
+__host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }
+// the symbols a chain kernel decodes of a unit: count, or the ceiling in whole 128-symbol chunks when that is less
+__host__ __device__ inline uint32_t mic_sym_ceiling(const MicUnit &u, uint32_t count) {
+    if (u.sym_limit == 0 || u.sym_limit > 0xFFFFFF00u) return count;
+    const uint32_t c = (u.sym_limit + 127u) & ~127u;
+    return c < count ? c : count;
+}
 
 // A pointer read out of a MicUnit is "generic" to the compiler, and generic accesses are flat_load / flat_store: those count on
 // lgkmcnt as well as on vmcnt, so every s_waitcnt lgkmcnt(0) -- there is one in front of every work-group barrier -- waits for the

@@ -156,7 +156,9 @@ __global__ void __launch_bounds__(256) k_wv_fwd2d(const void *__restrict__ src_,
 // The inverse of one level (columns, then rows: waveletu16.go:213-257): the smooth subband from `ll` (the level below wrote it; the
 // coarsest level's lies in `a`), the detail subbands from `a`, the restored region to `dst` (a compact plane, or the 16-bit pixels).
 // A lane owns smooth column gi and detail column gi of the Mallat layout -- after the rows pass, samples 2 gi and 2 gi + 1.
-template <bool TO_U16>
+// SAT (with TO_U16): the samples are saturated to [0, 65535] -- the last level of a reduced-resolution decode, whose LL band may
+// over- or undershoot the pixel range at edges; the full decode's store keeps the reference's plain truncation.
+template <bool TO_U16, bool SAT = false>
 __global__ void __launch_bounds__(256) k_wv_inv2d(const int32_t *__restrict__ a, int stride, size_t fs, const int32_t *__restrict__ ll, int llstride, size_t llfs,
                                                   void *__restrict__ dst_, int dstride, size_t dfs, int r, int c, int nf) {
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
@@ -193,7 +195,9 @@ __global__ void __launch_bounds__(256) k_wv_inv2d(const int32_t *__restrict__ a,
             const size_t o = (size_t)f * dfs + (size_t)y * dstride + (size_t)(2 * gi);
             if (TO_U16) {
                 uint16_t *d = (uint16_t *)dst_ + o;
-                if (has1) *(wv_u32u *)d = ((uint32_t)ev & 0xFFFFu) | ((uint32_t)od << 16); else d[0] = (uint16_t)ev;
+                const int32_t e16 = SAT ? min(max(ev, 0), 65535) : ev, o16 = SAT ? min(max(od, 0), 65535) : od;
+                if (SAT) { if (has1) *(wv_u32u *)d = (uint32_t)e16 | ((uint32_t)o16 << 16); else d[0] = (uint16_t)e16; }
+                else if (has1) *(wv_u32u *)d = ((uint32_t)ev & 0xFFFFu) | ((uint32_t)od << 16); else d[0] = (uint16_t)ev;
             } else {
                 int32_t *d = (int32_t *)dst_ + o;
                 if (has1) *(wv_u64u *)d = (uint32_t)ev | ((unsigned long long)(uint32_t)od << 32); else d[0] = ev;
@@ -224,6 +228,15 @@ __global__ void __launch_bounds__(256) k_wv_load(const uint16_t *px, int32_t *a,
 }
 __global__ void __launch_bounds__(256) k_wv_store(const int32_t *a, uint16_t *px, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) px[i] = (uint16_t)a[i];
+}
+// the coarsest LL band (nr x nc, at the top left of each frame's coefficient plane of stride `cols`, frame stride fs) saturated to u16,
+// row stride nc: a decode at reduced resolution r = levels, which runs no inverse level at all
+__global__ void __launch_bounds__(256) k_wv_band(const int32_t *a, int cols, size_t fs, uint16_t *px, int nr, int nc, int nf) {
+    const size_t band = (size_t)nr * (size_t)nc, n = band * (size_t)nf;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t f = i / band, k = i - f * band, y = k / (size_t)nc, x = k - y * (size_t)nc;
+        px[i] = (uint16_t)min(max(a[f * fs + y * (size_t)cols + x], 0), 65535);
+    }
 }
 
 // collectSubbandOrder / scatterSubbandOrder as an index map (waveletfsecompressu16.go:202-282):
@@ -316,16 +329,17 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ntok = u.ntok; const uint16_t *tok = u.tok;
     if (ntok < 3) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
+    const bool pre = mic_is_prefix(u);                                   // the tokens end at the chain's ceiling, not at the stream's end
     const int d0 = mic_len16(tok[0]);
     if (d0 == 0) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     const uint32_t mid = (1u << (d0 - 1)) - 1;
-    const uint32_t outlen = ((uint32_t)tok[1] << 16) + tok[2];
+    uint32_t outlen = ((uint32_t)tok[1] << 16) + tok[2];
     if (outlen > u.sym_cap) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     uint2 *seg = u.seg; uint16_t *sym = u.sym;
     if (wave == 0) {
-        uint32_t pos = 3, outp = 0, nseg = 0, err = 0;
+        uint32_t pos = 3, outp = 0, nseg = 0, err = 0, fin = 0;
         const uint32_t segcap = u.seg_cap;
-        while (pos < ntok && outp < outlen && !err) {
+        while (pos < ntok && outp < outlen && !err && !fin) {
             const uint32_t w = (pos + lane < ntok) ? tok[pos + lane] : 0u;
             uint32_t j = 0;
             while (j < 64 && pos + j < ntok && outp < outlen) {
@@ -333,7 +347,7 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
                 if (nseg >= segcap) { err = 1; break; }
                 if (h == 0) h = 65536u;                                  // the reference's reading of a zero count: a literal chunk of 65536 - midCount (mic_decode_px.hip)
                 if (h <= mid) {
-                    if (pos + j + 1 >= ntok) { err = 1; break; }
+                    if (pos + j + 1 >= ntok) { if (pre) fin = 1; else err = 1; break; }   // (a prefix: the run's value lies behind it)
                     if (j == 63) break;
                     if (lane == 0) seg[nseg] = make_uint2(pos + j, outp);
                     nseg++; outp += h; j += 2;
@@ -344,12 +358,15 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
             }
             pos += j;
         }
-        if (outp < outlen) err = 1;                                    // tokens ran out (Go: index panic)
-        if (lane == 0) { s_misc[0] = nseg; s_misc[1] = err; s_misc[2] = 0; }
+        if (outp < outlen && !pre) err = 1;                            // tokens ran out (Go: index panic)
+        // the words the tokens cover: a prefix's last literal chunk may reach past its last token (pos: the header behind that chunk)
+        const uint32_t cover = pre ? min(outlen, outp - (pos > ntok ? pos - ntok : 0u)) : outlen;
+        if (lane == 0) { s_misc[0] = nseg; s_misc[1] = err; s_misc[2] = cover; }
     }
     __syncthreads();
     if (s_misc[1]) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     const uint32_t nseg = s_misc[0];
+    outlen = s_misc[2];                                                  // (a prefix: the words it covers)
     uint32_t bad = 0;
     for (uint32_t si = wave; si < nseg; si += WV_WAVES) {
         const uint2 r = seg[si];
@@ -374,18 +391,18 @@ __device__ __forceinline__ uint32_t wv_fn_compose(uint32_t g, uint32_t f) {     
     const uint32_t f0 = f & 3, f1 = (f >> 2) & 3, f2 = (f >> 4) & 3;
     return ((g >> (2 * f0)) & 3) | (((g >> (2 * f1)) & 3) << 2) | (((g >> (2 * f2)) & 3) << 4);
 }
-__global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_t *a, WvDims d) {
+// lim: the coefficients wanted -- n, or P(r) of a decode at reduced resolution (the first P(r) of the subband scan); fewer is an error
+__global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_t *a, WvDims d, uint32_t lim) {
     MicUnit &u = units[blockIdx.x];
     a += (size_t)blockIdx.x * (size_t)d.rows * (size_t)d.cols;
     if (u.status != MICD_OK || !u.wv_slow) return;
     __shared__ uint32_t s_scan[WV_WAVES], s_fn[WV_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t m = u.nsym; const uint16_t *sym = u.sym;
-    const size_t n = (size_t)d.rows * d.cols;
     // state = payload words still to skip (0: a symbol starts here).  marker: 0 -> 2; payload: k -> k-1.
     // non-escape symbol: f = (0, 0, 1) i.e. state 0 -> 0, 1 -> 0, 2 -> 1 ; escape value 65535: f = (2, 0, 1)
     uint32_t carry_state = 0, carry_n = 0; bool bad = false;
-    for (uint32_t base = 0; base < m && carry_n < n; base += WV_THREADS) {
+    for (uint32_t base = 0; base < m && carry_n < lim; base += WV_THREADS) {
         const uint32_t i = base + tid;
         const bool in = i < m;
         const uint32_t x = in ? sym[i] : 0u;
@@ -408,7 +425,7 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_
         for (int w = 0; w < WV_WAVES; w++) { const uint32_t v = s_scan[w]; if ((uint32_t)w < wave) woff += v; tot += v; st_end = (s_fn[w] >> (2 * st_end)) & 3; }
         if (starts) {
             const size_t k = (size_t)carry_n + woff + incl - 1;
-            if (k < n) {
+            if (k < lim) {
                 int32_t v;
                 if (x != 65535u) v = (int32_t)((x >> 1) ^ (uint32_t)(-(int32_t)(x & 1)));        // zigzagDecode16, :543-546
                 else if (i + 2 < m) v = (int32_t)(((uint32_t)sym[i + 1] << 16) | (uint32_t)sym[i + 2]);
@@ -419,7 +436,7 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_
         carry_n += tot; carry_state = st_end;
     }
     const int anybad = __syncthreads_or(bad ? 1 : 0);
-    if (tid == 0 && (anybad || carry_n < n)) u.status = MICD_ERR_CORRUPT;          // fewer coefficients than pixels (Go: panic)
+    if (tid == 0 && (anybad || carry_n < lim)) u.status = MICD_ERR_CORRUPT;        // fewer coefficients than pixels (Go: panic)
 }
 
 // ---- the usual case in parallel: frames whose coefficients all fit 16 bits (no 3-word escapes), many groups per frame -------------
@@ -547,9 +564,10 @@ __global__ void __launch_bounds__(64) k_rle_walk_parts(MicUnit *units) {
     if (d0 == 0) return;
     const uint32_t mid = (1u << (d0 - 1)) - 1;
     uint2 *rec = u.seg + u.seg_cap / 2 + (size_t)p * wp_stride(L);
-    uint32_t pos = p ? lo : 3u, out = 0, nrec = 0, err = 0;
+    const bool pre = mic_is_prefix(u);                                      // the tokens end at the chain's ceiling
+    uint32_t pos = p ? lo : 3u, out = 0, nrec = 0, err = 0, fin = 0;
     const uint32_t start = pos;
-    while (pos < hi && !err) {
+    while (pos < hi && !err && !fin) {
         const uint32_t w = (pos + lane < ntok) ? tok[pos + lane] : 0u;
         uint32_t j = 0;
         while (j < 64 && pos + j < hi) {
@@ -562,7 +580,11 @@ __global__ void __launch_bounds__(64) k_rle_walk_parts(MicUnit *units) {
                 continue;
             }
             if (h <= mid) {
-                if (pos + j + 1 >= ntok) { if (p == 0) err = 1; else { nrec = 0; out = 0; j = 64; pos = hi; } break; }
+                if (pos + j + 1 >= ntok) {
+                    if (pre) { fin = 1; break; }                            // a prefix ends in front of a run whose value it lacks: exit = that header
+                    if (p == 0) err = 1; else { nrec = 0; out = 0; j = 64; pos = hi; }
+                    break;
+                }
                 if (lane == 0) rec[nrec] = make_uint2((pos + j + 1) | 0x80000000u, out);
                 nrec++; out += h; j += 2;
             } else {
@@ -586,7 +608,8 @@ __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
     const uint32_t ntok = u.ntok, lane = threadIdx.x;
     const uint32_t L = wp_part_len(max(ntok, 1u));
     const uint16_t *tok = u.tok;
-    bool ok = ntok >= 3 && wp_fits(u, L) && mic_len16(tok[0]) != 0;
+    bool ok = ntok >= 3 && wp_fits(u, L) && mic_len16(tok[0]) != 0, fin = false;
+    const bool pre = mic_is_prefix(u);                                      // a prefix: the walk ends cleanly where its tokens do
     const uint32_t cap = ok ? ((uint32_t)tok[1] << 16) + tok[2] : 0u;
     const uint32_t mid = ok ? (1u << (mic_len16(tok[0]) - 1)) - 1 : 0u;
     if (cap > u.sym_cap) ok = false;
@@ -625,7 +648,7 @@ __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
             const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)wtok, (int)(e - wbase));
             if (h == 0 || nx >= WP_EXTRA) { ok = false; break; }                // (a zero count: corrupt; too many: the one-group kernels take the frame)
             const bool run = h <= mid;
-            if (run && e + 1 >= ntok) { ok = false; break; }
+            if (run && e + 1 >= ntok) { if (pre) fin = true; else ok = false; break; }
             const uint32_t len = run ? h : h - mid;
             if (lane == 0) extra[nx] = make_uint2((e + 1) | (run ? 0x80000000u : 0u), O);
             nx++; O += len; e += run ? 2u : 1u + len;
@@ -636,14 +659,19 @@ __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
             S[q].first = first; S[q].nextra = nx; S[q].extra_base = N0; S[q].base_seg = N0 + nx; S[q].out_delta = O - r0;
         }
         N = N0 + nx;
+        if (fin) break;
         if (!synced) continue;                                              // the true walk left the part on its own (or the stream has its symbols)
         N += s.nrec - first; O += s.out_total - r0;
         if (s.err) { if (O < cap) ok = false; break; }                      // the zero header is reached before the stream has its symbols
         e = s.exit;
+        if (pre && e < hi) break;                                           // the part's walk stopped where the prefix does (a run without its value)
     }
-    if (ok && O < cap) ok = false;                                          // tokens ran out (Go: index panic)
+    if (ok && O < cap && !pre) ok = false;                                  // tokens ran out (Go: index panic)
+    // the words the tokens cover: all `cap`, or -- a prefix -- those in front of its end (e: the header behind the last one walked;
+    // past ntok when that was a literal chunk the prefix holds only the front of)
+    const uint32_t cover = pre ? min(cap, O - (e > ntok ? e - ntok : 0u)) : cap;
     if (lane == 0) {
-        if (ok) { u.nseg = N; u.nsym = cap; u.walk_ok = 1; }
+        if (ok) { u.nseg = N; u.nsym = cover; u.walk_ok = 1; }
         else u.walk_ok = 0;
     }
 }
@@ -682,17 +710,18 @@ __global__ void __launch_bounds__(256) k_rle_walk_compact(MicUnit *units) {
 // segment that holds every WS_T-th symbol) say where a position's symbol lies in the token stream (the fetch is
 // k_dec_pixels_wg's: segment table in LDS, gallop + bisection, one 16-byte load inside a literal chunk).  A frame with an escape
 // word (65535) in its symbols, fewer symbols than samples, or a stream the walker refused goes to k_wv_expand + k_wv_coeffs.
-__global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, int32_t *a, WvDims d) {
+// lim: the scan positions wanted -- n, or P(r) of a decode at reduced resolution (a prefix unit covering fewer goes the slow way)
+__global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, int32_t *a, WvDims d, uint32_t lim) {
     MicUnit &u = units[blockIdx.y];
     if (u.status != MICD_OK) return;
     const uint32_t n = (uint32_t)d.rows * (uint32_t)d.cols, tid = threadIdx.x;
-    if (u.walk_ok != 1 || u.nsym < n) { if (tid == 0) u.wv_slow = 1; return; }
+    if (u.walk_ok != 1 || u.nsym < lim) { if (tid == 0) u.wv_slow = 1; return; }
     __shared__ uint32_t s_segx[1024], s_segy[1024 + 1];
     a += (size_t)blockIdx.y * n;
     const uint32_t nseg = u.nseg, ntok = u.ntok;
     const uint16_t *tok = u.tok;
     const uint2 *seg = u.seg;
-    const uint32_t o0 = blockIdx.x * WS_T, tile_end = min(o0 + WS_T, n);
+    const uint32_t o0 = blockIdx.x * WS_T, tile_end = min(o0 + WS_T, lim);
     const uint32_t i0 = o0 + tid * 8, wend = min(i0 + 8, tile_end);
     uint32_t w8[4] = { 0u, 0u, 0u, 0u }, bad = 0;
     bool got = i0 >= tile_end;
@@ -840,14 +869,19 @@ int wv_compress_frames(mic_hip_session *s, const uint16_t *d_src, int nf, int ro
 }
 
 // nf FSE streams (already in s->io_comp at offs[i] .. offs[i + 1]) of frames of one shape -> pixels in s->io_px
+// level > 0: the image at that resolution (the nr[level] x nc[level] LL band, saturated to u16, row stride nc[level]) -- the first
+// P = nr[level] * nc[level] coefficients of the subband scan, the inverse levels levels - 1 .. level.  sym_limit: MicUnit::sym_limit of
+// every unit (0: the whole stream).  ends: frame i is offs[i] .. ends[i] instead (a subset of the streams, wv_decode_level_frames).
 int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, int nf, const uint64_t *offs, int rows, int cols, int levels,
-                         std::vector<int32_t> &st) {
+                         std::vector<int32_t> &st, int level = 0, uint32_t sym_limit = 0, const uint64_t *ends = nullptr) {
     const size_t n = (size_t)rows * (size_t)cols;
     int rc;
     // everything the launches below assume is checked before the first of them: grid limits, stream ranges
     if (nf <= 0 || nf > 65535 || n >= ((size_t)65535 * WS_T)) return MIC_ERR_UNSUPPORTED;
+    if (level < 0 || level > levels) return MIC_ERR_ARGS;
+    auto end_of = [&](int i) { return ends ? ends[(size_t)i] : offs[(size_t)i + 1]; };
     for (int i = 0; i < nf; i++)
-        if (offs[(size_t)i + 1] < offs[(size_t)i] || offs[(size_t)i + 1] - offs[(size_t)i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
+        if (end_of(i) < offs[(size_t)i] || end_of(i) - offs[(size_t)i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
     if ((rc = s->ensure(nf, 2 * n + 16))) return rc;
     DevBuf &a = s->wv_a, &b = s->wv_b;
     const size_t ll_half = (size_t)((rows + 1) / 2) * (size_t)((cols + 1) / 2), ll_fs = 2 * ll_half;   // (the smooth planes between levels, as in wv_compress_frames)
@@ -856,34 +890,40 @@ int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_
     { const int arc = s->h_units.assign((size_t)nf, MicUnit{}); if (arc) return arc; }
     for (int i = 0; i < nf; i++) {
         MicUnit &u = s->h_units[(size_t)i];
-        u.comp_in = d_comp + offs[(size_t)i]; u.comp_len = (uint32_t)(offs[(size_t)i + 1] - offs[(size_t)i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
+        u.comp_in = d_comp + offs[(size_t)i]; u.comp_len = (uint32_t)(end_of(i) - offs[(size_t)i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
         s->fill_workspace(u, i);
         u.sym_cap = (uint32_t)std::min<size_t>(u.sym_cap, wv_sym_ceiling(n));   // the oracle's ceiling: DESIGN.md section 4, WaveletV2
+        u.sym_limit = sym_limit;
     }
     if (s->h_units.upload(s->units.p, (size_t)nf, s->stream) != MIC_OK) return done(MIC_ERR_DEVICE);
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;
     s->timer.reset(s->stream);
     mic_launch_decode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer, (int *)s->cls.p);
     const WvDims d = wv_dims(rows, cols, levels);
+    const uint32_t P = (uint32_t)d.nr[level] * (uint32_t)d.nc[level];   // the coefficients the output needs (n at level 0)
     if (s->timer.used) { s->timer.used--; s->timer.names.pop_back(); }   // (drop the chain's "end" mark: the wavelet kernels follow)
     s->timer.mark("k_rle_walk_parts+fix+compact");
     hipLaunchKernelGGL(k_rle_walk_parts, dim3(WP_PARTS, (unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
     hipLaunchKernelGGL(k_rle_walk_fix, dim3((unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
     hipLaunchKernelGGL(k_rle_walk_compact, dim3(WP_PARTS, (unsigned)nf), dim3(256), 0, s->stream, (MicUnit *)s->units.p);
     s->timer.mark("k_wv_scatter");
-    hipLaunchKernelGGL(k_wv_scatter, dim3((unsigned)((n + WS_T - 1) / WS_T), (unsigned)nf), dim3(1024), 0, s->stream, (MicUnit *)s->units.p, A, d);
+    hipLaunchKernelGGL(k_wv_scatter, dim3((unsigned)((P + WS_T - 1) / WS_T), (unsigned)nf), dim3(1024), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
     s->timer.mark("k_wv_expand+coeffs (escape frames)");
     hipLaunchKernelGGL(k_wv_expand, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, -1, 1);
-    hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, A, d);
+    hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
     s->timer.mark("k_wv_inv2d");
     if (levels == 0) hipLaunchKernelGGL(k_wv_store, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, d_dst, n * (size_t)nf);
-    for (int l = levels - 1; l >= 0; l--) {                                                 // coarse -> fine, :519-527
+    else if (level == levels)                                                               // the coarsest LL band itself: no inverse level
+        hipLaunchKernelGGL(k_wv_band, dim3(grid_for((size_t)P * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, cols, n, d_dst, d.nr[level], d.nc[level], nf);
+    for (int l = levels - 1; l >= level; l--) {                                             // coarse -> fine, :519-527
         const int r = d.nr[l], cc = d.nc[l];
         const dim3 g((unsigned)(((cc + 1) / 2 + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)(((r + 1) / 2 + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
         const bool coarsest = l == levels - 1;
         const int32_t *lls = coarsest ? A : B + (((l + 1) & 1) ? ll_half : 0);
         const int llst = coarsest ? cols : d.nc[l + 1]; const size_t llf = coarsest ? n : ll_fs;
         if (l == 0) hipLaunchKernelGGL(k_wv_inv2d<true>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cols, n, r, cc, nf);
+        else if (l == level)                                                                // reduced resolution: the band, saturated, stride nc[level]
+            hipLaunchKernelGGL((k_wv_inv2d<true, true>), g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cc, (size_t)P, r, cc, nf);
         else hipLaunchKernelGGL(k_wv_inv2d<false>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)(B + ((l & 1) ? ll_half : 0)), cc, ll_fs, r, cc, nf);
     }
     s->timer.mark("end");
@@ -892,6 +932,56 @@ int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_
     st.assign((size_t)nf, 0);
     if ((rc = session_decode_finish(s, st.data()))) return done(rc);
     return done(MIC_OK);
+}
+
+// The tANS ceiling of pass 1 of a decode at reduced resolution ("WaveletV2 at reduced resolution"): the image at
+// level r needs the first P = nr[r] * nc[r] coefficients of the subband scan -- P RLE words when none of them is escaped -- and
+// those take the first tokens of the stream: fewer than P where runs fold them, a header per literal chunk more.  P + P/4 + 512 tokens
+// (whole 128-symbol chunks) cover every frame whose coefficients are not escape-heavy; a frame they do not cover is decoded again
+// whole (pass 2).  P = n (level 0) is the whole stream: 0, no ceiling.
+uint32_t wv_level_sym_limit(size_t P, size_t n) {
+    if (P >= n) return 0;
+    const size_t lim = (P + P / 4 + 512 + 127) & ~(size_t)127;
+    return (uint32_t)std::min<size_t>(lim, 0xFFFFFF00u);
+}
+
+// The image at `level` of nf streams of one shape (wv_decompress_frames' arguments), in two passes under one rule.  Pass 1 decodes
+// every frame with the tANS chain stopped at wv_level_sym_limit; a frame whose prefix did not give its P coefficients -- escape-heavy
+// frames (every 16-bit coefficient outside +-32767 is three words), or any failure inside the prefix -- is decoded again in pass 2,
+// whole (sym_limit 0), in a launch chain of its own, and that pass's status and output are the frame's.  Every other frame keeps
+// pass 1's.  The outputs are the same whichever pass made them; only a pass-2 (or level-0) decode checks the whole stream.
+// syms (nullable): tANS symbols the chain decoded per frame, both passes summed.
+int wv_decode_level_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, int nf, const uint64_t *offs, int rows, int cols,
+                           int levels, int level, std::vector<int32_t> &st, uint64_t *syms) {
+    const size_t n = (size_t)rows * (size_t)cols;
+    if (level < 0 || level > levels || levels > 8) return MIC_ERR_ARGS;
+    const WvDims d = wv_dims(rows, cols, levels);
+    const size_t P = (size_t)d.nr[level] * (size_t)d.nc[level];
+    const uint32_t lim = wv_level_sym_limit(P, n);
+    int rc = wv_decompress_frames(s, d_comp, d_dst, nf, offs, rows, cols, levels, st, level, lim);
+    if (rc) return rc;
+    std::vector<int> redo; std::vector<uint64_t> begins, ends;
+    for (int i = 0; i < nf; i++) {
+        const MicUnit &u = s->h_units[(size_t)i];                       // (read back by session_decode_finish)
+        if (syms) syms[i] = u.ntok;
+        if (st[(size_t)i] != MIC_OK && mic_is_prefix(u)) { redo.push_back(i); begins.push_back(offs[(size_t)i]); ends.push_back(offs[(size_t)i + 1]); }
+    }
+    if (redo.empty()) return MIC_OK;
+    // pass 2: the frames side by side into a staging plane of the session (unused by this path), then each to its place
+    const int k = (int)redo.size();
+    DevBuf &tmp = s->io_px2;
+    if ((rc = tmp.reserve(P * 2 * (size_t)k + 64))) return rc;
+    std::vector<int32_t> st2;
+    if ((rc = wv_decompress_frames(s, d_comp, (uint16_t *)tmp.p, k, begins.data(), rows, cols, levels, st2, level, 0, ends.data()))) return rc;
+    for (int j = 0; j < k; j++) {
+        const int i = redo[(size_t)j];
+        st[(size_t)i] = st2[(size_t)j];
+        if (syms) syms[i] += s->h_units[(size_t)j].ntok;
+        if (st2[(size_t)j] == MIC_OK)
+            HIP_TRY(hipMemcpyAsync(d_dst + (size_t)i * P, (uint16_t *)tmp.p + (size_t)j * P, P * 2, hipMemcpyDeviceToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return MIC_OK;
 }
 
 void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int applied) {     // :346-350
@@ -985,18 +1075,24 @@ int mic_hip_wavelet_v2_info(const uint8_t *c, size_t len, int *rows, int *cols, 
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
-// WaveletV2RLEFSEDecompressU16 over nframes files of ONE shape (same rows, cols, levels) in one launch chain; pixels_out receives
-// nframes x rows*cols u16, status[i] frame i's status.  Files of another shape than the first: MIC_ERR_ARGS for that frame.
-int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_t *lens, int nframes, uint16_t *pixels_out, size_t out_cap_px,
-                                        int32_t *status) try {
+}  // extern "C"
+
+namespace {
+// WaveletV2RLEFSEDecompressU16 over nframes files of ONE shape at resolution `level` (0: the full image): the batch entry points below
+int wv_decompress_files(const uint8_t *const *files, const size_t *lens, int nframes, int level, uint16_t *pixels_out, size_t out_cap_px,
+                        int32_t *status, uint64_t *syms) {
     if (!files || !lens || !pixels_out || !status || nframes <= 0) return MIC_ERR_ARGS;
+    if (syms) for (int i = 0; i < nframes; i++) syms[i] = 0;
     int rows, cols, maxv, levels;
     int rc = mic_hip_wavelet_v2_info(files[0], lens[0], &rows, &cols, &maxv, &levels);
     if (rc) return rc;
     if (rows <= 0 || cols <= 0 || levels > 8) return MIC_ERR_CORRUPT;
+    if (level < 0 || level > levels) return MIC_ERR_ARGS;
     const size_t n = (size_t)rows * (size_t)cols;
     if (n > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
-    if (n * (size_t)nframes > out_cap_px) return MIC_ERR_CAPACITY;
+    const WvDims dm = wv_dims(rows, cols, levels);
+    const size_t P = (size_t)dm.nr[level] * (size_t)dm.nc[level];          // pixels of a frame's output (n at level 0)
+    if (P * (size_t)nframes > out_cap_px) return MIC_ERR_CAPACITY;
     return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session; shape: files[0]'s
         DefaultLease lease;
         int rc = lease.acquire(device);
@@ -1018,22 +1114,65 @@ int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_
             }
             if (!good) continue;
             if ((rc = s->ensure(good, 2 * n + 16))) return rc;
-            if ((rc = s->io_comp.reserve((size_t)offs.back() + 64)) || (rc = s->io_px.reserve(n * 2 * (size_t)good + 64))) return rc;
+            if ((rc = s->io_comp.reserve((size_t)offs.back() + 64)) || (rc = s->io_px.reserve(P * 2 * (size_t)good + 64))) return rc;
             for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0)
                 HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + offs[(size_t)slot[(size_t)i]], files[f0 + (size_t)i] + 11, lens[f0 + (size_t)i] - 11,
                                        hipMemcpyHostToDevice, s->stream));
-            std::vector<int32_t> st;
-            if ((rc = wv_decompress_frames(s, (const uint8_t *)s->io_comp.p, (uint16_t *)s->io_px.p, good, offs.data(), rows, cols, levels, st))) return rc;
+            std::vector<int32_t> st; std::vector<uint64_t> sy((size_t)good, 0);
+            if ((rc = wv_decode_level_frames(s, (const uint8_t *)s->io_comp.p, (uint16_t *)s->io_px.p, good, offs.data(), rows, cols, levels, level, st,
+                                             sy.data()))) return rc;
             for (int i = 0; i < nf; i++) if (slot[(size_t)i] >= 0) {
                 const size_t k = (size_t)slot[(size_t)i];
                 status[f0 + (size_t)i] = st[k];
+                if (syms) syms[f0 + (size_t)i] = sy[k];
                 if (st[k] == MIC_OK)
-                    HIP_TRY(hipMemcpyAsync(pixels_out + (f0 + (size_t)i) * n, (uint16_t *)s->io_px.p + k * n, n * 2, hipMemcpyDeviceToHost, s->stream));
+                    HIP_TRY(hipMemcpyAsync(pixels_out + (f0 + (size_t)i) * P, (uint16_t *)s->io_px.p + k * P, P * 2, hipMemcpyDeviceToHost, s->stream));
             }
             HIP_TRY(hipStreamSynchronize(s->stream));
         }
         return MIC_OK;
     });
+}
+}  // namespace
+
+extern "C" {
+
+// WaveletV2RLEFSEDecompressU16 over nframes files of ONE shape (same rows, cols, levels) in one launch chain; pixels_out receives
+// nframes x rows*cols u16, status[i] frame i's status.  Files of another shape than the first: MIC_ERR_ARGS for that frame.
+int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_t *lens, int nframes, uint16_t *pixels_out, size_t out_cap_px,
+                                        int32_t *status) try {
+    return wv_decompress_files(files, lens, nframes, 0, pixels_out, out_cap_px, status, nullptr);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+// ---- the image at reduced resolution ("WaveletV2 at reduced resolution") --------------------------------------
+// Level r of a file whose header carries `levels`: the nr[r] x nc[r] LL band the forward transform holds after r levels (nr[0] = rows,
+// nr[l + 1] = (nr[l] + 1) / 2, nc alike), saturated to [0, 65535]; r = 0 is the decode itself.  Only the first nr[r] * nc[r] coefficients
+// of the subband scan are needed, and the tANS chain stops after the symbols that hold them (wv_decode_level_frames), so a preview
+// validates only the part of the stream it decodes.
+int mic_hip_wavelet_v2_level_info(const uint8_t *c, size_t len, int level, int *out_rows, int *out_cols) try {
+    int rows, cols, levels;
+    const int rc = mic_hip_wavelet_v2_info(c, len, &rows, &cols, nullptr, &levels);
+    if (rc) return rc;
+    if (rows <= 0 || cols <= 0 || levels > 8) return MIC_ERR_CORRUPT;
+    if (level < 0 || level > levels) return MIC_ERR_ARGS;
+    const WvDims d = wv_dims(rows, cols, levels);
+    if (out_rows) *out_rows = d.nr[level];
+    if (out_cols) *out_cols = d.nc[level];
+    return MIC_OK;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+// mic_hip_wavelet_v2_decompress_batch at `level`: frame i's band goes to pixels_out + i * nr[level] * nc[level]; symbols_decoded
+// (nullable): the tANS symbols the chain decoded per frame, both passes summed
+int mic_hip_wavelet_v2_decompress_level_batch(const uint8_t *const *files, const size_t *lens, int nframes, int level, uint16_t *pixels_out,
+                                              size_t out_cap_px, int32_t *status, uint64_t *symbols_decoded) try {
+    return wv_decompress_files(files, lens, nframes, level, pixels_out, out_cap_px, status, symbols_decoded);
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+
+int mic_hip_wavelet_v2_decompress_level(const uint8_t *c, size_t len, int level, uint16_t *pixels_out, size_t out_cap_px) try {
+    if (!c || !pixels_out) return MIC_ERR_ARGS;
+    int32_t st = 0;
+    const int rc = mic_hip_wavelet_v2_decompress_level_batch(&c, &len, 1, level, pixels_out, out_cap_px, &st, nullptr);
+    return rc ? rc : st;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
 
 // WaveletV2RLEFSEDecompressU16 / WaveletV2SIMDRLEFSEDecompressU16 (:380-425, :493-534)
@@ -1074,6 +1213,21 @@ int mic_hip_session_wavelet_v2_decode(mic_hip_session *s, const uint8_t *d_strea
     if (rc) return rc;
     std::vector<int32_t> st;
     if ((rc = wv_decompress_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, st))) return rc;
+    for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
+    return MIC_OK;
+} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+// The same at `level` (mic_hip_wavelet_v2_level_info): frame i's nr[level] x nc[level] band to d_pixels_out + i * nr[level] * nc[level];
+// h_symbols_decoded (nullable): the tANS symbols the chain decoded per frame, both passes summed.
+int mic_hip_session_wavelet_v2_decode_level(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
+                                            int rows, int cols, int levels, int level, uint16_t *d_pixels_out,
+                                            int32_t *h_status, uint64_t *h_symbols_decoded) try {
+    if (!s || !d_streams || !h_offsets || !d_pixels_out || !h_status || nframes <= 0 || rows <= 0 || cols <= 0 || levels < 0 || levels > 8) return MIC_ERR_ARGS;
+    if (level < 0 || level > levels) return MIC_ERR_ARGS;
+    if ((size_t)rows * (size_t)cols > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
+    int rc = s->activate();
+    if (rc) return rc;
+    std::vector<int32_t> st;
+    if ((rc = wv_decode_level_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, level, st, h_symbols_decoded))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
     return MIC_OK;
 } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
