@@ -126,7 +126,7 @@ size_t workspace_budget() {
 static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, int tier) {
     size_t max_px = 0;
     for (int i = 0; i < n; i++) max_px = std::max(max_px, (size_t)units[i].width * (size_t)units[i].height);
-    int rc = s->ensure(n, max_px, tier);
+    int rc = s->lay_out(n, max_px, tier);
     if (rc) return rc;
     // The packed buffer is sized from what the session's last batch needed; it is reserved here, in front of the chain (a reallocation
     // behind it would wait for the queued chain to drain).
@@ -137,7 +137,6 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         if ((rc = s->packed.reserve(want))) return rc;
         if ((rc = s->pin_off.reserve((size_t)n + 1))) return rc;
     }
-    { const int arc = s->h_units.assign((size_t)n, MicUnit{}); if (arc) return arc; }
     bool any_grad = false, narrow = true, any_gap = false;
     for (int i = 0; i < n; i++) any_gap |= (units[i].nstates & MIC_HIP_GAP_REMOVAL) != 0;
     if (any_gap && (rc = s->gap.reserve((size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)n))) return rc;
@@ -149,12 +148,8 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         u.max_value = units[i].max_value; u.nstates = units[i].nstates & 0xFF;
         u.pred = (units[i].nstates & MIC_HIP_PRED_GRAD) ? 1u : 0u; any_grad |= u.pred != 0;
         if (units[i].nstates & MIC_HIP_GAP_REMOVAL) { u.gap = 1; u.gap_buf = (uint8_t *)s->gap.p + (size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)i; }
-        s->fill_workspace(u, i);
         u.tok_cap = (uint32_t)tok_cap_tier((size_t)u.w * (size_t)u.h, tier);
     }
-    { const int urc = s->h_units.upload(s->units.p, (size_t)n, s->stream); if (urc) return urc; }
-    if ((rc = s->prepare_hist(n))) return rc;
-    s->timer.reset(s->stream);
     // The encoder's classes: what the session's last batches used, plus what the HOST can tell -- the two big instances always (a
     // two-state unit whose attempt fails is handed to the wide one; a miss there is the serial encoder, 0.8 s for an XR batch:
     // tools/mask_miss.py), the one-wave instances when a unit is small enough for them, the tableLog 14-16 ones when a unit is deep
@@ -164,12 +159,9 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         if ((size_t)units[i].width * (size_t)units[i].height <= 131072u) enc_hint |= MIC_ENC_CLS_SMALL12 | MIC_ENC_CLS_SMALL13;
         if (units[i].max_value >= 2048u) enc_hint |= MIC_ENC_CLS_TL14 | MIC_ENC_CLS_TL15 | MIC_ENC_CLS_TL16;
     }
-    mic_launch_encode((MicUnit *)s->units.p, n, s->stream, s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0) |
-                      (any_gap ? MIC_VARIANT_GAP : 0), &s->timer,
-                      s->enc_classes.mask() | enc_hint);
-    if (hipGetLastError() != hipSuccess) { s->hist_unknown(); return MIC_ERR_DEVICE; }
-    s->begin_chain(n);
-    s->learn_encode = true;                                              // (behind begin_chain, which clears it: the masks were never learned)
+    const int variant = s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0) | (any_gap ? MIC_VARIANT_GAP : 0);
+    if ((rc = s->run_encode([&] { mic_launch_encode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, s->enc_classes.mask() | enc_hint); }))) return rc;
+    s->learn_encode = true;
     // Compaction and the read-back of the results ride behind the chain, so that session_encode_finish is ONE synchronisation (round 3:
     // descriptors down, a synchronisation, sizes summed on the host, scan + pack launched, a second synchronisation -- 86 us of idle
     // device between the chain and the pack of every call).  The pack kernels leave a batch that does not fit the packed buffer alone
@@ -234,7 +226,7 @@ static void tier_review(mic_hip_session *s, int n) {
     const size_t ts1 = tab_syms_tier(1);
     for (int i = 0; i < n && fits; i++) {
         const MicUnit &u = s->h_units[(size_t)i];
-        if (u.mode != 0) { fits = false; break; }                       // (units laid out by the wavelet / temporal paths: theirs to decide)
+        if (u.mode != 0) { fits = false; break; }                       // (symbol units: laid out in tier 2 by their paths, mic_hip_session::lay_out)
         const size_t px = (size_t)std::max(u.w, 0) * (size_t)std::max(u.h, 0);
         const size_t ntok = std::max<size_t>(u.ntok, u.count);
         fits = u.status == MICD_OK && ntok + 64 <= tok_cap_tier(px, 1) && (size_t)u.nseg + 8 <= seg_cap_tier(px, 1) &&
@@ -331,10 +323,9 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
         s->retry = std::move(r);
         begins = s->retry.begins.data(); ends = s->retry.ends.data(); units = s->retry.units.data();
     } else if (s->retry.kind != 0 && begins != s->retry.begins.data()) s->retry.kind = 0;
-    int rc = s->ensure(n, max_px, tier);
+    int rc = s->lay_out(n, max_px, tier);
     if (rc) return rc;
     if (any_gap && (rc = s->gap.reserve((size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)n))) return rc;
-    { const int arc = s->h_units.assign((size_t)n, MicUnit{}); if (arc) return arc; }
     bool any_grad = false;
     uint32_t rows_kmask = 0;                                             // predictor classes (by width) this batch holds
     for (int i = 0; i < n; i++) {
@@ -346,17 +337,12 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
         u.w = units[i].width; u.h = units[i].height;
         u.pred = (units[i].nstates & MIC_HIP_PRED_GRAD) ? 1u : 0u; any_grad |= u.pred != 0;
         if (units[i].nstates & MIC_HIP_GAP_REMOVAL) { u.gap = 1; u.gap_buf = (uint8_t *)s->gap.p + (size_t)mic_gap_stride((uint32_t)s->tab_syms) * (size_t)i; }
-        s->fill_workspace(u, i);
         u.tok_cap = (uint32_t)tok_cap_tier((size_t)u.w * (size_t)u.h, tier);
         u.sym_cap = (uint32_t)std::min<size_t>(tok_cap_for((size_t)u.w * (size_t)u.h) + 64, 0xFFFFFFF0u);   // (a bound on the symbols a frame can use, not a slab size: the symbol slab is idle on this side)
     }
-    { const int urc = s->h_units.upload(s->units.p, (size_t)n, s->stream); if (urc) return urc; }
-    HIP_TRY(hipMemsetAsync(s->flags.p, 0, s->flag_stride * (size_t)n, s->stream));
-    s->timer.reset(s->stream);
-    mic_launch_decode((MicUnit *)s->units.p, n, s->stream, s->variant | (any_grad ? MIC_VARIANT_GRAD : 0) | (any_gap ? MIC_VARIANT_GAP : 0), &s->timer, (int *)s->cls.p, rows_kmask,
-                      s->dec_classes.mask());
-    HIP_TRY(hipGetLastError());
-    s->begin_chain(n);
+    const int variant = s->variant | (any_grad ? MIC_VARIANT_GRAD : 0) | (any_gap ? MIC_VARIANT_GAP : 0);
+    if ((rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
+            mic_launch_decode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, (int *)s->cls.p, rows_kmask, s->dec_classes.mask()); }))) return rc;
     s->learn_decode = true;
     HIP_TRY(hipMemcpyAsync(s->h_units.data(), s->units.p, sizeof(MicUnit) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
     s->readback_queued = true;
@@ -391,9 +377,6 @@ size_t batch_units_for(size_t px, size_t mult, size_t extra) {
     return std::max<size_t>(1, std::min(n1, n2));
 }
 
-void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-uint32_t get_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 }  // namespace micapi
 
 // ================================================================================ C ABI
@@ -408,9 +391,9 @@ int mic_hip_device_copy(void *d_dst, const void *d_src, size_t bytes) try {
     if ((!d_dst || !d_src) && bytes) return MIC_ERR_ARGS;
     if (bytes) HIP_TRY(hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice));
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
-int mic_hip_set_device(int device) try { return mic_hip_set_devices(&device, 1); } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+int mic_hip_set_device(int device) try { return mic_hip_set_devices(&device, 1); } MIC_ABI_CATCH
 
 int mic_hip_set_devices(const int *devices, int n) try {
     if (!devices || n <= 0 || n > 64) return MIC_ERR_ARGS;
@@ -433,12 +416,12 @@ int mic_hip_set_devices(const int *devices, int n) try {
     if (g_device != devices[0]) g_device_ok = false;
     g_device = devices[0];
     return ensure_device_locked();
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_get_devices(int *devices, int cap) try {
     std::lock_guard<std::mutex> lk(g_mu);
     for (int i = 0; i < (int)g_devices.size() && i < cap; i++) if (devices) devices[i] = g_devices[(size_t)i];
     return (int)g_devices.size();
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 const char *mic_hip_device_name(void) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -457,7 +440,7 @@ int mic_hip_compress_frame(const uint16_t *pixels, int width, int height, uint16
     if (rc) return rc;
     if (j.status == MIC_OK) *out_len = j.out_len;
     return j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_decompress_frame(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height) try {
     if (!compressed || !pixels_out || width <= 0 || height <= 0) return MIC_ERR_ARGS;
@@ -466,7 +449,7 @@ int mic_hip_decompress_frame(const uint8_t *compressed, size_t compressed_len, u
     int rc = mic_hip_decompress_batch(&j, 1);
     if (rc) return rc;
     return j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- gap removal (gapremovalcompressu16.go:52-282): the unit codec with MIC_HIP_GAP_REMOVAL, through the batch pipeline
 int mic_hip_compress_frame_gap(const uint16_t *pixels, int width, int height, uint16_t max_value, int nstates,
@@ -480,7 +463,7 @@ int mic_hip_compress_frame_gap(const uint16_t *pixels, int width, int height, ui
     if (rc) return rc;
     if (j.status == MIC_OK) *out_len = j.out_len;
     return j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_decompress_frame_gap(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height) try {
     if (!compressed || !pixels_out || width <= 0 || height <= 0) return MIC_ERR_ARGS;
@@ -489,12 +472,12 @@ int mic_hip_decompress_frame_gap(const uint8_t *compressed, size_t compressed_le
     int rc = mic_hip_decompress_batch_gap(&j, 1);
     if (rc) return rc;
     return j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- bare FSE stage (fsecompressu16.go:19, fse2state.go:22/102, fse4state.go:24, fse8state.go:31, rans8state.go:31)
 int mic_hip_fse_compress_u16(const uint16_t *symbols, size_t n, int flavour, uint8_t *out, size_t out_cap, size_t *out_len) try {
     return mic_hip_fse_compress_u16_ex(symbols, n, flavour, 0, out, out_cap, out_len);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_fse_compress_u16_ex(const uint16_t *symbols, size_t n, int flavour, int table_log, uint8_t *out, size_t out_cap, size_t *out_len) try {
     if (!symbols || !out || !out_len) return MIC_ERR_ARGS;
@@ -507,19 +490,13 @@ int mic_hip_fse_compress_u16_ex(const uint16_t *symbols, size_t n, int flavour, 
     if (rc) return rc;
     mic_hip_session *s = cur_default();
     const size_t px = (n + 3) / 4 + 16;
-    if ((rc = s->ensure(1, px))) return rc;
+    if ((rc = s->lay_out(1, px))) return rc;
     if ((rc = s->io_px.reserve(n * 2 + 64))) return rc;
     HIP_TRY(hipMemcpyAsync(s->io_px.p, symbols, n * 2, hipMemcpyHostToDevice, s->stream));
-    { const int arc = s->h_units.assign(1, MicUnit{}); if (arc) return arc; }
     MicUnit &u = s->h_units[0];
     u.px_in = (const uint16_t *)s->io_px.p; u.w = (int32_t)n; u.h = 1; u.max_value = 0;
     u.nstates = (uint16_t)flavour; u.mode = 1; u.no_fallback = 1; u.req_tl = (uint32_t)table_log;
-    s->fill_workspace(u, 0);
-    { const int urc = s->h_units.upload(s->units.p, 1, s->stream); if (urc) return urc; }
-    if ((rc = s->prepare_hist(1))) return rc;
-    mic_launch_encode((MicUnit *)s->units.p, 1, s->stream, s->variant, nullptr);
-    if (hipGetLastError() != hipSuccess) { s->hist_unknown(); return MIC_ERR_DEVICE; }
-    s->begin_chain(1);
+    if ((rc = s->run_encode([&] { mic_launch_encode((MicUnit *)s->units.p, 1, s->stream, s->variant, nullptr); }))) return rc;
     uint64_t offs[2]; int32_t st = 0, ns = 0; const uint8_t *d_blobs = nullptr;
     if ((rc = session_encode_finish(s, &d_blobs, offs, &st, &ns))) return rc;
     if (st != MIC_OK) return st;
@@ -528,11 +505,11 @@ int mic_hip_fse_compress_u16_ex(const uint16_t *symbols, size_t n, int flavour, 
     HIP_TRY(hipMemcpy(out, d_blobs, len, hipMemcpyDeviceToHost));
     *out_len = len;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_fse_decompress_u16_auto(const uint8_t *in, size_t in_len, uint16_t *out, size_t out_cap, size_t *out_n) try {
     return mic_hip_fse_decompress_u16_ex(in, in_len, 0, out, out_cap, out_n);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ScratchU16.DecompressLimit (fseu16.go:87-91): the reference compares len(OutU16) with the limit every time its 65536-symbol ring
 // wraps (fse2state.go:249/283, fse4state.go:246/..., fse8state.go, fsedecompressu16.go:318/353) and, for 1-state streams, once more
@@ -552,18 +529,13 @@ int mic_hip_fse_decompress_u16_ex(const uint8_t *in, size_t in_len, int64_t deco
     if (rc) return rc;
     mic_hip_session *s = cur_default();
     const size_t px = (out_cap + 3) / 4 + 16;
-    if ((rc = s->ensure(1, px))) return rc;
+    if ((rc = s->lay_out(1, px))) return rc;
     if ((rc = s->io_comp.reserve(in_len + 64))) return rc;
     HIP_TRY(hipMemcpyAsync(s->io_comp.p, in, in_len, hipMemcpyHostToDevice, s->stream));
-    { const int arc = s->h_units.assign(1, MicUnit{}); if (arc) return arc; }
     MicUnit &u = s->h_units[0];
     u.comp_in = (const uint8_t *)s->io_comp.p; u.comp_len = (uint32_t)in_len; u.w = 1; u.h = 1; u.mode = 1;
-    s->fill_workspace(u, 0);
     u.tok_cap = (uint32_t)std::min<size_t>(out_cap, u.tok_cap);
-    { const int urc = s->h_units.upload(s->units.p, 1, s->stream); if (urc) return urc; }
-    mic_launch_decode((MicUnit *)s->units.p, 1, s->stream, s->variant, nullptr, (int *)s->cls.p);
-    HIP_TRY(hipGetLastError());
-    s->begin_chain(1);
+    if ((rc = s->run_decode(mic_hip_session::FlagSlab::Idle, [&] { mic_launch_decode((MicUnit *)s->units.p, 1, s->stream, s->variant, nullptr, (int *)s->cls.p); }))) return rc;
     int32_t st = 0;
     if ((rc = session_decode_finish(s, &st))) return rc;
     if (st != MIC_OK) return st;
@@ -573,7 +545,7 @@ int mic_hip_fse_decompress_u16_ex(const uint8_t *in, size_t in_len, int64_t deco
     if (n) HIP_TRY(hipMemcpy(out, s->h_units[0].tok, n * 2, hipMemcpyDeviceToHost));
     *out_n = n;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- PICS / MIC2 headers (the container codecs themselves: mic_host_io.hip) ------------------------
 int mic_hip_pics_info(const uint8_t *c, size_t len, int *width, int *height, int *num_strips, int *strip_height) try {
@@ -584,13 +556,13 @@ int mic_hip_pics_info(const uint8_t *c, size_t len, int *width, int *height, int
     if (w <= 0 || h <= 0 || n <= 0 || sh <= 0) return MIC_ERR_CORRUPT;   // :284-286
     if (width) *width = w; if (height) *height = h; if (num_strips) *num_strips = n; if (strip_height) *strip_height = sh;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_mic2_compress_temporal(const uint16_t *frames, int width, int height, int nframes, uint16_t max_value,
                                    uint8_t *out, size_t out_cap, size_t *out_len) try {
     if (!frames || !out || !out_len || width <= 0 || height <= 0 || nframes <= 0) return MIC_ERR_ARGS;
     return mic2_temporal_compress(frames, width, height, nframes, max_value, out, out_cap, out_len);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_mic2_info(const uint8_t *c, size_t len, int *width, int *height, int *nframes, int *temporal) try {
     if (!c) return MIC_ERR_ARGS;
@@ -599,7 +571,7 @@ int mic_hip_mic2_info(const uint8_t *c, size_t len, int *width, int *height, int
     if (n < 0 || (size_t)n > (len - 20) / 8) return MIC_ERR_CORRUPT;     // :112-116
     if (width) *width = w; if (height) *height = h; if (nframes) *nframes = n; if (temporal) *temporal = (c[16] & 0x02) != 0;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressFrame (multiframecompress.go:266-315): one frame of a MIC2 file.  Independent mode decodes just that
 // frame; temporal mode needs frames 0..idx (all their residual streams are decoded at once, mic_temporal.hip).
@@ -623,7 +595,7 @@ int mic_hip_mic2_decompress_frame(const uint8_t *c, size_t len, int frame_idx, u
     if (rc) return rc;
     memcpy(pixels_out, tmp.data() + npx * (size_t)frame_idx, npx * 2);
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- sessions ------------------------------------------------------------------------------------
 int mic_hip_session_create_on(int device, mic_hip_session **out, int max_units, size_t max_px_per_unit) try {
@@ -637,13 +609,13 @@ int mic_hip_session_create_on(int device, mic_hip_session **out, int max_units, 
     if (rc) { s->release(); delete s; return rc; }
     *out = s;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_create(mic_hip_session **out, int max_units, size_t max_px_per_unit) try {
     int dev;
     { std::lock_guard<std::mutex> lk(g_mu); dev = g_device; }
     return mic_hip_session_create_on(dev, out, max_units, max_px_per_unit);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
-int mic_hip_session_device(mic_hip_session *s) try { return s ? s->device : -1; } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
+int mic_hip_session_device(mic_hip_session *s) try { return s ? s->device : -1; } MIC_ABI_CATCH
 // device memory the session holds right now (workspace slabs, staging, stores), and whether a batch has needed the tier-2 slabs
 size_t mic_hip_session_workspace_bytes(mic_hip_session *s, int *tier2) {
     if (!s) return 0;
@@ -657,35 +629,35 @@ int mic_hip_session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels,
     if (!s || !d_pixels || !units) return MIC_ERR_ARGS;
     { const int arc = s->activate(); if (arc) return arc; }
     return session_encode_enqueue(s, d_pixels, units, n);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_encode_finish(mic_hip_session *s, const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *h_status, int32_t *h_nstates) try {
     if (!s || !h_offsets || !h_status) return MIC_ERR_ARGS;
     { const int arc = s->activate(); if (arc) return arc; }
     return session_encode_finish(s, d_blobs, h_offsets, h_status, h_nstates);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_encode(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n,
                            const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *h_status, int32_t *h_nstates) try {
     int rc = mic_hip_session_encode_enqueue(s, d_pixels, units, n);
     if (rc) return rc;
     return mic_hip_session_encode_finish(s, d_blobs, h_offsets, h_status, h_nstates);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_decode_enqueue(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets,
                                    const mic_hip_unit *units, int n, uint16_t *d_pixels_out) try {
     if (!s || !d_blobs || !h_offsets || !units || !d_pixels_out) return MIC_ERR_ARGS;
     { const int arc = s->activate(); if (arc) return arc; }
     return session_decode_enqueue(s, d_blobs, h_offsets, units, n, d_pixels_out);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_decode_finish(mic_hip_session *s, int32_t *h_status) try {
     if (!s || !h_status) return MIC_ERR_ARGS;
     { const int arc = s->activate(); if (arc) return arc; }
     return session_decode_finish(s, h_status);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_decode(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets, const mic_hip_unit *units, int n,
                            uint16_t *d_pixels_out, int32_t *h_status) try {
     int rc = mic_hip_session_decode_enqueue(s, d_blobs, h_offsets, units, n, d_pixels_out);
     if (rc) return rc;
     return mic_hip_session_decode_finish(s, h_status);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 // debug probe (not part of the public header): raw result fields of unit i after a *_finish
 int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {
     if (!s || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
@@ -695,26 +667,26 @@ int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {
     out8[8] = u.count; out8[9] = u.bits_off; out8[10] = (uint32_t)u.nstates_used; out8[11] = (uint32_t)u.status; out8[12] = u.nseg; out8[13] = u.nsym; out8[14] = u.seg_cap;
     for (int k = 0; k < 16; k++) out8[16 + k] = u.dbg[k];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 // debug probe (not in the public header): bytes of unit i's histogram slab after a *_finish (LS_DEBUG builds dump there)
 int mic_hip_debug_fetch_hist(mic_hip_session *s, int i, void *dst, size_t bytes) try {
     if (!s || i < 0 || i >= s->n_last || bytes > kSym * 4) return MIC_ERR_ARGS;
     HIP_TRY(hipMemcpy(dst, s->h_units[(size_t)i].hist, bytes, hipMemcpyDeviceToHost));
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 // debug probe (not in the public header): the first n u16 of unit i's token slab after a *_finish
 int mic_hip_debug_fetch_tok(mic_hip_session *s, int i, void *dst, size_t n) try {
     if (!s || i < 0 || i >= s->n_last || n > s->h_units[(size_t)i].tok_cap) return MIC_ERR_ARGS;
     HIP_TRY(hipMemcpy(dst, s->h_units[(size_t)i].tok, n * 2, hipMemcpyDeviceToHost));
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled) try {
     if (!s) return MIC_ERR_ARGS;
     s->timer.enabled = enabled != 0;
     s->timer.accumulate = enabled == 2;                                   // 2: sum over every launch chain until the next set_timing
     s->timer.clear();
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_session_last_timings(mic_hip_session *s, const char **names, float *ms, int cap) try {
     if (!s) return 0;
     s->t_names.clear(); s->t_ms.clear();
@@ -733,6 +705,6 @@ int mic_hip_session_last_timings(mic_hip_session *s, const char **names, float *
     int n = (int)std::min<size_t>(s->t_names.size(), (size_t)std::max(cap, 0));
     for (int i = 0; i < n; i++) { names[i] = s->t_names[(size_t)i].c_str(); ms[i] = s->t_ms[(size_t)i]; }
     return n;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"

@@ -22,11 +22,6 @@ struct WsiPlane { uint8_t mode; uint16_t value; uint64_t off, len; };
 
 namespace {
 
-void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-uint32_t get_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-void put_u64(uint8_t *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
-uint64_t get_u64(const uint8_t *p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
-
 // Downsample2xRGB (wsipyramid.go:10-32): (v00+v10+v01+v11+2)/4 per channel, odd edge dropped.
 __global__ void __launch_bounds__(256) k_wsi_downsample(const uint8_t *src, int sw, uint8_t *dst, int dw, int dh) {
     const size_t n = (size_t)dw * dh * 3;
@@ -754,7 +749,7 @@ int mic_hip_wsi_band_plan(int width, int height, int tile_w, int tile_h, int lev
     if (tile_h == 0) tile_h = 256;
     *k_out = band_plan(height, tile_h, (int)plan_levels(width, height, tile_w, tile_h, levels).size(), shards, row_first);
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // CompressWSI (wsicompress.go:27-171): 8-bit RGB (channels 3) or 8/16-bit greyscale (channels 1, little-endian samples).
 // Bands of tile rows over the devices of mic_hip_set_devices when that gives two or more (and the call is not nested), else one band.
@@ -778,7 +773,7 @@ int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int chann
     std::vector<int> row_first(2);                                                          // the default device, or the session held
     const int K = band_plan(height, fmt.th, (int)lv.size(), 1, row_first.data());
     return wsi_compress_bands(rgb, fmt, lv, K, row_first, std::vector<int>(1, -1), out, out_cap, out_len);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // CompressRGB (rgbcompress.go:25-27) = compressRGBTileBlob on the whole image: one "tile" of width x height
 int mic_hip_rgb_compress(const uint8_t *rgb, int width, int height, uint8_t *out, size_t out_cap, size_t *out_len) try {
@@ -799,7 +794,7 @@ int mic_hip_rgb_compress(const uint8_t *rgb, int width, int height, uint8_t *out
     memcpy(out, blob.bytes.data(), blob.bytes.size());
     *out_len = blob.bytes.size();
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressRGB (rgbcompress.go:31-33)
 int mic_hip_rgb_decompress(const uint8_t *c, size_t len, int width, int height, uint8_t *rgb_out, size_t out_cap) try {
@@ -811,7 +806,7 @@ int mic_hip_rgb_decompress(const uint8_t *c, size_t len, int width, int height, 
     int rc = lease.acquire();
     if (rc) return rc;
     return decode_blobs(m, std::vector<TileBlob>(1, TileBlob{ c, len }), std::vector<int4>(1, make_int4(0, 0, width, height)), rgb_out, width, height);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // MICR file = "MICR", width, height (u32 LE), CompressRGB blob (writeMICRFile, cmd/mic-compress/main.go:62-91)
 int mic_hip_micr_compress(const uint8_t *rgb, int width, int height, uint8_t *out, size_t out_cap, size_t *out_len) try {
@@ -823,7 +818,7 @@ int mic_hip_micr_compress(const uint8_t *rgb, int width, int height, uint8_t *ou
     memcpy(out, "MICR", 4); put_u32(out + 4, (uint32_t)width); put_u32(out + 8, (uint32_t)height);
     *out_len = 12 + n;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_micr_info(const uint8_t *c, size_t len, int *width, int *height) try {
     if (!c) return MIC_ERR_ARGS;
     if (len < 12 || memcmp(c, "MICR", 4) != 0) return MIC_ERR_CORRUPT;
@@ -831,13 +826,13 @@ int mic_hip_micr_info(const uint8_t *c, size_t len, int *width, int *height) try
     if (w == 0 || h == 0 || w > (1u << 26) || h > (1u << 26)) return MIC_ERR_CORRUPT;
     if (width) *width = (int)w; if (height) *height = (int)h;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_micr_decompress(const uint8_t *c, size_t len, uint8_t *rgb_out, size_t out_cap) try {
     int w = 0, h = 0;
     const int rc = mic_hip_micr_info(c, len, &w, &h);
     if (rc) return rc;
     return mic_hip_rgb_decompress(c + 12, len - 12, w, h, rgb_out, out_cap);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // MIC1 file = "MIC1", width, height, pipeline 1, payload length (u32 LE each), CompressSingleFrame stream
 // (writeMicFile, cmd/mic-compress/main.go:26-59; the stream's own magic tells the state count)
@@ -852,7 +847,7 @@ int mic_hip_mic1_compress(const uint16_t *pixels, int width, int height, uint16_
     memcpy(out, "MIC1", 4); put_u32(out + 4, (uint32_t)width); put_u32(out + 8, (uint32_t)height); put_u32(out + 12, 1); put_u32(out + 16, (uint32_t)n);
     *out_len = 20 + n;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_mic1_info(const uint8_t *c, size_t len, int *width, int *height) try {
     if (!c) return MIC_ERR_ARGS;
     if (len < 20 || memcmp(c, "MIC1", 4) != 0) return MIC_ERR_CORRUPT;
@@ -860,19 +855,19 @@ int mic_hip_mic1_info(const uint8_t *c, size_t len, int *width, int *height) try
     if (w == 0 || h == 0 || w > (1u << 26) || h > (1u << 26) || get_u32(c + 12) != 1 || (size_t)get_u32(c + 16) > len - 20) return MIC_ERR_CORRUPT;
     if (width) *width = (int)w; if (height) *height = (int)h;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_mic1_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, size_t out_cap_px) try {
     int w = 0, h = 0;
     const int rc = mic_hip_mic1_info(c, len, &w, &h);
     if (rc) return rc;
     if ((size_t)w * h > out_cap_px) return MIC_ERR_CAPACITY;
     return mic_hip_decompress_frame(c + 20, get_u32(c + 16), pixels_out, w, h);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wsi_compress(const uint8_t *rgb, int width, int height, int tile_w, int tile_h, int levels,
                          uint8_t *out, size_t out_cap, size_t *out_len) try {
     return mic_hip_wsi_compress_ex(rgb, width, height, 3, 8, tile_w, tile_h, levels, out, out_cap, out_len);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // WSIHeader.Channels / BitsPerSample / ColorTransform (wsiformat.go:169-227)
 int mic_hip_wsi_format(const uint8_t *c, size_t len, int *channels, int *bits_per_sample, int *color_transform) try {
@@ -881,7 +876,7 @@ int mic_hip_wsi_format(const uint8_t *c, size_t len, int *channels, int *bits_pe
     if (rc) return rc;
     if (channels) *channels = m.channels; if (bits_per_sample) *bits_per_sample = m.bps; if (color_transform) *color_transform = (m.flags & 0x02) ? 1 : 0;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ReadWSIHeader (wsicompress.go:299-306)
 int mic_hip_wsi_info(const uint8_t *c, size_t len, int *width, int *height, int *tile_w, int *tile_h, int *levels, uint64_t *total_tiles) try {
@@ -891,7 +886,7 @@ int mic_hip_wsi_info(const uint8_t *c, size_t len, int *width, int *height, int 
     if (width) *width = m.w; if (height) *height = m.h; if (tile_w) *tile_w = m.tw; if (tile_h) *tile_h = m.th;
     if (levels) *levels = m.nlev; if (total_tiles) *total_tiles = m.total;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_wsi_level_info(const uint8_t *c, size_t len, int level, int *width, int *height, int *tiles_x, int *tiles_y) try {
     if (!c) return MIC_ERR_ARGS;
     Mic3 m; int rc = parse_mic3(c, len, m);
@@ -900,7 +895,7 @@ int mic_hip_wsi_level_info(const uint8_t *c, size_t len, int level, int *width, 
     const Level &L = m.lv[(size_t)level];
     if (width) *width = L.w; if (height) *height = L.h; if (tiles_x) *tiles_x = L.tx; if (tiles_y) *tiles_y = L.ty;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressWSITile (wsicompress.go:175-217): one tile, cropped at the level's edge
 int mic_hip_wsi_decompress_tile(const uint8_t *c, size_t len, int level, int tile_x, int tile_y,
@@ -909,7 +904,7 @@ int mic_hip_wsi_decompress_tile(const uint8_t *c, size_t len, int level, int til
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
     return wsi_tile(flat_source(c, len, m), m, level, tile_x, tile_y, rgb_out, out_cap, out_w, out_h);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // Whole pyramid level in one batch: every tile of the level, stitched (viewer / bench path)
 int mic_hip_wsi_decompress_level(const uint8_t *c, size_t len, int level, uint8_t *rgb_out, size_t out_cap) try {
@@ -922,7 +917,7 @@ int mic_hip_wsi_decompress_level(const uint8_t *c, size_t len, int level, uint8_
     if (L.w <= 0 || L.h <= 0 || (size_t)L.w * L.h * m.bpp() > out_cap) return (L.w <= 0 || L.h <= 0) ? MIC_ERR_CORRUPT : MIC_ERR_CAPACITY;
     if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
     return decode_box(c, len, m, L, 0, L.tx - 1, 0, L.ty - 1, 0, L.w, L.h, rgb_out);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressWSIRegion (wsicompress.go:219-297): the tiles that overlap the rectangle are decoded in one batch into
 // their tile-aligned bounding box, the rectangle is cut out of it.  w / h are clamped to the level like the reference does.
@@ -932,7 +927,7 @@ int mic_hip_wsi_decompress_region(const uint8_t *c, size_t len, int level, int x
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
     return wsi_region(flat_source(c, len, m), m, level, x, y, w, h, rgb_out, out_cap, out_w, out_h);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 
 }  // extern "C"
@@ -1039,7 +1034,7 @@ int mic_hip_session_wsi_encode(mic_hip_session *s, const uint8_t *d_pixels, int 
         *compressed_bytes = n;
     }
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // The store as the container's payload, on the device: *d_payload (valid until the session's next wsi call), its size, and the
 // byte length of every tile in container order (tile_lens[cap >= total tiles], host).  What a multi-GPU writer gathers.
@@ -1052,7 +1047,7 @@ int mic_hip_session_wsi_payload(mic_hip_session *s, const uint8_t **d_payload, u
     if ((rc = wsi_assemble(s, tile_lens, payload_bytes))) return rc;
     *d_payload = (const uint8_t *)s->wsi_payload.p;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // WriteMIC3 (wsiformat.go:99-165) around the store: one device-to-host copy of the assembled payload, then header, level table and
 // tile index in front of it
@@ -1070,7 +1065,7 @@ int mic_hip_session_wsi_write(mic_hip_session *s, uint8_t *out, size_t out_cap, 
     put_mic3_index(out, W.fmt, W.lv, tlen);
     *out_len = hdr + (size_t)total;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // every tile of one level, from the store, into a device image of the level's size (bytes per pixel as the slide's)
 int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_pixels_out, size_t out_cap) try {
@@ -1095,14 +1090,14 @@ int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_p
                                 s->wsi_planes, s->wsi_stats, d_pixels_out, L.w))) return rc;
     }
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int *heights, int cap) try {
     if (!s || !s->wsi || !levels) return MIC_ERR_ARGS;
     *levels = (int)s->wsi->lv.size();
     for (int i = 0; i < *levels && i < cap; i++) { if (widths) widths[i] = s->wsi->lv[(size_t)i].w; if (heights) heights[i] = s->wsi->lv[(size_t)i].h; }
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"
 
@@ -1391,7 +1386,7 @@ int mic_hip_wsi_writer_open(int width, int height, int channels, int bits_per_sa
     w->note_host();
     *out = w.release();
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wsi_writer_push_rows(mic_hip_wsi_writer *w, const uint8_t *rows, int nrows) try {
     if (!w) return MIC_ERR_ARGS;
@@ -1409,7 +1404,7 @@ int mic_hip_wsi_writer_push_rows(mic_hip_wsi_writer *w, const uint8_t *rows, int
     if (rc == MIC_OK && hipStreamSynchronize(w->s->stream) != hipSuccess) rc = MIC_ERR_DEVICE;   // the caller's rows are consumed
     if (rc) w->err = rc;
     return rc;
-} catch (const std::bad_alloc &) { w->err = MIC_ERR_NOMEM; return MIC_ERR_NOMEM; } catch (...) { w->err = MIC_ERR_INTERNAL; return MIC_ERR_INTERNAL; }
+} catch (...) { return w->err = exception_code(); }
 
 int mic_hip_wsi_writer_finish(mic_hip_wsi_writer *w, uint64_t *file_len) try {
     if (!w) return MIC_ERR_ARGS;
@@ -1432,7 +1427,7 @@ int mic_hip_wsi_writer_finish(mic_hip_wsi_writer *w, uint64_t *file_len) try {
     w->done = true;
     if (file_len) *file_len = off;
     return MIC_OK;
-} catch (const std::bad_alloc &) { w->err = MIC_ERR_NOMEM; return MIC_ERR_NOMEM; } catch (...) { w->err = MIC_ERR_INTERNAL; return MIC_ERR_INTERNAL; }
+} catch (...) { return w->err = exception_code(); }
 
 int mic_hip_wsi_writer_device_bytes(const mic_hip_wsi_writer *w, uint64_t *bytes) {
     if (!w || !bytes) return MIC_ERR_ARGS;
@@ -1466,7 +1461,7 @@ int mic_hip_wsi_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len,
     if ((rc = parse_mic3_levels(r->head.data(), r->m))) return rc;
     *out = r.release();
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wsi_reader_info(const mic_hip_wsi_reader *r, int *width, int *height, int *tile_w, int *tile_h, int *levels,
                             int *channels, int *bits_per_sample) {
@@ -1481,14 +1476,14 @@ int mic_hip_wsi_reader_decompress_tile(mic_hip_wsi_reader *r, int level, int til
     if (!r || !out) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     return wsi_tile(r->source(), r->m, level, tile_x, tile_y, out, out_cap, out_w, out_h);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x, int y, int w, int h,
                                          uint8_t *out, size_t out_cap, int *out_w, int *out_h) try {
     if (!r || !out) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     return wsi_region(r->source(), r->m, level, x, y, w, h, out, out_cap, out_w, out_h);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
 

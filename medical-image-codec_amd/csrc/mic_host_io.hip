@@ -17,11 +17,6 @@
 #include <deque>
 #include <thread>
 
-namespace micapi {
-void put_u32(uint8_t *p, uint32_t v);
-uint32_t get_u32(const uint8_t *p);
-}
-
 namespace {
 
 // ============================================================================ transfer engine
@@ -492,7 +487,7 @@ int run_parallel(int n, const std::function<int(int)> &work) {
     std::vector<int> rcs((size_t)std::max(n, 0), MIC_OK);
     auto one = [&](int k) {
         try { rcs[(size_t)k] = work(k); }
-        catch (const std::bad_alloc &) { rcs[(size_t)k] = MIC_ERR_NOMEM; } catch (...) { rcs[(size_t)k] = MIC_ERR_INTERNAL; }
+        catch (...) { rcs[(size_t)k] = exception_code(); }
     };
     std::vector<std::thread> th;
     int started = 1;                                  // 1 .. started - 1 have a thread; what could not get one runs here, one after the other
@@ -517,7 +512,7 @@ int mic_hip_shard_plan(const uint64_t *weights, int n, int shards, int *first) t
     if (!weights || !first || n < 0 || shards <= 0) return MIC_ERR_ARGS;
     shard_plan(weights, n, shards, first);
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // Pinned host memory for a caller's frame and stream buffers: the entry points below DMA such buffers in place instead of
 // staging them through the transfer engine's slots.
@@ -555,10 +550,10 @@ static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
 }
 int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
     return compress_jobs(jobs, njobs, 0);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_compress_batch_gap(mic_hip_enc_job *jobs, int njobs) try {
     return compress_jobs(jobs, njobs, MIC_HIP_GAP_REMOVAL);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
@@ -582,10 +577,10 @@ static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
 }
 int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs) try {
     return decompress_jobs(jobs, njobs, 0);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs) try {
     return decompress_jobs(jobs, njobs, MIC_HIP_GAP_REMOVAL);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- PICS (parallelstrips.go) ----------------------------------------------------------------
 int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
@@ -633,12 +628,12 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
         j.out_len = g.hdr + g.written;
     }
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_pics_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips, int nstates,
                           uint8_t *out, size_t out_cap, size_t *out_len) try {
     return mic_hip_pics_compress_ex(pixels, width, height, max_value, num_strips, nstates, out, out_cap, out_len, nullptr);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_pics_compress_ex(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips, int nstates,
                              uint8_t *out, size_t out_cap, size_t *out_len, int *failed_strip) try {
     if (failed_strip) *failed_strip = -1;
@@ -652,7 +647,7 @@ int mic_hip_pics_compress_ex(const uint16_t *pixels, int width, int height, uint
     if (j.status == MIC_OK) *out_len = j.out_len;
     else if (failed_strip) *failed_strip = j.failed_strip;
     return j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs) try {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
@@ -692,11 +687,11 @@ int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs) try {
     if ((rc = decode_sharded(G, U))) return rc;
     for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "strip %d: %w", parallelstrips.go:316
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_pics_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
     return mic_hip_pics_decompress_ex(c, len, pixels_out, width, height, nullptr);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 int mic_hip_pics_decompress_ex(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height, int *failed_strip) try {
     if (failed_strip) *failed_strip = -1;
     if (!c || !pixels_out) return MIC_ERR_ARGS;
@@ -705,7 +700,7 @@ int mic_hip_pics_decompress_ex(const uint8_t *c, size_t len, uint16_t *pixels_ou
     const int rc = mic_hip_pics_decompress_batch(&j, 1);
     if (rc == MIC_OK && j.status != MIC_OK && failed_strip) *failed_strip = j.failed_strip;
     return rc ? rc : j.status;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- MIC2 independent mode (multiframe.go, multiframecompress.go:179-261) -----------------------
 int mic_hip_mic2_compress(const uint16_t *frames, int width, int height, int nframes, uint16_t max_value,
@@ -751,7 +746,7 @@ int mic_hip_mic2_compress(const uint16_t *frames, int width, int height, int nfr
     }
     *out_len = header + G[0].written;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, size_t frames_cap_px) try {
     if (!c || !frames_out) return MIC_ERR_ARGS;
@@ -780,6 +775,6 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
     if ((rc = decode_sharded(G, U))) return rc;
     for (const DecGroup &g : G) if (g.status != MIC_OK) return g.status;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"

@@ -10,9 +10,6 @@
 
 namespace {
 
-void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-uint32_t get_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 // rowCost[y] = sum over x of |p[y][x] - p[y-1][x]|, y >= 1 (parallelstripsadaptive.go:236-247).  One group per row.
 __global__ void __launch_bounds__(256) k_pica_rowcost(const uint16_t *px, int w, int h, unsigned long long *cost) {
     const int y = (int)blockIdx.x + 1;
@@ -79,7 +76,7 @@ int mic_hip_compress_frame_grad(const uint16_t *pixels, int width, int height, u
     HIP_TRY(hipMemcpy(out, d_blobs + offs[0], len, hipMemcpyDeviceToHost));
     *out_len = len;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressSingleFrameGrad (multiframecompress.go:132-142)
 int mic_hip_decompress_frame_grad(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
@@ -103,7 +100,7 @@ int mic_hip_decompress_frame_grad(const uint8_t *c, size_t len, uint16_t *pixels
     if (st != MIC_OK) return st;
     HIP_TRY(hipMemcpy(pixels_out, s->io_px.p, npx * 2, hipMemcpyDeviceToHost));
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // CompressParallelStripsAdaptive (parallelstripsadaptive.go:54-137)
 int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
@@ -196,7 +193,7 @@ int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_
     }
     *out_len = header + total;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_pica_info(const uint8_t *c, size_t len, int *width, int *height, int *num_strips) try {
     if (!c) return MIC_ERR_ARGS;
@@ -206,7 +203,7 @@ int mic_hip_pica_info(const uint8_t *c, size_t len, int *width, int *height, int
     if (w <= 0 || h <= 0 || n <= 0) return MIC_ERR_CORRUPT;                                 // :154-156
     if (width) *width = w; if (height) *height = h; if (num_strips) *num_strips = n;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141-214)
 int mic_hip_pica_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
@@ -262,6 +259,6 @@ int mic_hip_pica_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, 
     }
     HIP_TRY(hipMemcpy(pixels_out, s->io_px.p, npx * 2, hipMemcpyDeviceToHost));
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 #include "mic_dev.h"
 #include "mic_launch.h"
 
+struct mic_hip_session;
+
 #define HIP_TRY(expr)                                                                     \
     do {                                                                                  \
         hipError_t _e = (expr);                                                           \
@@ -30,6 +32,19 @@
     } while (0)
 
 namespace micapi {
+
+// No C++ exception crosses the C ABI: every extern "C" entry point is a function-try-block closed by MIC_ABI_CATCH.
+// exception_code(): the status of the exception in flight (call it inside a catch block only).
+inline int exception_code() {
+    try { throw; } catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }
+}
+#define MIC_ABI_CATCH catch (...) { return micapi::exception_code(); }
+
+// little-endian fields of the container headers
+inline void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+inline uint32_t get_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+inline void put_u64(uint8_t *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
+inline uint64_t get_u64(const uint8_t *p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
 
 extern std::mutex g_mu;     // guards the device choice and the pool of default sessions (mic_api.hip)
 extern int g_device;
@@ -66,7 +81,15 @@ struct DevBuf {
 // The host copy of a launch's unit descriptors, in pinned memory: the upload in front of every launch chain and the download of
 // the results behind it are DMA transfers that really are asynchronous (a pageable vector cost ~0.1 ms of staging each way per call).
 // Because the upload is asynchronous, the descriptors may not be rewritten while it is in flight: assign() waits for it.
+// Only the session's chain protocol (lay_out / run_encode / run_decode) writes and uploads them.
 struct PinnedUnits {
+    MicUnit *data() { return p; }
+    MicUnit &operator[](size_t i) { return p[i]; }
+    const MicUnit &operator[](size_t i) const { return p[i]; }
+    size_t size() const { return n; }
+    void release() { if (inflight) (void)hipEventSynchronize(ev); inflight = false; if (p) (void)hipHostFree(p); p = nullptr; cap = n = 0; if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+private:
+    friend struct ::mic_hip_session;
     MicUnit *p = nullptr; size_t cap = 0, n = 0;
     hipEvent_t ev = nullptr; bool inflight = false;
     int assign(size_t count, const MicUnit &v) {
@@ -89,11 +112,6 @@ struct PinnedUnits {
         inflight = true;
         return MIC_OK;
     }
-    MicUnit *data() { return p; }
-    MicUnit &operator[](size_t i) { return p[i]; }
-    const MicUnit &operator[](size_t i) const { return p[i]; }
-    size_t size() const { return n; }
-    void release() { if (inflight) (void)hipEventSynchronize(ev); inflight = false; if (p) (void)hipHostFree(p); p = nullptr; cap = n = 0; if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
 };
 
 // a small pinned array the device writes results into (offsets of the packed streams)
@@ -161,8 +179,6 @@ struct mic_hip_session {
     size_t pack_cap = 0, pack_hint = 0;           // pack_hint: bytes the session's last batch packed to
     PinnedU64 pin_off;
     int n_last = 0;
-    // a launch chain over n units has been enqueued; nothing is queued behind it yet (the enqueue that queues its read-back says so after this)
-    void begin_chain(int n) { n_last = n; readback_queued = false; pack_queued = false; learn_decode = learn_encode = false; }
     bool learn_decode = false, learn_encode = false;   // the chain in flight was launched under the session's class masks: finish updates them
     int variant = 0;                        // launch flags (MIC_VARIANT_GRAD is OR-ed in per call)
     // Kernel classes this session's last batches used (mic_launch.h: launch masks): age[c] = batches since class c was last seen;
@@ -179,15 +195,6 @@ struct mic_hip_session {
     // reallocation, after a failed launch).  The invariant is tied to the ALLOCATION (DevBuf::gen),
     // not to the address: hipFree + a larger hipMalloc may hand the same address back with undefined contents.
     uint64_t hist_zero_gen = ~0ull; size_t hist_zero_units = 0;
-    int prepare_hist(int n) {
-        if (hist.gen != hist_zero_gen) { hist_zero_gen = hist.gen; hist_zero_units = 0; }
-        if ((size_t)n > hist_zero_units) {
-            HIP_TRY(hipMemsetAsync((char *)hist.p + tab_syms * 4 * hist_zero_units, 0, tab_syms * 4 * ((size_t)n - hist_zero_units), stream));
-            hist_zero_units = (size_t)n;
-        }
-        return MIC_OK;
-    }
-    void hist_unknown() { hist_zero_units = 0; }
     MicTimer timer;
     std::vector<std::string> t_names; std::vector<float> t_ms;
     size_t tok_stride = 0, blob_stride = 0, seg_stride = 0, sym_stride = 0, flag_stride = 0;
@@ -243,6 +250,58 @@ struct mic_hip_session {
         max_units = nn; max_px = pp; tier = want_tier; tab_syms = ts;
         return MIC_OK;
     }
+    // ---- the launch-chain protocol: every kernel chain over unit descriptors goes through these three ----------------------------
+    // lay_out(): the workspace takes the shape of n units of up to px pixels and the host descriptors 0 .. n-1 are reset and pointed
+    // at their slabs, capacities set to the slabs' sizes.  The caller then fills in its own fields of h_units[i] -- a capacity
+    // override (a frame's own tok_cap, a stream's sym_cap) included, which therefore always comes after the slab's -- and runs the chain.
+    // want_tier: the frame-unit codec starts in tier 1 and runs again in tier 2 (session_*_finish).  The paths that lay out symbol
+    // units themselves (bare FSE, MIC2 temporal residuals, WaveletV2) have no second run and take tier 2, the worst case; tier_review
+    // (mic_api.hip) leaves their batches (mode != 0) out of its count for that reason.
+    int lay_out(int n, size_t px, int want_tier = 2) {
+        int rc = ensure(n, px, want_tier);                              // (before anything points into a slab)
+        if (rc || (rc = h_units.assign((size_t)n, MicUnit{}))) return rc;   // (waits for the previous chain's upload)
+        for (int i = 0; i < n; i++) fill_workspace(h_units[(size_t)i], i);
+        return MIC_OK;
+    }
+    // run_encode / run_decode(launch): the laid-out descriptors go up, the slabs are put in the state the chain assumes, `launch()`
+    // enqueues the kernels on `stream` -- mic_launch_encode / mic_launch_decode with the path's own kernels in front of or behind it, in
+    // the caller's order; every launch that `timer` is to see belongs in there -- and the chain is the session's current one:
+    // session_*_finish reads it back.  Anything the caller queues behind the chain (pack, read-back) and the flags that say so
+    // (readback_queued, pack_queued, learn_*) come AFTER the call returns: the call clears them.
+    template <class F> int run_encode(F &&launch) {
+        return run_chain(true, false, launch);
+    }
+    // The escape-flag slab (a bit per pixel "stored raw behind an escape", mic_decode_px.hip) is OR-ed into by the pixel kernels, so
+    // units that reach them -- frames, mode 0 -- need it zero: Clear.  Symbol units (mode 1 / 3: bare FSE, temporal residuals,
+    // WaveletV2) stop at tokens or symbols and never read it, and k_rle_walk_compact uses it as scratch: Idle, no memset.  A batch that
+    // may hold a frame among its symbol units (MIC2 temporal: unit 0 of the first sub-batch) is Clear.
+    enum class FlagSlab { Clear, Idle };
+    template <class F> int run_decode(FlagSlab flag_slab, F &&launch) {
+        return run_chain(false, flag_slab == FlagSlab::Clear, launch);
+    }
+
+private:
+    template <class F> int run_chain(bool encode, bool clear_flags, F &&launch) {
+        const int n = (int)h_units.size();
+        int rc = h_units.upload(units.p, (size_t)n, stream);
+        if (rc || (encode && (rc = prepare_hist(n)))) return rc;
+        if (clear_flags) HIP_TRY(hipMemsetAsync(flags.p, 0, flag_stride * (size_t)n, stream));
+        timer.reset(stream);                                            // (in front of the first timed kernel)
+        launch();
+        if (hipGetLastError() != hipSuccess) { if (encode) hist_unknown(); return MIC_ERR_DEVICE; }   // (whatever a chain that failed left in its histograms)
+        // the chain over n units is enqueued; nothing is queued behind it yet
+        n_last = n; readback_queued = false; pack_queued = false; learn_decode = learn_encode = false;
+        return MIC_OK;
+    }
+    int prepare_hist(int n) {
+        if (hist.gen != hist_zero_gen) { hist_zero_gen = hist.gen; hist_zero_units = 0; }
+        if ((size_t)n > hist_zero_units) {
+            HIP_TRY(hipMemsetAsync((char *)hist.p + tab_syms * 4 * hist_zero_units, 0, tab_syms * 4 * ((size_t)n - hist_zero_units), stream));
+            hist_zero_units = (size_t)n;
+        }
+        return MIC_OK;
+    }
+    void hist_unknown() { hist_zero_units = 0; }
     void fill_workspace(MicUnit &u, int i) {
         const size_t ts = tab_syms;
         u.tier = (uint32_t)tier; u.tab_cap = (uint32_t)ts;
@@ -263,6 +322,7 @@ struct mic_hip_session {
         u.sym_cap = (uint32_t)std::min<size_t>(tok_cap_tier(max_px, tier) + 64, 0xFFFFFFF0u);
         u.flags = (uint32_t *)((char *)flags.p + flag_stride * (size_t)i);
     }
+public:
     size_t reserved_bytes() const {
         const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
         size_t t = 0;

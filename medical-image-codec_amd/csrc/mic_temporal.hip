@@ -58,8 +58,8 @@ __global__ void k_tmp_check(MicUnit *units, int n, uint32_t npx, int r0) {
     if (i < n && units[i].status == MICD_OK && units[i].nsym != npx) units[i].status = MICD_ERR_CORRUPT;
 }
 
-inline void put_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-inline uint32_t get_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+// frames per sub-batch: a unit's tier-2 slabs and its frame on the device, under the workspace ceiling (units are a launch's grid y)
+size_t frames_per_batch(size_t npx) { return std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535)); }
 
 }  // namespace
 
@@ -80,7 +80,7 @@ int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nf
     int rc = lease.acquire();
     if (rc) return rc;
     mic_hip_session *s = cur_default();
-    const size_t per = std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535));
+    const size_t per = frames_per_batch(npx);
     std::vector<uint32_t> lens((size_t)nframes);
     uint64_t total = 0;
     memset(out, 0, header);
@@ -88,31 +88,27 @@ int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nf
         const int nb = (int)std::min(per, (size_t)nframes - f0);
         const int lead = f0 ? 1 : 0;                                      // the frame in front of the sub-batch (its residuals' reference)
         if ((rc = s->io_px.reserve(npx * 2 * (size_t)(nb + lead)))) return rc;
-        if ((rc = s->ensure(nb, npx))) return rc;
+        if ((rc = s->lay_out(nb, npx))) return rc;
         HIP_TRY(hipMemcpyAsync(s->io_px.p, frames + (f0 - (size_t)lead) * npx, npx * 2 * (size_t)(nb + lead), hipMemcpyHostToDevice, s->stream));
         const uint16_t *d_first = (const uint16_t *)s->io_px.p + (size_t)lead * npx;   // frame f0 on the device
-        { const int arc = s->h_units.assign((size_t)nb, MicUnit{}); if (arc) return arc; }
         for (int i = 0; i < nb; i++) {
             MicUnit &u = s->h_units[(size_t)i];
             u.w = width; u.h = height; u.nstates = 2;
-            s->fill_workspace(u, i);
             u.tok_cap = (uint32_t)tok_cap_for(npx);
             if (f0 == 0 && i == 0) { u.mode = 0; u.px_in = d_first; u.max_value = max_value; }
             else { u.mode = 2; u.nsym = (uint32_t)npx; u.max_value = 0; }
         }
-        { const int urc = s->h_units.upload(s->units.p, (size_t)nb, s->stream); if (urc) return urc; }
-        if ((rc = s->prepare_hist(nb))) return rc;
         const int r0 = f0 ? 0 : 1;                                        // first residual unit of the sub-batch
-        if (nb > r0) {
-            const unsigned bx = (unsigned)std::min<size_t>((npx + 255) / 256, 1024);
-            hipLaunchKernelGGL(k_tmp_residual, dim3(bx, (unsigned)(nb - r0)), dim3(256), 0, s->stream,
-                               (MicUnit *)s->units.p, d_first, (uint32_t)npx, r0);
-            hipLaunchKernelGGL(k_tmp_set_max, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb, r0);
-        }
-        s->timer.reset(s->stream);
-        mic_launch_encode((MicUnit *)s->units.p, nb, s->stream, s->variant, nullptr);
-        if (hipGetLastError() != hipSuccess) { s->hist_unknown(); return MIC_ERR_DEVICE; }
-        s->begin_chain(nb);
+        rc = s->run_encode([&] {
+            if (nb > r0) {
+                const unsigned bx = (unsigned)std::min<size_t>((npx + 255) / 256, 1024);
+                hipLaunchKernelGGL(k_tmp_residual, dim3(bx, (unsigned)(nb - r0)), dim3(256), 0, s->stream,
+                                   (MicUnit *)s->units.p, d_first, (uint32_t)npx, r0);
+                hipLaunchKernelGGL(k_tmp_set_max, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb, r0);
+            }
+            mic_launch_encode((MicUnit *)s->units.p, nb, s->stream, s->variant, nullptr);
+        });
+        if (rc) return rc;
         std::vector<uint64_t> offs((size_t)nb + 1);
         std::vector<int32_t> st((size_t)nb), ns((size_t)nb);
         const uint8_t *d_blobs = nullptr;
@@ -143,14 +139,13 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
     int rc = lease.acquire();
     if (rc) return rc;
     mic_hip_session *s = cur_default();
-    const size_t per = std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535));
+    const size_t per = frames_per_batch(npx);
     for (size_t f0 = 0; f0 < (size_t)n; f0 += per) {
         const int nb = (int)std::min(per, (size_t)n - f0);
         const int lead = f0 ? 1 : 0;                                      // slot 0 holds the frame in front of the sub-batch
         if ((rc = s->io_px.reserve(npx * 2 * (size_t)(nb + 1)))) return rc;   // (grown before the carry below could be lost: sized for the first pass too)
-        if ((rc = s->ensure(nb, npx))) return rc;
+        if ((rc = s->lay_out(nb, npx))) return rc;
         size_t c0 = (size_t)-1, c1 = 0;                                   // byte range of the sub-batch's streams
-        { const int arc = s->h_units.assign((size_t)nb, MicUnit{}); if (arc) return arc; }
         for (int i = 0; i < nb; i++) {
             const size_t fi = f0 + (size_t)i;
             const size_t start = data_off + get_u32(c + 20 + fi * 8), bl = get_u32(c + 24 + fi * 8);
@@ -165,23 +160,20 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
             MicUnit &u = s->h_units[(size_t)i];
             u.comp_in = (const uint8_t *)s->io_comp.p + (start - c0); u.comp_len = (uint32_t)bl;
             u.w = w; u.h = h;
-            s->fill_workspace(u, i);
             u.tok_cap = (uint32_t)tok_cap_for(npx);
             if (fi == 0) { u.mode = 0; u.px_out = (uint16_t *)s->io_px.p; }
             else u.mode = 3;                                             // FSE + RLE-of-symbols into u.sym
         }
         HIP_TRY(hipMemcpyAsync(s->io_comp.p, c + c0, c1 - c0, hipMemcpyHostToDevice, s->stream));
-        { const int urc = s->h_units.upload(s->units.p, (size_t)nb, s->stream); if (urc) return urc; }
-        HIP_TRY(hipMemsetAsync(s->flags.p, 0, s->flag_stride * (size_t)nb, s->stream));
-        s->timer.reset(s->stream);
-        mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, nullptr, (int *)s->cls.p);
         const int r0 = f0 ? 0 : 1;                                        // first residual unit
-        if (nb > r0) {
-            mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
-            hipLaunchKernelGGL(k_tmp_check, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb, (uint32_t)npx, r0);
-        }
-        HIP_TRY(hipGetLastError());
-        s->begin_chain(nb);
+        rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {        // (unit 0 of the first sub-batch is the spatial frame)
+            mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, nullptr, (int *)s->cls.p);
+            if (nb > r0) {
+                mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
+                hipLaunchKernelGGL(k_tmp_check, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb, (uint32_t)npx, r0);
+            }
+        });
+        if (rc) return rc;
         std::vector<int32_t> st((size_t)nb);
         if ((rc = session_decode_finish(s, st.data()))) return rc;
         for (int i = 0; i < nb; i++) if (st[(size_t)i] != MIC_OK) return st[(size_t)i];

@@ -813,59 +813,54 @@ int wv_compress_frames(mic_hip_session *s, const uint16_t *d_src, int nf, int ro
                        const uint8_t **d_blobs_out = nullptr, uint64_t *offs_out = nullptr) {
     const size_t n = (size_t)rows * (size_t)cols;
     int rc;
-    if ((rc = s->ensure(nf, 2 * n + 16))) return rc;                     // room for 3-word escapes
+    if ((rc = s->lay_out(nf, 2 * n + 16))) return rc;                    // room for 3-word escapes
     DevBuf &a = s->wv_a, &b = s->wv_b;                                   // coefficient planes: kept by the session (no hipMalloc per call)
     // b: the smooth planes between levels, two per frame (levels alternate), each (rows + 1) / 2 x (cols + 1) / 2 at most
     const size_t ll_half = (size_t)((rows + 1) / 2) * (size_t)((cols + 1) / 2), ll_fs = 2 * ll_half;
     if ((rc = a.reserve(n * 4 * (size_t)nf + 64)) || (rc = b.reserve(ll_fs * 4 * (size_t)nf + 64))) return rc;
-    auto done = [&](int code) { return code; };
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;
-    s->timer.reset(s->stream);
-    s->timer.mark("k_wv_fwd2d");
-    if (applied == 0) hipLaunchKernelGGL(k_wv_load, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, d_src, A, n * (size_t)nf);
-    { int r = rows, c = cols;
-      for (int l = 0; l < applied; l++) {                                  // a level per launch: level l's smooth plane in B, parity l
-          const int rn = (r + 1) / 2, cn = (c + 1) / 2;
-          const dim3 g((unsigned)((cn + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)((rn + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
-          const bool last = l == applied - 1;
-          int32_t *lld = last ? A : B + ((l & 1) ? ll_half : 0);
-          const int lls = last ? cols : cn; const size_t llf = last ? n : ll_fs;
-          if (l == 0) hipLaunchKernelGGL(k_wv_fwd2d<true>, g, dim3(256), 0, s->stream, (const void *)d_src, cols, n, A, cols, n, lld, lls, llf, r, c, nf);
-          else hipLaunchKernelGGL(k_wv_fwd2d<false>, g, dim3(256), 0, s->stream, (const void *)(B + (((l - 1) & 1) ? ll_half : 0)), c, ll_fs, A, cols, n, lld, lls, llf, r, c, nf);
-          r = rn; c = cn;
-      } }
-    { const int arc = s->h_units.assign((size_t)nf, MicUnit{}); if (arc) return arc; }
     for (int i = 0; i < nf; i++) {
         MicUnit &u = s->h_units[(size_t)i];
         u.w = 1; u.h = 1; u.nstates = 4; u.mode = 2; u.no_fallback = 1; // FSECompressU16FourState, no fallback (:344)
-        s->fill_workspace(u, i);
     }
-    if (s->h_units.upload(s->units.p, (size_t)nf, s->stream) != MIC_OK) return done(MIC_ERR_DEVICE);
-    if ((rc = s->prepare_hist(nf))) return done(rc);
-    s->timer.mark("k_wv_symbols");
-    {
-        const WvDims d = wv_dims(rows, cols, applied);
-        hipLaunchKernelGGL(k_wv_symbols_par, dim3((unsigned)((n + WS_T - 1) / WS_T), (unsigned)std::min(nf, 65535)), dim3(1024), 0, s->stream,
-                           (MicUnit *)s->units.p, (const int32_t *)A, d, nf);
-        hipLaunchKernelGGL(k_wv_symbols_fin, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, d, nf);
-        hipLaunchKernelGGL(k_wv_symbols, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, (const int32_t *)A, d);   // frames with wide coefficients
-    }
-    mic_launch_encode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer);
-    if (hipGetLastError() != hipSuccess) { s->hist_unknown(); return done(MIC_ERR_DEVICE); }
-    s->begin_chain(nf);
+    rc = s->run_encode([&] {
+        s->timer.mark("k_wv_fwd2d");
+        if (applied == 0) hipLaunchKernelGGL(k_wv_load, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, d_src, A, n * (size_t)nf);
+        { int r = rows, c = cols;
+          for (int l = 0; l < applied; l++) {                                  // a level per launch: level l's smooth plane in B, parity l
+              const int rn = (r + 1) / 2, cn = (c + 1) / 2;
+              const dim3 g((unsigned)((cn + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)((rn + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
+              const bool last = l == applied - 1;
+              int32_t *lld = last ? A : B + ((l & 1) ? ll_half : 0);
+              const int lls = last ? cols : cn; const size_t llf = last ? n : ll_fs;
+              if (l == 0) hipLaunchKernelGGL(k_wv_fwd2d<true>, g, dim3(256), 0, s->stream, (const void *)d_src, cols, n, A, cols, n, lld, lls, llf, r, c, nf);
+              else hipLaunchKernelGGL(k_wv_fwd2d<false>, g, dim3(256), 0, s->stream, (const void *)(B + (((l - 1) & 1) ? ll_half : 0)), c, ll_fs, A, cols, n, lld, lls, llf, r, c, nf);
+              r = rn; c = cn;
+          } }
+        s->timer.mark("k_wv_symbols");
+        {
+            const WvDims d = wv_dims(rows, cols, applied);
+            hipLaunchKernelGGL(k_wv_symbols_par, dim3((unsigned)((n + WS_T - 1) / WS_T), (unsigned)std::min(nf, 65535)), dim3(1024), 0, s->stream,
+                               (MicUnit *)s->units.p, (const int32_t *)A, d, nf);
+            hipLaunchKernelGGL(k_wv_symbols_fin, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, d, nf);
+            hipLaunchKernelGGL(k_wv_symbols, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, (const int32_t *)A, d);   // frames with wide coefficients
+        }
+        mic_launch_encode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer);
+    });
+    if (rc) return rc;
     std::vector<uint64_t> offs((size_t)nf + 1); std::vector<int32_t> ns((size_t)nf); const uint8_t *d_blobs = nullptr;
     st.assign((size_t)nf, 0);
-    if ((rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data()))) return done(rc);
+    if ((rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data()))) return rc;
     if (!blobs) {
         if (d_blobs_out) *d_blobs_out = d_blobs;
         if (offs_out) memcpy(offs_out, offs.data(), sizeof(uint64_t) * ((size_t)nf + 1));
-        return done(MIC_OK);
+        return MIC_OK;
     }
     std::vector<uint8_t> host((size_t)offs[(size_t)nf] + 16);
-    if (offs[(size_t)nf] && hipMemcpy(host.data(), d_blobs, (size_t)offs[(size_t)nf], hipMemcpyDeviceToHost) != hipSuccess) return done(MIC_ERR_DEVICE);
+    if (offs[(size_t)nf] && hipMemcpy(host.data(), d_blobs, (size_t)offs[(size_t)nf], hipMemcpyDeviceToHost) != hipSuccess) return MIC_ERR_DEVICE;
     blobs->assign((size_t)nf, std::vector<uint8_t>());
     for (int i = 0; i < nf; i++) if (st[(size_t)i] == MIC_OK) (*blobs)[(size_t)i].assign(host.begin() + (long)offs[(size_t)i], host.begin() + (long)offs[(size_t)i + 1]);
-    return done(MIC_OK);
+    return MIC_OK;
 }
 
 // nf FSE streams (already in s->io_comp at offs[i] .. offs[i + 1]) of frames of one shape -> pixels in s->io_px
@@ -882,56 +877,51 @@ int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_
     auto end_of = [&](int i) { return ends ? ends[(size_t)i] : offs[(size_t)i + 1]; };
     for (int i = 0; i < nf; i++)
         if (end_of(i) < offs[(size_t)i] || end_of(i) - offs[(size_t)i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
-    if ((rc = s->ensure(nf, 2 * n + 16))) return rc;
+    if ((rc = s->lay_out(nf, 2 * n + 16))) return rc;
     DevBuf &a = s->wv_a, &b = s->wv_b;
     const size_t ll_half = (size_t)((rows + 1) / 2) * (size_t)((cols + 1) / 2), ll_fs = 2 * ll_half;   // (the smooth planes between levels, as in wv_compress_frames)
     if ((rc = a.reserve(n * 4 * (size_t)nf + 64)) || (rc = b.reserve(ll_fs * 4 * (size_t)nf + 64))) return rc;
-    auto done = [&](int code) { return code; };
-    { const int arc = s->h_units.assign((size_t)nf, MicUnit{}); if (arc) return arc; }
     for (int i = 0; i < nf; i++) {
         MicUnit &u = s->h_units[(size_t)i];
         u.comp_in = d_comp + offs[(size_t)i]; u.comp_len = (uint32_t)(end_of(i) - offs[(size_t)i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
-        s->fill_workspace(u, i);
         u.sym_cap = (uint32_t)std::min<size_t>(u.sym_cap, wv_sym_ceiling(n));   // the oracle's ceiling: DESIGN.md section 4, WaveletV2
         u.sym_limit = sym_limit;
     }
-    if (s->h_units.upload(s->units.p, (size_t)nf, s->stream) != MIC_OK) return done(MIC_ERR_DEVICE);
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;
-    s->timer.reset(s->stream);
-    mic_launch_decode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer, (int *)s->cls.p);
-    const WvDims d = wv_dims(rows, cols, levels);
-    const uint32_t P = (uint32_t)d.nr[level] * (uint32_t)d.nc[level];   // the coefficients the output needs (n at level 0)
-    if (s->timer.used) { s->timer.used--; s->timer.names.pop_back(); }   // (drop the chain's "end" mark: the wavelet kernels follow)
-    s->timer.mark("k_rle_walk_parts+fix+compact");
-    hipLaunchKernelGGL(k_rle_walk_parts, dim3(WP_PARTS, (unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
-    hipLaunchKernelGGL(k_rle_walk_fix, dim3((unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
-    hipLaunchKernelGGL(k_rle_walk_compact, dim3(WP_PARTS, (unsigned)nf), dim3(256), 0, s->stream, (MicUnit *)s->units.p);
-    s->timer.mark("k_wv_scatter");
-    hipLaunchKernelGGL(k_wv_scatter, dim3((unsigned)((P + WS_T - 1) / WS_T), (unsigned)nf), dim3(1024), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
-    s->timer.mark("k_wv_expand+coeffs (escape frames)");
-    hipLaunchKernelGGL(k_wv_expand, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, -1, 1);
-    hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
-    s->timer.mark("k_wv_inv2d");
-    if (levels == 0) hipLaunchKernelGGL(k_wv_store, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, d_dst, n * (size_t)nf);
-    else if (level == levels)                                                               // the coarsest LL band itself: no inverse level
-        hipLaunchKernelGGL(k_wv_band, dim3(grid_for((size_t)P * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, cols, n, d_dst, d.nr[level], d.nc[level], nf);
-    for (int l = levels - 1; l >= level; l--) {                                             // coarse -> fine, :519-527
-        const int r = d.nr[l], cc = d.nc[l];
-        const dim3 g((unsigned)(((cc + 1) / 2 + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)(((r + 1) / 2 + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
-        const bool coarsest = l == levels - 1;
-        const int32_t *lls = coarsest ? A : B + (((l + 1) & 1) ? ll_half : 0);
-        const int llst = coarsest ? cols : d.nc[l + 1]; const size_t llf = coarsest ? n : ll_fs;
-        if (l == 0) hipLaunchKernelGGL(k_wv_inv2d<true>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cols, n, r, cc, nf);
-        else if (l == level)                                                                // reduced resolution: the band, saturated, stride nc[level]
-            hipLaunchKernelGGL((k_wv_inv2d<true, true>), g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cc, (size_t)P, r, cc, nf);
-        else hipLaunchKernelGGL(k_wv_inv2d<false>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)(B + ((l & 1) ? ll_half : 0)), cc, ll_fs, r, cc, nf);
-    }
-    s->timer.mark("end");
-    if (hipGetLastError() != hipSuccess) return done(MIC_ERR_DEVICE);
-    s->begin_chain(nf);
+    rc = s->run_decode(mic_hip_session::FlagSlab::Idle, [&] {            // (k_rle_walk_compact's scratch)
+        mic_launch_decode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer, (int *)s->cls.p);
+        const WvDims d = wv_dims(rows, cols, levels);
+        const uint32_t P = (uint32_t)d.nr[level] * (uint32_t)d.nc[level];   // the coefficients the output needs (n at level 0)
+        if (s->timer.used) { s->timer.used--; s->timer.names.pop_back(); }   // (drop the chain's "end" mark: the wavelet kernels follow)
+        s->timer.mark("k_rle_walk_parts+fix+compact");
+        hipLaunchKernelGGL(k_rle_walk_parts, dim3(WP_PARTS, (unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
+        hipLaunchKernelGGL(k_rle_walk_fix, dim3((unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
+        hipLaunchKernelGGL(k_rle_walk_compact, dim3(WP_PARTS, (unsigned)nf), dim3(256), 0, s->stream, (MicUnit *)s->units.p);
+        s->timer.mark("k_wv_scatter");
+        hipLaunchKernelGGL(k_wv_scatter, dim3((unsigned)((P + WS_T - 1) / WS_T), (unsigned)nf), dim3(1024), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
+        s->timer.mark("k_wv_expand+coeffs (escape frames)");
+        hipLaunchKernelGGL(k_wv_expand, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, -1, 1);
+        hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
+        s->timer.mark("k_wv_inv2d");
+        if (levels == 0) hipLaunchKernelGGL(k_wv_store, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, d_dst, n * (size_t)nf);
+        else if (level == levels)                                                               // the coarsest LL band itself: no inverse level
+            hipLaunchKernelGGL(k_wv_band, dim3(grid_for((size_t)P * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, cols, n, d_dst, d.nr[level], d.nc[level], nf);
+        for (int l = levels - 1; l >= level; l--) {                                             // coarse -> fine, :519-527
+            const int r = d.nr[l], cc = d.nc[l];
+            const dim3 g((unsigned)(((cc + 1) / 2 + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)(((r + 1) / 2 + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
+            const bool coarsest = l == levels - 1;
+            const int32_t *lls = coarsest ? A : B + (((l + 1) & 1) ? ll_half : 0);
+            const int llst = coarsest ? cols : d.nc[l + 1]; const size_t llf = coarsest ? n : ll_fs;
+            if (l == 0) hipLaunchKernelGGL(k_wv_inv2d<true>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cols, n, r, cc, nf);
+            else if (l == level)                                                                // reduced resolution: the band, saturated, stride nc[level]
+                hipLaunchKernelGGL((k_wv_inv2d<true, true>), g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cc, (size_t)P, r, cc, nf);
+            else hipLaunchKernelGGL(k_wv_inv2d<false>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)(B + ((l & 1) ? ll_half : 0)), cc, ll_fs, r, cc, nf);
+        }
+        s->timer.mark("end");
+    });
+    if (rc) return rc;
     st.assign((size_t)nf, 0);
-    if ((rc = session_decode_finish(s, st.data()))) return done(rc);
-    return done(MIC_OK);
+    return session_decode_finish(s, st.data());
 }
 
 // The tANS ceiling of pass 1 of a decode at reduced resolution ("WaveletV2 at reduced resolution"): the image at
@@ -991,6 +981,19 @@ void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int app
     out[10] = (uint8_t)applied;
 }
 
+// the argument gate of every entry point: MIC_OK, or why rows x cols (a decode: at `level` of a header's `levels`) is not coded here
+int wv_check_shape(int rows, int cols, int levels = 0, int level = 0) {
+    if (rows <= 0 || cols <= 0 || levels < 0 || levels > 8 || level < 0 || level > levels) return MIC_ERR_ARGS;
+    return (size_t)rows * (size_t)cols > ((size_t)1 << 27) ? MIC_ERR_UNSUPPORTED : MIC_OK;
+}
+// the level count the header carries: `levels` clamped to 1 .. 8, stopped where a side falls below 2 (waveletfsecompressu16.go:321-330)
+int wv_levels_applied(int rows, int cols, int levels) {
+    levels = std::min(std::max(levels, 1), 8);
+    int applied = 0;
+    for (int r = rows, c = cols; applied < levels && r >= 2 && c >= 2; applied++) { r = (r + 1) / 2; c = (c + 1) / 2; }
+    return applied;
+}
+
 size_t wv_frames_per_batch(size_t n) { return std::max<size_t>(1, kWorkspaceBudget / (unit_ws_bytes(2 * n + 16) + 8 * n)); }
 
 // range(f0, f1, device) over frames [0, nframes) of rows x cols pixels: one call on the default device, or -- several devices listed,
@@ -1017,14 +1020,11 @@ extern "C" {
 // status to status[i] (a frame that fails does not stop the others).
 int mic_hip_wavelet_v2_compress_batch(const uint16_t *frames, int nframes, int rows, int cols, uint16_t max_value, int levels,
                                       uint8_t *out, size_t out_stride, size_t *out_lens, int32_t *status) try {
-    if (!frames || !out || !out_lens || !status || nframes <= 0 || rows <= 0 || cols <= 0) return MIC_ERR_ARGS;
+    if (!frames || !out || !out_lens || !status || nframes <= 0) return MIC_ERR_ARGS;
+    if (const int gate = wv_check_shape(rows, cols)) return gate;
     const size_t n = (size_t)rows * (size_t)cols;
-    if (n > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
     if (out_stride < 11) return MIC_ERR_CAPACITY;
-    if (levels < 1) levels = 1;
-    if (levels > 8) levels = 8;
-    int applied = 0;
-    { int r = rows, c = cols; for (; applied < levels; applied++) { if (r < 2 || c < 2) break; r = (r + 1) / 2; c = (c + 1) / 2; } }   // :321-330
+    const int applied = wv_levels_applied(rows, cols, levels);
     return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session
         DefaultLease lease;
         int rc = lease.acquire(device);
@@ -1050,7 +1050,7 @@ int mic_hip_wavelet_v2_compress_batch(const uint16_t *frames, int nframes, int r
         }
         return MIC_OK;
     });
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // WaveletV2RLEFSECompressU16 / WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303, :374)
 int mic_hip_wavelet_v2_compress(const uint16_t *pixels, int rows, int cols, uint16_t max_value, int levels,
@@ -1063,7 +1063,7 @@ int mic_hip_wavelet_v2_compress(const uint16_t *pixels, int rows, int cols, uint
     if (st != MIC_OK) return st;
     *out_len = len;
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wavelet_v2_info(const uint8_t *c, size_t len, int *rows, int *cols, int *max_value, int *levels) try {
     if (!c) return MIC_ERR_ARGS;
@@ -1073,7 +1073,7 @@ int mic_hip_wavelet_v2_info(const uint8_t *c, size_t len, int *rows, int *cols, 
     if (max_value) *max_value = c[8] | (c[9] << 8);
     if (levels) *levels = c[10];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"
 
@@ -1088,8 +1088,8 @@ int wv_decompress_files(const uint8_t *const *files, const size_t *lens, int nfr
     if (rc) return rc;
     if (rows <= 0 || cols <= 0 || levels > 8) return MIC_ERR_CORRUPT;
     if (level < 0 || level > levels) return MIC_ERR_ARGS;
+    if ((rc = wv_check_shape(rows, cols))) return rc;
     const size_t n = (size_t)rows * (size_t)cols;
-    if (n > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
     const WvDims dm = wv_dims(rows, cols, levels);
     const size_t P = (size_t)dm.nr[level] * (size_t)dm.nc[level];          // pixels of a frame's output (n at level 0)
     if (P * (size_t)nframes > out_cap_px) return MIC_ERR_CAPACITY;
@@ -1142,7 +1142,7 @@ extern "C" {
 int mic_hip_wavelet_v2_decompress_batch(const uint8_t *const *files, const size_t *lens, int nframes, uint16_t *pixels_out, size_t out_cap_px,
                                         int32_t *status) try {
     return wv_decompress_files(files, lens, nframes, 0, pixels_out, out_cap_px, status, nullptr);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- the image at reduced resolution ("WaveletV2 at reduced resolution") --------------------------------------
 // Level r of a file whose header carries `levels`: the nr[r] x nc[r] LL band the forward transform holds after r levels (nr[0] = rows,
@@ -1159,21 +1159,21 @@ int mic_hip_wavelet_v2_level_info(const uint8_t *c, size_t len, int level, int *
     if (out_rows) *out_rows = d.nr[level];
     if (out_cols) *out_cols = d.nc[level];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // mic_hip_wavelet_v2_decompress_batch at `level`: frame i's band goes to pixels_out + i * nr[level] * nc[level]; symbols_decoded
 // (nullable): the tANS symbols the chain decoded per frame, both passes summed
 int mic_hip_wavelet_v2_decompress_level_batch(const uint8_t *const *files, const size_t *lens, int nframes, int level, uint16_t *pixels_out,
                                               size_t out_cap_px, int32_t *status, uint64_t *symbols_decoded) try {
     return wv_decompress_files(files, lens, nframes, level, pixels_out, out_cap_px, status, symbols_decoded);
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 int mic_hip_wavelet_v2_decompress_level(const uint8_t *c, size_t len, int level, uint16_t *pixels_out, size_t out_cap_px) try {
     if (!c || !pixels_out) return MIC_ERR_ARGS;
     int32_t st = 0;
     const int rc = mic_hip_wavelet_v2_decompress_level_batch(&c, &len, 1, level, pixels_out, out_cap_px, &st, nullptr);
     return rc ? rc : st;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // WaveletV2RLEFSEDecompressU16 / WaveletV2SIMDRLEFSEDecompressU16 (:380-425, :493-534)
 int mic_hip_wavelet_v2_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, size_t out_cap_px) try {
@@ -1181,7 +1181,7 @@ int mic_hip_wavelet_v2_decompress(const uint8_t *c, size_t len, uint16_t *pixels
     int32_t st = 0;
     const int rc = mic_hip_wavelet_v2_decompress_batch(&c, &len, 1, pixels_out, out_cap_px, &st);
     return rc ? rc : st;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 // ---- device-resident forms (what bench.py times for BASELINE config 3): frames, streams and pixels stay in HBM ----------------
 // nframes frames of rows x cols u16, contiguous at d_frames -> their WaveletV2 streams WITHOUT the 11-byte file header (rows, cols,
@@ -1189,47 +1189,39 @@ int mic_hip_wavelet_v2_decompress(const uint8_t *c, size_t len, uint16_t *pixels
 // *levels_applied = the level count the header would carry (waveletfsecompressu16.go:321-330).
 int mic_hip_session_wavelet_v2_encode(mic_hip_session *s, const uint16_t *d_frames, int nframes, int rows, int cols, int levels,
                                       const uint8_t **d_streams, uint64_t *h_offsets, int32_t *h_status, int *levels_applied) try {
-    if (!s || !d_frames || !d_streams || !h_offsets || !h_status || nframes <= 0 || rows <= 0 || cols <= 0) return MIC_ERR_ARGS;
-    const size_t n = (size_t)rows * (size_t)cols;
-    if (n > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
-    if (levels < 1) levels = 1;
-    if (levels > 8) levels = 8;
-    int applied = 0;
-    { int r = rows, c = cols; for (; applied < levels; applied++) { if (r < 2 || c < 2) break; r = (r + 1) / 2; c = (c + 1) / 2; } }
+    if (!s || !d_frames || !d_streams || !h_offsets || !h_status || nframes <= 0) return MIC_ERR_ARGS;
+    int rc = wv_check_shape(rows, cols);
+    if (rc || (rc = s->activate())) return rc;
+    const int applied = wv_levels_applied(rows, cols, levels);
     if (levels_applied) *levels_applied = applied;
-    int rc = s->activate();
-    if (rc) return rc;
     std::vector<int32_t> st;
     if ((rc = wv_compress_frames(s, d_frames, nframes, rows, cols, applied, nullptr, st, d_streams, h_offsets))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 // The inverse: nframes header-less streams at d_streams + h_offsets[i] (all of one shape / level count) -> pixels at d_pixels_out.
 int mic_hip_session_wavelet_v2_decode(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
                                       int rows, int cols, int levels, uint16_t *d_pixels_out, int32_t *h_status) try {
-    if (!s || !d_streams || !h_offsets || !d_pixels_out || !h_status || nframes <= 0 || rows <= 0 || cols <= 0 || levels < 0 || levels > 8) return MIC_ERR_ARGS;
-    if ((size_t)rows * (size_t)cols > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
-    int rc = s->activate();
-    if (rc) return rc;
+    if (!s || !d_streams || !h_offsets || !d_pixels_out || !h_status || nframes <= 0) return MIC_ERR_ARGS;
+    int rc = wv_check_shape(rows, cols, levels);
+    if (rc || (rc = s->activate())) return rc;
     std::vector<int32_t> st;
     if ((rc = wv_decompress_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, st))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 // The same at `level` (mic_hip_wavelet_v2_level_info): frame i's nr[level] x nc[level] band to d_pixels_out + i * nr[level] * nc[level];
 // h_symbols_decoded (nullable): the tANS symbols the chain decoded per frame, both passes summed.
 int mic_hip_session_wavelet_v2_decode_level(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
                                             int rows, int cols, int levels, int level, uint16_t *d_pixels_out,
                                             int32_t *h_status, uint64_t *h_symbols_decoded) try {
-    if (!s || !d_streams || !h_offsets || !d_pixels_out || !h_status || nframes <= 0 || rows <= 0 || cols <= 0 || levels < 0 || levels > 8) return MIC_ERR_ARGS;
-    if (level < 0 || level > levels) return MIC_ERR_ARGS;
-    if ((size_t)rows * (size_t)cols > ((size_t)1 << 27)) return MIC_ERR_UNSUPPORTED;
-    int rc = s->activate();
-    if (rc) return rc;
+    if (!s || !d_streams || !h_offsets || !d_pixels_out || !h_status || nframes <= 0) return MIC_ERR_ARGS;
+    int rc = wv_check_shape(rows, cols, levels, level);
+    if (rc || (rc = s->activate())) return rc;
     std::vector<int32_t> st;
     if ((rc = wv_decode_level_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, level, st, h_symbols_decoded))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
     return MIC_OK;
-} catch (const std::bad_alloc &) { return MIC_ERR_NOMEM; } catch (...) { return MIC_ERR_INTERNAL; }   // (no C++ exception crosses the C ABI)
+} MIC_ABI_CATCH
 
 }  // extern "C"
