@@ -245,15 +245,59 @@ int mic_hip_compress_batch_gap(mic_hip_enc_job *jobs, int njobs);
 int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs);
 
 /* ---- PICA container: content-adaptive strips, per-strip predictor choice ------------------------ */
+/* out_cap >= MIC_HIP_PICA_BOUND(width, height, num_strips) is always sufficient: 16 header bytes, 16 per entry, and the kept
+ * candidate of every strip within its MIC_HIP_FRAME_BOUND (the strips' pixels add up to the image's). */
+#define MIC_HIP_PICA_BOUND(width, height, num_strips) \
+    (16 + 16 * (size_t)(num_strips) + 4 * (size_t)(width) * (size_t)(height) + 135168 * (size_t)(num_strips))
 /* Replaces CompressParallelStripsAdaptive (parallelstripsadaptive.go:54): strip boundaries by equal-cost partition of the rows'
  * summed |vertical delta| (adaptiveStripBoundaries, :222-289, float64 like the reference), every strip coded with both the avg
  * and the gradient-adaptive predictor (CompressSingleFrame / CompressSingleFrameGrad, two-state FSE) and the smaller kept, ties to
  * the gradient one (:97-105).  num_strips must be given (the reference's default is GOMAXPROCS). */
 int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
                           uint8_t *out, size_t out_cap, size_t *out_len);
+/* The same with the index of the strip the error belongs to (the reference wraps it: "pica: strip %d: %w",
+ * parallelstripsadaptive.go:110): the first strip, in strip order, whose kept candidate failed (:95-114) -- a strip fails only when
+ * both encodes did, and its error is then the avg one's -- or that has no rows (the partition clamps late boundaries, :282-284:
+ * MIC_ERR_ARGS); -1 when the call succeeded or the error is not a strip's. */
+int mic_hip_pica_compress_ex(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
+                             uint8_t *out, size_t out_cap, size_t *out_len, int *failed_strip);
 int mic_hip_pica_info(const uint8_t *compressed, size_t compressed_len, int *width, int *height, int *num_strips);
-/* Replaces DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141). */
+/* Replaces DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141).  Rows no strip covers come back zero (:175). */
 int mic_hip_pica_decompress(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height);
+/* ... and with the index of the strip that failed to decode ("pica: strip %d: %w", :207; -1: none). */
+int mic_hip_pica_decompress_ex(const uint8_t *compressed, size_t compressed_len, uint16_t *pixels_out, int width, int height,
+                               int *failed_strip);
+/* Many images, one call, through the pipeline of mic_hip_pics_compress_batch (sub-batches, pinned staging, mic_hip_set_devices
+ * shards by pixels): the reference reaches this by calling CompressParallelStripsAdaptive from many goroutines, each fanning out
+ * two encodes per strip (:86-108).  Row costs and boundaries of all images of a sub-batch are found on the device, both candidates
+ * of every strip run in one unit batch, the winner is picked there and only it is packed and downloaded.  Every job's file equals
+ * mic_hip_pica_compress's, byte for byte; a job with bad arguments or a failing strip fails alone. */
+typedef struct mic_hip_pica_enc_job {
+    const uint16_t *pixels;   /* in : width*height u16 (host memory) */
+    int32_t   width, height;  /* in  */
+    uint16_t  max_value;      /* in  (two-state FSE only: :90-92) */
+    int32_t   num_strips;     /* in : > 0 */
+    uint8_t  *out;            /* in : caller buffer, out_cap >= MIC_HIP_PICA_BOUND(...) is always sufficient */
+    size_t    out_cap;        /* in  */
+    size_t    out_len;        /* out */
+    int32_t   status;         /* out */
+    int32_t   failed_strip;   /* out: as mic_hip_pica_compress_ex */
+} mic_hip_pica_enc_job;
+typedef struct mic_hip_pica_dec_job {
+    const uint8_t *compressed; /* in : a PICA file (host memory) */
+    size_t    compressed_len;  /* in  */
+    uint16_t *pixels_out;      /* in : width*height u16 (host memory) */
+    int32_t   width, height;   /* in : must equal the header's */
+    int32_t   status;          /* out */
+    int32_t   failed_strip;    /* out: the first strip that failed to decode, -1: none */
+} mic_hip_pica_dec_job;
+int mic_hip_pica_compress_batch(mic_hip_pica_enc_job *jobs, int njobs);
+int mic_hip_pica_decompress_batch(mic_hip_pica_dec_job *jobs, int njobs);
+/* adaptiveStripBoundaries alone (:222-289): starts[0 .. *n_out) of one image, n_out = min(num_strips, height) <= cap.
+ * on_host = 0: the device's partition kernel, as the batch uses it; 1: the reference's float64 loop on the host, fed with the
+ * device's row costs -- the two agree for every input (tests/test_gpu_pica_batch.py). */
+int mic_hip_pica_boundaries(const uint16_t *pixels, int width, int height, int num_strips, int on_host,
+                            int32_t *starts, int cap, int *n_out);
 
 /* ---- MIC2 container, independent frames --------------------------------------------------- */
 /* Replaces CompressMultiFrame(..., temporal=false) (multiframecompress.go:179) +

@@ -93,6 +93,19 @@ class PicsDecJob(C.Structure):
                 ("failed_strip", C.c_int32)]
 
 
+class PicaEncJob(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("max_value", C.c_uint16), ("num_strips", C.c_int32),
+                ("out", C.c_void_p), ("out_cap", C.c_size_t), ("out_len", C.c_size_t), ("status", C.c_int32),
+                ("failed_strip", C.c_int32)]
+
+
+class PicaDecJob(C.Structure):
+    _fields_ = [("compressed", C.c_void_p), ("compressed_len", C.c_size_t),
+                ("pixels_out", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("status", C.c_int32),
+                ("failed_strip", C.c_int32)]
+
+
 class Unit(C.Structure):
     _fields_ = [("px_offset", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
@@ -112,6 +125,7 @@ ABI_SYMBOLS = [
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
     "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
     "mic_hip_compress_frame_grad", "mic_hip_decompress_frame_grad", "mic_hip_pica_compress", "mic_hip_pica_info", "mic_hip_pica_decompress",
+    "mic_hip_pica_compress_ex", "mic_hip_pica_decompress_ex", "mic_hip_pica_compress_batch", "mic_hip_pica_decompress_batch", "mic_hip_pica_boundaries",
     "mic_hip_rgb_compress", "mic_hip_rgb_decompress", "mic_hip_micr_compress", "mic_hip_micr_info", "mic_hip_micr_decompress",
     "mic_hip_mic1_compress", "mic_hip_mic1_info", "mic_hip_mic1_decompress",
     "mic_hip_wsi_compress", "mic_hip_wsi_compress_ex", "mic_hip_wsi_format", "mic_hip_wsi_info", "mic_hip_wsi_level_info",
@@ -278,6 +292,11 @@ def lib() -> C.CDLL:
     L.mic_hip_decompress_frame_grad.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     L.mic_hip_pica_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_pica_info.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 3
+    L.mic_hip_pica_compress_ex.argtypes = L.mic_hip_pica_compress.argtypes + [C.POINTER(C.c_int)]
+    L.mic_hip_pica_decompress_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.mic_hip_pica_compress_batch.argtypes = [C.POINTER(PicaEncJob), C.c_int]
+    L.mic_hip_pica_decompress_batch.argtypes = [C.POINTER(PicaDecJob), C.c_int]
+    L.mic_hip_pica_boundaries.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.mic_hip_pica_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     L.mic_hip_rgb_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_rgb_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
@@ -1051,17 +1070,32 @@ def decompress_single_frame_grad(compressed, width: int, height: int) -> np.ndar
     return out.reshape(height, width)
 
 
+def _raise_strip(rc: int, where: str, strip: int):
+    """a strip's error carries its index, as the reference's "pica: strip %d: %w" does: MicError.strip"""
+    try:
+        _raise(rc, where + (f": strip {strip}" if strip >= 0 else ""))
+    except MicError as e:
+        e.strip = strip
+        raise
+
+
+def pica_bound(width: int, height: int, num_strips: int) -> int:
+    """MIC_HIP_PICA_BOUND"""
+    ns = max(num_strips, 1)
+    return 16 + 16 * ns + 4 * width * height + 135168 * ns
+
+
 def compress_parallel_strips_adaptive(pixels, width: int, height: int, max_value: int, num_strips: int) -> bytes:
-    """CompressParallelStripsAdaptive (parallelstripsadaptive.go:54)."""
+    """CompressParallelStripsAdaptive (parallelstripsadaptive.go:54); a strip's error carries its index (:110): MicError.strip."""
     px = np.ascontiguousarray(pixels, dtype=np.uint16).reshape(-1)
     if px.size != width * height:
         raise MicError(MIC_ERR_ARGS, "compress_parallel_strips_adaptive")
-    cap = px.size * 4 + 135168 * max(1, num_strips) + 16 * max(1, num_strips) + 16
+    cap = pica_bound(width, height, num_strips)
     out = np.empty(cap, dtype=np.uint8)
-    n = C.c_size_t(0)
-    rc = lib().mic_hip_pica_compress(px.ctypes.data, width, height, max_value, num_strips, out.ctypes.data, cap, C.byref(n))
+    n = C.c_size_t(0); bad = C.c_int(-1)
+    rc = lib().mic_hip_pica_compress_ex(px.ctypes.data, width, height, max_value, num_strips, out.ctypes.data, cap, C.byref(n), C.byref(bad))
     if rc:
-        _raise(rc, "compress_parallel_strips_adaptive")
+        _raise_strip(rc, "compress_parallel_strips_adaptive", bad.value)
     return out[: n.value].tobytes()
 
 
@@ -1073,10 +1107,65 @@ def decompress_parallel_strips_adaptive(compressed) -> np.ndarray:
     if rc:
         _raise(rc, "decompress_parallel_strips_adaptive")
     out = np.empty(w.value * h.value, dtype=np.uint16)
-    rc = lib().mic_hip_pica_decompress(c.ctypes.data, c.size, out.ctypes.data, w.value, h.value)
+    bad = C.c_int(-1)
+    rc = lib().mic_hip_pica_decompress_ex(c.ctypes.data, c.size, out.ctypes.data, w.value, h.value, C.byref(bad))
     if rc:
-        _raise(rc, "decompress_parallel_strips_adaptive")
+        _raise_strip(rc, "decompress_parallel_strips_adaptive", bad.value)
     return out.reshape(h.value, w.value)
+
+
+def compress_parallel_strips_adaptive_batch(images: Sequence[np.ndarray], max_value, num_strips,
+                                            outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
+    """Many images, one call (mic_hip_pica_compress_batch): [(status, file bytes as a uint8 view of its out buffer)].
+    images: (height, width) uint16 arrays (ordinary or pinned memory); max_value, num_strips: one value, or one per image;
+    outs: caller buffers of >= pica_bound bytes, or None."""
+    n = len(images)
+    arrs = [_u16(a) for a in images]
+    mxs = list(max_value) if np.ndim(max_value) else [max_value] * n
+    nss = list(num_strips) if np.ndim(num_strips) else [num_strips] * n
+    if outs is None:
+        outs = [np.empty(pica_bound(a.shape[1], a.shape[0], nss[i]), dtype=np.uint8) for i, a in enumerate(arrs)]
+    jobs = (PicaEncJob * n)()
+    for i, a in enumerate(arrs):
+        jobs[i].pixels = a.ctypes.data; jobs[i].width = a.shape[1]; jobs[i].height = a.shape[0]
+        jobs[i].max_value = int(mxs[i]); jobs[i].num_strips = int(nss[i])
+        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
+    rc = lib().mic_hip_pica_compress_batch(jobs, n)
+    if rc:
+        _raise(rc, "compress_parallel_strips_adaptive_batch")
+    compress_parallel_strips_adaptive_batch.failed_strips = [jobs[i].failed_strip for i in range(n)]   # (of the last call: index of each job's failing strip, -1)
+    return [(jobs[i].status, outs[i][: jobs[i].out_len]) for i in range(n)]
+
+
+def decompress_parallel_strips_adaptive_batch(files: Sequence, dims: Sequence[Tuple[int, int]],
+                                              outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
+    """Many PICA files, one call (mic_hip_pica_decompress_batch): [(status, (height, width) uint16 pixels)]; dims: (width, height)."""
+    n = len(files)
+    cs = [_bytes_arr(f) for f in files]
+    if outs is None:
+        outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
+    jobs = (PicaDecJob * n)()
+    for i in range(n):
+        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
+        jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
+    rc = lib().mic_hip_pica_decompress_batch(jobs, n)
+    if rc:
+        _raise(rc, "decompress_parallel_strips_adaptive_batch")
+    decompress_parallel_strips_adaptive_batch.failed_strips = [jobs[i].failed_strip for i in range(n)]
+    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0])) for i in range(n)]
+
+
+def pica_boundaries(pixels, num_strips: int, on_host: bool = False) -> List[int]:
+    """adaptiveStripBoundaries (parallelstripsadaptive.go:222) of a (height, width) image: the device's partition kernel, or
+    (on_host) the reference's float64 loop fed with the device's row costs."""
+    px = _u16(pixels)
+    h, w = px.shape
+    starts = np.zeros(max(min(num_strips, h), 1), dtype=np.int32)
+    n = C.c_int(0)
+    rc = lib().mic_hip_pica_boundaries(px.ctypes.data, w, h, num_strips, 1 if on_host else 0, starts.ctypes.data, starts.size, C.byref(n))
+    if rc:
+        _raise(rc, "pica_boundaries")
+    return [int(v) for v in starts[: n.value]]
 
 
 # ------------------------------------------------------------------ single-frame RGB, MIC1 / MICR files

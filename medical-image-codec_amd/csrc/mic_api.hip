@@ -123,7 +123,7 @@ size_t workspace_budget() {
 // A launch chain in the given tier.  Tier 1 (the small slabs) is where a batch starts unless the session has needed tier 2 before or
 // a unit's depth says so (14 bits and more: an alphabet past the 8192-bin tables); session_*_finish runs the batch again in tier 2
 // when a unit reports MICD_INT_GROW.
-static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, int tier) {
+static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, int tier, bool pairs) {
     size_t max_px = 0;
     for (int i = 0; i < n; i++) max_px = std::max(max_px, (size_t)units[i].width * (size_t)units[i].height);
     int rc = s->lay_out(n, max_px, tier);
@@ -160,7 +160,12 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
         if (units[i].max_value >= 2048u) enc_hint |= MIC_ENC_CLS_TL14 | MIC_ENC_CLS_TL15 | MIC_ENC_CLS_TL16;
     }
     const int variant = s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0) | (any_gap ? MIC_VARIANT_GAP : 0);
-    if ((rc = s->run_encode([&] { mic_launch_encode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, s->enc_classes.mask() | enc_hint); }))) return rc;
+    if ((rc = s->run_encode([&] {
+            mic_launch_encode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, s->enc_classes.mask() | enc_hint);
+#ifndef MIC_PICA_NO_PICK   // (A / B builds, tools/bench_pica_batch.py: both candidates are packed and the host picks)
+            if (pairs) mic_launch_pica_pick((MicUnit *)s->units.p, n / 2, s->stream, &s->timer);   // (the sizes are final: pick before the scan and the pack)
+#endif
+        }))) return rc;
     s->learn_encode = true;
     // Compaction and the read-back of the results ride behind the chain, so that session_encode_finish is ONE synchronisation (round 3:
     // descriptors down, a synchronisation, sizes summed on the host, scan + pack launched, a second synchronisation -- 86 us of idle
@@ -176,8 +181,8 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
     return MIC_OK;
 }
 
-int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n) {
-    if (n <= 0) return MIC_ERR_ARGS;
+int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, bool pica_pairs) {
+    if (n <= 0 || (pica_pairs && (n & 1))) return MIC_ERR_ARGS;
     if (n > 65535) return MIC_ERR_UNSUPPORTED;                           // units are a launch's grid y in several kernels: callers sub-batch
     size_t max_px = 0;
     bool deep = false;
@@ -192,8 +197,8 @@ int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const m
     if (max_px > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
     const int tier = (s->force_big || deep) ? 2 : 1;
     s->retry.kind = 0;
-    if (tier == 1) { s->retry.kind = 1; s->retry.d_in = d_pixels; s->retry.units.assign(units, units + n); }
-    return encode_enqueue_tier(s, d_pixels, units, n, tier);
+    if (tier == 1) { s->retry.kind = 1; s->retry.pairs = pica_pairs; s->retry.d_in = d_pixels; s->retry.units.assign(units, units + n); }
+    return encode_enqueue_tier(s, d_pixels, units, n, tier, pica_pairs);
 }
 
 // reads the units back; a tier-1 chain that reported MICD_INT_GROW somewhere is run again in tier 2 first
@@ -209,7 +214,7 @@ static int finish_units(mic_hip_session *s, int n) {
         s->force_big = true;
         const mic_hip_session::Retry r = s->retry;                       // (the enqueue below rewrites it)
         int rc;
-        if (r.kind == 1) rc = encode_enqueue_tier(s, (const uint16_t *)r.d_in, r.units.data(), n, 2);
+        if (r.kind == 1) rc = encode_enqueue_tier(s, (const uint16_t *)r.d_in, r.units.data(), n, 2, r.pairs);
         else rc = session_decode_enqueue_spans(s, (const uint8_t *)r.d_in, r.begins.data(), r.ends.data(), r.units.data(), n, (uint16_t *)r.d_out);
         if (rc) return rc;
     }
@@ -275,7 +280,7 @@ int session_encode_finish(mic_hip_session *s, const uint8_t **d_blobs, uint64_t 
     for (int i = 0; i < n; i++) {
         const MicUnit &u = s->h_units[(size_t)i];
         h_offsets[i] = total;
-        if (u.status == MICD_OK) total += u.blob_len;
+        if (u.status == MICD_OK && !u.skip_pack) total += u.blob_len;        // (as k_scan_lens counts: a PICA strip's loser takes no room)
         h_status[i] = u.status;
         if (h_nstates) h_nstates[i] = u.nstates_used;
     }

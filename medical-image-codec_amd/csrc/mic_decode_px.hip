@@ -876,8 +876,15 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
 // four-pixel group: at step t it rebuilds columns 4 (t - r) .. + 3 from W = its own previous pixel, N / NW = the group lane r - 1
 // produced one step earlier (DPP wave_shr), and NE of the group's last pixel = the first pixel lane r - 1 produces in THIS step,
 // handed over in the middle of the step.  Lane 0 takes the row above from an LDS row buffer that lane 63 of the previous band
-// filled (wave-private, no barriers).  Symbols are fetched one step ahead as 8-byte vectors.
+// filled (wave-private, no barriers).  Symbols are fetched PG_AHEAD steps ahead as 8-byte vectors.  Deeper prefetch does not pay: for
+// 768 XR strips of 2577 x 256 the kernel takes 4.27 / 4.28 / 4.42 / 4.77 ms at 1 / 2 / 4 / 8 steps (profiles/pica_batch.json) -- a unit is
+// one wave of nq + 63 dependent steps per band, bound by that wave's own instruction issue, not by its loads (DESIGN.md "PICA").
+// The row buffer is sized by the launch's width class (8 KiB, 16 KiB, PR_MAX_W columns), and only the classes the batch's widths
+// call for are launched.
 #define PG_Q 4
+#ifndef PG_AHEAD
+#define PG_AHEAD 1
+#endif
 __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_lo, int w_hi) {
     MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK || u.mode != 0 || !u.pred) return;
@@ -917,12 +924,16 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
         uint32_t left = 0;                                       // W of the next pixel
         uint32_t nw = 0;                                         // ... and at the column before them
         uint32_t mine[PG_Q] = { 0u, 0u, 0u, 0u };                // this lane's previous result
-        Grp nx = fetch(-(int)lane);
+        Grp nx[PG_AHEAD];                                        // groups q .. q + PG_AHEAD - 1 of this lane, on their way
+#pragma unroll
+        for (int a = 0; a < PG_AHEAD; a++) nx[a] = fetch(a - (int)lane);
         const int steps = nq + 63;
         for (int t = 0; t < steps; t++) {
             const int q = t - (int)lane;
-            const Grp g = nx;
-            nx = fetch(q + 1);
+            const Grp g = nx[0];
+#pragma unroll
+            for (int a = 0; a + 1 < PG_AHEAD; a++) nx[a] = nx[a + 1];
+            nx[PG_AHEAD - 1] = fetch(q + PG_AHEAD);
             const bool act = row_ok && q >= 0 && q < nq;
             // N of the four columns: what lane r - 1 produced in the previous step; lane 0: the row buffer
             uint32_t up[PG_Q];
@@ -1011,7 +1022,13 @@ void mic_launch_decode_pixels(MicUnit *d_units, int n, hipStream_t stream, MicTi
         if (t) t->mark("k_dec_predict_grad");
         static MicPerDeviceOnce once;
         once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_predict_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (PR_MAX_W + 2 * PG_Q) * 2); });
-        hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), 8192 * 2, stream, d_units, 0, 8192 - 2 * PG_Q);
-        hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), (PR_MAX_W + 2 * PG_Q) * 2, stream, d_units, 8192 - 2 * PG_Q, PR_MAX_W);
+        // row-buffer classes by width, as above: 8 KiB up to 4088 columns, 16 KiB up to 8184, then the wide one -- launched when the
+        // batch has a width of the class (pred_mask speaks for all units, gradient or not: a class without gradient units exits at once)
+        if (pred_mask & (0x7Fu | MIC_PRED_NARROW | MIC_PRED_WAVE2))
+            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), 4096 * 2, stream, d_units, 0, 4096 - 2 * PG_Q);
+        if (pred_mask & (MIC_PRED_WAVE2 | MIC_PRED_WIDE))
+            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), 8192 * 2, stream, d_units, 4096 - 2 * PG_Q, 8192 - 2 * PG_Q);
+        if (pred_mask & MIC_PRED_WIDE)
+            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), (PR_MAX_W + 2 * PG_Q) * 2, stream, d_units, 8192 - 2 * PG_Q, PR_MAX_W);
     }
 }

@@ -91,6 +91,7 @@ struct MicUnit {
     uint32_t count;           // decode: symbol count from the 6-byte prefix
     uint32_t flavour;         // decode: 1/2/4/8, 108 = rANS-8
     uint32_t packed_direct;   // encode: 1 = the bitstream goes straight to the packed buffer (k_enc_tans_pack); the blob holds only the framing
+    uint32_t skip_pack;       // encode: 1 = the losing candidate of a PICA strip (k_pica_pick): k_scan_lens does not count it, the pack kernels leave it alone
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
     // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------
     uint32_t sym_limit;       // 0: the whole stream.  Else the chain kernels that honour it decode only the first
@@ -105,6 +106,16 @@ __host__ __device__ inline uint32_t mic_sym_ceiling(const MicUnit &u, uint32_t c
     const uint32_t c = (u.sym_limit + 127u) & ~127u;
     return c < count ? c : count;
 }
+
+// One image of a PICA sub-batch (mic_pica.hip): where its pixels, its row costs and its strip boundaries lie.
+struct MicPicaImage {
+    uint64_t px_off;          // first pixel, in u16 from the sub-batch's pixel buffer
+    int32_t  w, h;
+    int32_t  nstrips;         // 1 .. h (the host has clamped it, parallelstripsadaptive.go:61-66)
+    uint32_t rows;            // h when the partition needs the row costs (1 < nstrips < h), else 0
+    uint32_t row0;            // the image's first entry of the cost array (running sum of rows)
+    uint32_t start0;          // the image's first entry of the boundary array (running sum of nstrips)
+};
 
 // A pointer read out of a MicUnit is "generic" to the compiler, and generic accesses are flat_load / flat_store: those count on
 // lgkmcnt as well as on vmcnt, so every s_waitcnt lgkmcnt(0) -- there is one in front of every work-group barrier -- waits for the

@@ -1376,6 +1376,7 @@ __global__ void __launch_bounds__(T, TE_NARROW_WPS) k_enc_tans_pack(const MicUni
     __shared__ unsigned long long s_edge[2];                           // the unit's two words shared with its neighbours (te_pack)
     const MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK || !u.packed_direct) return;
+    if (u.skip_pack) return;                                             // (a PICA strip's losing candidate: k_pica_pick)
     if (dst_off[nu] + 16 > cap) return;                                  // (the batch does not fit: the host packs it again into a larger buffer)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n = u.ntok, tl = u.table_log, size = 1u << tl;
@@ -1443,6 +1444,7 @@ __global__ void __launch_bounds__(T, TE_NARROW_WPS) k_enc_tans_pack(const MicUni
 __global__ void __launch_bounds__(256) k_enc_pack(const MicUnit *units, const uint64_t *dst_off, uint8_t *dst, uint64_t cap, int n) {
     const MicUnit &u = units[blockIdx.y];
     if (u.status != MICD_OK || u.packed_direct) return;                 // (k_enc_tans_pack has written that one)
+    if (u.skip_pack) return;                                             // (a PICA strip's losing candidate: k_pica_pick)
     if (dst_off[n] + 16 > cap) return;                                   // (the batch does not fit: the host packs it again into a larger buffer)
     const mic_gp<const uint8_t> src = mic_g((const uint8_t *)u.blob) + (u.nstates_used == 1 ? 6 : 0);
     mic_gp<uint8_t> d = mic_g(dst) + dst_off[blockIdx.y];
@@ -1462,14 +1464,14 @@ __global__ void __launch_bounds__(256) k_enc_pack(const MicUnit *units, const ui
     if (blockIdx.x == 0 && threadIdx.x < (len & 15u)) d[nvec * 16 + threadIdx.x] = src[nvec * 16 + threadIdx.x];
 }
 
-// exclusive scan of blob lengths (single block; n units <= a few 100k)
+// exclusive scan of blob lengths (single block; n units <= a few 100k); a unit k_pica_pick marked skip_pack takes no room
 __global__ void __launch_bounds__(1024) k_scan_lens(const MicUnit *units, int n, uint64_t *dst_off) {
     __shared__ uint64_t s_part[1024];
     const int t = threadIdx.x;
     const int per = (n + 1023) / 1024;
     const int lo = t * per, hi = min(n, lo + per);
     uint64_t sum = 0;
-    for (int i = lo; i < hi; i++) sum += (units[i].status == MICD_OK) ? units[i].blob_len : 0;
+    for (int i = lo; i < hi; i++) sum += (units[i].status == MICD_OK && !units[i].skip_pack) ? units[i].blob_len : 0;
     s_part[t] = sum;
     __syncthreads();
     if (t == 0) {
@@ -1481,7 +1483,7 @@ __global__ void __launch_bounds__(1024) k_scan_lens(const MicUnit *units, int n,
     uint64_t run = s_part[t];
     for (int i = lo; i < hi; i++) {
         dst_off[i] = run;
-        run += (units[i].status == MICD_OK) ? units[i].blob_len : 0;
+        run += (units[i].status == MICD_OK && !units[i].skip_pack) ? units[i].blob_len : 0;
     }
 }
 

@@ -473,6 +473,234 @@ inline void pics_geometry(int height, int num_strips, int &strip_h, int &actual)
     actual = (height + strip_h - 1) / strip_h;                       // :72
 }
 
+
+// ============================================================================ PICA: many images, boundaries and pick on the device
+// A PICA image's units are not known before its pixels are on the device: the strip boundaries follow the content.  So the call is
+// cut into PARTS of whole images (about as many units as a PICS sub-batch holds, pixels inside a staging half); a part's pixels
+// come up once, k_pica_rowcost / k_pica_partition find the boundaries of all its images, one small read-back brings them to the
+// host, and the strips -- two units each over the same pixels, avg and gradient -- run as launch chains under the workspace
+// ceiling.  The boundary stage of part k + 1 is queued BEHIND the last chain of part k, before the host waits for that chain: its
+// read-back is complete at the chain's one synchronisation, and part k + 1 starts without a round trip of its own.
+struct PicaRun {                                       // one job the call runs
+    mic_hip_pica_enc_job *j; int n;                    // n: strips (num_strips clamped to the height, parallelstripsadaptive.go:61-66)
+    std::vector<int32_t> y0, err; std::vector<uint32_t> len, flag;   // per strip; err: the strip's error (both candidates failed, no rows)
+    size_t written = 0; bool cap_fail = false;
+    size_t hdr() const { return 16 + 16 * (size_t)n; }
+    bool failed() const { if (cap_fail) return true; for (int32_t e : err) if (e != MIC_OK) return true; return false; }
+};
+static_assert(sizeof(MicPicaImage) == 32, "the table travels as four u64 per image");
+
+// -DMIC_PICA_TIMING (A / B builds only, tools/bench_pica_batch.py): per-kernel device times of every PICA batch call on stderr.
+// The product library has none of it.
+#ifdef MIC_PICA_TIMING
+struct PicaTimingScope {
+    mic_hip_session *s; const char *what;
+    PicaTimingScope(mic_hip_session *s_, const char *w) : s(s_), what(w) { (void)mic_hip_session_set_timing(s, 2); }
+    ~PicaTimingScope() {
+        const char *names[96]; float ms[96];
+        const int n = mic_hip_session_last_timings(s, names, ms, 96);
+        for (int i = 0; i < n; i++) fprintf(stderr, "[mic_hip pica %s] %9.4f ms  %s\n", what, ms[i], names[i]);
+        (void)mic_hip_session_set_timing(s, 0);
+    }
+};
+#endif
+
+struct PicaPart {
+    int g0 = 0, g1 = 0; IoReq up;
+    std::vector<MicPicaImage> tab; uint32_t rows = 0, nstarts = 0; size_t px = 0;
+};
+
+// table up, costs, boundaries, boundaries down: all on the session's stream, nothing waited for
+int pica_bounds_enqueue(mic_hip_session *s, PicaPart &p, const uint16_t *d_px, int half) {
+    const size_t nimg = p.tab.size();
+    int rc;
+    if ((rc = s->pica_pin[half].reserve(4 * nimg + ((size_t)p.nstarts + 1) / 2))) return rc;
+    if ((rc = s->pica_tab.reserve(sizeof(MicPicaImage) * nimg))) return rc;
+    if ((rc = s->pica_cost.reserve(8 * std::max<size_t>(p.rows, 1)))) return rc;
+    if ((rc = s->pica_starts.reserve(4 * (size_t)p.nstarts))) return rc;
+    memcpy(s->pica_pin[half].p, p.tab.data(), sizeof(MicPicaImage) * nimg);
+    HIP_TRY(hipMemcpyAsync(s->pica_tab.p, s->pica_pin[half].p, sizeof(MicPicaImage) * nimg, hipMemcpyHostToDevice, s->stream));
+    s->timer.stream = s->stream;
+    mic_launch_pica_bounds(d_px, (const MicPicaImage *)s->pica_tab.p, (int)nimg, p.rows, (unsigned long long *)s->pica_cost.p,
+                           (int32_t *)s->pica_starts.p, s->stream, &s->timer);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->pica_pin[half].p + 4 * nimg, s->pica_starts.p, 4 * (size_t)p.nstarts, hipMemcpyDeviceToHost, s->stream));
+    return MIC_OK;
+}
+inline const int32_t *pica_starts_of(const mic_hip_session *s, const PicaPart &p, int half) { return (const int32_t *)(s->pica_pin[half].p + 4 * p.tab.size()); }
+
+int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J) {
+    const int nj = (int)J.size();
+    if (nj == 0) return MIC_OK;
+    int rc = s->ensure(1, 1);                                             // (the stream)
+    if (rc) return rc;
+#ifdef MIC_PICA_TIMING
+    PicaTimingScope timing(s, "encode");
+#endif
+    size_t all_units = 0;
+    for (const PicaRun &r : J) all_units += 2 * (size_t)r.n;
+    const size_t target = pipeline_target(all_units, true);
+    const size_t px_cap = workspace_budget() / 16;                        // u16 per staging half: the two halves take an eighth of the ceiling each
+    std::vector<std::unique_ptr<PicaPart>> parts;
+    for (int g = 0; g < nj;) {
+        auto p = std::make_unique<PicaPart>();
+        p->g0 = g;
+        size_t units = 0;
+        for (; g < nj; g++) {
+            const mic_hip_pica_enc_job &j = *J[(size_t)g].j;
+            const int n = J[(size_t)g].n;
+            const size_t ipx = (size_t)j.width * (size_t)j.height;
+            const uint32_t irows = (n > 1 && n < j.height) ? (uint32_t)j.height : 0u;
+            if (g > p->g0 && (units >= target || p->px + ipx > px_cap || (uint64_t)p->rows + irows > 0x7FFFFFFFull || (uint64_t)p->nstarts + (uint64_t)n > 0x7FFFFFFFull)) break;
+            p->tab.push_back(MicPicaImage{ (uint64_t)p->px, j.width, j.height, n, irows, p->rows, p->nstarts });
+            p->px += ipx; p->rows += irows; p->nstarts += (uint32_t)n; units += 2 * (size_t)n;
+        }
+        p->g1 = g;
+        parts.push_back(std::move(p));
+    }
+    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: the pipeline's stages on stderr)
+    if (trace) for (size_t k = 0; k < parts.size(); k++) fprintf(stderr, "[mic_hip pica encode] part %zu of %zu: images %d .. %d, %zu pixels\n", k + 1, parts.size(), parts[k]->g0, parts[k]->g1 - 1, parts[k]->px);
+    DevBuf *in[2] = { &s->io_px, &s->io_px2 };
+    auto upload = [&](PicaPart &p, int half) -> int {
+        int r = in[half]->reserve(p.px * 2 + 64);
+        for (int g = p.g0; g < p.g1 && r == MIC_OK; g++) {
+            const mic_hip_pica_enc_job &j = *J[(size_t)g].j;
+            r = io_submit(p.up, s->device, (uint16_t *)in[half]->p + p.tab[(size_t)(g - p.g0)].px_off, j.pixels, (size_t)j.width * (size_t)j.height * 2, true);
+        }
+        return r;
+    };
+    struct Strip { int job, idx; uint64_t px_off; int32_t w, rows; uint16_t maxv; };
+    std::vector<std::unique_ptr<IoReq>> downs;
+    bool chain_queued = false;                                           // an enqueued chain nobody has finished: an error return waits for it
+    auto drain = [&](int r) { if (chain_queued) { (void)hipStreamSynchronize(s->stream); chain_queued = false; } for (auto &p : parts) { const int r2 = p->up.wait(); if (r == MIC_OK) r = r2; } for (auto &d : downs) { const int r2 = d->wait(); if (r == MIC_OK) r = r2; } return r; };
+    if ((rc = upload(*parts[0], 0))) return drain(rc);
+    if ((rc = parts[0]->up.wait())) return drain(rc);
+    if ((rc = pica_bounds_enqueue(s, *parts[0], (const uint16_t *)in[0]->p, 0))) return drain(rc);
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return drain(MIC_ERR_DEVICE);
+    for (size_t k = 0; k < parts.size(); k++) {
+        PicaPart &p = *parts[k];
+        const int half = (int)(k & 1);
+        // the part's strips, from the boundaries the device found
+        std::vector<Strip> strips;
+        const int32_t *starts = pica_starts_of(s, p, half);
+        for (int g = p.g0; g < p.g1; g++) {
+            PicaRun &r = J[(size_t)g];
+            const MicPicaImage &im = p.tab[(size_t)(g - p.g0)];
+            const int32_t *st = starts + im.start0;
+            for (int i = 0; i < r.n; i++) {
+                const int32_t y0 = st[i], y1 = (i + 1 < r.n) ? st[i + 1] : im.h;
+                if (y0 < 0 || y0 >= im.h || y1 > im.h) return drain(MIC_ERR_INTERNAL);
+                r.y0[(size_t)i] = y0;
+                // a strip of no rows (the partition clamps late boundaries to the last row, :282-284) has nothing to code: the unit
+                // codec rejects it like the reference's does, in strip order with the other strips' errors
+                if (y1 <= y0) { r.err[(size_t)i] = MIC_ERR_ARGS; continue; }
+                if ((size_t)(y1 - y0) * (size_t)im.w > ((size_t)1 << 28)) { r.err[(size_t)i] = MIC_ERR_UNSUPPORTED; continue; }
+                strips.push_back(Strip{ g, i, im.px_off + (uint64_t)y0 * (uint64_t)im.w, im.w, y1 - y0, r.j->max_value });
+            }
+        }
+        if (k + 1 < parts.size() && (rc = upload(*parts[k + 1], half ^ 1))) return drain(rc);   // (that half's chains are finished)
+        bool next_bounds = k + 1 == parts.size();                       // the next part's boundary stage is queued (or there is none)
+        const int nsr = (int)strips.size();
+        for (int s0 = 0; s0 < nsr || !next_bounds;) {
+            // strips [s0, s1) of the next chain: two units each, under the workspace ceiling
+            size_t max_px = 0, cap = 0; int s1 = s0;
+            while (s1 < nsr) {
+                const size_t mp = std::max(max_px, (size_t)strips[(size_t)s1].w * (size_t)strips[(size_t)s1].rows);
+                if (mp != max_px || cap == 0) cap = batch_units_for(mp, 1, 6 * mp);   // (+ the staging: half a strip's pixels and streams per unit, two halves each)
+                if (s1 > s0 && (2 * (size_t)(s1 - s0 + 1) > cap || 2 * (s1 - s0 + 1) > 65534)) break;
+                max_px = mp; s1++;
+            }
+            const int nb = 2 * (s1 - s0);
+            std::vector<mic_hip_unit> units((size_t)nb);
+            for (int q = s0; q < s1; q++) {
+                const Strip &t = strips[(size_t)q];
+                units[(size_t)(2 * (q - s0))] = mic_hip_unit{ t.px_off, t.w, t.rows, t.maxv, 2 };                                         // :92
+                units[(size_t)(2 * (q - s0) + 1)] = mic_hip_unit{ t.px_off, t.w, t.rows, t.maxv, (uint16_t)(2 | MIC_HIP_PRED_GRAD) };     // :94
+            }
+            if (nb && (rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, units.data(), nb, true))) return drain(rc);
+            chain_queued = nb != 0;
+            if (s1 == nsr && !next_bounds) {                              // behind the part's last chain: the next part's boundaries
+                if ((rc = parts[k + 1]->up.wait())) return drain(rc);
+                if ((rc = pica_bounds_enqueue(s, *parts[k + 1], (const uint16_t *)in[half ^ 1]->p, half ^ 1))) return drain(rc);
+                next_bounds = true;
+                if (!nb && hipStreamSynchronize(s->stream) != hipSuccess) return drain(MIC_ERR_DEVICE);
+            }
+            if (!nb) break;
+            std::vector<uint64_t> offs((size_t)nb + 1); std::vector<int32_t> st((size_t)nb), nst((size_t)nb);
+            const uint8_t *d_blobs = nullptr;
+            rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), nst.data());
+            chain_queued = false;
+            if (rc) return drain(rc);
+            if (!downs.empty() && (rc = downs.back()->wait())) return drain(rc);   // (frees the packed buffer the next chain writes)
+            std::swap(s->packed, s->packed2);                             // d_blobs stays where it is while the next chain packs into the other half
+            downs.push_back(std::make_unique<IoReq>());
+            for (int q = s0; q < s1;) {                                   // per image: its winners of this chain lie back to back -- one transfer
+                PicaRun &r = J[(size_t)strips[(size_t)q].job];
+                int e = q;
+                for (; e < s1 && strips[(size_t)e].job == strips[(size_t)q].job; e++) {
+                    const size_t a = (size_t)(2 * (e - s0));
+#ifndef MIC_PICA_NO_PICK
+                    const int pick = s->h_units[a].skip_pack ? 1 : 0;       // k_pica_pick: the avg candidate lost (:95-103)
+#else                   // (A / B builds: both candidates were packed; the rule on the host, the winner fetched by a copy of its own)
+                    const int pick = (st[a + 1] == MIC_OK && (st[a] != MIC_OK || offs[a + 2] - offs[a + 1] <= offs[a + 1] - offs[a])) ? 1 : 0;
+#endif
+                    const int idx = strips[(size_t)e].idx;
+                    r.flag[(size_t)idx] = (uint32_t)pick;                   // picaFlagGradPredictor
+                    r.len[(size_t)idx] = (uint32_t)(offs[a + (size_t)pick + 1] - offs[a + (size_t)pick]);
+                    r.err[(size_t)idx] = pick ? st[a + 1] : st[a];          // both failed: the avg error ("pica: strip %d: ...", :110-114)
+                }
+#ifndef MIC_PICA_NO_PICK
+                const size_t bytes = (size_t)(offs[(size_t)(2 * (e - s0))] - offs[(size_t)(2 * (q - s0))]);
+                if (!r.failed()) {
+                    if (r.hdr() + r.written + bytes > r.j->out_cap) r.cap_fail = true;
+                    else {
+                        if ((rc = io_submit(*downs.back(), s->device, const_cast<uint8_t *>(d_blobs) + offs[(size_t)(2 * (q - s0))], r.j->out + r.hdr() + r.written, bytes, false))) return drain(rc);
+                        r.written += bytes;
+                    }
+                }
+#else
+                for (int z = q; z < e && !r.failed(); z++) {
+                    const size_t a = (size_t)(2 * (z - s0)) + r.flag[(size_t)strips[(size_t)z].idx], bytes = (size_t)(offs[a + 1] - offs[a]);
+                    if (r.hdr() + r.written + bytes > r.j->out_cap) { r.cap_fail = true; break; }
+                    if ((rc = io_submit(*downs.back(), s->device, const_cast<uint8_t *>(d_blobs) + offs[a], r.j->out + r.hdr() + r.written, bytes, false))) return drain(rc);
+                    r.written += bytes;
+                }
+#endif
+                q = e;
+            }
+            s0 = s1;
+        }
+    }
+    return drain(MIC_OK);
+}
+
+// the valid jobs of a call, one contiguous range per device of mic_hip_set_devices, weighted by pixels
+template <class Run, class Weight, class Work>
+int pica_sharded(std::vector<Run> &J, Weight weight, Work work) {
+    const std::vector<int> devs = default_devices();
+    int shards = (int)std::min<size_t>(devs.size(), J.size());
+    if (cur_default()) shards = 1;                    // (a nested call runs on the session its thread already holds)
+    if (shards <= 1) {
+        DefaultLease lease;
+        const int rc = lease.acquire();
+        return rc ? rc : work(lease.s, J);
+    }
+    std::vector<uint64_t> w(J.size());
+    for (size_t i = 0; i < J.size(); i++) w[i] = weight(J[i]);
+    std::vector<int> first((size_t)shards + 1);
+    shard_plan(w.data(), (int)J.size(), shards, first.data());
+    std::vector<std::vector<Run>> S((size_t)shards);
+    for (int k = 0; k < shards; k++) S[(size_t)k].assign(std::make_move_iterator(J.begin() + first[(size_t)k]), std::make_move_iterator(J.begin() + first[(size_t)k + 1]));
+    const int rc = run_parallel(shards, [&](int k) {
+        if (S[(size_t)k].empty()) return (int)MIC_OK;
+        DefaultLease lease;
+        const int r = lease.acquire(devs[(size_t)k]);
+        return r ? r : work(lease.s, S[(size_t)k]);
+    });
+    for (int k = 0; k < shards; k++) std::move(S[(size_t)k].begin(), S[(size_t)k].end(), J.begin() + first[(size_t)k]);
+    return rc;
+}
+
 }  // namespace
 
 namespace micapi {
@@ -698,6 +926,166 @@ int mic_hip_pics_decompress_ex(const uint8_t *c, size_t len, uint16_t *pixels_ou
     mic_hip_pics_dec_job j{};
     j.compressed = c; j.compressed_len = len; j.pixels_out = pixels_out; j.width = width; j.height = height;
     const int rc = mic_hip_pics_decompress_batch(&j, 1);
+    if (rc == MIC_OK && j.status != MIC_OK && failed_strip) *failed_strip = j.failed_strip;
+    return rc ? rc : j.status;
+} MIC_ABI_CATCH
+
+// ---- PICA (parallelstripsadaptive.go) ----------------------------------------------------------
+int mic_hip_pica_compress_batch(mic_hip_pica_enc_job *jobs, int njobs) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::vector<PicaRun> J;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_pica_enc_job &j = jobs[i];
+        j.out_len = 0; j.failed_strip = -1;
+        if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || j.num_strips <= 0) { j.status = MIC_ERR_ARGS; continue; }
+        if ((size_t)j.width * (size_t)j.height > ((size_t)1 << 31)) { j.status = MIC_ERR_UNSUPPORTED; continue; }
+        PicaRun r; r.j = &j; r.n = std::min(j.num_strips, j.height);                             // :61-66
+        if (j.out_cap < r.hdr()) { j.status = MIC_ERR_CAPACITY; continue; }
+        r.y0.assign((size_t)r.n, 0); r.err.assign((size_t)r.n, MIC_OK); r.len.assign((size_t)r.n, 0); r.flag.assign((size_t)r.n, 0);
+        j.status = MIC_ERR_DEVICE;                                                                 // (until the job has run: a call that fails as a whole leaves no stale status)
+        J.push_back(std::move(r));
+    }
+    rc = pica_sharded(J, [](const PicaRun &r) { return (uint64_t)r.j->width * (uint64_t)r.j->height; },
+                      [](mic_hip_session *s, std::vector<PicaRun> &part) { return pica_encode_run(s, part); });
+    if (rc) return rc;
+    for (PicaRun &r : J) {
+        mic_hip_pica_enc_job &j = *r.j;
+        j.status = MIC_OK;
+        for (int k = 0; k < r.n && j.status == MIC_OK; k++)
+            if (r.err[(size_t)k] != MIC_OK) { j.status = r.err[(size_t)k]; j.failed_strip = k; }   // the first strip, in strip order (:110-114)
+        if (j.status == MIC_OK && r.cap_fail) j.status = MIC_ERR_CAPACITY;
+        if (j.status == MIC_OK && r.written > 0xFFFFFFFFull) j.status = MIC_ERR_UNSUPPORTED;    // u32 offsets (:120-128)
+        if (j.status != MIC_OK) continue;
+        uint8_t *out = j.out;
+        memcpy(out, "PICA", 4);
+        put_u32(out + 4, (uint32_t)j.width); put_u32(out + 8, (uint32_t)j.height); put_u32(out + 12, (uint32_t)r.n);
+        size_t off = 0;
+        for (int k = 0; k < r.n; k++) {
+            uint8_t *e = out + 16 + (size_t)k * 16;
+            put_u32(e, (uint32_t)r.y0[(size_t)k]); put_u32(e + 4, (uint32_t)off); put_u32(e + 8, r.len[(size_t)k]); put_u32(e + 12, r.flag[(size_t)k]);
+            off += r.len[(size_t)k];
+        }
+        j.out_len = r.hdr() + r.written;
+    }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// CompressParallelStripsAdaptive (parallelstripsadaptive.go:54-137): a batch of one
+int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
+                          uint8_t *out, size_t out_cap, size_t *out_len) try {
+    return mic_hip_pica_compress_ex(pixels, width, height, max_value, num_strips, out, out_cap, out_len, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_pica_compress_ex(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
+                             uint8_t *out, size_t out_cap, size_t *out_len, int *failed_strip) try {
+    if (failed_strip) *failed_strip = -1;
+    if (!pixels || !out || !out_len || width <= 0 || height <= 0 || num_strips <= 0) return MIC_ERR_ARGS;
+    mic_hip_pica_enc_job j{};
+    j.pixels = pixels; j.width = width; j.height = height; j.max_value = max_value; j.num_strips = num_strips;
+    j.out = out; j.out_cap = out_cap;
+    const int rc = mic_hip_pica_compress_batch(&j, 1);
+    if (rc) return rc;
+    if (j.status == MIC_OK) *out_len = j.out_len;
+    else if (failed_strip) *failed_strip = j.failed_strip;
+    return j.status;
+} MIC_ABI_CATCH
+
+int mic_hip_pica_boundaries(const uint16_t *pixels, int width, int height, int num_strips, int on_host,
+                            int32_t *starts, int cap, int *n_out) try {
+    if (!pixels || !starts || !n_out || width <= 0 || height <= 0 || num_strips <= 0) return MIC_ERR_ARGS;
+    if ((size_t)width * (size_t)height > ((size_t)1 << 31)) return MIC_ERR_UNSUPPORTED;
+    const int n = std::min(num_strips, height);
+    if (cap < n) return MIC_ERR_CAPACITY;
+    DefaultLease lease;
+    int rc = lease.acquire();
+    if (rc) return rc;
+    mic_hip_session *s = lease.s;
+    if ((rc = s->ensure(1, 1))) return rc;
+    const size_t npx = (size_t)width * (size_t)height;
+    if ((rc = s->io_px.reserve(npx * 2 + 64))) return rc;
+    if ((rc = host_copy(s->device, s->io_px.p, const_cast<uint16_t *>(pixels), npx * 2, true))) return rc;
+    PicaPart p;
+    p.rows = (n > 1 && n < height) ? (uint32_t)height : 0u; p.nstarts = (uint32_t)n; p.px = npx;
+    p.tab.push_back(MicPicaImage{ 0, width, height, n, p.rows, 0, 0 });
+    if ((rc = pica_bounds_enqueue(s, p, (const uint16_t *)s->io_px.p, 0))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (!on_host) memcpy(starts, pica_starts_of(s, p, 0), 4 * (size_t)n);
+    else {
+        // the kernel left the inclusive prefix sums of the costs: exact integers, so their differences are the costs again
+        std::vector<unsigned long long> cost((size_t)height, 0ull);
+        if (p.rows) {
+            HIP_TRY(hipMemcpy(cost.data(), s->pica_cost.p, 8 * (size_t)height, hipMemcpyDeviceToHost));
+            for (int y = height - 1; y > 0; y--) cost[(size_t)y] -= cost[(size_t)y - 1];
+        }
+        const std::vector<int> ref = pica_boundaries(cost, height, n);
+        if ((int)ref.size() != n) return MIC_ERR_INTERNAL;
+        for (int i = 0; i < n; i++) starts[i] = ref[(size_t)i];
+    }
+    *n_out = n;
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_pica_decompress_batch(mic_hip_pica_dec_job *jobs, int njobs) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::vector<DecGroup> G; std::vector<DecUnit> U; std::vector<int> job_of;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_pica_dec_job &j = jobs[i];
+        j.failed_strip = -1;
+        if (!j.compressed || !j.pixels_out) { j.status = MIC_ERR_ARGS; continue; }
+        int w, h, n;
+        if ((j.status = mic_hip_pica_info(j.compressed, j.compressed_len, &w, &h, &n))) continue;
+        if (w != j.width || h != j.height) { j.status = MIC_ERR_ARGS; continue; }
+        const uint8_t *c = j.compressed; const size_t len = j.compressed_len;
+        const size_t header = 16 + (size_t)n * 16;
+        const size_t u0 = U.size();
+        int32_t bad = MIC_OK; size_t covered = 0;
+        for (int k = 0; k < n && bad == MIC_OK; k++) {
+            const uint8_t *e = c + 16 + (size_t)k * 16;
+            const long y0 = (long)get_u32(e), y1 = (k + 1 < n) ? (long)get_u32(e + 16) : h;
+            const size_t start = header + get_u32(e + 4), end = start + get_u32(e + 8); const uint32_t flags = get_u32(e + 12);
+            if (end > len || start > end) { bad = MIC_ERR_CORRUPT; break; }                      // :186-190
+            if (y0 < 0 || y1 <= y0 || y1 > h) { bad = MIC_ERR_CORRUPT; break; }                  // Go: make / slice panics
+            if (end == start) { bad = MIC_ERR_CORRUPT; break; }
+            if ((size_t)w * (size_t)(y1 - y0) > ((size_t)1 << 28)) { bad = MIC_ERR_UNSUPPORTED; break; }
+            U.push_back(DecUnit{ start, end - start, (uint64_t)y0 * (uint64_t)w, w, (int32_t)(y1 - y0),
+                                 (uint16_t)(2 | ((flags & 1u) ? MIC_HIP_PRED_GRAD : 0)), (int)G.size() });   // picaFlagGradPredictor, :198-202
+            covered += (size_t)w * (size_t)(y1 - y0);
+        }
+        if (bad != MIC_OK) { U.resize(u0); j.status = bad; continue; }
+        if (covered < (size_t)w * (size_t)h) memset(j.pixels_out, 0, (size_t)w * (size_t)h * 2);   // rows no strip covers stay 0 (make([]uint16), :175)
+        G.push_back(DecGroup{ c, j.pixels_out, (int)u0, n });
+        job_of.push_back(i);
+    }
+#ifdef MIC_PICA_TIMING
+    {                                                   // (on the session the call then runs on: one device)
+        DefaultLease lease;
+        if ((rc = lease.acquire())) return rc;
+        PicaTimingScope timing(lease.s, "decode");
+        rc = decode_sharded(G, U);
+    }
+#else
+    rc = decode_sharded(G, U);
+#endif
+    if (rc) return rc;
+    for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "pica: strip %d: %w", :207
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141-214): a batch of one
+int mic_hip_pica_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
+    return mic_hip_pica_decompress_ex(c, len, pixels_out, width, height, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_pica_decompress_ex(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height, int *failed_strip) try {
+    if (failed_strip) *failed_strip = -1;
+    if (!c || !pixels_out) return MIC_ERR_ARGS;
+    mic_hip_pica_dec_job j{};
+    j.compressed = c; j.compressed_len = len; j.pixels_out = pixels_out; j.width = width; j.height = height;
+    const int rc = mic_hip_pica_decompress_batch(&j, 1);
     if (rc == MIC_OK && j.status != MIC_OK && failed_strip) *failed_strip = j.failed_strip;
     return rc ? rc : j.status;
 } MIC_ABI_CATCH

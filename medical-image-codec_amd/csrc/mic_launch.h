@@ -77,6 +77,12 @@ void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant,
 void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, hipStream_t stream, MicTimer *t, uint32_t cls_mask = ~0u);
 // d_cap: bytes of d_dst -- a batch whose streams do not fit is left alone (dst_off[n], the total, says so)
 void mic_launch_pack(const MicUnit *d_units, int n, uint64_t *d_off, uint8_t *d_dst, uint64_t d_cap, hipStream_t stream, MicTimer *t);
+// PICA (mic_pica.hip).  _bounds: row costs (d_cost: `rows` entries, the sum of d_tab[].rows) and strip boundaries (d_starts: the sum of
+// d_tab[].nstrips entries) of the nimg images of d_tab, whose pixels lie in d_px.  _pick: units 2 p / 2 p + 1 are the avg / gradient
+// candidates of strip p; runs behind mic_launch_encode and in front of mic_launch_pack, which then packs the winners only.
+void mic_launch_pica_bounds(const uint16_t *d_px, const MicPicaImage *d_tab, int nimg, uint32_t rows, unsigned long long *d_cost,
+                            int32_t *d_starts, hipStream_t stream, MicTimer *t);
+void mic_launch_pica_pick(MicUnit *d_units, int npairs, hipStream_t stream, MicTimer *t);
 // pred_mask: the predictor kernels the batch's widths call for (mic_pred_bit) -- bits 0..6 the chunk classes of k_dec_predict_rows
 // (bit (K - 18) / 4), MIC_PRED_* the others; ~0u when the caller does not know its widths
 #define MIC_PRED_NARROW 0x100u          // k_dec_predict<0, 16>: up to MIC_ROWS_LO columns

@@ -3,29 +3,123 @@
 // CompressParallelStripsAdaptive = adaptiveStripBoundaries (equal-cost partition of the rows by summed |vertical delta|) ->
 // every strip coded twice, CompressSingleFrame (avg predictor) and CompressSingleFrameGrad (gradient-adaptive predictor), the
 // smaller blob kept (ties: gradient) -> "PICA" header + 16-byte entries {y0, offset, length, flags} + blobs.
-// On the device: the image is uploaded once; one kernel sums the row costs; the 2 x strips units (two predictors over the same
-// pixels) go through the unit codec in one batch; the host does the float64 partition (it must round exactly as the reference's
-// float64 does) and writes the container.  Decode: one batch over the strips, each with the predictor its flags word names.
+// This file holds the device side: the row costs and the boundaries of every image of a sub-batch (two launches, one small
+// read-back of the boundaries), and the pick of each strip's winner between the tANS walk and the pack.  The host pipeline that
+// drives them -- sub-batches, staging, containers -- is with the other containers' in mic_host_io.hip.
 #include "mic_session.h"
 
 namespace {
 
-// rowCost[y] = sum over x of |p[y][x] - p[y-1][x]|, y >= 1 (parallelstripsadaptive.go:236-247).  One group per row.
-__global__ void __launch_bounds__(256) k_pica_rowcost(const uint16_t *px, int w, int h, unsigned long long *cost) {
-    const int y = (int)blockIdx.x + 1;
-    if (y >= h) return;
-    const uint16_t *a = px + (size_t)y * w, *b = a - w;
+// rowCost[y] = sum over x of |p[y][x] - p[y-1][x]|, y >= 1 (parallelstripsadaptive.go:236-247).  One group per (image, row) of the
+// sub-batch: grid = the table's rows in all, block = 256.  BOUNDS: blockIdx.x < sum of tab[].rows, so the image found has
+// y < rows = h and the loads stay inside rows y - 1 and y of it; cost[] has one entry per grid block.
+typedef uint16_t pica_u16x4 __attribute__((ext_vector_type(4)));
+typedef pica_u16x4 PicaQ __attribute__((aligned(2)));                  // (a row starts at any even address: gfx950 loads it unaligned)
+__global__ void __launch_bounds__(256) k_pica_rowcost(const uint16_t *px, const MicPicaImage *tab, int nimg, unsigned long long *cost) {
+    int lo = 0, hi = nimg - 1;                                          // the last image whose row0 <= this row
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].row0 <= blockIdx.x) lo = mid; else hi = mid - 1; }
+    const MicPicaImage im = tab[lo];
+    const uint32_t y = blockIdx.x - im.row0;
+    if (y >= im.rows) return;
+    if (y == 0) { if (threadIdx.x == 0) cost[blockIdx.x] = 0; return; }
+    const int w = im.w;
+    const mic_gp<const uint16_t> a = mic_g(px) + im.px_off + (size_t)y * (size_t)w, b = a - w;
     unsigned long long sum = 0;
-    for (int x = (int)threadIdx.x; x < w; x += 256) sum += __sad((int)a[x], (int)b[x], 0u);
+    for (int x = (int)threadIdx.x * 4; x + 4 <= w; x += 1024) {
+        const pica_u16x4 va = *(mic_gp<const PicaQ>)(a + x), vb = *(mic_gp<const PicaQ>)(b + x);
+        sum += __sad((unsigned)va.x, (unsigned)vb.x, __sad((unsigned)va.y, (unsigned)vb.y, __sad((unsigned)va.z, (unsigned)vb.z, __sad((unsigned)va.w, (unsigned)vb.w, 0u))));
+    }
+    { const int x = (w & ~3) + (int)threadIdx.x; if (x < w) sum += __sad((unsigned)a[x], (unsigned)b[x], 0u); }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
     __shared__ unsigned long long s_part[4];
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sum;
     __syncthreads();
-    if (threadIdx.x == 0) cost[y] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    if (threadIdx.x == 0) cost[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
-// adaptiveStripBoundaries, parallelstripsadaptive.go:222-289 -- float64 throughout, evaluated in the reference's order
+// adaptiveStripBoundaries (parallelstripsadaptive.go:222-289) for every image of the sub-batch: grid = images, block = 256.
+// The reference works in float64; the boundaries here equal its exactly, without emulating anything:
+//   * every rowCost[y] is an integer, at most 65535 w;
+//   * cum[] is a float64 sum of those.  w h <= 2^31 (the entry points refuse more), so every partial sum is an integer below
+//     2^47 < 2^53: the float64 sums are exact and equal a u64 prefix sum converted once -- a parallel scan is as good as the
+//     reference's serial loop;
+//   * target = total * float64(i) / float64(numStrips) is one IEEE multiply, then one IEEE divide: nothing there can contract into
+//     an FMA, and fp64 multiply and divide are correctly rounded on gfx950 (__dmul_rn / __ddiv_rn say so to the compiler);
+//   * the comparison is cum[mid] < target with cum[mid] converted from the exact integer.
+// cum[] is monotone, so the reference's binary search over [starts[i-1] + 1, height) finds max(starts[i-1] + 1, t_i), t_i the first
+// row of [1, height) whose cum reaches the target (height when none does): the t_i are found side by side, the running maximum and
+// the clamp to height - 1 (:282-284) by one thread.  The two special cases stay: total == 0 gives i * height / numStrips (:262-268),
+// numStrips >= height one row per strip (:223-229).
+// BOUNDS: cost[row0 .. row0 + h) and starts[start0 .. start0 + nstrips) are the image's own; mid - 1 lies in [0, h - 2].
+__global__ void __launch_bounds__(256) k_pica_partition(const MicPicaImage *tab, unsigned long long *cost, int32_t *starts) {
+    const MicPicaImage im = tab[blockIdx.x];
+    const mic_gp<int32_t> st = mic_g(starts) + im.start0;
+    const int n = im.nstrips, h = im.h, tid = (int)threadIdx.x;
+    if (n >= h) { for (int i = tid; i < h; i += 256) st[i] = i; return; }
+    if (n == 1) { if (tid == 0) st[0] = 0; return; }
+    const mic_gp<unsigned long long> c = mic_g(cost) + im.row0;         // becomes the inclusive prefix sum: cum[mid] = c[mid - 1]
+    __shared__ unsigned long long s_part[256];
+    const int per = (int)(((unsigned)h + 255u) / 256u), lo = (int)min((long long)h, (long long)tid * per), hi = (int)min((long long)h, (long long)lo + per);   // (h up to 2^31 - 1: w = 1)
+    unsigned long long run = 0;
+    for (int i = lo; i < hi; i++) run += c[i];
+    s_part[tid] = run;
+    __syncthreads();
+    if (tid == 0) { unsigned long long r = 0; for (int i = 0; i < 256; i++) { const unsigned long long v = s_part[i]; s_part[i] = r; r += v; } }
+    __syncthreads();
+    run = s_part[tid];
+    for (int i = lo; i < hi; i++) { run += c[i]; c[i] = run; }
+    __threadfence(); __syncthreads();                                   // (the sums are read by other threads of the group)
+    const unsigned long long total = c[h - 1];
+    if (total == 0) { for (int i = tid; i < n; i += 256) st[i] = (int32_t)((long long)i * h / n); return; }
+    const double tot = (double)total;
+    for (int i = tid; i < n; i += 256) {
+        int l = 0;
+        if (i > 0) {
+            const double target = __ddiv_rn(__dmul_rn(tot, (double)i), (double)n);
+            int r = h; l = 1;
+            while (l < r) { const int mid = (l + r) >> 1; if ((double)c[mid - 1] < target) l = mid + 1; else r = mid; }
+        }
+        st[i] = l;
+    }
+    __threadfence(); __syncthreads();
+    if (tid == 0) {
+        int prev = 0;
+        for (int i = 1; i < n; i++) { int v = max((int)st[i], prev + 1); if (v >= h) v = h - 1; st[i] = v; prev = v; }
+    }
+}
+
+// The predictor of every strip (parallelstripsadaptive.go:95-103), between the tANS walk -- which knows each candidate's final size --
+// and the offset scan: units 2 p (avg) and 2 p + 1 (gradient) are strip p's candidates; the gradient one is kept when it succeeded
+// and is not longer (or the avg one failed), and the other is marked skip_pack.  When both failed neither is packed anyway.
+// One thread per strip; BOUNDS: p < npairs, the batch holds 2 npairs units.
+__global__ void __launch_bounds__(256) k_pica_pick(MicUnit *units, int npairs) {
+    const int p = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (p >= npairs) return;
+    MicUnit &a = units[2 * p], &g = units[2 * p + 1];
+    const bool grad = g.status == MICD_OK && (a.status != MICD_OK || g.blob_len <= a.blob_len);
+    (grad ? a : g).skip_pack = 1u;
+}
+
+}  // namespace
+
+void mic_launch_pica_bounds(const uint16_t *d_px, const MicPicaImage *d_tab, int nimg, uint32_t rows, unsigned long long *d_cost,
+                            int32_t *d_starts, hipStream_t stream, MicTimer *t) {
+    if (t) t->mark("k_pica_rowcost");
+    if (rows) hipLaunchKernelGGL(k_pica_rowcost, dim3(rows), dim3(256), 0, stream, d_px, d_tab, nimg, d_cost);
+    if (t) t->mark("k_pica_partition");
+    hipLaunchKernelGGL(k_pica_partition, dim3((unsigned)nimg), dim3(256), 0, stream, d_tab, d_cost, d_starts);
+    if (t) t->mark("end");
+}
+void mic_launch_pica_pick(MicUnit *d_units, int npairs, hipStream_t stream, MicTimer *t) {
+    if (t) t->mark("k_pica_pick");
+    hipLaunchKernelGGL(k_pica_pick, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, stream, d_units, npairs);
+    if (t) t->mark("end");
+}
+
+namespace micapi {
+// adaptiveStripBoundaries, parallelstripsadaptive.go:222-289 -- the rule as the reference states it: float64 throughout, evaluated in
+// its order.  k_pica_partition is tested against it (mic_hip_pica_boundaries).
 std::vector<int> pica_boundaries(const std::vector<unsigned long long> &cost, int height, int num_strips) {
     std::vector<int> starts;
     if (num_strips >= height) { for (int i = 0; i < height; i++) starts.push_back(i); return starts; }
@@ -49,7 +143,7 @@ std::vector<int> pica_boundaries(const std::vector<unsigned long long> &cost, in
     return starts;
 }
 
-}  // namespace
+}  // namespace micapi
 
 extern "C" {
 
@@ -102,99 +196,6 @@ int mic_hip_decompress_frame_grad(const uint8_t *c, size_t len, uint16_t *pixels
     return MIC_OK;
 } MIC_ABI_CATCH
 
-// CompressParallelStripsAdaptive (parallelstripsadaptive.go:54-137)
-int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
-                          uint8_t *out, size_t out_cap, size_t *out_len) try {
-    if (!pixels || !out || !out_len || width <= 0 || height <= 0 || num_strips <= 0) return MIC_ERR_ARGS;
-    if ((size_t)width * (size_t)height > ((size_t)1 << 31)) return MIC_ERR_UNSUPPORTED;
-    if (num_strips > height) num_strips = height;                                          // :61-66
-    DefaultLease lease;
-    int rc = lease.acquire();
-    if (rc) return rc;
-    mic_hip_session *s = cur_default();
-    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the stream)
-    const size_t npx = (size_t)width * (size_t)height;
-    if ((rc = s->io_px.reserve(npx * 2 + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->io_px.p, pixels, npx * 2, hipMemcpyHostToDevice, s->stream));
-    std::vector<unsigned long long> cost((size_t)height, 0ull);
-    if (num_strips > 1 && num_strips < height) {
-        DevBuf d_cost;
-        if ((rc = d_cost.reserve((size_t)height * 8))) return rc;
-        hipLaunchKernelGGL(k_pica_rowcost, dim3((unsigned)std::max(1, height - 1)), dim3(256), 0, s->stream, (const uint16_t *)s->io_px.p, width, height,
-                           (unsigned long long *)d_cost.p);
-        hipError_t e = hipMemcpyAsync(cost.data(), d_cost.p, (size_t)height * 8, hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        d_cost.release();
-        if (e != hipSuccess) return MIC_ERR_DEVICE;
-        cost[0] = 0;
-    }
-    const std::vector<int> starts = pica_boundaries(cost, height, num_strips);
-    const int actual = (int)starts.size();
-    const size_t header = 16 + (size_t)actual * 16;
-    if (out_cap < header) return MIC_ERR_CAPACITY;
-    // units 2 s (avg) and 2 s + 1 (gradient) over the same pixels, in sub-batches that keep the workspace bounded
-    std::vector<std::vector<uint8_t>> blob((size_t)actual);
-    std::vector<uint32_t> flags((size_t)actual, 0);
-    int s0 = 0;
-    while (s0 < actual) {
-        size_t max_px = 0; int s1 = s0;
-        while (s1 < actual) {
-            const int y0 = starts[(size_t)s1], y1 = (s1 + 1 < actual) ? starts[(size_t)s1 + 1] : height;
-            const size_t mp = std::max(max_px, (size_t)(y1 - y0) * (size_t)width);
-            if (mp > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
-            if (s1 > s0 && unit_ws_bytes(mp) * 2 * (size_t)(s1 - s0 + 1) > kWorkspaceBudget) break;
-            max_px = mp; s1++;
-        }
-        const int ns = s1 - s0;
-        // a strip of no rows (the partition clamps late boundaries to the last row, :282-284) has nothing to code: the unit codec
-        // rejects it like the oracle does, in strip order with the other strips' errors
-        std::vector<mic_hip_unit> units; std::vector<int> slot((size_t)ns, -1);
-        for (int k = 0; k < ns; k++) {
-            const int y0 = starts[(size_t)(s0 + k)], y1 = (s0 + k + 1 < actual) ? starts[(size_t)(s0 + k) + 1] : height;
-            if (y1 <= y0) continue;
-            slot[(size_t)k] = (int)units.size();
-            units.push_back(mic_hip_unit{ (uint64_t)y0 * (uint64_t)width, width, y1 - y0, max_value, 2 });                                          // :92
-            units.push_back(mic_hip_unit{ (uint64_t)y0 * (uint64_t)width, width, y1 - y0, max_value, (uint16_t)(2 | MIC_HIP_PRED_GRAD) });         // :94
-        }
-        const int nu = (int)units.size();
-        std::vector<uint64_t> offs((size_t)nu + 1, 0); std::vector<int32_t> st((size_t)nu), nst((size_t)nu);
-        const uint8_t *d_blobs = nullptr;
-        if (nu) {
-            if ((rc = session_encode_enqueue(s, (const uint16_t *)s->io_px.p, units.data(), nu))) return rc;
-            if ((rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), nst.data()))) return rc;
-        }
-        for (int k = 0; k < ns; k++) {
-            if (slot[(size_t)k] < 0) return MIC_ERR_ARGS;
-            const size_t a = (size_t)slot[(size_t)k];
-            const int32_t e1 = st[a], e2 = st[a + 1];
-            const size_t la = (size_t)(offs[a + 1] - offs[a]), lg = (size_t)(offs[a + 2] - offs[a + 1]);
-            int pick;
-            if (e2 == MIC_OK && (e1 != MIC_OK || lg <= la)) pick = 1;                          // the smaller, or the one that succeeded (:97-105)
-            else { pick = 0; if (e1 != MIC_OK) return e1; }                                    // "pica: strip %d: ..." (:110-114)
-            const size_t len = pick ? lg : la;
-            blob[(size_t)(s0 + k)].resize(len);
-            flags[(size_t)(s0 + k)] = pick ? 1u : 0u;
-            if (len) HIP_TRY(hipMemcpy(blob[(size_t)(s0 + k)].data(), d_blobs + offs[a + (size_t)pick], len, hipMemcpyDeviceToHost));
-        }
-        s0 = s1;
-    }
-    size_t total = 0;
-    for (const auto &b : blob) total += b.size();
-    if (total > 0xFFFFFFFFull) return MIC_ERR_UNSUPPORTED;
-    if (out_cap < header + total) return MIC_ERR_CAPACITY;
-    memcpy(out, "PICA", 4);
-    put_u32(out + 4, (uint32_t)width); put_u32(out + 8, (uint32_t)height); put_u32(out + 12, (uint32_t)actual);
-    size_t off = 0;
-    for (int k = 0; k < actual; k++) {
-        uint8_t *e = out + 16 + (size_t)k * 16;
-        put_u32(e, (uint32_t)starts[(size_t)k]); put_u32(e + 4, (uint32_t)off); put_u32(e + 8, (uint32_t)blob[(size_t)k].size()); put_u32(e + 12, flags[(size_t)k]);
-        memcpy(out + header + off, blob[(size_t)k].data(), blob[(size_t)k].size());
-        off += blob[(size_t)k].size();
-    }
-    *out_len = header + total;
-    return MIC_OK;
-} MIC_ABI_CATCH
-
 int mic_hip_pica_info(const uint8_t *c, size_t len, int *width, int *height, int *num_strips) try {
     if (!c) return MIC_ERR_ARGS;
     if (len < 16 || memcmp(c, "PICA", 4) != 0) return MIC_ERR_CORRUPT;                      // :142-144
@@ -202,62 +203,6 @@ int mic_hip_pica_info(const uint8_t *c, size_t len, int *width, int *height, int
     if (n < 0 || (size_t)n > (len - 16) / 16) return MIC_ERR_CORRUPT;                       // truncated header, :150-153
     if (w <= 0 || h <= 0 || n <= 0) return MIC_ERR_CORRUPT;                                 // :154-156
     if (width) *width = w; if (height) *height = h; if (num_strips) *num_strips = n;
-    return MIC_OK;
-} MIC_ABI_CATCH
-
-// DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141-214)
-int mic_hip_pica_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
-    if (!c || !pixels_out) return MIC_ERR_ARGS;
-    int w, h, n;
-    int rc = mic_hip_pica_info(c, len, &w, &h, &n);
-    if (rc) return rc;
-    if (w != width || h != height) return MIC_ERR_ARGS;
-    const size_t header = 16 + (size_t)n * 16;
-    struct Strip { long y0, y1; size_t start, end; uint32_t flags; };
-    std::vector<Strip> st((size_t)n);
-    for (int k = 0; k < n; k++) {
-        const uint8_t *e = c + 16 + (size_t)k * 16;
-        Strip &t = st[(size_t)k];
-        t.y0 = (long)get_u32(e); t.y1 = (k + 1 < n) ? (long)get_u32(e + 16) : h;
-        t.start = header + get_u32(e + 4); t.end = t.start + get_u32(e + 8); t.flags = get_u32(e + 12);
-        if (t.end > len || t.start > t.end) return MIC_ERR_CORRUPT;                         // :186-190
-        if (t.y0 < 0 || t.y1 <= t.y0 || t.y1 > h) return MIC_ERR_CORRUPT;                   // Go: make / slice panics
-    }
-    DefaultLease lease;
-    if ((rc = lease.acquire())) return rc;
-    mic_hip_session *s = cur_default();
-    const size_t npx = (size_t)w * (size_t)h;
-    if ((rc = s->ensure(1, 1))) return rc;
-    if ((rc = s->io_px.reserve(npx * 2 + 64))) return rc;
-    HIP_TRY(hipMemsetAsync(s->io_px.p, 0, npx * 2, s->stream));                              // rows no strip covers stay 0 (make([]uint16), :175)
-    int k0 = 0;
-    while (k0 < n) {
-        size_t max_px = 0, comp = 0; int k1 = k0;
-        while (k1 < n) {
-            const size_t px = (size_t)(st[(size_t)k1].y1 - st[(size_t)k1].y0) * (size_t)w;
-            const size_t mp = std::max(max_px, px);
-            if (mp > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
-            if (k1 > k0 && unit_ws_bytes(mp) * (size_t)(k1 - k0 + 1) > kWorkspaceBudget) break;
-            max_px = mp; comp += st[(size_t)k1].end - st[(size_t)k1].start; k1++;
-        }
-        const int ns = k1 - k0;
-        if ((rc = s->io_comp.reserve(comp + 64))) return rc;
-        std::vector<mic_hip_unit> units((size_t)ns); std::vector<uint64_t> offs((size_t)ns + 1, 0);
-        for (int k = 0; k < ns; k++) {
-            const Strip &t = st[(size_t)(k0 + k)];
-            if (t.end == t.start) return MIC_ERR_CORRUPT;
-            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + offs[(size_t)k], c + t.start, t.end - t.start, hipMemcpyHostToDevice, s->stream));
-            offs[(size_t)k + 1] = offs[(size_t)k] + (t.end - t.start);
-            units[(size_t)k] = mic_hip_unit{ (uint64_t)t.y0 * (uint64_t)w, w, (int)(t.y1 - t.y0), 0,
-                                            (uint16_t)(2 | ((t.flags & 1u) ? MIC_HIP_PRED_GRAD : 0)) };   // picaFlagGradPredictor, :198-202
-        }
-        if ((rc = session_decode_enqueue(s, (const uint8_t *)s->io_comp.p, offs.data(), units.data(), ns, (uint16_t *)s->io_px.p))) return rc;
-        std::vector<int32_t> stt((size_t)ns);
-        if ((rc = session_decode_finish(s, stt.data()))) return rc;
-        for (int32_t v : stt) if (v != MIC_OK) return v;
-        k0 = k1;
-    }
-    HIP_TRY(hipMemcpy(pixels_out, s->io_px.p, npx * 2, hipMemcpyDeviceToHost));
     return MIC_OK;
 } MIC_ABI_CATCH
 

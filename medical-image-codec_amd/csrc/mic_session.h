@@ -159,7 +159,7 @@ struct mic_hip_session {
     bool shrink_pending = false;            //     set there; the next tier-1 layout then starts from released slabs
     static constexpr int kTierCalm = 8;     //     the session goes back to the small slabs and gives the large ones' memory back
     // what a tier-1 launch chain needs to be run again in tier 2 (session_*_finish)
-    struct Retry { int kind = 0; const void *d_in = nullptr; void *d_out = nullptr; std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; } retry;
+    struct Retry { int kind = 0; bool pairs = false; const void *d_in = nullptr; void *d_out = nullptr; std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; } retry;
     hipStream_t stream = nullptr;
     // Entry points may be called from any OS thread (cgo: any goroutine's thread), and a process may hold sessions on several
     // devices: every public call makes the session's device the calling thread's current one first.
@@ -168,6 +168,8 @@ struct mic_hip_session {
     DevBuf gap;                            // gap-removal units' map slabs (mic_gap_stride(tab_syms) each), reserved by the first batch that has one
     DevBuf io_px, io_comp;                 // staging for the host-pointer entry points
     DevBuf io_px2, io_comp2, packed2;      // their second halves: sub-batch k + 1 comes up while k is coded and k - 1 goes down (mic_host_io.hip)
+    DevBuf pica_tab, pica_cost, pica_starts;   // PICA: a sub-batch's image table, row costs and strip boundaries (mic_pica.hip)
+    PinnedU64 pica_pin[2];                 // ... and the host's copy of table + boundaries, one per staging half
     DevBuf wv_a, wv_b;                     // WaveletV2 coefficient planes (int32, two per frame of the batch)
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
@@ -324,18 +326,18 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
         if (wsi) { mic_wsi_store_free(wsi); wsi = nullptr; }
-        h_units.release(); pin_off.release();
+        h_units.release(); pin_off.release(); pica_pin[0].release(); pica_pin[1].release();
         readback_queued = pack_queued = false;
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
@@ -357,7 +359,9 @@ struct DefaultLease {
 };
 mic_hip_session *cur_default();     // the session the calling thread holds
 std::vector<int> default_devices(); // the devices of the host-pointer entry points (mic_hip_set_devices), the default first
-int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n);
+// pica_pairs: units 2 p and 2 p + 1 are the two candidates of one PICA strip -- k_pica_pick runs between the chain and the pack, the
+// loser is not packed and takes no room in the offsets session_encode_finish returns (its status is still reported)
+int session_encode_enqueue(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, bool pica_pairs = false);
 int session_encode_finish(mic_hip_session *s, const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *h_status, int32_t *h_nstates);
 int session_decode_enqueue(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets,
                            const mic_hip_unit *units, int n, uint16_t *d_pixels_out);
@@ -373,6 +377,8 @@ int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nf
                            uint8_t *out, size_t out_cap, size_t *out_len);
 int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_total, int n, uint16_t *frames_out);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
+// adaptiveStripBoundaries as the reference states it, on the host (mic_pica.hip); cost[y] = rowCost[y], cost[0] ignored
+std::vector<int> pica_boundaries(const std::vector<unsigned long long> &cost, int height, int num_strips);
 // one blocking host <-> device copy through the transfer engine of mic_host_io.hip (pinned host memory: DMA in place; ordinary
 // memory: staged through pinned slots by the worker threads).  The device side must be ready / is complete on return.
 int host_copy(int device, void *dev, void *host, size_t bytes, bool to_device);
