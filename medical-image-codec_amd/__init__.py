@@ -401,37 +401,56 @@ def decompress_single_frame(compressed, width: int, height: int) -> np.ndarray:
     return out.reshape(height, width)
 
 
-def compress_batch(frames: Sequence[np.ndarray], max_values: Sequence[int], nstates: int = 2
-                   ) -> List[Tuple[int, bytes, int]]:
-    """One launch chain over many frames; returns [(status, blob, nstates_used)]."""
-    n = len(frames)
-    arrs = [_u16(f) for f in frames]
-    outs = [np.empty(_frame_bound(a.size), dtype=np.uint8) for a in arrs]
-    jobs = (EncJob * n)()
+def _encode_batch(where: str, symbol: str, job_type, images, bound, outs=None, **fields):
+    """The body of every batch encoder: one `job_type` job per (height, width) uint16 image, every other input field one value
+    or one per image; without the caller's `outs`, image i gets a buffer of bound(i, array) bytes.  Returns (jobs, outs) once
+    `symbol` has run."""
+    n = len(images)
+    arrs = [_u16(a) for a in images]
+    if outs is None:
+        outs = [np.empty(bound(i, a), dtype=np.uint8) for i, a in enumerate(arrs)]
+    per = {k: v if np.ndim(v) else [v] * n for k, v in fields.items()}
+    jobs = (job_type * n)()
     for i, a in enumerate(arrs):
         h, w = a.shape
         jobs[i].pixels = a.ctypes.data; jobs[i].width = w; jobs[i].height = h
-        jobs[i].max_value = int(max_values[i]); jobs[i].nstates = nstates
+        for k, v in per.items():
+            setattr(jobs[i], k, int(v[i]))
         jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
-    rc = lib().mic_hip_compress_batch(jobs, n)
+    rc = getattr(lib(), symbol)(jobs, n)
     if rc:
-        _raise(rc, "compress_batch")
-    return [(jobs[i].status, outs[i][: jobs[i].out_len].tobytes() if jobs[i].status == 0 else b"", jobs[i].nstates_used)
-            for i in range(n)]
+        _raise(rc, where)
+    return jobs, outs
 
 
-def decompress_batch(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]]) -> List[Tuple[int, Optional[np.ndarray]]]:
-    n = len(blobs)
-    cs = [_bytes_arr(b) for b in blobs]
-    outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
-    jobs = (DecJob * n)()
+def _decode_batch(where: str, symbol: str, job_type, files, dims, outs=None):
+    """The body of every batch decoder: one `job_type` job per file, dims: (width, height) per file.  Returns (jobs, images),
+    images[i] the (height, width) uint16 view of file i's out buffer."""
+    n = len(files)
+    cs = [_bytes_arr(f) for f in files]
+    if outs is None:
+        outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
+    jobs = (job_type * n)()
     for i in range(n):
         jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
         jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
-    rc = lib().mic_hip_decompress_batch(jobs, n)
+    rc = getattr(lib(), symbol)(jobs, n)
     if rc:
-        _raise(rc, "decompress_batch")
-    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0]) if jobs[i].status == 0 else None) for i in range(n)]
+        _raise(rc, where)
+    return jobs, [o.reshape(h, w) for o, (w, h) in zip(outs, dims)]
+
+
+def compress_batch(frames: Sequence[np.ndarray], max_values: Sequence[int], nstates: int = 2
+                   ) -> List[Tuple[int, bytes, int]]:
+    """One launch chain over many frames; returns [(status, blob, nstates_used)]."""
+    jobs, outs = _encode_batch("compress_batch", "mic_hip_compress_batch", EncJob, frames, lambda i, a: _frame_bound(a.size),
+                               max_value=max_values, nstates=nstates)
+    return [(j.status, o[: j.out_len].tobytes() if j.status == 0 else b"", j.nstates_used) for j, o in zip(jobs, outs)]
+
+
+def decompress_batch(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]]) -> List[Tuple[int, Optional[np.ndarray]]]:
+    jobs, imgs = _decode_batch("decompress_batch", "mic_hip_decompress_batch", DecJob, blobs, dims)
+    return [(j.status, im if j.status == 0 else None) for j, im in zip(jobs, imgs)]
 
 
 # ------------------------------------------------------------------ gap removal
@@ -469,35 +488,15 @@ def decompress_single_frame_gap_removal(compressed, width: int, height: int) -> 
 def compress_batch_gap_removal(frames: Sequence[np.ndarray], max_values: Sequence[int], nstates: int = 2
                                ) -> List[Tuple[int, bytes, int]]:
     """compress_single_frame_gap_removal over many frames in one call; returns [(status, blob, nstates_used)]."""
-    n = len(frames)
-    arrs = [_u16(f) for f in frames]
-    outs = [np.empty(_gap_frame_bound(a.size), dtype=np.uint8) for a in arrs]
-    jobs = (EncJob * n)()
-    for i, a in enumerate(arrs):
-        h, w = a.shape
-        jobs[i].pixels = a.ctypes.data; jobs[i].width = w; jobs[i].height = h
-        jobs[i].max_value = int(max_values[i]); jobs[i].nstates = nstates
-        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
-    rc = lib().mic_hip_compress_batch_gap(jobs, n)
-    if rc:
-        _raise(rc, "compress_batch_gap_removal")
-    return [(jobs[i].status, outs[i][: jobs[i].out_len].tobytes() if jobs[i].status == 0 else b"", jobs[i].nstates_used)
-            for i in range(n)]
+    jobs, outs = _encode_batch("compress_batch_gap_removal", "mic_hip_compress_batch_gap", EncJob, frames,
+                               lambda i, a: _gap_frame_bound(a.size), max_value=max_values, nstates=nstates)
+    return [(j.status, o[: j.out_len].tobytes() if j.status == 0 else b"", j.nstates_used) for j, o in zip(jobs, outs)]
 
 
 def decompress_batch_gap_removal(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]]) -> List[Tuple[int, Optional[np.ndarray]]]:
     """decompress_single_frame_gap_removal over many streams in one call; returns [(status, pixels or None)]."""
-    n = len(blobs)
-    cs = [_bytes_arr(b) for b in blobs]
-    outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
-    jobs = (DecJob * n)()
-    for i in range(n):
-        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
-        jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
-    rc = lib().mic_hip_decompress_batch_gap(jobs, n)
-    if rc:
-        _raise(rc, "decompress_batch_gap_removal")
-    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0]) if jobs[i].status == 0 else None) for i in range(n)]
+    jobs, imgs = _decode_batch("decompress_batch_gap_removal", "mic_hip_decompress_batch_gap", DecJob, blobs, dims)
+    return [(j.status, im if j.status == 0 else None) for j, im in zip(jobs, imgs)]
 
 
 # ------------------------------------------------------------------ PICS
@@ -564,37 +563,18 @@ def compress_parallel_strips_batch(images: Sequence[np.ndarray], max_value: int,
                                    outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
     """Many images, one call (mic_hip_pics_compress_batch): [(status, file bytes as a uint8 view of its out buffer)].
     images: (height, width) uint16 arrays (ordinary or pinned memory); outs: caller buffers of >= pics_bound bytes, or None."""
-    n = len(images)
-    arrs = [_u16(a) for a in images]
-    if outs is None:
-        outs = [np.empty(pics_bound(a.shape[1], a.shape[0], num_strips), dtype=np.uint8) for a in arrs]
-    jobs = (PicsEncJob * n)()
-    for i, a in enumerate(arrs):
-        jobs[i].pixels = a.ctypes.data; jobs[i].width = a.shape[1]; jobs[i].height = a.shape[0]
-        jobs[i].max_value = max_value; jobs[i].nstates = nstates; jobs[i].num_strips = num_strips
-        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
-    rc = lib().mic_hip_pics_compress_batch(jobs, n)
-    if rc:
-        _raise(rc, "compress_parallel_strips_batch")
-    compress_parallel_strips_batch.failed_strips = [jobs[i].failed_strip for i in range(n)]     # (of the last call: index of each job's failing strip, -1)
-    return [(jobs[i].status, outs[i][: jobs[i].out_len]) for i in range(n)]
+    jobs, outs = _encode_batch("compress_parallel_strips_batch", "mic_hip_pics_compress_batch", PicsEncJob, images,
+                               lambda i, a: pics_bound(a.shape[1], a.shape[0], num_strips), outs,
+                               max_value=max_value, nstates=nstates, num_strips=num_strips)
+    compress_parallel_strips_batch.failed_strips = [j.failed_strip for j in jobs]     # (of the last call: index of each job's failing strip, -1)
+    return [(j.status, o[: j.out_len]) for j, o in zip(jobs, outs)]
 
 
 def decompress_parallel_strips_batch(files: Sequence, dims: Sequence[Tuple[int, int]],
                                      outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
     """Many PICS files, one call (mic_hip_pics_decompress_batch): [(status, (height, width) uint16 pixels)]."""
-    n = len(files)
-    cs = [_bytes_arr(f) for f in files]
-    if outs is None:
-        outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
-    jobs = (PicsDecJob * n)()
-    for i in range(n):
-        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
-        jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
-    rc = lib().mic_hip_pics_decompress_batch(jobs, n)
-    if rc:
-        _raise(rc, "decompress_parallel_strips_batch")
-    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0])) for i in range(n)]
+    jobs, imgs = _decode_batch("decompress_parallel_strips_batch", "mic_hip_pics_decompress_batch", PicsDecJob, files, dims, outs)
+    return [(j.status, im) for j, im in zip(jobs, imgs)]
 
 
 def host_alloc(nbytes: int, dtype=np.uint8) -> np.ndarray:
@@ -1119,40 +1099,19 @@ def compress_parallel_strips_adaptive_batch(images: Sequence[np.ndarray], max_va
     """Many images, one call (mic_hip_pica_compress_batch): [(status, file bytes as a uint8 view of its out buffer)].
     images: (height, width) uint16 arrays (ordinary or pinned memory); max_value, num_strips: one value, or one per image;
     outs: caller buffers of >= pica_bound bytes, or None."""
-    n = len(images)
-    arrs = [_u16(a) for a in images]
-    mxs = list(max_value) if np.ndim(max_value) else [max_value] * n
-    nss = list(num_strips) if np.ndim(num_strips) else [num_strips] * n
-    if outs is None:
-        outs = [np.empty(pica_bound(a.shape[1], a.shape[0], nss[i]), dtype=np.uint8) for i, a in enumerate(arrs)]
-    jobs = (PicaEncJob * n)()
-    for i, a in enumerate(arrs):
-        jobs[i].pixels = a.ctypes.data; jobs[i].width = a.shape[1]; jobs[i].height = a.shape[0]
-        jobs[i].max_value = int(mxs[i]); jobs[i].num_strips = int(nss[i])
-        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
-    rc = lib().mic_hip_pica_compress_batch(jobs, n)
-    if rc:
-        _raise(rc, "compress_parallel_strips_adaptive_batch")
-    compress_parallel_strips_adaptive_batch.failed_strips = [jobs[i].failed_strip for i in range(n)]   # (of the last call: index of each job's failing strip, -1)
-    return [(jobs[i].status, outs[i][: jobs[i].out_len]) for i in range(n)]
+    jobs, outs = _encode_batch("compress_parallel_strips_adaptive_batch", "mic_hip_pica_compress_batch", PicaEncJob, images,
+                               lambda i, a: pica_bound(a.shape[1], a.shape[0], num_strips[i] if np.ndim(num_strips) else num_strips), outs,
+                               max_value=max_value, num_strips=num_strips)
+    compress_parallel_strips_adaptive_batch.failed_strips = [j.failed_strip for j in jobs]   # (of the last call: index of each job's failing strip, -1)
+    return [(j.status, o[: j.out_len]) for j, o in zip(jobs, outs)]
 
 
 def decompress_parallel_strips_adaptive_batch(files: Sequence, dims: Sequence[Tuple[int, int]],
                                               outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
     """Many PICA files, one call (mic_hip_pica_decompress_batch): [(status, (height, width) uint16 pixels)]; dims: (width, height)."""
-    n = len(files)
-    cs = [_bytes_arr(f) for f in files]
-    if outs is None:
-        outs = [np.empty(w * h, dtype=np.uint16) for (w, h) in dims]
-    jobs = (PicaDecJob * n)()
-    for i in range(n):
-        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
-        jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
-    rc = lib().mic_hip_pica_decompress_batch(jobs, n)
-    if rc:
-        _raise(rc, "decompress_parallel_strips_adaptive_batch")
-    decompress_parallel_strips_adaptive_batch.failed_strips = [jobs[i].failed_strip for i in range(n)]
-    return [(jobs[i].status, outs[i].reshape(dims[i][1], dims[i][0])) for i in range(n)]
+    jobs, imgs = _decode_batch("decompress_parallel_strips_adaptive_batch", "mic_hip_pica_decompress_batch", PicaDecJob, files, dims, outs)
+    decompress_parallel_strips_adaptive_batch.failed_strips = [j.failed_strip for j in jobs]
+    return [(j.status, im) for j, im in zip(jobs, imgs)]
 
 
 def pica_boundaries(pixels, num_strips: int, on_host: bool = False) -> List[int]:

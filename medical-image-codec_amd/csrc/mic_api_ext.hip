@@ -552,14 +552,15 @@ struct PinnedHost {                                  // staging for the rows tha
     ~PinnedHost() { if (p) (void)hipHostFree(p); }
 };
 
-// mic_hip_wsi_compress_ex with shard b coding rows [row_first[b], row_first[b + 1]) on devs[b]: levels 0..K of its band, each
-// tile with the single-device tile path; devs[0] codes levels K + 1 .. L - 1 from the bands' rows of level K + 1 (of level K when
+// mic_hip_wsi_compress_ex with shard b coding rows [row_first[b], row_first[b + 1]) on the b-th listed device (micapi::over_devices
+// with the bands as its cut): levels 0..K of its band, each tile with the single-device tile path; the default device -- the first
+// listed -- codes levels K + 1 .. L - 1 from the bands' rows of level K + 1 (of level K when
 // tile_h is odd: a band of an odd number of level-K rows does not end on a row pair).  Within a level the tiles of band b are one
 // contiguous run of the tile table, so the lengths scan into the file's offsets and each shard writes its own runs of `out`.
 // One band (band_plan with one shard: K = L - 1) is the one-device slide.
 int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Level> &lv, int K, const std::vector<int> &row_first,
-                       const std::vector<int> &devs, uint8_t *out, size_t out_cap, size_t *out_len) {
-    const int nlev = (int)lv.size(), shards = (int)devs.size(), width = fmt.w, tile_h = fmt.th;
+                       uint8_t *out, size_t out_cap, size_t *out_len) {
+    const int nlev = (int)lv.size(), shards = (int)row_first.size() - 1, width = fmt.w, tile_h = fmt.th;
     const size_t bpp = fmt.bpp();
     size_t total_tiles = 0;
     for (const Level &l : lv) total_tiles += (size_t)l.tx * l.ty;
@@ -567,13 +568,13 @@ int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Lev
     if (out_cap < hdr) return MIC_ERR_CAPACITY;
     int rc = ensure_device();
     if (rc) return rc;
-    // the level devs[0] starts the top of the pyramid from: -1 none, 0 the caller's slide itself, else rows gathered from the bands
+    // the level the default device starts the top of the pyramid from: -1 none, 0 the caller's slide itself, else rows gathered from the bands
     const int top = nlev > K + 1 ? ((tile_h & 1) ? K : K + 1) : -1;
     PinnedHost stage;
     if (top > 0 && hipHostMalloc(&stage.p, (size_t)lv[(size_t)top].w * lv[(size_t)top].h * bpp + 64, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError(); return MIC_ERR_NOMEM;
     }
-    std::vector<std::vector<TileRun>> runs((size_t)shards);                   // shard b's runs: levels 0..K of its band (devs[0]: + the top)
+    std::vector<std::vector<TileRun>> runs((size_t)shards);                   // shard b's runs: levels 0..K of its band (band 0: + the top)
     // level L of an image on the device as one more run of `rs` (L.first: the level's first tile in the file)
     auto code_run = [&](mic_hip_session *s, const void *d_img, const Level &L, std::vector<TileRun> &rs) -> int {
         SlabBufs bufs;                                                          // (freed behind each level)
@@ -581,19 +582,16 @@ int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Lev
         rs.back().first = (size_t)L.first;
         return code_level(s, fmt, d_img, L, bufs, slab_tiles(fmt, (size_t)8 << 30), rs.back());
     };
-    rc = run_parallel(shards, [&](int b) -> int {
-        const int y0 = row_first[(size_t)b], rows = row_first[(size_t)b + 1] - y0;
-        if (rows <= 0) return MIC_OK;
+    rc = over_devices(row_first, [&](mic_hip_session *s, int y0, int y1) -> int {
+        const int rows = y1 - y0;
+        const size_t b = (size_t)(std::upper_bound(row_first.begin(), row_first.end(), y0) - row_first.begin()) - 1;   // the band that starts at y0
         std::vector<Level> bl;                                                  // the band's levels 0..K; first: global tile index
         for (int k = 0; k <= K; k++) {
             const int h = rows >> k;
             bl.push_back(Level{ lv[(size_t)k].w, h, lv[(size_t)k].tx, (h + tile_h - 1) / tile_h, lv[(size_t)k].first + (y0 >> k) / tile_h * lv[(size_t)k].tx });
         }
-        DefaultLease lease;
-        int r = lease.acquire(devs[(size_t)b]);
+        int r = s->ensure(1, (size_t)fmt.tw * fmt.th);
         if (r) return r;
-        mic_hip_session *s = lease.s;
-        if ((r = s->ensure(1, (size_t)fmt.tw * fmt.th))) return r;
         struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;   // freed on every return path
         std::vector<DevBuf> &img = bufs.img;
         img.resize((size_t)K + 2);
@@ -616,13 +614,13 @@ int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Lev
                                        hipMemcpyDeviceToHost, s->stream));
             HIP_TRY(hipStreamSynchronize(s->stream));
         }
-        for (int k = 0; k <= K && r == MIC_OK; k++) r = code_run(s, img[(size_t)k].p, bl[(size_t)k], runs[(size_t)b]);
+        for (int k = 0; k <= K && r == MIC_OK; k++) r = code_run(s, img[(size_t)k].p, bl[(size_t)k], runs[b]);
         return r;
     });
     if (rc) return rc;
-    if (top >= 0) {                                                             // the top of the pyramid on devs[0]
+    if (top >= 0) {                                                             // the top of the pyramid on the default device
         DefaultLease lease;
-        if ((rc = lease.acquire(devs[0]))) return rc;
+        if ((rc = lease.acquire())) return rc;
         mic_hip_session *s = lease.s;
         if ((rc = s->ensure(1, (size_t)fmt.tw * fmt.th))) return rc;
         struct Bufs { std::vector<DevBuf> img; ~Bufs() { for (auto &d : img) d.release(); } } bufs;
@@ -659,11 +657,14 @@ int wsi_compress_bands(const uint8_t *px, const Mic3 &fmt, const std::vector<Lev
 
 // Tiles [tx0, tx1] x [ty0, ty1] of level L into dst, an image of bw x bh pixels whose corner is the level's (bx, by = ty0 * th).
 // One device, or -- when the box spans two tile rows or more, several devices are listed and the call is not nested -- one
-// contiguous range of tile rows per device (shard_plan, weighted by pixels), each decoded into its own rows of dst.
+// contiguous range of tile rows per device (micapi::over_devices, weighted by pixels), each decoded into its own rows of dst.
 int decode_box(const BlobSource &src, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
                uint8_t *dst) {
     const int by = ty0 * m.th;
-    auto rows = [&](int r0, int r1, int device) -> int {                        // tile rows r0 .. r1 - 1
+    const int nrows = ty1 - ty0 + 1;
+    // tile row ty0 + r weighs its pixels; rows ty0 + r0 .. ty0 + r1 - 1 on one session
+    return over_devices(nrows, [&](int r) { return (uint64_t)bw * (uint64_t)std::min(m.th, by + bh - (ty0 + r) * m.th); }, [&](mic_hip_session *, int r0, int r1) -> int {
+        r0 += ty0; r1 += ty0;
         const int ys = r0 * m.th, hs = std::min(r1 * m.th, by + bh) - ys;
         std::vector<size_t> tiles; std::vector<int4> place;
         for (int ty = r0; ty < r1; ty++) for (int tx = tx0; tx <= tx1; tx++) {
@@ -672,22 +673,7 @@ int decode_box(const BlobSource &src, const Mic3 &m, const Level &L, int tx0, in
             tiles.push_back((size_t)L.first + (size_t)ty * L.tx + tx);
             place.push_back(make_int4(tx * m.tw - bx, ty * m.th - ys, aw, ah));
         }
-        DefaultLease lease;
-        const int rc = lease.acquire(device);
-        if (rc) return rc;
-        return decode_tiles(src, m, tiles, place, dst + (size_t)(ys - by) * bw * m.bpp(), bw, hs);
-    };
-    const int nrows = ty1 - ty0 + 1;
-    const std::vector<int> devs = default_devices();
-    const int shards = cur_default() ? 1 : (int)std::min<size_t>(devs.size(), (size_t)nrows);
-    if (shards <= 1) return rows(ty0, ty1 + 1, -1);
-    std::vector<uint64_t> w((size_t)nrows);
-    for (int r = 0; r < nrows; r++) w[(size_t)r] = (uint64_t)bw * (uint64_t)std::min(m.th, by + bh - (ty0 + r) * m.th);
-    std::vector<int> first((size_t)shards + 1);
-    plan_shards(w.data(), nrows, shards, first.data());
-    return run_parallel(shards, [&](int k) {
-        const int r0 = ty0 + first[(size_t)k], r1 = ty0 + first[(size_t)k + 1];
-        return r0 < r1 ? rows(r0, r1, devs[(size_t)k]) : MIC_OK;
+        return decode_tiles(src, m, tiles, place, dst + (size_t)(ys - by) * bw * m.bpp(), bw, hs);   // (on the session this thread now holds)
     });
 }
 int decode_box(const uint8_t *c, size_t len, const Mic3 &m, const Level &L, int tx0, int tx1, int ty0, int ty1, int bx, int bw, int bh,
@@ -767,12 +753,12 @@ int mic_hip_wsi_compress_ex(const uint8_t *rgb, int width, int height, int chann
             const int K = band_plan(height, fmt.th, (int)lv.size(), (int)devs.size(), row_first.data());
             int bands = 0;
             for (size_t b = 0; b < devs.size(); b++) bands += row_first[b + 1] > row_first[b];
-            if (bands >= 2) return wsi_compress_bands(rgb, fmt, lv, K, row_first, devs, out, out_cap, out_len);
+            if (bands >= 2) return wsi_compress_bands(rgb, fmt, lv, K, row_first, out, out_cap, out_len);
         }
     }
     std::vector<int> row_first(2);                                                          // the default device, or the session held
     const int K = band_plan(height, fmt.th, (int)lv.size(), 1, row_first.data());
-    return wsi_compress_bands(rgb, fmt, lv, K, row_first, std::vector<int>(1, -1), out, out_cap, out_len);
+    return wsi_compress_bands(rgb, fmt, lv, K, row_first, out, out_cap, out_len);
 } MIC_ABI_CATCH
 
 // CompressRGB (rgbcompress.go:25-27) = compressRGBTileBlob on the whole image: one "tile" of width x height

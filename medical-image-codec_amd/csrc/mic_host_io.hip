@@ -174,10 +174,28 @@ int io_submit(IoReq &req, int device, void *dev, const void *host, size_t bytes,
 // ============================================================================ pipelined unit codec over host buffers
 // A GROUP is what one destination buffer receives (a job, a PICS image, a MIC2 stack); its units are consecutive, their pixels
 // lie back to back in the group's host buffer, their streams go back to back behind `hdr` bytes of the group's output.
+struct DestRun {                                      // the run of streams a destination buffer receives behind its `hdr` bytes
+    uint8_t *out; size_t cap, hdr;
+    size_t written = 0; bool cap_fail = false;        // cap_fail: the run did not fit (the owner reports MIC_ERR_CAPACITY and appends no more)
+    // the next `bytes` of the run, from device memory that is ready (io_submit): queued on `down`, or the run is marked as too long
+    int append(IoReq &down, int device, const uint8_t *d_src, size_t bytes) {
+        if (hdr + written + bytes > cap) { cap_fail = true; return MIC_OK; }
+        const int rc = io_submit(down, device, const_cast<uint8_t *>(d_src), out + hdr + written, bytes, false);
+        written += bytes;
+        return rc;
+    }
+};
+// session_encode_finish has left a chain's streams in s->packed: they stay there while the next chain packs into the other half, which
+// the download `prev` (of the chain before; null: none) may still be reading
+inline int keep_packed(mic_hip_session *s, IoReq *prev) {
+    const int rc = prev ? prev->wait() : MIC_OK;
+    if (rc == MIC_OK) std::swap(s->packed, s->packed2);
+    return rc;
+}
 struct EncGroup {
-    const uint16_t *h_px; uint8_t *out; size_t out_cap, hdr;
+    const uint16_t *h_px; DestRun dst;
     int first, n;
-    size_t written = 0; int32_t status = MIC_OK;
+    int32_t status = MIC_OK;
     int failed = -1;                                  // the group's first unit that failed, counted from `first` ("strip %d", parallelstrips.go:97)
 };
 struct EncUnit {
@@ -197,12 +215,11 @@ struct DecUnit {
 
 inline bool unit_gap(const EncUnit &u) { return (u.nstates & MIC_HIP_GAP_REMOVAL) != 0; }
 inline bool unit_gap(const DecUnit &u) { return (u.flags & MIC_HIP_GAP_REMOVAL) != 0; }
-// units [i0, i1) of the next sub-batch: under the workspace ceiling, and -- when the call is large enough to be worth a pipeline --
+// units [i0, i1) of the next sub-batch of units [.., n): under the workspace ceiling, and -- when the call is large enough to be worth a pipeline --
 // about `target` units (the kernels want a couple of thousand units per launch: the tANS decode chain takes as long for ten
 // streams as for 2304)
 template <class U>
-int next_cut(const std::vector<U> &units, int i0, size_t target) {
-    const int n = (int)units.size();
+int next_cut(const std::vector<U> &units, int i0, int n, size_t target) {
     size_t max_px = 0, cap = 0, gap_x = 0; int i1 = i0;
     while (i1 < n) {
         const size_t px = (size_t)units[(size_t)i1].w * (size_t)units[(size_t)i1].h;
@@ -228,13 +245,15 @@ inline size_t pipeline_target(size_t n_units, bool encode) {
     return (n_units + parts - 1) / parts;
 }
 
-int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncUnit> &U) {
-    const int n = (int)U.size();
-    if (n == 0) return MIC_OK;
-    const size_t target = pipeline_target((size_t)n, true);
+// Groups [g0, g1) of the call -- their units are one range of U -- on session s; G and U are the caller's, every index is the call's.
+int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncUnit> &U, int g0, int g1) {
+    if (g0 >= g1) return MIC_OK;
+    const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
+    if (u0 == n) return MIC_OK;
+    const size_t target = pipeline_target((size_t)(n - u0), true);
     struct Sub { int i0, i1; IoReq up, down; std::vector<mic_hip_unit> units; size_t px = 0; };
     std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = 0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
+    for (int i0 = u0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, n, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
     DevBuf *in[2] = { &s->io_px, &s->io_px2 };
     int rc = MIC_OK;
     auto upload = [&](Sub &sb, int half) -> int {
@@ -272,9 +291,8 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
         const uint8_t *d_blobs = nullptr;
         if (rc == MIC_OK) rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, sb.units.data(), nb);
         if (rc == MIC_OK) rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data());
-        if (k >= 1) { const int r2 = subs[k - 1]->down.wait(); if (rc == MIC_OK) rc = r2; }   // (frees the packed buffer the next finish writes)
+        if (rc == MIC_OK) rc = keep_packed(s, k ? &subs[k - 1]->down : nullptr);
         if (rc != MIC_OK) break;
-        std::swap(s->packed, s->packed2);                  // d_blobs stays where it is while the next sub-batch packs into the other half
         for (int i = sb.i0; i < sb.i1;) {                  // per group: its streams of this sub-batch, one transfer
             EncGroup &g = G[(size_t)U[(size_t)i].group];
             int j = i;
@@ -288,12 +306,9 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
                 bytes += u.len;
             }
             if (g.status == MIC_OK) {
-                if (g.hdr + g.written + bytes > g.out_cap) g.status = MIC_ERR_CAPACITY;
-                else {
-                    rc = io_submit(sb.down, s->device, const_cast<uint8_t *>(d_blobs) + offs[(size_t)(i - sb.i0)], g.out + g.hdr + g.written, bytes, false);
-                    g.written += bytes;
-                    if (rc) break;
-                }
+                rc = g.dst.append(sb.down, s->device, d_blobs + offs[(size_t)(i - sb.i0)], bytes);
+                if (g.dst.cap_fail) g.status = MIC_ERR_CAPACITY;
+                if (rc) break;
             }
             i = j;
         }
@@ -302,13 +317,14 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
     return rc;
 }
 
-int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecUnit> &U) {
-    const int n = (int)U.size();
-    if (n == 0) return MIC_OK;
-    const size_t target = pipeline_target((size_t)n, false);
+int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecUnit> &U, int g0, int g1) {
+    if (g0 >= g1) return MIC_OK;
+    const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
+    if (u0 == n) return MIC_OK;
+    const size_t target = pipeline_target((size_t)(n - u0), false);
     struct Sub { int i0, i1; IoReq up, down; std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; size_t px = 0; };
     std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = 0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
+    for (int i0 = u0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, n, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
     DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
     int rc = MIC_OK;
     auto upload = [&](Sub &sb, int half) -> int {
@@ -393,77 +409,20 @@ int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecU
 }
 
 // ============================================================================ several devices
-// mic_hip_set_devices lists the GPUs the batch entry points may use.  A call's groups (jobs, images) are cut into one CONTIGUOUS
-// shard per listed device, balanced by pixels -- the static assignment of the reference's fan-outs (parallelstrips.go:77-93,
-// multiframecompress.go:186-209, wsicompress.go:126-145) -- and the shards run side by side, each on a thread of its own with a
-// session of its device's pool, its own sub-batch pipeline and the transfer engine's per-device streams and pinned slots.  Results
-// go straight into the caller's buffers: the caller's memory is what a rank-0 view would be, there is no gather.  (A device may be
+// mic_hip_set_devices lists the GPUs the batch entry points may use.  A call's items (groups, jobs, frames, tile rows) are cut into
+// one CONTIGUOUS shard per listed device, balanced by pixels -- the static assignment of the reference's fan-outs
+// (parallelstrips.go:77-93, multiframecompress.go:186-209, wsicompress.go:126-145) -- and micapi::over_devices below runs the shards
+// side by side, each on a thread of its own with a session of its device's pool, its own sub-batch pipeline and the transfer engine's
+// per-device streams and pinned slots.  Every shard works on the caller's own tables with the call's indices and its results go
+// straight into the caller's buffers: the caller's memory is what a rank-0 view would be, there is no gather.  (A device may be
 // listed twice: two shards, two sessions of one GPU.)
-// first[k] .. first[k + 1]: the items of shard k; boundary k is where the running weight first reaches k / shards of the total
-void shard_plan(const uint64_t *w, int n, int shards, int *first) {
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) total += w[i] ? w[i] : 1;
-    first[0] = 0;
-    uint64_t run = 0; int i = 0;
-    for (int k = 1; k < shards; k++) {
-        const uint64_t goal = (uint64_t)(((unsigned __int128)total * (unsigned)k) / (unsigned)shards);
-        while (i < n && run < goal) { run += w[i] ? w[i] : 1; i++; }
-        first[k] = i;
-    }
-    first[shards] = n;
-}
 
-template <class Grp, class Unt, class Run>
-int run_shards(std::vector<Grp> &G, std::vector<Unt> &U, Run run_one) {
-    const std::vector<int> devs = default_devices();
-    const int ng = (int)G.size();
-    int shards = (int)std::min<size_t>(devs.size(), (size_t)ng);
-    if (cur_default()) shards = 1;                    // (a nested call runs on the session its thread already holds)
-    if (shards <= 1) {
-        DefaultLease lease;
-        const int rc = lease.acquire();
-        return rc ? rc : run_one(lease.s, G, U);
-    }
-    std::vector<uint64_t> w((size_t)ng);
-    for (int g = 0; g < ng; g++) {
-        uint64_t px = 0;
-        for (int q = G[(size_t)g].first; q < G[(size_t)g].first + G[(size_t)g].n; q++) px += (uint64_t)U[(size_t)q].w * (uint64_t)U[(size_t)q].h;
-        w[(size_t)g] = px;
-    }
-    std::vector<int> first((size_t)shards + 1);
-    shard_plan(w.data(), ng, shards, first.data());
-    struct Shard { std::vector<Grp> G; std::vector<Unt> U; int rc = MIC_OK; };
-    std::vector<Shard> S((size_t)shards);
-    for (int k = 0; k < shards; k++) {
-        const int g0 = first[(size_t)k], g1 = first[(size_t)k + 1];
-        if (g0 == g1) continue;
-        const int u0 = G[(size_t)g0].first, u1 = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
-        S[(size_t)k].G.assign(G.begin() + g0, G.begin() + g1);
-        S[(size_t)k].U.assign(U.begin() + u0, U.begin() + u1);
-        for (Grp &g : S[(size_t)k].G) g.first -= u0;
-        for (Unt &u : S[(size_t)k].U) u.group -= g0;
-    }
-    int rc = run_parallel(shards, [&](int k) {
-        if (S[(size_t)k].G.empty()) return MIC_OK;
-        DefaultLease lease;
-        int r = lease.acquire(devs[(size_t)k]);
-        if (r == MIC_OK) r = run_one(lease.s, S[(size_t)k].G, S[(size_t)k].U);
-        return S[(size_t)k].rc = r;
-    });
-    for (int k = 0; k < shards; k++) {
-        const int g0 = first[(size_t)k];
-        if (S[(size_t)k].G.empty()) continue;
-        const int u0 = G[(size_t)g0].first;
-        for (size_t i = 0; i < S[(size_t)k].G.size(); i++) { Grp g = S[(size_t)k].G[i]; g.first += u0; G[(size_t)g0 + i] = g; }
-        for (size_t i = 0; i < S[(size_t)k].U.size(); i++) { Unt u = S[(size_t)k].U[i]; u.group += g0; U[(size_t)u0 + i] = u; }
-    }
-    return rc;
-}
-int encode_sharded(std::vector<EncGroup> &G, std::vector<EncUnit> &U) {
-    return run_shards(G, U, [](mic_hip_session *s, std::vector<EncGroup> &g, std::vector<EncUnit> &u) { return encode_groups(s, g, u); });
-}
-int decode_sharded(std::vector<DecGroup> &G, std::vector<DecUnit> &U) {
-    return run_shards(G, U, [](mic_hip_session *s, std::vector<DecGroup> &g, std::vector<DecUnit> &u) { return decode_groups(s, g, u); });
+// what the fan-out weighs a group by: its pixels
+template <class Grp, class Unt>
+uint64_t group_px(const Grp &g, const std::vector<Unt> &U) {
+    uint64_t px = 0;
+    for (int q = g.first; q < g.first + g.n; q++) px += (uint64_t)U[(size_t)q].w * (uint64_t)U[(size_t)q].h;
+    return px;
 }
 
 // the strips of a PICS image (parallelstrips.go:59-72)
@@ -484,9 +443,8 @@ inline void pics_geometry(int height, int num_strips, int &strip_h, int &actual)
 struct PicaRun {                                       // one job the call runs
     mic_hip_pica_enc_job *j; int n;                    // n: strips (num_strips clamped to the height, parallelstripsadaptive.go:61-66)
     std::vector<int32_t> y0, err; std::vector<uint32_t> len, flag;   // per strip; err: the strip's error (both candidates failed, no rows)
-    size_t written = 0; bool cap_fail = false;
-    size_t hdr() const { return 16 + 16 * (size_t)n; }
-    bool failed() const { if (cap_fail) return true; for (int32_t e : err) if (e != MIC_OK) return true; return false; }
+    DestRun dst;                                       // (behind the 16 + 16 n bytes of the header)
+    bool failed() const { if (dst.cap_fail) return true; for (int32_t e : err) if (e != MIC_OK) return true; return false; }
 };
 static_assert(sizeof(MicPicaImage) == 32, "the table travels as four u64 per image");
 
@@ -529,20 +487,20 @@ int pica_bounds_enqueue(mic_hip_session *s, PicaPart &p, const uint16_t *d_px, i
 }
 inline const int32_t *pica_starts_of(const mic_hip_session *s, const PicaPart &p, int half) { return (const int32_t *)(s->pica_pin[half].p + 4 * p.tab.size()); }
 
-int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J) {
-    const int nj = (int)J.size();
-    if (nj == 0) return MIC_OK;
+// jobs [j0, nj) of the call's J on session s
+int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj) {
+    if (j0 >= nj) return MIC_OK;
     int rc = s->ensure(1, 1);                                             // (the stream)
     if (rc) return rc;
 #ifdef MIC_PICA_TIMING
     PicaTimingScope timing(s, "encode");
 #endif
     size_t all_units = 0;
-    for (const PicaRun &r : J) all_units += 2 * (size_t)r.n;
+    for (int g = j0; g < nj; g++) all_units += 2 * (size_t)J[(size_t)g].n;
     const size_t target = pipeline_target(all_units, true);
     const size_t px_cap = workspace_budget() / 16;                        // u16 per staging half: the two halves take an eighth of the ceiling each
     std::vector<std::unique_ptr<PicaPart>> parts;
-    for (int g = 0; g < nj;) {
+    for (int g = j0; g < nj;) {
         auto p = std::make_unique<PicaPart>();
         p->g0 = g;
         size_t units = 0;
@@ -631,8 +589,7 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J) {
             rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), nst.data());
             chain_queued = false;
             if (rc) return drain(rc);
-            if (!downs.empty() && (rc = downs.back()->wait())) return drain(rc);   // (frees the packed buffer the next chain writes)
-            std::swap(s->packed, s->packed2);                             // d_blobs stays where it is while the next chain packs into the other half
+            if ((rc = keep_packed(s, downs.empty() ? nullptr : downs.back().get()))) return drain(rc);
             downs.push_back(std::make_unique<IoReq>());
             for (int q = s0; q < s1;) {                                   // per image: its winners of this chain lie back to back -- one transfer
                 PicaRun &r = J[(size_t)strips[(size_t)q].job];
@@ -651,19 +608,11 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J) {
                 }
 #ifndef MIC_PICA_NO_PICK
                 const size_t bytes = (size_t)(offs[(size_t)(2 * (e - s0))] - offs[(size_t)(2 * (q - s0))]);
-                if (!r.failed()) {
-                    if (r.hdr() + r.written + bytes > r.j->out_cap) r.cap_fail = true;
-                    else {
-                        if ((rc = io_submit(*downs.back(), s->device, const_cast<uint8_t *>(d_blobs) + offs[(size_t)(2 * (q - s0))], r.j->out + r.hdr() + r.written, bytes, false))) return drain(rc);
-                        r.written += bytes;
-                    }
-                }
+                if (!r.failed() && (rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[(size_t)(2 * (q - s0))], bytes))) return drain(rc);
 #else
                 for (int z = q; z < e && !r.failed(); z++) {
                     const size_t a = (size_t)(2 * (z - s0)) + r.flag[(size_t)strips[(size_t)z].idx], bytes = (size_t)(offs[a + 1] - offs[a]);
-                    if (r.hdr() + r.written + bytes > r.j->out_cap) { r.cap_fail = true; break; }
-                    if ((rc = io_submit(*downs.back(), s->device, const_cast<uint8_t *>(d_blobs) + offs[a], r.j->out + r.hdr() + r.written, bytes, false))) return drain(rc);
-                    r.written += bytes;
+                    if ((rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[a], bytes))) return drain(rc);
                 }
 #endif
                 q = e;
@@ -674,31 +623,52 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J) {
     return drain(MIC_OK);
 }
 
-// the valid jobs of a call, one contiguous range per device of mic_hip_set_devices, weighted by pixels
-template <class Run, class Weight, class Work>
-int pica_sharded(std::vector<Run> &J, Weight weight, Work work) {
-    const std::vector<int> devs = default_devices();
-    int shards = (int)std::min<size_t>(devs.size(), J.size());
-    if (cur_default()) shards = 1;                    // (a nested call runs on the session its thread already holds)
-    if (shards <= 1) {
-        DefaultLease lease;
-        const int rc = lease.acquire();
-        return rc ? rc : work(lease.s, J);
+// ============================================================================ strip files: PICS (parallelstrips.go), PICA (parallelstripsadaptive.go)
+// The batch decoder of both: a file is a header and one unit per strip.  info: the file's width, height and strip count;
+// entry(c, h, n, k): strip k as its header states it; pica: the call is a PICA one (-DMIC_PICA_TIMING builds time those).
+struct StripEntry { long y0, y1; size_t start, len; uint16_t flags; };   // rows [y0, y1), bytes [start, start + len) of the file, the unit's flags
+template <class Job, class Info, class Entry>
+int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry entry) {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::vector<DecGroup> G; std::vector<DecUnit> U; std::vector<int> job_of;
+    for (int i = 0; i < njobs; i++) {
+        Job &j = jobs[i];
+        j.failed_strip = -1;
+        if (!j.compressed || !j.pixels_out) { j.status = MIC_ERR_ARGS; continue; }
+        int w, h, n;
+        if ((j.status = info(j.compressed, j.compressed_len, &w, &h, &n))) continue;
+        if (w != j.width || h != j.height) { j.status = MIC_ERR_ARGS; continue; }
+        const size_t u0 = U.size();
+        int32_t bad = MIC_OK; size_t covered = 0;
+        for (int k = 0; k < n && bad == MIC_OK; k++) {
+            const StripEntry e = entry(j.compressed, h, n, k);
+            const size_t end = e.start + e.len;
+            if (end > j.compressed_len || e.start > end) { bad = MIC_ERR_CORRUPT; break; }    // parallelstrips.go:300-304, parallelstripsadaptive.go:186-190
+            if (e.y0 < 0 || e.y1 <= e.y0 || e.y1 > h) { bad = MIC_ERR_CORRUPT; break; }       // Go: make / slice panics
+            if (e.len == 0) { bad = MIC_ERR_CORRUPT; break; }
+            if ((size_t)w * (size_t)(e.y1 - e.y0) > ((size_t)1 << 28)) { bad = MIC_ERR_UNSUPPORTED; break; }
+            U.push_back(DecUnit{ e.start, e.len, (uint64_t)e.y0 * (uint64_t)w, w, (int32_t)(e.y1 - e.y0), e.flags, (int)G.size() });
+            covered += (size_t)w * (size_t)(e.y1 - e.y0);
+        }
+        if (bad != MIC_OK) { U.resize(u0); j.status = bad; continue; }
+        // pixels no strip writes come back as zeros, like the reference's make([]uint16, w*h) (parallelstrips.go:288,
+        // parallelstripsadaptive.go:175): a header whose strips do not cover the image is accepted there
+        if (covered < (size_t)w * (size_t)h) memset(j.pixels_out, 0, (size_t)w * (size_t)h * 2);
+        G.push_back(DecGroup{ j.compressed, j.pixels_out, (int)u0, n });
+        job_of.push_back(i);
     }
-    std::vector<uint64_t> w(J.size());
-    for (size_t i = 0; i < J.size(); i++) w[i] = weight(J[i]);
-    std::vector<int> first((size_t)shards + 1);
-    shard_plan(w.data(), (int)J.size(), shards, first.data());
-    std::vector<std::vector<Run>> S((size_t)shards);
-    for (int k = 0; k < shards; k++) S[(size_t)k].assign(std::make_move_iterator(J.begin() + first[(size_t)k]), std::make_move_iterator(J.begin() + first[(size_t)k + 1]));
-    const int rc = run_parallel(shards, [&](int k) {
-        if (S[(size_t)k].empty()) return (int)MIC_OK;
-        DefaultLease lease;
-        const int r = lease.acquire(devs[(size_t)k]);
-        return r ? r : work(lease.s, S[(size_t)k]);
-    });
-    for (int k = 0; k < shards; k++) std::move(S[(size_t)k].begin(), S[(size_t)k].end(), J.begin() + first[(size_t)k]);
-    return rc;
+#ifdef MIC_PICA_TIMING
+    DefaultLease lease;                                 // (the call then runs on this session: one device)
+    if (pica && (rc = lease.acquire())) return rc;
+    std::unique_ptr<PicaTimingScope> timing(pica ? new PicaTimingScope(lease.s, "decode") : nullptr);
+#endif
+    if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
+                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1); }))) return rc;
+    for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "strip %d: %w", parallelstrips.go:316; "pica: strip %d: %w", :207
+    return MIC_OK;
 }
 
 }  // namespace
@@ -710,7 +680,19 @@ int host_copy(int device, void *dev, void *host, size_t bytes, bool to_device) {
     const int r2 = req.wait();
     return rc ? rc : r2;
 }
-void plan_shards(const uint64_t *w, int n, int shards, int *first) { shard_plan(w, n, shards, first); }
+// first[k] .. first[k + 1]: the items of shard k; boundary k is where the running weight first reaches k / shards of the total
+void plan_shards(const uint64_t *w, int n, int shards, int *first) {
+    uint64_t total = 0;
+    for (int i = 0; i < n; i++) total += w[i] ? w[i] : 1;
+    first[0] = 0;
+    uint64_t run = 0; int i = 0;
+    for (int k = 1; k < shards; k++) {
+        const uint64_t goal = (uint64_t)(((unsigned __int128)total * (unsigned)k) / (unsigned)shards);
+        while (i < n && run < goal) { run += w[i] ? w[i] : 1; i++; }
+        first[k] = i;
+    }
+    first[shards] = n;
+}
 int run_parallel(int n, const std::function<int(int)> &work) {
     std::vector<int> rcs((size_t)std::max(n, 0), MIC_OK);
     auto one = [&](int k) {
@@ -729,6 +711,33 @@ int run_parallel(int n, const std::function<int(int)> &work) {
     for (int r : rcs) if (r != MIC_OK) return r;
     return MIC_OK;
 }
+int over_devices(const std::vector<int> &first, const ShardWork &work) {
+    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: on stderr)
+    const std::vector<int> devs = default_devices();
+    const int cut = (int)first.size() - 1;
+    if (cut < 1) return MIC_ERR_INTERNAL;
+    const int shards = (cur_default() || (size_t)cut > devs.size()) ? 1 : cut;   // (a nested call runs on the session its thread already holds)
+    return run_parallel(shards, [&](int k) -> int {
+        const int i0 = shards == 1 ? first.front() : first[(size_t)k], i1 = shards == 1 ? first.back() : first[(size_t)k + 1];
+        if (i0 >= i1) return MIC_OK;
+        DefaultLease lease;
+        const int rc = lease.acquire(shards == 1 ? -1 : devs[(size_t)k]);
+        if (rc) return rc;
+        if (trace) fprintf(stderr, "[mic_hip devices] shard %d of %d on device %d: items %d .. %d\n", k + 1, shards, lease.s->device, i0, i1 - 1);
+        return work(lease.s, i0, i1);
+    });
+}
+int over_devices(int n, const std::function<uint64_t(int)> &weight, const ShardWork &work) {
+    const int shards = cur_default() ? 1 : (int)std::min<size_t>(default_devices().size(), (size_t)std::max(n, 0));
+    std::vector<int> first{ 0, n };
+    if (shards > 1) {
+        std::vector<uint64_t> w((size_t)n);
+        for (int i = 0; i < n; i++) w[(size_t)i] = weight(i);
+        first.resize((size_t)shards + 1);
+        plan_shards(w.data(), n, shards, first.data());
+    }
+    return over_devices(first, work);
+}
 }  // namespace micapi
 
 // ================================================================================ C ABI
@@ -738,7 +747,7 @@ extern "C" {
 // mic_hip_set_devices (first[0 .. shards]: item i belongs to shard k iff first[k] <= i < first[k + 1]); no device needed.
 int mic_hip_shard_plan(const uint64_t *weights, int n, int shards, int *first) try {
     if (!weights || !first || n < 0 || shards <= 0) return MIC_ERR_ARGS;
-    shard_plan(weights, n, shards, first);
+    plan_shards(weights, n, shards, first);
     return MIC_OK;
 } MIC_ABI_CATCH
 
@@ -764,15 +773,16 @@ static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
         j.out_len = 0; j.nstates_used = 0;
         if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || (size_t)j.width * (size_t)j.height > ((size_t)1 << 28) ||
             !(j.nstates == 2 || j.nstates == 4 || j.nstates == 8)) { j.status = MIC_ERR_ARGS; continue; }
-        G.push_back(EncGroup{ j.pixels, j.out, j.out_cap, 0, (int)U.size(), 1 });
+        G.push_back(EncGroup{ j.pixels, DestRun{ j.out, j.out_cap, 0 }, (int)U.size(), 1 });
         U.push_back(EncUnit{ 0, j.width, j.height, j.max_value, (uint16_t)(j.nstates | flags), (int)G.size() - 1 });
         job_of.push_back(i);
     }
-    if ((rc = encode_sharded(G, U))) return rc;
+    if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
+                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) {
         mic_hip_enc_job &j = jobs[job_of[k]];
         j.status = G[k].status; j.nstates_used = U[k].nstates_used;
-        j.out_len = G[k].status == MIC_OK ? G[k].written : 0;
+        j.out_len = G[k].status == MIC_OK ? G[k].dst.written : 0;
     }
     return MIC_OK;
 }
@@ -799,7 +809,8 @@ static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
         U.push_back(DecUnit{ 0, j.compressed_len, 0, j.width, j.height, flags, (int)G.size() - 1 });
         job_of.push_back(i);
     }
-    if ((rc = decode_sharded(G, U))) return rc;
+    if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
+                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) jobs[job_of[k]].status = G[k].status;
     return MIC_OK;
 }
@@ -827,21 +838,22 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
         const size_t header = 20 + (size_t)actual * 8;
         if ((size_t)j.width * (size_t)strip_h > ((size_t)1 << 28)) { j.status = MIC_ERR_UNSUPPORTED; continue; }
         if (j.out_cap < header) { j.status = MIC_ERR_CAPACITY; continue; }
-        G.push_back(EncGroup{ j.pixels, j.out, j.out_cap, header, (int)U.size(), actual });
+        G.push_back(EncGroup{ j.pixels, DestRun{ j.out, j.out_cap, header }, (int)U.size(), actual });
         for (int s = 0; s < actual; s++) {
             const int y0 = s * strip_h, y1 = std::min(j.height, y0 + strip_h);
             U.push_back(EncUnit{ (uint64_t)y0 * (uint64_t)j.width, j.width, y1 - y0, j.max_value, j.nstates, (int)G.size() - 1 });   // global maxValue for every strip, :88
         }
         job_of.push_back(i); geo.push_back(Geo{ strip_h, actual });
     }
-    if ((rc = encode_sharded(G, U))) return rc;
+    if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
+                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) {
         mic_hip_pics_enc_job &j = jobs[job_of[k]];
         const EncGroup &g = G[k];
         j.status = g.status;                                                   // first failing strip, :95-99
         j.failed_strip = g.failed;                                             // "parallelstrips: strip %d: %w", :97
         if (j.status != MIC_OK) continue;
-        if (g.written > 0xFFFFFFFFull) { j.status = MIC_ERR_UNSUPPORTED; continue; }
+        if (g.dst.written > 0xFFFFFFFFull) { j.status = MIC_ERR_UNSUPPORTED; continue; }
         uint8_t *out = j.out;
         memcpy(out, "PICS", 4);
         put_u32(out + 4, (uint32_t)j.width); put_u32(out + 8, (uint32_t)j.height);
@@ -853,7 +865,7 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
             put_u32(out + 24 + (size_t)s * 8, (uint32_t)len);
             off += len;
         }
-        j.out_len = g.hdr + g.written;
+        j.out_len = g.dst.hdr + g.dst.written;
     }
     return MIC_OK;
 } MIC_ABI_CATCH
@@ -878,43 +890,12 @@ int mic_hip_pics_compress_ex(const uint16_t *pixels, int width, int height, uint
 } MIC_ABI_CATCH
 
 int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs) try {
-    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
-    if (njobs == 0) return MIC_OK;
-    int rc = ensure_device();
-    if (rc) return rc;
-    std::vector<DecGroup> G; std::vector<DecUnit> U; std::vector<int> job_of;
-    for (int i = 0; i < njobs; i++) {
-        mic_hip_pics_dec_job &j = jobs[i];
-        j.failed_strip = -1;
-        if (!j.compressed || !j.pixels_out) { j.status = MIC_ERR_ARGS; continue; }
-        int w, h, n, sh;
-        if ((j.status = mic_hip_pics_info(j.compressed, j.compressed_len, &w, &h, &n, &sh))) continue;
-        if (w != j.width || h != j.height) { j.status = MIC_ERR_ARGS; continue; }
-        const uint8_t *c = j.compressed; const size_t len = j.compressed_len;
-        const size_t header = 20 + (size_t)n * 8;
-        const size_t u0 = U.size();
-        int32_t bad = MIC_OK; size_t covered = 0;
-        for (int s = 0; s < n && bad == MIC_OK; s++) {
-            const size_t so = get_u32(c + 20 + (size_t)s * 8), sl = get_u32(c + 24 + (size_t)s * 8);
-            const size_t start = header + so, end = start + sl;
-            if (end > len || start > end) { bad = MIC_ERR_CORRUPT; break; }          // :300-304
-            const long y0 = (long)s * sh, y1 = std::min<long>(h, y0 + sh);
-            if (y0 >= h) { bad = MIC_ERR_CORRUPT; break; }
-            if (sl == 0) { bad = MIC_ERR_CORRUPT; break; }
-            if ((size_t)w * (size_t)(y1 - y0) > ((size_t)1 << 28)) { bad = MIC_ERR_UNSUPPORTED; break; }
-            U.push_back(DecUnit{ start, sl, (uint64_t)y0 * (uint64_t)w, w, (int32_t)(y1 - y0), 0, (int)G.size() });
-            covered += (size_t)w * (size_t)(y1 - y0);
-        }
-        if (bad != MIC_OK) { U.resize(u0); j.status = bad; continue; }
-        // pixels no strip writes come back as zeros, like the reference's make([]uint16, w*h) (parallelstrips.go:288): a header
-        // whose strips do not cover the image is accepted there
-        if (covered < (size_t)w * (size_t)h) memset(j.pixels_out, 0, (size_t)w * (size_t)h * 2);
-        G.push_back(DecGroup{ c, j.pixels_out, (int)u0, n });
-        job_of.push_back(i);
-    }
-    if ((rc = decode_sharded(G, U))) return rc;
-    for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "strip %d: %w", parallelstrips.go:316
-    return MIC_OK;
+    return strips_decompress_batch(jobs, njobs, false,
+        [](const uint8_t *c, size_t len, int *w, int *h, int *n) { return mic_hip_pics_info(c, len, w, h, n, nullptr); },
+        [](const uint8_t *c, int h, int n, int k) {                            // strip k: strip_height rows from k * strip_height (:288-304)
+            const long sh = (long)get_u32(c + 16), y0 = k * sh;
+            return StripEntry{ y0, std::min<long>(h, y0 + sh), 20 + (size_t)n * 8 + get_u32(c + 20 + (size_t)k * 8), get_u32(c + 24 + (size_t)k * 8), 0 };
+        });
 } MIC_ABI_CATCH
 
 int mic_hip_pics_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
@@ -943,21 +924,22 @@ int mic_hip_pica_compress_batch(mic_hip_pica_enc_job *jobs, int njobs) try {
         if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || j.num_strips <= 0) { j.status = MIC_ERR_ARGS; continue; }
         if ((size_t)j.width * (size_t)j.height > ((size_t)1 << 31)) { j.status = MIC_ERR_UNSUPPORTED; continue; }
         PicaRun r; r.j = &j; r.n = std::min(j.num_strips, j.height);                             // :61-66
-        if (j.out_cap < r.hdr()) { j.status = MIC_ERR_CAPACITY; continue; }
+        r.dst = DestRun{ j.out, j.out_cap, 16 + 16 * (size_t)r.n };
+        if (j.out_cap < r.dst.hdr) { j.status = MIC_ERR_CAPACITY; continue; }
         r.y0.assign((size_t)r.n, 0); r.err.assign((size_t)r.n, MIC_OK); r.len.assign((size_t)r.n, 0); r.flag.assign((size_t)r.n, 0);
         j.status = MIC_ERR_DEVICE;                                                                 // (until the job has run: a call that fails as a whole leaves no stale status)
         J.push_back(std::move(r));
     }
-    rc = pica_sharded(J, [](const PicaRun &r) { return (uint64_t)r.j->width * (uint64_t)r.j->height; },
-                      [](mic_hip_session *s, std::vector<PicaRun> &part) { return pica_encode_run(s, part); });
+    rc = over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i].j->width * (uint64_t)J[(size_t)i].j->height; },
+                      [&](mic_hip_session *s, int j0, int j1) { return pica_encode_run(s, J, j0, j1); });
     if (rc) return rc;
     for (PicaRun &r : J) {
         mic_hip_pica_enc_job &j = *r.j;
         j.status = MIC_OK;
         for (int k = 0; k < r.n && j.status == MIC_OK; k++)
             if (r.err[(size_t)k] != MIC_OK) { j.status = r.err[(size_t)k]; j.failed_strip = k; }   // the first strip, in strip order (:110-114)
-        if (j.status == MIC_OK && r.cap_fail) j.status = MIC_ERR_CAPACITY;
-        if (j.status == MIC_OK && r.written > 0xFFFFFFFFull) j.status = MIC_ERR_UNSUPPORTED;    // u32 offsets (:120-128)
+        if (j.status == MIC_OK && r.dst.cap_fail) j.status = MIC_ERR_CAPACITY;
+        if (j.status == MIC_OK && r.dst.written > 0xFFFFFFFFull) j.status = MIC_ERR_UNSUPPORTED;    // u32 offsets (:120-128)
         if (j.status != MIC_OK) continue;
         uint8_t *out = j.out;
         memcpy(out, "PICA", 4);
@@ -968,7 +950,7 @@ int mic_hip_pica_compress_batch(mic_hip_pica_enc_job *jobs, int njobs) try {
             put_u32(e, (uint32_t)r.y0[(size_t)k]); put_u32(e + 4, (uint32_t)off); put_u32(e + 8, r.len[(size_t)k]); put_u32(e + 12, r.flag[(size_t)k]);
             off += r.len[(size_t)k];
         }
-        j.out_len = r.hdr() + r.written;
+        j.out_len = r.dst.hdr + r.dst.written;
     }
     return MIC_OK;
 } MIC_ABI_CATCH
@@ -1028,52 +1010,12 @@ int mic_hip_pica_boundaries(const uint16_t *pixels, int width, int height, int n
 } MIC_ABI_CATCH
 
 int mic_hip_pica_decompress_batch(mic_hip_pica_dec_job *jobs, int njobs) try {
-    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
-    if (njobs == 0) return MIC_OK;
-    int rc = ensure_device();
-    if (rc) return rc;
-    std::vector<DecGroup> G; std::vector<DecUnit> U; std::vector<int> job_of;
-    for (int i = 0; i < njobs; i++) {
-        mic_hip_pica_dec_job &j = jobs[i];
-        j.failed_strip = -1;
-        if (!j.compressed || !j.pixels_out) { j.status = MIC_ERR_ARGS; continue; }
-        int w, h, n;
-        if ((j.status = mic_hip_pica_info(j.compressed, j.compressed_len, &w, &h, &n))) continue;
-        if (w != j.width || h != j.height) { j.status = MIC_ERR_ARGS; continue; }
-        const uint8_t *c = j.compressed; const size_t len = j.compressed_len;
-        const size_t header = 16 + (size_t)n * 16;
-        const size_t u0 = U.size();
-        int32_t bad = MIC_OK; size_t covered = 0;
-        for (int k = 0; k < n && bad == MIC_OK; k++) {
+    return strips_decompress_batch(jobs, njobs, true, mic_hip_pica_info,
+        [](const uint8_t *c, int h, int n, int k) {                            // strip k: from its y0 to the next strip's (:186-202)
             const uint8_t *e = c + 16 + (size_t)k * 16;
-            const long y0 = (long)get_u32(e), y1 = (k + 1 < n) ? (long)get_u32(e + 16) : h;
-            const size_t start = header + get_u32(e + 4), end = start + get_u32(e + 8); const uint32_t flags = get_u32(e + 12);
-            if (end > len || start > end) { bad = MIC_ERR_CORRUPT; break; }                      // :186-190
-            if (y0 < 0 || y1 <= y0 || y1 > h) { bad = MIC_ERR_CORRUPT; break; }                  // Go: make / slice panics
-            if (end == start) { bad = MIC_ERR_CORRUPT; break; }
-            if ((size_t)w * (size_t)(y1 - y0) > ((size_t)1 << 28)) { bad = MIC_ERR_UNSUPPORTED; break; }
-            U.push_back(DecUnit{ start, end - start, (uint64_t)y0 * (uint64_t)w, w, (int32_t)(y1 - y0),
-                                 (uint16_t)(2 | ((flags & 1u) ? MIC_HIP_PRED_GRAD : 0)), (int)G.size() });   // picaFlagGradPredictor, :198-202
-            covered += (size_t)w * (size_t)(y1 - y0);
-        }
-        if (bad != MIC_OK) { U.resize(u0); j.status = bad; continue; }
-        if (covered < (size_t)w * (size_t)h) memset(j.pixels_out, 0, (size_t)w * (size_t)h * 2);   // rows no strip covers stay 0 (make([]uint16), :175)
-        G.push_back(DecGroup{ c, j.pixels_out, (int)u0, n });
-        job_of.push_back(i);
-    }
-#ifdef MIC_PICA_TIMING
-    {                                                   // (on the session the call then runs on: one device)
-        DefaultLease lease;
-        if ((rc = lease.acquire())) return rc;
-        PicaTimingScope timing(lease.s, "decode");
-        rc = decode_sharded(G, U);
-    }
-#else
-    rc = decode_sharded(G, U);
-#endif
-    if (rc) return rc;
-    for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "pica: strip %d: %w", :207
-    return MIC_OK;
+            return StripEntry{ (long)get_u32(e), (k + 1 < n) ? (long)get_u32(e + 16) : h, 16 + (size_t)n * 16 + get_u32(e + 4), get_u32(e + 8),
+                               (uint16_t)(2 | ((get_u32(e + 12) & 1u) ? MIC_HIP_PRED_GRAD : 0)) };   // picaFlagGradPredictor
+        });
 } MIC_ABI_CATCH
 
 // DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141-214): a batch of one
@@ -1106,22 +1048,23 @@ int mic_hip_mic2_compress(const uint16_t *frames, int width, int height, int nfr
     const size_t fb = MIC_HIP_FRAME_BOUND(npx);
     int shards = cur_default() ? 1 : (int)std::min<size_t>(default_devices().size(), (size_t)nframes / 8);
     if (shards < 1 || out_cap < header + (size_t)nframes * fb) shards = 1;
-    std::vector<EncGroup> G; std::vector<EncUnit> U;
+    std::vector<EncGroup> G; std::vector<EncUnit> U; std::vector<int> first(1, 0);
     for (int k = 0; k < shards; k++) {
-        const int f0 = (int)((int64_t)nframes * k / shards), f1 = (int)((int64_t)nframes * (k + 1) / shards);
+        const int f0 = first.back(), f1 = (int)((int64_t)nframes * (k + 1) / shards);
         const size_t start = shards == 1 ? header : header + (size_t)f0 * fb;
-        G.push_back(EncGroup{ frames, out, shards == 1 ? out_cap : start + (size_t)(f1 - f0) * fb, start, f0, f1 - f0 });
+        G.push_back(EncGroup{ frames, DestRun{ out, shards == 1 ? out_cap : start + (size_t)(f1 - f0) * fb, start }, f0, f1 - f0 });
         for (int i = f0; i < f1; i++) U.push_back(EncUnit{ (uint64_t)npx * (uint64_t)i, width, height, max_value, 2, k });
+        first.push_back(f1);
     }
-    if ((rc = encode_sharded(G, U))) return rc;
+    // (the cut is this function's own: frames [first[k], first[k + 1]) are group k, on the k-th listed device)
+    if ((rc = over_devices(first, [&](mic_hip_session *s, int f0, int f1) { return encode_groups(s, G, U, U[(size_t)f0].group, U[(size_t)f1 - 1].group + 1); }))) return rc;
     size_t written = 0;
     for (int k = 0; k < shards; k++) {
         if (G[(size_t)k].status != MIC_OK) return G[(size_t)k].status;
-        if (k && G[(size_t)k].written) memmove(out + header + written, out + G[(size_t)k].hdr, G[(size_t)k].written);
-        written += G[(size_t)k].written;
+        if (k && G[(size_t)k].dst.written) memmove(out + header + written, out + G[(size_t)k].dst.hdr, G[(size_t)k].dst.written);
+        written += G[(size_t)k].dst.written;
     }
-    G[0].written = written;
-    if (G[0].written > 0xFFFFFFFFull) return MIC_ERR_UNSUPPORTED;       // u32 offsets, multiframe.go:75-80
+    if (written > 0xFFFFFFFFull) return MIC_ERR_UNSUPPORTED;            // u32 offsets, multiframe.go:75-80
     memset(out, 0, 20);
     memcpy(out, "MIC2", 4);
     put_u32(out + 4, (uint32_t)width); put_u32(out + 8, (uint32_t)height); put_u32(out + 12, (uint32_t)nframes);
@@ -1132,7 +1075,7 @@ int mic_hip_mic2_compress(const uint16_t *frames, int width, int height, int nfr
         put_u32(out + 24 + (size_t)i * 8, (uint32_t)U[(size_t)i].len);
         off += U[(size_t)i].len;
     }
-    *out_len = header + G[0].written;
+    *out_len = header + written;
     return MIC_OK;
 } MIC_ABI_CATCH
 
@@ -1149,9 +1092,10 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
     const size_t data_off = 20 + (size_t)n * 8;
     if ((rc = ensure_device())) return rc;
     const int shards = cur_default() ? 1 : std::max(1, (int)std::min<size_t>(default_devices().size(), (size_t)n / 8));   // (frames decode into fixed places: any cut will do)
-    std::vector<DecGroup> G; std::vector<DecUnit> U;
+    std::vector<DecGroup> G; std::vector<DecUnit> U; std::vector<int> first(1, 0);
     for (int k = 0; k < shards; k++) {
-        const int f0 = (int)((int64_t)n * k / shards), f1 = (int)((int64_t)n * (k + 1) / shards);
+        const int f0 = first.back(), f1 = (int)((int64_t)n * (k + 1) / shards);
+        first.push_back(f1);
         G.push_back(DecGroup{ c, frames_out, f0, f1 - f0 });
         for (int i = f0; i < f1; i++) {
             const size_t start = data_off + get_u32(c + 20 + (size_t)i * 8), bl = get_u32(c + 24 + (size_t)i * 8);
@@ -1160,7 +1104,7 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
             U.push_back(DecUnit{ start, bl, (uint64_t)npx * (uint64_t)i, w, h, 0, k });
         }
     }
-    if ((rc = decode_sharded(G, U))) return rc;
+    if ((rc = over_devices(first, [&](mic_hip_session *s, int f0, int f1) { return decode_groups(s, G, U, U[(size_t)f0].group, U[(size_t)f1 - 1].group + 1); }))) return rc;
     for (const DecGroup &g : G) if (g.status != MIC_OK) return g.status;
     return MIC_OK;
 } MIC_ABI_CATCH

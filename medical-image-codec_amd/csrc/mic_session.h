@@ -387,5 +387,15 @@ void plan_shards(const uint64_t *w, int n, int shards, int *first);
 // work(0 .. n - 1) side by side, each on a thread of its own (work(0) on the calling thread); returns the code of the first
 // (lowest) k that failed.  An exception inside work(k) is that k's MIC_ERR_NOMEM / MIC_ERR_INTERNAL.
 int run_parallel(int n, const std::function<int(int)> &work);
+// THE fan-out of a host entry point over the devices of mic_hip_set_devices ("several devices"): shard k -- items
+// [first[k], first[k + 1]) -- runs work(s, i0, i1) on a thread of its own (run_parallel) with a session `s` leased from devs[k]; empty
+// shards are skipped, the lowest failing shard's code comes back.  ONE shard over all the items, on the default device or the session
+// the thread already holds, when `first` has two entries, the call is nested, or there are fewer devices than shards.
+// MIC_HIP_TRACE=1: a line per shard on stderr.  (MIC_LOCAL: for the library's own sources, not among its dynamic symbols.)
+#define MIC_LOCAL __attribute__((visibility("hidden")))
+using ShardWork = std::function<int(mic_hip_session *s, int i0, int i1)>;
+MIC_LOCAL int over_devices(const std::vector<int> &first, const ShardWork &work);
+// the same over items [0, n) cut by plan_shards: min(devices, n) shards, item i weighing weight(i)
+MIC_LOCAL int over_devices(int n, const std::function<uint64_t(int)> &weight, const ShardWork &work);
 #define kWorkspaceBudget (micapi::workspace_budget())
 }  // namespace micapi

@@ -996,20 +996,6 @@ int wv_levels_applied(int rows, int cols, int levels) {
 
 size_t wv_frames_per_batch(size_t n) { return std::max<size_t>(1, kWorkspaceBudget / (unit_ws_bytes(2 * n + 16) + 8 * n)); }
 
-// range(f0, f1, device) over frames [0, nframes) of rows x cols pixels: one call on the default device, or -- several devices listed,
-// the call not nested -- one contiguous shard per device (shard_plan), side by side; the first failing shard's code
-int wv_sharded(int nframes, size_t n, const std::function<int(size_t, size_t, int)> &range) {
-    const std::vector<int> devs = default_devices();
-    const int shards = cur_default() ? 1 : (int)std::min<size_t>(devs.size(), (size_t)nframes);
-    if (shards <= 1) return range(0, (size_t)nframes, -1);
-    std::vector<uint64_t> w((size_t)nframes, (uint64_t)n);
-    std::vector<int> first((size_t)shards + 1);
-    plan_shards(w.data(), nframes, shards, first.data());
-    return run_parallel(shards, [&](int k) {
-        return first[(size_t)k] < first[(size_t)k + 1] ? range((size_t)first[(size_t)k], (size_t)first[(size_t)k + 1], devs[(size_t)k]) : MIC_OK;
-    });
-}
-
 }  // namespace
 
 extern "C" {
@@ -1025,14 +1011,11 @@ int mic_hip_wavelet_v2_compress_batch(const uint16_t *frames, int nframes, int r
     const size_t n = (size_t)rows * (size_t)cols;
     if (out_stride < 11) return MIC_ERR_CAPACITY;
     const int applied = wv_levels_applied(rows, cols, levels);
-    return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session
-        DefaultLease lease;
-        int rc = lease.acquire(device);
-        if (rc) return rc;
-        mic_hip_session *s = cur_default();
+    return over_devices(nframes, [n](int) { return (uint64_t)n; }, [&](mic_hip_session *s, int fa, int fb) -> int {   // frames [fa, fb) on one session
+        int rc;
         const size_t per = wv_frames_per_batch(n);
-        for (size_t f0 = fa; f0 < fb; f0 += per) {
-            const int nf = (int)std::min(per, fb - f0);
+        for (size_t f0 = (size_t)fa; f0 < (size_t)fb; f0 += per) {
+            const int nf = (int)std::min(per, (size_t)fb - f0);
             if ((rc = s->ensure(nf, 2 * n + 16))) return rc;
             if ((rc = s->io_px.reserve(n * 2 * (size_t)nf + 64))) return rc;
             HIP_TRY(hipMemcpyAsync(s->io_px.p, frames + f0 * n, n * 2 * (size_t)nf, hipMemcpyHostToDevice, s->stream));
@@ -1093,14 +1076,11 @@ int wv_decompress_files(const uint8_t *const *files, const size_t *lens, int nfr
     const WvDims dm = wv_dims(rows, cols, levels);
     const size_t P = (size_t)dm.nr[level] * (size_t)dm.nc[level];          // pixels of a frame's output (n at level 0)
     if (P * (size_t)nframes > out_cap_px) return MIC_ERR_CAPACITY;
-    return wv_sharded(nframes, n, [&](size_t fa, size_t fb, int device) -> int {   // frames [fa, fb) on one session; shape: files[0]'s
-        DefaultLease lease;
-        int rc = lease.acquire(device);
-        if (rc) return rc;
-        mic_hip_session *s = cur_default();
+    return over_devices(nframes, [n](int) { return (uint64_t)n; }, [&](mic_hip_session *s, int fa, int fb) -> int {   // frames [fa, fb) on one session; shape: files[0]'s
+        int rc;
         const size_t per = wv_frames_per_batch(n);
-        for (size_t f0 = fa; f0 < fb; f0 += per) {
-            const int nf = (int)std::min(per, fb - f0);
+        for (size_t f0 = (size_t)fa; f0 < (size_t)fb; f0 += per) {
+            const int nf = (int)std::min(per, (size_t)fb - f0);
             std::vector<int> slot((size_t)nf, -1); std::vector<uint64_t> offs(1, 0); int good = 0;   // streams packed back to back
             for (int i = 0; i < nf; i++) {
                 const uint8_t *c = files[f0 + (size_t)i]; const size_t len = lens[f0 + (size_t)i];

@@ -1,9 +1,16 @@
 """The several-devices path of the C ABI (mic_hip_set_devices): the batch entry points cut their jobs into one contiguous shard per
-listed device and run the shards side by side, each on a session of its device's pool (csrc/mic_host_io.hip: run_shards).  The test box
+listed device and run the shards side by side, each on a session of its device's pool (csrc/mic_host_io.hip: over_devices).  The test box
 has one GPU, so the lists here are {0}, {0, 0} and {0, 0, 0}: the same code path with two and three pools' worth of sessions on one
 device.  Every result is compared with the oracle; reference fan-outs: parallelstrips.go:77-93, multiframecompress.go:186-209."""
+import os
+import re
+import subprocess
+import sys
+
 import numpy as np
 import pytest
+
+from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -80,6 +87,39 @@ def test_mic2_frames_are_sharded_and_moved_into_place(mic, mico, synth, device_l
         assert got == want, devs
         back = mic.decompress_multi_frame(want)
         assert np.array_equal(back.reshape(frames.shape), frames), devs
+
+
+_MIC2_CHILD = r'''
+import sys, numpy as np
+sys.path.insert(0, %r)
+import __graft_entry__ as e
+mic = e.load_package()
+import importlib
+synth = importlib.import_module("medical_image_codec_amd.synth")
+from oracle import mico
+frames = np.stack([synth.xr_like(cols=160, rows=120, depth=12, seed=500 + i, noise=3.0 + i) for i in range(26)])
+rc, want = mico.mic2_compress(frames, 4095)
+assert rc == 0
+mic.set_devices([0, 0, 0])
+sys.stderr.write("== compress\n"); sys.stderr.flush()
+assert mic.compress_multi_frame(frames, 160, 120, 4095) == want
+sys.stderr.write("== decompress\n"); sys.stderr.flush()
+assert np.array_equal(mic.decompress_multi_frame(want).reshape(frames.shape), frames)
+print("ok")
+''' % ROOT
+
+
+def test_mic2_shards_keep_their_own_frame_cut(gpu_ready):
+    """26 frames over three listed devices are the groups of 8, 9 and 9 frames that mic_hip_mic2_compress / _decompress cut
+    (n k / shards), and each must run as a shard of its own.  Planning those groups a second time by weight leaves the third
+    shard empty (tests/test_shard_plan.py: the cut [0, 2, 3, 3]) without changing a byte, so the bytes cannot show it: a child
+    process (the environment is read once) with MIC_HIP_TRACE=1 names every shard of both calls on stderr."""
+    r = subprocess.run([sys.executable, "-c", _MIC2_CHILD], env=dict(os.environ, MIC_HIP_TRACE="1"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    _, enc, dec = re.split(r"== (?:de)?compress\n", r.stderr)
+    for what, log in (("compress", enc), ("decompress", dec)):
+        shards = re.findall(r"\[mic_hip devices\] shard (\d+) of (\d+) on device (\d+): items (\d+) \.\. (\d+)", log)
+        assert sorted(tuple(int(x) for x in m) for m in shards) == [(1, 3, 0, 0, 7), (2, 3, 0, 8, 16), (3, 3, 0, 17, 25)], (what, log[-2000:])
 
 
 def test_the_failing_strip_is_named(mic, mico, synth, gpu_ready):

@@ -1,5 +1,5 @@
 """MIC3 slides and WaveletV2 batches over the devices of mic_hip_set_devices (csrc/mic_api_ext.hip: wsi_compress_bands, decode_box;
-csrc/mic_wavelet.hip: wv_sharded).  A slide is cut into one band of tile rows per device (mic_hip_wsi_band_plan); each band codes
+csrc/mic_host_io.hip: over_devices).  A slide is cut into one band of tile rows per device (mic_hip_wsi_band_plan); each band codes
 levels 0..K as a slide of its own, devices[0] codes the top of the pyramid from the bands' gathered rows.  The file must be the
 one-device file byte for byte, whatever the list.  The test box has one GPU, so the lists are {0}, {0, 0} and {0, 0, 0}: the same
 code path with two and three shards on one device.  Reference fan-out: wsicompress.go:126-145."""

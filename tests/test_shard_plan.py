@@ -42,3 +42,16 @@ def test_zero_weights_and_bad_arguments(mic):
     import pytest
     with pytest.raises(mic.MicError):
         mic.shard_plan([1, 2], 0)
+
+
+def test_groups_cut_by_frame_count_do_not_survive_a_second_plan(mic):
+    """mic_hip_mic2_compress / _decompress cut n frames into the groups [n k / shards, n (k + 1) / shards): 26 frames on three
+    devices are 8, 9 and 9.  Planned again by weight, the goals are 26 npx k / 3 = 8.67 npx and 17.33 npx: the first group's 8 npx
+    is below the first, so shard 0 takes the second group too; 17 npx is below the second, so shard 1 takes the third -- two shards
+    of 17 and 9 frames and an idle third device, where the groups were made for three.  17 frames on two devices (8 and 9, goal
+    8.5 npx) end on one.  So MIC2 hands its own cut to the fan-out (micapi::over_devices, the explicit form) and does not go
+    through this plan; tests/test_gpu_multi_device.py checks the shards that run."""
+    npx = 160 * 120
+    assert mic.shard_plan([8 * npx, 9 * npx, 9 * npx], 3) == [0, 2, 3, 3]
+    assert mic.shard_plan([8 * npx, 9 * npx], 2) == [0, 2, 2]
+    assert mic.shard_plan([npx] * 26, 3) == [0, 9, 18, 26]                   # (frames planned one by one: no such collapse)
