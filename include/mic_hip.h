@@ -402,6 +402,32 @@ int mic_hip_wsi_decompress_region(const uint8_t *compressed, size_t compressed_l
                                   int x, int y, int w, int h,
                                   uint8_t *rgb_out, size_t out_cap, int *out_w, int *out_h);
 
+/* Many patches per call, into a tensor that already lives on the device (no reference counterpart; beside
+ * mic_hip_wsi_decompress_region, which serves one rectangle through the host).  Patch i is the rectangle [xy[2i], xy[2i] + pw) x
+ * [xy[2i + 1], xy[2i + 1] + ph) of pyramid level `level`; coordinates may be negative and the rectangle may overhang the level:
+ * pixels outside the level are 0 (_decompress_region clamps instead; a batch needs one shape).  The union of the tiles the
+ * patches touch is decoded, each tile once, in slabs of the unit codec's sub-batch size, and a kernel writes each patch-tile
+ * overlap (a "piece") from the decoded planes straight into d_out: n x ph x pw x channels samples, patch-major, row-major,
+ * interleaved, in the slide's sample format (u8 RGB; u8 or little-endian u16 greyscale), n * ph * pw * bytes-per-pixel bytes, every
+ * one of them written.  d_out is memory the device can write: a device allocation on the call's device or pinned host memory
+ * (mic_hip_host_alloc); anything else is MIC_ERR_ARGS, found with hipPointerGetAttributes before anything is launched.
+ * status[i] (host, may be NULL): MIC_OK, or the first non-OK status among patch i's tiles in tile-index order -- the code
+ * mic_hip_wsi_decompress_tile returns for that tile; such a patch's pixels are unspecified, every other patch is exact.
+ * Returns MIC_OK when the call ran, even if patches failed; n == 0 is MIC_OK; MIC_ERR_ARGS for level, pw, ph <= 0 or n < 0,
+ * MIC_ERR_CAPACITY for out_cap below the tensor's size, MIC_ERR_UNSUPPORTED / MIC_ERR_CORRUPT for the header (a tile index entry
+ * that points outside the file counts as the header's).  One device: the calling thread's default session (the file and reader
+ * forms) or the given session; no fan-out over mic_hip_set_devices, the output being one device tensor.
+ * stats (may be NULL): tiles decoded (the union's size), pieces gathered, slabs (decode chains) the call ran. */
+typedef struct { uint64_t tiles_decoded, pieces, slabs; } mic_hip_patch_stats;
+/* The host planner of those calls, beside mic_hip_shard_plan and mic_hip_wsi_band_plan: the tiles (ty * tiles_x + tx of a level of
+ * level_w x level_h pixels; tile sizes 0 = 256) the patches touch, ascending, each once, into tiles[cap]; *ntiles their number,
+ * *npieces the number of patch-tile overlaps with non-empty area (both may be NULL).  More than cap tiles: MIC_ERR_CAPACITY with
+ * the counts set and tiles untouched.  Needs no device. */
+int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, const int32_t *xy, int n, int pw, int ph,
+                           uint64_t *tiles, size_t cap, uint64_t *ntiles, uint64_t *npieces);
+int mic_hip_wsi_read_patches(const uint8_t *compressed, size_t compressed_len, int level, const int32_t *xy, int n, int pw, int ph,
+                             void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
+
 /* ---- MIC3 streaming: a row-push writer and a random-access reader ------------------------------- */
 /* For slides too large for one host buffer (the reference's "WSI streaming API" roadmap item, io.ReaderAt / io.WriteSeeker).
  * pwrite-like sink: write len bytes at an absolute offset, 0 = success.  The ranges of one file never overlap.
@@ -444,6 +470,10 @@ int mic_hip_wsi_reader_decompress_tile(mic_hip_wsi_reader *r, int level, int til
                                        uint8_t *out, size_t out_cap, int *out_w, int *out_h);
 int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x, int y, int w, int h,
                                          uint8_t *out, size_t out_cap, int *out_w, int *out_h);
+/* mic_hip_wsi_read_patches through the reader (beside _reader_decompress_region): the blobs of the union's tiles are pulled in one
+ * pass, each once, contiguous ones in one read; nothing else of the file is read. */
+int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r);
 
 /* ---- single-frame RGB and the CLI's single-frame files ------------------------------------------ */
@@ -553,6 +583,11 @@ int mic_hip_session_wsi_write(mic_hip_session *s, uint8_t *out, size_t out_cap, 
 int mic_hip_session_wsi_payload(mic_hip_session *s, const uint8_t **d_payload, uint64_t *payload_bytes, uint64_t *tile_lens, size_t cap);
 int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_pixels_out, size_t out_cap);
 int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int *heights, int cap);
+/* mic_hip_wsi_read_patches from the slide mic_hip_session_wsi_encode left in the session (beside _decode_level): the compressed
+ * slide stays in HBM, the plane records are used as they stand -- a training loop's sampler.  d_out on the session's device. */
+int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
+
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);
 /* Per-kernel device time (ms, HIP events on the session stream) of the last enqueue:

@@ -106,6 +106,11 @@ class PicaDecJob(C.Structure):
                 ("failed_strip", C.c_int32)]
 
 
+class PatchStats(C.Structure):
+    """mic_hip_patch_stats"""
+    _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
+
+
 class Unit(C.Structure):
     _fields_ = [("px_offset", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
@@ -130,6 +135,7 @@ ABI_SYMBOLS = [
     "mic_hip_mic1_compress", "mic_hip_mic1_info", "mic_hip_mic1_decompress",
     "mic_hip_wsi_compress", "mic_hip_wsi_compress_ex", "mic_hip_wsi_format", "mic_hip_wsi_info", "mic_hip_wsi_level_info",
     "mic_hip_wsi_decompress_tile", "mic_hip_wsi_decompress_level", "mic_hip_wsi_decompress_region",
+    "mic_hip_wsi_patch_plan", "mic_hip_wsi_read_patches", "mic_hip_wsi_reader_read_patches", "mic_hip_session_wsi_read_patches",
     "mic_hip_wsi_writer_open", "mic_hip_wsi_writer_push_rows", "mic_hip_wsi_writer_finish", "mic_hip_wsi_writer_device_bytes",
     "mic_hip_wsi_writer_stats", "mic_hip_wsi_writer_close",
     "mic_hip_wsi_reader_open", "mic_hip_wsi_reader_info", "mic_hip_wsi_reader_decompress_tile", "mic_hip_wsi_reader_decompress_region",
@@ -239,6 +245,12 @@ def lib() -> C.CDLL:
     L.mic_hip_wsi_reader_decompress_region.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t,
                                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mic_hip_wsi_reader_close.argtypes = [C.c_void_p]
+    _patch_args = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(PatchStats)]
+    L.mic_hip_wsi_patch_plan.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mic_hip_wsi_read_patches.argtypes = [C.c_void_p, C.c_size_t] + _patch_args
+    L.mic_hip_wsi_reader_read_patches.argtypes = [C.c_void_p] + _patch_args
+    L.mic_hip_session_wsi_read_patches.argtypes = [C.c_void_p] + _patch_args
     L.mic_hip_wsi_reader_close.restype = None
     L.mic_hip_session_destroy.restype = None
     L.mic_hip_compress_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int,
@@ -862,6 +874,53 @@ def decompress_wsi_level(compressed, level: int = 0) -> np.ndarray:
     return _wsi_shape(hdr, out, lv["width"], lv["height"])
 
 
+def _patch_xy(xy) -> np.ndarray:
+    """(n, 2) patch origins (x, y) as the int32 pairs the C calls take"""
+    a = np.ascontiguousarray(np.asarray(xy, dtype=np.int64).reshape(-1, 2).astype(np.int32))
+    return a
+
+
+def wsi_patch_plan(level_w: int, level_h: int, tile_w: int, tile_h: int, xy, pw: int, ph: int, cap: Optional[int] = None
+                   ) -> Tuple[np.ndarray, int]:
+    """mic_hip_wsi_patch_plan: (tiles the patches touch -- ty * tiles_x + tx, ascending, each once --, number of patch-tile
+    pieces).  Needs no device.  cap: room for that many tiles (default: as many as it takes); too few raises MicError
+    (MIC_ERR_CAPACITY) whose ``ntiles`` attribute is the count."""
+    a = _patch_xy(xy)
+    nt, npc = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        rc = lib().mic_hip_wsi_patch_plan(level_w, level_h, tile_w, tile_h, a.ctypes.data, len(a), pw, ph, None, 0, C.byref(nt), C.byref(npc))
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "wsi_patch_plan")
+        cap = nt.value
+    tiles = np.zeros(max(cap, 1), dtype=np.uint64)
+    rc = lib().mic_hip_wsi_patch_plan(level_w, level_h, tile_w, tile_h, a.ctypes.data, len(a), pw, ph, tiles.ctypes.data, cap, C.byref(nt), C.byref(npc))
+    if rc:
+        e = MicError(rc, "wsi_patch_plan")
+        e.ntiles = nt.value
+        raise e
+    return tiles[: nt.value].copy(), npc.value
+
+
+def _read_patches(where: str, call, xy, d_out: int, out_cap: int):
+    a = _patch_xy(xy)
+    st = np.zeros(len(a), dtype=np.int32)
+    ps = PatchStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, C.byref(ps))
+    return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs)
+
+
+def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+    """mic_hip_wsi_read_patches: the pw x ph patches at the (x, y) origins `xy` of one level, into the caller's device tensor
+    d_out (an int: ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit
+    greyscale) of out_cap bytes.  Pixels outside the level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs))."""
+    c = _bytes_arr(compressed)
+    rc, st, stats = _read_patches("wsi_read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_wsi_read_patches(
+        c.ctypes.data, c.size, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
+    if rc:
+        _raise(rc, "wsi_read_patches")
+    return st, stats
+
+
 class _Callback:
     """A ctypes callback that never lets an exception pass as success: the first exception it meets is kept, the callback
     returns non-zero (the library then reports MIC_ERR_IO), and the caller re-raises it once the C call has returned.
@@ -1006,6 +1065,13 @@ class WsiReader:
         self._cb.check(lib().mic_hip_wsi_reader_decompress_region(self._h, level, x, y, w, h, out.ctypes.data, out.size,
                                                                   C.byref(ow), C.byref(oh)), "WsiReader.region")
         return _wsi_shape(self.info, out, ow.value, oh.value)
+
+    def read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+        """as wsi_read_patches on the whole file; only the blobs of the tiles the patches touch are read, each once"""
+        rc, st, stats = _read_patches("WsiReader.read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_wsi_reader_read_patches(
+            self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
+        self._cb.check(rc, "WsiReader.read_patches")
+        return st, stats
 
     def close(self) -> None:
         if self._h:
@@ -1351,3 +1417,11 @@ class Session:
         rc = lib().mic_hip_session_wsi_decode_level(self._h, level, d_pixels_out, out_cap)
         if rc:
             _raise(rc, "session_wsi_decode_level")
+
+    def wsi_read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+        """wsi_read_patches from the slide wsi_encode left in the session (it stays in HBM); d_out on the session's device"""
+        rc, st, stats = _read_patches("session_wsi_read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_session_wsi_read_patches(
+            self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
+        if rc:
+            _raise(rc, "session_wsi_read_patches")
+        return st, stats

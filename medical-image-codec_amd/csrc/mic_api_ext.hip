@@ -139,6 +139,56 @@ __global__ void __launch_bounds__(256) k_wsi_plane_to_grey(const uint16_t *plane
     }
 }
 
+// ---- patches: many rectangles of one level, gathered from the decoded planes into an n x ph x pw x C tensor -----------------------
+// A piece is one patch-tile overlap: w x h pixels from (sx, sy) of the tile in slab slot `slot` to (dx, dy) of patch `patch`.
+// The host plans them (plan_patches): the kernels divide nothing.
+struct PatchPiece { int32_t patch, slot, sx, sy, dx, dy, w, h; };
+
+// Lanes run along x of a piece row.  A piece narrower than a wave puts 64 / lw of its rows side by side in one (lw: the power of
+// two >= w, at most 64), so a 17-pixel overlap keeps 32 + 17 lanes of 64 busy instead of 17.  grid = (pieces, row chunks).
+struct PieceLanes { int col, lw, row, rstep; };
+__device__ __forceinline__ PieceLanes piece_lanes(int w) {
+    const int sh = min(6, 32 - __clz(w - 1));                                       // (w >= 1; __clz(0) = 32: one lane per row)
+    return PieceLanes{ (int)threadIdx.x & ((1 << sh) - 1), 1 << sh, (int)(threadIdx.x >> sh) + (int)blockIdx.y * (256 >> sh), (256 >> sh) * (int)gridDim.y };
+}
+
+// YCoCgRInverse (asm_amd64.go:106-121) of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at
+// whatever byte offset the patch row has.  planes: [slot][3][tw * th] u16; out: [patch][ph][pw][3] u8.
+__global__ void __launch_bounds__(256) k_wsi_gather_patches(const uint16_t *planes, int tw, int th, const PatchPiece *pieces,
+                                                          uint8_t *out, int pw, int ph) {
+    const PatchPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const size_t npx = (size_t)tw * th;
+    const mic_gp<const uint16_t> py = mic_g(planes + (size_t)pc.slot * 3 * npx + (size_t)pc.sy * tw + pc.sx), pco = py + npx, pcg = pco + npx;
+    const mic_gp<uint8_t> o = mic_g(out + (((size_t)pc.patch * ph + pc.dy) * pw + pc.dx) * 3);
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const size_t si = (size_t)y * tw, di = (size_t)y * pw * 3;
+        for (int x = ln.col; x < pc.w; x += ln.lw) {
+            const int yv = py[si + x];
+            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
+            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, :113-116
+            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
+            const int t = yv - (cg >> 1);
+            const int g = cg + t;
+            const int b = t - (co >> 1);
+            const int r = co + b;
+            const size_t d = di + (size_t)x * 3;
+            o[d] = (uint8_t)r; o[d + 1] = (uint8_t)g; o[d + 2] = (uint8_t)b;
+        }
+    }
+}
+// uint16ToBytes (wsicompress.go:589-603) of the piece's samples.  planes: [slot][tw * th] u16; out: [patch][ph][pw] T.
+template <typename T>
+__global__ void __launch_bounds__(256) k_wsi_gather_patches_grey(const uint16_t *planes, int tw, int th, const PatchPiece *pieces,
+                                                               T *out, int pw, int ph) {
+    const PatchPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const mic_gp<const uint16_t> src = mic_g(planes + (size_t)pc.slot * tw * th + (size_t)pc.sy * tw + pc.sx);
+    const mic_gp<T> o = mic_g(out + ((size_t)pc.patch * ph + pc.dy) * pw + pc.dx);
+    for (int y = ln.row; y < pc.h; y += ln.rstep)
+        for (int x = ln.col; x < pc.w; x += ln.lw) o[(size_t)y * pw + x] = (T)src[(size_t)y * tw + x];
+}
+
 // constant planes of a slab in one launch: grid = (chunks, planes); fill[k] = {plane index, value}
 __global__ void __launch_bounds__(256) k_fill_planes(uint16_t *planes, size_t npx, const uint2 *fill) {
     const uint2 f = fill[blockIdx.y];
@@ -239,6 +289,18 @@ void launch_planes_to_pixels(hipStream_t st, const Mic3 &m, const uint16_t *plan
     else
         hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint8_t *)dst, dst_w);
 }
+// np pieces (device) of the planes of a slab's tiles -> out, the patch tensor (pw x ph pixels a patch).  A block walks its piece in
+// passes of 256 pixels; grid y cuts the rows of large tiles so that a 256 x 256 overlap is not one block's 256 passes.
+void launch_gather_patches(hipStream_t st, const Mic3 &m, const uint16_t *planes, const PatchPiece *pieces, size_t np, void *out, int pw, int ph) {
+    const size_t npx = (size_t)m.tw * m.th;
+    const dim3 grid((unsigned)np, (unsigned)std::min<size_t>(8, std::max<size_t>(1, npx / 16384))), block(256);
+    if (m.planes() == 3)
+        hipLaunchKernelGGL(k_wsi_gather_patches, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint8_t *)out, pw, ph);
+    else if (m.bps == 16)
+        hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint16_t>, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint16_t *)out, pw, ph);
+    else
+        hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint8_t *)out, pw, ph);
+}
 // one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
 void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
     if (fmt.planes() == 3)
@@ -333,25 +395,28 @@ void put_mic3_index(uint8_t *out, const Mic3 &fmt, const std::vector<Level> &lv,
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------------
-// decompressTileBlob (wsicompress.go:424-527) for nt tiles from their plane records (bytes at base + off on the device): constant
-// planes filled, streams through the unit codec, raw planes copied; then YCoCg-R inverse / uint16ToBytes + crop into dst (dst_w
-// pixels across), tile k at place[k] (host).  planes holds the nt * P planes, aux the place rectangles and the fill list.
-int decode_planes(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, const int4 *place,
-                  DevBuf &planes, DevBuf &aux, void *dst, int dst_w) {
+// decompressTileBlob (wsicompress.go:424-527) for nt tiles from their plane records (bytes at base + off on the device), up to the
+// planes: constant planes filled, streams through the unit codec, raw planes copied into `planes` ([nt][P][tw * th] u16).  aux
+// keeps `front` bytes at its start for the caller (the place rectangles, the patch pieces: to be uploaded after this call, which
+// may move aux) and holds the fill list behind them.  plane_status = NULL: the first unit that fails ends the call with its status;
+// else plane_status[q] (nt * P entries) receives every plane's status and the call goes on.  The planes are complete on the
+// session's stream on return (the host has waited for the stream: the fill list is this call's own).
+int decode_plane_data(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, DevBuf &planes, DevBuf &aux,
+                      size_t front, int32_t *plane_status) {
     const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
     int rc;
     if ((rc = planes.reserve(nt * P * npx * 2 + 64))) return rc;
     uint16_t *dp = (uint16_t *)planes.p;
-    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<uint2> fills;
+    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<uint2> fills; std::vector<size_t> unit_plane;
     for (size_t q = 0; q < nt * P; q++) {
         const WsiPlane &wp = pl[q];
+        if (plane_status) plane_status[q] = MIC_OK;
         if (wp.mode <= 1) fills.push_back(make_uint2((uint32_t)q, wp.mode ? wp.value : 0u));
-        else if (wp.mode == 2) { units.push_back(mic_hip_unit{ q * npx, m.tw, m.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); }
+        else if (wp.mode == 2) { units.push_back(mic_hip_unit{ q * npx, m.tw, m.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); unit_plane.push_back(q); }
         else HIP_TRY(hipMemcpyAsync(dp + q * npx, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
     }
-    if ((rc = aux.reserve(fills.size() * sizeof(uint2) + nt * sizeof(int4) + 64))) return rc;
-    int4 *d_place = (int4 *)aux.p; uint2 *d_fill = (uint2 *)((char *)aux.p + nt * sizeof(int4));
-    HIP_TRY(hipMemcpyAsync(d_place, place, nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
+    if ((rc = aux.reserve(fills.size() * sizeof(uint2) + front + 64))) return rc;
+    uint2 *d_fill = (uint2 *)((char *)aux.p + front);
     if (!fills.empty()) {
         HIP_TRY(hipMemcpyAsync(d_fill, fills.data(), fills.size() * sizeof(uint2), hipMemcpyHostToDevice, s->stream));
         s->timer.reset(s->stream); s->timer.mark("k_fill_planes");
@@ -362,20 +427,57 @@ int decode_planes(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const 
         if ((rc = session_decode_enqueue_spans(s, base, begins.data(), ends.data(), units.data(), (int)units.size(), dp))) return rc;
         std::vector<int32_t> st(units.size());
         if ((rc = session_decode_finish(s, st.data()))) return rc;
-        for (int32_t v : st) if (v != MIC_OK) return v;
-    }
+        if (plane_status) for (size_t u = 0; u < st.size(); u++) plane_status[unit_plane[u]] = st[u];
+        else for (int32_t v : st) if (v != MIC_OK) return v;
+    } else if (!fills.empty()) HIP_TRY(hipStreamSynchronize(s->stream));                  // (session_decode_finish waits otherwise)
+    return MIC_OK;
+}
+
+// ... then YCoCg-R inverse / uint16ToBytes + crop into dst (dst_w pixels across), tile k at place[k] (host).  planes holds the
+// nt * P planes, aux the place rectangles and the fill list.
+int decode_planes(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, const int4 *place,
+                  DevBuf &planes, DevBuf &aux, void *dst, int dst_w) {
+    int rc;
+    if ((rc = decode_plane_data(s, m, base, pl, nt, planes, aux, nt * sizeof(int4), nullptr))) return rc;
+    int4 *d_place = (int4 *)aux.p;
+    HIP_TRY(hipMemcpyAsync(d_place, place, nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
     s->timer.reset(s->stream); s->timer.mark("k_wsi_planes_to_pixels");
-    launch_planes_to_pixels(s->stream, m, dp, d_place, nt, dst, dst_w);
+    launch_planes_to_pixels(s->stream, m, (const uint16_t *)planes.p, d_place, nt, dst, dst_w);
     s->timer.mark("end");
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIC_OK;
 }
 
+struct TileBlob { const uint8_t *p; size_t len; };
+// one tile blob checked on the host (decompressTileBlob, wsicompress.go:424-527): its P plane records are appended to pl, the bytes
+// of its streams and raw planes to `bytes` (the records' off: into it).  A blob that fails leaves fewer than P records behind.
+int parse_tile_blob(const Mic3 &m, const uint8_t *blob, size_t bl, std::vector<WsiPlane> &pl, std::vector<uint8_t> &bytes) {
+    const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
+    size_t pl_off[3] = { 0, 0, 0 }, pl_len[3] = { (size_t)bl, 0, 0 };                      // greyscale: the blob is the plane, :477-484
+    if (P == 3) {
+        if (bl < 12) return MIC_ERR_CORRUPT;
+        const size_t l0 = get_u32(blob), l1 = get_u32(blob + 4), l2 = get_u32(blob + 8);
+        if (12 + l0 + l1 + l2 > bl) return MIC_ERR_CORRUPT;                                // wsicompress.go:440-442
+        pl_off[0] = 12; pl_off[1] = 12 + l0; pl_off[2] = 12 + l0 + l1; pl_len[0] = l0; pl_len[1] = l1; pl_len[2] = l2;
+    }
+    for (size_t p = 0; p < P; p++) {                                                       // decompressWSIPlane, :487-527
+        const uint8_t *d = blob + pl_off[p]; const size_t dl = pl_len[p];
+        if (dl == 0) return MIC_ERR_CORRUPT;
+        WsiPlane wp{ d[0], 0, bytes.size(), 0 };
+        if (d[0] == 0) { }
+        else if (d[0] == 1) { if (dl < 3) return MIC_ERR_CORRUPT; wp.value = (uint16_t)(d[1] | (d[2] << 8)); }
+        else if (d[0] == 2) wp.len = dl - 1;
+        else if (d[0] == 3) { if (dl < 1 + 2 * npx) return MIC_ERR_CORRUPT; wp.len = 2 * npx; }
+        else return MIC_ERR_CORRUPT;
+        if (wp.mode >= 2) bytes.insert(bytes.end(), d + 1, d + 1 + wp.len);
+        pl.push_back(wp);
+    }
+    return MIC_OK;
+}
 // decode the given tiles (global indices) of one level into dst (an image of dst_w x dst_h pixels of the slide's format);
 // place[k] = where tile k goes and how much of it is kept.  Slab by slab: the blobs are checked on the host, their planes' bytes
 // go up in one copy, decode_planes does the rest.
-struct TileBlob { const uint8_t *p; size_t len; };
 int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::vector<int4> &place,
                  uint8_t *rgb_out, int dst_w, int dst_h) {
     if (!m.supported()) return MIC_ERR_UNSUPPORTED;
@@ -393,28 +495,7 @@ int decode_blobs(const Mic3 &m, const std::vector<TileBlob> &tiles, const std::v
     for (size_t t0 = 0; t0 < ntile && rc == MIC_OK; t0 += per) {
         const size_t nt = std::min(per, ntile - t0);
         pl.clear(); bytes.clear();
-        for (size_t k = 0; k < nt && rc == MIC_OK; k++) {
-            const uint8_t *blob = tiles[t0 + k].p; const size_t bl = tiles[t0 + k].len;
-            size_t pl_off[3] = { 0, 0, 0 }, pl_len[3] = { (size_t)bl, 0, 0 };              // greyscale: the blob is the plane, :477-484
-            if (P == 3) {
-                if (bl < 12) { rc = MIC_ERR_CORRUPT; break; }
-                const size_t l0 = get_u32(blob), l1 = get_u32(blob + 4), l2 = get_u32(blob + 8);
-                if (12 + l0 + l1 + l2 > bl) { rc = MIC_ERR_CORRUPT; break; }               // wsicompress.go:440-442
-                pl_off[0] = 12; pl_off[1] = 12 + l0; pl_off[2] = 12 + l0 + l1; pl_len[0] = l0; pl_len[1] = l1; pl_len[2] = l2;
-            }
-            for (size_t p = 0; p < P; p++) {                                               // decompressWSIPlane, :487-527
-                const uint8_t *d = blob + pl_off[p]; const size_t dl = pl_len[p];
-                if (dl == 0) { rc = MIC_ERR_CORRUPT; break; }
-                WsiPlane wp{ d[0], 0, bytes.size(), 0 };
-                if (d[0] == 0) { }
-                else if (d[0] == 1) { if (dl < 3) { rc = MIC_ERR_CORRUPT; break; } wp.value = (uint16_t)(d[1] | (d[2] << 8)); }
-                else if (d[0] == 2) wp.len = dl - 1;
-                else if (d[0] == 3) { if (dl < 1 + 2 * npx) { rc = MIC_ERR_CORRUPT; break; } wp.len = 2 * npx; }
-                else { rc = MIC_ERR_CORRUPT; break; }
-                if (wp.mode >= 2) bytes.insert(bytes.end(), d + 1, d + 1 + wp.len);
-                pl.push_back(wp);
-            }
-        }
+        for (size_t k = 0; k < nt && rc == MIC_OK; k++) rc = parse_tile_blob(m, tiles[t0 + k].p, tiles[t0 + k].len, pl, bytes);
         if (rc) break;
         if ((rc = s->ensure(1, npx)) || (rc = s->io_comp.reserve(bytes.size() + 64))) break;
         if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
@@ -724,6 +805,149 @@ int wsi_region(const BlobSource &src, const Mic3 &m, int level, int x, int y, in
     if (out_h) *out_h = h;
     return MIC_OK;
 }
+
+// ---- patches -----------------------------------------------------------------------------------------------------------------
+// The tiles n patches of pw x ph pixels touch in a level of level_w x level_h pixels (tiles of tw x th), and their pieces.
+// Patch i is [xy[2i], xy[2i] + pw) x [xy[2i + 1], xy[2i + 1] + ph); what lies outside the level has no piece.  tiles: ty * tiles_x +
+// tx, ascending, each once.  pieces: sorted by tile, then by patch; slot = the tile's index in `tiles`.  first[u] .. first[u + 1]:
+// the pieces of tiles[u].
+struct PatchPlan { std::vector<uint64_t> tiles; std::vector<PatchPiece> pieces; std::vector<size_t> first; };
+int plan_patches(int level_w, int level_h, int tw, int th, const int32_t *xy, int n, int pw, int ph, PatchPlan &plan) {
+    const int64_t tiles_x = ((int64_t)level_w + tw - 1) / tw;
+    std::vector<std::pair<uint64_t, PatchPiece>> all;
+    for (int i = 0; i < n; i++) {
+        const int64_t px = xy[2 * i], py = xy[2 * i + 1];
+        const int64_t x0 = std::max<int64_t>(px, 0), x1 = std::min<int64_t>(px + pw, level_w);
+        const int64_t y0 = std::max<int64_t>(py, 0), y1 = std::min<int64_t>(py + ph, level_h);
+        if (x0 >= x1 || y0 >= y1) continue;
+        for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
+            const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
+            all.emplace_back((uint64_t)(ty * tiles_x + tx), PatchPiece{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py),
+                                                                         (int32_t)(bx - ax), (int32_t)(by - ay) });
+        }
+    }
+    if (all.size() > 0x7FFFFFFFu) return MIC_ERR_UNSUPPORTED;                              // (pieces are a launch's grid x)
+    std::stable_sort(all.begin(), all.end(), [](const std::pair<uint64_t, PatchPiece> &a, const std::pair<uint64_t, PatchPiece> &b) { return a.first < b.first; });
+    plan.tiles.clear(); plan.pieces.clear(); plan.first.clear();
+    plan.pieces.reserve(all.size());
+    for (const auto &tp : all) {
+        if (plan.tiles.empty() || plan.tiles.back() != tp.first) { plan.tiles.push_back(tp.first); plan.first.push_back(plan.pieces.size()); }
+        plan.pieces.push_back(tp.second);
+        plan.pieces.back().slot = (int32_t)(plan.tiles.size() - 1);
+    }
+    plan.first.push_back(plan.pieces.size());
+    return MIC_OK;
+}
+
+// What the three patch entry points check of their arguments before a device is touched; *need = bytes of the patch tensor.
+int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, size_t out_cap, size_t *need) {
+    if (level < 0 || level >= m.nlev || pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xy)) return MIC_ERR_ARGS;
+    if (!m.supported()) return MIC_ERR_UNSUPPORTED;
+    const Level &L = m.lv[(size_t)level];
+    if (L.w <= 0 || L.h <= 0 || m.tw <= 0 || m.th <= 0) return MIC_ERR_CORRUPT;
+    if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
+    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ph * (unsigned)pw * m.bpp();
+    if (bytes > out_cap) return MIC_ERR_CAPACITY;
+    *need = (size_t)bytes;
+    return MIC_OK;
+}
+
+// d_out must be memory the session's device can write `need` bytes of: an allocation of that device, or pinned host memory
+// (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched; *d_out becomes the
+// address the device uses.
+int patch_pointer(const mic_hip_session *s, void **d_out, size_t need) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, *d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }   // (unregistered memory)
+    if (at.type == hipMemoryTypeDevice) {
+        if (at.device != s->device) return MIC_ERR_ARGS;
+        hipDeviceptr_t b = nullptr; size_t sz = 0;
+        if (hipMemGetAddressRange(&b, &sz, (hipDeviceptr_t)*d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }
+        if ((size_t)((char *)*d_out - (char *)b) + need > sz) return MIC_ERR_CAPACITY;     // (the allocation ends before out_cap does)
+    } else if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) {
+        if (at.devicePointer) *d_out = at.devicePointer;
+    } else return MIC_ERR_ARGS;
+    return MIC_OK;
+}
+
+// The planes of union tiles t0 .. t0 + nt - 1 (indices into the plan's tile list) as records over *base (device), and each tile's
+// own status: a tile that fails on the host (a blob that does not parse) still has its P records, constant zero.
+typedef std::function<int(size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status)> PatchSlabs;
+
+// n patches of level L into d_out ([n][ph][pw] pixels of the slide's format, on s's device; pixels outside the level 0): every tile
+// of the plan once, `per` tiles a slab -- their planes decoded (decode_plane_data), their pieces gathered straight into d_out.
+// status[i] (may be NULL): MIC_OK, or the first failing tile of patch i in tile order, with the code mic_hip_wsi_decompress_tile has
+// for it (the blob's, else its first failing plane's).
+int read_patches(mic_hip_session *s, const Mic3 &m, const PatchPlan &plan, int n, int pw, int ph, size_t per, void *d_out, size_t need,
+                 int32_t *status, mic_hip_patch_stats *stats, const PatchSlabs &slabs) {
+    const size_t P = (size_t)m.planes(), ntile = plan.tiles.size();
+    int rc;
+    if ((rc = s->ensure(1, (size_t)m.tw * m.th))) return rc;                                // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // margins outside the level; every byte is written
+    std::vector<int32_t> tst(ntile, MIC_OK), pst;
+    std::vector<WsiPlane> pl; std::vector<PatchPiece> pcs;
+    uint64_t nslab = 0;
+    for (size_t t0 = 0; t0 < ntile; t0 += per, nslab++) {
+        const size_t nt = std::min(per, ntile - t0), p0 = plan.first[t0], np = plan.first[t0 + nt] - p0;
+        const uint8_t *base = nullptr;
+        pl.clear();
+        if ((rc = slabs(t0, nt, &base, pl, tst.data() + t0))) return rc;
+        pst.assign(nt * P, MIC_OK);
+        if ((rc = decode_plane_data(s, m, base, pl.data(), nt, s->wsi_planes, s->wsi_stats, np * sizeof(PatchPiece), pst.data()))) return rc;
+        for (size_t q = 0; q < nt * P; q++) if (tst[t0 + q / P] == MIC_OK) tst[t0 + q / P] = pst[q];
+        pcs.assign(plan.pieces.begin() + (long)p0, plan.pieces.begin() + (long)(p0 + np));
+        for (PatchPiece &pc : pcs) pc.slot -= (int32_t)t0;
+        HIP_TRY(hipMemcpyAsync(s->wsi_stats.p, pcs.data(), np * sizeof(PatchPiece), hipMemcpyHostToDevice, s->stream));
+        s->timer.reset(s->stream); s->timer.mark("k_wsi_gather_patches");
+        launch_gather_patches(s->stream, m, (const uint16_t *)s->wsi_planes.p, (const PatchPiece *)s->wsi_stats.p, np, d_out, pw, ph);
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s->stream));                                           // (pcs, and the slab's planes, are reused by the next one)
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (status) {
+        for (int i = 0; i < n; i++) status[i] = MIC_OK;
+        for (const PatchPiece &pc : plan.pieces) if (status[pc.patch] == MIC_OK) status[pc.patch] = tst[(size_t)pc.slot];
+    }
+    if (stats) { stats->tiles_decoded = ntile; stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
+    return MIC_OK;
+}
+
+// mic_hip_wsi_read_patches / mic_hip_wsi_reader_read_patches on a parsed header, on the session the thread holds: the blobs of
+// the union's tiles from `src` in ONE request (a reader then pulls those blobs only, contiguous ones in one read), a slab's blobs
+// checked on the host and their planes' bytes uploaded in one copy, as decode_blobs does it.
+int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, void *d_out, size_t need,
+                int32_t *status, mic_hip_patch_stats *stats) {
+    mic_hip_session *s = cur_default();
+    const Level &L = m.lv[(size_t)level];
+    const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
+    int rc;
+    if ((rc = patch_pointer(s, &d_out, need))) return rc;
+    PatchPlan plan;
+    if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
+    std::vector<size_t> tiles(plan.tiles.size());
+    for (size_t u = 0; u < tiles.size(); u++) tiles[u] = (size_t)L.first + (size_t)plan.tiles[u];
+    std::vector<TileBlob> blobs; std::vector<uint8_t> keep, bytes;
+    if (!tiles.empty() && (rc = src(tiles, blobs, keep))) return rc;
+    const size_t per = std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P));
+    return read_patches(s, m, plan, n, pw, ph, per, d_out, need, status, stats,
+                        [&](size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status) -> int {
+        bytes.clear();
+        for (size_t k = 0; k < nt; k++) {
+            const size_t b0 = bytes.size();
+            if ((tile_status[k] = parse_tile_blob(m, blobs[t0 + k].p, blobs[t0 + k].len, pl, bytes)) != MIC_OK) {
+                bytes.resize(b0);
+                pl.resize(k * P);
+                pl.resize((k + 1) * P, WsiPlane{ 0, 0, 0, 0 });
+            }
+        }
+        int r = s->io_comp.reserve(bytes.size() + 64);
+        if (r) return r;
+        if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
+        *base = (const uint8_t *)s->io_comp.p;
+        return MIC_OK;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -915,6 +1139,35 @@ int mic_hip_wsi_decompress_region(const uint8_t *c, size_t len, int level, int x
     return wsi_region(flat_source(c, len, m), m, level, x, y, w, h, rgb_out, out_cap, out_w, out_h);
 } MIC_ABI_CATCH
 
+// plan_patches behind the three read_patches calls: the tiles n patches touch (sorted, each once) and the number of pieces
+int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, const int32_t *xy, int n, int pw, int ph,
+                           uint64_t *tiles, size_t cap, uint64_t *ntiles, uint64_t *npieces) try {
+    if (level_w <= 0 || level_h <= 0 || tile_w < 0 || tile_h < 0 || n < 0 || (n > 0 && !xy) || pw <= 0 || ph <= 0 || (cap > 0 && !tiles)) return MIC_ERR_ARGS;
+    PatchPlan plan;
+    const int rc = plan_patches(level_w, level_h, tile_w ? tile_w : 256, tile_h ? tile_h : 256, xy, n, pw, ph, plan);
+    if (rc) return rc;
+    if (ntiles) *ntiles = plan.tiles.size();
+    if (npieces) *npieces = plan.pieces.size();
+    if (plan.tiles.size() > cap) return MIC_ERR_CAPACITY;
+    std::copy(plan.tiles.begin(), plan.tiles.end(), tiles);
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// n patches of one level of a MIC3 file in host memory, into a tensor on the default session's device
+int mic_hip_wsi_read_patches(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                             void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+    if (!c) return MIC_ERR_ARGS;
+    Mic3 m; int rc = parse_mic3(c, len, m);
+    if (rc) return rc;
+    size_t need = 0;
+    if ((rc = patch_args(m, level, xy, n, pw, ph, out_cap, &need))) return rc;
+    if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    DefaultLease lease;
+    if ((rc = lease.acquire())) return rc;
+    return wsi_patches(flat_source(c, len, m), m, level, xy, n, pw, ph, d_out, need, status, stats);
+} MIC_ABI_CATCH
 
 }  // extern "C"
 
@@ -1076,6 +1329,35 @@ int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_p
                                 s->wsi_planes, s->wsi_stats, d_pixels_out, L.w))) return rc;
     }
     return MIC_OK;
+} MIC_ABI_CATCH
+
+// n patches of one level from the store: the plane records of the union's tiles as they stand (no blob is put together or parsed),
+// their bytes where mic_hip_session_wsi_encode left them
+int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+    if (!s || !s->wsi) return MIC_ERR_ARGS;
+    mic_hip_wsi_store &W = *s->wsi;
+    Mic3 m = W.fmt; m.lv = W.lv; m.nlev = (int)W.lv.size();
+    size_t need = 0;
+    int rc = patch_args(m, level, xy, n, pw, ph, out_cap, &need);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    if ((rc = s->activate()) || (rc = patch_pointer(s, &d_out, need))) return rc;
+    const Level &L = m.lv[(size_t)level];
+    const size_t P = (size_t)m.planes();
+    PatchPlan plan;
+    if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
+    return read_patches(s, m, plan, n, pw, ph, session_slab_tiles(m), d_out, need, status, stats,
+                        [&](size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
+        for (size_t k = 0; k < nt; k++) {
+            const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)plan.tiles[t0 + k]) * P;
+            pl.insert(pl.end(), rec, rec + P);
+        }
+        *base = (const uint8_t *)W.bytes.p;
+        return MIC_OK;
+    });
 } MIC_ABI_CATCH
 
 int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int *heights, int cap) try {
@@ -1469,6 +1751,21 @@ int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x
     if (!r || !out) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     return wsi_region(r->source(), r->m, level, x, y, w, h, out, out_cap, out_w, out_h);
+} MIC_ABI_CATCH
+
+int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+    if (!r) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    size_t need = 0;
+    int rc = patch_args(r->m, level, xy, n, pw, ph, out_cap, &need);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    DefaultLease lease;
+    if ((rc = lease.acquire())) return rc;
+    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, d_out, need, status, stats);
 } MIC_ABI_CATCH
 
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
