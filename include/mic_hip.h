@@ -321,6 +321,43 @@ int mic_hip_mic2_decompress(const uint8_t *compressed, size_t compressed_len,
 int mic_hip_mic2_decompress_frame(const uint8_t *compressed, size_t compressed_len, int frame_idx,
                                   uint16_t *pixels_out, size_t pixels_cap);
 
+/* Many 3-D crops per call, into a tensor that already lives on the device (no reference counterpart; beside
+ * mic_hip_mic2_decompress / _decompress_frame, which serve whole frames through the host, and the MIC3 patch calls, whose semantics
+ * carry over).  Crop i is the box [x, x + cw) x [y, y + ch) x [z, z + cd) with (x, y, z) = xyz[3i .. 3i + 2], z the frame index;
+ * origins may be negative and a box may overhang the volume in any axis or lie wholly outside it: samples outside the volume are
+ * 0.  d_out receives n x cd x ch x cw little-endian u16 -- crop-major, then frame, row, column --, n * cd * ch * cw * 2 bytes, every
+ * one of them written.  d_out is memory the device can write: a device allocation on the call's device that is long enough for
+ * the tensor, or pinned host memory (mic_hip_host_alloc); anything else is MIC_ERR_ARGS, found with hipPointerGetAttributes before
+ * anything is launched.
+ * Independent files: only the frames some crop overlaps are entropy-decoded, each once, and a kernel writes every (crop, frame)
+ * overlap -- a "piece" -- from the decoded frames into d_out.  Temporal files: frame_i = frame_0 + sum UnZigZag(res_j) mod 2^16 is
+ * summed under the crops' footprints only, by a kernel that walks the residual symbols and stores the crop slices; frames 1.. never
+ * exist as images, and residual streams behind the last frame a crop overlaps are not decoded.  Both run in sub-batches of frames
+ * under the workspace ceiling.
+ * status[i] (host, may be NULL): MIC_OK, or the unit codec's code of the first failing frame, in frame order, among the frames
+ * crop i depends on -- independent: the frames it overlaps with non-empty area; temporal: frames 0 .. the last one it overlaps (a
+ * damaged residual poisons everything behind it).  Such a crop's samples are unspecified, every other crop is exact.
+ * Returns MIC_OK when the call ran, even if crops failed; n == 0 is MIC_OK; MIC_ERR_ARGS for cw, ch, cd <= 0 or n < 0;
+ * MIC_ERR_CAPACITY for out_cap below the tensor's size; the header's and table's errors are mic_hip_mic2_info's; a table entry of a
+ * needed frame that has length 0 or points outside the file fails the whole call with MIC_ERR_CORRUPT, as mic_hip_mic2_decompress
+ * does.  One device: the calling thread's default session (the file and reader forms) or the given session; no fan-out over
+ * mic_hip_set_devices.
+ * stats (may be NULL): frames entropy-decoded and pieces (the plan's counts), slabs = decode chains the call ran. */
+typedef struct { uint64_t frames_decoded, pieces, slabs; } mic_hip_crop_stats;
+/* The host planner of those calls: frames[cap] receives the frames whose streams must be entropy-decoded, ascending, each once --
+ * independent (temporal = 0): the union of the frames the crops overlap; temporal: 0 .. the last overlapped frame; none when no
+ * crop has a non-empty overlap.  *nframes_out their number, *npieces the number of (crop, frame) pairs with non-empty overlap area,
+ * in both modes (both may be NULL).  More than cap frames: MIC_ERR_CAPACITY with the counts set and frames untouched.  Needs no
+ * device. */
+int mic_hip_mic2_crop_plan(int width, int height, int nframes, int temporal,
+                           const int32_t *xyz, int n, int cw, int ch, int cd,
+                           uint32_t *frames, size_t cap, uint64_t *nframes_out, uint64_t *npieces);
+int mic_hip_mic2_read_crops(const uint8_t *compressed, size_t compressed_len,
+                            const int32_t *xyz, int n, int cw, int ch, int cd,
+                            void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
+/* (the reader form, mic_hip_mic2_reader_*, stands with the streaming calls below, the session form,
+ * mic_hip_session_mic2_read_crops, with the session calls: they need those sections' types) */
+
 /* ---- WaveletV2 -------------------------------------------------------------------------------- */
 /* Replaces WaveletV2RLEFSECompressU16 and WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303,
  * :374; identical streams): up to 8 levels of 5/3 integer lifting in Mallat layout, subband scan, zigzag
@@ -475,6 +512,16 @@ int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x
 int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r);
+/* MIC2 reader: mic_hip_mic2_read_crops on a file behind a pread-like source.  open pulls the 20-byte header and then the
+ * 8 * nframes-byte frame table through the callback, and nothing else, and validates them as mic_hip_mic2_info does; open and
+ * info need no device.  read_crops pulls only the blobs of the plan's frames (mic_hip_mic2_crop_plan), each once, contiguous ones in
+ * one read.  Calls on one handle are serialised, and so are its callbacks. */
+typedef struct mic_hip_mic2_reader mic_hip_mic2_reader;
+int mic_hip_mic2_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len, mic_hip_mic2_reader **r);
+int mic_hip_mic2_reader_info(const mic_hip_mic2_reader *r, int *width, int *height, int *nframes, int *temporal);
+int mic_hip_mic2_reader_read_crops(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
+void mic_hip_mic2_reader_close(mic_hip_mic2_reader *r);
 
 /* ---- single-frame RGB and the CLI's single-frame files ------------------------------------------ */
 /* Replaces CompressRGB / DecompressRGB (rgbcompress.go:25-33): YCoCg-R, then the three planes as in a WSI tile blob
@@ -587,6 +634,15 @@ int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int
  * slide stays in HBM, the plane records are used as they stand -- a training loop's sampler.  d_out on the session's device. */
 int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
+
+/* mic_hip_mic2_read_crops on a MIC2 file that lies in device memory: head = the file's first 20 + 8 * nframes bytes on the host,
+ * d_file = the whole file (file_len bytes) on the session's device.  The streams of the plan's frames go device to device into the
+ * session's compressed-input buffer (which keeps the 64 bytes of slack the decode kernels may read past a stream's end; the
+ * caller's allocation owes them nothing) -- nothing crosses PCIe.  d_out on the session's device, or pinned host memory. */
+int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, size_t head_len,
+                                    const uint8_t *d_file, size_t file_len,
+                                    const int32_t *xyz, int n, int cw, int ch, int cd,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
 
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);

@@ -111,6 +111,11 @@ class PatchStats(C.Structure):
     _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class CropStats(C.Structure):
+    """mic_hip_crop_stats"""
+    _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
+
+
 class Unit(C.Structure):
     _fields_ = [("px_offset", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
@@ -126,6 +131,8 @@ ABI_SYMBOLS = [
     "mic_hip_pics_compress_batch", "mic_hip_pics_decompress_batch",
     "mic_hip_mic2_compress", "mic_hip_mic2_compress_temporal", "mic_hip_mic2_info", "mic_hip_mic2_decompress",
     "mic_hip_mic2_decompress_frame",
+    "mic_hip_mic2_crop_plan", "mic_hip_mic2_read_crops", "mic_hip_mic2_reader_open", "mic_hip_mic2_reader_info",
+    "mic_hip_mic2_reader_read_crops", "mic_hip_mic2_reader_close", "mic_hip_session_mic2_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
     "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
@@ -289,6 +296,16 @@ def lib() -> C.CDLL:
     L.mic_hip_mic2_info.argtypes = [C.c_void_p, C.c_size_t] + [C.POINTER(C.c_int)] * 4
     L.mic_hip_mic2_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.mic_hip_mic2_decompress_frame.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+    _crop_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(CropStats)]
+    L.mic_hip_mic2_crop_plan.argtypes = [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mic_hip_mic2_read_crops.argtypes = [C.c_void_p, C.c_size_t] + _crop_args
+    L.mic_hip_mic2_reader_open.argtypes = [_READ_FN, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mic_hip_mic2_reader_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+    L.mic_hip_mic2_reader_read_crops.argtypes = [C.c_void_p] + _crop_args
+    L.mic_hip_mic2_reader_close.argtypes = [C.c_void_p]
+    L.mic_hip_mic2_reader_close.restype = None
+    L.mic_hip_session_mic2_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + _crop_args
     L.mic_hip_wavelet_v2_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_wavelet_v2_compress_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
@@ -684,6 +701,54 @@ def decompress_frame(compressed, frame_idx: int) -> np.ndarray:
     return out.reshape(h.value, w.value)
 
 
+def _crop_xyz(xyz) -> np.ndarray:
+    """(n, 3) crop origins (x, y, z) as the int32 triples the C calls take"""
+    return np.ascontiguousarray(np.asarray(xyz, dtype=np.int64).reshape(-1, 3).astype(np.int32))
+
+
+def mic2_crop_plan(width: int, height: int, nframes: int, temporal: bool, xyz, cw: int, ch: int, cd: int,
+                   cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """mic_hip_mic2_crop_plan: (frames whose streams the crops need entropy-decoded -- ascending, each once --, number of
+    (crop, frame) pieces).  Needs no device.  cap: room for that many frames (default: as many as it takes); too few raises
+    MicError (MIC_ERR_CAPACITY) whose ``nframes`` and ``pieces`` attributes are the counts."""
+    a = _crop_xyz(xyz)
+    nf, npc = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        rc = lib().mic_hip_mic2_crop_plan(width, height, nframes, int(bool(temporal)), a.ctypes.data, len(a), cw, ch, cd, None, 0,
+                                          C.byref(nf), C.byref(npc))
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "mic2_crop_plan")
+        cap = nf.value
+    frames = np.zeros(max(cap, 1), dtype=np.uint32)
+    rc = lib().mic_hip_mic2_crop_plan(width, height, nframes, int(bool(temporal)), a.ctypes.data, len(a), cw, ch, cd,
+                                      frames.ctypes.data, cap, C.byref(nf), C.byref(npc))
+    if rc:
+        e = MicError(rc, "mic2_crop_plan")
+        e.nframes, e.pieces = nf.value, npc.value
+        raise e
+    return frames[: nf.value].copy(), npc.value
+
+
+def _read_crops(call, xyz, d_out: int, out_cap: int):
+    a = _crop_xyz(xyz)
+    st = np.zeros(len(a), dtype=np.int32)
+    cs = CropStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, C.byref(cs))
+    return rc, st, dict(frames_decoded=cs.frames_decoded, pieces=cs.pieces, slabs=cs.slabs)
+
+
+def mic2_read_crops(compressed, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    """mic_hip_mic2_read_crops: the cw x ch x cd crops at the (x, y, z) origins `xyz` of a MIC2 file (z = frame index), into the
+    caller's device tensor d_out (an int: ``torch.empty((n, cd, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned
+    host memory) of out_cap bytes.  Samples outside the volume are 0.  -> (status per crop, dict(frames_decoded, pieces, slabs))."""
+    c = _bytes_arr(compressed)
+    rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_mic2_read_crops(
+        c.ctypes.data, c.size, a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
+    if rc:
+        _raise(rc, "mic2_read_crops")
+    return st, stats
+
+
 # ------------------------------------------------------------------ WaveletV2
 def wavelet_v2_compress(pixels, rows: int, cols: int, max_value: int, levels: int = 5) -> bytes:
     """WaveletV2RLEFSECompressU16 / WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303, :374)."""
@@ -1017,25 +1082,31 @@ class WsiWriter:
             pass
 
 
+def _read_source(source, file_len: Optional[int], where: str):
+    """(get(offset, n) -> bytes-like, file_len) of a reader's source: bytes, a binary file object, or a callable"""
+    if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
+        buf = memoryview(source).cast("B")
+        get = lambda off, n: buf[off: off + n]
+        file_len = len(buf) if file_len is None else file_len
+    elif hasattr(source, "seek") and hasattr(source, "read"):
+        def get(off, n):
+            source.seek(off)
+            return source.read(n)
+        if file_len is None:
+            file_len = source.seek(0, os.SEEK_END)
+    else:
+        get = source
+    if file_len is None:
+        raise MicError(MIC_ERR_ARGS, where + ": file_len")
+    return get, int(file_len)
+
+
 class WsiReader:
     """MIC3 random-access reader (mic_hip_wsi_reader_*): reads the header and tile index at open, then only the blobs of the
     tiles a tile() or region() covers.  source: a binary file object (seek + read), bytes, or a callable (offset, n) -> bytes."""
 
     def __init__(self, source, file_len: Optional[int] = None):
-        if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
-            buf = memoryview(source).cast("B")
-            get = lambda off, n: buf[off: off + n]
-            file_len = len(buf) if file_len is None else file_len
-        elif hasattr(source, "seek") and hasattr(source, "read"):
-            def get(off, n):
-                source.seek(off)
-                return source.read(n)
-            if file_len is None:
-                file_len = source.seek(0, os.SEEK_END)
-        else:
-            get = source
-        if file_len is None:
-            raise MicError(MIC_ERR_ARGS, "WsiReader: file_len")
+        get, file_len = _read_source(source, file_len, "WsiReader")
 
         def fill(off, ptr, n):
             data = get(off, n)
@@ -1076,6 +1147,54 @@ class WsiReader:
     def close(self) -> None:
         if self._h:
             lib().mic_hip_wsi_reader_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mic2Reader:
+    """MIC2 random-access reader (mic_hip_mic2_reader_*): reads the header and the frame table at open, then only the streams of
+    the frames a read_crops() needs.  source: a binary file object (seek + read), bytes, or a callable (offset, n) -> bytes."""
+
+    def __init__(self, source, file_len: Optional[int] = None):
+        get, file_len = _read_source(source, file_len, "Mic2Reader")
+
+        def fill(off, ptr, n):
+            data = get(off, n)
+            if len(data) != n:
+                raise EOFError(f"Mic2Reader: {len(data)} of {n} bytes at {off}")
+            C.memmove(ptr, bytes(data), n)
+        self._cb = _Callback(fill, _READ_FN)
+        self._h = C.c_void_p()
+        self._cb.check(lib().mic_hip_mic2_reader_open(self._cb.c, None, file_len, C.byref(self._h)), "Mic2Reader")
+
+    def info(self):
+        """dict(width, height, nframes, temporal), as mic_hip_mic2_info of the whole file"""
+        v = [C.c_int() for _ in range(4)]
+        self._cb.check(lib().mic_hip_mic2_reader_info(self._h, *[C.byref(x) for x in v]), "Mic2Reader.info")
+        w, h, n, t = (x.value for x in v)
+        return dict(width=w, height=h, nframes=n, temporal=bool(t))
+
+    def read_crops(self, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+        """as mic2_read_crops on the whole file; only the streams of the plan's frames are read, each once"""
+        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_mic2_reader_read_crops(
+            self._h, a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
+        self._cb.check(rc, "Mic2Reader.read_crops")
+        return st, stats
+
+    def close(self) -> None:
+        if self._h:
+            lib().mic_hip_mic2_reader_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -1424,4 +1543,14 @@ class Session:
             self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
         if rc:
             _raise(rc, "session_wsi_read_patches")
+        return st, stats
+
+    def mic2_read_crops(self, head, d_file: int, file_len: int, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+        """mic2_read_crops of a MIC2 file that lies on the session's device: head = its first 20 + 8 * nframes bytes (host),
+        d_file = the whole file (file_len bytes) in device memory; the streams go device to device"""
+        hd = _bytes_arr(head)
+        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_session_mic2_read_crops(
+            self._h, hd.ctypes.data, hd.size, int(d_file) or None, int(file_len), a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
+        if rc:
+            _raise(rc, "session_mic2_read_crops")
         return st, stats

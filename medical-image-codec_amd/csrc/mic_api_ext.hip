@@ -9,6 +9,7 @@
 // writes the container around the plane blobs.  Decode mirrors it: one batch over the planes of
 // the requested tiles, then inverse transform + crop on the device.
 #include "mic_session.h"
+#include "mic_pieces.h"
 
 #include <memory>
 
@@ -143,14 +144,6 @@ __global__ void __launch_bounds__(256) k_wsi_plane_to_grey(const uint16_t *plane
 // A piece is one patch-tile overlap: w x h pixels from (sx, sy) of the tile in slab slot `slot` to (dx, dy) of patch `patch`.
 // The host plans them (plan_patches): the kernels divide nothing.
 struct PatchPiece { int32_t patch, slot, sx, sy, dx, dy, w, h; };
-
-// Lanes run along x of a piece row.  A piece narrower than a wave puts 64 / lw of its rows side by side in one (lw: the power of
-// two >= w, at most 64), so a 17-pixel overlap keeps 32 + 17 lanes of 64 busy instead of 17.  grid = (pieces, row chunks).
-struct PieceLanes { int col, lw, row, rstep; };
-__device__ __forceinline__ PieceLanes piece_lanes(int w) {
-    const int sh = min(6, 32 - __clz(w - 1));                                       // (w >= 1; __clz(0) = 32: one lane per row)
-    return PieceLanes{ (int)threadIdx.x & ((1 << sh) - 1), 1 << sh, (int)(threadIdx.x >> sh) + (int)blockIdx.y * (256 >> sh), (256 >> sh) * (int)gridDim.y };
-}
 
 // YCoCgRInverse (asm_amd64.go:106-121) of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at
 // whatever byte offset the patch row has.  planes: [slot][3][tw * th] u16; out: [patch][ph][pw][3] u8.
@@ -852,23 +845,7 @@ int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int p
     return MIC_OK;
 }
 
-// d_out must be memory the session's device can write `need` bytes of: an allocation of that device, or pinned host memory
-// (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched; *d_out becomes the
-// address the device uses.
-int patch_pointer(const mic_hip_session *s, void **d_out, size_t need) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, *d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }   // (unregistered memory)
-    if (at.type == hipMemoryTypeDevice) {
-        if (at.device != s->device) return MIC_ERR_ARGS;
-        hipDeviceptr_t b = nullptr; size_t sz = 0;
-        if (hipMemGetAddressRange(&b, &sz, (hipDeviceptr_t)*d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }
-        if ((size_t)((char *)*d_out - (char *)b) + need > sz) return MIC_ERR_CAPACITY;     // (the allocation ends before out_cap does)
-    } else if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) {
-        if (at.devicePointer) *d_out = at.devicePointer;
-    } else return MIC_ERR_ARGS;
-    return MIC_OK;
-}
+// (patch_pointer -- d_out must be memory the session's device can write -- is shared with the MIC2 crop calls: mic_mic2_crops.hip)
 
 // The planes of union tiles t0 .. t0 + nt - 1 (indices into the plan's tile list) as records over *base (device), and each tile's
 // own status: a tile that fails on the host (a blob that does not parse) still has its P records, constant zero.

@@ -1,0 +1,406 @@
+// mic_mic2_crops.hip -- MIC2: many 3-D crops per call into a device tensor (mic_hip_mic2_read_crops, mic_hip_mic2_reader_*,
+// mic_hip_session_mic2_read_crops; no reference counterpart).
+//
+// One core (mic2_read_crops) behind the three doors; a door brings the parsed header, the frame table and a Mic2Source that says
+// where a frame's stream lies (the caller's file, the blobs a reader pulled, a file in device memory).  The host plans
+// (mic2_plan_crops): which frames' streams must be entropy-decoded, and the (crop, frame) overlaps -- pieces.  The frames go through
+// the unit codec in sub-batches of mic2_frames_per_batch, and behind each sub-batch a kernel writes into the crop tensor:
+//   independent files: k_mic2_gather_crops copies the sub-batch's pieces out of the decoded frames;
+//   temporal files:    frame_i = frame_0 + sum_{j<=i} UnZigZag(res_j) (mod 2^16) is a running sum per pixel (mic_temporal.hip), and a
+//                      crop needs it under its own footprint only: k_mic2_accumulate_crops walks the sub-batch's residual symbols
+//                      with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0, the
+//                      spatial unit, is the only full image on the device; the carry from one sub-batch to the next lives in the
+//                      tensor itself.
+#include <climits>
+#include <memory>
+#include "mic_session.h"
+#include "mic_pieces.h"
+
+void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter);   // mic_wavelet.hip
+
+namespace {
+
+// frames: the sub-batch's decoded frames, [slot][npx] u16 of fw samples a row, slot = pc.k - k0; out: [crop][cd][ch][cw] u16.
+// grid = (pieces, row chunks); lanes along x (piece_lanes).  A row whose source and destination are both 4-byte aligned moves as
+// dwords (the odd sample behind them as u16), any other row as u16: with an odd frame or crop width every second row is such a row.
+__global__ void __launch_bounds__(256) k_mic2_gather_crops(const uint16_t *frames, int fw, size_t npx, const CropPiece *pieces, int k0,
+                                                         uint16_t *out, int cw, int ch, int cd) {
+    const CropPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const uint16_t *src = frames + (size_t)(pc.k - k0) * npx + (size_t)pc.sy * fw + pc.sx;
+    uint16_t *dst = out + (((size_t)pc.crop * cd + pc.dz) * ch + pc.dy) * cw + pc.dx;
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * fw);
+        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
+        if ((((size_t)s | (size_t)d) & 3) == 0) {
+            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
+            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
+            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
+            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = s[pc.w - 1];
+        } else
+            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = s[x];
+    }
+}
+
+// units 0 .. nb-1 hold frames f0 .. f0 + nb - 1 (unit 0 of the first sub-batch, f0 = 0, is the spatial frame in frame0; every other
+// unit a residual whose symbols lie in its sym slab).  fp = a crop's footprint: w x h pixels at (sx, sy) of every frame, the crop's
+// frames inside the volume zf = fp.frame .. fp.k, slice dz the one of zf.  One lane per footprint pixel:
+//   acc = frame f0 - 1 of that pixel -- frame0's sample, or the carry the sub-batch before left in the tensor: in slice(zf) while the
+//         sum has not reached zf, in slice(f0 - 1) from then on;
+//   acc = (acc + UnZigZag(res_f)) & 0xFFFF for f = f0 .. min(f0 + nb - 1, fp.k), stored into slice(f) when f >= zf     (k_tmp_accumulate);
+//   a sum that has not reached zf at the sub-batch's end goes into slice(zf), the next sub-batch's carry.
+// A crop that is complete (fp.k < f0) or depends on a failed unit (fp.k >= fbad, the first failed frame) is left alone.
+__global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *units, int nb, int f0, int fbad, const uint16_t *frame0, int fw,
+                                                             const CropPiece *prints, uint16_t *out, int cw, int ch, int cd) {
+    const CropPiece fp = prints[blockIdx.x];
+    if (fp.k < f0 || fp.k >= fbad) return;
+    const PieceLanes ln = piece_lanes(fp.w);
+    const int zf = fp.frame, iend = min(nb, fp.k - f0 + 1), r0 = f0 ? 0 : 1;
+    const size_t slice = (size_t)ch * cw;
+    uint16_t *dst = out + (((size_t)fp.crop * cd + fp.dz) * ch + fp.dy) * cw + fp.dx;
+    for (int y = ln.row; y < fp.h; y += ln.rstep) {
+        const size_t srow = (size_t)(fp.sy + y) * fw + fp.sx;
+        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
+        for (int x = ln.col; x < fp.w; x += ln.lw) {
+            uint32_t acc;
+            if (f0 == 0) {
+                acc = mic_g(frame0)[srow + x];
+                if (zf == 0) d[x] = (uint16_t)acc;
+            } else acc = d[(size_t)max(f0 - 1 - zf, 0) * slice + x];
+            for (int i = r0; i < iend; i++) {
+                acc = (acc + unzigzag16(mic_g(units[i].sym)[srow + x])) & 0xFFFFu;          // temporaldelta.go:27-37
+                if (f0 + i >= zf) d[(size_t)(f0 + i - zf) * slice + x] = (uint16_t)acc;
+            }
+            if (f0 + iend - 1 < zf) d[x] = (uint16_t)acc;
+        }
+    }
+}
+
+// rows of a piece per block pass = 256 / lanes per row; grid y cuts pieces of more than 16 passes
+unsigned row_chunks(int w, int h) {
+    int lw = 1;
+    while (lw < w && lw < 64) lw *= 2;
+    const int passes = (h + 256 / lw - 1) / (256 / lw) * ((w + 63) / 64);
+    return (unsigned)std::min(16, std::max(1, passes / 16));
+}
+
+}  // namespace
+
+namespace micapi {
+
+int patch_pointer(const mic_hip_session *s, void **d_out, size_t need) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, *d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }   // (unregistered memory)
+    if (at.type == hipMemoryTypeDevice) {
+        if (at.device != s->device) return MIC_ERR_ARGS;
+        hipDeviceptr_t b = nullptr; size_t sz = 0;
+        if (hipMemGetAddressRange(&b, &sz, (hipDeviceptr_t)*d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }
+        if ((size_t)((char *)*d_out - (char *)b) + need > sz) return MIC_ERR_CAPACITY;     // (the allocation ends before out_cap does)
+    } else if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) {
+        if (at.devicePointer) *d_out = at.devicePointer;
+    } else return MIC_ERR_ARGS;
+    return MIC_OK;
+}
+
+// The plan of n crops of cw x ch x cd in a volume of width x height x nframes: the clipped box of each crop, one piece per frame of
+// it (sorted by frame, so a sub-batch of frames owns a contiguous range), one footprint per crop, and the frames to entropy-decode --
+// independent: the frames some crop overlaps; temporal: 0 .. the last of them, whatever lies in between being part of the sum.
+int mic2_plan_crops(int width, int height, int nframes, int temporal, const int32_t *xyz, int n, int cw, int ch, int cd, CropPlan &plan) {
+    plan.frames.clear(); plan.pieces.clear(); plan.prints.clear();
+    std::vector<uint32_t> per_frame((size_t)std::max(nframes, 0) + 1, 0);       // pieces of each frame, then their first index
+    for (int i = 0; i < n; i++) {
+        const int64_t x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        const int64_t x0 = std::max<int64_t>(x, 0), x1 = std::min<int64_t>(x + cw, width), y0 = std::max<int64_t>(y, 0), y1 = std::min<int64_t>(y + ch, height);
+        const int64_t z0 = std::max<int64_t>(z, 0), z1 = std::min<int64_t>(z + cd, nframes);
+        if (x1 <= x0 || y1 <= y0 || z1 <= z0) continue;
+        plan.prints.push_back(CropPiece{ i, (int32_t)z0, (int32_t)x0, (int32_t)y0, (int32_t)(x0 - x), (int32_t)(y0 - y), (int32_t)(z0 - z),
+                                         (int32_t)(x1 - x0), (int32_t)(y1 - y0), (int32_t)(z1 - 1) });
+        for (int64_t f = z0; f < z1; f++) per_frame[(size_t)f]++;
+    }
+    size_t total = 0;
+    int last = -1;
+    for (int f = 0; f < nframes; f++) {
+        const uint32_t c = per_frame[(size_t)f];
+        per_frame[(size_t)f] = (uint32_t)total;
+        total += c;
+        if (c) last = f;
+        if (c && !temporal) plan.frames.push_back((uint32_t)f);
+    }
+    if (total > 0xFFFFFFFFull) return MIC_ERR_UNSUPPORTED;
+    if (temporal) for (int f = 0; f <= last; f++) plan.frames.push_back((uint32_t)f);
+    std::vector<int32_t> place((size_t)std::max(nframes, 0), 0);                // frame -> its index in plan.frames
+    for (size_t k = 0; k < plan.frames.size(); k++) place[plan.frames[k]] = (int32_t)k;
+    plan.pieces.resize(total);
+    for (const CropPiece &fp : plan.prints)
+        for (int f = fp.frame; f <= fp.k; f++) {
+            CropPiece pc = fp;
+            pc.frame = f; pc.dz = fp.dz + (f - fp.frame); pc.k = place[(size_t)f];
+            plan.pieces[per_frame[(size_t)f]++] = pc;
+        }
+    return MIC_OK;
+}
+
+// What the three crop entry points check of their arguments before a device is touched; *need = bytes of the crop tensor.
+int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need) {
+    if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || (n > 0 && !xyz)) return MIC_ERR_ARGS;
+    if (m.w <= 0 || m.h <= 0) return MIC_ERR_CORRUPT;                                       // (as mic_hip_mic2_decompress)
+    if ((size_t)m.w * (size_t)m.h > ((size_t)1 << 28) || m.file_len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
+    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)cd * (unsigned)ch * (unsigned)cw * 2;
+    if (bytes > out_cap) return MIC_ERR_CAPACITY;
+    *need = (size_t)bytes;
+    return MIC_OK;
+}
+
+// n crops into d_out ([n][cd][ch][cw] u16, an address s's device can write: patch_pointer; samples outside the volume 0), on a session
+// the caller holds and has made current; the table entries of the plan's frames have been checked (crops_call).  status[i] (may be NULL): MIC_OK, or the code of the first failing frame crop i depends on.
+int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
+                    void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats) {
+    const size_t npx = (size_t)m.w * (size_t)m.h, nfr = plan.frames.size();
+    int rc;
+    std::vector<uint64_t> len(nfr);
+    for (size_t k = 0; k < nfr; k++) len[k] = get_u32(m.table + 8 * (size_t)plan.frames[k] + 4);
+    if ((rc = s->ensure(1, npx))) return rc;                                                // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volume; every byte is written
+    const std::vector<CropPiece> &list = m.temporal ? plan.prints : plan.pieces;
+    if (nfr) {
+        if ((rc = s->mic2_pieces.reserve(list.size() * sizeof(CropPiece)))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->mic2_pieces.p, list.data(), list.size() * sizeof(CropPiece), hipMemcpyHostToDevice, s->stream));
+    }
+    const CropPiece *d_list = (const CropPiece *)s->mic2_pieces.p;
+    std::vector<size_t> first(nfr + 1, 0);                                                  // independent: the pieces of plan frame k
+    if (!m.temporal) {
+        for (const CropPiece &pc : plan.pieces) first[(size_t)pc.k + 1]++;
+        for (size_t k = 0; k < nfr; k++) first[k + 1] += first[k];
+    }
+    int mw = 1, mh = 1;
+    for (const CropPiece &fp : plan.prints) { mw = std::max(mw, fp.w); mh = std::max(mh, fp.h); }
+    const unsigned gy = row_chunks(mw, mh);
+    const size_t per = mic2_frames_per_batch(npx);
+    std::vector<int32_t> fst(nfr, MIC_OK);                                                  // status of plan frame k
+    std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
+    int fbad = INT_MAX, bad_code = MIC_OK;                                                  // temporal: the first failed frame
+    uint64_t nslab = 0;
+    for (size_t k0 = 0; k0 < nfr && fbad == INT_MAX; k0 += per) {
+        const int nb = (int)std::min(per, nfr - k0);
+        // the sub-batch's streams back to back in the compressed-input buffer, neighbours in the source in one copy
+        begins.assign((size_t)nb, 0); ends.assign((size_t)nb, 0);
+        uint64_t total = 0;
+        for (int i = 0; i < nb; i++) { begins[(size_t)i] = total; total += len[k0 + (size_t)i]; ends[(size_t)i] = total; }
+        if ((rc = s->io_comp.reserve((size_t)total + 64))) return rc;
+        for (int i = 0; i < nb;) {
+            const uint8_t *p = src.blob(plan.frames[k0 + (size_t)i]);
+            size_t bytes = (size_t)len[k0 + (size_t)i];
+            int j = i + 1;
+            while (j < nb && src.blob(plan.frames[k0 + (size_t)j]) == p + bytes) bytes += (size_t)len[k0 + (size_t)j++];
+            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + begins[(size_t)i], p, bytes, src.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+            i = j;
+        }
+        nslab++;
+        if (!m.temporal) {
+            if ((rc = s->io_px.reserve(npx * 2 * (size_t)nb + 64))) return rc;
+            units.assign((size_t)nb, mic_hip_unit{ 0, m.w, m.h, 0, 0 });
+            for (int i = 0; i < nb; i++) units[(size_t)i].px_offset = (uint64_t)i * npx;
+            if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
+            if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
+            const size_t p0 = first[k0], np = first[k0 + (size_t)nb] - p0;
+            s->timer.reset(s->stream); s->timer.mark("k_mic2_gather_crops");
+            for (size_t q = 0; q < np; q += 0x7FFFFFFF)
+                hipLaunchKernelGGL(k_mic2_gather_crops, dim3((unsigned)std::min<size_t>(np - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
+                                   (const uint16_t *)s->io_px.p, m.w, npx, d_list + p0 + q, (int)k0, (uint16_t *)d_out, cw, ch, cd);
+            s->timer.mark("end");
+        } else {
+            // (as mic2_temporal_decompress: the frames of a temporal plan are 0 .. nfr - 1, so plan index = frame)
+            if ((rc = s->io_px.reserve(npx * 2 + 64))) return rc;
+            if ((rc = s->lay_out(nb, npx))) return rc;
+            for (int i = 0; i < nb; i++) {
+                MicUnit &u = s->h_units[(size_t)i];
+                u.comp_in = (const uint8_t *)s->io_comp.p + begins[(size_t)i]; u.comp_len = (uint32_t)len[k0 + (size_t)i];
+                u.w = m.w; u.h = m.h;
+                u.tok_cap = (uint32_t)tok_cap_for(npx);
+                if (k0 == 0 && i == 0) { u.mode = 0; u.px_out = (uint16_t *)s->io_px.p; }
+                else u.mode = 3;                                         // FSE + RLE-of-symbols into u.sym
+            }
+            const int r0 = k0 ? 0 : 1;                                    // first residual unit
+            rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
+                mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p);
+                if (nb > r0) {
+                    mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
+                    mic2_launch_residual_check((MicUnit *)s->units.p, nb, (uint32_t)npx, r0, s->stream);
+                }
+            });
+            if (rc) return rc;
+            if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
+            for (int i = 0; i < nb && fbad == INT_MAX; i++) if (fst[k0 + (size_t)i] != MIC_OK) { fbad = (int)k0 + i; bad_code = fst[k0 + (size_t)i]; }
+            s->timer.reset(s->stream); s->timer.mark("k_mic2_accumulate_crops");
+            for (size_t q = 0; q < list.size() && fbad > (int)k0; q += 0x7FFFFFFF)
+                hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)std::min<size_t>(list.size() - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
+                                   (const MicUnit *)s->units.p, nb, (int)k0, fbad, (const uint16_t *)s->io_px.p, m.w, d_list + q, (uint16_t *)d_out, cw, ch, cd);
+            s->timer.mark("end");
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (status) {
+        for (int i = 0; i < n; i++) status[i] = MIC_OK;
+        if (m.temporal) { for (const CropPiece &fp : plan.prints) if (fp.k >= fbad) status[fp.crop] = bad_code; }
+        else for (const CropPiece &pc : plan.pieces) if (status[pc.crop] == MIC_OK) status[pc.crop] = fst[(size_t)pc.k];
+    }
+    if (stats) { stats->frames_decoded = nfr; stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
+    return MIC_OK;
+}
+
+}  // namespace micapi
+
+namespace {
+
+// the fixed 20 bytes (mic_hip_mic2_info's checks, against the whole file's length) into m; the table is the caller's to attach
+int parse_mic2(const uint8_t *head, uint64_t file_len, Mic2Head &m) {
+    const int rc = mic_hip_mic2_info(head, (size_t)file_len, &m.w, &m.h, &m.n, &m.temporal);
+    m.file_len = file_len;
+    return rc;
+}
+
+// a door's call on its parsed file: arguments, n == 0, the plan, then the core on session s (leased here when s is NULL)
+int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(const CropPlan &, Mic2Source &)> &source,
+               const int32_t *xyz, int n, int cw, int ch, int cd, void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+    size_t need = 0;
+    int rc = mic2_crop_args(m, xyz, n, cw, ch, cd, out_cap, &need);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_crop_stats{ 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    CropPlan plan;
+    if ((rc = mic2_plan_crops(m.w, m.h, m.n, m.temporal, xyz, n, cw, ch, cd, plan))) return rc;
+    DefaultLease lease;
+    if (!s) { if ((rc = lease.acquire())) return rc; s = cur_default(); }
+    else if ((rc = s->activate())) return rc;
+    // the pointer and the table are judged before a source is asked for a byte, and before anything is launched
+    rc = patch_pointer(s, &d_out, need);
+    if (rc == MIC_ERR_CAPACITY || ((size_t)d_out & 1)) rc = MIC_ERR_ARGS;                   // (out_cap held the tensor: it is the allocation that does not)
+    if (rc) return rc;
+    for (uint32_t f : plan.frames) {                                                        // as mic_hip_mic2_decompress, multiframe.go:137-139
+        const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)f), bl = get_u32(m.table + 8 * (size_t)f + 4);
+        if (bl == 0 || off + bl > m.file_len) return MIC_ERR_CORRUPT;
+    }
+    Mic2Source src;
+    if ((rc = source(plan, src))) return rc;
+    return mic2_read_crops(s, m, plan, src, n, cw, ch, cd, d_out, need, status, stats);
+}
+
+}  // namespace
+
+struct mic_hip_mic2_reader {
+    std::mutex mu;                          // one call at a time (and with it one callback at a time)
+    mic_hip_read_fn read = nullptr; void *user = nullptr;
+    Mic2Head m;
+    std::vector<uint8_t> head;              // the fixed header and the frame table
+    std::vector<uint8_t> keep;              // the blobs of the last call's plan, in plan order
+    std::vector<size_t> pos;                // frame -> its blob's place in keep
+    // the blobs of the plan's frames (their table entries checked by crops_call) through the callback, one read per run of neighbours
+    int fetch(const CropPlan &plan, Mic2Source &src) {
+        const size_t nfr = plan.frames.size(), data_off = 20 + 8 * (size_t)m.n;
+        std::vector<uint64_t> off(nfr), len(nfr);
+        size_t total = 0;
+        for (size_t k = 0; k < nfr; k++) {
+            const uint8_t *e = m.table + 8 * (size_t)plan.frames[k];
+            off[k] = data_off + get_u32(e); len[k] = get_u32(e + 4);
+            total += (size_t)len[k];
+        }
+        keep.resize(total + 1);
+        pos.assign((size_t)m.n, 0);
+        size_t at = 0;
+        for (size_t i = 0; i < nfr;) {
+            size_t j = i + 1, bytes = (size_t)len[i];
+            while (j < nfr && off[j] == off[j - 1] + len[j - 1]) bytes += (size_t)len[j++];
+            if (read(user, off[i], keep.data() + at, bytes) != 0) return MIC_ERR_IO;
+            for (; i < j; i++) { pos[plan.frames[i]] = at; at += (size_t)len[i]; }
+        }
+        src.device = false;
+        src.blob = [this](uint32_t f) { return (const uint8_t *)keep.data() + pos[f]; };
+        return MIC_OK;
+    }
+};
+
+extern "C" {
+
+int mic_hip_mic2_crop_plan(int width, int height, int nframes, int temporal, const int32_t *xyz, int n, int cw, int ch, int cd,
+                           uint32_t *frames, size_t cap, uint64_t *nframes_out, uint64_t *npieces) try {
+    if (width <= 0 || height <= 0 || nframes < 0 || n < 0 || (n > 0 && !xyz) || cw <= 0 || ch <= 0 || cd <= 0 || (cap > 0 && !frames)) return MIC_ERR_ARGS;
+    CropPlan plan;
+    const int rc = mic2_plan_crops(width, height, nframes, temporal != 0, xyz, n, cw, ch, cd, plan);
+    if (rc) return rc;
+    if (nframes_out) *nframes_out = plan.frames.size();
+    if (npieces) *npieces = plan.pieces.size();
+    if (plan.frames.size() > cap) return MIC_ERR_CAPACITY;
+    std::copy(plan.frames.begin(), plan.frames.end(), frames);
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// n crops of a MIC2 file in host memory, into a tensor on the default session's device
+int mic_hip_mic2_read_crops(const uint8_t *c, size_t len, const int32_t *xyz, int n, int cw, int ch, int cd,
+                            void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+    Mic2Head m;
+    int rc = parse_mic2(c, len, m);
+    if (rc) return rc;
+    m.table = c + 20;
+    return crops_call(nullptr, m, [&](const CropPlan &, Mic2Source &src) {
+        src.device = false;
+        src.blob = [&m, c](uint32_t f) { return c + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
+        return MIC_OK;
+    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+} MIC_ABI_CATCH
+
+int mic_hip_mic2_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len, mic_hip_mic2_reader **out) try {
+    if (!read || !out) return MIC_ERR_ARGS;
+    *out = nullptr;
+    std::unique_ptr<mic_hip_mic2_reader> r(new mic_hip_mic2_reader());
+    r->read = read; r->user = user;
+    if (file_len < 20) return MIC_ERR_CORRUPT;
+    r->head.resize(20);
+    if (read(user, 0, r->head.data(), 20) != 0) return MIC_ERR_IO;
+    int rc = parse_mic2(r->head.data(), file_len, r->m);
+    if (rc) return rc;
+    r->head.resize(20 + 8 * (size_t)r->m.n);
+    if (r->m.n > 0 && read(user, 20, r->head.data() + 20, 8 * (size_t)r->m.n) != 0) return MIC_ERR_IO;
+    r->m.table = r->head.data() + 20;
+    *out = r.release();
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_mic2_reader_info(const mic_hip_mic2_reader *r, int *width, int *height, int *nframes, int *temporal) {
+    if (!r) return MIC_ERR_ARGS;
+    if (width) *width = r->m.w; if (height) *height = r->m.h; if (nframes) *nframes = r->m.n; if (temporal) *temporal = r->m.temporal;
+    return MIC_OK;
+}
+
+int mic_hip_mic2_reader_read_crops(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+    if (!r) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    return crops_call(nullptr, r->m, [&](const CropPlan &plan, Mic2Source &src) { return r->fetch(plan, src); },
+                      xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+} MIC_ABI_CATCH
+
+void mic_hip_mic2_reader_close(mic_hip_mic2_reader *r) { delete r; }
+
+// n crops of a MIC2 file that lies on the session's device: the streams go device to device
+int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, size_t head_len, const uint8_t *d_file, size_t file_len,
+                                    const int32_t *xyz, int n, int cw, int ch, int cd,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+    if (!s || !head) return MIC_ERR_ARGS;
+    if (head_len < 20) return MIC_ERR_CORRUPT;
+    Mic2Head m;
+    int rc = parse_mic2(head, file_len, m);
+    if (rc) return rc;
+    if (head_len < 20 + 8 * (size_t)m.n) return MIC_ERR_ARGS;                            // (the table is not all there)
+    m.table = head + 20;
+    return crops_call(s, m, [&](const CropPlan &plan, Mic2Source &src) {
+        if (!d_file && !plan.frames.empty()) return (int)MIC_ERR_ARGS;
+        src.device = true;
+        src.blob = [&m, d_file](uint32_t f) { return d_file + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
+        return (int)MIC_OK;
+    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+} MIC_ABI_CATCH
+
+}  // extern "C"

@@ -173,6 +173,7 @@ struct mic_hip_session {
     DevBuf wv_a, wv_b;                     // WaveletV2 coefficient planes (int32, two per frame of the batch)
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
+    DevBuf mic2_pieces;                    // MIC2 crops: a call's piece / footprint list (mic_mic2_crops.hip)
     PinnedUnits h_units;
     std::vector<uint64_t> h_off;
     // what an enqueue has already put behind its chain (session_*_finish then only synchronises): the read-back of the descriptors;
@@ -326,13 +327,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -376,6 +377,30 @@ size_t batch_units_for(size_t px, size_t mult, size_t extra = 0);   // units per
 int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nframes, uint16_t max_value,
                            uint8_t *out, size_t out_cap, size_t *out_len);
 int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_total, int n, uint16_t *frames_out);
+// frames per sub-batch of the MIC2 decoders: a unit's tier-2 slabs and its frame on the device, under the workspace ceiling
+size_t mic2_frames_per_batch(size_t npx);
+// residual units r0 .. n-1 must expand to exactly npx symbols (k_tmp_check), behind their chain on `stream`
+void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream);
+// d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
+// pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
+// *d_out becomes the address the device uses.  (mic_mic2_crops.hip)
+int patch_pointer(const mic_hip_session *s, void **d_out, size_t need);
+// MIC2 crops (mic_mic2_crops.hip).  A piece is one (crop, frame) overlap: w x h samples from (sx, sy) of frame `frame` to (dx, dy) of
+// slice dz of crop `crop`, k = the frame's place in the plan's frame list.  The temporal kernel takes one record per crop instead,
+// its footprint: frame = max(z, 0), the crop's first frame inside the volume, dz = that frame's slice, k = its last frame inside it.
+struct CropPiece { int32_t crop, frame, sx, sy, dx, dy, dz, w, h, k; };
+struct CropPlan {
+    std::vector<uint32_t> frames;           // frames whose streams are entropy-decoded, ascending, each once
+    std::vector<CropPiece> pieces;          // sorted by frame (stable: crop order inside a frame)
+    std::vector<CropPiece> prints;          // one per crop with a non-empty overlap, in crop order
+};
+int mic2_plan_crops(int width, int height, int nframes, int temporal, const int32_t *xyz, int n, int cw, int ch, int cd, CropPlan &plan);
+// where the core finds the stream of a frame: blob(frame) -> its first byte, on the host or (device = true) on the session's device
+struct Mic2Source { bool device = false; std::function<const uint8_t *(uint32_t frame)> blob; };
+struct Mic2Head { int w = 0, h = 0, n = 0, temporal = 0; const uint8_t *table = nullptr; uint64_t file_len = 0; };   // table: the 8 n bytes behind the fixed header (host)
+int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need);
+int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
+                    void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // adaptiveStripBoundaries as the reference states it, on the host (mic_pica.hip); cost[y] = rowCost[y], cost[0] ignored
 std::vector<int> pica_boundaries(const std::vector<unsigned long long> &cost, int height, int num_strips);

@@ -12,13 +12,11 @@
 #include "../../include/mic_hip.h"
 #include "mic_session.h"
 #include "mic_launch.h"
+#include "mic_pieces.h"
 
 using namespace micapi;
 
 namespace {
-
-__device__ __forceinline__ uint32_t zigzag16(int32_t v) { const uint32_t x = (uint32_t)v & 0xFFFFu; return ((x << 1) ^ ((x & 0x8000u) ? 0xFFFFu : 0u)) & 0xFFFFu; }   // deltazigzagcompressu16.go:108-111
-__device__ __forceinline__ uint32_t unzigzag16(uint32_t u) { return ((u >> 1) ^ ((u & 1u) ? 0xFFFFu : 0u)) & 0xFFFFu; }                                            // :113-116
 
 // residual symbols of the units r0 .. n-1 into their symbol slabs, their maxima into dec_thr (free on the encode side).  first = the frame
 // of unit 0 on the device; the frame in front of it (unit 0's reference when r0 = 0) lies directly before it.
@@ -58,14 +56,17 @@ __global__ void k_tmp_check(MicUnit *units, int n, uint32_t npx, int r0) {
     if (i < n && units[i].status == MICD_OK && units[i].nsym != npx) units[i].status = MICD_ERR_CORRUPT;
 }
 
-// frames per sub-batch: a unit's tier-2 slabs and its frame on the device, under the workspace ceiling (units are a launch's grid y)
-size_t frames_per_batch(size_t npx) { return std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535)); }
-
 }  // namespace
 
 void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter);   // mic_wavelet.hip
 
 namespace micapi {
+
+// frames per sub-batch: a unit's tier-2 slabs and its frame on the device, under the workspace ceiling (units are a launch's grid y)
+size_t mic2_frames_per_batch(size_t npx) { return std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535)); }
+void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tmp_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_units, n, npx, r0);
+}
 
 // Frames go through in sub-batches under the workspace ceiling.  Encode: a residual needs the ORIGINAL frame before it, so a sub-batch
 // uploads one frame more than it codes (its predecessor's last) and is otherwise independent of the others.  Decode: the running sum
@@ -80,7 +81,7 @@ int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nf
     int rc = lease.acquire();
     if (rc) return rc;
     mic_hip_session *s = cur_default();
-    const size_t per = frames_per_batch(npx);
+    const size_t per = mic2_frames_per_batch(npx);
     std::vector<uint32_t> lens((size_t)nframes);
     uint64_t total = 0;
     memset(out, 0, header);
@@ -139,7 +140,7 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
     int rc = lease.acquire();
     if (rc) return rc;
     mic_hip_session *s = cur_default();
-    const size_t per = frames_per_batch(npx);
+    const size_t per = mic2_frames_per_batch(npx);
     for (size_t f0 = 0; f0 < (size_t)n; f0 += per) {
         const int nb = (int)std::min(per, (size_t)n - f0);
         const int lead = f0 ? 1 : 0;                                      // slot 0 holds the frame in front of the sub-batch
@@ -170,7 +171,7 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
             mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, nullptr, (int *)s->cls.p);
             if (nb > r0) {
                 mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
-                hipLaunchKernelGGL(k_tmp_check, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb, (uint32_t)npx, r0);
+                mic2_launch_residual_check((MicUnit *)s->units.p, nb, (uint32_t)npx, r0, s->stream);
             }
         });
         if (rc) return rc;

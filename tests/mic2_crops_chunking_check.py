@@ -1,0 +1,45 @@
+"""Run by tests/test_gpu_mic2_crops.py::test_sub_batch_seams_under_a_small_workspace in a child process with MIC_HIP_WS_BUDGET_MB set
+small, so that the MIC2 crop calls cut the frames into sub-batches of three: the temporal sum's carry then crosses the seams inside
+the crop tensor, and an independent file's pieces are gathered slab by slab.  Every crop must equal the padded source volume."""
+import importlib, os, sys
+import numpy as np
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as entry
+mic = entry.load_package(); synth = importlib.import_module("medical_image_codec_amd.synth")
+import mic2_crop_volumes as V
+
+assert os.environ.get("MIC_HIP_WS_BUDGET_MB"), "meant to run with a small workspace budget"
+vol, maxv = V.volume_12bit(synth)
+n, h, w = vol.shape
+for temporal in (True, False):
+    data = mic.compress_multi_frame(vol, w, h, maxv, temporal=temporal)
+    assert np.array_equal(mic.decompress_multi_frame(data), vol)
+    m = V.Mic2File(data)
+    rd = mic.Mic2Reader(data)
+    sess = mic.Session(4, w * h)
+    d_file = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    doors = [lambda *a: mic.mic2_read_crops(data, *a), lambda *a: rd.read_crops(*a),
+             lambda *a: sess.mic2_read_crops(m.head(), d_file.data_ptr(), len(data), *a)]
+    for cw, ch, cd in V.SHAPES:
+        # the shared origins hold crops with z < 0; these start behind the first sub-batch, inside the second and the third, and one
+        # spans three seams
+        xyz = V.origins(w, h, n, cw, ch, cd) + [(9, 9, 4), (40, 20, 7), (3, 30, 9), (11, 2, 1)]
+        want = V.expected(vol, xyz, cw, ch, cd)
+        frames, pieces = mic.mic2_crop_plan(w, h, n, temporal, xyz, cw, ch, cd)
+        for k, door in enumerate(doors):
+            t = torch.full((len(xyz), cd, ch, cw, 2), 0xA5, dtype=torch.uint8, device="cuda")
+            st, stats = door(xyz, cw, ch, cd, t.data_ptr(), t.numel())
+            got = t.cpu().numpy().view("<u2")[..., 0]
+            for i in range(len(xyz)):
+                assert np.array_equal(got[i], want[i]), (temporal, k, (cw, ch, cd), xyz[i])
+            assert (st == 0).all() and stats["frames_decoded"] == frames.size and stats["pieces"] == pieces, (temporal, k, stats)
+            assert stats["slabs"] == -(-frames.size // 3) >= 3, (temporal, k, stats)     # three frames a sub-batch
+    # a crop deep in the stack alone: a temporal file still sums from frame 0, an independent one decodes its own frames only
+    t = torch.full((1, 2, 40, 48, 2), 0xA5, dtype=torch.uint8, device="cuda")
+    st, stats = mic.mic2_read_crops(data, [(30, 10, 8)], 48, 40, 2, t.data_ptr(), t.numel())
+    assert np.array_equal(t.cpu().numpy().view("<u2")[..., 0], V.expected(vol, [(30, 10, 8)], 48, 40, 2)) and (st == 0).all()
+    assert (stats["frames_decoded"], stats["slabs"]) == ((10, 4) if temporal else (2, 1)), stats
+    rd.close(); sess.close()
+print("mic2 crop seams ok")
