@@ -358,6 +358,48 @@ int mic_hip_mic2_read_crops(const uint8_t *compressed, size_t compressed_len,
 /* (the reader form, mic_hip_mic2_reader_*, stands with the streaming calls below, the session form,
  * mic_hip_session_mic2_read_crops, with the session calls: they need those sections' types) */
 
+/* ---- strip files: many crops per call --------------------------------------------------------- */
+/* Many 2-D crops of many PICS / PICA files per call, into a tensor that already lives on the device (no reference counterpart;
+ * beside mic_hip_pics_decompress_batch / mic_hip_pica_decompress_batch, which serve whole images through the host, and the MIC3 patch
+ * and MIC2 crop calls, whose semantics carry over).  files[f] (lens[f] bytes, host memory) is a PICS or a PICA file, told apart by its
+ * magic; one call may mix the two kinds, any sizes, strip counts and state flavours.  Crop i is the rectangle [x, x + cw) x [y, y + ch)
+ * of file xyf[3i + 2], (x, y) = xyf[3i .. 3i + 1]; origins may be negative and a crop may overhang its image or lie wholly outside
+ * it: samples outside the image are 0, and so are rows no strip of the header covers, as the whole-image decoders return them.
+ * d_out receives n x ch x cw little-endian u16 -- crop-major, then row, column --, n * ch * cw * 2 bytes, every one of them written.
+ * d_out is memory the device can write: a device allocation on the call's device that is long enough for the tensor, or pinned host
+ * memory (mic_hip_host_alloc); anything else is MIC_ERR_ARGS, found with hipPointerGetAttributes before anything is launched.
+ * A strip is a unit of its own, so only the strips some crop overlaps with non-empty area are uploaded and entropy-decoded, each
+ * once, in sub-batches under the workspace ceiling, each into a slab of decoded strips; behind each sub-batch a kernel writes every
+ * (crop, strip) overlap -- a "piece" -- from the slab into d_out.  A strip is decoded whole, whatever part of it a crop needs.
+ * A file fails alone: one whose header or table mic_hip_pics_info / mic_hip_pica_info refuse, or with an entry the whole-image
+ * decoders refuse -- a byte range outside the file, an empty or inverted row range, length 0 (all MIC_ERR_CORRUPT), a strip of more
+ * than 2^28 pixels (MIC_ERR_UNSUPPORTED) --, or whose pointer is NULL (MIC_ERR_ARGS), gives that code to status[i] of every crop of
+ * it, and those crops are all zero; no other file is affected.  Files no crop names are not looked at.
+ * status[i] (host, may be NULL) is otherwise MIC_OK, or the unit codec's code of the first failing strip, in strip order, among
+ * the strips crop i overlaps with non-empty area; failed_strip[i] (host, may be NULL) that strip's index, else -1.  Such a crop's
+ * samples are unspecified, every other crop is exact.
+ * Returns MIC_OK when the call ran, even if crops failed; n == 0 is MIC_OK; before anything is launched MIC_ERR_ARGS for cw, ch <= 0,
+ * n < 0, nfiles < 0, a NULL array or a file index outside [0, nfiles), and MIC_ERR_CAPACITY for out_cap below the tensor's size.
+ * One device: the calling thread's default session, or the given session (mic_hip_session_strips_read_crops, with the session
+ * calls below); no fan-out over mic_hip_set_devices.  There is no callback-reader form: a strip file's table is a few hundred
+ * bytes, and its reader would be the file form.
+ * stats (may be NULL): strips entropy-decoded and pieces (the plan's counts), strips_total = the strips of the files some crop
+ * names, refused files left out (what whole-image decodes of them would run), slabs = decode chains the call ran. */
+typedef struct { uint64_t strips_decoded, strips_total, pieces, slabs; } mic_hip_strip_crop_stats;
+/* The host planner of those calls: file_of[cap] / strip_of[cap] receive the (file, strip) units whose streams must be
+ * entropy-decoded -- the strips some crop overlaps with non-empty area --, ascending by file, then strip, each once.  *nstrips_out
+ * their number, *npieces the number of (crop, strip) overlaps with non-empty area (both may be NULL).  file_status[nfiles] (may be
+ * NULL): the code of each file as above; MIC_OK for a file no crop names.  More than cap units: MIC_ERR_CAPACITY with the counts
+ * and file_status set and the arrays untouched.  Only the files' headers and tables are read.  Needs no device. */
+int mic_hip_strips_crop_plan(const uint8_t *const *files, const size_t *lens, int nfiles,
+                             const int32_t *xyf, int n, int cw, int ch,
+                             uint32_t *file_of, uint32_t *strip_of, size_t cap,
+                             uint64_t *nstrips_out, uint64_t *npieces, int32_t *file_status);
+int mic_hip_strips_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles,
+                              const int32_t *xyf, int n, int cw, int ch,
+                              void *d_out, size_t out_cap,
+                              int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats);
+
 /* ---- WaveletV2 -------------------------------------------------------------------------------- */
 /* Replaces WaveletV2RLEFSECompressU16 and WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303,
  * :374; identical streams): up to 8 levels of 5/3 integer lifting in Mallat layout, subband scan, zigzag
@@ -643,6 +685,20 @@ int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, siz
                                     const uint8_t *d_file, size_t file_len,
                                     const int32_t *xyz, int n, int cw, int ch, int cd,
                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
+
+/* mic_hip_strips_read_crops on strip files that lie in device memory -- a dataset kept compressed in HBM and sampled from there.
+ * heads[f] (host, head_lens[f] bytes) = at least the header and strip table of file f: its first 20 + 8 * num_strips (PICS) or
+ * 16 + 16 * num_strips (PICA) bytes -- fewer is that file's MIC_ERR_ARGS --; d_files[f] = the whole file (lens[f] bytes) on the
+ * session's device; it may be NULL for a file none of whose strips is needed.  The streams of the plan's strips go device to device
+ * into the session's compressed-input buffer (which keeps the 64 bytes of slack the decode kernels may read past a stream's end; the
+ * caller's allocations owe them nothing) -- nothing but the piece list crosses PCIe.  d_out on the session's device, or pinned host
+ * memory. */
+int mic_hip_session_strips_read_crops(mic_hip_session *s,
+                                      const uint8_t *const *heads, const size_t *head_lens,
+                                      const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                      const int32_t *xyf, int n, int cw, int ch,
+                                      void *d_out, size_t out_cap,
+                                      int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats);
 
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);

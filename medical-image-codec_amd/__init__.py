@@ -116,6 +116,11 @@ class CropStats(C.Structure):
     _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class StripCropStats(C.Structure):
+    """mic_hip_strip_crop_stats"""
+    _fields_ = [("strips_decoded", C.c_uint64), ("strips_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
+
+
 class Unit(C.Structure):
     _fields_ = [("px_offset", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
@@ -133,6 +138,7 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_decompress_frame",
     "mic_hip_mic2_crop_plan", "mic_hip_mic2_read_crops", "mic_hip_mic2_reader_open", "mic_hip_mic2_reader_info",
     "mic_hip_mic2_reader_read_crops", "mic_hip_mic2_reader_close", "mic_hip_session_mic2_read_crops",
+    "mic_hip_strips_crop_plan", "mic_hip_strips_read_crops", "mic_hip_session_strips_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
     "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
@@ -306,6 +312,11 @@ def lib() -> C.CDLL:
     L.mic_hip_mic2_reader_close.argtypes = [C.c_void_p]
     L.mic_hip_mic2_reader_close.restype = None
     L.mic_hip_session_mic2_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + _crop_args
+    _strip_crop_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(StripCropStats)]
+    L.mic_hip_strips_crop_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.mic_hip_strips_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _strip_crop_args
+    L.mic_hip_session_strips_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + _strip_crop_args
     L.mic_hip_wavelet_v2_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_wavelet_v2_compress_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
@@ -747,6 +758,81 @@ def mic2_read_crops(compressed, xyz, cw: int, ch: int, cd: int, d_out: int, out_
     if rc:
         _raise(rc, "mic2_read_crops")
     return st, stats
+
+
+# ------------------------------------------------------------------ strip files: many crops per call
+def strips_head(file) -> bytes:
+    """The header and strip table of a PICS or PICA file: its first 20 + 8 * num_strips / 16 + 16 * num_strips bytes -- what
+    Session.strips_read_crops takes as `heads` while the file itself lies in device memory."""
+    c = _bytes_arr(file)
+    pica = c[:4].tobytes() == b"PICA"
+    w, h, n = C.c_int(), C.c_int(), C.c_int()
+    rc = (lib().mic_hip_pica_info(c.ctypes.data, c.size, C.byref(w), C.byref(h), C.byref(n)) if pica else
+          lib().mic_hip_pics_info(c.ctypes.data, c.size, C.byref(w), C.byref(h), C.byref(n), None))
+    if rc:
+        _raise(rc, "strips_head")
+    return c[: 16 + 16 * n.value if pica else 20 + 8 * n.value].tobytes()
+
+
+def _crop_xyf(xyf) -> np.ndarray:
+    """(n, 3) crop origins and file indices (x, y, file) as the int32 triples the C calls take"""
+    return np.ascontiguousarray(np.asarray(xyf, dtype=np.int64).reshape(-1, 3).astype(np.int32))
+
+
+def _file_table(files):
+    """the (pointer, length) arrays of a list of host buffers, and the arrays that keep the buffers alive"""
+    arrs = [_bytes_arr(f) for f in files]
+    ptrs = np.asarray([a.ctypes.data for a in arrs], dtype=np.uintp)
+    lens = np.asarray([a.size for a in arrs], dtype=np.uintp)
+    return arrs, ptrs, lens
+
+
+def strips_crop_plan(files, xyf, cw: int, ch: int, cap: Optional[int] = None):
+    """mic_hip_strips_crop_plan: ((n, 2) uint32 array of the (file, strip) units the crops need entropy-decoded -- ascending by file,
+    then strip, each once --, number of (crop, strip) pieces, int32 status of each file).  Needs no device.  cap: room for that many
+    units (default: as many as it takes); too few raises MicError (MIC_ERR_CAPACITY) whose ``nstrips``, ``pieces`` and
+    ``file_status`` attributes are the counts and the files' codes."""
+    arrs, ptrs, lens = _file_table(files)
+    a = _crop_xyf(xyf)
+    ns, npc = C.c_uint64(0), C.c_uint64(0)
+    fs = np.zeros(max(len(arrs), 1), dtype=np.int32)
+    if cap is None:
+        rc = lib().mic_hip_strips_crop_plan(ptrs.ctypes.data, lens.ctypes.data, len(arrs), a.ctypes.data, len(a), cw, ch, None, None, 0,
+                                            C.byref(ns), C.byref(npc), fs.ctypes.data)
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "strips_crop_plan")
+        cap = ns.value
+    file_of, strip_of = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+    rc = lib().mic_hip_strips_crop_plan(ptrs.ctypes.data, lens.ctypes.data, len(arrs), a.ctypes.data, len(a), cw, ch,
+                                        file_of.ctypes.data, strip_of.ctypes.data, cap, C.byref(ns), C.byref(npc), fs.ctypes.data)
+    if rc:
+        e = MicError(rc, "strips_crop_plan")
+        e.nstrips, e.pieces, e.file_status = ns.value, npc.value, fs[: len(arrs)].copy()
+        raise e
+    return np.stack([file_of[: ns.value], strip_of[: ns.value]], axis=1), npc.value, fs[: len(arrs)].copy()
+
+
+def _read_strip_crops(call, xyf, d_out: int, out_cap: int):
+    a = _crop_xyf(xyf)
+    st = np.zeros(len(a), dtype=np.int32)
+    bad = np.full(len(a), -1, dtype=np.int32)
+    cs = StripCropStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, bad.ctypes.data, C.byref(cs))
+    return rc, st, bad, dict(strips_decoded=cs.strips_decoded, strips_total=cs.strips_total, pieces=cs.pieces, slabs=cs.slabs)
+
+
+def strips_read_crops(files, xyf, cw: int, ch: int, d_out: int, out_cap: int):
+    """mic_hip_strips_read_crops: the cw x ch crops at the (x, y, file) triples `xyf` of the PICS / PICA files `files` (host
+    buffers; file = an index into the list), into the caller's device tensor d_out (an int:
+    ``torch.empty((n, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned host memory) of out_cap bytes.  Samples
+    outside an image are 0.  Only the strips the crops overlap are uploaded and decoded.
+    -> (status per crop, failed strip per crop (-1: none), dict(strips_decoded, strips_total, pieces, slabs))."""
+    arrs, ptrs, lens = _file_table(files)
+    rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_strips_read_crops(
+        ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, cw, ch, d, cap, s, b, p), xyf, d_out, out_cap)
+    if rc:
+        _raise(rc, "strips_read_crops")
+    return st, bad, stats
 
 
 # ------------------------------------------------------------------ WaveletV2
@@ -1554,3 +1640,19 @@ class Session:
         if rc:
             _raise(rc, "session_mic2_read_crops")
         return st, stats
+
+    def strips_read_crops(self, heads, d_files, lens, xyf, cw: int, ch: int, d_out: int, out_cap: int):
+        """strips_read_crops of PICS / PICA files that lie on the session's device: heads[f] = strips_head(file f) (host),
+        d_files[f] = the device address of the whole file, lens[f] its length.  The streams of the needed strips go device to
+        device."""
+        harrs, hptrs, hlens = _file_table(heads)
+        dptrs = np.asarray([int(p) for p in d_files], dtype=np.uintp)
+        flens = np.asarray([int(n) for n in lens], dtype=np.uintp)
+        if not (len(harrs) == dptrs.size == flens.size):
+            raise ValueError("heads, d_files and lens must name the same files")
+        rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_session_strips_read_crops(
+            self._h, hptrs.ctypes.data, hlens.ctypes.data, dptrs.ctypes.data, flens.ctypes.data, len(harrs), a, n, cw, ch, d, cap, s, b, p),
+            xyf, d_out, out_cap)
+        if rc:
+            _raise(rc, "session_strips_read_crops")
+        return st, bad, stats

@@ -625,8 +625,8 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
 
 // ============================================================================ strip files: PICS (parallelstrips.go), PICA (parallelstripsadaptive.go)
 // The batch decoder of both: a file is a header and one unit per strip.  info: the file's width, height and strip count;
-// entry(c, h, n, k): strip k as its header states it; pica: the call is a PICA one (-DMIC_PICA_TIMING builds time those).
-struct StripEntry { long y0, y1; size_t start, len; uint16_t flags; };   // rows [y0, y1), bytes [start, start + len) of the file, the unit's flags
+// entry(c, h, n, k): strip k as its header states it (pics_strip_entry / pica_strip_entry, mic_session.h); pica: the call is a PICA
+// one (-DMIC_PICA_TIMING builds time those).
 template <class Job, class Info, class Entry>
 int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry entry) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
@@ -645,11 +645,7 @@ int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry en
         int32_t bad = MIC_OK; size_t covered = 0;
         for (int k = 0; k < n && bad == MIC_OK; k++) {
             const StripEntry e = entry(j.compressed, h, n, k);
-            const size_t end = e.start + e.len;
-            if (end > j.compressed_len || e.start > end) { bad = MIC_ERR_CORRUPT; break; }    // parallelstrips.go:300-304, parallelstripsadaptive.go:186-190
-            if (e.y0 < 0 || e.y1 <= e.y0 || e.y1 > h) { bad = MIC_ERR_CORRUPT; break; }       // Go: make / slice panics
-            if (e.len == 0) { bad = MIC_ERR_CORRUPT; break; }
-            if ((size_t)w * (size_t)(e.y1 - e.y0) > ((size_t)1 << 28)) { bad = MIC_ERR_UNSUPPORTED; break; }
+            if ((bad = strip_entry_check(e, w, h, j.compressed_len))) break;
             U.push_back(DecUnit{ e.start, e.len, (uint64_t)e.y0 * (uint64_t)w, w, (int32_t)(e.y1 - e.y0), e.flags, (int)G.size() });
             covered += (size_t)w * (size_t)(e.y1 - e.y0);
         }
@@ -891,11 +887,7 @@ int mic_hip_pics_compress_ex(const uint16_t *pixels, int width, int height, uint
 
 int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs) try {
     return strips_decompress_batch(jobs, njobs, false,
-        [](const uint8_t *c, size_t len, int *w, int *h, int *n) { return mic_hip_pics_info(c, len, w, h, n, nullptr); },
-        [](const uint8_t *c, int h, int n, int k) {                            // strip k: strip_height rows from k * strip_height (:288-304)
-            const long sh = (long)get_u32(c + 16), y0 = k * sh;
-            return StripEntry{ y0, std::min<long>(h, y0 + sh), 20 + (size_t)n * 8 + get_u32(c + 20 + (size_t)k * 8), get_u32(c + 24 + (size_t)k * 8), 0 };
-        });
+        [](const uint8_t *c, size_t len, int *w, int *h, int *n) { return mic_hip_pics_info(c, len, w, h, n, nullptr); }, pics_strip_entry);
 } MIC_ABI_CATCH
 
 int mic_hip_pics_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {
@@ -1010,12 +1002,7 @@ int mic_hip_pica_boundaries(const uint16_t *pixels, int width, int height, int n
 } MIC_ABI_CATCH
 
 int mic_hip_pica_decompress_batch(mic_hip_pica_dec_job *jobs, int njobs) try {
-    return strips_decompress_batch(jobs, njobs, true, mic_hip_pica_info,
-        [](const uint8_t *c, int h, int n, int k) {                            // strip k: from its y0 to the next strip's (:186-202)
-            const uint8_t *e = c + 16 + (size_t)k * 16;
-            return StripEntry{ (long)get_u32(e), (k + 1 < n) ? (long)get_u32(e + 16) : h, 16 + (size_t)n * 16 + get_u32(e + 4), get_u32(e + 8),
-                               (uint16_t)(2 | ((get_u32(e + 12) & 1u) ? MIC_HIP_PRED_GRAD : 0)) };   // picaFlagGradPredictor
-        });
+    return strips_decompress_batch(jobs, njobs, true, mic_hip_pica_info, pica_strip_entry);
 } MIC_ABI_CATCH
 
 // DecompressParallelStripsAdaptive (parallelstripsadaptive.go:141-214): a batch of one

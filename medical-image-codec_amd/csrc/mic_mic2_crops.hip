@@ -76,14 +76,6 @@ __global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *un
     }
 }
 
-// rows of a piece per block pass = 256 / lanes per row; grid y cuts pieces of more than 16 passes
-unsigned row_chunks(int w, int h) {
-    int lw = 1;
-    while (lw < w && lw < 64) lw *= 2;
-    const int passes = (h + 256 / lw - 1) / (256 / lw) * ((w + 63) / 64);
-    return (unsigned)std::min(16, std::max(1, passes / 16));
-}
-
 }  // namespace
 
 namespace micapi {

@@ -174,6 +174,7 @@ struct mic_hip_session {
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
     DevBuf mic2_pieces;                    // MIC2 crops: a call's piece / footprint list (mic_mic2_crops.hip)
+    DevBuf strip_pieces;                   // strip-file crops: a call's piece list (mic_strip_crops.hip)
     PinnedUnits h_units;
     std::vector<uint64_t> h_off;
     // what an enqueue has already put behind its chain (session_*_finish then only synchronises): the read-back of the descriptors;
@@ -327,13 +328,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -402,6 +403,28 @@ int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch,
 int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
                     void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
+// Strip files (PICS: parallelstrips.go, PICA: parallelstripsadaptive.go): a header, a table and one unit per strip.  Strip k of a
+// file of height h and n strips as its header states it -- rows [y0, y1), bytes [start, start + len) of the file, the unit's flags --
+// read from the header and the table alone; what the whole-image decoders (mic_host_io.hip) and the crop calls (mic_strip_crops.hip) decode by.
+struct StripEntry { long y0, y1; size_t start, len; uint16_t flags; };
+inline StripEntry pics_strip_entry(const uint8_t *c, int h, int n, int k) {       // strip_height rows from k * strip_height (:288-304)
+    const long sh = (long)get_u32(c + 16), y0 = k * sh;
+    return StripEntry{ y0, std::min<long>(h, y0 + sh), 20 + (size_t)n * 8 + get_u32(c + 20 + (size_t)k * 8), get_u32(c + 24 + (size_t)k * 8), 0 };
+}
+inline StripEntry pica_strip_entry(const uint8_t *c, int h, int n, int k) {       // from its y0 to the next strip's (:186-202)
+    const uint8_t *e = c + 16 + (size_t)k * 16;
+    return StripEntry{ (long)get_u32(e), (k + 1 < n) ? (long)get_u32(e + 16) : h, 16 + (size_t)n * 16 + get_u32(e + 4), get_u32(e + 8),
+                       (uint16_t)(2 | ((get_u32(e + 12) & 1u) ? MIC_HIP_PRED_GRAD : 0)) };   // picaFlagGradPredictor
+}
+// what a decoder asks of an entry of a w x h file of file_len bytes before it decodes the strip: MIC_OK, or the file's code
+inline int strip_entry_check(const StripEntry &e, int w, int h, size_t file_len) {
+    const size_t end = e.start + e.len;
+    if (end > file_len || e.start > end) return MIC_ERR_CORRUPT;                 // parallelstrips.go:300-304, parallelstripsadaptive.go:186-190
+    if (e.y0 < 0 || e.y1 <= e.y0 || e.y1 > h) return MIC_ERR_CORRUPT;            // Go: make / slice panics
+    if (e.len == 0) return MIC_ERR_CORRUPT;
+    if ((size_t)w * (size_t)(e.y1 - e.y0) > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
+    return MIC_OK;
+}
 // adaptiveStripBoundaries as the reference states it, on the host (mic_pica.hip); cost[y] = rowCost[y], cost[0] ignored
 std::vector<int> pica_boundaries(const std::vector<unsigned long long> &cost, int height, int num_strips);
 // one blocking host <-> device copy through the transfer engine of mic_host_io.hip (pinned host memory: DMA in place; ordinary

@@ -1,0 +1,319 @@
+// mic_strip_crops.hip -- strip files (PICS, PICA): many 2-D crops of many files per call into a device tensor
+// (mic_hip_strips_crop_plan, mic_hip_strips_read_crops, mic_hip_session_strips_read_crops; no reference counterpart).
+//
+// One core (strips_read_crops) behind the two doors; a door brings, per file, the bytes its header and table are read from and the
+// address its streams are copied from (the caller's file, a file in device memory).  The host plans (strips_plan_crops): a strip is a
+// unit of its own, so a crop needs the strips it overlaps and no others -- the plan is those (file, strip) units, each once, and the
+// (crop, strip) overlaps, pieces.  The units go through the unit codec in sub-batches under the workspace ceiling, each into a slab
+// of decoded strips, and behind each sub-batch k_strips_gather_crops copies its pieces out of the slab into the crop tensor.
+#include "mic_session.h"
+#include "mic_pieces.h"
+
+namespace {
+
+// One (crop, strip) overlap: w x h samples from (sx, sy) of a decoded strip of fw samples a row, which starts `src` samples into its
+// sub-batch's slab, to (dx, dy) of crop `crop`.
+struct StripPiece { uint64_t src; int32_t crop, fw, sx, sy, dx, dy, w, h; };
+
+// slab: a sub-batch's decoded strips; out: [crop][ch][cw] u16.  grid = (pieces, row chunks); lanes along x (piece_lanes).  A row whose
+// source and destination are both 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16: with an
+// odd image or crop width every second row is such a row (as k_mic2_gather_crops).
+__global__ void __launch_bounds__(256) k_strips_gather_crops(const uint16_t *slab, const StripPiece *pieces, uint16_t *out, int cw, int ch) {
+    const StripPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const uint16_t *src = slab + pc.src + (size_t)pc.sy * pc.fw + pc.sx;
+    uint16_t *dst = out + ((size_t)pc.crop * ch + pc.dy) * cw + pc.dx;
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * pc.fw);
+        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
+        if ((((size_t)s | (size_t)d) & 3) == 0) {
+            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
+            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
+            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
+            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = s[pc.w - 1];
+        } else
+            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = s[x];
+    }
+}
+
+// a file of the call: where its header and table are read (host) and what they said
+struct StripFile {
+    const uint8_t *head = nullptr; size_t head_len = 0, len = 0;
+    bool named = false;                     // some crop names it: only then is it looked at
+    int32_t status = MIC_OK;
+    int w = 0, h = 0, n = 0;
+    std::vector<StripEntry> e;              // its strips (status == MIC_OK): rows ascending and disjoint, which strip_entry_check's non-empty ranges make them in both containers
+    std::vector<uint32_t> count;            // pieces of each strip, then the strip's unit (kNoUnit: no crop overlaps it)
+};
+constexpr uint32_t kNoUnit = 0xFFFFFFFFu;
+struct StripUnit { uint32_t file, strip; };
+struct PlannedPiece { int32_t crop; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
+struct StripPlan {
+    std::vector<StripFile> files;
+    std::vector<StripUnit> units;           // the strips to entropy-decode, ascending by file, then strip, each once
+    std::vector<PlannedPiece> pieces;       // sorted by unit (stable: crop order inside a unit)
+    uint64_t strips_total = 0;              // strips of the files some crop names
+};
+
+// header and table of file f: PICS or PICA by the magic, the checks of mic_hip_pics_info / mic_hip_pica_info against the whole file's
+// length and those the whole-image decoders make of every entry (strip_entry_check)
+void parse_strip_file(StripFile &f) {
+    f.status = MIC_OK;
+    if (!f.head) { f.status = MIC_ERR_ARGS; return; }
+    if (f.head_len < 16) { f.status = MIC_ERR_CORRUPT; return; }
+    const bool pica = memcmp(f.head, "PICA", 4) == 0;
+    if (!pica && f.head_len < 20) { f.status = MIC_ERR_CORRUPT; return; }
+    f.status = pica ? mic_hip_pica_info(f.head, f.len, &f.w, &f.h, &f.n) : mic_hip_pics_info(f.head, f.len, &f.w, &f.h, &f.n, nullptr);
+    if (f.status) return;
+    if (f.head_len < (pica ? 16 + 16 * (size_t)f.n : 20 + 8 * (size_t)f.n)) { f.status = MIC_ERR_ARGS; return; }   // (the table is not all there)
+    f.e.resize((size_t)f.n);
+    for (int k = 0; k < f.n && f.status == MIC_OK; k++) {
+        f.e[(size_t)k] = pica ? pica_strip_entry(f.head, f.h, f.n, k) : pics_strip_entry(f.head, f.h, f.n, k);
+        f.status = strip_entry_check(f.e[(size_t)k], f.w, f.h, f.len);
+    }
+    if (f.status) f.e.clear();
+}
+
+// The plan of n crops of cw x ch over the files (head, head_len, len set by the caller).  MIC_ERR_ARGS for a file index outside the
+// list; a file that is refused keeps its code in files[f].status and its crops have no pieces.
+int strips_plan_crops(StripPlan &plan, const int32_t *xyf, int n, int cw, int ch) {
+    const int nfiles = (int)plan.files.size();
+    plan.units.clear(); plan.pieces.clear(); plan.strips_total = 0;
+    for (int i = 0; i < n; i++) {
+        const int32_t f = xyf[3 * (size_t)i + 2];
+        if (f < 0 || f >= nfiles) return MIC_ERR_ARGS;
+        plan.files[(size_t)f].named = true;
+    }
+    for (StripFile &f : plan.files) {
+        if (!f.named) continue;
+        parse_strip_file(f);
+        if (f.status == MIC_OK) { plan.strips_total += (uint64_t)f.n; f.count.assign((size_t)f.n, 0); }
+    }
+    // the strips [k0, k1) crop i overlaps with non-empty area, and its clipped columns and rows
+    struct Clip { int64_t x0, x1, y0, y1; size_t k0, k1; };
+    auto clip = [&](int i, Clip &c) {
+        const StripFile &f = plan.files[(size_t)xyf[3 * (size_t)i + 2]];
+        if (f.status != MIC_OK) return false;
+        const int64_t x = xyf[3 * (size_t)i], y = xyf[3 * (size_t)i + 1];
+        c.x0 = std::max<int64_t>(x, 0); c.x1 = std::min<int64_t>(x + cw, f.w); c.y0 = std::max<int64_t>(y, 0); c.y1 = std::min<int64_t>(y + ch, f.h);
+        if (c.x1 <= c.x0 || c.y1 <= c.y0) return false;
+        c.k0 = (size_t)(std::partition_point(f.e.begin(), f.e.end(), [&](const StripEntry &e) { return e.y1 <= c.y0; }) - f.e.begin());
+        c.k1 = (size_t)(std::partition_point(f.e.begin(), f.e.end(), [&](const StripEntry &e) { return e.y0 < c.y1; }) - f.e.begin());
+        return c.k0 < c.k1;
+    };
+    Clip c;
+    for (int i = 0; i < n; i++)
+        if (clip(i, c)) for (size_t k = c.k0; k < c.k1; k++) plan.files[(size_t)xyf[3 * (size_t)i + 2]].count[k]++;
+    std::vector<size_t> first;                                                              // unit -> its first piece, then the next free one
+    size_t total = 0;
+    for (size_t fi = 0; fi < plan.files.size(); fi++) {
+        StripFile &f = plan.files[fi];
+        for (size_t k = 0; k < f.count.size(); k++) {
+            const uint32_t cnt = f.count[k];
+            f.count[k] = cnt ? (uint32_t)plan.units.size() : kNoUnit;
+            if (!cnt) continue;
+            if (plan.units.size() >= kNoUnit - 1) return MIC_ERR_UNSUPPORTED;
+            plan.units.push_back(StripUnit{ (uint32_t)fi, (uint32_t)k });
+            first.push_back(total);
+            total += cnt;
+        }
+    }
+    plan.pieces.resize(total);
+    for (int i = 0; i < n; i++) {
+        if (!clip(i, c)) continue;
+        const StripFile &f = plan.files[(size_t)xyf[3 * (size_t)i + 2]];
+        const int64_t x = xyf[3 * (size_t)i], y = xyf[3 * (size_t)i + 1];
+        for (size_t k = c.k0; k < c.k1; k++) {
+            const StripEntry &e = f.e[k];
+            const int64_t r0 = std::max<int64_t>(c.y0, e.y0), r1 = std::min<int64_t>(c.y1, e.y1);
+            plan.pieces[first[f.count[k]]++] = PlannedPiece{ i, f.count[k], (int32_t)c.x0, (int32_t)(r0 - e.y0), (int32_t)(c.x0 - x), (int32_t)(r0 - y),
+                                                             (int32_t)(c.x1 - c.x0), (int32_t)(r1 - r0) };
+        }
+    }
+    return MIC_OK;
+}
+
+// what the entry points check of their arguments before a file is looked at
+int strips_crop_args(const void *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch) {
+    if (cw <= 0 || ch <= 0 || n < 0 || nfiles < 0 || (n > 0 && !xyf) || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
+    return MIC_OK;
+}
+
+// Units [i0, i1) of the next sub-batch: as many as the workspace ceiling holds of the largest of them -- a unit's tier-2 slabs and its
+// strip in the staging slab, as mic2_frames_per_batch counts a frame -- and at most what one launch chain takes.
+size_t next_strip_cut(const std::vector<size_t> &px, size_t i0) {
+    size_t max_px = 0, i1 = i0;
+    while (i1 < px.size()) {
+        const size_t mp = std::max(max_px, px[i1]);
+        if (i1 > i0 && (i1 - i0 + 1 > kWorkspaceBudget / (unit_ws_bytes(mp) + 2 * mp) || i1 - i0 >= 65535)) break;
+        max_px = mp; i1++;
+    }
+    return i1;
+}
+
+// n crops into d_out ([n][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
+// current.  base[f]: where file f's bytes lie -- on the host, or (device) on the session's device.
+int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *const *base, bool device, int n, int cw, int ch,
+                      void *d_out, size_t need, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
+    const size_t nu = plan.units.size();
+    int rc;
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the images, rows no strip covers, refused files
+    auto entry = [&](size_t u) -> const StripEntry & { return plan.files[plan.units[u].file].e[plan.units[u].strip]; };
+    std::vector<size_t> px(nu), cuts{ 0 };
+    for (size_t u = 0; u < nu; u++) px[u] = (size_t)plan.files[plan.units[u].file].w * (size_t)(entry(u).y1 - entry(u).y0);
+    while (cuts.back() < nu) cuts.push_back(next_strip_cut(px, cuts.back()));
+    // every unit's place in its sub-batch's slab, the largest slab and the most stream bytes of a sub-batch
+    std::vector<uint64_t> slab_off(nu);
+    size_t slab_max = 0, comp_max = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        size_t off = 0, comp = 0;
+        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += px[u]; comp += entry(u).len; }
+        slab_max = std::max(slab_max, off); comp_max = std::max(comp_max, comp);
+    }
+    std::vector<size_t> first(nu + 1, 0);                                                   // the pieces of unit u
+    std::vector<StripPiece> list(plan.pieces.size());
+    int mw = 1, mh = 1;
+    for (size_t q = 0; q < plan.pieces.size(); q++) {
+        const PlannedPiece &p = plan.pieces[q];
+        first[(size_t)p.unit + 1]++;
+        list[q] = StripPiece{ slab_off[p.unit], p.crop, plan.files[plan.units[p.unit].file].w, p.sx, p.sy, p.dx, p.dy, p.w, p.h };
+        mw = std::max(mw, p.w); mh = std::max(mh, p.h);
+    }
+    for (size_t u = 0; u < nu; u++) first[u + 1] += first[u];
+    if (nu) {
+        if ((rc = s->strip_pieces.reserve(list.size() * sizeof(StripPiece)))) return rc;
+        if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (+ what the decode kernels may read past a stream's end)
+        if ((rc = s->io_px.reserve(slab_max * 2 + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->strip_pieces.p, list.data(), list.size() * sizeof(StripPiece), hipMemcpyHostToDevice, s->stream));
+    }
+    const StripPiece *d_list = (const StripPiece *)s->strip_pieces.p;
+    const unsigned gy = row_chunks(mw, mh);
+    std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
+    std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        const size_t u0 = cuts[b];
+        const int nb = (int)(cuts[b + 1] - u0);
+        // the sub-batch's streams back to back in the compressed-input buffer, neighbours in the source in one copy
+        begins.assign((size_t)nb, 0); ends.assign((size_t)nb, 0); units.resize((size_t)nb);
+        uint64_t total = 0;
+        for (int i = 0; i < nb; i++) {
+            const StripEntry &e = entry(u0 + (size_t)i);
+            begins[(size_t)i] = total; total += e.len; ends[(size_t)i] = total;
+            units[(size_t)i] = mic_hip_unit{ slab_off[u0 + (size_t)i], plan.files[plan.units[u0 + (size_t)i].file].w, (int32_t)(e.y1 - e.y0), 0, e.flags };
+        }
+        for (int i = 0; i < nb;) {
+            const uint32_t fi = plan.units[u0 + (size_t)i].file;
+            const size_t start = entry(u0 + (size_t)i).start;
+            size_t bytes = entry(u0 + (size_t)i).len;
+            int j = i + 1;
+            while (j < nb && plan.units[u0 + (size_t)j].file == fi && entry(u0 + (size_t)j).start == start + bytes) bytes += entry(u0 + (size_t)j++).len;
+            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + begins[(size_t)i], base[fi] + start, bytes, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+            i = j;
+        }
+        if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
+        if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
+        const size_t p0 = first[u0], np = first[u0 + (size_t)nb] - p0;
+        s->timer.reset(s->stream); s->timer.mark("k_strips_gather_crops");
+        for (size_t q = 0; q < np; q += 0x7FFFFFFF)
+            hipLaunchKernelGGL(k_strips_gather_crops, dim3((unsigned)std::min<size_t>(np - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
+                               (const uint16_t *)s->io_px.p, d_list + p0 + q, (uint16_t *)d_out, cw, ch);
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (int i = 0; i < n; i++) {
+        if (status) status[i] = MIC_OK;
+        if (failed_strip) failed_strip[i] = -1;
+    }
+    std::vector<char> failed(status || failed_strip ? (size_t)n : 0, 0);                   // (pieces are in strip order inside a crop's file)
+    for (const PlannedPiece &p : plan.pieces) {
+        if (failed.empty() || failed[(size_t)p.crop] || ust[p.unit] == MIC_OK) continue;
+        failed[(size_t)p.crop] = 1;
+        if (status) status[p.crop] = ust[p.unit];
+        if (failed_strip) failed_strip[p.crop] = (int32_t)plan.units[p.unit].strip;
+    }
+    if (stats) *stats = mic_hip_strip_crop_stats{ nu, plan.strips_total, plan.pieces.size(), cuts.size() - 1 };
+    return MIC_OK;
+}
+
+// a refused file's code for each of its crops (which have no pieces: their samples stay 0)
+void file_codes(const StripPlan &plan, const int32_t *xyf, int n, int32_t *status) {
+    if (!status) return;
+    for (int i = 0; i < n; i++) {
+        const int32_t fs = plan.files[(size_t)xyf[3 * (size_t)i + 2]].status;
+        if (fs != MIC_OK) status[i] = fs;
+    }
+}
+
+// a door's call: arguments, n == 0, the plan, the pointer, then the core on session s (leased here when s is NULL)
+int strips_call(mic_hip_session *s, StripPlan &plan, const uint8_t *const *base, bool device, const int32_t *xyf, int n, int cw, int ch,
+                void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
+    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ch * (unsigned)cw * 2;
+    if (bytes > out_cap) return MIC_ERR_CAPACITY;
+    const size_t need = (size_t)bytes;
+    int rc = strips_plan_crops(plan, xyf, n, cw, ch);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_strip_crop_stats{ 0, 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    if (device) for (const StripUnit &u : plan.units) if (!base[u.file]) return MIC_ERR_ARGS;    // (a file whose strips are needed is not there)
+    DefaultLease lease;
+    if (!s) { if ((rc = lease.acquire())) return rc; s = cur_default(); }
+    else if ((rc = s->activate())) return rc;
+    rc = patch_pointer(s, &d_out, need);                                                    // judged before anything is launched
+    if (rc == MIC_ERR_CAPACITY || ((size_t)d_out & 1)) rc = MIC_ERR_ARGS;                   // (out_cap held the tensor: it is the allocation that does not)
+    if (rc) return rc;
+    if ((rc = strips_read_crops(s, plan, base, device, n, cw, ch, d_out, need, status, failed_strip, stats))) return rc;
+    file_codes(plan, xyf, n, status);
+    return MIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mic_hip_strips_crop_plan(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                             uint32_t *file_of, uint32_t *strip_of, size_t cap, uint64_t *nstrips_out, uint64_t *npieces, int32_t *file_status) try {
+    int rc = strips_crop_args(files, lens, nfiles, xyf, n, cw, ch);
+    if (rc) return rc;
+    if (cap > 0 && (!file_of || !strip_of)) return MIC_ERR_ARGS;
+    StripPlan plan;
+    plan.files.resize((size_t)nfiles);
+    for (int f = 0; f < nfiles; f++) { plan.files[(size_t)f].head = files[f]; plan.files[(size_t)f].head_len = plan.files[(size_t)f].len = lens[f]; }
+    if ((rc = strips_plan_crops(plan, xyf, n, cw, ch))) return rc;
+    if (file_status) for (int f = 0; f < nfiles; f++) file_status[f] = plan.files[(size_t)f].status;
+    if (nstrips_out) *nstrips_out = plan.units.size();
+    if (npieces) *npieces = plan.pieces.size();
+    if (plan.units.size() > cap) return MIC_ERR_CAPACITY;
+    for (size_t u = 0; u < plan.units.size(); u++) { file_of[u] = plan.units[u].file; strip_of[u] = plan.units[u].strip; }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// n crops of strip files in host memory, into a tensor on the default session's device
+int mic_hip_strips_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                              void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) try {
+    const int rc = strips_crop_args(files, lens, nfiles, xyf, n, cw, ch);
+    if (rc) return rc;
+    StripPlan plan;
+    plan.files.resize((size_t)nfiles);
+    for (int f = 0; f < nfiles; f++) { plan.files[(size_t)f].head = files[f]; plan.files[(size_t)f].head_len = plan.files[(size_t)f].len = lens[f]; }
+    return strips_call(nullptr, plan, files, false, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats);
+} MIC_ABI_CATCH
+
+// n crops of strip files that lie on the session's device: the streams go device to device
+int mic_hip_session_strips_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                      const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                      const int32_t *xyf, int n, int cw, int ch,
+                                      void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) try {
+    if (!s) return MIC_ERR_ARGS;
+    const int rc = strips_crop_args(heads, lens, nfiles, xyf, n, cw, ch);
+    if (rc) return rc;
+    if (nfiles > 0 && (!head_lens || !d_files)) return MIC_ERR_ARGS;
+    StripPlan plan;
+    plan.files.resize((size_t)nfiles);
+    for (int f = 0; f < nfiles; f++) { plan.files[(size_t)f].head = heads[f]; plan.files[(size_t)f].head_len = head_lens[f]; plan.files[(size_t)f].len = lens[f]; }
+    return strips_call(s, plan, d_files, true, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats);
+} MIC_ABI_CATCH
+
+}  // extern "C"
