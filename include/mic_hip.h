@@ -575,6 +575,40 @@ int mic_hip_rgb_decompress(const uint8_t *compressed, size_t compressed_len, int
 int mic_hip_micr_compress(const uint8_t *rgb, int width, int height, uint8_t *out, size_t out_cap, size_t *out_len);
 int mic_hip_micr_info(const uint8_t *compressed, size_t compressed_len, int *width, int *height);
 int mic_hip_micr_decompress(const uint8_t *compressed, size_t compressed_len, uint8_t *rgb_out, size_t out_cap);
+/* Many RGB images of any sizes, one call (rgbcompress.go:25-33; compressRGBTileBlob / decompressRGBTileBlob, wsicompress.go:319-363,
+ * 431-475): the reference reaches this by calling CompressRGB from many goroutines -- the frames of an ultrasound cine loop, a
+ * directory of visible-light images.  A sub-batch's images come up once, one kernel runs YCoCg-R over all of them and finds every
+ * plane's {min, max}, the host picks the plane modes (compressWSIPlane, :373-421), ONE unit batch codes every non-constant plane, a
+ * kernel assembles the blobs and each job's bytes go down in one copy.  Through the pipeline of the other batches: sub-batches under
+ * the workspace ceiling with the transfers of one overlapping the kernels of its neighbours, pinned buffers sent in place,
+ * mic_hip_set_devices shards by pixels.  Every job's bytes equal mic_hip_rgb_compress's (container 0) or mic_hip_micr_compress's
+ * (container 1), byte for byte.  The return value is MIC_OK when the batch ran; a job with bad arguments, a buffer too small, a
+ * corrupt blob or a failing plane fails alone: status, and failed_plane = the plane the error is about (0 Y, 1 Co, 2 Cg -- the
+ * reference's "Y plane: %w", :339-347, :448-460), -1 when it is not a plane's.
+ * out_cap >= MIC_HIP_RGB_BOUND(width * height) (+ 12 for a MICR file) is always sufficient: three raw planes. */
+#define MIC_HIP_RGB_BOUND(npx) (12 + 3 * (1 + 2 * (size_t)(npx)))
+typedef struct mic_hip_rgb_enc_job {
+    const uint8_t *rgb;        /* in : width*height*3 bytes, interleaved (host memory) */
+    int32_t   width, height;   /* in : width * height <= 2^26 */
+    int32_t   container;       /* in : 0: CompressRGB blob, 1: MICR file */
+    uint8_t  *out;             /* in : caller buffer */
+    size_t    out_cap;         /* in  */
+    size_t    out_len;         /* out */
+    int32_t   status;          /* out */
+    int32_t   failed_plane;    /* out */
+} mic_hip_rgb_enc_job;
+typedef struct mic_hip_rgb_dec_job {
+    const uint8_t *compressed; /* in : a CompressRGB blob or a MICR file (host memory) */
+    size_t    compressed_len;  /* in  */
+    uint8_t  *rgb_out;         /* in : width*height*3 bytes (host memory) */
+    size_t    out_cap;         /* in  */
+    int32_t   width, height;   /* in : blob: the image's.  MICR: 0 = take the header's, else must equal it */
+    int32_t   container;       /* in : 0 / 1 as above */
+    int32_t   status;          /* out */
+    int32_t   failed_plane;    /* out */
+} mic_hip_rgb_dec_job;
+int mic_hip_rgb_compress_batch(mic_hip_rgb_enc_job *jobs, int njobs);     /* rgbcompress.go:25-27, wsicompress.go:319-363 */
+int mic_hip_rgb_decompress_batch(mic_hip_rgb_dec_job *jobs, int njobs);   /* rgbcompress.go:31-33, wsicompress.go:431-475 */
 /* MIC1 file (writeMicFile, cmd/mic-compress/main.go:26-59): "MIC1", width, height, pipeline = 1, payload length,
  * CompressSingleFrame{,4State,8State} stream (nstates = 2, 4 or 8; the decoder auto-detects). */
 int mic_hip_mic1_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int nstates,
@@ -677,6 +711,16 @@ int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int
 int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
 
+/* mic_hip_rgb_compress_batch / _decompress_batch on device-resident data (rgbcompress.go:25-33; wsicompress.go:319-363, 431-475):
+ * image i is imgs[i].width x imgs[i].height interleaved RGB at d_rgb + imgs[i].rgb_off (any byte alignment).  encode leaves the
+ * CompressRGB blobs back to back in the session -- *d_blobs, blob i at h_offsets[i] .. h_offsets[i + 1], none for an image that
+ * failed -- until the session's next call (mic_hip_device_copy keeps them); decode reads blobs laid out that way and writes image
+ * i's pixels to d_rgb_out + imgs[i].rgb_off.  status / failed_plane per image as in the batch jobs. */
+typedef struct mic_hip_rgb_image { uint64_t rgb_off; int32_t width, height; } mic_hip_rgb_image;
+int mic_hip_session_rgb_encode(mic_hip_session *s, const uint8_t *d_rgb, const mic_hip_rgb_image *imgs, int n,
+                               const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *status, int32_t *failed_plane);
+int mic_hip_session_rgb_decode(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets,
+                               const mic_hip_rgb_image *imgs, int n, uint8_t *d_rgb_out, int32_t *status, int32_t *failed_plane);
 /* mic_hip_mic2_read_crops on a MIC2 file that lies in device memory: head = the file's first 20 + 8 * nframes bytes on the host,
  * d_file = the whole file (file_len bytes) on the session's device.  The streams of the plan's frames go device to device into the
  * session's compressed-input buffer (which keeps the 64 bytes of slack the decode kernels may read past a stream's end; the

@@ -106,6 +106,25 @@ class PicaDecJob(C.Structure):
                 ("failed_strip", C.c_int32)]
 
 
+class RgbEncJob(C.Structure):
+    """mic_hip_rgb_enc_job"""
+    _fields_ = [("rgb", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("container", C.c_int32),
+                ("out", C.c_void_p), ("out_cap", C.c_size_t), ("out_len", C.c_size_t), ("status", C.c_int32),
+                ("failed_plane", C.c_int32)]
+
+
+class RgbDecJob(C.Structure):
+    """mic_hip_rgb_dec_job"""
+    _fields_ = [("compressed", C.c_void_p), ("compressed_len", C.c_size_t), ("rgb_out", C.c_void_p), ("out_cap", C.c_size_t),
+                ("width", C.c_int32), ("height", C.c_int32), ("container", C.c_int32), ("status", C.c_int32),
+                ("failed_plane", C.c_int32)]
+
+
+class RgbImage(C.Structure):
+    """mic_hip_rgb_image"""
+    _fields_ = [("rgb_off", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class PatchStats(C.Structure):
     """mic_hip_patch_stats"""
     _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
@@ -145,6 +164,7 @@ ABI_SYMBOLS = [
     "mic_hip_compress_frame_grad", "mic_hip_decompress_frame_grad", "mic_hip_pica_compress", "mic_hip_pica_info", "mic_hip_pica_decompress",
     "mic_hip_pica_compress_ex", "mic_hip_pica_decompress_ex", "mic_hip_pica_compress_batch", "mic_hip_pica_decompress_batch", "mic_hip_pica_boundaries",
     "mic_hip_rgb_compress", "mic_hip_rgb_decompress", "mic_hip_micr_compress", "mic_hip_micr_info", "mic_hip_micr_decompress",
+    "mic_hip_rgb_compress_batch", "mic_hip_rgb_decompress_batch", "mic_hip_session_rgb_encode", "mic_hip_session_rgb_decode",
     "mic_hip_mic1_compress", "mic_hip_mic1_info", "mic_hip_mic1_decompress",
     "mic_hip_wsi_compress", "mic_hip_wsi_compress_ex", "mic_hip_wsi_format", "mic_hip_wsi_info", "mic_hip_wsi_level_info",
     "mic_hip_wsi_decompress_tile", "mic_hip_wsi_decompress_level", "mic_hip_wsi_decompress_region",
@@ -341,6 +361,10 @@ def lib() -> C.CDLL:
     L.mic_hip_rgb_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_rgb_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     L.mic_hip_micr_compress.argtypes = L.mic_hip_rgb_compress.argtypes
+    L.mic_hip_rgb_compress_batch.argtypes = [C.POINTER(RgbEncJob), C.c_int]
+    L.mic_hip_rgb_decompress_batch.argtypes = [C.POINTER(RgbDecJob), C.c_int]
+    L.mic_hip_session_rgb_encode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RgbImage), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mic_hip_session_rgb_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RgbImage), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mic_hip_micr_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mic_hip_micr_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.mic_hip_mic1_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -1433,6 +1457,66 @@ def decompress_rgb(compressed, width: int = 0, height: int = 0) -> np.ndarray:
     return out.reshape(height, width, 3)
 
 
+def rgb_bound(width: int, height: int, container: bool = False) -> int:
+    """MIC_HIP_RGB_BOUND: three raw planes behind the three lengths (+ the 12-byte header of a MICR file)"""
+    return 12 + 3 * (1 + 2 * width * height) + (12 if container else 0)
+
+
+def compress_rgb_batch(images: Sequence[np.ndarray], container=False,
+                       outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, "np.ndarray"]]:
+    """Many RGB images, one call (mic_hip_rgb_compress_batch): [(status, CompressRGB blob / MICR file as a uint8 view of its out
+    buffer)].  images: (height, width, 3) uint8 arrays of any sizes (ordinary or pinned memory); container: one value, or one per
+    image; outs: caller buffers of >= rgb_bound bytes, or None.  compress_rgb_batch.failed_planes: of the last call, the plane
+    each job's error is about (0 Y, 1 Co, 2 Cg; -1 none)."""
+    n = len(images)
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+    for a in arrs:
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise MicError(MIC_ERR_ARGS, "compress_rgb_batch")
+    cont = [bool(c) for c in container] if np.ndim(container) else [bool(container)] * n
+    if outs is None:
+        outs = [np.empty(rgb_bound(a.shape[1], a.shape[0], c), dtype=np.uint8) for a, c in zip(arrs, cont)]
+    jobs = (RgbEncJob * n)()
+    for i, a in enumerate(arrs):
+        jobs[i].rgb = a.ctypes.data; jobs[i].width = a.shape[1]; jobs[i].height = a.shape[0]; jobs[i].container = int(cont[i])
+        jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
+    rc = lib().mic_hip_rgb_compress_batch(jobs, n)
+    if rc:
+        _raise(rc, "compress_rgb_batch")
+    compress_rgb_batch.failed_planes = [j.failed_plane for j in jobs]
+    return [(j.status, o[: j.out_len]) for j, o in zip(jobs, outs)]
+
+
+def decompress_rgb_batch(files: Sequence, dims: Optional[Sequence] = None,
+                         outs: Optional[Sequence[np.ndarray]] = None) -> List[Tuple[int, Optional["np.ndarray"]]]:
+    """Many CompressRGB blobs / MICR files, one call (mic_hip_rgb_decompress_batch): [(status, (height, width, 3) uint8 pixels)].
+    dims = None: every file is a MICR file; else dims[i] = (width, height) of blob i, or None for a MICR file.  A MICR file whose
+    header cannot be read fails its job without a buffer (pixels None).  decompress_rgb_batch.failed_planes: as compress_rgb_batch."""
+    n = len(files)
+    cs = [_bytes_arr(f) for f in files]
+    dims = list(dims) if dims is not None else [None] * n
+    shape = []
+    for c, d in zip(cs, dims):
+        if d is None:
+            w, h = C.c_int(), C.c_int()
+            shape.append((w.value, h.value) if lib().mic_hip_micr_info(c.ctypes.data, c.size, C.byref(w), C.byref(h)) == 0 else None)
+        else:
+            shape.append((int(d[0]), int(d[1])))
+    if outs is None:
+        outs = [np.empty(max(sh[0] * sh[1] * 3, 1) if sh else 1, dtype=np.uint8) for sh in shape]
+    jobs = (RgbDecJob * n)()
+    for i in range(n):
+        jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
+        jobs[i].rgb_out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
+        jobs[i].container = 1 if dims[i] is None else 0
+        jobs[i].width, jobs[i].height = (0, 0) if dims[i] is None else shape[i]
+    rc = lib().mic_hip_rgb_decompress_batch(jobs, n)
+    if rc:
+        _raise(rc, "decompress_rgb_batch")
+    decompress_rgb_batch.failed_planes = [j.failed_plane for j in jobs]
+    return [(j.status, o[: sh[0] * sh[1] * 3].reshape(sh[1], sh[0], 3) if (sh and j.status == 0) else None) for j, o, sh in zip(jobs, outs, shape)]
+
+
 def write_mic1(pixels, width: int, height: int, max_value: int, nstates: int = 2) -> bytes:
     """The CLI's single-frame .mic file (writeMicFile, cmd/mic-compress/main.go:26-59)."""
     px = np.ascontiguousarray(pixels, dtype=np.uint16).reshape(-1)
@@ -1547,6 +1631,42 @@ class Session:
         if rc:
             _raise(rc, "session_decode_finish")
         return st
+
+    # ---- RGB images on the device (rgbcompress.go:25-33) ----------------------------------------------------------------
+    @staticmethod
+    def make_rgb_images(images: Sequence[Tuple[int, int, int]]):
+        """images: (byte offset of the image's RGB, width, height) each -> the mic_hip_rgb_image table"""
+        arr = (RgbImage * len(images))()
+        for i, (off, w, h) in enumerate(images):
+            arr[i].rgb_off = off; arr[i].width = w; arr[i].height = h
+        return arr
+
+    def rgb_encode(self, d_rgb: int, images):
+        """mic_hip_session_rgb_encode: images = make_rgb_images(...) (or the tuples), their RGB at d_rgb + offset on the session's
+        device -> (device pointer of the CompressRGB blobs, offsets[n + 1], status[n], failed_plane[n]); the blobs stay in the
+        session until its next call"""
+        tab = images if isinstance(images, C.Array) else self.make_rgb_images(images)
+        n = len(tab)
+        offs = np.zeros(n + 1, dtype=np.uint64); st = np.zeros(n, dtype=np.int32); fp = np.full(n, -1, dtype=np.int32)
+        d = C.c_void_p()
+        rc = lib().mic_hip_session_rgb_encode(self._h, d_rgb, tab, n, C.byref(d), offs.ctypes.data, st.ctypes.data, fp.ctypes.data)
+        if rc:
+            _raise(rc, "session_rgb_encode")
+        return d.value, offs, st, fp
+
+    def rgb_decode(self, d_blobs: int, offsets: np.ndarray, images, d_rgb_out: int):
+        """mic_hip_session_rgb_decode: blob i at d_blobs + offsets[i] .. offsets[i + 1] -> image i's pixels at d_rgb_out + its offset
+        -> (status[n], failed_plane[n])"""
+        tab = images if isinstance(images, C.Array) else self.make_rgb_images(images)
+        n = len(tab)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.size < n + 1:
+            raise ValueError("rgb_decode: offsets must hold len(images) + 1 entries")
+        st = np.zeros(n, dtype=np.int32); fp = np.full(n, -1, dtype=np.int32)
+        rc = lib().mic_hip_session_rgb_decode(self._h, d_blobs, offs.ctypes.data, tab, n, d_rgb_out, st.ctypes.data, fp.ctypes.data)
+        if rc:
+            _raise(rc, "session_rgb_decode")
+        return st, fp
 
     # ---- WaveletV2 on device-resident frames (waveletfsecompressu16.go:303-534) -------------------------------------------
     def wavelet_v2_encode(self, d_frames: int, nframes: int, rows: int, cols: int, levels: int = 5):

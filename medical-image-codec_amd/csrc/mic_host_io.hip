@@ -667,6 +667,136 @@ int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry en
     return MIC_OK;
 }
 
+// ============================================================================ RGB: many images per call (mic_rgb_batch.hip)
+// The call's jobs are cut into sub-batches of whole images (rgb_next_cut: their units under the workspace ceiling, about a part's
+// share of the pixels); a sub-batch's images come up back to back -- so an image starts at whatever byte its neighbours leave -- into
+// one half of the staging while the other half's sub-batch is coded, and its blobs, assembled on the device, go down from one half
+// of the payload, one copy per job, while the next sub-batch runs.
+inline size_t rgb_target_px(size_t images, size_t total_px, bool encode) {
+    static const char *ov = getenv("MIC_HIP_PIPELINE_PARTS");              // (as pipeline_target: force the number of parts)
+    // a unit chain costs about the same for a few units as for hundreds: parts of >= 256 / 384 units (encode / decode), three / two at most
+    const size_t parts = ov ? (size_t)std::max(1, atoi(ov)) : std::min<size_t>(encode ? 3 : 2, 3 * images / (encode ? 256 : 384));
+    if (parts < 2) return ~(size_t)0;
+    return std::max<size_t>(1, (total_px + parts - 1) / parts);
+}
+void rgb_trace_parts(const char *what, size_t k, size_t parts, int i0, int i1, size_t px) {
+    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: the pipeline's stages on stderr)
+    if (trace) fprintf(stderr, "[mic_hip rgb %s] part %zu of %zu: images %d .. %d, %zu pixels\n", what, k + 1, parts, i0, i1 - 1, px);
+}
+
+// jobs J[j0 .. j1) (checked: arguments fine) on session s
+int rgb_encode_host(mic_hip_session *s, std::vector<mic_hip_rgb_enc_job *> &J, int j0, int j1) {
+    if (j0 >= j1) return MIC_OK;
+    int rc = s->ensure(1, 1);                                             // (the stream)
+    if (rc) return rc;
+    auto npx = [&](int i) { return (size_t)J[(size_t)i]->width * (size_t)J[(size_t)i]->height; };
+    size_t total_px = 0;
+    for (int i = j0; i < j1; i++) total_px += npx(i);
+    const size_t target = rgb_target_px((size_t)(j1 - j0), total_px, true);
+    struct Sub { int i0, i1; IoReq up, down; std::vector<RgbImage> img; size_t bytes = 0; };
+    std::vector<std::unique_ptr<Sub>> subs;
+    for (int i0 = j0; i0 < j1;) {
+        auto sb = std::make_unique<Sub>();
+        sb->i0 = i0; sb->i1 = rgb_next_cut(npx, i0, j1, target);
+        for (int i = sb->i0; i < sb->i1; i++) {
+            sb->img.push_back(RgbImage{ (uint64_t)sb->bytes, J[(size_t)i]->width, J[(size_t)i]->height, J[(size_t)i]->container, MIC_OK, -1, 0, 0 });
+            sb->bytes += npx(i) * 3;
+        }
+        i0 = sb->i1; subs.push_back(std::move(sb));
+    }
+    for (size_t k = 0; k < subs.size(); k++) rgb_trace_parts("encode", k, subs.size(), subs[k]->i0, subs[k]->i1, subs[k]->bytes / 3);
+    DevBuf *in[2] = { &s->io_px, &s->io_px2 }, *pay[2] = { &s->rgb_payload, &s->rgb_payload2 };
+    auto upload = [&](Sub &sb, int half) -> int {
+        int r = in[half]->reserve(sb.bytes + 64);
+        for (int i = sb.i0; i < sb.i1 && r == MIC_OK; i++)
+            r = io_submit(sb.up, s->device, (uint8_t *)in[half]->p + sb.img[(size_t)(i - sb.i0)].rgb_off, J[(size_t)i]->rgb, npx(i) * 3, true);
+        return r;
+    };
+    rc = upload(*subs[0], 0);
+    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
+        Sub &sb = *subs[k];
+        const int half = (int)(k & 1);
+        rc = sb.up.wait();
+        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);       // (that half's sub-batch is coded: its kernels have been waited for)
+        if (rc == MIC_OK && k >= 2) rc = subs[k - 2]->down.wait();                          // this sub-batch's blobs go where those of k - 2 are (were) going down from
+        uint64_t end = 0;
+        if (rc == MIC_OK) rc = rgb_encode_run(s, (const uint8_t *)in[half]->p, sb.img.data(), sb.i1 - sb.i0, *pay[half], 0, &end);
+        if (rc != MIC_OK) break;
+        for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
+            mic_hip_rgb_enc_job &j = *J[(size_t)i];
+            const RgbImage &im = sb.img[(size_t)(i - sb.i0)];
+            j.status = im.status; j.failed_plane = im.failed_plane;
+            if (j.status != MIC_OK) continue;
+            if (im.blob_len > j.out_cap) { j.status = MIC_ERR_CAPACITY; continue; }
+            rc = io_submit(sb.down, s->device, (uint8_t *)pay[half]->p + im.blob_off, j.out, (size_t)im.blob_len, false);   // the job's bytes: one copy
+            j.out_len = (size_t)im.blob_len;
+        }
+    }
+    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
+    return rc;
+}
+
+struct RgbDecRun { mic_hip_rgb_dec_job *j; const uint8_t *blob; size_t len; int32_t w, h; RgbPlaneRec pl[3]; };
+int rgb_decode_host(mic_hip_session *s, std::vector<RgbDecRun> &J, int j0, int j1) {
+    if (j0 >= j1) return MIC_OK;
+    int rc = s->ensure(1, 1);
+    if (rc) return rc;
+    auto npx = [&](int i) { return (size_t)J[(size_t)i].w * (size_t)J[(size_t)i].h; };
+    size_t total_px = 0;
+    for (int i = j0; i < j1; i++) total_px += npx(i);
+    const size_t target = rgb_target_px((size_t)(j1 - j0), total_px, false);
+    // small blobs in ordinary memory are gathered on the host and go up in one copy; large or pinned ones go up from where they lie
+    struct Sub { int i0, i1; IoReq up, down; std::vector<RgbBlob> bl; std::vector<uint8_t> small; size_t comp = 0, bytes = 0; };
+    std::vector<std::unique_ptr<Sub>> subs;
+    for (int i0 = j0; i0 < j1;) {
+        auto sb = std::make_unique<Sub>();
+        sb->i0 = i0; sb->i1 = rgb_next_cut(npx, i0, j1, target);
+        for (int i = sb->i0; i < sb->i1; i++) {
+            const RgbDecRun &r = J[(size_t)i];
+            RgbBlob b{ 0, r.len, (uint64_t)sb->bytes, r.w, r.h, MIC_OK, -1, { r.pl[0], r.pl[1], r.pl[2] } };
+            sb->bl.push_back(b);
+            sb->bytes += npx(i) * 3;
+        }
+        i0 = sb->i1; subs.push_back(std::move(sb));
+    }
+    for (size_t k = 0; k < subs.size(); k++) rgb_trace_parts("decode", k, subs.size(), subs[k]->i0, subs[k]->i1, subs[k]->bytes / 3);
+    DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
+    auto upload = [&](Sub &sb, int half) -> int {
+        std::vector<int> direct;
+        for (int i = sb.i0; i < sb.i1; i++) {
+            const RgbDecRun &r = J[(size_t)i];
+            if (r.len <= kInline && !host_is_pinned(r.blob)) { sb.bl[(size_t)(i - sb.i0)].blob_off = sb.small.size(); sb.small.insert(sb.small.end(), r.blob, r.blob + r.len); }
+            else direct.push_back(i);
+        }
+        sb.comp = sb.small.size();
+        for (int i : direct) { sb.bl[(size_t)(i - sb.i0)].blob_off = sb.comp; sb.comp += J[(size_t)i].len; }
+        int r = in[half]->reserve(sb.comp + 64);
+        if (r == MIC_OK && !sb.small.empty()) r = io_submit(sb.up, s->device, in[half]->p, sb.small.data(), sb.small.size(), true);
+        for (size_t q = 0; q < direct.size() && r == MIC_OK; q++)
+            r = io_submit(sb.up, s->device, (uint8_t *)in[half]->p + sb.bl[(size_t)(direct[q] - sb.i0)].blob_off, J[(size_t)direct[q]].blob, J[(size_t)direct[q]].len, true);
+        return r;
+    };
+    rc = upload(*subs[0], 0);
+    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
+        Sub &sb = *subs[k];
+        const int half = (int)(k & 1);
+        rc = sb.up.wait();
+        if (rc == MIC_OK && k >= 2) rc = subs[k - 2]->down.wait();                          // this sub-batch decodes into the half that k - 2 is (was) going down from
+        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);
+        if (rc == MIC_OK) rc = outb[half]->reserve(sb.bytes + 64);
+        if (rc == MIC_OK) rc = rgb_decode_run(s, (const uint8_t *)in[half]->p, sb.bl.data(), sb.i1 - sb.i0, (uint8_t *)outb[half]->p);
+        if (rc != MIC_OK) break;
+        for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
+            const RgbBlob &b = sb.bl[(size_t)(i - sb.i0)];
+            mic_hip_rgb_dec_job &j = *J[(size_t)i].j;
+            j.status = b.status; j.failed_plane = b.failed_plane;
+            if (b.status == MIC_OK) rc = io_submit(sb.down, s->device, (uint8_t *)outb[half]->p + b.rgb_off, j.rgb_out, npx(i) * 3, false);
+        }
+    }
+    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
+    return rc;
+}
+
 }  // namespace
 
 namespace micapi {
@@ -1094,6 +1224,55 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
     if ((rc = over_devices(first, [&](mic_hip_session *s, int f0, int f1) { return decode_groups(s, G, U, U[(size_t)f0].group, U[(size_t)f1 - 1].group + 1); }))) return rc;
     for (const DecGroup &g : G) if (g.status != MIC_OK) return g.status;
     return MIC_OK;
+} MIC_ABI_CATCH
+
+// ---- RGB (rgbcompress.go:25-33): many images per call ----------------------------------------------
+int mic_hip_rgb_compress_batch(mic_hip_rgb_enc_job *jobs, int njobs) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::vector<mic_hip_rgb_enc_job *> J;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_rgb_enc_job &j = jobs[i];
+        j.out_len = 0; j.failed_plane = -1;
+        if (!j.rgb || !j.out || j.width <= 0 || j.height <= 0 || (j.container != 0 && j.container != 1)) { j.status = MIC_ERR_ARGS; continue; }
+        if ((size_t)j.width * (size_t)j.height > ((size_t)1 << 26)) { j.status = MIC_ERR_UNSUPPORTED; continue; }   // as mic_hip_rgb_compress
+        if (j.out_cap < (j.container ? 24u : 12u)) { j.status = MIC_ERR_CAPACITY; continue; }
+        j.status = MIC_ERR_DEVICE;                                                                 // (until the job has run: a call that fails as a whole leaves no stale status)
+        J.push_back(&j);
+    }
+    return over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i]->width * (uint64_t)J[(size_t)i]->height; },
+                        [&](mic_hip_session *s, int j0, int j1) { return rgb_encode_host(s, J, j0, j1); });
+} MIC_ABI_CATCH
+
+int mic_hip_rgb_decompress_batch(mic_hip_rgb_dec_job *jobs, int njobs) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::vector<RgbDecRun> J;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_rgb_dec_job &j = jobs[i];
+        j.failed_plane = -1;
+        if (!j.compressed || !j.rgb_out || j.width < 0 || j.height < 0 || (j.container != 0 && j.container != 1)) { j.status = MIC_ERR_ARGS; continue; }
+        RgbDecRun r{ &j, j.compressed, j.compressed_len, j.width, j.height, {} };
+        if (j.container) {                                                                         // readMICRFile: the header names the size
+            int w = 0, h = 0;
+            if ((j.status = mic_hip_micr_info(j.compressed, j.compressed_len, &w, &h))) continue;
+            if ((j.width || j.height) && (j.width != w || j.height != h)) { j.status = MIC_ERR_ARGS; continue; }
+            r.blob += 12; r.len -= 12; r.w = w; r.h = h;
+        } else if (j.width == 0 || j.height == 0) { j.status = MIC_ERR_ARGS; continue; }
+        if ((size_t)r.w * (size_t)r.h > ((size_t)1 << 26)) { j.status = MIC_ERR_UNSUPPORTED; continue; }   // as mic_hip_rgb_decompress
+        if ((size_t)r.w * (size_t)r.h * 3 > j.out_cap) { j.status = MIC_ERR_CAPACITY; continue; }
+        RgbHead head;
+        rgb_head_of(r.blob, r.len, head);
+        if ((j.status = rgb_parse_head(head, r.len, (size_t)r.w * (size_t)r.h, r.pl, &j.failed_plane))) continue;
+        j.status = MIC_ERR_DEVICE;
+        J.push_back(r);
+    }
+    return over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i].w * (uint64_t)J[(size_t)i].h; },
+                        [&](mic_hip_session *s, int j0, int j1) { return rgb_decode_host(s, J, j0, j1); });
 } MIC_ABI_CATCH
 
 }  // extern "C"

@@ -175,6 +175,9 @@ struct mic_hip_session {
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
     DevBuf mic2_pieces;                    // MIC2 crops: a call's piece / footprint list (mic_mic2_crops.hip)
     DevBuf strip_pieces;                   // strip-file crops: a call's piece list (mic_strip_crops.hip)
+    DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
+    DevBuf rgb_payload, rgb_payload2;      // ... and its assembled blobs: two halves, one goes down while the other is written
+    PinnedU64 rgb_pin;                     // ... the host's copy of the plane statistics / the blob heads
     PinnedUnits h_units;
     std::vector<uint64_t> h_off;
     // what an enqueue has already put behind its chain (session_*_finish then only synchronises): the read-back of the descriptors;
@@ -328,18 +331,18 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
         if (wsi) { mic_wsi_store_free(wsi); wsi = nullptr; }
-        h_units.release(); pin_off.release(); pica_pin[0].release(); pica_pin[1].release();
+        h_units.release(); pin_off.release(); pica_pin[0].release(); pica_pin[1].release(); rgb_pin.release();
         readback_queued = pack_queued = false;
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
@@ -403,6 +406,29 @@ int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch,
 int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
                     void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
+// RGB batches (mic_rgb_batch.hip): many images of different sizes per call, CompressRGB / DecompressRGB (rgbcompress.go:25-33) of each.
+// One image of a sub-batch on the encode side: its RGB at d_rgb + rgb_off; container 1 = a MICR header in front of its blob.
+// status on entry: not MIC_OK = skip the image.  On return: status / failed_plane (0 Y, 1 Co, 2 Cg, -1 not a plane's), and the
+// blob at [blob_off, blob_off + blob_len) of the payload buffer (a failed image has none).
+struct RgbImage { uint64_t rgb_off; int32_t w, h, container; int32_t status = MIC_OK, failed_plane = -1; uint64_t blob_off = 0, blob_len = 0; };
+// a plane of a blob as decompressWSIPlane sees it (wsicompress.go:487-524): mode 0 zero, 1 `value`, 2 a stream, 3 raw; off / len:
+// the bytes of modes 2 / 3, off from the blob's first byte
+struct RgbPlaneRec { uint8_t mode; uint16_t value; uint64_t off, len; };
+// One blob of a sub-batch on the decode side: [blob_off, blob_off + blob_len) of d_blobs, pixels to d_rgb_out + rgb_off
+struct RgbBlob { uint64_t blob_off, blob_len, rgb_off; int32_t w, h; int32_t status = MIC_OK, failed_plane = -1; RgbPlaneRec pl[3]; };
+// what the host needs of a blob to check it: the three plane lengths and the first three bytes of each plane (zero where the blob ends before)
+struct RgbHead { uint32_t len[3]; uint8_t b[3][3]; uint8_t pad[3]; };
+void rgb_head_of(const uint8_t *blob, uint64_t bl, RgbHead &h);
+// decompressRGBTileBlob's checks (wsicompress.go:431-461) + decompressWSIPlane's for every plane: the blob's status, the plane it names
+int rgb_parse_head(const RgbHead &h, uint64_t bl, size_t npx, RgbPlaneRec pl[3], int32_t *failed_plane);
+// images [i0, return) of the next sub-batch of images [.., n), npx(i) pixels each: their three units a launch's grid y and under the
+// workspace ceiling, about target_px pixels
+int rgb_next_cut(const std::function<size_t(int)> &npx, int i0, int n, size_t target_px);
+// the core, on device buffers: the plane kernel, ONE unit batch over every non-constant plane, the blobs assembled in `payload` from
+// byte pay0 on (a caller that passes pay0 > 0 has reserved the buffer; *pay_end: where they end).  Complete on return.
+int rgb_encode_run(mic_hip_session *s, const uint8_t *d_rgb, RgbImage *img, int n, DevBuf &payload, uint64_t pay0, uint64_t *pay_end);
+// the blobs (checked: pl[] filled in, status MIC_OK) -> pixels: fills, ONE unit batch over every mode-2 plane, the inverse transform
+int rgb_decode_run(mic_hip_session *s, const uint8_t *d_blobs, RgbBlob *blobs, int n, uint8_t *d_rgb_out);
 // Strip files (PICS: parallelstrips.go, PICA: parallelstripsadaptive.go): a header, a table and one unit per strip.  Strip k of a
 // file of height h and n strips as its header states it -- rows [y0, y1), bytes [start, start + len) of the file, the unit's flags --
 // read from the header and the table alone; what the whole-image decoders (mic_host_io.hip) and the crop calls (mic_strip_crops.hip) decode by.

@@ -170,6 +170,35 @@ def wsi_like(width: int, height: int, seed: int = 4) -> np.ndarray:
     return img
 
 
+def us_like(width: int, height: int, frame: int = 0, seed: int = 5) -> np.ndarray:
+    """Ultrasound-like RGB frame (height x width x 3, uint8) of a cine loop: a greyscale sector (R = G = B, so Co and Cg are
+    constant zero) on black, with speckle that drifts with `frame`; on every fourth frame from frame 1 on a colour box (a Doppler
+    overlay) inside the sector.  Frame f of a loop is a pure function of (width, height, f, seed)."""
+    yy = np.arange(height, dtype=np.float64)[:, None]
+    xx = np.arange(width, dtype=np.float64)[None, :]
+    ax, ay = width / 2.0, -0.08 * height                                  # the sector's apex, above the image
+    rr = np.hypot(xx - ax, yy - ay)
+    inside = (np.abs(xx - ax) < 0.75 * (yy - ay)) & (rr > 0.14 * height) & (rr < 1.02 * height)
+    # speckle: a field hashed per pixel, read at a column that drifts with the frame, over a smooth depth-dependent envelope
+    h = hash_u64(height * width, seed).reshape(height, width)
+    h = np.roll(h, shift=(frame // 3, frame), axis=(0, 1))
+    sp = (h & np.uint64(0xFF)).astype(np.float64) * ((h >> np.uint64(8)) & np.uint64(0xFF)).astype(np.float64) / 255.0
+    env = 0.25 + 0.55 * np.exp(-rr / (0.9 * height)) + 0.2 * np.sin(rr / 23.0 + 0.15 * frame) * np.cos((xx - ax) / 31.0)
+    grey = np.where(inside, np.clip(np.rint(sp * env), 0, 255), 0).astype(np.uint8)
+    img = np.repeat(grey[:, :, None], 3, axis=2)
+    if frame % 4 == 1 and height >= 8 and width >= 8:                     # the colour box: flow towards / away from the probe
+        y0, y1, x0, x1 = int(0.45 * height), int(0.7 * height), int(0.4 * width), int(0.62 * width)
+        hb = hash_u64((y1 - y0) * (x1 - x0), seed * 7919 + frame).reshape(y1 - y0, x1 - x0)
+        v = np.sin((xx[:, x0:x1] + 2.0 * frame) / 11.0) * np.cos(yy[y0:y1] / 13.0) + ((hb & np.uint64(0xF)).astype(np.float64) - 7.5) / 40.0
+        flow = np.abs(v) > 0.35
+        box = img[y0:y1, x0:x1]
+        m = flow & inside[y0:y1, x0:x1]
+        amp = np.clip(np.rint(np.abs(v) * 255.0), 0, 255).astype(np.uint8)
+        box[..., 0][m & (v > 0)] = amp[m & (v > 0)]; box[..., 1][m & (v > 0)] = 0; box[..., 2][m & (v > 0)] //= 4
+        box[..., 2][m & (v < 0)] = amp[m & (v < 0)]; box[..., 1][m & (v < 0)] = 0; box[..., 0][m & (v < 0)] //= 4
+    return img
+
+
 def closed_form(n: int, mul: int = 131, add: int = 7, mod: int = 65536) -> np.ndarray:
     """The reference wavelet tests' closed-form inputs: (i*131+7)%65536, (i*97+13)%4096
     (waveletu16_test.go:190-248)."""
