@@ -670,9 +670,13 @@ int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {
     out8[0] = u.ntok; out8[1] = u.blob_len; out8[2] = u.table_log; out8[3] = u.symbol_len;
     out8[4] = u.max_count; out8[5] = u.hdr_len; out8[6] = u.zero_bits; out8[7] = u.flavour;
     out8[8] = u.count; out8[9] = u.bits_off; out8[10] = (uint32_t)u.nstates_used; out8[11] = (uint32_t)u.status; out8[12] = u.nseg; out8[13] = u.nsym; out8[14] = u.seg_cap;
+    out8[15] = u.dec_kernel;                                             // 1 + lane-per-state class, MIC_DEC_BY_GL, MIC_DEC_BY_SERIAL; 0: no tANS kernel took the unit
     for (int k = 0; k < 16; k++) out8[16 + k] = u.dbg[k];
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py
+// holds its own restatement against it, value by value)
+int mic_hip_debug_dec_cls(uint32_t flavour, uint32_t table_log, uint32_t zero_bits) { return mic_dec_cls(flavour, table_log, zero_bits); }
 // debug probe (not in the public header): bytes of unit i's histogram slab after a *_finish (LS_DEBUG builds dump there)
 int mic_hip_debug_fetch_hist(mic_hip_session *s, int i, void *dst, size_t bytes) try {
     if (!s || i < 0 || i >= s->n_last || bytes > kSym * 4) return MIC_ERR_ARGS;

@@ -88,6 +88,7 @@ __global__ void __launch_bounds__(64) k_dec_tans_serial(MicUnit *units) {
     if (threadIdx.x != 0 || u.status != MICD_OK) return;
     if (u.ntok != 0) return;                                           // a fast variant already decoded it
     dec_tans_serial_body(u);
+    u.dec_kernel = MIC_DEC_BY_SERIAL;
 }
 
 // Gap removal's checking path (mic_gap.hip: k_dec_gap_expand parks a unit whose table gives weight to a compact symbol >= numSymbols
@@ -291,6 +292,7 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
         walk(count, [&](uint32_t pos) -> uint32_t { return __builtin_amdgcn_readlane(tv0, pos - done); });
     }
     if (lane == 0) {
+        u.dec_kernel = MIC_DEC_BY_GL;
         if (count == u.count && q + 32 - (int32_t)(8u * sb) < 0) u.status = MICD_ERR_CORRUPT;   // bitreader.go:113-120 (a prefix reads less)
         else {
             u.ntok = count;

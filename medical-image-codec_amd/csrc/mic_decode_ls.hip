@@ -494,6 +494,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     // ---- results: one lane per stream -------------------------------------------------------------------------------
     if (have && lane % LS_LS == 0 && lane < LS_SPW * LS_LS) {
         MicUnit &uo = units[list[slot0 + (int)g]];
+        uo.dec_kernel = 1u + (uint32_t)((TL <= 12 ? 4 : TL - 13) * 6 + (N == 2 ? 0 : N == 4 ? 2 : 4) + (ZB ? 1 : 0));   // this instance's class, as mic_dec_cls numbers it
         // bitreader.go:113-120: more bits taken than the stream holds -- a prefix has read only the bits behind its own symbols
         if (count == uo.count && q + 32 - (int32_t)(8u * sb) < 0) uo.status = MICD_ERR_CORRUPT;
         else { uo.ntok = count; uo.walk_ok = 2; }                           // tok holds STATES: k_dec_translate turns them into symbols
@@ -741,4 +742,17 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
         hipLaunchKernelGGL(k_dec_translate_wide, dim3((unsigned)n), dim3(TRW_THREADS), 0, stream, d_units);   // (marks its units walk_ok 3: the next launch skips them)
         hipLaunchKernelGGL(k_dec_translate<16>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);
     }
+}
+
+// debug probe (not in the public header): streams per wave and waves per group of the kernels of a table-size class
+// (table_log 12 stands for every smaller one), 0 for no class
+extern "C" int mic_hip_debug_ls_geom(int table_log, int *spw, int *waves) {
+    switch (table_log) {
+    case 12: *spw = LsGeom<12>::SPW; *waves = LsGeom<12>::WAVES; return 1;
+    case 13: *spw = LsGeom<13>::SPW; *waves = LsGeom<13>::WAVES; return 1;
+    case 14: *spw = LsGeom<14>::SPW; *waves = LsGeom<14>::WAVES; return 1;
+    case 15: *spw = LsGeom<15>::SPW; *waves = LsGeom<15>::WAVES; return 1;
+    case 16: *spw = LsGeom<16>::SPW; *waves = LsGeom<16>::WAVES; return 1;
+    }
+    return 0;
 }

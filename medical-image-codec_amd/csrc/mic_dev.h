@@ -29,6 +29,9 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 #define MICD_ERR_INCOMPRESSIBLE -10
 #define MICD_INT_GROW           -21    // internal: a tier-1 slab would overflow; the host runs the batch again in tier 2 (never surfaces)
 #define MICD_GAP_CHECK          -22    // internal: a gap-removal unit for k_dec_gap_check, the checking decode path (never surfaces)
+// MicUnit.dec_kernel behind the 30 lane-per-state classes (1 .. 30)
+#define MIC_DEC_BY_GL           31u
+#define MIC_DEC_BY_SERIAL       32u
 
 struct MicUnit {
     // ---- inputs ------------------------------------------------------------------
@@ -92,6 +95,9 @@ struct MicUnit {
     uint32_t flavour;         // decode: 1/2/4/8, 108 = rANS-8
     uint32_t packed_direct;   // encode: 1 = the bitstream goes straight to the packed buffer (k_enc_tans_pack); the blob holds only the framing
     uint32_t skip_pack;       // encode: 1 = the losing candidate of a PICA strip (k_pica_pick): k_scan_lens does not count it, the pack kernels leave it alone
+    uint32_t dec_kernel;      // decode: which kernel ran the unit's tANS chain -- 1 + its class (mic_dec_cls) for k_dec_tans_ls,
+                              // MIC_DEC_BY_GL for k_dec_tans_gl, MIC_DEC_BY_SERIAL for k_dec_tans_serial; 0: nobody (tests/test_gpu_decode_classes.py).  Cleared with the
+                              // other results: every enqueue's lay_out() starts each descriptor again from MicUnit{}
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
     // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------
     uint32_t sym_limit;       // 0: the whole stream.  Else the chain kernels that honour it decode only the first

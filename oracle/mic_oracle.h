@@ -69,6 +69,19 @@ typedef struct {
 /* histogram+tableLog+normalise; norm must hold 65536 entries */
 int mico_fse_normalize(const uint16_t *in, size_t n, int32_t *norm,
                        mico_fse_info *info);
+/* what mico_fse_compress_tl(in, n, nstates, table_log) decides in front of its bitstream: the tableLog it ends up with, whether
+ * a decoder's table has the zeroBits flag, and hdr_len = the bytes in front of the bitstream (the 6-byte prefix of the N-state
+ * flavours and the NCount header).  Same gates, same return codes (one function runs them for both); an encode can still fail
+ * behind them (incompressible).  norm: NULL, or room for 65536 entries -- the normalised counts the header states. */
+typedef struct {
+    uint32_t table_log;
+    uint32_t zero_bits;
+    uint32_t hdr_len;
+    uint32_t symbol_len;
+    uint32_t max_count;
+} mico_fse_facts;
+int mico_fse_stream_facts(const uint16_t *in, size_t n, int nstates, int table_log,
+                          mico_fse_facts *facts, int32_t *norm);
 
 /* ---- L3: unit codec (multiframecompress.go:15-107) ---------------------- */
 /* nstates 2 -> CompressSingleFrame, 4 -> ...4State, 8 -> ...8State

@@ -681,24 +681,34 @@ int mico_fse_compress(const uint16_t *in, size_t n, int nstates,
     return mico_fse_compress_tl(in, n, nstates, 0, out, cap, out_len);
 }
 
-/* the same with ScratchU16.TableLog set by the caller (fseu16.go:101-102, :133-138: 0 = default 11, > 16 is an error) */
-int mico_fse_compress_tl(const uint16_t *in, size_t n, int nstates, int table_log,
-                         uint8_t *out, size_t cap, size_t *out_len) {
-    int lanes = (nstates == 108) ? 8 : nstates;
+/* The front of FSECompressU16* with ScratchU16.TableLog set by the caller (fseu16.go:101-102, :133-138: 0 = default 11, > 16 is an
+ * error): the argument checks, the histogram, the USE_RLE and INCOMPRESSIBLE gates, optimal_table_log and the normalisation.  On
+ * MICO_OK *s holds the table the encoder will write (the caller frees it); on an error it is freed already. */
+static int fse_enc_front(fse_enc *s, const uint16_t *in, size_t n, int lanes, int table_log, uint32_t *max_count) {
     if (table_log < 0 || table_log > MAX_TABLELOG) return MICO_ERR_ARGS;   /* "tableLog (%d) > maxTableLog (%d)" */
     if (!(lanes == 1 || lanes == 2 || lanes == 4 || lanes == 8)) return MICO_ERR_ARGS;
     if (n <= (size_t)(lanes - 1) || n <= 1) return MICO_ERR_INCOMPRESSIBLE;
     if (n > ((size_t)2 << 30) - 1) return MICO_ERR_ARGS;
-    fse_enc s;
-    int rc = fse_enc_prepare(&s, in, n);
+    int rc = fse_enc_prepare(s, in, n);
     if (rc) return rc;
-    s.req_table_log = (uint8_t)table_log;
-    uint32_t max_count = count_simple(&s, in, n);
-    if ((size_t)max_count == n) { fse_enc_free(&s); return MICO_ERR_USE_RLE; }
-    if (max_count == 1 || (size_t)max_count < (n >> 15)) { fse_enc_free(&s); return MICO_ERR_INCOMPRESSIBLE; }
-    optimal_table_log(&s);
-    rc = normalize_count(&s);
-    if (rc) { fse_enc_free(&s); return rc; }
+    s->req_table_log = (uint8_t)table_log;
+    *max_count = count_simple(s, in, n);
+    if ((size_t)*max_count == n) { fse_enc_free(s); return MICO_ERR_USE_RLE; }
+    if (*max_count == 1 || (size_t)*max_count < (n >> 15)) { fse_enc_free(s); return MICO_ERR_INCOMPRESSIBLE; }
+    optimal_table_log(s);
+    rc = normalize_count(s);
+    if (rc) fse_enc_free(s);
+    return rc;
+}
+
+/* the same with ScratchU16.TableLog set by the caller */
+int mico_fse_compress_tl(const uint16_t *in, size_t n, int nstates, int table_log,
+                         uint8_t *out, size_t cap, size_t *out_len) {
+    int lanes = (nstates == 108) ? 8 : nstates;
+    fse_enc s;
+    uint32_t max_count;
+    int rc = fse_enc_front(&s, in, n, lanes, table_log, &max_count);
+    if (rc) return rc;
     size_t pos = (lanes == 1) ? 0 : 6;
     if (cap < pos + 8) { fse_enc_free(&s); return MICO_ERR_CAPACITY; }
     rc = write_count(&s, out, cap, &pos);
@@ -726,6 +736,33 @@ int mico_fse_compress_tl(const uint16_t *in, size_t n, int nstates, int table_lo
     }
     *out_len = hdr_end + bw.len;
     return MICO_OK;
+}
+
+/* What the encoder above decides about a stream before it writes a single state: fse_enc_front and the NCount header of
+ * mico_fse_compress_tl, and nothing behind them.  zero_bits is the DECODER's flag (fsedecompressu16.go:214-216: some norm >=
+ * tableSize / 2, build_dtable below), the one a decoder's choice of path hangs on; the encoder's own (a norm ABOVE half the table,
+ * build_ctable) differs from it when a count is exactly half the table.  norm: NULL, or room for the 65536 normalised counts. */
+int mico_fse_stream_facts(const uint16_t *in, size_t n, int nstates, int table_log, mico_fse_facts *facts, int32_t *norm) {
+    int lanes = (nstates == 108) ? 8 : nstates;
+    fse_enc s;
+    uint32_t max_count;
+    int rc = fse_enc_front(&s, in, n, lanes, table_log, &max_count);
+    if (rc) return rc;
+    size_t cap = (size_t)s.symbol_len * 4 + 64, pos = (lanes == 1) ? 0 : 6;   /* (an NCount entry is under four bytes) */
+    uint8_t *hdr = (uint8_t *)malloc(cap);
+    if (!hdr) { fse_enc_free(&s); return MICO_ERR_NOMEM; }
+    rc = write_count(&s, hdr, cap, &pos);
+    free(hdr);
+    if (rc == MICO_OK) {
+        int32_t large_limit = (int32_t)1 << (s.table_log - 1);
+        facts->table_log = s.table_log; facts->symbol_len = s.symbol_len; facts->max_count = max_count;
+        facts->hdr_len = (uint32_t)pos;
+        facts->zero_bits = 0;
+        for (uint32_t i = 0; i < s.symbol_len; i++) if (s.norm[i] >= large_limit) facts->zero_bits = 1;
+        if (norm) memcpy(norm, s.norm, sizeof(int32_t) * (MAXSYM + 1));
+    }
+    fse_enc_free(&s);
+    return rc;
 }
 
 /* ------------------------------------------------------------- FSE decode */

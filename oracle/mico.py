@@ -84,6 +84,27 @@ def fse_compress_tl(sym: np.ndarray, nstates: int, table_log: int):
     return rc, (out[: n.value].tobytes() if rc == 0 else b"")
 
 
+class _FseFacts(C.Structure):
+    _fields_ = [("table_log", C.c_uint32), ("zero_bits", C.c_uint32), ("hdr_len", C.c_uint32), ("symbol_len", C.c_uint32),
+                ("max_count", C.c_uint32)]
+
+
+def fse_stream_facts(sym: np.ndarray, nstates: int, table_log: int = 0, want_norm: bool = False):
+    """what fse_compress_tl(sym, nstates, table_log) decides in front of its bitstream: (rc, {table_log, zero_bits (the decoder's
+    flag), hdr_len (bytes in front of the bitstream, the 6-byte prefix included), symbol_len, max_count}); want_norm adds `norm`,
+    the 65536 normalised counts (-1: a symbol of less than one table cell, which gets one)"""
+    sym = np.ascontiguousarray(sym, dtype=np.uint16)
+    f = _FseFacts()
+    norm = np.zeros(65536, np.int32) if want_norm else None
+    rc = lib().mico_fse_stream_facts(_p(sym), C.c_size_t(sym.size), nstates, table_log, C.byref(f), _p(norm) if want_norm else None)
+    if rc:
+        return rc, None
+    facts = {k: int(getattr(f, k)) for k, _ in _FseFacts._fields_}
+    if want_norm:
+        facts["norm"] = norm
+    return rc, facts
+
+
 def fse_decompress_auto(b: bytes, cap: int):
     a = np.frombuffer(bytes(b), dtype=np.uint8)
     out = np.empty(cap, dtype=np.uint16)
