@@ -683,6 +683,13 @@ int mic_hip_debug_fetch_hist(mic_hip_session *s, int i, void *dst, size_t bytes)
     HIP_TRY(hipMemcpy(dst, s->h_units[(size_t)i].hist, bytes, hipMemcpyDeviceToHost));
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): the MIC_TK_PATHS route counts k_enc_tokens_wg left in unit i (MIC_TKP_*, mic_dev.h) after an
+// encode's *_finish
+int mic_hip_debug_tok_paths(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    for (int k = 0; k < MIC_TK_PATHS; k++) out[k] = s->h_units[(size_t)i].tk_paths[k];
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): the first n u16 of unit i's token slab after a *_finish
 int mic_hip_debug_fetch_tok(mic_hip_session *s, int i, void *dst, size_t n) try {
     if (!s || i < 0 || i >= s->n_last || n > s->h_units[(size_t)i].tok_cap) return MIC_ERR_ARGS;

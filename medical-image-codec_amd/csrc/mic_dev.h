@@ -32,6 +32,18 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 // MicUnit.dec_kernel behind the 30 lane-per-state classes (1 .. 30)
 #define MIC_DEC_BY_GL           31u
 #define MIC_DEC_BY_SERIAL       32u
+// MicUnit.tk_paths: routes of k_enc_tokens_wg (mic_encode.hip).  A pass is one walk over a symbol window: one per tile, two for a tile
+// that holds an escape, one more for the flush; a wave-pass is one wave's share of it.
+#define MIC_TKP_FAST            0      // passes that took the fast tile
+#define MIC_TKP_REFUSED         1      // fast votes that were refused (each starts a cool-down)
+#define MIC_TKP_ESC             2      // tiles that held an escape
+#define MIC_TKP_GENERAL         3      // passes that took the general route (the flush included)
+#define MIC_TKP_PERLANE         4      // wave-passes that wrote their boundary threads one position per lane
+#define MIC_TKP_ROUND2          5      // ... of which needed a second round of eight threads
+#define MIC_TKP_SERIAL          6      // wave-passes whose boundary threads (more than sixteen) walked their positions serially
+#define MIC_TKP_PACKED          7      // thread-tiles whose eight symbols came from the packed residuals (symbol units: from the vector load)
+#define MIC_TKP_KIND2           8      // thread-tiles that fetched pixel by pixel
+#define MIC_TK_PATHS            9
 
 struct MicUnit {
     // ---- inputs ------------------------------------------------------------------
@@ -99,6 +111,8 @@ struct MicUnit {
                               // MIC_DEC_BY_GL for k_dec_tans_gl, MIC_DEC_BY_SERIAL for k_dec_tans_serial; 0: nobody (tests/test_gpu_decode_classes.py).  Cleared with the
                               // other results: every enqueue's lay_out() starts each descriptor again from MicUnit{}
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
+    uint32_t tk_paths[MIC_TK_PATHS];   // encode: which routes k_enc_tokens_wg took through the unit (MIC_TKP_*), written once next to ntok;
+                              // read by mic_hip_debug_tok_paths, predicted by tests/tokeniser_paths.py
     // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------
     uint32_t sym_limit;       // 0: the whole stream.  Else the chain kernels that honour it decode only the first
                               // round_up(sym_limit, 128) symbols (whole 128-symbol chunks) and leave ntok < count: a PREFIX unit,

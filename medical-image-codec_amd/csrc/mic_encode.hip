@@ -113,10 +113,12 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
     __shared__ uint32_t s_hist[TK_HWIN];
     __shared__ uint32_t s_tmaxall;
     __shared__ tk_v4 s_item[TK_THREADS / 64][8];                // per wave: the threads whose positions are written one per lane (phase D)
+    __shared__ uint32_t s_paths[MIC_TK_PATHS];                  // the waves' route counts, summed once at the end (MicUnit.tk_paths)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (u.mode != (SRC ? 2u : 0u)) return;                    // bare-FSE units (mode 1) bring their own tokens
     if (SRC && u.status != MICD_OK) return;                   // the symbol producer already failed
     if (tid == 0) { u.status = MICD_OK; u.ntok = 0; u.blob_len = 0; u.nstates_used = 0; u.packed_direct = 0; s_ovf = 0; s_last[0] = s_last[1] = 0; s_tmaxall = 0; s_frun = 0; }
+    if (tid < MIC_TK_PATHS) { s_paths[tid] = 0; u.tk_paths[tid] = 0; }
     const int depth = mic_len16(u.max_value);
     if (!SRC && (u.w <= 0 || u.h <= 0)) { if (tid == 0) u.status = MICD_ERR_ARGS; return; }
     if (depth < 4) { if (tid == 0) u.status = MICD_ERR_UNSUPPORTED; return; }   // see k_enc_tokens_serial
@@ -146,6 +148,9 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
     uint32_t par = 0;                // window parity: every pass over a window flips it
     bool prev_fast = false;          // the pass before took the fast path: run1 is in s_frun
     uint32_t fast_cool = 0;          // passes to go before a fast tile is tried again (a refused try costs a barrier)
+    // Which route ran (MIC_TKP_*) is counted in LDS, by thread 0 for the group's routes and by lane 0 of each wave for a wave's: the
+    // scalar registers are spilling as it is, and a count carried in one costs a vector register in the end.
+    auto tk_note = [&](uint32_t what, uint32_t by) { (void)__hip_atomic_fetch_add(&s_paths[what], by, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
     const uint32_t thr2 = thr | (thr << 16), lim2 = (2 * thr - 2) | ((2 * thr - 2) << 16);
     const uint32_t hlo = (!SRC && delim >= TK_HWIN && thr > TK_HWIN / 2) ? thr - TK_HWIN / 2 : 0u;   // window [hlo, hlo + TK_HWIN)
     const mic_gp<uint32_t> ghist = mic_g(u.hist);
@@ -301,7 +306,12 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
                 for (int k = 0; k < TK_PPT; k++) if ((uint32_t)k < cnt) xs[6 + tid * TK_PPT + k] = (uint16_t)ls[k];
             }
         }
+        {
+            const uint32_t npk = (uint32_t)__popcll(__ballot(pk_ok)), nk2 = (uint32_t)__popcll(__ballot(!flush && gbase < npx && f.kind == 2));
+            if (lane == 0) { if (npk) tk_note(MIC_TKP_PACKED, npk); if (nk2) tk_note(MIC_TKP_KIND2, nk2); }
+        }
         const bool esc_tile = __syncthreads_or(esc) != 0;
+        if (esc_tile && tid == 0) tk_note(MIC_TKP_ESC, 1u);
         if (prev_fast) { run1 = s_frun; prev_fast = false; }    // written behind the fast tile's decision barrier, ordered by this one
         if (esc_tile && pk_ok) {
 #pragma unroll
@@ -385,8 +395,12 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
         bool tile_fast = false;
         if (!flush && !esc_tile && n == TP && c >= 16 && g0 >= 6 && str1 != 0 && g0 >= str1 + 3) {
             if (fast_cool) fast_cool--;
-            else { tile_fast = !__syncthreads_or(lit8 ? 0 : 1); fast_cool = tile_fast ? 0u : 12u; }
+            else {
+                tile_fast = !__syncthreads_or(lit8 ? 0 : 1); fast_cool = tile_fast ? 0u : 12u;
+                if (!tile_fast && tid == 0) tk_note(MIC_TKP_REFUSED, 1u);
+            }
         }
+        if (tid == 0) tk_note(tile_fast ? MIC_TKP_FAST : MIC_TKP_GENERAL, 1u);
         uint32_t run_in = 0, str_in = str1, run_tot = run1, str_tot = str1;
         if (!tile_fast) {
             // exclusive max-scan of the thread-latest starts (positions grow with the thread index)
@@ -487,6 +501,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
         // ---- D: write ----------------------------------------------------------------------------
         uint64_t cf_bal = (TK_ABL & 6) ? 0ull : __ballot(cf && tsum != 0);   // (a thread inside a run owns no token)
         const bool cf_loop = __popcll(cf_bal) > 16;             // too many of them in this wave: the serial walk is cheaper
+        if (cf_loop && lane == 0) tk_note(MIC_TKP_SERIAL, 1u);
         if (lit8) {
             if (pos + TK_SPT + 1 <= cap) {
                 if (bq >= TK_SPT) {
@@ -567,6 +582,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
             bool pending = cf && tsum != 0;
             const uint16_t *xw = xs + 3 + (size_t)wave * 64 * TK_SPT;
             while (bal) {
+                if (lane == 0) tk_note(bal == cf_bal ? MIC_TKP_PERLANE : MIC_TKP_ROUND2, 1u);   // (the first round of eight, a later one)
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
                 const bool mine = pending && rank < 8;
                 if (mine) s_item[wave][rank] = tk_v4{itx, ity, itz, pos};
@@ -647,6 +663,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
     tmax = tk_wave_incl_max(tmax, lane);
     if (lane == 63 && tmax) atomicMax(&s_tmaxall, tmax);
     __syncthreads();
+    if (tid < MIC_TK_PATHS) u.tk_paths[tid] = s_paths[tid];
     if (tid == 0) {
         if (s_ovf || outp > cap) u.status = u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CAPACITY;
         else u.ntok = outp;
