@@ -507,6 +507,45 @@ int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, con
 int mic_hip_wsi_read_patches(const uint8_t *compressed, size_t compressed_len, int level, const int32_t *xy, int n, int pw, int ph,
                              void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
 
+/* Patches of many slides and levels per call (no reference counterpart; what mic_hip_strips_read_crops is to strip files).  The
+ * text of "Many patches per call" above carries over except as stated here.  Patch i = xysl[4i .. 4i + 3] = (x, y, slide, level) is
+ * the rectangle [x, x + pw) x [y, y + ph) of pyramid level `level` of files[slide] (readers[slide]); origins may be negative, a
+ * patch may overhang its level or lie wholly outside it, samples outside the level are 0.  d_out receives n x ph x pw x channels
+ * samples, every byte written; it is a device allocation on the call's device or pinned host memory, judged before anything is
+ * launched (and 2-byte aligned for 16-bit samples, else MIC_ERR_ARGS).
+ * The caller states the call's ONE sample format: channels / bits_per_sample = 3/8, 1/8 or 1/16.  In this order, before a file is
+ * looked at: MIC_ERR_ARGS for pw, ph <= 0, n < 0, nfiles < 0 or a NULL array that is needed (xysl with n > 0; files, lens or readers
+ * with nfiles > 0); MIC_ERR_UNSUPPORTED for any other format pair; MIC_ERR_CAPACITY for out_cap below the tensor's size.  Then
+ * MIC_ERR_ARGS for a slide index outside [0, nfiles); n == 0 is MIC_OK with zeroed stats; d_out == NULL is MIC_ERR_ARGS.
+ * A slide fails alone: a NULL pointer or reader (MIC_ERR_ARGS), a header that is refused or unsupported (the header's code), a
+ * sample format other than the call's (MIC_ERR_ARGS), a tile-index entry of a touched tile that points outside the file
+ * (MIC_ERR_CORRUPT) give that code to status[i] of every patch of that slide, whose samples are all 0; no other slide is affected.
+ * Slides no patch names are not looked at: not parsed, not read through their reader, and may be NULL.  A patch whose level is
+ * outside its slide's [0, levels) gets MIC_ERR_ARGS and zeros.  Otherwise status[i] is MIC_OK or the code of the first failing tile
+ * of patch i in tile-index order, as in mic_hip_wsi_decompress_tile; such a patch's samples are unspecified, every other patch is
+ * exact.  Returns MIC_OK when the call ran, even if patches failed.
+ * Work is the union of the touched tiles over all slides and levels, each entropy-decoded once, ordered by slide, then by global
+ * tile index (level.first + ty * tiles_x + tx).  They go through the unit codec in sub-batches of at most 65535 / P tiles (P planes
+ * a tile) and no more than the workspace ceiling holds of the sub-batch's largest tile; slides of different tile sizes share
+ * sub-batches, a cut may fall anywhere.  Behind each sub-batch one gather launch writes its pieces into d_out.
+ * stats (may be NULL): tiles_decoded and pieces are the planner's counts, slabs the number of decode chains, slides_read the
+ * number of named slides whose header was accepted (format included).
+ * One device: the calling thread's default session; no fan-out over mic_hip_set_devices.  There is no session-store form: a
+ * session's store holds one slide. */
+typedef struct { uint64_t tiles_decoded, pieces, slabs, slides_read; } mic_hip_multi_patch_stats;
+/* The host planner of those calls: needs no device and reads only headers, level tables and tile indexes.  slide_of[u] / tile_of[u]
+ * (cap entries each) receive the units in decode order; *ntiles_out their number, *npieces the number of patch-tile overlaps with
+ * non-empty area (both may be NULL); file_status[nfiles] (may be NULL) each slide's code, MIC_OK for slides no patch names.  More
+ * than cap units: MIC_ERR_CAPACITY with the counts and file_status set and the arrays untouched.  More than 2^31 - 1 pieces:
+ * MIC_ERR_UNSUPPORTED. */
+int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                 const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                 uint32_t *slide_of, uint64_t *tile_of, size_t cap,
+                                 uint64_t *ntiles_out, uint64_t *npieces, int32_t *file_status);
+int mic_hip_wsi_multi_read_patches(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                   const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats);
+
 /* ---- MIC3 streaming: a row-push writer and a random-access reader ------------------------------- */
 /* For slides too large for one host buffer (the reference's "WSI streaming API" roadmap item, io.ReaderAt / io.WriteSeeker).
  * pwrite-like sink: write len bytes at an absolute offset, 0 = success.  The ranges of one file never overlap.
@@ -553,6 +592,13 @@ int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x
  * pass, each once, contiguous ones in one read; nothing else of the file is read. */
 int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats);
+/* mic_hip_wsi_multi_read_patches through readers (slide = an index into readers[]): each named slide's blobs are pulled in one
+ * request, each once, contiguous ones in one read; a reader no patch names is never called and may be NULL.  A callback that
+ * fails makes the call MIC_ERR_IO before anything is launched (d_out is then untouched).  Every distinct named reader is locked
+ * once, in address order: a reader listed twice, or two threads that pass the same readers in different orders, do not deadlock. */
+int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
+                                     const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats);
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r);
 /* MIC2 reader: mic_hip_mic2_read_crops on a file behind a pread-like source.  open pulls the 20-byte header and then the
  * 8 * nframes-byte frame table through the callback, and nothing else, and validates them as mic_hip_mic2_info does; open and

@@ -130,6 +130,11 @@ class PatchStats(C.Structure):
     _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class MultiPatchStats(C.Structure):
+    """mic_hip_multi_patch_stats"""
+    _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64), ("slides_read", C.c_uint64)]
+
+
 class CropStats(C.Structure):
     """mic_hip_crop_stats"""
     _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
@@ -169,6 +174,7 @@ ABI_SYMBOLS = [
     "mic_hip_wsi_compress", "mic_hip_wsi_compress_ex", "mic_hip_wsi_format", "mic_hip_wsi_info", "mic_hip_wsi_level_info",
     "mic_hip_wsi_decompress_tile", "mic_hip_wsi_decompress_level", "mic_hip_wsi_decompress_region",
     "mic_hip_wsi_patch_plan", "mic_hip_wsi_read_patches", "mic_hip_wsi_reader_read_patches", "mic_hip_session_wsi_read_patches",
+    "mic_hip_wsi_multi_patch_plan", "mic_hip_wsi_multi_read_patches", "mic_hip_wsi_readers_read_patches",
     "mic_hip_wsi_writer_open", "mic_hip_wsi_writer_push_rows", "mic_hip_wsi_writer_finish", "mic_hip_wsi_writer_device_bytes",
     "mic_hip_wsi_writer_stats", "mic_hip_wsi_writer_close",
     "mic_hip_wsi_reader_open", "mic_hip_wsi_reader_info", "mic_hip_wsi_reader_decompress_tile", "mic_hip_wsi_reader_decompress_region",
@@ -284,6 +290,12 @@ def lib() -> C.CDLL:
     L.mic_hip_wsi_read_patches.argtypes = [C.c_void_p, C.c_size_t] + _patch_args
     L.mic_hip_wsi_reader_read_patches.argtypes = [C.c_void_p] + _patch_args
     L.mic_hip_session_wsi_read_patches.argtypes = [C.c_void_p] + _patch_args
+    _multi_patch_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]            # xysl, n, pw, ph, channels, bits_per_sample
+    _multi_patch_out = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(MultiPatchStats)]
+    L.mic_hip_wsi_multi_patch_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _multi_patch_args + [
+        C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.mic_hip_wsi_multi_read_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _multi_patch_args + _multi_patch_out
+    L.mic_hip_wsi_readers_read_patches.argtypes = [C.c_void_p, C.c_int] + _multi_patch_args + _multi_patch_out
     L.mic_hip_wsi_reader_close.restype = None
     L.mic_hip_session_destroy.restype = None
     L.mic_hip_compress_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int,
@@ -1096,6 +1108,57 @@ def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, o
     return st, stats
 
 
+def _patch_xysl(xysl) -> np.ndarray:
+    """(n, 4) patches (x, y, slide, level) as the int32 quadruples the C calls take"""
+    return np.ascontiguousarray(np.asarray(xysl, dtype=np.int64).reshape(-1, 4).astype(np.int32))
+
+
+def wsi_multi_patch_plan(files, xysl, pw: int, ph: int, channels: int = 3, bits_per_sample: int = 8, cap: Optional[int] = None):
+    """mic_hip_wsi_multi_patch_plan: (uint32 slide of each tile the patches need entropy-decoded, uint64 global tile index of each
+    -- ascending by slide, then tile, each once --, number of patch-tile pieces, int32 status of each file).  Needs no device.
+    cap: room for that many tiles (default: as many as it takes); too few raises MicError (MIC_ERR_CAPACITY) whose ``ntiles``,
+    ``pieces`` and ``file_status`` attributes are the counts and the files' codes."""
+    arrs, ptrs, lens = _file_table(files)
+    a = _patch_xysl(xysl)
+    nt, npc = C.c_uint64(0), C.c_uint64(0)
+    fs = np.zeros(max(len(arrs), 1), dtype=np.int32)
+    head = (ptrs.ctypes.data, lens.ctypes.data, len(arrs), a.ctypes.data, len(a), pw, ph, channels, bits_per_sample)
+    if cap is None:
+        rc = lib().mic_hip_wsi_multi_patch_plan(*head, None, None, 0, C.byref(nt), C.byref(npc), fs.ctypes.data)
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "wsi_multi_patch_plan")
+        cap = nt.value
+    slide_of, tile_of = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64)
+    rc = lib().mic_hip_wsi_multi_patch_plan(*head, slide_of.ctypes.data, tile_of.ctypes.data, cap, C.byref(nt), C.byref(npc), fs.ctypes.data)
+    if rc:
+        e = MicError(rc, "wsi_multi_patch_plan")
+        e.ntiles, e.pieces, e.file_status = nt.value, npc.value, fs[: len(arrs)].copy()
+        raise e
+    return slide_of[: nt.value].copy(), tile_of[: nt.value].copy(), npc.value, fs[: len(arrs)].copy()
+
+
+def _read_multi_patches(call, xysl, d_out: int, out_cap: int):
+    a = _patch_xysl(xysl)
+    st = np.zeros(len(a), dtype=np.int32)
+    ps = MultiPatchStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, C.byref(ps))
+    return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs, slides_read=ps.slides_read)
+
+
+def wsi_multi_read_patches(files, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8):
+    """mic_hip_wsi_multi_read_patches: the pw x ph patches (x, y, slide, level) `xysl` of the MIC3 files `files` (host buffers;
+    slide = an index into the list), into the caller's device tensor d_out (an int:
+    ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit greyscale; or pinned host
+    memory) of out_cap bytes.  Every file must have the call's sample format; one that has not, or does not parse, fails alone.
+    Pixels outside a level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs, slides_read))."""
+    arrs, ptrs, lens = _file_table(files)
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: lib().mic_hip_wsi_multi_read_patches(
+        ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
+    if rc:
+        _raise(rc, "wsi_multi_read_patches")
+    return st, stats
+
+
 class _Callback:
     """A ctypes callback that never lets an exception pass as success: the first exception it meets is kept, the callback
     returns non-zero (the library then reports MIC_ERR_IO), and the caller re-raises it once the C call has returned.
@@ -1270,6 +1333,21 @@ class WsiReader:
             self.close()
         except Exception:
             pass
+
+
+def wsi_readers_read_patches(readers, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8):
+    """mic_hip_wsi_readers_read_patches: wsi_multi_read_patches over a sequence of WsiReader (slide = an index into it; an entry
+    no patch names may be None and is never read).  Only the blobs of the tiles the patches touch are read, each once."""
+    readers = list(readers)
+    hs = np.asarray([(r._h.value or 0) if r is not None else 0 for r in readers], dtype=np.uintp)
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: lib().mic_hip_wsi_readers_read_patches(
+        hs.ctypes.data, len(readers), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
+    for r in readers:                                  # an exception a source raised comes first
+        if r is not None and r._cb.exc is not None:
+            r._cb.check(rc, "wsi_readers_read_patches")
+    if rc:
+        _raise(rc, "wsi_readers_read_patches")
+    return st, stats
 
 
 class Mic2Reader:

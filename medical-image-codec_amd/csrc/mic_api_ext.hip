@@ -189,6 +189,66 @@ __global__ void __launch_bounds__(256) k_fill_planes(uint16_t *planes, size_t np
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint16_t)f.y;
 }
 
+// ---- patches of many slides and levels: tiles of different sizes in one slab, pieces that carry their own tile geometry -----------
+// Tile u of a sub-batch has its P planes at a sample offset of its own in the slab (the prefix sum of P * tw * th over the
+// sub-batch), so a constant plane is a span of the slab ...
+struct FillSpan { uint64_t off; uint32_t npx, value; };
+// constant planes of such a slab in one launch: grid = (chunks, spans)
+__global__ void __launch_bounds__(256) k_fill_spans(uint16_t *slab, const FillSpan *fill) {
+    const FillSpan f = fill[blockIdx.y];
+    uint16_t *p = slab + f.off;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < f.npx; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint16_t)f.value;
+}
+// ... and a piece says where its first sample lies in plane 0 (src, samples into the slab), how far apart the tile's rows (stride =
+// tw) and planes (pstride = tw * th) are, and where its w x h samples go: (dx, dy) of patch `patch`.  The host plans them
+// (multi_plan): the kernels divide nothing.
+struct MultiPiece { uint64_t src; int32_t patch, stride, pstride, dx, dy, w, h, pad; };
+
+// k_wsi_gather_patches for such pieces.  slab: a sub-batch's planes; out: [patch][ph][pw][3] u8.  grid = (pieces, row chunks); lanes
+// along x of a piece row (piece_lanes): a wave reads 64 neighbouring samples of each plane and writes 192 neighbouring bytes.
+__global__ void __launch_bounds__(256) k_wsi_multi_gather(const uint16_t *slab, const MultiPiece *pieces, uint8_t *out, int pw, int ph) {
+    const MultiPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
+    const mic_gp<uint8_t> o = mic_g(out + (((size_t)pc.patch * ph + pc.dy) * pw + pc.dx) * 3);
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const size_t si = (size_t)y * pc.stride, di = (size_t)y * pw * 3;
+        for (int x = ln.col; x < pc.w; x += ln.lw) {
+            const int yv = py[si + x];
+            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
+            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, :113-116
+            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
+            const int t = yv - (cg >> 1);                                                   // YCoCgRInverse, asm_amd64.go:106-121
+            const int g = cg + t;
+            const int b = t - (co >> 1);
+            const int r = co + b;
+            const size_t d = di + (size_t)x * 3;
+            o[d] = (uint8_t)r; o[d + 1] = (uint8_t)g; o[d + 2] = (uint8_t)b;
+        }
+    }
+}
+// k_wsi_gather_patches_grey for such pieces.  out: [patch][ph][pw] T.  16-bit samples: a row whose source and destination are both
+// 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16 -- with an odd tile or patch width every
+// second row is such a row (as k_strips_gather_crops).
+template <typename T>
+__global__ void __launch_bounds__(256) k_wsi_multi_gather_grey(const uint16_t *slab, const MultiPiece *pieces, T *out, int pw, int ph) {
+    const MultiPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const uint16_t *src = slab + pc.src;
+    T *dst = out + ((size_t)pc.patch * ph + pc.dy) * pw + pc.dx;
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * pc.stride);
+        const mic_gp<T> d = mic_g(dst + (size_t)y * pw);
+        if (sizeof(T) == 2 && (((size_t)s | (size_t)d) & 3) == 0) {
+            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
+            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
+            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
+            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = (T)s[pc.w - 1];
+        } else
+            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = (T)s[x];
+    }
+}
+
 struct Level { int w, h, tx, ty, first; };
 
 // autoLevelCount + computeLevels (wsiformat.go:244-285) with the truncation of wsicompress.go:47-77
@@ -925,6 +985,273 @@ int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *
         return MIC_OK;
     });
 }
+
+// ---- patches of many slides and levels ------------------------------------------------------------------------------------------
+// A slide of the call: where its header, level table and tile index are read (host; a file in memory starts there) and what they
+// said.  m: a header parsed before (a reader's), else `own` is parsed from head.
+struct MultiSlide {
+    const uint8_t *head = nullptr; uint64_t file_len = 0;
+    const Mic3 *m = nullptr; Mic3 own;
+    bool named = false;                     // some patch names it: only then is it looked at
+    bool header_ok = false;                 // its header was accepted, the call's sample format included
+    int32_t status = MIC_OK;
+    const Mic3 &hdr() const { return m ? *m : own; }
+};
+struct MultiUnit { uint32_t slide; uint64_t tile; };                                        // tile: global index, level.first + ty * tiles_x + tx
+struct MultiPlanned { int32_t patch; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
+struct MultiPlan {
+    std::vector<MultiSlide> slides;
+    std::vector<MultiUnit> units;           // the tiles to entropy-decode, ascending by slide, then tile, each once
+    std::vector<MultiPlanned> pieces;       // sorted by unit (stable: patch order inside a unit)
+    std::vector<size_t> first;              // first[u] .. first[u + 1]: the pieces of units[u]
+};
+
+// the tile-index entry of global tile gi: false when it points outside the file (as flat_source and the reader's fetch judge it)
+bool multi_tile_entry(const MultiSlide &sl, uint64_t gi, uint64_t *off, uint64_t *len) {
+    const Mic3 &m = sl.hdr();
+    if (gi >= m.total) return false;
+    const uint8_t *e = sl.head + 48 + 20 * (size_t)m.nlev + 16 * (size_t)gi;
+    const uint64_t bo = get_u64(e), bl = get_u64(e + 8);
+    if (bo > sl.file_len || bl > sl.file_len || m.data_off + bo + bl > sl.file_len) return false;
+    *off = m.data_off + bo; *len = bl;
+    return true;
+}
+
+// The plan of n patches of pw x ph over the slides (head, file_len, m set by the caller), patch i = q[4i .. 4i + 3] = (x, y, slide,
+// level), for a call whose sample format is channels / bps.  MIC_ERR_ARGS for a slide index outside the list; a slide that is refused
+// keeps its code in slides[f].status and its patches have no pieces; nor has a patch whose level its slide does not have.
+int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int channels, int bps) {
+    const int ns = (int)plan.slides.size();
+    plan.units.clear(); plan.pieces.clear(); plan.first.assign(1, 0);
+    for (int i = 0; i < n; i++) {
+        const int32_t f = q[4 * (size_t)i + 2];
+        if (f < 0 || f >= ns) return MIC_ERR_ARGS;
+        plan.slides[(size_t)f].named = true;
+    }
+    for (MultiSlide &sl : plan.slides) {
+        if (!sl.named) continue;
+        if (!sl.head) { sl.status = MIC_ERR_ARGS; continue; }
+        if (!sl.m && (sl.status = parse_mic3(sl.head, (size_t)sl.file_len, sl.own)) != MIC_OK) continue;
+        const Mic3 &m = sl.hdr();
+        if (!m.supported()) sl.status = MIC_ERR_UNSUPPORTED;
+        else if (m.channels != channels || m.bps != bps) sl.status = MIC_ERR_ARGS;
+        sl.header_ok = sl.status == MIC_OK;
+    }
+    struct Key { uint32_t slide; uint64_t tile; MultiPlanned pc; };
+    std::vector<Key> all;
+    for (int i = 0; i < n; i++) {
+        const uint32_t f = (uint32_t)q[4 * (size_t)i + 2];
+        const MultiSlide &sl = plan.slides[f];
+        if (sl.status != MIC_OK) continue;
+        const Mic3 &m = sl.hdr();
+        const int32_t level = q[4 * (size_t)i + 3];
+        if (level < 0 || level >= (int)m.lv.size()) continue;
+        const Level &L = m.lv[(size_t)level];
+        const int64_t tw = m.tw, th = m.th, px = q[4 * (size_t)i], py = q[4 * (size_t)i + 1];
+        const int64_t x0 = std::max<int64_t>(px, 0), x1 = std::min<int64_t>(px + pw, L.w);
+        const int64_t y0 = std::max<int64_t>(py, 0), y1 = std::min<int64_t>(py + ph, L.h);
+        if (x0 >= x1 || y0 >= y1) continue;
+        for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
+            const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
+            all.push_back(Key{ f, (uint64_t)((int64_t)L.first + ty * L.tx + tx),
+                               MultiPlanned{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py), (int32_t)(bx - ax), (int32_t)(by - ay) } });
+        }
+    }
+    if (all.size() > 0x7FFFFFFFu) return MIC_ERR_UNSUPPORTED;                              // (pieces are a launch's grid x)
+    std::stable_sort(all.begin(), all.end(), [](const Key &a, const Key &b) { return a.slide != b.slide ? a.slide < b.slide : a.tile < b.tile; });
+    // a touched tile whose index entry points outside the file fails its slide
+    uint64_t off, len;
+    for (size_t k = 0; k < all.size(); k++)
+        if ((k == 0 || all[k].slide != all[k - 1].slide || all[k].tile != all[k - 1].tile) && plan.slides[all[k].slide].status == MIC_OK &&
+            !multi_tile_entry(plan.slides[all[k].slide], all[k].tile, &off, &len)) plan.slides[all[k].slide].status = MIC_ERR_CORRUPT;
+    plan.first.clear();
+    for (const Key &k : all) {
+        if (plan.slides[k.slide].status != MIC_OK) continue;
+        if (plan.units.empty() || plan.units.back().slide != k.slide || plan.units.back().tile != k.tile) {
+            if (plan.units.size() >= 0xFFFFFFFEu) return MIC_ERR_UNSUPPORTED;
+            plan.units.push_back(MultiUnit{ k.slide, k.tile });
+            plan.first.push_back(plan.pieces.size());
+        }
+        plan.pieces.push_back(k.pc);
+        plan.pieces.back().unit = (uint32_t)(plan.units.size() - 1);
+    }
+    plan.first.push_back(plan.pieces.size());
+    return MIC_OK;
+}
+
+// what the entry points check before a file is looked at; *need = bytes of the patch tensor
+int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps, size_t out_cap, size_t *need) {
+    if (pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xysl)) return MIC_ERR_ARGS;
+    if (!((channels == 3 && bps == 8) || (channels == 1 && (bps == 8 || bps == 16)))) return MIC_ERR_UNSUPPORTED;   // (Mic3::supported)
+    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ph * (unsigned)pw * (size_t)(channels * (bps == 16 ? 2 : 1));
+    if (bytes > out_cap) return MIC_ERR_CAPACITY;
+    *need = (size_t)bytes;
+    return MIC_OK;
+}
+
+// The plan's tiles (blobs[u]: the blob of units[u], host) into d_out (an address s's device can write: patch_pointer) on a session the
+// caller holds.  Sub-batches of tiles through the unit codec: tile u's P planes start slab_off[u] samples into the sub-batch's slab
+// (the prefix sum of P * tw * th), constant planes are spans filled there, raw planes copied there, streams decoded there; behind
+// each sub-batch one gather launch writes its pieces.  tile_status[u]: the blob's code, else its first failing plane's.
+int multi_read(mic_hip_session *s, const MultiPlan &plan, const std::vector<TileBlob> &blobs, size_t P, int bps, int pw, int ph,
+               void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
+    const size_t nu = plan.units.size();
+    int rc;
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the levels, refused slides and patches
+    tile_status.assign(nu, MIC_OK);
+    *nslab = 0;
+    if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
+    auto hdr = [&](size_t u) -> const Mic3 & { return plan.slides[plan.units[u].slide].hdr(); };
+    // cuts: as many tiles as the workspace ceiling holds of the largest of them, at most what one launch chain takes
+    std::vector<size_t> px(nu), cuts{ 0 };
+    for (size_t u = 0; u < nu; u++) px[u] = (size_t)hdr(u).tw * hdr(u).th;
+    std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds)
+    auto cap_for = [&](size_t npx) {
+        for (const auto &c : caps) if (c.first == npx) return c.second;
+        caps.emplace_back(npx, std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)));
+        return caps.back().second;
+    };
+    while (cuts.back() < nu) {
+        size_t i1 = cuts.back(), mp = 0;
+        while (i1 < nu) {
+            const size_t m2 = std::max(mp, px[i1]);
+            if (i1 > cuts.back() && i1 - cuts.back() + 1 > cap_for(m2)) break;
+            mp = m2; i1++;
+        }
+        cuts.push_back(i1);
+    }
+    std::vector<uint64_t> slab_off(nu);
+    size_t slab_max = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        size_t off = 0;
+        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += P * px[u]; }
+        slab_max = std::max(slab_max, off);
+    }
+    std::vector<MultiPiece> list(plan.pieces.size());
+    for (size_t k = 0; k < list.size(); k++) {
+        const MultiPlanned &p = plan.pieces[k];
+        const Mic3 &m = hdr(p.unit);
+        list[k] = MultiPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)m.tw + (uint64_t)p.sx, p.patch, m.tw, (int32_t)px[p.unit], p.dx, p.dy, p.w, p.h, 0 };
+    }
+    if ((rc = s->wsi_multi_pieces.reserve(list.size() * sizeof(MultiPiece) + 64))) return rc;
+    if ((rc = s->wsi_planes.reserve(slab_max * 2 + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->wsi_multi_pieces.p, list.data(), list.size() * sizeof(MultiPiece), hipMemcpyHostToDevice, s->stream));
+    const MultiPiece *d_list = (const MultiPiece *)s->wsi_multi_pieces.p;
+    uint16_t *slab = (uint16_t *)s->wsi_planes.p;
+    std::vector<WsiPlane> pl; std::vector<uint8_t> bytes; std::vector<FillSpan> fills;
+    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<size_t> unit_tile; std::vector<int32_t> ust;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        const size_t u0 = cuts[b], nt = cuts[b + 1] - u0;
+        pl.clear(); bytes.clear(); fills.clear(); units.clear(); begins.clear(); ends.clear(); unit_tile.clear();
+        for (size_t k = 0; k < nt; k++) {                                                   // the blobs checked on the host, their bytes up in one copy
+            const size_t b0 = bytes.size();
+            if ((tile_status[u0 + k] = parse_tile_blob(hdr(u0 + k), blobs[u0 + k].p, blobs[u0 + k].len, pl, bytes)) != MIC_OK) {
+                bytes.resize(b0);
+                pl.resize(k * P);
+                pl.resize((k + 1) * P, WsiPlane{ 0, 0, 0, 0 });
+            }
+        }
+        if ((rc = s->io_comp.reserve(bytes.size() + 64))) return rc;
+        const uint8_t *base = (const uint8_t *)s->io_comp.p;
+        if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
+        for (size_t q = 0; q < nt * P; q++) {
+            const WsiPlane &wp = pl[q];
+            const size_t u = u0 + q / P, npx = px[u];
+            const uint64_t at = slab_off[u] + (q % P) * npx;
+            if (wp.mode <= 1) fills.push_back(FillSpan{ at, (uint32_t)npx, wp.mode ? wp.value : 0u });
+            else if (wp.mode == 2) { units.push_back(mic_hip_unit{ at, hdr(u).tw, hdr(u).th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); unit_tile.push_back(u); }
+            else HIP_TRY(hipMemcpyAsync(slab + at, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
+        }
+        if (!fills.empty()) {
+            if ((rc = s->wsi_stats.reserve(fills.size() * sizeof(FillSpan) + 64))) return rc;
+            HIP_TRY(hipMemcpyAsync(s->wsi_stats.p, fills.data(), fills.size() * sizeof(FillSpan), hipMemcpyHostToDevice, s->stream));
+            s->timer.reset(s->stream); s->timer.mark("k_fill_spans");
+            for (size_t f0 = 0; f0 < fills.size(); f0 += kMaxGridY)
+                hipLaunchKernelGGL(k_fill_spans, dim3(4, (unsigned)std::min<size_t>(kMaxGridY, fills.size() - f0)), dim3(256), 0, s->stream, slab, (const FillSpan *)s->wsi_stats.p + f0);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!units.empty()) {
+            if ((rc = session_decode_enqueue_spans(s, base, begins.data(), ends.data(), units.data(), (int)units.size(), slab))) return rc;
+            ust.resize(units.size());
+            if ((rc = session_decode_finish(s, ust.data()))) return rc;
+            for (size_t k = 0; k < ust.size(); k++) if (tile_status[unit_tile[k]] == MIC_OK) tile_status[unit_tile[k]] = ust[k];
+        }
+        const size_t p0 = plan.first[u0], np = plan.first[u0 + nt] - p0;
+        int mw = 1, mh = 1;
+        for (size_t k = p0; k < p0 + np; k++) { mw = std::max(mw, plan.pieces[k].w); mh = std::max(mh, plan.pieces[k].h); }
+        const dim3 grid((unsigned)np, row_chunks(mw, mh)), block(256);                      // (np >= 1: every unit has a piece; np <= 2^31 - 1: multi_plan)
+        s->timer.reset(s->stream); s->timer.mark("k_wsi_multi_gather");
+        if (P == 3) hipLaunchKernelGGL(k_wsi_multi_gather, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint8_t *)d_out, pw, ph);
+        else if (bps == 16) hipLaunchKernelGGL(k_wsi_multi_gather_grey<uint16_t>, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint16_t *)d_out, pw, ph);
+        else hipLaunchKernelGGL(k_wsi_multi_gather_grey<uint8_t>, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint8_t *)d_out, pw, ph);
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+        if (units.empty()) HIP_TRY(hipStreamSynchronize(s->stream));                        // (session_decode_finish has waited otherwise: bytes and fills are reused)
+        ++*nslab;
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return MIC_OK;
+}
+
+// slide `f`'s blobs of `tiles` (global indices, entries checked by the plan) through its reader; NULL: the slides are files in memory
+typedef std::function<int(uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep)> MultiFetch;
+
+// a door's call on a plan whose slides are set: arguments judged (multi_args), then the plan, n == 0, the pointer, the blobs, the core
+int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, int n, int pw, int ph, int channels, int bps,
+               void *d_out, size_t need, int32_t *status, mic_hip_multi_patch_stats *stats) {
+    int rc = multi_plan(plan, xysl, n, pw, ph, channels, bps);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_multi_patch_stats{ 0, 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    DefaultLease lease;
+    if ((rc = lease.acquire())) return rc;
+    mic_hip_session *s = cur_default();
+    if ((rc = patch_pointer(s, &d_out, need))) return rc;                                   // judged before anything is launched
+    if (bps == 16 && ((size_t)d_out & 1)) return MIC_ERR_ARGS;
+    const size_t nu = plan.units.size();
+    std::vector<TileBlob> blobs; blobs.reserve(nu);
+    std::vector<std::vector<uint8_t>> keep;
+    std::vector<size_t> tiles;
+    for (size_t u = 0; u < nu;) {                                                           // each slide's blobs in one request
+        const uint32_t f = plan.units[u].slide;
+        size_t v = u;
+        tiles.clear();
+        for (; v < nu && plan.units[v].slide == f; v++) tiles.push_back((size_t)plan.units[v].tile);
+        if (fetch) {
+            std::vector<TileBlob> got;
+            keep.emplace_back();
+            if ((rc = fetch(f, tiles, got, keep.back()))) return rc;
+            if (got.size() != tiles.size()) return MIC_ERR_INTERNAL;
+            blobs.insert(blobs.end(), got.begin(), got.end());
+        } else {
+            uint64_t off = 0, len = 0;
+            for (size_t gi : tiles) {
+                if (!multi_tile_entry(plan.slides[f], gi, &off, &len)) return MIC_ERR_INTERNAL;   // (the plan has checked it)
+                blobs.push_back(TileBlob{ plan.slides[f].head + off, (size_t)len });
+            }
+        }
+        u = v;
+    }
+    std::vector<int32_t> tst;
+    uint64_t nslab = 0;
+    if ((rc = multi_read(s, plan, blobs, channels == 3 ? 3 : 1, bps, pw, ph, d_out, need, tst, &nslab))) return rc;
+    if (status) {
+        for (int i = 0; i < n; i++) {
+            const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]];
+            const int32_t level = xysl[4 * (size_t)i + 3];
+            status[i] = sl.status != MIC_OK ? sl.status : (level < 0 || level >= (int)sl.hdr().lv.size()) ? MIC_ERR_ARGS : MIC_OK;
+        }
+        for (const MultiPlanned &p : plan.pieces) if (status[p.patch] == MIC_OK) status[p.patch] = tst[p.unit];   // (pieces: in tile order)
+    }
+    if (stats) {
+        uint64_t read = 0;
+        for (const MultiSlide &sl : plan.slides) read += sl.header_ok ? 1 : 0;
+        *stats = mic_hip_multi_patch_stats{ nu, plan.pieces.size(), nslab, read };
+    }
+    return MIC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1144,6 +1471,41 @@ int mic_hip_wsi_read_patches(const uint8_t *c, size_t len, int level, const int3
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
     return wsi_patches(flat_source(c, len, m), m, level, xy, n, pw, ph, d_out, need, status, stats);
+} MIC_ABI_CATCH
+
+// multi_plan behind the two multi-slide calls: the (slide, tile) units n patches need decoded and the number of pieces
+int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                 const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                 uint32_t *slide_of, uint64_t *tile_of, size_t cap,
+                                 uint64_t *ntiles_out, uint64_t *npieces, int32_t *file_status) try {
+    if (nfiles < 0 || (nfiles > 0 && (!files || !lens)) || (cap > 0 && (!slide_of || !tile_of))) return MIC_ERR_ARGS;
+    size_t need = 0;
+    int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, SIZE_MAX, &need);
+    if (rc) return rc;
+    MultiPlan plan;
+    plan.slides.resize((size_t)nfiles);
+    for (int f = 0; f < nfiles; f++) { plan.slides[(size_t)f].head = files[f]; plan.slides[(size_t)f].file_len = lens[f]; }
+    if ((rc = multi_plan(plan, xysl, n, pw, ph, channels, bits_per_sample))) return rc;
+    if (file_status) for (int f = 0; f < nfiles; f++) file_status[f] = plan.slides[(size_t)f].status;
+    if (ntiles_out) *ntiles_out = plan.units.size();
+    if (npieces) *npieces = plan.pieces.size();
+    if (plan.units.size() > cap) return MIC_ERR_CAPACITY;
+    for (size_t u = 0; u < plan.units.size(); u++) { slide_of[u] = plan.units[u].slide; tile_of[u] = plan.units[u].tile; }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// n patches of many MIC3 files in host memory, any levels, into a tensor on the default session's device
+int mic_hip_wsi_multi_read_patches(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                   const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) try {
+    if (nfiles < 0 || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
+    size_t need = 0;
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, out_cap, &need);
+    if (rc) return rc;
+    MultiPlan plan;
+    plan.slides.resize((size_t)nfiles);
+    for (int f = 0; f < nfiles; f++) { plan.slides[(size_t)f].head = files[f]; plan.slides[(size_t)f].file_len = lens[f]; }
+    return multi_call(plan, nullptr, xysl, n, pw, ph, channels, bits_per_sample, d_out, need, status, stats);
 } MIC_ABI_CATCH
 
 }  // extern "C"
@@ -1743,6 +2105,38 @@ int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int3
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
     return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, d_out, need, status, stats);
+} MIC_ABI_CATCH
+
+// mic_hip_wsi_multi_read_patches through readers.  Only the readers some patch names are touched: each distinct one is locked once,
+// in address order (one order for every caller), and asked for its blobs in one fetch.
+int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
+                                     const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) try {
+    if (nreaders < 0 || (nreaders > 0 && !readers)) return MIC_ERR_ARGS;
+    size_t need = 0;
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, out_cap, &need);
+    if (rc) return rc;
+    std::vector<mic_hip_wsi_reader *> named;
+    for (int i = 0; i < n; i++) {
+        const int32_t f = xysl[4 * (size_t)i + 2];
+        if (f < 0 || f >= nreaders) return MIC_ERR_ARGS;
+        if (readers[f]) named.push_back(readers[f]);
+    }
+    std::sort(named.begin(), named.end(), std::less<mic_hip_wsi_reader *>());
+    named.erase(std::unique(named.begin(), named.end()), named.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve(named.size());
+    for (mic_hip_wsi_reader *r : named) locks.emplace_back(r->mu);
+    MultiPlan plan;
+    plan.slides.resize((size_t)nreaders);
+    for (int i = 0; i < n; i++) {
+        const size_t f = (size_t)xysl[4 * (size_t)i + 2];
+        mic_hip_wsi_reader *r = readers[f];
+        if (r) { plan.slides[f].head = r->head.data(); plan.slides[f].file_len = r->file_len; plan.slides[f].m = &r->m; }
+    }
+    return multi_call(plan, [&](uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
+        return readers[f]->fetch(tiles, blobs, keep);
+    }, xysl, n, pw, ph, channels, bits_per_sample, d_out, need, status, stats);
 } MIC_ABI_CATCH
 
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
