@@ -140,74 +140,26 @@ __global__ void __launch_bounds__(256) k_wsi_plane_to_grey(const uint16_t *plane
     }
 }
 
-// ---- patches: many rectangles of one level, gathered from the decoded planes into an n x ph x pw x C tensor -----------------------
-// A piece is one patch-tile overlap: w x h pixels from (sx, sy) of the tile in slab slot `slot` to (dx, dy) of patch `patch`.
-// The host plans them (plan_patches): the kernels divide nothing.
-struct PatchPiece { int32_t patch, slot, sx, sy, dx, dy, w, h; };
-
-// YCoCgRInverse (asm_amd64.go:106-121) of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at
-// whatever byte offset the patch row has.  planes: [slot][3][tw * th] u16; out: [patch][ph][pw][3] u8.
-__global__ void __launch_bounds__(256) k_wsi_gather_patches(const uint16_t *planes, int tw, int th, const PatchPiece *pieces,
-                                                          uint8_t *out, int pw, int ph) {
-    const PatchPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const size_t npx = (size_t)tw * th;
-    const mic_gp<const uint16_t> py = mic_g(planes + (size_t)pc.slot * 3 * npx + (size_t)pc.sy * tw + pc.sx), pco = py + npx, pcg = pco + npx;
-    const mic_gp<uint8_t> o = mic_g(out + (((size_t)pc.patch * ph + pc.dy) * pw + pc.dx) * 3);
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const size_t si = (size_t)y * tw, di = (size_t)y * pw * 3;
-        for (int x = ln.col; x < pc.w; x += ln.lw) {
-            const int yv = py[si + x];
-            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
-            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, :113-116
-            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
-            const int t = yv - (cg >> 1);
-            const int g = cg + t;
-            const int b = t - (co >> 1);
-            const int r = co + b;
-            const size_t d = di + (size_t)x * 3;
-            o[d] = (uint8_t)r; o[d + 1] = (uint8_t)g; o[d + 2] = (uint8_t)b;
-        }
-    }
-}
-// uint16ToBytes (wsicompress.go:589-603) of the piece's samples.  planes: [slot][tw * th] u16; out: [patch][ph][pw] T.
-template <typename T>
-__global__ void __launch_bounds__(256) k_wsi_gather_patches_grey(const uint16_t *planes, int tw, int th, const PatchPiece *pieces,
-                                                               T *out, int pw, int ph) {
-    const PatchPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const mic_gp<const uint16_t> src = mic_g(planes + (size_t)pc.slot * tw * th + (size_t)pc.sy * tw + pc.sx);
-    const mic_gp<T> o = mic_g(out + ((size_t)pc.patch * ph + pc.dy) * pw + pc.dx);
-    for (int y = ln.row; y < pc.h; y += ln.rstep)
-        for (int x = ln.col; x < pc.w; x += ln.lw) o[(size_t)y * pw + x] = (T)src[(size_t)y * tw + x];
-}
-
-// constant planes of a slab in one launch: grid = (chunks, planes); fill[k] = {plane index, value}
-__global__ void __launch_bounds__(256) k_fill_planes(uint16_t *planes, size_t npx, const uint2 *fill) {
-    const uint2 f = fill[blockIdx.y];
-    uint16_t *p = planes + (size_t)f.x * npx;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint16_t)f.y;
-}
-
-// ---- patches of many slides and levels: tiles of different sizes in one slab, pieces that carry their own tile geometry -----------
+// ---- patches: many rectangles of many tiles, gathered from the decoded planes into an n x ph x pw x C tensor -----------------------
 // Tile u of a sub-batch has its P planes at a sample offset of its own in the slab (the prefix sum of P * tw * th over the
-// sub-batch), so a constant plane is a span of the slab ...
+// sub-batch: tiles of different sizes share a slab), so a constant plane is a span of the slab ...
 struct FillSpan { uint64_t off; uint32_t npx, value; };
-// constant planes of such a slab in one launch: grid = (chunks, spans)
+// constant planes of a slab in one launch: grid = (chunks, spans)
 __global__ void __launch_bounds__(256) k_fill_spans(uint16_t *slab, const FillSpan *fill) {
     const FillSpan f = fill[blockIdx.y];
     uint16_t *p = slab + f.off;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < f.npx; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint16_t)f.value;
 }
-// ... and a piece says where its first sample lies in plane 0 (src, samples into the slab), how far apart the tile's rows (stride =
-// tw) and planes (pstride = tw * th) are, and where its w x h samples go: (dx, dy) of patch `patch`.  The host plans them
-// (multi_plan): the kernels divide nothing.
-struct MultiPiece { uint64_t src; int32_t patch, stride, pstride, dx, dy, w, h, pad; };
+// ... and a piece, one patch-tile overlap, says where its first sample lies in plane 0 (src, samples into the slab), how far apart
+// the tile's rows (stride = tw) and planes (pstride = tw * th) are, and where its w x h samples go: (dx, dy) of patch `patch`.  The
+// host plans them (plan_clip): the kernels divide nothing.
+struct GatherPiece { uint64_t src; int32_t patch, stride, pstride, dx, dy, w, h, pad; };
 
-// k_wsi_gather_patches for such pieces.  slab: a sub-batch's planes; out: [patch][ph][pw][3] u8.  grid = (pieces, row chunks); lanes
-// along x of a piece row (piece_lanes): a wave reads 64 neighbouring samples of each plane and writes 192 neighbouring bytes.
-__global__ void __launch_bounds__(256) k_wsi_multi_gather(const uint16_t *slab, const MultiPiece *pieces, uint8_t *out, int pw, int ph) {
-    const MultiPiece pc = pieces[blockIdx.x];
+// YCoCgRInverse of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at whatever byte offset the patch
+// row has.  slab: a sub-batch's planes; out: [patch][ph][pw][3] u8.  grid = (pieces, row chunks); lanes along x of a piece row
+// (piece_lanes): a wave reads 64 neighbouring samples of each plane and writes 192 neighbouring bytes.
+__global__ void __launch_bounds__(256) k_wsi_gather_patches(const uint16_t *slab, const GatherPiece *pieces, uint8_t *out, int pw, int ph) {
+    const GatherPiece pc = pieces[blockIdx.x];
     const PieceLanes ln = piece_lanes(pc.w);
     const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
     const mic_gp<uint8_t> o = mic_g(out + (((size_t)pc.patch * ph + pc.dy) * pw + pc.dx) * 3);
@@ -227,12 +179,12 @@ __global__ void __launch_bounds__(256) k_wsi_multi_gather(const uint16_t *slab, 
         }
     }
 }
-// k_wsi_gather_patches_grey for such pieces.  out: [patch][ph][pw] T.  16-bit samples: a row whose source and destination are both
-// 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16 -- with an odd tile or patch width every
-// second row is such a row (as k_strips_gather_crops).
+// uint16ToBytes (wsicompress.go:589-603) of the piece's samples.  out: [patch][ph][pw] T.  16-bit samples: a row whose source and
+// destination are both 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16 -- with an odd tile
+// or patch width every second row is such a row (as k_strips_gather_crops).
 template <typename T>
-__global__ void __launch_bounds__(256) k_wsi_multi_gather_grey(const uint16_t *slab, const MultiPiece *pieces, T *out, int pw, int ph) {
-    const MultiPiece pc = pieces[blockIdx.x];
+__global__ void __launch_bounds__(256) k_wsi_gather_patches_grey(const uint16_t *slab, const GatherPiece *pieces, T *out, int pw, int ph) {
+    const GatherPiece pc = pieces[blockIdx.x];
     const PieceLanes ln = piece_lanes(pc.w);
     const uint16_t *src = slab + pc.src;
     T *dst = out + ((size_t)pc.patch * ph + pc.dy) * pw + pc.dx;
@@ -342,17 +294,14 @@ void launch_planes_to_pixels(hipStream_t st, const Mic3 &m, const uint16_t *plan
     else
         hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint8_t *)dst, dst_w);
 }
-// np pieces (device) of the planes of a slab's tiles -> out, the patch tensor (pw x ph pixels a patch).  A block walks its piece in
-// passes of 256 pixels; grid y cuts the rows of large tiles so that a 256 x 256 overlap is not one block's 256 passes.
-void launch_gather_patches(hipStream_t st, const Mic3 &m, const uint16_t *planes, const PatchPiece *pieces, size_t np, void *out, int pw, int ph) {
-    const size_t npx = (size_t)m.tw * m.th;
-    const dim3 grid((unsigned)np, (unsigned)std::min<size_t>(8, std::max<size_t>(1, npx / 16384))), block(256);
-    if (m.planes() == 3)
-        hipLaunchKernelGGL(k_wsi_gather_patches, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint8_t *)out, pw, ph);
-    else if (m.bps == 16)
-        hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint16_t>, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint16_t *)out, pw, ph);
-    else
-        hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, pieces, (uint8_t *)out, pw, ph);
+// np pieces (device) of a slab's planes -> out, the patch tensor (pw x ph pixels a patch; P planes a tile, bps bits a sample).  A
+// block walks its piece in passes of 256 lanes; grid y cuts the rows of tall pieces (row_chunks of mw x mh, the launch's largest).
+void launch_gather(hipStream_t st, size_t P, int bps, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh,
+                   void *out, int pw, int ph) {
+    const dim3 grid((unsigned)np, row_chunks(mw, mh)), block(256);
+    if (P == 3) hipLaunchKernelGGL(k_wsi_gather_patches, grid, block, 0, st, slab, pieces, (uint8_t *)out, pw, ph);
+    else if (bps == 16) hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint16_t>, grid, block, 0, st, slab, pieces, (uint16_t *)out, pw, ph);
+    else hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint8_t>, grid, block, 0, st, slab, pieces, (uint8_t *)out, pw, ph);
 }
 // one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
 void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
@@ -448,33 +397,37 @@ void put_mic3_index(uint8_t *out, const Mic3 &fmt, const std::vector<Level> &lv,
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------------
-// decompressTileBlob (wsicompress.go:424-527) for nt tiles from their plane records (bytes at base + off on the device), up to the
-// planes: constant planes filled, streams through the unit codec, raw planes copied into `planes` ([nt][P][tw * th] u16).  aux
-// keeps `front` bytes at its start for the caller (the place rectangles, the patch pieces: to be uploaded after this call, which
-// may move aux) and holds the fill list behind them.  plane_status = NULL: the first unit that fails ends the call with its status;
-// else plane_status[q] (nt * P entries) receives every plane's status and the call goes on.  The planes are complete on the
-// session's stream on return (the host has waited for the stream: the fill list is this call's own).
-int decode_plane_data(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, DevBuf &planes, DevBuf &aux,
-                      size_t front, int32_t *plane_status) {
-    const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
+// decompressTileBlob (wsicompress.go:424-527) for the nq planes of a slab of tiles, from their records (bytes at base + off on the
+// device) up to the planes: at(q) says where plane q lies in `slab` (samples) and how large its tile is.  Constant planes are spans
+// filled by one launch (the list: s->wsi_fills), raw planes are copied, streams go through the unit codec in one chain.
+// plane_status = NULL: the first unit that fails ends the call with its status; else plane_status[q] receives every plane's status
+// and the call goes on.  The planes are complete on the session's stream on return, and the host has waited for the stream: the
+// caller may reuse the bytes behind `base`, the next call the fill list.  (It waits even for a slab of raw planes only, where
+// nothing of the host's is in flight: one rule, at the price of one wait the tile, region and level decoders did not have there.)
+struct PlaneAt { uint64_t at; int32_t tw, th; };
+template <class At>
+int decode_plane_slab(mic_hip_session *s, const uint8_t *base, const WsiPlane *pl, size_t nq, At at, DevBuf &slab, size_t samples,
+                      int32_t *plane_status) {
     int rc;
-    if ((rc = planes.reserve(nt * P * npx * 2 + 64))) return rc;
-    uint16_t *dp = (uint16_t *)planes.p;
-    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<uint2> fills; std::vector<size_t> unit_plane;
-    for (size_t q = 0; q < nt * P; q++) {
+    if ((rc = slab.reserve(samples * 2 + 64))) return rc;
+    uint16_t *dp = (uint16_t *)slab.p;
+    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<FillSpan> fills; std::vector<size_t> unit_plane;
+    for (size_t q = 0; q < nq; q++) {
         const WsiPlane &wp = pl[q];
+        const PlaneAt a = at(q);
+        const size_t npx = (size_t)a.tw * a.th;
         if (plane_status) plane_status[q] = MIC_OK;
-        if (wp.mode <= 1) fills.push_back(make_uint2((uint32_t)q, wp.mode ? wp.value : 0u));
-        else if (wp.mode == 2) { units.push_back(mic_hip_unit{ q * npx, m.tw, m.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); unit_plane.push_back(q); }
-        else HIP_TRY(hipMemcpyAsync(dp + q * npx, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
+        if (wp.mode <= 1) fills.push_back(FillSpan{ a.at, (uint32_t)npx, wp.mode ? wp.value : 0u });
+        else if (wp.mode == 2) { units.push_back(mic_hip_unit{ a.at, a.tw, a.th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); unit_plane.push_back(q); }
+        else HIP_TRY(hipMemcpyAsync(dp + a.at, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
     }
-    if ((rc = aux.reserve(fills.size() * sizeof(uint2) + front + 64))) return rc;
-    uint2 *d_fill = (uint2 *)((char *)aux.p + front);
     if (!fills.empty()) {
-        HIP_TRY(hipMemcpyAsync(d_fill, fills.data(), fills.size() * sizeof(uint2), hipMemcpyHostToDevice, s->stream));
-        s->timer.reset(s->stream); s->timer.mark("k_fill_planes");
-        for (size_t f0 = 0; f0 < fills.size(); f0 += 65535)
-            hipLaunchKernelGGL(k_fill_planes, dim3(4, (unsigned)std::min<size_t>(65535, fills.size() - f0)), dim3(256), 0, s->stream, dp, npx, (const uint2 *)d_fill + f0);
+        if ((rc = s->wsi_fills.reserve(fills.size() * sizeof(FillSpan) + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->wsi_fills.p, fills.data(), fills.size() * sizeof(FillSpan), hipMemcpyHostToDevice, s->stream));
+        s->timer.reset(s->stream); s->timer.mark("k_fill_spans");
+        for (size_t f0 = 0; f0 < fills.size(); f0 += kMaxGridY)
+            hipLaunchKernelGGL(k_fill_spans, dim3(4, (unsigned)std::min<size_t>(kMaxGridY, fills.size() - f0)), dim3(256), 0, s->stream, dp, (const FillSpan *)s->wsi_fills.p + f0);
+        HIP_TRY(hipGetLastError());
     }
     if (!units.empty()) {
         if ((rc = session_decode_enqueue_spans(s, base, begins.data(), ends.data(), units.data(), (int)units.size(), dp))) return rc;
@@ -482,16 +435,18 @@ int decode_plane_data(mic_hip_session *s, const Mic3 &m, const uint8_t *base, co
         if ((rc = session_decode_finish(s, st.data()))) return rc;
         if (plane_status) for (size_t u = 0; u < st.size(); u++) plane_status[unit_plane[u]] = st[u];
         else for (int32_t v : st) if (v != MIC_OK) return v;
-    } else if (!fills.empty()) HIP_TRY(hipStreamSynchronize(s->stream));                  // (session_decode_finish waits otherwise)
+    } else HIP_TRY(hipStreamSynchronize(s->stream));                                        // (session_decode_finish waits otherwise)
     return MIC_OK;
 }
 
-// ... then YCoCg-R inverse / uint16ToBytes + crop into dst (dst_w pixels across), tile k at place[k] (host).  planes holds the
-// nt * P planes, aux the place rectangles and the fill list.
+// ... for nt tiles of one size, plane q at q * tw * th of `planes`, then YCoCg-R inverse / uint16ToBytes + crop into dst (dst_w
+// pixels across), tile k at place[k] (host).  aux holds the place rectangles.
 int decode_planes(mic_hip_session *s, const Mic3 &m, const uint8_t *base, const WsiPlane *pl, size_t nt, const int4 *place,
                   DevBuf &planes, DevBuf &aux, void *dst, int dst_w) {
+    const size_t nq = nt * (size_t)m.planes(), npx = (size_t)m.tw * m.th;
     int rc;
-    if ((rc = decode_plane_data(s, m, base, pl, nt, planes, aux, nt * sizeof(int4), nullptr))) return rc;
+    if ((rc = decode_plane_slab(s, base, pl, nq, [&](size_t q) { return PlaneAt{ q * npx, m.tw, m.th }; }, planes, nq * npx, nullptr))) return rc;
+    if ((rc = aux.reserve(nt * sizeof(int4) + 64))) return rc;
     int4 *d_place = (int4 *)aux.p;
     HIP_TRY(hipMemcpyAsync(d_place, place, nt * sizeof(int4), hipMemcpyHostToDevice, s->stream));
     s->timer.reset(s->stream); s->timer.mark("k_wsi_planes_to_pixels");
@@ -860,39 +815,62 @@ int wsi_region(const BlobSource &src, const Mic3 &m, int level, int x, int y, in
 }
 
 // ---- patches -----------------------------------------------------------------------------------------------------------------
-// The tiles n patches of pw x ph pixels touch in a level of level_w x level_h pixels (tiles of tw x th), and their pieces.
-// Patch i is [xy[2i], xy[2i] + pw) x [xy[2i + 1], xy[2i + 1] + ph); what lies outside the level has no piece.  tiles: ty * tiles_x +
-// tx, ascending, each once.  pieces: sorted by tile, then by patch; slot = the tile's index in `tiles`.  first[u] .. first[u + 1]:
-// the pieces of tiles[u].
-struct PatchPlan { std::vector<uint64_t> tiles; std::vector<PatchPiece> pieces; std::vector<size_t> first; };
-int plan_patches(int level_w, int level_h, int tw, int th, const int32_t *xy, int n, int pw, int ph, PatchPlan &plan) {
-    const int64_t tiles_x = ((int64_t)level_w + tw - 1) / tw;
-    std::vector<std::pair<uint64_t, PatchPiece>> all;
-    for (int i = 0; i < n; i++) {
-        const int64_t px = xy[2 * i], py = xy[2 * i + 1];
-        const int64_t x0 = std::max<int64_t>(px, 0), x1 = std::min<int64_t>(px + pw, level_w);
-        const int64_t y0 = std::max<int64_t>(py, 0), y1 = std::min<int64_t>(py + ph, level_h);
-        if (x0 >= x1 || y0 >= y1) continue;
-        for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
-            const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
-            all.emplace_back((uint64_t)(ty * tiles_x + tx), PatchPiece{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py),
-                                                                         (int32_t)(bx - ax), (int32_t)(by - ay) });
-        }
+// The plan of a patch call.  A unit is a tile to entropy-decode (slide: index into the call's slide list, 0 for the one-slide calls;
+// tile: its index as the door counts it); a piece is one patch-tile overlap: w x h pixels from (sx, sy) of unit `unit`'s tile to
+// (dx, dy) of patch `patch`.  units: ascending by slide, then tile, each once.  pieces: sorted by unit (stable: patch order inside a
+// unit).  first[u] .. first[u + 1]: the pieces of units[u].
+struct PatchUnit { uint32_t slide; uint64_t tile; };
+struct PlanPiece { int32_t patch; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
+struct PatchPlan { std::vector<PatchUnit> units; std::vector<PlanPiece> pieces; std::vector<size_t> first; };
+struct PlanKey { PatchUnit u; PlanPiece pc; };
+
+// Patch i = [px, px + pw) x [py, py + ph) clipped to a level of level_w x level_h pixels and cut into its overlaps with the level's
+// tiles (tw x th, tiles_x a row): one key per overlap, tile = first + ty * tiles_x + tx.  What lies outside the level has no piece.
+void plan_clip(std::vector<PlanKey> &all, uint32_t slide, int level_w, int level_h, int64_t tw, int64_t th, int64_t tiles_x, int64_t first,
+               int32_t i, int64_t px, int64_t py, int pw, int ph) {
+    const int64_t x0 = std::max<int64_t>(px, 0), x1 = std::min<int64_t>(px + pw, level_w);
+    const int64_t y0 = std::max<int64_t>(py, 0), y1 = std::min<int64_t>(py + ph, level_h);
+    if (x0 >= x1 || y0 >= y1) return;
+    for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
+        const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
+        all.push_back(PlanKey{ PatchUnit{ slide, (uint64_t)(first + ty * tiles_x + tx) },
+                               PlanPiece{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py), (int32_t)(bx - ax), (int32_t)(by - ay) } });
     }
+}
+// the keys in unit order ...
+int plan_sort(std::vector<PlanKey> &all) {
     if (all.size() > 0x7FFFFFFFu) return MIC_ERR_UNSUPPORTED;                              // (pieces are a launch's grid x)
-    std::stable_sort(all.begin(), all.end(), [](const std::pair<uint64_t, PatchPiece> &a, const std::pair<uint64_t, PatchPiece> &b) { return a.first < b.first; });
-    plan.tiles.clear(); plan.pieces.clear(); plan.first.clear();
-    plan.pieces.reserve(all.size());
-    for (const auto &tp : all) {
-        if (plan.tiles.empty() || plan.tiles.back() != tp.first) { plan.tiles.push_back(tp.first); plan.first.push_back(plan.pieces.size()); }
-        plan.pieces.push_back(tp.second);
-        plan.pieces.back().slot = (int32_t)(plan.tiles.size() - 1);
+    std::stable_sort(all.begin(), all.end(), [](const PlanKey &a, const PlanKey &b) { return a.u.slide != b.u.slide ? a.u.slide < b.u.slide : a.u.tile < b.u.tile; });
+    return MIC_OK;
+}
+// ... and those of the slides that `keep` accepts as the plan
+template <class Keep>
+void plan_group(const std::vector<PlanKey> &all, PatchPlan &plan, Keep keep) {
+    plan.units.clear(); plan.pieces.clear(); plan.first.clear();
+    for (const PlanKey &k : all) {
+        if (!keep(k.u.slide)) continue;
+        if (plan.units.empty() || plan.units.back().slide != k.u.slide || plan.units.back().tile != k.u.tile) {
+            plan.units.push_back(k.u);
+            plan.first.push_back(plan.pieces.size());
+        }
+        plan.pieces.push_back(k.pc);
+        plan.pieces.back().unit = (uint32_t)(plan.units.size() - 1);
     }
     plan.first.push_back(plan.pieces.size());
+}
+
+// The plan of n patches of pw x ph pixels, patch i at (xy[2i], xy[2i + 1]), in one level of level_w x level_h pixels (tiles of
+// tw x th): slide 0, tile = ty * tiles_x + tx inside the level.
+int plan_patches(int level_w, int level_h, int tw, int th, const int32_t *xy, int n, int pw, int ph, PatchPlan &plan) {
+    std::vector<PlanKey> all;
+    for (int i = 0; i < n; i++) plan_clip(all, 0, level_w, level_h, tw, th, ((int64_t)level_w + tw - 1) / tw, 0, i, xy[2 * (size_t)i], xy[2 * (size_t)i + 1], pw, ph);
+    const int rc = plan_sort(all);
+    if (rc) return rc;
+    plan_group(all, plan, [](uint32_t) { return true; });
     return MIC_OK;
 }
 
-// What the three patch entry points check of their arguments before a device is touched; *need = bytes of the patch tensor.
+// What the three one-slide patch entry points check of their arguments before a device is touched; *need = bytes of the patch tensor.
 int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, size_t out_cap, size_t *need) {
     if (level < 0 || level >= m.nlev || pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xy)) return MIC_ERR_ARGS;
     if (!m.supported()) return MIC_ERR_UNSUPPORTED;
@@ -907,83 +885,145 @@ int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int p
 
 // (patch_pointer -- d_out must be memory the session's device can write -- is shared with the MIC2 crop calls: mic_mic2_crops.hip)
 
-// The planes of union tiles t0 .. t0 + nt - 1 (indices into the plan's tile list) as records over *base (device), and each tile's
-// own status: a tile that fails on the host (a blob that does not parse) still has its P records, constant zero.
-typedef std::function<int(size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status)> PatchSlabs;
+// Where a call's tiles come from: the planes of units u0 .. u0 + nt - 1 of the plan as nt * P records over *base (device), and each
+// tile's own host-side status: a tile that fails on the host (a blob that does not parse) still has its P records, constant zero.
+typedef std::function<int(size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status)> PatchSlabs;
+// how many tiles a sub-batch may hold when its largest has npx pixels
+typedef std::function<size_t(size_t npx)> SlabCeiling;
+// ... for blobs through the unit codec's workspace (tiles are a launch's grid y)
+SlabCeiling blob_ceiling(size_t P) { return [P](size_t npx) { return std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)); }; }
 
-// n patches of level L into d_out ([n][ph][pw] pixels of the slide's format, on s's device; pixels outside the level 0): every tile
-// of the plan once, `per` tiles a slab -- their planes decoded (decode_plane_data), their pieces gathered straight into d_out.
-// status[i] (may be NULL): MIC_OK, or the first failing tile of patch i in tile order, with the code mic_hip_wsi_decompress_tile has
-// for it (the blob's, else its first failing plane's).
-int read_patches(mic_hip_session *s, const Mic3 &m, const PatchPlan &plan, int n, int pw, int ph, size_t per, void *d_out, size_t need,
-                 int32_t *status, mic_hip_patch_stats *stats, const PatchSlabs &slabs) {
-    const size_t P = (size_t)m.planes(), ntile = plan.tiles.size();
+// The core of every patch call: the plan's pieces into d_out ([patch][ph][pw] pixels of the slides' format, an address s's device
+// can write: patch_pointer; what no piece covers is 0) on a session the caller holds.  um[u]: the header unit u's tile is coded
+// under (all of one sample format).  Every unit is decoded once, in sub-batches of as many tiles as `ceiling` allows of the largest
+// of them: tile u's P planes start slab_off[u] samples into the sub-batch's slab (the prefix sum of P * tw * th), decode_plane_slab
+// fills them from the source's records, and behind each sub-batch one gather launch writes its pieces.  The piece list goes up
+// once per call (s->wsi_pieces).  tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
+int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const SlabCeiling &ceiling,
+                 const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
+    const size_t nu = plan.units.size();
     int rc;
-    if ((rc = s->ensure(1, (size_t)m.tw * m.th))) return rc;                                // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // margins outside the level; every byte is written
-    std::vector<int32_t> tst(ntile, MIC_OK), pst;
-    std::vector<WsiPlane> pl; std::vector<PatchPiece> pcs;
-    uint64_t nslab = 0;
-    for (size_t t0 = 0; t0 < ntile; t0 += per, nslab++) {
-        const size_t nt = std::min(per, ntile - t0), p0 = plan.first[t0], np = plan.first[t0 + nt] - p0;
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the levels, refused slides and patches
+    tile_status.assign(nu, MIC_OK);
+    *nslab = 0;
+    if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
+    const size_t P = (size_t)um[0]->planes();
+    // cuts: as many tiles as the ceiling holds of the largest of them (tiles of one size: `ceiling` tiles a sub-batch)
+    std::vector<size_t> px(nu), cuts{ 0 };
+    for (size_t u = 0; u < nu; u++) px[u] = (size_t)um[u]->tw * um[u]->th;
+    std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds)
+    auto cap_for = [&](size_t npx) {
+        for (const auto &c : caps) if (c.first == npx) return c.second;
+        caps.emplace_back(npx, ceiling(npx));
+        return caps.back().second;
+    };
+    while (cuts.back() < nu) {
+        size_t i1 = cuts.back(), mp = 0;
+        while (i1 < nu) {
+            const size_t m2 = std::max(mp, px[i1]);
+            if (i1 > cuts.back() && i1 - cuts.back() + 1 > cap_for(m2)) break;
+            mp = m2; i1++;
+        }
+        cuts.push_back(i1);
+    }
+    std::vector<uint64_t> slab_off(nu);
+    size_t slab_max = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        size_t off = 0;
+        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += P * px[u]; }
+        slab_max = std::max(slab_max, off);
+    }
+    std::vector<GatherPiece> list(plan.pieces.size());
+    for (size_t k = 0; k < list.size(); k++) {
+        const PlanPiece &p = plan.pieces[k];
+        const int tw = um[p.unit]->tw;
+        list[k] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)tw + (uint64_t)p.sx, p.patch, tw, (int32_t)px[p.unit], p.dx, p.dy, p.w, p.h, 0 };
+    }
+    if ((rc = s->wsi_pieces.reserve(list.size() * sizeof(GatherPiece) + 64))) return rc;
+    if ((rc = s->wsi_planes.reserve(slab_max * 2 + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->wsi_pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+    std::vector<WsiPlane> pl; std::vector<int32_t> pst;
+    for (size_t b = 0; b + 1 < cuts.size(); b++, ++*nslab) {
+        const size_t u0 = cuts[b], nt = cuts[b + 1] - u0;
         const uint8_t *base = nullptr;
         pl.clear();
-        if ((rc = slabs(t0, nt, &base, pl, tst.data() + t0))) return rc;
+        if ((rc = source(u0, nt, &base, pl, tile_status.data() + u0))) return rc;
         pst.assign(nt * P, MIC_OK);
-        if ((rc = decode_plane_data(s, m, base, pl.data(), nt, s->wsi_planes, s->wsi_stats, np * sizeof(PatchPiece), pst.data()))) return rc;
-        for (size_t q = 0; q < nt * P; q++) if (tst[t0 + q / P] == MIC_OK) tst[t0 + q / P] = pst[q];
-        pcs.assign(plan.pieces.begin() + (long)p0, plan.pieces.begin() + (long)(p0 + np));
-        for (PatchPiece &pc : pcs) pc.slot -= (int32_t)t0;
-        HIP_TRY(hipMemcpyAsync(s->wsi_stats.p, pcs.data(), np * sizeof(PatchPiece), hipMemcpyHostToDevice, s->stream));
+        if ((rc = decode_plane_slab(s, base, pl.data(), nt * P, [&](size_t q) {
+                const size_t u = u0 + q / P;
+                return PlaneAt{ slab_off[u] + (q % P) * px[u], um[u]->tw, um[u]->th };
+            }, s->wsi_planes, slab_max, pst.data()))) return rc;
+        for (size_t q = 0; q < nt * P; q++) if (tile_status[u0 + q / P] == MIC_OK) tile_status[u0 + q / P] = pst[q];
+        const size_t p0 = plan.first[u0], np = plan.first[u0 + nt] - p0;                    // (np >= 1: every unit has a piece; np <= 2^31 - 1: plan_sort)
+        int mw = 1, mh = 1;
+        for (size_t k = p0; k < p0 + np; k++) { mw = std::max(mw, plan.pieces[k].w); mh = std::max(mh, plan.pieces[k].h); }
         s->timer.reset(s->stream); s->timer.mark("k_wsi_gather_patches");
-        launch_gather_patches(s->stream, m, (const uint16_t *)s->wsi_planes.p, (const PatchPiece *)s->wsi_stats.p, np, d_out, pw, ph);
+        launch_gather(s->stream, P, um[0]->bps, (const uint16_t *)s->wsi_planes.p, (const GatherPiece *)s->wsi_pieces.p + p0, np, mw, mh, d_out, pw, ph);
         s->timer.mark("end");
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));                                           // (pcs, and the slab's planes, are reused by the next one)
+        HIP_TRY(hipGetLastError());                                                         // (the next sub-batch follows on the stream; decode_plane_slab has waited for this one's bytes)
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (status) {
-        for (int i = 0; i < n; i++) status[i] = MIC_OK;
-        for (const PatchPiece &pc : plan.pieces) if (status[pc.patch] == MIC_OK) status[pc.patch] = tst[(size_t)pc.slot];
-    }
-    if (stats) { stats->tiles_decoded = ntile; stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
     return MIC_OK;
 }
+// status[p] == MIC_OK becomes the status of the first failing tile of patch p, in tile order
+void fold_tile_status(const PatchPlan &plan, const std::vector<int32_t> &tile_status, int32_t *status) {
+    for (const PlanPiece &p : plan.pieces) if (status[p.patch] == MIC_OK) status[p.patch] = tile_status[p.unit];
+}
 
-// mic_hip_wsi_read_patches / mic_hip_wsi_reader_read_patches on a parsed header, on the session the thread holds: the blobs of
-// the union's tiles from `src` in ONE request (a reader then pulls those blobs only, contiguous ones in one read), a slab's blobs
-// checked on the host and their planes' bytes uploaded in one copy, as decode_blobs does it.
-int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, void *d_out, size_t need,
-                int32_t *status, mic_hip_patch_stats *stats) {
-    mic_hip_session *s = cur_default();
-    const Level &L = m.lv[(size_t)level];
-    const size_t P = (size_t)m.planes(), npx = (size_t)m.tw * m.th;
-    int rc;
-    if ((rc = patch_pointer(s, &d_out, need))) return rc;
-    PatchPlan plan;
-    if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
-    std::vector<size_t> tiles(plan.tiles.size());
-    for (size_t u = 0; u < tiles.size(); u++) tiles[u] = (size_t)L.first + (size_t)plan.tiles[u];
-    std::vector<TileBlob> blobs; std::vector<uint8_t> keep, bytes;
-    if (!tiles.empty() && (rc = src(tiles, blobs, keep))) return rc;
-    const size_t per = std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P));
-    return read_patches(s, m, plan, n, pw, ph, per, d_out, need, status, stats,
-                        [&](size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status) -> int {
+// The source of the file and reader doors: blobs[u] (host) is the blob of unit u.  A sub-batch's blobs are checked on the host, each
+// under its own header, and their planes' bytes go up in one copy (s->io_comp), as decode_blobs does it.
+PatchSlabs blob_slabs(mic_hip_session *s, const std::vector<const Mic3 *> &um, const std::vector<TileBlob> &blobs) {
+    return [s, &um, &blobs](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status) -> int {
+        std::vector<uint8_t> &bytes = s->wsi_host_bytes;                                    // (the session's: no fresh pages per call)
         bytes.clear();
         for (size_t k = 0; k < nt; k++) {
-            const size_t b0 = bytes.size();
-            if ((tile_status[k] = parse_tile_blob(m, blobs[t0 + k].p, blobs[t0 + k].len, pl, bytes)) != MIC_OK) {
+            const size_t b0 = bytes.size(), P = (size_t)um[u0 + k]->planes();
+            if ((tile_status[k] = parse_tile_blob(*um[u0 + k], blobs[u0 + k].p, blobs[u0 + k].len, pl, bytes)) != MIC_OK) {
                 bytes.resize(b0);
                 pl.resize(k * P);
                 pl.resize((k + 1) * P, WsiPlane{ 0, 0, 0, 0 });
             }
         }
-        int r = s->io_comp.reserve(bytes.size() + 64);
-        if (r) return r;
+        const int rc = s->io_comp.reserve(bytes.size() + 64);
+        if (rc) return rc;
         if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
         *base = (const uint8_t *)s->io_comp.p;
         return MIC_OK;
-    });
+    };
+}
+
+// ---- patches of one level: what the three one-slide doors share ----------------------------------------------------------------------
+// The plan of one level of `m` through the core.  status[i] (may be NULL): MIC_OK, or the first failing tile of patch i in tile
+// order, with the code mic_hip_wsi_decompress_tile has for it (the blob's, else its first failing plane's).
+int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int n, int pw, int ph, const SlabCeiling &ceiling,
+                  const PatchSlabs &source, void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats) {
+    std::vector<int32_t> tst;
+    uint64_t nslab = 0;
+    const int rc = read_patches(s, plan, um, pw, ph, ceiling, source, d_out, need, tst, &nslab);
+    if (rc) return rc;
+    if (status) { std::fill(status, status + n, (int32_t)MIC_OK); fold_tile_status(plan, tst, status); }
+    if (stats) { stats->tiles_decoded = plan.units.size(); stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
+    return MIC_OK;
+}
+
+// mic_hip_wsi_read_patches / mic_hip_wsi_reader_read_patches on a parsed header, on the session the thread holds: the blobs of
+// the union's tiles from `src` in ONE request (a reader then pulls those blobs only, contiguous ones in one read); a tile whose
+// index entry points outside the file fails the call with the source's code before anything is launched.
+int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, void *d_out, size_t need,
+                int32_t *status, mic_hip_patch_stats *stats) {
+    mic_hip_session *s = cur_default();
+    const Level &L = m.lv[(size_t)level];
+    int rc;
+    if ((rc = patch_pointer(s, &d_out, need))) return rc;
+    PatchPlan plan;
+    if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
+    std::vector<size_t> tiles(plan.units.size());
+    for (size_t u = 0; u < tiles.size(); u++) tiles[u] = (size_t)L.first + (size_t)plan.units[u].tile;
+    std::vector<TileBlob> blobs; std::vector<uint8_t> keep;
+    if (!tiles.empty() && (rc = src(tiles, blobs, keep))) return rc;
+    const std::vector<const Mic3 *> um(tiles.size(), &m);
+    return level_patches(s, plan, um, n, pw, ph, blob_ceiling((size_t)m.planes()), blob_slabs(s, um, blobs), d_out, need, status, stats);
 }
 
 // ---- patches of many slides and levels ------------------------------------------------------------------------------------------
@@ -997,14 +1037,7 @@ struct MultiSlide {
     int32_t status = MIC_OK;
     const Mic3 &hdr() const { return m ? *m : own; }
 };
-struct MultiUnit { uint32_t slide; uint64_t tile; };                                        // tile: global index, level.first + ty * tiles_x + tx
-struct MultiPlanned { int32_t patch; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
-struct MultiPlan {
-    std::vector<MultiSlide> slides;
-    std::vector<MultiUnit> units;           // the tiles to entropy-decode, ascending by slide, then tile, each once
-    std::vector<MultiPlanned> pieces;       // sorted by unit (stable: patch order inside a unit)
-    std::vector<size_t> first;              // first[u] .. first[u + 1]: the pieces of units[u]
-};
+struct MultiPlan : PatchPlan { std::vector<MultiSlide> slides; };                          // units[u].tile: global index, level.first + ty * tiles_x + tx
 
 // the tile-index entry of global tile gi: false when it points outside the file (as flat_source and the reader's fetch judge it)
 bool multi_tile_entry(const MultiSlide &sl, uint64_t gi, uint64_t *off, uint64_t *len) {
@@ -1037,8 +1070,7 @@ int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int cha
         else if (m.channels != channels || m.bps != bps) sl.status = MIC_ERR_ARGS;
         sl.header_ok = sl.status == MIC_OK;
     }
-    struct Key { uint32_t slide; uint64_t tile; MultiPlanned pc; };
-    std::vector<Key> all;
+    std::vector<PlanKey> all;
     for (int i = 0; i < n; i++) {
         const uint32_t f = (uint32_t)q[4 * (size_t)i + 2];
         const MultiSlide &sl = plan.slides[f];
@@ -1047,35 +1079,16 @@ int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int cha
         const int32_t level = q[4 * (size_t)i + 3];
         if (level < 0 || level >= (int)m.lv.size()) continue;
         const Level &L = m.lv[(size_t)level];
-        const int64_t tw = m.tw, th = m.th, px = q[4 * (size_t)i], py = q[4 * (size_t)i + 1];
-        const int64_t x0 = std::max<int64_t>(px, 0), x1 = std::min<int64_t>(px + pw, L.w);
-        const int64_t y0 = std::max<int64_t>(py, 0), y1 = std::min<int64_t>(py + ph, L.h);
-        if (x0 >= x1 || y0 >= y1) continue;
-        for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
-            const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
-            all.push_back(Key{ f, (uint64_t)((int64_t)L.first + ty * L.tx + tx),
-                               MultiPlanned{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py), (int32_t)(bx - ax), (int32_t)(by - ay) } });
-        }
+        plan_clip(all, f, L.w, L.h, m.tw, m.th, L.tx, L.first, i, q[4 * (size_t)i], q[4 * (size_t)i + 1], pw, ph);
     }
-    if (all.size() > 0x7FFFFFFFu) return MIC_ERR_UNSUPPORTED;                              // (pieces are a launch's grid x)
-    std::stable_sort(all.begin(), all.end(), [](const Key &a, const Key &b) { return a.slide != b.slide ? a.slide < b.slide : a.tile < b.tile; });
+    const int rc = plan_sort(all);
+    if (rc) return rc;
     // a touched tile whose index entry points outside the file fails its slide
     uint64_t off, len;
     for (size_t k = 0; k < all.size(); k++)
-        if ((k == 0 || all[k].slide != all[k - 1].slide || all[k].tile != all[k - 1].tile) && plan.slides[all[k].slide].status == MIC_OK &&
-            !multi_tile_entry(plan.slides[all[k].slide], all[k].tile, &off, &len)) plan.slides[all[k].slide].status = MIC_ERR_CORRUPT;
-    plan.first.clear();
-    for (const Key &k : all) {
-        if (plan.slides[k.slide].status != MIC_OK) continue;
-        if (plan.units.empty() || plan.units.back().slide != k.slide || plan.units.back().tile != k.tile) {
-            if (plan.units.size() >= 0xFFFFFFFEu) return MIC_ERR_UNSUPPORTED;
-            plan.units.push_back(MultiUnit{ k.slide, k.tile });
-            plan.first.push_back(plan.pieces.size());
-        }
-        plan.pieces.push_back(k.pc);
-        plan.pieces.back().unit = (uint32_t)(plan.units.size() - 1);
-    }
-    plan.first.push_back(plan.pieces.size());
+        if ((k == 0 || all[k].u.slide != all[k - 1].u.slide || all[k].u.tile != all[k - 1].u.tile) && plan.slides[all[k].u.slide].status == MIC_OK &&
+            !multi_tile_entry(plan.slides[all[k].u.slide], all[k].u.tile, &off, &len)) plan.slides[all[k].u.slide].status = MIC_ERR_CORRUPT;
+    plan_group(all, plan, [&](uint32_t f) { return plan.slides[f].status == MIC_OK; });
     return MIC_OK;
 }
 
@@ -1086,111 +1099,6 @@ int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps
     const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ph * (unsigned)pw * (size_t)(channels * (bps == 16 ? 2 : 1));
     if (bytes > out_cap) return MIC_ERR_CAPACITY;
     *need = (size_t)bytes;
-    return MIC_OK;
-}
-
-// The plan's tiles (blobs[u]: the blob of units[u], host) into d_out (an address s's device can write: patch_pointer) on a session the
-// caller holds.  Sub-batches of tiles through the unit codec: tile u's P planes start slab_off[u] samples into the sub-batch's slab
-// (the prefix sum of P * tw * th), constant planes are spans filled there, raw planes copied there, streams decoded there; behind
-// each sub-batch one gather launch writes its pieces.  tile_status[u]: the blob's code, else its first failing plane's.
-int multi_read(mic_hip_session *s, const MultiPlan &plan, const std::vector<TileBlob> &blobs, size_t P, int bps, int pw, int ph,
-               void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
-    const size_t nu = plan.units.size();
-    int rc;
-    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the levels, refused slides and patches
-    tile_status.assign(nu, MIC_OK);
-    *nslab = 0;
-    if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
-    auto hdr = [&](size_t u) -> const Mic3 & { return plan.slides[plan.units[u].slide].hdr(); };
-    // cuts: as many tiles as the workspace ceiling holds of the largest of them, at most what one launch chain takes
-    std::vector<size_t> px(nu), cuts{ 0 };
-    for (size_t u = 0; u < nu; u++) px[u] = (size_t)hdr(u).tw * hdr(u).th;
-    std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds)
-    auto cap_for = [&](size_t npx) {
-        for (const auto &c : caps) if (c.first == npx) return c.second;
-        caps.emplace_back(npx, std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)));
-        return caps.back().second;
-    };
-    while (cuts.back() < nu) {
-        size_t i1 = cuts.back(), mp = 0;
-        while (i1 < nu) {
-            const size_t m2 = std::max(mp, px[i1]);
-            if (i1 > cuts.back() && i1 - cuts.back() + 1 > cap_for(m2)) break;
-            mp = m2; i1++;
-        }
-        cuts.push_back(i1);
-    }
-    std::vector<uint64_t> slab_off(nu);
-    size_t slab_max = 0;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        size_t off = 0;
-        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += P * px[u]; }
-        slab_max = std::max(slab_max, off);
-    }
-    std::vector<MultiPiece> list(plan.pieces.size());
-    for (size_t k = 0; k < list.size(); k++) {
-        const MultiPlanned &p = plan.pieces[k];
-        const Mic3 &m = hdr(p.unit);
-        list[k] = MultiPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)m.tw + (uint64_t)p.sx, p.patch, m.tw, (int32_t)px[p.unit], p.dx, p.dy, p.w, p.h, 0 };
-    }
-    if ((rc = s->wsi_multi_pieces.reserve(list.size() * sizeof(MultiPiece) + 64))) return rc;
-    if ((rc = s->wsi_planes.reserve(slab_max * 2 + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->wsi_multi_pieces.p, list.data(), list.size() * sizeof(MultiPiece), hipMemcpyHostToDevice, s->stream));
-    const MultiPiece *d_list = (const MultiPiece *)s->wsi_multi_pieces.p;
-    uint16_t *slab = (uint16_t *)s->wsi_planes.p;
-    std::vector<WsiPlane> pl; std::vector<uint8_t> bytes; std::vector<FillSpan> fills;
-    std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; std::vector<size_t> unit_tile; std::vector<int32_t> ust;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        const size_t u0 = cuts[b], nt = cuts[b + 1] - u0;
-        pl.clear(); bytes.clear(); fills.clear(); units.clear(); begins.clear(); ends.clear(); unit_tile.clear();
-        for (size_t k = 0; k < nt; k++) {                                                   // the blobs checked on the host, their bytes up in one copy
-            const size_t b0 = bytes.size();
-            if ((tile_status[u0 + k] = parse_tile_blob(hdr(u0 + k), blobs[u0 + k].p, blobs[u0 + k].len, pl, bytes)) != MIC_OK) {
-                bytes.resize(b0);
-                pl.resize(k * P);
-                pl.resize((k + 1) * P, WsiPlane{ 0, 0, 0, 0 });
-            }
-        }
-        if ((rc = s->io_comp.reserve(bytes.size() + 64))) return rc;
-        const uint8_t *base = (const uint8_t *)s->io_comp.p;
-        if (!bytes.empty()) HIP_TRY(hipMemcpyAsync(s->io_comp.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s->stream));
-        for (size_t q = 0; q < nt * P; q++) {
-            const WsiPlane &wp = pl[q];
-            const size_t u = u0 + q / P, npx = px[u];
-            const uint64_t at = slab_off[u] + (q % P) * npx;
-            if (wp.mode <= 1) fills.push_back(FillSpan{ at, (uint32_t)npx, wp.mode ? wp.value : 0u });
-            else if (wp.mode == 2) { units.push_back(mic_hip_unit{ at, hdr(u).tw, hdr(u).th, 0, 0 }); begins.push_back(wp.off); ends.push_back(wp.off + wp.len); unit_tile.push_back(u); }
-            else HIP_TRY(hipMemcpyAsync(slab + at, base + wp.off, npx * 2, hipMemcpyDeviceToDevice, s->stream));
-        }
-        if (!fills.empty()) {
-            if ((rc = s->wsi_stats.reserve(fills.size() * sizeof(FillSpan) + 64))) return rc;
-            HIP_TRY(hipMemcpyAsync(s->wsi_stats.p, fills.data(), fills.size() * sizeof(FillSpan), hipMemcpyHostToDevice, s->stream));
-            s->timer.reset(s->stream); s->timer.mark("k_fill_spans");
-            for (size_t f0 = 0; f0 < fills.size(); f0 += kMaxGridY)
-                hipLaunchKernelGGL(k_fill_spans, dim3(4, (unsigned)std::min<size_t>(kMaxGridY, fills.size() - f0)), dim3(256), 0, s->stream, slab, (const FillSpan *)s->wsi_stats.p + f0);
-            HIP_TRY(hipGetLastError());
-        }
-        if (!units.empty()) {
-            if ((rc = session_decode_enqueue_spans(s, base, begins.data(), ends.data(), units.data(), (int)units.size(), slab))) return rc;
-            ust.resize(units.size());
-            if ((rc = session_decode_finish(s, ust.data()))) return rc;
-            for (size_t k = 0; k < ust.size(); k++) if (tile_status[unit_tile[k]] == MIC_OK) tile_status[unit_tile[k]] = ust[k];
-        }
-        const size_t p0 = plan.first[u0], np = plan.first[u0 + nt] - p0;
-        int mw = 1, mh = 1;
-        for (size_t k = p0; k < p0 + np; k++) { mw = std::max(mw, plan.pieces[k].w); mh = std::max(mh, plan.pieces[k].h); }
-        const dim3 grid((unsigned)np, row_chunks(mw, mh)), block(256);                      // (np >= 1: every unit has a piece; np <= 2^31 - 1: multi_plan)
-        s->timer.reset(s->stream); s->timer.mark("k_wsi_multi_gather");
-        if (P == 3) hipLaunchKernelGGL(k_wsi_multi_gather, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint8_t *)d_out, pw, ph);
-        else if (bps == 16) hipLaunchKernelGGL(k_wsi_multi_gather_grey<uint16_t>, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint16_t *)d_out, pw, ph);
-        else hipLaunchKernelGGL(k_wsi_multi_gather_grey<uint8_t>, grid, block, 0, s->stream, (const uint16_t *)slab, d_list + p0, (uint8_t *)d_out, pw, ph);
-        s->timer.mark("end");
-        HIP_TRY(hipGetLastError());
-        if (units.empty()) HIP_TRY(hipStreamSynchronize(s->stream));                        // (session_decode_finish has waited otherwise: bytes and fills are reused)
-        ++*nslab;
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
     return MIC_OK;
 }
 
@@ -1212,13 +1120,14 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     if (bps == 16 && ((size_t)d_out & 1)) return MIC_ERR_ARGS;
     const size_t nu = plan.units.size();
     std::vector<TileBlob> blobs; blobs.reserve(nu);
+    std::vector<const Mic3 *> um(nu);
     std::vector<std::vector<uint8_t>> keep;
     std::vector<size_t> tiles;
     for (size_t u = 0; u < nu;) {                                                           // each slide's blobs in one request
         const uint32_t f = plan.units[u].slide;
         size_t v = u;
         tiles.clear();
-        for (; v < nu && plan.units[v].slide == f; v++) tiles.push_back((size_t)plan.units[v].tile);
+        for (; v < nu && plan.units[v].slide == f; v++) { tiles.push_back((size_t)plan.units[v].tile); um[v] = &plan.slides[f].hdr(); }
         if (fetch) {
             std::vector<TileBlob> got;
             keep.emplace_back();
@@ -1236,14 +1145,14 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     }
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
-    if ((rc = multi_read(s, plan, blobs, channels == 3 ? 3 : 1, bps, pw, ph, d_out, need, tst, &nslab))) return rc;
+    if ((rc = read_patches(s, plan, um, pw, ph, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab))) return rc;
     if (status) {
         for (int i = 0; i < n; i++) {
             const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]];
             const int32_t level = xysl[4 * (size_t)i + 3];
             status[i] = sl.status != MIC_OK ? sl.status : (level < 0 || level >= (int)sl.hdr().lv.size()) ? MIC_ERR_ARGS : MIC_OK;
         }
-        for (const MultiPlanned &p : plan.pieces) if (status[p.patch] == MIC_OK) status[p.patch] = tst[p.unit];   // (pieces: in tile order)
+        fold_tile_status(plan, tst, status);
     }
     if (stats) {
         uint64_t read = 0;
@@ -1450,10 +1359,10 @@ int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, con
     PatchPlan plan;
     const int rc = plan_patches(level_w, level_h, tile_w ? tile_w : 256, tile_h ? tile_h : 256, xy, n, pw, ph, plan);
     if (rc) return rc;
-    if (ntiles) *ntiles = plan.tiles.size();
+    if (ntiles) *ntiles = plan.units.size();
     if (npieces) *npieces = plan.pieces.size();
-    if (plan.tiles.size() > cap) return MIC_ERR_CAPACITY;
-    std::copy(plan.tiles.begin(), plan.tiles.end(), tiles);
+    if (plan.units.size() > cap) return MIC_ERR_CAPACITY;
+    for (size_t u = 0; u < plan.units.size(); u++) tiles[u] = plan.units[u].tile;
     return MIC_OK;
 } MIC_ABI_CATCH
 
@@ -1688,15 +1597,16 @@ int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_
     const size_t P = (size_t)m.planes();
     PatchPlan plan;
     if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
-    return read_patches(s, m, plan, n, pw, ph, session_slab_tiles(m), d_out, need, status, stats,
-                        [&](size_t t0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
+    const std::vector<const Mic3 *> um(plan.units.size(), &m);
+    return level_patches(s, plan, um, n, pw, ph, [&](size_t) { return session_slab_tiles(m); },
+                         [&](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
         for (size_t k = 0; k < nt; k++) {
-            const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)plan.tiles[t0 + k]) * P;
+            const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)plan.units[u0 + k].tile) * P;
             pl.insert(pl.end(), rec, rec + P);
         }
         *base = (const uint8_t *)W.bytes.p;
         return MIC_OK;
-    });
+    }, d_out, need, status, stats);
 } MIC_ABI_CATCH
 
 int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int *heights, int cap) try {

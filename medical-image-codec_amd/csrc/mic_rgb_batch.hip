@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) k_rgb_batch_from_planes(const uint16_t *p
 
 // Planes the unit codec does not write, on decode (decompressWSIPlane, wsicompress.go:494-519): mode 0 / 1 a constant -- the plane's
 // padded extent in 16-byte stores, a plane starts 16-byte aligned --, mode 3 the raw little-endian pixels at blobs + src_off, which
-// may be an odd address: two byte loads a pixel.  grid = (chunks, records): k_fill_planes with a record per plane.
+// may be an odd address: two byte loads a pixel.  grid = (chunks, records): as k_fill_spans, a record per plane.
 // BOUNDS: a record's plane holds rgb_stride(npx) u16 at plane_off; the host has checked that the blob holds 2 npx bytes at src_off.
 struct RgbFill { uint64_t plane_off, src_off; uint32_t npx, mode_value; };   // mode_value = mode | value << 8
 __global__ void __launch_bounds__(256) k_rgb_batch_fill(uint16_t *planes, const uint8_t *blobs, const RgbFill *fill) {

@@ -175,7 +175,8 @@ struct mic_hip_session {
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
     DevBuf mic2_pieces;                    // MIC2 crops: a call's piece / footprint list (mic_mic2_crops.hip)
     DevBuf strip_pieces;                   // strip-file crops: a call's piece list (mic_strip_crops.hip)
-    DevBuf wsi_multi_pieces;               // MIC3 patches of many slides: a call's piece list (mic_api_ext.hip)
+    DevBuf wsi_pieces, wsi_fills;          // MIC3 patches: a call's piece list; MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
+    std::vector<uint8_t> wsi_host_bytes;   // MIC3 patches from blobs: a sub-batch's stream bytes on their way up; kept, so that a loop of calls touches the same pages
     DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
     DevBuf rgb_payload, rgb_payload2;      // ... and its assembled blobs: two halves, one goes down while the other is written
     PinnedU64 rgb_pin;                     // ... the host's copy of the plane statistics / the blob heads
@@ -332,13 +333,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_multi_pieces, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_multi_pieces, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();

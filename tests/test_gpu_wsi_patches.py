@@ -20,7 +20,10 @@ import wsi_patch_slides as S
 
 pytestmark = pytest.mark.gpu
 
-PATCHES = [(48, 40), (130, 70), (1, 1)]
+# (47, 3): an odd width, so that every second row of a 16-bit patch starts off a 4-byte boundary -- the grey kernel's dword rows and
+# its u16 rows alternate inside one piece
+PATCHES = [(48, 40), (130, 70), (1, 1), (47, 3)]
+ODD = (47, 3)
 
 
 @pytest.fixture(scope="module")
@@ -131,7 +134,11 @@ def test_three_front_doors_give_the_same_bytes(mic, slides, fmt):
         assert sum(n for _, n in src.reads) == body
         src.reads.clear()
         got, st, stats = _read(lambda a, w, h, d, cap: rd.read_patches(level, a, w, h, d, cap), xy, pw, ph, img)
+        reads = list(src.reads)
+        oxy = S.origins(img.shape[1], img.shape[0], S.TILE, S.TILE, *ODD)
+        odd, ost, _ = _read(lambda a, w, h, d, cap: rd.read_patches(level, a, w, h, d, cap), oxy, *ODD, img)
     assert np.array_equal(got, base) and np.array_equal(st, st0) and stats == stats0
+    assert np.array_equal(odd, S.expected(img, oxy, *ODD)) and (ost == 0).all()
     tiles, _ = _touched(mic, sl, level, xy, pw, ph)
     offs = np.concatenate([[0], np.cumsum([len(b) for b in f.blobs])])
     want = np.zeros(len(sl["file"]), dtype=np.int32)
@@ -139,7 +146,7 @@ def test_three_front_doors_give_the_same_bytes(mic, slides, fmt):
         t = f.levels[level][4] + int(t)
         want[body + offs[t]: body + offs[t + 1]] += 1
     fetched = np.zeros_like(want)
-    for off, n in src.reads:
+    for off, n in reads:
         fetched[off: off + n] += 1
     assert np.array_equal(fetched, want)
     # the store: the same pixels through Session.wsi_encode; the coded slide stays on the device
@@ -154,6 +161,20 @@ def test_three_front_doors_give_the_same_bytes(mic, slides, fmt):
             assert np.array_equal(got, S.expected(li, pts, pw, ph)) and (st == 0).all(), lv
             if lv == level:
                 assert np.array_equal(got, base) and stats == stats0
+            # the odd width, and (level 0) one sub-batch that holds constant planes (the white and the black tile) beside streams
+            # (the noise tile, the ramp).  The store keeps no mode bytes a test can read: that the white and the black tile are
+            # constant planes there is inferred from their pixels (one value over the whole tile), not read back.  Raw planes:
+            # the store has none -- it is written by the encoder, which never emits mode 3 here (see the module docstring) --
+            # so mode 3 is the file door's to cover (test_patches_equal_the_padded_level_image).
+            pts = S.origins(li.shape[1], li.shape[0], S.TILE, S.TILE, *ODD)
+            if lv == 0:
+                pts = pts + [(2 * S.TILE + 3, S.TILE + 5)]                # inside the white tile, which no origin of S.origins reaches
+                tiles, _ = _touched(mic, sl, 0, pts, *ODD)
+                assert {S.NOISE_TILE, S.WHITE_TILE, S.BLACK_TILE} <= set(int(t) for t in tiles)
+            got, st, stats = _read(lambda a, w, h, d, cap: sess.wsi_read_patches(lv, a, w, h, d, cap), pts, *ODD, li)
+            assert np.array_equal(got, S.expected(li, pts, *ODD)) and (st == 0).all(), lv
+            if lv == 0:
+                assert stats["slabs"] == 1 and stats["tiles_decoded"] == tiles.size
     finally:
         sess.close()
 
@@ -161,7 +182,9 @@ def test_three_front_doors_give_the_same_bytes(mic, slides, fmt):
 def test_slabs_under_a_small_workspace(mic, slides):
     """A child process with an 8 MB workspace ceiling: a sub-batch of the unit codec then holds six 64 x 64 RGB tiles (about 0.42 MB
     of tier-1 slabs per plane), so the twelve tiles of level 0 take two slabs.  The bytes must be those of the unconstrained call,
-    and decompress_wsi_level of the same file must succeed under the same ceiling."""
+    and decompress_wsi_level of the same file must succeed under the same ceiling.  The store door cuts by the same figure: its
+    ceiling is the smaller of that workspace bound and of what a 16 GB plane slab holds (far more tiles than twelve), so under 8 MB
+    it reports the file door's slab count for the same twelve tiles."""
     sl = slides["rgb"]
     xy = [(x, y) for y in range(-10, S.H, 45) for x in range(-10, S.W, 55)]
     want, st, stats = _read(_file_call(mic, sl["file"], 0), xy, 48, 40, sl["levels"][0])
@@ -180,6 +203,15 @@ st, stats = mic.wsi_read_patches(data, 0, xy, 48, 40, t.data_ptr(), t.numel())
 assert (st == 0).all() and stats["tiles_decoded"] == 12 and stats["slabs"] >= 2, stats
 got = t.cpu().numpy()
 assert np.array_equal(got, S.expected(img, xy, 48, 40))
+sess = mic.Session(64, S.TILE * S.TILE)
+d_px = torch.from_numpy(img.reshape(-1).copy()).cuda()
+sess.wsi_encode(d_px.data_ptr(), S.W, S.H, tile_w=S.TILE, tile_h=S.TILE, levels=S.LEVELS, **S.fmt_args("rgb"))
+t2 = torch.full((len(xy), 40, 48, 3), 0xA5, dtype=torch.uint8, device="cuda")
+st2, stats2 = sess.wsi_read_patches(0, xy, 48, 40, t2.data_ptr(), t2.numel())
+sess.close()
+assert (st2 == 0).all() and stats2["tiles_decoded"] == 12, stats2
+assert stats2["slabs"] == stats["slabs"] and stats2["slabs"] >= 2, (stats2, stats)
+assert np.array_equal(t2.cpu().numpy(), S.expected(img, xy, 48, 40))
 print("ok", hashlib.sha256(got.tobytes()).hexdigest())
 ''' % (ROOT, os.path.join(ROOT, "tests"), xy)
     env = dict(os.environ, MIC_HIP_WS_BUDGET_MB="8")

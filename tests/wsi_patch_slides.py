@@ -4,6 +4,7 @@ import numpy as np
 W, H, TILE, LEVELS = 200, 150, 64, 3
 FORMATS = ("rgb", "grey8", "grey16")
 NOISE_TILE = 1          # level-0 tile (1, 0): whole-tile noise; raw_plane_file stores it raw
+WHITE_TILE, BLACK_TILE = 6, 4   # level-0 tiles (2, 1) and (0, 1): constant planes
 
 
 def fmt_args(fmt):
