@@ -12,8 +12,9 @@
 //   * a round = ONE table look-up instruction for all N states of all three streams, nbBits from v_ffbh, the offset of a
 //     state's bits inside the round from a DPP prefix sum over the N lanes of its stream (quad_perm / row_shr: no LDS, no
 //     readlane), the bits from a funnel shift of the stream's bit window, kept in a 256-dword LDS ring;
-//   * N = 2 and N = 4: the round's window (32 / 64 bits) is read at the round's start position together with the table look-ups,
-//     so a round costs one LDS round trip (115 cycles for two symbols, 136 for four); N = 8: every lane reads its own window at
+//   * N = 4: the round's 64-bit window is read at the round's start position together with the table look-ups, so a round costs
+//     one LDS round trip (136 cycles for four symbols); N = 2: the 32-bit window is picked from three ring dwords read a round
+//     EARLIER, so nothing but the look-up's own wait stands in the round (108 cycles for two symbols); N = 8: every lane reads its own window at
 //     its own bit position once the prefix sum is known: two round trips for eight symbols.  More states decode FASTER;
 //   * the lanes of a wave that own no state clone stream 0 (same addresses: LDS broadcasts); all 64 lanes share the
 //     per-chunk work, which is small: ring refill (64 dwords per stream and 128 symbols, prefetched a chunk ahead) and one
@@ -41,6 +42,11 @@ template <int TL> struct LsGeom {
     // The bit window's ring: blocks of 64 dwords.  A chunk of 128 symbols takes at most 4 * tableLog dwords off it (+ 2 the window
     // reads reach below the position): under a block up to tableLog 15, so three blocks stored (the position's, one above, one below)
     // and a fourth in flight do; at tableLog 16 a chunk can take a whole block, so the ring is twice as long and runs a block deeper.
+    // The reads that reach furthest are those of N = 2 and N = 4, three dwords from the dword of p - 32 on for every position p of a
+    // chunk, its last included: with D the dword of the chunk's first position, in block b, they span dwords D - 4 * tableLog - 1
+    // ... D + 1.  tableLog 15: D - 61 >= 64 b - 61 = 64 (b - 1) + 3, inside block b - 1, and D + 1 inside b + 1 at the most: the
+    // three stored blocks.  tableLog 16: D - 65 >= 64 (b - 2) + 63, inside block b - 2, the fourth of the four stored there (DEPTH 3).
+    // The block stored at a chunk's end takes the slot of block b + 2 (b + 5), which no chunk from here on reads.
     static constexpr int RING_BLOCKS = TL == 16 ? 8 : 4;
     static constexpr int DEPTH = TL == 16 ? 3 : 2;                        // the block in flight is the position's block - DEPTH
     static constexpr int RING_BITS = TL == 16 ? 9 : 8;                    // dword index bits
@@ -271,72 +277,97 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
         }
     };
     // N = 2: the 64 rounds of a chunk as ONE hand-scheduled instruction stream.  A lone wave issues in order, one instruction per
-    // ~6 cycles whether it depends on its predecessor or not (tools/ubench_ls.hip), and a round is bound by that: what counts is
-    // the number of instructions.  Sixteen per round:
-    //   head  s_waitcnt (entry) | v_ffbh | v_sub: m = -nbBits | ds_write_b16: the state the round starts from, to the stage |
-    //         s_waitcnt (window) | v_alignbit: the 32-bit window at q | v_and_dpp: the partner's m for the second state, 0 for the
-    //         first | v_alignbit(window, window, that): a ROTATE, so the first state (shift 0) keeps the window and the second sees
-    //         it past the first one's bits (what wraps into the low bits is never read: two states take <= 26 of the 32) |
-    //         v_alignbit(entry, window', m): the next state | v_lshl_add: its table address | ds_read_u16
-    //   tail  v_add_dpp: minus the round's bits | v_add: bit position | v_bfe + v_lshl_add: ring address | ds_read2_b32 (window)
-    //         -- behind the look-up, in the shadow of its latency.
-    // 115 cycles per round (tools/ubench_ls.hip: the table look-up alone, entry -> ffbh -> sub -> alignbit -> lshl_add -> entry, takes
-    // 80: ~60 of LDS latency and ~4.3 per instruction, DPP, s_waitcnt and LDS issue alike; the stage store in the tail instead:
-    // 122, because the window read then leaves later and the head waits for it; v_and_dpp in front of the window wait: 118).
-    // The stage store, the s_waitcnt and the window v_alignbit cover the two wait states a DPP read of a freshly written VGPR
-    // needs.  LDS queue at the top of a round, oldest first: entry, window.  v62 / v63 take the window's two dwords (a 64-bit asm
+    // ~4.3-6 cycles whether it depends on its predecessor or not (tools/ubench_ls.hip), and a round is the table look-up's LDS trip
+    // (~64 cycles) plus every issue slot between the entry's arrival and the next look-up.  Seven sit there (ZB: nine):
+    //   head  s_waitcnt (entry) | v_ffbh_u32_dpp: the PARTNER's leading zeros, from its entry (fresh from LDS, so the DPP read has no
+    //         VALU-write hazard to pad) | v_ffbh | v_mad_i32_i24: the second state's offset C - c' = minus the first state's nbBits,
+    //         0 * c' + 0 for the first state | v_sub: m = -nbBits | v_alignbit(window, window, offset): a ROTATE, so the first state
+    //         (shift 0) keeps the window and the second sees it past the first one's bits (what wraps into the low bits is never
+    //         read: the two states take <= 32 bits together) | v_alignbit(entry, window', m): the next state (ZB: + compare and
+    //         select, m = 0 keeps the entry) | v_lshl_add: its table address | ds_read_u16
+    //   tail  ds_write_b16: the state the NEXT round starts from, to the stage (the chunk's first by the prologue) | v_add_dpp: minus
+    //         the round's bits | v_add: bit position | v_bfe + v_lshl_add: ring address | the next round's window (below) | ds_read2_b32
+    //         + ds_read_b32: three ring dwords at the new position -- behind the look-up, in the shadow of its latency.
+    // The window is NOT read at the round's position and waited for in the head (that was 115 cycles per round: the read could
+    // leave only ~20 cycles behind the look-up and the head waited for it).  It is picked, in the tail, from the three dwords the
+    // tail of the round BEFORE read at ITS position p: the chunk tracks q - 32, so they are the dwords of q - 32, q, q + 32 there and
+    // hold grid bits [p - 32, p + 32) at least; two states take <= 2 * tableLog <= 32 bits, so the new position p' is in [p - 32, p]
+    // and its window [p', p' + 32) is inside them: v_alignbit of the upper pair when the ring address of p' - 32 is still that of
+    // p - 32, of the lower pair when it is the one below (they differ by one dword at most; a 0-bit round keeps the address) -- a
+    // compare of the two addresses, two v_cndmask, one v_alignbit with the same shift operand (it uses the low five bits).  The
+    // selects read the old dwords before the new read is issued, so one register set does; the two ring addresses alternate
+    // between two registers: the .rept body is a double round.  108 cycles per round against 116 for the earlier order
+    // (profiles/ubench_ls_early_window.txt; either change alone gains nothing: the early window with v_and_dpp of m and its two
+    // pad slots 115-117, v_ffbh_dpp with the window read in the head 118-120).
+    // Ring reach: dwords (p - 32) >> 5 ... + 2 for every position p of the chunk, its last included -- one dword below the
+    // position's and one above, exactly what N = 4 reads (LsGeom); the two mirror dwords keep three dwords from slot 255 linear.
+    // LDS queue, oldest first, at the entry's wait: entry, stage, dwords (2) -> lgkmcnt(3); at the tail's wait for the dwords of
+    // the round before: dwords (2), entry, stage -> lgkmcnt(2).  The chunk's last round neither looks up nor reads: the next
+    // chunk's prologue does both again, no window state crosses the statement.  v60-v62 take the three dwords (a 64-bit asm
     // operand cannot be split into its halves, fixed registers can).
-#define LS_ROUND_LOOKUP \
+#define LS2_LOOKUP \
         "v_lshl_add_u32 %[at], %[st], 1, %[cb]\n\t" \
         "ds_read_u16 %[e], %[at]\n\t"
-#define LS_ROUND_ADVANCE \
-        "v_add_u32_dpp %[pre], %[m], %[m] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "v_add_u32 %[q], %[q], %[pre]\n\t"
-#define LS_ROUND_WINDOW \
-        "v_bfe_u32 %[at], %[q], 5, %[RW]\n\t" \
-        "v_lshl_add_u32 %[at], %[at], 2, %[ringb]\n\t" \
-        "ds_read2_b32 v[62:63], %[at] offset1:1\n\t"
-#define LS_ROUND_HEAD \
-        "s_waitcnt lgkmcnt(1)\n\t" \
+#define LS2_DWORDS(A_) \
+        "ds_read2_b32 v[60:61], " A_ " offset1:1\n\t" \
+        "ds_read_b32 v62, " A_ " offset:8\n\t"
+    // AN_ / AO_: the registers of the new and of the previous ring address
+#define LS2_ROUND(AN_, AO_) \
+        "s_waitcnt lgkmcnt(3)\n\t" \
+        "v_ffbh_u32_dpp %[cp], %[e] quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_ffbh_u32 %[c], %[e]\n\t" \
+        "v_mad_i32_i24 %[pre], %[cp], %[mk1], %[Ck]\n\t" \
         "v_sub_u32 %[m], %[C], %[c]\n\t" \
+        "v_alignbit_b32 %[hi], %[hi], %[hi], %[pre]\n\t" \
+        ".if %[ZBF]\n\t" \
+        "v_alignbit_b32 %[hi], %[e], %[hi], %[m]\n\t" \
+        "v_cmp_eq_u32 vcc, 0, %[m]\n\t" \
+        "v_cndmask_b32 %[st], %[hi], %[e], vcc\n\t" \
+        ".else\n\t" \
+        "v_alignbit_b32 %[st], %[e], %[hi], %[m]\n\t" \
+        ".endif\n\t" \
+        ".if ls_off < 256\n\t" \
+        LS2_LOOKUP \
         "ds_write_b16 %[stg], %[st] offset:ls_off\n\t" \
-        ".set ls_off, ls_off+4\n\t" \
-        "s_waitcnt lgkmcnt(1)\n\t" \
-        "v_alignbit_b32 %[hi], v63, v62, %[q]\n\t" \
-        "v_and_b32_dpp %[pre], %[m], %[mk1] quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-        "v_alignbit_b32 %[hi], %[hi], %[hi], %[pre]\n\t"
-#define LS_ROUND_TAIL LS_ROUND_LOOKUP LS_ROUND_ADVANCE LS_ROUND_WINDOW
-    // START / COUNT: stage byte offset of the first state and rounds of this piece (a whole chunk: 0, 64)
+        ".endif\n\t" \
+        "v_add_u32_dpp %[pre], %[m], %[m] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_add_u32 %[q], %[q], %[pre]\n\t" \
+        ".if ls_off < 256\n\t" \
+        "v_bfe_u32 " AN_ ", %[q], 5, %[RW]\n\t" \
+        "v_lshl_add_u32 " AN_ ", " AN_ ", 2, %[ringb]\n\t" \
+        "v_cmp_eq_u32 vcc, " AN_ ", " AO_ "\n\t" \
+        "s_waitcnt lgkmcnt(2)\n\t" \
+        "v_cndmask_b32 %[lo], v60, v61, vcc\n\t" \
+        "v_cndmask_b32 %[hh], v61, v62, vcc\n\t" \
+        "v_alignbit_b32 %[hi], %[hh], %[lo], %[q]\n\t" \
+        LS2_DWORDS(AN_) \
+        ".endif\n\t" \
+        ".set ls_off, ls_off+4\n\t"
+    // a whole chunk: 64 rounds.  The prologue looks up, stages the first state, reads the three dwords at the chunk's first position
+    // and takes round 0's window from their upper pair; round 0's tail takes round 1's from the same three.
     // (a macro, not a lambda: clang does not capture through asm operands in a generic lambda)
-#define LS_CHUNK2(START_, COUNT_) do { \
-        uint32_t e, c, m, hi, pre, at; \
-        if (ZB) \
-            asm volatile(".set ls_off, %[S]\n\t" \
-                         LS_ROUND_LOOKUP LS_ROUND_WINDOW \
-                         ".rept %[R]\n\t" \
-                         LS_ROUND_HEAD \
-                         "v_alignbit_b32 %[hi], %[e], %[hi], %[m]\n\t" \
-                         "v_cmp_eq_u32 vcc, 0, %[m]\n\t" \
-                         "v_cndmask_b32 %[st], %[hi], %[e], vcc\n\t" \
-                         LS_ROUND_TAIL \
-                         ".endr\n\t" \
-                         "s_waitcnt lgkmcnt(0)" \
-                         : [st] "+v"(st), [q] "+v"(q), [e] "=&v"(e), [c] "=&v"(c), [m] "=&v"(m), [hi] "=&v"(hi), [pre] "=&v"(pre), [at] "=&v"(at) \
-                         : [C] "v"(C), [mk1] "v"(mk1), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(stgb), [S] "n"(START_), [R] "n"(COUNT_), [RW] "n"(LS_RBITS) \
-                         : "memory", "vcc", "v62", "v63"); \
-        else \
-            asm volatile(".set ls_off, %[S]\n\t" \
-                         LS_ROUND_LOOKUP LS_ROUND_WINDOW \
-                         ".rept %[R]\n\t" \
-                         LS_ROUND_HEAD \
-                         "v_alignbit_b32 %[st], %[e], %[hi], %[m]\n\t" \
-                         LS_ROUND_TAIL \
-                         ".endr\n\t" \
-                         "s_waitcnt lgkmcnt(0)" \
-                         : [st] "+v"(st), [q] "+v"(q), [e] "=&v"(e), [c] "=&v"(c), [m] "=&v"(m), [hi] "=&v"(hi), [pre] "=&v"(pre), [at] "=&v"(at) \
-                         : [C] "v"(C), [mk1] "v"(mk1), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(stgb), [S] "n"(START_), [R] "n"(COUNT_), [RW] "n"(LS_RBITS) \
-                         : "memory", "v62", "v63"); \
+#define LS_CHUNK2() do { \
+        uint32_t e, c, cp, m, hi, pre, at, a0, a1, lo, hh; \
+        q -= 32; \
+        asm volatile(".set ls_off, 4\n\t" \
+                     LS2_LOOKUP \
+                     "ds_write_b16 %[stg], %[st]\n\t" \
+                     "v_bfe_u32 %[a1], %[q], 5, %[RW]\n\t" \
+                     "v_lshl_add_u32 %[a1], %[a1], 2, %[ringb]\n\t" \
+                     LS2_DWORDS("%[a1]") \
+                     "s_waitcnt lgkmcnt(0)\n\t" \
+                     "v_alignbit_b32 %[hi], v62, v61, %[q]\n\t" \
+                     ".rept 32\n\t" \
+                     LS2_ROUND("%[a0]", "%[a1]") \
+                     LS2_ROUND("%[a1]", "%[a0]") \
+                     ".endr\n\t" \
+                     "s_waitcnt lgkmcnt(0)" \
+                     : [st] "+v"(st), [q] "+v"(q), [e] "=&v"(e), [c] "=&v"(c), [cp] "=&v"(cp), [m] "=&v"(m), [hi] "=&v"(hi), [pre] "=&v"(pre), \
+                       [at] "=&v"(at), [a0] "=&v"(a0), [a1] "=&v"(a1), [lo] "=&v"(lo), [hh] "=&v"(hh) \
+                     : [C] "v"(C), [mk1] "v"(mk1), [Ck] "v"(mk1 & C), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(stgb), [RW] "n"(LS_RBITS), \
+                       [ZBF] "n"(ZB ? 1 : 0) \
+                     : "memory", "vcc", "v60", "v61", "v62"); \
+        q += 32; \
     } while (0)
     // N = 4: one LDS round trip per round as well (tools/ubench_ls.hip, k_cand4: 136 cycles per round of four symbols; with every
     // lane reading its own window behind the prefix sum -- two round trips -- it was 200).  The round's 64-bit window is read at
@@ -417,7 +448,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 #endif
     for (uint32_t ch = 0; ch < maxch; ch++) {
         if (ch == chunks) { sv_st = st; sv_q = q; }                         // (per lane) this stream is done: it runs on, harmlessly, on its own table
-        if (N == 2) LS_CHUNK2(0, 64);
+        if (N == 2) LS_CHUNK2();
         else if (N == 4) LS_CHUNK4();
         else {
 #pragma unroll

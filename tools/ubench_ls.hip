@@ -193,6 +193,123 @@ template <int W, int P> int cand(const char *name, const uint16_t *d_tab, uint32
     return 0;
 }
 
+// Candidate rounds that take the window read off the round's dependent path (measured against k_cand<0, 1>, the shipped order).
+// E1: 1 = the window a round early.  The tail of a round, where the next position q' is known, picks the next round's window from
+//     three ring dwords read a round before (the dwords of q - 32, q, q + 32 for the position q of that time: two states take
+//     <= 32 bits, so q' is in the first or the second of them -- the same ring address as then, or the one below) with a compare
+//     of the two ring addresses, two v_cndmask and one v_alignbit, and then reads the three dwords at q'.  All of it sits in the
+//     shadow of the look-up; behind the entry's s_waitcnt the head holds no LDS wait.  One register set does: the selects read
+//     the old dwords before the new read is issued.  The ring addresses alternate between two registers: a double round.
+// E2: where the second state's offset (the first state's nbBits) comes from.  0 = v_and_b32_dpp of m (shipped; m is fresh from a
+//     VALU write, so two slots must separate them) | 1 = v_ffbh_u32_dpp of the partner's ENTRY (fresh from LDS: no hazard), then one
+//     v_mad_i32_i24 per lane (state 1: C - c', state 0: 0 * c' + 0), lanes as shipped | 2 = the same on N = 4's lane layout (a DPP
+//     row per stream, EXEC = lanes 0 and 1 of a row): row_shr:1 without bound_ctrl leaves lane 0's register at its preset C, v_sub.
+//     With E1 the stage store moves to the tail (it stores the state the NEXT round starts from); E1 alone keeps it in the head,
+//     beside an s_nop, as the two slots the DPP read of m needs.
+// LDS queue, oldest first, at the entry's wait | at the tail's wait for the three dwords (E1):
+//     E1 = 0: entry, window                                   (as shipped)
+//     E1 = 1, E2 = 0: entry, dwords (2)                       | dwords (2), stage, entry
+//     E1 = 1, E2 > 0: entry, stage, dwords (2)                | dwords (2), entry, stage
+#define UE_LOOKUP "v_lshl_add_u32 %[at], %[st], 1, %[cb]\n\tds_read_u16 %[e], %[at]\n\t"
+#define UE_ROUND(AN_, AO_) \
+            ".if %[E1] == 0\n\ts_waitcnt lgkmcnt(1)\n\t.elseif %[E2] == 0\n\ts_waitcnt lgkmcnt(2)\n\t.else\n\ts_waitcnt lgkmcnt(3)\n\t.endif\n\t" \
+            ".if %[E2] == 0\n\t" \
+            "v_ffbh_u32 %[c], %[e]\n\t" \
+            "v_sub_u32 %[m], %[C], %[c]\n\t" \
+            "ds_write_b16 %[stg], %[st] offset:ls_off\n\t.set ls_off, ls_off+4\n\t" \
+            ".if %[E1] == 0\n\ts_waitcnt lgkmcnt(1)\n\tv_alignbit_b32 %[hi], v63, v62, %[q]\n\t.else\n\ts_nop 0\n\t.endif\n\t" \
+            "v_and_b32_dpp %[pre], %[m], %[mk1] quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+            ".else\n\t" \
+            ".if %[E2] == 1\n\tv_ffbh_u32_dpp %[cp], %[e] quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+            ".else\n\tv_ffbh_u32_dpp %[cp], %[e] row_shr:1 row_mask:0xf bank_mask:0xf\n\t.endif\n\t" \
+            "v_ffbh_u32 %[c], %[e]\n\t" \
+            ".if %[E2] == 1\n\tv_mad_i32_i24 %[pre], %[cp], %[mk1], %[Ck]\n\t.else\n\tv_sub_u32 %[pre], %[C], %[cp]\n\t.endif\n\t" \
+            "v_sub_u32 %[m], %[C], %[c]\n\t" \
+            ".if %[E1] == 0\n\t" \
+            "ds_write_b16 %[stg], %[st] offset:ls_off\n\t.set ls_off, ls_off+4\n\t" \
+            "s_waitcnt lgkmcnt(1)\n\tv_alignbit_b32 %[hi], v63, v62, %[q]\n\t" \
+            ".endif\n\t" \
+            ".endif\n\t" \
+            "v_alignbit_b32 %[hi], %[hi], %[hi], %[pre]\n\t" \
+            "v_alignbit_b32 %[st], %[e], %[hi], %[m]\n\t" \
+            UE_LOOKUP \
+            ".if %[E1] != 0 && %[E2] != 0\n\t.if ls_off < 256\n\tds_write_b16 %[stg], %[st] offset:ls_off\n\t.endif\n\t.set ls_off, ls_off+4\n\t.endif\n\t" \
+            "v_add_u32_dpp %[pre], %[m], %[m] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+            "v_add_u32 %[q], %[q], %[pre]\n\t" \
+            "v_bfe_u32 " AN_ ", %[q], 5, 8\n\tv_lshl_add_u32 " AN_ ", " AN_ ", 2, %[ringb]\n\t" \
+            ".if %[E1] == 0\n\t" \
+            "ds_read2_b32 v[62:63], " AN_ " offset1:1\n\t" \
+            ".else\n\t" \
+            "v_cmp_eq_u32 vcc, " AN_ ", " AO_ "\n\t" \
+            "s_waitcnt lgkmcnt(2)\n\t" \
+            "v_cndmask_b32 %[lo], v56, v57, vcc\n\t" \
+            "v_cndmask_b32 %[hh], v57, v58, vcc\n\t" \
+            "v_alignbit_b32 %[hi], %[hh], %[lo], %[q]\n\t" \
+            "ds_read2_b32 v[56:57], " AN_ " offset1:1\n\t" \
+            "ds_read_b32 v58, " AN_ " offset:8\n\t" \
+            ".endif\n\t"
+template <int E1, int E2>
+__global__ void __launch_bounds__(192) k_early(const uint16_t *tab, uint32_t *out, int chunks, unsigned long long *cyc) {
+    extern __shared__ uint32_t s_mem[];
+    constexpr uint32_t LS = E2 == 2 ? 16 : 2;
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t g = lane / LS; if (g >= 3) g = 0;
+    const uint32_t k = lane & 1;
+    const uint32_t sbase = (wv * 3 + g) * STREAM_BYTES;
+    for (uint32_t j = 0; j < 3; j++) {
+        const uint32_t tb = ((wv * 3 + j) * STREAM_BYTES + TAB) >> 2;
+        for (uint32_t i = lane; i < 4096; i += 64) s_mem[tb + i] = ((const uint32_t *)tab)[i];
+        const uint32_t rb = ((wv * 3 + j) * STREAM_BYTES) >> 2;
+        for (uint32_t i = lane; i < 260; i += 64) s_mem[rb + i] = 0x9E3779B9u * (i + 1 + j);
+    }
+    __syncthreads();
+    const uint32_t cb = sbase + TAB - 2u * 8192u, C = 31u - 13u, ringb = sbase, stgb = sbase + STAGE + 2u * k;
+    const uint32_t mk1 = k ? ~0u : 0u, Ck = k ? C : 0u;
+    const uint64_t em = E2 == 2 ? 0x0000000300030003ull : ~0ull;
+    uint32_t st = 8192u + ((out[0] + 17u * lane) & 8191u), q = 1u << 20, cp = C;
+    uint32_t e, c, m, hi, pre, at, a0, a1, lo, hh;
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int ch = 0; ch < chunks; ch++) {
+        asm volatile(
+            ".set ls_off, 0\n\t"
+            "s_mov_b64 exec, %[em]\n\t"
+            UE_LOOKUP
+            ".if %[E1] != 0 && %[E2] != 0\n\tds_write_b16 %[stg], %[st]\n\t.set ls_off, 4\n\t.endif\n\t"
+            "v_bfe_u32 %[a1], %[q], 5, 8\n\tv_lshl_add_u32 %[a1], %[a1], 2, %[ringb]\n\t"
+            ".if %[E1] == 0\n\t"
+            "ds_read2_b32 v[62:63], %[a1] offset1:1\n\t"
+            ".else\n\t"                                                      // round 0's window from the upper pair; round 0's tail picks round 1's from the same three
+            "ds_read2_b32 v[56:57], %[a1] offset1:1\n\t"
+            "ds_read_b32 v58, %[a1] offset:8\n\t"
+            "s_waitcnt lgkmcnt(0)\n\t"
+            "v_alignbit_b32 %[hi], v58, v57, %[q]\n\t"
+            ".endif\n\t"
+            ".rept 32\n\t"
+            UE_ROUND("%[a0]", "%[a1]")
+            UE_ROUND("%[a1]", "%[a0]")
+            ".endr\n\t"
+            "s_waitcnt lgkmcnt(0)\n\t"
+            "s_mov_b64 exec, -1"
+            : [st] "+v"(st), [q] "+v"(q), [cp] "+v"(cp), [e] "=&v"(e), [c] "=&v"(c), [m] "=&v"(m), [hi] "=&v"(hi), [pre] "=&v"(pre), [at] "=&v"(at),
+              [a0] "=&v"(a0), [a1] "=&v"(a1), [lo] "=&v"(lo), [hh] "=&v"(hh)
+            : [C] "v"(C), [mk1] "v"(mk1), [Ck] "v"(Ck), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(stgb), [em] "s"(em), [E1] "n"(E1), [E2] "n"(E2)
+            : "memory", "vcc", "v56", "v57", "v58", "v62", "v63");
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    if (lane == 0) cyc[blockIdx.x * 3 + wv] = t1 - t0;
+    if (st == 0xFFFFFFFFu) out[1] = st + q + cp;
+}
+template <int E1, int E2> int early(const char *name, const uint16_t *d_tab, uint32_t *d_out, unsigned long long *d_cyc, int chunks) {
+    CK(hipFuncSetAttribute((const void *)k_early<E1, E2>, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * STREAM_BYTES));
+    hipLaunchKernelGGL((k_early<E1, E2>), dim3(1), dim3(192), 9 * STREAM_BYTES, 0, d_tab, d_out, chunks, d_cyc);
+    CK(hipDeviceSynchronize());
+    unsigned long long c[3];
+    CK(hipMemcpy(c, d_cyc, 24, hipMemcpyDeviceToHost));
+    printf("%-70s %6.1f cycles/round (waves %.1f %.1f %.1f)\n", name, (double)c[1] / ((double)chunks * 64.0), (double)c[0] / ((double)chunks * 64.0),
+           (double)c[1] / ((double)chunks * 64.0), (double)c[2] / ((double)chunks * 64.0));
+    return 0;
+}
+
 // N = 4 in ONE LDS round trip: the round's 64-bit window (three ring dwords at the round's start position) is read with the table
 // look-ups; a state's bits are the top nbBits of window << (bits of the earlier states), a v_lshlrev_b64.  The prefix sum of
 // m = -nbBits over a stream's four lanes runs in place on two v_add_u32_dpp (row_shr:1, row_shr:2, no bound_ctrl): a stream's lanes
@@ -303,12 +420,19 @@ int main() {
     CK(hipMalloc(&d_tab, 16384)); CK(hipMalloc(&d_out, 64)); CK(hipMalloc(&d_cyc, 8 * 3 * 1024));
     CK(hipMemcpy(d_tab, tab.data(), 16384, hipMemcpyHostToDevice)); CK(hipMemset(d_out, 0, 64));
     const int chunks = 400;
-    cand<0, 0>("m-only round, ds_read2 window, stage store in the tail (shipped)", d_tab, d_out, d_cyc, chunks);
+    cand<0, 0>("m-only round, ds_read2 window, stage store in the tail", d_tab, d_out, d_cyc, chunks);
     cand<1, 0>("m-only round, two ds_read_b32, stage store in the tail", d_tab, d_out, d_cyc, chunks);
-    cand<0, 1>("m-only round, ds_read2 window, stage store in the head", d_tab, d_out, d_cyc, chunks);
+    cand<0, 1>("m-only round, ds_read2 window, stage store in the head (shipped)", d_tab, d_out, d_cyc, chunks);
     cand<1, 1>("m-only round, two ds_read_b32, stage store in the head", d_tab, d_out, d_cyc, chunks);
     cand<0, 2>("... and v_and_dpp in front of the window wait", d_tab, d_out, d_cyc, chunks);
     cand<1, 2>("... the same with two ds_read_b32", d_tab, d_out, d_cyc, chunks);
+    early<0, 0>("double round, shipped order (= k_cand<0,1>)", d_tab, d_out, d_cyc, chunks);
+    early<1, 0>("E1: window a round early", d_tab, d_out, d_cyc, chunks);
+    early<0, 1>("E2: partner's nbBits by v_ffbh_dpp of its entry + v_mad, lanes as shipped", d_tab, d_out, d_cyc, chunks);
+    early<0, 2>("E2: ... row per stream, row_shr:1 + v_sub", d_tab, d_out, d_cyc, chunks);
+    early<1, 1>("E1 + E2, lanes as shipped (v_mad)", d_tab, d_out, d_cyc, chunks);
+    early<1, 2>("E1 + E2, row per stream (v_sub)", d_tab, d_out, d_cyc, chunks);
+    cand<0, 1>("shipped order again", d_tab, d_out, d_cyc, chunks);
     cand4<0>("N = 4, one LDS round trip, v_lshlrev_b64", d_tab, d_out, d_cyc, chunks);
     cand4<1>("N = 4, one LDS round trip, funnel shifts + selects", d_tab, d_out, d_cyc, chunks);
     cost<7, 1>("v_mov, v_lshlrev_b64, v_mov", d_tab, d_out, d_cyc, chunks); cost<7, 4>("v_mov, v_lshlrev_b64, v_mov", d_tab, d_out, d_cyc, chunks);
