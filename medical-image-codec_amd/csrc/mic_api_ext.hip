@@ -150,56 +150,8 @@ __global__ void __launch_bounds__(256) k_fill_spans(uint16_t *slab, const FillSp
     uint16_t *p = slab + f.off;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < f.npx; i += (size_t)gridDim.x * blockDim.x) p[i] = (uint16_t)f.value;
 }
-// ... and a piece, one patch-tile overlap, says where its first sample lies in plane 0 (src, samples into the slab), how far apart
-// the tile's rows (stride = tw) and planes (pstride = tw * th) are, and where its w x h samples go: (dx, dy) of patch `patch`.  The
-// host plans them (plan_clip): the kernels divide nothing.
-struct GatherPiece { uint64_t src; int32_t patch, stride, pstride, dx, dy, w, h, pad; };
-
-// YCoCgRInverse of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at whatever byte offset the patch
-// row has.  slab: a sub-batch's planes; out: [patch][ph][pw][3] u8.  grid = (pieces, row chunks); lanes along x of a piece row
-// (piece_lanes): a wave reads 64 neighbouring samples of each plane and writes 192 neighbouring bytes.
-__global__ void __launch_bounds__(256) k_wsi_gather_patches(const uint16_t *slab, const GatherPiece *pieces, uint8_t *out, int pw, int ph) {
-    const GatherPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
-    const mic_gp<uint8_t> o = mic_g(out + (((size_t)pc.patch * ph + pc.dy) * pw + pc.dx) * 3);
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const size_t si = (size_t)y * pc.stride, di = (size_t)y * pw * 3;
-        for (int x = ln.col; x < pc.w; x += ln.lw) {
-            const int yv = py[si + x];
-            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
-            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, :113-116
-            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
-            const int t = yv - (cg >> 1);                                                   // YCoCgRInverse, asm_amd64.go:106-121
-            const int g = cg + t;
-            const int b = t - (co >> 1);
-            const int r = co + b;
-            const size_t d = di + (size_t)x * 3;
-            o[d] = (uint8_t)r; o[d + 1] = (uint8_t)g; o[d + 2] = (uint8_t)b;
-        }
-    }
-}
-// uint16ToBytes (wsicompress.go:589-603) of the piece's samples.  out: [patch][ph][pw] T.  16-bit samples: a row whose source and
-// destination are both 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16 -- with an odd tile
-// or patch width every second row is such a row (as k_strips_gather_crops).
-template <typename T>
-__global__ void __launch_bounds__(256) k_wsi_gather_patches_grey(const uint16_t *slab, const GatherPiece *pieces, T *out, int pw, int ph) {
-    const GatherPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const uint16_t *src = slab + pc.src;
-    T *dst = out + ((size_t)pc.patch * ph + pc.dy) * pw + pc.dx;
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * pc.stride);
-        const mic_gp<T> d = mic_g(dst + (size_t)y * pw);
-        if (sizeof(T) == 2 && (((size_t)s | (size_t)d) & 3) == 0) {
-            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
-            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
-            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
-            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = (T)s[pc.w - 1];
-        } else
-            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = (T)s[x];
-    }
-}
+// ... and a piece, one patch-tile overlap, is a GatherPiece (mic_pieces.h): plane 0's first sample of the overlap in the slab, the
+// tile's rows tw apart and its planes tw * th, to its place in the patch tensor.  The host plans them (plan_clip).
 
 struct Level { int w, h, tx, ty, first; };
 
@@ -293,15 +245,6 @@ void launch_planes_to_pixels(hipStream_t st, const Mic3 &m, const uint16_t *plan
         hipLaunchKernelGGL(k_wsi_plane_to_grey<uint16_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint16_t *)dst, dst_w);
     else
         hipLaunchKernelGGL(k_wsi_plane_to_grey<uint8_t>, grid, block, 0, st, planes, m.tw, m.th, place, (uint8_t *)dst, dst_w);
-}
-// np pieces (device) of a slab's planes -> out, the patch tensor (pw x ph pixels a patch; P planes a tile, bps bits a sample).  A
-// block walks its piece in passes of 256 lanes; grid y cuts the rows of tall pieces (row_chunks of mw x mh, the launch's largest).
-void launch_gather(hipStream_t st, size_t P, int bps, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh,
-                   void *out, int pw, int ph) {
-    const dim3 grid((unsigned)np, row_chunks(mw, mh)), block(256);
-    if (P == 3) hipLaunchKernelGGL(k_wsi_gather_patches, grid, block, 0, st, slab, pieces, (uint8_t *)out, pw, ph);
-    else if (bps == 16) hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint16_t>, grid, block, 0, st, slab, pieces, (uint16_t *)out, pw, ph);
-    else hipLaunchKernelGGL(k_wsi_gather_patches_grey<uint8_t>, grid, block, 0, st, slab, pieces, (uint8_t *)out, pw, ph);
 }
 // one level of the pyramid: Downsample2xRGB / Downsample2xGrey of src (sw samples across) into dst (dw x dh)
 void launch_downsample(hipStream_t st, const Mic3 &fmt, const void *src, int sw, void *dst, int dw, int dh) {
@@ -883,8 +826,6 @@ int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int p
     return MIC_OK;
 }
 
-// (patch_pointer -- d_out must be memory the session's device can write -- is shared with the MIC2 crop calls: mic_mic2_crops.hip)
-
 // Where a call's tiles come from: the planes of units u0 .. u0 + nt - 1 of the plan as nt * P records over *base (device), and each
 // tile's own host-side status: a tile that fails on the host (a blob that does not parse) still has its P records, constant zero.
 typedef std::function<int(size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *tile_status)> PatchSlabs;
@@ -898,7 +839,7 @@ SlabCeiling blob_ceiling(size_t P) { return [P](size_t npx) { return std::min<si
 // under (all of one sample format).  Every unit is decoded once, in sub-batches of as many tiles as `ceiling` allows of the largest
 // of them: tile u's P planes start slab_off[u] samples into the sub-batch's slab (the prefix sum of P * tw * th), decode_plane_slab
 // fills them from the source's records, and behind each sub-batch one gather launch writes its pieces.  The piece list goes up
-// once per call (s->wsi_pieces).  tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
+// once per call (s->pieces).  tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
 int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const SlabCeiling &ceiling,
                  const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
     const size_t nu = plan.units.size();
@@ -909,6 +850,7 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
     *nslab = 0;
     if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
     const size_t P = (size_t)um[0]->planes();
+    const GatherKind kind = P == 3 ? kGatherRGB : um[0]->bps == 16 ? kGatherU16 : kGatherU8;
     // cuts: as many tiles as the ceiling holds of the largest of them (tiles of one size: `ceiling` tiles a sub-batch)
     std::vector<size_t> px(nu), cuts{ 0 };
     for (size_t u = 0; u < nu; u++) px[u] = (size_t)um[u]->tw * um[u]->th;
@@ -938,11 +880,12 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
     for (size_t k = 0; k < list.size(); k++) {
         const PlanPiece &p = plan.pieces[k];
         const int tw = um[p.unit]->tw;
-        list[k] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)tw + (uint64_t)p.sx, p.patch, tw, (int32_t)px[p.unit], p.dx, p.dy, p.w, p.h, 0 };
+        list[k] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)tw + (uint64_t)p.sx,
+                               ((uint64_t)p.patch * (uint64_t)ph + (uint64_t)p.dy) * (uint64_t)pw + (uint64_t)p.dx, tw, pw, p.w, p.h, (int32_t)px[p.unit], 0 };
     }
-    if ((rc = s->wsi_pieces.reserve(list.size() * sizeof(GatherPiece) + 64))) return rc;
+    if ((rc = s->pieces.reserve(list.size() * sizeof(GatherPiece) + 64))) return rc;
     if ((rc = s->wsi_planes.reserve(slab_max * 2 + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->wsi_pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
     std::vector<WsiPlane> pl; std::vector<int32_t> pst;
     for (size_t b = 0; b + 1 < cuts.size(); b++, ++*nslab) {
         const size_t u0 = cuts[b], nt = cuts[b + 1] - u0;
@@ -959,7 +902,7 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
         int mw = 1, mh = 1;
         for (size_t k = p0; k < p0 + np; k++) { mw = std::max(mw, plan.pieces[k].w); mh = std::max(mh, plan.pieces[k].h); }
         s->timer.reset(s->stream); s->timer.mark("k_wsi_gather_patches");
-        launch_gather(s->stream, P, um[0]->bps, (const uint16_t *)s->wsi_planes.p, (const GatherPiece *)s->wsi_pieces.p + p0, np, mw, mh, d_out, pw, ph);
+        launch_gather(s->stream, kind, (const uint16_t *)s->wsi_planes.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());                                                         // (the next sub-batch follows on the stream; decode_plane_slab has waited for this one's bytes)
     }

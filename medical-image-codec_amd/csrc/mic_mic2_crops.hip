@@ -5,7 +5,7 @@
 // where a frame's stream lies (the caller's file, the blobs a reader pulled, a file in device memory).  The host plans
 // (mic2_plan_crops): which frames' streams must be entropy-decoded, and the (crop, frame) overlaps -- pieces.  The frames go through
 // the unit codec in sub-batches of mic2_frames_per_batch, and behind each sub-batch a kernel writes into the crop tensor:
-//   independent files: k_mic2_gather_crops copies the sub-batch's pieces out of the decoded frames;
+//   independent files: the shared gather (launch_gather, mic_gather.hip) copies the sub-batch's pieces out of the decoded frames;
 //   temporal files:    frame_i = frame_0 + sum_{j<=i} UnZigZag(res_j) (mod 2^16) is a running sum per pixel (mic_temporal.hip), and a
 //                      crop needs it under its own footprint only: k_mic2_accumulate_crops walks the sub-batch's residual symbols
 //                      with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0, the
@@ -19,28 +19,6 @@
 void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter);   // mic_wavelet.hip
 
 namespace {
-
-// frames: the sub-batch's decoded frames, [slot][npx] u16 of fw samples a row, slot = pc.k - k0; out: [crop][cd][ch][cw] u16.
-// grid = (pieces, row chunks); lanes along x (piece_lanes).  A row whose source and destination are both 4-byte aligned moves as
-// dwords (the odd sample behind them as u16), any other row as u16: with an odd frame or crop width every second row is such a row.
-__global__ void __launch_bounds__(256) k_mic2_gather_crops(const uint16_t *frames, int fw, size_t npx, const CropPiece *pieces, int k0,
-                                                         uint16_t *out, int cw, int ch, int cd) {
-    const CropPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const uint16_t *src = frames + (size_t)(pc.k - k0) * npx + (size_t)pc.sy * fw + pc.sx;
-    uint16_t *dst = out + (((size_t)pc.crop * cd + pc.dz) * ch + pc.dy) * cw + pc.dx;
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * fw);
-        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
-        if ((((size_t)s | (size_t)d) & 3) == 0) {
-            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
-            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
-            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
-            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = s[pc.w - 1];
-        } else
-            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = s[x];
-    }
-}
 
 // units 0 .. nb-1 hold frames f0 .. f0 + nb - 1 (unit 0 of the first sub-batch, f0 = 0, is the spatial frame in frame0; every other
 // unit a residual whose symbols lie in its sym slab).  fp = a crop's footprint: w x h pixels at (sx, sy) of every frame, the crop's
@@ -79,21 +57,6 @@ __global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *un
 }  // namespace
 
 namespace micapi {
-
-int patch_pointer(const mic_hip_session *s, void **d_out, size_t need) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, *d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }   // (unregistered memory)
-    if (at.type == hipMemoryTypeDevice) {
-        if (at.device != s->device) return MIC_ERR_ARGS;
-        hipDeviceptr_t b = nullptr; size_t sz = 0;
-        if (hipMemGetAddressRange(&b, &sz, (hipDeviceptr_t)*d_out) != hipSuccess) { (void)hipGetLastError(); return MIC_ERR_ARGS; }
-        if ((size_t)((char *)*d_out - (char *)b) + need > sz) return MIC_ERR_CAPACITY;     // (the allocation ends before out_cap does)
-    } else if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) {
-        if (at.devicePointer) *d_out = at.devicePointer;
-    } else return MIC_ERR_ARGS;
-    return MIC_OK;
-}
 
 // The plan of n crops of cw x ch x cd in a volume of width x height x nframes: the clipped box of each crop, one piece per frame of
 // it (sorted by frame, so a sub-batch of frames owns a contiguous range), one footprint per crop, and the frames to entropy-decode --
@@ -154,40 +117,35 @@ int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan,
     for (size_t k = 0; k < nfr; k++) len[k] = get_u32(m.table + 8 * (size_t)plan.frames[k] + 4);
     if ((rc = s->ensure(1, npx))) return rc;                                                // (the session's stream)
     HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volume; every byte is written
-    const std::vector<CropPiece> &list = m.temporal ? plan.prints : plan.pieces;
-    if (nfr) {
-        if ((rc = s->mic2_pieces.reserve(list.size() * sizeof(CropPiece)))) return rc;
-        HIP_TRY(hipMemcpyAsync(s->mic2_pieces.p, list.data(), list.size() * sizeof(CropPiece), hipMemcpyHostToDevice, s->stream));
-    }
-    const CropPiece *d_list = (const CropPiece *)s->mic2_pieces.p;
+    const size_t per = mic2_frames_per_batch(npx);
+    // the call's list, up once: temporal files their footprints as they are; independent files their pieces as the gather reads
+    // them -- plan frame k is decoded into slot k % per of its sub-batch's slab, the sub-batches starting at multiples of per
+    std::vector<GatherPiece> list(m.temporal ? 0 : plan.pieces.size());
     std::vector<size_t> first(nfr + 1, 0);                                                  // independent: the pieces of plan frame k
-    if (!m.temporal) {
-        for (const CropPiece &pc : plan.pieces) first[(size_t)pc.k + 1]++;
-        for (size_t k = 0; k < nfr; k++) first[k + 1] += first[k];
+    for (size_t q = 0; q < list.size(); q++) {
+        const CropPiece &pc = plan.pieces[q];
+        first[(size_t)pc.k + 1]++;
+        list[q] = GatherPiece{ (uint64_t)((size_t)pc.k % per) * npx + (uint64_t)pc.sy * (uint64_t)m.w + (uint64_t)pc.sx,
+                               (((uint64_t)pc.crop * (uint64_t)cd + (uint64_t)pc.dz) * (uint64_t)ch + (uint64_t)pc.dy) * (uint64_t)cw + (uint64_t)pc.dx,
+                               m.w, cw, pc.w, pc.h, 0, 0 };
+    }
+    for (size_t k = 0; k < nfr; k++) first[k + 1] += first[k];
+    const void *h_list = m.temporal ? (const void *)plan.prints.data() : (const void *)list.data();
+    const size_t list_bytes = m.temporal ? plan.prints.size() * sizeof(CropPiece) : list.size() * sizeof(GatherPiece);
+    if (nfr) {
+        if ((rc = s->pieces.reserve(list_bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->pieces.p, h_list, list_bytes, hipMemcpyHostToDevice, s->stream));
     }
     int mw = 1, mh = 1;
     for (const CropPiece &fp : plan.prints) { mw = std::max(mw, fp.w); mh = std::max(mh, fp.h); }
-    const unsigned gy = row_chunks(mw, mh);
-    const size_t per = mic2_frames_per_batch(npx);
     std::vector<int32_t> fst(nfr, MIC_OK);                                                  // status of plan frame k
     std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
     int fbad = INT_MAX, bad_code = MIC_OK;                                                  // temporal: the first failed frame
     uint64_t nslab = 0;
     for (size_t k0 = 0; k0 < nfr && fbad == INT_MAX; k0 += per) {
         const int nb = (int)std::min(per, nfr - k0);
-        // the sub-batch's streams back to back in the compressed-input buffer, neighbours in the source in one copy
-        begins.assign((size_t)nb, 0); ends.assign((size_t)nb, 0);
-        uint64_t total = 0;
-        for (int i = 0; i < nb; i++) { begins[(size_t)i] = total; total += len[k0 + (size_t)i]; ends[(size_t)i] = total; }
-        if ((rc = s->io_comp.reserve((size_t)total + 64))) return rc;
-        for (int i = 0; i < nb;) {
-            const uint8_t *p = src.blob(plan.frames[k0 + (size_t)i]);
-            size_t bytes = (size_t)len[k0 + (size_t)i];
-            int j = i + 1;
-            while (j < nb && src.blob(plan.frames[k0 + (size_t)j]) == p + bytes) bytes += (size_t)len[k0 + (size_t)j++];
-            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + begins[(size_t)i], p, bytes, src.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-            i = j;
-        }
+        if ((rc = pack_streams(s, nb, [&](int i) { return len[k0 + (size_t)i]; }, [&](int i) { return src.blob(plan.frames[k0 + (size_t)i]); },
+                               src.device, begins, ends))) return rc;
         nslab++;
         if (!m.temporal) {
             if ((rc = s->io_px.reserve(npx * 2 * (size_t)nb + 64))) return rc;
@@ -197,9 +155,7 @@ int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan,
             if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
             const size_t p0 = first[k0], np = first[k0 + (size_t)nb] - p0;
             s->timer.reset(s->stream); s->timer.mark("k_mic2_gather_crops");
-            for (size_t q = 0; q < np; q += 0x7FFFFFFF)
-                hipLaunchKernelGGL(k_mic2_gather_crops, dim3((unsigned)std::min<size_t>(np - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
-                                   (const uint16_t *)s->io_px.p, m.w, npx, d_list + p0 + q, (int)k0, (uint16_t *)d_out, cw, ch, cd);
+            launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
             s->timer.mark("end");
         } else {
             // (as mic2_temporal_decompress: the frames of a temporal plan are 0 .. nfr - 1, so plan index = frame)
@@ -225,9 +181,9 @@ int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan,
             if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
             for (int i = 0; i < nb && fbad == INT_MAX; i++) if (fst[k0 + (size_t)i] != MIC_OK) { fbad = (int)k0 + i; bad_code = fst[k0 + (size_t)i]; }
             s->timer.reset(s->stream); s->timer.mark("k_mic2_accumulate_crops");
-            for (size_t q = 0; q < list.size() && fbad > (int)k0; q += 0x7FFFFFFF)
-                hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)std::min<size_t>(list.size() - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
-                                   (const MicUnit *)s->units.p, nb, (int)k0, fbad, (const uint16_t *)s->io_px.p, m.w, d_list + q, (uint16_t *)d_out, cw, ch, cd);
+            for (size_t q = 0; q < plan.prints.size() && fbad > (int)k0; q += 0x7FFFFFFF)
+                hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)std::min<size_t>(plan.prints.size() - q, 0x7FFFFFFF), row_chunks(mw, mh)), dim3(256), 0, s->stream,
+                                   (const MicUnit *)s->units.p, nb, (int)k0, fbad, (const uint16_t *)s->io_px.p, m.w, (const CropPiece *)s->pieces.p + q, (uint16_t *)d_out, cw, ch, cd);
             s->timer.mark("end");
         }
         HIP_TRY(hipGetLastError());
@@ -265,12 +221,8 @@ int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(co
     CropPlan plan;
     if ((rc = mic2_plan_crops(m.w, m.h, m.n, m.temporal, xyz, n, cw, ch, cd, plan))) return rc;
     DefaultLease lease;
-    if (!s) { if ((rc = lease.acquire())) return rc; s = cur_default(); }
-    else if ((rc = s->activate())) return rc;
     // the pointer and the table are judged before a source is asked for a byte, and before anything is launched
-    rc = patch_pointer(s, &d_out, need);
-    if (rc == MIC_ERR_CAPACITY || ((size_t)d_out & 1)) rc = MIC_ERR_ARGS;                   // (out_cap held the tensor: it is the allocation that does not)
-    if (rc) return rc;
+    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
     for (uint32_t f : plan.frames) {                                                        // as mic_hip_mic2_decompress, multiframe.go:137-139
         const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)f), bl = get_u32(m.table + 8 * (size_t)f + 4);
         if (bl == 0 || off + bl > m.file_len) return MIC_ERR_CORRUPT;

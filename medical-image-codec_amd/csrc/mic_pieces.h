@@ -1,4 +1,5 @@
-// mic_pieces.h -- helpers shared by the gather kernels (MIC3 patches, MIC2 crops, strip-file crops) and the MIC2 temporal pipeline.
+// mic_pieces.h -- what the readers of many rectangles per call share (MIC3 patches, MIC2 crops, strip-file crops): the piece record,
+// the lane layout of a piece, the gather launcher (mic_gather.hip); and the zigzag of the MIC2 temporal pipeline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -21,3 +22,22 @@ inline unsigned row_chunks(int w, int h) {
     const int passes = (h + 256 / lw - 1) / (256 / lw) * ((w + 63) / 64);
     return (unsigned)std::min(16, std::max(1, passes / 16));
 }
+
+// A piece, one overlap of a rectangle of the call with a decoded unit: w x h samples from `src` samples into the sub-batch's slab
+// (rows sstride apart) to `dst` samples into the output tensor (pixels for the RGB tensor; rows dstride apart).  pstride: how far
+// apart the unit's planes are, which only the RGB kernel reads.  The host plans and multiplies out both places (64 bits: crop x
+// depth x rows x columns passes 2^31); the kernels multiply nothing but y * stride.
+struct GatherPiece { uint64_t src, dst; int32_t sstride, dstride, w, h, pstride, pad; };
+
+struct mic_hip_session;
+namespace micapi {
+// what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), or three YCoCg-R planes' RGB bytes
+enum GatherKind { kGatherU16, kGatherU8, kGatherRGB };
+// np pieces (device) of a slab -> out, behind what `stream` holds; mw x mh: the largest of them.  The one place that picks the
+// kernel, cuts the rows of tall pieces over grid y (row_chunks) and the pieces over launches of at most 2^31 - 1.
+void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out);
+// d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
+// pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
+// *d_out becomes the address the device uses.
+int patch_pointer(const mic_hip_session *s, void **d_out, size_t need);
+}  // namespace micapi

@@ -173,9 +173,8 @@ struct mic_hip_session {
     DevBuf wv_a, wv_b;                     // WaveletV2 coefficient planes (int32, two per frame of the batch)
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
-    DevBuf mic2_pieces;                    // MIC2 crops: a call's piece / footprint list (mic_mic2_crops.hip)
-    DevBuf strip_pieces;                   // strip-file crops: a call's piece list (mic_strip_crops.hip)
-    DevBuf wsi_pieces, wsi_fills;          // MIC3 patches: a call's piece list; MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
+    DevBuf pieces;                         // patch and crop calls: the call's piece list (GatherPiece, mic_pieces.h; MIC2 temporal: its footprints)
+    DevBuf wsi_fills;                      // MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
     std::vector<uint8_t> wsi_host_bytes;   // MIC3 patches from blobs: a sub-batch's stream bytes on their way up; kept, so that a loop of calls touches the same pages
     DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
     DevBuf rgb_payload, rgb_payload2;      // ... and its assembled blobs: two halves, one goes down while the other is written
@@ -333,13 +332,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &mic2_pieces, &strip_pieces, &wsi_pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -387,10 +386,16 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
 size_t mic2_frames_per_batch(size_t npx);
 // residual units r0 .. n-1 must expand to exactly npx symbols (k_tmp_check), behind their chain on `stream`
 void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream);
-// d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
-// pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
-// *d_out becomes the address the device uses.  (mic_mic2_crops.hip)
-int patch_pointer(const mic_hip_session *s, void **d_out, size_t need);
+// What the patch and crop readers share beside the gather (mic_gather.hip; patch_pointer and the kernels' launcher: mic_pieces.h).
+// A sub-batch's nb streams, len(i) bytes at src(i) -- host memory, or (device) the session's device --, back to back into s->io_comp
+// (reserved here, with the 64 bytes the decode kernels may read past a stream's end): neighbours in the source go in one copy.
+// begins[i] .. ends[i]: stream i in the buffer.
+int pack_streams(mic_hip_session *s, int nb, const std::function<uint64_t(int)> &len, const std::function<const uint8_t *(int)> &src, bool device,
+                 std::vector<uint64_t> &begins, std::vector<uint64_t> &ends);
+// What a crop door does once it has a plan: the session -- *s, made current, or when NULL one leased here --, then d_out judged for a
+// u16 tensor of `need` bytes (patch_pointer; an allocation that ends before the tensor does and an odd address are MIC_ERR_ARGS:
+// out_cap held the tensor).
+int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need);
 // MIC2 crops (mic_mic2_crops.hip).  A piece is one (crop, frame) overlap: w x h samples from (sx, sy) of frame `frame` to (dx, dy) of
 // slice dz of crop `crop`, k = the frame's place in the plan's frame list.  The temporal kernel takes one record per crop instead,
 // its footprint: frame = max(z, 0), the crop's first frame inside the volume, dz = that frame's slice, k = its last frame inside it.

@@ -5,36 +5,12 @@
 // address its streams are copied from (the caller's file, a file in device memory).  The host plans (strips_plan_crops): a strip is a
 // unit of its own, so a crop needs the strips it overlaps and no others -- the plan is those (file, strip) units, each once, and the
 // (crop, strip) overlaps, pieces.  The units go through the unit codec in sub-batches under the workspace ceiling, each into a slab
-// of decoded strips, and behind each sub-batch k_strips_gather_crops copies its pieces out of the slab into the crop tensor.
+// of decoded strips, and behind each sub-batch the shared gather (launch_gather, mic_gather.hip) copies its pieces out of the slab
+// into the crop tensor.
 #include "mic_session.h"
 #include "mic_pieces.h"
 
 namespace {
-
-// One (crop, strip) overlap: w x h samples from (sx, sy) of a decoded strip of fw samples a row, which starts `src` samples into its
-// sub-batch's slab, to (dx, dy) of crop `crop`.
-struct StripPiece { uint64_t src; int32_t crop, fw, sx, sy, dx, dy, w, h; };
-
-// slab: a sub-batch's decoded strips; out: [crop][ch][cw] u16.  grid = (pieces, row chunks); lanes along x (piece_lanes).  A row whose
-// source and destination are both 4-byte aligned moves as dwords (the odd sample behind them as u16), any other row as u16: with an
-// odd image or crop width every second row is such a row (as k_mic2_gather_crops).
-__global__ void __launch_bounds__(256) k_strips_gather_crops(const uint16_t *slab, const StripPiece *pieces, uint16_t *out, int cw, int ch) {
-    const StripPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const uint16_t *src = slab + pc.src + (size_t)pc.sy * pc.fw + pc.sx;
-    uint16_t *dst = out + ((size_t)pc.crop * ch + pc.dy) * cw + pc.dx;
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const mic_gp<const uint16_t> s = mic_g(src + (size_t)y * pc.fw);
-        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
-        if ((((size_t)s | (size_t)d) & 3) == 0) {
-            const mic_gp<const uint32_t> s2 = (mic_gp<const uint32_t>)s;
-            const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
-            for (int x = ln.col; x < (pc.w >> 1); x += ln.lw) d2[x] = s2[x];
-            if ((pc.w & 1) && ln.col == 0) d[pc.w - 1] = s[pc.w - 1];
-        } else
-            for (int x = ln.col; x < pc.w; x += ln.lw) d[x] = s[x];
-    }
-}
 
 // a file of the call: where its header and table are read (host) and what they said
 struct StripFile {
@@ -172,52 +148,40 @@ int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *
         slab_max = std::max(slab_max, off); comp_max = std::max(comp_max, comp);
     }
     std::vector<size_t> first(nu + 1, 0);                                                   // the pieces of unit u
-    std::vector<StripPiece> list(plan.pieces.size());
+    std::vector<GatherPiece> list(plan.pieces.size());                                      // a strip starts slab_off samples into its sub-batch's slab
     int mw = 1, mh = 1;
     for (size_t q = 0; q < plan.pieces.size(); q++) {
         const PlannedPiece &p = plan.pieces[q];
         first[(size_t)p.unit + 1]++;
-        list[q] = StripPiece{ slab_off[p.unit], p.crop, plan.files[plan.units[p.unit].file].w, p.sx, p.sy, p.dx, p.dy, p.w, p.h };
+        const int fw = plan.files[plan.units[p.unit].file].w;
+        list[q] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)fw + (uint64_t)p.sx,
+                               ((uint64_t)p.crop * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx, fw, cw, p.w, p.h, 0, 0 };
         mw = std::max(mw, p.w); mh = std::max(mh, p.h);
     }
     for (size_t u = 0; u < nu; u++) first[u + 1] += first[u];
     if (nu) {
-        if ((rc = s->strip_pieces.reserve(list.size() * sizeof(StripPiece)))) return rc;
-        if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (+ what the decode kernels may read past a stream's end)
+        if ((rc = s->pieces.reserve(list.size() * sizeof(GatherPiece)))) return rc;
+        if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
         if ((rc = s->io_px.reserve(slab_max * 2 + 64))) return rc;
-        HIP_TRY(hipMemcpyAsync(s->strip_pieces.p, list.data(), list.size() * sizeof(StripPiece), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
     }
-    const StripPiece *d_list = (const StripPiece *)s->strip_pieces.p;
-    const unsigned gy = row_chunks(mw, mh);
     std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
     std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
     for (size_t b = 0; b + 1 < cuts.size(); b++) {
         const size_t u0 = cuts[b];
         const int nb = (int)(cuts[b + 1] - u0);
-        // the sub-batch's streams back to back in the compressed-input buffer, neighbours in the source in one copy
-        begins.assign((size_t)nb, 0); ends.assign((size_t)nb, 0); units.resize((size_t)nb);
-        uint64_t total = 0;
+        if ((rc = pack_streams(s, nb, [&](int i) { return (uint64_t)entry(u0 + (size_t)i).len; },
+                               [&](int i) { return base[plan.units[u0 + (size_t)i].file] + entry(u0 + (size_t)i).start; }, device, begins, ends))) return rc;
+        units.resize((size_t)nb);
         for (int i = 0; i < nb; i++) {
             const StripEntry &e = entry(u0 + (size_t)i);
-            begins[(size_t)i] = total; total += e.len; ends[(size_t)i] = total;
             units[(size_t)i] = mic_hip_unit{ slab_off[u0 + (size_t)i], plan.files[plan.units[u0 + (size_t)i].file].w, (int32_t)(e.y1 - e.y0), 0, e.flags };
-        }
-        for (int i = 0; i < nb;) {
-            const uint32_t fi = plan.units[u0 + (size_t)i].file;
-            const size_t start = entry(u0 + (size_t)i).start;
-            size_t bytes = entry(u0 + (size_t)i).len;
-            int j = i + 1;
-            while (j < nb && plan.units[u0 + (size_t)j].file == fi && entry(u0 + (size_t)j).start == start + bytes) bytes += entry(u0 + (size_t)j++).len;
-            HIP_TRY(hipMemcpyAsync((uint8_t *)s->io_comp.p + begins[(size_t)i], base[fi] + start, bytes, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-            i = j;
         }
         if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
         if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
         const size_t p0 = first[u0], np = first[u0 + (size_t)nb] - p0;
         s->timer.reset(s->stream); s->timer.mark("k_strips_gather_crops");
-        for (size_t q = 0; q < np; q += 0x7FFFFFFF)
-            hipLaunchKernelGGL(k_strips_gather_crops, dim3((unsigned)std::min<size_t>(np - q, 0x7FFFFFFF), gy), dim3(256), 0, s->stream,
-                               (const uint16_t *)s->io_px.p, d_list + p0 + q, (uint16_t *)d_out, cw, ch);
+        launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());
     }
@@ -259,11 +223,7 @@ int strips_call(mic_hip_session *s, StripPlan &plan, const uint8_t *const *base,
     if (!d_out) return MIC_ERR_ARGS;
     if (device) for (const StripUnit &u : plan.units) if (!base[u.file]) return MIC_ERR_ARGS;    // (a file whose strips are needed is not there)
     DefaultLease lease;
-    if (!s) { if ((rc = lease.acquire())) return rc; s = cur_default(); }
-    else if ((rc = s->activate())) return rc;
-    rc = patch_pointer(s, &d_out, need);                                                    // judged before anything is launched
-    if (rc == MIC_ERR_CAPACITY || ((size_t)d_out & 1)) rc = MIC_ERR_ARGS;                   // (out_cap held the tensor: it is the allocation that does not)
-    if (rc) return rc;
+    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
     if ((rc = strips_read_crops(s, plan, base, device, n, cw, ch, d_out, need, status, failed_strip, stats))) return rc;
     file_codes(plan, xyf, n, status);
     return MIC_OK;

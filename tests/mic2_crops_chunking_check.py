@@ -1,6 +1,7 @@
 """Run by tests/test_gpu_mic2_crops.py::test_sub_batch_seams_under_a_small_workspace in a child process with MIC_HIP_WS_BUDGET_MB set
 small, so that the MIC2 crop calls cut the frames into sub-batches of three: the temporal sum's carry then crosses the seams inside
-the crop tensor, and an independent file's pieces are gathered slab by slab.  Every crop must equal the padded source volume."""
+the crop tensor, and an independent file's pieces are gathered slab by slab, each from its frame's slot in the slab.  Every crop must
+equal the padded source volume."""
 import importlib, os, sys
 import numpy as np
 import torch
@@ -36,6 +37,22 @@ for temporal in (True, False):
                 assert np.array_equal(got[i], want[i]), (temporal, k, (cw, ch, cd), xyz[i])
             assert (st == 0).all() and stats["frames_decoded"] == frames.size and stats["pieces"] == pieces, (temporal, k, stats)
             assert stats["slabs"] == -(-frames.size // 3) >= 3, (temporal, k, stats)     # three frames a sub-batch
+    # the slot of a frame in its sub-batch's slab, at the smallest seam: every frame is decoded, so plan index = frame and the
+    # sub-batches are frames 0-2, 3-5, 6-8, 9-10.  One crop lies wholly inside the last sub-batch, one spans the first seam; a frame
+    # is its neighbour rolled by 3 columns, so a wrong slot shows as a wrong frame
+    cw, ch, cd = 48, 40, 2
+    xyz = [(3 * z, z, z) for z in range(0, n - 1, 2)] + [(30, 10, 9), (60, 20, 2)]
+    want = V.expected(vol, xyz, cw, ch, cd)
+    assert not np.array_equal(want[-2][0], want[-2][1]) and not np.array_equal(want[-1][0], want[-1][1])
+    frames, pieces = mic.mic2_crop_plan(w, h, n, temporal, xyz, cw, ch, cd)
+    assert frames.tolist() == list(range(n))
+    for k, door in enumerate(doors):
+        t = torch.full((len(xyz), cd, ch, cw, 2), 0xA5, dtype=torch.uint8, device="cuda")
+        st, stats = door(xyz, cw, ch, cd, t.data_ptr(), t.numel())
+        got = t.cpu().numpy().view("<u2")[..., 0]
+        for i in range(len(xyz)):
+            assert np.array_equal(got[i], want[i]), (temporal, k, xyz[i])
+        assert (st == 0).all() and stats["pieces"] == pieces and stats["slabs"] == 4, (temporal, k, stats)
     # a crop deep in the stack alone: a temporal file still sums from frame 0, an independent one decodes its own frames only
     t = torch.full((1, 2, 40, 48, 2), 0xA5, dtype=torch.uint8, device="cuda")
     st, stats = mic.mic2_read_crops(data, [(30, 10, 8)], 48, 40, 2, t.data_ptr(), t.numel())

@@ -238,6 +238,16 @@ def test_argument_errors_come_back_before_any_launch(mic, volumes):
         doors.close()
 
 
+def test_the_gather_kernel_is_timed_under_its_name(mic, volumes):
+    doors = _Doors(mic, volumes["xr12"]["files"][False])
+    try:
+        doors.sess.set_timing(True)
+        _read(doors.session, [(0, 0, 0), (5, 5, 3)], 48, 40, 3)
+        assert "k_mic2_gather_crops" in dict(doors.sess.last_timings())
+    finally:
+        doors.close()
+
+
 def test_sub_batch_seams_under_a_small_workspace():
     """tests/mic2_crops_chunking_check.py in a fresh process with a 7 MiB workspace ceiling.  A sub-batch holds
     budget / (unit_ws_bytes(npx) + 2 npx) frames (mic2_frames_per_batch); for 150 x 70 = 10500 pixels the tier-2 slabs of a unit are

@@ -207,6 +207,31 @@ def test_the_gather_kernel_is_timed_under_its_name(mic, files):
         doors.close()
 
 
+def test_a_tall_piece_is_cut_over_grid_y(mic, synth, gpu_ready):
+    """A piece of 128 x 72: lanes are 64 wide, a block pass takes 4 rows, so the piece is 2 column passes x 18 row passes = 36 passes
+    and row_chunks cuts it over grid y = 2 -- which no piece of the shared files reaches.  One PICS file of one strip, 130 x 72 at 12
+    bits (file A's recipe).  The crop at (1, -4) starts one sample into every strip row: 130 samples a row are a multiple of four
+    bytes, so each of its rows is 2-byte-aligned only and moves as u16; the rows of the crop at (0, 0) move as dwords."""
+    w, h, cw, ch = 130, 72, 128, 80
+    x, y = np.arange(w)[None, :], np.arange(h)[:, None]
+    img = np.clip(np.rint(900 + 5 * x + 11 * y + 2.0 * synth.approx_gauss(h * w, 11).reshape(h, w)), 0, 65535).astype(np.uint16)
+    data = bytes(mic.compress_parallel_strips(img, w, h, 4095, 1, 2))
+    assert F.StripFile(data).n == 1 and np.array_equal(np.asarray(mic.decompress_parallel_strips(data)[0]).reshape(h, w), img)
+    tall = [("tall", img, data)]
+    xyf = [(1, -4, 0), (0, 0, 0)]
+    want = F.expected(tall, xyf, cw, ch)
+    assert np.array_equal(want[0, 4:76], img[:, 1:129]) and not want[0, :4].any() and not want[0, 76:].any()
+    doors = _Doors(mic, [data])
+    try:
+        for door, call in doors.all:
+            got, st, bad, stats = _read(call, xyf, cw, ch)
+            assert np.array_equal(got, want), door
+            assert (st == mic.MIC_OK).all() and (bad == -1).all(), (door, st, bad)
+            assert stats == dict(strips_decoded=1, strips_total=1, pieces=2, slabs=1), (door, stats)
+    finally:
+        doors.close()
+
+
 def test_sub_batch_seams_under_a_small_workspace():
     """tests/strip_crops_chunking_check.py in a fresh process with a 5 MiB workspace ceiling.  A sub-batch takes units while their
     number times (unit_ws_bytes(px) + 2 px), px the largest of them, stays under the ceiling (next_strip_cut).  The tier-2 slabs of a

@@ -179,6 +179,20 @@ def test_three_front_doors_give_the_same_bytes(mic, slides, fmt):
         sess.close()
 
 
+def test_the_gather_kernel_is_timed_under_its_name(mic, slides):
+    import torch
+    sl = slides["grey16"]
+    sess = mic.Session(64, S.TILE * S.TILE)
+    try:
+        d_px = torch.from_numpy(np.ascontiguousarray(sl["img"]).view(np.uint8).reshape(-1).copy()).cuda()
+        sess.wsi_encode(d_px.data_ptr(), S.W, S.H, tile_w=S.TILE, tile_h=S.TILE, levels=S.LEVELS, **S.fmt_args("grey16"))
+        sess.set_timing(True)
+        _read(lambda a, w, h, d, cap: sess.wsi_read_patches(0, a, w, h, d, cap), [(0, 0), (40, 40)], 48, 40, sl["levels"][0])
+        assert "k_wsi_gather_patches" in dict(sess.last_timings())
+    finally:
+        sess.close()
+
+
 def test_slabs_under_a_small_workspace(mic, slides):
     """A child process with an 8 MB workspace ceiling: a sub-batch of the unit codec then holds six 64 x 64 RGB tiles (about 0.42 MB
     of tier-1 slabs per plane), so the twelve tiles of level 0 take two slabs.  The bytes must be those of the unconstrained call,
