@@ -155,7 +155,7 @@ typedef struct mic_hip_dec_job {
  * upload, kernels and download of neighbouring sub-batches overlap -- and concurrent callers run on different sessions of a
  * small pool (MIC_HIP_POOL sessions, default 3), as the reference's C codec runs concurrent goroutines (ojph/mic_parallel.h:47-48).
  * Environment, read once: MIC_HIP_WS_BUDGET_MB (device memory a default session may grow to), MIC_HIP_PIPELINE_PARTS (force the
- * number of sub-batches), MIC_HIP_TRACE=1 (the pipeline's stages with wall times on stderr). */
+ * number of sub-batches), MIC_HIP_TRACE=1 (on stderr: every call's parts, the decode pipeline's stages with wall times, the devices' shards). */
 int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs);
 int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs);
 

@@ -4,13 +4,14 @@
 // (parallelstrips.go:77-93, multiframecompress.go:201-203).  Here a call
 //   * leases a session of the default pool (mic_api.hip: concurrent callers run on different sessions),
 //   * cuts its units into sub-batches and runs them as a three-stage pipeline -- sub-batch k + 1 comes up over PCIe while k is
-//     coded and k - 1 goes down -- with two halves of every staging buffer,
+//     coded and k - 1 goes down -- with two halves of every staging buffer (run_staged, mic_staged.h: the one place that does),
 //   * moves bytes through the transfer engine below: a caller's buffer is ordinary pageable memory (a Go slice), which the
 //     runtime can only DMA through its own small bounce buffer; a handful of worker threads copy 4 MiB chunks into pinned slots
 //     and DMA them on their own streams, so the link stays busy.  Memory from mic_hip_host_alloc (or any registered memory) is
 //     pinned already and is DMA-ed in place.
 // There is no CPU codec here: the host copies bytes and writes container headers.
 #include "mic_session.h"
+#include "mic_staged.h"
 #include <chrono>
 
 #include <atomic>
@@ -23,23 +24,6 @@ namespace {
 constexpr size_t kChunk = (size_t)4 << 20;        // bytes per pinned slot
 constexpr size_t kDirectChunk = (size_t)64 << 20; // pinned user memory: pieces this large, spread over the workers' streams
 constexpr size_t kInline = (size_t)128 << 10;     // pageable transfers up to this size: a plain hipMemcpy on the calling thread
-
-struct IoReq {                                    // a set of transfers the caller waits for together
-    std::atomic<int> pending{0};
-    std::atomic<int> error{0};
-    std::mutex mu; std::condition_variable cv;
-    void add(int n) { std::lock_guard<std::mutex> lk(mu); pending.fetch_add(n); }
-    void done(bool ok) {                              // (the count goes down under the lock: the waiter may free the request right after)
-        std::lock_guard<std::mutex> lk(mu);
-        if (!ok) error.store(1);
-        if (pending.fetch_sub(1) == 1) cv.notify_all();
-    }
-    int wait() {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return pending.load() == 0; });
-        return error.load() ? MIC_ERR_DEVICE : MIC_OK;
-    }
-};
 
 struct IoChunk { IoReq *req; int device; void *dev; void *host; size_t bytes; bool to_device; bool direct; };
 
@@ -78,9 +62,9 @@ private:
         cv_.notify_all();
         for (auto &t : th_) if (t.joinable()) t.join();
     }
-    static void retire(Slot &s) {
+    static void retire(Slot &s, bool ok = true) {
         if (!s.busy) return;
-        const bool ok = hipEventSynchronize(s.ev) == hipSuccess;
+        ok = ok && hipEventSynchronize(s.ev) == hipSuccess;
         if (ok && s.host_dst) memcpy(s.host_dst, s.pin, s.bytes);
         s.busy = false;
         s.req->done(ok);
@@ -89,8 +73,10 @@ private:
     // the worker takes more work: waiting for the slot's next use held a request's last chunks back for two more submissions, and
     // with callers on several devices for as long as the other device's request kept the worker fed
     static void retire_finished(Slot &s) {
-        if (s.busy && hipEventQuery(s.ev) == hipSuccess) retire(s);
-        else (void)hipGetLastError();                  // (hipErrorNotReady is not an error to keep)
+        if (!s.busy) return;
+        const hipError_t e = hipEventQuery(s.ev);
+        if (e == hipErrorNotReady) (void)hipGetLastError();   // (not an error to keep)
+        else retire(s, e == hipSuccess);                      // (any other failure is the slot's transfer's)
     }
     void run(int first) {
         std::vector<PerDev> devs;
@@ -251,21 +237,22 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
     const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
     if (u0 == n) return MIC_OK;
     const size_t target = pipeline_target((size_t)(n - u0), true);
-    struct Sub { int i0, i1; IoReq up, down; std::vector<mic_hip_unit> units; size_t px = 0; };
-    std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = u0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, n, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
-    DevBuf *in[2] = { &s->io_px, &s->io_px2 };
-    int rc = MIC_OK;
-    auto upload = [&](Sub &sb, int half) -> int {
-        sb.units.resize((size_t)(sb.i1 - sb.i0));
-        size_t off = 0;
-        for (int i = sb.i0; i < sb.i1; i++) {
+    struct Sub { int i0, i1; std::vector<mic_hip_unit> units; size_t px; };
+    const std::vector<Sub> subs = staged_cut<Sub>(u0, n, [&](int i0) { return next_cut(U, i0, n, target); }, [&](int i0, int i1) {
+        Sub sb{ i0, i1, std::vector<mic_hip_unit>((size_t)(i1 - i0)), 0 };
+        for (int i = i0; i < i1; i++) {
             const EncUnit &u = U[(size_t)i];
-            sb.units[(size_t)(i - sb.i0)] = mic_hip_unit{ off, u.w, u.h, u.maxv, u.nstates };
-            off += (size_t)u.w * (size_t)u.h;
+            sb.units[(size_t)(i - i0)] = mic_hip_unit{ sb.px, u.w, u.h, u.maxv, u.nstates };
+            sb.px += (size_t)u.w * (size_t)u.h;
         }
-        sb.px = off;
-        int r = in[half]->reserve(off * 2 + 64);
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("units encode", k, subs.size(), "units", subs[k].i0, subs[k].i1, subs[k].px);
+    DevBuf *in[2] = { &s->io_px, &s->io_px2 };
+    IoReq *prev = nullptr;                                // the download of the part before: keep_packed waits for it
+    return run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const Sub &sb = subs[k];
+        int r = in[half]->reserve(sb.px * 2 + 64);
         if (r) return r;
         // one transfer per run of units that are neighbours in one host buffer
         size_t doff = 0;
@@ -275,24 +262,20 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
             while (j < sb.i1 && U[(size_t)j].group == U[(size_t)i].group && U[(size_t)j].px_off == U[(size_t)i].px_off + run) {
                 run += (size_t)U[(size_t)j].w * (size_t)U[(size_t)j].h; j++;
             }
-            if ((r = io_submit(sb.up, s->device, (uint16_t *)in[half]->p + doff, g.h_px + U[(size_t)i].px_off, run * 2, true))) return r;
+            if ((r = io_submit(up, s->device, (uint16_t *)in[half]->p + doff, g.h_px + U[(size_t)i].px_off, run * 2, true))) return r;
             doff += run; i = j;
         }
         return MIC_OK;
-    };
-    if ((rc = upload(*subs[0], 0))) { (void)subs[0]->up.wait(); return rc; }
-    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
-        Sub &sb = *subs[k];
-        const int half = (int)(k & 1);
-        rc = sb.up.wait();
-        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        const Sub &sb = subs[k];
         const int nb = sb.i1 - sb.i0;
         std::vector<uint64_t> offs((size_t)nb + 1); std::vector<int32_t> st((size_t)nb), ns((size_t)nb);
         const uint8_t *d_blobs = nullptr;
-        if (rc == MIC_OK) rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, sb.units.data(), nb);
+        int rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, sb.units.data(), nb);
         if (rc == MIC_OK) rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data());
-        if (rc == MIC_OK) rc = keep_packed(s, k ? &subs[k - 1]->down : nullptr);
-        if (rc != MIC_OK) break;
+        if (rc == MIC_OK) rc = keep_packed(s, prev);
+        if (rc != MIC_OK) return rc;
+        prev = &down;
         for (int i = sb.i0; i < sb.i1;) {                  // per group: its streams of this sub-batch, one transfer
             EncGroup &g = G[(size_t)U[(size_t)i].group];
             int j = i;
@@ -306,15 +289,14 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
                 bytes += u.len;
             }
             if (g.status == MIC_OK) {
-                rc = g.dst.append(sb.down, s->device, d_blobs + offs[(size_t)(i - sb.i0)], bytes);
+                rc = g.dst.append(down, s->device, d_blobs + offs[(size_t)(i - sb.i0)], bytes);
                 if (g.dst.cap_fail) g.status = MIC_ERR_CAPACITY;
-                if (rc) break;
+                if (rc) return rc;
             }
             i = j;
         }
-    }
-    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
-    return rc;
+        return MIC_OK;
+    });
 }
 
 int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecUnit> &U, int g0, int g1) {
@@ -322,16 +304,28 @@ int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecU
     const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
     if (u0 == n) return MIC_OK;
     const size_t target = pipeline_target((size_t)(n - u0), false);
-    struct Sub { int i0, i1; IoReq up, down; std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; size_t px = 0; };
-    std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = u0; i0 < n;) { auto sb = std::make_unique<Sub>(); sb->i0 = i0; sb->i1 = next_cut(U, i0, n, target); i0 = sb->i1; subs.push_back(std::move(sb)); }
+    struct Sub { int i0, i1; std::vector<mic_hip_unit> units; std::vector<uint64_t> begins, ends; size_t px; };
+    std::vector<Sub> subs = staged_cut<Sub>(u0, n, [&](int i0) { return next_cut(U, i0, n, target); }, [&](int i0, int i1) {
+        const size_t nb = (size_t)(i1 - i0);
+        Sub sb{ i0, i1, std::vector<mic_hip_unit>(nb), std::vector<uint64_t>(nb), std::vector<uint64_t>(nb), 0 };
+        for (int i = i0; i < i1; i++) {
+            const DecUnit &u = U[(size_t)i];
+            sb.units[(size_t)(i - i0)] = mic_hip_unit{ sb.px, u.w, u.h, 0, u.flags };
+            sb.px += (size_t)u.w * (size_t)u.h;
+        }
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("units decode", k, subs.size(), "units", subs[k].i0, subs[k].i1, subs[k].px);
     DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
-    int rc = MIC_OK;
-    auto upload = [&](Sub &sb, int half) -> int {
-        const int nb = sb.i1 - sb.i0;
-        sb.units.resize((size_t)nb); sb.begins.resize((size_t)nb); sb.ends.resize((size_t)nb);
+    // MIC_HIP_TRACE=1: the stages of the pipeline with their wall times on stderr (tools/: where a call's time goes)
+    const auto t0 = std::chrono::steady_clock::now();
+    auto mark = [&](const char *what, size_t k) {
+        if (io_trace()) fprintf(stderr, "[mic_hip decode] %7.2f ms  %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what, k);
+    };
+    const int rc = run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        Sub &sb = subs[k];
         // device layout: every run of streams that are neighbours in one host buffer keeps its shape, runs start 16-byte aligned
-        size_t coff = 0, poff = 0;
+        size_t coff = 0;
         struct Run { size_t dev, host_off, len; const uint8_t *base; };
         std::vector<Run> runs;
         for (int i = sb.i0; i < sb.i1;) {
@@ -348,40 +342,23 @@ int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecU
             coff += align_up(end - start, 16);
             i = j;
         }
-        for (int i = sb.i0; i < sb.i1; i++) {
-            const DecUnit &u = U[(size_t)i];
-            sb.units[(size_t)(i - sb.i0)] = mic_hip_unit{ poff, u.w, u.h, 0, u.flags };
-            poff += (size_t)u.w * (size_t)u.h;
-        }
-        sb.px = poff;
         int r = in[half]->reserve(coff + 64);
         if (r) return r;
         for (const Run &q : runs)
-            if ((r = io_submit(sb.up, s->device, (uint8_t *)in[half]->p + q.dev, q.base + q.host_off, q.len, true))) return r;
+            if ((r = io_submit(up, s->device, (uint8_t *)in[half]->p + q.dev, q.base + q.host_off, q.len, true))) return r;
         return MIC_OK;
-    };
-    // MIC_HIP_TRACE=1: the stages of the pipeline with their wall times on stderr (tools/: where a call's time goes)
-    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what, size_t k) {
-        if (trace) fprintf(stderr, "[mic_hip decode] %7.2f ms  %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what, k);
-    };
-    if ((rc = upload(*subs[0], 0))) { (void)subs[0]->up.wait(); return rc; }
-    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
-        Sub &sb = *subs[k];
-        const int half = (int)(k & 1);
-        rc = sb.up.wait();
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        const Sub &sb = subs[k];
+        // (this sub-batch decodes into the pixel half that sub-batch k - 2 was downloaded from)
         mark("streams on the device", k);
-        // this sub-batch decodes into the pixel half that sub-batch k - 2 is (was) being downloaded from
-        if (k >= 2) { const int r2 = subs[k - 2]->down.wait(); if (rc == MIC_OK) rc = r2; mark("pixels of sub-batch on the host", k - 2); }
-        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);
-        if (rc == MIC_OK) rc = outb[half]->reserve(sb.px * 2 + 64);
+        if (k >= 2) mark("pixels of sub-batch on the host", k - 2);
+        int rc = outb[half]->reserve(sb.px * 2 + 64);
         const int nb = sb.i1 - sb.i0;
         std::vector<int32_t> st((size_t)nb);
         if (rc == MIC_OK) rc = session_decode_enqueue_spans(s, (const uint8_t *)in[half]->p, sb.begins.data(), sb.ends.data(), sb.units.data(), nb, (uint16_t *)outb[half]->p);
         if (rc == MIC_OK) rc = session_decode_finish(s, st.data());
         mark("decoded", k);
-        if (rc != MIC_OK) break;
+        if (rc != MIC_OK) return rc;
         for (int i = sb.i0; i < sb.i1;) {
             DecGroup &g = G[(size_t)U[(size_t)i].group];
             int j = i;
@@ -394,16 +371,14 @@ int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecU
                 for (int q = i; q < j;) {
                     int e = q; size_t run = 0;
                     while (e < j && U[(size_t)e].px_off == U[(size_t)q].px_off + run) { run += (size_t)U[(size_t)e].w * (size_t)U[(size_t)e].h; e++; }
-                    rc = io_submit(sb.down, s->device, (uint16_t *)outb[half]->p + sb.units[(size_t)(q - sb.i0)].px_offset, g.h_px + U[(size_t)q].px_off, run * 2, false);
-                    if (rc) break;
+                    if ((rc = io_submit(down, s->device, (uint16_t *)outb[half]->p + sb.units[(size_t)(q - sb.i0)].px_offset, g.h_px + U[(size_t)q].px_off, run * 2, false))) return rc;
                     q = e;
                 }
-                if (rc) break;
             }
             i = j;
         }
-    }
-    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
+        return MIC_OK;
+    });
     mark("all pixels on the host", subs.size());
     return rc;
 }
@@ -464,7 +439,7 @@ struct PicaTimingScope {
 #endif
 
 struct PicaPart {
-    int g0 = 0, g1 = 0; IoReq up;
+    int g0 = 0, g1 = 0;
     std::vector<MicPicaImage> tab; uint32_t rows = 0, nstarts = 0; size_t px = 0;
 };
 
@@ -487,6 +462,9 @@ int pica_bounds_enqueue(mic_hip_session *s, PicaPart &p, const uint16_t *d_px, i
 }
 inline const int32_t *pica_starts_of(const mic_hip_session *s, const PicaPart &p, int half) { return (const int32_t *)(s->pica_pin[half].p + 4 * p.tab.size()); }
 
+// an enqueued chain nobody has finished: whichever way its owner leaves, the stream is waited for first
+struct QueuedChain { mic_hip_session *s; bool queued = false; ~QueuedChain() { if (queued) (void)hipStreamSynchronize(s->stream); } };
+
 // jobs [j0, nj) of the call's J on session s
 int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj) {
     if (j0 >= nj) return MIC_OK;
@@ -499,45 +477,44 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
     for (int g = j0; g < nj; g++) all_units += 2 * (size_t)J[(size_t)g].n;
     const size_t target = pipeline_target(all_units, true);
     const size_t px_cap = workspace_budget() / 16;                        // u16 per staging half: the two halves take an eighth of the ceiling each
-    std::vector<std::unique_ptr<PicaPart>> parts;
+    std::vector<PicaPart> parts;
     for (int g = j0; g < nj;) {
-        auto p = std::make_unique<PicaPart>();
-        p->g0 = g;
+        PicaPart p;
+        p.g0 = g;
         size_t units = 0;
         for (; g < nj; g++) {
             const mic_hip_pica_enc_job &j = *J[(size_t)g].j;
             const int n = J[(size_t)g].n;
             const size_t ipx = (size_t)j.width * (size_t)j.height;
             const uint32_t irows = (n > 1 && n < j.height) ? (uint32_t)j.height : 0u;
-            if (g > p->g0 && (units >= target || p->px + ipx > px_cap || (uint64_t)p->rows + irows > 0x7FFFFFFFull || (uint64_t)p->nstarts + (uint64_t)n > 0x7FFFFFFFull)) break;
-            p->tab.push_back(MicPicaImage{ (uint64_t)p->px, j.width, j.height, n, irows, p->rows, p->nstarts });
-            p->px += ipx; p->rows += irows; p->nstarts += (uint32_t)n; units += 2 * (size_t)n;
+            if (g > p.g0 && (units >= target || p.px + ipx > px_cap || (uint64_t)p.rows + irows > 0x7FFFFFFFull || (uint64_t)p.nstarts + (uint64_t)n > 0x7FFFFFFFull)) break;
+            p.tab.push_back(MicPicaImage{ (uint64_t)p.px, j.width, j.height, n, irows, p.rows, p.nstarts });
+            p.px += ipx; p.rows += irows; p.nstarts += (uint32_t)n; units += 2 * (size_t)n;
         }
-        p->g1 = g;
+        p.g1 = g;
         parts.push_back(std::move(p));
     }
-    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: the pipeline's stages on stderr)
-    if (trace) for (size_t k = 0; k < parts.size(); k++) fprintf(stderr, "[mic_hip pica encode] part %zu of %zu: images %d .. %d, %zu pixels\n", k + 1, parts.size(), parts[k]->g0, parts[k]->g1 - 1, parts[k]->px);
+    for (size_t k = 0; k < parts.size(); k++) trace_part("pica encode", k, parts.size(), "images", parts[k].g0, parts[k].g1, parts[k].px);
     DevBuf *in[2] = { &s->io_px, &s->io_px2 };
-    auto upload = [&](PicaPart &p, int half) -> int {
+    struct Strip { int job, idx; uint64_t px_off; int32_t w, rows; uint16_t maxv; };
+    // one download per chain, not per part: keep_packed waits for the chain before, across parts.  Waited for below, whatever happened.
+    std::vector<std::unique_ptr<IoReq>> downs;
+    rc = run_staged(parts.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const PicaPart &p = parts[k];
         int r = in[half]->reserve(p.px * 2 + 64);
         for (int g = p.g0; g < p.g1 && r == MIC_OK; g++) {
             const mic_hip_pica_enc_job &j = *J[(size_t)g].j;
-            r = io_submit(p.up, s->device, (uint16_t *)in[half]->p + p.tab[(size_t)(g - p.g0)].px_off, j.pixels, (size_t)j.width * (size_t)j.height * 2, true);
+            r = io_submit(up, s->device, (uint16_t *)in[half]->p + p.tab[(size_t)(g - p.g0)].px_off, j.pixels, (size_t)j.width * (size_t)j.height * 2, true);
         }
         return r;
-    };
-    struct Strip { int job, idx; uint64_t px_off; int32_t w, rows; uint16_t maxv; };
-    std::vector<std::unique_ptr<IoReq>> downs;
-    bool chain_queued = false;                                           // an enqueued chain nobody has finished: an error return waits for it
-    auto drain = [&](int r) { if (chain_queued) { (void)hipStreamSynchronize(s->stream); chain_queued = false; } for (auto &p : parts) { const int r2 = p->up.wait(); if (r == MIC_OK) r = r2; } for (auto &d : downs) { const int r2 = d->wait(); if (r == MIC_OK) r = r2; } return r; };
-    if ((rc = upload(*parts[0], 0))) return drain(rc);
-    if ((rc = parts[0]->up.wait())) return drain(rc);
-    if ((rc = pica_bounds_enqueue(s, *parts[0], (const uint16_t *)in[0]->p, 0))) return drain(rc);
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return drain(MIC_ERR_DEVICE);
-    for (size_t k = 0; k < parts.size(); k++) {
-        PicaPart &p = *parts[k];
-        const int half = (int)(k & 1);
+    }, [&](size_t k, int half, IoReq &, IoReq *next_up) -> int {
+        PicaPart &p = parts[k];
+        int rc;
+        QueuedChain chain{ s };
+        if (k == 0) {                                                   // (the later parts' boundaries rode behind the chains of the part before)
+            if ((rc = pica_bounds_enqueue(s, p, (const uint16_t *)in[0]->p, 0))) return rc;
+            if (hipStreamSynchronize(s->stream) != hipSuccess) return MIC_ERR_DEVICE;
+        }
         // the part's strips, from the boundaries the device found
         std::vector<Strip> strips;
         const int32_t *starts = pica_starts_of(s, p, half);
@@ -547,7 +524,7 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
             const int32_t *st = starts + im.start0;
             for (int i = 0; i < r.n; i++) {
                 const int32_t y0 = st[i], y1 = (i + 1 < r.n) ? st[i + 1] : im.h;
-                if (y0 < 0 || y0 >= im.h || y1 > im.h) return drain(MIC_ERR_INTERNAL);
+                if (y0 < 0 || y0 >= im.h || y1 > im.h) return MIC_ERR_INTERNAL;
                 r.y0[(size_t)i] = y0;
                 // a strip of no rows (the partition clamps late boundaries to the last row, :282-284) has nothing to code: the unit
                 // codec rejects it like the reference's does, in strip order with the other strips' errors
@@ -556,8 +533,7 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
                 strips.push_back(Strip{ g, i, im.px_off + (uint64_t)y0 * (uint64_t)im.w, im.w, y1 - y0, r.j->max_value });
             }
         }
-        if (k + 1 < parts.size() && (rc = upload(*parts[k + 1], half ^ 1))) return drain(rc);   // (that half's chains are finished)
-        bool next_bounds = k + 1 == parts.size();                       // the next part's boundary stage is queued (or there is none)
+        bool next_bounds = !next_up;                                    // the next part's boundary stage is queued (or there is none)
         const int nsr = (int)strips.size();
         for (int s0 = 0; s0 < nsr || !next_bounds;) {
             // strips [s0, s1) of the next chain: two units each, under the workspace ceiling
@@ -575,21 +551,21 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
                 units[(size_t)(2 * (q - s0))] = mic_hip_unit{ t.px_off, t.w, t.rows, t.maxv, 2 };                                         // :92
                 units[(size_t)(2 * (q - s0) + 1)] = mic_hip_unit{ t.px_off, t.w, t.rows, t.maxv, (uint16_t)(2 | MIC_HIP_PRED_GRAD) };     // :94
             }
-            if (nb && (rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, units.data(), nb, true))) return drain(rc);
-            chain_queued = nb != 0;
+            if (nb && (rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, units.data(), nb, true))) return rc;
+            chain.queued = nb != 0;
             if (s1 == nsr && !next_bounds) {                              // behind the part's last chain: the next part's boundaries
-                if ((rc = parts[k + 1]->up.wait())) return drain(rc);
-                if ((rc = pica_bounds_enqueue(s, *parts[k + 1], (const uint16_t *)in[half ^ 1]->p, half ^ 1))) return drain(rc);
+                if ((rc = next_up->wait())) return rc;
+                if ((rc = pica_bounds_enqueue(s, parts[k + 1], (const uint16_t *)in[half ^ 1]->p, half ^ 1))) return rc;
                 next_bounds = true;
-                if (!nb && hipStreamSynchronize(s->stream) != hipSuccess) return drain(MIC_ERR_DEVICE);
+                if (!nb && hipStreamSynchronize(s->stream) != hipSuccess) return MIC_ERR_DEVICE;
             }
             if (!nb) break;
             std::vector<uint64_t> offs((size_t)nb + 1); std::vector<int32_t> st((size_t)nb), nst((size_t)nb);
             const uint8_t *d_blobs = nullptr;
             rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), nst.data());
-            chain_queued = false;
-            if (rc) return drain(rc);
-            if ((rc = keep_packed(s, downs.empty() ? nullptr : downs.back().get()))) return drain(rc);
+            chain.queued = false;
+            if (rc) return rc;
+            if ((rc = keep_packed(s, downs.empty() ? nullptr : downs.back().get()))) return rc;
             downs.push_back(std::make_unique<IoReq>());
             for (int q = s0; q < s1;) {                                   // per image: its winners of this chain lie back to back -- one transfer
                 PicaRun &r = J[(size_t)strips[(size_t)q].job];
@@ -608,19 +584,21 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
                 }
 #ifndef MIC_PICA_NO_PICK
                 const size_t bytes = (size_t)(offs[(size_t)(2 * (e - s0))] - offs[(size_t)(2 * (q - s0))]);
-                if (!r.failed() && (rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[(size_t)(2 * (q - s0))], bytes))) return drain(rc);
+                if (!r.failed() && (rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[(size_t)(2 * (q - s0))], bytes))) return rc;
 #else
                 for (int z = q; z < e && !r.failed(); z++) {
                     const size_t a = (size_t)(2 * (z - s0)) + r.flag[(size_t)strips[(size_t)z].idx], bytes = (size_t)(offs[a + 1] - offs[a]);
-                    if ((rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[a], bytes))) return drain(rc);
+                    if ((rc = r.dst.append(*downs.back(), s->device, d_blobs + offs[a], bytes))) return rc;
                 }
 #endif
                 q = e;
             }
             s0 = s1;
         }
-    }
-    return drain(MIC_OK);
+        return MIC_OK;
+    });
+    for (auto &d : downs) { const int r2 = d->wait(); if (rc == MIC_OK) rc = r2; }
+    return rc;
 }
 
 // ============================================================================ strip files: PICS (parallelstrips.go), PICA (parallelstripsadaptive.go)
@@ -669,9 +647,8 @@ int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry en
 
 // ============================================================================ RGB: many images per call (mic_rgb_batch.hip)
 // The call's jobs are cut into sub-batches of whole images (rgb_next_cut: their units under the workspace ceiling, about a part's
-// share of the pixels); a sub-batch's images come up back to back -- so an image starts at whatever byte its neighbours leave -- into
-// one half of the staging while the other half's sub-batch is coded, and its blobs, assembled on the device, go down from one half
-// of the payload, one copy per job, while the next sub-batch runs.
+// share of the pixels) and run on run_staged; a sub-batch's images come up back to back -- so an image starts at whatever byte its
+// neighbours leave -- and its blobs, assembled on the device, go down from its half of the payload, one copy per job.
 inline size_t rgb_target_px(size_t images, size_t total_px, bool encode) {
     static const char *ov = getenv("MIC_HIP_PIPELINE_PARTS");              // (as pipeline_target: force the number of parts)
     // a unit chain costs about the same for a few units as for hundreds: parts of >= 256 / 384 units (encode / decode), three / two at most
@@ -679,11 +656,6 @@ inline size_t rgb_target_px(size_t images, size_t total_px, bool encode) {
     if (parts < 2) return ~(size_t)0;
     return std::max<size_t>(1, (total_px + parts - 1) / parts);
 }
-void rgb_trace_parts(const char *what, size_t k, size_t parts, int i0, int i1, size_t px) {
-    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: the pipeline's stages on stderr)
-    if (trace) fprintf(stderr, "[mic_hip rgb %s] part %zu of %zu: images %d .. %d, %zu pixels\n", what, k + 1, parts, i0, i1 - 1, px);
-}
-
 // jobs J[j0 .. j1) (checked: arguments fine) on session s
 int rgb_encode_host(mic_hip_session *s, std::vector<mic_hip_rgb_enc_job *> &J, int j0, int j1) {
     if (j0 >= j1) return MIC_OK;
@@ -693,47 +665,38 @@ int rgb_encode_host(mic_hip_session *s, std::vector<mic_hip_rgb_enc_job *> &J, i
     size_t total_px = 0;
     for (int i = j0; i < j1; i++) total_px += npx(i);
     const size_t target = rgb_target_px((size_t)(j1 - j0), total_px, true);
-    struct Sub { int i0, i1; IoReq up, down; std::vector<RgbImage> img; size_t bytes = 0; };
-    std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = j0; i0 < j1;) {
-        auto sb = std::make_unique<Sub>();
-        sb->i0 = i0; sb->i1 = rgb_next_cut(npx, i0, j1, target);
-        for (int i = sb->i0; i < sb->i1; i++) {
-            sb->img.push_back(RgbImage{ (uint64_t)sb->bytes, J[(size_t)i]->width, J[(size_t)i]->height, J[(size_t)i]->container, MIC_OK, -1, 0, 0 });
-            sb->bytes += npx(i) * 3;
+    struct Sub { int i0, i1; std::vector<RgbImage> img; size_t bytes; };
+    std::vector<Sub> subs = staged_cut<Sub>(j0, j1, [&](int i0) { return rgb_next_cut(npx, i0, j1, target); }, [&](int i0, int i1) {
+        Sub sb{ i0, i1, {}, 0 };
+        for (int i = i0; i < i1; i++) {
+            sb.img.push_back(RgbImage{ (uint64_t)sb.bytes, J[(size_t)i]->width, J[(size_t)i]->height, J[(size_t)i]->container, MIC_OK, -1, 0, 0 });
+            sb.bytes += npx(i) * 3;
         }
-        i0 = sb->i1; subs.push_back(std::move(sb));
-    }
-    for (size_t k = 0; k < subs.size(); k++) rgb_trace_parts("encode", k, subs.size(), subs[k]->i0, subs[k]->i1, subs[k]->bytes / 3);
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("rgb encode", k, subs.size(), "images", subs[k].i0, subs[k].i1, subs[k].bytes / 3);
     DevBuf *in[2] = { &s->io_px, &s->io_px2 }, *pay[2] = { &s->rgb_payload, &s->rgb_payload2 };
-    auto upload = [&](Sub &sb, int half) -> int {
+    return run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const Sub &sb = subs[k];
         int r = in[half]->reserve(sb.bytes + 64);
         for (int i = sb.i0; i < sb.i1 && r == MIC_OK; i++)
-            r = io_submit(sb.up, s->device, (uint8_t *)in[half]->p + sb.img[(size_t)(i - sb.i0)].rgb_off, J[(size_t)i]->rgb, npx(i) * 3, true);
+            r = io_submit(up, s->device, (uint8_t *)in[half]->p + sb.img[(size_t)(i - sb.i0)].rgb_off, J[(size_t)i]->rgb, npx(i) * 3, true);
         return r;
-    };
-    rc = upload(*subs[0], 0);
-    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
-        Sub &sb = *subs[k];
-        const int half = (int)(k & 1);
-        rc = sb.up.wait();
-        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);       // (that half's sub-batch is coded: its kernels have been waited for)
-        if (rc == MIC_OK && k >= 2) rc = subs[k - 2]->down.wait();                          // this sub-batch's blobs go where those of k - 2 are (were) going down from
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        Sub &sb = subs[k];
         uint64_t end = 0;
-        if (rc == MIC_OK) rc = rgb_encode_run(s, (const uint8_t *)in[half]->p, sb.img.data(), sb.i1 - sb.i0, *pay[half], 0, &end);
-        if (rc != MIC_OK) break;
+        int rc = rgb_encode_run(s, (const uint8_t *)in[half]->p, sb.img.data(), sb.i1 - sb.i0, *pay[half], 0, &end);
         for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
             mic_hip_rgb_enc_job &j = *J[(size_t)i];
             const RgbImage &im = sb.img[(size_t)(i - sb.i0)];
             j.status = im.status; j.failed_plane = im.failed_plane;
             if (j.status != MIC_OK) continue;
             if (im.blob_len > j.out_cap) { j.status = MIC_ERR_CAPACITY; continue; }
-            rc = io_submit(sb.down, s->device, (uint8_t *)pay[half]->p + im.blob_off, j.out, (size_t)im.blob_len, false);   // the job's bytes: one copy
+            rc = io_submit(down, s->device, (uint8_t *)pay[half]->p + im.blob_off, j.out, (size_t)im.blob_len, false);   // the job's bytes: one copy
             j.out_len = (size_t)im.blob_len;
         }
-    }
-    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
-    return rc;
+        return rc;
+    });
 }
 
 struct RgbDecRun { mic_hip_rgb_dec_job *j; const uint8_t *blob; size_t len; int32_t w, h; RgbPlaneRec pl[3]; };
@@ -746,22 +709,20 @@ int rgb_decode_host(mic_hip_session *s, std::vector<RgbDecRun> &J, int j0, int j
     for (int i = j0; i < j1; i++) total_px += npx(i);
     const size_t target = rgb_target_px((size_t)(j1 - j0), total_px, false);
     // small blobs in ordinary memory are gathered on the host and go up in one copy; large or pinned ones go up from where they lie
-    struct Sub { int i0, i1; IoReq up, down; std::vector<RgbBlob> bl; std::vector<uint8_t> small; size_t comp = 0, bytes = 0; };
-    std::vector<std::unique_ptr<Sub>> subs;
-    for (int i0 = j0; i0 < j1;) {
-        auto sb = std::make_unique<Sub>();
-        sb->i0 = i0; sb->i1 = rgb_next_cut(npx, i0, j1, target);
-        for (int i = sb->i0; i < sb->i1; i++) {
+    struct Sub { int i0, i1; std::vector<RgbBlob> bl; std::vector<uint8_t> small; size_t comp, bytes; };
+    std::vector<Sub> subs = staged_cut<Sub>(j0, j1, [&](int i0) { return rgb_next_cut(npx, i0, j1, target); }, [&](int i0, int i1) {
+        Sub sb{ i0, i1, {}, {}, 0, 0 };
+        for (int i = i0; i < i1; i++) {
             const RgbDecRun &r = J[(size_t)i];
-            RgbBlob b{ 0, r.len, (uint64_t)sb->bytes, r.w, r.h, MIC_OK, -1, { r.pl[0], r.pl[1], r.pl[2] } };
-            sb->bl.push_back(b);
-            sb->bytes += npx(i) * 3;
+            sb.bl.push_back(RgbBlob{ 0, r.len, (uint64_t)sb.bytes, r.w, r.h, MIC_OK, -1, { r.pl[0], r.pl[1], r.pl[2] } });
+            sb.bytes += npx(i) * 3;
         }
-        i0 = sb->i1; subs.push_back(std::move(sb));
-    }
-    for (size_t k = 0; k < subs.size(); k++) rgb_trace_parts("decode", k, subs.size(), subs[k]->i0, subs[k]->i1, subs[k]->bytes / 3);
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("rgb decode", k, subs.size(), "images", subs[k].i0, subs[k].i1, subs[k].bytes / 3);
     DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
-    auto upload = [&](Sub &sb, int half) -> int {
+    return run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        Sub &sb = subs[k];
         std::vector<int> direct;
         for (int i = sb.i0; i < sb.i1; i++) {
             const RgbDecRun &r = J[(size_t)i];
@@ -771,30 +732,22 @@ int rgb_decode_host(mic_hip_session *s, std::vector<RgbDecRun> &J, int j0, int j
         sb.comp = sb.small.size();
         for (int i : direct) { sb.bl[(size_t)(i - sb.i0)].blob_off = sb.comp; sb.comp += J[(size_t)i].len; }
         int r = in[half]->reserve(sb.comp + 64);
-        if (r == MIC_OK && !sb.small.empty()) r = io_submit(sb.up, s->device, in[half]->p, sb.small.data(), sb.small.size(), true);
+        if (r == MIC_OK && !sb.small.empty()) r = io_submit(up, s->device, in[half]->p, sb.small.data(), sb.small.size(), true);
         for (size_t q = 0; q < direct.size() && r == MIC_OK; q++)
-            r = io_submit(sb.up, s->device, (uint8_t *)in[half]->p + sb.bl[(size_t)(direct[q] - sb.i0)].blob_off, J[(size_t)direct[q]].blob, J[(size_t)direct[q]].len, true);
+            r = io_submit(up, s->device, (uint8_t *)in[half]->p + sb.bl[(size_t)(direct[q] - sb.i0)].blob_off, J[(size_t)direct[q]].blob, J[(size_t)direct[q]].len, true);
         return r;
-    };
-    rc = upload(*subs[0], 0);
-    for (size_t k = 0; k < subs.size() && rc == MIC_OK; k++) {
-        Sub &sb = *subs[k];
-        const int half = (int)(k & 1);
-        rc = sb.up.wait();
-        if (rc == MIC_OK && k >= 2) rc = subs[k - 2]->down.wait();                          // this sub-batch decodes into the half that k - 2 is (was) going down from
-        if (rc == MIC_OK && k + 1 < subs.size()) rc = upload(*subs[k + 1], half ^ 1);
-        if (rc == MIC_OK) rc = outb[half]->reserve(sb.bytes + 64);
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        Sub &sb = subs[k];
+        int rc = outb[half]->reserve(sb.bytes + 64);
         if (rc == MIC_OK) rc = rgb_decode_run(s, (const uint8_t *)in[half]->p, sb.bl.data(), sb.i1 - sb.i0, (uint8_t *)outb[half]->p);
-        if (rc != MIC_OK) break;
         for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
             const RgbBlob &b = sb.bl[(size_t)(i - sb.i0)];
             mic_hip_rgb_dec_job &j = *J[(size_t)i].j;
             j.status = b.status; j.failed_plane = b.failed_plane;
-            if (b.status == MIC_OK) rc = io_submit(sb.down, s->device, (uint8_t *)outb[half]->p + b.rgb_off, j.rgb_out, npx(i) * 3, false);
+            if (b.status == MIC_OK) rc = io_submit(down, s->device, (uint8_t *)outb[half]->p + b.rgb_off, j.rgb_out, npx(i) * 3, false);
         }
-    }
-    for (auto &sb : subs) { const int r2 = sb->up.wait(); const int r3 = sb->down.wait(); if (rc == MIC_OK) rc = r2 ? r2 : r3; }
-    return rc;
+        return rc;
+    });
 }
 
 }  // namespace
@@ -838,7 +791,6 @@ int run_parallel(int n, const std::function<int(int)> &work) {
     return MIC_OK;
 }
 int over_devices(const std::vector<int> &first, const ShardWork &work) {
-    static const bool trace = getenv("MIC_HIP_TRACE") != nullptr;        // (as decode_groups: on stderr)
     const std::vector<int> devs = default_devices();
     const int cut = (int)first.size() - 1;
     if (cut < 1) return MIC_ERR_INTERNAL;
@@ -849,7 +801,7 @@ int over_devices(const std::vector<int> &first, const ShardWork &work) {
         DefaultLease lease;
         const int rc = lease.acquire(shards == 1 ? -1 : devs[(size_t)k]);
         if (rc) return rc;
-        if (trace) fprintf(stderr, "[mic_hip devices] shard %d of %d on device %d: items %d .. %d\n", k + 1, shards, lease.s->device, i0, i1 - 1);
+        if (io_trace()) fprintf(stderr, "[mic_hip devices] shard %d of %d on device %d: items %d .. %d\n", k + 1, shards, lease.s->device, i0, i1 - 1);
         return work(lease.s, i0, i1);
     });
 }

@@ -2,6 +2,7 @@
 sub-batch pipeline, and concurrent callers (the header promises what ojph/mic_parallel.h:47-48 promises: any thread, any time).
 Everything is compared with the oracle, bit for bit."""
 import os
+import re
 import subprocess
 import sys
 import threading
@@ -76,10 +77,7 @@ def test_pinned_buffers_take_the_direct_path(mic, mico, synth, gpu_ready):
         mic.host_free(np.zeros(16, dtype=np.uint8))                      # never pinned
 
 
-def test_sub_batch_pipeline_under_a_small_workspace(mic, mico, synth):
-    """A child process with an 8 MB workspace ceiling: every call walks several sub-batches (both staging halves, the packed-buffer
-    swap); results must not depend on the cut."""
-    code = r'''
+_CHILD_HEAD = r'''
 import sys, numpy as np
 sys.path.insert(0, %r)
 import __graft_entry__ as e
@@ -87,6 +85,24 @@ mic = e.load_package()
 import importlib
 synth = importlib.import_module("medical_image_codec_amd.synth")
 from oracle import mico
+''' % ROOT
+
+
+def _parts_per_call(stderr, what):
+    """[the number of parts of each call] from the '[mic_hip units <what>] part k of n: ...' lines of MIC_HIP_TRACE=1"""
+    lines = re.findall(r"\[mic_hip units %s\] part (\d+) of (\d+):" % what, stderr)
+    return [int(n) for k, n in lines if k == "1"]
+
+
+WS_BUDGET_MB = 8
+
+
+def test_sub_batch_pipeline_under_a_small_workspace(mic, mico, synth):
+    """A child process with a workspace ceiling of WS_BUDGET_MB: every call walks several sub-batches (both staging halves, the
+    packed-buffer swap, the wait for the download of sub-batch k - 2); results must not depend on the cut.  MIC_HIP_TRACE=1 makes the
+    library name its parts on stderr: each of the four calls must really have been cut into three parts or more.
+    Observed on an MI355X at 8 MB: PICS encode 6 parts, PICS decode 6, frame encode 3, frame decode 3."""
+    code = _CHILD_HEAD + r'''
 imgs = [synth.xr_like(cols=322, rows=256, depth=12, seed=200 + i) for i in range(9)]
 res = mic.compress_parallel_strips_batch(imgs, 4095, 8, 2)
 files = []
@@ -104,10 +120,78 @@ back = mic.decompress_batch([b for _, b, _ in jobs], [(322, 256)] * 9)
 for img, (st, px) in zip(imgs, back):
     assert st == 0 and np.array_equal(px, img)
 print("ok")
-''' % ROOT
-    env = dict(os.environ, MIC_HIP_WS_BUDGET_MB="8")
+'''
+    env = dict(os.environ, MIC_HIP_WS_BUDGET_MB=str(WS_BUDGET_MB), MIC_HIP_TRACE="1")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    enc, dec = _parts_per_call(r.stderr, "encode"), _parts_per_call(r.stderr, "decode")
+    print("parts per call: encode", enc, "decode", dec)
+    assert len(enc) == 2 and len(dec) == 2 and min(enc + dec) >= 3, (enc, dec, r.stderr)   # (PICS, frames)
+
+
+def _seam_jobs(synth):
+    """nine jobs of mixed sizes, 8 strips each: with three forced parts the cuts fall after jobs 2 and 5"""
+    def small(seed):                                                     # 129 x 77 with few enough symbols per ten-row strip to be coded
+        rng = np.random.default_rng(seed)
+        return ((np.arange(77 * 129).reshape(77, 129) // 3) % 900 + rng.integers(0, 3, (77, 129))).astype(np.uint16)
+    shapes = [(322, 256), (257, 200)]
+    imgs = [small(300 + i) if i % 3 == 2 else synth.xr_like(cols=shapes[i % 3][0], rows=shapes[i % 3][1], depth=12, seed=300 + i) for i in range(9)]
+    imgs[7] = synth.xr_like(cols=129, rows=77, depth=10, seed=7)         # noise: the reference cannot code it (test_pics_batch_equals_...)
+    return imgs
+
+
+SEAM_SMALL_JOB, SEAM_SMALL_CAP, SEAM_PINNED_JOB = 4, 1024, 0               # job 4's buffer holds its header and no more than a strip: the middle part
+
+
+def test_three_forced_parts_with_failing_jobs_in_a_child_process(mic, mico, synth, gpu_ready, tmp_path):
+    """MIC_HIP_PIPELINE_PARTS=3 (read once: a child process): one PICS batch call over nine jobs of mixed sizes, one of them with
+    too small a buffer in the middle part, one that the reference cannot code, one in pinned memory.  Every status and every good
+    file equals the oracle's and the uncut call's of this process; the good files come back exact through the batch decoder in the
+    same child; MIC_HIP_TRACE=1 shows three parts for both calls."""
+    code = _CHILD_HEAD + r'''
+sys.path.insert(0, %r)
+import test_gpu_host_path as t
+imgs = t._seam_jobs(synth)
+st, blobs = t._seam_encode(mic, imgs)
+np.savez(sys.argv[1], status=np.array(st), **{"f%%d" %% i: b for i, b in enumerate(blobs)})
+good = [i for i in range(len(imgs)) if st[i] == 0]
+out = mic.decompress_parallel_strips_batch([blobs[i].tobytes() for i in good], [(imgs[i].shape[1], imgs[i].shape[0]) for i in good])
+for i, (rc, px) in zip(good, out):
+    assert rc == 0 and np.array_equal(px, imgs[i]), i
+print("ok")
+''' % os.path.join(ROOT, "tests")
+    npz = str(tmp_path / "cut.npz")
+    env = dict(os.environ, MIC_HIP_PIPELINE_PARTS="3", MIC_HIP_TRACE="1")
+    r = subprocess.run([sys.executable, "-c", code, npz], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    assert _parts_per_call(r.stderr, "encode") == [3] and _parts_per_call(r.stderr, "decode") == [3], r.stderr
+    cut = np.load(npz)
+    imgs = _seam_jobs(synth)
+    st, blobs = _seam_encode(mic, imgs)                                   # the uncut call
+    for i, img in enumerate(imgs):
+        rc, want = mico.pics_compress(img, 4095, 8, 2)
+        if i == SEAM_SMALL_JOB:
+            assert rc == 0 and len(want) > SEAM_SMALL_CAP
+            rc = mic.MIC_ERR_CAPACITY
+        assert cut["status"][i] == rc == st[i], i
+        if rc == 0:
+            assert cut["f%d" % i].tobytes() == want == blobs[i].tobytes(), i
+    assert sorted(i for i in range(9) if st[i] != 0) == [SEAM_SMALL_JOB, 7]
+
+
+def _seam_encode(mic, imgs):
+    """the seam jobs through one compress_parallel_strips_batch call: ([status], [file bytes])"""
+    imgs = list(imgs)
+    outs = [np.empty(SEAM_SMALL_CAP if i == SEAM_SMALL_JOB else mic.pics_bound(a.shape[1], a.shape[0], 8), dtype=np.uint8) for i, a in enumerate(imgs)]
+    src = mic.host_alloc(imgs[SEAM_PINNED_JOB].nbytes, np.uint16).reshape(imgs[SEAM_PINNED_JOB].shape)
+    dst = mic.host_alloc(outs[SEAM_PINNED_JOB].size)
+    try:
+        src[...] = imgs[SEAM_PINNED_JOB]
+        imgs[SEAM_PINNED_JOB], outs[SEAM_PINNED_JOB] = src, dst
+        res = mic.compress_parallel_strips_batch(imgs, 4095, 8, 2, outs=outs)
+        return [st for st, _ in res], [blob.copy() for _, blob in res]
+    finally:
+        mic.host_free(src); mic.host_free(dst)
 
 
 def test_concurrent_callers_default_pool_and_sessions(mic, mico, synth, gpu_ready):
