@@ -358,6 +358,45 @@ int mic_hip_mic2_read_crops(const uint8_t *compressed, size_t compressed_len,
 /* (the reader form, mic_hip_mic2_reader_*, stands with the streaming calls below, the session form,
  * mic_hip_session_mic2_read_crops, with the session calls: they need those sections' types) */
 
+/* Crops of many volumes per call: a training batch takes each box from another volume of the dataset, and a call per volume pays a
+ * whole decode chain per box.  The semantics of the calls above carry over except as stated.  Crop i is (x, y, z, volume) =
+ * xyzv[4i .. 4i + 3], the box [x, x + cw) x [y, y + ch) x [z, z + cd) of files[volume].  One call may mix volumes of any width, height,
+ * frame count and bit depth, independent and temporal files, and list a volume twice (it is then two volumes).
+ * The frames the crops need, of all volumes, go through the unit codec in plan order -- ascending by volume, then frame -- in
+ * sub-batches cut under the workspace ceiling by the frames' sizes alone: a cut may fall between volumes or inside one, frames of
+ * independent volumes, frame 0 of temporal ones and residual units share a sub-batch, and when everything fits one sub-batch the call
+ * runs ONE decode chain (stats->slabs == 1).
+ * Before a file is looked at and before anything is launched, d_out untouched, in this order: MIC_ERR_ARGS for cw, ch, cd <= 0, n < 0,
+ * nfiles < 0 or a NULL array that is needed; MIC_ERR_CAPACITY for out_cap below the tensor's size; MIC_ERR_ARGS for a volume index
+ * outside [0, nfiles); MIC_ERR_ARGS for d_out NULL or not memory the call's device can write.  n == 0 is MIC_OK with zeroed stats.
+ * A volume fails alone: status[i] of every crop of it gets the volume's code, those crops are all 0 and no other volume is affected
+ * -- a NULL file or reader (MIC_ERR_ARGS), a header mic_hip_mic2_info refuses (its code; width or height 0: MIC_ERR_CORRUPT), more than
+ * 2^28 pixels a frame or a file longer than 0xFFFFFFF0 (MIC_ERR_UNSUPPORTED), in the session form a head shorter than 20 + 8 * nframes
+ * or a NULL d_files entry of a volume whose frames are needed (MIC_ERR_ARGS), a table entry of a needed frame with length 0 or a range
+ * outside the file (MIC_ERR_CORRUPT -- on purpose not the single-file call's way, which fails as a whole: a batch over a dataset must
+ * not die for one bad file).  Volumes no crop names are not parsed and not read; they may be NULL or garbage.
+ * status[i] (may be NULL) is otherwise MIC_OK or the unit codec's code of the first failing frame, in frame order, among the frames
+ * crop i depends on (independent: the frames it overlaps; temporal: 0 .. the last it overlaps); failed_frame[i] (may be NULL) that
+ * frame, else -1, also for a volume-level failure.  A failed crop's samples are unspecified, every other crop is exact; a temporal
+ * volume's failed frame stops only that volume.  Returns MIC_OK when the call ran.
+ * stats (may be NULL): frames_decoded and pieces are the planner's counts, slabs the decode chains the call ran, volumes_read the
+ * named volumes whose header and needed table entries were accepted. */
+typedef struct { uint64_t frames_decoded, pieces, slabs, volumes_read; } mic_hip_multi_crop_stats;
+/* The host planner: volume_of[cap] / frame_of[cap] receive the (volume, frame) units whose streams must be entropy-decoded, ascending
+ * by volume, then frame, each once -- independent volume: the overlapped frames; temporal: 0 .. the last overlapped frame.
+ * *nframes_out their number, *npieces the (crop, frame) overlaps with non-empty area (both may be NULL); file_status[nfiles] (may be
+ * NULL) each volume's code as above, MIC_OK for a volume no crop names.  More than cap units: MIC_ERR_CAPACITY with the counts and
+ * file_status set and the arrays untouched; more than 2^32 - 1 pieces: MIC_ERR_UNSUPPORTED.  Reads only the 20-byte headers and the
+ * frame tables.  Needs no device. */
+int mic_hip_mic2_multi_crop_plan(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                 const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                 uint32_t *volume_of, uint32_t *frame_of, size_t cap,
+                                 uint64_t *nframes_out, uint64_t *npieces, int32_t *file_status);
+int mic_hip_mic2_multi_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                  const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                  int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats);
+/* (mic_hip_mic2_readers_read_crops stands with the streaming calls, mic_hip_session_mic2_multi_read_crops with the session calls) */
+
 /* ---- strip files: many crops per call --------------------------------------------------------- */
 /* Many 2-D crops of many PICS / PICA files per call, into a tensor that already lives on the device (no reference counterpart;
  * beside mic_hip_pics_decompress_batch / mic_hip_pica_decompress_batch, which serve whole images through the host, and the MIC3 patch
@@ -610,6 +649,12 @@ int mic_hip_mic2_reader_info(const mic_hip_mic2_reader *r, int *width, int *heig
 int mic_hip_mic2_reader_read_crops(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
 void mic_hip_mic2_reader_close(mic_hip_mic2_reader *r);
+/* mic_hip_mic2_multi_read_crops through readers (volume = an index into readers[]; an entry no crop names may be NULL and is not
+ * read): each named reader's blobs are pulled before anything is launched, each once, neighbours in the file in one read; a failing
+ * callback makes the call MIC_ERR_IO with d_out untouched.  Distinct named readers are locked once, in address order. */
+int mic_hip_mic2_readers_read_crops(mic_hip_mic2_reader *const *readers, int nreaders,
+                                    const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                    int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats);
 
 /* ---- single-frame RGB and the CLI's single-frame files ------------------------------------------ */
 /* Replaces CompressRGB / DecompressRGB (rgbcompress.go:25-33): YCoCg-R, then the three planes as in a WSI tile blob
@@ -775,6 +820,15 @@ int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, siz
                                     const uint8_t *d_file, size_t file_len,
                                     const int32_t *xyz, int n, int cw, int ch, int cd,
                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats);
+/* mic_hip_mic2_multi_read_crops on MIC2 files that lie in device memory: heads[v] (host, head_lens[v] bytes) = at least the first
+ * 20 + 8 * nframes bytes of volume v -- fewer is that volume's MIC_ERR_ARGS --, d_files[v] = the whole file (lens[v] bytes) on the
+ * session's device; it may be NULL when none of that volume's frames is needed.  The streams go device to device; nothing but the
+ * piece and footprint lists crosses PCIe. */
+int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s,
+                                          const uint8_t *const *heads, const size_t *head_lens,
+                                          const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                          const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                          int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats);
 
 /* mic_hip_strips_read_crops on strip files that lie in device memory -- a dataset kept compressed in HBM and sampled from there.
  * heads[f] (host, head_lens[f] bytes) = at least the header and strip table of file f: its first 20 + 8 * num_strips (PICS) or

@@ -140,6 +140,11 @@ class CropStats(C.Structure):
     _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class MultiCropStats(C.Structure):
+    """mic_hip_multi_crop_stats"""
+    _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64), ("volumes_read", C.c_uint64)]
+
+
 class StripCropStats(C.Structure):
     """mic_hip_strip_crop_stats"""
     _fields_ = [("strips_decoded", C.c_uint64), ("strips_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
@@ -162,6 +167,8 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_decompress_frame",
     "mic_hip_mic2_crop_plan", "mic_hip_mic2_read_crops", "mic_hip_mic2_reader_open", "mic_hip_mic2_reader_info",
     "mic_hip_mic2_reader_read_crops", "mic_hip_mic2_reader_close", "mic_hip_session_mic2_read_crops",
+    "mic_hip_mic2_multi_crop_plan", "mic_hip_mic2_multi_read_crops", "mic_hip_mic2_readers_read_crops",
+    "mic_hip_session_mic2_multi_read_crops",
     "mic_hip_strips_crop_plan", "mic_hip_strips_read_crops", "mic_hip_session_strips_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
@@ -344,6 +351,13 @@ def lib() -> C.CDLL:
     L.mic_hip_mic2_reader_close.argtypes = [C.c_void_p]
     L.mic_hip_mic2_reader_close.restype = None
     L.mic_hip_session_mic2_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + _crop_args
+    _multi_crop_args = [C.c_void_p] + [C.c_int] * 4                                        # xyzv, n, cw, ch, cd
+    _multi_crop_out = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(MultiCropStats)]
+    L.mic_hip_mic2_multi_crop_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _multi_crop_args + [
+        C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.mic_hip_mic2_multi_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _multi_crop_args + _multi_crop_out
+    L.mic_hip_mic2_readers_read_crops.argtypes = [C.c_void_p, C.c_int] + _multi_crop_args + _multi_crop_out
+    L.mic_hip_session_mic2_multi_read_crops.argtypes = [C.c_void_p] * 5 + [C.c_int] + _multi_crop_args + _multi_crop_out
     _strip_crop_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(StripCropStats)]
     L.mic_hip_strips_crop_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
@@ -794,6 +808,67 @@ def mic2_read_crops(compressed, xyz, cw: int, ch: int, cd: int, d_out: int, out_
     if rc:
         _raise(rc, "mic2_read_crops")
     return st, stats
+
+
+def _crop_xyzv(xyzv) -> np.ndarray:
+    """(n, 4) crop origins and volume indices (x, y, z, volume) as the int32 quadruples the C calls take"""
+    return np.ascontiguousarray(np.asarray(xyzv, dtype=np.int64).reshape(-1, 4).astype(np.int32))
+
+
+def _volume_table(files):
+    """_file_table of a list whose entries may be None (a volume no crop names): a NULL pointer of length 0"""
+    arrs = [None if f is None else _bytes_arr(f) for f in files]
+    ptrs = np.asarray([0 if a is None else a.ctypes.data for a in arrs], dtype=np.uintp)
+    lens = np.asarray([0 if a is None else a.size for a in arrs], dtype=np.uintp)
+    return arrs, ptrs, lens
+
+
+def mic2_multi_crop_plan(files, xyzv, cw: int, ch: int, cd: int, cap: Optional[int] = None):
+    """mic_hip_mic2_multi_crop_plan: ((n, 2) uint32 array of the (volume, frame) units the crops need entropy-decoded -- ascending by
+    volume, then frame, each once --, number of (crop, frame) pieces, int32 status of each volume).  `files`: MIC2 files, or at least
+    their headers and frame tables (an entry no crop names may be None).  Needs no device.  cap: room for that many units
+    (default: as many as it takes); too few raises MicError (MIC_ERR_CAPACITY) whose ``nframes``, ``pieces`` and ``file_status``
+    attributes are the counts and the volumes' codes."""
+    arrs, ptrs, lens = _volume_table(files)
+    a = _crop_xyzv(xyzv)
+    nf, npc = C.c_uint64(0), C.c_uint64(0)
+    fs = np.zeros(max(len(arrs), 1), dtype=np.int32)
+    head = (ptrs.ctypes.data, lens.ctypes.data, len(arrs), a.ctypes.data, len(a), cw, ch, cd)
+    if cap is None:
+        rc = lib().mic_hip_mic2_multi_crop_plan(*head, None, None, 0, C.byref(nf), C.byref(npc), fs.ctypes.data)
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "mic2_multi_crop_plan")
+        cap = nf.value
+    volume_of, frame_of = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+    rc = lib().mic_hip_mic2_multi_crop_plan(*head, volume_of.ctypes.data, frame_of.ctypes.data, cap, C.byref(nf), C.byref(npc), fs.ctypes.data)
+    if rc:
+        e = MicError(rc, "mic2_multi_crop_plan")
+        e.nframes, e.pieces, e.file_status = nf.value, npc.value, fs[: len(arrs)].copy()
+        raise e
+    return np.stack([volume_of[: nf.value], frame_of[: nf.value]], axis=1), npc.value, fs[: len(arrs)].copy()
+
+
+def _read_multi_crops(call, xyzv, d_out: int, out_cap: int):
+    a = _crop_xyzv(xyzv)
+    st = np.zeros(len(a), dtype=np.int32)
+    bad = np.full(len(a), -1, dtype=np.int32)
+    cs = MultiCropStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, bad.ctypes.data, C.byref(cs))
+    return rc, st, bad, dict(frames_decoded=cs.frames_decoded, pieces=cs.pieces, slabs=cs.slabs, volumes_read=cs.volumes_read)
+
+
+def mic2_multi_read_crops(files, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    """mic_hip_mic2_multi_read_crops: the cw x ch x cd crops (x, y, z, volume) `xyzv` of the MIC2 files `files` (host buffers;
+    volume = an index into the list; an entry no crop names may be None), into the caller's device tensor d_out (an int:
+    ``torch.empty((n, cd, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned host memory) of out_cap bytes.  The
+    volumes may differ in size, depth and pipeline; one that does not parse fails alone.  Samples outside a volume are 0.
+    -> (status per crop, failed frame per crop (-1: none), dict(frames_decoded, pieces, slabs, volumes_read))."""
+    arrs, ptrs, lens = _volume_table(files)
+    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_mic2_multi_read_crops(
+        ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, cw, ch, cd, d, cap, s, b, p), xyzv, d_out, out_cap)
+    if rc:
+        _raise(rc, "mic2_multi_read_crops")
+    return st, bad, stats
 
 
 # ------------------------------------------------------------------ strip files: many crops per call
@@ -1398,6 +1473,21 @@ class Mic2Reader:
             pass
 
 
+def mic2_readers_read_crops(readers, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    """mic_hip_mic2_readers_read_crops: mic2_multi_read_crops over a sequence of Mic2Reader (volume = an index into it; an entry no
+    crop names may be None and is never read).  Only the streams of the plan's frames are read, each once."""
+    readers = list(readers)
+    hs = np.asarray([(r._h.value or 0) if r is not None else 0 for r in readers], dtype=np.uintp)
+    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_mic2_readers_read_crops(
+        hs.ctypes.data, len(readers), a, n, cw, ch, cd, d, cap, s, b, p), xyzv, d_out, out_cap)
+    for r in readers:                                  # an exception a source raised comes first
+        if r is not None and r._cb.exc is not None:
+            r._cb.check(rc, "mic2_readers_read_crops")
+    if rc:
+        _raise(rc, "mic2_readers_read_crops")
+    return st, bad, stats
+
+
 # ------------------------------------------------------------------ gradient predictor, PICA
 def compress_single_frame_grad(pixels, width: int, height: int, max_value: int) -> bytes:
     """CompressSingleFrameGrad (multiframecompress.go:111)."""
@@ -1838,6 +1928,22 @@ class Session:
         if rc:
             _raise(rc, "session_mic2_read_crops")
         return st, stats
+
+    def mic2_multi_read_crops(self, heads, d_files, lens, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+        """mic2_multi_read_crops of MIC2 files that lie on the session's device: heads[v] = the first 20 + 8 * nframes bytes of volume
+        v (host; None for a volume no crop names), d_files[v] = the device address of the whole file (0 / None when none of its
+        frames is needed), lens[v] its length.  The streams of the needed frames go device to device."""
+        harrs, hptrs, hlens = _volume_table(heads)
+        dptrs = np.asarray([int(p or 0) for p in d_files], dtype=np.uintp)
+        flens = np.asarray([int(n) for n in lens], dtype=np.uintp)
+        if not (len(harrs) == dptrs.size == flens.size):
+            raise ValueError("heads, d_files and lens must name the same volumes")
+        rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_session_mic2_multi_read_crops(
+            self._h, hptrs.ctypes.data, hlens.ctypes.data, dptrs.ctypes.data, flens.ctypes.data, len(harrs), a, n, cw, ch, cd, d, cap, s, b, p),
+            xyzv, d_out, out_cap)
+        if rc:
+            _raise(rc, "session_mic2_multi_read_crops")
+        return st, bad, stats
 
     def strips_read_crops(self, heads, d_files, lens, xyf, cw: int, ch: int, d_out: int, out_cap: int):
         """strips_read_crops of PICS / PICA files that lie on the session's device: heads[f] = strips_head(file f) (host),

@@ -11,6 +11,13 @@
 //                      with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0, the
 //                      spatial unit, is the only full image on the device; the carry from one sub-batch to the next lives in the
 //                      tensor itself.
+// Crops of many volumes per call (mic_hip_mic2_multi_crop_plan, mic_hip_mic2_multi_read_crops, mic_hip_mic2_readers_read_crops,
+// mic_hip_session_mic2_multi_read_crops): one core of its own (mic2_multi_read_crops) behind three doors.  Every named volume is planned
+// as above; the units of all of them, ascending by volume, then frame, go through the unit codec in sub-batches that are cut by the
+// units' sizes alone (next_strip_cut), so a sub-batch holds frames of independent volumes, frame 0 of temporal ones -- both decoded
+// into one pixel slab -- and residual symbol units side by side: a batch of crops from sixteen volumes is one decode chain.  Behind
+// each sub-batch the gather copies the independent volumes' pieces and k_mic2_accumulate_crops_multi sums under the footprints of the
+// temporal volumes the sub-batch holds a part of.
 #include <climits>
 #include <memory>
 #include "mic_session.h"
@@ -47,6 +54,44 @@ __global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *un
             } else acc = d[(size_t)max(f0 - 1 - zf, 0) * slice + x];
             for (int i = r0; i < iend; i++) {
                 acc = (acc + unzigzag16(mic_g(units[i].sym)[srow + x])) & 0xFFFFu;          // temporaldelta.go:27-37
+                if (f0 + i >= zf) d[(size_t)(f0 + i - zf) * slice + x] = (uint16_t)acc;
+            }
+            if (f0 + iend - 1 < zf) d[x] = (uint16_t)acc;
+        }
+    }
+}
+
+// k_mic2_accumulate_crops for a sub-batch that holds parts of several temporal volumes.  A footprint names its volume by its slot
+// among the call's temporal volumes (the list is sorted by it); spans[slot - slot0] says what the sub-batch holds of that volume:
+// its units u0 .. u0 + nb - 1 are the volume's frames f0 .. f0 + nb - 1, fbad the volume's first failed frame so far (INT_MAX: none),
+// frame0 where its frame 0 lies in the pixel slab (f0 == 0 only), fw its width.  The launch covers the footprints of the volumes
+// present; everything a block loops over is uniform in it.
+struct VolPrint { CropPiece fp; int32_t slot, pad; };
+struct VolSpan { uint64_t frame0; int32_t u0, nb, f0, fbad, fw, pad; };
+__global__ void __launch_bounds__(256) k_mic2_accumulate_crops_multi(const MicUnit *__restrict__ units, const VolSpan *__restrict__ spans, int slot0,
+                                                                   const uint16_t *__restrict__ slab, const VolPrint *__restrict__ prints,
+                                                                   uint16_t *out, int cw, int ch, int cd) {
+    const VolPrint vp = prints[blockIdx.x];
+    const CropPiece &fp = vp.fp;
+    const VolSpan v = spans[vp.slot - slot0];
+    const int f0 = v.f0, fw = v.fw;
+    if (fp.k < f0 || fp.k >= v.fbad) return;
+    const MicUnit *vu = units + v.u0;
+    const PieceLanes ln = piece_lanes(fp.w);
+    const int zf = fp.frame, iend = min(v.nb, fp.k - f0 + 1), r0 = f0 ? 0 : 1;
+    const size_t slice = (size_t)ch * cw;
+    uint16_t *dst = out + (((size_t)fp.crop * cd + fp.dz) * ch + fp.dy) * cw + fp.dx;
+    for (int y = ln.row; y < fp.h; y += ln.rstep) {
+        const size_t srow = (size_t)(fp.sy + y) * fw + fp.sx;
+        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
+        for (int x = ln.col; x < fp.w; x += ln.lw) {
+            uint32_t acc;
+            if (f0 == 0) {
+                acc = mic_g(slab)[v.frame0 + srow + x];
+                if (zf == 0) d[x] = (uint16_t)acc;
+            } else acc = d[(size_t)max(f0 - 1 - zf, 0) * slice + x];
+            for (int i = r0; i < iend; i++) {
+                acc = (acc + unzigzag16(mic_g(vu[i].sym)[srow + x])) & 0xFFFFu;             // temporaldelta.go:27-37
                 if (f0 + i >= zf) d[(size_t)(f0 + i - zf) * slice + x] = (uint16_t)acc;
             }
             if (f0 + iend - 1 < zf) d[x] = (uint16_t)acc;
@@ -232,6 +277,276 @@ int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(co
     return mic2_read_crops(s, m, plan, src, n, cw, ch, cd, d_out, need, status, stats);
 }
 
+// ---- crops of many volumes per call ------------------------------------------------------------------------------------------
+
+// a volume of the call: where its header and table are read (host), what they said, and the plan of the crops that name it
+struct Mic2Vol {
+    const uint8_t *head = nullptr; size_t head_len = 0; uint64_t file_len = 0;      // (the door's)
+    bool named = false;                     // some crop names it: only then is it looked at
+    int32_t status = MIC_OK;
+    Mic2Head m;
+    CropPlan plan;                          // crop = the call's index; empty for a refused volume
+};
+struct Mic2MultiPlan {
+    std::vector<Mic2Vol> vols;
+    uint64_t units = 0, pieces = 0, read = 0;   // frames to entropy-decode, (crop, frame) overlaps, named volumes that were accepted
+};
+
+// header and table of a named volume: mic_hip_mic2_info's checks against the whole file's length, and mic2_crop_args' of the volume
+int parse_vol(Mic2Vol &f) {
+    if (!f.head) return MIC_ERR_ARGS;
+    if (f.head_len < 20) return MIC_ERR_CORRUPT;
+    const int rc = parse_mic2(f.head, f.file_len, f.m);
+    if (rc) return rc;
+    if (f.m.w <= 0 || f.m.h <= 0) return MIC_ERR_CORRUPT;
+    if ((size_t)f.m.w * (size_t)f.m.h > ((size_t)1 << 28) || f.file_len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
+    if (f.head_len < 20 + 8 * (size_t)f.m.n) return MIC_ERR_ARGS;                           // (the table is not all there)
+    f.m.table = f.head + 20;
+    return MIC_OK;
+}
+
+// a volume fails alone: its crops keep no pieces (their samples stay 0) and carry `code`
+void refuse_vol(Mic2MultiPlan &mp, Mic2Vol &f, int code) {
+    mp.units -= f.plan.frames.size(); mp.pieces -= f.plan.pieces.size(); mp.read--;
+    f.status = code; f.plan = CropPlan();
+}
+
+// The plan of n crops (x, y, z, volume) of cw x ch x cd over the volumes (head, head_len, file_len set by the door): each named
+// volume's own mic2_plan_crops.  MIC_ERR_ARGS for a volume index outside the list; a volume that is refused keeps its code in
+// vols[v].status and no plan.
+int mic2_multi_plan(Mic2MultiPlan &mp, const int32_t *xyzv, int n, int cw, int ch, int cd) {
+    const int nv = (int)mp.vols.size();
+    std::vector<std::vector<int32_t>> mine((size_t)nv);                                     // the crops that name volume v
+    for (int i = 0; i < n; i++) {
+        const int32_t v = xyzv[4 * (size_t)i + 3];
+        if (v < 0 || v >= nv) return MIC_ERR_ARGS;
+        mine[(size_t)v].push_back(i);
+    }
+    mp.units = mp.pieces = mp.read = 0;
+    std::vector<int32_t> xyz;
+    for (int v = 0; v < nv; v++) {
+        Mic2Vol &f = mp.vols[(size_t)v];
+        const std::vector<int32_t> &cr = mine[(size_t)v];
+        f.named = !cr.empty(); f.status = MIC_OK; f.plan = CropPlan();
+        if (!f.named || (f.status = parse_vol(f)) != MIC_OK) continue;
+        xyz.resize(3 * cr.size());
+        for (size_t j = 0; j < cr.size(); j++) std::copy(xyzv + 4 * (size_t)cr[j], xyzv + 4 * (size_t)cr[j] + 3, xyz.begin() + 3 * j);
+        const int rc = mic2_plan_crops(f.m.w, f.m.h, f.m.n, f.m.temporal, xyz.data(), (int)cr.size(), cw, ch, cd, f.plan);
+        if (rc) return rc;
+        for (CropPiece &pc : f.plan.pieces) pc.crop = cr[(size_t)pc.crop];
+        for (CropPiece &fp : f.plan.prints) fp.crop = cr[(size_t)fp.crop];
+        mp.units += f.plan.frames.size(); mp.pieces += f.plan.pieces.size(); mp.read++;
+        for (uint32_t fr : f.plan.frames) {                                                 // as mic_hip_mic2_decompress, multiframe.go:137-139
+            const uint64_t off = 20 + 8 * (uint64_t)f.m.n + get_u32(f.m.table + 8 * (size_t)fr), bl = get_u32(f.m.table + 8 * (size_t)fr + 4);
+            if (bl == 0 || off + bl > f.file_len) { refuse_vol(mp, f, MIC_ERR_CORRUPT); break; }
+        }
+    }
+    return mp.pieces > 0xFFFFFFFFull ? MIC_ERR_UNSUPPORTED : MIC_OK;
+}
+
+// where the core finds the stream of a volume's frame, on the host or (device) on the session's device
+struct Mic2MultiSource { bool device = false; std::function<const uint8_t *(uint32_t vol, uint32_t frame)> blob; };
+
+// n crops into d_out ([n][cd][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
+// current.  The units of every planned volume go through the unit codec in plan order, in sub-batches cut by their sizes alone.
+int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic2MultiSource &src, int n, int cw, int ch, int cd,
+                          void *d_out, size_t need, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
+    struct Unit { uint32_t vol, frame; };
+    const size_t nv = mp.vols.size();
+    std::vector<Unit> un; std::vector<size_t> px, unit0(nv, 0), cuts{ 0 };
+    for (size_t v = 0; v < nv; v++) {
+        const Mic2Vol &f = mp.vols[v];
+        unit0[v] = un.size();
+        for (uint32_t fr : f.plan.frames) { un.push_back(Unit{ (uint32_t)v, fr }); px.push_back((size_t)f.m.w * (size_t)f.m.h); }
+    }
+    const size_t nu = un.size();
+    int rc;
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volumes, refused volumes; every byte is written
+    while (cuts.back() < nu) cuts.push_back(next_strip_cut(px, cuts.back()));
+    auto vol = [&](size_t u) -> const Mic2Vol & { return mp.vols[un[u].vol]; };
+    auto is_frame = [&](size_t u) { return !vol(u).m.temporal || un[u].frame == 0; };       // a frame unit (mode 0), else a residual's symbols (mode 3)
+    auto blob_len = [&](size_t u) { return (uint64_t)get_u32(vol(u).m.table + 8 * (size_t)un[u].frame + 4); };
+    // a frame unit's place in its sub-batch's pixel slab, the largest slab and the most stream bytes of a sub-batch
+    std::vector<uint64_t> slab_off(nu, 0);
+    size_t slab_max = 0, comp_max = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        size_t off = 0, comp = 0;
+        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { if (is_frame(u)) { slab_off[u] = off; off += px[u]; } comp += (size_t)blob_len(u); }
+        slab_max = std::max(slab_max, off); comp_max = std::max(comp_max, comp);
+    }
+    // the call's lists: independent volumes their pieces as the gather reads them, in unit order; temporal volumes their footprints,
+    // in volume order, each volume that has units a slot
+    std::vector<GatherPiece> list; std::vector<size_t> first(nu + 1, 0);                    // the pieces of unit u
+    std::vector<VolPrint> prints; std::vector<size_t> pfirst;                               // the footprints of slot t
+    std::vector<int32_t> slot_of(nv, -1), slot_vol;
+    int mw = 1, mh = 1, tw = 1, th = 1;
+    for (size_t v = 0; v < nv; v++) {
+        const Mic2Vol &f = mp.vols[v];
+        if (f.plan.frames.empty()) continue;
+        if (!f.m.temporal) {
+            for (const CropPiece &pc : f.plan.pieces) {
+                const size_t u = unit0[v] + (size_t)pc.k;
+                first[u + 1]++;
+                list.push_back(GatherPiece{ slab_off[u] + (uint64_t)pc.sy * (uint64_t)f.m.w + (uint64_t)pc.sx,
+                                            (((uint64_t)pc.crop * (uint64_t)cd + (uint64_t)pc.dz) * (uint64_t)ch + (uint64_t)pc.dy) * (uint64_t)cw + (uint64_t)pc.dx,
+                                            f.m.w, cw, pc.w, pc.h, 0, 0 });
+                mw = std::max(mw, pc.w); mh = std::max(mh, pc.h);
+            }
+        } else {
+            slot_of[v] = (int32_t)slot_vol.size(); slot_vol.push_back((int32_t)v);
+            pfirst.push_back(prints.size());
+            for (const CropPiece &fp : f.plan.prints) { prints.push_back(VolPrint{ fp, slot_of[v], 0 }); tw = std::max(tw, fp.w); th = std::max(th, fp.h); }
+        }
+    }
+    pfirst.push_back(prints.size());
+    for (size_t u = 0; u < nu; u++) first[u + 1] += first[u];
+    // ... and, per sub-batch, a span per temporal volume it holds a part of: written when the sub-batch's statuses are known, each
+    // into a place of its own on the host and on the device
+    size_t nspan = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++)
+        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) nspan += vol(u).m.temporal && (u == cuts[b] || un[u].vol != un[u - 1].vol);
+    std::vector<VolSpan> spans; spans.reserve(nspan);
+    const size_t list_bytes = align_up(list.size() * sizeof(GatherPiece), 16), print_bytes = align_up(prints.size() * sizeof(VolPrint), 16);
+    if (nu) {
+        if ((rc = s->pieces.reserve(list_bytes + print_bytes + nspan * sizeof(VolSpan)))) return rc;
+        if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
+        if ((rc = s->io_px.reserve(slab_max * 2 + 64))) return rc;
+        if (!list.empty()) HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+        if (!prints.empty()) HIP_TRY(hipMemcpyAsync((char *)s->pieces.p + list_bytes, prints.data(), prints.size() * sizeof(VolPrint), hipMemcpyHostToDevice, s->stream));
+    }
+    const GatherPiece *d_list = (const GatherPiece *)s->pieces.p;
+    const VolPrint *d_prints = (const VolPrint *)((char *)s->pieces.p + list_bytes);
+    VolSpan *d_spans = (VolSpan *)((char *)s->pieces.p + list_bytes + print_bytes);
+    std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
+    std::vector<int32_t> fbad(slot_vol.size(), INT_MAX), bad_code(slot_vol.size(), MIC_OK); // a temporal volume's first failed frame
+    std::vector<uint64_t> begins, ends;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        const size_t u0 = cuts[b];
+        const int nb = (int)(cuts[b + 1] - u0);
+        if ((rc = pack_streams(s, nb, [&](int i) { return blob_len(u0 + (size_t)i); },
+                               [&](int i) { return src.blob(un[u0 + (size_t)i].vol, un[u0 + (size_t)i].frame); }, src.device, begins, ends))) return rc;
+        if ((rc = s->lay_out(nb, *std::max_element(px.begin() + (ptrdiff_t)u0, px.begin() + (ptrdiff_t)u0 + nb)))) return rc;
+        bool any_sym = false;
+        uint32_t pred_mask = 0;                                                             // predictor classes (by width) of the sub-batch's frames
+        for (int i = 0; i < nb; i++) {
+            const size_t g = u0 + (size_t)i;
+            MicUnit &u = s->h_units[(size_t)i];
+            u.comp_in = (const uint8_t *)s->io_comp.p + begins[(size_t)i]; u.comp_len = (uint32_t)blob_len(g);
+            u.w = vol(g).m.w; u.h = vol(g).m.h;
+            u.tok_cap = (uint32_t)tok_cap_for(px[g]);                                       // (the unit's own bounds, whatever the largest of the sub-batch)
+            u.sym_cap = (uint32_t)std::min<size_t>(tok_cap_for(px[g]) + 64, 0xFFFFFFF0u);
+            if (is_frame(g)) { u.mode = 0; u.px_out = (uint16_t *)s->io_px.p + slab_off[g]; pred_mask |= mic_pred_bit(u.w); }
+            else { u.mode = 3; any_sym = true; }                                            // FSE + RLE-of-symbols into u.sym
+        }
+        s->retry.kind = 0;                                                                  // (laid out here, in tier 2: no second run)
+        rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
+            mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p, pred_mask, s->dec_classes.mask());
+            if (any_sym) {
+                mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
+                mic2_launch_residual_check_units((MicUnit *)s->units.p, nb, s->stream);
+            }
+        });
+        if (rc) return rc;
+        s->learn_decode = true;                                                             // (frames and residuals run the same tANS classes)
+        if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
+        // the temporal volumes of this sub-batch: runs of units of one volume
+        const size_t sp0 = spans.size();
+        int slot0 = 0;
+        for (int i = 0; i < nb;) {
+            const size_t g = u0 + (size_t)i;
+            int j = i + 1;
+            while (j < nb && un[u0 + (size_t)j].vol == un[g].vol) j++;
+            if (vol(g).m.temporal) {
+                const int t = slot_of[un[g].vol];
+                if (spans.size() == sp0) slot0 = t;
+                for (int k = i; k < j && fbad[(size_t)t] == INT_MAX; k++)
+                    if (ust[u0 + (size_t)k] != MIC_OK) { fbad[(size_t)t] = (int32_t)un[u0 + (size_t)k].frame; bad_code[(size_t)t] = ust[u0 + (size_t)k]; }
+                spans.push_back(VolSpan{ un[g].frame == 0 ? slab_off[g] : 0, i, j - i, (int32_t)un[g].frame, fbad[(size_t)t], vol(g).m.w, 0 });
+            }
+            i = j;
+        }
+        const size_t nsp = spans.size() - sp0, p0 = first[u0], np = first[u0 + (size_t)nb] - p0;
+        s->timer.reset(s->stream);
+        if (np) {
+            s->timer.mark("k_mic2_gather_crops");
+            launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, d_list + p0, np, mw, mh, d_out);
+        }
+        if (nsp) {
+            const size_t q0 = pfirst[(size_t)slot0], nq = pfirst[(size_t)slot0 + nsp] - q0;
+            HIP_TRY(hipMemcpyAsync(d_spans + sp0, spans.data() + sp0, nsp * sizeof(VolSpan), hipMemcpyHostToDevice, s->stream));
+            s->timer.mark("k_mic2_accumulate_crops_multi");
+            hipLaunchKernelGGL(k_mic2_accumulate_crops_multi, dim3((unsigned)nq, row_chunks(tw, th)), dim3(256), 0, s->stream,
+                               (const MicUnit *)s->units.p, (const VolSpan *)d_spans + sp0, slot0, (const uint16_t *)s->io_px.p, d_prints + q0,
+                               (uint16_t *)d_out, cw, ch, cd);
+        }
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (int i = 0; i < n; i++) {
+        if (status) status[i] = MIC_OK;
+        if (failed_frame) failed_frame[i] = -1;
+    }
+    if (status || failed_frame) {
+        std::vector<char> failed((size_t)n, 0);                                             // independent volumes: pieces are in frame order
+        for (size_t v = 0; v < nv; v++) {
+            const Mic2Vol &f = mp.vols[v];
+            if (slot_of[v] >= 0) {
+                const int32_t fb = fbad[(size_t)slot_of[v]];
+                for (const CropPiece &fp : f.plan.prints) {
+                    if (fp.k < fb) continue;
+                    if (status) status[fp.crop] = bad_code[(size_t)slot_of[v]];
+                    if (failed_frame) failed_frame[fp.crop] = fb;
+                }
+            } else {
+                for (const CropPiece &pc : f.plan.pieces) {
+                    const int32_t st = ust[unit0[v] + (size_t)pc.k];
+                    if (st == MIC_OK || failed[(size_t)pc.crop]) continue;
+                    failed[(size_t)pc.crop] = 1;
+                    if (status) status[pc.crop] = st;
+                    if (failed_frame) failed_frame[pc.crop] = pc.frame;
+                }
+            }
+        }
+    }
+    if (stats) *stats = mic_hip_multi_crop_stats{ mp.units, mp.pieces, cuts.size() - 1, mp.read };
+    return MIC_OK;
+}
+
+// what the doors check of their arguments before a file is looked at; *need = bytes of the crop tensor
+int multi_crop_args(const void *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd, size_t out_cap, size_t *need) {
+    if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || nfiles < 0 || (n > 0 && !xyzv) || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
+    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)cd * (unsigned)ch * (unsigned)cw * 2;
+    if (bytes > out_cap) return MIC_ERR_CAPACITY;
+    *need = (size_t)bytes;
+    for (int i = 0; i < n; i++) if (xyzv[4 * (size_t)i + 3] < 0 || xyzv[4 * (size_t)i + 3] >= nfiles) return MIC_ERR_ARGS;
+    return MIC_OK;
+}
+
+// a door's call once its arguments stand (multi_crop_args): n == 0, the pointer and the session (leased here when s is NULL), the plan,
+// `source` -- which may still refuse a volume (refuse_vol) or fail the call --, the core, then the refused volumes' codes
+int multi_call(mic_hip_session *s, Mic2MultiPlan &mp, const std::function<int(Mic2MultiSource &)> &source,
+               const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t need,
+               int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
+    if (stats) *stats = mic_hip_multi_crop_stats{ 0, 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    DefaultLease lease;
+    int rc = crop_door(&s, lease, &d_out, need);                                            // judged before a file is looked at
+    if (rc) return rc;
+    if ((rc = mic2_multi_plan(mp, xyzv, n, cw, ch, cd))) return rc;
+    Mic2MultiSource src;
+    if ((rc = source(src))) return rc;
+    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, d_out, need, status, failed_frame, stats))) return rc;
+    if (status)
+        for (int i = 0; i < n; i++) {
+            const int32_t vs = mp.vols[(size_t)xyzv[4 * (size_t)i + 3]].status;
+            if (vs != MIC_OK) status[i] = vs;
+        }
+    return MIC_OK;
+}
+
 }  // namespace
 
 struct mic_hip_mic2_reader {
@@ -345,6 +660,104 @@ int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, siz
         src.blob = [&m, d_file](uint32_t f) { return d_file + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
         return (int)MIC_OK;
     }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+} MIC_ABI_CATCH
+
+int mic_hip_mic2_multi_crop_plan(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                 uint32_t *volume_of, uint32_t *frame_of, size_t cap, uint64_t *nframes_out, uint64_t *npieces, int32_t *file_status) try {
+    size_t need = 0;
+    int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, ~(size_t)0, &need);
+    if (rc) return rc;
+    if (cap > 0 && (!volume_of || !frame_of)) return MIC_ERR_ARGS;
+    Mic2MultiPlan mp;
+    mp.vols.resize((size_t)nfiles);
+    for (int v = 0; v < nfiles; v++) { mp.vols[(size_t)v].head = files[v]; mp.vols[(size_t)v].head_len = mp.vols[(size_t)v].file_len = lens[v]; }
+    rc = mic2_multi_plan(mp, xyzv, n, cw, ch, cd);
+    if (rc) return rc;
+    if (file_status) for (int v = 0; v < nfiles; v++) file_status[v] = mp.vols[(size_t)v].status;
+    if (nframes_out) *nframes_out = mp.units;
+    if (npieces) *npieces = mp.pieces;
+    if (mp.units > cap) return MIC_ERR_CAPACITY;
+    size_t k = 0;
+    for (int v = 0; v < nfiles; v++)
+        for (uint32_t fr : mp.vols[(size_t)v].plan.frames) { volume_of[k] = (uint32_t)v; frame_of[k++] = fr; }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// n crops of MIC2 files in host memory, into a tensor on the default session's device
+int mic_hip_mic2_multi_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                  void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+    size_t need = 0;
+    const int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, out_cap, &need);
+    if (rc) return rc;
+    Mic2MultiPlan mp;
+    mp.vols.resize((size_t)nfiles);
+    for (int v = 0; v < nfiles; v++) { mp.vols[(size_t)v].head = files[v]; mp.vols[(size_t)v].head_len = mp.vols[(size_t)v].file_len = lens[v]; }
+    return multi_call(nullptr, mp, [&](Mic2MultiSource &src) {
+        src.device = false;
+        src.blob = [&mp](uint32_t v, uint32_t f) { const Mic2Head &m = mp.vols[v].m; return m.table + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
+        return (int)MIC_OK;
+    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
+} MIC_ABI_CATCH
+
+// the same through readers (volume = an index into readers[]): every named reader's blobs are pulled before anything is launched
+int mic_hip_mic2_readers_read_crops(mic_hip_mic2_reader *const *readers, int nreaders, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                    void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+    static const size_t no_lens = 0;                                                        // (readers bring their lengths)
+    size_t need = 0;
+    const int rc = multi_crop_args(readers, &no_lens, nreaders, xyzv, n, cw, ch, cd, out_cap, &need);
+    if (rc) return rc;
+    std::vector<mic_hip_mic2_reader *> named;                                               // distinct, in address order: locked once each
+    for (int i = 0; i < n; i++) if (readers[xyzv[4 * (size_t)i + 3]]) named.push_back(readers[xyzv[4 * (size_t)i + 3]]);
+    std::sort(named.begin(), named.end(), std::less<mic_hip_mic2_reader *>());
+    named.erase(std::unique(named.begin(), named.end()), named.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve(named.size());
+    for (mic_hip_mic2_reader *r : named) locks.emplace_back(r->mu);
+    Mic2MultiPlan mp;
+    mp.vols.resize((size_t)nreaders);
+    for (int i = 0; i < n; i++) {
+        const size_t v = (size_t)xyzv[4 * (size_t)i + 3];
+        if (const mic_hip_mic2_reader *r = readers[v]) { mp.vols[v].head = r->head.data(); mp.vols[v].head_len = r->head.size(); mp.vols[v].file_len = r->m.file_len; }
+    }
+    return multi_call(nullptr, mp, [&](Mic2MultiSource &src) {
+        // a reader listed as several volumes pulls the union of their frames, once
+        CropPlan all;
+        Mic2Source one;
+        for (mic_hip_mic2_reader *r : named) {
+            all.frames.clear();
+            for (int v = 0; v < nreaders; v++) if (readers[v] == r) all.frames.insert(all.frames.end(), mp.vols[(size_t)v].plan.frames.begin(), mp.vols[(size_t)v].plan.frames.end());
+            std::sort(all.frames.begin(), all.frames.end());
+            all.frames.erase(std::unique(all.frames.begin(), all.frames.end()), all.frames.end());
+            if (all.frames.empty()) continue;
+            const int frc = r->fetch(all, one);
+            if (frc) return frc;
+        }
+        src.device = false;
+        src.blob = [readers](uint32_t v, uint32_t f) { return (const uint8_t *)readers[v]->keep.data() + readers[v]->pos[f]; };
+        return (int)MIC_OK;
+    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
+} MIC_ABI_CATCH
+
+// n crops of MIC2 files that lie on the session's device: the streams go device to device
+int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                          const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                          const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                          int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+    if (!s) return MIC_ERR_ARGS;
+    size_t need = 0;
+    if (nfiles > 0 && (!head_lens || !d_files)) return MIC_ERR_ARGS;
+    const int rc = multi_crop_args(heads, lens, nfiles, xyzv, n, cw, ch, cd, out_cap, &need);
+    if (rc) return rc;
+    Mic2MultiPlan mp;
+    mp.vols.resize((size_t)nfiles);
+    for (int v = 0; v < nfiles; v++) { mp.vols[(size_t)v].head = heads[v]; mp.vols[(size_t)v].head_len = head_lens[v]; mp.vols[(size_t)v].file_len = lens[v]; }
+    return multi_call(s, mp, [&](Mic2MultiSource &src) {
+        for (int v = 0; v < nfiles; v++)                                                    // (a file whose frames are needed is not there)
+            if (!d_files[v] && !mp.vols[(size_t)v].plan.frames.empty()) refuse_vol(mp, mp.vols[(size_t)v], MIC_ERR_ARGS);
+        src.device = true;
+        src.blob = [&mp, d_files](uint32_t v, uint32_t f) { const Mic2Head &m = mp.vols[v].m; return d_files[v] + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
+        return (int)MIC_OK;
+    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
 } MIC_ABI_CATCH
 
 }  // extern "C"

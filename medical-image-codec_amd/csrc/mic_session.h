@@ -386,6 +386,9 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
 size_t mic2_frames_per_batch(size_t npx);
 // residual units r0 .. n-1 must expand to exactly npx symbols (k_tmp_check), behind their chain on `stream`
 void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream);
+// the same for a chain of units of several sizes (MIC2 crops of many volumes): every symbol unit (mode 3) among units 0 .. n-1 must
+// expand to its own w * h symbols (k_tmp_check_units)
+void mic2_launch_residual_check_units(MicUnit *d_units, int n, hipStream_t stream);
 // What the patch and crop readers share beside the gather (mic_gather.hip; patch_pointer and the kernels' launcher: mic_pieces.h).
 // A sub-batch's nb streams, len(i) bytes at src(i) -- host memory, or (device) the session's device --, back to back into s->io_comp
 // (reserved here, with the 64 bytes the decode kernels may read past a stream's end): neighbours in the source go in one copy.
@@ -413,6 +416,9 @@ int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch,
 int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
                     void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
+// Units [i0, return) of the next sub-batch of a list of units of px[i] pixels each, for the readers that decode units of mixed sizes
+// into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip)
+size_t next_strip_cut(const std::vector<size_t> &px, size_t i0);
 // RGB batches (mic_rgb_batch.hip): many images of different sizes per call, CompressRGB / DecompressRGB (rgbcompress.go:25-33) of each.
 // One image of a sub-batch on the encode side: its RGB at d_rgb + rgb_off; container 1 = a MICR header in front of its blob.
 // status on entry: not MIC_OK = skip the image.  On return: status / failed_plane (0 Y, 1 Co, 2 Cg, -1 not a plane's), and the

@@ -115,9 +115,11 @@ int strips_crop_args(const void *files, const size_t *lens, int nfiles, const in
     return MIC_OK;
 }
 
+}  // namespace
+
 // Units [i0, i1) of the next sub-batch: as many as the workspace ceiling holds of the largest of them -- a unit's tier-2 slabs and its
 // strip in the staging slab, as mic2_frames_per_batch counts a frame -- and at most what one launch chain takes.
-size_t next_strip_cut(const std::vector<size_t> &px, size_t i0) {
+size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0) {
     size_t max_px = 0, i1 = i0;
     while (i1 < px.size()) {
         const size_t mp = std::max(max_px, px[i1]);
@@ -126,6 +128,8 @@ size_t next_strip_cut(const std::vector<size_t> &px, size_t i0) {
     }
     return i1;
 }
+
+namespace {
 
 // n crops into d_out ([n][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
 // current.  base[f]: where file f's bytes lie -- on the host, or (device) on the session's device.

@@ -55,6 +55,11 @@ __global__ void k_tmp_check(MicUnit *units, int n, uint32_t npx, int r0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x + r0;
     if (i < n && units[i].status == MICD_OK && units[i].nsym != npx) units[i].status = MICD_ERR_CORRUPT;
 }
+// ... each symbol unit of a chain of mixed sizes to exactly its own frame
+__global__ void k_tmp_check_units(MicUnit *units, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && units[i].mode == 3 && units[i].status == MICD_OK && units[i].nsym != (uint32_t)units[i].w * (uint32_t)units[i].h) units[i].status = MICD_ERR_CORRUPT;
+}
 
 }  // namespace
 
@@ -66,6 +71,9 @@ namespace micapi {
 size_t mic2_frames_per_batch(size_t npx) { return std::max<size_t>(1, std::min<size_t>(kWorkspaceBudget / (unit_ws_bytes(npx) + 2 * npx), 65535)); }
 void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream) {
     hipLaunchKernelGGL(k_tmp_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_units, n, npx, r0);
+}
+void mic2_launch_residual_check_units(MicUnit *d_units, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tmp_check_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_units, n);
 }
 
 // Frames go through in sub-batches under the workspace ceiling.  Encode: a residual needs the ORIGINAL frame before it, so a sub-batch
