@@ -55,7 +55,7 @@ extern "C" {
  * one session per device with mic_hip_session_create_on and uses the session entry points. */
 int mic_hip_set_device(int device);
 /* SEVERAL devices for the batch entry points below (mic_hip_compress_batch / _decompress_batch, mic_hip_pics_compress_batch /
- * _decompress_batch, mic_hip_mic2_compress / _decompress, mic_hip_wavelet_v2_compress_batch / _decompress_batch / _decompress_level_batch) and for the MIC3
+ * _decompress_batch, mic_hip_mic2_compress / _decompress, mic_hip_mic2_compress_batch / _decompress_batch, mic_hip_wavelet_v2_compress_batch / _decompress_batch / _decompress_level_batch) and for the MIC3
  * calls mic_hip_wsi_compress / _compress_ex (bands of tile rows, see there), mic_hip_wsi_decompress_level and
  * mic_hip_wsi_decompress_region (tile rows; a region of two tile rows or more): a call's jobs are cut into one contiguous shard per listed device,
  * balanced by pixels -- the static assignment of the reference's fan-outs (parallelstrips.go:77-93, multiframecompress.go:186-209,
@@ -320,6 +320,57 @@ int mic_hip_mic2_decompress(const uint8_t *compressed, size_t compressed_len,
  * one frame of a MIC2 file; temporal files decode frames 0..frame_idx. */
 int mic_hip_mic2_decompress_frame(const uint8_t *compressed, size_t compressed_len, int frame_idx,
                                   uint16_t *pixels_out, size_t pixels_cap);
+
+/* Many volumes per call (no reference counterpart: CompressMultiFrame / DecompressMultiFrame, multiframecompress.go:179-261, and
+ * WriteMIC2 / ReadMIC2, multiframe.go:49-142, of each job).  A dataset of small volumes -- cine loops, NM and tomosynthesis stacks --
+ * pays one entropy chain per volume through the single calls, and a chain costs about the same for 30 units as for 2304.  Here one
+ * call may mix volumes of any width, height, frame count and bit depth, independent (temporal = 0) and temporal (1:
+ * TemporalDeltaEncode / TemporalDeltaDecode, temporaldelta.go:11-37) ones; the units of all of them -- volume order, then frame
+ * order -- go through the unit codec in shared sub-batches cut under the workspace ceiling by the units' sizes alone (the rule of
+ * mic_hip_mic2_multi_read_crops; mic_hip_mic2_batch_plan states it): a cut may fall between volumes or inside one, frames, frame 0 of
+ * temporal volumes and residual units share a sub-batch, and when everything fits one sub-batch the call runs ONE chain
+ * (stats->slabs == 1).  Every file written equals the file mic_hip_mic2_compress / mic_hip_mic2_compress_temporal writes for that
+ * volume, byte for byte; every decode equals mic_hip_mic2_decompress.
+ * Returns MIC_OK when the batch ran; njobs == 0 is MIC_OK with zeroed stats; MIC_ERR_ARGS for njobs < 0 or jobs NULL.
+ * A volume fails alone, with the single call's code in status: bad arguments (MIC_ERR_ARGS), more than 2^28 pixels a frame
+ * (MIC_ERR_UNSUPPORTED), a buffer too small (MIC_ERR_CAPACITY), a header mic_hip_mic2_info refuses (its code; a dimension of 0:
+ * MIC_ERR_CORRUPT), a table entry of length 0 or outside the file (MIC_ERR_CORRUPT), a frame the unit codec refuses (its code), a
+ * payload over the u32 offsets (MIC_ERR_UNSUPPORTED, multiframe.go:75-80).  failed_frame is the first failing frame in frame order,
+ * -1 when the error is not a frame's.  A failed encode job has out_len 0, a failed decode job's pixels are unspecified, every other
+ * volume is exact; a temporal volume's failed frame stops only that volume.
+ * The sub-batches are the parts of the host pipeline: part k + 1 comes up while part k is coded and part k - 1 goes down; pinned
+ * buffers (mic_hip_host_alloc) are sent in place.  A part that starts inside a temporal volume uploads the ORIGINAL frame in front of
+ * it on encode, and on decode takes the running sum from where the part before left that frame on the device.
+ * mic_hip_set_devices shards the volumes by pixels, a shard boundary between volumes only; each shard cuts its own units.
+ * stats (may be NULL): units = the frames of the volumes whose arguments (decode: header and table) were accepted, slabs = the
+ * chains the call ran, volumes_done = the volumes whose status is MIC_OK. */
+typedef struct mic_hip_mic2_enc_job {
+    const uint16_t *frames;            /* in : nframes*width*height u16, frame-major (host) */
+    int32_t  width, height, nframes;   /* in  */
+    uint16_t max_value;                /* in  */
+    uint16_t temporal;                 /* in : 0 independent, 1 temporal */
+    uint8_t *out; size_t out_cap;      /* in : MIC_HIP_MIC2_BOUND(...) always suffices */
+    size_t   out_len;                  /* out */
+    int32_t  status, failed_frame;     /* out: first failing frame, -1 when not a frame's error */
+} mic_hip_mic2_enc_job;
+typedef struct mic_hip_mic2_dec_job {
+    const uint8_t *compressed; size_t compressed_len;   /* in (host) */
+    uint16_t *frames_out; size_t frames_cap_px;          /* in (host) */
+    int32_t  width, height, nframes, temporal;           /* out: the header's (0 when the header was refused) */
+    int32_t  status, failed_frame;                       /* out */
+} mic_hip_mic2_dec_job;
+typedef struct { uint64_t units, slabs, volumes_done; } mic_hip_mic2_batch_stats;
+int mic_hip_mic2_compress_batch(mic_hip_mic2_enc_job *jobs, int njobs, mic_hip_mic2_batch_stats *stats);
+int mic_hip_mic2_decompress_batch(mic_hip_mic2_dec_job *jobs, int njobs, mic_hip_mic2_batch_stats *stats);
+/* The cut rule of those calls as a host function: whn = (width, height, nframes) of nvol volumes; their units, volume by volume and
+ * frame by frame, are cut into sub-batches -- a sub-batch takes units while their number stays within
+ * budget_bytes / (tier-2 slabs of its largest frame + that frame's pixels) and within 65535, at least one.  budget_bytes == 0: the
+ * default ceiling (MIC_HIP_WS_BUDGET_MB, else from the device's memory).  cuts[0 .. *ncuts) receives 0, ..., *nunits: sub-batch b is
+ * units cuts[b] .. cuts[b + 1] - 1, so a call over these volumes runs *ncuts - 1 chains (no volumes: cuts = { 0 }).  cap short:
+ * MIC_ERR_CAPACITY with the counts set and cuts untouched; a dimension <= 0: MIC_ERR_ARGS.  Needs no device. */
+int mic_hip_mic2_batch_plan(const int32_t *whn, int nvol, size_t budget_bytes,
+                            uint32_t *cuts, size_t cap, uint64_t *ncuts, uint64_t *nunits);
+/* (the device-resident forms, mic_hip_session_mic2_encode / _decode, stand with the session calls) */
 
 /* Many 3-D crops per call, into a tensor that already lives on the device (no reference counterpart; beside
  * mic_hip_mic2_decompress / _decompress_frame, which serve whole frames through the host, and the MIC3 patch calls, whose semantics
@@ -829,6 +880,32 @@ int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s,
                                           const uint8_t *const *d_files, const size_t *lens, int nfiles,
                                           const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
                                           int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats);
+
+/* mic_hip_mic2_compress_batch on volumes that lie in device memory, the files staying there: volume v is read at
+ * d_frames + vols[v].px_off (u16 units; every residual's predecessor is the volume's own frame before it).  *d_files receives the
+ * complete MIC2 files back to back, file v -- the 20-byte header, the frame table, the streams -- at h_offsets[v] .. h_offsets[v + 1]
+ * (h_offsets: n + 1 entries on the host; a failed volume has h_offsets[v + 1] == h_offsets[v]); a kernel writes the headers and
+ * tables and moves the streams to their final, arbitrarily aligned offsets.  The files are valid until the session's next call;
+ * mic_hip_device_copy keeps them.  h_heads (host, may be NULL) receives the first 20 + 8 * nframes bytes of every file that was
+ * written, one after the other in volume order: with d_files + h_offsets[v] and the lengths they are the arguments of
+ * mic_hip_session_mic2_decode and mic_hip_session_mic2_multi_read_crops.  heads_cap below the sum over the volumes whose arguments
+ * were accepted is MIC_ERR_CAPACITY before anything is launched; s, vols, d_files or h_offsets NULL, n < 0, d_frames NULL with
+ * n > 0: MIC_ERR_ARGS.  status / failed_frame (n entries each, may be NULL) and stats as in the host form; nothing but tables and
+ * statuses crosses PCIe. */
+typedef struct mic_hip_mic2_volume { uint64_t px_off; int32_t width, height, nframes; uint16_t max_value, temporal; } mic_hip_mic2_volume;
+int mic_hip_session_mic2_encode(mic_hip_session *s, const uint16_t *d_frames, const mic_hip_mic2_volume *vols, int n,
+                                const uint8_t **d_files, uint64_t *h_offsets /* n+1 */,
+                                uint8_t *h_heads, size_t heads_cap,
+                                int32_t *status, int32_t *failed_frame, mic_hip_mic2_batch_stats *stats);
+/* mic_hip_mic2_decompress_batch on MIC2 files that lie in device memory, at any byte alignment: heads[v] (host, head_lens[v] bytes) =
+ * at least the first 20 + 8 * nframes bytes of volume v -- fewer is that volume's MIC_ERR_ARGS --, d_files[v] = the whole file
+ * (lens[v] bytes) on the session's device.  Volume v goes to d_frames_out + px_off[v] (u16 units); a volume that would end behind
+ * out_cap_px is MIC_ERR_CAPACITY alone.  The streams go device to device into the session's compressed-input buffer, frames and
+ * running sums are written straight to their final place. */
+int mic_hip_session_mic2_decode(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                const uint8_t *const *d_files, const size_t *lens, int n,
+                                uint16_t *d_frames_out, const uint64_t *px_off, size_t out_cap_px,
+                                int32_t *status, int32_t *failed_frame, mic_hip_mic2_batch_stats *stats);
 
 /* mic_hip_strips_read_crops on strip files that lie in device memory -- a dataset kept compressed in HBM and sampled from there.
  * heads[f] (host, head_lens[f] bytes) = at least the header and strip table of file f: its first 20 + 8 * num_strips (PICS) or

@@ -145,6 +145,32 @@ class MultiCropStats(C.Structure):
     _fields_ = [("frames_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64), ("volumes_read", C.c_uint64)]
 
 
+class Mic2EncJob(C.Structure):
+    """mic_hip_mic2_enc_job"""
+    _fields_ = [("frames", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("nframes", C.c_int32),
+                ("max_value", C.c_uint16), ("temporal", C.c_uint16),
+                ("out", C.c_void_p), ("out_cap", C.c_size_t), ("out_len", C.c_size_t),
+                ("status", C.c_int32), ("failed_frame", C.c_int32)]
+
+
+class Mic2DecJob(C.Structure):
+    """mic_hip_mic2_dec_job"""
+    _fields_ = [("compressed", C.c_void_p), ("compressed_len", C.c_size_t), ("frames_out", C.c_void_p), ("frames_cap_px", C.c_size_t),
+                ("width", C.c_int32), ("height", C.c_int32), ("nframes", C.c_int32), ("temporal", C.c_int32),
+                ("status", C.c_int32), ("failed_frame", C.c_int32)]
+
+
+class Mic2BatchStats(C.Structure):
+    """mic_hip_mic2_batch_stats"""
+    _fields_ = [("units", C.c_uint64), ("slabs", C.c_uint64), ("volumes_done", C.c_uint64)]
+
+
+class Mic2Volume(C.Structure):
+    """mic_hip_mic2_volume"""
+    _fields_ = [("px_off", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32), ("nframes", C.c_int32),
+                ("max_value", C.c_uint16), ("temporal", C.c_uint16)]
+
+
 class StripCropStats(C.Structure):
     """mic_hip_strip_crop_stats"""
     _fields_ = [("strips_decoded", C.c_uint64), ("strips_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
@@ -169,6 +195,8 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_reader_read_crops", "mic_hip_mic2_reader_close", "mic_hip_session_mic2_read_crops",
     "mic_hip_mic2_multi_crop_plan", "mic_hip_mic2_multi_read_crops", "mic_hip_mic2_readers_read_crops",
     "mic_hip_session_mic2_multi_read_crops",
+    "mic_hip_mic2_compress_batch", "mic_hip_mic2_decompress_batch", "mic_hip_mic2_batch_plan",
+    "mic_hip_session_mic2_encode", "mic_hip_session_mic2_decode",
     "mic_hip_strips_crop_plan", "mic_hip_strips_read_crops", "mic_hip_session_strips_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
@@ -358,6 +386,13 @@ def lib() -> C.CDLL:
     L.mic_hip_mic2_multi_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _multi_crop_args + _multi_crop_out
     L.mic_hip_mic2_readers_read_crops.argtypes = [C.c_void_p, C.c_int] + _multi_crop_args + _multi_crop_out
     L.mic_hip_session_mic2_multi_read_crops.argtypes = [C.c_void_p] * 5 + [C.c_int] + _multi_crop_args + _multi_crop_out
+    L.mic_hip_mic2_compress_batch.argtypes = [C.POINTER(Mic2EncJob), C.c_int, C.POINTER(Mic2BatchStats)]
+    L.mic_hip_mic2_decompress_batch.argtypes = [C.POINTER(Mic2DecJob), C.c_int, C.POINTER(Mic2BatchStats)]
+    L.mic_hip_mic2_batch_plan.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mic_hip_session_mic2_encode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Mic2Volume), C.c_int, C.POINTER(C.c_void_p), C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(Mic2BatchStats)]
+    L.mic_hip_session_mic2_decode.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Mic2BatchStats)]
     _strip_crop_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(StripCropStats)]
     L.mic_hip_strips_crop_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
@@ -760,6 +795,95 @@ def decompress_frame(compressed, frame_idx: int) -> np.ndarray:
     if rc:
         _raise(rc, "decompress_frame")
     return out.reshape(h.value, w.value)
+
+
+def mic2_bound(width: int, height: int, nframes: int) -> int:
+    """MIC_HIP_MIC2_BOUND: the capacity that always suffices for a MIC2 file of either pipeline"""
+    return 20 + nframes * (8 + _frame_bound(width * height))
+
+
+def _mic2_stats(bs) -> dict:
+    return dict(units=bs.units, slabs=bs.slabs, volumes_done=bs.volumes_done)
+
+
+def mic2_batch_plan(whn, budget_bytes: int = 0, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """mic_hip_mic2_batch_plan: the sub-batch cuts [0, ..., units] over the units of the volumes whn = [(width, height, nframes)],
+    volume by volume and frame by frame, and the number of units; a batch call over these volumes runs len(cuts) - 1 chains.
+    budget_bytes 0: the default workspace ceiling.  Needs no device.  cap: room for that many cuts (default: as many as it takes);
+    too few raises MicError (MIC_ERR_CAPACITY) whose ``ncuts`` and ``nunits`` attributes are the counts."""
+    a = np.ascontiguousarray(np.asarray(whn, dtype=np.int64).reshape(-1, 3).astype(np.int32))
+    nc, nu = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        rc = lib().mic_hip_mic2_batch_plan(a.ctypes.data, len(a), int(budget_bytes), None, 0, C.byref(nc), C.byref(nu))
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "mic2_batch_plan")
+        cap = nc.value
+    cuts = np.zeros(max(cap, 1), dtype=np.uint32)
+    rc = lib().mic_hip_mic2_batch_plan(a.ctypes.data, len(a), int(budget_bytes), cuts.ctypes.data, cap, C.byref(nc), C.byref(nu))
+    if rc:
+        e = MicError(rc, "mic2_batch_plan")
+        e.ncuts, e.nunits = nc.value, nu.value
+        raise e
+    return cuts[: nc.value].copy(), nu.value
+
+
+def compress_multi_frame_batch(volumes: Sequence, max_values, temporal, outs: Optional[Sequence[np.ndarray]] = None,
+                               caps: Optional[Sequence[Optional[int]]] = None):
+    """mic_hip_mic2_compress_batch: every volume -- an (nframes, height, width) uint16 array; None: a NULL pointer -- as
+    compress_multi_frame writes it, independent or temporal per volume (`max_values` and `temporal`: one value, or one per volume),
+    all through shared sub-batches of the unit codec.  outs: the callers' output buffers (e.g. from host_alloc); caps: a capacity
+    per volume other than the buffer's.  A volume fails alone.
+    -> ([(status, failed frame or -1, file bytes or None)], dict(units, slabs, volumes_done))"""
+    n = len(volumes)
+    maxv = list(max_values) if hasattr(max_values, "__len__") else [max_values] * n
+    temp = list(temporal) if hasattr(temporal, "__len__") else [temporal] * n
+    arrs = [None if v is None else _u16(v) for v in volumes]
+    jobs = (Mic2EncJob * max(n, 1))()
+    bufs = []
+    for i, a in enumerate(arrs):
+        nf, h, w = (a.shape if a is not None else (1, 1, 1))
+        out = outs[i] if outs is not None else np.empty(mic2_bound(w, h, nf), dtype=np.uint8)
+        bufs.append(out)
+        cap = out.size if caps is None or caps[i] is None else caps[i]
+        jobs[i] = Mic2EncJob(None if a is None else a.ctypes.data, w, h, nf, int(maxv[i]), int(bool(temp[i])), out.ctypes.data, cap, 0, 0, -1)
+    bs = Mic2BatchStats()
+    rc = lib().mic_hip_mic2_compress_batch(jobs, n, C.byref(bs))
+    if rc:
+        _raise(rc, "compress_multi_frame_batch")
+    return [(jobs[i].status, jobs[i].failed_frame, bufs[i][: jobs[i].out_len].tobytes() if jobs[i].status == MIC_OK else None)
+            for i in range(n)], _mic2_stats(bs)
+
+
+def decompress_multi_frame_batch(files: Sequence, outs: Optional[Sequence[np.ndarray]] = None):
+    """mic_hip_mic2_decompress_batch: every MIC2 file (None: a NULL pointer) as decompress_multi_frame reads it, both pipelines,
+    all through shared sub-batches of the unit codec.  outs: the callers' uint16 output buffers (default: sized from the headers).
+    A volume fails alone.
+    -> ([(status, failed frame or -1, (width, height, nframes, temporal) of the header, (nframes, height, width) array or None)],
+        dict(units, slabs, volumes_done))"""
+    n = len(files)
+    arrs = [None if f is None else _bytes_arr(f) for f in files]
+    jobs = (Mic2DecJob * max(n, 1))()
+    bufs = []
+    for i, c in enumerate(arrs):
+        px = 1
+        if c is not None and outs is None:
+            w, h, nf, t = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            if lib().mic_hip_mic2_info(c.ctypes.data, c.size, C.byref(w), C.byref(h), C.byref(nf), C.byref(t)) == MIC_OK:
+                px = max(nf.value, 0) * max(w.value, 0) * max(h.value, 0)
+        out = outs[i] if outs is not None else np.empty(max(px, 1), dtype=np.uint16)
+        bufs.append(out)
+        jobs[i] = Mic2DecJob(None if c is None else c.ctypes.data, 0 if c is None else c.size, out.ctypes.data, out.size)
+    bs = Mic2BatchStats()
+    rc = lib().mic_hip_mic2_decompress_batch(jobs, n, C.byref(bs))
+    if rc:
+        _raise(rc, "decompress_multi_frame_batch")
+    res = []
+    for i in range(n):
+        j = jobs[i]
+        px = j.nframes * j.height * j.width
+        res.append((j.status, j.failed_frame, (j.width, j.height, j.nframes, j.temporal),
+                    bufs[i][:px].reshape(j.nframes, j.height, j.width) if j.status == MIC_OK else None))
+    return res, _mic2_stats(bs)
 
 
 def _crop_xyz(xyz) -> np.ndarray:
@@ -1944,6 +2068,59 @@ class Session:
         if rc:
             _raise(rc, "session_mic2_multi_read_crops")
         return st, bad, stats
+
+    def mic2_encode(self, d_frames: int, vols, heads: bool = True):
+        """mic_hip_session_mic2_encode: the volumes vols = [(px_off, width, height, nframes, max_value, temporal)] that lie at
+        d_frames + px_off (uint16 units) on the session's device, each to a complete MIC2 file that stays there.
+        -> (d_files: the device address of the files, back to back, valid until the session's next call; offsets: uint64 array of
+            len(vols) + 1, file v at offsets[v] .. offsets[v + 1], empty for a failed volume; heads: per volume the first
+            20 + 8 * nframes bytes of its file, None for a failed one (all None with heads=False); status and failed frame per
+            volume; dict(units, slabs, volumes_done))"""
+        n = len(vols)
+        va = (Mic2Volume * max(n, 1))()
+        for i, v in enumerate(vols):
+            va[i] = Mic2Volume(int(v[0]), int(v[1]), int(v[2]), int(v[3]), int(v[4]), int(bool(v[5])))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        bad = np.full(max(n, 1), -1, dtype=np.int32)
+        hb = np.zeros(sum(20 + 8 * max(int(v[3]), 0) for v in vols) + 1, dtype=np.uint8) if heads else None
+        d = C.c_void_p()
+        bs = Mic2BatchStats()
+        rc = lib().mic_hip_session_mic2_encode(self._h, int(d_frames) or None, va, n, C.byref(d), offs.ctypes.data,
+                                               None if hb is None else hb.ctypes.data, 0 if hb is None else hb.size - 1,
+                                               st.ctypes.data, bad.ctypes.data, C.byref(bs))
+        if rc:
+            _raise(rc, "session_mic2_encode")
+        hs, at = [], 0
+        for i, v in enumerate(vols):
+            if hb is None or st[i] != MIC_OK:
+                hs.append(None)
+                continue
+            hs.append(hb[at: at + 20 + 8 * int(v[3])].tobytes())
+            at += 20 + 8 * int(v[3])
+        return d.value or 0, offs, hs, st[:n].copy(), bad[:n].copy(), _mic2_stats(bs)
+
+    def mic2_decode(self, heads, d_files, lens, d_frames_out: int, px_off, out_cap_px: int):
+        """mic_hip_session_mic2_decode: the MIC2 files that lie on the session's device -- heads[v] = the first 20 + 8 * nframes
+        bytes of volume v (host), d_files[v] = the device address of the whole file, at any byte alignment, lens[v] its length --
+        each to d_frames_out + px_off[v] (uint16 units) of a device buffer of out_cap_px samples.
+        -> (status per volume, failed frame per volume, dict(units, slabs, volumes_done))"""
+        harrs, hptrs, hlens = _volume_table(heads)
+        dptrs = np.asarray([int(p or 0) for p in d_files], dtype=np.uintp)
+        flens = np.asarray([int(n) for n in lens], dtype=np.uintp)
+        offs = np.asarray([int(o) for o in px_off], dtype=np.uint64)
+        n = len(harrs)
+        if not (n == dptrs.size == flens.size == offs.size):
+            raise ValueError("heads, d_files, lens and px_off must name the same volumes")
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        bad = np.full(max(n, 1), -1, dtype=np.int32)
+        bs = Mic2BatchStats()
+        rc = lib().mic_hip_session_mic2_decode(self._h, hptrs.ctypes.data, hlens.ctypes.data, dptrs.ctypes.data, flens.ctypes.data, n,
+                                               int(d_frames_out) or None, offs.ctypes.data, int(out_cap_px),
+                                               st.ctypes.data, bad.ctypes.data, C.byref(bs))
+        if rc:
+            _raise(rc, "session_mic2_decode")
+        return st[:n].copy(), bad[:n].copy(), _mic2_stats(bs)
 
     def strips_read_crops(self, heads, d_files, lens, xyf, cw: int, ch: int, d_out: int, out_cap: int):
         """strips_read_crops of PICS / PICA files that lie on the session's device: heads[f] = strips_head(file f) (host),

@@ -13,6 +13,7 @@
 #include "mic_session.h"
 #include "mic_staged.h"
 #include <chrono>
+#include <climits>
 
 #include <atomic>
 #include <deque>
@@ -750,6 +751,168 @@ int rgb_decode_host(mic_hip_session *s, std::vector<RgbDecRun> &J, int j0, int j
     });
 }
 
+// ============================================================================ MIC2: many volumes per call (mic_mic2_batch.hip)
+// The units of a shard's volumes -- volume order, then frame order -- are cut into sub-batches by their sizes alone
+// (mic2_batch_cuts), and the sub-batches are the PARTS of run_staged: the call runs exactly the chains the planner
+// (mic_hip_mic2_batch_plan) counts, and MIC_HIP_PIPELINE_PARTS has no say here.  A part's frames lie back to back in its staging half.
+struct Mic2Count {                                     // what the shards of a call add up
+    std::mutex mu; uint64_t slabs = 0;
+    void add(uint64_t n) { std::lock_guard<std::mutex> lk(mu); slabs += n; }
+};
+struct Mic2Run { int vol, i0, i1, f0; uint64_t off; };  // units [i0, i1) of a part (counted from its first) are frames f0 .. of volume vol; off: where frame f0 lies in the part's pixels
+struct Mic2EncVol { mic_hip_mic2_enc_job *j; size_t npx; DestRun dst; std::vector<uint32_t> len; int32_t status = MIC_OK, failed = -1; };
+struct Mic2DecVol {
+    mic_hip_mic2_dec_job *j; Mic2Head m; size_t npx;
+    int32_t status = MIC_OK, failed = -1;
+    const uint16_t *d_last = nullptr;                  // where the part before left the volume's last frame so far: the next part's carry
+};
+struct Mic2Part { std::vector<Mic2Run> runs; int nb = 0; size_t px = 0; };
+// the parts of volumes [v0, v1) with n(v) frames of npx(v) pixels; lead(v): a run that starts behind frame 0 keeps a frame's room in front of it
+template <class N, class P, class L>
+std::vector<Mic2Part> mic2_parts(int v0, int v1, N &&n, P &&npx, L &&lead) {
+    struct Unit { int vol, frame; };
+    std::vector<Unit> un; std::vector<size_t> px;
+    for (int v = v0; v < v1; v++) for (int f = 0; f < n(v); f++) { un.push_back(Unit{ v, f }); px.push_back(npx(v)); }
+    const std::vector<size_t> cuts = mic2_batch_cuts(px, kWorkspaceBudget);
+    std::vector<Mic2Part> parts(cuts.size() - 1);
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        Mic2Part &p = parts[b];
+        p.nb = (int)(cuts[b + 1] - cuts[b]);
+        for (int i = 0; i < p.nb;) {
+            const Unit &u = un[cuts[b] + (size_t)i];
+            int e = i + 1;
+            while (e < p.nb && un[cuts[b] + (size_t)e].vol == u.vol) e++;
+            if (u.frame > 0 && lead(u.vol)) p.px += px[cuts[b] + (size_t)i];
+            p.runs.push_back(Mic2Run{ u.vol, i, e, u.frame, (uint64_t)p.px });
+            p.px += (size_t)(e - i) * px[cuts[b] + (size_t)i];
+            i = e;
+        }
+    }
+    return parts;
+}
+
+// volumes V[v0 .. v1) (arguments fine) on session s
+int mic2_encode_host(mic_hip_session *s, std::vector<Mic2EncVol> &V, int v0, int v1, Mic2Count &count) {
+    if (v0 >= v1) return MIC_OK;
+    int rc = s->ensure(1, 1);                                             // (the stream)
+    if (rc) return rc;
+    // a residual needs the ORIGINAL frame before it: a part that starts inside a temporal volume uploads that frame in front
+    const std::vector<Mic2Part> parts = mic2_parts(v0, v1, [&](int v) { return V[(size_t)v].j->nframes; }, [&](int v) { return V[(size_t)v].npx; },
+                                                   [&](int v) { return V[(size_t)v].j->temporal != 0; });
+    count.add(parts.size());
+    for (size_t k = 0; k < parts.size(); k++) trace_part("mic2 encode", k, parts.size(), "units", 0, parts[k].nb, parts[k].px);
+    DevBuf *in[2] = { &s->io_px, &s->io_px2 };
+    IoReq *prev = nullptr;                                // the download of the part before: keep_packed waits for it
+    return run_staged(parts.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const Mic2Part &p = parts[k];
+        int r = in[half]->reserve(p.px * 2 + 64);
+        for (size_t q = 0; q < p.runs.size() && r == MIC_OK; q++) {
+            const Mic2Run &run = p.runs[q];
+            const Mic2EncVol &v = V[(size_t)run.vol];
+            const size_t lead = (run.f0 > 0 && v.j->temporal) ? 1 : 0;
+            r = io_submit(up, s->device, (uint16_t *)in[half]->p + run.off - lead * v.npx, v.j->frames + ((size_t)run.f0 - lead) * v.npx,
+                          ((size_t)(run.i1 - run.i0) + lead) * v.npx * 2, true);
+        }
+        return r;
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        const Mic2Part &p = parts[k];
+        std::vector<Mic2EncUnit> u((size_t)p.nb);
+        for (const Mic2Run &run : p.runs) {
+            const Mic2EncVol &v = V[(size_t)run.vol];
+            for (int i = run.i0; i < run.i1; i++)
+                u[(size_t)i] = Mic2EncUnit{ (const uint16_t *)in[half]->p + run.off + (size_t)(i - run.i0) * v.npx, v.j->width, v.j->height, v.j->max_value,
+                                            (uint16_t)(v.j->temporal && run.f0 + (i - run.i0) > 0) };
+        }
+        std::vector<uint64_t> offs((size_t)p.nb + 1); std::vector<int32_t> st((size_t)p.nb);
+        const uint8_t *d_blobs = nullptr;
+        int rc = mic2_batch_encode_units(s, u.data(), p.nb, &d_blobs, offs.data(), st.data());
+        if (rc == MIC_OK) rc = keep_packed(s, prev);
+        if (rc != MIC_OK) return rc;
+        prev = &down;
+        for (const Mic2Run &run : p.runs) {               // per volume: its streams of this part, one transfer
+            Mic2EncVol &v = V[(size_t)run.vol];
+            for (int i = run.i0; i < run.i1; i++) {
+                const int f = run.f0 + (i - run.i0);
+                v.len[(size_t)f] = (uint32_t)(offs[(size_t)i + 1] - offs[(size_t)i]);
+                if (st[(size_t)i] != MIC_OK && v.status == MIC_OK) { v.status = st[(size_t)i]; v.failed = f; }   // the first failing frame names the error
+            }
+            if (v.status != MIC_OK) continue;
+            rc = v.dst.append(down, s->device, d_blobs + offs[(size_t)run.i0], (size_t)(offs[(size_t)run.i1] - offs[(size_t)run.i0]));
+            if (v.dst.cap_fail) v.status = MIC_ERR_CAPACITY;
+            if (rc) return rc;
+        }
+        return MIC_OK;
+    });
+}
+
+int mic2_decode_host(mic_hip_session *s, std::vector<Mic2DecVol> &V, int v0, int v1, Mic2Count &count) {
+    if (v0 >= v1) return MIC_OK;
+    int rc = s->ensure(1, 1);
+    if (rc) return rc;
+    const std::vector<Mic2Part> parts = mic2_parts(v0, v1, [&](int v) { return V[(size_t)v].m.n; }, [&](int v) { return V[(size_t)v].npx; },
+                                                   [](int) { return false; });
+    count.add(parts.size());
+    for (size_t k = 0; k < parts.size(); k++) trace_part("mic2 decode", k, parts.size(), "units", 0, parts[k].nb, parts[k].px);
+    DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
+    auto stream_of = [&](const Mic2DecVol &v, int f, uint32_t *len) {
+        *len = get_u32(v.m.table + 8 * (size_t)f + 4);
+        return v.j->compressed + 20 + 8 * (size_t)v.m.n + get_u32(v.m.table + 8 * (size_t)f);
+    };
+    std::vector<uint64_t> begins[2];                                      // where a part's streams lie in its half
+    return run_staged(parts.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const Mic2Part &p = parts[k];
+        std::vector<uint64_t> &bg = begins[half];
+        bg.assign((size_t)p.nb + 1, 0);
+        std::vector<const uint8_t *> src((size_t)p.nb);
+        for (const Mic2Run &run : p.runs)
+            for (int i = run.i0; i < run.i1; i++) {
+                uint32_t len;
+                src[(size_t)i] = stream_of(V[(size_t)run.vol], run.f0 + (i - run.i0), &len);
+                bg[(size_t)i + 1] = bg[(size_t)i] + len;
+            }
+        int r = in[half]->reserve((size_t)bg[(size_t)p.nb] + 64);
+        for (int i = 0; i < p.nb && r == MIC_OK;) {                       // streams that are neighbours in a file go up in one transfer
+            int e = i + 1;
+            while (e < p.nb && src[(size_t)e] == src[(size_t)i] + (bg[(size_t)e] - bg[(size_t)i])) e++;
+            r = io_submit(up, s->device, (uint8_t *)in[half]->p + bg[(size_t)i], src[(size_t)i], (size_t)(bg[(size_t)e] - bg[(size_t)i]), true);
+            i = e;
+        }
+        return r;
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        const Mic2Part &p = parts[k];
+        const std::vector<uint64_t> &bg = begins[half];
+        int rc = outb[half]->reserve(p.px * 2 + 64);
+        if (rc) return rc;
+        uint16_t *d_px = (uint16_t *)outb[half]->p;
+        std::vector<Mic2DecUnit> u((size_t)p.nb);
+        for (const Mic2Run &run : p.runs) {
+            const Mic2DecVol &v = V[(size_t)run.vol];
+            for (int i = run.i0; i < run.i1; i++)
+                u[(size_t)i] = Mic2DecUnit{ (const uint8_t *)in[half]->p + bg[(size_t)i], (uint32_t)(bg[(size_t)i + 1] - bg[(size_t)i]), v.m.w, v.m.h,
+                                            d_px + run.off + (size_t)(i - run.i0) * v.npx, (uint32_t)(v.m.temporal && run.f0 + (i - run.i0) > 0) };
+        }
+        std::vector<int32_t> st((size_t)p.nb);
+        if ((rc = mic2_batch_decode_units(s, u.data(), p.nb, st.data()))) return rc;
+        std::vector<Mic2DecSpan> spans;
+        for (const Mic2Run &run : p.runs) {
+            Mic2DecVol &v = V[(size_t)run.vol];
+            for (int i = run.i0; i < run.i1 && v.status == MIC_OK; i++)
+                if (st[(size_t)i] != MIC_OK) { v.status = st[(size_t)i]; v.failed = run.f0 + (i - run.i0); }
+            // the running sum of a part that starts inside a temporal volume goes on from the frame the part before left in the other half
+            if (v.m.temporal) spans.push_back(Mic2DecSpan{ v.d_last, d_px + run.off, (uint32_t)v.npx, run.i0, run.i1 - run.i0, run.f0,
+                                                           v.status == MIC_OK ? INT_MAX : v.failed, 0 });
+            v.d_last = d_px + run.off + (size_t)(run.i1 - run.i0 - 1) * v.npx;
+        }
+        if ((rc = mic2_batch_accumulate(s, spans.data(), (int)spans.size()))) return rc;
+        for (const Mic2Run &run : p.runs) {
+            const Mic2DecVol &v = V[(size_t)run.vol];
+            if (v.status != MIC_OK) continue;
+            if ((rc = io_submit(down, s->device, d_px + run.off, v.j->frames_out + (size_t)run.f0 * v.npx, (size_t)(run.i1 - run.i0) * v.npx * 2, false))) return rc;
+        }
+        return MIC_OK;
+    });
+}
+
 }  // namespace
 
 namespace micapi {
@@ -1175,6 +1338,79 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
     }
     if ((rc = over_devices(first, [&](mic_hip_session *s, int f0, int f1) { return decode_groups(s, G, U, U[(size_t)f0].group, U[(size_t)f1 - 1].group + 1); }))) return rc;
     for (const DecGroup &g : G) if (g.status != MIC_OK) return g.status;
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// ---- MIC2: many volumes per call, both pipelines (mic_mic2_batch.hip) ---------------------------------
+int mic_hip_mic2_compress_batch(mic_hip_mic2_enc_job *jobs, int njobs, mic_hip_mic2_batch_stats *stats) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (stats) *stats = mic_hip_mic2_batch_stats{ 0, 0, 0 };
+    if (njobs == 0) return MIC_OK;
+    std::vector<Mic2EncVol> V;
+    uint64_t units = 0;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_mic2_enc_job &j = jobs[i];
+        j.out_len = 0; j.status = MIC_OK; j.failed_frame = -1;
+        if (!j.frames || !j.out || j.width <= 0 || j.height <= 0 || j.nframes <= 0 || j.temporal > 1) { j.status = MIC_ERR_ARGS; continue; }
+        const size_t npx = (size_t)j.width * (size_t)j.height, header = 20 + (size_t)j.nframes * 8;
+        if (npx > ((size_t)1 << 28)) { j.status = MIC_ERR_UNSUPPORTED; continue; }
+        if (j.out_cap < header) { j.status = MIC_ERR_CAPACITY; continue; }
+        V.push_back(Mic2EncVol{ &j, npx, DestRun{ j.out, j.out_cap, header }, std::vector<uint32_t>((size_t)j.nframes, 0) });
+        units += (uint64_t)j.nframes;
+    }
+    if (V.empty()) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    Mic2Count count;
+    if ((rc = over_devices((int)V.size(), [&](int v) { return (uint64_t)V[(size_t)v].npx * (uint64_t)V[(size_t)v].j->nframes; },
+                           [&](mic_hip_session *s, int v0, int v1) { return mic2_encode_host(s, V, v0, v1, count); }))) return rc;
+    uint64_t done = 0;
+    for (Mic2EncVol &v : V) {
+        mic_hip_mic2_enc_job &j = *v.j;
+        if (v.status == MIC_OK && v.dst.written > 0xFFFFFFFFull) v.status = MIC_ERR_UNSUPPORTED;   // u32 offsets, multiframe.go:75-80
+        j.status = v.status; j.failed_frame = v.failed;
+        if (v.status != MIC_OK) continue;
+        mic2_write_head(j.out, j.width, j.height, j.nframes, j.temporal != 0, v.len.data());
+        j.out_len = v.dst.hdr + v.dst.written;
+        done++;
+    }
+    if (stats) *stats = mic_hip_mic2_batch_stats{ units, count.slabs, done };
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_mic2_decompress_batch(mic_hip_mic2_dec_job *jobs, int njobs, mic_hip_mic2_batch_stats *stats) try {
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (stats) *stats = mic_hip_mic2_batch_stats{ 0, 0, 0 };
+    if (njobs == 0) return MIC_OK;
+    std::vector<Mic2DecVol> V;
+    uint64_t units = 0;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_mic2_dec_job &j = jobs[i];
+        j.width = j.height = j.nframes = j.temporal = 0; j.status = MIC_OK; j.failed_frame = -1;
+        if (!j.compressed || !j.frames_out) { j.status = MIC_ERR_ARGS; continue; }
+        Mic2Head m;
+        if (mic_hip_mic2_info(j.compressed, j.compressed_len, &m.w, &m.h, &m.n, &m.temporal) == MIC_OK) { j.width = m.w; j.height = m.h; j.nframes = m.n; j.temporal = m.temporal; }
+        if ((j.status = mic2_batch_parse(j.compressed, j.compressed_len, j.compressed_len, m)) != MIC_OK) continue;
+        const size_t npx = (size_t)m.w * (size_t)m.h;
+        if (npx * (size_t)m.n > j.frames_cap_px) { j.status = MIC_ERR_CAPACITY; continue; }
+        for (int f = 0; f < m.n && j.status == MIC_OK; f++) {                // multiframe.go:137-139
+            const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)f), bl = get_u32(m.table + 8 * (size_t)f + 4);
+            if (bl == 0 || off + bl > m.file_len) { j.status = MIC_ERR_CORRUPT; j.failed_frame = f; }
+        }
+        if (j.status != MIC_OK) continue;
+        Mic2DecVol v; v.j = &j; v.m = m; v.npx = npx;
+        V.push_back(v);
+        units += (uint64_t)m.n;
+    }
+    if (V.empty()) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    Mic2Count count;
+    if ((rc = over_devices((int)V.size(), [&](int v) { return (uint64_t)V[(size_t)v].npx * (uint64_t)V[(size_t)v].m.n; },
+                           [&](mic_hip_session *s, int v0, int v1) { return mic2_decode_host(s, V, v0, v1, count); }))) return rc;
+    uint64_t done = 0;
+    for (const Mic2DecVol &v : V) { v.j->status = v.status; v.j->failed_frame = v.failed; done += v.status == MIC_OK; }
+    if (stats) *stats = mic_hip_mic2_batch_stats{ units, count.slabs, done };
     return MIC_OK;
 } MIC_ABI_CATCH
 

@@ -178,6 +178,7 @@ struct mic_hip_session {
     std::vector<uint8_t> wsi_host_bytes;   // MIC3 patches from blobs: a sub-batch's stream bytes on their way up; kept, so that a loop of calls touches the same pages
     DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
     DevBuf rgb_payload, rgb_payload2;      // ... and its assembled blobs: two halves, one goes down while the other is written
+    DevBuf mic2_files, mic2_payload;       // mic_hip_session_mic2_encode: the call's MIC2 files back to back; the streams of its sub-batches until they are assembled (mic_mic2_batch.hip)
     PinnedU64 rgb_pin;                     // ... the host's copy of the plane statistics / the blob heads
     PinnedUnits h_units;
     std::vector<uint64_t> h_off;
@@ -332,13 +333,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2 };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -419,6 +420,32 @@ size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // Units [i0, return) of the next sub-batch of a list of units of px[i] pixels each, for the readers that decode units of mixed sizes
 // into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip)
 size_t next_strip_cut(const std::vector<size_t> &px, size_t i0);
+size_t next_strip_cut(const std::vector<size_t> &px, size_t i0, size_t budget);   // ... under a ceiling of `budget` bytes instead of the default
+// MIC2 whole-volume batches (mic_mic2_batch.hip; the host doors: mic_host_io.hip).  The units of a call's volumes -- volume order, then
+// frame order -- go through the unit codec in sub-batches cut by their sizes alone: next_strip_cut's rule under `budget` bytes.
+// -> [0, ..., px.size()]
+std::vector<size_t> mic2_batch_cuts(const std::vector<size_t> &px, size_t budget);
+// One unit of an encode sub-batch: the frame at `cur` on the session's device.  residual: coded as TemporalDeltaEncode against the
+// frame that lies directly in front of it (cur - w * h: the volume's own predecessor, or the lead frame a host part uploads).
+struct Mic2EncUnit { const uint16_t *cur; int32_t w, h; uint16_t max_value, residual; };
+// nb units through ONE encode chain (k_mic2_residual in front); on return the streams of the units that coded lie
+// packed at *d_blobs + offs[i] .. offs[i + 1] (s->packed, until the session's next chain), st[i] = the unit's code.
+int mic2_batch_encode_units(mic_hip_session *s, const Mic2EncUnit *u, int nb, const uint8_t **d_blobs, uint64_t *offs, int32_t *st);
+// One unit of a decode sub-batch: its stream on the session's device (64 readable bytes behind it); a frame unit decodes to `out`, a
+// residual unit (out unused) into its symbol slab.
+struct Mic2DecUnit { const uint8_t *comp; uint32_t len; int32_t w, h; uint16_t *out; uint32_t residual; };
+// What a sub-batch holds of one temporal volume: its units u0 .. u0 + nb - 1 are the volume's frames f0 .. f0 + nb - 1, which go to
+// dst, dst + npx, ...; carry = frame f0 - 1 (unused when f0 == 0: unit u0 decoded frame 0 into dst); fbad = the volume's first failed
+// frame so far (INT_MAX: none) -- the sum stops in front of it.
+struct Mic2DecSpan { const uint16_t *carry; uint16_t *dst; uint32_t npx; int32_t u0, nb, f0, fbad, pad; };
+// nb units through ONE decode chain, complete on return with st[i] = the unit's code; then, for the temporal spans of that chain
+// (built from st), the running sums -- one launch, complete on return.
+int mic2_batch_decode_units(mic_hip_session *s, const Mic2DecUnit *u, int nb, int32_t *st);
+int mic2_batch_accumulate(mic_hip_session *s, const Mic2DecSpan *spans, int nspans);
+// a MIC2 file's 20-byte header and frame table (multiframe.go:49-91) from its frames' stream lengths
+void mic2_write_head(uint8_t *out, int w, int h, int n, bool temporal, const uint32_t *lens);
+// what the decode doors ask of a file's head before a frame is looked at (mic_hip_mic2_decompress's checks): MIC_OK, or the volume's code
+int mic2_batch_parse(const uint8_t *head, size_t head_len, uint64_t file_len, Mic2Head &m);
 // RGB batches (mic_rgb_batch.hip): many images of different sizes per call, CompressRGB / DecompressRGB (rgbcompress.go:25-33) of each.
 // One image of a sub-batch on the encode side: its RGB at d_rgb + rgb_off; container 1 = a MICR header in front of its blob.
 // status on entry: not MIC_OK = skip the image.  On return: status / failed_plane (0 Y, 1 Co, 2 Cg, -1 not a plane's), and the

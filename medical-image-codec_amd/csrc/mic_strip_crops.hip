@@ -119,15 +119,16 @@ int strips_crop_args(const void *files, const size_t *lens, int nfiles, const in
 
 // Units [i0, i1) of the next sub-batch: as many as the workspace ceiling holds of the largest of them -- a unit's tier-2 slabs and its
 // strip in the staging slab, as mic2_frames_per_batch counts a frame -- and at most what one launch chain takes.
-size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0) {
+size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0, size_t budget) {
     size_t max_px = 0, i1 = i0;
     while (i1 < px.size()) {
         const size_t mp = std::max(max_px, px[i1]);
-        if (i1 > i0 && (i1 - i0 + 1 > kWorkspaceBudget / (unit_ws_bytes(mp) + 2 * mp) || i1 - i0 >= 65535)) break;
+        if (i1 > i0 && (i1 - i0 + 1 > budget / (unit_ws_bytes(mp) + 2 * mp) || i1 - i0 >= 65535)) break;
         max_px = mp; i1++;
     }
     return i1;
 }
+size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0) { return next_strip_cut(px, i0, kWorkspaceBudget); }
 
 namespace {
 
