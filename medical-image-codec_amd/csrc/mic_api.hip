@@ -696,6 +696,71 @@ int mic_hip_debug_fetch_tok(mic_hip_session *s, int i, void *dst, size_t n) try 
     HIP_TRY(hipMemcpy(dst, s->h_units[(size_t)i].tok, n * 2, hipMemcpyDeviceToHost));
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): the table stage's route record of unit i (MicUnit.tb_route: MIC_TBR_* bits, nbig << 16,
+// mic_dev.h) after a *_finish
+int mic_hip_debug_tab_route(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    *out = s->h_units[(size_t)i].tb_route;
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug probe (not in the public header): the head of one of unit i's table slabs after a *_finish.
+// which: 0 state_tab (u32), 1 tt_nb (u32), 2 tt_find (i32), 3 tab_sym (u16), 4 norm (i32)
+int mic_hip_debug_fetch_table(mic_hip_session *s, int i, int which, void *dst, size_t bytes) try {
+    if (!s || !dst || i < 0 || i >= s->n_last || which < 0 || which > 4) return MIC_ERR_ARGS;
+    const MicUnit &u = s->h_units[(size_t)i];
+    const void *slabs[5] = { u.state_tab, u.tt_nb, u.tt_find, u.tab_sym, u.norm };
+    if (bytes > (size_t)u.tab_cap * (which == 3 ? 2 : 4)) return MIC_ERR_ARGS;
+    { const int arc = s->activate(); if (arc) return arc; }
+    if (bytes) HIP_TRY(hipMemcpy(dst, slabs[which], bytes, hipMemcpyDeviceToHost));
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug doors (not in the public header): many bare FSE units side by side in ONE launch chain of the caller's session, laid out in
+// tier 2 as mic_hip_fse_compress_u16_ex / mic_hip_fse_decompress_u16_ex lay out their one (tests/test_gpu_table_routes.py).
+// Encode: unit i codes counts[i] symbols from d_symbols + sym_off[i] with FSECompressU16* semantics (mode 1, no fallback chain),
+// flavour flavours[i], ScratchU16.TableLog req_tl[i]; mic_hip_session_encode_finish then returns blobs, offsets and statuses.
+int mic_hip_debug_fse_encode_enqueue(mic_hip_session *s, const uint16_t *d_symbols, const uint64_t *sym_off, const uint32_t *counts,
+                                     const int32_t *flavours, const int32_t *req_tl, int n) try {
+    if (!s || !d_symbols || !sym_off || !counts || !flavours || !req_tl || n <= 0 || n > 65535) return MIC_ERR_ARGS;
+    size_t most = 0;
+    for (int i = 0; i < n; i++) {
+        const int f = flavours[i];
+        if (!(f == 1 || f == 2 || f == 4 || f == 8 || f == 108) || req_tl[i] < 0 || req_tl[i] > MIC_MAX_TABLELOG) return MIC_ERR_ARGS;
+        if (counts[i] == 0 || counts[i] > (1u << 30)) return MIC_ERR_ARGS;
+        most = std::max(most, (size_t)counts[i]);
+    }
+    int rc = s->activate();
+    if (rc) return rc;
+    s->retry.kind = 0;
+    if ((rc = s->lay_out(n, (most + 3) / 4 + 16))) return rc;
+    for (int i = 0; i < n; i++) {
+        MicUnit &u = s->h_units[(size_t)i];
+        u.px_in = d_symbols + sym_off[i]; u.w = (int32_t)counts[i]; u.h = 1; u.max_value = 0;
+        u.nstates = (uint16_t)flavours[i]; u.mode = 1; u.no_fallback = 1; u.req_tl = (uint32_t)req_tl[i];
+    }
+    return s->run_encode([&] { mic_launch_encode((MicUnit *)s->units.p, n, s->stream, s->variant, nullptr); });
+} MIC_ABI_CATCH
+// Decode: unit i is the FSE stream at d_blobs + [begins[i], ends[i]) (FSEDecompressU16Auto), at most caps[i] symbols;
+// mic_hip_session_decode_finish returns the statuses, mic_hip_debug_unit the counts and mic_hip_debug_fetch_tok the symbols.
+int mic_hip_debug_fse_decode_enqueue(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *begins, const uint64_t *ends,
+                                     const uint32_t *caps, int n) try {
+    if (!s || !d_blobs || !begins || !ends || !caps || n <= 0 || n > 65535) return MIC_ERR_ARGS;
+    size_t most = 0;
+    for (int i = 0; i < n; i++) {
+        if (ends[i] <= begins[i] || ends[i] - begins[i] > 0xFFFFFFF0ull || caps[i] > (1u << 30)) return MIC_ERR_ARGS;
+        most = std::max(most, (size_t)caps[i]);
+    }
+    int rc = s->activate();
+    if (rc) return rc;
+    s->retry.kind = 0;
+    if ((rc = s->lay_out(n, (most + 3) / 4 + 16))) return rc;
+    for (int i = 0; i < n; i++) {
+        MicUnit &u = s->h_units[(size_t)i];
+        u.comp_in = d_blobs + begins[i]; u.comp_len = (uint32_t)(ends[i] - begins[i]); u.w = 1; u.h = 1; u.mode = 1;
+        u.tok_cap = (uint32_t)std::min<size_t>(caps[i], u.tok_cap);
+    }
+    return s->run_decode(mic_hip_session::FlagSlab::Idle, [&] {
+        mic_launch_decode((MicUnit *)s->units.p, n, s->stream, s->variant, nullptr, (int *)s->cls.p); });
+} MIC_ABI_CATCH
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled) try {
     if (!s) return MIC_ERR_ARGS;
     s->timer.enabled = enabled != 0;

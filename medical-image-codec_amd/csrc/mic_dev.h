@@ -44,6 +44,28 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 #define MIC_TKP_PACKED          7      // thread-tiles whose eight symbols came from the packed residuals (symbol units: from the vector load)
 #define MIC_TKP_KIND2           8      // thread-tiles that fetched pixel by pixel
 #define MIC_TK_PATHS            9
+// MicUnit.tb_route: which forks of the table stage (mic_tables.hip, mic_tables_par.h, mic_read_ncount) a unit took.  Lane 0 writes it
+// next to the unit's other results.  A unit that fails in k_enc_tables_wg keeps 0; on decode a failing unit keeps what was stored
+// before it failed (a P_DEFER_* bit from k_dec_parse<false>, the parse bits when k_dec_tables_wg refuses the counts): read it with the status.  The upper 16 bits hold tp_build's count of symbols
+// of more than TP_SMALLV slots (0 on the rANS branch, which has no spread).  Predicted by tests/table_routes.py.
+#define MIC_TBR_SMALL           (1u << 0)    // scratch class: 16-bit values in LDS (alphabet <= 8192 symbols, tableLog <= 13)
+#define MIC_TBR_HBM             (1u << 1)    // scratch class: 32-bit values in the unit's HBM slabs
+#define MIC_TBR_RANS            (1u << 2)    // the rANS table branch (flavour 108) instead of tp_build
+// k_enc_tables_wg
+#define MIC_TBR_PRIMARY         (1u << 3)    // the primary normaliser finished the unit
+#define MIC_TBR_N2_PAR          (1u << 4)    // normalizeCount2, weights by the whole group
+#define MIC_TBR_N2_UNIFORM      (1u << 5)    // ... its "uniform" second classification pass was taken (with N2_PAR or N2_SERIAL)
+#define MIC_TBR_N2_SERIAL       (1u << 6)    // ... one of its two serial corner cases: mic_normalize_count2 on one lane
+#define MIC_TBR_W_PAR           (1u << 7)    // header by tb_write_ncount_par
+#define MIC_TBR_W_SERIAL        (1u << 8)    // header by mic_write_ncount on one lane
+// k_dec_parse / k_dec_tables_wg (a deferred unit carries its P_DEFER_* bit and the P_BIG_* bit of the parse that finished it)
+#define MIC_TBR_P_SMALL         (1u << 9)    // parsed by k_dec_parse<false> from its 8 KiB stage
+#define MIC_TBR_P_DEFER_TL      (1u << 10)   // left to <true>: tableLog > 13
+#define MIC_TBR_P_DEFER_LEN     (1u << 11)   // left to <true>: a blob longer than the stage whose header did not end 8 bytes inside it
+#define MIC_TBR_P_DEFER_SYMS    (1u << 12)   // left to <true>: a wholly staged blob with more than 8192 symbols
+#define MIC_TBR_P_BIG_STAGE     (1u << 13)   // parsed by k_dec_parse<true> from its 40 KiB stage
+#define MIC_TBR_P_BIG_HBM       (1u << 14)   // parsed by k_dec_parse<true> starting over from HBM
+#define MIC_TBR_P_WINDOW        (1u << 15)   // the window loop of mic_read_ncount read at least one field (clear: the byte-wise loop read them all)
 
 struct MicUnit {
     // ---- inputs ------------------------------------------------------------------
@@ -111,6 +133,8 @@ struct MicUnit {
                               // MIC_DEC_BY_GL for k_dec_tans_gl, MIC_DEC_BY_SERIAL for k_dec_tans_serial; 0: nobody (tests/test_gpu_decode_classes.py).  Cleared with the
                               // other results: every enqueue's lay_out() starts each descriptor again from MicUnit{}
     uint32_t dbg[16];         // MIC_STAMP builds: shader-clock ticks per kernel phase (tools/stamp_*.py)
+    uint32_t tb_route;        // which forks of the table stage the unit took (MIC_TBR_*), nbig << 16; read by mic_hip_debug_tab_route,
+                              // predicted by tests/table_routes.py
     uint32_t tk_paths[MIC_TK_PATHS];   // encode: which routes k_enc_tokens_wg took through the unit (MIC_TKP_*), written once next to ntok;
                               // read by mic_hip_debug_tok_paths, predicted by tests/tokeniser_paths.py
     // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------

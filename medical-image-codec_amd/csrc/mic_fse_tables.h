@@ -268,11 +268,13 @@ __device__ inline uint32_t mic_rd_u32(const uint8_t *b, uint32_t len, int64_t of
 // (off = P >> 3, bitCount = P & 7, bitStream = the bits from P on), so the window reader is the same machine; the last sixteen
 // bytes -- where the reference's refill rules differ, fsedecompressu16.go:100-160 -- are left to the byte-wise loop below, which
 // takes over from the canonical state.
+// win (optional): set to 1 when the window loop read at least one count field, to 0 when the byte-wise loop read them all.
 template <typename NormT, bool PREZEROED = false>
 __device__ inline int mic_read_ncount(const uint8_t *b, uint32_t len, NormT *norm,
                                       uint32_t *symbol_len_out, uint32_t *tl_out, uint32_t *consumed,
-                                      uint32_t norm_cap, const uint32_t *dw = nullptr, uint32_t boff = 0) {
+                                      uint32_t norm_cap, const uint32_t *dw = nullptr, uint32_t boff = 0, uint32_t *win = nullptr) {
     uint32_t charnum = 0;
+    if (win) *win = 0;
     bool previous0 = false;
     int err = 0;
     int64_t iend = (int64_t)len, off = 0;
@@ -353,6 +355,7 @@ __device__ inline int mic_read_ncount(const uint8_t *b, uint32_t len, NormT *nor
             }
         }
         if (fail) return fail;
+        if (win) *win = charnum != 0 ? 1u : 0u;                           // (charnum only moves behind a field)
         off = (int64_t)(P >> 3); bit_count = (uint32_t)P & 7u;            // the canonical state of the byte-wise reader
         bit_stream = mic_rd_u32(b, len, off, &err) >> bit_count;
         if (err) return MICD_ERR_CORRUPT;

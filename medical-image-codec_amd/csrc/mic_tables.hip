@@ -166,6 +166,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t size = 1u << tl;
     const uint32_t *hist = u.hist;
+    uint32_t route = sizeof(NormT) == 2 ? MIC_TBR_SMALL : MIC_TBR_HBM;  // group-uniform; lane 0 stores it with zero_bits
     MIC_STAMP_BEGIN();
     // ---- normalise, primary method (fsecompressu16.go:524-571), one symbol per thread -----------
     {
@@ -218,7 +219,8 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             s_misc[2] = second; s_misc[3] = (uint32_t)rc;
         }
         __syncthreads();
-        if (s_misc[2]) {
+        if (!s_misc[2]) route |= MIC_TBR_PRIMARY;
+        else {
             // normalizeCount2 (fsecompressu16.go:573-651).  Common for alphabets close to the table size
             // (12-bit frames at tableLog 13), so it runs on the whole group: two classification passes with
             // block reductions, then the weights  (end >> v) - (start >> v)  where `end` is a running sum of
@@ -259,6 +261,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             else {
                 to_distribute = size - distributed;
                 if ((total / to_distribute) > low_one) {                 // uniform
+                    route |= MIC_TBR_N2_UNIFORM;
                     low_one = (total * 3) / (to_distribute * 2);
                     uint32_t d2 = 0; uint64_t sub2 = 0;
                     for (uint32_t s2 = tid; s2 < symbol_len; s2 += TP_THREADS) {
@@ -311,6 +314,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
                     for (uint32_t s2 = tid; s2 < symbol_len; s2 += TP_THREADS) norm[s2] = (NormT)u.norm[s2];
             }
             if (rc2 != MICD_OK) { if (tid == 0) u.status = rc2; return; }
+            route |= serial ? MIC_TBR_N2_SERIAL : MIC_TBR_N2_PAR;
         }
     }
     __threadfence_block();
@@ -331,6 +335,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
         if (rc_par != MICD_ERR_UNSUPPORTED && tid == 0) { if (rc_par == MICD_OK) u.hdr_len = hdr; s_misc[3] = (uint32_t)rc_par; }
         __syncthreads();
     }
+    route |= rc_par != MICD_ERR_UNSUPPORTED ? MIC_TBR_W_PAR : MIC_TBR_W_SERIAL;
     if (rc_par != MICD_ERR_UNSUPPORTED) {
     } else if (tid == 0) {
         int rc = MICD_OK;
@@ -369,7 +374,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             u.tt_nb[s2] = freq | (k0 << 20);
             u.tt_find[s2] = (int32_t)(v > 0 ? (uint32_t)first_visit[s2] : carry_pos + (uint32_t)first_visit[s2]);
         }
-        if (tid == 0) u.zero_bits = 0;
+        if (tid == 0) { u.zero_bits = 0; u.tb_route = route | MIC_TBR_RANS; }
         return;
     }
     // ---- CTable: stateTable via the parallel spread, symbolTT per symbol ------------------------------
@@ -396,8 +401,8 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             u.tt_find[s] = total - v;
         }
     }
-    if (__syncthreads_or((int)zb)) { if (tid == 0) u.zero_bits = 1; }
-    else if (tid == 0) u.zero_bits = 0;
+    const int anyzb = __syncthreads_or((int)zb);
+    if (tid == 0) { u.zero_bits = anyzb ? 1u : 0u; u.tb_route = route | (s_tmp[TP_WAVES] << 16); }   // (tp_build's nbig is still there)
     MIC_STAMP_AT(u, 7);
 }
 
@@ -463,10 +468,12 @@ __device__ void dec_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     const uint32_t size = 1u << tl;
     uint32_t *dt = u.tt_nb; uint16_t *ds = u.tab_sym;
     uint32_t bad = 0, zb = 0;
+    uint32_t route = sizeof(NormT) == 2 ? MIC_TBR_SMALL : MIC_TBR_HBM;
     const int32_t large_limit = (int32_t)(size >> 1);
     for (uint32_t s = tid; s < symbol_len; s += TP_THREADS) if ((int32_t)norm[s] >= large_limit) zb = 1;   // fsedecompressu16.go:214-216
     if (flavour == 108) {
         // buildRansDecTable (ransu16.go:77-135): slots filled in symbol order, positives first, then the -1 symbols
+        route |= MIC_TBR_RANS;
         uint32_t carry_pos = 0, carry_low = 0;
         for (uint32_t base = 0; base < symbol_len; base += TP_THREADS) {
             const uint32_t s = base + tid;
@@ -508,7 +515,11 @@ __device__ void dec_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     }
     const int anybad = __syncthreads_or((int)bad);
     const int anyzb = __syncthreads_or((int)zb);
-    if (tid == 0) { if (anybad) u.status = MICD_ERR_CORRUPT; u.zero_bits = anyzb ? 1u : 0u; }
+    if (tid == 0) {
+        if (anybad) u.status = MICD_ERR_CORRUPT;
+        u.zero_bits = anyzb ? 1u : 0u;
+        u.tb_route |= route | (flavour == 108 ? 0u : s_tmp[TP_WAVES] << 16);   // (beside k_dec_parse's bits; tp_build's nbig is still there)
+    }
 }
 
 // Stream prefix + NCount parse (FSEDecompressU16Auto, fse2state.go:102-116; readNCount, fsedecompressu16.go:48-167).
@@ -547,6 +558,7 @@ __global__ void __launch_bounds__(64) k_dec_parse(MicUnit *units) {
         u.status = MICD_OK; u.ntok = 0;
         int rc = MICD_OK;
         uint32_t flavour = 1, count = 0, off = 0, used = 0, symbol_len = 0, tl = 0;
+        uint32_t win = 0, route = BIG ? MIC_TBR_P_BIG_STAGE : MIC_TBR_P_SMALL, defer = MIC_TBR_P_DEFER_TL;
         do {
             if ((u.mode == 0 && (u.w <= 0 || u.h <= 0)) || !u.comp_in) { rc = MICD_ERR_ARGS; break; }
             if (len >= 2 && s_in[0] == 0xFF) {
@@ -570,24 +582,28 @@ __global__ void __launch_bounds__(64) k_dec_parse(MicUnit *units) {
             // Parse from the staged bytes when that is certain to be identical: the whole blob is staged, or the
             // header ends well inside the stage; otherwise from HBM.
             // (the window reader may look 8 bytes past the bytes it is given: the stage is DP_STAGE + 16 bytes long)
-            if (len <= DP_STAGE) rc = mic_read_ncount<int32_t, true>(s_in + off, len - off, u.norm, &symbol_len, &tl, &used, DP_SYMS, (const uint32_t *)s_in, off);
-            else {
-                rc = mic_read_ncount<int32_t, true>(s_in + off, DP_STAGE - off, u.norm, &symbol_len, &tl, &used, DP_SYMS, (const uint32_t *)s_in, off);
+            if (len <= DP_STAGE) {
+                rc = mic_read_ncount<int32_t, true>(s_in + off, len - off, u.norm, &symbol_len, &tl, &used, DP_SYMS, (const uint32_t *)s_in, off, &win);
+                defer = MIC_TBR_P_DEFER_SYMS;
+            } else {
+                rc = mic_read_ncount<int32_t, true>(s_in + off, DP_STAGE - off, u.norm, &symbol_len, &tl, &used, DP_SYMS, (const uint32_t *)s_in, off, &win);
                 if (!(rc == MICD_OK && used + 8 < DP_STAGE - off)) {
-                    if (!BIG) rc = MICD_ERR_UNSUPPORTED;
+                    if (!BIG) { rc = MICD_ERR_UNSUPPORTED; defer = MIC_TBR_P_DEFER_LEN; }
                     else {
                         for (uint32_t i = 0; i < 65536; i++) u.norm[i] = 0;    // (rare: header longer than the stage) start over from HBM
-                        rc = mic_read_ncount<int32_t, true>(u.comp_in + off, len - off, u.norm, &symbol_len, &tl, &used, 65536u);
+                        rc = mic_read_ncount<int32_t, true>(u.comp_in + off, len - off, u.norm, &symbol_len, &tl, &used, 65536u, nullptr, 0, &win);
+                        route = MIC_TBR_P_BIG_HBM;
                     }
                 }
             }
         } while (0);
         if (!BIG && rc == MICD_ERR_UNSUPPORTED) {
             if (u.tier == 1) { u.status = MICD_INT_GROW; return; }            // (more than 8192 symbols: the count slab is tier 1's)
-            u.flavour = DP_DEFER; return;
+            u.flavour = DP_DEFER; u.tb_route = defer; return;
         }
         if (rc == MICD_OK && (1u << tl) > u.tab_cap) rc = MICD_INT_GROW;       // (tier 1: the decode table slabs hold 8192 states)
-        if (rc == MICD_OK) { u.flavour = flavour; u.count = count; u.symbol_len = symbol_len; u.table_log = tl; u.bits_off = off + used; }
+        if (rc == MICD_OK) { u.flavour = flavour; u.count = count; u.symbol_len = symbol_len; u.table_log = tl; u.bits_off = off + used;
+                            u.tb_route = (BIG ? u.tb_route : 0u) | route | (win ? MIC_TBR_P_WINDOW : 0u); }
         else u.status = rc;
     }
 }
