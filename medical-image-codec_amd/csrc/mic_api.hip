@@ -579,7 +579,7 @@ int mic_hip_mic2_info(const uint8_t *c, size_t len, int *width, int *height, int
 } MIC_ABI_CATCH
 
 // DecompressFrame (multiframecompress.go:266-315): one frame of a MIC2 file.  Independent mode decodes just that
-// frame; temporal mode needs frames 0..idx (all their residual streams are decoded at once, mic_temporal.hip).
+// frame; temporal mode needs frames 0..idx (all their residual streams are decoded at once, mic_mic2_batch.hip).
 int mic_hip_mic2_decompress_frame(const uint8_t *c, size_t len, int frame_idx, uint16_t *pixels_out, size_t pixels_cap) try {
     if (!c || !pixels_out) return MIC_ERR_ARGS;
     int w, h, n, temporal;

@@ -1320,7 +1320,7 @@ int mic_hip_mic2_decompress(const uint8_t *c, size_t len, uint16_t *frames_out, 
     const size_t npx = (size_t)w * (size_t)h;
     if (npx * (size_t)n > frames_cap_px) return MIC_ERR_CAPACITY;
     if (npx > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
-    if (temporal) return mic2_temporal_decompress(c, len, w, h, n, n, frames_out);   // mic_temporal.hip
+    if (temporal) return mic2_temporal_decompress(c, len, w, h, n, n, frames_out);   // mic_mic2_batch.hip
     const size_t data_off = 20 + (size_t)n * 8;
     if ((rc = ensure_device())) return rc;
     const int shards = cur_default() ? 1 : std::max(1, (int)std::min<size_t>(default_devices().size(), (size_t)n / 8));   // (frames decode into fixed places: any cut will do)

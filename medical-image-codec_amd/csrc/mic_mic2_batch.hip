@@ -1,11 +1,21 @@
-// mic_mic2_batch.hip -- MIC2: many whole volumes per call (mic_hip_mic2_compress_batch / _decompress_batch, whose host pipeline is in
-// mic_host_io.hip; mic_hip_session_mic2_encode / _decode; mic_hip_mic2_batch_plan).  No reference counterpart: every volume is
-// CompressMultiFrame / DecompressMultiFrame (multiframecompress.go:179-261) in the MIC2 container (multiframe.go:49-142), the temporal
-// ones through TemporalDeltaEncode / TemporalDeltaDecode (temporaldelta.go:11-37).
+// mic_mic2_batch.hip -- MIC2: the unit chains of whole volumes.  One temporal volume per call (mic2_temporal_compress / _decompress,
+// behind mic_hip_mic2_compress_temporal, mic_hip_mic2_decompress and mic_hip_mic2_decompress_frame) and many volumes per call
+// (mic_hip_mic2_compress_batch / _decompress_batch, whose host pipeline is in mic_host_io.hip; mic_hip_session_mic2_encode / _decode;
+// mic_hip_mic2_batch_plan; the many-volume calls have no reference counterpart).  Every volume is CompressMultiFrame /
+// DecompressMultiFrame (multiframecompress.go:179-261) in the MIC2 container (multiframe.go:49-142).
+//
+// A temporal volume (flags 0x01 | 0x02, multiframecompress.go:179-224): frame 0 is a spatial frame; frame i > 0 is
+// TemporalDeltaEncode(frame i, frame i-1) = ZigZag(cur - prev) (temporaldelta.go:11-23) coded by compressResidualFrame = RleCompressU16
+// + FSE 2-state with the 1-state fallback (multiframecompress.go:146-163).  DecompressMultiFrame (:227-261) inverts it frame by frame.
+// Both directions are parallel over frames here: the encoder differences ORIGINAL frames, and on the decode side
+// frame_i = frame_0 + sum_{j<=i} UnZigZag(res_j)  (mod 2^16) is a running sum along the frame axis, so every residual stream is
+// entropy-decoded at once and one kernel accumulates per pixel.
 //
 // The units of a call's volumes -- volume order, then frame order -- go through the unit codec in sub-batches cut by their sizes
 // alone (mic2_batch_cuts: next_strip_cut's rule), so a sub-batch holds frames of independent volumes, frame 0 of temporal ones and
-// residual units of any sizes side by side, and a dataset of small volumes is one chain.  What is new on the device:
+// residual units of any sizes side by side, and a dataset of small volumes is one chain.  Every caller -- the single calls, the
+// batches, the crop readers (mic_mic2_crops.hip) -- runs its sub-batches through mic2_batch_encode_units / mic2_batch_decode_units,
+// the one place where the MIC2 unit chain is written out.  On the device:
 //   k_mic2_residual    one launch over the residual units of a sub-batch whatever their sizes: a tile list of (unit, first pixel)
 //                      entries balances a 245-pixel frame against a 15 360-pixel one; every unit brings its own cur / prev pointers.
 //   k_mic2_accumulate  frame_i = frame_{i-1} + UnZigZag(res_i) for the temporal volumes a sub-batch holds parts of: a span per
@@ -68,8 +78,17 @@ __global__ void k_mic2_set_max(MicUnit *units, const ResUnit *__restrict__ res, 
     if (i < n) { MicUnit &u = units[res[i].unit]; u.max_value = (uint16_t)u.dec_thr; }
 }
 
-// ---- decode: running sums -------------------------------------------------------------------------------------------------------
-constexpr uint32_t kAccTile = 1024;                  // pixels a block takes: 256 lanes x 4, each lane walks the frame axis of its pixels
+// ---- decode: residual lengths, running sums -------------------------------------------------------------------------------------
+// a residual stream must expand to exactly its own frame (multiframecompress.go:170-172)
+__global__ void k_mic2_check_units(MicUnit *units, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && units[i].mode == 3 && units[i].status == MICD_OK && units[i].nsym != (uint32_t)units[i].w * (uint32_t)units[i].h) units[i].status = MICD_ERR_CORRUPT;
+}
+
+// pixels a block takes: a lane each, which walks the frame axis of its pixel.  The walk is a chain of dependent stores as long as the
+// span has frames, so the launch wants lanes, not work per lane: at 1024 pixels a block (four a lane) the one span of a single
+// 128 x 512 x 512 volume took 215 us, at 256 it takes 72 us (kernel trace; a batch of sixteen such volumes fills the device either way)
+constexpr uint32_t kAccTile = 256;
 
 // tiles[b] = (index into spans, first pixel).  One lane per pixel along the frame axis: consecutive lanes read consecutive symbols of
 // a unit and store consecutive samples of a frame.  The sum starts from frame 0, which the span's first unit decoded into dst
@@ -218,7 +237,7 @@ int mic2_batch_decode_units(mic_hip_session *s, const Mic2DecUnit *u, int nb, in
         mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p, pred_mask, s->dec_classes.mask());
         if (any_sym) {
             mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
-            mic2_launch_residual_check_units((MicUnit *)s->units.p, nb, s->stream);         // a residual expands to exactly its frame (multiframecompress.go:170-172)
+            hipLaunchKernelGGL(k_mic2_check_units, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb);
         }
     });
     if (rc) return rc;
@@ -270,6 +289,97 @@ int mic2_batch_parse(const uint8_t *head, size_t head_len, uint64_t file_len, Mi
     if ((size_t)m.w * (size_t)m.h > ((size_t)1 << 28) || file_len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
     if (head_len < 20 + 8 * (size_t)m.n) return MIC_ERR_ARGS;                               // (the table is not all there)
     m.table = head + 20;
+    return MIC_OK;
+}
+
+// ---- one temporal volume per call -----------------------------------------------------------------------------------------------
+// The single calls keep their own transfers -- plain copies of the caller's buffers on the session's stream, no staging pipeline -- and
+// run their sub-batches through the cores above.  Encode: a residual needs the ORIGINAL frame before it, so a sub-batch uploads one
+// frame more than it codes (its predecessor's last) and is otherwise independent of the others.  Decode: the running sum needs the
+// frame before the sub-batch's first residual: it is carried on the device in the slot in front of the sub-batch's frames.
+int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nframes, uint16_t max_value,
+                           uint8_t *out, size_t out_cap, size_t *out_len) {
+    const size_t npx = (size_t)width * (size_t)height;
+    if (npx > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
+    const size_t header = 20 + (size_t)nframes * 8;
+    if (out_cap < header) return MIC_ERR_CAPACITY;
+    DefaultLease lease;
+    int rc = lease.acquire();
+    if (rc) return rc;
+    mic_hip_session *s = cur_default();
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    const std::vector<size_t> cuts = mic2_batch_cuts(std::vector<size_t>((size_t)nframes, npx), kWorkspaceBudget);
+    std::vector<uint32_t> lens((size_t)nframes);
+    std::vector<Mic2EncUnit> eu; std::vector<uint64_t> offs; std::vector<int32_t> st;
+    uint64_t total = 0;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        const size_t f0 = cuts[b];
+        const int nb = (int)(cuts[b + 1] - f0);
+        const int lead = f0 ? 1 : 0;                                                        // the frame in front of the sub-batch (its residuals' reference)
+        if ((rc = s->io_px.reserve(npx * 2 * (size_t)(nb + lead)))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->io_px.p, frames + (f0 - (size_t)lead) * npx, npx * 2 * (size_t)(nb + lead), hipMemcpyHostToDevice, s->stream));
+        eu.resize((size_t)nb); offs.resize((size_t)nb + 1); st.resize((size_t)nb);
+        for (int i = 0; i < nb; i++)
+            eu[(size_t)i] = Mic2EncUnit{ (const uint16_t *)s->io_px.p + (size_t)(lead + i) * npx, width, height, max_value, (uint16_t)(f0 + (size_t)i > 0) };
+        const uint8_t *d_blobs = nullptr;
+        if ((rc = mic2_batch_encode_units(s, eu.data(), nb, &d_blobs, offs.data(), st.data()))) return rc;
+        for (int i = 0; i < nb; i++) if (st[(size_t)i] != MIC_OK) return st[(size_t)i];
+        const uint64_t bytes = offs[(size_t)nb];
+        if (total + bytes > 0xFFFFFFFFull) return MIC_ERR_UNSUPPORTED;                      // u32 offsets, multiframe.go:75-80
+        if (out_cap < header + total + bytes) return MIC_ERR_CAPACITY;
+        for (int i = 0; i < nb; i++) lens[f0 + (size_t)i] = (uint32_t)(offs[(size_t)i + 1] - offs[(size_t)i]);
+        if (bytes) HIP_TRY(hipMemcpy(out + header + total, d_blobs, (size_t)bytes, hipMemcpyDeviceToHost));
+        total += bytes;
+    }
+    mic2_write_head(out, width, height, nframes, true, lens.data());
+    *out_len = header + (size_t)total;
+    return MIC_OK;
+}
+
+// frames 0 .. n-1 of the n_total the file holds (mic_hip_mic2_decompress_frame stops at the frame it is asked for)
+int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_total, int n, uint16_t *frames_out) {
+    const size_t npx = (size_t)w * (size_t)h;
+    if (npx > ((size_t)1 << 28) || len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
+    const size_t data_off = 20 + (size_t)n_total * 8;
+    DefaultLease lease;
+    int rc = lease.acquire();
+    if (rc) return rc;
+    mic_hip_session *s = cur_default();
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    const std::vector<size_t> cuts = mic2_batch_cuts(std::vector<size_t>((size_t)n, npx), kWorkspaceBudget);
+    std::vector<Mic2DecUnit> du; std::vector<int32_t> st;
+    for (size_t b = 0; b + 1 < cuts.size(); b++) {
+        const size_t f0 = cuts[b];
+        const int nb = (int)(cuts[b + 1] - f0);
+        const int lead = f0 ? 1 : 0;                                                        // slot 0 holds the frame in front of the sub-batch
+        if ((rc = s->io_px.reserve(npx * 2 * (size_t)(nb + 1)))) return rc;                 // (grown before the carry below could be lost: sized for the first pass too)
+        size_t c0 = (size_t)-1, c1 = 0;                                                     // byte range of the sub-batch's streams
+        for (int i = 0; i < nb; i++) {
+            const size_t fi = f0 + (size_t)i;
+            const size_t start = data_off + get_u32(c + 20 + fi * 8), bl = get_u32(c + 24 + fi * 8);
+            if (start + bl > len) return MIC_ERR_CORRUPT;                                   // multiframe.go:137-139
+            if (bl == 0) return MIC_ERR_CORRUPT;
+            c0 = std::min(c0, start); c1 = std::max(c1, start + bl);
+        }
+        if ((rc = s->io_comp.reserve(c1 - c0 + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->io_comp.p, c + c0, c1 - c0, hipMemcpyHostToDevice, s->stream));
+        // frames of the sub-batch at slots lead .. lead + nb - 1; slot 0 = frame f0 - 1 (carried) when lead
+        uint16_t *d_frames = (uint16_t *)s->io_px.p;
+        du.resize((size_t)nb); st.resize((size_t)nb);
+        for (int i = 0; i < nb; i++) {
+            const size_t fi = f0 + (size_t)i;
+            du[(size_t)i] = Mic2DecUnit{ (const uint8_t *)s->io_comp.p + (data_off + get_u32(c + 20 + fi * 8) - c0), get_u32(c + 24 + fi * 8), w, h,
+                                         fi ? nullptr : d_frames, (uint32_t)(fi > 0) };     // (frame 0 decodes into slot 0)
+        }
+        if ((rc = mic2_batch_decode_units(s, du.data(), nb, st.data()))) return rc;
+        for (int i = 0; i < nb; i++) if (st[(size_t)i] != MIC_OK) return st[(size_t)i];
+        const Mic2DecSpan span{ d_frames, d_frames + (size_t)lead * npx, (uint32_t)npx, 0, nb, (int32_t)f0, INT_MAX, 0 };
+        if ((rc = mic2_batch_accumulate(s, &span, 1))) return rc;
+        HIP_TRY(hipMemcpyAsync(frames_out + f0 * npx, d_frames + (size_t)lead * npx, npx * 2 * (size_t)nb, hipMemcpyDeviceToHost, s->stream));
+        if (f0 + (size_t)nb < (size_t)n && lead + nb - 1 != 0)                              // carry the last frame to slot 0 for the next sub-batch
+            HIP_TRY(hipMemcpyAsync(d_frames, d_frames + (size_t)(lead + nb - 1) * npx, npx * 2, hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
     return MIC_OK;
 }
 

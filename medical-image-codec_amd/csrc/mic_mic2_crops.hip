@@ -1,76 +1,45 @@
-// mic_mic2_crops.hip -- MIC2: many 3-D crops per call into a device tensor (mic_hip_mic2_read_crops, mic_hip_mic2_reader_*,
-// mic_hip_session_mic2_read_crops; no reference counterpart).
+// mic_mic2_crops.hip -- MIC2: many 3-D crops per call into a device tensor, of one volume (mic_hip_mic2_read_crops,
+// mic_hip_mic2_reader_*, mic_hip_session_mic2_read_crops) or of many (mic_hip_mic2_multi_crop_plan, mic_hip_mic2_multi_read_crops,
+// mic_hip_mic2_readers_read_crops, mic_hip_session_mic2_multi_read_crops); no reference counterpart.
 //
-// One core (mic2_read_crops) behind the three doors; a door brings the parsed header, the frame table and a Mic2Source that says
-// where a frame's stream lies (the caller's file, the blobs a reader pulled, a file in device memory).  The host plans
-// (mic2_plan_crops): which frames' streams must be entropy-decoded, and the (crop, frame) overlaps -- pieces.  The frames go through
-// the unit codec in sub-batches of mic2_frames_per_batch, and behind each sub-batch a kernel writes into the crop tensor:
-//   independent files: the shared gather (launch_gather, mic_gather.hip) copies the sub-batch's pieces out of the decoded frames;
-//   temporal files:    frame_i = frame_0 + sum_{j<=i} UnZigZag(res_j) (mod 2^16) is a running sum per pixel (mic_temporal.hip), and a
-//                      crop needs it under its own footprint only: k_mic2_accumulate_crops walks the sub-batch's residual symbols
-//                      with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0, the
-//                      spatial unit, is the only full image on the device; the carry from one sub-batch to the next lives in the
-//                      tensor itself.
-// Crops of many volumes per call (mic_hip_mic2_multi_crop_plan, mic_hip_mic2_multi_read_crops, mic_hip_mic2_readers_read_crops,
-// mic_hip_session_mic2_multi_read_crops): one core of its own (mic2_multi_read_crops) behind three doors.  Every named volume is planned
-// as above; the units of all of them, ascending by volume, then frame, go through the unit codec in sub-batches that are cut by the
-// units' sizes alone (next_strip_cut), so a sub-batch holds frames of independent volumes, frame 0 of temporal ones -- both decoded
-// into one pixel slab -- and residual symbol units side by side: a batch of crops from sixteen volumes is one decode chain.  Behind
-// each sub-batch the gather copies the independent volumes' pieces and k_mic2_accumulate_crops_multi sums under the footprints of the
-// temporal volumes the sub-batch holds a part of.
+// One core (mic2_multi_read_crops) behind the six doors; a door brings the parsed headers, the frame tables and a source that says
+// where a frame's stream lies (the caller's file, the blobs a reader pulled, a file in device memory); a one-volume door makes a
+// one-volume plan of its own.  The host plans every named volume (mic2_plan_crops): which frames' streams must be entropy-decoded, and
+// the (crop, frame) overlaps -- pieces.  The units of all volumes, ascending by volume, then frame, go through the MIC2 decode chain
+// (mic2_batch_decode_units, mic_mic2_batch.hip) in sub-batches that are cut by the units' sizes alone (next_strip_cut), so a
+// sub-batch holds frames of independent volumes, frame 0 of temporal ones -- both decoded into one pixel slab -- and residual symbol
+// units side by side: a batch of crops from sixteen volumes is one decode chain.  Behind each sub-batch a kernel writes into the
+// crop tensor:
+//   independent volumes: the shared gather (launch_gather, mic_gather.hip) copies the sub-batch's pieces out of the decoded frames;
+//   temporal volumes:    frame_i = frame_0 + sum_{j<=i} UnZigZag(res_j) (mod 2^16) is a running sum per pixel (mic_mic2_batch.hip), and
+//                        a crop needs it under its own footprint only: k_mic2_accumulate_crops walks the sub-batch's residual
+//                        symbols with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0,
+//                        the spatial unit, is the only full image of the volume on the device; the carry from one sub-batch to the
+//                        next lives in the tensor itself.
 #include <climits>
 #include <memory>
 #include "mic_session.h"
 #include "mic_pieces.h"
 
-void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter);   // mic_wavelet.hip
-
 namespace {
 
-// units 0 .. nb-1 hold frames f0 .. f0 + nb - 1 (unit 0 of the first sub-batch, f0 = 0, is the spatial frame in frame0; every other
-// unit a residual whose symbols lie in its sym slab).  fp = a crop's footprint: w x h pixels at (sx, sy) of every frame, the crop's
-// frames inside the volume zf = fp.frame .. fp.k, slice dz the one of zf.  One lane per footprint pixel:
-//   acc = frame f0 - 1 of that pixel -- frame0's sample, or the carry the sub-batch before left in the tensor: in slice(zf) while the
+// What a sub-batch holds of one temporal volume: its units u0 .. u0 + nb - 1 are the volume's frames f0 .. f0 + nb - 1 (unit u0 of the
+// volume's first sub-batch, f0 = 0, is the spatial frame, at frame0 of the pixel slab; every other unit a residual whose symbols lie
+// in its sym slab), fbad the volume's first failed frame so far (INT_MAX: none), fw its width.  A footprint names its volume by its
+// slot among the call's temporal volumes (the list is sorted by it) and finds the span at spans[slot - slot0]; the launch covers the
+// footprints of the volumes present, and everything a block loops over is uniform in it.
+// fp = a crop's footprint: w x h pixels at (sx, sy) of every frame, the crop's frames inside the volume zf = fp.frame .. fp.k, slice
+// dz the one of zf.  One lane per footprint pixel:
+//   acc = frame f0 - 1 of that pixel -- frame 0's sample, or the carry the sub-batch before left in the tensor: in slice(zf) while the
 //         sum has not reached zf, in slice(f0 - 1) from then on;
-//   acc = (acc + UnZigZag(res_f)) & 0xFFFF for f = f0 .. min(f0 + nb - 1, fp.k), stored into slice(f) when f >= zf     (k_tmp_accumulate);
+//   acc = (acc + UnZigZag(res_f)) & 0xFFFF for f = f0 .. min(f0 + nb - 1, fp.k), stored into slice(f) when f >= zf     (k_mic2_accumulate);
 //   a sum that has not reached zf at the sub-batch's end goes into slice(zf), the next sub-batch's carry.
-// A crop that is complete (fp.k < f0) or depends on a failed unit (fp.k >= fbad, the first failed frame) is left alone.
-__global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *units, int nb, int f0, int fbad, const uint16_t *frame0, int fw,
-                                                             const CropPiece *prints, uint16_t *out, int cw, int ch, int cd) {
-    const CropPiece fp = prints[blockIdx.x];
-    if (fp.k < f0 || fp.k >= fbad) return;
-    const PieceLanes ln = piece_lanes(fp.w);
-    const int zf = fp.frame, iend = min(nb, fp.k - f0 + 1), r0 = f0 ? 0 : 1;
-    const size_t slice = (size_t)ch * cw;
-    uint16_t *dst = out + (((size_t)fp.crop * cd + fp.dz) * ch + fp.dy) * cw + fp.dx;
-    for (int y = ln.row; y < fp.h; y += ln.rstep) {
-        const size_t srow = (size_t)(fp.sy + y) * fw + fp.sx;
-        const mic_gp<uint16_t> d = mic_g(dst + (size_t)y * cw);
-        for (int x = ln.col; x < fp.w; x += ln.lw) {
-            uint32_t acc;
-            if (f0 == 0) {
-                acc = mic_g(frame0)[srow + x];
-                if (zf == 0) d[x] = (uint16_t)acc;
-            } else acc = d[(size_t)max(f0 - 1 - zf, 0) * slice + x];
-            for (int i = r0; i < iend; i++) {
-                acc = (acc + unzigzag16(mic_g(units[i].sym)[srow + x])) & 0xFFFFu;          // temporaldelta.go:27-37
-                if (f0 + i >= zf) d[(size_t)(f0 + i - zf) * slice + x] = (uint16_t)acc;
-            }
-            if (f0 + iend - 1 < zf) d[x] = (uint16_t)acc;
-        }
-    }
-}
-
-// k_mic2_accumulate_crops for a sub-batch that holds parts of several temporal volumes.  A footprint names its volume by its slot
-// among the call's temporal volumes (the list is sorted by it); spans[slot - slot0] says what the sub-batch holds of that volume:
-// its units u0 .. u0 + nb - 1 are the volume's frames f0 .. f0 + nb - 1, fbad the volume's first failed frame so far (INT_MAX: none),
-// frame0 where its frame 0 lies in the pixel slab (f0 == 0 only), fw its width.  The launch covers the footprints of the volumes
-// present; everything a block loops over is uniform in it.
+// A crop that is complete (fp.k < f0) or depends on a failed unit (fp.k >= fbad) is left alone.
 struct VolPrint { CropPiece fp; int32_t slot, pad; };
 struct VolSpan { uint64_t frame0; int32_t u0, nb, f0, fbad, fw, pad; };
-__global__ void __launch_bounds__(256) k_mic2_accumulate_crops_multi(const MicUnit *__restrict__ units, const VolSpan *__restrict__ spans, int slot0,
-                                                                   const uint16_t *__restrict__ slab, const VolPrint *__restrict__ prints,
-                                                                   uint16_t *out, int cw, int ch, int cd) {
+__global__ void __launch_bounds__(256) k_mic2_accumulate_crops(const MicUnit *__restrict__ units, const VolSpan *__restrict__ spans, int slot0,
+                                                             const uint16_t *__restrict__ slab, const VolPrint *__restrict__ prints,
+                                                             uint16_t *out, int cw, int ch, int cd) {
     const VolPrint vp = prints[blockIdx.x];
     const CropPiece &fp = vp.fp;
     const VolSpan v = spans[vp.slot - slot0];
@@ -152,97 +121,6 @@ int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch,
     return MIC_OK;
 }
 
-// n crops into d_out ([n][cd][ch][cw] u16, an address s's device can write: patch_pointer; samples outside the volume 0), on a session
-// the caller holds and has made current; the table entries of the plan's frames have been checked (crops_call).  status[i] (may be NULL): MIC_OK, or the code of the first failing frame crop i depends on.
-int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
-                    void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats) {
-    const size_t npx = (size_t)m.w * (size_t)m.h, nfr = plan.frames.size();
-    int rc;
-    std::vector<uint64_t> len(nfr);
-    for (size_t k = 0; k < nfr; k++) len[k] = get_u32(m.table + 8 * (size_t)plan.frames[k] + 4);
-    if ((rc = s->ensure(1, npx))) return rc;                                                // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volume; every byte is written
-    const size_t per = mic2_frames_per_batch(npx);
-    // the call's list, up once: temporal files their footprints as they are; independent files their pieces as the gather reads
-    // them -- plan frame k is decoded into slot k % per of its sub-batch's slab, the sub-batches starting at multiples of per
-    std::vector<GatherPiece> list(m.temporal ? 0 : plan.pieces.size());
-    std::vector<size_t> first(nfr + 1, 0);                                                  // independent: the pieces of plan frame k
-    for (size_t q = 0; q < list.size(); q++) {
-        const CropPiece &pc = plan.pieces[q];
-        first[(size_t)pc.k + 1]++;
-        list[q] = GatherPiece{ (uint64_t)((size_t)pc.k % per) * npx + (uint64_t)pc.sy * (uint64_t)m.w + (uint64_t)pc.sx,
-                               (((uint64_t)pc.crop * (uint64_t)cd + (uint64_t)pc.dz) * (uint64_t)ch + (uint64_t)pc.dy) * (uint64_t)cw + (uint64_t)pc.dx,
-                               m.w, cw, pc.w, pc.h, 0, 0 };
-    }
-    for (size_t k = 0; k < nfr; k++) first[k + 1] += first[k];
-    const void *h_list = m.temporal ? (const void *)plan.prints.data() : (const void *)list.data();
-    const size_t list_bytes = m.temporal ? plan.prints.size() * sizeof(CropPiece) : list.size() * sizeof(GatherPiece);
-    if (nfr) {
-        if ((rc = s->pieces.reserve(list_bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(s->pieces.p, h_list, list_bytes, hipMemcpyHostToDevice, s->stream));
-    }
-    int mw = 1, mh = 1;
-    for (const CropPiece &fp : plan.prints) { mw = std::max(mw, fp.w); mh = std::max(mh, fp.h); }
-    std::vector<int32_t> fst(nfr, MIC_OK);                                                  // status of plan frame k
-    std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
-    int fbad = INT_MAX, bad_code = MIC_OK;                                                  // temporal: the first failed frame
-    uint64_t nslab = 0;
-    for (size_t k0 = 0; k0 < nfr && fbad == INT_MAX; k0 += per) {
-        const int nb = (int)std::min(per, nfr - k0);
-        if ((rc = pack_streams(s, nb, [&](int i) { return len[k0 + (size_t)i]; }, [&](int i) { return src.blob(plan.frames[k0 + (size_t)i]); },
-                               src.device, begins, ends))) return rc;
-        nslab++;
-        if (!m.temporal) {
-            if ((rc = s->io_px.reserve(npx * 2 * (size_t)nb + 64))) return rc;
-            units.assign((size_t)nb, mic_hip_unit{ 0, m.w, m.h, 0, 0 });
-            for (int i = 0; i < nb; i++) units[(size_t)i].px_offset = (uint64_t)i * npx;
-            if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
-            if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
-            const size_t p0 = first[k0], np = first[k0 + (size_t)nb] - p0;
-            s->timer.reset(s->stream); s->timer.mark("k_mic2_gather_crops");
-            launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
-            s->timer.mark("end");
-        } else {
-            // (as mic2_temporal_decompress: the frames of a temporal plan are 0 .. nfr - 1, so plan index = frame)
-            if ((rc = s->io_px.reserve(npx * 2 + 64))) return rc;
-            if ((rc = s->lay_out(nb, npx))) return rc;
-            for (int i = 0; i < nb; i++) {
-                MicUnit &u = s->h_units[(size_t)i];
-                u.comp_in = (const uint8_t *)s->io_comp.p + begins[(size_t)i]; u.comp_len = (uint32_t)len[k0 + (size_t)i];
-                u.w = m.w; u.h = m.h;
-                u.tok_cap = (uint32_t)tok_cap_for(npx);
-                if (k0 == 0 && i == 0) { u.mode = 0; u.px_out = (uint16_t *)s->io_px.p; }
-                else u.mode = 3;                                         // FSE + RLE-of-symbols into u.sym
-            }
-            const int r0 = k0 ? 0 : 1;                                    // first residual unit
-            rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
-                mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p);
-                if (nb > r0) {
-                    mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
-                    mic2_launch_residual_check((MicUnit *)s->units.p, nb, (uint32_t)npx, r0, s->stream);
-                }
-            });
-            if (rc) return rc;
-            if ((rc = session_decode_finish(s, fst.data() + k0))) return rc;
-            for (int i = 0; i < nb && fbad == INT_MAX; i++) if (fst[k0 + (size_t)i] != MIC_OK) { fbad = (int)k0 + i; bad_code = fst[k0 + (size_t)i]; }
-            s->timer.reset(s->stream); s->timer.mark("k_mic2_accumulate_crops");
-            for (size_t q = 0; q < plan.prints.size() && fbad > (int)k0; q += 0x7FFFFFFF)
-                hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)std::min<size_t>(plan.prints.size() - q, 0x7FFFFFFF), row_chunks(mw, mh)), dim3(256), 0, s->stream,
-                                   (const MicUnit *)s->units.p, nb, (int)k0, fbad, (const uint16_t *)s->io_px.p, m.w, (const CropPiece *)s->pieces.p + q, (uint16_t *)d_out, cw, ch, cd);
-            s->timer.mark("end");
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (status) {
-        for (int i = 0; i < n; i++) status[i] = MIC_OK;
-        if (m.temporal) { for (const CropPiece &fp : plan.prints) if (fp.k >= fbad) status[fp.crop] = bad_code; }
-        else for (const CropPiece &pc : plan.pieces) if (status[pc.crop] == MIC_OK) status[pc.crop] = fst[(size_t)pc.k];
-    }
-    if (stats) { stats->frames_decoded = nfr; stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
-    return MIC_OK;
-}
-
 }  // namespace micapi
 
 namespace {
@@ -252,29 +130,6 @@ int parse_mic2(const uint8_t *head, uint64_t file_len, Mic2Head &m) {
     const int rc = mic_hip_mic2_info(head, (size_t)file_len, &m.w, &m.h, &m.n, &m.temporal);
     m.file_len = file_len;
     return rc;
-}
-
-// a door's call on its parsed file: arguments, n == 0, the plan, then the core on session s (leased here when s is NULL)
-int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(const CropPlan &, Mic2Source &)> &source,
-               const int32_t *xyz, int n, int cw, int ch, int cd, void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
-    size_t need = 0;
-    int rc = mic2_crop_args(m, xyz, n, cw, ch, cd, out_cap, &need);
-    if (rc) return rc;
-    if (stats) *stats = mic_hip_crop_stats{ 0, 0, 0 };
-    if (n == 0) return MIC_OK;
-    if (!d_out) return MIC_ERR_ARGS;
-    CropPlan plan;
-    if ((rc = mic2_plan_crops(m.w, m.h, m.n, m.temporal, xyz, n, cw, ch, cd, plan))) return rc;
-    DefaultLease lease;
-    // the pointer and the table are judged before a source is asked for a byte, and before anything is launched
-    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
-    for (uint32_t f : plan.frames) {                                                        // as mic_hip_mic2_decompress, multiframe.go:137-139
-        const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)f), bl = get_u32(m.table + 8 * (size_t)f + 4);
-        if (bl == 0 || off + bl > m.file_len) return MIC_ERR_CORRUPT;
-    }
-    Mic2Source src;
-    if ((rc = source(plan, src))) return rc;
-    return mic2_read_crops(s, m, plan, src, n, cw, ch, cd, d_out, need, status, stats);
 }
 
 // ---- crops of many volumes per call ------------------------------------------------------------------------------------------
@@ -348,7 +203,10 @@ int mic2_multi_plan(Mic2MultiPlan &mp, const int32_t *xyzv, int n, int cw, int c
 struct Mic2MultiSource { bool device = false; std::function<const uint8_t *(uint32_t vol, uint32_t frame)> blob; };
 
 // n crops into d_out ([n][cd][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
-// current.  The units of every planned volume go through the unit codec in plan order, in sub-batches cut by their sizes alone.
+// current.  The units of every planned volume go through the MIC2 decode chain in plan order, in sub-batches cut by their sizes alone;
+// the call stops in front of a sub-batch when every unit left belongs to a temporal volume that has already failed (a one-volume call
+// whose frame failed).  status[i] / failed_frame[i] (each may be NULL): MIC_OK / -1, or the code of the first failing frame crop i
+// depends on and that frame.
 int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic2MultiSource &src, int n, int cw, int ch, int cd,
                           void *d_out, size_t need, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
     struct Unit { uint32_t vol, frame; };
@@ -420,36 +278,24 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
     VolSpan *d_spans = (VolSpan *)((char *)s->pieces.p + list_bytes + print_bytes);
     std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
     std::vector<int32_t> fbad(slot_vol.size(), INT_MAX), bad_code(slot_vol.size(), MIC_OK); // a temporal volume's first failed frame
-    std::vector<uint64_t> begins, ends;
+    std::vector<uint64_t> begins, ends; std::vector<Mic2DecUnit> du;
+    uint64_t nslab = 0;                                                                     // decode chains run
     for (size_t b = 0; b + 1 < cuts.size(); b++) {
         const size_t u0 = cuts[b];
         const int nb = (int)(cuts[b + 1] - u0);
+        // units lie in volume order: when the first and the last one left are of one volume, nothing but that volume is left, and when
+        // it is a temporal one that has failed, no crop is waiting for any of them
+        if (un[u0].vol == un[nu - 1].vol && slot_of[un[u0].vol] >= 0 && fbad[(size_t)slot_of[un[u0].vol]] != INT_MAX) break;
         if ((rc = pack_streams(s, nb, [&](int i) { return blob_len(u0 + (size_t)i); },
                                [&](int i) { return src.blob(un[u0 + (size_t)i].vol, un[u0 + (size_t)i].frame); }, src.device, begins, ends))) return rc;
-        if ((rc = s->lay_out(nb, *std::max_element(px.begin() + (ptrdiff_t)u0, px.begin() + (ptrdiff_t)u0 + nb)))) return rc;
-        bool any_sym = false;
-        uint32_t pred_mask = 0;                                                             // predictor classes (by width) of the sub-batch's frames
+        du.resize((size_t)nb);
         for (int i = 0; i < nb; i++) {
             const size_t g = u0 + (size_t)i;
-            MicUnit &u = s->h_units[(size_t)i];
-            u.comp_in = (const uint8_t *)s->io_comp.p + begins[(size_t)i]; u.comp_len = (uint32_t)blob_len(g);
-            u.w = vol(g).m.w; u.h = vol(g).m.h;
-            u.tok_cap = (uint32_t)tok_cap_for(px[g]);                                       // (the unit's own bounds, whatever the largest of the sub-batch)
-            u.sym_cap = (uint32_t)std::min<size_t>(tok_cap_for(px[g]) + 64, 0xFFFFFFF0u);
-            if (is_frame(g)) { u.mode = 0; u.px_out = (uint16_t *)s->io_px.p + slab_off[g]; pred_mask |= mic_pred_bit(u.w); }
-            else { u.mode = 3; any_sym = true; }                                            // FSE + RLE-of-symbols into u.sym
+            du[(size_t)i] = Mic2DecUnit{ (const uint8_t *)s->io_comp.p + begins[(size_t)i], (uint32_t)blob_len(g), vol(g).m.w, vol(g).m.h,
+                                         is_frame(g) ? (uint16_t *)s->io_px.p + slab_off[g] : nullptr, (uint32_t)!is_frame(g) };
         }
-        s->retry.kind = 0;                                                                  // (laid out here, in tier 2: no second run)
-        rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
-            mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p, pred_mask, s->dec_classes.mask());
-            if (any_sym) {
-                mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
-                mic2_launch_residual_check_units((MicUnit *)s->units.p, nb, s->stream);
-            }
-        });
-        if (rc) return rc;
-        s->learn_decode = true;                                                             // (frames and residuals run the same tANS classes)
-        if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
+        if ((rc = mic2_batch_decode_units(s, du.data(), nb, ust.data() + u0))) return rc;
+        nslab++;
         // the temporal volumes of this sub-batch: runs of units of one volume
         const size_t sp0 = spans.size();
         int slot0 = 0;
@@ -475,8 +321,8 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         if (nsp) {
             const size_t q0 = pfirst[(size_t)slot0], nq = pfirst[(size_t)slot0 + nsp] - q0;
             HIP_TRY(hipMemcpyAsync(d_spans + sp0, spans.data() + sp0, nsp * sizeof(VolSpan), hipMemcpyHostToDevice, s->stream));
-            s->timer.mark("k_mic2_accumulate_crops_multi");
-            hipLaunchKernelGGL(k_mic2_accumulate_crops_multi, dim3((unsigned)nq, row_chunks(tw, th)), dim3(256), 0, s->stream,
+            s->timer.mark("k_mic2_accumulate_crops");
+            hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)nq, row_chunks(tw, th)), dim3(256), 0, s->stream,
                                (const MicUnit *)s->units.p, (const VolSpan *)d_spans + sp0, slot0, (const uint16_t *)s->io_px.p, d_prints + q0,
                                (uint16_t *)d_out, cw, ch, cd);
         }
@@ -510,7 +356,41 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
             }
         }
     }
-    if (stats) *stats = mic_hip_multi_crop_stats{ mp.units, mp.pieces, cuts.size() - 1, mp.read };
+    if (stats) *stats = mic_hip_multi_crop_stats{ mp.units, mp.pieces, nslab, mp.read };
+    return MIC_OK;
+}
+
+// a one-volume door's call on its parsed file: arguments, n == 0, the plan, the session (leased here when s is NULL), the table
+// entries of the plan's frames, `source`, then the core on a plan of that one volume
+int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(const CropPlan &, Mic2Source &)> &source,
+               const int32_t *xyz, int n, int cw, int ch, int cd, void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+    size_t need = 0;
+    int rc = mic2_crop_args(m, xyz, n, cw, ch, cd, out_cap, &need);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_crop_stats{ 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    Mic2MultiPlan mp;
+    mp.vols.resize(1);
+    Mic2Vol &f = mp.vols[0];
+    f.named = true; f.m = m;
+    if ((rc = mic2_plan_crops(m.w, m.h, m.n, m.temporal, xyz, n, cw, ch, cd, f.plan))) return rc;
+    mp.units = f.plan.frames.size(); mp.pieces = f.plan.pieces.size(); mp.read = 1;
+    DefaultLease lease;
+    // the pointer and the table are judged before a source is asked for a byte, and before anything is launched
+    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
+    for (uint32_t fr : f.plan.frames) {                                                     // as mic_hip_mic2_decompress, multiframe.go:137-139
+        const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)fr), bl = get_u32(m.table + 8 * (size_t)fr + 4);
+        if (bl == 0 || off + bl > m.file_len) return MIC_ERR_CORRUPT;
+    }
+    Mic2Source one;
+    if ((rc = source(f.plan, one))) return rc;
+    Mic2MultiSource src;
+    src.device = one.device;
+    src.blob = [&one](uint32_t, uint32_t frame) { return one.blob(frame); };
+    mic_hip_multi_crop_stats ms{ 0, 0, 0, 0 };
+    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, d_out, need, status, nullptr, &ms))) return rc;
+    if (stats) *stats = mic_hip_crop_stats{ ms.frames_decoded, ms.pieces, ms.slabs };
     return MIC_OK;
 }
 

@@ -379,17 +379,11 @@ int session_decode_finish(mic_hip_session *s, int32_t *h_status);
 size_t unit_ws_bytes(size_t px);
 size_t unit_ws_bytes_tier(size_t px, int tier);
 size_t batch_units_for(size_t px, size_t mult, size_t extra = 0);   // units per sub-batch of the tiered unit codec (mic_api.hip)
-// MIC2 temporal pipeline (mic_temporal.hip)
+// MIC2, one temporal volume per call (mic_mic2_batch.hip): its frames through the sub-batch cores below, cut by mic2_batch_cuts;
+// decompress: frames 0 .. n-1 of the file's n_total
 int mic2_temporal_compress(const uint16_t *frames, int width, int height, int nframes, uint16_t max_value,
                            uint8_t *out, size_t out_cap, size_t *out_len);
 int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_total, int n, uint16_t *frames_out);
-// frames per sub-batch of the MIC2 decoders: a unit's tier-2 slabs and its frame on the device, under the workspace ceiling
-size_t mic2_frames_per_batch(size_t npx);
-// residual units r0 .. n-1 must expand to exactly npx symbols (k_tmp_check), behind their chain on `stream`
-void mic2_launch_residual_check(MicUnit *d_units, int n, uint32_t npx, int r0, hipStream_t stream);
-// the same for a chain of units of several sizes (MIC2 crops of many volumes): every symbol unit (mode 3) among units 0 .. n-1 must
-// expand to its own w * h symbols (k_tmp_check_units)
-void mic2_launch_residual_check_units(MicUnit *d_units, int n, hipStream_t stream);
 // What the patch and crop readers share beside the gather (mic_gather.hip; patch_pointer and the kernels' launcher: mic_pieces.h).
 // A sub-batch's nb streams, len(i) bytes at src(i) -- host memory, or (device) the session's device --, back to back into s->io_comp
 // (reserved here, with the 64 bytes the decode kernels may read past a stream's end): neighbours in the source go in one copy.
@@ -410,12 +404,10 @@ struct CropPlan {
     std::vector<CropPiece> prints;          // one per crop with a non-empty overlap, in crop order
 };
 int mic2_plan_crops(int width, int height, int nframes, int temporal, const int32_t *xyz, int n, int cw, int ch, int cd, CropPlan &plan);
-// where the core finds the stream of a frame: blob(frame) -> its first byte, on the host or (device = true) on the session's device
+// where a one-volume crop door finds the stream of a frame: blob(frame) -> its first byte, on the host or (device = true) on the session's device
 struct Mic2Source { bool device = false; std::function<const uint8_t *(uint32_t frame)> blob; };
 struct Mic2Head { int w = 0, h = 0, n = 0, temporal = 0; const uint8_t *table = nullptr; uint64_t file_len = 0; };   // table: the 8 n bytes behind the fixed header (host)
 int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need);
-int mic2_read_crops(mic_hip_session *s, const Mic2Head &m, const CropPlan &plan, const Mic2Source &src, int n, int cw, int ch, int cd,
-                    void *d_out, size_t need, int32_t *status, mic_hip_crop_stats *stats);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // Units [i0, return) of the next sub-batch of a list of units of px[i] pixels each, for the readers that decode units of mixed sizes
 // into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip)
@@ -428,6 +420,7 @@ std::vector<size_t> mic2_batch_cuts(const std::vector<size_t> &px, size_t budget
 // One unit of an encode sub-batch: the frame at `cur` on the session's device.  residual: coded as TemporalDeltaEncode against the
 // frame that lies directly in front of it (cur - w * h: the volume's own predecessor, or the lead frame a host part uploads).
 struct Mic2EncUnit { const uint16_t *cur; int32_t w, h; uint16_t max_value, residual; };
+// The MIC2 unit chains, written once: the single calls, the batches and the crop readers (mic_mic2_crops.hip) all run through them.
 // nb units through ONE encode chain (k_mic2_residual in front); on return the streams of the units that coded lie
 // packed at *d_blobs + offs[i] .. offs[i + 1] (s->packed, until the session's next chain), st[i] = the unit's code.
 int mic2_batch_encode_units(mic_hip_session *s, const Mic2EncUnit *u, int nb, const uint8_t **d_blobs, uint64_t *offs, int32_t *st);
@@ -438,8 +431,9 @@ struct Mic2DecUnit { const uint8_t *comp; uint32_t len; int32_t w, h; uint16_t *
 // dst, dst + npx, ...; carry = frame f0 - 1 (unused when f0 == 0: unit u0 decoded frame 0 into dst); fbad = the volume's first failed
 // frame so far (INT_MAX: none) -- the sum stops in front of it.
 struct Mic2DecSpan { const uint16_t *carry; uint16_t *dst; uint32_t npx; int32_t u0, nb, f0, fbad, pad; };
-// nb units through ONE decode chain, complete on return with st[i] = the unit's code; then, for the temporal spans of that chain
-// (built from st), the running sums -- one launch, complete on return.
+// nb units through ONE decode chain -- frame units and symbol units (tANS, RLE expansion, k_mic2_check_units: a residual expands to
+// exactly its own frame) --, complete on return with st[i] = the unit's code; then, for the temporal spans of that chain (built from
+// st), the running sums -- one launch, complete on return.
 int mic2_batch_decode_units(mic_hip_session *s, const Mic2DecUnit *u, int nb, int32_t *st);
 int mic2_batch_accumulate(mic_hip_session *s, const Mic2DecSpan *spans, int nspans);
 // a MIC2 file's 20-byte header and frame table (multiframe.go:49-91) from its frames' stream lengths

@@ -118,7 +118,7 @@ int strips_crop_args(const void *files, const size_t *lens, int nfiles, const in
 }  // namespace
 
 // Units [i0, i1) of the next sub-batch: as many as the workspace ceiling holds of the largest of them -- a unit's tier-2 slabs and its
-// strip in the staging slab, as mic2_frames_per_batch counts a frame -- and at most what one launch chain takes.
+// strip in the staging slab, as every MIC2 chain counts a frame (mic2_batch_cuts) -- and at most what one launch chain takes.
 size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0, size_t budget) {
     size_t max_px = 0, i1 = i0;
     while (i1 < px.size()) {

@@ -32,6 +32,17 @@ rc, want = mico.mic2_compress(stack, 4095, True)          # temporal: a residual
 assert rc == 0 and mic.compress_multi_frame(stack, 300, 64, 4095, temporal=True) == want
 assert np.array_equal(np.asarray(mic.decompress_multi_frame(want)).reshape(stack.shape), stack)
 assert np.array_equal(np.asarray(mic.decompress_frame(want, 7)).reshape(64, 300), stack[7])
+# 149 x 63 = 9387 pixels, an odd number: every second frame is only 2-byte aligned on the device, so the residual kernel's scalar path
+# and a frame's partial last group meet the carry at the sub-batch seams
+odd = np.stack([np.roll(img[:63, :149], 3 * k, axis=1) for k in range(11)])
+cuts, nunits = mic.mic2_batch_plan([(149, 63, 11)])       # (the default ceiling: this process's small one)
+print("cuts of 11 frames of 149 x 63:", cuts.tolist())
+assert nunits == 11 and cuts[0] == 0 and cuts[-1] == 11 and len(cuts) - 2 >= 2, cuts   # at least two seams inside the volume
+rc, want = mico.mic2_compress(odd, 4095, True)
+assert rc == 0 and mic.compress_multi_frame(odd, 149, 63, 4095, temporal=True) == want
+assert np.array_equal(np.asarray(mic.decompress_multi_frame(want)).reshape(odd.shape), odd)
+for k in (4, 9):                                          # inside a sub-batch; the first of one
+    assert np.array_equal(np.asarray(mic.decompress_frame(want, k)).reshape(63, 149), odd[k])
 res = mic.compress_batch([stack[k] for k in range(9)], [4095] * 9, 2)
 for k, (st, blob, used) in enumerate(res):
     rc, w1 = mico.compress_single_frame(stack[k], 4095, 2)

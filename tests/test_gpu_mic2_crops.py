@@ -250,8 +250,8 @@ def test_the_gather_kernel_is_timed_under_its_name(mic, volumes):
 
 def test_sub_batch_seams_under_a_small_workspace():
     """tests/mic2_crops_chunking_check.py in a fresh process with a 7 MiB workspace ceiling.  A sub-batch holds
-    budget / (unit_ws_bytes(npx) + 2 npx) frames (mic2_frames_per_batch); for 150 x 70 = 10500 pixels the tier-2 slabs of a unit are
-    4 * 42016 (tokens, symbols) + 215136 (blob) + 8 * 21008 (segments) + 1312 (flags) + 26 * 65536 (tables) + 8192 = 2264704 bytes,
+    budget / (unit_ws_bytes(npx) + 2 npx) frames (mic2_batch_cuts over frames of one size); for 150 x 70 = 10500 pixels the tier-2 slabs
+    of a unit are 4 * 42016 (tokens, symbols) + 215136 (blob) + 8 * 21008 (segments) + 1312 (flags) + 26 * 65536 (tables) + 8192 = 2264704 bytes,
     with the frame 2285704: 7 MiB = 7340032 bytes hold three frames, 11 frames take four sub-batches and the carry crosses three
     seams (1 MiB steps are fine enough: 6 MiB would give two frames, 9 MiB four)."""
     env = dict(os.environ, MIC_HIP_WS_BUDGET_MB="7")

@@ -387,7 +387,7 @@ def test_both_kernels_are_timed_under_their_names(mic, volumes):
         got, st, bad, stats = _read(doors.session, xyzv, 48, 40, 3)
         assert np.array_equal(got, M.expected_multi(vols, xyzv, 48, 40, 3)) and stats["slabs"] == 1
         names = dict(doors.sess.last_timings())
-        assert "k_mic2_gather_crops" in names and "k_mic2_accumulate_crops_multi" in names, names
+        assert "k_mic2_gather_crops" in names and "k_mic2_accumulate_crops" in names, names
     finally:
         doors.close()
 
