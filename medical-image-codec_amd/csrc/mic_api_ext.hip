@@ -9,6 +9,7 @@
 // writes the container around the plane blobs.  Decode mirrors it: one batch over the planes of
 // the requested tiles, then inverse transform + crop on the device.
 #include "mic_session.h"
+#include "mic_wave.h"
 #include "mic_pieces.h"
 
 #include <memory>
@@ -63,8 +64,7 @@ __global__ void __launch_bounds__(256) k_wsi_tile_planes(const uint8_t *img, int
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { mn[k] = min(mn[k], (uint32_t)__shfl_xor((int)mn[k], d)); mx[k] = max(mx[k], (uint32_t)__shfl_xor((int)mx[k], d)); }
+        mn[k] = mic_wave_reduce_min(mn[k]); mx[k] = mic_wave_reduce_max(mx[k]);
         if ((threadIdx.x & 63) == 0) { atomicMin(&stats[((size_t)tile * 3 + k) * 2], mn[k]); atomicMax(&stats[((size_t)tile * 3 + k) * 2 + 1], mx[k]); }
     }
 }
@@ -122,8 +122,7 @@ __global__ void __launch_bounds__(256) k_wsi_tile_plane_grey(const T *img, int i
         pl[i] = (uint16_t)v;
         mn = min(mn, v); mx = max(mx, v);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, d)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d)); }
+    mn = mic_wave_reduce_min(mn); mx = mic_wave_reduce_max(mx);
     if ((threadIdx.x & 63) == 0) { atomicMin(&stats[(size_t)tile * 2], mn); atomicMax(&stats[(size_t)tile * 2 + 1], mx); }
 }
 

@@ -24,6 +24,7 @@
 #include "mic_dev.h"
 #include "mic_launch.h"
 #include "mic_rowpred.h"
+#include "mic_wave.h"
 
 typedef uint32_t rf_v4 __attribute__((ext_vector_type(4)));
 typedef rf_v4 RfQ __attribute__((aligned(2)));
@@ -329,34 +330,18 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
             // (rolled loops over the LDS row, a symbol at a time: escape rows are rare, and unrolled over registers the two passes are
             // what the kernel's register count would be set by)
             const uint32_t i0 = lane * CH;
-            uint32_t s0 = 0, s1 = 1, c0 = 0, c1 = 0;                     // exit state / pixels for entry state 0 and 1
+            typedef MicMarkerFn<15> Fn;
+            Fn tr;                                                       // exit state / pixels for entry state 0 and 1
 #pragma unroll 1
             for (int k = 0; k < CH; k++) {
                 const uint32_t x = sb16[i0 + k];
-                const uint32_t in = (i0 + k < have) ? 1u : 0u, d = (in && x == delim) ? 1u : 0u;
-                const uint32_t m0 = d & (s0 ^ 1u), m1 = d & (s1 ^ 1u);
-                c0 += in & (m0 ^ 1u); c1 += in & (m1 ^ 1u);
-                s0 = in ? m0 : s0; s1 = in ? m1 : s1;
+                const uint32_t in = (i0 + k < have) ? 1u : 0u;
+                tr.step((in && x == delim) ? 1u : 0u, in);
             }
-            uint32_t tr = s0 | (s1 << 1) | (c0 << 2) | (c1 << 17);
-            auto compose = [](uint32_t a, uint32_t b) -> uint32_t {       // a then b
-                const uint32_t a0 = a & 1u, a1 = (a >> 1) & 1u;
-                const uint32_t bc0 = (b >> 2) & 0x7FFFu, bc1 = b >> 17;
-                const uint32_t n0 = (b >> a0) & 1u, n1 = (b >> a1) & 1u;
-                const uint32_t q0 = ((a >> 2) & 0x7FFFu) + (a0 ? bc1 : bc0);
-                const uint32_t q1 = (a >> 17) + (a1 ? bc1 : bc0);
-                return n0 | (n1 << 1) | (q0 << 2) | (q1 << 17);
-            };
-            uint32_t incl = tr;
-#pragma unroll
-            for (int dd = 1; dd < 64; dd <<= 1) {
-                const uint32_t o = __shfl_up(incl, dd);
-                if (lane >= (uint32_t)dd) incl = compose(o, incl);
-            }
-            uint32_t excl = __shfl_up(incl, 1);
-            if (lane == 0) excl = 2u;                                    // identity: s0 = 0, s1 = 1, no pixels
-            uint32_t st = excl & 1u, pl = (excl >> 2) & 0x7FFFu;         // (a row starts behind a pixel: entry state 0)
-            const uint32_t total = ((uint32_t)__builtin_amdgcn_readlane((int)incl, 63) >> 2) & 0x7FFFu;
+            const uint32_t incl = mic_wave_incl_scan(tr.pack(), lane, [](uint32_t a, uint32_t b) { return Fn::compose(a, b); });
+            const uint32_t excl = mic_wave_prev(incl, lane, Fn::identity);
+            uint32_t st = Fn::state(excl, 0), pl = Fn::count(excl, 0);   // (a row starts behind a pixel: entry state 0)
+            const uint32_t total = Fn::count((uint32_t)__builtin_amdgcn_readlane((int)incl, 63), 0);
             if (total < (uint32_t)W) return;                             // more escapes than the slack holds: the other path
             uint16_t *const pb16 = (uint16_t *)pb;
             uint32_t last_at = 0xFFFFFFFFu;

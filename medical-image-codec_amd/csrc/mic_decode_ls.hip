@@ -29,6 +29,7 @@
 #include <type_traits>
 #include "mic_dev.h"
 #include "mic_launch.h"
+#include "mic_wave.h"
 
 // Table-size classes: streams per wave x waves per group are what the LDS holds of 2 << tableLog byte tables.
 //   tableLog 13: 3 x 3 = nine streams (159 120 bytes) | 14: 2 x 2 (136 256) | 15: 1 x 2 (134 736) | 16: 1 x 1 (133 392)
@@ -554,12 +555,6 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 #define TR_SEG (TR_TILE / 64)                     // tokens per walker lane
 #define TR_DENSE 6                                // headers in a tile from which on the next one is walked by all lanes
 static_assert(TR_SEG == 24 && TR_SEG * 64 == TR_TILE, "lane = position / 24 below is (position * 2731) >> 16");
-#define TR_DPP(x, ctrl, rmask) (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), (rmask), 0xF, false)
-__device__ __forceinline__ uint32_t tr_incl_add(uint32_t v) {             // wave-wide inclusive sum: row_shr 1/2/4/8, row_bcast 15 / 31
-    v += TR_DPP(v, 0x111, 0xF); v += TR_DPP(v, 0x112, 0xF); v += TR_DPP(v, 0x114, 0xF); v += TR_DPP(v, 0x118, 0xF);
-    v += TR_DPP(v, 0x142, 0xA); v += TR_DPP(v, 0x143, 0xC);
-    return v;
-}
 template <int TRTL>   // 13: tables up to 2^13 states (two groups per CU) | 16: up to 2^16 (128 KiB of LDS: one group per CU)
 __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
@@ -666,7 +661,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
             uint32_t oc = 0;
             for (uint32_t t = tm; t; t &= t - 1) { const uint32_t h = tile[s0 + (uint32_t)__builtin_ctz(t)]; oc += (h <= w_mid) ? h : h - w_mid; }
             const uint32_t hc = (uint32_t)__popc(tm);
-            const uint32_t ihc = tr_incl_add(hc), ioc = tr_incl_add(oc);
+            const uint32_t ihc = mic_wave_incl_add(hc), ioc = mic_wave_incl_add(oc);
             const uint32_t tot_h = ls_rl(ihc, 63), tot_o = ls_rl(ioc, 63);
             uint32_t idx = w_nseg + ihc - hc, o = w_out + ioc - oc, nval = 0;
             bool bad = ent != 0xFFu && ex == 0xFFFFFFFFu && w_out + ioc < w_cap;   // the zero header is reached before the stream has its symbols
@@ -684,7 +679,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
                 idx++; o += len;
             }
             if (__ballot(bad)) { w_on = false; w_err = true; continue; }
-            if (w_out + tot_o >= w_cap) { w_nseg += ls_rl(tr_incl_add(nval), 63); w_on = false; }   // the stream has its symbols: headers behind that are not read
+            if (w_out + tot_o >= w_cap) { w_nseg += ls_rl(mic_wave_incl_add(nval), 63); w_on = false; }   // the stream has its symbols: headers behind that are not read
             else w_nseg += tot_h;
             w_out += tot_o;
             w_pos = base + cur;

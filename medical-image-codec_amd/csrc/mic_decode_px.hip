@@ -17,6 +17,7 @@
 //                       step earlier (LDS hand-off, one barrier per step).
 #include "mic_dev.h"
 #include "mic_launch.h"
+#include "mic_wave.h"
 
 #define PX_THREADS 1024
 #define PX_WAVES (PX_THREADS / 64)
@@ -28,20 +29,6 @@
 #define PR_NARROW 1008                            // frames up to this many columns take 16-pixel groups (row buffer: 2 KiB per unit)
 #define PR_MAX_W 32768                            // its row buffer is 2 bytes per column of LDS
 struct __attribute__((packed, aligned(2))) PxVec { uint16_t v[PX_K]; };
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t o = __shfl_up(v, d);
-        if (lane >= (uint32_t)d) v += o;
-    }
-    return v;
-}
-
-// 2-state transition functions packed as f(0) | f(1) << 1; cmp(g, f) = g after f
-__device__ __forceinline__ uint32_t fn_compose(uint32_t g, uint32_t f) {
-    return ((g >> (f & 1)) & 1) | (((g >> ((f >> 1) & 1)) & 1) << 1);
-}
 
 // 8 waves per SIMD (= two groups per CU): keeps the kernel under 96 SGPRs and 64 VGPRs, which it nearly is anyway
 __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units) {
@@ -247,35 +234,13 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                 carry_px += cnt_all;
                 continue;
             }
-            uint32_t tr;
-            {
-                uint32_t s0 = 0, s1 = 1, c0 = 0, c1 = 0;
+            typedef MicMarkerFn<14> Fn;                                  // (a tile holds 8192 symbols)
+            Fn tr;
 #pragma unroll
-                for (int k = 0; k < PX_SPT; k++) {
-                    const uint32_t d = (dmask >> k) & 1u, v = (vmask >> k) & 1u;
-                    const uint32_t m0 = d & (s0 ^ 1u), m1 = d & (s1 ^ 1u);
-                    c0 += v & (m0 ^ 1u); c1 += v & (m1 ^ 1u);
-                    s0 = m0; s1 = m1;
-                }
-                tr = s0 | (s1 << 1) | (c0 << 2) | (c1 << 16);
-            }
-            auto compose = [](uint32_t a, uint32_t b) -> uint32_t {     // a then b
-                const uint32_t a0 = a & 1u, a1 = (a >> 1) & 1u;
-                const uint32_t bc0 = (b >> 2) & 0x3FFFu, bc1 = b >> 16;
-                const uint32_t n0 = (b >> a0) & 1u, n1 = (b >> a1) & 1u;
-                const uint32_t c0 = ((a >> 2) & 0x3FFFu) + (a0 ? bc1 : bc0);
-                const uint32_t c1 = (a >> 16) + (a1 ? bc1 : bc0);
-                return n0 | (n1 << 1) | (c0 << 2) | (c1 << 16);
-            };
-            uint32_t incl = tr;
-#pragma unroll
-            for (int dd = 1; dd < 64; dd <<= 1) {
-                const uint32_t o = __shfl_up(incl, dd);
-                if (lane >= (uint32_t)dd) incl = compose(o, incl);
-            }
+            for (int k = 0; k < PX_SPT; k++) tr.step((dmask >> k) & 1u, (vmask >> k) & 1u);
+            const uint32_t incl = mic_wave_incl_scan(tr.pack(), lane, [](uint32_t a, uint32_t b) { return Fn::compose(a, b); });
             if (lane == 63) s_fn[wave] = incl;
-            uint32_t excl = __shfl_up(incl, 1);
-            if (lane == 0) excl = 2u;                                    // identity: s0 = 0, s1 = 1, no pixels
+            const uint32_t excl = mic_wave_prev(incl, lane, Fn::identity);
             __syncthreads();
             MIC_STAMP_AT(u, 1);
             // entry (state, pixel count) of this wave and exit of the tile, from the 16 wave totals
@@ -285,13 +250,13 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                 for (uint32_t wv = 0; wv < PX_WAVES; wv++) {
                     if (wv == wave) { st_w = stt; cnt_w = cc; }
                     const uint32_t f = s_fn[wv];
-                    cc += stt ? (f >> 16) : ((f >> 2) & 0x3FFFu);
-                    stt = (f >> stt) & 1u;
+                    cc += Fn::count(f, stt);
+                    stt = Fn::state(f, stt);
                 }
                 st_all = stt; cnt_all = cc;
             }
-            uint32_t st_in = (excl >> st_w) & 1u;
-            uint32_t pl = cnt_w + (st_w ? (excl >> 16) : ((excl >> 2) & 0x3FFFu));    // tile-local pixel index
+            uint32_t st_in = Fn::state(excl, st_w);
+            uint32_t pl = cnt_w + Fn::count(excl, st_w);                 // tile-local pixel index
 #pragma unroll
             for (int k = 0; k < PX_SPT; k++) {
                 const uint32_t x = (w8[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
@@ -489,34 +454,8 @@ __global__ void __launch_bounds__(WIDE ? 64 : 256) k_dec_predict(MicUnit *units,
     const int P = max(ngrp, 64);
     const int nb = (H + 63) >> 6;
 
-    // ---- row 0: out[x] = raw ? sym : out[x-1] + sym - thr, out[-1] = 0; a scan of (reset, sum) pairs ----
-    {
-        uint16_t *row16 = (uint16_t *)s_rowbuf;
-        for (int x = (int)lane; x < ngrp * PR_K; x += 64) row16[x] = (x < W) ? px[x] : (uint16_t)0;
-        __builtin_amdgcn_s_waitcnt(0xC07F);                          // wave-private LDS: writes above land before the reads below
-        const int cw = (W + 63) >> 6;
-        const int x0 = min(W, (int)lane * cw), x1 = min(W, x0 + cw);
-        uint32_t rs = 0, sum = 0;
-        for (int x = x0; x < x1; x++) {
-            const uint32_t raw = (flags[x >> 5] >> (x & 31)) & 1u, v = row16[x];
-            if (raw) { rs = 1; sum = v; } else sum = (sum + v - thr) & 0xFFFFu;
-        }
-        // inclusive scan of the composition (a then b) = b.reset ? b : (a.reset, a.sum + b.sum)
-        uint32_t is = sum, ir = rs;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t os = __shfl_up(is, dd), orr = __shfl_up(ir, dd);
-            if (lane >= (uint32_t)dd && !ir) { is = (is + os) & 0xFFFFu; ir = orr; }
-        }
-        uint32_t cur = __shfl_up(is, 1);
-        if (lane == 0) cur = 0;
-        for (int x = x0; x < x1; x++) {
-            const uint32_t raw = (flags[x >> 5] >> (x & 31)) & 1u, v = row16[x];
-            cur = raw ? v : ((cur + v - thr) & 0xFFFFu);
-            row16[x] = (uint16_t)cur;
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);                          // wave-private LDS: writes above land before the reads below
-    }
+    // ---- row 0: left neighbours only ----
+    pr_row0_scan((uint16_t *)s_rowbuf, px, flags, W, ngrp * PR_K, thr, lane);
 
     // ---- the pipeline ----
     int32_t cg = -(int32_t)lane, cb = 0;                         // cursor of the NEXT group to fetch
@@ -663,31 +602,8 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
     const int steps = nb * P + 63;
 
     if (wave_c) {
-        // ---- row 0: out[x] = raw ? sym : out[x-1] + sym - thr, out[-1] = 0; a scan of (reset, sum) pairs (as in k_dec_predict) ----
-        uint16_t *row16 = (uint16_t *)s_rowbuf;
-        for (int x = (int)lane; x < ngrp * P2_K; x += 64) row16[x] = (x < W) ? px[x] : (uint16_t)0;
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        const int cw = (W + 63) >> 6;
-        const int x0 = min(W, (int)lane * cw), x1 = min(W, x0 + cw);
-        uint32_t rs = 0, sum = 0;
-        for (int x = x0; x < x1; x++) {
-            const uint32_t raw = (flags[x >> 5] >> (x & 31)) & 1u, v = row16[x];
-            if (raw) { rs = 1; sum = v; } else sum = (sum + v - thr) & 0xFFFFu;
-        }
-        uint32_t is = sum, ir = rs;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t os = __shfl_up(is, dd), orr = __shfl_up(ir, dd);
-            if (lane >= (uint32_t)dd && !ir) { is = (is + os) & 0xFFFFu; ir = orr; }
-        }
-        uint32_t cur = __shfl_up(is, 1);
-        if (lane == 0) cur = 0;
-        for (int x = x0; x < x1; x++) {
-            const uint32_t raw = (flags[x >> 5] >> (x & 31)) & 1u, v = row16[x];
-            cur = raw ? v : ((cur + v - thr) & 0xFFFFu);
-            row16[x] = (uint16_t)cur;
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        // ---- row 0: left neighbours only ----
+        pr_row0_scan((uint16_t *)s_rowbuf, px, flags, W, ngrp * P2_K, thr, lane);
     }
 
     // ---- wave M: tile mover -------------------------------------------------------------------------------------------------
@@ -724,9 +640,6 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
                 r[k] = pr_v4{0u, 0u, 0u, 0u};
                 if ((uint32_t)lc[k].cg < cmax) {
                     const uint32_t p = lc[k].p;
-#if defined(P2_ABL) && (P2_ABL & 2)
-                    r[k] = pr_v4{p, p, p, p};
-#else
                     if (p + 8 <= npx) r[k] = *(const __attribute__((address_space(1))) PrQ *)(px + p);
                     else {                                                   // the unit's last pixels: stay inside the buffer
                         uint32_t e[8];
@@ -734,7 +647,6 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
                         for (int j = 0; j < 8; j++) e[j] = (p + (uint32_t)j < npx) ? (uint32_t)px[p + j] : 0u;
                         r[k] = pr_v4{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
                     }
-#endif
                 }
                 cur_next(lc[k], 16 * k + (int)(lane >> 2), ch * 8);
             }
@@ -758,10 +670,8 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
                 if ((uint32_t)sc[k].cg < cmax) {
                     const pr_gu16 dst = px + sc[k].p;
                     const uint32_t cnt = ((uint32_t)sc[k].cg == cmax - 1) ? min(8u, crem) : 8u;
-#if !(defined(P2_ABL) && (P2_ABL & 4))
                     if (cnt == 8) { pr_v4 w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w; *(__attribute__((address_space(1))) PrQ *)dst = w; }   // (a non-temporal store here: 3.3 -> 4.0 ms)
                     else { const uint32_t d[4] = { v.x, v.y, v.z, v.w }; pr_store_cnt<8>(dst, d, (int)cnt); }
-#endif
                 }
                 cur_next(sc[k], line, ch * 8);
             }
@@ -825,12 +735,6 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
         }
         uint32_t (&res)[P2_DW] = last;                           // (every lane has read its neighbour's `last` by now)
         if (cg == 0) left = top[0] & 0xFFFFu;                    // column 0: predictor = top ((top+top)>>1)
-#if defined(P2_ABL) && (P2_ABL & 1)
-        if (true) {
-#pragma unroll
-            for (int i = 0; i < P2_DW; i++) res[i] = d[i] + top[i];
-        } else
-#endif
         if (!__any(raw != 0)) {
 #pragma unroll
             for (int i = 0; i < P2_DW; i++) {
@@ -882,9 +786,7 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
 // The row buffer is sized by the launch's width class (8 KiB, 16 KiB, PR_MAX_W columns), and only the classes the batch's widths
 // call for are launched.
 #define PG_Q 4
-#ifndef PG_AHEAD
 #define PG_AHEAD 1
-#endif
 __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_lo, int w_hi) {
     MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK || u.mode != 0 || !u.pred) return;
@@ -990,12 +892,10 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
 }
 
 void mic_launch_decode_pixels(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t, bool any_grad, uint32_t pred_mask) {
-#ifndef MIC_NO_FUSED       // (A / B builds: the two-kernel path for every unit)
     if (pred_mask & 0x7Fu) {
         if (t) t->mark("k_dec_rows_tok");
         mic_launch_decode_fused(d_units, n, stream, pred_mask & 0x7Fu);
     }
-#endif
     if (t) t->mark("k_dec_pixels_wg");
     hipLaunchKernelGGL(k_dec_pixels_wg, dim3(n), dim3(PX_THREADS), 0, stream, d_units);
     // row-buffer classes so that ordinary widths keep many waves per CU: a row buffer is 2 bytes per column and unit, four units per
@@ -1006,11 +906,7 @@ void mic_launch_decode_pixels(MicUnit *d_units, int n, hipStream_t stream, MicTi
     // frames of 1009 .. 2688 columns: row by row, the lanes side by side in a row (k_dec_predict_rows, mic_decode_rows.hip)
     static_assert(PR_NARROW == MIC_ROWS_LO, "the narrow class ends where the row-by-row class begins");
     if (t) t->mark("k_dec_predict_rows");
-#ifdef MIC_PREDICT2_ALL      // (A / B builds: the two-wave wavefront kernel of round 3 for those widths too)
-    hipLaunchKernelGGL(k_dec_predict2, dim3(n), dim3(128), (1344u + 2 * P2_TILE + 128) * 4, stream, d_units, PR_NARROW, MIC_ROWS_HI, 1344u);
-#else
     mic_launch_decode_rows(d_units, n, stream, pred_mask & 0x7Fu);
-#endif
     // wider frames: two waves per unit (k_dec_predict2: a mover wave and a computing wave over a 64-row band, 16 KiB of row buffer)
     if (t) t->mark("k_dec_predict2");
     if (pred_mask & MIC_PRED_WAVE2)

@@ -10,6 +10,7 @@
 #include "mic_dev.h"
 #include "mic_fse_tables.h"
 #include "mic_launch.h"
+#include "mic_wave.h"
 
 // ------------------------------------------------------------------------------------------
 // Parallel Delta(avg) + RLE tokeniser: one work-group of 1024 threads per unit.
@@ -38,25 +39,12 @@
 #define TK_WIN (TK_THREADS * TK_SPT)
 #define TK_HWIN 8192               // histogram window in LDS
 
-// Wave-wide inclusive scans on the DPP network (row_shr 1/2/4/8, then row_bcast 15 and 31); lanes
-// without a source read the identity 0, so the same shape serves add and max.
-#define TK_DPP(x, ctrl, rmask) __builtin_amdgcn_update_dpp(0u, (x), (ctrl), (rmask), 0xF, false)
-__device__ __forceinline__ uint32_t tk_wave_incl_add(uint32_t v, uint32_t) {
-    v += TK_DPP(v, 0x111, 0xF); v += TK_DPP(v, 0x112, 0xF); v += TK_DPP(v, 0x114, 0xF); v += TK_DPP(v, 0x118, 0xF);
-    v += TK_DPP(v, 0x142, 0xA); v += TK_DPP(v, 0x143, 0xC);
-    return v;
-}
-__device__ __forceinline__ uint32_t tk_wave_incl_max(uint32_t v, uint32_t) {
-    v = max(v, TK_DPP(v, 0x111, 0xF)); v = max(v, TK_DPP(v, 0x112, 0xF)); v = max(v, TK_DPP(v, 0x114, 0xF)); v = max(v, TK_DPP(v, 0x118, 0xF));
-    v = max(v, TK_DPP(v, 0x142, 0xA)); v = max(v, TK_DPP(v, 0x143, 0xC));
-    return v;
-}
 // TK_WAVES per-wave partials in LDS -> this wave's exclusive prefix and the group total (add / max).  Every lane
 // takes partial (lane & 7); a 3-step DPP scan inside the row and two lane reads replace a loop over the partials.
 __device__ __forceinline__ void tk_block16_add(const uint32_t *s, uint32_t wave, uint32_t &excl, uint32_t &total) {
     const uint32_t v = s[threadIdx.x & 7];
     uint32_t x = v;
-    x += TK_DPP(x, 0x111, 0xF); x += TK_DPP(x, 0x112, 0xF); x += TK_DPP(x, 0x114, 0xF);     // inclusive over lanes 0..7 of each row
+    x += mic_dpp<0x111>(0u, x); x += mic_dpp<0x112>(0u, x); x += mic_dpp<0x114>(0u, x);     // inclusive over lanes 0..7 of each row
     const uint32_t w = __builtin_amdgcn_readfirstlane(wave);
     total = __builtin_amdgcn_readlane(x, 7);
     excl = __builtin_amdgcn_readlane(x, w) - __builtin_amdgcn_readlane(v, w);
@@ -64,7 +52,7 @@ __device__ __forceinline__ void tk_block16_add(const uint32_t *s, uint32_t wave,
 __device__ __forceinline__ void tk_block16_max(const uint32_t *s, uint32_t wave, uint32_t &excl, uint32_t &total) {
     const uint32_t v = s[threadIdx.x & 7];
     uint32_t x = v;
-    x = max(x, TK_DPP(x, 0x111, 0xF)); x = max(x, TK_DPP(x, 0x112, 0xF)); x = max(x, TK_DPP(x, 0x114, 0xF));
+    x = max(x, mic_dpp<0x111>(0u, x)); x = max(x, mic_dpp<0x112>(0u, x)); x = max(x, mic_dpp<0x114>(0u, x));
     const uint32_t w = __builtin_amdgcn_readfirstlane(wave);
     total = __builtin_amdgcn_readlane(x, 7);
     excl = w ? __builtin_amdgcn_readlane(x, w - 1) : 0u;
@@ -324,7 +312,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
         if (esc_tile) {                                         // rare: an escape doubles its pixel, offsets need a scan (per half tile)
             const bool mine = (tid >> 8) == pass;
             const uint32_t mycnt = mine ? cnt : 0u;
-            const uint32_t incl = tk_wave_incl_add(mycnt, lane);
+            const uint32_t incl = mic_wave_incl_add(mycnt);
             if (lane == 63) s_cnt[wave] = incl;
             __syncthreads();
             uint32_t woff;
@@ -404,7 +392,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
         uint32_t run_in = 0, str_in = str1, run_tot = run1, str_tot = str1;
         if (!tile_fast) {
             // exclusive max-scan of the thread-latest starts (positions grow with the thread index)
-            const uint32_t run_incl = tk_wave_incl_max(my_run, lane), str_incl = tk_wave_incl_max(my_str, lane);
+            const uint32_t run_incl = mic_wave_incl_max(my_run), str_incl = mic_wave_incl_max(my_str);
             if (lane == 63) { s_run[wave] = run_incl; s_str[wave] = str_incl; }
             run_in = __shfl_up(run_incl, 1); str_in = __shfl_up(str_incl, 1);
             if (lane == 0) { run_in = 0; str_in = 0; }
@@ -490,7 +478,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
             pos = outp + p0 + (jq - c0);
             ttot = TP + (cT - c0);
         } else {
-            const uint32_t tincl = tk_wave_incl_add(tsum, lane);
+            const uint32_t tincl = mic_wave_incl_add(tsum);
             if (lane == 63) s_tc[wave] = tincl;
             __syncthreads();
             uint32_t toff;
@@ -660,7 +648,7 @@ __global__ void __launch_bounds__(TK_THREADS, TK_WPS) k_enc_tokens_wg(MicUnit *u
         if (vv) { if (hlo + i < tabcap) (void)__hip_atomic_fetch_add(&ghist[hlo + i], vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else s_ovf = 1; }
     }
     // what k_enc_tables_wg has to scan of the 65536 bins: the window and whatever was counted outside it
-    tmax = tk_wave_incl_max(tmax, lane);
+    tmax = mic_wave_incl_max(tmax);
     if (lane == 63 && tmax) atomicMax(&s_tmaxall, tmax);
     __syncthreads();
     if (tid < MIC_TK_PATHS) u.tk_paths[tid] = s_paths[tid];
@@ -797,19 +785,13 @@ __global__ void __launch_bounds__(64) k_enc_tans_serial(MicUnit *units) {
 // LDS: stateTable as u16 (state - 2^tl).  grid = units, block = 1024, dynamic LDS = 2 << tl.
 #define TE_THREADS 512              // two groups per CU (128 VGPRs each): the fix-up stalls of one overlap the other's work
 #define TE_WAVES 8
-#ifndef TE_THREADS16
 #define TE_THREADS16 1024         // threads of the tableLog-16 instance: its 128 KiB table leaves a CU one group whatever its size
-#endif
 #define TE_BLK 64                 // the largest block a walk reads at a time, in tokens (te_encode: BLK)
-#ifndef TE_WARM_TOK
 #define TE_WARM_TOK 128           // tokens of the predecessor's range a thread walks first (a multiple of 64)
-#endif
 #ifndef TE_NARROW_WPS
 #define TE_NARROW_WPS 6          // waves per SIMD the two-state instance is compiled for (6: three groups per CU; it needs 64 registers)
 #endif
-#ifndef TE_BLK2
 #define TE_BLK2 64                // tokens per block of the one- and two-state walks
-#endif
 #ifndef TE_ABL
 #define TE_ABL 0         // timing-only ablations: 1 = every block read comes from the unit's first 4 KiB, 2 = the pack pass stores nothing (and is optimised away), 4 = it does its work and stores nothing
 #endif
@@ -842,33 +824,20 @@ __device__ __forceinline__ void te_set(TeBlkT<B> &b, int j, uint32_t x) {
 // tokens are walked together (N independent LDS look-ups in flight), 64 bytes per memory access.
 // TTL: the per-symbol records (symbolTT / rANS freq+bias) were copied to LDS (alphabets up to TE_TT_SYMS);
 // otherwise every coding step gathers them from HBM.
-#if defined(TE_INLINE)
-#define TE_FN_ATTR __forceinline__
-#elif defined(TE_NOINLINE)
-#define TE_FN_ATTR __noinline__
-#else
-#define TE_FN_ATTR
-#endif
-#ifdef TE_BAR_VM        // diagnostic: every barrier of the walk also waits for the group's outstanding global memory operations
-#define TE_SYNC() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
-#else
-#define TE_SYNC() __syncthreads()
-#endif
 // Phase 4 of the walk below, and the trailer: thread t packs its blocks [b_lo, b_hi) from the true start states stp into the bit grid
 // `words` from grid bit gstart on; thread 0 then writes the final states fin (fse2state.go:194-197) and the end mark at grid bit pos.
 // BOUND (k_enc_tans_pack: the grid is the final buffer, where the unit's neighbours live): the 64-bit word holding the first grid byte
 // `lead` when that is not 8-aligned, and the one holding the last, end_b - 1, when that does not end a word, are shared with the
 // neighbours, which another group (on another XCD, behind another L2) writes at the same time.  Nothing of this group touches them in
 // HBM: every store and OR into them goes to s_edge[2] in LDS (zeroed by the caller), and thread 0 stores their own bytes at the end.
-// Returns the bits packed (TE_CHECK builds compare them with the walk's).
 #ifndef TE_RING
 #define TE_RING 4                 // units of a store group (a power of two): 4 = 32 bytes, a memory sector
 #endif
 template <int N, int BLK, bool BOUND, class Step>
-__device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> src, mic_gp<uint32_t> words, uint64_t gstart,
-                                            uint32_t b_lo, uint32_t b_hi, uint32_t n, uint32_t (&stp)[N], uint32_t mybits,
-                                            uint64_t pos, const uint32_t (&fin)[N], uint32_t tl, uint64_t lead, uint64_t end_b,
-                                            unsigned long long *s_edge) {
+__device__ __forceinline__ void te_pack(Step &step, mic_gp<const uint16_t> src, mic_gp<uint32_t> words, uint64_t gstart,
+                                        uint32_t b_lo, uint32_t b_hi, uint32_t n, uint32_t (&stp)[N], uint32_t mybits,
+                                        uint64_t pos, const uint32_t (&fin)[N], uint32_t tl, uint64_t lead, uint64_t end_b,
+                                        unsigned long long *s_edge) {
     typedef TeBlkT<BLK> TeBlk;
     const uint32_t tid = threadIdx.x;
     // 64-bit units, stored in aligned PAIRS (16 bytes): the memory counters charge every store instruction a 32-byte write whatever
@@ -924,7 +893,6 @@ __device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> s
         }
         q++;
     };
-    uint32_t pbits = 0;
     // Four tokens (<= 64 bits) are gathered branch-free before they meet the accumulator: the test "does a 64-bit unit fill up"
     // is a divergent branch that some lane takes at almost every token, so it is made once per four of them.
     for (uint32_t b = b_hi; b > b_lo; b--) {
@@ -947,9 +915,6 @@ __device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> s
                     f4 += nb;
                 }
             }
-#ifdef TE_CHECK
-            pbits += f4;
-#endif
             acc |= t4 << filled;                                             // filled < 64
             const uint32_t nf = filled + f4;
             if (nf >= 64) {
@@ -962,17 +927,13 @@ __device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> s
     if (mybits > 0 && filled > 0) emit(acc);                             // the thread's last, partial unit
     if ((TE_ABL & 4) && abl_chk == 0x1234567ull) words64[first_q] = abl_chk;
     if (rmask) flush4((q - 1u) & ~(TE_RING - 1u), 0ull, false);           // (a group the next thread completes)
-#ifdef TE_NO_HANDOFF    // diagnostic: the barrier round 3 had here before MIC_GROUP_HANDOFF
-    __threadfence_block(); __syncthreads();
-#else
     MIC_GROUP_HANDOFF();                                   // (every unit is in L2 before anything is OR-ed into it)
-#endif
     if (have_lead && lead_val) {
         if (edge(first_q) >= 0) or_edge(edge(first_q), lead_val);
         else (void)__hip_atomic_fetch_or(&words64[first_q], (unsigned long long)lead_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __threadfence_block();
-    TE_SYNC();
+    __syncthreads();
     if (tid == 0) {
         // final states, last lane first (fse2state.go:194-197), then the end mark.  The word the symbols' last bit lies in is shared
         // with the atomic ORs other threads have just made (executed at L2, nothing here waits for them): the trailer ORs its bits in
@@ -981,15 +942,11 @@ __device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> s
         const uint64_t end = pos + (uint64_t)N * tl + 1;
         for (uint64_t ww = (pos + 31) >> 5; ww <= ((end - 1) >> 5); ww++) if (edge(ww >> 1) < 0) words[ww] = 0;   // (s_edge starts at zero)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef TE_OLD_TRAILER   // diagnostic: round 3's trailer, a plain read-modify-write of the shared word
-        auto or32 = [&](uint32_t wi, uint32_t bits) { words[wi] |= bits; };
-#else
         auto or32 = [&](uint32_t wi, uint32_t bits) {
             if (!bits) return;
             if (edge(wi >> 1) >= 0) or_edge(edge(wi >> 1), (uint64_t)bits << (32 * (wi & 1)));
             else (void)__hip_atomic_fetch_or(&words[wi], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
-#endif
         for (int k = N - 1; k >= 0; k--) {
             const uint64_t v = (uint64_t)fin[k] & (((uint64_t)1 << tl) - 1);  // addBits32NC(state, tl)
             const uint32_t wi = (uint32_t)(pos >> 5), sh = (uint32_t)(pos & 31);
@@ -1007,20 +964,15 @@ __device__ __forceinline__ uint32_t te_pack(Step &step, mic_gp<const uint16_t> s
             }
         }
     }
-    return pbits;
 }
 
 template <int N, bool RANS, bool TTL, int T, bool FS, bool DEFER = false>   // FS: the LDS state table holds whole states (they fit 16 bits up to tableLog 15);
                                                                        // DEFER: stop after phase 3 (the records are what k_enc_tans_pack starts from)
-__device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *s_tt,
+__device__ void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *s_tt,
                           uint16_t *s_E, uint32_t *s_scan, int &rc_out, uint32_t &total_bytes_out) {   // s_E: T x N end states
     // tokens per block: the two-state walk (the usual flavour) reads a whole 128-byte line at a time (two 64-byte halves read apart were two
     // fetches: the line does not survive in a cache between them); the wider walks have no registers for that
-#ifdef TE_BLK1_64   // diagnostic: the one-state walk on whole lines too (the state of the code when round 3 saw the differences)
-    constexpr int BLK = (N <= 2 && !RANS && TTL) ? TE_BLK2 : 32;
-#else
     constexpr int BLK = (N == 2 && !RANS && TTL) ? TE_BLK2 : 32;
-#endif
     constexpr uint32_t RGRP = 128 / BLK, WARM = TE_WARM_TOK / BLK;   // blocks per fix-up record (128 tokens); blocks of the predecessor's range walked as warm-up
     typedef TeBlkT<BLK> TeBlk;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1133,7 +1085,7 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
     MIC_STAMP_AT(u, 8);
     // ---- 2. fix-up rounds to the fixed point -----------------------------------------------------
     for (uint32_t round = 0; round < T; round++) {
-        TE_SYNC();
+        __syncthreads();
         int changed = 0;
         uint32_t e_out[N], st2[N]; bool any = false;
 #pragma unroll
@@ -1173,7 +1125,7 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
                 for (int k = 0; k < N; k++) if (st2[k] != e_out[k]) { e_out[k] = st2[k]; changed = 1; }
             }
         }
-        TE_SYNC();                                   // every thread has read its predecessor's states
+        __syncthreads();                                   // every thread has read its predecessor's states
 #pragma unroll
         for (int k = 0; k < N; k++) s_E[(tid) * N + k] = (uint16_t)(e_out[k] - size);
 #ifdef MIC_STAMP
@@ -1181,7 +1133,7 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
 #endif
         if (!__syncthreads_or(changed)) break;
     }
-    TE_SYNC();
+    __syncthreads();
     // empty tail threads may not have been reached by a round: propagate the final states down
     // (thread T-1 must hold the end states of every chain for the trailer)
     if (tid == 0) {
@@ -1190,38 +1142,18 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
         for (int k = 0; k < N; k++) s_E[(T - 1) * N + k] = s_E[(last) * N + k];
     }
     __threadfence_block();
-    TE_SYNC();
-#ifdef TE_CHECK     // diagnostic: the walk's invariants, reported through u.dbg[15] (the kernel turns it into a status)
-    {
-        const uint32_t lastown_c = (nblk + per - 1) / per; uint32_t bad = 0;
-        if (tid > 0 && tid < lastown_c) for (int k = 0; k < N; k++) if (assumed[k] != (uint32_t)s_E[(tid - 1) * N + k] + size) bad |= 1u;
-        if (bad) { atomicOr(&u.dbg[15], bad); atomicMin(&u.dbg[14], tid | 0x10000u); }
-    }
-#endif
+    __syncthreads();
     MIC_STAMP_AT(u, 9);
     // ---- 3. bit offsets ---------------------------------------------------------------------------
-    const uint32_t incl = tk_wave_incl_add(mybits, lane);
+    const uint32_t incl = mic_wave_incl_add(mybits);
     if (lane == 63) s_scan[wave] = incl;
-    TE_SYNC();
+    __syncthreads();
     uint32_t woff = 0, sym_bits = 0;
 #pragma unroll
     for (int wv = 0; wv < (T / 64); wv++) { const uint32_t v = s_scan[wv]; if ((uint32_t)wv < wave) woff += v; sym_bits += v; }
     const uint64_t gstart = 8ull * lead + woff + incl - mybits;            // first grid bit of this thread
     const uint64_t total_bits = (uint64_t)sym_bits + (uint64_t)N * tl + 1;
     const uint32_t total_bytes = (uint32_t)((total_bits + 7) >> 3);
-#ifdef MIC_GATE_REG
-    // diagnostic build: every thread forms the verdict from its own registers (the variant that misbehaved in round 1)
-    int rc_reg = MICD_OK;
-    if ((8ull * lead + total_bits + 255) / 32 >= words_cap) rc_reg = MICD_ERR_CAPACITY;
-    else if ((uint64_t)hdr_len + total_bytes >= (uint64_t)n * 2) rc_reg = MICD_ERR_INCOMPRESSIBLE;
-#ifdef MIC_GATE_REG2
-    if (rc_reg == MICD_ERR_CAPACITY) { total_bytes_out = total_bytes; rc_out = rc_reg; return; }   // (the verdict itself is used after the pack loop)
-#else
-    total_bytes_out = total_bytes; rc_out = rc_reg;
-    if (rc_reg != MICD_OK) return;
-#endif
-    const int rc = rc_reg; (void)rc;
-#else
     // the verdict goes through LDS so that every thread (and the caller) sees one value
     if (tid == 0) {
         int rc0 = MICD_OK;
@@ -1229,12 +1161,11 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
         else if ((uint64_t)hdr_len + total_bytes >= (uint64_t)n * 2) rc0 = MICD_ERR_INCOMPRESSIBLE;   // fse2state.go:58-60
         s_scan[(T / 64)] = (uint32_t)rc0; s_scan[(T / 64) + 1] = total_bytes;
     }
-    TE_SYNC();
+    __syncthreads();
     const int rc = (int)s_scan[(T / 64)];
     total_bytes_out = s_scan[(T / 64) + 1];
     rc_out = rc;
     if (rc != MICD_OK) return;
-#endif
     MIC_STAMP_AT(u, 10);
     if (DEFER) return;                                   // (the records hold the true states: k_enc_tans_pack packs into the final buffer)
     // ---- 4. pack -------------------------------------------------------------------------------------
@@ -1246,19 +1177,8 @@ __device__ TE_FN_ATTR void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *
             stp[k] = (tid > 0 && tid < lastown) ? (uint32_t)s_E[(tid - 1) * N + k] + size : size;
             fin[k] = (uint32_t)s_E[(T - 1) * N + k] + size;
         }
-        const uint32_t pbits = te_pack<N, BLK, false>(step, src, words, gstart, b_lo, b_hi, n, stp, mybits, 8ull * lead + sym_bits, fin, tl, lead, 0, nullptr);
-        (void)pbits;
-#ifdef TE_CHECK
-        {
-            uint32_t bad = pbits != mybits ? 2u : 0u;
-            if (tid < lastown && tid != T - 1) for (int k = 0; k < N; k++) if (stp[k] != (uint32_t)s_E[tid * N + k] + size) bad |= 4u;
-            if (bad) { atomicOr(&u.dbg[15], bad); atomicMin(&u.dbg[13], tid | 0x10000u); }
-        }
-#endif
+        te_pack<N, BLK, false>(step, src, words, gstart, b_lo, b_hi, n, stp, mybits, 8ull * lead + sym_bits, fin, tl, lead, 0, nullptr);
     }
-#ifdef MIC_GATE_REG2
-    total_bytes_out = total_bytes; rc_out = rc_reg;
-#endif
     MIC_STAMP_AT(u, 11);
 }
 
@@ -1295,11 +1215,7 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
     if (u.status != MICD_OK) return;
     const bool handed = u.nstates_used == -2;                              // the two-state instance gave up on its first attempt (below)
     if (u.nstates_used != 0 && !(WIDTH == 2 && handed)) return;
-#ifdef TE_COMBINED   // diagnostic build: the round-3 layout in which one-state streams differed from call to call
-    if (WIDTH != 0 && ((u.nstates > 2 || u.symbol_len > TTS || handed) ? 2 : 1) != WIDTH) return;
-#else
     if (WIDTH != 0 && ((u.nstates != 2 || u.symbol_len > TTS || handed) ? 2 : 1) != WIDTH) return;   // (1: two states, coding records in LDS)
-#endif
     if ((u.nstates == 108 ? 8 : (int)u.nstates) > e_states) { if (threadIdx.x == 0) u.status = MICD_ERR_INTERNAL; return; }   // (the launcher sizes the LDS for e_states)
     const uint32_t tl = u.table_log;
     if (tl < tl_lo || tl > tl_hi) return;
@@ -1331,9 +1247,7 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
                 else if (WIDTH != 1 && lanes == 8) te_encode<8, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
                 else if (WIDTH != 1 && lanes == 4) te_encode<4, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
                 else if (lanes == 2) te_encode<2, false, true, T, (TLHI <= 15), (WIDTH == 1)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
-#ifndef TE_COMBINED
                 else if (WIDTH == 1) rc = MICD_ERR_INTERNAL;                            // (not reached: the two-state instance hands its fall-backs over)
-#endif
                 else te_encode<1, false, true, T, (TLHI <= 15)>(u, s_stab, s_tt, s_E, s_scan, rc, total_bytes);
             } else {
                 if (WIDTH == 1) rc = MICD_ERR_INTERNAL;                                 // (not reached: such units go to the wide instance)
@@ -1345,13 +1259,6 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
             }
         }
         __syncthreads();
-#ifdef TE_CHECK
-        {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
-            const uint32_t d = __hip_atomic_load(&u.dbg[15], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (d) { if (tid == 0) u.status = -40 - (int)d; return; }
-        }
-#endif
         if (rc == MICD_OK) {
             if (tid == 0) {
                 if (lanes != 1) {
@@ -1370,9 +1277,7 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
         if (tid == 0) { u.count = (uint32_t)rc; u.bits_off = total_bytes; u.flavour = lanes; }   // probe: why the attempt failed
         if (rc == MICD_ERR_CAPACITY && u.tier == 1) rc = MICD_INT_GROW;               // (the staging blob is tier 1's)
         if (lanes == 1 || rc == MICD_ERR_CAPACITY || rc == MICD_INT_GROW || single) { if (tid == 0) u.status = rc; return; }
-#ifndef TE_COMBINED
         if (WIDTH == 1) { if (tid == 0) u.nstates_used = -2; return; }        // the one-state attempt is the wide instance's (it starts over)
-#endif
         __syncthreads();
     }
 }
@@ -1434,7 +1339,7 @@ __global__ void __launch_bounds__(T, TE_NARROW_WPS) k_enc_tans_pack(const MicUni
             fin[k] = ((wf >> (16 * k)) & 0xFFFFu) + size;
         }
     }
-    const uint32_t incl = tk_wave_incl_add(mybits, lane);
+    const uint32_t incl = mic_wave_incl_add(mybits);
     if (lane == 63) s_scan[wave] = incl;
     __syncthreads();
     uint32_t woff = 0, sym_bits = 0;
@@ -1451,7 +1356,7 @@ __global__ void __launch_bounds__(T, TE_NARROW_WPS) k_enc_tans_pack(const MicUni
         nb_out = nb;
         return s_stab[(int32_t)(state >> nb) + (int32_t)r.y];
     };
-    (void)te_pack<N, BLK, true>(step, mic_g((const uint16_t *)u.tok), words, 8ull * lead + woff + incl - mybits, b_lo, b_hi, n, stp, mybits,
+    te_pack<N, BLK, true>(step, mic_g((const uint16_t *)u.tok), words, 8ull * lead + woff + incl - mybits, b_lo, b_hi, n, stp, mybits,
                                 8ull * lead + sym_bits, fin, tl, lead, end_b, s_edge);
 }
 

@@ -13,6 +13,7 @@
 // it see a plain FSE stream; k_dec_gap_expand rewrites tab_sym (symbol of each state) through the map once the tables stand, so the
 // decoders emit the original tokens at no cost per symbol, in the class of the COMPACT table's log.
 #include "mic_launch.h"
+#include "mic_wave.h"
 
 #define GAP_THREADS 256
 #define GAP_WAVES (GAP_THREADS / 64)
@@ -20,31 +21,18 @@
 
 // exclusive prefix sum over the work-group; *total = the sum of all.  (every thread calls it; it ends on a barrier)
 __device__ __forceinline__ uint32_t gap_scan_add(uint32_t v, uint32_t *s_w, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if ((int)lane >= d) x += y; }
-    if (lane == 63) s_w[wave] = x;
+    const uint32_t ex = mic_group_excl_add<GAP_WAVES>(v, s_w, total);
     __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t k = 0; k < GAP_WAVES; k++) { const uint32_t t = s_w[k]; if (k < wave) before += t; all += t; }
-    __syncthreads();
-    *total = all;
-    return before + x - v;
+    return ex;
 }
-// exclusive prefix maximum (identity -1) and the maximum of all
+// exclusive prefix maximum (identity -1) and the maximum of all, of values >= -1: scanned as v + 1 on the unsigned maximum, whose
+// identity is 0.  (it ends on a barrier too)
 __device__ __forceinline__ int32_t gap_scan_max(int32_t v, int32_t *s_w, int32_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    int32_t x = v;
-    for (int d = 1; d < 64; d <<= 1) { const int32_t y = __shfl_up(x, d, 64); if ((int)lane >= d) x = max(x, y); }
-    int32_t ex = __shfl_up(x, 1, 64);
-    if (lane == 0) ex = -1;
-    if (lane == 63) s_w[wave] = x;
+    uint32_t all;
+    const uint32_t ex = mic_group_excl_max<GAP_WAVES>((uint32_t)(v + 1), (uint32_t *)s_w, &all);
     __syncthreads();
-    int32_t before = -1, all = -1;
-    for (uint32_t k = 0; k < GAP_WAVES; k++) { const int32_t t = s_w[k]; if (k < wave) before = max(before, t); all = max(all, t); }
-    __syncthreads();
-    *total = all;
-    return max(before, ex);
+    *total = (int32_t)all - 1;
+    return (int32_t)ex - 1;
 }
 
 // One step of the walk over the histogram: the four bins of this thread at `base`, the used values among them, their compact
@@ -187,8 +175,7 @@ __global__ void __launch_bounds__(64) k_dec_gap_map(MicUnit *units) {
                 };
                 uint32_t cnt = 0;
                 for (uint32_t b = lo; b < hi; b++) cnt += __popc(byte_at(b));
-                uint32_t x = cnt;
-                for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if ((int)lane >= d) x += y; }
+                const uint32_t x = mic_wave_incl_add(cnt);
                 uint32_t idx = x - cnt;
                 nsym = __shfl(x, 63, 64);
                 for (uint32_t b = lo; b < hi; b++)

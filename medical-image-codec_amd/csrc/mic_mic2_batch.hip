@@ -23,6 +23,7 @@
 //   k_mic2_assemble    the session form's files: headers, frame tables and the streams moved to their final byte offsets.
 #include <climits>
 #include "mic_session.h"
+#include "mic_wave.h"
 #include "mic_pieces.h"
 
 void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode_filter);   // mic_wavelet.hip
@@ -68,8 +69,7 @@ __global__ void __launch_bounds__(256) k_mic2_residual(MicUnit *units, const Res
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+    m = mic_wave_reduce_max(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(&units[r.unit].dec_thr, m);
 }
 // a residual unit's max_value is its largest symbol (multiframecompress.go:146-163)

@@ -7,6 +7,7 @@
 // read-back of the boundaries), and the pick of each strip's winner between the tANS walk and the pack.  The host pipeline that
 // drives them -- sub-batches, staging, containers -- is with the other containers' in mic_host_io.hip.
 #include "mic_session.h"
+#include "mic_wave.h"
 
 namespace {
 
@@ -30,8 +31,7 @@ __global__ void __launch_bounds__(256) k_pica_rowcost(const uint16_t *px, const 
         sum += __sad((unsigned)va.x, (unsigned)vb.x, __sad((unsigned)va.y, (unsigned)vb.y, __sad((unsigned)va.z, (unsigned)vb.z, __sad((unsigned)va.w, (unsigned)vb.w, 0u))));
     }
     { const int x = (w & ~3) + (int)threadIdx.x; if (x < w) sum += __sad((unsigned)a[x], (unsigned)b[x], 0u); }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    sum = mic_wave_reduce_add((uint64_t)sum);
     __shared__ unsigned long long s_part[4];
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sum;
     __syncthreads();

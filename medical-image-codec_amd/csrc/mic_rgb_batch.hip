@@ -8,6 +8,7 @@
 // This file holds the kernels, the core on device buffers (rgb_encode_run / rgb_decode_run) and the session entry points; the host
 // pipeline -- sub-batches, staging, devices -- is with the other containers' in mic_host_io.hip.
 #include "mic_session.h"
+#include "mic_wave.h"
 
 namespace {
 
@@ -108,8 +109,7 @@ __global__ void __launch_bounds__(256) k_rgb_batch_planes(const uint8_t *rgb, co
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { mn[k] = min(mn[k], (uint32_t)__shfl_xor((int)mn[k], d)); mx[k] = max(mx[k], (uint32_t)__shfl_xor((int)mx[k], d)); }
+        mn[k] = mic_wave_reduce_min(mn[k]); mx[k] = mic_wave_reduce_max(mx[k]);
         if ((tid & 63) == 0 && mn[k] <= mx[k]) { atomicMin(&stats[((size_t)im.slot * 3 + k) * 2], mn[k]); atomicMin(&stats[((size_t)im.slot * 3 + k) * 2 + 1], ~mx[k]); }
     }
 }

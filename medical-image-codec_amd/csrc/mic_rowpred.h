@@ -24,11 +24,9 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "mic_wave.h"
 
 #define RW_NEVER 65536u
-template <int CTRL, int RMASK> __device__ __forceinline__ uint32_t rw_dpp(uint32_t old, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, RMASK, 0xF, false);
-}
 #ifndef RW_ABL
 #define RW_ABL 0      // timing-only ablations (the output is wrong): 1 = no stores, 2 = one row's loads only, 4 = no pass 1 / scan, 8 = no pass 2
 #endif
@@ -128,13 +126,13 @@ template <int K> struct RowPred {
                 const uint32_t thh = (th == cg + 1u) ? tg : RW_NEVER;
                 c = has ? ch : c; th = has ? thh : th;
             };
-            { const uint32_t cg = rw_dpp<0x111, 0xF>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x111, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 1u); }
-            { const uint32_t cg = rw_dpp<0x112, 0xF>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x112, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 2u); }
-            { const uint32_t cg = rw_dpp<0x114, 0xF>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x114, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 4u); }
-            { const uint32_t cg = rw_dpp<0x118, 0xF>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x118, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 8u); }
-            { const uint32_t cg = rw_dpp<0x142, 0xA>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x142, 0xA>(th, th); step(cg, tg, ((lane >> 4) & 1u) != 0u); }
-            { const uint32_t cg = rw_dpp<0x143, 0xC>((uint32_t)c, (uint32_t)c), tg = rw_dpp<0x143, 0xC>(th, th); step(cg, tg, lane >= 32u); }
-            v = rw_dpp<0x138, 0xF>(lo(tp[0]), (uint32_t)c);              // wave_shr:1 -- the left neighbour; lane 0: the pixel above
+            { const uint32_t cg = mic_dpp<0x111, 0xF>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x111, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 1u); }
+            { const uint32_t cg = mic_dpp<0x112, 0xF>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x112, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 2u); }
+            { const uint32_t cg = mic_dpp<0x114, 0xF>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x114, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 4u); }
+            { const uint32_t cg = mic_dpp<0x118, 0xF>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x118, 0xF>(th, th); step(cg, tg, (lane & 15u) >= 8u); }
+            { const uint32_t cg = mic_dpp<0x142, 0xA>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x142, 0xA>(th, th); step(cg, tg, ((lane >> 4) & 1u) != 0u); }
+            { const uint32_t cg = mic_dpp<0x143, 0xC>((uint32_t)c, (uint32_t)c), tg = mic_dpp<0x143, 0xC>(th, th); step(cg, tg, lane >= 32u); }
+            v = mic_dpp<0x138, 0xF>(lo(tp[0]), (uint32_t)c);              // wave_shr:1 -- the left neighbour; lane 0: the pixel above
         } else v = lo(tp[0]);
         __builtin_amdgcn_sched_barrier(0);
         // ---- pass 2: the chunk, and whether anything left 0..65535 on the way ----

@@ -17,6 +17,7 @@
 #include "mic_fse_tables.h"
 #include "mic_tables_par.h"
 #include "mic_launch.h"
+#include "mic_wave.h"
 
 #define TB_SMALL_SYMS 8192
 #define TB_SMALL_TL 13
@@ -31,12 +32,6 @@
 #define TB_OFF_BIG    (64 * 1024 + 16512)    // uint32[4096 + 2]
 #define TB_OFF_TMP    (64 * 1024 + 32960)    // uint32[128]
 #define TB_LDS_BYTES  (64 * 1024 + 32960 + 512)    // ~96.4 KiB  (1 group / CU; the small path alone would fit 2)
-
-__device__ __forceinline__ uint32_t tb_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------
 // writeCount (fsecompressu16.go:191-289) on the whole group, for tableLog <= 14 (a field is at most
@@ -76,17 +71,10 @@ __device__ int tb_write_ncount_par(const NormT *norm, uint32_t symbol_len, uint3
         const uint32_t ex = tp_block_excl((uint32_t)(v < 0 ? -v : v), s_tmp, &tot);
         // exclusive max-scan of (index + 1) of first zeros
         const uint32_t fz = (s2 < symbol_len && v == 0 && vp != 0) ? s2 + 1 : 0u;
-        uint32_t mi = fz;
-        const uint32_t lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(mi, d); if (lane >= (uint32_t)d) mi = max(mi, o); }
-        uint32_t me = __shfl_up(mi, 1); if (lane == 0) me = 0;
         __syncthreads();
-        if (lane == 63) s_tmp[32 + wave] = mi;
-        __syncthreads();
-        uint32_t mtot = carry_fz;
-        for (uint32_t w = 0; w < TP_WAVES; w++) { const uint32_t x = s_tmp[32 + w]; if (w < wave) me = max(me, x); mtot = max(mtot, x); }
-        me = max(me, carry_fz);
+        uint32_t mtot;
+        const uint32_t me = max(mic_group_excl_max<TP_WAVES>(fz, s_tmp + 32, &mtot), carry_fz);
+        mtot = max(mtot, carry_fz);
         if (s2 < symbol_len) { rem16[s2] = (ScrT)(size + 1 - (carry_sum + ex)); s016[s2] = (ScrT)me; }
         carry_sum += tot; carry_fz = mtot;
     }
@@ -194,16 +182,9 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             norm[s] = (NormT)nv;
         }
         // reduce: sum(used); argmax(best_p) with the smallest symbol index on ties
-        uint32_t sum = used;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d);
+        const uint32_t sum = mic_wave_reduce_add(used);
         // key = proba << 17 | (65536 - s)  -> larger proba wins, then smaller s   (proba <= 65536 -> use 64 bit)
-        unsigned long long key = ((unsigned long long)best_p << 20) | (unsigned long long)(0xFFFFF - best_s);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const unsigned long long o = (unsigned long long)__shfl_xor((long long)key, d);
-            key = key > o ? key : o;
-        }
+        const unsigned long long key = mic_wave_reduce_max((uint64_t)(((unsigned long long)best_p << 20) | (unsigned long long)(0xFFFFF - best_s)));
         __syncthreads();
         if (lane == 0) { s_tmp[wave] = sum; ((unsigned long long *)(s_tmp + 32))[wave] = key; }
         __syncthreads();
@@ -229,8 +210,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             const int32_t not_yet = -2;
             uint64_t *s_t64 = (uint64_t *)(s_tmp + 32);                  // 16 wave partials + spare, 8-byte aligned
             auto reduce2 = [&](uint32_t a, uint64_t b, uint32_t &ra, uint64_t &rb) {
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) { a += (uint32_t)__shfl_xor((int)a, d); b += (uint64_t)__shfl_xor((long long)b, d); }
+                a = mic_wave_reduce_add(a); b = mic_wave_reduce_add(b);
                 __syncthreads();
                 if (lane == 0) { s_tmp[wave] = a; s_t64[wave] = b; }
                 __syncthreads();
@@ -286,9 +266,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
                     const uint32_t s2 = base + tid;
                     const bool ny = s2 < symbol_len && (int32_t)norm[s2] == not_yet;
                     const uint64_t val = ny ? (uint64_t)hist[s2] * r_step : 0ull;
-                    uint64_t incl = val;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) { const uint64_t o = (uint64_t)__shfl_up((long long)incl, d); if (lane >= (uint32_t)d) incl += o; }
+                    const uint64_t incl = mic_wave_incl_scan(val, lane, [](uint64_t a, uint64_t b) { return a + b; });
                     __syncthreads();
                     if (lane == 63) s_t64[wave] = incl;
                     __syncthreads();
@@ -420,7 +398,7 @@ __global__ void __launch_bounds__(TP_THREADS) k_enc_tables_wg(MicUnit *units) {
         const uint32_t c = u.hist[i];
         if (c) { m = max(m, c); sl = max(sl, i + 1); }
     }
-    m = tb_wave_max(m); sl = tb_wave_max(sl);
+    m = mic_wave_reduce_max(m); sl = mic_wave_reduce_max(sl);
     if (lane == 0) { s_tmp[wave] = m; s_tmp[16 + wave] = sl; }
     __syncthreads();
     if (tid == 0) {

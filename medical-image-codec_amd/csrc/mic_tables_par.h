@@ -17,30 +17,17 @@
 // stateTable[cumul[s] + rank] = size + position, the decoder the transition of that position.
 #pragma once
 #include "mic_dev.h"
+#include "mic_wave.h"
 
 #define TP_THREADS 1024
 #define TP_WAVES 16
 #define TP_SMALLV 16          // symbols with up to this many slots are ranked by one thread
 
-__device__ __forceinline__ uint32_t tp_wave_incl_add(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(v, d); if (lane >= (uint32_t)d) v += o; }
-    return v;
-}
-
 // Work-group exclusive scan of one value per thread; returns the exclusive prefix, *total = sum.
-// s_tmp: TP_WAVES words of LDS.  Contains two barriers.
+// s_tmp: TP_WAVES words of LDS.  Contains two barriers: it begins on one (s_tmp may still be read from the call before).
 __device__ __forceinline__ uint32_t tp_block_excl(uint32_t v, uint32_t *s_tmp, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t incl = tp_wave_incl_add(v, lane);
     __syncthreads();
-    if (lane == 63) s_tmp[wave] = incl;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < TP_WAVES; w++) { const uint32_t x = s_tmp[w]; if ((uint32_t)w < wave) off += x; tot += x; }
-    *total = tot;
-    return off + incl - v;
+    return mic_group_excl_add<TP_WAVES>(v, s_tmp, total);
 }
 
 // Scratch handed to the core.  NormT/IdxT: int16/uint16 when everything lives in LDS
@@ -143,7 +130,7 @@ __device__ int tp_build(const TpScratch<NormT, IdxT> &S, uint32_t symbol_len, ui
             uint32_t c[4], tot = 0;                                         // lane l owns words 4 l .. 4 l + 3
 #pragma unroll
             for (int k = 0; k < 4; k++) { const uint32_t w = lane * 4 + (uint32_t)k; c[k] = (w < nwords) ? (uint32_t)__popc(bm[w]) : 0u; tot += c[k]; }
-            uint32_t run = tp_wave_incl_add(tot, lane) - tot;
+            uint32_t run = mic_wave_incl_add(tot) - tot;
 #pragma unroll
             for (int k = 0; k < 4; k++) { const uint32_t w = lane * 4 + (uint32_t)k; if (w < nwords) pf[w] = (uint16_t)run; run += c[k]; }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();

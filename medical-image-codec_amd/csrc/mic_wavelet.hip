@@ -11,6 +11,7 @@
 // The subband scan is a closed-form index map, so collect + zigzag + escape + max is one pass with a
 // prefix sum for the rare escapes.  RLE / FSE reuse the unit-codec kernels (mode 2 / mode 1 units).
 #include "mic_session.h"
+#include "mic_wave.h"
 
 namespace {
 
@@ -84,7 +85,7 @@ __device__ __forceinline__ void wv_pair(Get cf, int n, int i, int32_t &ev, int32
 #define WS_ROWS 64
 #define WS_LANES 62                 // pairs a wave writes
 template <int CTRL> __device__ __forceinline__ int32_t wv_shift(int32_t v) {    // 0x130: from the lane to the right, 0x138: from the lane to the left
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
+    return (int32_t)mic_dpp<CTRL>(0u, (uint32_t)v);
 }
 typedef uint32_t wv_u32u __attribute__((aligned(2)));
 typedef unsigned long long wv_u64u __attribute__((aligned(4)));
@@ -262,12 +263,6 @@ __device__ __forceinline__ size_t wv_pos_to_index(const WvDims &d, size_t p) {
     return 0;
 }
 
-__device__ __forceinline__ uint32_t wv_wave_incl(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) { uint32_t o = __shfl_up(v, dd); if (lane >= (uint32_t)dd) v += o; }
-    return v;
-}
-
 // subband scan + waveletCoeffsToU16 (:28-40) + zzMax (:335-349).  One work-group per image; writes the
 // symbol stream into u.sym, its length into u.nsym and the RLE maxValue into u.max_value.
 __global__ void __launch_bounds__(WV_THREADS) k_wv_symbols(MicUnit *units, const int32_t *a, WvDims d) {
@@ -283,14 +278,9 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_symbols(MicUnit *units, const
         const size_t p = base + tid;
         int32_t v = 0; uint32_t cnt = 0;
         if (p < n) { v = a[wv_pos_to_index(d, p)]; cnt = (v >= -32767 && v <= 32767) ? 1u : 3u; }
-        const uint32_t incl = wv_wave_incl(cnt, lane);
         __syncthreads();
-        if (lane == 63) s_scan[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < WV_WAVES; w++) { const uint32_t x = s_scan[w]; if ((uint32_t)w < wave) woff += x; tot += x; }
-        const uint32_t o = carry + woff + incl - cnt;
+        uint32_t tot;
+        const uint32_t o = carry + mic_group_excl_add<WV_WAVES>(cnt, s_scan, &tot);
         if (cnt == 1) {
             const uint32_t z = (uint32_t)((v >> 31) ^ (int32_t)((uint32_t)v << 1)) & 0xFFFF;   // zigzagEncode16, :538-541
             if (o < cap) sym[o] = (uint16_t)z; else ovf = true;
@@ -301,8 +291,7 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_symbols(MicUnit *units, const
         }
         carry += tot;
     }
-#pragma unroll
-    for (int dd = 32; dd > 0; dd >>= 1) zmax = max(zmax, (uint32_t)__shfl_xor((int)zmax, dd));
+    zmax = mic_wave_reduce_max(zmax);
     __syncthreads();
     if (lane == 0) s_max[wave] = zmax;
     const int any_ovf = __syncthreads_or(ovf ? 1 : 0);
@@ -406,9 +395,8 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_
         const uint32_t i = base + tid;
         const bool in = i < m;
         const uint32_t x = in ? sym[i] : 0u;
-        uint32_t f = (x == 65535u && in) ? (2u | (0u << 2) | (1u << 4)) : (0u | (0u << 2) | (1u << 4));
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o = __shfl_up(f, dd); if (lane >= (uint32_t)dd) f = wv_fn_compose(f, o); }
+        const uint32_t f = mic_wave_incl_scan((x == 65535u && in) ? (2u | (0u << 2) | (1u << 4)) : (0u | (0u << 2) | (1u << 4)), lane,
+                                              [](uint32_t earlier, uint32_t later) { return wv_fn_compose(later, earlier); });
         __syncthreads();
         if (lane == 63) s_fn[wave] = f;
         __syncthreads();
@@ -417,14 +405,12 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_
         const uint32_t st_after = (f >> (2 * st_in)) & 3;                          // state after symbol i
         uint32_t st_before = __shfl_up(st_after, 1); if (lane == 0) st_before = st_in;
         const bool starts = in && st_before == 0;                                  // a coefficient begins at i
-        const uint32_t incl = wv_wave_incl(starts ? 1u : 0u, lane);
-        if (lane == 63) s_scan[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0, tot = 0, st_end = carry_state;
+        uint32_t tot, st_end = carry_state;
+        const uint32_t before = mic_group_excl_add<WV_WAVES>(starts ? 1u : 0u, s_scan, &tot);
 #pragma unroll
-        for (int w = 0; w < WV_WAVES; w++) { const uint32_t v = s_scan[w]; if ((uint32_t)w < wave) woff += v; tot += v; st_end = (s_fn[w] >> (2 * st_end)) & 3; }
+        for (int w = 0; w < WV_WAVES; w++) st_end = (s_fn[w] >> (2 * st_end)) & 3;
         if (starts) {
-            const size_t k = (size_t)carry_n + woff + incl - 1;
+            const size_t k = (size_t)carry_n + before;
             if (k < lim) {
                 int32_t v;
                 if (x != 65535u) v = (int32_t)((x >> 1) ^ (uint32_t)(-(int32_t)(x & 1)));        // zigzagDecode16, :543-546
@@ -504,8 +490,7 @@ __global__ void __launch_bounds__(1024) k_wv_symbols_par(MicUnit *units, const i
         uint16_t *sym = u.sym;
         if (i0 + 8 <= n) { wv_v4 v; v.x = w8[0]; v.y = w8[1]; v.z = w8[2]; v.w = w8[3]; *(wv_v4 *)(sym + i0) = v; }   // (256-byte aligned slab, i0 a multiple of 8)
         else for (int k = 0; k < 8; k++) if (i0 + (uint32_t)k < n) sym[i0 + k] = (uint16_t)(w8[k >> 1] >> (16 * (k & 1)));
-#pragma unroll
-        for (int dd = 32; dd > 0; dd >>= 1) zmax = max(zmax, (uint32_t)__shfl_xor((int)zmax, dd));
+        zmax = mic_wave_reduce_max(zmax);
         // (one address per frame: an atomic per wave was 59 k atomics in a row on it.  The maximum only grows, so a wave whose own is
         // not above what the frame has already -- nearly every wave after the first few -- has nothing to say; a stale read only costs
         // an atomic that changes nothing)

@@ -51,6 +51,44 @@ def test_rows_predictor_full_strip_with_escapes(mic, mico, synth, gpu_ready):
         assert np.array_equal(got.reshape(h, w), img)
 
 
+# The two-wave wavefront predictor (k_dec_predict2, csrc/mic_decode_px.hip: frames of 2689..8128 columns) at the seams of its class:
+# the first width (row 0's scan gives a lane 43 columns, so lane 63 stays empty; a tail group of 1 pixel), a tail group of 31 pixels,
+# whole groups, and the last width (every lane of the scan full); row 0 alone, two rows, one whole 64-row band, the band seam, three bands.
+WAVE2_WIDTHS = [2689, 2719, 4096, 8128]
+WAVE2_HEIGHTS = [1, 2, 64, 65, 129]
+
+
+def _wave2_ramp(synth, w, h):
+    """The ramp of test_gpu_parity's wide-frame test with escapes forced into the first, middle and last lane of the row-0 scan and
+    into the frame's last pixel."""
+    noise = (synth.hash_u64(w * h, w + h) % np.uint64(5)).astype(np.int64).reshape(h, w)
+    img = ((np.add.outer(np.arange(h) * 7, np.arange(w) // 8) + noise) % 4096).astype(np.uint16)
+    img[0, 0] = 4095
+    img[0, w // 2] = 4095
+    img[0, w - 1] = 0
+    img[h - 1, w - 1] = 4095
+    return img
+
+
+_WAVE2_IMAGES = {
+    "ramp": _wave2_ramp,
+    "spiky": lambda synth, w, h: _spiky(synth, w, h, 12, w + h),
+    "xr": lambda synth, w, h: synth.xr_like(cols=w, rows=h, depth=12, seed=w + h),
+}
+WAVE2_CASES = [(kind, w, h) for kind in _WAVE2_IMAGES for w in WAVE2_WIDTHS for h in WAVE2_HEIGHTS
+               if kind == "ramp" or h >= 64]           # (the XR-like frames of one and two rows are incompressible)
+
+
+@pytest.mark.parametrize("kind,w,h", WAVE2_CASES)
+def test_wave2_predictor_class_seams_match_the_oracle(mic, mico, synth, gpu_ready, kind, w, h):
+    img = _WAVE2_IMAGES[kind](synth, w, h)
+    rc, want = mico.compress_single_frame(img, 4095, 2)
+    assert rc == 0
+    assert mic.compress_single_frame(img, w, h, 4095, 2) == want
+    got = mic.decompress_single_frame(want, w, h)
+    assert np.array_equal(np.asarray(got).reshape(h, w), img)
+
+
 def test_rows_predictor_wrapping_streams_agree_with_the_oracle(mic, mico, synth, gpu_ready):
     """Symbols no encoder writes (far outside thr +- thr) make pixels wrap around 16 bits -- in the reference that is plain uint16
     arithmetic.  The closed form of the row kernel does not hold there: it must notice and produce the reference's pixels."""

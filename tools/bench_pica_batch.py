@@ -7,7 +7,7 @@ Each measurement runs in a child process of its own (one library per process), a
 Then, each a pass of its own: the per-kernel device times of a PICA batch call from A / B builds of this tree (--timing-lib:
 EXTRA_FLAGS=-DMIC_PICA_TIMING; --nopick-lib: -DMIC_PICA_TIMING -DMIC_PICA_NO_PICK, the pack WITHOUT k_pica_pick; neither switch exists
 in the product library), and the avg and gradient chains over the same 768 equal strips through the session API with timing on, for
-this tree and for every build of --session-libs (the parent, PG_AHEAD variants of k_dec_predict_grad).
+this tree and for every build of --session-libs (the parent, variants of k_dec_predict_grad).
 Host buffers in and out, pageable and pinned.  min / median wall ms over --steps after --warmup; GB/s count raw pixels.
 Prints one JSON line.
 
@@ -207,7 +207,7 @@ def main():
     ap.add_argument("--lib", default=None, help="another build of libmic_hip.so to loop over (the parent commit's)")
     ap.add_argument("--timing-lib", default=None, help="this tree built with EXTRA_FLAGS=-DMIC_PICA_TIMING: per-kernel times of the batch call")
     ap.add_argument("--nopick-lib", default=None, help="... with -DMIC_PICA_TIMING -DMIC_PICA_NO_PICK: both candidates packed, the host picks")
-    ap.add_argument("--session-libs", default="", help="name=path,...: builds whose session chains are timed beside this tree's (parent, PG_AHEAD variants)")
+    ap.add_argument("--session-libs", default="", help="name=path,...: builds whose session chains are timed beside this tree's (parent, variants)")
     ap.add_argument("--reuse-rounds", nargs="*", default=[], help="earlier outputs of this tool whose rounds are taken over (tagged with their file name)")
     ap.add_argument("--child", default=None)
     ap.add_argument("--child-timeout", type=int, default=900)
