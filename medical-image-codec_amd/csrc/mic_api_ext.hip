@@ -10,7 +10,7 @@
 // the requested tiles, then inverse transform + crop on the device.
 #include "mic_session.h"
 #include "mic_wave.h"
-#include "mic_pieces.h"
+#include "mic_rects.h"
 
 #include <memory>
 
@@ -758,13 +758,11 @@ int wsi_region(const BlobSource &src, const Mic3 &m, int level, int x, int y, in
 
 // ---- patches -----------------------------------------------------------------------------------------------------------------
 // The plan of a patch call.  A unit is a tile to entropy-decode (slide: index into the call's slide list, 0 for the one-slide calls;
-// tile: its index as the door counts it); a piece is one patch-tile overlap: w x h pixels from (sx, sy) of unit `unit`'s tile to
-// (dx, dy) of patch `patch`.  units: ascending by slide, then tile, each once.  pieces: sorted by unit (stable: patch order inside a
-// unit).  first[u] .. first[u + 1]: the pieces of units[u].
+// tile: its index as the door counts it); a piece is one patch-tile overlap (RectPiece, mic_rects.h: rect = the patch).  units:
+// ascending by slide, then tile, each once.  pieces: sorted by unit (stable: patch order inside a unit).
 struct PatchUnit { uint32_t slide; uint64_t tile; };
-struct PlanPiece { int32_t patch; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
-struct PatchPlan { std::vector<PatchUnit> units; std::vector<PlanPiece> pieces; std::vector<size_t> first; };
-struct PlanKey { PatchUnit u; PlanPiece pc; };
+struct PatchPlan { std::vector<PatchUnit> units; std::vector<RectPiece> pieces; };
+struct PlanKey { PatchUnit u; RectPiece pc; };
 
 // Patch i = [px, px + pw) x [py, py + ph) clipped to a level of level_w x level_h pixels and cut into its overlaps with the level's
 // tiles (tw x th, tiles_x a row): one key per overlap, tile = first + ty * tiles_x + tx.  What lies outside the level has no piece.
@@ -776,7 +774,7 @@ void plan_clip(std::vector<PlanKey> &all, uint32_t slide, int level_w, int level
     for (int64_t ty = y0 / th; ty <= (y1 - 1) / th; ty++) for (int64_t tx = x0 / tw; tx <= (x1 - 1) / tw; tx++) {
         const int64_t ax = std::max(x0, tx * tw), bx = std::min(x1, (tx + 1) * tw), ay = std::max(y0, ty * th), by = std::min(y1, (ty + 1) * th);
         all.push_back(PlanKey{ PatchUnit{ slide, (uint64_t)(first + ty * tiles_x + tx) },
-                               PlanPiece{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py), (int32_t)(bx - ax), (int32_t)(by - ay) } });
+                               RectPiece{ i, 0, (int32_t)(ax - tx * tw), (int32_t)(ay - ty * th), (int32_t)(ax - px), (int32_t)(ay - py), (int32_t)(bx - ax), (int32_t)(by - ay) } });
     }
 }
 // the keys in unit order ...
@@ -788,17 +786,13 @@ int plan_sort(std::vector<PlanKey> &all) {
 // ... and those of the slides that `keep` accepts as the plan
 template <class Keep>
 void plan_group(const std::vector<PlanKey> &all, PatchPlan &plan, Keep keep) {
-    plan.units.clear(); plan.pieces.clear(); plan.first.clear();
+    plan.units.clear(); plan.pieces.clear();
     for (const PlanKey &k : all) {
         if (!keep(k.u.slide)) continue;
-        if (plan.units.empty() || plan.units.back().slide != k.u.slide || plan.units.back().tile != k.u.tile) {
-            plan.units.push_back(k.u);
-            plan.first.push_back(plan.pieces.size());
-        }
+        if (plan.units.empty() || plan.units.back().slide != k.u.slide || plan.units.back().tile != k.u.tile) plan.units.push_back(k.u);
         plan.pieces.push_back(k.pc);
         plan.pieces.back().unit = (uint32_t)(plan.units.size() - 1);
     }
-    plan.first.push_back(plan.pieces.size());
 }
 
 // The plan of n patches of pw x ph pixels, patch i at (xy[2i], xy[2i + 1]), in one level of level_w x level_h pixels (tiles of
@@ -819,10 +813,7 @@ int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int p
     const Level &L = m.lv[(size_t)level];
     if (L.w <= 0 || L.h <= 0 || m.tw <= 0 || m.th <= 0) return MIC_ERR_CORRUPT;
     if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
-    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ph * (unsigned)pw * m.bpp();
-    if (bytes > out_cap) return MIC_ERR_CAPACITY;
-    *need = (size_t)bytes;
-    return MIC_OK;
+    return tensor_bytes(n, 1, ph, pw, m.bpp(), out_cap, need);
 }
 
 // Where a call's tiles come from: the planes of units u0 .. u0 + nt - 1 of the plan as nt * P records over *base (device), and each
@@ -835,10 +826,9 @@ SlabCeiling blob_ceiling(size_t P) { return [P](size_t npx) { return std::min<si
 
 // The core of every patch call: the plan's pieces into d_out ([patch][ph][pw] pixels of the slides' format, an address s's device
 // can write: patch_pointer; what no piece covers is 0) on a session the caller holds.  um[u]: the header unit u's tile is coded
-// under (all of one sample format).  Every unit is decoded once, in sub-batches of as many tiles as `ceiling` allows of the largest
-// of them: tile u's P planes start slab_off[u] samples into the sub-batch's slab (the prefix sum of P * tw * th), decode_plane_slab
-// fills them from the source's records, and behind each sub-batch one gather launch writes its pieces.  The piece list goes up
-// once per call (s->pieces).  tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
+// under (all of one sample format).  The skeleton is the one the strip and MIC2 crop readers run (mic_rects.h); here are the rule -- as
+// many tiles as `ceiling` allows of the largest, a tile P * tw * th samples of the slab -- and the decode (decode_plane_slab).
+// tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
 int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const SlabCeiling &ceiling,
                  const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
     const size_t nu = plan.units.size();
@@ -850,67 +840,37 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
     if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
     const size_t P = (size_t)um[0]->planes();
     const GatherKind kind = P == 3 ? kGatherRGB : um[0]->bps == 16 ? kGatherU16 : kGatherU8;
-    // cuts: as many tiles as the ceiling holds of the largest of them (tiles of one size: `ceiling` tiles a sub-batch)
-    std::vector<size_t> px(nu), cuts{ 0 };
+    std::vector<size_t> px(nu);
     for (size_t u = 0; u < nu; u++) px[u] = (size_t)um[u]->tw * um[u]->th;
-    std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds)
-    auto cap_for = [&](size_t npx) {
+    std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds: the ceiling is asked once per size)
+    auto cap = [&](size_t, size_t npx) {                                                    // (what a launch takes is inside the ceiling)
         for (const auto &c : caps) if (c.first == npx) return c.second;
         caps.emplace_back(npx, ceiling(npx));
         return caps.back().second;
     };
-    while (cuts.back() < nu) {
-        size_t i1 = cuts.back(), mp = 0;
-        while (i1 < nu) {
-            const size_t m2 = std::max(mp, px[i1]);
-            if (i1 > cuts.back() && i1 - cuts.back() + 1 > cap_for(m2)) break;
-            mp = m2; i1++;
-        }
-        cuts.push_back(i1);
-    }
-    std::vector<uint64_t> slab_off(nu);
-    size_t slab_max = 0;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        size_t off = 0;
-        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += P * px[u]; }
-        slab_max = std::max(slab_max, off);
-    }
-    std::vector<GatherPiece> list(plan.pieces.size());
-    for (size_t k = 0; k < list.size(); k++) {
-        const PlanPiece &p = plan.pieces[k];
-        const int tw = um[p.unit]->tw;
-        list[k] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)tw + (uint64_t)p.sx,
-                               ((uint64_t)p.patch * (uint64_t)ph + (uint64_t)p.dy) * (uint64_t)pw + (uint64_t)p.dx, tw, pw, p.w, p.h, (int32_t)px[p.unit], 0 };
-    }
-    if ((rc = s->pieces.reserve(list.size() * sizeof(GatherPiece) + 64))) return rc;
-    if ((rc = s->wsi_planes.reserve(slab_max * 2 + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+    const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_sub_batch(i0, nu, [&](size_t u) { return px[u]; }, cap, CutRule{ ~(size_t)0 }); },
+                                       [&](size_t u) { return P * px[u]; }, plan.pieces, pw, ph, [&](size_t u) { return UnitStride{ um[u]->tw, (int32_t)px[u] }; });
+    if ((rc = s->wsi_planes.reserve(L.slab_max * 2 + 64))) return rc;
+    if ((rc = upload_gather(s, L))) return rc;
     std::vector<WsiPlane> pl; std::vector<int32_t> pst;
-    for (size_t b = 0; b + 1 < cuts.size(); b++, ++*nslab) {
-        const size_t u0 = cuts[b], nt = cuts[b + 1] - u0;
+    for (size_t b = 0; b < L.subs(); b++, ++*nslab) {
+        const size_t u0 = L.cuts[b], nt = L.cuts[b + 1] - u0;
         const uint8_t *base = nullptr;
         pl.clear();
         if ((rc = source(u0, nt, &base, pl, tile_status.data() + u0))) return rc;
         pst.assign(nt * P, MIC_OK);
         if ((rc = decode_plane_slab(s, base, pl.data(), nt * P, [&](size_t q) {
                 const size_t u = u0 + q / P;
-                return PlaneAt{ slab_off[u] + (q % P) * px[u], um[u]->tw, um[u]->th };
-            }, s->wsi_planes, slab_max, pst.data()))) return rc;
+                return PlaneAt{ L.slab_off[u] + (q % P) * px[u], um[u]->tw, um[u]->th };
+            }, s->wsi_planes, L.slab_max, pst.data()))) return rc;
         for (size_t q = 0; q < nt * P; q++) if (tile_status[u0 + q / P] == MIC_OK) tile_status[u0 + q / P] = pst[q];
-        const size_t p0 = plan.first[u0], np = plan.first[u0 + nt] - p0;                    // (np >= 1: every unit has a piece; np <= 2^31 - 1: plan_sort)
-        int mw = 1, mh = 1;
-        for (size_t k = p0; k < p0 + np; k++) { mw = std::max(mw, plan.pieces[k].w); mh = std::max(mh, plan.pieces[k].h); }
-        s->timer.reset(s->stream); s->timer.mark("k_wsi_gather_patches");
-        launch_gather(s->stream, kind, (const uint16_t *)s->wsi_planes.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
+        s->timer.reset(s->stream);                                                          // (every unit has a piece; no more than 2^31 - 1 in all: plan_sort)
+        gather_units(s, "k_wsi_gather_patches", kind, s->wsi_planes.p, L, b, d_out);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());                                                         // (the next sub-batch follows on the stream; decode_plane_slab has waited for this one's bytes)
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIC_OK;
-}
-// status[p] == MIC_OK becomes the status of the first failing tile of patch p, in tile order
-void fold_tile_status(const PatchPlan &plan, const std::vector<int32_t> &tile_status, int32_t *status) {
-    for (const PlanPiece &p : plan.pieces) if (status[p.patch] == MIC_OK) status[p.patch] = tile_status[p.unit];
 }
 
 // The source of the file and reader doors: blobs[u] (host) is the blob of unit u.  A sub-batch's blobs are checked on the host, each
@@ -944,7 +904,7 @@ int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<c
     uint64_t nslab = 0;
     const int rc = read_patches(s, plan, um, pw, ph, ceiling, source, d_out, need, tst, &nslab);
     if (rc) return rc;
-    if (status) { std::fill(status, status + n, (int32_t)MIC_OK); fold_tile_status(plan, tst, status); }
+    fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
     if (stats) { stats->tiles_decoded = plan.units.size(); stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
     return MIC_OK;
 }
@@ -997,7 +957,7 @@ bool multi_tile_entry(const MultiSlide &sl, uint64_t gi, uint64_t *off, uint64_t
 // keeps its code in slides[f].status and its patches have no pieces; nor has a patch whose level its slide does not have.
 int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int channels, int bps) {
     const int ns = (int)plan.slides.size();
-    plan.units.clear(); plan.pieces.clear(); plan.first.assign(1, 0);
+    plan.units.clear(); plan.pieces.clear();
     for (int i = 0; i < n; i++) {
         const int32_t f = q[4 * (size_t)i + 2];
         if (f < 0 || f >= ns) return MIC_ERR_ARGS;
@@ -1038,10 +998,7 @@ int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int cha
 int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps, size_t out_cap, size_t *need) {
     if (pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xysl)) return MIC_ERR_ARGS;
     if (!((channels == 3 && bps == 8) || (channels == 1 && (bps == 8 || bps == 16)))) return MIC_ERR_UNSUPPORTED;   // (Mic3::supported)
-    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ph * (unsigned)pw * (size_t)(channels * (bps == 16 ? 2 : 1));
-    if (bytes > out_cap) return MIC_ERR_CAPACITY;
-    *need = (size_t)bytes;
-    return MIC_OK;
+    return tensor_bytes(n, 1, ph, pw, (size_t)(channels * (bps == 16 ? 2 : 1)), out_cap, need);
 }
 
 // slide `f`'s blobs of `tiles` (global indices, entries checked by the plan) through its reader; NULL: the slides are files in memory
@@ -1088,14 +1045,11 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
     if ((rc = read_patches(s, plan, um, pw, ph, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab))) return rc;
-    if (status) {
-        for (int i = 0; i < n; i++) {
-            const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]];
-            const int32_t level = xysl[4 * (size_t)i + 3];
-            status[i] = sl.status != MIC_OK ? sl.status : (level < 0 || level >= (int)sl.hdr().lv.size()) ? MIC_ERR_ARGS : MIC_OK;
-        }
-        fold_tile_status(plan, tst, status);
-    }
+    fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
+    container_codes(n, status, [&](int i) {                                                 // a refused slide's code; a level the slide does not have
+        const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]]; const int32_t level = xysl[4 * (size_t)i + 3];
+        return sl.status != MIC_OK ? sl.status : (level < 0 || level >= (int)sl.hdr().lv.size()) ? (int32_t)MIC_ERR_ARGS : (int32_t)MIC_OK;
+    });
     if (stats) {
         uint64_t read = 0;
         for (const MultiSlide &sl : plan.slides) read += sl.header_ok ? 1 : 0;

@@ -207,18 +207,14 @@ inline bool unit_gap(const DecUnit &u) { return (u.flags & MIC_HIP_GAP_REMOVAL) 
 // streams as for 2304)
 template <class U>
 int next_cut(const std::vector<U> &units, int i0, int n, size_t target) {
-    size_t max_px = 0, cap = 0, gap_x = 0; int i1 = i0;
-    while (i1 < n) {
-        const size_t px = (size_t)units[(size_t)i1].w * (size_t)units[(size_t)i1].h;
-        const size_t mp = std::max(max_px, px);
+    size_t max_px = 0, gap_x = 0, cap = 0;
+    return (int)next_sub_batch((size_t)i0, (size_t)n, [&](size_t i) { return (size_t)units[i].w * (size_t)units[i].h; }, [&](size_t i, size_t mp) {
         // (a gap-removal unit holds a map slab beside the others: the tier-2 one is counted)
-        const size_t gx = std::max(gap_x, unit_gap(units[(size_t)i1]) ? (size_t)mic_gap_stride(65536u) : (size_t)0);
+        const size_t gx = std::max(gap_x, unit_gap(units[i]) ? (size_t)mic_gap_stride(65536u) : (size_t)0);
         if (mp != max_px || gx != gap_x || cap == 0) cap = batch_units_for(mp, 1, 12 * mp + gx);   // (+ the staging: two halves each of the pixels, the streams, the packed buffer)
-        gap_x = gx;
-        if (i1 > i0 && ((size_t)(i1 - i0 + 1) > cap || (size_t)(i1 - i0) >= target || i1 - i0 >= 65535)) break;
-        max_px = mp; i1++;
-    }
-    return i1;
+        max_px = mp; gap_x = gx;
+        return cap;
+    }, CutRule{ 65535, target });
 }
 // Sub-batches of a call: the transfers of one overlap the kernels of its neighbours.  A decode costs the tANS chain's ~17 ms whatever
 // its size (one serial chain per stream), so decode cuts into parts of >= 1152 units; encode kernels scale with their units (7 ms
@@ -538,13 +534,9 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
         const int nsr = (int)strips.size();
         for (int s0 = 0; s0 < nsr || !next_bounds;) {
             // strips [s0, s1) of the next chain: two units each, under the workspace ceiling
-            size_t max_px = 0, cap = 0; int s1 = s0;
-            while (s1 < nsr) {
-                const size_t mp = std::max(max_px, (size_t)strips[(size_t)s1].w * (size_t)strips[(size_t)s1].rows);
-                if (mp != max_px || cap == 0) cap = batch_units_for(mp, 1, 6 * mp);   // (+ the staging: half a strip's pixels and streams per unit, two halves each)
-                if (s1 > s0 && (2 * (size_t)(s1 - s0 + 1) > cap || 2 * (s1 - s0 + 1) > 65534)) break;
-                max_px = mp; s1++;
-            }
+            const int s1 = (int)next_sub_batch((size_t)s0, (size_t)nsr, [&](size_t q) { return (size_t)strips[q].w * (size_t)strips[q].rows; },
+                cap_by_largest([](size_t mp) { return batch_units_for(mp, 1, 6 * mp) / 2; }),   // (+ the staging: half a strip's pixels and streams per unit, two halves each)
+                CutRule{ 65534 / 2 });
             const int nb = 2 * (s1 - s0);
             std::vector<mic_hip_unit> units((size_t)nb);
             for (int q = s0; q < s1; q++) {
@@ -1461,6 +1453,28 @@ int mic_hip_rgb_decompress_batch(mic_hip_rgb_dec_job *jobs, int njobs) try {
     }
     return over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i].w * (uint64_t)J[(size_t)i].h; },
                         [&](mic_hip_session *s, int j0, int j1) { return rgb_decode_host(s, J, j0, j1); });
+} MIC_ABI_CATCH
+
+// debug probe (not in the public header; no device): next_sub_batch over n items of px[i] pixels under a rule the caller states.  The
+// capacity is a step function of the largest item, units / per items: row k of tab is (px, units), the first row whose px >= the largest
+// item holds, the last row beyond it; from the first item with flag[i] != 0 (flag may be NULL) on, tab_flag's.  -> cuts [0, ..., n].
+int mic_hip_debug_cuts(const uint64_t *px, const uint8_t *flag, int n, const uint64_t *tab, int ntab, const uint64_t *tab_flag, int ntab_flag,
+                       uint64_t per, uint64_t limit, uint64_t item_target, uint64_t px_target, uint64_t *cuts, size_t cap, uint64_t *ncuts) try {
+    if (n < 0 || (n > 0 && !px) || !tab || ntab < 1 || (flag && (!tab_flag || ntab_flag < 1)) || per < 1 || !ncuts || (cap > 0 && !cuts)) return MIC_ERR_ARGS;
+    std::vector<uint64_t> c{ 0 };
+    while (c.back() < (uint64_t)n) {
+        bool flagged = false;
+        c.push_back(next_sub_batch((size_t)c.back(), (size_t)n, [&](size_t i) { return (size_t)px[i]; }, [&](size_t i, size_t mp) {
+            flagged |= flag && flag[i];
+            const uint64_t *t = flagged ? tab_flag : tab;
+            int k = 0;
+            while (k + 1 < (flagged ? ntab_flag : ntab) && t[2 * k] < mp) k++;
+            return (size_t)(t[2 * k + 1] / per);
+        }, CutRule{ (size_t)limit, (size_t)item_target, (size_t)px_target }));
+    }
+    *ncuts = c.size();
+    if (c.size() <= cap) std::copy(c.begin(), c.end(), cuts);
+    return c.size() <= cap ? MIC_OK : MIC_ERR_CAPACITY;
 } MIC_ABI_CATCH
 
 }  // extern "C"

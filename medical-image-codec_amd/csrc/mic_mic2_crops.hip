@@ -16,10 +16,11 @@
 //                        symbols with one lane per footprint pixel and stores the sums that fall into the crop's z range.  Frame 0,
 //                        the spatial unit, is the only full image of the volume on the device; the carry from one sub-batch to the
 //                        next lives in the tensor itself.
+// Shared with the MIC3 patch and strip-file crop readers (mic_rects.h): the piece record, the sub-batch layout, the gather list and
+// its launch, the independent volumes' status fold, the tensor check.  Here: the plans, the decode chain, everything temporal.
 #include <climits>
 #include <memory>
-#include "mic_session.h"
-#include "mic_pieces.h"
+#include "mic_rects.h"
 
 namespace {
 
@@ -115,10 +116,7 @@ int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch,
     if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || (n > 0 && !xyz)) return MIC_ERR_ARGS;
     if (m.w <= 0 || m.h <= 0) return MIC_ERR_CORRUPT;                                       // (as mic_hip_mic2_decompress)
     if ((size_t)m.w * (size_t)m.h > ((size_t)1 << 28) || m.file_len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
-    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)cd * (unsigned)ch * (unsigned)cw * 2;
-    if (bytes > out_cap) return MIC_ERR_CAPACITY;
-    *need = (size_t)bytes;
-    return MIC_OK;
+    return tensor_bytes(n, cd, ch, cw, 2, out_cap, need);
 }
 
 }  // namespace micapi
@@ -211,7 +209,7 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
                           void *d_out, size_t need, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
     struct Unit { uint32_t vol, frame; };
     const size_t nv = mp.vols.size();
-    std::vector<Unit> un; std::vector<size_t> px, unit0(nv, 0), cuts{ 0 };
+    std::vector<Unit> un; std::vector<size_t> px, unit0(nv, 0);
     for (size_t v = 0; v < nv; v++) {
         const Mic2Vol &f = mp.vols[v];
         unit0[v] = un.size();
@@ -221,36 +219,22 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
     int rc;
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
     HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volumes, refused volumes; every byte is written
-    while (cuts.back() < nu) cuts.push_back(next_strip_cut(px, cuts.back()));
     auto vol = [&](size_t u) -> const Mic2Vol & { return mp.vols[un[u].vol]; };
     auto is_frame = [&](size_t u) { return !vol(u).m.temporal || un[u].frame == 0; };       // a frame unit (mode 0), else a residual's symbols (mode 3)
     auto blob_len = [&](size_t u) { return (uint64_t)get_u32(vol(u).m.table + 8 * (size_t)un[u].frame + 4); };
-    // a frame unit's place in its sub-batch's pixel slab, the largest slab and the most stream bytes of a sub-batch
-    std::vector<uint64_t> slab_off(nu, 0);
-    size_t slab_max = 0, comp_max = 0;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        size_t off = 0, comp = 0;
-        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { if (is_frame(u)) { slab_off[u] = off; off += px[u]; } comp += (size_t)blob_len(u); }
-        slab_max = std::max(slab_max, off); comp_max = std::max(comp_max, comp);
-    }
-    // the call's lists: independent volumes their pieces as the gather reads them, in unit order; temporal volumes their footprints,
-    // in volume order, each volume that has units a slot
-    std::vector<GatherPiece> list; std::vector<size_t> first(nu + 1, 0);                    // the pieces of unit u
+    // the call's lists: independent volumes their pieces, in unit order -- the tensor as n * cd slices of ch x cw --; temporal volumes
+    // their footprints, in volume order, each volume that has units a slot.  Only a frame unit has a place in its sub-batch's slab.
+    std::vector<RectPiece> pieces;
     std::vector<VolPrint> prints; std::vector<size_t> pfirst;                               // the footprints of slot t
     std::vector<int32_t> slot_of(nv, -1), slot_vol;
-    int mw = 1, mh = 1, tw = 1, th = 1;
+    int tw = 1, th = 1;
     for (size_t v = 0; v < nv; v++) {
         const Mic2Vol &f = mp.vols[v];
         if (f.plan.frames.empty()) continue;
         if (!f.m.temporal) {
-            for (const CropPiece &pc : f.plan.pieces) {
-                const size_t u = unit0[v] + (size_t)pc.k;
-                first[u + 1]++;
-                list.push_back(GatherPiece{ slab_off[u] + (uint64_t)pc.sy * (uint64_t)f.m.w + (uint64_t)pc.sx,
-                                            (((uint64_t)pc.crop * (uint64_t)cd + (uint64_t)pc.dz) * (uint64_t)ch + (uint64_t)pc.dy) * (uint64_t)cw + (uint64_t)pc.dx,
-                                            f.m.w, cw, pc.w, pc.h, 0, 0 });
-                mw = std::max(mw, pc.w); mh = std::max(mh, pc.h);
-            }
+            if ((uint64_t)n * (uint64_t)cd > (uint64_t)INT_MAX) return MIC_ERR_UNSUPPORTED;      // (a slice's index is an int32)
+            for (const CropPiece &pc : f.plan.pieces)
+                pieces.push_back(RectPiece{ pc.crop * cd + pc.dz, (uint32_t)(unit0[v] + (size_t)pc.k), pc.sx, pc.sy, pc.dx, pc.dy, pc.w, pc.h });
         } else {
             slot_of[v] = (int32_t)slot_vol.size(); slot_vol.push_back((int32_t)v);
             pfirst.push_back(prints.size());
@@ -258,31 +242,33 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         }
     }
     pfirst.push_back(prints.size());
-    for (size_t u = 0; u < nu; u++) first[u + 1] += first[u];
+    const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_strip_cut(px, i0); }, [&](size_t u) { return is_frame(u) ? px[u] : (size_t)0; },
+                                       pieces, cw, ch, [&](size_t u) { return UnitStride{ vol(u).m.w, 0 }; });
+    size_t comp_max = 0;                                                                    // the most stream bytes of a sub-batch
+    for (size_t b = 0, comp = 0; b < L.subs(); b++, comp = 0)
+        for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) comp_max = std::max(comp_max, comp += (size_t)blob_len(u));
     // ... and, per sub-batch, a span per temporal volume it holds a part of: written when the sub-batch's statuses are known, each
     // into a place of its own on the host and on the device
     size_t nspan = 0;
-    for (size_t b = 0; b + 1 < cuts.size(); b++)
-        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) nspan += vol(u).m.temporal && (u == cuts[b] || un[u].vol != un[u - 1].vol);
+    for (size_t b = 0; b + 1 < L.cuts.size(); b++)
+        for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) nspan += vol(u).m.temporal && (u == L.cuts[b] || un[u].vol != un[u - 1].vol);
     std::vector<VolSpan> spans; spans.reserve(nspan);
-    const size_t list_bytes = align_up(list.size() * sizeof(GatherPiece), 16), print_bytes = align_up(prints.size() * sizeof(VolPrint), 16);
+    const size_t list_bytes = gather_bytes(L), print_bytes = align_up(prints.size() * sizeof(VolPrint), 16);
     if (nu) {
-        if ((rc = s->pieces.reserve(list_bytes + print_bytes + nspan * sizeof(VolSpan)))) return rc;
         if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
-        if ((rc = s->io_px.reserve(slab_max * 2 + 64))) return rc;
-        if (!list.empty()) HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+        if ((rc = s->io_px.reserve(L.slab_max * 2 + 64))) return rc;
+        if ((rc = upload_gather(s, L, print_bytes + nspan * sizeof(VolSpan)))) return rc;   // (the footprints and the spans behind the list)
         if (!prints.empty()) HIP_TRY(hipMemcpyAsync((char *)s->pieces.p + list_bytes, prints.data(), prints.size() * sizeof(VolPrint), hipMemcpyHostToDevice, s->stream));
     }
-    const GatherPiece *d_list = (const GatherPiece *)s->pieces.p;
     const VolPrint *d_prints = (const VolPrint *)((char *)s->pieces.p + list_bytes);
     VolSpan *d_spans = (VolSpan *)((char *)s->pieces.p + list_bytes + print_bytes);
     std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
     std::vector<int32_t> fbad(slot_vol.size(), INT_MAX), bad_code(slot_vol.size(), MIC_OK); // a temporal volume's first failed frame
     std::vector<uint64_t> begins, ends; std::vector<Mic2DecUnit> du;
     uint64_t nslab = 0;                                                                     // decode chains run
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        const size_t u0 = cuts[b];
-        const int nb = (int)(cuts[b + 1] - u0);
+    for (size_t b = 0; b + 1 < L.cuts.size(); b++) {
+        const size_t u0 = L.cuts[b];
+        const int nb = (int)(L.cuts[b + 1] - u0);
         // units lie in volume order: when the first and the last one left are of one volume, nothing but that volume is left, and when
         // it is a temporal one that has failed, no crop is waiting for any of them
         if (un[u0].vol == un[nu - 1].vol && slot_of[un[u0].vol] >= 0 && fbad[(size_t)slot_of[un[u0].vol]] != INT_MAX) break;
@@ -292,7 +278,7 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         for (int i = 0; i < nb; i++) {
             const size_t g = u0 + (size_t)i;
             du[(size_t)i] = Mic2DecUnit{ (const uint8_t *)s->io_comp.p + begins[(size_t)i], (uint32_t)blob_len(g), vol(g).m.w, vol(g).m.h,
-                                         is_frame(g) ? (uint16_t *)s->io_px.p + slab_off[g] : nullptr, (uint32_t)!is_frame(g) };
+                                         is_frame(g) ? (uint16_t *)s->io_px.p + L.slab_off[g] : nullptr, (uint32_t)!is_frame(g) };
         }
         if ((rc = mic2_batch_decode_units(s, du.data(), nb, ust.data() + u0))) return rc;
         nslab++;
@@ -308,16 +294,13 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
                 if (spans.size() == sp0) slot0 = t;
                 for (int k = i; k < j && fbad[(size_t)t] == INT_MAX; k++)
                     if (ust[u0 + (size_t)k] != MIC_OK) { fbad[(size_t)t] = (int32_t)un[u0 + (size_t)k].frame; bad_code[(size_t)t] = ust[u0 + (size_t)k]; }
-                spans.push_back(VolSpan{ un[g].frame == 0 ? slab_off[g] : 0, i, j - i, (int32_t)un[g].frame, fbad[(size_t)t], vol(g).m.w, 0 });
+                spans.push_back(VolSpan{ un[g].frame == 0 ? L.slab_off[g] : 0, i, j - i, (int32_t)un[g].frame, fbad[(size_t)t], vol(g).m.w, 0 });
             }
             i = j;
         }
-        const size_t nsp = spans.size() - sp0, p0 = first[u0], np = first[u0 + (size_t)nb] - p0;
+        const size_t nsp = spans.size() - sp0;
         s->timer.reset(s->stream);
-        if (np) {
-            s->timer.mark("k_mic2_gather_crops");
-            launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, d_list + p0, np, mw, mh, d_out);
-        }
+        gather_units(s, "k_mic2_gather_crops", kGatherU16, s->io_px.p, L, b, d_out);
         if (nsp) {
             const size_t q0 = pfirst[(size_t)slot0], nq = pfirst[(size_t)slot0 + nsp] - q0;
             HIP_TRY(hipMemcpyAsync(d_spans + sp0, spans.data() + sp0, nsp * sizeof(VolSpan), hipMemcpyHostToDevice, s->stream));
@@ -330,30 +313,14 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    for (int i = 0; i < n; i++) {
-        if (status) status[i] = MIC_OK;
-        if (failed_frame) failed_frame[i] = -1;
-    }
-    if (status || failed_frame) {
-        std::vector<char> failed((size_t)n, 0);                                             // independent volumes: pieces are in frame order
-        for (size_t v = 0; v < nv; v++) {
-            const Mic2Vol &f = mp.vols[v];
-            if (slot_of[v] >= 0) {
-                const int32_t fb = fbad[(size_t)slot_of[v]];
-                for (const CropPiece &fp : f.plan.prints) {
-                    if (fp.k < fb) continue;
-                    if (status) status[fp.crop] = bad_code[(size_t)slot_of[v]];
-                    if (failed_frame) failed_frame[fp.crop] = fb;
-                }
-            } else {
-                for (const CropPiece &pc : f.plan.pieces) {
-                    const int32_t st = ust[unit0[v] + (size_t)pc.k];
-                    if (st == MIC_OK || failed[(size_t)pc.crop]) continue;
-                    failed[(size_t)pc.crop] = 1;
-                    if (status) status[pc.crop] = st;
-                    if (failed_frame) failed_frame[pc.crop] = pc.frame;
-                }
-            }
+    fold_unit_status(pieces, ust, n, cd, status, failed_frame, [&](uint32_t u) { return (int32_t)un[u].frame; });   // independent volumes: pieces are in frame order
+    for (size_t v = 0; v < nv; v++) {                                                       // temporal volumes: every crop that reaches the failed frame
+        if (slot_of[v] < 0) continue;
+        const int32_t fb = fbad[(size_t)slot_of[v]];
+        for (const CropPiece &fp : mp.vols[v].plan.prints) {
+            if (fp.k < fb) continue;
+            if (status) status[fp.crop] = bad_code[(size_t)slot_of[v]];
+            if (failed_frame) failed_frame[fp.crop] = fb;
         }
     }
     if (stats) *stats = mic_hip_multi_crop_stats{ mp.units, mp.pieces, nslab, mp.read };
@@ -397,9 +364,8 @@ int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(co
 // what the doors check of their arguments before a file is looked at; *need = bytes of the crop tensor
 int multi_crop_args(const void *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd, size_t out_cap, size_t *need) {
     if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || nfiles < 0 || (n > 0 && !xyzv) || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
-    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)cd * (unsigned)ch * (unsigned)cw * 2;
-    if (bytes > out_cap) return MIC_ERR_CAPACITY;
-    *need = (size_t)bytes;
+    const int rc = tensor_bytes(n, cd, ch, cw, 2, out_cap, need);
+    if (rc) return rc;
     for (int i = 0; i < n; i++) if (xyzv[4 * (size_t)i + 3] < 0 || xyzv[4 * (size_t)i + 3] >= nfiles) return MIC_ERR_ARGS;
     return MIC_OK;
 }
@@ -419,11 +385,7 @@ int multi_call(mic_hip_session *s, Mic2MultiPlan &mp, const std::function<int(Mi
     Mic2MultiSource src;
     if ((rc = source(src))) return rc;
     if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, d_out, need, status, failed_frame, stats))) return rc;
-    if (status)
-        for (int i = 0; i < n; i++) {
-            const int32_t vs = mp.vols[(size_t)xyzv[4 * (size_t)i + 3]].status;
-            if (vs != MIC_OK) status[i] = vs;
-        }
+    container_codes(n, status, [&](int i) { return mp.vols[(size_t)xyzv[4 * (size_t)i + 3]].status; });
     return MIC_OK;
 }
 

@@ -8,6 +8,7 @@
 // This file holds the kernels, the core on device buffers (rgb_encode_run / rgb_decode_run) and the session entry points; the host
 // pipeline -- sub-batches, staging, devices -- is with the other containers' in mic_host_io.hip.
 #include "mic_session.h"
+#include "mic_staged.h"
 #include "mic_wave.h"
 
 namespace {
@@ -255,16 +256,10 @@ int rgb_parse_head(const RgbHead &h, uint64_t bl, size_t npx, RgbPlaneRec pl[3],
 }
 
 int rgb_next_cut(const std::function<size_t(int)> &npx, int i0, int n, size_t target_px) {
-    size_t max_px = 0, cap = 0, px = 0; int i1 = i0;
-    while (i1 < n) {
-        const size_t p = npx(i1), mp = std::max(max_px, p);
-        // (beside a unit's slabs: its share of the staged RGB, the planes, the packed streams and the assembled blobs, two halves of each that has two)
-        if (mp != max_px || cap == 0) cap = batch_units_for(std::max<size_t>(mp, 1), 1, 10 * mp);
-        const size_t cnt = (size_t)(i1 - i0);
-        if (cnt > 0 && (3 * (cnt + 1) > cap || px >= target_px || cnt >= (size_t)kRgbMaxImages)) break;
-        max_px = mp; px += p; i1++;
-    }
-    return i1;
+    // (beside a unit's slabs: its share of the staged RGB, the planes, the packed streams and the assembled blobs, two halves of each that has two)
+    return (int)next_sub_batch((size_t)i0, (size_t)n, [&](size_t i) { return npx((int)i); },
+        cap_by_largest([](size_t mp) { return batch_units_for(std::max<size_t>(mp, 1), 1, 10 * mp) / 3; }),
+        CutRule{ (size_t)kRgbMaxImages, ~(size_t)0, target_px });
 }
 
 // the table of the images that take part (status MIC_OK), their planes laid out back to back; of[k]: the image behind table row k

@@ -410,7 +410,7 @@ struct Mic2Head { int w = 0, h = 0, n = 0, temporal = 0; const uint8_t *table = 
 int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // Units [i0, return) of the next sub-batch of a list of units of px[i] pixels each, for the readers that decode units of mixed sizes
-// into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip)
+// into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip): next_sub_batch (mic_staged.h) under their capacity
 size_t next_strip_cut(const std::vector<size_t> &px, size_t i0);
 size_t next_strip_cut(const std::vector<size_t> &px, size_t i0, size_t budget);   // ... under a ceiling of `budget` bytes instead of the default
 // MIC2 whole-volume batches (mic_mic2_batch.hip; the host doors: mic_host_io.hip).  The units of a call's volumes -- volume order, then

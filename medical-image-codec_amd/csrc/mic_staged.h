@@ -1,4 +1,4 @@
-// mic_staged.h -- the one staging pipeline of the host batch entry points (mic_host_io.hip).  Standard C++ only: no HIP here.
+// mic_staged.h -- the one staging pipeline of the host batch entry points (mic_host_io.hip); next_sub_batch, the one cut of a unit list.  Standard C++ only: no HIP here.
 //
 // A call's items are cut into PARTS.  Part k + 1 comes up into one half of the staging while part k is coded out of the other
 // half and part k - 1 goes down; half = k & 1 for inputs and outputs alike.  run_staged(n, upload, run) keeps this protocol:
@@ -15,6 +15,7 @@
 //     request or into a caller's buffer.  It returns the first failure in the order above.
 //   * the requests live on the heap and do not move: the transfer workers hold pointers to them.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -66,6 +67,29 @@ std::vector<Part> staged_cut(int i0, int n, Next &&next, Make &&make) {
     std::vector<Part> parts;
     while (i0 < n) { const int i1 = next(i0); parts.push_back(make(i0, i1)); i0 = i1; }
     return parts;
+}
+
+// THE greedy cut of a list of items into sub-batches: items [i0, return) of the next sub-batch of items [.., n), px(i) pixels each.
+// An item joins while the count with it stays within cap(i, mp) -- the items a sub-batch may hold once item i has joined, mp the
+// largest so far, i included; it is asked for every item in order and may keep running maxima of its own -- and while the items taken
+// stay below `limit` (what one launch takes) and `item_target`, and their pixels below `px_target`.  The first item always joins.
+struct CutRule { size_t limit, item_target = ~(size_t)0, px_target = ~(size_t)0; };
+template <class Px, class Cap>                        // (a caller whose items are k units each passes capacity / k and limit / k)
+size_t next_sub_batch(size_t i0, size_t n, Px &&px, Cap &&cap, const CutRule &rule) {
+    size_t i1 = i0, mp = 0, sum = 0;
+    while (i1 < n) {
+        const size_t p = px(i1), cnt = i1 - i0;
+        mp = std::max(mp, p);
+        const size_t c = cap(i1, mp);
+        if (cnt > 0 && (cnt + 1 > c || cnt >= rule.limit || cnt >= rule.item_target || sum >= rule.px_target)) break;
+        sum += p; i1++;
+    }
+    return i1;
+}
+// cap(i, mp) of a capacity that depends on the largest item alone: f(mp), asked again only when mp has changed (f may ask the device)
+template <class F>
+auto cap_by_largest(F f) {
+    return [f, last = ~(size_t)0, c = (size_t)0](size_t, size_t mp) mutable { if (mp != last) { last = mp; c = f(mp); } return c; };
 }
 
 // MIC_HIP_TRACE=1: the pipeline's parts, the decode's stages with wall times and the devices' shards on stderr

@@ -5,10 +5,10 @@
 // address its streams are copied from (the caller's file, a file in device memory).  The host plans (strips_plan_crops): a strip is a
 // unit of its own, so a crop needs the strips it overlaps and no others -- the plan is those (file, strip) units, each once, and the
 // (crop, strip) overlaps, pieces.  The units go through the unit codec in sub-batches under the workspace ceiling, each into a slab
-// of decoded strips, and behind each sub-batch the shared gather (launch_gather, mic_gather.hip) copies its pieces out of the slab
-// into the crop tensor.
-#include "mic_session.h"
-#include "mic_pieces.h"
+// of decoded strips, and behind each sub-batch the shared gather copies its pieces out of the slab into the crop tensor.
+// Shared with the MIC3 patch and MIC2 crop readers (mic_rects.h): the piece record, the sub-batch layout, the gather list and its
+// launch, the status fold and the tensor check.  Here: the strip tables, the plan, the capacity of a sub-batch and its decode.
+#include "mic_rects.h"
 
 namespace {
 
@@ -23,11 +23,10 @@ struct StripFile {
 };
 constexpr uint32_t kNoUnit = 0xFFFFFFFFu;
 struct StripUnit { uint32_t file, strip; };
-struct PlannedPiece { int32_t crop; uint32_t unit; int32_t sx, sy, dx, dy, w, h; };
 struct StripPlan {
     std::vector<StripFile> files;
     std::vector<StripUnit> units;           // the strips to entropy-decode, ascending by file, then strip, each once
-    std::vector<PlannedPiece> pieces;       // sorted by unit (stable: crop order inside a unit)
+    std::vector<RectPiece> pieces;          // rect: the crop; sorted by unit (stable: crop order inside a unit)
     uint64_t strips_total = 0;              // strips of the files some crop names
 };
 
@@ -102,8 +101,8 @@ int strips_plan_crops(StripPlan &plan, const int32_t *xyf, int n, int cw, int ch
         for (size_t k = c.k0; k < c.k1; k++) {
             const StripEntry &e = f.e[k];
             const int64_t r0 = std::max<int64_t>(c.y0, e.y0), r1 = std::min<int64_t>(c.y1, e.y1);
-            plan.pieces[first[f.count[k]]++] = PlannedPiece{ i, f.count[k], (int32_t)c.x0, (int32_t)(r0 - e.y0), (int32_t)(c.x0 - x), (int32_t)(r0 - y),
-                                                             (int32_t)(c.x1 - c.x0), (int32_t)(r1 - r0) };
+            plan.pieces[first[f.count[k]]++] = RectPiece{ i, f.count[k], (int32_t)c.x0, (int32_t)(r0 - e.y0), (int32_t)(c.x0 - x), (int32_t)(r0 - y),
+                                                          (int32_t)(c.x1 - c.x0), (int32_t)(r1 - r0) };
         }
     }
     return MIC_OK;
@@ -120,13 +119,8 @@ int strips_crop_args(const void *files, const size_t *lens, int nfiles, const in
 // Units [i0, i1) of the next sub-batch: as many as the workspace ceiling holds of the largest of them -- a unit's tier-2 slabs and its
 // strip in the staging slab, as every MIC2 chain counts a frame (mic2_batch_cuts) -- and at most what one launch chain takes.
 size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0, size_t budget) {
-    size_t max_px = 0, i1 = i0;
-    while (i1 < px.size()) {
-        const size_t mp = std::max(max_px, px[i1]);
-        if (i1 > i0 && (i1 - i0 + 1 > budget / (unit_ws_bytes(mp) + 2 * mp) || i1 - i0 >= 65535)) break;
-        max_px = mp; i1++;
-    }
-    return i1;
+    return next_sub_batch(i0, px.size(), [&](size_t i) { return px[i]; },
+                          [&](size_t, size_t mp) { return budget / (unit_ws_bytes(mp) + 2 * mp); }, CutRule{ 65535 });
 }
 size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0) { return next_strip_cut(px, i0, kWorkspaceBudget); }
 
@@ -141,88 +135,51 @@ int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
     HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the images, rows no strip covers, refused files
     auto entry = [&](size_t u) -> const StripEntry & { return plan.files[plan.units[u].file].e[plan.units[u].strip]; };
-    std::vector<size_t> px(nu), cuts{ 0 };
-    for (size_t u = 0; u < nu; u++) px[u] = (size_t)plan.files[plan.units[u].file].w * (size_t)(entry(u).y1 - entry(u).y0);
-    while (cuts.back() < nu) cuts.push_back(next_strip_cut(px, cuts.back()));
-    // every unit's place in its sub-batch's slab, the largest slab and the most stream bytes of a sub-batch
-    std::vector<uint64_t> slab_off(nu);
-    size_t slab_max = 0, comp_max = 0;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        size_t off = 0, comp = 0;
-        for (size_t u = cuts[b]; u < cuts[b + 1]; u++) { slab_off[u] = off; off += px[u]; comp += entry(u).len; }
-        slab_max = std::max(slab_max, off); comp_max = std::max(comp_max, comp);
-    }
-    std::vector<size_t> first(nu + 1, 0);                                                   // the pieces of unit u
-    std::vector<GatherPiece> list(plan.pieces.size());                                      // a strip starts slab_off samples into its sub-batch's slab
-    int mw = 1, mh = 1;
-    for (size_t q = 0; q < plan.pieces.size(); q++) {
-        const PlannedPiece &p = plan.pieces[q];
-        first[(size_t)p.unit + 1]++;
-        const int fw = plan.files[plan.units[p.unit].file].w;
-        list[q] = GatherPiece{ slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)fw + (uint64_t)p.sx,
-                               ((uint64_t)p.crop * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx, fw, cw, p.w, p.h, 0, 0 };
-        mw = std::max(mw, p.w); mh = std::max(mh, p.h);
-    }
-    for (size_t u = 0; u < nu; u++) first[u + 1] += first[u];
+    auto width = [&](size_t u) { return plan.files[plan.units[u].file].w; };
+    std::vector<size_t> px(nu);
+    for (size_t u = 0; u < nu; u++) px[u] = (size_t)width(u) * (size_t)(entry(u).y1 - entry(u).y0);
+    const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_strip_cut(px, i0); }, [&](size_t u) { return px[u]; },
+                                       plan.pieces, cw, ch, [&](size_t u) { return UnitStride{ width(u), 0 }; });
+    size_t comp_max = 0;                                                                    // the most stream bytes of a sub-batch
+    for (size_t b = 0, comp = 0; b < L.subs(); b++, comp = 0)
+        for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) comp_max = std::max(comp_max, comp += entry(u).len);
     if (nu) {
-        if ((rc = s->pieces.reserve(list.size() * sizeof(GatherPiece)))) return rc;
         if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
-        if ((rc = s->io_px.reserve(slab_max * 2 + 64))) return rc;
-        HIP_TRY(hipMemcpyAsync(s->pieces.p, list.data(), list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+        if ((rc = s->io_px.reserve(L.slab_max * 2 + 64))) return rc;
+        if ((rc = upload_gather(s, L))) return rc;
     }
     std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
     std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
-    for (size_t b = 0; b + 1 < cuts.size(); b++) {
-        const size_t u0 = cuts[b];
-        const int nb = (int)(cuts[b + 1] - u0);
+    for (size_t b = 0; b < L.subs(); b++) {
+        const size_t u0 = L.cuts[b];
+        const int nb = (int)(L.cuts[b + 1] - u0);
         if ((rc = pack_streams(s, nb, [&](int i) { return (uint64_t)entry(u0 + (size_t)i).len; },
                                [&](int i) { return base[plan.units[u0 + (size_t)i].file] + entry(u0 + (size_t)i).start; }, device, begins, ends))) return rc;
         units.resize((size_t)nb);
         for (int i = 0; i < nb; i++) {
             const StripEntry &e = entry(u0 + (size_t)i);
-            units[(size_t)i] = mic_hip_unit{ slab_off[u0 + (size_t)i], plan.files[plan.units[u0 + (size_t)i].file].w, (int32_t)(e.y1 - e.y0), 0, e.flags };
+            units[(size_t)i] = mic_hip_unit{ L.slab_off[u0 + (size_t)i], width(u0 + (size_t)i), (int32_t)(e.y1 - e.y0), 0, e.flags };
         }
         if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
         if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
-        const size_t p0 = first[u0], np = first[u0 + (size_t)nb] - p0;
-        s->timer.reset(s->stream); s->timer.mark("k_strips_gather_crops");
-        launch_gather(s->stream, kGatherU16, (const uint16_t *)s->io_px.p, (const GatherPiece *)s->pieces.p + p0, np, mw, mh, d_out);
+        s->timer.reset(s->stream);
+        gather_units(s, "k_strips_gather_crops", kGatherU16, s->io_px.p, L, b, d_out);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    for (int i = 0; i < n; i++) {
-        if (status) status[i] = MIC_OK;
-        if (failed_strip) failed_strip[i] = -1;
-    }
-    std::vector<char> failed(status || failed_strip ? (size_t)n : 0, 0);                   // (pieces are in strip order inside a crop's file)
-    for (const PlannedPiece &p : plan.pieces) {
-        if (failed.empty() || failed[(size_t)p.crop] || ust[p.unit] == MIC_OK) continue;
-        failed[(size_t)p.crop] = 1;
-        if (status) status[p.crop] = ust[p.unit];
-        if (failed_strip) failed_strip[p.crop] = (int32_t)plan.units[p.unit].strip;
-    }
-    if (stats) *stats = mic_hip_strip_crop_stats{ nu, plan.strips_total, plan.pieces.size(), cuts.size() - 1 };
+    fold_unit_status(plan.pieces, ust, n, 1, status, failed_strip, [&](uint32_t u) { return (int32_t)plan.units[u].strip; });   // (pieces are in strip order inside a crop's file)
+    if (stats) *stats = mic_hip_strip_crop_stats{ nu, plan.strips_total, plan.pieces.size(), L.subs() };
     return MIC_OK;
-}
-
-// a refused file's code for each of its crops (which have no pieces: their samples stay 0)
-void file_codes(const StripPlan &plan, const int32_t *xyf, int n, int32_t *status) {
-    if (!status) return;
-    for (int i = 0; i < n; i++) {
-        const int32_t fs = plan.files[(size_t)xyf[3 * (size_t)i + 2]].status;
-        if (fs != MIC_OK) status[i] = fs;
-    }
 }
 
 // a door's call: arguments, n == 0, the plan, the pointer, then the core on session s (leased here when s is NULL)
 int strips_call(mic_hip_session *s, StripPlan &plan, const uint8_t *const *base, bool device, const int32_t *xyf, int n, int cw, int ch,
                 void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
-    const unsigned __int128 bytes = (unsigned __int128)n * (unsigned)ch * (unsigned)cw * 2;
-    if (bytes > out_cap) return MIC_ERR_CAPACITY;
-    const size_t need = (size_t)bytes;
-    int rc = strips_plan_crops(plan, xyf, n, cw, ch);
+    size_t need = 0;
+    int rc = tensor_bytes(n, 1, ch, cw, 2, out_cap, &need);
     if (rc) return rc;
+    if ((rc = strips_plan_crops(plan, xyf, n, cw, ch))) return rc;
     if (stats) *stats = mic_hip_strip_crop_stats{ 0, 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
@@ -230,7 +187,7 @@ int strips_call(mic_hip_session *s, StripPlan &plan, const uint8_t *const *base,
     DefaultLease lease;
     if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
     if ((rc = strips_read_crops(s, plan, base, device, n, cw, ch, d_out, need, status, failed_strip, stats))) return rc;
-    file_codes(plan, xyf, n, status);
+    container_codes(n, status, [&](int i) { return plan.files[(size_t)xyf[3 * (size_t)i + 2]].status; });
     return MIC_OK;
 }
 

@@ -120,4 +120,31 @@ last = {tuple(c): k for c, (zf, k) in zip(M.crops_of(xyzv, 0)[1], zrange(0))}
 assert len(last) == len(order[0][2]) and 0 < sum(k >= 5 for k in last.values()) < len(last)
 assert any(units[c][0] > 0 for c in cuts[1:-1])                           # (volumes behind it start in later sub-batches)
 run([damaged] + files[1:], want2, lambda c: (code, 5) if c[3] == 0 and code and last[tuple(c[:3])] >= 5 else (0, -1))
+
+# Sub-batches whose largest pieces differ: the gather's grid y follows the largest piece of each sub-batch.  Independent volumes
+# only (temporal ones are not gathered), crops of 65 x 64: such a piece takes two row chunks, the 1 x 1 and 25 x 4 pieces of the
+# first sub-batch one.  The first crop touches the first unit -- the 7 x 35 frame -- in its corner pixel alone, the last one lies
+# wholly inside the last unit, frame 5 of the 160 x 96 volume.
+names = ["tiny", "narrow", "xr12", "wrap16"]
+vols2 = [made[k][0] for k in names]
+files2 = [mic.compress_multi_frame(v, v.shape[2], v.shape[1], made[k][1], temporal=False) for k, v in zip(names, vols2)]
+for f, v in zip(files2, vols2):
+    assert np.array_equal(mic.decompress_multi_frame(f), v)                # the whole-volume decode is the source
+xyzv2 = [(-64, -63, 0, 0), (-40, -60, 0, 1), (10, 3, 0, 2), (10, 3, 3, 2), (20, 10, 3, 3)]
+want3 = M.expected_multi(vols2, xyzv2, 65, 64, 3)
+assert np.count_nonzero(want3[0]) <= 1 and want3[0, 0, 63, 64] == vols2[0][0, 0, 0] and (want3[4] == vols2[3][3:6, 10:74, 20:85]).all()
+units2, pieces2, _ = mic.mic2_multi_crop_plan(files2, xyzv2, 65, 64, 3)
+units2 = [tuple(u) for u in units2.tolist()]
+assert len(units2) == 13 and units2[0] == (0, 0) and units2[-1] == (3, 5)
+cuts2 = M.cuts_of([vols2[v].shape[1] * vols2[v].shape[2] for v, f in units2], budget)
+assert cuts2[1] <= 4 and len(cuts2) - 1 >= 2, cuts2                        # the first sub-batch ends before the large frames' pieces
+sess = mic.Session(4, 160 * 96)
+d_files2 = [torch.from_numpy(np.frombuffer(f, dtype=np.uint8).copy()).cuda() for f in files2]
+for k, door in enumerate([lambda *a: mic.mic2_multi_read_crops(files2, *a),
+                          lambda *a: sess.mic2_multi_read_crops([M.Mic2File(f).head() for f in files2], [d.data_ptr() for d in d_files2], [len(f) for f in files2], *a)]):
+    t = torch.full((len(xyzv2), 3, 64, 65, 2), 0xA5, dtype=torch.uint8, device="cuda")
+    st, bad, stats = door(xyzv2, 65, 64, 3, t.data_ptr(), t.numel())
+    assert (st == 0).all() and stats["slabs"] == len(cuts2) - 1 and stats["slabs"] >= 2 and stats["pieces"] == pieces2, (k, stats)
+    assert np.array_equal(t.cpu().numpy().view("<u2")[..., 0], want3), k
+sess.close()
 print("mic2 multi crop seams ok")

@@ -39,5 +39,26 @@ t = torch.full((1, 4, 8, 2), 0xA5, dtype=torch.uint8, device="cuda")
 st, bad, stats = mic.strips_read_crops(datas, [(30, 10, 0)], 8, 4, t.data_ptr(), t.numel())
 assert np.array_equal(t.cpu().numpy().view("<u2")[..., 0], F.expected(files, [(30, 10, 0)], 8, 4)) and (st == 0).all()
 assert (stats["strips_decoded"], stats["slabs"]) == (1, 1), stats
+# Sub-batches whose largest pieces differ: the gather's grid y follows the largest piece of each sub-batch.  Crops of 65 x 64 over
+# the five files and a sixth of one 96 x 70 strip: the first crop touches the first unit, strip 0 of A, in its corner pixel alone
+# (a 1 x 1 piece, one row chunk), the last lies wholly inside the last unit (a 65 x 64 piece, two row chunks); B's and C's strips
+# lie between them.
+one = mic.compress_parallel_strips(files[0][1], 96, 70, 4095, 1, 2)
+px, w, h = mic.decompress_parallel_strips(one)
+assert (w, h) == (96, 70) and np.array_equal(np.asarray(px).reshape(70, 96), files[0][1])   # the whole-image decode is the source
+files6, datas6 = files + [("F", files[0][1], bytes(one))], datas + [bytes(one)]
+xyf = [(-64, -63, 0), (0, 0, 1), (20, 3, 2), (10, 3, 5)]
+want = F.expected(files6, xyf, 65, 64)
+assert np.count_nonzero(want[0]) <= 1 and want[0, 63, 64] == files[0][1][0, 0] and np.array_equal(want[3], files[0][1][3:67, 10:75])
+units, pieces, _ = mic.strips_crop_plan(datas6, xyf, 65, 64)
+assert len(units) >= 7 and tuple(units[0]) == (0, 0) and tuple(units[-1]) == (5, 0), units
+d_one = torch.from_numpy(np.frombuffer(datas6[5], dtype=np.uint8).copy()).cuda()
+for k, door in enumerate([lambda *a: mic.strips_read_crops(datas6, *a),
+                          lambda *a: sess.strips_read_crops(heads + [mic.strips_head(datas6[5])], ptrs + [d_one.data_ptr()], lens + [len(datas6[5])], *a)]):
+    t = torch.full((len(xyf), 64, 65, 2), 0xA5, dtype=torch.uint8, device="cuda")
+    st, bad, stats = door(xyf, 65, 64, t.data_ptr(), t.numel())
+    assert (st == 0).all() and stats["strips_decoded"] == len(units) and stats["pieces"] == pieces and stats["slabs"] >= 2, (k, stats)
+    assert stats["slabs"] == -(-len(units) // 2), (k, stats)                # two strips a sub-batch: first and last unit apart
+    assert np.array_equal(t.cpu().numpy().view("<u2")[..., 0], want), k
 sess.close()
 print("strip crop seams ok")

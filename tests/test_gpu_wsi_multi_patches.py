@@ -203,6 +203,25 @@ q = %r
 t = torch.full((len(q), 20, 24, 3), 0xA5, dtype=torch.uint8, device="cuda")
 st, stats = mic.wsi_multi_read_patches(files, q, 24, 20, t.data_ptr(), t.numel())
 assert (st == 0).all() and stats["tiles_decoded"] == 27 and stats["slabs"] >= 2, stats
+# Sub-batches whose largest pieces differ (the gather's grid y follows the largest piece of each sub-batch): patches of 65 x 64 over
+# B, C and a slide of 128 x 128 tiles.  The first patch touches the first unit, B's tile 0, in its corner pixel alone; C's nine
+# 16 x 16 tiles follow; the last patch lies wholly inside the last unit, the slide's tile 3 -- a 65 x 64 piece, two row chunks.
+yy, xx = np.mgrid[0:256, 0:256]
+ramp = (3 * xx + 2 * yy) // 2 + np.random.default_rng(13).integers(0, 4, (256, 256))
+big = np.stack([ramp %% 256, (ramp // 2 + 40) %% 256, (255 - ramp) %% 256], -1).astype(np.uint8)
+files2 = [files[1], files[2], mic.compress_wsi(big, 256, 256, tile_w=128, tile_h=128, levels=1)]
+whole = [mic.decompress_wsi_level(f, 0) for f in files2]
+assert np.array_equal(whole[2], big)
+q2 = [(-64, -63, 0, 0), (0, 0, 1, 0), (130, 130, 2, 0)]
+slide_of, tile_of, pieces, fs = mic.wsi_multi_patch_plan(files2, q2, 65, 64)
+assert slide_of.tolist() == [0] + [1] * 9 + [2] and tile_of.tolist()[0] == 0 and tile_of.tolist()[-1] == 3 and pieces == 11
+t2 = torch.full((len(q2), 64, 65, 3), 0xA5, dtype=torch.uint8, device="cuda")
+st, stats = mic.wsi_multi_read_patches(files2, q2, 65, 64, t2.data_ptr(), t2.numel())
+assert (st == 0).all() and stats["tiles_decoded"] == 11 and stats["slabs"] >= 2, stats
+got = t2.cpu().numpy()
+for i, (x, y, s, l) in enumerate(q2):
+    assert np.array_equal(got[i], M.S.expected(whole[s], [(x, y)], 65, 64)[0]), q2[i]
+assert np.count_nonzero(got[0].any(-1)) <= 1 and np.array_equal(got[0, 63, 64], whole[0][0, 0]) and np.array_equal(got[2], big[130:194, 130:195])
 print("ok", hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest())
 ''' % (ROOT, os.path.join(ROOT, "tests"), q)
     env = dict(os.environ, MIC_HIP_WS_BUDGET_MB="8")
