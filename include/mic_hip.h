@@ -529,6 +529,45 @@ int mic_hip_wavelet_v2_decompress_level(const uint8_t *compressed, size_t compre
 int mic_hip_wavelet_v2_decompress_level_batch(const uint8_t *const *files, const size_t *lens, int nframes, int level,
                                               uint16_t *pixels_out, size_t out_cap_px, int32_t *status, uint64_t *symbols_decoded);
 
+/* Frames of ANY shapes and level counts in one call (no reference counterpart: WaveletV2RLEFSECompressU16 / ...DecompressU16,
+ * waveletfsecompressu16.go:303-534, of every job).  A directory mixes shapes and level counts, and a WaveletV2 file is one serial tANS
+ * stream: grouped by shape on the host, a group of three frames pays the launch chain's latency as 256 frames do.  Here every launch is
+ * driven by a table of the frames -- a 2 x 2 frame beside a 2140 x 1760 one costs one block -- and a frame takes part in the transform
+ * levels it has.
+ * A job's file equals mic_hip_wavelet_v2_compress's byte for byte (levels_applied: the level count its header carries, :321-330); a
+ * decoded job equals mic_hip_wavelet_v2_decompress's, or -- level > 0 -- mic_hip_wavelet_v2_decompress_level's: out_rows x out_cols =
+ * nr[level] x nc[level] pixels, row stride out_cols.  The calls return MIC_OK when the batch ran; a job with bad arguments
+ * (MIC_ERR_ARGS: a null pointer, a side <= 0, level < 0 or > the header's levels), a shape over 2^27 pixels (MIC_ERR_UNSUPPORTED), a
+ * buffer too small (MIC_ERR_CAPACITY), a file shorter than 13 bytes, with a bad header or no four-state stream (MIC_ERR_CORRUPT), or a
+ * frame the FSE stage refuses fails alone with its code in `status` and does not move its neighbours' outputs.
+ * The jobs are cut into sub-batches (mic_hip_wavelet_v2_batch_plan) that run one launch chain each, their transfers beside the
+ * neighbours' kernels; buffers from mic_hip_host_alloc are sent in place; with several devices (mic_hip_set_devices) the jobs are
+ * shared out by pixels.  Every unit of a sub-batch is laid out by its largest frame (the tier-2 slabs of this path are not tiered),
+ * which the cut rule bounds.
+ * stats (nullable): sub_batches = the sub-batches run, chains = the launch chains (one per sub-batch, one more for each sub-batch whose
+ * reduced decode sent frames round again whole), frames_done = jobs with MIC_OK, redo_frames = the frames decoded twice. */
+typedef struct mic_hip_wv_enc_job {
+    const uint16_t *pixels; int32_t rows, cols; uint16_t max_value; int32_t levels;   /* in  */
+    uint8_t *out; size_t out_cap;                                                     /* in  */
+    size_t out_len; int32_t status; int32_t levels_applied;                           /* out */
+} mic_hip_wv_enc_job;
+typedef struct mic_hip_wv_dec_job {
+    const uint8_t *compressed; size_t compressed_len; int32_t level;                  /* in: 0 = full image */
+    uint16_t *pixels_out; size_t out_cap_px;                                          /* in  */
+    int32_t rows, cols, levels;       /* out: the header's (0 when refused) */
+    int32_t out_rows, out_cols;       /* out: what was written, nr[level] x nc[level] */
+    int32_t status; uint64_t symbols_decoded;                                         /* out */
+} mic_hip_wv_dec_job;
+typedef struct { uint64_t sub_batches, chains, frames_done, redo_frames; } mic_hip_wv_batch_stats;
+int mic_hip_wavelet_v2_compress_jobs  (mic_hip_wv_enc_job *jobs, int njobs, mic_hip_wv_batch_stats *stats);
+int mic_hip_wavelet_v2_decompress_jobs(mic_hip_wv_dec_job *jobs, int njobs, mic_hip_wv_batch_stats *stats);
+/* The cut of the calls above (host only, needs no device): rc = nframes x (rows, cols); a sub-batch takes frames in order while they
+ * stay within budget_bytes / (workspace of a unit of the largest frame so far + its planes), 65535 frames and 2^30 pixels; the first
+ * frame always joins.  budget_bytes 0: the calls' own ceiling.  cuts[0 .. *ncuts) = 0, ..., nframes; more than `cap`:
+ * MIC_ERR_CAPACITY with *ncuts set; a side <= 0: MIC_ERR_ARGS. */
+int mic_hip_wavelet_v2_batch_plan(const int32_t *rc, int nframes, size_t budget_bytes,
+                                  uint32_t *cuts, size_t cap, uint64_t *ncuts);
+
 /* ---- MIC3 container: tiled RGB whole-slide images ---------------------------------------------- */
 /* Replaces CompressWSI (wsicompress.go:27) + WriteMIC3 (wsiformat.go:99) for 8-bit RGB with the
  * YCoCg-R colour transform (forced on for RGB, wsiformat.go:93-95).  tile_w / tile_h = 0 select the
@@ -832,6 +871,18 @@ int mic_hip_session_wavelet_v2_decode(mic_hip_session *s, const uint8_t *d_strea
  * h_symbols_decoded (nullable): tANS symbols decoded per frame. */
 int mic_hip_session_wavelet_v2_decode_level(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, int nframes,
                                             int rows, int cols, int levels, int level, uint16_t *d_pixels_out,
+                                            int32_t *h_status, uint64_t *h_symbols_decoded);
+/* The same pair over frames of any shapes in ONE launch chain (mic_hip_wavelet_v2_compress_jobs on device-resident data; the caller
+ * cuts lists that outgrow the workspace, mic_hip_wavelet_v2_batch_plan).  encode_mixed: frame i = h_rows_cols[2 i] x h_rows_cols[2 i + 1]
+ * u16 at d_frames + h_px_offsets[i] (elements), `levels` asked of every frame; its header-less stream at *d_streams + h_offsets[i] ..
+ * h_offsets[i + 1] (empty when h_status[i] != MIC_OK), h_levels_applied[i] = what its header carries.  decode_mixed: stream i of a frame
+ * of h_rows_cols_levels[3 i .. 3 i + 2], wanted at h_level[i] (NULL: all 0); its nr[level] x nc[level] pixels to d_pixels_out +
+ * h_out_offsets[i] (elements).  A frame refused by the argument gate fails alone. */
+int mic_hip_session_wavelet_v2_encode_mixed(mic_hip_session *s, const uint16_t *d_frames, const uint64_t *h_px_offsets, const int32_t *h_rows_cols,
+                                            int nframes, int levels, const uint8_t **d_streams, uint64_t *h_offsets, int32_t *h_status,
+                                            int32_t *h_levels_applied);
+int mic_hip_session_wavelet_v2_decode_mixed(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, const int32_t *h_rows_cols_levels,
+                                            const int32_t *h_level, int nframes, uint16_t *d_pixels_out, const uint64_t *h_out_offsets,
                                             int32_t *h_status, uint64_t *h_symbols_decoded);
 /* MIC3 on a device-resident slide (BASELINE config 5 as bench.py times it).  encode = CompressWSI (wsicompress.go:27-171) up
  * to, but without, the container: pyramid, tiles, YCoCg-R, plane modes and every plane's CompressSingleFrame on the device, the

@@ -171,6 +171,26 @@ class Mic2Volume(C.Structure):
                 ("max_value", C.c_uint16), ("temporal", C.c_uint16)]
 
 
+class WvEncJob(C.Structure):
+    """mic_hip_wv_enc_job"""
+    _fields_ = [("pixels", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("max_value", C.c_uint16), ("levels", C.c_int32),
+                ("out", C.c_void_p), ("out_cap", C.c_size_t), ("out_len", C.c_size_t), ("status", C.c_int32),
+                ("levels_applied", C.c_int32)]
+
+
+class WvDecJob(C.Structure):
+    """mic_hip_wv_dec_job"""
+    _fields_ = [("compressed", C.c_void_p), ("compressed_len", C.c_size_t), ("level", C.c_int32),
+                ("pixels_out", C.c_void_p), ("out_cap_px", C.c_size_t),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("levels", C.c_int32), ("out_rows", C.c_int32), ("out_cols", C.c_int32),
+                ("status", C.c_int32), ("symbols_decoded", C.c_uint64)]
+
+
+class WvBatchStats(C.Structure):
+    """mic_hip_wv_batch_stats"""
+    _fields_ = [("sub_batches", C.c_uint64), ("chains", C.c_uint64), ("frames_done", C.c_uint64), ("redo_frames", C.c_uint64)]
+
+
 class StripCropStats(C.Structure):
     """mic_hip_strip_crop_stats"""
     _fields_ = [("strips_decoded", C.c_uint64), ("strips_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
@@ -200,6 +220,8 @@ ABI_SYMBOLS = [
     "mic_hip_strips_crop_plan", "mic_hip_strips_read_crops", "mic_hip_session_strips_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
+    "mic_hip_wavelet_v2_compress_jobs", "mic_hip_wavelet_v2_decompress_jobs", "mic_hip_wavelet_v2_batch_plan",
+    "mic_hip_session_wavelet_v2_encode_mixed", "mic_hip_session_wavelet_v2_decode_mixed",
     "mic_hip_compress_frame_gap", "mic_hip_decompress_frame_gap", "mic_hip_compress_batch_gap", "mic_hip_decompress_batch_gap",
     "mic_hip_compress_frame_grad", "mic_hip_decompress_frame_grad", "mic_hip_pica_compress", "mic_hip_pica_info", "mic_hip_pica_decompress",
     "mic_hip_pica_compress_ex", "mic_hip_pica_decompress_ex", "mic_hip_pica_compress_batch", "mic_hip_pica_decompress_batch", "mic_hip_pica_boundaries",
@@ -408,6 +430,13 @@ def lib() -> C.CDLL:
     L.mic_hip_wavelet_v2_decompress_level.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
     L.mic_hip_wavelet_v2_decompress_level_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p,
                                                             C.c_size_t, C.POINTER(C.c_int32), C.c_void_p]
+    L.mic_hip_wavelet_v2_compress_jobs.argtypes = [C.POINTER(WvEncJob), C.c_int, C.POINTER(WvBatchStats)]
+    L.mic_hip_wavelet_v2_decompress_jobs.argtypes = [C.POINTER(WvDecJob), C.c_int, C.POINTER(WvBatchStats)]
+    L.mic_hip_wavelet_v2_batch_plan.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.mic_hip_session_wavelet_v2_encode_mixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mic_hip_session_wavelet_v2_decode_mixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]
     L.mic_hip_wsi_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_compress_frame_grad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_decompress_frame_grad.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
@@ -1167,6 +1196,92 @@ def wavelet_v2_decompress_level_batch(files: Sequence[bytes], level: int, counts
     if counts:
         return [int(v) for v in st], out, syms
     return [int(v) for v in st], out
+
+
+def _wv_stats(bs) -> dict:
+    return dict(sub_batches=bs.sub_batches, chains=bs.chains, frames_done=bs.frames_done, redo_frames=bs.redo_frames)
+
+
+def wavelet_v2_batch_plan(rc, budget_bytes: int = 0, cap: Optional[int] = None) -> np.ndarray:
+    """mic_hip_wavelet_v2_batch_plan: the sub-batch cuts [0, ..., nframes] of the jobs calls over frames rc = [(rows, cols)]; a call
+    over these frames runs len(cuts) - 1 sub-batches.  budget_bytes 0: the default workspace ceiling.  Needs no device.  cap: room
+    for that many cuts (default: as many as it takes); too few raises MicError (MIC_ERR_CAPACITY) whose ``ncuts`` is the count."""
+    a = np.ascontiguousarray(np.asarray(rc, dtype=np.int64).reshape(-1, 2).astype(np.int32))
+    nc = C.c_uint64(0)
+    if cap is None:
+        r = lib().mic_hip_wavelet_v2_batch_plan(a.ctypes.data, len(a), int(budget_bytes), None, 0, C.byref(nc))
+        if r not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(r, "wavelet_v2_batch_plan")
+        cap = nc.value
+    cuts = np.zeros(max(cap, 1), dtype=np.uint32)
+    r = lib().mic_hip_wavelet_v2_batch_plan(a.ctypes.data, len(a), int(budget_bytes), cuts.ctypes.data, cap, C.byref(nc))
+    if r:
+        e = MicError(r, "wavelet_v2_batch_plan")
+        e.ncuts = nc.value
+        raise e
+    return cuts[: nc.value].copy()
+
+
+def wavelet_v2_compress_jobs(frames: Sequence, max_values, levels=5, outs: Optional[Sequence[np.ndarray]] = None,
+                             caps: Optional[Sequence[Optional[int]]] = None):
+    """mic_hip_wavelet_v2_compress_jobs: frames of ANY shapes -- each a (rows, cols) uint16 array; None: a NULL pointer -- in one
+    call, every file as wavelet_v2_compress writes it (`max_values` and `levels`: one value, or one per frame).  outs: the callers'
+    output buffers (e.g. from host_alloc); caps: a capacity per job instead of the buffer's size.
+    -> ([(status, file bytes, levels applied)], stats dict: sub_batches, chains, frames_done, redo_frames); a job fails alone."""
+    n = len(frames)
+    mv = [int(max_values)] * n if np.isscalar(max_values) else [int(v) for v in max_values]
+    lv = [int(levels)] * n if np.isscalar(levels) else [int(v) for v in levels]
+    px = [None if f is None else np.ascontiguousarray(f, dtype=np.uint16) for f in frames]
+    jobs = (WvEncJob * max(n, 1))()
+    bufs = []
+    for i in range(n):
+        rows, cols = (0, 0) if px[i] is None else px[i].shape
+        out = outs[i] if outs is not None else np.empty(rows * cols * 6 + 200000, dtype=np.uint8)
+        bufs.append(out)
+        cap = out.nbytes if caps is None or caps[i] is None else int(caps[i])
+        jobs[i] = WvEncJob(None if px[i] is None else px[i].ctypes.data, rows, cols, mv[i], lv[i], out.ctypes.data, cap, 0, 0, 0)
+    bs = WvBatchStats()
+    rc = lib().mic_hip_wavelet_v2_compress_jobs(jobs, n, C.byref(bs))
+    if rc:
+        _raise(rc, "wavelet_v2_compress_jobs")
+    res = [(int(jobs[i].status), bufs[i].view(np.uint8).reshape(-1)[: jobs[i].out_len].tobytes() if jobs[i].status == 0 else b"",
+            int(jobs[i].levels_applied)) for i in range(n)]
+    return res, _wv_stats(bs)
+
+
+def wavelet_v2_decompress_jobs(files: Sequence, levels=None, outs: Optional[Sequence[np.ndarray]] = None):
+    """mic_hip_wavelet_v2_decompress_jobs: WaveletV2 files of ANY shapes and level counts -- None: a NULL pointer -- in one call,
+    job i at resolution levels[i] (None: all 0, the full images; wavelet_v2_decompress_level's band otherwise).  outs: the callers'
+    uint16 buffers (default: one of the band's size per job).
+    -> ([(status, (out_rows, out_cols) uint16 image or None, tANS symbols decoded)], stats dict); a job fails alone."""
+    n = len(files)
+    lv = [0] * n if levels is None else ([int(levels)] * n if np.isscalar(levels) else [int(v) for v in levels])
+    cs = [None if f is None else _bytes_arr(f) for f in files]
+    jobs = (WvDecJob * max(n, 1))()
+    bufs = []
+    for i in range(n):
+        if outs is not None:
+            out = outs[i]
+        else:
+            r = cc = 0
+            if cs[i] is not None:
+                a, b = C.c_int(), C.c_int()
+                if lib().mic_hip_wavelet_v2_level_info(cs[i].ctypes.data, cs[i].size, lv[i], C.byref(a), C.byref(b)) == MIC_OK:
+                    r, cc = max(a.value, 0), max(b.value, 0)
+            out = np.zeros(max(r * cc, 1) if r * cc <= (1 << 27) else 1, dtype=np.uint16)
+        bufs.append(out)
+        jobs[i] = WvDecJob(None if cs[i] is None else cs[i].ctypes.data, 0 if cs[i] is None else cs[i].size, lv[i],
+                           out.ctypes.data, out.size)
+    bs = WvBatchStats()
+    rc = lib().mic_hip_wavelet_v2_decompress_jobs(jobs, n, C.byref(bs))
+    if rc:
+        _raise(rc, "wavelet_v2_decompress_jobs")
+    res = []
+    for i in range(n):
+        j = jobs[i]
+        img = bufs[i].reshape(-1)[: j.out_rows * j.out_cols].reshape(j.out_rows, j.out_cols) if j.status == 0 else None
+        res.append((int(j.status), img, int(j.symbols_decoded)))
+    return res, _wv_stats(bs)
 
 
 # ------------------------------------------------------------------ MIC3 / WSI
@@ -1987,6 +2102,38 @@ class Session:
         if rc:
             _raise(rc, "session_wavelet_v2_decode_level")
         return np.array(st[:], dtype=np.int32), syms
+
+    def wavelet_v2_encode_mixed(self, d_frames: int, px_offsets, rows_cols, levels: int = 5):
+        """mic_hip_session_wavelet_v2_encode_mixed: frame i = rows_cols[i] uint16 at d_frames + px_offsets[i] elements, any shapes, ONE
+        launch chain.  -> (device pointer of the packed header-less streams, offsets[n + 1], status[n], levels applied[n])"""
+        rc_ = np.ascontiguousarray(np.asarray(rows_cols, dtype=np.int64).reshape(-1, 2).astype(np.int32))
+        n = len(rc_)
+        po = np.ascontiguousarray(px_offsets, dtype=np.uint64)
+        if po.size < n:
+            raise ValueError("wavelet_v2_encode_mixed: px_offsets must hold one entry per frame")
+        d = C.c_void_p(); offs = np.zeros(n + 1, dtype=np.uint64); st = np.zeros(n, dtype=np.int32); ap = np.zeros(n, dtype=np.int32)
+        rc = lib().mic_hip_session_wavelet_v2_encode_mixed(self._h, d_frames, po.ctypes.data, rc_.ctypes.data, n, int(levels), C.byref(d),
+                                                           offs.ctypes.data, st.ctypes.data, ap.ctypes.data)
+        if rc:
+            _raise(rc, "session_wavelet_v2_encode_mixed")
+        return d.value, offs, st, ap
+
+    def wavelet_v2_decode_mixed(self, d_streams: int, offsets, rows_cols_levels, d_pixels_out: int, out_offsets, level=None):
+        """mic_hip_session_wavelet_v2_decode_mixed: stream i (offsets[i] .. offsets[i + 1]) of a frame of rows_cols_levels[i], wanted at
+        level[i] (None: all 0), to d_pixels_out + out_offsets[i] elements.  -> (status[n], tANS symbols decoded per frame)"""
+        rcl = np.ascontiguousarray(np.asarray(rows_cols_levels, dtype=np.int64).reshape(-1, 3).astype(np.int32))
+        n = len(rcl)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64); oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        if offs.size < n + 1 or oo.size < n:
+            raise ValueError("wavelet_v2_decode_mixed: offsets must hold n + 1 entries, out_offsets n")
+        lv = None if level is None else np.ascontiguousarray(level, dtype=np.int32)
+        st = np.zeros(n, dtype=np.int32); syms = np.zeros(n, dtype=np.uint64)
+        rc = lib().mic_hip_session_wavelet_v2_decode_mixed(self._h, d_streams, offs.ctypes.data, rcl.ctypes.data,
+                                                           None if lv is None else lv.ctypes.data, n, d_pixels_out, oo.ctypes.data,
+                                                           st.ctypes.data, syms.ctypes.data)
+        if rc:
+            _raise(rc, "session_wavelet_v2_decode_mixed")
+        return st, syms
 
     # ---- MIC3 on a device-resident slide (wsicompress.go:27-171) ---------------------------------------------------------------
     def wsi_encode(self, d_pixels: int, width: int, height: int, channels: int = 3, bits_per_sample: int = 8,

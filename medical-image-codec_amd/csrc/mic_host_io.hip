@@ -743,6 +743,119 @@ int rgb_decode_host(mic_hip_session *s, std::vector<RgbDecRun> &J, int j0, int j
     });
 }
 
+// ============================================================================ WaveletV2: frames of any shapes per call (mic_wavelet.hip)
+// A shard's jobs are cut into sub-batches by wv_next_cut alone -- the rule mic_hip_wavelet_v2_batch_plan states -- and the sub-batches
+// are the PARTS of run_staged: one launch chain each (one more where a reduced decode sends frames round again), and
+// MIC_HIP_PIPELINE_PARTS has no say here.  A part's frames lie back to back in its staging half, its streams and bands likewise.
+struct WvCount {                                       // what the shards of a call add up
+    std::mutex mu; uint64_t subs = 0, chains = 0, redo = 0;
+    void add(uint64_t s, uint64_t c, uint64_t r) { std::lock_guard<std::mutex> lk(mu); subs += s; chains += c; redo += r; }
+};
+// jobs J[j0 .. j1) (checked: arguments fine) on session s
+int wv_encode_host(mic_hip_session *s, std::vector<mic_hip_wv_enc_job *> &J, int j0, int j1, WvCount &count) {
+    if (j0 >= j1) return MIC_OK;
+    int rc = s->ensure(1, 1);                                             // (the stream)
+    if (rc) return rc;
+    auto npx = [&](size_t i) { return (size_t)J[i]->rows * (size_t)J[i]->cols; };
+    const size_t budget = kWorkspaceBudget;
+    struct Sub { int i0, i1; std::vector<WvEncFrame> fr; size_t px; };
+    const std::vector<Sub> subs = staged_cut<Sub>(j0, j1, [&](int i0) { return (int)wv_next_cut(npx, (size_t)i0, (size_t)j1, budget); }, [&](int i0, int i1) {
+        Sub sb{ i0, i1, {}, 0 };
+        for (int i = i0; i < i1; i++) {
+            sb.fr.push_back(WvEncFrame{ (uint64_t)sb.px, J[(size_t)i]->rows, J[(size_t)i]->cols, J[(size_t)i]->levels_applied });
+            sb.px += npx((size_t)i);
+        }
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("wavelet encode", k, subs.size(), "frames", subs[k].i0, subs[k].i1, subs[k].px);
+    DevBuf *in[2] = { &s->io_px, &s->io_px2 };
+    IoReq *prev = nullptr;                                // the download of the part before: keep_packed waits for it
+    return run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        const Sub &sb = subs[k];
+        int r = in[half]->reserve(sb.px * 2 + 64);
+        for (int i = sb.i0; i < sb.i1 && r == MIC_OK; i++)
+            r = io_submit(up, s->device, (uint16_t *)in[half]->p + sb.fr[(size_t)(i - sb.i0)].px_off, J[(size_t)i]->pixels, npx((size_t)i) * 2, true);
+        return r;
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        const Sub &sb = subs[k];
+        const int nb = sb.i1 - sb.i0;
+        std::vector<uint64_t> offs((size_t)nb + 1); std::vector<int32_t> st((size_t)nb);
+        const uint8_t *d_blobs = nullptr;
+        int rc = wv_encode_run(s, (const uint16_t *)in[half]->p, sb.fr.data(), nb, &d_blobs, offs.data(), st.data());
+        if (rc == MIC_OK) rc = keep_packed(s, prev);
+        if (rc != MIC_OK) return rc;
+        prev = &down;
+        count.add(1, 1, 0);
+        for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
+            mic_hip_wv_enc_job &j = *J[(size_t)i];
+            const size_t q = (size_t)(i - sb.i0), len = (size_t)(offs[q + 1] - offs[q]);
+            if ((j.status = st[q]) != MIC_OK) continue;
+            if (11 + len > j.out_cap) { j.status = MIC_ERR_CAPACITY; continue; }
+            wv_put_header(j.out, j.rows, j.cols, j.max_value, j.levels_applied);
+            rc = io_submit(down, s->device, const_cast<uint8_t *>(d_blobs) + offs[q], j.out + 11, len, false);   // the job's stream: one copy
+            j.out_len = 11 + len;
+        }
+        return rc;
+    });
+}
+
+// jobs J[j0 .. j1) (checked: header and arguments fine, rows / cols / levels / out_rows / out_cols set) on session s
+int wv_decode_host(mic_hip_session *s, std::vector<mic_hip_wv_dec_job *> &J, int j0, int j1, WvCount &count) {
+    if (j0 >= j1) return MIC_OK;
+    int rc = s->ensure(1, 1);
+    if (rc) return rc;
+    auto npx = [&](size_t i) { return (size_t)J[i]->rows * (size_t)J[i]->cols; };
+    auto band = [&](size_t i) { return (size_t)J[i]->out_rows * (size_t)J[i]->out_cols; };
+    const size_t budget = kWorkspaceBudget;
+    // small files in ordinary memory are gathered on the host and go up in one copy; large or pinned ones go up from where they lie
+    struct Sub { int i0, i1; std::vector<WvDecFrame> fr; std::vector<uint8_t> small; size_t comp, px; };
+    std::vector<Sub> subs = staged_cut<Sub>(j0, j1, [&](int i0) { return (int)wv_next_cut(npx, (size_t)i0, (size_t)j1, budget); }, [&](int i0, int i1) {
+        Sub sb{ i0, i1, {}, {}, 0, 0 };
+        for (int i = i0; i < i1; i++) {
+            const mic_hip_wv_dec_job &j = *J[(size_t)i];
+            sb.fr.push_back(WvDecFrame{ 0, 0, (uint64_t)sb.px, j.rows, j.cols, j.levels, j.level });
+            sb.px += band((size_t)i);
+        }
+        return sb;
+    });
+    for (size_t k = 0; k < subs.size(); k++) trace_part("wavelet decode", k, subs.size(), "frames", subs[k].i0, subs[k].i1, subs[k].px);
+    DevBuf *in[2] = { &s->io_comp, &s->io_comp2 }, *outb[2] = { &s->io_px, &s->io_px2 };
+    return run_staged(subs.size(), [&](size_t k, int half, IoReq &up) -> int {
+        Sub &sb = subs[k];
+        std::vector<int> direct;
+        auto place = [&](int i, size_t at) { WvDecFrame &f = sb.fr[(size_t)(i - sb.i0)]; f.begin = at; f.end = at + (J[(size_t)i]->compressed_len - 11); };
+        for (int i = sb.i0; i < sb.i1; i++) {                                // (the streams: the files without their 11-byte headers)
+            const mic_hip_wv_dec_job &j = *J[(size_t)i];
+            if (j.compressed_len - 11 <= kInline && !host_is_pinned(j.compressed)) { place(i, sb.small.size()); sb.small.insert(sb.small.end(), j.compressed + 11, j.compressed + j.compressed_len); }
+            else direct.push_back(i);
+        }
+        sb.comp = sb.small.size();
+        for (int i : direct) { place(i, sb.comp); sb.comp += J[(size_t)i]->compressed_len - 11; }
+        int r = in[half]->reserve(sb.comp + 64);
+        if (r == MIC_OK && !sb.small.empty()) r = io_submit(up, s->device, in[half]->p, sb.small.data(), sb.small.size(), true);
+        for (size_t q = 0; q < direct.size() && r == MIC_OK; q++)
+            r = io_submit(up, s->device, (uint8_t *)in[half]->p + sb.fr[(size_t)(direct[q] - sb.i0)].begin, J[(size_t)direct[q]]->compressed + 11,
+                          J[(size_t)direct[q]]->compressed_len - 11, true);
+        return r;
+    }, [&](size_t k, int half, IoReq &down, IoReq *) -> int {
+        Sub &sb = subs[k];
+        const int nb = sb.i1 - sb.i0;
+        std::vector<int32_t> st((size_t)nb); std::vector<uint64_t> sy((size_t)nb, 0);
+        uint64_t redone = 0;
+        int rc = outb[half]->reserve(sb.px * 2 + 64);
+        if (rc == MIC_OK) rc = wv_decode_run(s, (const uint8_t *)in[half]->p, (uint16_t *)outb[half]->p, sb.fr.data(), nb, st.data(), sy.data(), &redone);
+        if (rc != MIC_OK) return rc;
+        count.add(1, redone ? 2 : 1, redone);
+        for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) {
+            mic_hip_wv_dec_job &j = *J[(size_t)i];
+            const size_t q = (size_t)(i - sb.i0);
+            j.status = st[q]; j.symbols_decoded = sy[q];
+            if (j.status == MIC_OK) rc = io_submit(down, s->device, (uint16_t *)outb[half]->p + sb.fr[q].px_off, j.pixels_out, band((size_t)i) * 2, false);
+        }
+        return rc;
+    });
+}
+
 // ============================================================================ MIC2: many volumes per call (mic_mic2_batch.hip)
 // The units of a shard's volumes -- volume order, then frame order -- are cut into sub-batches by their sizes alone
 // (mic2_batch_cuts), and the sub-batches are the PARTS of run_staged: the call runs exactly the chains the planner
@@ -1403,6 +1516,84 @@ int mic_hip_mic2_decompress_batch(mic_hip_mic2_dec_job *jobs, int njobs, mic_hip
     uint64_t done = 0;
     for (const Mic2DecVol &v : V) { v.j->status = v.status; v.j->failed_frame = v.failed; done += v.status == MIC_OK; }
     if (stats) *stats = mic_hip_mic2_batch_stats{ units, count.slabs, done };
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// ---- WaveletV2 (waveletfsecompressu16.go:303-534): frames of any shapes and level counts per call ----------------------------------
+int mic_hip_wavelet_v2_compress_jobs(mic_hip_wv_enc_job *jobs, int njobs, mic_hip_wv_batch_stats *stats) try {
+    if (stats) *stats = mic_hip_wv_batch_stats{ 0, 0, 0, 0 };
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    std::vector<mic_hip_wv_enc_job *> J;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_wv_enc_job &j = jobs[i];
+        j.out_len = 0; j.levels_applied = 0;
+        if (!j.pixels || !j.out) { j.status = MIC_ERR_ARGS; continue; }
+        if ((j.status = wv_check_shape(j.rows, j.cols))) continue;
+        if (j.out_cap < 11) { j.status = MIC_ERR_CAPACITY; continue; }
+        j.levels_applied = wv_levels_applied(j.rows, j.cols, j.levels);
+        j.status = MIC_ERR_DEVICE;                                                                 // (until the job has run: a call that fails as a whole leaves no stale status)
+        J.push_back(&j);
+    }
+    if (J.empty()) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    WvCount count;
+    if ((rc = over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i]->rows * (uint64_t)J[(size_t)i]->cols; },
+                           [&](mic_hip_session *s, int j0, int j1) { return wv_encode_host(s, J, j0, j1, count); }))) return rc;
+    uint64_t done = 0;
+    for (int i = 0; i < njobs; i++) done += jobs[i].status == MIC_OK;
+    if (stats) *stats = mic_hip_wv_batch_stats{ count.subs, count.chains, done, count.redo };
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_wavelet_v2_decompress_jobs(mic_hip_wv_dec_job *jobs, int njobs, mic_hip_wv_batch_stats *stats) try {
+    if (stats) *stats = mic_hip_wv_batch_stats{ 0, 0, 0, 0 };
+    if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    if (njobs == 0) return MIC_OK;
+    std::vector<mic_hip_wv_dec_job *> J;
+    for (int i = 0; i < njobs; i++) {
+        mic_hip_wv_dec_job &j = jobs[i];
+        j.rows = j.cols = j.levels = j.out_rows = j.out_cols = 0; j.symbols_decoded = 0;
+        if (!j.compressed || !j.pixels_out) { j.status = MIC_ERR_ARGS; continue; }
+        int rows = 0, cols = 0, levels = 0;
+        if ((j.status = mic_hip_wavelet_v2_info(j.compressed, j.compressed_len, &rows, &cols, nullptr, &levels))) continue;   // :494-496
+        if (rows <= 0 || cols <= 0 || levels > 8) { j.status = MIC_ERR_CORRUPT; continue; }
+        if ((j.status = wv_check_shape(rows, cols, levels, j.level))) continue;
+        j.rows = rows; j.cols = cols; j.levels = levels;
+        if ((j.status = mic_hip_wavelet_v2_level_info(j.compressed, j.compressed_len, j.level, &j.out_rows, &j.out_cols))) continue;
+        if ((size_t)j.out_rows * (size_t)j.out_cols > j.out_cap_px) { j.status = MIC_ERR_CAPACITY; continue; }
+        if (j.compressed_len < 13 || j.compressed[11] != 0xFF || j.compressed[12] != 0x04 || j.compressed_len - 11 > 0xFFFFFFF0ull) { j.status = MIC_ERR_CORRUPT; continue; }   // FSEDecompressU16FourState only, :503
+        j.status = MIC_ERR_DEVICE;
+        J.push_back(&j);
+    }
+    if (J.empty()) return MIC_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    WvCount count;
+    if ((rc = over_devices((int)J.size(), [&](int i) { return (uint64_t)J[(size_t)i]->rows * (uint64_t)J[(size_t)i]->cols; },
+                           [&](mic_hip_session *s, int j0, int j1) { return wv_decode_host(s, J, j0, j1, count); }))) return rc;
+    uint64_t done = 0;
+    for (int i = 0; i < njobs; i++) done += jobs[i].status == MIC_OK;
+    if (stats) *stats = mic_hip_wv_batch_stats{ count.subs, count.chains, done, count.redo };
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_wavelet_v2_batch_plan(const int32_t *rc, int nframes, size_t budget_bytes, uint32_t *cuts, size_t cap, uint64_t *ncuts) try {
+    if (nframes < 0 || (nframes > 0 && !rc) || (cap > 0 && !cuts)) return MIC_ERR_ARGS;
+    std::vector<size_t> px((size_t)nframes);
+    for (int i = 0; i < nframes; i++) {
+        const int32_t r = rc[2 * (size_t)i], c = rc[2 * (size_t)i + 1];
+        if (r <= 0 || c <= 0) return MIC_ERR_ARGS;
+        px[(size_t)i] = (size_t)r * (size_t)c;
+    }
+    const size_t budget = budget_bytes ? budget_bytes : kWorkspaceBudget;
+    if (!budget_bytes) (void)hipGetLastError();                                             // (the default ceiling asks the device when there is one)
+    std::vector<uint32_t> c{ 0 };
+    while (c.back() < (uint32_t)nframes) c.push_back((uint32_t)wv_next_cut([&](size_t i) { return px[i]; }, c.back(), (size_t)nframes, budget));
+    if (ncuts) *ncuts = c.size();
+    if (c.size() > cap) return MIC_ERR_CAPACITY;
+    std::copy(c.begin(), c.end(), cuts);
     return MIC_OK;
 } MIC_ABI_CATCH
 

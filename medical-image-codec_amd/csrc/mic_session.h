@@ -171,6 +171,8 @@ struct mic_hip_session {
     DevBuf pica_tab, pica_cost, pica_starts;   // PICA: a sub-batch's image table, row costs and strip boundaries (mic_pica.hip)
     PinnedU64 pica_pin[2];                 // ... and the host's copy of table + boundaries, one per staging half
     DevBuf wv_a, wv_b;                     // WaveletV2 coefficient planes (int32, two per frame of the batch)
+    DevBuf wv_tab_enc, wv_tab_dec;         // WaveletV2: a launch chain's frame records and work records (mic_wavelet.hip), encode's and decode's
+    struct WvTabHeld { std::vector<uint8_t> key; std::vector<uint32_t> spans; uint64_t gen = ~0ull; } wv_tab_held[2];   // ... and what each holds: the frame records it was built from, its work lists, the allocation
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
     DevBuf pieces;                         // patch and crop calls: the call's piece list (GatherPiece, mic_pieces.h; MIC2 temporal: its footprints)
@@ -333,13 +335,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -463,6 +465,25 @@ int rgb_next_cut(const std::function<size_t(int)> &npx, int i0, int n, size_t ta
 int rgb_encode_run(mic_hip_session *s, const uint8_t *d_rgb, RgbImage *img, int n, DevBuf &payload, uint64_t pay0, uint64_t *pay_end);
 // the blobs (checked: pl[] filled in, status MIC_OK) -> pixels: fills, ONE unit batch over every mode-2 plane, the inverse transform
 int rgb_decode_run(mic_hip_session *s, const uint8_t *d_blobs, RgbBlob *blobs, int n, uint8_t *d_rgb_out);
+// WaveletV2 batches of frames of any shapes and level counts (mic_wavelet.hip; the host doors: mic_host_io.hip).
+// the argument gate of every entry point: MIC_OK, or why rows x cols (a decode: at `level` of a header's `levels`) is not coded here
+int wv_check_shape(int rows, int cols, int levels = 0, int level = 0);
+// the level count the header carries: `levels` clamped to 1 .. 8, stopped where a side falls below 2 (waveletfsecompressu16.go:321-330)
+int wv_levels_applied(int rows, int cols, int levels);
+void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int applied);     // the 11 bytes of :346-350
+// frames [i0, return) of the next sub-batch of frames [.., n) of px(i) pixels: budget / (unit_ws_bytes(2 mp + 16) + 8 mp) frames of the
+// largest so far (every unit is laid out by it), at most 65535 (the chain's grids) and 2^30 pixels (the position groups of a launch
+// stay below 2^31 whatever the shapes)
+size_t wv_next_cut(const std::function<size_t(size_t)> &px, size_t i0, size_t n, size_t budget);
+// One frame of an encode sub-batch: rows x cols at d_px + px_off, `applied` levels.  The core: ONE launch chain over the n frames; on
+// return the streams (no 11-byte header) of the frames that coded lie packed at *d_blobs + offs[i] .. offs[i + 1] (s->packed).
+struct WvEncFrame { uint64_t px_off; int32_t rows, cols, applied; };
+int wv_encode_run(mic_hip_session *s, const uint16_t *d_px, const WvEncFrame *f, int n, const uint8_t **d_blobs, uint64_t *offs, int32_t *st);
+// One frame of a decode sub-batch: the stream d_comp + begin .. end of a rows x cols frame of `levels`, wanted at `level`; its
+// nr[level] x nc[level] pixels go to d_out + px_off.  The core: one launch chain, and one more over the frames that the prefix rule of a
+// reduced decode sends round again (*redone += their count).  syms (nullable): tANS symbols decoded per frame.
+struct WvDecFrame { uint64_t begin, end, px_off; int32_t rows, cols, levels, level; };
+int wv_decode_run(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_out, const WvDecFrame *f, int n, int32_t *st, uint64_t *syms, uint64_t *redone);
 // Strip files (PICS: parallelstrips.go, PICA: parallelstripsadaptive.go): a header, a table and one unit per strip.  Strip k of a
 // file of height h and n strips as its header states it -- rows [y0, y1), bytes [start, start + len) of the file, the unit's flags --
 // read from the header and the table alone; what the whole-image decoders (mic_host_io.hip) and the crop calls (mic_strip_crops.hip) decode by.

@@ -10,7 +10,12 @@
 // rows and columns over a tile in LDS, de-interleaving on the fly, the smooth plane handed from level to level in a scratch plane).
 // The subband scan is a closed-form index map, so collect + zigzag + escape + max is one pass with a
 // prefix sum for the rare escapes.  RLE / FSE reuse the unit-codec kernels (mode 2 / mode 1 units).
+// Every launch is driven by tables (WvFrame, WvWork below): a launch chain takes frames of any shapes and level counts -- the
+// one-shape entry points are callers with a table of equal rows (mic_hip_wavelet_v2_compress_jobs / _decompress_jobs: mic_host_io.hip).
+// A chain still lays every unit out by its largest frame, in the tier-2 slabs; the cut rule of the
+// host doors (wv_next_cut) bounds what that costs.
 #include "mic_session.h"
+#include "mic_staged.h"
 #include "mic_wave.h"
 
 namespace {
@@ -25,6 +30,28 @@ __host__ __device__ inline WvDims wv_dims(int rows, int cols, int levels) {
     d.nr[0] = rows; d.nc[0] = cols;
     for (int l = 1; l <= 8; l++) { d.nr[l] = (d.nr[l - 1] + 1) / 2; d.nc[l] = (d.nc[l - 1] + 1) / 2; }
     return d;
+}
+
+// ---- table-driven geometry: frames of any shapes and level counts in one launch chain -------------------------------------------------
+// A sub-batch's frames are described by one WvFrame each, uploaded with the unit descriptors (frame f <-> unit f).  Their planes lie
+// back to back, with no padding to the largest frame: the u16 pixels px_off elements behind the launch's pixel pointer (a decode at
+// `level`: the nr[level] x nc[level] band), the int32 coefficient plane (row stride = the frame's own cols) a_off elements into the
+// session's wv_a, the two smooth planes of ll_half elements each b_off elements into wv_b -- the int32 offsets multiples of 4, so
+// that the 16-byte accesses of the scan kernels keep the alignment a frame on its own has.
+// A block finds its frame and tile with ONE load of a WvWork record the host builds per launch ("WaveletV2,
+// mixed frames"): the grid of a launch is the sum of its frames' own tiles, and a frame takes part in a level launch only if it has
+// that level.  The one-group kernels run group f on frame f and need no work records.
+struct WvFrame {
+    WvDims d;                       // rows, cols, the level count applied (the header's)
+    int32_t level;                  // decode: the resolution wanted (0: the full image)
+    uint32_t lim;                   // the scan positions wanted: nr[level] * nc[level] (rows * cols at level 0)
+    uint32_t ll_half, pad[2];       // elements of one smooth plane: nr[1] * nc[1] rounded up to 4 (pad: no hole, the host compares records bytewise)
+    uint64_t px_off, a_off, b_off;
+};
+struct WvWork { uint32_t frame, bx, by, pad; };
+__device__ __forceinline__ WvWork wv_work(const WvWork *__restrict__ wk) {
+    const uint4 v = *(const uint4 *)(wk + blockIdx.x);
+    return WvWork{ v.x, v.y, v.z, v.w };
 }
 
 // ---- lifting, one output sample at a time (waveletu16.go:26-122) ---------------------------------
@@ -90,68 +117,77 @@ template <int CTRL> __device__ __forceinline__ int32_t wv_shift(int32_t v) {    
 typedef uint32_t wv_u32u __attribute__((aligned(2)));
 typedef unsigned long long wv_u64u __attribute__((aligned(4)));
 
+// Level l of the frames a launch's work records name: src16 = the launch's pixels (level 0), A / B = the session's planes.
 template <bool FROM_U16>
-__global__ void __launch_bounds__(256) k_wv_fwd2d(const void *__restrict__ src_, int sstride, size_t sfs, int32_t *__restrict__ a, int stride, size_t fs,
-                                                  int32_t *__restrict__ ll, int llstride, size_t llfs, int r, int c, int nf) {
+__global__ void __launch_bounds__(256) k_wv_fwd2d(const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const uint16_t *__restrict__ src16,
+                                                  int32_t *__restrict__ A, int32_t *__restrict__ B, int l) {
+    const WvWork wr = wv_work(wk);
+    const WvFrame &fr = ft[wr.frame];
+    const int r = fr.d.nr[l], c = fr.d.nc[l];
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int nlc = (c + 1) / 2, nlr = (r + 1) / 2;
-    const int gi = ((int)blockIdx.x * 4 + wave) * WS_LANES - 1 + lane;          // this lane's pair (lanes 0 and 63: context only)
-    const int gp0 = (int)blockIdx.y * WS_ROWS, gp1 = min(gp0 + WS_ROWS, nlr);
-    if (((int)blockIdx.x * 4 + wave) * WS_LANES >= nlc) return;
+    const int gi = ((int)wr.bx * 4 + wave) * WS_LANES - 1 + lane;               // this lane's pair (lanes 0 and 63: context only)
+    const int gp0 = (int)wr.by * WS_ROWS, gp1 = min(gp0 + WS_ROWS, nlr);
+    if (((int)wr.bx * 4 + wave) * WS_LANES >= nlc) return;
+    // level l reads the pixels (l = 0) or the smooth plane of parity l - 1; its own smooth plane has parity l, the last level's goes to `a`
+    const bool last = l == fr.d.levels - 1;
+    int32_t *const a = A + fr.a_off, *const bf = B + fr.b_off;
+    const int stride = fr.d.cols, sstride = c;
+    const void *const src_ = FROM_U16 ? (const void *)(src16 + fr.px_off) : (const void *)(bf + (((l - 1) & 1) ? fr.ll_half : 0u));
+    int32_t *const ll = last ? a : bf + ((l & 1) ? fr.ll_half : 0u);
+    const int llstride = last ? stride : nlc;
     const bool has0 = gi >= 0 && 2 * gi < c, has1 = gi >= 0 && 2 * gi + 1 < c, hasr = 2 * gi + 2 < c, left = gi > 0;
     const bool out_lo = lane >= 1 && lane <= WS_LANES && has0, out_hi = lane >= 1 && lane <= WS_LANES && has1;
-    for (int f = (int)blockIdx.z; f < nf; f += (int)gridDim.z) {
-        // input row y: this lane's two samples ...
-        auto fetch = [&](int y, int32_t &x0, int32_t &x1) {
-            x0 = 0; x1 = 0;
-            const size_t o = (size_t)f * sfs + (size_t)y * sstride + (size_t)(2 * gi);
-            if (FROM_U16) {
-                const uint16_t *p = (const uint16_t *)src_ + o;
-                if (has1) { const uint32_t w = *(const wv_u32u *)p; x0 = (int32_t)(w & 0xFFFFu); x1 = (int32_t)(w >> 16); }
-                else if (has0) x0 = (int32_t)p[0];
-            } else {
-                const int32_t *p = (const int32_t *)src_ + o;
-                if (has1) { const unsigned long long w = *(const wv_u64u *)p; x0 = (int32_t)(uint32_t)w; x1 = (int32_t)(uint32_t)(w >> 32); }
-                else if (has0) x0 = p[0];
-            }
-        };
-        // ... and its rows pass (waveletu16.go:26-74, :170-182): smooth and detail of the pair
-        auto lift = [&](int32_t x0, int32_t x1, int32_t &lo, int32_t &hi) {
-            const int32_t xn = wv_shift<0x130>(x0), xr = hasr ? xn : x0;       // symmetric extension on the right
-            const int32_t d = x1 - ((x0 + xr) >> 1);
-            const int32_t dp = wv_shift<0x138>(d);
-            const int32_t dr = has1 ? d : (left ? dp : 0), dl = left ? dp : dr;
-            lo = x0 + ((dl + dr + 2) >> 2); hi = d;
-        };
-        auto row = [&](int y, int32_t &lo, int32_t &hi) { int32_t x0, x1; fetch(y, x0, x1); lift(x0, x1, lo, hi); };
-        // the columns pass (:183-208) down the strip: rows 2 gp, 2 gp + 1 in (l0, h0), (l1, h1); row 2 gp + 2 in (ln, hn)
-        int32_t l0, h0, l1 = 0, h1 = 0, ln = 0, hn = 0, dlo = 0, dhi = 0;       // dlo, dhi: the details of pair-row gp - 1
-        if (gp0 > 0) {
-            int32_t pl0, ph0, pl1, ph1;
-            row(2 * gp0 - 2, pl0, ph0); row(2 * gp0 - 1, pl1, ph1); row(2 * gp0, l0, h0);
-            dlo = pl1 - ((pl0 + l0) >> 1); dhi = ph1 - ((ph0 + h0) >> 1);
-        } else row(0, l0, h0);
-        if (2 * gp0 + 1 < r) row(2 * gp0 + 1, l1, h1);
-        for (int gp = gp0; gp < gp1; gp++) {
-            const bool odd = 2 * gp + 1 < r, more = 2 * gp + 2 < r, more1 = 2 * gp + 3 < r;
-            int32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;                              // (both rows of the next pair are fetched before either is used)
-            if (more) fetch(2 * gp + 2, a0, a1);
-            if (more1) fetch(2 * gp + 3, b0, b1);
-            if (more) lift(a0, a1, ln, hn);
-            const int32_t rl = more ? ln : l0, rh = more ? hn : h0;
-            const int32_t d_l = l1 - ((l0 + rl) >> 1), d_h = h1 - ((h0 + rh) >> 1);
-            const int32_t drl = odd ? d_l : (gp > 0 ? dlo : 0), drh = odd ? d_h : (gp > 0 ? dhi : 0);
-            const int32_t dll = gp > 0 ? dlo : drl, dlh = gp > 0 ? dhi : drh;
-            const int32_t s_l = l0 + ((dll + drl + 2) >> 2), s_h = h0 + ((dlh + drh + 2) >> 2);
-            if (out_lo) ll[(size_t)f * llfs + (size_t)gp * llstride + gi] = s_l;
-            if (out_hi) a[(size_t)f * fs + (size_t)gp * stride + nlc + gi] = s_h;
-            if (odd) {
-                if (out_lo) a[(size_t)f * fs + (size_t)(nlr + gp) * stride + gi] = d_l;
-                if (out_hi) a[(size_t)f * fs + (size_t)(nlr + gp) * stride + nlc + gi] = d_h;
-            }
-            dlo = d_l; dhi = d_h; l0 = ln; h0 = hn;
-            if (more1) lift(b0, b1, l1, h1);
+    // input row y: this lane's two samples ...
+    auto fetch = [&](int y, int32_t &x0, int32_t &x1) {
+        x0 = 0; x1 = 0;
+        const size_t o = (size_t)y * sstride + (size_t)(2 * gi);
+        if (FROM_U16) {
+            const uint16_t *p = (const uint16_t *)src_ + o;
+            if (has1) { const uint32_t w = *(const wv_u32u *)p; x0 = (int32_t)(w & 0xFFFFu); x1 = (int32_t)(w >> 16); }
+            else if (has0) x0 = (int32_t)p[0];
+        } else {
+            const int32_t *p = (const int32_t *)src_ + o;
+            if (has1) { const unsigned long long w = *(const wv_u64u *)p; x0 = (int32_t)(uint32_t)w; x1 = (int32_t)(uint32_t)(w >> 32); }
+            else if (has0) x0 = p[0];
         }
+    };
+    // ... and its rows pass (waveletu16.go:26-74, :170-182): smooth and detail of the pair
+    auto lift = [&](int32_t x0, int32_t x1, int32_t &lo, int32_t &hi) {
+        const int32_t xn = wv_shift<0x130>(x0), xr = hasr ? xn : x0;       // symmetric extension on the right
+        const int32_t d = x1 - ((x0 + xr) >> 1);
+        const int32_t dp = wv_shift<0x138>(d);
+        const int32_t dr = has1 ? d : (left ? dp : 0), dl = left ? dp : dr;
+        lo = x0 + ((dl + dr + 2) >> 2); hi = d;
+    };
+    auto row = [&](int y, int32_t &lo, int32_t &hi) { int32_t x0, x1; fetch(y, x0, x1); lift(x0, x1, lo, hi); };
+    // the columns pass (:183-208) down the strip: rows 2 gp, 2 gp + 1 in (l0, h0), (l1, h1); row 2 gp + 2 in (ln, hn)
+    int32_t l0, h0, l1 = 0, h1 = 0, ln = 0, hn = 0, dlo = 0, dhi = 0;       // dlo, dhi: the details of pair-row gp - 1
+    if (gp0 > 0) {
+        int32_t pl0, ph0, pl1, ph1;
+        row(2 * gp0 - 2, pl0, ph0); row(2 * gp0 - 1, pl1, ph1); row(2 * gp0, l0, h0);
+        dlo = pl1 - ((pl0 + l0) >> 1); dhi = ph1 - ((ph0 + h0) >> 1);
+    } else row(0, l0, h0);
+    if (2 * gp0 + 1 < r) row(2 * gp0 + 1, l1, h1);
+    for (int gp = gp0; gp < gp1; gp++) {
+        const bool odd = 2 * gp + 1 < r, more = 2 * gp + 2 < r, more1 = 2 * gp + 3 < r;
+        int32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;                              // (both rows of the next pair are fetched before either is used)
+        if (more) fetch(2 * gp + 2, a0, a1);
+        if (more1) fetch(2 * gp + 3, b0, b1);
+        if (more) lift(a0, a1, ln, hn);
+        const int32_t rl = more ? ln : l0, rh = more ? hn : h0;
+        const int32_t d_l = l1 - ((l0 + rl) >> 1), d_h = h1 - ((h0 + rh) >> 1);
+        const int32_t drl = odd ? d_l : (gp > 0 ? dlo : 0), drh = odd ? d_h : (gp > 0 ? dhi : 0);
+        const int32_t dll = gp > 0 ? dlo : drl, dlh = gp > 0 ? dhi : drh;
+        const int32_t s_l = l0 + ((dll + drl + 2) >> 2), s_h = h0 + ((dlh + drh + 2) >> 2);
+        if (out_lo) ll[(size_t)gp * llstride + gi] = s_l;
+        if (out_hi) a[(size_t)gp * stride + nlc + gi] = s_h;
+        if (odd) {
+            if (out_lo) a[(size_t)(nlr + gp) * stride + gi] = d_l;
+            if (out_hi) a[(size_t)(nlr + gp) * stride + nlc + gi] = d_h;
+        }
+        dlo = d_l; dhi = d_h; l0 = ln; h0 = hn;
+        if (more1) lift(b0, b1, l1, h1);
     }
 }
 // The inverse of one level (columns, then rows: waveletu16.go:213-257): the smooth subband from `ll` (the level below wrote it; the
@@ -160,83 +196,102 @@ __global__ void __launch_bounds__(256) k_wv_fwd2d(const void *__restrict__ src_,
 // SAT (with TO_U16): the samples are saturated to [0, 65535] -- the last level of a reduced-resolution decode, whose LL band may
 // over- or undershoot the pixel range at edges; the full decode's store keeps the reference's plain truncation.
 template <bool TO_U16, bool SAT = false>
-__global__ void __launch_bounds__(256) k_wv_inv2d(const int32_t *__restrict__ a, int stride, size_t fs, const int32_t *__restrict__ ll, int llstride, size_t llfs,
-                                                  void *__restrict__ dst_, int dstride, size_t dfs, int r, int c, int nf) {
+__global__ void __launch_bounds__(256) k_wv_inv2d(const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const int32_t *__restrict__ A, int32_t *__restrict__ B,
+                                                  uint16_t *__restrict__ dst16, int l) {
+    const WvWork wr = wv_work(wk);
+    const WvFrame &fr = ft[wr.frame];
+    const int r = fr.d.nr[l], c = fr.d.nc[l];
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int nlc = (c + 1) / 2, nlr = (r + 1) / 2;
-    const int gi = ((int)blockIdx.x * 4 + wave) * WS_LANES - 1 + lane;
-    const int gp0 = (int)blockIdx.y * WS_ROWS, gp1 = min(gp0 + WS_ROWS, nlr);
-    if (((int)blockIdx.x * 4 + wave) * WS_LANES >= nlc) return;
+    const int gi = ((int)wr.bx * 4 + wave) * WS_LANES - 1 + lane;
+    const int gp0 = (int)wr.by * WS_ROWS, gp1 = min(gp0 + WS_ROWS, nlr);
+    if (((int)wr.bx * 4 + wave) * WS_LANES >= nlc) return;
+    // level l reads the smooth plane of parity l + 1 (the coarsest level's lies in `a`) and restores into the plane of parity l --
+    // or into the pixels: level 0, or level `level` of a reduced decode (SAT); either way a compact plane of this level's width
+    const bool coarsest = l == fr.d.levels - 1;
+    const int stride = fr.d.cols;
+    const int32_t *const af = A + fr.a_off;
+    const int32_t *const lf = coarsest ? af : B + fr.b_off + (((l + 1) & 1) ? fr.ll_half : 0u);
+    const int llstride = coarsest ? stride : nlc;
+    void *const dst_ = TO_U16 ? (void *)(dst16 + fr.px_off) : (void *)(B + fr.b_off + ((l & 1) ? fr.ll_half : 0u));
+    const int dstride = c;
     const bool has0 = gi >= 0 && 2 * gi < c, has1 = gi >= 0 && 2 * gi + 1 < c, hasr = 2 * gi + 2 < c, left = gi > 0;
     const bool out0 = lane >= 1 && lane <= WS_LANES && has0;
-    for (int f = (int)blockIdx.z; f < nf; f += (int)gridDim.z) {
-        const int32_t *af = a + (size_t)f * fs, *lf = ll + (size_t)f * llfs;
-        // Mallat row j of this lane's two columns: smooth rows j < nlr, detail rows nlr + j
-        auto smooth = [&](int j, int32_t &vs, int32_t &vd) {
-            vs = has0 ? lf[(size_t)j * llstride + gi] : 0;
-            vd = has1 ? af[(size_t)j * stride + nlc + gi] : 0;
-        };
-        auto detail = [&](int j, int32_t &vs, int32_t &vd) {
-            vs = has0 ? af[(size_t)(nlr + j) * stride + gi] : 0;
-            vd = has1 ? af[(size_t)(nlr + j) * stride + nlc + gi] : 0;
-        };
-        // even sample j of a column from its smooth value and the details on either side (wv_even's rules)
-        auto even = [&](int j, int32_t cs, int32_t dm, int32_t d0) -> int32_t {
-            const int32_t dr = (2 * j + 1 < r) ? d0 : (j > 0 ? dm : 0), dl = j > 0 ? dm : dr;
-            return cs - ((dl + dr + 2) >> 2);
-        };
-        // one restored row of the columns pass through the rows pass, to `dst`
-        auto put = [&](int y, int32_t vs, int32_t vd) {
-            const int32_t dp = wv_shift<0x138>(vd);
-            const int32_t dr = has1 ? vd : (left ? dp : 0), dl = left ? dp : dr;
-            const int32_t ev = vs - ((dl + dr + 2) >> 2);
-            const int32_t en = wv_shift<0x130>(ev);
-            const int32_t od = vd + ((ev + (hasr ? en : ev)) >> 1);
-            if (!out0) return;
-            const size_t o = (size_t)f * dfs + (size_t)y * dstride + (size_t)(2 * gi);
-            if (TO_U16) {
-                uint16_t *d = (uint16_t *)dst_ + o;
-                const int32_t e16 = SAT ? min(max(ev, 0), 65535) : ev, o16 = SAT ? min(max(od, 0), 65535) : od;
-                if (SAT) { if (has1) *(wv_u32u *)d = (uint32_t)e16 | ((uint32_t)o16 << 16); else d[0] = (uint16_t)e16; }
-                else if (has1) *(wv_u32u *)d = ((uint32_t)ev & 0xFFFFu) | ((uint32_t)od << 16); else d[0] = (uint16_t)ev;
-            } else {
-                int32_t *d = (int32_t *)dst_ + o;
-                if (has1) *(wv_u64u *)d = (uint32_t)ev | ((unsigned long long)(uint32_t)od << 32); else d[0] = ev;
-            }
-        };
-        // the columns pass down the strip: (es, ed) = even sample gp of the two columns, (ds, dd) = their details gp
-        int32_t ss, sd, ds = 0, dd = 0, pms = 0, pmd = 0;
-        if (gp0 > 0) detail(gp0 - 1, pms, pmd);
-        smooth(gp0, ss, sd);
-        if (2 * gp0 + 1 < r) detail(gp0, ds, dd);
-        int32_t es = even(gp0, ss, pms, ds), ed = even(gp0, sd, pmd, dd);
-        for (int gp = gp0; gp < gp1; gp++) {
-            const bool odd = 2 * gp + 1 < r, more = 2 * gp + 2 < r;
-            int32_t ns = 0, nd = 0, nds = 0, ndd = 0, es1 = es, ed1 = ed;
-            if (more) {
-                smooth(gp + 1, ns, nd);
-                if (2 * gp + 3 < r) detail(gp + 1, nds, ndd);
-                es1 = even(gp + 1, ns, ds, nds); ed1 = even(gp + 1, nd, dd, ndd);
-            }
-            put(2 * gp, es, ed);
-            if (odd) put(2 * gp + 1, ds + ((es + es1) >> 1), dd + ((ed + ed1) >> 1));
-            es = es1; ed = ed1; ds = nds; dd = ndd;
+    // Mallat row j of this lane's two columns: smooth rows j < nlr, detail rows nlr + j
+    auto smooth = [&](int j, int32_t &vs, int32_t &vd) {
+        vs = has0 ? lf[(size_t)j * llstride + gi] : 0;
+        vd = has1 ? af[(size_t)j * stride + nlc + gi] : 0;
+    };
+    auto detail = [&](int j, int32_t &vs, int32_t &vd) {
+        vs = has0 ? af[(size_t)(nlr + j) * stride + gi] : 0;
+        vd = has1 ? af[(size_t)(nlr + j) * stride + nlc + gi] : 0;
+    };
+    // even sample j of a column from its smooth value and the details on either side (wv_even's rules)
+    auto even = [&](int j, int32_t cs, int32_t dm, int32_t d0) -> int32_t {
+        const int32_t dr = (2 * j + 1 < r) ? d0 : (j > 0 ? dm : 0), dl = j > 0 ? dm : dr;
+        return cs - ((dl + dr + 2) >> 2);
+    };
+    // one restored row of the columns pass through the rows pass, to `dst`
+    auto put = [&](int y, int32_t vs, int32_t vd) {
+        const int32_t dp = wv_shift<0x138>(vd);
+        const int32_t dr = has1 ? vd : (left ? dp : 0), dl = left ? dp : dr;
+        const int32_t ev = vs - ((dl + dr + 2) >> 2);
+        const int32_t en = wv_shift<0x130>(ev);
+        const int32_t od = vd + ((ev + (hasr ? en : ev)) >> 1);
+        if (!out0) return;
+        const size_t o = (size_t)y * dstride + (size_t)(2 * gi);
+        if (TO_U16) {
+            uint16_t *d = (uint16_t *)dst_ + o;
+            const int32_t e16 = SAT ? min(max(ev, 0), 65535) : ev, o16 = SAT ? min(max(od, 0), 65535) : od;
+            if (SAT) { if (has1) *(wv_u32u *)d = (uint32_t)e16 | ((uint32_t)o16 << 16); else d[0] = (uint16_t)e16; }
+            else if (has1) *(wv_u32u *)d = ((uint32_t)ev & 0xFFFFu) | ((uint32_t)od << 16); else d[0] = (uint16_t)ev;
+        } else {
+            int32_t *d = (int32_t *)dst_ + o;
+            if (has1) *(wv_u64u *)d = (uint32_t)ev | ((unsigned long long)(uint32_t)od << 32); else d[0] = ev;
         }
+    };
+    // the columns pass down the strip: (es, ed) = even sample gp of the two columns, (ds, dd) = their details gp
+    int32_t ss, sd, ds = 0, dd = 0, pms = 0, pmd = 0;
+    if (gp0 > 0) detail(gp0 - 1, pms, pmd);
+    smooth(gp0, ss, sd);
+    if (2 * gp0 + 1 < r) detail(gp0, ds, dd);
+    int32_t es = even(gp0, ss, pms, ds), ed = even(gp0, sd, pmd, dd);
+    for (int gp = gp0; gp < gp1; gp++) {
+        const bool odd = 2 * gp + 1 < r, more = 2 * gp + 2 < r;
+        int32_t ns = 0, nd = 0, nds = 0, ndd = 0, es1 = es, ed1 = ed;
+        if (more) {
+            smooth(gp + 1, ns, nd);
+            if (2 * gp + 3 < r) detail(gp + 1, nds, ndd);
+            es1 = even(gp + 1, ns, ds, nds); ed1 = even(gp + 1, nd, dd, ndd);
+        }
+        put(2 * gp, es, ed);
+        if (odd) put(2 * gp + 1, ds + ((es + es1) >> 1), dd + ((ed + ed1) >> 1));
+        es = es1; ed = ed1; ds = nds; dd = ndd;
     }
 }
-__global__ void __launch_bounds__(256) k_wv_load(const uint16_t *px, int32_t *a, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = (int32_t)px[i];
+// The frames without a level (a side below 2: applied == 0) and the coarsest LL band of a reduced decode at level == levels, which
+// runs no inverse level at all: a work record is WV_CHUNK consecutive elements of its frame (bx: which).
+#define WV_CHUNK 4096u
+__global__ void __launch_bounds__(256) k_wv_load(const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const uint16_t *__restrict__ px, int32_t *__restrict__ A) {
+    const WvWork wr = wv_work(wk);
+    const WvFrame &fr = ft[wr.frame];
+    const uint32_t n = (uint32_t)fr.d.rows * (uint32_t)fr.d.cols, i1 = min(n, (wr.bx + 1) * WV_CHUNK);
+    for (uint32_t i = wr.bx * WV_CHUNK + threadIdx.x; i < i1; i += 256) A[fr.a_off + i] = (int32_t)px[fr.px_off + i];
 }
-__global__ void __launch_bounds__(256) k_wv_store(const int32_t *a, uint16_t *px, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) px[i] = (uint16_t)a[i];
+__global__ void __launch_bounds__(256) k_wv_store(const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const int32_t *__restrict__ A, uint16_t *__restrict__ px) {
+    const WvWork wr = wv_work(wk);
+    const WvFrame &fr = ft[wr.frame];
+    const uint32_t n = (uint32_t)fr.d.rows * (uint32_t)fr.d.cols, i1 = min(n, (wr.bx + 1) * WV_CHUNK);
+    for (uint32_t i = wr.bx * WV_CHUNK + threadIdx.x; i < i1; i += 256) px[fr.px_off + i] = (uint16_t)A[fr.a_off + i];
 }
-// the coarsest LL band (nr x nc, at the top left of each frame's coefficient plane of stride `cols`, frame stride fs) saturated to u16,
-// row stride nc: a decode at reduced resolution r = levels, which runs no inverse level at all
-__global__ void __launch_bounds__(256) k_wv_band(const int32_t *a, int cols, size_t fs, uint16_t *px, int nr, int nc, int nf) {
-    const size_t band = (size_t)nr * (size_t)nc, n = band * (size_t)nf;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t f = i / band, k = i - f * band, y = k / (size_t)nc, x = k - y * (size_t)nc;
-        px[i] = (uint16_t)min(max(a[f * fs + y * (size_t)cols + x], 0), 65535);
+// the band (nr x nc at the top left of the frame's coefficient plane, row stride cols) saturated to u16, row stride nc
+__global__ void __launch_bounds__(256) k_wv_band(const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const int32_t *__restrict__ A, uint16_t *__restrict__ px) {
+    const WvWork wr = wv_work(wk);
+    const WvFrame &fr = ft[wr.frame];
+    const uint32_t nc = (uint32_t)fr.d.nc[fr.level], cols = (uint32_t)fr.d.cols, i1 = min(fr.lim, (wr.bx + 1) * WV_CHUNK);
+    for (uint32_t i = wr.bx * WV_CHUNK + threadIdx.x; i < i1; i += 256) {
+        const uint32_t y = i / nc, x = i - y * nc;
+        px[fr.px_off + i] = (uint16_t)min(max(A[fr.a_off + (size_t)y * cols + x], 0), 65535);
     }
 }
 
@@ -265,10 +320,11 @@ __device__ __forceinline__ size_t wv_pos_to_index(const WvDims &d, size_t p) {
 
 // subband scan + waveletCoeffsToU16 (:28-40) + zzMax (:335-349).  One work-group per image; writes the
 // symbol stream into u.sym, its length into u.nsym and the RLE maxValue into u.max_value.
-__global__ void __launch_bounds__(WV_THREADS) k_wv_symbols(MicUnit *units, const int32_t *a, WvDims d) {
+__global__ void __launch_bounds__(WV_THREADS) k_wv_symbols(MicUnit *units, const WvFrame *__restrict__ ft, const int32_t *a) {
     MicUnit &u = units[blockIdx.x];
     if (!u.wv_slow) return;                                               // k_wv_symbols_par did this frame
-    a += (size_t)blockIdx.x * (size_t)d.rows * (size_t)d.cols;             // one group per frame of the batch
+    const WvDims &d = ft[blockIdx.x].d;
+    a += ft[blockIdx.x].a_off;                                            // one group per frame of the batch
     __shared__ uint32_t s_scan[WV_WAVES], s_max[WV_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t n = (size_t)d.rows * d.cols;
@@ -380,10 +436,12 @@ __device__ __forceinline__ uint32_t wv_fn_compose(uint32_t g, uint32_t f) {     
     const uint32_t f0 = f & 3, f1 = (f >> 2) & 3, f2 = (f >> 4) & 3;
     return ((g >> (2 * f0)) & 3) | (((g >> (2 * f1)) & 3) << 2) | (((g >> (2 * f2)) & 3) << 4);
 }
-// lim: the coefficients wanted -- n, or P(r) of a decode at reduced resolution (the first P(r) of the subband scan); fewer is an error
-__global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, int32_t *a, WvDims d, uint32_t lim) {
+// lim (the frame's): the coefficients wanted -- n, or P(r) of a decode at reduced resolution (the first P(r) of the subband scan); fewer is an error
+__global__ void __launch_bounds__(WV_THREADS) k_wv_coeffs(MicUnit *units, const WvFrame *__restrict__ ft, int32_t *a) {
     MicUnit &u = units[blockIdx.x];
-    a += (size_t)blockIdx.x * (size_t)d.rows * (size_t)d.cols;
+    const WvDims &d = ft[blockIdx.x].d;
+    const uint32_t lim = ft[blockIdx.x].lim;
+    a += ft[blockIdx.x].a_off;
     if (u.status != MICD_OK || !u.wv_slow) return;
     __shared__ uint32_t s_scan[WV_WAVES], s_fn[WV_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -454,52 +512,52 @@ __device__ __forceinline__ void wv_pos_row(const WvDims &d, uint32_t p, uint32_t
 typedef uint32_t wv_v4 __attribute__((ext_vector_type(4)));
 typedef wv_v4 WvQ2 __attribute__((aligned(2)));
 typedef wv_v4 WvQ4 __attribute__((aligned(4)));
-// subband scan + zigzag, WS_T positions per group (grid: x = position tiles, y = frames).  A coefficient outside 16 bits sends the
+// subband scan + zigzag, WS_T positions per group (a work record: frame, bx = position tile).  A coefficient outside 16 bits sends the
 // frame to k_wv_symbols (wv_slow); the frame's largest symbol is gathered with an atomic max.
-__global__ void __launch_bounds__(1024) k_wv_symbols_par(MicUnit *units, const int32_t *a, WvDims d, int nf) {
+__global__ void __launch_bounds__(1024) k_wv_symbols_par(MicUnit *units, const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, const int32_t *a) {
+    const WvWork wr = wv_work(wk);
+    const WvDims &d = ft[wr.frame].d;
     const uint32_t n = (uint32_t)d.rows * (uint32_t)d.cols, tid = threadIdx.x, lane = tid & 63;
-    const uint32_t i0 = blockIdx.x * WS_T + tid * 8;
-    for (int f = (int)blockIdx.y; f < nf; f += (int)gridDim.y) {
-        MicUnit &u = units[f];
-        const int32_t *af = a + (size_t)f * n;
-        uint32_t w8[4] = { 0u, 0u, 0u, 0u }, zmax = 0, idx = 0, left = 0; bool wide = false;
-        int32_t v8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        if (i0 < n) wv_pos_row(d, i0, idx, left);
-        if (i0 + 8 <= n && left >= 8) {                                    // the usual case: eight positions inside one subband row
-            const wv_v4 lo = *(const WvQ4 *)(af + idx), hi = *(const WvQ4 *)(af + idx + 4);
-            v8[0] = (int32_t)lo.x; v8[1] = (int32_t)lo.y; v8[2] = (int32_t)lo.z; v8[3] = (int32_t)lo.w;
-            v8[4] = (int32_t)hi.x; v8[5] = (int32_t)hi.y; v8[6] = (int32_t)hi.z; v8[7] = (int32_t)hi.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const uint32_t p = i0 + (uint32_t)k;
-                if (p < n) {
-                    if (left == 0) wv_pos_row(d, p, idx, left);
-                    v8[k] = af[idx]; idx++; left--;
-                }
-            }
-        }
+    const uint32_t i0 = wr.bx * WS_T + tid * 8;
+    MicUnit &u = units[wr.frame];
+    const int32_t *af = a + ft[wr.frame].a_off;
+    uint32_t w8[4] = { 0u, 0u, 0u, 0u }, zmax = 0, idx = 0, left = 0; bool wide = false;
+    int32_t v8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (i0 < n) wv_pos_row(d, i0, idx, left);
+    if (i0 + 8 <= n && left >= 8) {                                    // the usual case: eight positions inside one subband row
+        const wv_v4 lo = *(const WvQ4 *)(af + idx), hi = *(const WvQ4 *)(af + idx + 4);
+        v8[0] = (int32_t)lo.x; v8[1] = (int32_t)lo.y; v8[2] = (int32_t)lo.z; v8[3] = (int32_t)lo.w;
+        v8[4] = (int32_t)hi.x; v8[5] = (int32_t)hi.y; v8[6] = (int32_t)hi.z; v8[7] = (int32_t)hi.w;
+    } else {
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const int32_t v = v8[k];
-            if (v < -32767 || v > 32767) wide = true;
-            const uint32_t z = (uint32_t)((v >> 31) ^ (int32_t)((uint32_t)v << 1)) & 0xFFFF;   // zigzagEncode16, :538-541
-            zmax = max(zmax, z);
-            w8[k >> 1] |= z << (16 * (k & 1));
+            const uint32_t p = i0 + (uint32_t)k;
+            if (p < n) {
+                if (left == 0) wv_pos_row(d, p, idx, left);
+                v8[k] = af[idx]; idx++; left--;
+            }
         }
-        uint16_t *sym = u.sym;
-        if (i0 + 8 <= n) { wv_v4 v; v.x = w8[0]; v.y = w8[1]; v.z = w8[2]; v.w = w8[3]; *(wv_v4 *)(sym + i0) = v; }   // (256-byte aligned slab, i0 a multiple of 8)
-        else for (int k = 0; k < 8; k++) if (i0 + (uint32_t)k < n) sym[i0 + k] = (uint16_t)(w8[k >> 1] >> (16 * (k & 1)));
-        zmax = mic_wave_reduce_max(zmax);
-        // (one address per frame: an atomic per wave was 59 k atomics in a row on it.  The maximum only grows, so a wave whose own is
-        // not above what the frame has already -- nearly every wave after the first few -- has nothing to say; a stale read only costs
-        // an atomic that changes nothing)
-        if (lane == 0 && zmax > __hip_atomic_load(&u.wv_zmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&u.wv_zmax, zmax);
-        if (wide) u.wv_slow = 1;
     }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int32_t v = v8[k];
+        if (v < -32767 || v > 32767) wide = true;
+        const uint32_t z = (uint32_t)((v >> 31) ^ (int32_t)((uint32_t)v << 1)) & 0xFFFF;   // zigzagEncode16, :538-541
+        zmax = max(zmax, z);
+        w8[k >> 1] |= z << (16 * (k & 1));
+    }
+    uint16_t *sym = u.sym;
+    if (i0 + 8 <= n) { wv_v4 v; v.x = w8[0]; v.y = w8[1]; v.z = w8[2]; v.w = w8[3]; *(wv_v4 *)(sym + i0) = v; }   // (256-byte aligned slab, i0 a multiple of 8)
+    else for (int k = 0; k < 8; k++) if (i0 + (uint32_t)k < n) sym[i0 + k] = (uint16_t)(w8[k >> 1] >> (16 * (k & 1)));
+    zmax = mic_wave_reduce_max(zmax);
+    // (one address per frame: an atomic per wave was 59 k atomics in a row on it.  The maximum only grows, so a wave whose own is
+    // not above what the frame has already -- nearly every wave after the first few -- has nothing to say; a stale read only costs
+    // an atomic that changes nothing)
+    if (lane == 0 && zmax > __hip_atomic_load(&u.wv_zmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&u.wv_zmax, zmax);
+    if (wide) u.wv_slow = 1;
 }
 // zzMax (:335-349) of the frames k_wv_symbols_par finished
-__global__ void __launch_bounds__(256) k_wv_symbols_fin(MicUnit *units, WvDims d, int nf) {
+__global__ void __launch_bounds__(256) k_wv_symbols_fin(MicUnit *units, const WvFrame *__restrict__ ft, int nf) {
     const int f = (int)(blockIdx.x * 256 + threadIdx.x);
     if (f >= nf) return;
     MicUnit &u = units[f];
@@ -508,7 +566,7 @@ __global__ void __launch_bounds__(256) k_wv_symbols_fin(MicUnit *units, WvDims d
     int depth = m ? 32 - __clz(m) : 0;
     if (depth < 1) depth = 1;
     u.max_value = (uint16_t)((1u << depth) - 1);
-    u.nsym = (uint32_t)d.rows * (uint32_t)d.cols;
+    u.nsym = (uint32_t)ft[f].d.rows * (uint32_t)ft[f].d.cols;
     u.status = (u.nsym <= u.sym_cap) ? MICD_OK : MICD_ERR_CAPACITY;
 }
 
@@ -695,22 +753,24 @@ __global__ void __launch_bounds__(256) k_rle_walk_compact(MicUnit *units) {
 // segment that holds every WS_T-th symbol) say where a position's symbol lies in the token stream (the fetch is
 // k_dec_pixels_wg's: segment table in LDS, gallop + bisection, one 16-byte load inside a literal chunk).  A frame with an escape
 // word (65535) in its symbols, fewer symbols than samples, or a stream the walker refused goes to k_wv_expand + k_wv_coeffs.
-// lim: the scan positions wanted -- n, or P(r) of a decode at reduced resolution (a prefix unit covering fewer goes the slow way)
-__global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, int32_t *a, WvDims d, uint32_t lim) {
-    MicUnit &u = units[blockIdx.y];
+// lim (the frame's): the scan positions wanted -- n, or P(r) of a decode at reduced resolution (a prefix unit covering fewer goes the slow way)
+__global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, const WvFrame *__restrict__ ft, const WvWork *__restrict__ wk, int32_t *a) {
+    const WvWork wr = wv_work(wk);
+    MicUnit &u = units[wr.frame];
     if (u.status != MICD_OK) return;
-    const uint32_t n = (uint32_t)d.rows * (uint32_t)d.cols, tid = threadIdx.x;
+    const WvDims &d = ft[wr.frame].d;
+    const uint32_t lim = ft[wr.frame].lim, tid = threadIdx.x;
     if (u.walk_ok != 1 || u.nsym < lim) { if (tid == 0) u.wv_slow = 1; return; }
     __shared__ uint32_t s_segx[1024], s_segy[1024 + 1];
-    a += (size_t)blockIdx.y * n;
+    a += ft[wr.frame].a_off;
     const uint32_t nseg = u.nseg, ntok = u.ntok;
     const uint16_t *tok = u.tok;
     const uint2 *seg = u.seg;
-    const uint32_t o0 = blockIdx.x * WS_T, tile_end = min(o0 + WS_T, lim);
+    const uint32_t o0 = wr.bx * WS_T, tile_end = min(o0 + WS_T, lim);
     const uint32_t i0 = o0 + tid * 8, wend = min(i0 + 8, tile_end);
     uint32_t w8[4] = { 0u, 0u, 0u, 0u }, bad = 0;
     bool got = i0 >= tile_end;
-    for (uint32_t r0 = u.flags[blockIdx.x];; r0 += 1024 - 8) {            // table rounds overlap by 8 segments (8 symbols span at most 8)
+    for (uint32_t r0 = u.flags[wr.bx];; r0 += 1024 - 8) {            // table rounds overlap by 8 segments (8 symbols span at most 8)
         __syncthreads();
         const uint32_t si = r0 + tid;
         uint2 sg = make_uint2(0u, 0xFFFFFFFFu);
@@ -775,8 +835,6 @@ __global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, int32_t *a,
     }
 }
 
-int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
-
 // The most symbols a WaveletV2 stream of n pixels may announce: every coefficient escaped (3 words), + 8.  Go has no ceiling
 // (rledecompressu16.go:87-97 allocates what the stream announces); a stream above this one is MIC_ERR_CORRUPT here and in the oracle.
 inline size_t wv_sym_ceiling(size_t n) { return 3 * n + 8; }
@@ -789,118 +847,179 @@ void mic_launch_rle_expand(MicUnit *d_units, int n, hipStream_t stream, int mode
 
 namespace {
 
-// nf frames of rows x cols, contiguous on the device in s->io_px: forward transform, symbols, RLE + 4-state FSE in one batch.
-// blobs[i] receives frame i's FSE stream (without the 11-byte header), st[i] its status.
-// d_src: the frames on the device.  blobs == nullptr: the streams stay on the device (session_encode_finish's packed buffer:
-// *d_blobs_out / offs_out), nothing is copied to the host.
-int wv_compress_frames(mic_hip_session *s, const uint16_t *d_src, int nf, int rows, int cols, int applied,
-                       std::vector<std::vector<uint8_t>> *blobs, std::vector<int32_t> &st,
-                       const uint8_t **d_blobs_out = nullptr, uint64_t *offs_out = nullptr) {
-    const size_t n = (size_t)rows * (size_t)cols;
+// ---- the tables of a launch chain, on the host -------------------------------------------------------------------------------------
+// The work lists of a chain, one per launch (a span of the chain's work records), in this order.
+enum { WV_ENC_LOAD = 0, WV_ENC_FWD = 1 /* + l, 0 .. 7 */, WV_ENC_POS = 9, WV_ENC_LISTS = 10 };
+enum { WV_DEC_POS = 0, WV_DEC_STORE = 1, WV_DEC_BAND = 2, WV_DEC_INV = 3 /* + l: level l restored as it is */,
+       WV_DEC_SAT = 11 /* + l, 1 .. 7: level l as the saturated band of a reduced decode */, WV_DEC_LISTS = 19 };
+struct WvTables {
+    std::vector<WvFrame> fr; std::vector<WvWork> wk; std::vector<uint32_t> spans;       // spans: first, count per list
+    size_t a_elems = 0, b_elems = 0, n_max = 0;
+    // frame i: rows x cols with `levels` applied, wanted at `level`, its pixels px_off elements into the launch's pixel buffer
+    void add(int rows, int cols, int levels, int level, uint64_t px_off) {
+        WvFrame f{};
+        f.d = wv_dims(rows, cols, levels); f.level = level;
+        f.lim = (uint32_t)f.d.nr[level] * (uint32_t)f.d.nc[level];
+        f.ll_half = (uint32_t)align_up((size_t)f.d.nr[1] * (size_t)f.d.nc[1], 4);
+        f.px_off = px_off; f.a_off = a_elems; f.b_off = b_elems;
+        const size_t n = (size_t)rows * (size_t)cols;
+        a_elems += align_up(n, 4); b_elems += 2 * (size_t)f.ll_half;
+        n_max = std::max(n_max, n);
+        fr.push_back(f);
+    }
+    // the next list: nbx x nby records (tiles(f, nbx, nby)) of every frame that takes part
+    template <class Take, class Tiles> void list(Take &&take, Tiles &&tiles) {
+        const size_t first = wk.size();
+        for (size_t f = 0; f < fr.size(); f++) {
+            if (!take(fr[f])) continue;
+            uint32_t nbx = 0, nby = 1;
+            tiles(fr[f], nbx, nby);
+            for (uint32_t by = 0; by < nby; by++) for (uint32_t bx = 0; bx < nbx; bx++) wk.push_back(WvWork{ (uint32_t)f, bx, by, 0u });
+        }
+        spans.push_back((uint32_t)first); spans.push_back((uint32_t)(wk.size() - first));
+    }
+    static void level_tiles(const WvFrame &f, int l, uint32_t &nbx, uint32_t &nby) {     // the blocks of level l: pairs of columns x pairs of rows
+        nbx = (uint32_t)(((f.d.nc[l] + 1) / 2 + 4 * WS_LANES - 1) / (4 * WS_LANES));
+        nby = (uint32_t)(((f.d.nr[l] + 1) / 2 + WS_ROWS - 1) / WS_ROWS);
+    }
+    void encode_lists() {
+        list([](const WvFrame &f) { return f.d.levels == 0; }, [](const WvFrame &f, uint32_t &nbx, uint32_t &) { nbx = (f.lim + WV_CHUNK - 1) / WV_CHUNK; });
+        for (int l = 0; l < 8; l++)
+            list([l](const WvFrame &f) { return l < f.d.levels; }, [l](const WvFrame &f, uint32_t &nbx, uint32_t &nby) { level_tiles(f, l, nbx, nby); });
+        list([](const WvFrame &) { return true; }, [](const WvFrame &f, uint32_t &nbx, uint32_t &) { nbx = (f.lim + WS_T - 1) / WS_T; });
+    }
+    void decode_lists() {
+        list([](const WvFrame &) { return true; }, [](const WvFrame &f, uint32_t &nbx, uint32_t &) { nbx = (f.lim + WS_T - 1) / WS_T; });
+        list([](const WvFrame &f) { return f.d.levels == 0; }, [](const WvFrame &f, uint32_t &nbx, uint32_t &) { nbx = (f.lim + WV_CHUNK - 1) / WV_CHUNK; });
+        list([](const WvFrame &f) { return f.d.levels > 0 && f.level == f.d.levels; }, [](const WvFrame &f, uint32_t &nbx, uint32_t &) { nbx = (f.lim + WV_CHUNK - 1) / WV_CHUNK; });
+        for (int l = 0; l < 8; l++)
+            list([l](const WvFrame &f) { return l < f.d.levels && (l == 0 ? f.level == 0 : f.level < l); },
+                 [l](const WvFrame &f, uint32_t &nbx, uint32_t &nby) { level_tiles(f, l, nbx, nby); });
+        for (int l = 0; l < 8; l++)
+            list([l](const WvFrame &f) { return l > 0 && l < f.d.levels && f.level == l; },
+                 [l](const WvFrame &f, uint32_t &nbx, uint32_t &nby) { level_tiles(f, l, nbx, nby); });
+    }
+};
+// The chain's tables on the device, in the session's wv_tab_enc / wv_tab_dec: the frame records, then the work records.  A chain over the
+// frame records the buffer holds already builds and uploads nothing -- a loop of encode and decode calls on one list of shapes, each
+// with a buffer of its own, pays for its tables once.  The stream orders an upload behind the kernels of the chain before.
+struct WvDevTables { const WvFrame *ft; const WvWork *wk; const uint32_t *spans; };
+int wv_upload_tables(mic_hip_session *s, WvTables &t, bool encode, WvDevTables &dev) {
+    DevBuf &buf = encode ? s->wv_tab_enc : s->wv_tab_dec;
+    mic_hip_session::WvTabHeld &held = s->wv_tab_held[encode ? 1 : 0];
+    const size_t fbytes = t.fr.size() * sizeof(WvFrame);
+    const bool hit = buf.p && buf.gen == held.gen && held.key.size() == fbytes && memcmp(held.key.data(), t.fr.data(), fbytes) == 0;
+    if (!hit) {
+        held.gen = ~0ull;                                                 // (nothing is known of the buffer until the upload is queued)
+        if (encode) t.encode_lists(); else t.decode_lists();
+        // what the launches assume of their grids is checked before the first of them
+        if (t.wk.size() >= ((size_t)1 << 31)) return MIC_ERR_UNSUPPORTED;
+        const size_t wbytes = t.wk.size() * sizeof(WvWork);
+        int rc = buf.reserve(fbytes + wbytes + 64);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(buf.p, t.fr.data(), fbytes, hipMemcpyHostToDevice, s->stream));
+        if (wbytes) HIP_TRY(hipMemcpyAsync((char *)buf.p + fbytes, t.wk.data(), wbytes, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));                         // (the host vectors go away with the call)
+        held.key.assign((const uint8_t *)t.fr.data(), (const uint8_t *)t.fr.data() + fbytes);
+        held.spans.swap(t.spans); held.gen = buf.gen;
+    }
+    dev.ft = (const WvFrame *)buf.p;
+    dev.wk = (const WvWork *)((const char *)buf.p + fbytes);
+    dev.spans = held.spans.data();
+    return MIC_OK;
+}
+static_assert(sizeof(WvFrame) == 128 && sizeof(WvWork) == 16, "the work records behind the frame records are loaded 16 bytes at a time");
+
+// THE core of every WaveletV2 encode: the frames of `t` (any shapes and level counts; their pixels at d_src + px_off) through one
+// launch chain -- forward transform level by level, each level over the frames that have it; symbols; RLE + 4-state FSE.  On return
+// the streams (without the 11-byte header) lie packed in the session: *d_blobs + offs[i] .. offs[i + 1], st[i] = frame i's status.
+// Every unit is laid out by the largest frame (the tier-2 slabs of this path are not tiered: DESIGN.md section 7 item 6).
+int wv_compress_core(mic_hip_session *s, const uint16_t *d_src, WvTables &t, std::vector<int32_t> &st, const uint8_t **d_blobs, uint64_t *offs) {
+    const int nf = (int)t.fr.size();
+    if (nf <= 0) return MIC_ERR_ARGS;
     int rc;
-    if ((rc = s->lay_out(nf, 2 * n + 16))) return rc;                    // room for 3-word escapes
+    if ((rc = s->lay_out(nf, 2 * t.n_max + 16))) return rc;              // room for 3-word escapes
     DevBuf &a = s->wv_a, &b = s->wv_b;                                   // coefficient planes: kept by the session (no hipMalloc per call)
-    // b: the smooth planes between levels, two per frame (levels alternate), each (rows + 1) / 2 x (cols + 1) / 2 at most
-    const size_t ll_half = (size_t)((rows + 1) / 2) * (size_t)((cols + 1) / 2), ll_fs = 2 * ll_half;
-    if ((rc = a.reserve(n * 4 * (size_t)nf + 64)) || (rc = b.reserve(ll_fs * 4 * (size_t)nf + 64))) return rc;
+    // b: the smooth planes between levels, two per frame (levels alternate), each (rows + 1) / 2 x (cols + 1) / 2
+    if ((rc = a.reserve(t.a_elems * 4 + 64)) || (rc = b.reserve(t.b_elems * 4 + 64))) return rc;
+    WvDevTables dv;
+    if ((rc = wv_upload_tables(s, t, true, dv))) return rc;
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;
     for (int i = 0; i < nf; i++) {
         MicUnit &u = s->h_units[(size_t)i];
         u.w = 1; u.h = 1; u.nstates = 4; u.mode = 2; u.no_fallback = 1; // FSECompressU16FourState, no fallback (:344)
     }
+    auto first = [&](int list) { return dv.wk + dv.spans[2 * list]; };
+    auto count = [&](int list) { return dv.spans[2 * list + 1]; };
     rc = s->run_encode([&] {
+        MicUnit *U = (MicUnit *)s->units.p;
         s->timer.mark("k_wv_fwd2d");
-        if (applied == 0) hipLaunchKernelGGL(k_wv_load, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, d_src, A, n * (size_t)nf);
-        { int r = rows, c = cols;
-          for (int l = 0; l < applied; l++) {                                  // a level per launch: level l's smooth plane in B, parity l
-              const int rn = (r + 1) / 2, cn = (c + 1) / 2;
-              const dim3 g((unsigned)((cn + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)((rn + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
-              const bool last = l == applied - 1;
-              int32_t *lld = last ? A : B + ((l & 1) ? ll_half : 0);
-              const int lls = last ? cols : cn; const size_t llf = last ? n : ll_fs;
-              if (l == 0) hipLaunchKernelGGL(k_wv_fwd2d<true>, g, dim3(256), 0, s->stream, (const void *)d_src, cols, n, A, cols, n, lld, lls, llf, r, c, nf);
-              else hipLaunchKernelGGL(k_wv_fwd2d<false>, g, dim3(256), 0, s->stream, (const void *)(B + (((l - 1) & 1) ? ll_half : 0)), c, ll_fs, A, cols, n, lld, lls, llf, r, c, nf);
-              r = rn; c = cn;
-          } }
-        s->timer.mark("k_wv_symbols");
-        {
-            const WvDims d = wv_dims(rows, cols, applied);
-            hipLaunchKernelGGL(k_wv_symbols_par, dim3((unsigned)((n + WS_T - 1) / WS_T), (unsigned)std::min(nf, 65535)), dim3(1024), 0, s->stream,
-                               (MicUnit *)s->units.p, (const int32_t *)A, d, nf);
-            hipLaunchKernelGGL(k_wv_symbols_fin, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, d, nf);
-            hipLaunchKernelGGL(k_wv_symbols, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, (const int32_t *)A, d);   // frames with wide coefficients
+        if (count(WV_ENC_LOAD)) hipLaunchKernelGGL(k_wv_load, dim3(count(WV_ENC_LOAD)), dim3(256), 0, s->stream, dv.ft, first(WV_ENC_LOAD), d_src, A);
+        for (int l = 0; l < 8 && count(WV_ENC_FWD + l); l++) {           // a level per launch, over the frames that have it: level l's smooth plane in B, parity l
+            if (l == 0) hipLaunchKernelGGL(k_wv_fwd2d<true>, dim3(count(WV_ENC_FWD)), dim3(256), 0, s->stream, dv.ft, first(WV_ENC_FWD), d_src, A, B, 0);
+            else hipLaunchKernelGGL(k_wv_fwd2d<false>, dim3(count(WV_ENC_FWD + l)), dim3(256), 0, s->stream, dv.ft, first(WV_ENC_FWD + l), d_src, A, B, l);
         }
-        mic_launch_encode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer);
+        s->timer.mark("k_wv_symbols");
+        hipLaunchKernelGGL(k_wv_symbols_par, dim3(count(WV_ENC_POS)), dim3(1024), 0, s->stream, U, dv.ft, first(WV_ENC_POS), (const int32_t *)A);
+        hipLaunchKernelGGL(k_wv_symbols_fin, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s->stream, U, dv.ft, nf);
+        hipLaunchKernelGGL(k_wv_symbols, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, U, dv.ft, (const int32_t *)A);   // frames with wide coefficients
+        mic_launch_encode(U, nf, s->stream, s->variant, &s->timer);
     });
     if (rc) return rc;
-    std::vector<uint64_t> offs((size_t)nf + 1); std::vector<int32_t> ns((size_t)nf); const uint8_t *d_blobs = nullptr;
+    std::vector<int32_t> ns((size_t)nf);
     st.assign((size_t)nf, 0);
-    if ((rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data()))) return rc;
-    if (!blobs) {
-        if (d_blobs_out) *d_blobs_out = d_blobs;
-        if (offs_out) memcpy(offs_out, offs.data(), sizeof(uint64_t) * ((size_t)nf + 1));
-        return MIC_OK;
-    }
-    std::vector<uint8_t> host((size_t)offs[(size_t)nf] + 16);
-    if (offs[(size_t)nf] && hipMemcpy(host.data(), d_blobs, (size_t)offs[(size_t)nf], hipMemcpyDeviceToHost) != hipSuccess) return MIC_ERR_DEVICE;
-    blobs->assign((size_t)nf, std::vector<uint8_t>());
-    for (int i = 0; i < nf; i++) if (st[(size_t)i] == MIC_OK) (*blobs)[(size_t)i].assign(host.begin() + (long)offs[(size_t)i], host.begin() + (long)offs[(size_t)i + 1]);
-    return MIC_OK;
+    return session_encode_finish(s, d_blobs, offs, st.data(), ns.data());
 }
 
-// nf FSE streams (already in s->io_comp at offs[i] .. offs[i + 1]) of frames of one shape -> pixels in s->io_px
-// level > 0: the image at that resolution (the nr[level] x nc[level] LL band, saturated to u16, row stride nc[level]) -- the first
-// P = nr[level] * nc[level] coefficients of the subband scan, the inverse levels levels - 1 .. level.  sym_limit: MicUnit::sym_limit of
-// every unit (0: the whole stream).  ends: frame i is offs[i] .. ends[i] instead (a subset of the streams, wv_decode_level_frames).
-int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, int nf, const uint64_t *offs, int rows, int cols, int levels,
-                         std::vector<int32_t> &st, int level = 0, uint32_t sym_limit = 0, const uint64_t *ends = nullptr) {
-    const size_t n = (size_t)rows * (size_t)cols;
+// One decode chain: the frames of `t` (frame i: the FSE stream d_comp + begins[i] .. ends[i], its pixels -- the band at its `level` -- to
+// d_dst + px_off) with MicUnit::sym_limit = limits[i] (0: the whole stream).
+int wv_decompress_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, WvTables &t, const uint64_t *begins, const uint64_t *ends,
+                        const uint32_t *limits, std::vector<int32_t> &st) {
+    const int nf = (int)t.fr.size();
     int rc;
     // everything the launches below assume is checked before the first of them: grid limits, stream ranges
-    if (nf <= 0 || nf > 65535 || n >= ((size_t)65535 * WS_T)) return MIC_ERR_UNSUPPORTED;
-    if (level < 0 || level > levels) return MIC_ERR_ARGS;
-    auto end_of = [&](int i) { return ends ? ends[(size_t)i] : offs[(size_t)i + 1]; };
+    if (nf <= 0 || nf > 65535) return MIC_ERR_UNSUPPORTED;
     for (int i = 0; i < nf; i++)
-        if (end_of(i) < offs[(size_t)i] || end_of(i) - offs[(size_t)i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
-    if ((rc = s->lay_out(nf, 2 * n + 16))) return rc;
+        if (ends[i] < begins[i] || ends[i] - begins[i] > 0xFFFFFFF0ull) return MIC_ERR_ARGS;
+    if ((rc = s->lay_out(nf, 2 * t.n_max + 16))) return rc;
     DevBuf &a = s->wv_a, &b = s->wv_b;
-    const size_t ll_half = (size_t)((rows + 1) / 2) * (size_t)((cols + 1) / 2), ll_fs = 2 * ll_half;   // (the smooth planes between levels, as in wv_compress_frames)
-    if ((rc = a.reserve(n * 4 * (size_t)nf + 64)) || (rc = b.reserve(ll_fs * 4 * (size_t)nf + 64))) return rc;
+    if ((rc = a.reserve(t.a_elems * 4 + 64)) || (rc = b.reserve(t.b_elems * 4 + 64))) return rc;   // (the smooth planes between levels, as in wv_compress_core)
+    WvDevTables dv;
+    if ((rc = wv_upload_tables(s, t, false, dv))) return rc;
     for (int i = 0; i < nf; i++) {
         MicUnit &u = s->h_units[(size_t)i];
-        u.comp_in = d_comp + offs[(size_t)i]; u.comp_len = (uint32_t)(end_of(i) - offs[(size_t)i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
-        u.sym_cap = (uint32_t)std::min<size_t>(u.sym_cap, wv_sym_ceiling(n));   // the oracle's ceiling: DESIGN.md section 4, WaveletV2
-        u.sym_limit = sym_limit;
+        const WvDims &d = t.fr[(size_t)i].d;
+        u.comp_in = d_comp + begins[i]; u.comp_len = (uint32_t)(ends[i] - begins[i]); u.w = 1; u.h = 1; u.mode = 1; u.walk_mode = 1;
+        u.sym_cap = (uint32_t)std::min<size_t>(u.sym_cap, wv_sym_ceiling((size_t)d.rows * (size_t)d.cols));   // the oracle's ceiling: DESIGN.md section 4, WaveletV2
+        u.sym_limit = limits[i];
     }
     int32_t *A = (int32_t *)a.p, *B = (int32_t *)b.p;
+    auto first = [&](int list) { return dv.wk + dv.spans[2 * list]; };
+    auto count = [&](int list) { return dv.spans[2 * list + 1]; };
     rc = s->run_decode(mic_hip_session::FlagSlab::Idle, [&] {            // (k_rle_walk_compact's scratch)
-        mic_launch_decode((MicUnit *)s->units.p, nf, s->stream, s->variant, &s->timer, (int *)s->cls.p);
-        const WvDims d = wv_dims(rows, cols, levels);
-        const uint32_t P = (uint32_t)d.nr[level] * (uint32_t)d.nc[level];   // the coefficients the output needs (n at level 0)
+        MicUnit *U = (MicUnit *)s->units.p;
+        mic_launch_decode(U, nf, s->stream, s->variant, &s->timer, (int *)s->cls.p);
         if (s->timer.used) { s->timer.used--; s->timer.names.pop_back(); }   // (drop the chain's "end" mark: the wavelet kernels follow)
         s->timer.mark("k_rle_walk_parts+fix+compact");
-        hipLaunchKernelGGL(k_rle_walk_parts, dim3(WP_PARTS, (unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
-        hipLaunchKernelGGL(k_rle_walk_fix, dim3((unsigned)nf), dim3(64), 0, s->stream, (MicUnit *)s->units.p);
-        hipLaunchKernelGGL(k_rle_walk_compact, dim3(WP_PARTS, (unsigned)nf), dim3(256), 0, s->stream, (MicUnit *)s->units.p);
+        hipLaunchKernelGGL(k_rle_walk_parts, dim3(WP_PARTS, (unsigned)nf), dim3(64), 0, s->stream, U);
+        hipLaunchKernelGGL(k_rle_walk_fix, dim3((unsigned)nf), dim3(64), 0, s->stream, U);
+        hipLaunchKernelGGL(k_rle_walk_compact, dim3(WP_PARTS, (unsigned)nf), dim3(256), 0, s->stream, U);
         s->timer.mark("k_wv_scatter");
-        hipLaunchKernelGGL(k_wv_scatter, dim3((unsigned)((P + WS_T - 1) / WS_T), (unsigned)nf), dim3(1024), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
+        hipLaunchKernelGGL(k_wv_scatter, dim3(count(WV_DEC_POS)), dim3(1024), 0, s->stream, U, dv.ft, first(WV_DEC_POS), A);
         s->timer.mark("k_wv_expand+coeffs (escape frames)");
-        hipLaunchKernelGGL(k_wv_expand, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, -1, 1);
-        hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, (MicUnit *)s->units.p, A, d, P);
+        hipLaunchKernelGGL(k_wv_expand, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, U, -1, 1);
+        hipLaunchKernelGGL(k_wv_coeffs, dim3((unsigned)nf), dim3(WV_THREADS), 0, s->stream, U, dv.ft, A);
         s->timer.mark("k_wv_inv2d");
-        if (levels == 0) hipLaunchKernelGGL(k_wv_store, dim3(grid_for(n * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, d_dst, n * (size_t)nf);
-        else if (level == levels)                                                               // the coarsest LL band itself: no inverse level
-            hipLaunchKernelGGL(k_wv_band, dim3(grid_for((size_t)P * (size_t)nf)), dim3(256), 0, s->stream, (const int32_t *)A, cols, n, d_dst, d.nr[level], d.nc[level], nf);
-        for (int l = levels - 1; l >= level; l--) {                                             // coarse -> fine, :519-527
-            const int r = d.nr[l], cc = d.nc[l];
-            const dim3 g((unsigned)(((cc + 1) / 2 + 4 * WS_LANES - 1) / (4 * WS_LANES)), (unsigned)(((r + 1) / 2 + WS_ROWS - 1) / WS_ROWS), (unsigned)std::min(nf, 65535));
-            const bool coarsest = l == levels - 1;
-            const int32_t *lls = coarsest ? A : B + (((l + 1) & 1) ? ll_half : 0);
-            const int llst = coarsest ? cols : d.nc[l + 1]; const size_t llf = coarsest ? n : ll_fs;
-            if (l == 0) hipLaunchKernelGGL(k_wv_inv2d<true>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cols, n, r, cc, nf);
-            else if (l == level)                                                                // reduced resolution: the band, saturated, stride nc[level]
-                hipLaunchKernelGGL((k_wv_inv2d<true, true>), g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)d_dst, cc, (size_t)P, r, cc, nf);
-            else hipLaunchKernelGGL(k_wv_inv2d<false>, g, dim3(256), 0, s->stream, (const int32_t *)A, cols, n, lls, llst, llf, (void *)(B + ((l & 1) ? ll_half : 0)), cc, ll_fs, r, cc, nf);
+        if (count(WV_DEC_STORE)) hipLaunchKernelGGL(k_wv_store, dim3(count(WV_DEC_STORE)), dim3(256), 0, s->stream, dv.ft, first(WV_DEC_STORE), (const int32_t *)A, d_dst);
+        if (count(WV_DEC_BAND)) hipLaunchKernelGGL(k_wv_band, dim3(count(WV_DEC_BAND)), dim3(256), 0, s->stream, dv.ft, first(WV_DEC_BAND), (const int32_t *)A, d_dst);
+        for (int l = 7; l >= 0; l--) {                                       // coarse -> fine, :519-527; a level over the frames that have it
+            const int plain = WV_DEC_INV + l, sat = WV_DEC_SAT + l;
+            if (count(plain)) {
+                if (l == 0) hipLaunchKernelGGL(k_wv_inv2d<true>, dim3(count(plain)), dim3(256), 0, s->stream, dv.ft, first(plain), (const int32_t *)A, B, d_dst, l);
+                else hipLaunchKernelGGL(k_wv_inv2d<false>, dim3(count(plain)), dim3(256), 0, s->stream, dv.ft, first(plain), (const int32_t *)A, B, d_dst, l);
+            }
+            if (count(sat))                                                  // reduced resolution: the band, saturated, stride nc[level]
+                hipLaunchKernelGGL((k_wv_inv2d<true, true>), dim3(count(sat)), dim3(256), 0, s->stream, dv.ft, first(sat), (const int32_t *)A, B, d_dst, l);
         }
         s->timer.mark("end");
     });
@@ -920,44 +1039,88 @@ uint32_t wv_level_sym_limit(size_t P, size_t n) {
     return (uint32_t)std::min<size_t>(lim, 0xFFFFFF00u);
 }
 
-// The image at `level` of nf streams of one shape (wv_decompress_frames' arguments), in two passes under one rule.  Pass 1 decodes
-// every frame with the tANS chain stopped at wv_level_sym_limit; a frame whose prefix did not give its P coefficients -- escape-heavy
-// frames (every 16-bit coefficient outside +-32767 is three words), or any failure inside the prefix -- is decoded again in pass 2,
-// whole (sym_limit 0), in a launch chain of its own, and that pass's status and output are the frame's.  Every other frame keeps
-// pass 1's.  The outputs are the same whichever pass made them; only a pass-2 (or level-0) decode checks the whole stream.
-// syms (nullable): tANS symbols the chain decoded per frame, both passes summed.
-int wv_decode_level_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, int nf, const uint64_t *offs, int rows, int cols,
-                           int levels, int level, std::vector<int32_t> &st, uint64_t *syms) {
-    const size_t n = (size_t)rows * (size_t)cols;
-    if (level < 0 || level > levels || levels > 8) return MIC_ERR_ARGS;
-    const WvDims d = wv_dims(rows, cols, levels);
-    const size_t P = (size_t)d.nr[level] * (size_t)d.nc[level];
-    const uint32_t lim = wv_level_sym_limit(P, n);
-    int rc = wv_decompress_frames(s, d_comp, d_dst, nf, offs, rows, cols, levels, st, level, lim);
+// THE core of every WaveletV2 decode: the frames of `t`, each at its own `level`, in two passes under one rule.  Pass 1 decodes every
+// frame with the tANS chain stopped at the frame's wv_level_sym_limit; a frame whose prefix did not give its P coefficients --
+// escape-heavy frames (every 16-bit coefficient outside +-32767 is three words), or any failure inside the prefix -- is decoded again
+// in pass 2, whole (sym_limit 0), in a launch chain of its own over a sub-table of those frames, to the same place; that pass's status
+// and output are the frame's.  Every other frame keeps pass 1's.  The outputs are the same whichever pass made them; only a pass-2
+// (or level-0) decode checks the whole stream.  syms (nullable): tANS symbols the chain decoded per frame, both passes summed.
+// redone (nullable): + the frames of pass 2 (a launch chain more when there are any).
+int wv_decompress_core(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, WvTables &t, const uint64_t *begins, const uint64_t *ends,
+                       std::vector<int32_t> &st, uint64_t *syms, uint64_t *redone = nullptr) {
+    const int nf = (int)t.fr.size();
+    std::vector<uint32_t> limits((size_t)std::max(nf, 0));
+    for (int i = 0; i < nf; i++) {
+        const WvFrame &f = t.fr[(size_t)i];
+        if (f.level < 0 || f.level > f.d.levels || f.d.levels > 8) return MIC_ERR_ARGS;
+        limits[(size_t)i] = wv_level_sym_limit(f.lim, (size_t)f.d.rows * (size_t)f.d.cols);
+    }
+    int rc = wv_decompress_frames(s, d_comp, d_dst, t, begins, ends, limits.data(), st);
     if (rc) return rc;
-    std::vector<int> redo; std::vector<uint64_t> begins, ends;
+    std::vector<int> redo; std::vector<uint64_t> b2, e2;
+    WvTables t2;
     for (int i = 0; i < nf; i++) {
         const MicUnit &u = s->h_units[(size_t)i];                       // (read back by session_decode_finish)
         if (syms) syms[i] = u.ntok;
-        if (st[(size_t)i] != MIC_OK && mic_is_prefix(u)) { redo.push_back(i); begins.push_back(offs[(size_t)i]); ends.push_back(offs[(size_t)i + 1]); }
+        if (st[(size_t)i] != MIC_OK && mic_is_prefix(u)) {
+            const WvFrame &f = t.fr[(size_t)i];
+            redo.push_back(i); b2.push_back(begins[i]); e2.push_back(ends[i]);
+            t2.add(f.d.rows, f.d.cols, f.d.levels, f.level, f.px_off);
+        }
     }
     if (redo.empty()) return MIC_OK;
-    // pass 2: the frames side by side into a staging plane of the session (unused by this path), then each to its place
     const int k = (int)redo.size();
-    DevBuf &tmp = s->io_px2;
-    if ((rc = tmp.reserve(P * 2 * (size_t)k + 64))) return rc;
-    std::vector<int32_t> st2;
-    if ((rc = wv_decompress_frames(s, d_comp, (uint16_t *)tmp.p, k, begins.data(), rows, cols, levels, st2, level, 0, ends.data()))) return rc;
+    if (redone) *redone += (uint64_t)k;
+    std::vector<int32_t> st2; const std::vector<uint32_t> whole((size_t)k, 0u);
+    if ((rc = wv_decompress_frames(s, d_comp, d_dst, t2, b2.data(), e2.data(), whole.data(), st2))) return rc;
     for (int j = 0; j < k; j++) {
         const int i = redo[(size_t)j];
         st[(size_t)i] = st2[(size_t)j];
         if (syms) syms[i] += s->h_units[(size_t)j].ntok;
-        if (st2[(size_t)j] == MIC_OK)
-            HIP_TRY(hipMemcpyAsync(d_dst + (size_t)i * P, (uint16_t *)tmp.p + (size_t)j * P, P * 2, hipMemcpyDeviceToDevice, s->stream));
     }
-    HIP_TRY(hipStreamSynchronize(s->stream));
     return MIC_OK;
 }
+
+// ---- the one-shape callers: a table of equal rows --------------------------------------------------------------------------------
+// nf frames of rows x cols, contiguous on the device at d_src.  blobs[i] receives frame i's FSE stream (without the 11-byte header),
+// st[i] its status.  blobs == nullptr: the streams stay on the device (session_encode_finish's packed buffer: *d_blobs_out /
+// offs_out), nothing is copied to the host.
+int wv_compress_frames(mic_hip_session *s, const uint16_t *d_src, int nf, int rows, int cols, int applied,
+                       std::vector<std::vector<uint8_t>> *blobs, std::vector<int32_t> &st,
+                       const uint8_t **d_blobs_out = nullptr, uint64_t *offs_out = nullptr) {
+    const size_t n = (size_t)rows * (size_t)cols;
+    WvTables t;
+    for (int i = 0; i < nf; i++) t.add(rows, cols, applied, 0, (uint64_t)i * n);
+    std::vector<uint64_t> offs((size_t)std::max(nf, 0) + 1); const uint8_t *d_blobs = nullptr;
+    int rc = wv_compress_core(s, d_src, t, st, &d_blobs, offs.data());
+    if (rc) return rc;
+    if (!blobs) {
+        if (d_blobs_out) *d_blobs_out = d_blobs;
+        if (offs_out) memcpy(offs_out, offs.data(), sizeof(uint64_t) * ((size_t)nf + 1));
+        return MIC_OK;
+    }
+    std::vector<uint8_t> host((size_t)offs[(size_t)nf] + 16);
+    if (offs[(size_t)nf] && hipMemcpy(host.data(), d_blobs, (size_t)offs[(size_t)nf], hipMemcpyDeviceToHost) != hipSuccess) return MIC_ERR_DEVICE;
+    blobs->assign((size_t)nf, std::vector<uint8_t>());
+    for (int i = 0; i < nf; i++) if (st[(size_t)i] == MIC_OK) (*blobs)[(size_t)i].assign(host.begin() + (long)offs[(size_t)i], host.begin() + (long)offs[(size_t)i + 1]);
+    return MIC_OK;
+}
+
+// nf FSE streams (d_comp + offs[i] .. offs[i + 1]) of frames of one shape at `level` -> frame i's nr[level] x nc[level] band (row stride
+// nc[level], saturated to u16; level 0: the image) at d_dst + i * nr[level] * nc[level]
+int wv_decode_level_frames(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_dst, int nf, const uint64_t *offs, int rows, int cols,
+                           int levels, int level, std::vector<int32_t> &st, uint64_t *syms) {
+    if (level < 0 || level > levels || levels > 8) return MIC_ERR_ARGS;
+    const WvDims d = wv_dims(rows, cols, levels);
+    const size_t P = (size_t)d.nr[level] * (size_t)d.nc[level];
+    WvTables t;
+    for (int i = 0; i < nf; i++) t.add(rows, cols, levels, level, (uint64_t)i * P);
+    return wv_decompress_core(s, d_comp, d_dst, t, offs, offs + 1, st, syms);
+}
+
+}  // namespace
+
+namespace micapi {
 
 void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int applied) {     // :346-350
     out[0] = (uint8_t)rows; out[1] = (uint8_t)(rows >> 8); out[2] = (uint8_t)(rows >> 16); out[3] = (uint8_t)((uint32_t)rows >> 24);
@@ -967,7 +1130,7 @@ void wv_put_header(uint8_t *out, int rows, int cols, uint16_t max_value, int app
 }
 
 // the argument gate of every entry point: MIC_OK, or why rows x cols (a decode: at `level` of a header's `levels`) is not coded here
-int wv_check_shape(int rows, int cols, int levels = 0, int level = 0) {
+int wv_check_shape(int rows, int cols, int levels, int level) {
     if (rows <= 0 || cols <= 0 || levels < 0 || levels > 8 || level < 0 || level > levels) return MIC_ERR_ARGS;
     return (size_t)rows * (size_t)cols > ((size_t)1 << 27) ? MIC_ERR_UNSUPPORTED : MIC_OK;
 }
@@ -978,6 +1141,37 @@ int wv_levels_applied(int rows, int cols, int levels) {
     for (int r = rows, c = cols; applied < levels && r >= 2 && c >= 2; applied++) { r = (r + 1) / 2; c = (c + 1) / 2; }
     return applied;
 }
+
+size_t wv_next_cut(const std::function<size_t(size_t)> &px, size_t i0, size_t n, size_t budget) {
+    return next_sub_batch(i0, n, px, cap_by_largest([budget](size_t mp) { return std::max<size_t>(1, budget / (unit_ws_bytes(2 * mp + 16) + 8 * mp)); }),
+                          CutRule{ 65535, ~(size_t)0, (size_t)1 << 30 });
+}
+
+int wv_encode_run(mic_hip_session *s, const uint16_t *d_px, const WvEncFrame *f, int n, const uint8_t **d_blobs, uint64_t *offs, int32_t *st) {
+    WvTables t;
+    for (int i = 0; i < n; i++) t.add(f[i].rows, f[i].cols, f[i].applied, 0, f[i].px_off);
+    std::vector<int32_t> sv;
+    const int rc = wv_compress_core(s, d_px, t, sv, d_blobs, offs);
+    if (rc == MIC_OK) std::copy(sv.begin(), sv.end(), st);
+    return rc;
+}
+
+int wv_decode_run(mic_hip_session *s, const uint8_t *d_comp, uint16_t *d_out, const WvDecFrame *f, int n, int32_t *st, uint64_t *syms, uint64_t *redone) {
+    WvTables t; std::vector<uint64_t> b((size_t)std::max(n, 0)), e((size_t)std::max(n, 0));
+    for (int i = 0; i < n; i++) {
+        if (wv_check_shape(f[i].rows, f[i].cols, f[i].levels, f[i].level)) return MIC_ERR_ARGS;
+        t.add(f[i].rows, f[i].cols, f[i].levels, f[i].level, f[i].px_off);
+        b[(size_t)i] = f[i].begin; e[(size_t)i] = f[i].end;
+    }
+    std::vector<int32_t> sv;
+    const int rc = wv_decompress_core(s, d_comp, d_out, t, b.data(), e.data(), sv, syms, redone);
+    if (rc == MIC_OK) std::copy(sv.begin(), sv.end(), st);
+    return rc;
+}
+
+}  // namespace micapi
+
+namespace {
 
 size_t wv_frames_per_batch(size_t n) { return std::max<size_t>(1, kWorkspaceBudget / (unit_ws_bytes(2 * n + 16) + 8 * n)); }
 
@@ -1171,7 +1365,7 @@ int mic_hip_session_wavelet_v2_decode(mic_hip_session *s, const uint8_t *d_strea
     int rc = wv_check_shape(rows, cols, levels);
     if (rc || (rc = s->activate())) return rc;
     std::vector<int32_t> st;
-    if ((rc = wv_decompress_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, st))) return rc;
+    if ((rc = wv_decode_level_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, 0, st, nullptr))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
     return MIC_OK;
 } MIC_ABI_CATCH
@@ -1186,6 +1380,58 @@ int mic_hip_session_wavelet_v2_decode_level(mic_hip_session *s, const uint8_t *d
     std::vector<int32_t> st;
     if ((rc = wv_decode_level_frames(s, d_streams, d_pixels_out, nframes, h_offsets, rows, cols, levels, level, st, h_symbols_decoded))) return rc;
     for (int i = 0; i < nframes; i++) h_status[i] = st[(size_t)i];
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// ---- the same pair over frames of any shapes and level counts, one launch chain (the cores above with the caller's table) ------------
+int mic_hip_session_wavelet_v2_encode_mixed(mic_hip_session *s, const uint16_t *d_frames, const uint64_t *h_px_offsets, const int32_t *h_rows_cols,
+                                            int nframes, int levels, const uint8_t **d_streams, uint64_t *h_offsets, int32_t *h_status,
+                                            int32_t *h_levels_applied) try {
+    if (!s || !d_frames || !h_px_offsets || !h_rows_cols || !d_streams || !h_offsets || !h_status || nframes <= 0) return MIC_ERR_ARGS;
+    int rc = s->activate();
+    if (rc) return rc;
+    std::vector<WvEncFrame> F; std::vector<int> at;
+    for (int i = 0; i < nframes; i++) {
+        const int rows = h_rows_cols[2 * (size_t)i], cols = h_rows_cols[2 * (size_t)i + 1];
+        if (h_levels_applied) h_levels_applied[i] = 0;
+        if ((h_status[i] = wv_check_shape(rows, cols))) continue;
+        F.push_back(WvEncFrame{ h_px_offsets[i], rows, cols, wv_levels_applied(rows, cols, levels) });
+        if (h_levels_applied) h_levels_applied[i] = F.back().applied;
+        at.push_back(i);
+    }
+    *d_streams = nullptr;
+    for (int i = 0; i <= nframes; i++) h_offsets[i] = 0;
+    if (F.empty()) return MIC_OK;
+    std::vector<uint64_t> offs(F.size() + 1); std::vector<int32_t> st(F.size());
+    if ((rc = wv_encode_run(s, d_frames, F.data(), (int)F.size(), d_streams, offs.data(), st.data()))) return rc;
+    size_t k = 0;
+    for (int i = 0; i < nframes; i++) {                                   // (a refused frame takes no room between its neighbours' streams)
+        h_offsets[i] = offs[k];
+        if (k < at.size() && at[k] == i) { h_status[i] = st[k]; k++; }
+    }
+    h_offsets[nframes] = offs[F.size()];
+    return MIC_OK;
+} MIC_ABI_CATCH
+int mic_hip_session_wavelet_v2_decode_mixed(mic_hip_session *s, const uint8_t *d_streams, const uint64_t *h_offsets, const int32_t *h_rows_cols_levels,
+                                            const int32_t *h_level, int nframes, uint16_t *d_pixels_out, const uint64_t *h_out_offsets,
+                                            int32_t *h_status, uint64_t *h_symbols_decoded) try {
+    if (!s || !d_streams || !h_offsets || !h_rows_cols_levels || !d_pixels_out || !h_out_offsets || !h_status || nframes <= 0) return MIC_ERR_ARGS;
+    int rc = s->activate();
+    if (rc) return rc;
+    std::vector<WvDecFrame> F; std::vector<int> at;
+    for (int i = 0; i < nframes; i++) {
+        const int32_t *q = h_rows_cols_levels + 3 * (size_t)i;
+        const int level = h_level ? h_level[i] : 0;
+        if (h_symbols_decoded) h_symbols_decoded[i] = 0;
+        if ((h_status[i] = wv_check_shape(q[0], q[1], q[2], level))) continue;
+        if (h_offsets[i + 1] < h_offsets[i]) { h_status[i] = MIC_ERR_ARGS; continue; }
+        F.push_back(WvDecFrame{ h_offsets[i], h_offsets[i + 1], h_out_offsets[i], q[0], q[1], q[2], level });
+        at.push_back(i);
+    }
+    if (F.empty()) return MIC_OK;
+    std::vector<int32_t> st(F.size()); std::vector<uint64_t> sy(F.size(), 0);
+    if ((rc = wv_decode_run(s, d_streams, d_pixels_out, F.data(), (int)F.size(), st.data(), sy.data(), nullptr))) return rc;
+    for (size_t k = 0; k < at.size(); k++) { h_status[at[k]] = st[k]; if (h_symbols_decoded) h_symbols_decoded[at[k]] = sy[k]; }
     return MIC_OK;
 } MIC_ABI_CATCH
 
