@@ -703,6 +703,15 @@ int mic_hip_debug_tab_route(mic_hip_session *s, int i, uint32_t *out) try {
     *out = s->h_units[(size_t)i].tb_route;
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): which tANS encode kernel decided unit i (MicUnit.enc_kernel, mic_dev.h) after an encode's
+// *_finish.  out[0]: 1 + the bit index of the MIC_ENC_CLS_* class, MIC_ENC_BY_SERIAL, or 0 for nobody; out[1]: MicUnit.enc_rounds,
+// the fix-up rounds of the deciding attempt; out[2]: 1 when the two-state instance had handed the unit over (MIC_ENC_HANDED)
+int mic_hip_debug_enc_kernel(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    const MicUnit &u = s->h_units[(size_t)i];
+    out[0] = u.enc_kernel & 0xFFu; out[1] = u.enc_rounds; out[2] = (u.enc_kernel & MIC_ENC_HANDED) ? 1u : 0u;
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): the head of one of unit i's table slabs after a *_finish.
 // which: 0 state_tab (u32), 1 tt_nb (u32), 2 tt_find (i32), 3 tab_sym (u16), 4 norm (i32)
 int mic_hip_debug_fetch_table(mic_hip_session *s, int i, int which, void *dst, size_t bytes) try {
@@ -718,13 +727,13 @@ int mic_hip_debug_fetch_table(mic_hip_session *s, int i, int which, void *dst, s
 // tier 2 as mic_hip_fse_compress_u16_ex / mic_hip_fse_decompress_u16_ex lay out their one (tests/test_gpu_table_routes.py).
 // Encode: unit i codes counts[i] symbols from d_symbols + sym_off[i] with FSECompressU16* semantics (mode 1, no fallback chain),
 // flavour flavours[i], ScratchU16.TableLog req_tl[i]; mic_hip_session_encode_finish then returns blobs, offsets and statuses.
-int mic_hip_debug_fse_encode_enqueue(mic_hip_session *s, const uint16_t *d_symbols, const uint64_t *sym_off, const uint32_t *counts,
-                                     const int32_t *flavours, const int32_t *req_tl, int n) try {
+static int debug_fse_encode_enqueue(mic_hip_session *s, const uint16_t *d_symbols, const uint64_t *sym_off, const uint32_t *counts,
+                                   const int32_t *flavours, const int32_t *req_tl, int n, bool chain) {
     if (!s || !d_symbols || !sym_off || !counts || !flavours || !req_tl || n <= 0 || n > 65535) return MIC_ERR_ARGS;
     size_t most = 0;
     for (int i = 0; i < n; i++) {
         const int f = flavours[i];
-        if (!(f == 1 || f == 2 || f == 4 || f == 8 || f == 108) || req_tl[i] < 0 || req_tl[i] > MIC_MAX_TABLELOG) return MIC_ERR_ARGS;
+        if (!(f == 1 || f == 2 || f == 4 || f == 8 || (f == 108 && !chain)) || req_tl[i] < 0 || req_tl[i] > MIC_MAX_TABLELOG) return MIC_ERR_ARGS;
         if (counts[i] == 0 || counts[i] > (1u << 30)) return MIC_ERR_ARGS;
         most = std::max(most, (size_t)counts[i]);
     }
@@ -735,9 +744,20 @@ int mic_hip_debug_fse_encode_enqueue(mic_hip_session *s, const uint16_t *d_symbo
     for (int i = 0; i < n; i++) {
         MicUnit &u = s->h_units[(size_t)i];
         u.px_in = d_symbols + sym_off[i]; u.w = (int32_t)counts[i]; u.h = 1; u.max_value = 0;
-        u.nstates = (uint16_t)flavours[i]; u.mode = 1; u.no_fallback = 1; u.req_tl = (uint32_t)req_tl[i];
+        u.nstates = (uint16_t)flavours[i]; u.mode = 1; u.no_fallback = chain ? 0u : 1u; u.req_tl = (uint32_t)req_tl[i];
     }
     return s->run_encode([&] { mic_launch_encode((MicUnit *)s->units.p, n, s->stream, s->variant, nullptr); });
+}
+int mic_hip_debug_fse_encode_enqueue(mic_hip_session *s, const uint16_t *d_symbols, const uint64_t *sym_off, const uint32_t *counts,
+                                     const int32_t *flavours, const int32_t *req_tl, int n) try {
+    return debug_fse_encode_enqueue(s, d_symbols, sym_off, counts, flavours, req_tl, n, false);
+} MIC_ABI_CATCH
+// The same door with the fallback chain of CompressSingleFrame* behind the table stage (no_fallback = 0: N -> N / 2 -> ... -> 1 over
+// one table, as k_enc_tans_wg runs it for frames), so that bare token streams can take the two-state instance's hand-over; flavour
+// 108 is not taken (the chain has no rANS member).  tests/test_gpu_tans_encode.py.
+int mic_hip_debug_fse_encode_chain_enqueue(mic_hip_session *s, const uint16_t *d_symbols, const uint64_t *sym_off, const uint32_t *counts,
+                                           const int32_t *flavours, const int32_t *req_tl, int n) try {
+    return debug_fse_encode_enqueue(s, d_symbols, sym_off, counts, flavours, req_tl, n, true);
 } MIC_ABI_CATCH
 // Decode: unit i is the FSE stream at d_blobs + [begins[i], ends[i]) (FSEDecompressU16Auto), at most caps[i] symbols;
 // mic_hip_session_decode_finish returns the statuses, mic_hip_debug_unit the counts and mic_hip_debug_fetch_tok the symbols.

@@ -32,6 +32,10 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 // MicUnit.dec_kernel behind the 30 lane-per-state classes (1 .. 30)
 #define MIC_DEC_BY_GL           31u
 #define MIC_DEC_BY_SERIAL       32u
+// MicUnit.enc_kernel: 1 + the bit index of the MIC_ENC_CLS_* class (mic_launch.h) whose k_enc_tans_wg instance gave the unit its tANS
+// verdict (1 .. 7), or MIC_ENC_BY_SERIAL; MIC_ENC_HANDED is set beside it when the two-state instance had handed the unit over first
+#define MIC_ENC_BY_SERIAL       8u
+#define MIC_ENC_HANDED          0x100u
 // MicUnit.tk_paths: routes of k_enc_tokens_wg (mic_encode.hip).  A pass is one walk over a symbol window: one per tile, two for a tile
 // that holds an escape, one more for the flush; a wave-pass is one wave's share of it.
 #define MIC_TKP_FAST            0      // passes that took the fast tile
@@ -137,6 +141,11 @@ struct MicUnit {
                               // predicted by tests/table_routes.py
     uint32_t tk_paths[MIC_TK_PATHS];   // encode: which routes k_enc_tokens_wg took through the unit (MIC_TKP_*), written once next to ntok;
                               // read by mic_hip_debug_tok_paths, predicted by tests/tokeniser_paths.py
+    uint32_t enc_kernel;      // encode: which kernel gave the unit's tANS stage its verdict, coded or refused (MIC_ENC_BY_SERIAL, MIC_ENC_HANDED
+                              // above); 0: nobody -- the unit failed in front of the stage, or no launched instance matched it.  Thread 0
+                              // writes it next to nstates_used / status; cleared with the other results (lay_out: MicUnit{})
+    uint32_t enc_rounds;      // encode: fix-up rounds te_encode ran in the attempt that decided the unit (>= 1; 0: k_enc_tans_serial, or no
+                              // walk ran).  Read by mic_hip_debug_enc_kernel, predicted by tests/tans_encode_model.py
     // ---- input, decode (WaveletV2 at reduced resolution, mic_wavelet.hip) -----------
     uint32_t sym_limit;       // 0: the whole stream.  Else the chain kernels that honour it decode only the first
                               // round_up(sym_limit, 128) symbols (whole 128-symbol chunks) and leave ntok < count: a PREFIX unit,

@@ -712,6 +712,7 @@ __global__ void __launch_bounds__(64) k_enc_tans_serial(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
     if (threadIdx.x != 0 || u.status != MICD_OK) return;
     if (u.nstates_used != 0) return;                                      // k_enc_tans_wg already wrote it
+    u.enc_kernel = MIC_ENC_BY_SERIAL; u.enc_rounds = 0;                   // (whatever the verdict below)
     if (u.nstates == 108) { u.status = MICD_ERR_UNSUPPORTED; return; }     // rANS encode exists only in k_enc_tans_wg
     const uint32_t n = u.ntok;
     const uint16_t *src = u.tok;
@@ -1084,8 +1085,10 @@ __device__ void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *s_tt,
     for (int k = 0; k < N; k++) s_E[(tid) * N + k] = (uint16_t)(st[k] - size);
     MIC_STAMP_AT(u, 8);
     // ---- 2. fix-up rounds to the fixed point -----------------------------------------------------
+    uint32_t rounds = 0;                                  // (uniform: every thread leaves the loop in the same round)
     for (uint32_t round = 0; round < T; round++) {
         __syncthreads();
+        rounds = round + 1;
         int changed = 0;
         uint32_t e_out[N], st2[N]; bool any = false;
 #pragma unroll
@@ -1137,6 +1140,7 @@ __device__ void te_encode(MicUnit &u, uint16_t *s_stab, const uint2 *s_tt,
     // empty tail threads may not have been reached by a round: propagate the final states down
     // (thread T-1 must hold the end states of every chain for the trailer)
     if (tid == 0) {
+        u.enc_rounds = rounds;                                            // (the attempt that decides the unit is the last to write it)
         // last thread that owns tokens
         uint32_t last = (nblk + per - 1) / per; if (last > 0) last--;
         for (int k = 0; k < N; k++) s_E[(T - 1) * N + k] = s_E[(last) * N + k];
@@ -1208,6 +1212,11 @@ template <int TLHI, int T, int TTS, int WIDTH = 0>      // table-size class of t
 // the name: the WaveletV2 four-state walk at tableLog 16 used to run on the 80 registers of the first class, 47 of them spilled).
 __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2 : TE_NARROW_WPS) : 2) k_enc_tans_wg(MicUnit *units, int e_states) {
     constexpr uint32_t tl_lo = (TLHI <= 13) ? 5u : (uint32_t)TLHI, tl_hi = (uint32_t)TLHI;
+    // MicUnit.enc_kernel of this instance: 1 + the bit index of the MIC_ENC_CLS_* class mic_launch_encode launches it for (mic_launch.h)
+    constexpr uint32_t ENC_CLS = T == 64 ? (TLHI == 12 ? MIC_ENC_CLS_SMALL12 : MIC_ENC_CLS_SMALL13) : TLHI == 14 ? MIC_ENC_CLS_TL14 : TLHI == 15 ? MIC_ENC_CLS_TL15
+                               : TLHI == 16 ? MIC_ENC_CLS_TL16 : WIDTH == 1 ? MIC_ENC_CLS_NARROW2 : MIC_ENC_CLS_WIDE;
+    constexpr uint32_t ENC_ID = 1u + (uint32_t)__builtin_ctz(ENC_CLS);
+    static_assert((ENC_CLS & (ENC_CLS - 1u)) == 0 && ENC_ID < MIC_ENC_BY_SERIAL, "one class bit per instance, below the serial kernel's value");
     extern __shared__ __attribute__((aligned(16))) uint16_t s_stab[];
     uint16_t *const s_E = s_stab + (1u << TLHI) + (TLHI <= 15 ? (uint32_t)TTS * 4u : 0u);
     __shared__ uint32_t s_scan[(T / 64) + 2];
@@ -1216,14 +1225,14 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
     const bool handed = u.nstates_used == -2;                              // the two-state instance gave up on its first attempt (below)
     if (u.nstates_used != 0 && !(WIDTH == 2 && handed)) return;
     if (WIDTH != 0 && ((u.nstates != 2 || u.symbol_len > TTS || handed) ? 2 : 1) != WIDTH) return;   // (1: two states, coding records in LDS)
-    if ((u.nstates == 108 ? 8 : (int)u.nstates) > e_states) { if (threadIdx.x == 0) u.status = MICD_ERR_INTERNAL; return; }   // (the launcher sizes the LDS for e_states)
+    if ((u.nstates == 108 ? 8 : (int)u.nstates) > e_states) { if (threadIdx.x == 0) { u.status = MICD_ERR_INTERNAL; u.enc_kernel = ENC_ID | (handed ? MIC_ENC_HANDED : 0u); } return; }   // (the launcher sizes the LDS for e_states)
     const uint32_t tl = u.table_log;
     if (tl < tl_lo || tl > tl_hi) return;
     if (TLHI <= 13 && te_small_class(u) != (T == 64 ? (TLHI == 12 ? 1 : 2) : 0)) return;   // (small units: the one-wave instances)
     const uint32_t tid = threadIdx.x;
     const uint32_t n = u.ntok;
     const uint32_t size = 1u << tl;
-    if (u.sym_cap < ((n + TE_BLK - 1) / TE_BLK) * TE_BLK) { if (tid == 0) u.status = u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CAPACITY; return; }
+    if (u.sym_cap < ((n + TE_BLK - 1) / TE_BLK) * TE_BLK) { if (tid == 0) { u.status = u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CAPACITY; u.enc_kernel = ENC_ID | (handed ? MIC_ENC_HANDED : 0u); } return; }
     if (u.nstates != 108) { const mic_gp<const uint32_t> gst = mic_g((const uint32_t *)u.state_tab); for (uint32_t i = tid; i < size; i += T) s_stab[i] = (uint16_t)(gst[i] - (TLHI <= 15 ? 0u : size)); }
     uint2 *s_tt = (uint2 *)(s_stab + (1u << TLHI));                              // TTS coding records, 8 bytes each
     const bool ttl = TLHI <= 15 && u.symbol_len <= TTS;
@@ -1270,13 +1279,14 @@ __global__ void __launch_bounds__(T, T != 512 ? 4 : TLHI <= 13 ? (WIDTH == 2 ? 2
                 u.blob_len = ((lanes == 1) ? 0 : 6) + hdr_len + total_bytes;      // 1-state blob starts at blob + 6
                 u.nstates_used = (int32_t)lanes;
                 u.packed_direct = (WIDTH == 1 && lanes == 2) ? 1u : 0u;           // (its bitstream is k_enc_tans_pack's to write)
+                u.enc_kernel = ENC_ID | (handed ? MIC_ENC_HANDED : 0u);
                 u.status = MICD_OK;
             }
             return;
         }
         if (tid == 0) { u.count = (uint32_t)rc; u.bits_off = total_bytes; u.flavour = lanes; }   // probe: why the attempt failed
         if (rc == MICD_ERR_CAPACITY && u.tier == 1) rc = MICD_INT_GROW;               // (the staging blob is tier 1's)
-        if (lanes == 1 || rc == MICD_ERR_CAPACITY || rc == MICD_INT_GROW || single) { if (tid == 0) u.status = rc; return; }
+        if (lanes == 1 || rc == MICD_ERR_CAPACITY || rc == MICD_INT_GROW || single) { if (tid == 0) { u.status = rc; u.enc_kernel = ENC_ID | (handed ? MIC_ENC_HANDED : 0u); } return; }
         if (WIDTH == 1) { if (tid == 0) u.nstates_used = -2; return; }        // the one-state attempt is the wide instance's (it starts over)
         __syncthreads();
     }

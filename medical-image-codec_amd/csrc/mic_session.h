@@ -233,7 +233,8 @@ struct mic_hip_session {
         int nn = n; size_t pp = px;
         const size_t tokc = tok_cap_tier(pp, want_tier), ts = tab_syms_tier(want_tier);
         const size_t tok_s = align_up(tokc * 2, 256);
-        const size_t blob_s = align_up(blob_cap_tok(tokc), 256);
+        const size_t blob_s = align_up(blob_cap_tok(tokc), 256);   // (te_encode's bit grid starts (6 + hdr_len) & 15 bytes into its 16-byte unit because of this
+                                                                   // alignment: tests/tans_encode_model.py, STAGING_ALIGN, aims streams at the grid's 64-bit units with it)
         const size_t seg_s = align_up(seg_cap_tier(pp, want_tier) * 8, 256);
         const size_t sym_s = align_up((tokc + 64) * 2, 256);       // + a block: the tANS encoder rounds its per-token states up to 32
         const size_t flag_s = align_up(pp / 8 + 16, 256);          // + the predictor's 3-word read at the last pixel

@@ -1,7 +1,9 @@
 """Thin ctypes bindings of the table stage's debug doors and probes (csrc/mic_api.hip; none of them is in the public header or in
 the package): many bare FSE units in one launch chain of a caller's Session, the route record, the table slabs and the tokens of a
-unit after a *_finish.  They use the Session's handle and its unit count as Session.encode_finish / decode_finish do; the first
-call checks that both are still there under those names.  Used by tests/test_gpu_table_routes.py."""
+unit after a *_finish; and of the tANS encode stage's (the same encode door with the fallback chain, the record of which kernel coded
+a unit).  They use the Session's handle and its unit count as Session.encode_finish / decode_finish do; the first
+call checks that both are still there under those names.  Used by tests/test_gpu_table_routes.py and
+tests/test_gpu_tans_encode.py."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +15,8 @@ _DT = {STATE_TAB: np.uint32, TT_NB: np.uint32, TT_FIND: np.int32, TAB_SYM: np.ui
 def _lib(mic):
     L = mic.lib()
     L.mic_hip_debug_fse_encode_enqueue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mic_hip_debug_fse_encode_chain_enqueue.argtypes = L.mic_hip_debug_fse_encode_enqueue.argtypes
+    L.mic_hip_debug_enc_kernel.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.mic_hip_debug_fse_decode_enqueue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.mic_hip_debug_tab_route.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.mic_hip_debug_fetch_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
@@ -32,11 +36,13 @@ def _session(sess):
     return sess._h
 
 
-def fse_encode_batch(mic, sess, d_symbols, sym_off, counts, flavours, req_tl):
-    """N bare FSE units in one encode chain of `sess` -> what Session.encode_finish returns"""
+def fse_encode_batch(mic, sess, d_symbols, sym_off, counts, flavours, req_tl, chain=False):
+    """N bare FSE units in one encode chain of `sess` -> what Session.encode_finish returns; chain: with the fallback chain
+    N -> N / 2 -> ... -> 1 behind the table stage (mic_hip_debug_fse_encode_chain_enqueue)"""
     a = [np.ascontiguousarray(sym_off, np.uint64), np.ascontiguousarray(counts, np.uint32),
          np.ascontiguousarray(flavours, np.int32), np.ascontiguousarray(req_tl, np.int32)]
-    rc = _lib(mic).mic_hip_debug_fse_encode_enqueue(_session(sess), d_symbols, *[x.ctypes.data for x in a], len(a[1]))
+    door = _lib(mic).mic_hip_debug_fse_encode_chain_enqueue if chain else _lib(mic).mic_hip_debug_fse_encode_enqueue
+    rc = door(_session(sess), d_symbols, *[x.ctypes.data for x in a], len(a[1]))
     assert rc == 0, rc
     sess._n = len(a[1])
     return sess.encode_finish()
@@ -65,6 +71,13 @@ def route(mic, sess, i):
     r = C.c_uint32()
     assert _lib(mic).mic_hip_debug_tab_route(_session(sess), i, C.byref(r)) == 0
     return int(r.value)
+
+
+def enc_kernel(mic, sess, i):
+    """(MicUnit.enc_kernel without its flag, MicUnit.enc_rounds, handed over) of unit i after an encode's *_finish"""
+    out = (C.c_uint32 * 3)()
+    assert _lib(mic).mic_hip_debug_enc_kernel(_session(sess), i, out) == 0
+    return int(out[0]), int(out[1]), bool(out[2])
 
 
 def table(mic, sess, i, which, entries):
