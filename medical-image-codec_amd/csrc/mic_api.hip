@@ -249,7 +249,10 @@ static void learn_classes(mic_hip_session *s, int n) {
         for (int i = 0; i < n; i++) {
             const MicUnit &u = s->h_units[(size_t)i];
             const int c = mic_dec_cls(u.flavour, u.table_log, u.zero_bits);
-            if (c >= 0 && u.comp_len - u.bits_off < (1u << 27)) seen |= 1u << c;
+            if (c >= 0 && u.comp_len - u.bits_off < (1u << 27)) {
+                seen |= 1u << c;
+                if (c == 0 && mic_split_gate(u, s->split_cfg)) seen |= MIC_CLS_SPLIT | MIC_CLS_RETRY;   // (the retry launch stands behind every split launch)
+            }
         }
         s->dec_classes.learn(seen);
     }
@@ -347,7 +350,7 @@ int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_blobs, con
     }
     const int variant = s->variant | (any_grad ? MIC_VARIANT_GRAD : 0) | (any_gap ? MIC_VARIANT_GAP : 0);
     if ((rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
-            mic_launch_decode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, (int *)s->cls.p, rows_kmask, s->dec_classes.mask()); }))) return rc;
+            mic_launch_decode((MicUnit *)s->units.p, n, s->stream, variant, &s->timer, (int *)s->cls.p, rows_kmask, s->dec_classes.mask(), &s->split_cfg); }))) return rc;
     s->learn_decode = true;
     HIP_TRY(hipMemcpyAsync(s->h_units.data(), s->units.p, sizeof(MicUnit) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
     s->readback_queued = true;
@@ -672,6 +675,23 @@ int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {
     out8[8] = u.count; out8[9] = u.bits_off; out8[10] = (uint32_t)u.nstates_used; out8[11] = (uint32_t)u.status; out8[12] = u.nseg; out8[13] = u.nsym; out8[14] = u.seg_cap;
     out8[15] = u.dec_kernel;                                             // 1 + lane-per-state class, MIC_DEC_BY_GL, MIC_DEC_BY_SERIAL; 0: no tANS kernel took the unit
     for (int k = 0; k < 16; k++) out8[16 + k] = u.dbg[k];
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug probe (not in the public header): what the split two-state decode instance made of unit i after a decode's *_finish --
+// out[0]: MIC_SPLIT_* (mic_dev.h: 0 not tried, 1 split, 2 .. fell back and why), out[1]: i_sync, out[2]: j_sync
+int mic_hip_debug_split(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    for (int k = 0; k < 3; k++) out[k] = s->h_units[(size_t)i].split[k];
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug setter (not in the public header): the session's split gate and overlap (MicSplitCfg, mic_dev.h); a zero keeps a value.
+// The session forgets its launch masks, so the next batch is classified under the new values.
+int mic_hip_debug_split_config(mic_hip_session *s, uint32_t min_tokens, uint32_t overlap, uint32_t min_bits16) try {
+    if (!s || (overlap && (overlap < 64u || (overlap & 63u)))) return MIC_ERR_ARGS;
+    if (min_tokens) s->split_cfg.min_tokens = min_tokens;
+    if (overlap) s->split_cfg.overlap = overlap;
+    if (min_bits16) s->split_cfg.min_bits16 = min_bits16;
+    s->dec_classes = mic_hip_session::ClsMemory{};
     return MIC_OK;
 } MIC_ABI_CATCH
 // debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py

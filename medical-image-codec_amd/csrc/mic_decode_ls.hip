@@ -84,11 +84,17 @@ __device__ __forceinline__ uint64_t ls_rl64(uint64_t v, int lane) {
 // N-state streams (rANS-8 decodes as 8-state), + 6 per table-size class (tableLog <= 13, 14, 15, 16); 1-state streams, very long
 // streams and tableLog-16 tables with 0-bit entries are left to the kernels of mic_decode.hip.
 // One group; the stream checks that need the blob (empty bitstream, zero end byte: bitreader.go:33-38) are made here.
-__global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, int *list, int *count) {
-    __shared__ uint32_t s_w[16][LS_CLASSES];
-    __shared__ uint32_t s_base[LS_CLASSES];
+// List LS_SPLIT_LIST holds the units of class 0 (two states, tableLog 13, no 0-bit entries) that k_dec_tans_ls_split takes when
+// `split` is set (the launcher's: that kernel is launched) -- whole streams of at least min_tokens tokens and min_bits16 / 16 bits
+// per token; list LS_RETRY_LIST is filled by that kernel with what it hands back, its count starts at zero here.
+#define LS_SPLIT_LIST MIC_CLS_CLASSES
+#define LS_RETRY_LIST (MIC_CLS_CLASSES + 1)
+#define LS_LISTS (MIC_CLS_CLASSES + 1)             // lists this kernel fills
+__global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, int *list, int *count, int split, MicSplitCfg cfg) {
+    __shared__ uint32_t s_w[16][LS_LISTS];
+    __shared__ uint32_t s_base[LS_LISTS];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < LS_CLASSES) s_base[tid] = 0;
+    if (tid < LS_LISTS) s_base[tid] = 0;
     __syncthreads();
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + (int)tid;
@@ -102,13 +108,16 @@ __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, in
                 if (u.bits_off >= u.comp_len) u.status = MICD_ERR_CORRUPT;
                 else if (u.comp_len - u.bits_off < (1u << 27)) {            // 32-bit bit positions here; the serial kernel takes longer ones
                     if (u.comp_in[u.comp_len - 1] == 0) u.status = MICD_ERR_CORRUPT;
-                    else cls = mic_dec_cls(flav, tl, u.zero_bits);
+                    else {
+                        cls = mic_dec_cls(flav, tl, u.zero_bits);
+                        if (cls == 0 && split && mic_split_gate(u, cfg)) cls = LS_SPLIT_LIST;
+                    }
                 }
             }
         }
         uint32_t rank = 0;
 #pragma unroll
-        for (int c = 0; c < LS_CLASSES; c++) {
+        for (int c = 0; c < LS_LISTS; c++) {
             const uint64_t m = __ballot(cls == c);
             if (cls == c) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             if (lane == 0) s_w[wave][c] = (uint32_t)__popcll(m);
@@ -120,10 +129,11 @@ __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, in
             list[(size_t)cls * (size_t)n + off + rank] = i;
         }
         __syncthreads();
-        if (tid < LS_CLASSES) { uint32_t t = 0; for (int w = 0; w < 16; w++) t += s_w[w][tid]; s_base[tid] += t; }
+        if (tid < LS_LISTS) { uint32_t t = 0; for (int w = 0; w < 16; w++) t += s_w[w][tid]; s_base[tid] += t; }
         __syncthreads();
     }
-    if (tid < LS_CLASSES) count[tid] = (int)s_base[tid];
+    if (tid < LS_LISTS) count[tid] = (int)s_base[tid];
+    if (tid == LS_RETRY_LIST) count[tid] = 0;
 }
 
 template <int N, bool ZB, int TL>
@@ -327,13 +337,13 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
         ".else\n\t" \
         "v_alignbit_b32 %[st], %[e], %[hi], %[m]\n\t" \
         ".endif\n\t" \
-        ".if ls_off < 256\n\t" \
+        ".if ls_off < ls_lim\n\t" \
         LS2_LOOKUP \
         "ds_write_b16 %[stg], %[st] offset:ls_off\n\t" \
         ".endif\n\t" \
         "v_add_u32_dpp %[pre], %[m], %[m] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
         "v_add_u32 %[q], %[q], %[pre]\n\t" \
-        ".if ls_off < 256\n\t" \
+        ".if ls_off < ls_lim\n\t" \
         "v_bfe_u32 " AN_ ", %[q], 5, %[RW]\n\t" \
         "v_lshl_add_u32 " AN_ ", " AN_ ", 2, %[ringb]\n\t" \
         "v_cmp_eq_u32 vcc, " AN_ ", " AO_ "\n\t" \
@@ -347,10 +357,14 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     // a whole chunk: 64 rounds.  The prologue looks up, stages the first state, reads the three dwords at the chunk's first position
     // and takes round 0's window from their upper pair; round 0's tail takes round 1's from the same three.
     // (a macro, not a lambda: clang does not capture through asm operands in a generic lambda)
-#define LS_CHUNK2() do { \
+    // DR_ double rounds, LIM_ = 4 * rounds: the stage offset behind which a round neither looks up nor reads (the split kernel's
+    // chunk is 32 rounds: LS_CHUNK2_N("16", "128"))
+#define LS_CHUNK2() LS_CHUNK2_N("32", "256")
+#define LS_CHUNK2_N(DR_, LIM_) do { \
         uint32_t e, c, cp, m, hi, pre, at, a0, a1, lo, hh; \
         q -= 32; \
         asm volatile(".set ls_off, 4\n\t" \
+                     ".set ls_lim, " LIM_ "\n\t" \
                      LS2_LOOKUP \
                      "ds_write_b16 %[stg], %[st]\n\t" \
                      "v_bfe_u32 %[a1], %[q], 5, %[RW]\n\t" \
@@ -358,7 +372,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
                      LS2_DWORDS("%[a1]") \
                      "s_waitcnt lgkmcnt(0)\n\t" \
                      "v_alignbit_b32 %[hi], v62, v61, %[q]\n\t" \
-                     ".rept 32\n\t" \
+                     ".rept " DR_ "\n\t" \
                      LS2_ROUND("%[a0]", "%[a1]") \
                      LS2_ROUND("%[a1]", "%[a0]") \
                      ".endr\n\t" \
@@ -534,6 +548,249 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 }
 
 // ==========================================================================================
+// The split instance: two states, tableLog 13, no 0-bit entries, and every long stream decoded as TWO HALVES by two decoders that
+// share the stream's table.  A tANS decoder that starts at a wrong bit position with wrong states falls in
+// with the true one after a few thousand symbols when a symbol replaces most of a state's bits with stream bits (9.6 of 13 on the
+// headline's strips), so part 1 starts in the middle of the stream with two states read from the bits there, part 0 at the true
+// start, and once part 0 reaches a point part 1 has passed -- same bit position, same two states, role by role -- everything part 1
+// decoded from there on is the stream's second half.
+//   * lanes 2 v, 2 v + 1 hold the two states of virtual stream v = 2 g + part of the wave's stream g: 12 state lanes a wave;
+//   * a part has its own ring (4 blocks of 32 dwords), mirror and stage (64 states): a chunk is 64 symbols, 32 rounds of the
+//     same hand-scheduled round as the unsplit instance (LS_CHUNK2_N);
+//   * the per-chunk upkeep serves both parts of a stream with one instruction each: lanes 0-31 part 0's block, lanes 32-63 part 1's;
+//   * part 0 writes true states to tok, part 1 its states to the unit's sym slab (idle between the table stage and
+//     k_dec_translate, which reads tokens [i_sync, count) from sym[j_sync + i - i_sync]).
+// Ring reach, as for LsGeom with blocks of 32 dwords: a chunk of 64 symbols takes at most 64 * 13 = 832 bits = 26 dwords; the reads
+// are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of the
+// chunk's first position, in block b, they span dwords D - 27 ... D + 1; D - 27 >= 32 b - 27 = 32 (b - 1) + 5, inside block b - 1,
+// and D + 1 inside block b + 1 at the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block b + 2 at
+// the chunk's end, which no chunk from here on reads.  The position behind the two initial states is at most 26 bits below the
+// start, so the same three blocks hold what the initial states read.
+// Meeting point: after Wc = W / 64 chunks part 1 stands at (q1, its two states), step j_sync = 64 Wc; part 0 remembers its last
+// chunk start above q1; behind the chunk loop one lane per stream steps part 0 symbol by symbol from there until its position is
+// q1 (the symbol index there may be odd: part 1's lanes are then role-swapped against the symbol parity, its output order is the
+// symbol order all the same).  The unit is split when the states agree there AND part 1 decoded count - i_sync + j_sync symbols
+// without reading below bit 0 (bitreader.go:113-120 at the stream's last symbol).  Everything else -- no meeting, a cut or
+// damaged stream -- goes to the retry list, which the unsplit instance decodes and reports as it always has.
+struct LsSplit {
+    static constexpr int TL = 13, SPW = 3, WAVES = 3;
+    static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = 7;         // blocks of 32 dwords
+    static constexpr uint32_t MIRROR = 128u * RING_BLOCKS;                  // two mirror dwords + two pad dwords
+    static constexpr uint32_t STAGE = MIRROR + 16u;                         // 64 u16 states of a chunk
+    static constexpr uint32_t PART_BYTES = STAGE + 128u;                    // 656
+    static constexpr uint32_t TAB = 2u * PART_BYTES;                        // both parts in front of the stream's table
+    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696
+    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264
+    static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
+};
+
+__global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUnit *units, const int *list, const int *count_p, int *retry_list,
+                                                                          int *retry_count, uint32_t overlap) {
+    constexpr int LS_SPW = LsSplit::SPW, LS_RBITS = LsSplit::RING_BITS, LS_DEPTH = LsSplit::DEPTH;
+    constexpr bool ZB = false;
+    constexpr uint32_t tl = LsSplit::TL, size = 1u << tl, SB = LsSplit::STREAM_BYTES, PB = LsSplit::PART_BYTES;
+    extern __shared__ uint32_t s_mem[];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_mem != 0u) return;   // layout assumes dynamic LDS at 0
+    const int n_cls = *count_p;
+    const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * LsSplit::WAVES + (int)wv) * LS_SPW);
+    if (slot0 >= n_cls) return;                                             // waves share nothing and never meet at a barrier
+    // ---- roles: lane 4 g + 2 part + k; lanes 12 .. 63 clone lane k of stream 0's part 0 (same addresses, same values) ----
+    const uint32_t k = lane & 1u;
+    const bool real = lane < 4u * LS_SPW;
+    const uint32_t g = real ? lane >> 2 : 0u, part = real ? (lane >> 1) & 1u : 0u;
+    const bool have = slot0 + (int)g < n_cls;
+    const uint32_t gs = have ? g : 0u;                                      // absent streams run on stream 0's table, on rings of zeros
+    const int unit_i = list[slot0 + (int)gs];
+    const MicUnit &u = units[unit_i];
+    const uint32_t T = have ? u.count : 0u;
+    const uint32_t bits_off = u.bits_off, len = u.comp_len - bits_off;
+    const uint32_t vbase = (wv * LS_SPW + g) * SB + part * PB;              // own ring / mirror / stage
+    const uint32_t tbase = (wv * LS_SPW + gs) * SB + LsSplit::TAB;
+    // ---- tables, as in k_dec_tans_ls: one per stream, both parts read it ----
+#pragma unroll 1
+    for (int j = 0; j < LS_SPW; j++) {
+        if (slot0 + j >= n_cls) break;
+        const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, 4 * j);
+        const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + LsSplit::TAB;
+        for (uint32_t p = lane * 4; p < size; p += 256) {
+            const uint4 e = *(const uint4 *)(dt + p);
+            const uint32_t n0 = ((e.x & 0xFFFF) + size) >> (e.x >> 16), n1 = ((e.y & 0xFFFF) + size) >> (e.y >> 16);
+            const uint32_t n2 = ((e.z & 0xFFFF) + size) >> (e.z >> 16), n3 = ((e.w & 0xFFFF) + size) >> (e.w >> 16);
+            ls_v2 v; v.x = n0 | (n1 << 16); v.y = n2 | (n3 << 16);
+            *(__attribute__((address_space(3))) ls_v2 *)(uintptr_t)(tb + p * 2) = v;
+        }
+    }
+    // ---- bit reader: grid of aligned dwords under the stream, as in k_dec_tans_ls ----
+    const uint8_t *bs = u.comp_in + bits_off;
+    const uint32_t last = bs[len - 1];                                      // non-zero: k_dec_classify
+    const uintptr_t addr = (uintptr_t)bs;
+    const uint32_t sb = (uint32_t)(addr & 3);
+    const uint64_t gaddr = (uint64_t)(addr - sb);
+    const uint32_t Lb = 8u * (len - 1) + (uint32_t)(31 - __clz(last));      // the stream's bits (below the end marker)
+    const int32_t cur0 = (int32_t)(Lb + 8u * sb);
+    const int32_t top_dw = have ? (cur0 - 1) >> 5 : -1;
+    // part 1 starts at bit pm: both parts then decode about (count + W) / 2 symbols -- part 0 covers bits [pm - Wb, Lb), Wb = W
+    // symbols' worth of bits at the stream's mean rate, part 1 [0, pm)
+    const uint32_t Wb = T ? (uint32_t)min((uint64_t)overlap * (uint64_t)Lb / (uint64_t)T, (uint64_t)Lb) : 0u;
+    const uint32_t pm = (uint32_t)(((uint64_t)Lb + (uint64_t)Wb) / 2u);
+    int32_t q = (part ? (int32_t)(pm + 8u * sb) : cur0) - 32;               // window of a round = grid bits [q, q+32)
+    const int32_t qz = (int32_t)(8u * sb) - 32;                             // q of "no bits left"
+    const uint32_t scr_cap = min(min(u.sym_cap, u.tok_cap), T) & ~63u;      // states part 1 may write (the sym slab is at least a tok slab)
+    bool s_have[LS_SPW];
+    __amdgpu_buffer_rsrc_t rs_in[LS_SPW], rs_tok[LS_SPW], rs_scr[LS_SPW];
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) {
+        const int src = 4 * j;
+        s_have[j] = slot0 + j < n_cls;
+        const uint32_t in_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ((uint32_t)((int32_t)ls_rl((uint32_t)top_dw, src) + 1)) * 4u : 0u));
+        const uint32_t tok_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? (ls_rl(T, src) / 64u) * 128u : 0u));
+        const uint32_t scr_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ls_rl(scr_cap, src) * 2u : 0u));
+        rs_in[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64(gaddr, src), 0, (int)in_bytes, 0x00020000);
+        rs_tok[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tok, src), 0, (int)tok_bytes, 0x00020000);
+        rs_scr[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.sym, src), 0, (int)scr_bytes, 0x00020000);
+    }
+    const bool hi_half = lane >= 32;                                        // upkeep: lanes 0-31 serve part 0, lanes 32-63 part 1
+    const uint32_t l32 = lane & 31u;
+    constexpr uint32_t LS_OOB = 0x7FFFFFF0u;                                // a byte offset no descriptor here reaches: the access is dropped
+    auto load_blk = [&](int j, int32_t b0, int32_t b1) -> uint32_t {      // dword l32 of block b0 | b1 of stream j, zero outside the stream
+        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], ((hi_half ? b1 : b0) * 32 + (int32_t)l32) * 4, 0, 2);
+    };
+    auto store_blk = [&](int j, int32_t b0, int32_t b1, uint32_t v) {
+        const uint32_t rb = (wv * LS_SPW + (uint32_t)j) * SB + (hi_half ? PB : 0u);
+        const uint32_t slot = (uint32_t)(hi_half ? b1 : b0) & (uint32_t)(LsSplit::RING_BLOCKS - 1);
+        *(ls_l32)(uintptr_t)(rb + (slot * 32u + l32) * 4) = v;
+        if (l32 < 2) *(ls_l32)(uintptr_t)(rb + LsSplit::MIRROR + l32 * 4 + (slot == 0u ? 0u : 8u)) = v;   // mirror | pad (an address select)
+    };
+    auto blk_of = [&](int32_t qq, int src) -> int32_t { return ((int32_t)ls_rl((uint32_t)qq, src) >> 5) >> 5; };
+    uint32_t pf[LS_SPW]; int32_t s_pf0[LS_SPW], s_pf1[LS_SPW];
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) {
+        const int32_t b0 = blk_of(q - (int32_t)(2 * tl), 4 * j), b1 = blk_of(q - (int32_t)(2 * tl), 4 * j + 2);   // block of the position BEHIND the initial states
+#pragma unroll
+        for (int dd = -1; dd < LS_DEPTH; dd++) store_blk(j, b0 - dd, b1 - dd, load_blk(j, b0 - dd, b1 - dd));
+        s_pf0[j] = b0 - LS_DEPTH; s_pf1[j] = b1 - LS_DEPTH;
+        pf[j] = load_blk(j, s_pf0[j], s_pf1[j]);                            // enters the rings at the end of the first chunk
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                                     // wave-private LDS: the writes above are in before the reads below
+    // ---- chain state ----
+    const uint32_t ringb = vbase;
+    const uint32_t stgb = vbase + LsSplit::STAGE + 2u * k;                  // stage16[r * 2 + k] = state k of round r
+    const uint32_t cb = tbase - 2u * size;
+    const uint32_t C = 31u - tl;
+    auto window = [&](int32_t qq) -> uint32_t {
+        const uint32_t a = (__builtin_amdgcn_ubfe((uint32_t)qq, 5, LS_RBITS) << 2) + ringb;
+        const uint32_t w0 = *(ls_l32)(uintptr_t)a, w1 = *(ls_l32)(uintptr_t)(a + 4);
+        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
+    };
+    auto entry = [&](uint32_t s) -> uint32_t { return *(ls_l16)(uintptr_t)(s * 2 + cb); };
+    // initial states: part 0's are the stream's, part 1's the same read at pm -- valid table indices, but guesses
+    uint32_t st = size + (window(q - (int32_t)(k * tl)) >> (32u - tl));
+    q -= (int32_t)(2 * tl);
+    const uint32_t mk1 = k ? ~0u : 0u;
+    // ---- chunks of 64 symbols per part ----
+    const uint32_t Wc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(overlap / 64u));
+    uint32_t maxT = 0;
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) if (s_have[j]) maxT = max(maxT, ls_rl(T, 4 * j));
+    const uint32_t ch_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxT / 64u + 2u));   // no part of the wave has anything to decode behind it
+    const uint32_t pl = (lane & ~3u) | 2u;                                  // part 1's first lane of this lane's stream
+    bool handed = false;
+    int32_t q1 = 0; uint32_t m_a = 0, m_b = 0;                              // the meeting point: part 1's position and its two states after Wc chunks
+    int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: part 0's last chunk start above q1, part 1's last with bits left
+    uint32_t ch = 0;
+    for (;; ch++) {
+        if (ch == Wc) {                                                     // (uniform, once)
+            q1 = __builtin_amdgcn_ds_bpermute((int)(pl << 2), q);
+            m_a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)st);
+            m_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((pl | 1u) << 2), (int)st);
+            handed = true;
+        }
+        const bool on = part ? q > qz : (!handed || q > q1);
+        if (on) { sn_q = q; sn_st = st; sn_ch = ch; }
+        if (ch >= ch_cap || (handed && !__any(on && real && have))) break;  // one wave-uniform test per chunk
+        LS_CHUNK2_N("16", "128");
+        // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) store_blk(j, s_pf0[j], s_pf1[j], pf[j]);
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) {
+            s_pf0[j] = blk_of(q, 4 * j) - LS_DEPTH; s_pf1[j] = blk_of(q, 4 * j + 2) - LS_DEPTH;
+            pf[j] = load_blk(j, s_pf0[j], s_pf1[j]);
+        }
+        {
+            uint32_t s2[LS_SPW];
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + (hi_half ? PB : 0u) + LsSplit::STAGE + l32 * 4);
+            const uint32_t off = ch * 128u + l32 * 4u;                      // (a part that runs on: its descriptor ends at what it may write)
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) {
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(hi_half ? LS_OOB : off), 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(hi_half ? off : LS_OOB), 0, 2);
+            }
+        }
+    }
+    const uint32_t ch_end = ch;                                             // chunks every part ran and stored
+    // ---- the join: one lane per stream ----
+    // the other lanes' values (all lanes take part in the permutes)
+    const uint32_t p0_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
+    const uint32_t p1_s0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)sn_st);
+    const uint32_t p1_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((pl | 1u) << 2), (int)sn_st);
+    const int32_t p1_q = __builtin_amdgcn_ds_bpermute((int)(pl << 2), sn_q);
+    const uint32_t p1_ch = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)sn_ch);
+    if (!(real && have && (lane & 3u) == 0u)) return;
+    const uint32_t *grid = (const uint32_t *)(uintptr_t)gaddr;
+    auto peek = [&](int32_t qq) -> uint32_t {                              // grid bits [qq, qq + 32), zeros outside the stream's dwords
+        const int32_t d = qq >> 5;
+        const uint32_t w0 = (d >= 0 && d <= top_dw) ? grid[d] : 0u, w1 = (d + 1 >= 0 && d + 1 <= top_dw) ? grid[d + 1] : 0u;
+        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
+    };
+    auto step = [&](uint32_t &s, int32_t &pos) {                           // one symbol: nbBits >= 1 in this class
+        const uint32_t e = entry(s), nb = (uint32_t)__builtin_clz(e) - C;
+        s = (e << nb) | (peek(pos) >> (32u - nb));
+        pos -= (int32_t)nb;
+    };
+    uint32_t outcome = MIC_SPLIT_NOT_MET, i_sync = 0;
+    const uint32_t j_sync = Wc * 64u;
+    if (handed) {
+        uint32_t s0 = sn_st, s1 = p0_s1, i = sn_ch * 64u; int32_t pos = sn_q;
+        for (int n = 0; n <= 64 && pos >= q1; n++) {
+            if (pos == q1) {
+                const uint32_t nxt = (i & 1u) ? s1 : s0, oth = (i & 1u) ? s0 : s1;
+                if (nxt == m_a && oth == m_b) { outcome = MIC_SPLIT_DONE; i_sync = i; }
+                break;
+            }
+            if (i & 1u) step(s1, pos); else step(s0, pos);
+            i++;
+        }
+    }
+    if (outcome == MIC_SPLIT_DONE) {
+        // part 0's states [0, i_sync) are in tok when i_sync lies inside its whole chunks; part 1 must hold steps [j_sync, j_end)
+        const uint64_t j_end64 = (uint64_t)T - (uint64_t)i_sync + (uint64_t)j_sync;
+        if (i_sync > (T / 64u) * 64u || j_end64 > (uint64_t)scr_cap) outcome = MIC_SPLIT_NO_ROOM;
+        else if (j_end64 > (uint64_t)ch_end * 64u) outcome = MIC_SPLIT_BAD_COUNT;   // (the loop ended: part 1 was out of bits with symbols to go)
+        else {
+            const uint32_t j_end = (uint32_t)j_end64, js = p1_ch * 64u;
+            // the over-read rule at the stream's last symbol: part 1's position behind step j_end - 1, from its last chunk start with bits left
+            if (j_end > js) {
+                if (j_end - js > 64u) outcome = MIC_SPLIT_BAD_COUNT;       // (the chunk behind the snapshot started without bits)
+                else {
+                    uint32_t s0 = p1_s0, s1 = p1_s1; int32_t pos = p1_q;
+                    for (uint32_t j = js; j < j_end; j++) { if (j & 1u) step(s1, pos); else step(s0, pos); }
+                    if (pos < qz) outcome = MIC_SPLIT_BAD_COUNT;
+                }
+            }
+        }
+    }
+    MicUnit &uo = units[unit_i];
+    uo.split[0] = outcome; uo.split[1] = i_sync; uo.split[2] = j_sync;
+    if (outcome == MIC_SPLIT_DONE) {
+        uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
+        uo.ntok = T; uo.walk_ok = 2;                                        // tok and sym hold STATES: k_dec_translate joins and translates them
+    } else retry_list[atomicAdd(retry_count, 1)] = unit_i;
+}
+
+// ==========================================================================================
 // States -> symbols, and the RLE header walk.  One group of 256 threads per unit that k_dec_tans_ls decoded (walk_ok == 2):
 // the unit's symbol table (tableSymbol of each state, <= 16 KiB) sits in LDS, waves 1-3 stream the states through it in tiles
 // of 1536 (16 bytes in, eight LDS look-ups, 16 bytes out, in place) and leave each translated tile in LDS as well, where wave 0
@@ -569,6 +826,11 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
         for (uint32_t i = tid; i < size / 2; i += TR_THREADS) ((uint32_t *)s_sym)[i] = src[i];
     }
     uint16_t *tok = u.tok;
+    // a split unit (k_dec_tans_ls_split): states [i_sync, ntok) still lie in the scratch slab, from j_sync on; they are read from
+    // there and written, translated, to tok -- everything behind this pass sees an ordinary tok
+    const bool sp = TRTL == 13 && u.split[0] == MIC_SPLIT_DONE;
+    const uint32_t sp_i = u.split[1], sp_j = u.split[2];
+    const uint16_t *scr = u.sym;
     const bool frame = u.mode == 0 && u.seg != nullptr;
     // (a length-prefixed RLE stream, walk_mode 1 -- a whole WaveletV2 frame -- is one unit of millions of tokens: walking it here would
     //  be one wave's work per frame; it is marked walk_ok = 3 and walked in parts by k_rle_walk_parts, mic_wavelet.hip)
@@ -588,8 +850,21 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
         uint16_t *tile = s_tile[it & 1];
         if (wave != 0) {
             const uint32_t l = (tid - 64) * 8, i0 = base + l;
-            if (i0 + 8 <= tile_end) {
-                const tr_v4 v = __builtin_nontemporal_load((const tr_v4 *)(tok + i0));
+            if (i0 + 8 <= tile_end && (!sp || i0 + 8 <= sp_i || i0 >= sp_i)) {
+                tr_v4 v;
+                if (!sp || i0 + 8 <= sp_i) v = __builtin_nontemporal_load((const tr_v4 *)(tok + i0));
+                else {
+                    // the second half of a split unit: eight states from the scratch slab, 2-byte aligned only -- five aligned dwords and
+                    // a funnel shift by the source's parity (the u16 in front of and behind the eight are inside the slab: j_sync >= 64,
+                    // and the slab is 64 tokens longer than what part 1 may write)
+                    const uint32_t sj = sp_j + (i0 - sp_i);
+                    const uint32_t *d = (const uint32_t *)(scr + (sj & ~1u));
+                    const uint32_t sh = (sj & 1u) * 16u;
+                    const uint32_t d0 = __builtin_nontemporal_load(d), d1 = __builtin_nontemporal_load(d + 1), d2 = __builtin_nontemporal_load(d + 2),
+                                   d3 = __builtin_nontemporal_load(d + 3), d4 = __builtin_nontemporal_load(d + 4);
+                    v.x = __builtin_amdgcn_alignbit(d1, d0, sh); v.y = __builtin_amdgcn_alignbit(d2, d1, sh);
+                    v.z = __builtin_amdgcn_alignbit(d3, d2, sh); v.w = __builtin_amdgcn_alignbit(d4, d3, sh);
+                }
                 tr_v4 o;
                 o.x = (uint32_t)s_sym[v.x & smask] | ((uint32_t)s_sym[(v.x >> 16) & smask] << 16);
                 o.y = (uint32_t)s_sym[v.y & smask] | ((uint32_t)s_sym[(v.y >> 16) & smask] << 16);
@@ -598,7 +873,9 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
                 *(tr_v4 *)(tok + i0) = o;
                 *(tr_v4 *)(tile + l) = o;
             } else {
-                for (uint32_t i = i0; i < tile_end; i++) { const uint16_t t = s_sym[tok[i] & smask]; tok[i] = t; tile[i - base] = t; }
+                for (uint32_t i = i0; i < min(i0 + 8u, tile_end); i++) {   // the tile's tail, or the eight tokens that straddle i_sync
+                    const uint16_t t = s_sym[((sp && i >= sp_i) ? scr[sp_j + (i - sp_i)] : tok[i]) & smask]; tok[i] = t; tile[i - base] = t;
+                }
             }
         }
         __syncthreads();                                                    // tile `it` is in LDS; the walker is done with tile it - 1
@@ -726,16 +1003,20 @@ __global__ void __launch_bounds__(TRW_THREADS) k_dec_translate_wide(MicUnit *uni
     if (tid == 0) u.walk_ok = 3u;                                           // translated; the headers are k_rle_walk_parts's
 }
 
+template <int N, bool ZB, int TL> static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *count, hipStream_t stream);
 template <int N, bool ZB, int TL>
 static void launch_ls_class(MicUnit *d_units, int n, const int *d_list, const int *d_count, hipStream_t stream, uint32_t cls_mask) {
     constexpr int cls = (TL <= 12 ? 4 : TL - 13) * 6 + (N == 2 ? 0 : N == 4 ? 2 : 4) + (ZB ? 1 : 0);
     if (!((cls_mask >> cls) & 1u)) return;                                  // (the session has not seen a stream of this class lately: mic_launch.h)
+    launch_ls_list<N, ZB, TL>(d_units, n, d_list + (size_t)cls * (size_t)n, d_count + cls, stream);
+}
+template <int N, bool ZB, int TL>
+static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *count, hipStream_t stream) {
     constexpr int per = LsGeom<TL>::WAVES * LsGeom<TL>::SPW;
     static MicPerDeviceOnce once;
     once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls<N, ZB, TL>, hipFuncAttributeMaxDynamicSharedMemorySize, LsGeom<TL>::LDS); });
     const unsigned groups = (unsigned)((n + per - 1) / per);
-    hipLaunchKernelGGL((k_dec_tans_ls<N, ZB, TL>), dim3(groups), dim3(64 * LsGeom<TL>::WAVES), LsGeom<TL>::LDS, stream, d_units,
-                       d_list + (size_t)cls * (size_t)n, d_count + cls);
+    hipLaunchKernelGGL((k_dec_tans_ls<N, ZB, TL>), dim3(groups), dim3(64 * LsGeom<TL>::WAVES), LsGeom<TL>::LDS, stream, d_units, list, count);
 }
 template <int TL>
 static void launch_ls_tl(MicUnit *d_units, int n, const int *d_list, const int *d_count, hipStream_t stream, bool skip_first, uint32_t m) {
@@ -747,10 +1028,28 @@ static void launch_ls_tl(MicUnit *d_units, int n, const int *d_list, const int *
     if constexpr (TL < 16) launch_ls_class<8, true, TL>(d_units, n, d_list, d_count, stream, m);
 }
 
-// d_list: LS_CLASSES * n ints, d_count: LS_CLASSES ints (session workspace)
-void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, hipStream_t stream, MicTimer *t, uint32_t cls_mask) {
+// d_list: MIC_CLS_LISTS * n ints, d_count: MIC_CLS_LISTS ints (session workspace)
+void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, hipStream_t stream, MicTimer *t, uint32_t cls_mask, const MicSplitCfg *cfg) {
+    const MicSplitCfg sc = cfg ? *cfg : MicSplitCfg{};
+    const bool split = (cls_mask & MIC_CLS_SPLIT) != 0;
     if (t) t->mark("k_dec_classify");
-    hipLaunchKernelGGL(k_dec_classify, dim3(1), dim3(1024), 0, stream, d_units, n, d_list, d_count);
+    hipLaunchKernelGGL(k_dec_classify, dim3(1), dim3(1024), 0, stream, d_units, n, d_list, d_count, split ? 1 : 0, sc);
+    if (split) {
+        // the split instance first (the longest kernel of the chain), then what it hands back: an empty list in the normal case, and
+        // the unsplit instance's blocks leave at once.  (Without the retry launch k_dec_tans_gl would take those units: slower, not wrong.)
+        constexpr int per = LsSplit::WAVES * LsSplit::SPW;
+        static MicPerDeviceOnce once;
+        once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_split, hipFuncAttributeMaxDynamicSharedMemorySize, LsSplit::LDS); });
+        const unsigned groups = (unsigned)((n + per - 1) / per);
+        if (t) t->mark("k_dec_tans_ls_split<13>");
+        hipLaunchKernelGGL(k_dec_tans_ls_split, dim3(groups), dim3(64 * LsSplit::WAVES), LsSplit::LDS, stream, d_units,
+                           d_list + (size_t)LS_SPLIT_LIST * (size_t)n, d_count + LS_SPLIT_LIST, d_list + (size_t)LS_RETRY_LIST * (size_t)n,
+                           d_count + LS_RETRY_LIST, sc.overlap & ~63u);
+        if (cls_mask & MIC_CLS_RETRY) {
+            if (t) t->mark("k_dec_tans_ls<2,false,13> retry");
+            launch_ls_list<2, false, 13>(d_units, n, d_list + (size_t)LS_RETRY_LIST * (size_t)n, d_count + LS_RETRY_LIST, stream);
+        }
+    }
     if (t) t->mark("k_dec_tans_ls<2,false,13>");
     launch_ls_class<2, false, 13>(d_units, n, d_list, d_count, stream, cls_mask);
     if (t) t->mark("k_dec_tans_ls<other,13>");
@@ -763,7 +1062,7 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
     launch_ls_tl<16>(d_units, n, d_list, d_count, stream, false, cls_mask);
     if (t) t->mark("k_dec_translate");
     // classes 0-5: tableLog 13, 24-29: tableLog <= 12 -> the 16 KiB symbol table; 6-23: tableLog 14..16 -> the 128 KiB one
-    if (cls_mask & 0x3F00003Fu) hipLaunchKernelGGL(k_dec_translate<13>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);
+    if (cls_mask & (0x3F00003Fu | MIC_CLS_SPLIT)) hipLaunchKernelGGL(k_dec_translate<13>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);
     if (cls_mask & 0x00FFFFC0u) {
         hipLaunchKernelGGL(k_dec_translate_wide, dim3((unsigned)n), dim3(TRW_THREADS), 0, stream, d_units);   // (marks its units walk_ok 3: the next launch skips them)
         hipLaunchKernelGGL(k_dec_translate<16>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);

@@ -71,10 +71,18 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
 // d_cls: per-session scratch of MIC_CLS_INTS(n) ints for the per-class unit lists of the lane-per-state tANS decoder (mic_decode_ls.hip)
 #define MIC_CLS_HEAD 32
 #define MIC_CLS_CLASSES 30
-#define MIC_CLS_INTS(n) (MIC_CLS_HEAD + MIC_CLS_CLASSES * (size_t)(n))
+#define MIC_CLS_LISTS 32                // the classes' lists, the split list and the retry list (mic_decode_ls.hip)
+#define MIC_CLS_INTS(n) (MIC_CLS_HEAD + MIC_CLS_LISTS * (size_t)(n))
+// cls_mask beside the 30 classes: the split instance of class 0 is launched (and k_dec_classify fills its list); the unsplit
+// instance is launched behind it over what it hands back
+#define MIC_CLS_SPLIT 0x40000000u
+#define MIC_CLS_RETRY 0x80000000u
 // pred_mask: predictor classes by frame width (mic_pred_bit); cls_mask: bit c = lane-per-state class c of mic_decode_ls.hip (MIC_CLS_CLASSES of them)
-void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant, MicTimer *t, int *d_cls, uint32_t pred_mask = ~0u, uint32_t cls_mask = ~0u);
-void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, hipStream_t stream, MicTimer *t, uint32_t cls_mask = ~0u);
+// split: which class-0 units the split instance takes (nullptr: MicSplitCfg's defaults)
+void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant, MicTimer *t, int *d_cls, uint32_t pred_mask = ~0u, uint32_t cls_mask = ~0u,
+                       const MicSplitCfg *split = nullptr);
+void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, hipStream_t stream, MicTimer *t, uint32_t cls_mask = ~0u,
+                            const MicSplitCfg *split = nullptr);
 // d_cap: bytes of d_dst -- a batch whose streams do not fit is left alone (dst_off[n], the total, says so)
 void mic_launch_pack(const MicUnit *d_units, int n, uint64_t *d_off, uint8_t *d_dst, uint64_t d_cap, hipStream_t stream, MicTimer *t);
 // PICA (mic_pica.hip).  _bounds: row costs (d_cost: `rows` entries, the sum of d_tab[].rows) and strip boundaries (d_starts: the sum of
@@ -109,6 +117,11 @@ __host__ __device__ inline int mic_dec_cls(uint32_t flavour, uint32_t tl, uint32
     const uint32_t ns = flavour == 108 ? 8u : flavour;
     if (!(ns == 2 || ns == 4 || ns == 8) || tl < MIC_MIN_TABLELOG || tl > MIC_MAX_TABLELOG || (tl == 16 && zero_bits)) return -1;
     return (tl <= 12 ? 4 : (int)tl - 13) * 6 + (ns == 2 ? 0 : ns == 4 ? 2 : 4) + (zero_bits ? 1 : 0);
+}
+// the units of class 0 that go to the split instance (k_dec_classify; learn_classes, mic_api.hip)
+__host__ __device__ inline bool mic_split_gate(const MicUnit &u, const MicSplitCfg &cfg) {
+    return u.flavour == 2 && u.table_log == 13 && !u.zero_bits && mic_sym_ceiling(u, u.count) == u.count && u.count >= cfg.min_tokens &&
+           u.count >= 128u && 128ull * (uint64_t)(u.comp_len - u.bits_off) >= (uint64_t)cfg.min_bits16 * (uint64_t)u.count;
 }
 void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream);
 // gap removal (mic_gap.hip): encode -- map and compact histogram behind the tokeniser, token remap in front of the tANS encoder, the

@@ -234,7 +234,7 @@ int mic2_batch_decode_units(mic_hip_session *s, const Mic2DecUnit *u, int nb, in
         else { m.mode = 0; m.px_out = u[i].out; pred_mask |= mic_pred_bit(m.w); }
     }
     rc = s->run_decode(mic_hip_session::FlagSlab::Clear, [&] {
-        mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p, pred_mask, s->dec_classes.mask());
+        mic_launch_decode((MicUnit *)s->units.p, nb, s->stream, s->variant, &s->timer, (int *)s->cls.p, pred_mask, s->dec_classes.mask(), &s->split_cfg);
         if (any_sym) {
             mic_launch_rle_expand((MicUnit *)s->units.p, nb, s->stream, 3);
             hipLaunchKernelGGL(k_mic2_check_units, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s->stream, (MicUnit *)s->units.p, nb);

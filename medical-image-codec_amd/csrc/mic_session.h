@@ -201,6 +201,7 @@ struct mic_hip_session {
         uint32_t mask() const { if (!any) return ~0u; uint32_t m = 0; for (int c = 0; c < 32; c++) if (age[c] < kClsKeep) m |= 1u << c; return m; }
         void learn(uint32_t seen) { any = true; for (int c = 0; c < 32; c++) age[c] = ((seen >> c) & 1u) ? 0 : (uint8_t)std::min<int>(age[c] + 1, 255); }
     } dec_classes, enc_classes;
+    MicSplitCfg split_cfg;                  // which two-state units the split decode instance takes (mic_hip_debug_split_config)
     // The per-unit 65536-bin histograms are ZERO between calls: the encode chain leaves them so (k_enc_hist_clean re-zeroes what a
     // unit's tokeniser counted), and nothing else writes them.  hist_zero_units = leading unit slabs known to be zero (0 after a
     // reallocation, after a failed launch).  The invariant is tied to the ALLOCATION (DevBuf::gen),

@@ -1,0 +1,36 @@
+"""Diagnostic: what the split instance of the two-state tANS chain (k_dec_tans_ls_split) makes of the headline step's strips --
+per step the count of units by MicUnit.split outcome (not tried / split / handed back and why), and the spread of i_sync.
+usage: tools/split_outcomes.py [frames=288] [steps=20]"""
+import ctypes as C, os, sys, importlib, collections
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry
+import torch
+mic = entry.load_package()
+synth = importlib.import_module("medical_image_codec_amd.synth")
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 288
+STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+W, H, S = 2577, 2048, 8
+NAMES = {0: "not tried", 1: "split", 2: "handed back: no meeting", 3: "handed back: count", 4: "handed back: no room"}
+L = mic.lib()
+L.mic_hip_debug_split.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+sh = (H + S - 1) // S
+units = mic.Session.make_units([(b * W * H + y0 * W, W, min(H, y0 + sh) - y0, 4095, 2) for b in range(B) for y0 in range(0, H, sh)])
+sess = mic.Session(B * S, W * sh)
+total = collections.Counter()
+for step in range(STEPS):
+    d_px = synth.xr_like_batch_torch(B, cols=W, rows=H, depth=12, seed0=1 + 1000 * step, noise=synth.XR_NOISE_PUBLISHED_RATIO, device=torch.device("cuda:0"))
+    d_out = torch.empty_like(d_px)
+    sess.encode_enqueue(d_px.data_ptr(), units); d_blobs, offs, st, ns = sess.encode_finish()
+    sess.decode_enqueue(d_blobs, offs, units, d_out.data_ptr()); dst = sess.decode_finish()
+    assert (st == 0).all() and (dst == 0).all() and torch.equal(d_out, d_px)
+    seen, isync = collections.Counter(), []
+    for i in range(B * S):
+        out = (C.c_uint32 * 3)()
+        assert L.mic_hip_debug_split(sess._h, i, out) == 0
+        seen[int(out[0])] += 1
+        if out[0] == 1: isync.append(int(out[1]))
+    total += seen
+    print(f"step {step}: " + ", ".join(f"{NAMES[k]} {v}" for k, v in sorted(seen.items())) +
+          (f"; i_sync {min(isync)} .. {max(isync)}" if isync else ""), flush=True)
+print("all steps: " + ", ".join(f"{NAMES[k]} {v}" for k, v in sorted(total.items())))
