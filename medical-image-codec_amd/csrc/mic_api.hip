@@ -694,6 +694,22 @@ int mic_hip_debug_split_config(mic_hip_session *s, uint32_t min_tokens, uint32_t
     s->dec_classes = mic_hip_session::ClsMemory{};
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): the four-part instance's record of unit i after a decode's *_finish -- out[0]: MIC_SPLIT_*,
+// out[1..3]: I_1, I_2, I_3 (token indices of the joins), out[4]: W, out[5]: R (0: not a four-part unit), out[6]: the failing boundary
+int mic_hip_debug_split4(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    const MicUnit &u = s->h_units[(size_t)i];
+    out[0] = u.split[0]; out[1] = u.split4[0]; out[2] = u.split4[1]; out[3] = u.split4[2]; out[4] = u.split[2]; out[5] = u.split4[3]; out[6] = u.split4[4];
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug setter (not in the public header): the length from which on a unit that passes the split gate goes to the four-part instance
+// (MicSplitCfg::min_tokens4); a zero keeps the value.  The session forgets its launch masks, as above.
+int mic_hip_debug_split4_config(mic_hip_session *s, uint32_t min_tokens4) try {
+    if (!s) return MIC_ERR_ARGS;
+    if (min_tokens4) s->split_cfg.min_tokens4 = min_tokens4;
+    s->dec_classes = mic_hip_session::ClsMemory{};
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py
 // holds its own restatement against it, value by value)
 int mic_hip_debug_dec_cls(uint32_t flavour, uint32_t table_log, uint32_t zero_bits) { return mic_dec_cls(flavour, table_log, zero_bits); }

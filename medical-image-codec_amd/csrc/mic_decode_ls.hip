@@ -87,9 +87,12 @@ __device__ __forceinline__ uint64_t ls_rl64(uint64_t v, int lane) {
 // List LS_SPLIT_LIST holds the units of class 0 (two states, tableLog 13, no 0-bit entries) that k_dec_tans_ls_split takes when
 // `split` is set (the launcher's: that kernel is launched) -- whole streams of at least min_tokens tokens and min_bits16 / 16 bits
 // per token; list LS_RETRY_LIST is filled by that kernel with what it hands back, its count starts at zero here.
+// List LS_SPLIT4_LIST holds those of them that have at least min_tokens4 tokens: k_dec_tans_ls_split4 takes them, and hands back to
+// the same retry list.
 #define LS_SPLIT_LIST MIC_CLS_CLASSES
 #define LS_RETRY_LIST (MIC_CLS_CLASSES + 1)
-#define LS_LISTS (MIC_CLS_CLASSES + 1)             // lists this kernel fills
+#define LS_SPLIT4_LIST (MIC_CLS_CLASSES + 2)
+#define LS_LISTS MIC_CLS_LISTS                     // lists this kernel counts (the retry list takes no unit here)
 __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, int *list, int *count, int split, MicSplitCfg cfg) {
     __shared__ uint32_t s_w[16][LS_LISTS];
     __shared__ uint32_t s_base[LS_LISTS];
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, in
                     if (u.comp_in[u.comp_len - 1] == 0) u.status = MICD_ERR_CORRUPT;
                     else {
                         cls = mic_dec_cls(flav, tl, u.zero_bits);
-                        if (cls == 0 && split && mic_split_gate(u, cfg)) cls = LS_SPLIT_LIST;
+                        if (cls == 0 && split && mic_split_gate(u, cfg)) cls = u.count >= cfg.min_tokens4 ? LS_SPLIT4_LIST : LS_SPLIT_LIST;
                     }
                 }
             }
@@ -572,6 +575,17 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // symbol order all the same).  The unit is split when the states agree there AND part 1 decoded count - i_sync + j_sync symbols
 // without reading below bit 0 (bitreader.go:113-120 at the stream's last symbol).  Everything else -- no meeting, a cut or
 // damaged stream -- goes to the retry list, which the unsplit instance decodes and reports as it always has.
+// LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop of the split instances, summed over the chunks,
+// into dbg[] of the wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over,
+// snapshot and ballot; dbg[5] chunks, dbg[6] parts per stream
+#ifdef LS_STAMP
+#define LS_ST_DECL uint64_t stamp[5] = { 0, 0, 0, 0, 0 }, t_prev = __builtin_amdgcn_s_memtime()
+#define LS_ST_OUT(parts_) do { if (lane == 0) { MicUnit &ud = units[unit_i]; for (int i_ = 0; i_ < 5; i_++) ud.dbg[i_] = (uint32_t)(stamp[i_] >> 4); \
+                                                ud.dbg[5] = ch_end; ud.dbg[6] = (parts_); } } while (0)
+#else
+#define LS_ST_DECL do { } while (0)
+#define LS_ST_OUT(parts_) do { } while (0)
+#endif
 struct LsSplit {
     static constexpr int TL = 13, SPW = 3, WAVES = 3;
     static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = 7;         // blocks of 32 dwords
@@ -699,6 +713,7 @@ __global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUn
     int32_t q1 = 0; uint32_t m_a = 0, m_b = 0;                              // the meeting point: part 1's position and its two states after Wc chunks
     int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: part 0's last chunk start above q1, part 1's last with bits left
     uint32_t ch = 0;
+    LS_ST_DECL;
     for (;; ch++) {
         if (ch == Wc) {                                                     // (uniform, once)
             q1 = __builtin_amdgcn_ds_bpermute((int)(pl << 2), q);
@@ -709,15 +724,19 @@ __global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUn
         const bool on = part ? q > qz : (!handed || q > q1);
         if (on) { sn_q = q; sn_st = st; sn_ch = ch; }
         if (ch >= ch_cap || (handed && !__any(on && real && have))) break;  // one wave-uniform test per chunk
+        LS_T(4);
         LS_CHUNK2_N("16", "128");
+        LS_T(0);
         // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
 #pragma unroll
         for (int j = 0; j < LS_SPW; j++) store_blk(j, s_pf0[j], s_pf1[j], pf[j]);
+        LS_T(1);
 #pragma unroll
         for (int j = 0; j < LS_SPW; j++) {
             s_pf0[j] = blk_of(q, 4 * j) - LS_DEPTH; s_pf1[j] = blk_of(q, 4 * j + 2) - LS_DEPTH;
             pf[j] = load_blk(j, s_pf0[j], s_pf1[j]);
         }
+        LS_T(2);
         {
             uint32_t s2[LS_SPW];
 #pragma unroll
@@ -729,8 +748,10 @@ __global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUn
                 __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(hi_half ? off : LS_OOB), 0, 2);
             }
         }
+        LS_T(3);
     }
     const uint32_t ch_end = ch;                                             // chunks every part ran and stored
+    LS_ST_OUT(2u);
     // ---- the join: one lane per stream ----
     // the other lanes' values (all lanes take part in the permutes)
     const uint32_t p0_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
@@ -791,6 +812,288 @@ __global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUn
 }
 
 // ==========================================================================================
+// The four-part instance: the same class, every stream decoded as FOUR parts by four decoders on the stream's one table (24 of a
+// wave's 64 lanes hold a state).  Part 0 starts at the true start and writes true states to tok; parts 1-3 start further down
+// the stream with guessed states and write to three regions of R tokens of the unit's sym slab.  Part p >= 1 hands its position
+// and states after W symbols to part p - 1, which runs until it has passed that position; behind the chunk loop the three
+// boundaries are joined by a lane of the upper part each, side by side.
+//   * lane 8 g + 2 part + k holds state k of part `part` of the wave's stream g; lanes 24-63 clone lane k of stream 0's part 0;
+//   * a part has its own ring (4 blocks of 16 dwords), mirror and stage (32 states): a chunk is 32 symbols, 16 rounds of the
+//     hand-scheduled round (LS_CHUNK2_N("8", "64"));
+//   * the per-chunk upkeep serves the four parts of a stream with one instruction each: lanes 16 p ... 16 p + 15 part p's block.
+// Ring reach, as for LsSplit with blocks of 16 dwords: a chunk of 32 symbols takes at most 32 * 13 = 416 bits = 13 dwords; the
+// reads are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of
+// the chunk's first position, in block b, they span dwords D - 14 ... D + 1; D - 14 >= 16 b - 14 = 16 (b - 1) + 2, inside block
+// b - 1, and D + 1 inside block b + 1 at the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block
+// b + 2 at the chunk's end, which no chunk from here on reads.  The position behind the two initial states is at most 26 bits
+// below the start, so the same three blocks hold what the initial states read.
+// Where the parts start: Lb the stream's bits, Wb = W symbols' worth of bits at the mean rate, x = (Lb + 3 Wb) / 4; part p >= 1
+// starts at bit (4 - p) x - (3 - p) Wb, so that every part covers about x bits, W symbols of them under its upper neighbour.
+// Joins: part p (0 .. 2) steps from its last chunk start above part p + 1's hand-over position q until its position is q; the
+// parts have met when its two states there are part p + 1's, role by role (part p's own step parity against part p + 1 at its
+// step W, which is even); e_p is part p's step index there (p >= 1: at least W).  One lane per stream turns them into token
+// indices, I_1 = e_0, I_p+1 = I_p + e_p - W: token i of [I_p, I_p+1) is part p's step W + i - I_p (I_4 = count).  Checked there:
+// I_1 inside part 0's whole chunks, every part's last step inside its region, and part 3's count by the over-read rule
+// (bitreader.go:113-120: it must decode count - I_3 + W steps without reading below bit 0).  The first boundary that fails
+// names the outcome, and the whole unit goes to the retry list.
+struct LsSplit4 {
+    static constexpr int TL = 13, SPW = 3, WAVES = 3, PARTS = 4;
+    static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = 6;         // blocks of 16 dwords
+    static constexpr uint32_t MIRROR = 64u * RING_BLOCKS;                   // two mirror dwords + two pad dwords
+    static constexpr uint32_t STAGE = MIRROR + 16u;                         // 32 u16 states of a chunk
+    static constexpr uint32_t PART_BYTES = STAGE + 64u;                     // 336
+    static constexpr uint32_t TAB = (uint32_t)PARTS * PART_BYTES;           // the four parts in front of the stream's table
+    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 728
+    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 552
+    static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
+};
+
+__global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(MicUnit *units, const int *list, const int *count_p, int *retry_list,
+                                                                           int *retry_count, uint32_t overlap) {
+    constexpr int LS_SPW = LsSplit4::SPW, LS_RBITS = LsSplit4::RING_BITS, LS_DEPTH = LsSplit4::DEPTH;
+    constexpr bool ZB = false;
+    constexpr uint32_t tl = LsSplit4::TL, size = 1u << tl, SB = LsSplit4::STREAM_BYTES, PB = LsSplit4::PART_BYTES;
+    extern __shared__ uint32_t s_mem[];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_mem != 0u) return;   // layout assumes dynamic LDS at 0
+    const int n_cls = *count_p;
+    const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * LsSplit4::WAVES + (int)wv) * LS_SPW);
+    if (slot0 >= n_cls) return;                                             // waves share nothing and never meet at a barrier
+    // ---- roles: lane 8 g + 2 part + k; lanes 24 .. 63 clone lane k of stream 0's part 0 (same addresses, same values) ----
+    const uint32_t k = lane & 1u;
+    const bool real = lane < 8u * LS_SPW;
+    const uint32_t g = real ? lane >> 3 : 0u, part = real ? (lane >> 1) & 3u : 0u;
+    const bool have = slot0 + (int)g < n_cls;
+    const uint32_t gs = have ? g : 0u;                                      // absent streams run on stream 0's table, on rings of zeros
+    const int unit_i = list[slot0 + (int)gs];
+    const MicUnit &u = units[unit_i];
+    const uint32_t T = have ? u.count : 0u;
+    const uint32_t bits_off = u.bits_off, len = u.comp_len - bits_off;
+    const uint32_t vbase = (wv * LS_SPW + g) * SB + part * PB;              // own ring / mirror / stage
+    const uint32_t tbase = (wv * LS_SPW + gs) * SB + LsSplit4::TAB;
+    // ---- tables, as in k_dec_tans_ls: one per stream, all parts read it ----
+#pragma unroll 1
+    for (int j = 0; j < LS_SPW; j++) {
+        if (slot0 + j >= n_cls) break;
+        const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, 8 * j);
+        const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + LsSplit4::TAB;
+        for (uint32_t p = lane * 4; p < size; p += 256) {
+            const uint4 e = *(const uint4 *)(dt + p);
+            const uint32_t n0 = ((e.x & 0xFFFF) + size) >> (e.x >> 16), n1 = ((e.y & 0xFFFF) + size) >> (e.y >> 16);
+            const uint32_t n2 = ((e.z & 0xFFFF) + size) >> (e.z >> 16), n3 = ((e.w & 0xFFFF) + size) >> (e.w >> 16);
+            ls_v2 v; v.x = n0 | (n1 << 16); v.y = n2 | (n3 << 16);
+            *(__attribute__((address_space(3))) ls_v2 *)(uintptr_t)(tb + p * 2) = v;
+        }
+    }
+    // ---- bit reader: grid of aligned dwords under the stream, as in k_dec_tans_ls ----
+    const uint8_t *bs = u.comp_in + bits_off;
+    const uint32_t last = bs[len - 1];                                      // non-zero: k_dec_classify
+    const uintptr_t addr = (uintptr_t)bs;
+    const uint32_t sb = (uint32_t)(addr & 3);
+    const uint64_t gaddr = (uint64_t)(addr - sb);
+    const uint32_t Lb = 8u * (len - 1) + (uint32_t)(31 - __clz(last));      // the stream's bits (below the end marker)
+    const int32_t cur0 = (int32_t)(Lb + 8u * sb);
+    const int32_t top_dw = have ? (cur0 - 1) >> 5 : -1;
+    // part p >= 1 starts at bit (4 - p) x - (3 - p) Wb (Wb <= Lb, so Wb <= x <= Lb and the starts lie in [x, Lb], in falling order)
+    const uint32_t Wb = T ? (uint32_t)min((uint64_t)overlap * (uint64_t)Lb / (uint64_t)T, (uint64_t)Lb) : 0u;
+    const uint32_t x = (uint32_t)(((uint64_t)Lb + 3ull * (uint64_t)Wb) / 4u);
+    const uint32_t pm = (uint32_t)((uint64_t)(4u - part) * (uint64_t)x - (uint64_t)(3u - part) * (uint64_t)Wb);
+    int32_t q = (part ? (int32_t)(pm + 8u * sb) : cur0) - 32;               // window of a round = grid bits [q, q+32)
+    const int32_t qz = (int32_t)(8u * sb) - 32;                             // q of "no bits left"
+    const uint32_t R = ((min(u.sym_cap, u.tok_cap) / 3u) & ~31u);           // tokens of a scratch region (the sym slab is at least a tok slab)
+    bool s_have[LS_SPW];
+    __amdgpu_buffer_rsrc_t rs_in[LS_SPW], rs_tok[LS_SPW], rs_scr[LS_SPW];
+    uint32_t s_R[LS_SPW];
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) {
+        const int src = 8 * j;
+        s_have[j] = slot0 + j < n_cls;
+        s_R[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ls_rl(R, src) : 0u));
+        const uint32_t in_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ((uint32_t)((int32_t)ls_rl((uint32_t)top_dw, src) + 1)) * 4u : 0u));
+        const uint32_t tok_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? (ls_rl(T, src) / 32u) * 64u : 0u));
+        const uint32_t scr_bytes = s_R[j] * 6u;                             // three regions of R states
+        rs_in[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64(gaddr, src), 0, (int)in_bytes, 0x00020000);
+        rs_tok[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tok, src), 0, (int)tok_bytes, 0x00020000);
+        rs_scr[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.sym, src), 0, (int)scr_bytes, 0x00020000);
+    }
+    const uint32_t up = lane >> 4, l16 = lane & 15u;                        // upkeep: lanes 16 p .. 16 p + 15 serve part p
+    constexpr uint32_t LS_OOB = 0x7FFFFFF0u;                                // a byte offset no descriptor here reaches: the access is dropped
+    auto blk_of = [&](int j, int32_t qq) -> int32_t {                      // block of the position of this lane's part of stream j (all lanes take part)
+        return (__builtin_amdgcn_ds_bpermute((int)((8u * (uint32_t)j + 2u * up) << 2), qq) >> 5) >> 4;
+    };
+    auto load_blk = [&](int j, int32_t b) -> uint32_t {                    // dword l16 of block b of stream j, zero outside the stream
+        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], (b * 16 + (int32_t)l16) * 4, 0, 2);
+    };
+    auto store_blk = [&](int j, int32_t b, uint32_t v) {
+        const uint32_t rb = (wv * LS_SPW + (uint32_t)j) * SB + up * PB;
+        const uint32_t slot = (uint32_t)b & (uint32_t)(LsSplit4::RING_BLOCKS - 1);
+        *(ls_l32)(uintptr_t)(rb + (slot * 16u + l16) * 4) = v;
+        if (l16 < 2) *(ls_l32)(uintptr_t)(rb + LsSplit4::MIRROR + l16 * 4 + (slot == 0u ? 0u : 8u)) = v;   // mirror | pad (an address select)
+    };
+    uint32_t pf[LS_SPW]; int32_t pfb[LS_SPW];
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) {
+        const int32_t b = blk_of(j, q - (int32_t)(2 * tl));                 // block of the position BEHIND the initial states
+#pragma unroll
+        for (int dd = -1; dd < LS_DEPTH; dd++) store_blk(j, b - dd, load_blk(j, b - dd));
+        pfb[j] = b - LS_DEPTH;
+        pf[j] = load_blk(j, pfb[j]);                                        // enters the rings at the end of the first chunk
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                                     // wave-private LDS: the writes above are in before the reads below
+    // ---- chain state ----
+    const uint32_t ringb = vbase;
+    const uint32_t stgb = vbase + LsSplit4::STAGE + 2u * k;                 // stage16[r * 2 + k] = state k of round r
+    const uint32_t cb = tbase - 2u * size;
+    const uint32_t C = 31u - tl;
+    auto window = [&](int32_t qq) -> uint32_t {
+        const uint32_t a = (__builtin_amdgcn_ubfe((uint32_t)qq, 5, LS_RBITS) << 2) + ringb;
+        const uint32_t w0 = *(ls_l32)(uintptr_t)a, w1 = *(ls_l32)(uintptr_t)(a + 4);
+        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
+    };
+    auto entry = [&](uint32_t s) -> uint32_t { return *(ls_l16)(uintptr_t)(s * 2 + cb); };
+    // initial states: part 0's are the stream's, the others' the same read at their starts -- valid table indices, but guesses
+    uint32_t st = size + (window(q - (int32_t)(k * tl)) >> (32u - tl));
+    q -= (int32_t)(2 * tl);
+    const uint32_t mk1 = k ? ~0u : 0u;
+    // ---- chunks of 32 symbols per part ----
+    const uint32_t Wc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(overlap / 32u));
+    uint32_t maxT = 0;
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) if (s_have[j]) maxT = max(maxT, ls_rl(T, 8 * j));
+    const uint32_t ch_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxT / 32u + 2u));   // no part of the wave has anything to decode behind it
+    const uint32_t own_cap = T / 32u + 2u;                                  // ... and no part of this stream: what a part does is its stream's business alone
+    const uint32_t nl = ((lane & ~1u) + 2u) & 63u;                          // the next part's first lane (part 3 has none: it stops at the stream's end)
+    // the scratch regions: byte offset of this lane's dword of chunk 0 (part 0's lanes aim out of range), and the same for tok
+    uint32_t scr0[LS_SPW];
+#pragma unroll
+    for (int j = 0; j < LS_SPW; j++) scr0[j] = up ? (up - 1u) * s_R[j] * 2u + l16 * 4u : LS_OOB;
+    const uint32_t tok0 = up ? LS_OOB : l16 * 4u;
+    bool handed = false;
+    int32_t qn = 0; uint32_t m_a = 0, m_b = 0;                              // the next part's position and its two states after Wc chunks
+    int32_t qlim = part == 3u ? qz : INT32_MIN;                             // a part is on above it: nothing up to the hand-over, then qn; part 3: bits left
+    int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: the last chunk start above qn; part 3: the last with bits left
+    uint32_t ch = 0;
+    LS_ST_DECL;
+    for (;; ch++) {
+        if (ch == Wc) {                                                     // (uniform, once)
+            qn = __builtin_amdgcn_ds_bpermute((int)(nl << 2), q);
+            m_a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nl << 2), (int)st);
+            m_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((nl | 1u) << 2), (int)st);
+            qlim = part == 3u ? qz : qn;
+            handed = true;
+        }
+        const bool on = (ch < own_cap) & (q > qlim);                        // (selects, no branch)
+        sn_q = on ? q : sn_q; sn_st = on ? st : sn_st; sn_ch = on ? ch : sn_ch;
+        if (ch >= ch_cap || !__any(on & real & have)) break;                // one wave-uniform test per chunk
+        LS_T(4);
+        LS_CHUNK2_N("8", "64");
+        LS_T(0);
+        // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) store_blk(j, pfb[j], pf[j]);
+        LS_T(1);
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) pfb[j] = blk_of(j, q) - LS_DEPTH;
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) pf[j] = load_blk(j, pfb[j]);
+        LS_T(2);
+        {
+            uint32_t s2[LS_SPW];
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + LsSplit4::STAGE + l16 * 4);
+            const uint32_t off = ch * 64u;                                  // (part 0 runs on into a descriptor that ends at its last whole chunk)
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) {
+                const bool fits = (ch + 1u) * 32u <= s_R[j];                // (a part that runs on past its region must not write into its neighbour's)
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, 2);   // (out of range + off < 2^32: still out of range)
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + off : LS_OOB), 0, 2);
+            }
+        }
+        LS_T(3);
+    }
+    const uint32_t ch_end = ch;                                             // chunks every part ran and stored
+    LS_ST_OUT(4u);
+    // ---- the joins: boundary p | p + 1 by lane 0 of part p, the three of a stream side by side ----
+    const uint32_t sn_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
+    const uint32_t *grid = (const uint32_t *)(uintptr_t)gaddr;
+    auto peek = [&](int32_t qq) -> uint32_t {                              // grid bits [qq, qq + 32), zeros outside the stream's dwords
+        const int32_t d = qq >> 5;
+        const uint32_t w0 = (d >= 0 && d <= top_dw) ? grid[d] : 0u, w1 = (d + 1 >= 0 && d + 1 <= top_dw) ? grid[d + 1] : 0u;
+        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
+    };
+    auto step = [&](uint32_t &s, int32_t &pos) {                           // one symbol: nbBits >= 1 in this class
+        const uint32_t e = entry(s), nb = (uint32_t)__builtin_clz(e) - C;
+        s = (e << nb) | (peek(pos) >> (32u - nb));
+        pos -= (int32_t)nb;
+    };
+    const uint32_t W = Wc * 32u;
+    uint32_t met = 0, e_p = 0;
+    if (real && have && handed && Wc < own_cap && k == 0u && part < 3u) {  // (Wc >= own_cap: a longer neighbour kept the loop going up to the hand-over)
+        uint32_t s0 = sn_st, s1 = sn_s1, i = sn_ch * 32u; int32_t pos = sn_q;
+        const uint32_t i_min = part ? W : 0u;                               // (a part's own first W steps are not its output)
+        for (int n = 0; n <= 32 && pos >= qn; n++) {
+            if (pos == qn) {
+                const uint32_t nxt = (i & 1u) ? s1 : s0, oth = (i & 1u) ? s0 : s1;
+                if (i >= i_min && nxt == m_a && oth == m_b) { met = 1u; e_p = i; }
+                break;
+            }
+            if (i & 1u) step(s1, pos); else step(s0, pos);
+            i++;
+        }
+    }
+    // ---- one lane per stream: the other boundaries' results and part 3's snapshot (all lanes take part in the permutes) ----
+    const uint32_t l0 = lane & ~7u;
+    const uint32_t met1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u) << 2), (int)met), e_1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u) << 2), (int)e_p);
+    const uint32_t met2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 4u) << 2), (int)met), e_2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 4u) << 2), (int)e_p);
+    const uint32_t p3_s0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), (int)sn_st);
+    const uint32_t p3_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 7u) << 2), (int)sn_st);
+    const int32_t p3_q = __builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), sn_q);
+    const uint32_t p3_ch = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), (int)sn_ch);
+    if (!(real && have && (lane & 7u) == 0u)) return;
+    // boundary b = 1 .. 3: met, then room -- I_1 inside tok's whole chunks, part b - 1's last step e inside its region; then the
+    // stream's end (4): part 3's room and its count
+    uint32_t outcome = MIC_SPLIT_DONE, fail = 0, I[3] = { 0, 0, 0 };
+    {
+        const uint32_t mets[3] = { met, met1, met2 }, es[3] = { e_p, e_1, e_2 };
+        uint32_t at = 0;
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (outcome != MIC_SPLIT_DONE) break;
+            if (!mets[b]) { outcome = MIC_SPLIT_NOT_MET; fail = (uint32_t)b + 1u; break; }
+            at = b ? at + es[b] - W : es[0];
+            I[b] = at;
+            if (b ? es[b] > R : at > (T / 32u) * 32u) { outcome = MIC_SPLIT_NO_ROOM; fail = (uint32_t)b + 1u; }
+        }
+    }
+    if (outcome == MIC_SPLIT_DONE) {
+        fail = 4u;
+        if (I[2] > T) outcome = MIC_SPLIT_BAD_COUNT;                         // (the parts in front hold more than the stream's symbols)
+        else {
+            const uint32_t j_end = T - I[2] + W, js = p3_ch * 32u;          // part 3 must hold steps [W, j_end)
+            if (j_end > R) outcome = MIC_SPLIT_NO_ROOM;
+            else if (j_end > ch_end * 32u) outcome = MIC_SPLIT_BAD_COUNT;   // (the loop ended: part 3 was out of bits with symbols to go)
+            else if (j_end > js) {
+                // the over-read rule at the stream's last symbol: part 3's position behind step j_end - 1, from its last chunk start with bits left
+                if (j_end - js > 32u) outcome = MIC_SPLIT_BAD_COUNT;       // (the chunk behind the snapshot started without bits)
+                else {
+                    uint32_t s0 = p3_s0, s1 = p3_s1; int32_t pos = p3_q;
+                    for (uint32_t j = js; j < j_end; j++) { if (j & 1u) step(s1, pos); else step(s0, pos); }
+                    if (pos < qz) outcome = MIC_SPLIT_BAD_COUNT;
+                }
+            }
+        }
+        if (outcome == MIC_SPLIT_DONE) fail = 0u;
+    }
+    MicUnit &uo = units[unit_i];
+    uo.split[0] = outcome; uo.split[1] = I[0]; uo.split[2] = W;
+    uo.split4[0] = I[0]; uo.split4[1] = I[1]; uo.split4[2] = I[2]; uo.split4[3] = R; uo.split4[4] = fail;
+    if (outcome == MIC_SPLIT_DONE) {
+        uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
+        uo.ntok = T; uo.walk_ok = 2;                                        // tok and sym hold STATES: k_dec_translate joins and translates them
+    } else retry_list[atomicAdd(retry_count, 1)] = unit_i;
+}
+
+// ==========================================================================================
 // States -> symbols, and the RLE header walk.  One group of 256 threads per unit that k_dec_tans_ls decoded (walk_ok == 2):
 // the unit's symbol table (tableSymbol of each state, <= 16 KiB) sits in LDS, waves 1-3 stream the states through it in tiles
 // of 1536 (16 bytes in, eight LDS look-ups, 16 bytes out, in place) and leave each translated tile in LDS as well, where wave 0
@@ -828,8 +1131,16 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
     uint16_t *tok = u.tok;
     // a split unit (k_dec_tans_ls_split): states [i_sync, ntok) still lie in the scratch slab, from j_sync on; they are read from
     // there and written, translated, to tok -- everything behind this pass sees an ordinary tok
+    // A four-part unit (k_dec_tans_ls_split4: split4[3] = R != 0) has three such joins: tokens [I_p, I_p+1) are the states
+    // sym[(p - 1) R + W + i - I_p].  Either way: up to three bounds b1 <= b2 <= b3 (none: ~0) and, for the tokens from bound p on,
+    // the offset o_p from token index to scratch index (modulo 2^32)
     const bool sp = TRTL == 13 && u.split[0] == MIC_SPLIT_DONE;
-    const uint32_t sp_i = u.split[1], sp_j = u.split[2];
+    const uint32_t sp_R = u.split4[3], sp_W = u.split[2];
+    const bool sp4 = sp && sp_R != 0u;
+    const uint32_t b1 = sp ? u.split[1] : ~0u, b2 = sp4 ? u.split4[1] : ~0u, b3 = sp4 ? u.split4[2] : ~0u;
+    const uint32_t o1 = sp_W - b1, o2 = sp_R + sp_W - b2, o3 = 2u * sp_R + sp_W - b3;
+    auto seg_of = [&](uint32_t i) -> uint32_t { return (uint32_t)(i >= b1) + (uint32_t)(i >= b2) + (uint32_t)(i >= b3); };
+    auto scr_of = [&](uint32_t p, uint32_t i) -> uint32_t { return i + (p == 1u ? o1 : p == 2u ? o2 : o3); };
     const uint16_t *scr = u.sym;
     const bool frame = u.mode == 0 && u.seg != nullptr;
     // (a length-prefixed RLE stream, walk_mode 1 -- a whole WaveletV2 frame -- is one unit of millions of tokens: walking it here would
@@ -850,14 +1161,15 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
         uint16_t *tile = s_tile[it & 1];
         if (wave != 0) {
             const uint32_t l = (tid - 64) * 8, i0 = base + l;
-            if (i0 + 8 <= tile_end && (!sp || i0 + 8 <= sp_i || i0 >= sp_i)) {
+            const uint32_t pseg = seg_of(i0);
+            if (i0 + 8 <= tile_end && pseg == seg_of(i0 + 7u)) {
                 tr_v4 v;
-                if (!sp || i0 + 8 <= sp_i) v = __builtin_nontemporal_load((const tr_v4 *)(tok + i0));
+                if (pseg == 0u) v = __builtin_nontemporal_load((const tr_v4 *)(tok + i0));
                 else {
-                    // the second half of a split unit: eight states from the scratch slab, 2-byte aligned only -- five aligned dwords and
-                    // a funnel shift by the source's parity (the u16 in front of and behind the eight are inside the slab: j_sync >= 64,
-                    // and the slab is 64 tokens longer than what part 1 may write)
-                    const uint32_t sj = sp_j + (i0 - sp_i);
+                    // behind a join of a split unit: eight states from the scratch slab, 2-byte aligned only -- five aligned dwords and
+                    // a funnel shift by the source's parity (the u16 in front of and behind the eight are inside the slab: W >= 32,
+                    // and the slab is 64 tokens longer than what the parts may write)
+                    const uint32_t sj = scr_of(pseg, i0);
                     const uint32_t *d = (const uint32_t *)(scr + (sj & ~1u));
                     const uint32_t sh = (sj & 1u) * 16u;
                     const uint32_t d0 = __builtin_nontemporal_load(d), d1 = __builtin_nontemporal_load(d + 1), d2 = __builtin_nontemporal_load(d + 2),
@@ -873,8 +1185,9 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
                 *(tr_v4 *)(tok + i0) = o;
                 *(tr_v4 *)(tile + l) = o;
             } else {
-                for (uint32_t i = i0; i < min(i0 + 8u, tile_end); i++) {   // the tile's tail, or the eight tokens that straddle i_sync
-                    const uint16_t t = s_sym[((sp && i >= sp_i) ? scr[sp_j + (i - sp_i)] : tok[i]) & smask]; tok[i] = t; tile[i - base] = t;
+                for (uint32_t i = i0; i < min(i0 + 8u, tile_end); i++) {   // the tile's tail, or the eight tokens that straddle a join (or two)
+                    const uint32_t p = seg_of(i);
+                    const uint16_t t = s_sym[(p ? scr[scr_of(p, i)] : tok[i]) & smask]; tok[i] = t; tile[i - base] = t;
                 }
             }
         }
@@ -1041,6 +1354,14 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
         static MicPerDeviceOnce once;
         once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_split, hipFuncAttributeMaxDynamicSharedMemorySize, LsSplit::LDS); });
         const unsigned groups = (unsigned)((n + per - 1) / per);
+        // the four-part instance in front of it (the same streams per group, so the same grid): the longest units first
+        static MicPerDeviceOnce once4;
+        once4.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_split4, hipFuncAttributeMaxDynamicSharedMemorySize, LsSplit4::LDS); });
+        static_assert(LsSplit4::WAVES * LsSplit4::SPW == per, "one grid for both split instances");
+        if (t) t->mark("k_dec_tans_ls_split4<13>");
+        hipLaunchKernelGGL(k_dec_tans_ls_split4, dim3(groups), dim3(64 * LsSplit4::WAVES), LsSplit4::LDS, stream, d_units,
+                           d_list + (size_t)LS_SPLIT4_LIST * (size_t)n, d_count + LS_SPLIT4_LIST, d_list + (size_t)LS_RETRY_LIST * (size_t)n,
+                           d_count + LS_RETRY_LIST, sc.overlap & ~63u);
         if (t) t->mark("k_dec_tans_ls_split<13>");
         hipLaunchKernelGGL(k_dec_tans_ls_split, dim3(groups), dim3(64 * LsSplit::WAVES), LsSplit::LDS, stream, d_units,
                            d_list + (size_t)LS_SPLIT_LIST * (size_t)n, d_count + LS_SPLIT_LIST, d_list + (size_t)LS_RETRY_LIST * (size_t)n,

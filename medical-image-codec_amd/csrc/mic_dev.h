@@ -44,6 +44,8 @@ struct MicSplitCfg {
     uint32_t min_tokens = 131072u;     // shorter units are not worth a second decoder's start-up
     uint32_t overlap = 32768u;         // W: symbols the second half decodes before its state is taken as the meeting point (a multiple of 64)
     uint32_t min_bits16 = 144u;        // G: 16 x the mean bits per token from which on a wrong start is forgotten inside W
+    uint32_t min_tokens4 = 262144u;    // units that pass the gate above and are at least this long go to the four-part instance
+                                       // (k_dec_tans_ls_split4); mic_hip_debug_split4_config sets it, mic_hip_debug_split_config does not
 };
 // MicUnit.enc_kernel: 1 + the bit index of the MIC_ENC_CLS_* class (mic_launch.h) whose k_enc_tans_wg instance gave the unit its tANS
 // verdict (1 .. 7), or MIC_ENC_BY_SERIAL; MIC_ENC_HANDED is set beside it when the two-state instance had handed the unit over first
@@ -167,6 +169,10 @@ struct MicUnit {
     uint32_t split[3];        // decode: MIC_SPLIT_* outcome of the split two-state chain, i_sync, j_sync (tokens [i_sync, count) are the states
                               // sym[j_sync + i - i_sync] until k_dec_translate has moved them); read by mic_hip_debug_split, predicted by
                               // tests/tans_split_model.py.  Cleared with the other results
+    uint32_t split4[5];       // decode, a unit of the four-part instance (k_dec_tans_ls_split4): I_1, I_2, I_3 -- tokens [I_p, I_p+1) are the
+                              // states sym[(p - 1) R + W + i - I_p], I_4 = count --, R (tokens per scratch region; 0: not a four-part unit) and
+                              // the failing boundary (1 .. 3: the join of parts p - 1 and p, 4: the stream's end, 0: none); split[] holds the
+                              // outcome, I_1 and W.  Read by mic_hip_debug_split4, predicted by tests/tans_split4_model.py
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }

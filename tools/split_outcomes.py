@@ -1,5 +1,6 @@
-"""Diagnostic: what the split instance of the two-state tANS chain (k_dec_tans_ls_split) makes of the headline step's strips --
-per step the count of units by MicUnit.split outcome (not tried / split / handed back and why), and the spread of i_sync.
+"""Diagnostic: what the split instances of the two-state tANS chain (k_dec_tans_ls_split4, k_dec_tans_ls_split) make of the headline
+step's strips -- per step the count of units by instance and MicUnit.split outcome (not tried / split / handed back and why, for
+four-part units with the boundary that failed), and the spread of the first join.
 usage: tools/split_outcomes.py [frames=288] [steps=20]"""
 import ctypes as C, os, sys, importlib, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,24 +14,36 @@ STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 W, H, S = 2577, 2048, 8
 NAMES = {0: "not tried", 1: "split", 2: "handed back: no meeting", 3: "handed back: count", 4: "handed back: no room"}
 L = mic.lib()
-L.mic_hip_debug_split.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+L.mic_hip_debug_split4.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 sh = (H + S - 1) // S
 units = mic.Session.make_units([(b * W * H + y0 * W, W, min(H, y0 + sh) - y0, 4095, 2) for b in range(B) for y0 in range(0, H, sh)])
 sess = mic.Session(B * S, W * sh)
 total = collections.Counter()
+
+
+def name(key):
+    parts, outcome, fail = key
+    if not outcome:
+        return NAMES[0]
+    return f"{parts} parts {NAMES[outcome]}" + (f" at boundary {fail}" if fail else "")
+
+
 for step in range(STEPS):
     d_px = synth.xr_like_batch_torch(B, cols=W, rows=H, depth=12, seed0=1 + 1000 * step, noise=synth.XR_NOISE_PUBLISHED_RATIO, device=torch.device("cuda:0"))
     d_out = torch.empty_like(d_px)
     sess.encode_enqueue(d_px.data_ptr(), units); d_blobs, offs, st, ns = sess.encode_finish()
     sess.decode_enqueue(d_blobs, offs, units, d_out.data_ptr()); dst = sess.decode_finish()
     assert (st == 0).all() and (dst == 0).all() and torch.equal(d_out, d_px)
-    seen, isync = collections.Counter(), []
+    seen, first = collections.Counter(), []
     for i in range(B * S):
-        out = (C.c_uint32 * 3)()
-        assert L.mic_hip_debug_split(sess._h, i, out) == 0
-        seen[int(out[0])] += 1
-        if out[0] == 1: isync.append(int(out[1]))
+        out = (C.c_uint32 * 8)()                                        # outcome, I_1, I_2, I_3, W, R (0: a two-part unit), failing boundary
+        assert L.mic_hip_debug_split4(sess._h, i, out) == 0
+        four = out[5] != 0
+        seen[(4 if four else 2, int(out[0]), int(out[6]))] += 1
+        if out[0] == 1: first.append(int(out[1]) if four else None)
+    first = [v for v in first if v is not None]
     total += seen
-    print(f"step {step}: " + ", ".join(f"{NAMES[k]} {v}" for k, v in sorted(seen.items())) +
-          (f"; i_sync {min(isync)} .. {max(isync)}" if isync else ""), flush=True)
-print("all steps: " + ", ".join(f"{NAMES[k]} {v}" for k, v in sorted(total.items())))
+    print(f"step {step}: " + ", ".join(f"{name(k)} {v}" for k, v in sorted(seen.items())) +
+          (f"; I_1 {min(first)} .. {max(first)}" if first else ""), flush=True)
+print("all steps: " + ", ".join(f"{name(k)} {v}" for k, v in sorted(total.items())))
+print("handed back: %d of %d" % (sum(v for k, v in total.items() if k[1] >= 2), sum(total.values())))

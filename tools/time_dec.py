@@ -1,5 +1,6 @@
 """Timing of the decode kernels on the bench workload, ignoring decode status (for ablation builds whose output is wrong).
-usage: python tools/time_dec.py [frames] [nstates]"""
+usage: python tools/time_dec.py [frames] [nstates] [noise]   (noise: a number, or "published" for the headline's level -- the
+streams the split instances take; default: xr_like's own)"""
 import os, sys, importlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,8 @@ synth = importlib.import_module("medical_image_codec_amd.synth")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 288
 NS = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 W, H, S = 2577, 2048, 8
-base = [synth.xr_like(cols=W, rows=H, depth=12, seed=1 + i) for i in range(4)]
+NOISE = {} if len(sys.argv) <= 3 else {"noise": synth.XR_NOISE_PUBLISHED_RATIO if sys.argv[3] == "published" else float(sys.argv[3])}
+base = [synth.xr_like(cols=W, rows=H, depth=12, seed=1 + i, **NOISE) for i in range(4)]
 host = np.stack([base[i % 4] for i in range(B)])
 d_px = torch.from_numpy(host.view(np.int16)).cuda()
 d_out = torch.empty_like(d_px)
@@ -38,5 +40,9 @@ L.mic_hip_debug_unit.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
 for i in (0, 9, 900):
     L.mic_hip_debug_unit(sess._h, i, out)
     d = [out[16 + k] * 16 for k in range(5)]
-    if d[4]:
+    if out[16 + 6]:                                                     # a split instance's stamps: five phases, chunks, parts per stream
+        n = out[16 + 5]
+        print("unit", i, "%d parts, cycles per chunk: rounds %.0f  ring stores %.0f  loads %.0f  state stores %.0f  hand-over/snapshot/ballot %.0f  "
+              "sum %.0f  (chunks %d)" % tuple([out[16 + 6]] + [d[k] / n for k in range(5)] + [sum(d) / n, n]))
+    elif d[4]:
         print("unit", i, "cycles per chunk: rounds %.0f  ring stores %.0f  loads %.0f  state stores %.0f  (chunks %d)" % tuple([d[k] / (d[4] / 16) for k in range(4)] + [d[4] // 16]))
