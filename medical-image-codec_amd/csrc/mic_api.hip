@@ -677,8 +677,8 @@ int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {
     for (int k = 0; k < 16; k++) out8[16 + k] = u.dbg[k];
     return MIC_OK;
 } MIC_ABI_CATCH
-// debug probe (not in the public header): what the split two-state decode instance made of unit i after a decode's *_finish --
-// out[0]: MIC_SPLIT_* (mic_dev.h: 0 not tried, 1 split, 2 .. fell back and why), out[1]: i_sync, out[2]: j_sync
+// debug probe (not in the public header): what a split two-state decode instance made of unit i after a decode's *_finish --
+// out[0]: MIC_SPLIT_* (mic_dev.h: 0 not tried, 1 split, 2 .. fell back and why), out[1]: i_sync (I_1), out[2]: j_sync (W)
 int mic_hip_debug_split(mic_hip_session *s, int i, uint32_t *out) try {
     if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
     for (int k = 0; k < 3; k++) out[k] = s->h_units[(size_t)i].split[k];
@@ -695,11 +695,13 @@ int mic_hip_debug_split_config(mic_hip_session *s, uint32_t min_tokens, uint32_t
     return MIC_OK;
 } MIC_ABI_CATCH
 // debug probe (not in the public header): the four-part instance's record of unit i after a decode's *_finish -- out[0]: MIC_SPLIT_*,
-// out[1..3]: I_1, I_2, I_3 (token indices of the joins), out[4]: W, out[5]: R (0: not a four-part unit), out[6]: the failing boundary
+// out[1..3]: I_1, I_2, I_3 (token indices of the joins), out[4]: W, out[5]: R (0: not a four-part unit), out[6]: the failing boundary;
+// of any other unit out[1..3], out[5] and out[6] are 0
 int mic_hip_debug_split4(mic_hip_session *s, int i, uint32_t *out) try {
     if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
-    const MicUnit &u = s->h_units[(size_t)i];
-    out[0] = u.split[0]; out[1] = u.split4[0]; out[2] = u.split4[1]; out[3] = u.split4[2]; out[4] = u.split[2]; out[5] = u.split4[3]; out[6] = u.split4[4];
+    const uint32_t *r = s->h_units[(size_t)i].split;
+    const uint32_t m = r[7] == 4u ? ~0u : 0u;
+    out[0] = r[0]; out[1] = r[1] & m; out[2] = r[3] & m; out[3] = r[4] & m; out[4] = r[2]; out[5] = r[5] & m; out[6] = r[6] & m;
     return MIC_OK;
 } MIC_ABI_CATCH
 // debug setter (not in the public header): the length from which on a unit that passes the split gate goes to the four-part instance

@@ -84,11 +84,11 @@ __device__ __forceinline__ uint64_t ls_rl64(uint64_t v, int lane) {
 // N-state streams (rANS-8 decodes as 8-state), + 6 per table-size class (tableLog <= 13, 14, 15, 16); 1-state streams, very long
 // streams and tableLog-16 tables with 0-bit entries are left to the kernels of mic_decode.hip.
 // One group; the stream checks that need the blob (empty bitstream, zero end byte: bitreader.go:33-38) are made here.
-// List LS_SPLIT_LIST holds the units of class 0 (two states, tableLog 13, no 0-bit entries) that k_dec_tans_ls_split takes when
+// List LS_SPLIT_LIST holds the units of class 0 (two states, tableLog 13, no 0-bit entries) that k_dec_tans_ls_parts<2> takes when
 // `split` is set (the launcher's: that kernel is launched) -- whole streams of at least min_tokens tokens and min_bits16 / 16 bits
 // per token; list LS_RETRY_LIST is filled by that kernel with what it hands back, its count starts at zero here.
-// List LS_SPLIT4_LIST holds those of them that have at least min_tokens4 tokens: k_dec_tans_ls_split4 takes them, and hands back to
-// the same retry list.
+// List LS_SPLIT4_LIST holds those of them that have at least min_tokens4 tokens: k_dec_tans_ls_parts<4> takes them, and hands back
+// to the same retry list.
 #define LS_SPLIT_LIST MIC_CLS_CLASSES
 #define LS_RETRY_LIST (MIC_CLS_CLASSES + 1)
 #define LS_SPLIT4_LIST (MIC_CLS_CLASSES + 2)
@@ -360,8 +360,8 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     // a whole chunk: 64 rounds.  The prologue looks up, stages the first state, reads the three dwords at the chunk's first position
     // and takes round 0's window from their upper pair; round 0's tail takes round 1's from the same three.
     // (a macro, not a lambda: clang does not capture through asm operands in a generic lambda)
-    // DR_ double rounds, LIM_ = 4 * rounds: the stage offset behind which a round neither looks up nor reads (the split kernel's
-    // chunk is 32 rounds: LS_CHUNK2_N("16", "128"))
+    // DR_ double rounds, LIM_ = 4 * rounds: the stage offset behind which a round neither looks up nor reads (the split instances'
+    // chunks are 32 and 16 rounds: LS_CHUNK2_N("16", "128"), LS_CHUNK2_N("8", "64"))
 #define LS_CHUNK2() LS_CHUNK2_N("32", "256")
 #define LS_CHUNK2_N(DR_, LIM_) do { \
         uint32_t e, c, cp, m, hi, pre, at, a0, a1, lo, hh; \
@@ -551,33 +551,43 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 }
 
 // ==========================================================================================
-// The split instance: two states, tableLog 13, no 0-bit entries, and every long stream decoded as TWO HALVES by two decoders that
-// share the stream's table.  A tANS decoder that starts at a wrong bit position with wrong states falls in
-// with the true one after a few thousand symbols when a symbol replaces most of a state's bits with stream bits (9.6 of 13 on the
-// headline's strips), so part 1 starts in the middle of the stream with two states read from the bits there, part 0 at the true
-// start, and once part 0 reaches a point part 1 has passed -- same bit position, same two states, role by role -- everything part 1
-// decoded from there on is the stream's second half.
-//   * lanes 2 v, 2 v + 1 hold the two states of virtual stream v = 2 g + part of the wave's stream g: 12 state lanes a wave;
-//   * a part has its own ring (4 blocks of 32 dwords), mirror and stage (64 states): a chunk is 64 symbols, 32 rounds of the
-//     same hand-scheduled round as the unsplit instance (LS_CHUNK2_N);
-//   * the per-chunk upkeep serves both parts of a stream with one instruction each: lanes 0-31 part 0's block, lanes 32-63 part 1's;
-//   * part 0 writes true states to tok, part 1 its states to the unit's sym slab (idle between the table stage and
-//     k_dec_translate, which reads tokens [i_sync, count) from sym[j_sync + i - i_sync]).
-// Ring reach, as for LsGeom with blocks of 32 dwords: a chunk of 64 symbols takes at most 64 * 13 = 832 bits = 26 dwords; the reads
-// are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of the
-// chunk's first position, in block b, they span dwords D - 27 ... D + 1; D - 27 >= 32 b - 27 = 32 (b - 1) + 5, inside block b - 1,
-// and D + 1 inside block b + 1 at the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block b + 2 at
-// the chunk's end, which no chunk from here on reads.  The position behind the two initial states is at most 26 bits below the
-// start, so the same three blocks hold what the initial states read.
-// Meeting point: after Wc = W / 64 chunks part 1 stands at (q1, its two states), step j_sync = 64 Wc; part 0 remembers its last
-// chunk start above q1; behind the chunk loop one lane per stream steps part 0 symbol by symbol from there until its position is
-// q1 (the symbol index there may be odd: part 1's lanes are then role-swapped against the symbol parity, its output order is the
-// symbol order all the same).  The unit is split when the states agree there AND part 1 decoded count - i_sync + j_sync symbols
-// without reading below bit 0 (bitreader.go:113-120 at the stream's last symbol).  Everything else -- no meeting, a cut or
-// damaged stream -- goes to the retry list, which the unsplit instance decodes and reports as it always has.
-// LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop of the split instances, summed over the chunks,
-// into dbg[] of the wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over,
-// snapshot and ballot; dbg[5] chunks, dbg[6] parts per stream
+// The split instances: two states, tableLog 13, no 0-bit entries, and every long stream decoded as PARTS (two or four) parts by as
+// many decoders that share the stream's table.  A tANS decoder that starts at a wrong bit position with wrong
+// states falls in with the true one after a few thousand symbols when a symbol replaces most of a state's bits with stream bits
+// (9.6 of 13 on the headline's strips).  So part 0 starts at the true start and writes true states to tok; part p >= 1 starts
+// further down the stream with two states read from the bits there and writes to region p - 1 (R tokens each) of the unit's sym
+// slab, idle between the table stage and k_dec_translate.  Part p >= 1 hands its position and states after W symbols to part
+// p - 1, which runs until it has passed that position; once it reaches it with the same two states, role by role, everything
+// part p decoded from there on is the stream's.
+//   * lane 2 PARTS g + 2 part + k holds state k of part `part` of the wave's stream g (12 or 24 state lanes a wave); the other
+//     lanes clone lane k of stream 0's part 0 (same addresses, same values);
+//   * a part has its own ring (4 blocks of B = 64 / PARTS dwords), mirror and stage: a chunk is 128 / PARTS symbols of the same
+//     hand-scheduled round as the unsplit instance (LS_CHUNK2_N);
+//   * the per-chunk upkeep serves the parts of a stream with one instruction each: lanes B p ... B p + B - 1 part p's block; one
+//     ds_bpermute per stream brings every upkeep lane its part's position.
+// Ring reach, as for LsGeom with blocks of B dwords: a chunk of 2 B symbols takes at most 2 B * 13 bits = 13 B / 16 < B dwords; the
+// reads are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of the
+// chunk's first position, in block b, they span dwords D - 13 B / 16 - 1 ... D + 1 (B = 32: D - 27, B = 16: D - 14);
+// D - 13 B / 16 - 1 >= B b - 13 B / 16 - 1 = B (b - 1) + 3 B / 16 - 1 (+ 5, + 2), inside block b - 1, and D + 1 inside block b + 1 at
+// the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block b + 2 at the chunk's end, which no chunk
+// from here on reads.  The position behind the two initial states is at most 26 bits below the start, so the same three blocks
+// hold what the initial states read.
+// Where the parts start: Lb the stream's bits, Wb = W symbols' worth of bits at the mean rate, x = (Lb + (PARTS - 1) Wb) / PARTS;
+// part p >= 1 starts at bit (PARTS - p) x - (PARTS - 1 - p) Wb, so that every part covers about x bits, W symbols of them under its
+// upper neighbour (two parts: part 1 starts at x = (Lb + Wb) / 2).
+// Joins: behind the chunk loop lane 0 of part p < PARTS - 1 steps part p symbol by symbol from its last chunk start above part
+// p + 1's hand-over position q until its position is q, the PARTS - 1 joins of a stream side by side; the parts have met when its
+// two states there are part p + 1's, role by role (part p's own step parity against part p + 1 at its step W, which is even: with
+// an odd step index the lower part's lanes are role-swapped against the symbol parity, its output order is the symbol order all
+// the same); e_p is part p's step index there (p >= 1: at least W).  One lane per stream turns them into token indices, I_1 = e_0,
+// I_p+1 = I_p + e_p - W: token i of [I_p, I_p+1) is part p's step W + i - I_p (I_PARTS = count).  Checked there: I_1 inside part
+// 0's whole chunks, every part's last step inside its region, and the last part's count by the over-read rule (bitreader.go:113-120:
+// it must decode count - I_last + W steps without reading below bit 0).  The first boundary that fails names the outcome, and the
+// whole unit -- no meeting, no room, a cut or damaged stream -- goes to the retry list, which the unsplit instance decodes and
+// reports as it always has.
+// LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop, summed over the chunks, into dbg[] of the
+// wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over, snapshot and ballot;
+// dbg[5] chunks, dbg[6] parts per stream
 #ifdef LS_STAMP
 #define LS_ST_DECL uint64_t stamp[5] = { 0, 0, 0, 0, 0 }, t_prev = __builtin_amdgcn_s_memtime()
 #define LS_ST_OUT(parts_) do { if (lane == 0) { MicUnit &ud = units[unit_i]; for (int i_ = 0; i_ < 5; i_++) ud.dbg[i_] = (uint32_t)(stamp[i_] >> 4); \
@@ -586,33 +596,46 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 #define LS_ST_DECL do { } while (0)
 #define LS_ST_OUT(parts_) do { } while (0)
 #endif
-struct LsSplit {
+template <int PARTS> struct LsParts {
+    static_assert(PARTS == 2 || PARTS == 4, "eight parts do not fit the sym slab (DESIGN.md section 4)");
     static constexpr int TL = 13, SPW = 3, WAVES = 3;
-    static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = 7;         // blocks of 32 dwords
-    static constexpr uint32_t MIRROR = 128u * RING_BLOCKS;                  // two mirror dwords + two pad dwords
-    static constexpr uint32_t STAGE = MIRROR + 16u;                         // 64 u16 states of a chunk
-    static constexpr uint32_t PART_BYTES = STAGE + 128u;                    // 656
-    static constexpr uint32_t TAB = 2u * PART_BYTES;                        // both parts in front of the stream's table
-    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696
-    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264
+    static constexpr int CHUNK = 128 / PARTS;                               // symbols of a chunk of one part: 64 | 32
+    static constexpr int BLK = 64 / PARTS, BLK_SHIFT = PARTS == 2 ? 5 : 4;  // dwords of a ring block = upkeep lanes of a part: 32 | 16
+    static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = BLK_SHIFT + 2;
+    static constexpr uint32_t MIRROR = 4u * BLK * RING_BLOCKS;              // two mirror dwords + two pad dwords
+    static constexpr uint32_t STAGE = MIRROR + 16u;                         // CHUNK u16 states of a chunk
+    static constexpr uint32_t PART_BYTES = STAGE + 2u * CHUNK;              // 656 | 336
+    static constexpr uint32_t TAB = (uint32_t)PARTS * PART_BYTES;           // the parts in front of the stream's table
+    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696 | 17 728
+    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264 | 159 552
     static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
+    // R, the tokens of one of the PARTS - 1 scratch regions, in whole chunks.  Recorded, and every NO_ROOM outcome depends on it, so
+    // each instance keeps its rule: two parts' one region is the slab, clamped by the stream's length (part 1 never has to hold
+    // more); four parts' is a third of the slab whatever the stream's length (the sym slab is at least a tok slab)
+    static __device__ __forceinline__ uint32_t region(uint32_t sym_cap, uint32_t tok_cap, uint32_t T) {
+        const uint32_t slab = min(sym_cap, tok_cap);
+        return (PARTS == 2 ? min(slab, T) : slab / (uint32_t)(PARTS - 1)) & ~(uint32_t)(CHUNK - 1);
+    }
 };
 
-__global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUnit *units, const int *list, const int *count_p, int *retry_list,
-                                                                          int *retry_count, uint32_t overlap) {
-    constexpr int LS_SPW = LsSplit::SPW, LS_RBITS = LsSplit::RING_BITS, LS_DEPTH = LsSplit::DEPTH;
+template <int PARTS>
+__global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_parts(MicUnit *units, const int *list, const int *count_p, int *retry_list,
+                                                                                int *retry_count, uint32_t overlap) {
+    using G = LsParts<PARTS>;
+    constexpr int LS_SPW = G::SPW, LS_RBITS = G::RING_BITS, LS_DEPTH = G::DEPTH;
     constexpr bool ZB = false;
-    constexpr uint32_t tl = LsSplit::TL, size = 1u << tl, SB = LsSplit::STREAM_BYTES, PB = LsSplit::PART_BYTES;
+    constexpr uint32_t tl = G::TL, size = 1u << tl, SB = G::STREAM_BYTES, PB = G::PART_BYTES, CH = G::CHUNK, BLK = G::BLK, LP = 2u * PARTS;
     extern __shared__ uint32_t s_mem[];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_mem != 0u) return;   // layout assumes dynamic LDS at 0
     const int n_cls = *count_p;
-    const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * LsSplit::WAVES + (int)wv) * LS_SPW);
+    const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * G::WAVES + (int)wv) * LS_SPW);
     if (slot0 >= n_cls) return;                                             // waves share nothing and never meet at a barrier
-    // ---- roles: lane 4 g + 2 part + k; lanes 12 .. 63 clone lane k of stream 0's part 0 (same addresses, same values) ----
+    // ---- roles: lane LP g + 2 part + k; the lanes behind the last stream clone lane k of stream 0's part 0 ----
     const uint32_t k = lane & 1u;
-    const bool real = lane < 4u * LS_SPW;
-    const uint32_t g = real ? lane >> 2 : 0u, part = real ? (lane >> 1) & 1u : 0u;
+    const bool real = lane < LP * LS_SPW;
+    const uint32_t g = real ? lane / LP : 0u, part = real ? (lane >> 1) & (uint32_t)(PARTS - 1) : 0u;
+    const bool last_part = part == (uint32_t)(PARTS - 1);                   // it has no lower neighbour: it stops at the stream's end
     const bool have = slot0 + (int)g < n_cls;
     const uint32_t gs = have ? g : 0u;                                      // absent streams run on stream 0's table, on rings of zeros
     const int unit_i = list[slot0 + (int)gs];
@@ -620,263 +643,13 @@ __global__ void __launch_bounds__(64 * LsSplit::WAVES) k_dec_tans_ls_split(MicUn
     const uint32_t T = have ? u.count : 0u;
     const uint32_t bits_off = u.bits_off, len = u.comp_len - bits_off;
     const uint32_t vbase = (wv * LS_SPW + g) * SB + part * PB;              // own ring / mirror / stage
-    const uint32_t tbase = (wv * LS_SPW + gs) * SB + LsSplit::TAB;
-    // ---- tables, as in k_dec_tans_ls: one per stream, both parts read it ----
-#pragma unroll 1
-    for (int j = 0; j < LS_SPW; j++) {
-        if (slot0 + j >= n_cls) break;
-        const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, 4 * j);
-        const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + LsSplit::TAB;
-        for (uint32_t p = lane * 4; p < size; p += 256) {
-            const uint4 e = *(const uint4 *)(dt + p);
-            const uint32_t n0 = ((e.x & 0xFFFF) + size) >> (e.x >> 16), n1 = ((e.y & 0xFFFF) + size) >> (e.y >> 16);
-            const uint32_t n2 = ((e.z & 0xFFFF) + size) >> (e.z >> 16), n3 = ((e.w & 0xFFFF) + size) >> (e.w >> 16);
-            ls_v2 v; v.x = n0 | (n1 << 16); v.y = n2 | (n3 << 16);
-            *(__attribute__((address_space(3))) ls_v2 *)(uintptr_t)(tb + p * 2) = v;
-        }
-    }
-    // ---- bit reader: grid of aligned dwords under the stream, as in k_dec_tans_ls ----
-    const uint8_t *bs = u.comp_in + bits_off;
-    const uint32_t last = bs[len - 1];                                      // non-zero: k_dec_classify
-    const uintptr_t addr = (uintptr_t)bs;
-    const uint32_t sb = (uint32_t)(addr & 3);
-    const uint64_t gaddr = (uint64_t)(addr - sb);
-    const uint32_t Lb = 8u * (len - 1) + (uint32_t)(31 - __clz(last));      // the stream's bits (below the end marker)
-    const int32_t cur0 = (int32_t)(Lb + 8u * sb);
-    const int32_t top_dw = have ? (cur0 - 1) >> 5 : -1;
-    // part 1 starts at bit pm: both parts then decode about (count + W) / 2 symbols -- part 0 covers bits [pm - Wb, Lb), Wb = W
-    // symbols' worth of bits at the stream's mean rate, part 1 [0, pm)
-    const uint32_t Wb = T ? (uint32_t)min((uint64_t)overlap * (uint64_t)Lb / (uint64_t)T, (uint64_t)Lb) : 0u;
-    const uint32_t pm = (uint32_t)(((uint64_t)Lb + (uint64_t)Wb) / 2u);
-    int32_t q = (part ? (int32_t)(pm + 8u * sb) : cur0) - 32;               // window of a round = grid bits [q, q+32)
-    const int32_t qz = (int32_t)(8u * sb) - 32;                             // q of "no bits left"
-    const uint32_t scr_cap = min(min(u.sym_cap, u.tok_cap), T) & ~63u;      // states part 1 may write (the sym slab is at least a tok slab)
-    bool s_have[LS_SPW];
-    __amdgpu_buffer_rsrc_t rs_in[LS_SPW], rs_tok[LS_SPW], rs_scr[LS_SPW];
-#pragma unroll
-    for (int j = 0; j < LS_SPW; j++) {
-        const int src = 4 * j;
-        s_have[j] = slot0 + j < n_cls;
-        const uint32_t in_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ((uint32_t)((int32_t)ls_rl((uint32_t)top_dw, src) + 1)) * 4u : 0u));
-        const uint32_t tok_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? (ls_rl(T, src) / 64u) * 128u : 0u));
-        const uint32_t scr_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ls_rl(scr_cap, src) * 2u : 0u));
-        rs_in[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64(gaddr, src), 0, (int)in_bytes, 0x00020000);
-        rs_tok[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tok, src), 0, (int)tok_bytes, 0x00020000);
-        rs_scr[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.sym, src), 0, (int)scr_bytes, 0x00020000);
-    }
-    const bool hi_half = lane >= 32;                                        // upkeep: lanes 0-31 serve part 0, lanes 32-63 part 1
-    const uint32_t l32 = lane & 31u;
-    constexpr uint32_t LS_OOB = 0x7FFFFFF0u;                                // a byte offset no descriptor here reaches: the access is dropped
-    auto load_blk = [&](int j, int32_t b0, int32_t b1) -> uint32_t {      // dword l32 of block b0 | b1 of stream j, zero outside the stream
-        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], ((hi_half ? b1 : b0) * 32 + (int32_t)l32) * 4, 0, 2);
-    };
-    auto store_blk = [&](int j, int32_t b0, int32_t b1, uint32_t v) {
-        const uint32_t rb = (wv * LS_SPW + (uint32_t)j) * SB + (hi_half ? PB : 0u);
-        const uint32_t slot = (uint32_t)(hi_half ? b1 : b0) & (uint32_t)(LsSplit::RING_BLOCKS - 1);
-        *(ls_l32)(uintptr_t)(rb + (slot * 32u + l32) * 4) = v;
-        if (l32 < 2) *(ls_l32)(uintptr_t)(rb + LsSplit::MIRROR + l32 * 4 + (slot == 0u ? 0u : 8u)) = v;   // mirror | pad (an address select)
-    };
-    auto blk_of = [&](int32_t qq, int src) -> int32_t { return ((int32_t)ls_rl((uint32_t)qq, src) >> 5) >> 5; };
-    uint32_t pf[LS_SPW]; int32_t s_pf0[LS_SPW], s_pf1[LS_SPW];
-#pragma unroll
-    for (int j = 0; j < LS_SPW; j++) {
-        const int32_t b0 = blk_of(q - (int32_t)(2 * tl), 4 * j), b1 = blk_of(q - (int32_t)(2 * tl), 4 * j + 2);   // block of the position BEHIND the initial states
-#pragma unroll
-        for (int dd = -1; dd < LS_DEPTH; dd++) store_blk(j, b0 - dd, b1 - dd, load_blk(j, b0 - dd, b1 - dd));
-        s_pf0[j] = b0 - LS_DEPTH; s_pf1[j] = b1 - LS_DEPTH;
-        pf[j] = load_blk(j, s_pf0[j], s_pf1[j]);                            // enters the rings at the end of the first chunk
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                     // wave-private LDS: the writes above are in before the reads below
-    // ---- chain state ----
-    const uint32_t ringb = vbase;
-    const uint32_t stgb = vbase + LsSplit::STAGE + 2u * k;                  // stage16[r * 2 + k] = state k of round r
-    const uint32_t cb = tbase - 2u * size;
-    const uint32_t C = 31u - tl;
-    auto window = [&](int32_t qq) -> uint32_t {
-        const uint32_t a = (__builtin_amdgcn_ubfe((uint32_t)qq, 5, LS_RBITS) << 2) + ringb;
-        const uint32_t w0 = *(ls_l32)(uintptr_t)a, w1 = *(ls_l32)(uintptr_t)(a + 4);
-        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
-    };
-    auto entry = [&](uint32_t s) -> uint32_t { return *(ls_l16)(uintptr_t)(s * 2 + cb); };
-    // initial states: part 0's are the stream's, part 1's the same read at pm -- valid table indices, but guesses
-    uint32_t st = size + (window(q - (int32_t)(k * tl)) >> (32u - tl));
-    q -= (int32_t)(2 * tl);
-    const uint32_t mk1 = k ? ~0u : 0u;
-    // ---- chunks of 64 symbols per part ----
-    const uint32_t Wc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(overlap / 64u));
-    uint32_t maxT = 0;
-#pragma unroll
-    for (int j = 0; j < LS_SPW; j++) if (s_have[j]) maxT = max(maxT, ls_rl(T, 4 * j));
-    const uint32_t ch_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxT / 64u + 2u));   // no part of the wave has anything to decode behind it
-    const uint32_t pl = (lane & ~3u) | 2u;                                  // part 1's first lane of this lane's stream
-    bool handed = false;
-    int32_t q1 = 0; uint32_t m_a = 0, m_b = 0;                              // the meeting point: part 1's position and its two states after Wc chunks
-    int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: part 0's last chunk start above q1, part 1's last with bits left
-    uint32_t ch = 0;
-    LS_ST_DECL;
-    for (;; ch++) {
-        if (ch == Wc) {                                                     // (uniform, once)
-            q1 = __builtin_amdgcn_ds_bpermute((int)(pl << 2), q);
-            m_a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)st);
-            m_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((pl | 1u) << 2), (int)st);
-            handed = true;
-        }
-        const bool on = part ? q > qz : (!handed || q > q1);
-        if (on) { sn_q = q; sn_st = st; sn_ch = ch; }
-        if (ch >= ch_cap || (handed && !__any(on && real && have))) break;  // one wave-uniform test per chunk
-        LS_T(4);
-        LS_CHUNK2_N("16", "128");
-        LS_T(0);
-        // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
-#pragma unroll
-        for (int j = 0; j < LS_SPW; j++) store_blk(j, s_pf0[j], s_pf1[j], pf[j]);
-        LS_T(1);
-#pragma unroll
-        for (int j = 0; j < LS_SPW; j++) {
-            s_pf0[j] = blk_of(q, 4 * j) - LS_DEPTH; s_pf1[j] = blk_of(q, 4 * j + 2) - LS_DEPTH;
-            pf[j] = load_blk(j, s_pf0[j], s_pf1[j]);
-        }
-        LS_T(2);
-        {
-            uint32_t s2[LS_SPW];
-#pragma unroll
-            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + (hi_half ? PB : 0u) + LsSplit::STAGE + l32 * 4);
-            const uint32_t off = ch * 128u + l32 * 4u;                      // (a part that runs on: its descriptor ends at what it may write)
-#pragma unroll
-            for (int j = 0; j < LS_SPW; j++) {
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(hi_half ? LS_OOB : off), 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(hi_half ? off : LS_OOB), 0, 2);
-            }
-        }
-        LS_T(3);
-    }
-    const uint32_t ch_end = ch;                                             // chunks every part ran and stored
-    LS_ST_OUT(2u);
-    // ---- the join: one lane per stream ----
-    // the other lanes' values (all lanes take part in the permutes)
-    const uint32_t p0_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
-    const uint32_t p1_s0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)sn_st);
-    const uint32_t p1_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((pl | 1u) << 2), (int)sn_st);
-    const int32_t p1_q = __builtin_amdgcn_ds_bpermute((int)(pl << 2), sn_q);
-    const uint32_t p1_ch = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)sn_ch);
-    if (!(real && have && (lane & 3u) == 0u)) return;
-    const uint32_t *grid = (const uint32_t *)(uintptr_t)gaddr;
-    auto peek = [&](int32_t qq) -> uint32_t {                              // grid bits [qq, qq + 32), zeros outside the stream's dwords
-        const int32_t d = qq >> 5;
-        const uint32_t w0 = (d >= 0 && d <= top_dw) ? grid[d] : 0u, w1 = (d + 1 >= 0 && d + 1 <= top_dw) ? grid[d + 1] : 0u;
-        return __builtin_amdgcn_alignbit(w1, w0, (uint32_t)qq);
-    };
-    auto step = [&](uint32_t &s, int32_t &pos) {                           // one symbol: nbBits >= 1 in this class
-        const uint32_t e = entry(s), nb = (uint32_t)__builtin_clz(e) - C;
-        s = (e << nb) | (peek(pos) >> (32u - nb));
-        pos -= (int32_t)nb;
-    };
-    uint32_t outcome = MIC_SPLIT_NOT_MET, i_sync = 0;
-    const uint32_t j_sync = Wc * 64u;
-    if (handed) {
-        uint32_t s0 = sn_st, s1 = p0_s1, i = sn_ch * 64u; int32_t pos = sn_q;
-        for (int n = 0; n <= 64 && pos >= q1; n++) {
-            if (pos == q1) {
-                const uint32_t nxt = (i & 1u) ? s1 : s0, oth = (i & 1u) ? s0 : s1;
-                if (nxt == m_a && oth == m_b) { outcome = MIC_SPLIT_DONE; i_sync = i; }
-                break;
-            }
-            if (i & 1u) step(s1, pos); else step(s0, pos);
-            i++;
-        }
-    }
-    if (outcome == MIC_SPLIT_DONE) {
-        // part 0's states [0, i_sync) are in tok when i_sync lies inside its whole chunks; part 1 must hold steps [j_sync, j_end)
-        const uint64_t j_end64 = (uint64_t)T - (uint64_t)i_sync + (uint64_t)j_sync;
-        if (i_sync > (T / 64u) * 64u || j_end64 > (uint64_t)scr_cap) outcome = MIC_SPLIT_NO_ROOM;
-        else if (j_end64 > (uint64_t)ch_end * 64u) outcome = MIC_SPLIT_BAD_COUNT;   // (the loop ended: part 1 was out of bits with symbols to go)
-        else {
-            const uint32_t j_end = (uint32_t)j_end64, js = p1_ch * 64u;
-            // the over-read rule at the stream's last symbol: part 1's position behind step j_end - 1, from its last chunk start with bits left
-            if (j_end > js) {
-                if (j_end - js > 64u) outcome = MIC_SPLIT_BAD_COUNT;       // (the chunk behind the snapshot started without bits)
-                else {
-                    uint32_t s0 = p1_s0, s1 = p1_s1; int32_t pos = p1_q;
-                    for (uint32_t j = js; j < j_end; j++) { if (j & 1u) step(s1, pos); else step(s0, pos); }
-                    if (pos < qz) outcome = MIC_SPLIT_BAD_COUNT;
-                }
-            }
-        }
-    }
-    MicUnit &uo = units[unit_i];
-    uo.split[0] = outcome; uo.split[1] = i_sync; uo.split[2] = j_sync;
-    if (outcome == MIC_SPLIT_DONE) {
-        uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
-        uo.ntok = T; uo.walk_ok = 2;                                        // tok and sym hold STATES: k_dec_translate joins and translates them
-    } else retry_list[atomicAdd(retry_count, 1)] = unit_i;
-}
-
-// ==========================================================================================
-// The four-part instance: the same class, every stream decoded as FOUR parts by four decoders on the stream's one table (24 of a
-// wave's 64 lanes hold a state).  Part 0 starts at the true start and writes true states to tok; parts 1-3 start further down
-// the stream with guessed states and write to three regions of R tokens of the unit's sym slab.  Part p >= 1 hands its position
-// and states after W symbols to part p - 1, which runs until it has passed that position; behind the chunk loop the three
-// boundaries are joined by a lane of the upper part each, side by side.
-//   * lane 8 g + 2 part + k holds state k of part `part` of the wave's stream g; lanes 24-63 clone lane k of stream 0's part 0;
-//   * a part has its own ring (4 blocks of 16 dwords), mirror and stage (32 states): a chunk is 32 symbols, 16 rounds of the
-//     hand-scheduled round (LS_CHUNK2_N("8", "64"));
-//   * the per-chunk upkeep serves the four parts of a stream with one instruction each: lanes 16 p ... 16 p + 15 part p's block.
-// Ring reach, as for LsSplit with blocks of 16 dwords: a chunk of 32 symbols takes at most 32 * 13 = 416 bits = 13 dwords; the
-// reads are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of
-// the chunk's first position, in block b, they span dwords D - 14 ... D + 1; D - 14 >= 16 b - 14 = 16 (b - 1) + 2, inside block
-// b - 1, and D + 1 inside block b + 1 at the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block
-// b + 2 at the chunk's end, which no chunk from here on reads.  The position behind the two initial states is at most 26 bits
-// below the start, so the same three blocks hold what the initial states read.
-// Where the parts start: Lb the stream's bits, Wb = W symbols' worth of bits at the mean rate, x = (Lb + 3 Wb) / 4; part p >= 1
-// starts at bit (4 - p) x - (3 - p) Wb, so that every part covers about x bits, W symbols of them under its upper neighbour.
-// Joins: part p (0 .. 2) steps from its last chunk start above part p + 1's hand-over position q until its position is q; the
-// parts have met when its two states there are part p + 1's, role by role (part p's own step parity against part p + 1 at its
-// step W, which is even); e_p is part p's step index there (p >= 1: at least W).  One lane per stream turns them into token
-// indices, I_1 = e_0, I_p+1 = I_p + e_p - W: token i of [I_p, I_p+1) is part p's step W + i - I_p (I_4 = count).  Checked there:
-// I_1 inside part 0's whole chunks, every part's last step inside its region, and part 3's count by the over-read rule
-// (bitreader.go:113-120: it must decode count - I_3 + W steps without reading below bit 0).  The first boundary that fails
-// names the outcome, and the whole unit goes to the retry list.
-struct LsSplit4 {
-    static constexpr int TL = 13, SPW = 3, WAVES = 3, PARTS = 4;
-    static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = 6;         // blocks of 16 dwords
-    static constexpr uint32_t MIRROR = 64u * RING_BLOCKS;                   // two mirror dwords + two pad dwords
-    static constexpr uint32_t STAGE = MIRROR + 16u;                         // 32 u16 states of a chunk
-    static constexpr uint32_t PART_BYTES = STAGE + 64u;                     // 336
-    static constexpr uint32_t TAB = (uint32_t)PARTS * PART_BYTES;           // the four parts in front of the stream's table
-    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 728
-    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 552
-    static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
-};
-
-__global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(MicUnit *units, const int *list, const int *count_p, int *retry_list,
-                                                                           int *retry_count, uint32_t overlap) {
-    constexpr int LS_SPW = LsSplit4::SPW, LS_RBITS = LsSplit4::RING_BITS, LS_DEPTH = LsSplit4::DEPTH;
-    constexpr bool ZB = false;
-    constexpr uint32_t tl = LsSplit4::TL, size = 1u << tl, SB = LsSplit4::STREAM_BYTES, PB = LsSplit4::PART_BYTES;
-    extern __shared__ uint32_t s_mem[];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_mem != 0u) return;   // layout assumes dynamic LDS at 0
-    const int n_cls = *count_p;
-    const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * LsSplit4::WAVES + (int)wv) * LS_SPW);
-    if (slot0 >= n_cls) return;                                             // waves share nothing and never meet at a barrier
-    // ---- roles: lane 8 g + 2 part + k; lanes 24 .. 63 clone lane k of stream 0's part 0 (same addresses, same values) ----
-    const uint32_t k = lane & 1u;
-    const bool real = lane < 8u * LS_SPW;
-    const uint32_t g = real ? lane >> 3 : 0u, part = real ? (lane >> 1) & 3u : 0u;
-    const bool have = slot0 + (int)g < n_cls;
-    const uint32_t gs = have ? g : 0u;                                      // absent streams run on stream 0's table, on rings of zeros
-    const int unit_i = list[slot0 + (int)gs];
-    const MicUnit &u = units[unit_i];
-    const uint32_t T = have ? u.count : 0u;
-    const uint32_t bits_off = u.bits_off, len = u.comp_len - bits_off;
-    const uint32_t vbase = (wv * LS_SPW + g) * SB + part * PB;              // own ring / mirror / stage
-    const uint32_t tbase = (wv * LS_SPW + gs) * SB + LsSplit4::TAB;
+    const uint32_t tbase = (wv * LS_SPW + gs) * SB + G::TAB;
     // ---- tables, as in k_dec_tans_ls: one per stream, all parts read it ----
 #pragma unroll 1
     for (int j = 0; j < LS_SPW; j++) {
         if (slot0 + j >= n_cls) break;
-        const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, 8 * j);
-        const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + LsSplit4::TAB;
+        const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, (int)LP * j);
+        const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + G::TAB;
         for (uint32_t p = lane * 4; p < size; p += 256) {
             const uint4 e = *(const uint4 *)(dt + p);
             const uint32_t n0 = ((e.x & 0xFFFF) + size) >> (e.x >> 16), n1 = ((e.y & 0xFFFF) + size) >> (e.y >> 16);
@@ -894,41 +667,41 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
     const uint32_t Lb = 8u * (len - 1) + (uint32_t)(31 - __clz(last));      // the stream's bits (below the end marker)
     const int32_t cur0 = (int32_t)(Lb + 8u * sb);
     const int32_t top_dw = have ? (cur0 - 1) >> 5 : -1;
-    // part p >= 1 starts at bit (4 - p) x - (3 - p) Wb (Wb <= Lb, so Wb <= x <= Lb and the starts lie in [x, Lb], in falling order)
+    // part p >= 1 starts at bit (PARTS - p) x - (PARTS - 1 - p) Wb (Wb <= Lb, so Wb <= x <= Lb and the starts lie in [x, Lb], in falling order)
     const uint32_t Wb = T ? (uint32_t)min((uint64_t)overlap * (uint64_t)Lb / (uint64_t)T, (uint64_t)Lb) : 0u;
-    const uint32_t x = (uint32_t)(((uint64_t)Lb + 3ull * (uint64_t)Wb) / 4u);
-    const uint32_t pm = (uint32_t)((uint64_t)(4u - part) * (uint64_t)x - (uint64_t)(3u - part) * (uint64_t)Wb);
+    const uint32_t x = (uint32_t)(((uint64_t)Lb + (uint64_t)(PARTS - 1) * (uint64_t)Wb) / (uint32_t)PARTS);
+    const uint32_t pm = (uint32_t)((uint64_t)((uint32_t)PARTS - part) * (uint64_t)x - (uint64_t)((uint32_t)(PARTS - 1) - part) * (uint64_t)Wb);
     int32_t q = (part ? (int32_t)(pm + 8u * sb) : cur0) - 32;               // window of a round = grid bits [q, q+32)
     const int32_t qz = (int32_t)(8u * sb) - 32;                             // q of "no bits left"
-    const uint32_t R = ((min(u.sym_cap, u.tok_cap) / 3u) & ~31u);           // tokens of a scratch region (the sym slab is at least a tok slab)
+    const uint32_t R = G::region(u.sym_cap, u.tok_cap, T);                  // tokens of a scratch region
     bool s_have[LS_SPW];
     __amdgpu_buffer_rsrc_t rs_in[LS_SPW], rs_tok[LS_SPW], rs_scr[LS_SPW];
     uint32_t s_R[LS_SPW];
 #pragma unroll
     for (int j = 0; j < LS_SPW; j++) {
-        const int src = 8 * j;
+        const int src = (int)LP * j;
         s_have[j] = slot0 + j < n_cls;
         s_R[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ls_rl(R, src) : 0u));
         const uint32_t in_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? ((uint32_t)((int32_t)ls_rl((uint32_t)top_dw, src) + 1)) * 4u : 0u));
-        const uint32_t tok_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? (ls_rl(T, src) / 32u) * 64u : 0u));
-        const uint32_t scr_bytes = s_R[j] * 6u;                             // three regions of R states
+        const uint32_t tok_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_have[j] ? (ls_rl(T, src) / CH) * CH * 2u : 0u));
+        const uint32_t scr_bytes = s_R[j] * 2u * (uint32_t)(PARTS - 1);     // PARTS - 1 regions of R states
         rs_in[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64(gaddr, src), 0, (int)in_bytes, 0x00020000);
         rs_tok[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tok, src), 0, (int)tok_bytes, 0x00020000);
         rs_scr[j] = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.sym, src), 0, (int)scr_bytes, 0x00020000);
     }
-    const uint32_t up = lane >> 4, l16 = lane & 15u;                        // upkeep: lanes 16 p .. 16 p + 15 serve part p
+    const uint32_t up = lane >> G::BLK_SHIFT, lb = lane & (BLK - 1u);       // upkeep: lanes BLK p .. BLK p + BLK - 1 serve part p
     constexpr uint32_t LS_OOB = 0x7FFFFFF0u;                                // a byte offset no descriptor here reaches: the access is dropped
     auto blk_of = [&](int j, int32_t qq) -> int32_t {                      // block of the position of this lane's part of stream j (all lanes take part)
-        return (__builtin_amdgcn_ds_bpermute((int)((8u * (uint32_t)j + 2u * up) << 2), qq) >> 5) >> 4;
+        return (__builtin_amdgcn_ds_bpermute((int)((LP * (uint32_t)j + 2u * up) << 2), qq) >> 5) >> G::BLK_SHIFT;
     };
-    auto load_blk = [&](int j, int32_t b) -> uint32_t {                    // dword l16 of block b of stream j, zero outside the stream
-        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], (b * 16 + (int32_t)l16) * 4, 0, 2);
+    auto load_blk = [&](int j, int32_t b) -> uint32_t {                    // dword lb of block b of stream j, zero outside the stream
+        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], (b * (int32_t)BLK + (int32_t)lb) * 4, 0, 2);
     };
     auto store_blk = [&](int j, int32_t b, uint32_t v) {
         const uint32_t rb = (wv * LS_SPW + (uint32_t)j) * SB + up * PB;
-        const uint32_t slot = (uint32_t)b & (uint32_t)(LsSplit4::RING_BLOCKS - 1);
-        *(ls_l32)(uintptr_t)(rb + (slot * 16u + l16) * 4) = v;
-        if (l16 < 2) *(ls_l32)(uintptr_t)(rb + LsSplit4::MIRROR + l16 * 4 + (slot == 0u ? 0u : 8u)) = v;   // mirror | pad (an address select)
+        const uint32_t slot = (uint32_t)b & (uint32_t)(G::RING_BLOCKS - 1);
+        *(ls_l32)(uintptr_t)(rb + (slot * BLK + lb) * 4) = v;
+        if (lb < 2) *(ls_l32)(uintptr_t)(rb + G::MIRROR + lb * 4 + (slot == 0u ? 0u : 8u)) = v;   // mirror | pad (an address select)
     };
     uint32_t pf[LS_SPW]; int32_t pfb[LS_SPW];
 #pragma unroll
@@ -942,7 +715,7 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
     __builtin_amdgcn_s_waitcnt(0xC07F);                                     // wave-private LDS: the writes above are in before the reads below
     // ---- chain state ----
     const uint32_t ringb = vbase;
-    const uint32_t stgb = vbase + LsSplit4::STAGE + 2u * k;                 // stage16[r * 2 + k] = state k of round r
+    const uint32_t stgb = vbase + G::STAGE + 2u * k;                        // stage16[r * 2 + k] = state k of round r
     const uint32_t cb = tbase - 2u * size;
     const uint32_t C = 31u - tl;
     auto window = [&](int32_t qq) -> uint32_t {
@@ -955,38 +728,42 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
     uint32_t st = size + (window(q - (int32_t)(k * tl)) >> (32u - tl));
     q -= (int32_t)(2 * tl);
     const uint32_t mk1 = k ? ~0u : 0u;
-    // ---- chunks of 32 symbols per part ----
-    const uint32_t Wc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(overlap / 32u));
+    // ---- chunks of CH symbols per part ----
+    const uint32_t Wc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(overlap / CH));
     uint32_t maxT = 0;
 #pragma unroll
-    for (int j = 0; j < LS_SPW; j++) if (s_have[j]) maxT = max(maxT, ls_rl(T, 8 * j));
-    const uint32_t ch_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxT / 32u + 2u));   // no part of the wave has anything to decode behind it
-    const uint32_t own_cap = T / 32u + 2u;                                  // ... and no part of this stream: what a part does is its stream's business alone
-    const uint32_t nl = ((lane & ~1u) + 2u) & 63u;                          // the next part's first lane (part 3 has none: it stops at the stream's end)
+    for (int j = 0; j < LS_SPW; j++) if (s_have[j]) maxT = max(maxT, ls_rl(T, (int)LP * j));
+    const uint32_t ch_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(maxT / CH + 2u));   // no part of the wave has anything to decode behind it
+    // ... and no part of this stream behind its own T / CH + 2: what a part does is its stream's business alone.  c < T / CH + 2 is
+    // (c - 1) CH <= T, a scalar product against a value the lane holds anyway (T < 2^31: a token takes a bit at least)
+    auto own_chunk = [&](uint32_t c) -> bool { return (int32_t)((c - 1u) * CH) <= (int32_t)T; };
+    const uint32_t nl = ((lane & ~1u) + 2u) & 63u;                          // the next part's first lane (the last part has none)
     // the scratch regions: byte offset of this lane's dword of chunk 0 (part 0's lanes aim out of range), and the same for tok
     uint32_t scr0[LS_SPW];
 #pragma unroll
-    for (int j = 0; j < LS_SPW; j++) scr0[j] = up ? (up - 1u) * s_R[j] * 2u + l16 * 4u : LS_OOB;
-    const uint32_t tok0 = up ? LS_OOB : l16 * 4u;
+    for (int j = 0; j < LS_SPW; j++) scr0[j] = up ? (PARTS > 2 ? (up - 1u) * s_R[j] * 2u : 0u) + lb * 4u : LS_OOB;
+    const uint32_t tok0 = up ? LS_OOB : lb * 4u;
     bool handed = false;
-    int32_t qn = 0; uint32_t m_a = 0, m_b = 0;                              // the next part's position and its two states after Wc chunks
-    int32_t qlim = part == 3u ? qz : INT32_MIN;                             // a part is on above it: nothing up to the hand-over, then qn; part 3: bits left
-    int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: the last chunk start above qn; part 3: the last with bits left
+    uint32_t m_ab = 0;                                                      // the next part's two states after Wc chunks, second << 16 (a state is below 2^14)
+    int32_t qlim = last_part ? qz : INT32_MIN;                              // a part is on above it: nothing up to the hand-over, then the next part's
+                                                                            // position after Wc chunks; the last part: bits left
+    int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: the last chunk start above qlim
     uint32_t ch = 0;
     LS_ST_DECL;
     for (;; ch++) {
         if (ch == Wc) {                                                     // (uniform, once)
-            qn = __builtin_amdgcn_ds_bpermute((int)(nl << 2), q);
-            m_a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nl << 2), (int)st);
-            m_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((nl | 1u) << 2), (int)st);
-            qlim = part == 3u ? qz : qn;
+            const int32_t qn = __builtin_amdgcn_ds_bpermute((int)(nl << 2), q);
+            m_ab = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nl << 2), (int)st) |
+                   ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((nl | 1u) << 2), (int)st) << 16);
+            qlim = last_part ? qz : qn;
             handed = true;
         }
-        const bool on = (ch < own_cap) & (q > qlim);                        // (selects, no branch)
+        const bool on = own_chunk(ch) & (q > qlim);                         // (selects, no branch)
         sn_q = on ? q : sn_q; sn_st = on ? st : sn_st; sn_ch = on ? ch : sn_ch;
+        asm volatile("" : "+v"(sn_q), "+v"(sn_st), "+v"(sn_ch));            // (taken here: sunk behind the chunk, the selects keep the old q and st alive across it)
         if (ch >= ch_cap || !__any(on & real & have)) break;                // one wave-uniform test per chunk
         LS_T(4);
-        LS_CHUNK2_N("8", "64");
+        if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else LS_CHUNK2_N("8", "64");
         LS_T(0);
         // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
 #pragma unroll
@@ -1000,11 +777,11 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
         {
             uint32_t s2[LS_SPW];
 #pragma unroll
-            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + LsSplit4::STAGE + l16 * 4);
-            const uint32_t off = ch * 64u;                                  // (part 0 runs on into a descriptor that ends at its last whole chunk)
+            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + lb * 4);
+            const uint32_t off = ch * 2u * CH;                              // (part 0 runs on into a descriptor that ends at its last whole chunk)
 #pragma unroll
             for (int j = 0; j < LS_SPW; j++) {
-                const bool fits = (ch + 1u) * 32u <= s_R[j];                // (a part that runs on past its region must not write into its neighbour's)
+                const bool fits = (ch + 1u) * CH <= s_R[j];                 // (a part that runs on past its region must not write into its neighbour's)
                 __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, 2);   // (out of range + off < 2^32: still out of range)
                 __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + off : LS_OOB), 0, 2);
             }
@@ -1012,8 +789,8 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
         LS_T(3);
     }
     const uint32_t ch_end = ch;                                             // chunks every part ran and stored
-    LS_ST_OUT(4u);
-    // ---- the joins: boundary p | p + 1 by lane 0 of part p, the three of a stream side by side ----
+    LS_ST_OUT((uint32_t)PARTS);
+    // ---- the joins: boundary p | p + 1 by lane 0 of part p, those of a stream side by side ----
     const uint32_t sn_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
     const uint32_t *grid = (const uint32_t *)(uintptr_t)gaddr;
     auto peek = [&](int32_t qq) -> uint32_t {                              // grid bits [qq, qq + 32), zeros outside the stream's dwords
@@ -1026,57 +803,61 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
         s = (e << nb) | (peek(pos) >> (32u - nb));
         pos -= (int32_t)nb;
     };
-    const uint32_t W = Wc * 32u;
+    const uint32_t W = Wc * CH;
     uint32_t met = 0, e_p = 0;
-    if (real && have && handed && Wc < own_cap && k == 0u && part < 3u) {  // (Wc >= own_cap: a longer neighbour kept the loop going up to the hand-over)
-        uint32_t s0 = sn_st, s1 = sn_s1, i = sn_ch * 32u; int32_t pos = sn_q;
+    if (real && have && handed && own_chunk(Wc) && k == 0u && !last_part) { // (not its own chunk: a longer neighbour kept the loop going up to the hand-over)
+        const int32_t qn = qlim;                                            // (handed, not the last part: the limit is the neighbour's hand-over position)
+        uint32_t s0 = sn_st, s1 = sn_s1, i = sn_ch * CH; int32_t pos = sn_q;
         const uint32_t i_min = part ? W : 0u;                               // (a part's own first W steps are not its output)
-        for (int n = 0; n <= 32 && pos >= qn; n++) {
+        for (int n = 0; n <= (int)CH && pos >= qn; n++) {
             if (pos == qn) {
                 const uint32_t nxt = (i & 1u) ? s1 : s0, oth = (i & 1u) ? s0 : s1;
-                if (i >= i_min && nxt == m_a && oth == m_b) { met = 1u; e_p = i; }
+                if (i >= i_min && (nxt | (oth << 16)) == m_ab) { met = 1u; e_p = i; }
                 break;
             }
             if (i & 1u) step(s1, pos); else step(s0, pos);
             i++;
         }
     }
-    // ---- one lane per stream: the other boundaries' results and part 3's snapshot (all lanes take part in the permutes) ----
-    const uint32_t l0 = lane & ~7u;
-    const uint32_t met1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u) << 2), (int)met), e_1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u) << 2), (int)e_p);
-    const uint32_t met2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 4u) << 2), (int)met), e_2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 4u) << 2), (int)e_p);
-    const uint32_t p3_s0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), (int)sn_st);
-    const uint32_t p3_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 7u) << 2), (int)sn_st);
-    const int32_t p3_q = __builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), sn_q);
-    const uint32_t p3_ch = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 6u) << 2), (int)sn_ch);
-    if (!(real && have && (lane & 7u) == 0u)) return;
-    // boundary b = 1 .. 3: met, then room -- I_1 inside tok's whole chunks, part b - 1's last step e inside its region; then the
-    // stream's end (4): part 3's room and its count
-    uint32_t outcome = MIC_SPLIT_DONE, fail = 0, I[3] = { 0, 0, 0 };
+    // ---- one lane per stream: the other boundaries' results and the last part's snapshot (all lanes take part in the permutes) ----
+    const uint32_t l0 = lane & ~(LP - 1u), ll = l0 + LP - 2u;               // the stream's first lane, its last part's first lane
+    uint32_t mets[PARTS - 1] = { met }, es[PARTS - 1] = { e_p };
+#pragma unroll
+    for (int b = 1; b < PARTS - 1; b++) {
+        mets[b] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u * (uint32_t)b) << 2), (int)met);
+        es[b] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l0 + 2u * (uint32_t)b) << 2), (int)e_p);
+    }
+    const uint32_t pl_s0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ll << 2), (int)sn_st);
+    const uint32_t pl_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ll + 1u) << 2), (int)sn_st);
+    const int32_t pl_q = __builtin_amdgcn_ds_bpermute((int)(ll << 2), sn_q);
+    const uint32_t pl_ch = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ll << 2), (int)sn_ch);
+    if (!(real && have && lane == l0)) return;
+    // boundary b = 1 .. PARTS - 1: met, then room -- I_1 inside tok's whole chunks, part b - 1's last step e inside its region; then
+    // the stream's end (PARTS): the last part's room and its count.  (Two parts: I_2 = I_3 = ~0, "no bound" to k_dec_translate)
+    uint32_t outcome = MIC_SPLIT_DONE, fail = 0, I[3] = { 0u, PARTS > 2 ? 0u : ~0u, PARTS > 2 ? 0u : ~0u };
     {
-        const uint32_t mets[3] = { met, met1, met2 }, es[3] = { e_p, e_1, e_2 };
         uint32_t at = 0;
 #pragma unroll
-        for (int b = 0; b < 3; b++) {
+        for (int b = 0; b < PARTS - 1; b++) {
             if (outcome != MIC_SPLIT_DONE) break;
             if (!mets[b]) { outcome = MIC_SPLIT_NOT_MET; fail = (uint32_t)b + 1u; break; }
             at = b ? at + es[b] - W : es[0];
             I[b] = at;
-            if (b ? es[b] > R : at > (T / 32u) * 32u) { outcome = MIC_SPLIT_NO_ROOM; fail = (uint32_t)b + 1u; }
+            if (b ? es[b] > R : at > (T / CH) * CH) { outcome = MIC_SPLIT_NO_ROOM; fail = (uint32_t)b + 1u; }
         }
     }
     if (outcome == MIC_SPLIT_DONE) {
-        fail = 4u;
-        if (I[2] > T) outcome = MIC_SPLIT_BAD_COUNT;                         // (the parts in front hold more than the stream's symbols)
+        fail = (uint32_t)PARTS;
+        if (I[PARTS - 2] > T) outcome = MIC_SPLIT_BAD_COUNT;                 // (the parts in front hold more than the stream's symbols)
         else {
-            const uint32_t j_end = T - I[2] + W, js = p3_ch * 32u;          // part 3 must hold steps [W, j_end)
+            const uint32_t j_end = T - I[PARTS - 2] + W, js = pl_ch * CH;   // the last part must hold steps [W, j_end)
             if (j_end > R) outcome = MIC_SPLIT_NO_ROOM;
-            else if (j_end > ch_end * 32u) outcome = MIC_SPLIT_BAD_COUNT;   // (the loop ended: part 3 was out of bits with symbols to go)
+            else if (j_end > ch_end * CH) outcome = MIC_SPLIT_BAD_COUNT;    // (the loop ended: the last part was out of bits with symbols to go)
             else if (j_end > js) {
-                // the over-read rule at the stream's last symbol: part 3's position behind step j_end - 1, from its last chunk start with bits left
-                if (j_end - js > 32u) outcome = MIC_SPLIT_BAD_COUNT;       // (the chunk behind the snapshot started without bits)
+                // the over-read rule at the stream's last symbol: the last part's position behind step j_end - 1, from its last chunk start with bits left
+                if (j_end - js > CH) outcome = MIC_SPLIT_BAD_COUNT;        // (the chunk behind the snapshot started without bits)
                 else {
-                    uint32_t s0 = p3_s0, s1 = p3_s1; int32_t pos = p3_q;
+                    uint32_t s0 = pl_s0, s1 = pl_s1; int32_t pos = pl_q;
                     for (uint32_t j = js; j < j_end; j++) { if (j & 1u) step(s1, pos); else step(s0, pos); }
                     if (pos < qz) outcome = MIC_SPLIT_BAD_COUNT;
                 }
@@ -1085,8 +866,8 @@ __global__ void __launch_bounds__(64 * LsSplit4::WAVES) k_dec_tans_ls_split4(Mic
         if (outcome == MIC_SPLIT_DONE) fail = 0u;
     }
     MicUnit &uo = units[unit_i];
-    uo.split[0] = outcome; uo.split[1] = I[0]; uo.split[2] = W;
-    uo.split4[0] = I[0]; uo.split4[1] = I[1]; uo.split4[2] = I[2]; uo.split4[3] = R; uo.split4[4] = fail;
+    uo.split[0] = outcome; uo.split[1] = I[0]; uo.split[2] = W; uo.split[3] = I[1]; uo.split[4] = I[2];
+    uo.split[5] = R; uo.split[6] = fail; uo.split[7] = (uint32_t)PARTS;
     if (outcome == MIC_SPLIT_DONE) {
         uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
         uo.ntok = T; uo.walk_ok = 2;                                        // tok and sym hold STATES: k_dec_translate joins and translates them
@@ -1129,15 +910,13 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
         for (uint32_t i = tid; i < size / 2; i += TR_THREADS) ((uint32_t *)s_sym)[i] = src[i];
     }
     uint16_t *tok = u.tok;
-    // a split unit (k_dec_tans_ls_split): states [i_sync, ntok) still lie in the scratch slab, from j_sync on; they are read from
-    // there and written, translated, to tok -- everything behind this pass sees an ordinary tok
-    // A four-part unit (k_dec_tans_ls_split4: split4[3] = R != 0) has three such joins: tokens [I_p, I_p+1) are the states
-    // sym[(p - 1) R + W + i - I_p].  Either way: up to three bounds b1 <= b2 <= b3 (none: ~0) and, for the tokens from bound p on,
-    // the offset o_p from token index to scratch index (modulo 2^32)
+    // a split unit (k_dec_tans_ls_parts): the states of tokens [I_p, I_p+1) still lie in the scratch slab, sym[(p - 1) R + W + i - I_p];
+    // they are read from there and written, translated, to tok -- everything behind this pass sees an ordinary tok.  Up to three
+    // bounds b1 <= b2 <= b3 (none: ~0, which is what a two-part unit's record holds for I_2 and I_3) and, for the tokens from bound p
+    // on, the offset o_p from token index to scratch index (modulo 2^32)
     const bool sp = TRTL == 13 && u.split[0] == MIC_SPLIT_DONE;
-    const uint32_t sp_R = u.split4[3], sp_W = u.split[2];
-    const bool sp4 = sp && sp_R != 0u;
-    const uint32_t b1 = sp ? u.split[1] : ~0u, b2 = sp4 ? u.split4[1] : ~0u, b3 = sp4 ? u.split4[2] : ~0u;
+    const uint32_t sp_R = u.split[5], sp_W = u.split[2];
+    const uint32_t b1 = sp ? u.split[1] : ~0u, b2 = sp ? u.split[3] : ~0u, b3 = sp ? u.split[4] : ~0u;
     const uint32_t o1 = sp_W - b1, o2 = sp_R + sp_W - b2, o3 = 2u * sp_R + sp_W - b3;
     auto seg_of = [&](uint32_t i) -> uint32_t { return (uint32_t)(i >= b1) + (uint32_t)(i >= b2) + (uint32_t)(i >= b3); };
     auto scr_of = [&](uint32_t p, uint32_t i) -> uint32_t { return i + (p == 1u ? o1 : p == 2u ? o2 : o3); };
@@ -1331,6 +1110,17 @@ static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *
     const unsigned groups = (unsigned)((n + per - 1) / per);
     hipLaunchKernelGGL((k_dec_tans_ls<N, ZB, TL>), dim3(groups), dim3(64 * LsGeom<TL>::WAVES), LsGeom<TL>::LDS, stream, d_units, list, count);
 }
+// a split instance on list `from`; what it hands back goes to the retry list
+template <int PARTS>
+static void launch_ls_parts(MicUnit *d_units, int n, int *d_list, int *d_count, int from, hipStream_t stream, uint32_t overlap) {
+    using G = LsParts<PARTS>;
+    constexpr int per = G::WAVES * G::SPW;
+    static MicPerDeviceOnce once;
+    once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_parts<PARTS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS); });
+    const unsigned groups = (unsigned)((n + per - 1) / per);
+    hipLaunchKernelGGL((k_dec_tans_ls_parts<PARTS>), dim3(groups), dim3(64 * G::WAVES), G::LDS, stream, d_units, d_list + (size_t)from * (size_t)n,
+                       d_count + from, d_list + (size_t)LS_RETRY_LIST * (size_t)n, d_count + LS_RETRY_LIST, overlap);
+}
 template <int TL>
 static void launch_ls_tl(MicUnit *d_units, int n, const int *d_list, const int *d_count, hipStream_t stream, bool skip_first, uint32_t m) {
     if (!skip_first) launch_ls_class<2, false, TL>(d_units, n, d_list, d_count, stream, m);
@@ -1348,24 +1138,13 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
     if (t) t->mark("k_dec_classify");
     hipLaunchKernelGGL(k_dec_classify, dim3(1), dim3(1024), 0, stream, d_units, n, d_list, d_count, split ? 1 : 0, sc);
     if (split) {
-        // the split instance first (the longest kernel of the chain), then what it hands back: an empty list in the normal case, and
-        // the unsplit instance's blocks leave at once.  (Without the retry launch k_dec_tans_gl would take those units: slower, not wrong.)
-        constexpr int per = LsSplit::WAVES * LsSplit::SPW;
-        static MicPerDeviceOnce once;
-        once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_split, hipFuncAttributeMaxDynamicSharedMemorySize, LsSplit::LDS); });
-        const unsigned groups = (unsigned)((n + per - 1) / per);
-        // the four-part instance in front of it (the same streams per group, so the same grid): the longest units first
-        static MicPerDeviceOnce once4;
-        once4.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_split4, hipFuncAttributeMaxDynamicSharedMemorySize, LsSplit4::LDS); });
-        static_assert(LsSplit4::WAVES * LsSplit4::SPW == per, "one grid for both split instances");
+        // the split instances first (the longest kernels of the chain, the four-part one with the longest units in front), then what
+        // they hand back: an empty list in the normal case, and the unsplit instance's blocks leave at once.  (Without the retry
+        // launch k_dec_tans_gl would take those units: slower, not wrong.)
         if (t) t->mark("k_dec_tans_ls_split4<13>");
-        hipLaunchKernelGGL(k_dec_tans_ls_split4, dim3(groups), dim3(64 * LsSplit4::WAVES), LsSplit4::LDS, stream, d_units,
-                           d_list + (size_t)LS_SPLIT4_LIST * (size_t)n, d_count + LS_SPLIT4_LIST, d_list + (size_t)LS_RETRY_LIST * (size_t)n,
-                           d_count + LS_RETRY_LIST, sc.overlap & ~63u);
+        launch_ls_parts<4>(d_units, n, d_list, d_count, LS_SPLIT4_LIST, stream, sc.overlap & ~63u);
         if (t) t->mark("k_dec_tans_ls_split<13>");
-        hipLaunchKernelGGL(k_dec_tans_ls_split, dim3(groups), dim3(64 * LsSplit::WAVES), LsSplit::LDS, stream, d_units,
-                           d_list + (size_t)LS_SPLIT_LIST * (size_t)n, d_count + LS_SPLIT_LIST, d_list + (size_t)LS_RETRY_LIST * (size_t)n,
-                           d_count + LS_RETRY_LIST, sc.overlap & ~63u);
+        launch_ls_parts<2>(d_units, n, d_list, d_count, LS_SPLIT_LIST, stream, sc.overlap & ~63u);
         if (cls_mask & MIC_CLS_RETRY) {
             if (t) t->mark("k_dec_tans_ls<2,false,13> retry");
             launch_ls_list<2, false, 13>(d_units, n, d_list + (size_t)LS_RETRY_LIST * (size_t)n, d_count + LS_RETRY_LIST, stream);

@@ -32,20 +32,20 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 // MicUnit.dec_kernel behind the 30 lane-per-state classes (1 .. 30)
 #define MIC_DEC_BY_GL           31u
 #define MIC_DEC_BY_SERIAL       32u
-// MicUnit.split[0]: what the split instance of the two-state chain (k_dec_tans_ls_split, mic_decode_ls.hip) made of the unit
-#define MIC_SPLIT_NOT_TRIED     0u     // classified as before: not on the split list
-#define MIC_SPLIT_DONE          1u     // both halves decoded and joined: split[1] = i_sync, split[2] = j_sync
-#define MIC_SPLIT_NOT_MET       2u     // fell back to the unsplit instance: the halves did not meet inside the overlap
-#define MIC_SPLIT_BAD_COUNT     3u     // fell back: the second half does not end with the stream's last symbol (cut or damaged stream)
-#define MIC_SPLIT_NO_ROOM       4u     // fell back: the second half does not fit the scratch slab, or the halves meet behind the last whole chunk
-// Which two-state tableLog-13 units are split, and how far the halves overlap.  Defaults below; a session's
+// MicUnit.split[0]: what a split instance of the two-state chain (k_dec_tans_ls_parts, mic_decode_ls.hip) made of the unit
+#define MIC_SPLIT_NOT_TRIED     0u     // classified as before: not on a split list
+#define MIC_SPLIT_DONE          1u     // all parts decoded and joined: split[1] = I_1, split[2] = W, ... (MicUnit.split below)
+#define MIC_SPLIT_NOT_MET       2u     // fell back to the unsplit instance: two neighbouring parts did not meet inside the overlap
+#define MIC_SPLIT_BAD_COUNT     3u     // fell back: the last part does not end with the stream's last symbol (cut or damaged stream)
+#define MIC_SPLIT_NO_ROOM       4u     // fell back: a part does not fit its scratch region, or the first two meet behind the last whole chunk
+// Which two-state tableLog-13 units are split, and how far the parts overlap.  Defaults below; a session's
 // values come from mic_hip_debug_split_config.
 struct MicSplitCfg {
     uint32_t min_tokens = 131072u;     // shorter units are not worth a second decoder's start-up
-    uint32_t overlap = 32768u;         // W: symbols the second half decodes before its state is taken as the meeting point (a multiple of 64)
+    uint32_t overlap = 32768u;         // W: symbols a part decodes before its state is taken as the meeting point (a multiple of 64)
     uint32_t min_bits16 = 144u;        // G: 16 x the mean bits per token from which on a wrong start is forgotten inside W
     uint32_t min_tokens4 = 262144u;    // units that pass the gate above and are at least this long go to the four-part instance
-                                       // (k_dec_tans_ls_split4); mic_hip_debug_split4_config sets it, mic_hip_debug_split_config does not
+                                       // (the others to the two-part one); mic_hip_debug_split4_config sets it, mic_hip_debug_split_config does not
 };
 // MicUnit.enc_kernel: 1 + the bit index of the MIC_ENC_CLS_* class (mic_launch.h) whose k_enc_tans_wg instance gave the unit its tANS
 // verdict (1 .. 7), or MIC_ENC_BY_SERIAL; MIC_ENC_HANDED is set beside it when the two-state instance had handed the unit over first
@@ -166,13 +166,12 @@ struct MicUnit {
                               // round_up(sym_limit, 128) symbols (whole 128-symbol chunks) and leave ntok < count: a PREFIX unit,
                               // whose bits behind the prefix are never read (no over-read check)
     // ---- result, decode (behind the inputs above: the older fields keep their offsets) -----
-    uint32_t split[3];        // decode: MIC_SPLIT_* outcome of the split two-state chain, i_sync, j_sync (tokens [i_sync, count) are the states
-                              // sym[j_sync + i - i_sync] until k_dec_translate has moved them); read by mic_hip_debug_split, predicted by
+    uint32_t split[8];        // decode, a unit of a split instance of the two-state chain (k_dec_tans_ls_parts): 0 MIC_SPLIT_* outcome, 1 I_1
+                              // (two parts: i_sync), 2 W (j_sync), 3 I_2, 4 I_3 (two parts: ~0, no such bound) -- tokens [I_p, I_p+1) are the
+                              // states sym[(p - 1) R + W + i - I_p] until k_dec_translate has moved them, I_parts = count --, 5 R (tokens per
+                              // scratch region), 6 the failing boundary (1 .. parts - 1: the join of parts p - 1 and p, parts: the stream's
+                              // end, 0: none), 7 parts.  Read by mic_hip_debug_split and mic_hip_debug_split4, predicted by
                               // tests/tans_split_model.py.  Cleared with the other results
-    uint32_t split4[5];       // decode, a unit of the four-part instance (k_dec_tans_ls_split4): I_1, I_2, I_3 -- tokens [I_p, I_p+1) are the
-                              // states sym[(p - 1) R + W + i - I_p], I_4 = count --, R (tokens per scratch region; 0: not a four-part unit) and
-                              // the failing boundary (1 .. 3: the join of parts p - 1 and p, 4: the stream's end, 0: none); split[] holds the
-                              // outcome, I_1 and W.  Read by mic_hip_debug_split4, predicted by tests/tans_split4_model.py
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }

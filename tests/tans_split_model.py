@@ -1,9 +1,11 @@
-"""CPU model of the split two-state tANS decode (csrc/mic_decode_ls.hip: k_dec_tans_ls_split).
+"""CPU model of the split two-state tANS decode (csrc/mic_decode_ls.hip: k_dec_tans_ls_parts<2> and <4>).
 
 A restatement, in plain Python, of the decode table (tests/table_routes.py: dtable), of the two-state decode loop
-(fse2state.go:203-308) and of the split rule: where part 1 starts, the states it starts with, the overlap W, the meeting test and
-the count check.  For an oracle-made stream `Stream.split(W)` predicts what the kernel records in MicUnit.split -- outcome, i_sync,
-j_sync -- exactly, and `Stream.gate` which units k_dec_classify puts on the split list.
+(fse2state.go:203-308) and of the split rule for `n` parts (2 or 4; a chunk is 128 / n symbols): where the parts start, the states
+they start with, the hand-over after W symbols, the n - 1 joins, the room and count checks, and the routing between the two
+instances.  For an oracle-made stream `split_parts` predicts what the kernel records in MicUnit.split -- outcome, I_1 .. I_{n-1} and
+the failing boundary -- exactly, `Stream.split` the same as the two-part instance's (outcome, i_sync, j_sync), `joined` the state
+sequence k_dec_translate reads out of tok and the scratch regions, and `route` the list k_dec_classify puts a unit on.
 
 Positions are counts of unread bits: the decoder reads bits [p - n, p) and moves to p - n; bits below 0 read as zeros."""
 import numpy as np
@@ -12,7 +14,8 @@ import table_routes as R
 
 NOT_TRIED, DONE, NOT_MET, BAD_COUNT, NO_ROOM = range(5)
 MIN_TOKENS, OVERLAP, MIN_BITS16 = 131072, 32768, 144          # MicSplitCfg's defaults (csrc/mic_dev.h)
-CHUNK = 64
+MIN_TOKENS4 = 262144                                            # MicSplitCfg::min_tokens4
+UNSPLIT, TWO_PARTS, FOUR_PARTS = "class 0", "split", "split4"   # the lists of k_dec_classify a class-0 unit can land on
 _PAD = 16                                                       # zero bytes in front of the stream: reads below bit 0
 
 
@@ -74,49 +77,14 @@ class Stream:
                 and 128 * self.nbytes >= min_bits16 * self.count)
 
     def split_start(self, W):
-        wb = min(W * self.bits // self.count, self.bits)
-        return (self.bits + wb) // 2
+        return starts(self, W, 2)[1]
 
     def split(self, W=OVERLAP, cap=None):
-        """(outcome, i_sync, j_sync) of the kernel for overlap W; cap: tokens of the scratch slab (default: enough)"""
-        T = self.count
-        W &= ~63
-        wc, j_sync = W // CHUNK, W
-        if wc >= T // CHUNK + 2:
-            return NOT_MET, 0, j_sync
-        pm = self.split_start(W)
-        p1, a, b = self.start(pm)
-        s1 = [a, b]
-        p1 = self.run(p1, s1, 0, j_sync)                                 # part 1 after Wc chunks: the meeting point
-        # part 0: its last chunk start above p1 (every chunk start before part 1 has got there)
-        p, a0, b0 = self.start(self.bits)
-        s = [a0, b0]
-        snap = (0, p, list(s))
-        for c in range(T // CHUNK + 2):
-            if c >= wc and p <= p1:
-                break
-            snap = (c, p, list(s))
-            p = self.run(p, s, c * CHUNK, CHUNK)
-        c, p, s = snap
-        i, met = c * CHUNK, False
-        for _ in range(CHUNK + 1):
-            if p < p1:
-                break
-            if p == p1:
-                met = s[i & 1] == s1[0] and s[(i + 1) & 1] == s1[1]
-                break
-            p = self.run(p, s, i, 1)
-            i += 1
-        if not met:
-            return NOT_MET, 0, j_sync
-        j_end = T - i + j_sync
-        room = (min(cap, T) if cap is not None else T) & ~63
-        if i > (T // CHUNK) * CHUNK or j_end > room:
-            return NO_ROOM, i, j_sync
-        # the over-read rule at the stream's last symbol (bitreader.go:113-120), on part 1's own count
-        if self.run(p1, list(s1), j_sync, j_end - j_sync) < 0:
-            return BAD_COUNT, i, j_sync
-        return DONE, i, j_sync
+        """(outcome, i_sync, j_sync) of the two-part instance for overlap W; cap: tokens of the scratch slab (default: enough).
+        Its one region is clamped by the stream's own length (LsParts<2>::region)"""
+        room = (self.count if cap is None else min(cap, self.count)) & ~63
+        outcome, I, _ = split_parts(self, W, R=room, n=2)
+        return outcome, I[0], W & ~63
 
     def meeting_distance(self, start_bit, s0, s1, limit):
         """symbols a decoder started at `start_bit` with states (s0, s1) runs before it has fallen in with the true decode (same
@@ -138,3 +106,127 @@ class Stream:
             if p < 0:
                 break
         return None
+
+
+def route(s, min_tokens=MIN_TOKENS, min_tokens4=MIN_TOKENS4, min_bits16=MIN_BITS16):
+    if not s.gate(min_tokens=min_tokens, min_bits16=min_bits16):
+        return UNSPLIT
+    return FOUR_PARTS if s.count >= min_tokens4 else TWO_PARTS
+
+
+def region(px):
+    """R, the tokens of a scratch region, of a tier-1 four-part unit of `px` pixels: a third of its token slab, in whole chunks"""
+    return ((px + px // 8 + 4096) // 3) & ~31
+
+
+def starts(s, W, n=4):
+    """the bit positions the n parts start at"""
+    wb = min(W * s.bits // s.count, s.bits)
+    x = (s.bits + (n - 1) * wb) // n
+    return [s.bits] + [(n - p) * x - (n - 1 - p) * wb for p in range(1, n)]
+
+
+class Parts:
+    """what the chunk loop of n parts leaves behind: per part the hand-over (position, states) after W steps and the snapshot
+    (chunk, position, states) it is joined from; `steps[p]` holds part p's states, step by step, when `keep` is set"""
+
+    def __init__(self, s, W, keep=False, n=4):
+        T = s.count
+        self.n, self.chunk = n, 128 // n
+        self.W = W = W & ~63
+        wc, cap = W // self.chunk, T // self.chunk + 2
+        self.handed = wc < cap
+        self.hand, self.snap, self.steps = [None] * n, [None] * n, [[] for _ in range(n)]
+        if not self.handed:
+            return
+        pos = starts(s, W, n)
+        # the hand-overs first: every part's position and states after wc chunks
+        for p in range(1, n):
+            q, a, b = s.start(pos[p])
+            st = [a, b]
+            q = s.run(q, st, 0, W)
+            self.hand[p] = (q, st[0], st[1])
+        for p in range(n):
+            q, a, b = s.start(pos[p])
+            st = [a, b]
+            snap = (0, q, list(st))
+            out = self.steps[p] if keep else None
+            for c in range(cap):
+                if p == n - 1:
+                    on = q > 0                                           # bits left
+                else:
+                    on = c < wc or q > self.hand[p + 1][0]
+                if on:
+                    snap = (c, q, list(st))
+                elif c >= wc:
+                    break                                                # (the kernel runs on while a neighbour is on; nothing is read of that)
+                q = s.run(q, st, c * self.chunk, self.chunk, out)
+            self.snap[p] = snap
+
+    def join(self, s, p):
+        """boundary p | p + 1 -> part p's step index where its position and states are part p + 1's hand-over, or None"""
+        c, q, st = self.snap[p]
+        st = list(st)
+        qn, a, b = self.hand[p + 1]
+        i = c * self.chunk
+        for _ in range(self.chunk + 1):
+            if q < qn:
+                return None
+            if q == qn:
+                if i >= (self.W if p else 0) and st[i & 1] == a and st[(i + 1) & 1] == b:
+                    return i
+                return None
+            q = s.run(q, st, i, 1)
+            i += 1
+        return None
+
+
+def split_parts(s, W=OVERLAP, R=None, parts=None, n=4):
+    """(outcome, (I_1 .. I_{n-1}), failing boundary) of the kernel for overlap W and regions of R tokens (default: enough)"""
+    T = s.count
+    P = parts or Parts(s, W, n=n)
+    W, n, chunk = P.W, P.n, P.chunk
+    R = (1 << 30) if R is None else R
+    I = [0] * (n - 1)
+    if not P.handed:
+        return NOT_MET, tuple(I), 1
+    at = 0
+    for b in range(n - 1):
+        e = P.join(s, b)
+        if e is None:
+            return NOT_MET, tuple(I), b + 1
+        at = at + e - W if b else e
+        I[b] = at
+        if (e > R) if b else (at > (T // chunk) * chunk):
+            return NO_ROOM, tuple(I), b + 1
+    if I[-1] > T:
+        return BAD_COUNT, tuple(I), n
+    j_end = T - I[-1] + W
+    if j_end > R:
+        return NO_ROOM, tuple(I), n
+    c, q, st = P.snap[n - 1]
+    js = c * chunk
+    if j_end > js:
+        # the over-read rule at the stream's last symbol (bitreader.go:113-120), on the last part's own count, from its last chunk
+        # start with bits left; more than a chunk behind it: the chunk behind the snapshot started without bits
+        if j_end - js > chunk or s.run(q, list(st), js, j_end - js) < 0:
+            return BAD_COUNT, tuple(I), n
+    return DONE, tuple(I), 0
+
+
+split4 = split_parts                                            # (n = 4 is the default)
+
+
+def joined(s, W=OVERLAP, n=4):
+    """the states k_dec_translate reads of a DONE unit: tok[i] below I_1, then part p's steps W + i - I_p"""
+    P = Parts(s, W, keep=True, n=n)
+    outcome, I, _ = split_parts(s, W, parts=P)
+    assert outcome == DONE, outcome
+    bounds = [0, *I, s.count]
+    out = list(P.steps[0][:I[0]])
+    for p in range(1, n):
+        k = bounds[p + 1] - bounds[p]
+        seg = P.steps[p][P.W:P.W + k]
+        assert len(seg) == k, (p, len(seg), k)
+        out += seg
+    return out, I

@@ -1,4 +1,4 @@
-"""The split instance of the two-state tANS chain (k_dec_tans_ls_split, csrc/mic_decode_ls.hip) at its seams, on small units.
+"""The two-part instance of the two-state tANS chain (k_dec_tans_ls_parts<2>, csrc/mic_decode_ls.hip) at its seams, on small units.
 
 The units are thin strips of the headline's frame (2577 columns, 24 .. 40 rows of 12-bit xr_like at the published noise: 60 - 100 k
 tokens, about 9.6 bits each), coded by the oracle; the session's split gate and overlap are lowered through the debug setter so that
@@ -197,6 +197,28 @@ def test_an_overlap_too_small_to_meet_in_hands_the_unit_back(mic, mico, synth, g
         for _ in range(2):
             st, rec, split, imgs, _ = _decode(mic, torch, sess, cand)
             _check(cand, want, st, rec, split, imgs)
+    finally:
+        sess.close()
+
+
+def test_a_stream_shorter_than_the_overlap_beside_a_longer_one(mic, mico, synth, gpu_ready):
+    """the per-stream chunk cap: the hand-over after W = 65536 symbols lies behind everything a 60 k-token strip has to decode, but
+    inside its 100 k-token neighbour's chunks, so the wave's loop runs up to the hand-over all the same; the short unit is not met
+    (its own cap, the model's rule) and comes back through the retry list, the long one is handed over and recorded as modelled"""
+    torch = pytest.importorskip("torch")
+    cand = _units(mico, synth)[0]
+    W, units = 65536, [cand[3], cand[5]]                                      # 24 and 40 rows
+    want = [_expect(u, W) for u in units]
+    # the CPU side: Wc against each stream's own cap; both pass the gate onto the two-part list, where they are neighbours: units 0
+    # and 1 of the batch are streams 0 and 1 of the first wave
+    assert W // 64 >= units[0].ntok // 64 + 2 and W // 64 < units[1].ntok // 64 + 2, [u.ntok for u in units]
+    assert all(M.route(u.model, min_tokens=MIN_TEST) == M.TWO_PARTS for u in units)
+    assert want[0] == (M.NOT_MET, 0, W) and want[1][0] != M.NOT_TRIED and want[1][2] == W, want
+    sess = mic.Session(len(units), max(u.img.size for u in units))
+    try:
+        _configure(mic, sess, overlap=W)
+        st, rec, split, imgs, _ = _decode(mic, torch, sess, units)
+        _check(units, want, st, rec, split, imgs)
     finally:
         sess.close()
 

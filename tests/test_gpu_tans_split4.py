@@ -1,10 +1,10 @@
-"""The four-part instance of the two-state tANS chain (k_dec_tans_ls_split4, csrc/mic_decode_ls.hip) at its seams, on small units.
+"""The four-part instance of the two-state tANS chain (k_dec_tans_ls_parts<4>, csrc/mic_decode_ls.hip) at its seams, on small units.
 
 The units are strips of the headline's frame (2577 columns, 44 .. 72 rows of 12-bit xr_like at the published noise: 110 - 180 k
 tokens, about 9.6 bits each), coded by the oracle; the session's four-part threshold is lowered to 65536 tokens and the overlap
 set to 8192 through the debug setters so that such units take the four-part instance.  What the kernel must make of each unit --
 joined or handed back, where the three joins lie and which boundary failed -- is worked out on the CPU by
-tests/tans_split4_model.py; the library is asked for its record (MicUnit.split / split4 through mic_hip_debug_split4) and for the
+tests/tans_split_model.py; the library is asked for its record (MicUnit.split through mic_hip_debug_split4) and for the
 pixels, which must be the source's bit for bit.
 
 The unit that has to stay with the two-part instance is a 24-row strip (60 k tokens): with the four-part threshold at 65536 a
@@ -17,9 +17,10 @@ import functools
 import numpy as np
 import pytest
 
-import tans_split4_model as M4
 import tans_split_model as M
 import test_gpu_tans_split as S2
+
+M4 = M                                             # (one model for both part counts; four parts are its default)
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +167,30 @@ def test_an_overlap_too_small_to_meet_in_hands_the_units_back(mic, mico, synth, 
         for _ in range(2):
             st, rec, split, rec4, imgs, _ = _decode(mic, torch, sess, cand)
             _check(cand, want, st, rec, split, rec4, imgs)
+    finally:
+        sess.close()
+
+
+def test_a_stream_shorter_than_the_overlap_beside_a_longer_one(mic, mico, synth, gpu_ready):
+    """the per-stream chunk cap: the hand-over after W = 131072 symbols lies behind everything a 110 k-token strip has to decode,
+    but inside its 180 k-token neighbour's chunks; the short unit is not met at boundary 1 (no hand-over of its own), the long one
+    is handed over and recorded as modelled -- a part's W steps alone overrun a region of about 70 k tokens"""
+    torch = pytest.importorskip("torch")
+    cand = _units(mico, synth)[0]
+    W, units = 131072, [cand[14], cand[10]]
+    assert [u.img.shape[0] for u in units] == [44, 72]
+    want = [_expect(u, W) for u in units]
+    # the CPU side: Wc against each stream's own cap; both pass the gate onto the four-part list, where they are neighbours: units 0
+    # and 1 of the batch are streams 0 and 1 of the first wave
+    assert W // 32 >= units[0].ntok // 32 + 2 and W // 32 < units[1].ntok // 32 + 2, [u.ntok for u in units]
+    assert all(M4.route(u.model, MIN_TEST, MIN4_TEST) == M4.FOUR_PARTS for u in units)
+    assert want[0][1][:2] == (M.NOT_MET, (0, 0, 0)) and want[0][1][4] == 1, want
+    assert want[1][1][0] != M.NOT_TRIED and want[1][1][3] == M4.region(units[1].img.size) < W, want
+    sess = mic.Session(len(units), max(u.img.size for u in units))
+    try:
+        _configure(mic, sess, overlap=W)
+        st, rec, split, rec4, imgs, _ = _decode(mic, torch, sess, units)
+        _check(units, want, st, rec, split, rec4, imgs)
     finally:
         sess.close()
 

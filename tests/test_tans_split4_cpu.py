@@ -1,12 +1,13 @@
-"""The CPU model of the four-part split decode (tests/tans_split4_model.py) against the oracle's own streams: the states read out
+"""The CPU model of the four-part split decode (tests/tans_split_model.py) against the oracle's own streams: the states read out
 of part 0's tok and the three scratch regions are the plain decode's, units are routed by length between the two split
 instances, and no part's output can leave its region.  No GPU."""
 import functools
 
 import numpy as np
 
-import tans_split4_model as M4
 import tans_split_model as M
+
+M4 = M                                             # (one model for both part counts; four parts are its default)
 
 W = 8192
 

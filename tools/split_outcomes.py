@@ -1,4 +1,4 @@
-"""Diagnostic: what the split instances of the two-state tANS chain (k_dec_tans_ls_split4, k_dec_tans_ls_split) make of the headline
+"""Diagnostic: what the split instances of the two-state tANS chain (k_dec_tans_ls_parts<4>, k_dec_tans_ls_parts<2>) make of the headline
 step's strips -- per step the count of units by instance and MicUnit.split outcome (not tried / split / handed back and why, for
 four-part units with the boundary that failed), and the spread of the first join.
 usage: tools/split_outcomes.py [frames=288] [steps=20]"""
