@@ -972,6 +972,94 @@ int mic_hip_session_strips_read_crops(mic_hip_session *s,
                                       void *d_out, size_t out_cap,
                                       int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats);
 
+/* ---- typed, scaled and channel-first output of the patch and crop readers ------------------------ */
+/* The thirteen readers of many rectangles per call write the file's own sample format (u16, u8, interleaved u8 RGB).  Their _as
+ * twins below take the same arguments and a trailing output description, and write the tensor a model consumes from the same
+ * one gather: no cast, multiply-add or permute kernel behind it (no reference counterpart).
+ * The value of an output sample, which a host reference reproduces bit for bit: x = the decoded sample as float (exact: at
+ * most 65535); v = fmaf(x, a, b), ONE rounding, (a, b) the pair of the sample's source and channel; with CLAMP
+ * v = fminf(fmaxf(v, clamp_lo), clamp_hi); then F32 stores v, F16 and BF16 convert that f32 value round-to-nearest-even (overflow
+ * to +-inf), U8 and U16 store rintf(v) (ties to even) saturated to the type's range.
+ * A source is what the multi doors index: a slide, a volume, a strip file; 0 in the one-source doors.  naffine picks the pair:
+ * 0 = (1, 0) for all (affine may be NULL), 1 = one pair, C = one per channel, nsources * C = one per (source, channel), source-major.
+ * pad is the value, converted to the output type as v is but with no affine and no clamp, of every sample the native door leaves 0
+ * by definition: outside the level, image or volume, rows no strip covers, rectangles of a refused or missing source, patches with a
+ * bad level.  A rectangle whose unit failed stays unspecified, with the status the native door gives it.
+ * With CHANNELS_FIRST the tensor is n x C x ph x pw instead of n x ph x pw x C (C = 3: RGB slides); the flag is ignored when C == 1.
+ * d_out must be aligned to the output sample (2 or 4 bytes) and out_cap hold the typed tensor; the order of the checks and their
+ * codes are the native door's.  spec NULL or dtype NATIVE is the native door itself: same bytes, statuses, stats and kernels.
+ * MIC2 temporal volumes keep their running sums in a u16 staging tensor of the session's workspace (the tensor's shape) and one
+ * convert kernel writes the typed samples at the end of the call; independent volumes of the same call gather directly. */
+#define MIC_HIP_OUT_NATIVE 0   /* the door's present format; everything else in the spec must be at its default */
+#define MIC_HIP_OUT_U8     1
+#define MIC_HIP_OUT_U16    2
+#define MIC_HIP_OUT_F16    3
+#define MIC_HIP_OUT_BF16   4
+#define MIC_HIP_OUT_F32    5
+#define MIC_HIP_OUT_CHANNELS_FIRST 1u   /* flags: n x C x ph x pw instead of n x ph x pw x C; ignored when C == 1 */
+#define MIC_HIP_OUT_CLAMP          2u   /* flags: clamp to [clamp_lo, clamp_hi] behind the affine; needs lo < hi */
+typedef struct {
+    int32_t dtype; uint32_t flags;
+    const float *affine;   /* naffine pairs (a, b); NULL with naffine 0 = (1, 0) */
+    int32_t naffine;       /* 0; 1 = one pair; C = one per channel; nsources * C = one per (source, channel) */
+    float clamp_lo, clamp_hi;
+    float pad;             /* the value, in the output type, of every sample the native door leaves 0 by definition */
+} mic_hip_out_spec;
+/* The one judgement of a spec, for a door whose sources have `channels` samples a pixel of bits_per_sample bits (8 or 16) and that
+ * takes nsources sources (1: a one-source door).  MIC_ERR_ARGS for a NULL spec or sample_bytes, an unknown dtype or flag bit,
+ * naffine none of 0, 1, channels, nsources * channels, a NULL affine with naffine > 0, CLAMP with clamp_lo >= clamp_hi, a
+ * non-finite a, b, clamp_lo, clamp_hi or pad, and NATIVE with anything else non-default (flags, affine, naffine, clamp, pad).
+ * Otherwise MIC_OK and *sample_bytes = 1, 2 or 4: the bytes of one output sample (NATIVE: the source format's).  Needs no device;
+ * every _as door calls it before anything is judged that needs one. */
+int mic_hip_out_spec_check(const mic_hip_out_spec *spec, int channels, int bits_per_sample, int nsources, size_t *sample_bytes);
+
+int mic_hip_wsi_read_patches_as(const uint8_t *compressed, size_t compressed_len, int level, const int32_t *xy, int n, int pw, int ph,
+                                void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_wsi_reader_read_patches_as(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_wsi_multi_read_patches_as(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats,
+                                      const mic_hip_out_spec *spec);
+int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int nreaders,
+                                        const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats,
+                                        const mic_hip_out_spec *spec);
+int mic_hip_mic2_read_crops_as(const uint8_t *compressed, size_t compressed_len,
+                               const int32_t *xyz, int n, int cw, int ch, int cd,
+                               void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_mic2_reader_read_crops_as(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
+                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_session_mic2_read_crops_as(mic_hip_session *s, const uint8_t *head, size_t head_len,
+                                       const uint8_t *d_file, size_t file_len,
+                                       const int32_t *xyz, int n, int cw, int ch, int cd,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_mic2_multi_read_crops_as(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                     const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                     int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_mic2_readers_read_crops_as(mic_hip_mic2_reader *const *readers, int nreaders,
+                                       const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                       int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_session_mic2_multi_read_crops_as(mic_hip_session *s,
+                                             const uint8_t *const *heads, const size_t *head_lens,
+                                             const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                             const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                             int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats,
+                                             const mic_hip_out_spec *spec);
+int mic_hip_strips_read_crops_as(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                 const int32_t *xyf, int n, int cw, int ch,
+                                 void *d_out, size_t out_cap,
+                                 int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats, const mic_hip_out_spec *spec);
+int mic_hip_session_strips_read_crops_as(mic_hip_session *s,
+                                         const uint8_t *const *heads, const size_t *head_lens,
+                                         const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                         const int32_t *xyf, int n, int cw, int ch,
+                                         void *d_out, size_t out_cap,
+                                         int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats,
+                                         const mic_hip_out_spec *spec);
+
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);
 /* Per-kernel device time (ms, HIP events on the session stream) of the last enqueue:

@@ -244,7 +244,24 @@ ABI_SYMBOLS = [
     "mic_hip_session_encode_enqueue", "mic_hip_session_encode_finish",
     "mic_hip_session_decode_enqueue", "mic_hip_session_decode_finish",
     "mic_hip_session_set_timing", "mic_hip_session_last_timings",
+    "mic_hip_out_spec_check",
+    "mic_hip_wsi_read_patches_as",
+    "mic_hip_wsi_reader_read_patches_as",
+    "mic_hip_session_wsi_read_patches_as",
+    "mic_hip_wsi_multi_read_patches_as",
+    "mic_hip_wsi_readers_read_patches_as",
+    "mic_hip_mic2_read_crops_as",
+    "mic_hip_mic2_reader_read_crops_as",
+    "mic_hip_session_mic2_read_crops_as",
+    "mic_hip_mic2_multi_read_crops_as",
+    "mic_hip_mic2_readers_read_crops_as",
+    "mic_hip_session_mic2_multi_read_crops_as",
+    "mic_hip_strips_read_crops_as",
+    "mic_hip_session_strips_read_crops_as",
 ]
+
+# the readers of many rectangles per call; each has an _as twin that takes a trailing mic_hip_out_spec (OutSpec)
+_RECT_DOORS = [s_[:-3] for s_ in ABI_SYMBOLS if s_.endswith("_as")]
 
 _lib: Optional[C.CDLL] = None
 # mic_hip_write_fn / mic_hip_read_fn (include/mic_hip.h)
@@ -474,10 +491,73 @@ def lib() -> C.CDLL:
     L.mic_hip_session_decode_enqueue.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                                  C.POINTER(Unit), C.c_int, C.c_void_p]
     L.mic_hip_session_decode_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    for name in _RECT_DOORS:
+        getattr(L, name + "_as").argtypes = getattr(L, name).argtypes + [C.c_void_p]
+    L.mic_hip_out_spec_check.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     L.mic_hip_session_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.mic_hip_session_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     _lib = L
     return L
+
+
+class _OutSpecStruct(C.Structure):
+    """mic_hip_out_spec"""
+    _fields_ = [("dtype", C.c_int32), ("flags", C.c_uint32), ("affine", C.c_void_p), ("naffine", C.c_int32),
+                ("clamp_lo", C.c_float), ("clamp_hi", C.c_float), ("pad", C.c_float)]
+
+
+OUT_DTYPES = {"native": 0, "u8": 1, "u16": 2, "f16": 3, "bf16": 4, "f32": 5}
+OUT_CHANNELS_FIRST, OUT_CLAMP = 1, 2
+
+
+class OutSpec:
+    """mic_hip_out_spec: what the patch and crop readers write when they are given ``spec=``.  dtype: "u8", "u16", "f16", "bf16",
+    "f32" (or "native": the door's own format, everything else at its default).  affine: None, or pairs (a, b) -- one, one per
+    channel, or one per (source, channel), source-major -- as anything np.asarray turns into an (n, 2) float32 array: the sample is
+    fmaf(x, a, b).  clamp: None or (lo, hi), applied behind the affine.  pad: the value of every sample the native door leaves 0
+    by definition.  The object keeps the struct and the affine array alive; pass it to as many calls as you like."""
+
+    def __init__(self, dtype="f32", channels_first: bool = False, affine=None, clamp=None, pad: float = 0.0):
+        if dtype not in OUT_DTYPES:
+            raise ValueError(f"OutSpec: unknown dtype {dtype!r}")
+        self.dtype = dtype
+        self.channels_first = bool(channels_first)
+        self._affine = None if affine is None else np.ascontiguousarray(np.asarray(affine, dtype=np.float32).reshape(-1, 2))
+        lo, hi = (0.0, 0.0) if clamp is None else clamp
+        flags = (OUT_CHANNELS_FIRST if channels_first else 0) | (OUT_CLAMP if clamp is not None else 0)
+        self.struct = _OutSpecStruct(OUT_DTYPES[dtype], flags, None if self._affine is None else self._affine.ctypes.data,
+                                     0 if self._affine is None else len(self._affine), lo, hi, pad)
+
+    def ref(self):
+        return C.addressof(self.struct)
+
+    def sample_bytes(self, channels: int = 1, bits: int = 16, nsources: int = 1) -> int:
+        """bytes of one output sample for sources of `channels` samples a pixel and `bits` bits a sample (out_spec_check)"""
+        return out_spec_check(self, channels, bits, nsources)
+
+    def shape(self, n: int, *dims: int, channels: int = 1) -> Tuple[int, ...]:
+        """the tensor's shape for n rectangles of `dims` (ph, pw or cd, ch, cw): channels last unless channels_first; no channel
+        axis for one channel"""
+        if channels == 1:
+            return (n, *dims)
+        return (n, channels, *dims) if self.channels_first else (n, *dims, channels)
+
+
+def out_spec_check(spec: OutSpec, channels: int = 1, bits_per_sample: int = 16, nsources: int = 1) -> int:
+    """mic_hip_out_spec_check: the bytes of one output sample, or MicError(MIC_ERR_ARGS) for a spec the doors refuse.  No device."""
+    nb = C.c_size_t(0)
+    rc = lib().mic_hip_out_spec_check(spec.ref() if spec is not None else None, channels, bits_per_sample, nsources, C.byref(nb))
+    if rc:
+        _raise(rc, "out_spec_check")
+    return nb.value
+
+
+def _door(name: str, spec: Optional[OutSpec]):
+    """the C entry point of a rectangle reader: the native symbol, or with a spec its _as twin with the spec bound as last argument"""
+    if spec is None:
+        return getattr(lib(), name)
+    twin = getattr(lib(), name + "_as")
+    return lambda *a: twin(*a, spec.ref())
 
 
 def device_name() -> str:
@@ -951,12 +1031,12 @@ def _read_crops(call, xyz, d_out: int, out_cap: int):
     return rc, st, dict(frames_decoded=cs.frames_decoded, pieces=cs.pieces, slabs=cs.slabs)
 
 
-def mic2_read_crops(compressed, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+def mic2_read_crops(compressed, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
     """mic_hip_mic2_read_crops: the cw x ch x cd crops at the (x, y, z) origins `xyz` of a MIC2 file (z = frame index), into the
     caller's device tensor d_out (an int: ``torch.empty((n, cd, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned
     host memory) of out_cap bytes.  Samples outside the volume are 0.  -> (status per crop, dict(frames_decoded, pieces, slabs))."""
     c = _bytes_arr(compressed)
-    rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_mic2_read_crops(
+    rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: _door("mic_hip_mic2_read_crops", spec)(
         c.ctypes.data, c.size, a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
     if rc:
         _raise(rc, "mic2_read_crops")
@@ -1010,14 +1090,14 @@ def _read_multi_crops(call, xyzv, d_out: int, out_cap: int):
     return rc, st, bad, dict(frames_decoded=cs.frames_decoded, pieces=cs.pieces, slabs=cs.slabs, volumes_read=cs.volumes_read)
 
 
-def mic2_multi_read_crops(files, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+def mic2_multi_read_crops(files, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
     """mic_hip_mic2_multi_read_crops: the cw x ch x cd crops (x, y, z, volume) `xyzv` of the MIC2 files `files` (host buffers;
     volume = an index into the list; an entry no crop names may be None), into the caller's device tensor d_out (an int:
     ``torch.empty((n, cd, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned host memory) of out_cap bytes.  The
     volumes may differ in size, depth and pipeline; one that does not parse fails alone.  Samples outside a volume are 0.
     -> (status per crop, failed frame per crop (-1: none), dict(frames_decoded, pieces, slabs, volumes_read))."""
     arrs, ptrs, lens = _volume_table(files)
-    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_mic2_multi_read_crops(
+    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_mic2_multi_read_crops", spec)(
         ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, cw, ch, cd, d, cap, s, b, p), xyzv, d_out, out_cap)
     if rc:
         _raise(rc, "mic2_multi_read_crops")
@@ -1085,14 +1165,14 @@ def _read_strip_crops(call, xyf, d_out: int, out_cap: int):
     return rc, st, bad, dict(strips_decoded=cs.strips_decoded, strips_total=cs.strips_total, pieces=cs.pieces, slabs=cs.slabs)
 
 
-def strips_read_crops(files, xyf, cw: int, ch: int, d_out: int, out_cap: int):
+def strips_read_crops(files, xyf, cw: int, ch: int, d_out: int, out_cap: int, spec=None):
     """mic_hip_strips_read_crops: the cw x ch crops at the (x, y, file) triples `xyf` of the PICS / PICA files `files` (host
     buffers; file = an index into the list), into the caller's device tensor d_out (an int:
     ``torch.empty((n, ch, cw), dtype=torch.uint16, device="cuda").data_ptr()``, or pinned host memory) of out_cap bytes.  Samples
     outside an image are 0.  Only the strips the crops overlap are uploaded and decoded.
     -> (status per crop, failed strip per crop (-1: none), dict(strips_decoded, strips_total, pieces, slabs))."""
     arrs, ptrs, lens = _file_table(files)
-    rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_strips_read_crops(
+    rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_strips_read_crops", spec)(
         ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, cw, ch, d, cap, s, b, p), xyf, d_out, out_cap)
     if rc:
         _raise(rc, "strips_read_crops")
@@ -1410,12 +1490,12 @@ def _read_patches(where: str, call, xy, d_out: int, out_cap: int):
     return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs)
 
 
-def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
     """mic_hip_wsi_read_patches: the pw x ph patches at the (x, y) origins `xy` of one level, into the caller's device tensor
     d_out (an int: ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit
     greyscale) of out_cap bytes.  Pixels outside the level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs))."""
     c = _bytes_arr(compressed)
-    rc, st, stats = _read_patches("wsi_read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_wsi_read_patches(
+    rc, st, stats = _read_patches("wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_read_patches", spec)(
         c.ctypes.data, c.size, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
     if rc:
         _raise(rc, "wsi_read_patches")
@@ -1459,14 +1539,14 @@ def _read_multi_patches(call, xysl, d_out: int, out_cap: int):
     return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs, slides_read=ps.slides_read)
 
 
-def wsi_multi_read_patches(files, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8):
+def wsi_multi_read_patches(files, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None):
     """mic_hip_wsi_multi_read_patches: the pw x ph patches (x, y, slide, level) `xysl` of the MIC3 files `files` (host buffers;
     slide = an index into the list), into the caller's device tensor d_out (an int:
     ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit greyscale; or pinned host
     memory) of out_cap bytes.  Every file must have the call's sample format; one that has not, or does not parse, fails alone.
     Pixels outside a level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs, slides_read))."""
     arrs, ptrs, lens = _file_table(files)
-    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: lib().mic_hip_wsi_multi_read_patches(
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_multi_read_patches", spec)(
         ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
     if rc:
         _raise(rc, "wsi_multi_read_patches")
@@ -1624,9 +1704,9 @@ class WsiReader:
                                                                   C.byref(ow), C.byref(oh)), "WsiReader.region")
         return _wsi_shape(self.info, out, ow.value, oh.value)
 
-    def read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+    def read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
         """as wsi_read_patches on the whole file; only the blobs of the tiles the patches touch are read, each once"""
-        rc, st, stats = _read_patches("WsiReader.read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_wsi_reader_read_patches(
+        rc, st, stats = _read_patches("WsiReader.read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_reader_read_patches", spec)(
             self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
         self._cb.check(rc, "WsiReader.read_patches")
         return st, stats
@@ -1649,12 +1729,12 @@ class WsiReader:
             pass
 
 
-def wsi_readers_read_patches(readers, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8):
+def wsi_readers_read_patches(readers, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None):
     """mic_hip_wsi_readers_read_patches: wsi_multi_read_patches over a sequence of WsiReader (slide = an index into it; an entry
     no patch names may be None and is never read).  Only the blobs of the tiles the patches touch are read, each once."""
     readers = list(readers)
     hs = np.asarray([(r._h.value or 0) if r is not None else 0 for r in readers], dtype=np.uintp)
-    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: lib().mic_hip_wsi_readers_read_patches(
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_readers_read_patches", spec)(
         hs.ctypes.data, len(readers), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
     for r in readers:                                  # an exception a source raised comes first
         if r is not None and r._cb.exc is not None:
@@ -1687,9 +1767,9 @@ class Mic2Reader:
         w, h, n, t = (x.value for x in v)
         return dict(width=w, height=h, nframes=n, temporal=bool(t))
 
-    def read_crops(self, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    def read_crops(self, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
         """as mic2_read_crops on the whole file; only the streams of the plan's frames are read, each once"""
-        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_mic2_reader_read_crops(
+        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: _door("mic_hip_mic2_reader_read_crops", spec)(
             self._h, a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
         self._cb.check(rc, "Mic2Reader.read_crops")
         return st, stats
@@ -1712,12 +1792,12 @@ class Mic2Reader:
             pass
 
 
-def mic2_readers_read_crops(readers, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+def mic2_readers_read_crops(readers, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
     """mic_hip_mic2_readers_read_crops: mic2_multi_read_crops over a sequence of Mic2Reader (volume = an index into it; an entry no
     crop names may be None and is never read).  Only the streams of the plan's frames are read, each once."""
     readers = list(readers)
     hs = np.asarray([(r._h.value or 0) if r is not None else 0 for r in readers], dtype=np.uintp)
-    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_mic2_readers_read_crops(
+    rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_mic2_readers_read_crops", spec)(
         hs.ctypes.data, len(readers), a, n, cw, ch, cd, d, cap, s, b, p), xyzv, d_out, out_cap)
     for r in readers:                                  # an exception a source raised comes first
         if r is not None and r._cb.exc is not None:
@@ -2182,25 +2262,25 @@ class Session:
         if rc:
             _raise(rc, "session_wsi_decode_level")
 
-    def wsi_read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int):
+    def wsi_read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
         """wsi_read_patches from the slide wsi_encode left in the session (it stays in HBM); d_out on the session's device"""
-        rc, st, stats = _read_patches("session_wsi_read_patches", lambda a, n, d, cap, s, p: lib().mic_hip_session_wsi_read_patches(
+        rc, st, stats = _read_patches("session_wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_session_wsi_read_patches", spec)(
             self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
         if rc:
             _raise(rc, "session_wsi_read_patches")
         return st, stats
 
-    def mic2_read_crops(self, head, d_file: int, file_len: int, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    def mic2_read_crops(self, head, d_file: int, file_len: int, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
         """mic2_read_crops of a MIC2 file that lies on the session's device: head = its first 20 + 8 * nframes bytes (host),
         d_file = the whole file (file_len bytes) in device memory; the streams go device to device"""
         hd = _bytes_arr(head)
-        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: lib().mic_hip_session_mic2_read_crops(
+        rc, st, stats = _read_crops(lambda a, n, d, cap, s, p: _door("mic_hip_session_mic2_read_crops", spec)(
             self._h, hd.ctypes.data, hd.size, int(d_file) or None, int(file_len), a, n, cw, ch, cd, d, cap, s, p), xyz, d_out, out_cap)
         if rc:
             _raise(rc, "session_mic2_read_crops")
         return st, stats
 
-    def mic2_multi_read_crops(self, heads, d_files, lens, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int):
+    def mic2_multi_read_crops(self, heads, d_files, lens, xyzv, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
         """mic2_multi_read_crops of MIC2 files that lie on the session's device: heads[v] = the first 20 + 8 * nframes bytes of volume
         v (host; None for a volume no crop names), d_files[v] = the device address of the whole file (0 / None when none of its
         frames is needed), lens[v] its length.  The streams of the needed frames go device to device."""
@@ -2209,7 +2289,7 @@ class Session:
         flens = np.asarray([int(n) for n in lens], dtype=np.uintp)
         if not (len(harrs) == dptrs.size == flens.size):
             raise ValueError("heads, d_files and lens must name the same volumes")
-        rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_session_mic2_multi_read_crops(
+        rc, st, bad, stats = _read_multi_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_session_mic2_multi_read_crops", spec)(
             self._h, hptrs.ctypes.data, hlens.ctypes.data, dptrs.ctypes.data, flens.ctypes.data, len(harrs), a, n, cw, ch, cd, d, cap, s, b, p),
             xyzv, d_out, out_cap)
         if rc:
@@ -2269,7 +2349,7 @@ class Session:
             _raise(rc, "session_mic2_decode")
         return st[:n].copy(), bad[:n].copy(), _mic2_stats(bs)
 
-    def strips_read_crops(self, heads, d_files, lens, xyf, cw: int, ch: int, d_out: int, out_cap: int):
+    def strips_read_crops(self, heads, d_files, lens, xyf, cw: int, ch: int, d_out: int, out_cap: int, spec=None):
         """strips_read_crops of PICS / PICA files that lie on the session's device: heads[f] = strips_head(file f) (host),
         d_files[f] = the device address of the whole file, lens[f] its length.  The streams of the needed strips go device to
         device."""
@@ -2278,7 +2358,7 @@ class Session:
         flens = np.asarray([int(n) for n in lens], dtype=np.uintp)
         if not (len(harrs) == dptrs.size == flens.size):
             raise ValueError("heads, d_files and lens must name the same files")
-        rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: lib().mic_hip_session_strips_read_crops(
+        rc, st, bad, stats = _read_strip_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_session_strips_read_crops", spec)(
             self._h, hptrs.ctypes.data, hlens.ctypes.data, dptrs.ctypes.data, flens.ctypes.data, len(harrs), a, n, cw, ch, d, cap, s, b, p),
             xyf, d_out, out_cap)
         if rc:

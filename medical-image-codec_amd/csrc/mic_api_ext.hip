@@ -806,14 +806,17 @@ int plan_patches(int level_w, int level_h, int tw, int th, const int32_t *xy, in
     return MIC_OK;
 }
 
-// What the three one-slide patch entry points check of their arguments before a device is touched; *need = bytes of the patch tensor.
-int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, size_t out_cap, size_t *need) {
+// What the three one-slide patch entry points check of their arguments before a device is touched; o = the output description,
+// *need = bytes of the patch tensor.
+int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const mic_hip_out_spec *spec, OutFormat &o, size_t out_cap, size_t *need) {
     if (level < 0 || level >= m.nlev || pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xy)) return MIC_ERR_ARGS;
     if (!m.supported()) return MIC_ERR_UNSUPPORTED;
+    const int orc = o.make(spec, m.channels, m.bps, 1);
+    if (orc) return orc;
     const Level &L = m.lv[(size_t)level];
     if (L.w <= 0 || L.h <= 0 || m.tw <= 0 || m.th <= 0) return MIC_ERR_CORRUPT;
     if ((size_t)L.tx * m.tw < (size_t)L.w || (size_t)L.ty * m.th < (size_t)L.h) return MIC_ERR_CORRUPT;
-    return tensor_bytes(n, 1, ph, pw, m.bpp(), out_cap, need);
+    return tensor_bytes(n, 1, ph, pw, o.pixel(), out_cap, need);
 }
 
 // Where a call's tiles come from: the planes of units u0 .. u0 + nt - 1 of the plan as nt * P records over *base (device), and each
@@ -824,17 +827,17 @@ typedef std::function<size_t(size_t npx)> SlabCeiling;
 // ... for blobs through the unit codec's workspace (tiles are a launch's grid y)
 SlabCeiling blob_ceiling(size_t P) { return [P](size_t npx) { return std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)); }; }
 
-// The core of every patch call: the plan's pieces into d_out ([patch][ph][pw] pixels of the slides' format, an address s's device
-// can write: patch_pointer; what no piece covers is 0) on a session the caller holds.  um[u]: the header unit u's tile is coded
+// The core of every patch call: the plan's pieces into d_out ([patch][ph][pw] pixels of the slides' format or of o's, an address s's
+// device can write: patch_pointer; what no piece covers is 0, or o's pad) on a session the caller holds.  um[u]: the header unit u's tile is coded
 // under (all of one sample format).  The skeleton is the one the strip and MIC2 crop readers run (mic_rects.h); here are the rule -- as
 // many tiles as `ceiling` allows of the largest, a tile P * tw * th samples of the slab -- and the decode (decode_plane_slab).
 // tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
-int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const SlabCeiling &ceiling,
+int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const OutFormat &o, const SlabCeiling &ceiling,
                  const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
     const size_t nu = plan.units.size();
     int rc;
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the levels, refused slides and patches
+    if ((rc = fill_pad(s->stream, o, d_out, need))) return rc;                              // outside the levels, refused slides and patches
     tile_status.assign(nu, MIC_OK);
     *nslab = 0;
     if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
@@ -849,9 +852,10 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
         return caps.back().second;
     };
     const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_sub_batch(i0, nu, [&](size_t u) { return px[u]; }, cap, CutRule{ ~(size_t)0 }); },
-                                       [&](size_t u) { return P * px[u]; }, plan.pieces, pw, ph, [&](size_t u) { return UnitStride{ um[u]->tw, (int32_t)px[u] }; });
+                                       [&](size_t u) { return P * px[u]; }, plan.pieces, pw, ph, [&](size_t u) { return UnitStride{ um[u]->tw, (int32_t)px[u] }; },
+                                       [&](size_t u) { return plan.units[u].slide; }, o);
     if ((rc = s->wsi_planes.reserve(L.slab_max * 2 + 64))) return rc;
-    if ((rc = upload_gather(s, L))) return rc;
+    if ((rc = upload_gather(s, L, o))) return rc;
     std::vector<WsiPlane> pl; std::vector<int32_t> pst;
     for (size_t b = 0; b < L.subs(); b++, ++*nslab) {
         const size_t u0 = L.cuts[b], nt = L.cuts[b + 1] - u0;
@@ -865,7 +869,7 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
             }, s->wsi_planes, L.slab_max, pst.data()))) return rc;
         for (size_t q = 0; q < nt * P; q++) if (tile_status[u0 + q / P] == MIC_OK) tile_status[u0 + q / P] = pst[q];
         s->timer.reset(s->stream);                                                          // (every unit has a piece; no more than 2^31 - 1 in all: plan_sort)
-        gather_units(s, "k_wsi_gather_patches", kind, s->wsi_planes.p, L, b, d_out);
+        gather_units(s, "k_wsi_gather_patches", kind, s->wsi_planes.p, L, b, d_out, o, (size_t)ph * (size_t)pw);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());                                                         // (the next sub-batch follows on the stream; decode_plane_slab has waited for this one's bytes)
     }
@@ -898,11 +902,11 @@ PatchSlabs blob_slabs(mic_hip_session *s, const std::vector<const Mic3 *> &um, c
 // ---- patches of one level: what the three one-slide doors share ----------------------------------------------------------------------
 // The plan of one level of `m` through the core.  status[i] (may be NULL): MIC_OK, or the first failing tile of patch i in tile
 // order, with the code mic_hip_wsi_decompress_tile has for it (the blob's, else its first failing plane's).
-int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int n, int pw, int ph, const SlabCeiling &ceiling,
+int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int n, int pw, int ph, const OutFormat &o, const SlabCeiling &ceiling,
                   const PatchSlabs &source, void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats) {
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
-    const int rc = read_patches(s, plan, um, pw, ph, ceiling, source, d_out, need, tst, &nslab);
+    const int rc = read_patches(s, plan, um, pw, ph, o, ceiling, source, d_out, need, tst, &nslab);
     if (rc) return rc;
     fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
     if (stats) { stats->tiles_decoded = plan.units.size(); stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
@@ -912,12 +916,13 @@ int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<c
 // mic_hip_wsi_read_patches / mic_hip_wsi_reader_read_patches on a parsed header, on the session the thread holds: the blobs of
 // the union's tiles from `src` in ONE request (a reader then pulls those blobs only, contiguous ones in one read); a tile whose
 // index entry points outside the file fails the call with the source's code before anything is launched.
-int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, void *d_out, size_t need,
+int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const OutFormat &o, void *d_out, size_t need,
                 int32_t *status, mic_hip_patch_stats *stats) {
     mic_hip_session *s = cur_default();
     const Level &L = m.lv[(size_t)level];
     int rc;
     if ((rc = patch_pointer(s, &d_out, need))) return rc;
+    if (!out_aligned(o, d_out)) return MIC_ERR_ARGS;
     PatchPlan plan;
     if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
     std::vector<size_t> tiles(plan.units.size());
@@ -925,7 +930,7 @@ int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *
     std::vector<TileBlob> blobs; std::vector<uint8_t> keep;
     if (!tiles.empty() && (rc = src(tiles, blobs, keep))) return rc;
     const std::vector<const Mic3 *> um(tiles.size(), &m);
-    return level_patches(s, plan, um, n, pw, ph, blob_ceiling((size_t)m.planes()), blob_slabs(s, um, blobs), d_out, need, status, stats);
+    return level_patches(s, plan, um, n, pw, ph, o, blob_ceiling((size_t)m.planes()), blob_slabs(s, um, blobs), d_out, need, status, stats);
 }
 
 // ---- patches of many slides and levels ------------------------------------------------------------------------------------------
@@ -994,18 +999,22 @@ int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int cha
     return MIC_OK;
 }
 
-// what the entry points check before a file is looked at; *need = bytes of the patch tensor
-int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps, size_t out_cap, size_t *need) {
+// what the entry points check before a file is looked at; o = the output description of a call on nsources slides, *need = bytes of
+// the patch tensor
+int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps, const mic_hip_out_spec *spec, int nsources, OutFormat &o,
+               size_t out_cap, size_t *need) {
     if (pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xysl)) return MIC_ERR_ARGS;
     if (!((channels == 3 && bps == 8) || (channels == 1 && (bps == 8 || bps == 16)))) return MIC_ERR_UNSUPPORTED;   // (Mic3::supported)
-    return tensor_bytes(n, 1, ph, pw, (size_t)(channels * (bps == 16 ? 2 : 1)), out_cap, need);
+    const int rc = o.make(spec, channels, bps, nsources);
+    if (rc) return rc;
+    return tensor_bytes(n, 1, ph, pw, o.pixel(), out_cap, need);
 }
 
 // slide `f`'s blobs of `tiles` (global indices, entries checked by the plan) through its reader; NULL: the slides are files in memory
 typedef std::function<int(uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep)> MultiFetch;
 
 // a door's call on a plan whose slides are set: arguments judged (multi_args), then the plan, n == 0, the pointer, the blobs, the core
-int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, int n, int pw, int ph, int channels, int bps,
+int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, int n, int pw, int ph, int channels, int bps, const OutFormat &o,
                void *d_out, size_t need, int32_t *status, mic_hip_multi_patch_stats *stats) {
     int rc = multi_plan(plan, xysl, n, pw, ph, channels, bps);
     if (rc) return rc;
@@ -1016,7 +1025,7 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     if ((rc = lease.acquire())) return rc;
     mic_hip_session *s = cur_default();
     if ((rc = patch_pointer(s, &d_out, need))) return rc;                                   // judged before anything is launched
-    if (bps == 16 && ((size_t)d_out & 1)) return MIC_ERR_ARGS;
+    if (o.typed() ? !out_aligned(o, d_out) : (bps == 16 && ((size_t)d_out & 1))) return MIC_ERR_ARGS;
     const size_t nu = plan.units.size();
     std::vector<TileBlob> blobs; blobs.reserve(nu);
     std::vector<const Mic3 *> um(nu);
@@ -1044,7 +1053,7 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     }
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
-    if ((rc = read_patches(s, plan, um, pw, ph, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab))) return rc;
+    if ((rc = read_patches(s, plan, um, pw, ph, o, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab))) return rc;
     fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
     container_codes(n, status, [&](int i) {                                                 // a refused slide's code; a level the slide does not have
         const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]]; const int32_t level = xysl[4 * (size_t)i + 3];
@@ -1263,20 +1272,25 @@ int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, con
 } MIC_ABI_CATCH
 
 // n patches of one level of a MIC3 file in host memory, into a tensor on the default session's device
-int mic_hip_wsi_read_patches(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
-                             void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+int mic_hip_wsi_read_patches_as(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                                void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
     if (!c) return MIC_ERR_ARGS;
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
     size_t need = 0;
-    if ((rc = patch_args(m, level, xy, n, pw, ph, out_cap, &need))) return rc;
+    OutFormat o;
+    if ((rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need))) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
-    return wsi_patches(flat_source(c, len, m), m, level, xy, n, pw, ph, d_out, need, status, stats);
+    return wsi_patches(flat_source(c, len, m), m, level, xy, n, pw, ph, o, d_out, need, status, stats);
 } MIC_ABI_CATCH
+int mic_hip_wsi_read_patches(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                             void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
+    return mic_hip_wsi_read_patches_as(c, len, level, xy, n, pw, ph, d_out, out_cap, status, stats, nullptr);
+}
 
 // multi_plan behind the two multi-slide calls: the (slide, tile) units n patches need decoded and the number of pieces
 int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens, int nfiles,
@@ -1285,7 +1299,8 @@ int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens
                                  uint64_t *ntiles_out, uint64_t *npieces, int32_t *file_status) try {
     if (nfiles < 0 || (nfiles > 0 && (!files || !lens)) || (cap > 0 && (!slide_of || !tile_of))) return MIC_ERR_ARGS;
     size_t need = 0;
-    int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, SIZE_MAX, &need);
+    OutFormat o;
+    int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, nullptr, 1, o, SIZE_MAX, &need);
     if (rc) return rc;
     MultiPlan plan;
     plan.slides.resize((size_t)nfiles);
@@ -1300,18 +1315,24 @@ int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens
 } MIC_ABI_CATCH
 
 // n patches of many MIC3 files in host memory, any levels, into a tensor on the default session's device
-int mic_hip_wsi_multi_read_patches(const uint8_t *const *files, const size_t *lens, int nfiles,
-                                   const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
-                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) try {
+int mic_hip_wsi_multi_read_patches_as(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
     if (nfiles < 0 || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
     size_t need = 0;
-    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, out_cap, &need);
+    OutFormat o;
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nfiles, o, out_cap, &need);
     if (rc) return rc;
     MultiPlan plan;
     plan.slides.resize((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) { plan.slides[(size_t)f].head = files[f]; plan.slides[(size_t)f].file_len = lens[f]; }
-    return multi_call(plan, nullptr, xysl, n, pw, ph, channels, bits_per_sample, d_out, need, status, stats);
+    return multi_call(plan, nullptr, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats);
 } MIC_ABI_CATCH
+int mic_hip_wsi_multi_read_patches(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                   const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) {
+    return mic_hip_wsi_multi_read_patches_as(files, lens, nfiles, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, nullptr);
+}
 
 }  // extern "C"
 
@@ -1477,24 +1498,26 @@ int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_p
 
 // n patches of one level from the store: the plane records of the union's tiles as they stand (no blob is put together or parsed),
 // their bytes where mic_hip_session_wsi_encode left them
-int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
-                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
     if (!s || !s->wsi) return MIC_ERR_ARGS;
     mic_hip_wsi_store &W = *s->wsi;
     Mic3 m = W.fmt; m.lv = W.lv; m.nlev = (int)W.lv.size();
     size_t need = 0;
-    int rc = patch_args(m, level, xy, n, pw, ph, out_cap, &need);
+    OutFormat o;
+    int rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need);
     if (rc) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     if ((rc = s->activate()) || (rc = patch_pointer(s, &d_out, need))) return rc;
+    if (!out_aligned(o, d_out)) return MIC_ERR_ARGS;
     const Level &L = m.lv[(size_t)level];
     const size_t P = (size_t)m.planes();
     PatchPlan plan;
     if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
     const std::vector<const Mic3 *> um(plan.units.size(), &m);
-    return level_patches(s, plan, um, n, pw, ph, [&](size_t) { return session_slab_tiles(m); },
+    return level_patches(s, plan, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); },
                          [&](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
         for (size_t k = 0; k < nt; k++) {
             const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)plan.units[u0 + k].tile) * P;
@@ -1504,6 +1527,10 @@ int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_
         return MIC_OK;
     }, d_out, need, status, stats);
 } MIC_ABI_CATCH
+int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
+    return mic_hip_session_wsi_read_patches_as(s, level, xy, n, pw, ph, d_out, out_cap, status, stats, nullptr);
+}
 
 int mic_hip_session_wsi_levels(mic_hip_session *s, int *levels, int *widths, int *heights, int cap) try {
     if (!s || !s->wsi || !levels) return MIC_ERR_ARGS;
@@ -1898,29 +1925,35 @@ int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x
     return wsi_region(r->source(), r->m, level, x, y, w, h, out, out_cap, out_w, out_h);
 } MIC_ABI_CATCH
 
-int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
-                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) try {
+int mic_hip_wsi_reader_read_patches_as(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
     if (!r) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     size_t need = 0;
-    int rc = patch_args(r->m, level, xy, n, pw, ph, out_cap, &need);
+    OutFormat o;
+    int rc = patch_args(r->m, level, xy, n, pw, ph, spec, o, out_cap, &need);
     if (rc) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
-    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, d_out, need, status, stats);
+    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, o, d_out, need, status, stats);
 } MIC_ABI_CATCH
+int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
+    return mic_hip_wsi_reader_read_patches_as(r, level, xy, n, pw, ph, d_out, out_cap, status, stats, nullptr);
+}
 
 // mic_hip_wsi_multi_read_patches through readers.  Only the readers some patch names are touched: each distinct one is locked once,
 // in address order (one order for every caller), and asked for its blobs in one fetch.
-int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
-                                     const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
-                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) try {
+int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int nreaders,
+                                        const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
     if (nreaders < 0 || (nreaders > 0 && !readers)) return MIC_ERR_ARGS;
     size_t need = 0;
-    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, out_cap, &need);
+    OutFormat o;
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nreaders, o, out_cap, &need);
     if (rc) return rc;
     std::vector<mic_hip_wsi_reader *> named;
     for (int i = 0; i < n; i++) {
@@ -1942,8 +1975,13 @@ int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nre
     }
     return multi_call(plan, [&](uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
         return readers[f]->fetch(tiles, blobs, keep);
-    }, xysl, n, pw, ph, channels, bits_per_sample, d_out, need, status, stats);
+    }, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats);
 } MIC_ABI_CATCH
+int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
+                                     const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats) {
+    return mic_hip_wsi_readers_read_patches_as(readers, nreaders, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, nullptr);
+}
 
 void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
 

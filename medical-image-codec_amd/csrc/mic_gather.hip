@@ -1,7 +1,12 @@
 // mic_gather.hip -- what the readers of many rectangles per call share (MIC3 patches: mic_api_ext.hip, MIC2 crops: mic_mic2_crops.hip,
 // strip-file crops: mic_strip_crops.hip).  Each of them plans on the host, decodes the touched units in sub-batches into a slab and
 // copies the pieces, the (rectangle, unit) overlaps, out of the slab into the output tensor.  Here: the kernels that copy and their
-// launcher, the judgement of the output pointer, the crop doors' way to a session, and the packing of a sub-batch's streams.
+// launcher, the judgement of the output pointer, the crop doors' way to a session, and the packing of a sub-batch's streams; and
+// the typed output of the _as doors (mic_hip_out_spec): its one judgement, the typed gather kernels, the pad fill and the convert
+// kernel of the MIC2 temporal staging tensor.
+#include <hip/hip_fp16.h>
+#include <hip/hip_bf16.h>
+#include <cmath>
 #include "mic_session.h"
 #include "mic_pieces.h"
 
@@ -54,18 +59,216 @@ __global__ void __launch_bounds__(256) k_gather_pieces_rgb(const uint16_t *slab,
     }
 }
 
+// ---- typed output (mic_hip_out_spec) ------------------------------------------------------------------------------------------
+// The value of an output sample (include/mic_hip.h): v = fmaf(x, a, b), one rounding; clamped in f32 when the spec says so; then
+// the output type's conversion of that f32 value -- round to nearest even for f16 and bf16 (overflow to inf), rintf and saturation
+// for u8 and u16.  DT: the spec's dtype; its samples are stored as their bits (u8, u16 or a dword).
+template <int DT> struct OutBits { typedef uint16_t type; };
+template <> struct OutBits<MIC_HIP_OUT_U8> { typedef uint8_t type; };
+template <> struct OutBits<MIC_HIP_OUT_F32> { typedef uint32_t type; };
+template <int DT> __device__ __forceinline__ typename OutBits<DT>::type out_bits(float v) {
+    if (DT == MIC_HIP_OUT_F32) return (typename OutBits<DT>::type)__float_as_uint(v);
+    if (DT == MIC_HIP_OUT_F16) return (typename OutBits<DT>::type)__half_as_ushort(__float2half_rn(v));
+    if (DT == MIC_HIP_OUT_BF16) return (typename OutBits<DT>::type)__bfloat16_as_ushort(__float2bfloat16(v));   // (RNE; gfx950: v_cvt_pk_bf16_f32)
+    const float top = DT == MIC_HIP_OUT_U8 ? 255.f : 65535.f;
+    return (typename OutBits<DT>::type)(uint32_t)fminf(fmaxf(rintf(v), 0.f), top);
+}
+struct Pair { float x, y; };
+__device__ __forceinline__ Pair out_pair(const OutParams &o, size_t i) { const mic_gp<const float> g = mic_g(o.affine); return Pair{ g[2 * i], g[2 * i + 1] }; }
+template <int DT> __device__ __forceinline__ typename OutBits<DT>::type out_sample(uint32_t x, Pair ab, const OutParams &o) {
+    float v = __fmaf_rn((float)x, ab.x, ab.y);
+    if (o.clamp) v = fminf(fmaxf(v, o.lo), o.hi);
+    return out_bits<DT>(v);
+}
+
+// A row of w one-plane samples as DT: the lanes of piece_lanes.  2-byte outputs keep the native kernel's trick: a row whose
+// destination is 4-byte aligned stores packed pairs as dwords (the odd sample behind them as one 2-byte store), any other row
+// 2-byte samples; f32 is one dword per lane.
+template <int DT>
+__device__ __forceinline__ void typed_row(mic_gp<const uint16_t> s, mic_gp<typename OutBits<DT>::type> d, int w, const PieceLanes &ln, Pair ab, const OutParams &o) {
+    typedef typename OutBits<DT>::type T;
+    if (sizeof(T) == 2 && ((size_t)d & 3) == 0) {
+        const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
+        for (int x = ln.col; x < (w >> 1); x += ln.lw)
+            d2[x] = (uint32_t)out_sample<DT>(s[2 * x], ab, o) | ((uint32_t)out_sample<DT>(s[2 * x + 1], ab, o) << 16);
+        if ((w & 1) && ln.col == 0) d[w - 1] = out_sample<DT>(s[w - 1], ab, o);
+    } else
+        for (int x = ln.col; x < w; x += ln.lw) d[x] = out_sample<DT>(s[x], ab, o);
+}
+
+// k_gather_pieces for a typed tensor: the same lanes and grid; the piece's pair is its source's (one plane: channel 0).  8-bit
+// greyscale slides enter as the slab's u16 samples, like every other one-plane source.
+template <int DT>
+__global__ void __launch_bounds__(256) k_gather_typed(const uint16_t *slab, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const Pair ab = out_pair(o, (size_t)pc.source * o.src_mul);
+    const uint16_t *src = slab + pc.src;
+    typename OutBits<DT>::type *dst = out + pc.dst;
+    for (int y = ln.row; y < pc.h; y += ln.rstep)
+        typed_row<DT>(mic_g(src + (size_t)y * pc.sstride), mic_g(dst + (size_t)y * pc.dstride), pc.w, ln, ab, o);
+}
+
+// k_gather_pieces_rgb for a typed tensor: the same YCoCg-R inverse, then r, g and b through their channel's pair to the pixel's
+// three places, o.plane samples apart: 1 in the interleaved tensor (pc.dst: the pixel's first sample), ph * pw in the
+// channels-first one (pc.dst: the piece's place in plane 0, rows dstride samples apart).
+template <int DT>
+__global__ void __launch_bounds__(256) k_gather_typed_rgb(const uint16_t *slab, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+    typedef typename OutBits<DT>::type T;
+    const GatherPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const size_t a0 = (size_t)pc.source * o.src_mul;
+    const Pair ar = out_pair(o, a0), ag = out_pair(o, a0 + o.ch_step), ab = out_pair(o, a0 + 2 * o.ch_step);
+    const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
+    const mic_gp<T> dr = mic_g(out + pc.dst), dg = dr + o.plane, db = dg + o.plane;
+    const int px = o.plane == 1 ? 3 : 1;                                                    // samples from a pixel to the next of its row
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const size_t si = (size_t)y * pc.sstride, di = (size_t)y * pc.dstride;
+        for (int x = ln.col; x < pc.w; x += ln.lw) {
+            const int yv = py[si + x];
+            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
+            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, deltazigzagcompressu16.go:113-116
+            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
+            const int t = yv - (cg >> 1);                                                   // YCoCgRInverse, asm_amd64.go:106-121
+            const int g = cg + t;
+            const int b = t - (co >> 1);
+            const int r = co + b;
+            const size_t d = di + (size_t)x * px;
+            dr[d] = out_sample<DT>((uint8_t)r, ar, o); dg[d] = out_sample<DT>((uint8_t)g, ag, o); db[d] = out_sample<DT>((uint8_t)b, ab, o);
+        }
+    }
+}
+
+// MIC2 temporal volumes: run = a crop's footprint, w x h samples of d slices from `at` of the u16 staging tensor (slices of ch x cw)
+// to the same place of the typed one, through its volume's pair.  grid = (runs, row chunks, slices), the lanes of a piece: a run is
+// as deep as its crop, so the slices go over grid z or a call of a few deep crops would leave most of the device idle.
+template <int DT>
+__global__ void __launch_bounds__(256) k_convert_runs(const uint16_t *stage, const ConvertRun *runs, typename OutBits<DT>::type *out, int cw, int ch, const OutParams o) {
+    const ConvertRun rn = runs[blockIdx.x];
+    const PieceLanes ln = piece_lanes(rn.w);
+    const Pair ab = out_pair(o, (size_t)rn.source * o.src_mul);
+    const size_t slice = (size_t)ch * cw;
+    for (int z = (int)blockIdx.z; z < rn.d; z += (int)gridDim.z)
+        for (int y = ln.row; y < rn.h; y += ln.rstep) {
+            const size_t at = rn.at + (size_t)z * slice + (size_t)y * cw;
+            typed_row<DT>(mic_g(stage + at), mic_g(out + at), rn.w, ln, ab, o);
+        }
+}
+
+// n dwords of `bits` from d (4-byte aligned)
+__global__ void __launch_bounds__(256) k_fill_dwords(uint32_t *d, size_t n, uint32_t bits) {
+    const mic_gp<uint32_t> g = mic_g(d);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) g[i] = bits;
+}
+
+// the host's copy of out_bits, for pad: the same conversions (round to nearest even is the host's rounding mode too)
+uint32_t host_bits(int dtype, float v) {
+    uint32_t u; memcpy(&u, &v, 4);
+    switch (dtype) {
+    case MIC_HIP_OUT_F32: return u;
+    case MIC_HIP_OUT_BF16: return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;                   // (v is finite)
+    case MIC_HIP_OUT_F16: { const _Float16 h = (_Float16)v; uint16_t b; memcpy(&b, &h, 2); return b; }
+    case MIC_HIP_OUT_U8: return (uint32_t)std::fmin(std::fmax(std::nearbyint(v), 0.f), 255.f);
+    default: return (uint32_t)std::fmin(std::fmax(std::nearbyint(v), 0.f), 65535.f);
+    }
+}
+
 }  // namespace
+
+extern "C" int mic_hip_out_spec_check(const mic_hip_out_spec *spec, int channels, int bits_per_sample, int nsources, size_t *sample_bytes) {
+    if (!spec || !sample_bytes || (channels != 1 && channels != 3) || (bits_per_sample != 8 && bits_per_sample != 16) || nsources < 1) return MIC_ERR_ARGS;
+    if (spec->dtype < MIC_HIP_OUT_NATIVE || spec->dtype > MIC_HIP_OUT_F32) return MIC_ERR_ARGS;
+    if (spec->flags & ~(MIC_HIP_OUT_CHANNELS_FIRST | MIC_HIP_OUT_CLAMP)) return MIC_ERR_ARGS;
+    const int64_t na = spec->naffine;
+    if (na != 0 && na != 1 && na != channels && na != (int64_t)nsources * channels) return MIC_ERR_ARGS;
+    if (na > 0 && !spec->affine) return MIC_ERR_ARGS;
+    for (int64_t i = 0; i < 2 * na; i++) if (!std::isfinite(spec->affine[i])) return MIC_ERR_ARGS;
+    if (!std::isfinite(spec->clamp_lo) || !std::isfinite(spec->clamp_hi) || !std::isfinite(spec->pad)) return MIC_ERR_ARGS;
+    if ((spec->flags & MIC_HIP_OUT_CLAMP) && !(spec->clamp_lo < spec->clamp_hi)) return MIC_ERR_ARGS;
+    if (spec->dtype == MIC_HIP_OUT_NATIVE) {
+        if (spec->flags || spec->affine || na || spec->clamp_lo != 0.f || spec->clamp_hi != 0.f || spec->pad != 0.f) return MIC_ERR_ARGS;
+        *sample_bytes = bits_per_sample == 16 ? 2 : 1;
+    } else
+        *sample_bytes = spec->dtype == MIC_HIP_OUT_U8 ? 1 : spec->dtype == MIC_HIP_OUT_F32 ? 4 : 2;
+    return MIC_OK;
+}
 
 namespace micapi {
 
-void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out) {
+int OutFormat::make(const mic_hip_out_spec *spec, int nch, int bits_per_sample, int nsources) {
+    *this = OutFormat();
+    channels = nch;
+    sample = (size_t)nch * (bits_per_sample == 16 ? 2 : 1);                                 // (NATIVE: the pixel, as the native doors count it)
+    if (!spec) return MIC_OK;
+    size_t sb = 0;
+    const int rc = mic_hip_out_spec_check(spec, nch, bits_per_sample, std::max(nsources, 1), &sb);
+    if (rc || spec->dtype == MIC_HIP_OUT_NATIVE) return rc;
+    dtype = spec->dtype; flags = spec->flags; sample = sb; lo = spec->clamp_lo; hi = spec->clamp_hi; pad = spec->pad;
+    if (spec->naffine > 0) table.assign(spec->affine, spec->affine + 2 * (size_t)spec->naffine);
+    if (spec->naffine > 1) { ch_step = nch > 1 ? 1 : 0; src_mul = spec->naffine == nch ? 0 : nch; }
+    return MIC_OK;
+}
+
+uint32_t OutFormat::pad_bits() const {
+    if (!typed()) return 0;
+    const uint32_t b = host_bits(dtype, pad);
+    return sample == 4 ? b : sample == 2 ? b * 0x10001u : b * 0x01010101u;
+}
+
+int fill_pad(hipStream_t stream, const OutFormat &o, void *d_out, size_t bytes) {
+    const uint32_t bits = o.pad_bits();
+    if (bits == 0 || bytes == 0) { HIP_TRY(hipMemsetAsync(d_out, 0, bytes, stream)); return MIC_OK; }
+    // the tensor's base is aligned to its sample, so the dword pattern holds at any byte of it: bytes in front of the first whole
+    // dword and behind the last one are set as bytes (the pattern of a 2-byte type has its two bytes wherever a dword starts)
+    const size_t head = std::min(bytes, (size_t)(-(intptr_t)d_out & 3)), nd = (bytes - head) / 4, tail = bytes - head - nd * 4;
+    const uint32_t rot = bits >> (8 * (unsigned)head) | (head ? bits << (32 - 8 * (unsigned)head) : 0);   // (little-endian; head 2: halves swap, equal anyway)
+    for (size_t i = 0; i < head; i++) HIP_TRY(hipMemsetAsync((char *)d_out + i, (int)((bits >> (8 * i)) & 0xFF), 1, stream));
+    if (nd) hipLaunchKernelGGL(k_fill_dwords, dim3((unsigned)std::min<size_t>((nd + 255) / 256, 4096)), dim3(256), 0, stream, (uint32_t *)((char *)d_out + head), nd, rot);
+    for (size_t i = 0; i < tail; i++) HIP_TRY(hipMemsetAsync((char *)d_out + head + nd * 4 + i, (int)((rot >> (8 * i)) & 0xFF), 1, stream));
+    return MIC_OK;
+}
+
+void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table, const uint16_t *stage, const ConvertRun *runs, size_t n,
+                    int mw, int mh, int md, int cw, int ch, void *out) {
+    constexpr size_t kMaxGridX = 0x7FFFFFFF;
+    const unsigned gy = row_chunks(mw, mh);
+    const OutParams op = o.params(d_table, 1);
+    for (size_t q = 0; q < n; q += kMaxGridX) {
+        const dim3 grid((unsigned)std::min(n - q, kMaxGridX), gy, (unsigned)std::min(std::max(md, 1), 64)), block(256);
+        switch (o.dtype) {
+        case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_U8>, grid, block, 0, stream, stage, runs + q, (uint8_t *)out, cw, ch, op); break;
+        case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_U16>, grid, block, 0, stream, stage, runs + q, (uint16_t *)out, cw, ch, op); break;
+        case MIC_HIP_OUT_F16: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_F16>, grid, block, 0, stream, stage, runs + q, (uint16_t *)out, cw, ch, op); break;
+        case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_BF16>, grid, block, 0, stream, stage, runs + q, (uint16_t *)out, cw, ch, op); break;
+        default: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_F32>, grid, block, 0, stream, stage, runs + q, (uint32_t *)out, cw, ch, op); break;
+        }
+    }
+}
+
+void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out,
+                   int dtype, const OutParams &op) {
     constexpr size_t kMaxGridX = 0x7FFFFFFF;
     const unsigned gy = row_chunks(mw, mh);
     for (size_t q = 0; q < np; q += kMaxGridX) {
         const dim3 grid((unsigned)std::min(np - q, kMaxGridX), gy), block(256);
-        if (kind == kGatherRGB) hipLaunchKernelGGL(k_gather_pieces_rgb, grid, block, 0, stream, slab, pieces + q, (uint8_t *)out);
-        else if (kind == kGatherU16) hipLaunchKernelGGL(k_gather_pieces<uint16_t>, grid, block, 0, stream, slab, pieces + q, (uint16_t *)out);
-        else hipLaunchKernelGGL(k_gather_pieces<uint8_t>, grid, block, 0, stream, slab, pieces + q, (uint8_t *)out);
+        const GatherPiece *pq = pieces + q;
+        if (dtype == MIC_HIP_OUT_NATIVE) {
+            if (kind == kGatherRGB) hipLaunchKernelGGL(k_gather_pieces_rgb, grid, block, 0, stream, slab, pq, (uint8_t *)out);
+            else if (kind == kGatherU16) hipLaunchKernelGGL(k_gather_pieces<uint16_t>, grid, block, 0, stream, slab, pq, (uint16_t *)out);
+            else hipLaunchKernelGGL(k_gather_pieces<uint8_t>, grid, block, 0, stream, slab, pq, (uint8_t *)out);
+        } else if (kind == kGatherRGB) switch (dtype) {
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_gather_typed_rgb<MIC_HIP_OUT_U8>, grid, block, 0, stream, slab, pq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_gather_typed_rgb<MIC_HIP_OUT_U16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL(k_gather_typed_rgb<MIC_HIP_OUT_F16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_gather_typed_rgb<MIC_HIP_OUT_BF16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL(k_gather_typed_rgb<MIC_HIP_OUT_F32>, grid, block, 0, stream, slab, pq, (uint32_t *)out, op); break;
+        } else switch (dtype) {
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_U8>, grid, block, 0, stream, slab, pq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_U16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_F16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_BF16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_F32>, grid, block, 0, stream, slab, pq, (uint32_t *)out, op); break;
+        }
     }
 }
 
@@ -84,12 +287,12 @@ int patch_pointer(const mic_hip_session *s, void **d_out, size_t need) {
     return MIC_OK;
 }
 
-int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need) {
+int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need, const OutFormat &o) {
     int rc;
     if (!*s) { if ((rc = lease.acquire())) return rc; *s = cur_default(); }
     else if ((rc = (*s)->activate())) return rc;
     rc = patch_pointer(*s, d_out, need);                                                    // judged before anything is launched
-    if (rc == MIC_ERR_CAPACITY || ((size_t)*d_out & 1)) rc = MIC_ERR_ARGS;
+    if (rc == MIC_ERR_CAPACITY || (o.typed() ? !out_aligned(o, *d_out) : ((size_t)*d_out & 1) != 0)) rc = MIC_ERR_ARGS;
     return rc;
 }
 

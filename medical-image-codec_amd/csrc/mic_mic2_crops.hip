@@ -112,11 +112,11 @@ int mic2_plan_crops(int width, int height, int nframes, int temporal, const int3
 }
 
 // What the three crop entry points check of their arguments before a device is touched; *need = bytes of the crop tensor.
-int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need) {
+int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t sample_bytes, size_t out_cap, size_t *need) {
     if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || (n > 0 && !xyz)) return MIC_ERR_ARGS;
     if (m.w <= 0 || m.h <= 0) return MIC_ERR_CORRUPT;                                       // (as mic_hip_mic2_decompress)
     if ((size_t)m.w * (size_t)m.h > ((size_t)1 << 28) || m.file_len > 0xFFFFFFF0ull) return MIC_ERR_UNSUPPORTED;
-    return tensor_bytes(n, cd, ch, cw, 2, out_cap, need);
+    return tensor_bytes(n, cd, ch, cw, sample_bytes, out_cap, need);
 }
 
 }  // namespace micapi
@@ -200,12 +200,14 @@ int mic2_multi_plan(Mic2MultiPlan &mp, const int32_t *xyzv, int n, int cw, int c
 // where the core finds the stream of a volume's frame, on the host or (device) on the session's device
 struct Mic2MultiSource { bool device = false; std::function<const uint8_t *(uint32_t vol, uint32_t frame)> blob; };
 
-// n crops into d_out ([n][cd][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
-// current.  The units of every planned volume go through the MIC2 decode chain in plan order, in sub-batches cut by their sizes alone;
+// n crops into d_out ([n][cd][ch][cw] samples of o's type, an address s's device can write: patch_pointer) on a session the caller
+// holds and has made current.  A typed tensor cannot carry the temporal volumes' running sums (u16, mod 2^16): they then live in a u16
+// tensor of the same shape in the session's workspace (s->crop_stage, reserved before the first launch), and behind the last
+// sub-batch one kernel converts the footprint of every temporal crop that is complete into d_out (launch_convert).  The units of every planned volume go through the MIC2 decode chain in plan order, in sub-batches cut by their sizes alone;
 // the call stops in front of a sub-batch when every unit left belongs to a temporal volume that has already failed (a one-volume call
 // whose frame failed).  status[i] / failed_frame[i] (each may be NULL): MIC_OK / -1, or the code of the first failing frame crop i
 // depends on and that frame.
-int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic2MultiSource &src, int n, int cw, int ch, int cd,
+int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic2MultiSource &src, int n, int cw, int ch, int cd, const OutFormat &o,
                           void *d_out, size_t need, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
     struct Unit { uint32_t vol, frame; };
     const size_t nv = mp.vols.size();
@@ -218,7 +220,7 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
     const size_t nu = un.size();
     int rc;
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the volumes, refused volumes; every byte is written
+    if ((rc = fill_pad(s->stream, o, d_out, need))) return rc;                              // outside the volumes, refused volumes; every byte is written
     auto vol = [&](size_t u) -> const Mic2Vol & { return mp.vols[un[u].vol]; };
     auto is_frame = [&](size_t u) { return !vol(u).m.temporal || un[u].frame == 0; };       // a frame unit (mode 0), else a residual's symbols (mode 3)
     auto blob_len = [&](size_t u) { return (uint64_t)get_u32(vol(u).m.table + 8 * (size_t)un[u].frame + 4); };
@@ -243,7 +245,8 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
     }
     pfirst.push_back(prints.size());
     const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_strip_cut(px, i0); }, [&](size_t u) { return is_frame(u) ? px[u] : (size_t)0; },
-                                       pieces, cw, ch, [&](size_t u) { return UnitStride{ vol(u).m.w, 0 }; });
+                                       pieces, cw, ch, [&](size_t u) { return UnitStride{ vol(u).m.w, 0 }; },
+                                       [&](size_t u) { return un[u].vol; }, o);
     size_t comp_max = 0;                                                                    // the most stream bytes of a sub-batch
     for (size_t b = 0, comp = 0; b < L.subs(); b++, comp = 0)
         for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) comp_max = std::max(comp_max, comp += (size_t)blob_len(u));
@@ -254,10 +257,14 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) nspan += vol(u).m.temporal && (u == L.cuts[b] || un[u].vol != un[u - 1].vol);
     std::vector<VolSpan> spans; spans.reserve(nspan);
     const size_t list_bytes = gather_bytes(L), print_bytes = align_up(prints.size() * sizeof(VolPrint), 16);
+    const bool staged = o.typed() && !prints.empty();                                       // temporal sums go through the u16 staging tensor
+    const size_t span_bytes = align_up(nspan * sizeof(VolSpan), 16), behind = print_bytes + span_bytes + (staged ? prints.size() * sizeof(ConvertRun) : 0);
+    if (staged && (rc = s->crop_stage.reserve(need / o.sample * 2 + 64))) return rc;
+    uint16_t *d_sums = staged ? (uint16_t *)s->crop_stage.p : (uint16_t *)d_out;
     if (nu) {
         if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
         if ((rc = s->io_px.reserve(L.slab_max * 2 + 64))) return rc;
-        if ((rc = upload_gather(s, L, print_bytes + nspan * sizeof(VolSpan)))) return rc;   // (the footprints and the spans behind the list)
+        if ((rc = upload_gather(s, L, o, behind))) return rc;                               // (the footprints, the spans and a typed call's runs behind the list)
         if (!prints.empty()) HIP_TRY(hipMemcpyAsync((char *)s->pieces.p + list_bytes, prints.data(), prints.size() * sizeof(VolPrint), hipMemcpyHostToDevice, s->stream));
     }
     const VolPrint *d_prints = (const VolPrint *)((char *)s->pieces.p + list_bytes);
@@ -300,17 +307,32 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
         }
         const size_t nsp = spans.size() - sp0;
         s->timer.reset(s->stream);
-        gather_units(s, "k_mic2_gather_crops", kGatherU16, s->io_px.p, L, b, d_out);
+        gather_units(s, "k_mic2_gather_crops", kGatherU16, s->io_px.p, L, b, d_out, o, (size_t)ch * (size_t)cw, behind);
         if (nsp) {
             const size_t q0 = pfirst[(size_t)slot0], nq = pfirst[(size_t)slot0 + nsp] - q0;
             HIP_TRY(hipMemcpyAsync(d_spans + sp0, spans.data() + sp0, nsp * sizeof(VolSpan), hipMemcpyHostToDevice, s->stream));
             s->timer.mark("k_mic2_accumulate_crops");
             hipLaunchKernelGGL(k_mic2_accumulate_crops, dim3((unsigned)nq, row_chunks(tw, th)), dim3(256), 0, s->stream,
                                (const MicUnit *)s->units.p, (const VolSpan *)d_spans + sp0, slot0, (const uint16_t *)s->io_px.p, d_prints + q0,
-                               (uint16_t *)d_out, cw, ch, cd);
+                               d_sums, cw, ch, cd);
         }
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());
+    }
+    std::vector<ConvertRun> runs;                                                           // (lives until the synchronise below)
+    if (staged) {
+        for (const VolPrint &vp : prints) {
+            const CropPiece &fp = vp.fp;
+            if (fp.k >= fbad[(size_t)vp.slot]) continue;                                    // (depends on a failed frame: unspecified, left as it is)
+            runs.push_back(ConvertRun{ (((uint64_t)fp.crop * (uint64_t)cd + (uint64_t)fp.dz) * (uint64_t)ch + (uint64_t)fp.dy) * (uint64_t)cw + (uint64_t)fp.dx,
+                                       fp.w, fp.h, fp.k - fp.frame + 1, slot_vol[(size_t)vp.slot] });
+        }
+        if (!runs.empty()) {
+            ConvertRun *d_runs = (ConvertRun *)((char *)s->pieces.p + list_bytes + print_bytes + span_bytes);
+            HIP_TRY(hipMemcpyAsync(d_runs, runs.data(), runs.size() * sizeof(ConvertRun), hipMemcpyHostToDevice, s->stream));
+            launch_convert(s->stream, o, out_table(s, L, behind), d_sums, d_runs, runs.size(), tw, th, cd, cw, ch, d_out);
+            HIP_TRY(hipGetLastError());
+        }
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     fold_unit_status(pieces, ust, n, cd, status, failed_frame, [&](uint32_t u) { return (int32_t)un[u].frame; });   // independent volumes: pieces are in frame order
@@ -330,10 +352,13 @@ int mic2_multi_read_crops(mic_hip_session *s, const Mic2MultiPlan &mp, const Mic
 // a one-volume door's call on its parsed file: arguments, n == 0, the plan, the session (leased here when s is NULL), the table
 // entries of the plan's frames, `source`, then the core on a plan of that one volume
 int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(const CropPlan &, Mic2Source &)> &source,
-               const int32_t *xyz, int n, int cw, int ch, int cd, void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+               const int32_t *xyz, int n, int cw, int ch, int cd, void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats,
+               const mic_hip_out_spec *spec) {
     size_t need = 0;
-    int rc = mic2_crop_args(m, xyz, n, cw, ch, cd, out_cap, &need);
+    OutFormat o;
+    int rc = o.make(spec, 1, 16, 1);
     if (rc) return rc;
+    if ((rc = mic2_crop_args(m, xyz, n, cw, ch, cd, o.pixel(), out_cap, &need))) return rc;
     if (stats) *stats = mic_hip_crop_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
@@ -345,7 +370,7 @@ int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(co
     mp.units = f.plan.frames.size(); mp.pieces = f.plan.pieces.size(); mp.read = 1;
     DefaultLease lease;
     // the pointer and the table are judged before a source is asked for a byte, and before anything is launched
-    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
+    if ((rc = crop_door(&s, lease, &d_out, need, o))) return rc;
     for (uint32_t fr : f.plan.frames) {                                                     // as mic_hip_mic2_decompress, multiframe.go:137-139
         const uint64_t off = 20 + 8 * (uint64_t)m.n + get_u32(m.table + 8 * (size_t)fr), bl = get_u32(m.table + 8 * (size_t)fr + 4);
         if (bl == 0 || off + bl > m.file_len) return MIC_ERR_CORRUPT;
@@ -356,16 +381,18 @@ int crops_call(mic_hip_session *s, const Mic2Head &m, const std::function<int(co
     src.device = one.device;
     src.blob = [&one](uint32_t, uint32_t frame) { return one.blob(frame); };
     mic_hip_multi_crop_stats ms{ 0, 0, 0, 0 };
-    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, d_out, need, status, nullptr, &ms))) return rc;
+    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, o, d_out, need, status, nullptr, &ms))) return rc;
     if (stats) *stats = mic_hip_crop_stats{ ms.frames_decoded, ms.pieces, ms.slabs };
     return MIC_OK;
 }
 
-// what the doors check of their arguments before a file is looked at; *need = bytes of the crop tensor
-int multi_crop_args(const void *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd, size_t out_cap, size_t *need) {
+// what the doors check of their arguments before a file is looked at; o = the output description, *need = bytes of the crop tensor
+int multi_crop_args(const void *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                    const mic_hip_out_spec *spec, OutFormat &o, size_t out_cap, size_t *need) {
     if (cw <= 0 || ch <= 0 || cd <= 0 || n < 0 || nfiles < 0 || (n > 0 && !xyzv) || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
-    const int rc = tensor_bytes(n, cd, ch, cw, 2, out_cap, need);
+    int rc = o.make(spec, 1, 16, nfiles);
     if (rc) return rc;
+    if ((rc = tensor_bytes(n, cd, ch, cw, o.pixel(), out_cap, need))) return rc;
     for (int i = 0; i < n; i++) if (xyzv[4 * (size_t)i + 3] < 0 || xyzv[4 * (size_t)i + 3] >= nfiles) return MIC_ERR_ARGS;
     return MIC_OK;
 }
@@ -373,18 +400,18 @@ int multi_crop_args(const void *files, const size_t *lens, int nfiles, const int
 // a door's call once its arguments stand (multi_crop_args): n == 0, the pointer and the session (leased here when s is NULL), the plan,
 // `source` -- which may still refuse a volume (refuse_vol) or fail the call --, the core, then the refused volumes' codes
 int multi_call(mic_hip_session *s, Mic2MultiPlan &mp, const std::function<int(Mic2MultiSource &)> &source,
-               const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t need,
+               const int32_t *xyzv, int n, int cw, int ch, int cd, const OutFormat &o, void *d_out, size_t need,
                int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
     if (stats) *stats = mic_hip_multi_crop_stats{ 0, 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
-    int rc = crop_door(&s, lease, &d_out, need);                                            // judged before a file is looked at
+    int rc = crop_door(&s, lease, &d_out, need, o);                                          // judged before a file is looked at
     if (rc) return rc;
     if ((rc = mic2_multi_plan(mp, xyzv, n, cw, ch, cd))) return rc;
     Mic2MultiSource src;
     if ((rc = source(src))) return rc;
-    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, d_out, need, status, failed_frame, stats))) return rc;
+    if ((rc = mic2_multi_read_crops(s, mp, src, n, cw, ch, cd, o, d_out, need, status, failed_frame, stats))) return rc;
     container_codes(n, status, [&](int i) { return mp.vols[(size_t)xyzv[4 * (size_t)i + 3]].status; });
     return MIC_OK;
 }
@@ -439,8 +466,8 @@ int mic_hip_mic2_crop_plan(int width, int height, int nframes, int temporal, con
 } MIC_ABI_CATCH
 
 // n crops of a MIC2 file in host memory, into a tensor on the default session's device
-int mic_hip_mic2_read_crops(const uint8_t *c, size_t len, const int32_t *xyz, int n, int cw, int ch, int cd,
-                            void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+int mic_hip_mic2_read_crops_as(const uint8_t *c, size_t len, const int32_t *xyz, int n, int cw, int ch, int cd,
+                               void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec) try {
     Mic2Head m;
     int rc = parse_mic2(c, len, m);
     if (rc) return rc;
@@ -449,8 +476,12 @@ int mic_hip_mic2_read_crops(const uint8_t *c, size_t len, const int32_t *xyz, in
         src.device = false;
         src.blob = [&m, c](uint32_t f) { return c + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
         return MIC_OK;
-    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats, spec);
 } MIC_ABI_CATCH
+int mic_hip_mic2_read_crops(const uint8_t *c, size_t len, const int32_t *xyz, int n, int cw, int ch, int cd,
+                            void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+    return mic_hip_mic2_read_crops_as(c, len, xyz, n, cw, ch, cd, d_out, out_cap, status, stats, nullptr);
+}
 
 int mic_hip_mic2_reader_open(mic_hip_read_fn read, void *user, uint64_t file_len, mic_hip_mic2_reader **out) try {
     if (!read || !out) return MIC_ERR_ARGS;
@@ -475,20 +506,24 @@ int mic_hip_mic2_reader_info(const mic_hip_mic2_reader *r, int *width, int *heig
     return MIC_OK;
 }
 
-int mic_hip_mic2_reader_read_crops(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
-                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+int mic_hip_mic2_reader_read_crops_as(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
+                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec) try {
     if (!r) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     return crops_call(nullptr, r->m, [&](const CropPlan &plan, Mic2Source &src) { return r->fetch(plan, src); },
-                      xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+                      xyz, n, cw, ch, cd, d_out, out_cap, status, stats, spec);
 } MIC_ABI_CATCH
+int mic_hip_mic2_reader_read_crops(mic_hip_mic2_reader *r, const int32_t *xyz, int n, int cw, int ch, int cd,
+                                   void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+    return mic_hip_mic2_reader_read_crops_as(r, xyz, n, cw, ch, cd, d_out, out_cap, status, stats, nullptr);
+}
 
 void mic_hip_mic2_reader_close(mic_hip_mic2_reader *r) { delete r; }
 
 // n crops of a MIC2 file that lies on the session's device: the streams go device to device
-int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, size_t head_len, const uint8_t *d_file, size_t file_len,
-                                    const int32_t *xyz, int n, int cw, int ch, int cd,
-                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) try {
+int mic_hip_session_mic2_read_crops_as(mic_hip_session *s, const uint8_t *head, size_t head_len, const uint8_t *d_file, size_t file_len,
+                                       const int32_t *xyz, int n, int cw, int ch, int cd,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats, const mic_hip_out_spec *spec) try {
     if (!s || !head) return MIC_ERR_ARGS;
     if (head_len < 20) return MIC_ERR_CORRUPT;
     Mic2Head m;
@@ -501,13 +536,19 @@ int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, siz
         src.device = true;
         src.blob = [&m, d_file](uint32_t f) { return d_file + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
         return (int)MIC_OK;
-    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats);
+    }, xyz, n, cw, ch, cd, d_out, out_cap, status, stats, spec);
 } MIC_ABI_CATCH
+int mic_hip_session_mic2_read_crops(mic_hip_session *s, const uint8_t *head, size_t head_len, const uint8_t *d_file, size_t file_len,
+                                    const int32_t *xyz, int n, int cw, int ch, int cd,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_crop_stats *stats) {
+    return mic_hip_session_mic2_read_crops_as(s, head, head_len, d_file, file_len, xyz, n, cw, ch, cd, d_out, out_cap, status, stats, nullptr);
+}
 
 int mic_hip_mic2_multi_crop_plan(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
                                  uint32_t *volume_of, uint32_t *frame_of, size_t cap, uint64_t *nframes_out, uint64_t *npieces, int32_t *file_status) try {
     size_t need = 0;
-    int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, ~(size_t)0, &need);
+    OutFormat o;
+    int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, nullptr, o, ~(size_t)0, &need);
     if (rc) return rc;
     if (cap > 0 && (!volume_of || !frame_of)) return MIC_ERR_ARGS;
     Mic2MultiPlan mp;
@@ -526,10 +567,12 @@ int mic_hip_mic2_multi_crop_plan(const uint8_t *const *files, const size_t *lens
 } MIC_ABI_CATCH
 
 // n crops of MIC2 files in host memory, into a tensor on the default session's device
-int mic_hip_mic2_multi_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
-                                  void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+int mic_hip_mic2_multi_read_crops_as(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                     void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats,
+                                     const mic_hip_out_spec *spec) try {
     size_t need = 0;
-    const int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, out_cap, &need);
+    OutFormat o;
+    const int rc = multi_crop_args(files, lens, nfiles, xyzv, n, cw, ch, cd, spec, o, out_cap, &need);
     if (rc) return rc;
     Mic2MultiPlan mp;
     mp.vols.resize((size_t)nfiles);
@@ -538,15 +581,21 @@ int mic_hip_mic2_multi_read_crops(const uint8_t *const *files, const size_t *len
         src.device = false;
         src.blob = [&mp](uint32_t v, uint32_t f) { const Mic2Head &m = mp.vols[v].m; return m.table + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
         return (int)MIC_OK;
-    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
+    }, xyzv, n, cw, ch, cd, o, d_out, need, status, failed_frame, stats);
 } MIC_ABI_CATCH
+int mic_hip_mic2_multi_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                  void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
+    return mic_hip_mic2_multi_read_crops_as(files, lens, nfiles, xyzv, n, cw, ch, cd, d_out, out_cap, status, failed_frame, stats, nullptr);
+}
 
 // the same through readers (volume = an index into readers[]): every named reader's blobs are pulled before anything is launched
-int mic_hip_mic2_readers_read_crops(mic_hip_mic2_reader *const *readers, int nreaders, const int32_t *xyzv, int n, int cw, int ch, int cd,
-                                    void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+int mic_hip_mic2_readers_read_crops_as(mic_hip_mic2_reader *const *readers, int nreaders, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                       void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats,
+                                       const mic_hip_out_spec *spec) try {
     static const size_t no_lens = 0;                                                        // (readers bring their lengths)
     size_t need = 0;
-    const int rc = multi_crop_args(readers, &no_lens, nreaders, xyzv, n, cw, ch, cd, out_cap, &need);
+    OutFormat o;
+    const int rc = multi_crop_args(readers, &no_lens, nreaders, xyzv, n, cw, ch, cd, spec, o, out_cap, &need);
     if (rc) return rc;
     std::vector<mic_hip_mic2_reader *> named;                                               // distinct, in address order: locked once each
     for (int i = 0; i < n; i++) if (readers[xyzv[4 * (size_t)i + 3]]) named.push_back(readers[xyzv[4 * (size_t)i + 3]]);
@@ -577,18 +626,23 @@ int mic_hip_mic2_readers_read_crops(mic_hip_mic2_reader *const *readers, int nre
         src.device = false;
         src.blob = [readers](uint32_t v, uint32_t f) { return (const uint8_t *)readers[v]->keep.data() + readers[v]->pos[f]; };
         return (int)MIC_OK;
-    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
+    }, xyzv, n, cw, ch, cd, o, d_out, need, status, failed_frame, stats);
 } MIC_ABI_CATCH
+int mic_hip_mic2_readers_read_crops(mic_hip_mic2_reader *const *readers, int nreaders, const int32_t *xyzv, int n, int cw, int ch, int cd,
+                                    void *d_out, size_t out_cap, int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
+    return mic_hip_mic2_readers_read_crops_as(readers, nreaders, xyzv, n, cw, ch, cd, d_out, out_cap, status, failed_frame, stats, nullptr);
+}
 
 // n crops of MIC2 files that lie on the session's device: the streams go device to device
-int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
-                                          const uint8_t *const *d_files, const size_t *lens, int nfiles,
-                                          const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
-                                          int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) try {
+int mic_hip_session_mic2_multi_read_crops_as(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                             const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                             const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                             int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats, const mic_hip_out_spec *spec) try {
     if (!s) return MIC_ERR_ARGS;
     size_t need = 0;
     if (nfiles > 0 && (!head_lens || !d_files)) return MIC_ERR_ARGS;
-    const int rc = multi_crop_args(heads, lens, nfiles, xyzv, n, cw, ch, cd, out_cap, &need);
+    OutFormat o;
+    const int rc = multi_crop_args(heads, lens, nfiles, xyzv, n, cw, ch, cd, spec, o, out_cap, &need);
     if (rc) return rc;
     Mic2MultiPlan mp;
     mp.vols.resize((size_t)nfiles);
@@ -599,7 +653,13 @@ int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s, const uint8_t *con
         src.device = true;
         src.blob = [&mp, d_files](uint32_t v, uint32_t f) { const Mic2Head &m = mp.vols[v].m; return d_files[v] + 20 + 8 * (size_t)m.n + get_u32(m.table + 8 * (size_t)f); };
         return (int)MIC_OK;
-    }, xyzv, n, cw, ch, cd, d_out, need, status, failed_frame, stats);
+    }, xyzv, n, cw, ch, cd, o, d_out, need, status, failed_frame, stats);
 } MIC_ABI_CATCH
+int mic_hip_session_mic2_multi_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                          const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                          const int32_t *xyzv, int n, int cw, int ch, int cd, void *d_out, size_t out_cap,
+                                          int32_t *status, int32_t *failed_frame, mic_hip_multi_crop_stats *stats) {
+    return mic_hip_session_mic2_multi_read_crops_as(s, heads, head_lens, d_files, lens, nfiles, xyzv, n, cw, ch, cd, d_out, out_cap, status, failed_frame, stats, nullptr);
+}
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <vector>
+#include "../../include/mic_hip.h"
 
 __device__ __forceinline__ uint32_t zigzag16(int32_t v) { const uint32_t x = (uint32_t)v & 0xFFFFu; return ((x << 1) ^ ((x & 0x8000u) ? 0xFFFFu : 0u)) & 0xFFFFu; }   // deltazigzagcompressu16.go:108-111
 __device__ __forceinline__ uint32_t unzigzag16(uint32_t u) { return ((u >> 1) ^ ((u & 1u) ? 0xFFFFu : 0u)) & 0xFFFFu; }                                            // :113-116
@@ -27,15 +29,49 @@ inline unsigned row_chunks(int w, int h) {
 // (rows sstride apart) to `dst` samples into the output tensor (pixels for the RGB tensor; rows dstride apart).  pstride: how far
 // apart the unit's planes are, which only the RGB kernel reads.  The host plans and multiplies out both places (64 bits: crop x
 // depth x rows x columns passes 2^31); the kernels multiply nothing but y * stride.
-struct GatherPiece { uint64_t src, dst; int32_t sstride, dstride, w, h, pstride, pad; };
+// source: the rectangle's source as the multi doors index it (slide, volume, strip file; 0 in the one-source doors), which only the
+// typed kernels read, to pick the affine pair.
+struct GatherPiece { uint64_t src, dst; int32_t sstride, dstride, w, h, pstride, source; };
+
+// What the typed kernels (mic_gather.hip) read of a call's output description: the pair of (source, channel) is
+// pair source * src_mul + channel * ch_step of affine (a, b each); plane: samples between the channels of a pixel's destination (1: interleaved,
+// ph * pw: channels first), multiplied out by the host.
+struct OutParams { const float *affine; int32_t src_mul, ch_step; uint32_t clamp; float lo, hi; uint64_t plane; };
 
 struct mic_hip_session;
 namespace micapi {
+// A door's output description as the core reads it: a mic_hip_out_spec that mic_hip_out_spec_check has accepted (make), for sources of
+// `channels` samples a pixel.  sample: bytes of an output sample; table: the pairs the kernels read, (1, 0) where the spec has none.
+struct OutFormat {
+    int dtype = 0; uint32_t flags = 0; int channels = 1; size_t sample = 2;
+    std::vector<float> table{ 1.f, 0.f }; int32_t src_mul = 0, ch_step = 0;
+    float lo = 0, hi = 0, pad = 0;
+    int make(const mic_hip_out_spec *spec, int channels, int bits_per_sample, int nsources);
+    bool typed() const { return dtype != 0; }                                        // (MIC_HIP_OUT_NATIVE)
+    bool planar() const { return channels > 1 && (flags & 1u); }                      // (MIC_HIP_OUT_CHANNELS_FIRST)
+    size_t pixel() const { return sample * (typed() ? (size_t)channels : 1); }       // bytes of a pixel (NATIVE: sample is the pixel)
+    size_t table_bytes() const { return table.size() * sizeof(float); }
+    uint32_t pad_bits() const;                                                       // pad in the output type, repeated to fill a dword
+    OutParams params(const void *d_table, size_t plane) const {
+        return OutParams{ (const float *)d_table, src_mul, ch_step, flags & 2u, lo, hi, planar() ? plane : 1 };
+    }
+};
+// a typed tensor's base must be aligned to its sample (checked with the pointer, before anything is launched)
+inline bool out_aligned(const OutFormat &o, const void *d_out) { return !o.typed() || ((size_t)d_out & (o.sample - 1)) == 0; }
+// every sample of the tensor = pad (hipMemsetAsync where its bits are all zero, else one fill kernel), behind what `stream` holds
+int fill_pad(hipStream_t stream, const OutFormat &o, void *d_out, size_t bytes);
+// n runs of w x h x d samples of a u16 staging tensor, laid out as the output tensor, into it as o's type (MIC2 temporal volumes);
+// mw x mh x md: the largest of them
+struct ConvertRun { uint64_t at; int32_t w, h, d, source; };
+void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table, const uint16_t *stage, const ConvertRun *runs, size_t n,
+                    int mw, int mh, int md, int cw, int ch, void *out);
 // what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), or three YCoCg-R planes' RGB bytes
 enum GatherKind { kGatherU16, kGatherU8, kGatherRGB };
 // np pieces (device) of a slab -> out, behind what `stream` holds; mw x mh: the largest of them.  The one place that picks the
-// kernel, cuts the rows of tall pieces over grid y (row_chunks) and the pieces over launches of at most 2^31 - 1.
-void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out);
+// kernel, cuts the rows of tall pieces over grid y (row_chunks) and the pieces over launches of at most 2^31 - 1.  dtype
+// MIC_HIP_OUT_NATIVE: the native kernels, which read nothing of op; else the typed ones (one plane: kGatherU16 and kGatherU8 alike).
+void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out,
+                   int dtype = 0, const OutParams &op = OutParams{ nullptr, 0, 0, 0, 0, 0, 1 });
 // d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
 // pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
 // *d_out becomes the address the device uses.

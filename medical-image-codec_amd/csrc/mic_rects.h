@@ -31,8 +31,13 @@ struct RectBatches {
 struct UnitStride { int32_t row, plane; };            // samples between a unit's rows in the slab, and between its planes (RGB tiles; else 0)
 // nu units: next(i0) ends the sub-batch that starts at i0 (next_sub_batch under the reader's rule); samples(u) is what unit u takes of
 // the slab (P planes of a tile, a strip, a frame; 0: not decoded into it).  A piece's two places are multiplied out in 64 bits.
-template <class Next, class Samples, class Stride>
-RectBatches rect_batches(size_t nu, Next &&next, Samples &&samples, const std::vector<RectPiece> &pieces, int cw, int ch, Stride &&stride) {
+// source(u): the source unit u belongs to, which a piece carries to the typed kernels.  o: the tensor's layout -- a typed RGB tensor
+// counts a piece's place in samples, not pixels: interleaved, three a pixel; channels first, three planes of ch x cw a rectangle
+// and the place the one in plane 0.
+template <class Next, class Samples, class Stride, class Source>
+RectBatches rect_batches(size_t nu, Next &&next, Samples &&samples, const std::vector<RectPiece> &pieces, int cw, int ch, Stride &&stride,
+                         Source &&source, const OutFormat &o) {
+    const uint64_t per_px = o.typed() && !o.planar() ? (uint64_t)o.channels : 1, per_rect = o.planar() ? (uint64_t)o.channels : 1;
     RectBatches B;
     B.slab_off.resize(nu); B.first.assign(nu + 1, 0); B.list.resize(pieces.size());
     while (B.cuts.back() < nu) {
@@ -48,26 +53,33 @@ RectBatches rect_batches(size_t nu, Next &&next, Samples &&samples, const std::v
         while (p.unit >= B.cuts[b + 1]) b++;
         const UnitStride st = stride((size_t)p.unit);
         B.list[q] = GatherPiece{ B.slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)st.row + (uint64_t)p.sx,
-                                 ((uint64_t)p.rect * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx, st.row, cw, p.w, p.h, st.plane, 0 };
+                                 (((uint64_t)p.rect * per_rect * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx) * per_px, st.row,
+                                 (int32_t)(cw * (int)per_px), p.w, p.h, st.plane, (int32_t)source((size_t)p.unit) };
         B.first[(size_t)p.unit + 1]++;
         B.mw[b] = std::max(B.mw[b], p.w); B.mh[b] = std::max(B.mh[b], p.h);
     }
     for (size_t u = 0; u < nu; u++) B.first[u + 1] += B.first[u];
     return B;
 }
-// the list at the head of s->pieces (gather_bytes of it), which is reserved for it and `behind` bytes more (a reader's own records)
+// the list at the head of s->pieces (gather_bytes of it), which is reserved for it and `behind` bytes more (a reader's own records);
+// a typed call's affine table lies behind both (out_table)
 inline size_t gather_bytes(const RectBatches &B) { return align_up(B.list.size() * sizeof(GatherPiece), 16); }
-inline int upload_gather(mic_hip_session *s, const RectBatches &B, size_t behind = 0) {
-    const int rc = s->pieces.reserve(gather_bytes(B) + behind + 64);
+inline const void *out_table(const mic_hip_session *s, const RectBatches &B, size_t behind) { return (const char *)s->pieces.p + gather_bytes(B) + align_up(behind, 16); }
+inline int upload_gather(mic_hip_session *s, const RectBatches &B, const OutFormat &o, size_t behind = 0) {
+    const int rc = s->pieces.reserve(gather_bytes(B) + align_up(behind, 16) + (o.typed() ? o.table_bytes() : 0) + 64);
     if (rc == MIC_OK && !B.list.empty()) HIP_TRY(hipMemcpyAsync(s->pieces.p, B.list.data(), B.list.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+    if (rc == MIC_OK && o.typed()) HIP_TRY(hipMemcpyAsync((void *)out_table(s, B, behind), o.table.data(), o.table_bytes(), hipMemcpyHostToDevice, s->stream));
     return rc;
 }
-// the pieces of sub-batch b out of its decoded slab into d_out, timed as `label`; the caller resets the timer before and marks "end" behind
-inline void gather_units(mic_hip_session *s, const char *label, GatherKind kind, const void *slab, const RectBatches &B, size_t b, void *d_out) {
+// the pieces of sub-batch b out of its decoded slab into d_out, timed as `label`; the caller resets the timer before and marks "end" behind.
+// plane: the samples of one rectangle's plane (ch x cw), which a channels-first tensor's kernel steps by.
+inline void gather_units(mic_hip_session *s, const char *label, GatherKind kind, const void *slab, const RectBatches &B, size_t b, void *d_out,
+                         const OutFormat &o, size_t plane, size_t behind = 0) {
     const size_t p0 = B.first[B.cuts[b]], np = B.first[B.cuts[b + 1]] - p0;
     if (!np) return;
     s->timer.mark(label);
-    launch_gather(s->stream, kind, (const uint16_t *)slab, (const GatherPiece *)s->pieces.p + p0, np, B.mw[b], B.mh[b], d_out);
+    launch_gather(s->stream, kind, (const uint16_t *)slab, (const GatherPiece *)s->pieces.p + p0, np, B.mw[b], B.mh[b], d_out, o.dtype,
+                  o.params(out_table(s, B, behind), plane));
 }
 
 // status[r] / failed[r] (may be NULL) of rectangle r = piece.rect / per of n: MIC_OK / -1, or its first failing unit's in piece order / label(it)

@@ -176,6 +176,7 @@ struct mic_hip_session {
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
     DevBuf pieces;                         // patch and crop calls: the call's piece list (GatherPiece, mic_pieces.h; MIC2 temporal: its footprints)
+    DevBuf crop_stage;                     // MIC2 crops into a typed tensor: the u16 tensor the temporal volumes' running sums live in (mic_mic2_crops.hip)
     DevBuf wsi_fills;                      // MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
     std::vector<uint8_t> wsi_host_bytes;   // MIC3 patches from blobs: a sub-batch's stream bytes on their way up; kept, so that a loop of calls touches the same pages
     DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
@@ -337,13 +338,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -395,9 +396,10 @@ int mic2_temporal_decompress(const uint8_t *c, size_t len, int w, int h, int n_t
 int pack_streams(mic_hip_session *s, int nb, const std::function<uint64_t(int)> &len, const std::function<const uint8_t *(int)> &src, bool device,
                  std::vector<uint64_t> &begins, std::vector<uint64_t> &ends);
 // What a crop door does once it has a plan: the session -- *s, made current, or when NULL one leased here --, then d_out judged for a
-// u16 tensor of `need` bytes (patch_pointer; an allocation that ends before the tensor does and an odd address are MIC_ERR_ARGS:
-// out_cap held the tensor).
-int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need);
+// tensor of `need` bytes in o's type (patch_pointer; an allocation that ends before the tensor does and an address that is not
+// aligned to the sample -- u16 for the native format -- are MIC_ERR_ARGS: out_cap held the tensor).
+struct OutFormat;                 // (mic_pieces.h)
+int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need, const OutFormat &o);
 // MIC2 crops (mic_mic2_crops.hip).  A piece is one (crop, frame) overlap: w x h samples from (sx, sy) of frame `frame` to (dx, dy) of
 // slice dz of crop `crop`, k = the frame's place in the plan's frame list.  The temporal kernel takes one record per crop instead,
 // its footprint: frame = max(z, 0), the crop's first frame inside the volume, dz = that frame's slice, k = its last frame inside it.
@@ -411,7 +413,7 @@ int mic2_plan_crops(int width, int height, int nframes, int temporal, const int3
 // where a one-volume crop door finds the stream of a frame: blob(frame) -> its first byte, on the host or (device = true) on the session's device
 struct Mic2Source { bool device = false; std::function<const uint8_t *(uint32_t frame)> blob; };
 struct Mic2Head { int w = 0, h = 0, n = 0, temporal = 0; const uint8_t *table = nullptr; uint64_t file_len = 0; };   // table: the 8 n bytes behind the fixed header (host)
-int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t out_cap, size_t *need);
+int mic2_crop_args(const Mic2Head &m, const int32_t *xyz, int n, int cw, int ch, int cd, size_t sample_bytes, size_t out_cap, size_t *need);
 size_t workspace_budget();        // per-call workspace ceiling (mic_api.hip)
 // Units [i0, return) of the next sub-batch of a list of units of px[i] pixels each, for the readers that decode units of mixed sizes
 // into one slab (strip-file crops, MIC2 crops of many volumes; mic_strip_crops.hip): next_sub_batch (mic_staged.h) under their capacity

@@ -126,27 +126,28 @@ size_t micapi::next_strip_cut(const std::vector<size_t> &px, size_t i0) { return
 
 namespace {
 
-// n crops into d_out ([n][ch][cw] u16, an address s's device can write: patch_pointer) on a session the caller holds and has made
-// current.  base[f]: where file f's bytes lie -- on the host, or (device) on the session's device.
-int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *const *base, bool device, int n, int cw, int ch,
+// n crops into d_out ([n][ch][cw] samples of o's type, an address s's device can write: patch_pointer) on a session the caller holds
+// and has made current.  base[f]: where file f's bytes lie -- on the host, or (device) on the session's device.
+int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *const *base, bool device, int n, int cw, int ch, const OutFormat &o,
                       void *d_out, size_t need, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
     const size_t nu = plan.units.size();
     int rc;
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
-    HIP_TRY(hipMemsetAsync(d_out, 0, need, s->stream));                                     // outside the images, rows no strip covers, refused files
+    if ((rc = fill_pad(s->stream, o, d_out, need))) return rc;                              // outside the images, rows no strip covers, refused files
     auto entry = [&](size_t u) -> const StripEntry & { return plan.files[plan.units[u].file].e[plan.units[u].strip]; };
     auto width = [&](size_t u) { return plan.files[plan.units[u].file].w; };
     std::vector<size_t> px(nu);
     for (size_t u = 0; u < nu; u++) px[u] = (size_t)width(u) * (size_t)(entry(u).y1 - entry(u).y0);
     const RectBatches L = rect_batches(nu, [&](size_t i0) { return next_strip_cut(px, i0); }, [&](size_t u) { return px[u]; },
-                                       plan.pieces, cw, ch, [&](size_t u) { return UnitStride{ width(u), 0 }; });
+                                       plan.pieces, cw, ch, [&](size_t u) { return UnitStride{ width(u), 0 }; },
+                                       [&](size_t u) { return plan.units[u].file; }, o);
     size_t comp_max = 0;                                                                    // the most stream bytes of a sub-batch
     for (size_t b = 0, comp = 0; b < L.subs(); b++, comp = 0)
         for (size_t u = L.cuts[b]; u < L.cuts[b + 1]; u++) comp_max = std::max(comp_max, comp += entry(u).len);
     if (nu) {
         if ((rc = s->io_comp.reserve(comp_max + 64))) return rc;                            // (once: pack_streams then finds room for every sub-batch)
         if ((rc = s->io_px.reserve(L.slab_max * 2 + 64))) return rc;
-        if ((rc = upload_gather(s, L))) return rc;
+        if ((rc = upload_gather(s, L, o))) return rc;
     }
     std::vector<int32_t> ust(nu, MIC_OK);                                                   // status of unit u
     std::vector<uint64_t> begins, ends; std::vector<mic_hip_unit> units;
@@ -163,7 +164,7 @@ int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *
         if ((rc = session_decode_enqueue_spans(s, (const uint8_t *)s->io_comp.p, begins.data(), ends.data(), units.data(), nb, (uint16_t *)s->io_px.p))) return rc;
         if ((rc = session_decode_finish(s, ust.data() + u0))) return rc;
         s->timer.reset(s->stream);
-        gather_units(s, "k_strips_gather_crops", kGatherU16, s->io_px.p, L, b, d_out);
+        gather_units(s, "k_strips_gather_crops", kGatherU16, s->io_px.p, L, b, d_out, o, (size_t)ch * (size_t)cw);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());
     }
@@ -175,18 +176,20 @@ int strips_read_crops(mic_hip_session *s, const StripPlan &plan, const uint8_t *
 
 // a door's call: arguments, n == 0, the plan, the pointer, then the core on session s (leased here when s is NULL)
 int strips_call(mic_hip_session *s, StripPlan &plan, const uint8_t *const *base, bool device, const int32_t *xyf, int n, int cw, int ch,
-                void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
+                void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats, const mic_hip_out_spec *spec) {
     size_t need = 0;
-    int rc = tensor_bytes(n, 1, ch, cw, 2, out_cap, &need);
+    OutFormat o;
+    int rc = o.make(spec, 1, 16, (int)plan.files.size());
     if (rc) return rc;
+    if ((rc = tensor_bytes(n, 1, ch, cw, o.pixel(), out_cap, &need))) return rc;
     if ((rc = strips_plan_crops(plan, xyf, n, cw, ch))) return rc;
     if (stats) *stats = mic_hip_strip_crop_stats{ 0, 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     if (device) for (const StripUnit &u : plan.units) if (!base[u.file]) return MIC_ERR_ARGS;    // (a file whose strips are needed is not there)
     DefaultLease lease;
-    if ((rc = crop_door(&s, lease, &d_out, need))) return rc;
-    if ((rc = strips_read_crops(s, plan, base, device, n, cw, ch, d_out, need, status, failed_strip, stats))) return rc;
+    if ((rc = crop_door(&s, lease, &d_out, need, o))) return rc;
+    if ((rc = strips_read_crops(s, plan, base, device, n, cw, ch, o, d_out, need, status, failed_strip, stats))) return rc;
     container_codes(n, status, [&](int i) { return plan.files[(size_t)xyf[3 * (size_t)i + 2]].status; });
     return MIC_OK;
 }
@@ -213,21 +216,27 @@ int mic_hip_strips_crop_plan(const uint8_t *const *files, const size_t *lens, in
 } MIC_ABI_CATCH
 
 // n crops of strip files in host memory, into a tensor on the default session's device
-int mic_hip_strips_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch,
-                              void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) try {
+int mic_hip_strips_read_crops_as(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                                 void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats,
+                                 const mic_hip_out_spec *spec) try {
     const int rc = strips_crop_args(files, lens, nfiles, xyf, n, cw, ch);
     if (rc) return rc;
     StripPlan plan;
     plan.files.resize((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) { plan.files[(size_t)f].head = files[f]; plan.files[(size_t)f].head_len = plan.files[(size_t)f].len = lens[f]; }
-    return strips_call(nullptr, plan, files, false, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats);
+    return strips_call(nullptr, plan, files, false, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats, spec);
 } MIC_ABI_CATCH
+int mic_hip_strips_read_crops(const uint8_t *const *files, const size_t *lens, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                              void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
+    return mic_hip_strips_read_crops_as(files, lens, nfiles, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats, nullptr);
+}
 
 // n crops of strip files that lie on the session's device: the streams go device to device
-int mic_hip_session_strips_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
-                                      const uint8_t *const *d_files, const size_t *lens, int nfiles,
-                                      const int32_t *xyf, int n, int cw, int ch,
-                                      void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) try {
+int mic_hip_session_strips_read_crops_as(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                         const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                         const int32_t *xyf, int n, int cw, int ch,
+                                         void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats,
+                                         const mic_hip_out_spec *spec) try {
     if (!s) return MIC_ERR_ARGS;
     const int rc = strips_crop_args(heads, lens, nfiles, xyf, n, cw, ch);
     if (rc) return rc;
@@ -235,7 +244,13 @@ int mic_hip_session_strips_read_crops(mic_hip_session *s, const uint8_t *const *
     StripPlan plan;
     plan.files.resize((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) { plan.files[(size_t)f].head = heads[f]; plan.files[(size_t)f].head_len = head_lens[f]; plan.files[(size_t)f].len = lens[f]; }
-    return strips_call(s, plan, d_files, true, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats);
+    return strips_call(s, plan, d_files, true, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats, spec);
 } MIC_ABI_CATCH
+int mic_hip_session_strips_read_crops(mic_hip_session *s, const uint8_t *const *heads, const size_t *head_lens,
+                                      const uint8_t *const *d_files, const size_t *lens, int nfiles,
+                                      const int32_t *xyf, int n, int cw, int ch,
+                                      void *d_out, size_t out_cap, int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats) {
+    return mic_hip_session_strips_read_crops_as(s, heads, head_lens, d_files, lens, nfiles, xyf, n, cw, ch, d_out, out_cap, status, failed_strip, stats, nullptr);
+}
 
 }  // extern "C"
