@@ -1,15 +1,16 @@
 // mic_decode.hip -- decode kernels of the MIC unit codec for gfx950.
 //
-//   k_dec_tans_serial / k_dec_tans_gl   what the lane-per-state kernels of mic_decode_ls.hip leave: 1-state streams
-//                  (fsedecompressu16.go:267-377) and tableLog-16 tables with 0-bit entries (table in L2), plus the decode launcher.
-//   Tables: mic_tables.hip; lane-per-state tANS: mic_decode_ls.hip; RLE expansion and inverse predictor: mic_decode_px.hip.
-//   (Round 1's decoders k_dec_tans_duo / k_dec_tans_lds and the serial kernel generation: tools/retired/.)
+//   k_dec_tans_gl      one wave per N-state stream, table in L2: what the lane-per-state kernels of mic_decode_ls.hip leave
+//                      (tableLog-16 tables with 0-bit entries); walks a frame's RLE headers as it goes (mic_rlewalk.h)
+//   k_dec_tans_serial  one lane per stream: 1-state streams (fsedecompressu16.go:267-377) and whatever nobody else took
+//   k_dec_gap_check    gap removal's checking decode path (mic_gap.hip); and mic_launch_decode, the decode chain's launcher
+//   Tables: mic_tables.hip; tANS per lane, states -> symbols: mic_decode_ls.hip; tokens -> pixels: mic_decode_px.hip, _rows.hip, _fused.hip.
 //
 // Launch shape: blockIdx.x = unit.
 #include "mic_dev.h"
 #include "mic_fse_tables.h"
 #include "mic_launch.h"
-
+#include "mic_rlewalk.h"
 
 // Reverse bit reader (bitreader.go): the highest set bit of the last byte is the end mark;
 // bits are consumed from there towards the front.  `cursor` = number of unread bits.
@@ -116,29 +117,8 @@ __global__ void __launch_bounds__(64) k_dec_gap_check(MicUnit *units) {
     if (__any(bad) && lane == 0) u.status = MICD_ERR_CORRUPT;
 }
 
-
-
-
-
 // ==========================================================================================
-// Two streams per wave (tableLog <= 13).  A SIMD issues one instruction per 4-cycle turn whatever its kind
-// (measured: a stream runs at 134 cycles per symbol pair alone, 142 with one wave per SIMD, ~214 with two, and a
-// launch waits for its slowest wave), so with more than one wave per SIMD the decode is bound by instructions
-// issued per pair -- about 21 -- and every lane of those instructions computes the same thing.  Here lanes 0-31 run
-// stream 2w and lanes 32-63 stream 2w+1 through the SAME instructions: per-half values (table base, ring base, bit
-// position, states, tableLog) live in VGPRs, the two tables / rings / stages sit side by side in LDS (35.5 KiB per
-// wave: four waves = eight streams per CU, one wave per SIMD), and a pair of streams costs what one did.
-// The halves differ in length: the loop runs for the longer one; the shorter one keeps decoding harmless garbage
-// (every table entry is valid, the ring wraps, block loads are bounds-checked) behind a snapshot of its true end
-// state, and its stores and header walk are switched off.  Units of another class in a pair are left to the
-// single-stream kernels.  LDS bytes: ring A 0, stage A 1056, ring B 2048, stage B 3104, table A 3584, table B 19968.
-#define T2_TAB0 3584u
-#define T2_WAVE 0x9000u                            // LDS bytes of one wave (its bits stay clear of the ring-index mask 0x3FC)
-#define T2_WAVES 4                                 // waves per group: one per SIMD by construction (four single-wave groups
-                                                   // landed two-on-a-SIMD on a third of the CUs, and the younger wave starves)
-
-// ==========================================================================================
-// The same decoder with the transition table left in HBM / L2 (u32 entries newState | nbBits << 16, as the
+// One wave per stream, the transition table left in HBM / L2 (u32 entries newState | nbBits << 16, as the
 // tables kernel writes them): for tableLog 16 -- every 16-bit-depth frame, CT above all -- the table has
 // 65536 entries and a 17-bit nextState, too much for LDS.  A chain step is then an L2 round trip instead
 // of an LDS one, but a wave needs only the 1.3 KiB ring + stage, so a CU holds as many streams as it has
@@ -223,32 +203,13 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
         st[k] = (e & 0xFFFFu) + take(hi, nb);
         q -= (int32_t)nb;
     };
-    // header walker, as in k_dec_tans_lds
-    bool w_on = u.mode == 0 && u.seg != nullptr;
-    bool w_err = false;
-    uint32_t w_pos = 0, w_out = 0, w_nseg = 0, w_mid = 0;
-    const uint32_t w_symcap = min(u.sym_cap, 2u * (uint32_t)u.w * (uint32_t)u.h + 2u), w_segcap = u.seg_cap;
-    typedef uint32_t w_v2 __attribute__((ext_vector_type(2)));
-    __attribute__((address_space(1))) w_v2 *const w_seg = (__attribute__((address_space(1))) w_v2 *)u.seg;
+    // header walker (mic_rlewalk.h): a chunk's headers are read out of the registers that hold its tokens
+    const bool frame = u.mode == 0 && u.seg != nullptr;
+    MicRleWalk wk; wk.init(u, frame, count);
     auto walk = [&](uint32_t cend, auto get) {
-        while (w_on && w_pos < cend) {
-            const uint32_t h = get(w_pos);
-            if (w_pos == 0) {
-                const int d0 = mic_len16((uint16_t)h);
-                if (d0 == 0) { w_on = false; w_err = true; break; }
-                w_mid = (1u << (d0 - 1)) - 1; w_pos = 1;
-                continue;
-            }
-            if (w_out >= w_symcap) { w_on = false; break; }
-            if (h == 0 || w_nseg >= w_segcap) { w_on = false; w_err = true; break; }
-            if (h <= w_mid) {
-                if (w_pos + 1 >= count) { w_on = false; w_err = true; break; }
-                if (lane == 0) { w_v2 r; r.x = (w_pos + 1) | 0x80000000u; r.y = w_out; w_seg[w_nseg] = r; }
-                w_nseg++; w_out += h; w_pos += 2;
-            } else {
-                if (lane == 0) { w_v2 r; r.x = w_pos + 1; r.y = w_out; w_seg[w_nseg] = r; }
-                w_nseg++; w_out += h - w_mid; w_pos += 1 + (h - w_mid);
-            }
+        while (wk.on && wk.pos < cend) {
+            const uint32_t h = get(wk.pos);
+            if (wk.pos == 0) wk.first(h); else wk.step(h, lane);
         }
     };
     constexpr uint32_t G = TG_CH / N;
@@ -296,11 +257,10 @@ __global__ void __launch_bounds__(64) k_dec_tans_gl(MicUnit *units) {
         if (count == u.count && q + 32 - (int32_t)(8u * sb) < 0) u.status = MICD_ERR_CORRUPT;   // bitreader.go:113-120 (a prefix reads less)
         else {
             u.ntok = count;
-            if (u.mode == 0 && u.seg != nullptr && !w_err) { u.nseg = w_nseg; u.nsym = min(w_out, w_symcap); u.walk_ok = 1; }
+            if (frame && !wk.err) wk.finish(u);
         }
     }
 }
-
 
 void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant, MicTimer *t, int *d_cls, uint32_t pred_mask, uint32_t cls_mask,
                        const MicSplitCfg *split) {

@@ -19,8 +19,8 @@
 //     row with their raw bits) over up to 512 symbols more than the row has pixels.
 //   * then the predictor, and the row leaves through the same LDS buffer in 1 KiB runs (mic_decode_rows.hip).
 // Whatever is out of the ordinary -- a literal piece that points past the stream, symbols that run out, a hole or a backward step in
-// the segment list, fewer than eight tokens -- is NOT handled here: the unit is left as it was (walk_ok stays 1) and the
-// two-kernel path behind this one decodes it, with the reference's error behaviour.  A unit done here is marked walk_ok = 4.
+// the segment list, fewer than eight tokens -- is NOT handled here: the unit is left as it was (it stays at MIC_STAGE_SEGS) and the
+// two-kernel path behind this one decodes it, with the reference's error behaviour.  A unit done here is marked MIC_STAGE_PIXELS.
 #include "mic_dev.h"
 #include "mic_launch.h"
 #include "mic_rowpred.h"
@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
     const int ui = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     if (ui >= n_units) return;
     MicUnit &u = units[ui];
-    if (u.status != MICD_OK || u.mode != 0 || u.pred || u.walk_ok != 1) return;
+    if (u.status != MICD_OK || u.mode != 0 || u.pred || u.dec_stage != MIC_STAGE_SEGS) return;
     const int W = __builtin_amdgcn_readfirstlane(u.w), H = __builtin_amdgcn_readfirstlane(u.h);
     if (mic_rows_k(W) != K) return;
     const uint32_t lane = threadIdx.x & 63;
@@ -63,15 +63,9 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
     const uint32_t ntok = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.ntok), nseg = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.nseg);
     const uint32_t nsym = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(u.nsym, min(u.sym_cap, 2u * npx + 2u)));
     if (ntok < 8 || nseg < 1 || nsym < 1 || nseg > 16u * (uint32_t)H + 64u) return;
-    const uintptr_t px_u = ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uintptr_t)u.px_out >> 32)) << 32) |
-                           (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)u.px_out);
-    const uintptr_t tok_u = ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uintptr_t)u.tok >> 32)) << 32) |
-                            (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)u.tok);
-    const rf_gu16 px = (rf_gu16)px_u;
-    const rf_gcu16 tok = (rf_gcu16)tok_u;
-    const uintptr_t seg_u = ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uintptr_t)u.seg >> 32)) << 32) |
-                            (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)u.seg);
-    const rf_gseg seg = (rf_gseg)seg_u;
+    const rf_gu16 px = mic_wave_gp(u.px_out);
+    const rf_gcu16 tok = mic_wave_gp((const uint16_t *)u.tok);
+    const rf_gseg seg = mic_wave_gp((const uint2 *)u.seg);
     // the stream's own parameters (deltarlecompressu16.go:25-27, :71): the first symbol is the max value
     const uint32_t seg0x = (uint32_t)__builtin_amdgcn_readfirstlane((int)(seg[0].x & 0x7FFFFFFFu));
     if (seg0x >= ntok) return;
@@ -79,12 +73,9 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
     if (depth == 0) return;
     const uint32_t thr = (1u << (depth - 1)) - 1u, delim = (1u << depth) - 1u;
     const uint32_t thr2 = thr | (thr << 16);
-    const uint32_t x0 = lane * K;
-    const int nv = min(max(W - (int)x0, 0), K);
-    const int nl = (W + K - 1) / K;
-    const uint32_t voff = lane * 16u;
-    const uint32_t nfull = (uint32_t)W / 8u, ntail = (uint32_t)W % 8u;
-    typedef uint16_t rf_pk __attribute__((ext_vector_type(2)));
+    const RowLanes<K> g(lane, W);
+    const uint32_t x0 = g.x0, voff = g.voff, nfull = g.nfull, ntail = g.ntail;
+    const int nv = g.nv;
 
     // ---- the segment window: records wbase + lane of the walk, in registers ----
     uint32_t wbase = 0, segx = 0, segy = 0;
@@ -366,19 +357,13 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
             __builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll
             for (int q = 0; q < KD; q++) e[q] = pb[lane * KD + q];
-            const uint32_t pf = min(x0, (uint32_t)W - 1u), w = pf >> 5;
-            const uint32_t f0 = rawb[w], f1 = rawb[w + 1], f2 = rawb[w + 2];
-            const uint32_t l32 = __builtin_amdgcn_alignbit(f1, f0, pf), h32 = __builtin_amdgcn_alignbit(f2, f1, pf);
-            raw = (((uint64_t)h32 << 32) | l32) & (nv >= 64 ? ~0ull : ((1ull << nv) - 1ull));
+            raw = mic_row_raw_bits(rawb, min(x0, (uint32_t)W - 1u)) & g.vmask();
         }
         // symbols minus thr, packed, back into LDS (the lane's own dwords of the pixel row): the predictor reads them from there, twice --
         // held in registers next to the row above AND the next row's loads they are what spills
         __builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll
-        for (int q = 0; q < KD; q++) {
-            const rf_pk a = __builtin_bit_cast(rf_pk, e[q]), t2 = __builtin_bit_cast(rf_pk, thr2);
-            pb[lane * KD + q] = __builtin_bit_cast(uint32_t, (rf_pk)(a - t2));   // (invalid positions were set to thr above: zero here)
-        }
+        for (int q = 0; q < KD; q++) pb[lane * KD + q] = mic_row_minus_thr(e[q], thr2);   // (invalid positions were set to thr above: zero here)
         RowSymsLds es{ pb + lane * KD };
         __builtin_amdgcn_s_waitcnt(0xC07F);                             // (the buffers are read: the row's results may go in)
         RF_T(5);
@@ -393,15 +378,9 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
         // registers the widest class is short of; a spill's reload waits for every memory operation in flight, the row before's
         // stores included)
         bool fine;
-        if (y == 0) { RP::slow_row(tp, es, raw, true, thr, lane, nl); fine = true; }
+        if (y == 0) { RP::slow_row(tp, es, raw, true, thr, lane, g.nl); fine = true; }
         else fine = RP::fast_row(tp, es, raw, thr, lane, nv);
-        if (!fine) {                                                    // the wrap-around fired somewhere: the row above again, then lane by lane
-            const uint32_t p = (uint32_t)(y - 1) * (uint32_t)W + x0;
-#pragma unroll
-            for (int q = 0; q < KD; q++) tp[q] = (uint32_t)px[min(p + 2 * q, npx - 1)] | ((uint32_t)px[min(p + 2 * q + 1, npx - 1)] << 16);
-            RP::slow_row(tp, es, raw, false, thr, lane, nl);
-            RF_ROW(3);
-        }
+        if (!fine) { RP::redo_row(tp, es, raw, thr, lane, g, px, y, W, npx); RF_ROW(3); }   // the wrap-around fired somewhere
         RF_T(2);
         put(y);
         RF_T(3);
@@ -411,7 +390,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
 #ifdef RF_STATS
     if (lane == 0) { for (int i = 0; i < 4; i++) { u.dbg[i] = st_rows[i]; u.dbg[4 + i] = (uint32_t)(st_t[i] >> 4); } u.dbg[1] = (uint32_t)(st_t[4] >> 4); u.dbg[2] = (uint32_t)(st_t[5] >> 4); }
 #endif
-    if (lane == 0) { u.dec_thr = thr; u.walk_ok = 4; }                   // pixels done: the two-kernel path skips this unit
+    if (lane == 0) { u.dec_thr = thr; u.dec_stage = MIC_STAGE_PIXELS; }  // pixels done: the two-kernel path skips this unit
 }
 
 void mic_launch_decode_fused(MicUnit *d_units, int n, hipStream_t stream, uint32_t kmask) {

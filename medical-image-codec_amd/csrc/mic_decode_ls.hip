@@ -5,7 +5,7 @@
 //   state_k -> table entry -> (nbBits, nextState) -> bits at the running position -> state_k'
 // and decode throughput = resident streams / latency of one round of N symbols.  Two things bound it on a
 // CU: the LDS holds the 16-bit nextState tables of at most NINE streams (tableLog 13: 16 KiB each), and a wave issues one
-// instruction per ~5 cycles whatever its lanes do.  The earlier kernel (k_dec_tans_duo, mic_decode.hip) ran every lane of a
+// instruction per ~5 cycles whatever its lanes do.  The retired k_dec_tans_duo ran every lane of a
 // wave through the same values -- two distinct streams per 64 lanes, N table look-ups issued one after the other -- so it
 // was bound by instructions issued per symbol and got slower with more states.  Here lane g*N + k of a wave owns state k of
 // the wave's stream g (three streams per wave, three waves per group, one group per CU; N = 4: lane 16 g + k, a DPP row a stream):
@@ -30,6 +30,7 @@
 #include "mic_dev.h"
 #include "mic_launch.h"
 #include "mic_wave.h"
+#include "mic_rlewalk.h"
 
 // Table-size classes: streams per wave x waves per group are what the LDS holds of 2 << tableLog byte tables.
 //   tableLog 13: 3 x 3 = nine streams (159 120 bytes) | 14: 2 x 2 (136 256) | 15: 1 x 2 (134 736) | 16: 1 x 1 (133 392)
@@ -546,7 +547,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
         uo.dec_kernel = 1u + (uint32_t)((TL <= 12 ? 4 : TL - 13) * 6 + (N == 2 ? 0 : N == 4 ? 2 : 4) + (ZB ? 1 : 0));   // this instance's class, as mic_dec_cls numbers it
         // bitreader.go:113-120: more bits taken than the stream holds -- a prefix has read only the bits behind its own symbols
         if (count == uo.count && q + 32 - (int32_t)(8u * sb) < 0) uo.status = MICD_ERR_CORRUPT;
-        else { uo.ntok = count; uo.walk_ok = 2; }                           // tok holds STATES: k_dec_translate turns them into symbols
+        else { uo.ntok = count; uo.dec_stage = MIC_STAGE_STATES; }   // tok holds STATES: k_dec_translate turns them into symbols
     }
 }
 
@@ -870,12 +871,12 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
     uo.split[5] = R; uo.split[6] = fail; uo.split[7] = (uint32_t)PARTS;
     if (outcome == MIC_SPLIT_DONE) {
         uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
-        uo.ntok = T; uo.walk_ok = 2;                                        // tok and sym hold STATES: k_dec_translate joins and translates them
+        uo.ntok = T; uo.dec_stage = MIC_STAGE_STATES;                // tok and sym hold STATES: k_dec_translate joins and translates them
     } else retry_list[atomicAdd(retry_count, 1)] = unit_i;
 }
 
 // ==========================================================================================
-// States -> symbols, and the RLE header walk.  One group of 256 threads per unit that k_dec_tans_ls decoded (walk_ok == 2):
+// States -> symbols, and the RLE header walk.  One group of 256 threads per unit that k_dec_tans_ls decoded (MIC_STAGE_STATES):
 // the unit's symbol table (tableSymbol of each state, <= 16 KiB) sits in LDS, waves 1-3 stream the states through it in tiles
 // of 1536 (16 bytes in, eight LDS look-ups, 16 bytes out, in place) and leave each translated tile in LDS as well, where wave 0
 // follows the linked list of RLE headers through it (rledecompressu16.go:59-85: a header <= midCount is a run of one value, a
@@ -888,7 +889,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
 // mask misses the arrival walks again from there) -- and the headers from the arrival bit on are the true ones.  Segment
 // records then leave from all lanes at once behind two DPP prefix sums (record index, first symbol).  Where headers are sparse
 // (long literal chunks: noisy frames) the plain header-to-header loop is the cheaper one; the previous tile's count picks.
-// Stop and error rules are those of the walkers in mic_decode.hip: on an error the segments are dropped and the consumer
+// Stop and error rules are MicRleWalk's (mic_rlewalk.h), which is the header-to-header loop: on an error the segments are dropped and the consumer
 // (k_dec_pixels_wg) walks the stream itself and reports it.  Frames (mode 0) are walked, other units are translated only.
 #define TR_THREADS 256                            // one walker wave + three translating waves: seven groups (walkers) per CU -- the walk is
                                                   // serial per unit, and on run-dense streams (WSI planes) it is what a unit waits for
@@ -899,7 +900,7 @@ static_assert(TR_SEG == 24 && TR_SEG * 64 == TR_TILE, "lane = position / 24 belo
 template <int TRTL>   // 13: tables up to 2^13 states (two groups per CU) | 16: up to 2^16 (128 KiB of LDS: one group per CU)
 __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
-    if (u.status != MICD_OK || u.walk_ok != 2) return;
+    if (u.status != MICD_OK || u.dec_stage != MIC_STAGE_STATES) return;
     if ((TRTL == 13) != (u.table_log <= 13)) return;
     __shared__ uint16_t s_sym[1 << TRTL];
     __shared__ __attribute__((aligned(16))) uint16_t s_tile[2][TR_TILE + 64];
@@ -923,15 +924,11 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
     const uint16_t *scr = u.sym;
     const bool frame = u.mode == 0 && u.seg != nullptr;
     // (a length-prefixed RLE stream, walk_mode 1 -- a whole WaveletV2 frame -- is one unit of millions of tokens: walking it here would
-    //  be one wave's work per frame; it is marked walk_ok = 3 and walked in parts by k_rle_walk_parts, mic_wavelet.hip)
+    //  be one wave's work per frame; it is marked MIC_STAGE_PARTS and walked in parts by k_rle_walk_parts, mic_wavelet.hip)
     const bool prefixed = u.mode == 1 && u.walk_mode == 1 && u.seg != nullptr;
-    // walker (wave 0; uniform values)
-    bool w_on = frame, w_err = false, w_dense = false;
-    uint32_t w_pos = 0, w_out = 0, w_nseg = 0, w_mid = 0;
-    const uint32_t w_cap = min(u.sym_cap, 2u * (uint32_t)u.w * (uint32_t)u.h + 2u);   // symbols the pixels can use
-    const uint32_t w_segcap = u.seg_cap;
-    typedef __attribute__((address_space(1))) ls_v2 *seg_p;
-    const seg_p w_seg = (seg_p)u.seg;
+    // walker (wave 0; uniform values: mic_rlewalk.h)
+    MicRleWalk wk; wk.init(u, frame, ntok);
+    bool w_dense = false;
     __syncthreads();
     typedef uint32_t tr_v4 __attribute__((ext_vector_type(4)));
     const uint32_t smask = size - 1;                                        // a state carries its +size offset: index = state - size
@@ -971,39 +968,24 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
             }
         }
         __syncthreads();                                                    // tile `it` is in LDS; the walker is done with tile it - 1
-        if (wave != 0 || !w_on || w_pos >= tile_end) continue;
-        if (w_pos == 0) {                                                   // token 0 fixes the run / literal split (rledecompressu16.go:21-25)
-            const int d0 = mic_len16(tile[0]);
-            if (d0 == 0) { w_on = false; w_err = true; continue; }
-            w_mid = (1u << (d0 - 1)) - 1; w_pos = 1;
+        if (wave != 0 || !wk.on || wk.pos >= tile_end) continue;
+        if (wk.pos == 0) {                                                  // token 0 fixes the run / literal split
+            wk.first(tile[0]);
+            if (!wk.on) continue;
         }
-        const uint32_t nseg_in = w_nseg;
+        const uint32_t nseg_in = wk.nseg;
         if (!w_dense) {
             // ---- header to header, from a 64-token window and v_readlane ----
-            while (w_on && w_pos < tile_end) {
-                const uint32_t rel = w_pos - base;                          // (>= 0: a header inside an earlier tile was taken there)
+            while (wk.on && wk.pos < tile_end) {
+                const uint32_t rel = wk.pos - base;                         // (>= 0: a header inside an earlier tile was taken there)
                 const uint32_t wv = (rel + lane < tile_end - base) ? (uint32_t)tile[rel + lane] : 0u;
                 uint32_t j = 0;
-                while (j < 64 && w_on && w_pos < tile_end) {
-                    const uint32_t hd = ls_rl(wv, (int)j);
-                    if (w_out >= w_cap) { w_on = false; break; }
-                    if (hd == 0 || w_nseg >= w_segcap) { w_on = false; w_err = true; break; }
-                    uint32_t adv, len;
-                    if (hd <= w_mid) {
-                        if (w_pos + 1 >= ntok) { w_on = false; w_err = true; break; }
-                        if (lane == 0) { ls_v2 r; r.x = (w_pos + 1) | 0x80000000u; r.y = w_out; w_seg[w_nseg] = r; }
-                        len = hd; adv = 2;
-                    } else {
-                        if (lane == 0) { ls_v2 r; r.x = w_pos + 1; r.y = w_out; w_seg[w_nseg] = r; }
-                        len = hd - w_mid; adv = 1 + len;
-                    }
-                    w_nseg++; w_out += len;
-                    w_pos += adv; j += adv;                                 // j >= 64: the next header is outside the window
-                }
+                while (j < 64 && wk.on && wk.pos < tile_end) j += wk.step(ls_rl(wv, (int)j), lane);   // j >= 64: the next header is outside the window
             }
         } else {
             // ---- all lanes: lane l walks tokens [24 l, 24 l + 24) of the tile from the first one on; the true walk enters at rel0 ----
-            const uint32_t tlen = tile_end - base, rel0 = w_pos - base;
+            // (the walker's stop and error rules in data-parallel form: only the header classifier is shared with it)
+            const uint32_t tlen = tile_end - base, rel0 = wk.pos - base;
             const uint32_t s0 = lane * TR_SEG, s1 = min(s0 + TR_SEG, tlen);
             uint32_t mask = 0, ex = 0;
             auto lane_walk = [&](uint32_t p) {                              // mask: visited positions (bit = position - s0); ex: where the walk leaves
@@ -1012,7 +994,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
                     const uint32_t h = tile[p];
                     if (h == 0) { p = 0xFFFFFFFFu; break; }
                     mask |= 1u << (p - s0);
-                    p += (h <= w_mid) ? 2u : 1u + h - w_mid;
+                    p += mic_rle_hdr(h, wk.mid).adv;
                 }
                 ex = p;
             };
@@ -1028,36 +1010,35 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
             }
             const uint32_t tm = (ent != 0xFFu) ? (mask & (0xFFFFFFFFu << ent)) : 0u;   // this lane's true headers
             uint32_t oc = 0;
-            for (uint32_t t = tm; t; t &= t - 1) { const uint32_t h = tile[s0 + (uint32_t)__builtin_ctz(t)]; oc += (h <= w_mid) ? h : h - w_mid; }
+            for (uint32_t t = tm; t; t &= t - 1) oc += mic_rle_hdr(tile[s0 + (uint32_t)__builtin_ctz(t)], wk.mid).len;
             const uint32_t hc = (uint32_t)__popc(tm);
             const uint32_t ihc = mic_wave_incl_add(hc), ioc = mic_wave_incl_add(oc);
             const uint32_t tot_h = ls_rl(ihc, 63), tot_o = ls_rl(ioc, 63);
-            uint32_t idx = w_nseg + ihc - hc, o = w_out + ioc - oc, nval = 0;
-            bool bad = ent != 0xFFu && ex == 0xFFFFFFFFu && w_out + ioc < w_cap;   // the zero header is reached before the stream has its symbols
+            uint32_t idx = wk.nseg + ihc - hc, o = wk.out + ioc - oc, nval = 0;
+            bool bad = ent != 0xFFu && ex == 0xFFFFFFFFu && wk.out + ioc < wk.symcap;   // the zero header is reached before the stream has its symbols
             for (uint32_t t = tm; t; t &= t - 1) {
-                const uint32_t b = (uint32_t)__builtin_ctz(t), pos = base + s0 + b, h = tile[s0 + b];
-                const bool run = h <= w_mid;
-                const uint32_t len = run ? h : h - w_mid;
-                if (o < w_cap) {
-                    if (idx >= w_segcap || (run && pos + 1 >= ntok)) bad = true;
+                const uint32_t b = (uint32_t)__builtin_ctz(t), pos = base + s0 + b;
+                const MicRleHdr hd = mic_rle_hdr(tile[s0 + b], wk.mid);
+                if (o < wk.symcap) {
+                    if (idx >= wk.segcap || (hd.run && pos + 1 >= ntok)) bad = true;
                     else {
-                        ls_v2 r; r.x = (pos + 1) | (run ? 0x80000000u : 0u); r.y = o; w_seg[idx] = r;
+                        MicRleWalk::v2 r; r.x = hd.rec(pos); r.y = o; wk.seg[idx] = r;
                     }
                     nval++;
                 }
-                idx++; o += len;
+                idx++; o += hd.len;
             }
-            if (__ballot(bad)) { w_on = false; w_err = true; continue; }
-            if (w_out + tot_o >= w_cap) { w_nseg += ls_rl(mic_wave_incl_add(nval), 63); w_on = false; }   // the stream has its symbols: headers behind that are not read
-            else w_nseg += tot_h;
-            w_out += tot_o;
-            w_pos = base + cur;
+            if (__ballot(bad)) { wk.fail(); continue; }
+            if (wk.out + tot_o >= wk.symcap) { wk.nseg += ls_rl(mic_wave_incl_add(nval), 63); wk.on = false; }   // the stream has its symbols: headers behind that are not read
+            else wk.nseg += tot_h;
+            wk.out += tot_o;
+            wk.pos = base + cur;
         }
-        w_dense = w_nseg - nseg_in >= TR_DENSE;
+        w_dense = wk.nseg - nseg_in >= TR_DENSE;
     }
     if (tid == 0) {
-        if (frame && !w_err) { u.nseg = w_nseg; u.nsym = min(w_out, w_cap); u.walk_ok = 1; }
-        else u.walk_ok = prefixed ? 3u : 0u;
+        if (frame && !wk.err) wk.finish(u);
+        else u.dec_stage = prefixed ? MIC_STAGE_PARTS : MIC_STAGE_NONE;
     }
 }
 
@@ -1068,7 +1049,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
 #define TRW_THREADS 1024
 __global__ void __launch_bounds__(TRW_THREADS) k_dec_translate_wide(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
-    if (u.status != MICD_OK || u.walk_ok != 2 || u.table_log <= 13) return;
+    if (u.status != MICD_OK || u.dec_stage != MIC_STAGE_STATES || u.table_log <= 13) return;
     if (!(u.mode == 1 && u.walk_mode == 1 && u.seg != nullptr)) return;     // (frames and bare streams: k_dec_translate<16>, which walks)
     __shared__ uint16_t s_sym[1 << 16];
     const uint32_t tid = threadIdx.x;
@@ -1092,7 +1073,7 @@ __global__ void __launch_bounds__(TRW_THREADS) k_dec_translate_wide(MicUnit *uni
     }
     for (uint32_t i = 8 * nvec + tid; i < ntok; i += TRW_THREADS) tok[i] = s_sym[tok[i] & smask];
     __syncthreads();                                                        // (every state of the unit has been read as a state)
-    if (tid == 0) u.walk_ok = 3u;                                           // translated; the headers are k_rle_walk_parts's
+    if (tid == 0) u.dec_stage = MIC_STAGE_PARTS;                            // translated; the headers are k_rle_walk_parts's
 }
 
 template <int N, bool ZB, int TL> static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *count, hipStream_t stream);
@@ -1164,7 +1145,7 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
     // classes 0-5: tableLog 13, 24-29: tableLog <= 12 -> the 16 KiB symbol table; 6-23: tableLog 14..16 -> the 128 KiB one
     if (cls_mask & (0x3F00003Fu | MIC_CLS_SPLIT)) hipLaunchKernelGGL(k_dec_translate<13>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);
     if (cls_mask & 0x00FFFFC0u) {
-        hipLaunchKernelGGL(k_dec_translate_wide, dim3((unsigned)n), dim3(TRW_THREADS), 0, stream, d_units);   // (marks its units walk_ok 3: the next launch skips them)
+        hipLaunchKernelGGL(k_dec_translate_wide, dim3((unsigned)n), dim3(TRW_THREADS), 0, stream, d_units);   // (marks its units MIC_STAGE_PARTS: the next launch skips them)
         hipLaunchKernelGGL(k_dec_translate<16>, dim3((unsigned)n), dim3(TR_THREADS), 0, stream, d_units);
     }
 }

@@ -18,6 +18,7 @@
 #include "mic_dev.h"
 #include "mic_launch.h"
 #include "mic_wave.h"
+#include "mic_rlewalk.h"
 
 #define PX_THREADS 1024
 #define PX_WAVES (PX_THREADS / 64)
@@ -34,7 +35,7 @@ struct __attribute__((packed, aligned(2))) PxVec { uint16_t v[PX_K]; };
 __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK || u.mode != 0) return;
-    if (u.walk_ok == 4) return;                                         // k_dec_rows_tok (mic_decode_fused.hip) has made this unit's pixels
+    if (u.dec_stage == MIC_STAGE_PIXELS) return;                        // k_dec_rows_tok (mic_decode_fused.hip) has made this unit's pixels
     __shared__ uint32_t s_fn[PX_WAVES + 1];
     __shared__ uint32_t s_misc[8];
     __shared__ uint32_t s_segx[PX_THREADS], s_segy[PX_THREADS + 1];
@@ -47,14 +48,14 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
     const int W = u.w, H = u.h;
     const uint32_t npx = (uint32_t)W * (uint32_t)H;
     if (ntok < 2) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
-    const int d0 = mic_len16(tok[0]);                                   // rledecompressu16.go:21-25
-    if (d0 == 0) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
-    const uint32_t mid = (1u << (d0 - 1)) - 1;
+    uint32_t mid;
+    if (!mic_rle_mid(tok[0], mid)) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     const uint32_t symcap = min(u.sym_cap, 2u * npx + 2u);
     uint2 *seg = u.seg;
 
     // ---- phase 1: header walk (wave 0) -----------------------------------------------------
-    if (u.walk_ok) {                                                    // k_dec_tans_lds walked the headers as it produced them
+    // (a unit with an OK status is at NONE or SEGS here: STATES never outlives the translate launch, PARTS is given to mode 1 units only)
+    if (u.dec_stage == MIC_STAGE_SEGS) {                                // the walker of k_dec_translate or k_dec_tans_gl has left the segments
         if (tid == 0) { s_misc[0] = u.nseg; s_misc[1] = u.nsym; s_misc[2] = 0; s_misc[3] = 0; }
     } else if (wave == 0) {
         uint32_t pos = 1, outp = 0, nseg = 0, err = 0;
@@ -68,17 +69,15 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                 // No encoder writes a count of 0, but the reference decodes one (DecodeNext2 keeps the count in a uint16: 0 passes as a run,
                 // is decremented to 65535 and counts down from there as a literal chunk): one symbol = the token behind the header, then the
                 // 65535 - midCount tokens behind that -- a literal chunk of 65536 - midCount symbols whose payload starts behind the header.
-                // (The walkers inside the entropy kernels stop at a zero and leave the stream to this one.)
+                // This is the ONE difference from MicRleWalk (mic_rlewalk.h), which stops at a zero and leaves the stream to this walk.
                 if (h == 0) h = 65536u;
-                if (h <= mid) {                                          // same-run: count, value
+                const MicRleHdr hd = mic_rle_hdr(h, mid);
+                if (hd.run) {                                            // same-run: count, value
                     if (pos + j + 1 >= ntok) { err = 1; break; }
                     if (j == 63) break;                                  // value not in the window: reload at the header
-                    if (lane == 0) seg[nseg] = make_uint2((pos + j + 1) | 0x80000000u, outp);
-                    nseg++; outp += h; j += 2;
-                } else {                                                 // literal run
-                    if (lane == 0) seg[nseg] = make_uint2(pos + j + 1, outp);
-                    nseg++; outp += h - mid; j += 1 + (h - mid);
                 }
+                if (lane == 0) seg[nseg] = make_uint2(hd.rec(pos + j), outp);
+                nseg++; outp += hd.len; j += hd.adv;
             }
             pos += j;
         }
@@ -106,7 +105,8 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
         uint32_t s_lo = 0;               // first segment that reaches into the tile
         uint32_t tab_r0 = 0; bool tab_ok = false;   // segment index of the LDS table's first entry
         // this thread's 8 symbols [i0, wend) out of the LDS segment table (entries from segment r0 on): gallop from
-        // table index j0, bisect, then one 16-byte load when the window lies inside one literal segment
+        // table index j0, bisect, then one 16-byte load when the window lies inside one literal segment.  bad: bit k = symbol i0 + k lies
+        // behind the last token (Go: index panic -- once a pixel WANTS it: the verdict waits until the tile's pixel count is known)
         typedef uint32_t px_v4 __attribute__((ext_vector_type(4)));
         typedef px_v4 PxQ __attribute__((aligned(2)));
         auto fetch8 = [&](uint32_t i0, uint32_t wend, uint32_t j0, uint32_t (&w8)[4], uint32_t &bad, uint32_t &jout) {
@@ -115,19 +115,15 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             for (stp >>= 1; stp; stp >>= 1) if (j + stp <= PX_THREADS && s_segy[j + stp] <= i0) j += stp;
             uint32_t start = s_segy[j], endj = min(s_segy[j + 1], nsym), sx = s_segx[j];
             w8[0] = w8[1] = w8[2] = w8[3] = 0;
-            if (wend - i0 == PX_SPT && i0 + PX_SPT <= endj) {
-                const uint32_t xs = sx & 0x7FFFFFFFu;
-                if (sx >> 31) {                                           // same-run: one value
-                    const uint32_t v = tok[xs];
-                    w8[0] = w8[1] = w8[2] = w8[3] = v | (v << 16);
-                } else {
-                    const uint32_t src = xs + (i0 - start);
-                    if (src + PX_SPT <= ntok) {
-                        const px_v4 v = *(const PxQ *)(tok + src);
-                        w8[0] = v.x; w8[1] = v.y; w8[2] = v.z; w8[3] = v.w;
-                    } else bad = 1;                                       // literal run past the end (Go: index panic)
-                }
-            } else {
+            const bool one = wend - i0 == PX_SPT && i0 + PX_SPT <= endj;   // the window lies inside one segment
+            const uint32_t xs0 = sx & 0x7FFFFFFFu, src0 = xs0 + (i0 - start);
+            if (one && (sx >> 31)) {                                      // same-run: one value
+                const uint32_t v = tok[xs0];
+                w8[0] = w8[1] = w8[2] = w8[3] = v | (v << 16);
+            } else if (one && src0 + PX_SPT <= ntok) {
+                const px_v4 v = *(const PxQ *)(tok + src0);
+                w8[0] = v.x; w8[1] = v.y; w8[2] = v.z; w8[3] = v.w;
+            } else {                                                      // (also: a literal chunk that ends behind the tokens)
 #pragma unroll
                 for (int k = 0; k < PX_SPT; k++) {
                     const uint32_t i = i0 + k;
@@ -135,7 +131,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                         while (i >= endj) { j++; start = s_segy[j]; endj = min(s_segy[j + 1], nsym); sx = s_segx[j]; }
                         const uint32_t xs = sx & 0x7FFFFFFFu;
                         const uint32_t src = (sx >> 31) ? xs : xs + (i - start);
-                        if (src < ntok) w8[k >> 1] |= (uint32_t)tok[src] << (16 * (k & 1)); else bad = 1;
+                        if (src < ntok) w8[k >> 1] |= (uint32_t)tok[src] << (16 * (k & 1)); else bad |= 1u << k;
                     }
                 }
             }
@@ -156,11 +152,12 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             uint32_t w8[4] = { 0u, 0u, 0u, 0u };
             bool got = i0 >= tile_end;
             uint32_t my_seg = s_lo;                                      // segment this thread found (absolute index; hint for the next tile)
+            uint32_t badm = 0;                                           // this thread's symbols behind the last token (fetch8)
             if (pre_cov) {
                 if (!got) {
 #pragma unroll
                     for (int k = 0; k < 4; k++) w8[k] = p8[k];
-                    if (pre_bad) s_misc[3] = 1;
+                    badm = pre_bad;
                     if (wend == tile_end) s_misc[5 + par] = tab_r0 + pre_j;
                     my_seg = tab_r0 + pre_j; got = true;
                 }
@@ -178,9 +175,8 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                     }
                     const uint32_t cover_end = s_segy[PX_THREADS];       // first symbol this table's segments do not cover
                     if (!got && s_segy[0] <= i0 && wend <= cover_end) {
-                        uint32_t bad = 0, j;
-                        fetch8(i0, wend, (s_lo > r0) ? s_lo - r0 : 0u, w8, bad, j);
-                        if (bad) s_misc[3] = 1;
+                        uint32_t j;
+                        fetch8(i0, wend, (s_lo > r0) ? s_lo - r0 : 0u, w8, badm, j);
                         if (wend == tile_end) s_misc[5 + par] = r0 + j;  // segment of the tile's last symbol: where the next tile starts
                         my_seg = r0 + j; got = true;
                     }
@@ -213,14 +209,15 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             }
             // Tiles without a delimiter (almost all: escapes are rare) need no scan: every symbol is a pixel and goes
             // straight from the registers to its place.  The barrier publishes the fetch phase's verdicts either way.
+            // (A symbol behind the tokens that a pixel wants raises s_misc[3], read behind the last tile's barrier; zeros stand in till then.)
             const bool plain = !__syncthreads_or((int)(dmask != 0)) && carry_state == 0;
             s_lo = s_misc[5 + par];
-            if (s_misc[3]) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
             if (plain) {
                 const uint32_t z = (base == 0) ? 1u : 0u;                // symbol 0 is not a pixel
                 const uint32_t cnt_all = tile_end - base - z;
                 const uint32_t n_out = min(cnt_all, npx - carry_px);
                 const uint32_t l0 = tid * PX_SPT - z;                    // tile-local pixel index of symbol i0 (tid 0, z = 1: of symbol 1)
+                if (badm & vmask) for (uint32_t k = 0; k < PX_SPT; k++) if ((((badm & vmask) >> k) & 1u) && l0 + k < n_out) s_misc[3] = 1;   // (rare)
                 if (vmask == 0xFFu && l0 + PX_SPT <= n_out) {
                     px_v4 v; v.x = w8[0]; v.y = w8[1]; v.z = w8[2]; v.w = w8[3];
                     *(PxQ *)(px + carry_px + l0) = v;
@@ -262,6 +259,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                 const uint32_t x = (w8[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
                 const uint32_t d = (dmask >> k) & 1u, v = (vmask >> k) & 1u;
                 const uint32_t m = d & (st_in ^ 1u);
+                if (((badm >> k) & v) && carry_px + pl < npx) s_misc[3] = 1;   // (a marker is wanted when the pixel behind it is)
                 if (v && !m) {
                     s_px[pl] = (uint16_t)x;
                     const uint32_t pg = carry_px + pl;
@@ -288,6 +286,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
     }
     __threadfence_block();
     __syncthreads();
+    if (s_misc[3]) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }           // a literal chunk past the end, under a pixel
 
     // ---- phase 4: inverse predictor, skewed wavefront ---------------------------------------------
     // Thread r owns row r of the band and works on the 8-pixel column group t - r at step t: its top

@@ -36,26 +36,20 @@ __global__ void __launch_bounds__(256, 3) k_dec_predict_rows(MicUnit *units, int
     const int ui = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);       // four units per group: a group's waves land on the four SIMDs
     if (ui >= n_units) return;
     MicUnit &u = units[ui];
-    if (u.status != MICD_OK || u.mode != 0 || u.pred || u.walk_ok == 4) return;   // (4: k_dec_rows_tok has made this unit's pixels)
+    if (u.status != MICD_OK || u.mode != 0 || u.pred || u.dec_stage == MIC_STAGE_PIXELS) return;   // (k_dec_rows_tok has made this unit's pixels)
     const int W = u.w, H = u.h;
     if (mic_rows_k(W) != K) return;
     const uint32_t lane = threadIdx.x & 63;
     uint32_t *const rb = s_rw + (threadIdx.x >> 6) * (32 * K + 4);      // this wave's row buffer: the row's bytes as they lie in memory
     const uint32_t npx = (uint32_t)W * (uint32_t)H;
     const uint32_t thr = u.dec_thr;
-    // (the unit's base as a wave-uniform value: every vector access is then scalar base + one 32-bit lane offset + an immediate, and
-    // no per-round address lives in -- or is spilled from -- vector registers: a spilled store address made every store wait for the
-    // one before it, 2.3 ms instead of 1.x)
-    const uintptr_t px_u = ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uintptr_t)u.px_out >> 32)) << 32) |
-                           (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)u.px_out);
-    const rw_gu16 px = (rw_gu16)px_u;
+    const rw_gu16 px = mic_wave_gp(u.px_out);                           // (wave-uniform: 2.3 ms instead of 1.x with a spilled store address)
     typedef __attribute__((address_space(1))) uint8_t *rw_gu8;
-    const uint32_t voff = lane * 16u;                                   // byte offset of this lane's vector inside a round
     const rw_gcu32 flags = (rw_gcu32)u.flags;
-    const uint32_t x0 = lane * K;
-    const int nv = min(max(W - (int)x0, 0), K);                        // pixels of a row in this lane's chunk
-    const int nl = (W + K - 1) / K;                                     // lanes with pixels
-    const uint64_t vmask = nv >= 64 ? ~0ull : ((1ull << nv) - 1ull);
+    const RowLanes<K> g(lane, W);
+    const uint32_t x0 = g.x0, voff = g.voff, nfull = g.nfull, ntail = g.ntail;
+    const int nv = g.nv;
+    const uint64_t vmask = g.vmask();
     const uint32_t thr2 = thr | (thr << 16);
 
     // tp: the row above = this lane's previous results, two pixels a dword.  e: the row's symbols minus thr, as packed 16-bit values.
@@ -65,12 +59,10 @@ __global__ void __launch_bounds__(256, 3) k_dec_predict_rows(MicUnit *units, int
 #pragma unroll
     for (int q = 0; q < KD; q++) tp[q] = 0;
     typedef RowPred<K> RP;
-    typedef uint16_t rw_pk __attribute__((ext_vector_type(2)));
     // row y's vectors on their way to registers: vector lane + 64 j of the row, all NVJ rounds whatever the row's length -- what
     // lies behind the row's end is the next row's (cache lines the next fetch wants anyway) and is not used; the address is
     // clamped to the unit's last eight pixels, which only moves vectors that hold none of this row's pixels -- or, in the unit's
     // LAST row, the vector that holds its last few: land() fetches those again.
-    const uint32_t nfull = (uint32_t)W / 8u, ntail = (uint32_t)W % 8u;  // whole vectors of a row, pixels behind them
     auto issue = [&](int y, rw_v4 (&nv4)[NVJ], uint64_t &raw) {
         const uint32_t ps = (uint32_t)y * (uint32_t)W;                  // the row's first pixel
         const rw_gu8 rowp = (rw_gu8)(px + ps);
@@ -83,10 +75,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_predict_rows(MicUnit *units, int
             for (int j = 0; j < NVJ; j++) nv4[j] = *(const __attribute__((address_space(1))) RwQ *)(rowp + min(1024u * j + voff, lim));
         }
         const uint32_t p = ps + x0;
-        const uint32_t pf = min(p, npx - 1), w = pf >> 5;                // (a lane without pixels reads the flags of the unit's last pixel)
-        const uint32_t f0 = flags[w], f1 = flags[w + 1], f2 = flags[w + 2];   // (the flag slab has spare words behind the last pixel)
-        const uint32_t l32 = __builtin_amdgcn_alignbit(f1, f0, pf), h32 = __builtin_amdgcn_alignbit(f2, f1, pf);
-        raw = (((uint64_t)h32 << 32) | l32) & vmask;
+        raw = mic_row_raw_bits(flags, min(p, npx - 1)) & vmask;         // (a lane without pixels reads the flags of the unit's last pixel)
     };
     // ... and from there through the row buffer into the lanes' chunks, as symbols minus thr
     auto land = [&](int y, const rw_v4 (&nv4)[NVJ], RowSymsReg<KD> &es) {
@@ -103,8 +92,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_predict_rows(MicUnit *units, int
         for (int q = 0; q < KD; q++) {
             // What lies behind the row's end in the last lanes' chunks is computed along (nothing reads the results) as the symbol
             // that changes nothing, so that it cannot look like a wrap-around.
-            const rw_pk a = __builtin_bit_cast(rw_pk, rb[lane * KD + q]), t2 = __builtin_bit_cast(rw_pk, thr2);
-            const uint32_t df = __builtin_bit_cast(uint32_t, (rw_pk)(a - t2));
+            const uint32_t df = mic_row_minus_thr(rb[lane * KD + q], thr2);
             e[q] = (2 * q + 2 <= nv) ? df : (2 * q + 1 == nv) ? (df & 0xFFFFu) : 0u;   // (the half of a dword behind the row's last pixel too)
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);                             // (the reads are done before the buffer is written again)
@@ -130,13 +118,8 @@ __global__ void __launch_bounds__(256, 3) k_dec_predict_rows(MicUnit *units, int
     land(0, nx, e);
     for (int y = 0; y < H; y++) {
         if (y + 1 < H && !((RW_ABL & 2) && y > 0)) issue(y + 1, nx, nraw);
-        if (y == 0) RP::slow_row(tp, e, raw, true, thr, lane, nl);
-        else if (!RP::fast_row(tp, e, raw, thr, lane, nv)) {            // the wrap-around fired somewhere: the row above again, then lane by lane
-            const uint32_t p = (uint32_t)(y - 1) * (uint32_t)W + x0;
-#pragma unroll
-            for (int q = 0; q < KD; q++) tp[q] = (uint32_t)px[min(p + 2 * q, npx - 1)] | ((uint32_t)px[min(p + 2 * q + 1, npx - 1)] << 16);
-            RP::slow_row(tp, e, raw, false, thr, lane, nl);
-        }
+        if (y == 0) RP::slow_row(tp, e, raw, true, thr, lane, g.nl);
+        else if (!RP::fast_row(tp, e, raw, thr, lane, nv)) RP::redo_row(tp, e, raw, thr, lane, g, px, y, W, npx);   // the wrap-around fired somewhere
         if (!(RW_ABL & 1)) put(y);
         land(y + 1, nx, e);
         raw = nraw;

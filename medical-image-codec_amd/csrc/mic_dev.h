@@ -86,6 +86,17 @@ struct MicSplitCfg {
 #define MIC_TBR_P_BIG_HBM       (1u << 14)   // parsed by k_dec_parse<true> starting over from HBM
 #define MIC_TBR_P_WINDOW        (1u << 15)   // the window loop of mic_read_ncount read at least one field (clear: the byte-wise loop read them all)
 
+// MicUnit.dec_stage: a decode unit's place in the chain behind the tANS kernels (DESIGN.md section 4 has the table).  Device code only;
+// every enqueue starts at NONE (lay_out: MicUnit{}).  The chain's other two hand-off signals: ntok != 0 ("decoded"), and wv_slow.
+enum MicStage : uint32_t {
+    MIC_STAGE_NONE   = 0,   // headers not walked.  Set: k_dec_translate (walk error, or no frame), k_rle_walk_fix (refused).  Read: k_dec_pixels_wg, k_wv_scatter
+    MIC_STAGE_SEGS   = 1,   // seg / nseg / nsym valid.  Set: MicRleWalk::finish (k_dec_tans_gl, k_dec_translate), k_rle_walk_fix.  Read: k_dec_rows_tok,
+                            // k_dec_pixels_wg (skips its own walk), k_rle_walk_compact, k_wv_scatter
+    MIC_STAGE_STATES = 2,   // tok (split units: and sym) holds tANS STATES.  Set: k_dec_tans_ls, k_dec_tans_ls_parts.  Read and replaced: k_dec_translate{,_wide}
+    MIC_STAGE_PARTS  = 3,   // translated, headers left to the walk in parts (mode 1, walk_mode 1).  Set: k_dec_translate{,_wide}.  Read: k_rle_walk_parts, _fix (replaces it)
+    MIC_STAGE_PIXELS = 4,   // px_out done.  Set: k_dec_rows_tok.  Read: k_dec_pixels_wg, k_dec_predict_rows (both skip the unit)
+};
+
 struct MicUnit {
     // ---- inputs ------------------------------------------------------------------
     const uint16_t *px_in;    // encode: source pixels (w*h u16)
@@ -120,11 +131,11 @@ struct MicUnit {
     uint32_t *flags;          // decode: 1 bit per pixel, set = pixel stored raw behind an escape
     uint32_t  nseg;
     uint32_t  nsym;
-    uint32_t  walk_ok;        // decode: seg/nseg/nsym already produced by the tANS kernel's header walker
+    uint32_t  dec_stage;      // decode: how far the chain behind the tables has brought the unit (MIC_STAGE_* above)
     uint32_t  dec_thr;        // decode: delta threshold (1 << (depth-1)) - 1 of the stream's own max value
-    uint32_t  walk_mode;      // decode, mode 1 units: 1 = the symbols are a length-prefixed RLE stream (WaveletV2): k_dec_translate marks it
-                              // walk_ok = 3 and k_rle_walk_* (mic_wavelet.hip) walk its headers in parts: seg / nseg / nsym, walk_ok = 1,
-                              // and in `flags` the segment that holds every 8192nd symbol
+    uint32_t  walk_mode;      // decode, mode 1 units: 1 = the symbols are a length-prefixed RLE stream (WaveletV2): the translate kernels mark it
+                              // MIC_STAGE_PARTS and k_rle_walk_* (mic_wavelet.hip) walk its headers in parts: seg / nseg / nsym,
+                              // MIC_STAGE_SEGS, and in `flags` the segment that holds every 8192nd symbol
     uint32_t  wv_slow;        // WaveletV2: this frame takes the one-group kernels (escape words in its stream, or a stream the walker refused)
     uint32_t  wv_zmax;        // WaveletV2 encode: largest zigzag symbol of the frame
     uint32_t  hist_hi;        // encode: every token the tokeniser counted is below this (0: unknown -- all 65536 bins are scanned)

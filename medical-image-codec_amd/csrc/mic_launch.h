@@ -98,7 +98,7 @@ void mic_launch_pica_pick(MicUnit *d_units, int npairs, hipStream_t stream, MicT
 #define MIC_PRED_WIDE   0x400u          // k_dec_predict<1, 64>: wider
 void mic_launch_decode_pixels(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t, bool any_grad = false, uint32_t pred_mask = ~0u);
 void mic_launch_decode_rows(MicUnit *d_units, int n, hipStream_t stream, uint32_t kmask);
-// tokens -> pixels in one kernel for the same widths (mic_decode_fused.hip); units it takes are marked walk_ok = 4 and skipped by the kernels behind it
+// tokens -> pixels in one kernel for the same widths (mic_decode_fused.hip); units it takes are marked MIC_STAGE_PIXELS and skipped by the kernels behind it
 void mic_launch_decode_fused(MicUnit *d_units, int n, hipStream_t stream, uint32_t kmask);
 // Frames of MIC_ROWS_LO < columns <= MIC_ROWS_HI take the row-by-row predictor: pixels per lane and row (0: another kernel's frame)
 #define MIC_ROWS_LO 1008

@@ -24,12 +24,42 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "mic_dev.h"
 #include "mic_wave.h"
 
 #define RW_NEVER 65536u
 #ifndef RW_ABL
 #define RW_ABL 0      // timing-only ablations (the output is wrong): 1 = no stores, 2 = one row's loads only, 4 = no pass 1 / scan, 8 = no pass 2
 #endif
+
+// A pointer out of a MicUnit as a wave-uniform value: every vector access through it is then scalar base + 32-bit lane offset + immediate,
+// and no address lives in -- or is spilled from -- vector registers (a spilled store address made every store wait for the one before it)
+template <class T> __device__ __forceinline__ mic_gp<T> mic_wave_gp(T *p) {
+    const uintptr_t a = (uintptr_t)p;
+    return (mic_gp<T>)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                       (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)a));
+}
+// where lane `lane` stands in a row of W pixels: its chunk of K columns, and its share of the row's 16-byte vectors
+template <int K> struct RowLanes {
+    uint32_t x0, voff, nfull, ntail; int nv, nl;
+    __device__ __forceinline__ RowLanes(uint32_t lane, int W)
+        : x0(lane * K), voff(lane * 16u),                               // first column of the chunk; byte offset of the lane's vector inside a round of 64
+          nfull((uint32_t)W / 8u), ntail((uint32_t)W % 8u),             // whole vectors of a row, pixels behind them
+          nv(min(max(W - (int)(lane * K), 0), K)), nl((W + K - 1) / K) { }   // pixels of a row in this lane's chunk; lanes with pixels
+    __device__ __forceinline__ uint64_t vmask() const { return nv >= 64 ? ~0ull : ((1ull << nv) - 1ull); }   // the chunk's pixels as raw bits
+};
+// 64 bits of a bit array from bit pf on (the array has two spare words behind the last bit asked for)
+template <class P> __device__ __forceinline__ uint64_t mic_row_raw_bits(P words, uint32_t pf) {
+    const uint32_t w = pf >> 5;
+    const uint32_t f0 = words[w], f1 = words[w + 1], f2 = words[w + 2];
+    const uint32_t l32 = __builtin_amdgcn_alignbit(f1, f0, pf), h32 = __builtin_amdgcn_alignbit(f2, f1, pf);
+    return ((uint64_t)h32 << 32) | l32;
+}
+// two symbols of a dword minus thr (thr2 = thr | thr << 16), each in 16 bits
+__device__ __forceinline__ uint32_t mic_row_minus_thr(uint32_t syms, uint32_t thr2) {
+    typedef uint16_t pk __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, (pk)(__builtin_bit_cast(pk, syms) - __builtin_bit_cast(pk, thr2)));
+}
 
 // the row's symbols minus thr in registers (k_dec_predict_rows) ...
 template <int KD_> struct RowSymsReg {
@@ -77,6 +107,17 @@ template <int K> struct RowPred {
             }
             carry = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
         }
+    }
+    // Row y (> 0) again after fast_row said no: the row above back into tp from the unit's pixels -- put(y - 1) has stored them, from
+    // OTHER lanes of this wave, so the stores must have been acknowledged before any lane reads them back -- then lane by lane.  Cold.
+    template <class E, class P>
+    static __device__ __forceinline__ void redo_row(uint32_t (&tp)[KD], const E &e, uint64_t raw, uint32_t thr, uint32_t lane, const RowLanes<K> &g,
+                                                    P px, int y, int W, uint32_t npx) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t p = (uint32_t)(y - 1) * (uint32_t)W + g.x0;
+#pragma unroll
+        for (int q = 0; q < KD; q++) tp[q] = (uint32_t)px[min(p + 2 * q, npx - 1)] | ((uint32_t)px[min(p + 2 * q + 1, npx - 1)] << 16);
+        slow_row(tp, e, raw, false, thr, lane, g.nl);
     }
     // A row below the first: tp (the row above) becomes this row.  false: the wrap-around fired somewhere -- tp is spoilt, the caller
     // puts the row above back into it and calls slow_row.  nv = this lane's pixels in the row (0: its results are nobody's business).

@@ -17,6 +17,7 @@
 #include "mic_session.h"
 #include "mic_staged.h"
 #include "mic_wave.h"
+#include "mic_rlewalk.h"
 
 namespace {
 
@@ -375,9 +376,8 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
     const uint32_t ntok = u.ntok; const uint16_t *tok = u.tok;
     if (ntok < 3) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     const bool pre = mic_is_prefix(u);                                   // the tokens end at the chain's ceiling, not at the stream's end
-    const int d0 = mic_len16(tok[0]);
-    if (d0 == 0) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
-    const uint32_t mid = (1u << (d0 - 1)) - 1;
+    uint32_t mid;
+    if (!mic_rle_mid(tok[0], mid)) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     uint32_t outlen = ((uint32_t)tok[1] << 16) + tok[2];
     if (outlen > u.sym_cap) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }
     uint2 *seg = u.seg; uint16_t *sym = u.sym;
@@ -391,15 +391,13 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
                 uint32_t h = __builtin_amdgcn_readlane(w, (int)j);
                 if (nseg >= segcap) { err = 1; break; }
                 if (h == 0) h = 65536u;                                  // the reference's reading of a zero count: a literal chunk of 65536 - midCount (mic_decode_px.hip)
-                if (h <= mid) {
+                const MicRleHdr hd = mic_rle_hdr(h, mid);
+                if (hd.run) {
                     if (pos + j + 1 >= ntok) { if (pre) fin = 1; else err = 1; break; }   // (a prefix: the run's value lies behind it)
                     if (j == 63) break;
-                    if (lane == 0) seg[nseg] = make_uint2(pos + j, outp);
-                    nseg++; outp += h; j += 2;
-                } else {
-                    if (lane == 0) seg[nseg] = make_uint2(pos + j, outp);
-                    nseg++; outp += h - mid; j += 1 + (h - mid);
                 }
+                if (lane == 0) seg[nseg] = make_uint2(pos + j, outp);     // (this kernel's own records: the HEADER's token)
+                nseg++; outp += hd.len; j += hd.adv;
             }
             pos += j;
         }
@@ -417,11 +415,12 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_expand(MicUnit *units, int mo
         const uint2 r = seg[si];
         uint32_t h = tok[r.x];
         if (h == 0) h = 65536u;                                          // (a zero count: see the walker above)
-        if (h <= mid) {
+        const MicRleHdr hd = mic_rle_hdr(h, mid);
+        if (hd.run) {
             const uint16_t v = tok[r.x + 1];
-            for (uint32_t k = lane; k < h && r.y + k < outlen; k += 64) sym[r.y + k] = v;
+            for (uint32_t k = lane; k < hd.len && r.y + k < outlen; k += 64) sym[r.y + k] = v;
         } else {
-            const uint32_t cnt = h - mid;
+            const uint32_t cnt = hd.len;
             for (uint32_t k = lane; k < cnt && r.y + k < outlen; k += 64) { if (r.x + 1 + k < ntok) sym[r.y + k] = tok[r.x + 1 + k]; else bad = 1; }
         }
     }
@@ -596,16 +595,15 @@ __device__ __forceinline__ bool wp_fits(const MicUnit &u, uint32_t L) {        /
 }
 __global__ void __launch_bounds__(64) k_rle_walk_parts(MicUnit *units) {
     MicUnit &u = units[blockIdx.y];
-    if (u.status != MICD_OK || u.walk_mode != 1 || u.walk_ok != 3) return;
+    if (u.status != MICD_OK || u.walk_mode != 1 || u.dec_stage != MIC_STAGE_PARTS) return;
     const uint32_t ntok = u.ntok, p = blockIdx.x, lane = threadIdx.x;
     if (ntok < 3) return;
     const uint16_t *tok = u.tok;
     const uint32_t L = wp_part_len(ntok), lo = p * L;
     if (lo >= ntok || !wp_fits(u, L)) return;
     const uint32_t hi = min(lo + L, ntok);
-    const int d0 = mic_len16(tok[0]);
-    if (d0 == 0) return;
-    const uint32_t mid = (1u << (d0 - 1)) - 1;
+    uint32_t mid;
+    if (!mic_rle_mid(tok[0], mid)) return;
     uint2 *rec = u.seg + u.seg_cap / 2 + (size_t)p * wp_stride(L);
     const bool pre = mic_is_prefix(u);                                      // the tokens end at the chain's ceiling
     uint32_t pos = p ? lo : 3u, out = 0, nrec = 0, err = 0, fin = 0;
@@ -622,18 +620,14 @@ __global__ void __launch_bounds__(64) k_rle_walk_parts(MicUnit *units) {
                 nrec = 0; out = 0; j += 1;
                 continue;
             }
-            if (h <= mid) {
-                if (pos + j + 1 >= ntok) {
-                    if (pre) { fin = 1; break; }                            // a prefix ends in front of a run whose value it lacks: exit = that header
-                    if (p == 0) err = 1; else { nrec = 0; out = 0; j = 64; pos = hi; }
-                    break;
-                }
-                if (lane == 0) rec[nrec] = make_uint2((pos + j + 1) | 0x80000000u, out);
-                nrec++; out += h; j += 2;
-            } else {
-                if (lane == 0) rec[nrec] = make_uint2(pos + j + 1, out);
-                nrec++; out += h - mid; j += 1 + (h - mid);
+            const MicRleHdr hd = mic_rle_hdr(h, mid);
+            if (hd.run && pos + j + 1 >= ntok) {
+                if (pre) { fin = 1; break; }                                // a prefix ends in front of a run whose value it lacks: exit = that header
+                if (p == 0) err = 1; else { nrec = 0; out = 0; j = 64; pos = hi; }
+                break;
             }
+            if (lane == 0) rec[nrec] = make_uint2(hd.rec(pos + j), out);
+            nrec++; out += hd.len; j += hd.adv;
         }
         pos += j;
     }
@@ -647,14 +641,14 @@ __global__ void __launch_bounds__(64) k_rle_walk_parts(MicUnit *units) {
 // window, noted as "extras" with their absolute symbol positions -- until it stands on a position the part has a record of.
 __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
     MicUnit &u = units[blockIdx.x];
-    if (u.status != MICD_OK || u.walk_mode != 1 || u.walk_ok != 3) return;
+    if (u.status != MICD_OK || u.walk_mode != 1 || u.dec_stage != MIC_STAGE_PARTS) return;
     const uint32_t ntok = u.ntok, lane = threadIdx.x;
     const uint32_t L = wp_part_len(max(ntok, 1u));
     const uint16_t *tok = u.tok;
-    bool ok = ntok >= 3 && wp_fits(u, L) && mic_len16(tok[0]) != 0, fin = false;
+    uint32_t mid = 0;
+    bool ok = ntok >= 3 && wp_fits(u, L) && mic_rle_mid(tok[0], mid), fin = false;
     const bool pre = mic_is_prefix(u);                                      // a prefix: the walk ends cleanly where its tokens do
     const uint32_t cap = ok ? ((uint32_t)tok[1] << 16) + tok[2] : 0u;
-    const uint32_t mid = ok ? (1u << (mic_len16(tok[0]) - 1)) - 1 : 0u;
     if (cap > u.sym_cap) ok = false;
     WpPart *S = (WpPart *)u.cumul;
     uint32_t e = 3, N = 0, O = 0;                                           // the next true header, records and symbols in front of it
@@ -690,11 +684,10 @@ __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
             if (e - wbase >= 64u) { wbase = e; wtok = (e + lane < ntok) ? tok[e + lane] : 0u; }
             const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)wtok, (int)(e - wbase));
             if (h == 0 || nx >= WP_EXTRA) { ok = false; break; }                // (a zero count: corrupt; too many: the one-group kernels take the frame)
-            const bool run = h <= mid;
-            if (run && e + 1 >= ntok) { if (pre) fin = true; else ok = false; break; }
-            const uint32_t len = run ? h : h - mid;
-            if (lane == 0) extra[nx] = make_uint2((e + 1) | (run ? 0x80000000u : 0u), O);
-            nx++; O += len; e += run ? 2u : 1u + len;
+            const MicRleHdr hd = mic_rle_hdr(h, mid);
+            if (hd.run && e + 1 >= ntok) { if (pre) fin = true; else ok = false; break; }
+            if (lane == 0) extra[nx] = make_uint2(hd.rec(e), O);
+            nx++; O += hd.len; e += hd.adv;
         }
         if (!ok) break;
         if (lane == 0) {
@@ -714,13 +707,13 @@ __global__ void __launch_bounds__(64) k_rle_walk_fix(MicUnit *units) {
     // past ntok when that was a literal chunk the prefix holds only the front of)
     const uint32_t cover = pre ? min(cap, O - (e > ntok ? e - ntok : 0u)) : cap;
     if (lane == 0) {
-        if (ok) { u.nseg = N; u.nsym = cover; u.walk_ok = 1; }
-        else u.walk_ok = 0;
+        if (ok) { u.nseg = N; u.nsym = cover; u.dec_stage = MIC_STAGE_SEGS; }
+        else u.dec_stage = MIC_STAGE_NONE;
     }
 }
 __global__ void __launch_bounds__(256) k_rle_walk_compact(MicUnit *units) {
     MicUnit &u = units[blockIdx.y];
-    if (u.status != MICD_OK || u.walk_mode != 1 || u.walk_ok != 1) return;
+    if (u.status != MICD_OK || u.walk_mode != 1 || u.dec_stage != MIC_STAGE_SEGS) return;
     const uint32_t L = wp_part_len(u.ntok), q = blockIdx.x;
     if (q * L >= u.ntok) return;
     const WpPart s = ((const WpPart *)u.cumul)[q];
@@ -760,7 +753,7 @@ __global__ void __launch_bounds__(1024) k_wv_scatter(MicUnit *units, const WvFra
     if (u.status != MICD_OK) return;
     const WvDims &d = ft[wr.frame].d;
     const uint32_t lim = ft[wr.frame].lim, tid = threadIdx.x;
-    if (u.walk_ok != 1 || u.nsym < lim) { if (tid == 0) u.wv_slow = 1; return; }
+    if (u.dec_stage != MIC_STAGE_SEGS || u.nsym < lim) { if (tid == 0) u.wv_slow = 1; return; }
     __shared__ uint32_t s_segx[1024], s_segy[1024 + 1];
     a += ft[wr.frame].a_off;
     const uint32_t nseg = u.nseg, ntok = u.ntok;
