@@ -490,6 +490,53 @@ int mic_hip_strips_read_crops(const uint8_t *const *files, const size_t *lens, i
                               void *d_out, size_t out_cap,
                               int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats);
 
+/* ---- single-frame RGB files: many crops of many files per call, written to a device tensor ------ */
+/* The same for CompressRGB blobs and MICR files (below; no reference counterpart): a sampler that feeds a model cw x ch crops of
+ * ultrasound frames or visible-light images otherwise decodes whole images (mic_hip_rgb_decompress_batch), crops on the host and
+ * uploads crop by crop.  files[f] is a blob with its width and height, or a MICR file (width = height = 0: the header's; else they
+ * must equal it); one call may mix the two kinds and any sizes.  Crop i is the rectangle [x, x + cw) x [y, y + ch) of file
+ * xyf[3i + 2], (x, y) = xyf[3i .. 3i + 1]; origins may be negative and a crop may overhang its image or lie wholly outside it:
+ * samples outside the image are 0.  d_out receives n x ch x cw x 3 interleaved u8 -- crop-major, then row, column, channel --,
+ * n * ch * cw * 3 bytes at any address, every one of them written.  d_out is memory the device can write: a device allocation on the
+ * call's device that is long enough for the tensor, or pinned host memory (mic_hip_host_alloc); anything else is MIC_ERR_ARGS, found
+ * with hipPointerGetAttributes before anything is launched.
+ * An image is one unit of the plan, so only the files some crop overlaps with non-empty area are looked at, uploaded and decoded,
+ * each once and whole, in sub-batches under the workspace ceiling; a file no crop names that way is not looked at beyond a MICR
+ * file's 12-byte header.  A sub-batch's slab holds the CODED planes alone (plane mode 2: an entropy-coded stream), and the cut counts
+ * only their samples: a grey ultrasound frame codes Y and has constant Co and Cg, so three times as many of them share one decode
+ * chain as full-colour images do.  Behind each sub-batch one kernel writes every (crop, image) overlap -- a "piece", at most one per
+ * crop -- into d_out, taking each plane from where it is: the decoded plane in the slab, the constant of a mode 0 / 1 plane from
+ * the piece's record, the raw samples of a mode 3 plane in place from the uploaded blob.  No constant or raw plane is materialised.
+ * A file fails alone, with the code and failed_plane mic_hip_rgb_decompress_batch gives the same file: a NULL pointer, a width or
+ * height < 0, 0 for a blob, or that disagrees with a MICR header, a container that is neither 0 nor 1 (MIC_ERR_ARGS), more than 2^26
+ * pixels (MIC_ERR_UNSUPPORTED), a MICR header mic_hip_micr_info refuses, a blob whose lengths or plane modes decompressRGBTileBlob
+ * refuses (MIC_ERR_CORRUPT).  Every crop of such a file gets that code, and its pixels are zero; no other file is affected.
+ * status[i] (host, may be NULL) is otherwise MIC_OK, or the unit codec's code of the first failing plane of crop i's file, in plane
+ * order; failed_plane[i] (host, may be NULL) that plane (0 Y, 1 Co, 2 Cg), else -1.  Such a crop's samples are unspecified, every
+ * other crop is exact.
+ * Returns MIC_OK when the call ran, even if crops failed; n == 0 is MIC_OK; before anything is launched MIC_ERR_ARGS for cw, ch <= 0,
+ * n < 0, nfiles < 0, a NULL array or a file index outside [0, nfiles), and MIC_ERR_CAPACITY for out_cap below the tensor's size.
+ * One device: the calling thread's default session, or the given session (mic_hip_session_rgb_read_crops, with the session calls
+ * below); no fan-out over mic_hip_set_devices.  There is no callback-reader form: a blob is one unit, its reader would be the file form.
+ * stats (may be NULL): planes_decoded = the mode 2 planes that were entropy-decoded, planes_total = 3 x the accepted files some crop
+ * names (what whole-image decodes of them would lay out), pieces = the crops with non-empty overlap, slabs = decode chains the call ran. */
+typedef struct mic_hip_rgb_file {
+    const uint8_t *data; size_t len;   /* a CompressRGB blob or a MICR file (host memory) */
+    int32_t width, height;             /* blob: the image's.  MICR: 0 = take the header's, else must equal it */
+    int32_t container;                 /* 0: CompressRGB blob, 1: MICR file */
+} mic_hip_rgb_file;
+typedef struct { uint64_t planes_decoded, planes_total, pieces, slabs; } mic_hip_rgb_crop_stats;
+/* The host planner of those calls: file_of[cap] receives the files whose planes must be decoded -- the accepted files some crop
+ * overlaps with non-empty area --, ascending and each once.  *nfiles_out their number, *nplanes_coded their mode 2 planes,
+ * *npieces the crops with non-empty overlap of them (each may be NULL).  file_status[nfiles] (may be NULL): the code of each file as
+ * above; MIC_OK for a file no crop names.  More than cap files: MIC_ERR_CAPACITY with the counts and file_status set and the array
+ * untouched.  Of a named file only the three lengths and the first bytes of each plane are read.  Needs no device. */
+int mic_hip_rgb_crop_plan(const mic_hip_rgb_file *files, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                          uint32_t *file_of, size_t cap, uint64_t *nfiles_out, uint64_t *nplanes_coded, uint64_t *npieces,
+                          int32_t *file_status);
+int mic_hip_rgb_read_crops(const mic_hip_rgb_file *files, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                           void *d_out, size_t out_cap, int32_t *status, int32_t *failed_plane, mic_hip_rgb_crop_stats *stats);
+
 /* ---- WaveletV2 -------------------------------------------------------------------------------- */
 /* Replaces WaveletV2RLEFSECompressU16 and WaveletV2SIMDRLEFSECompressU16 (waveletfsecompressu16.go:303,
  * :374; identical streams): up to 8 levels of 5/3 integer lifting in Mallat layout, subband scan, zigzag
@@ -972,15 +1019,27 @@ int mic_hip_session_strips_read_crops(mic_hip_session *s,
                                       void *d_out, size_t out_cap,
                                       int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats);
 
+/* mic_hip_rgb_read_crops on CompressRGB blobs that lie in device memory, laid out as mic_hip_session_rgb_encode leaves them and as
+ * mic_hip_session_rgb_decode reads them: file f is the blob at d_blobs + h_offsets[f] .. h_offsets[f + 1] (h_offsets: nfiles + 1
+ * entries on the host) of an image of imgs[f].width x imgs[f].height; imgs[f].rgb_off is ignored.  A width or height <= 0
+ * (MIC_ERR_ARGS), more than 2^26 pixels (MIC_ERR_UNSUPPORTED) or h_offsets[f + 1] < h_offsets[f] (MIC_ERR_ARGS) fails the file alone,
+ * as a blob the host form refuses does.  The heads of the named blobs -- three lengths and three bytes a plane -- are read by a
+ * kernel and come down in one copy; the blobs of a sub-batch go device to device into the session's compressed-input buffer (which
+ * keeps the 64 bytes of slack the decode kernels may read past a stream's end; the caller's allocation owes them nothing) --
+ * nothing but heads, the piece list and statuses crosses PCIe.  d_out on the session's device, or pinned host memory. */
+int mic_hip_session_rgb_read_crops(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets,
+                                   const mic_hip_rgb_image *imgs, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                                   void *d_out, size_t out_cap, int32_t *status, int32_t *failed_plane, mic_hip_rgb_crop_stats *stats);
+
 /* ---- typed, scaled and channel-first output of the patch and crop readers ------------------------ */
-/* The thirteen readers of many rectangles per call write the file's own sample format (u16, u8, interleaved u8 RGB).  Their _as
+/* The fifteen readers of many rectangles per call write the file's own sample format (u16, u8, interleaved u8 RGB).  Their _as
  * twins below take the same arguments and a trailing output description, and write the tensor a model consumes from the same
  * one gather: no cast, multiply-add or permute kernel behind it (no reference counterpart).
  * The value of an output sample, which a host reference reproduces bit for bit: x = the decoded sample as float (exact: at
  * most 65535); v = fmaf(x, a, b), ONE rounding, (a, b) the pair of the sample's source and channel; with CLAMP
  * v = fminf(fmaxf(v, clamp_lo), clamp_hi); then F32 stores v, F16 and BF16 convert that f32 value round-to-nearest-even (overflow
  * to +-inf), U8 and U16 store rintf(v) (ties to even) saturated to the type's range.
- * A source is what the multi doors index: a slide, a volume, a strip file; 0 in the one-source doors.  naffine picks the pair:
+ * A source is what the multi doors index: a slide, a volume, a strip file, an RGB file; 0 in the one-source doors.  naffine picks the pair:
  * 0 = (1, 0) for all (affine may be NULL), 1 = one pair, C = one per channel, nsources * C = one per (source, channel), source-major.
  * pad is the value, converted to the output type as v is but with no affine and no clamp, of every sample the native door leaves 0
  * by definition: outside the level, image or volume, rows no strip covers, rectangles of a refused or missing source, patches with a
@@ -1059,6 +1118,14 @@ int mic_hip_session_strips_read_crops_as(mic_hip_session *s,
                                          void *d_out, size_t out_cap,
                                          int32_t *status, int32_t *failed_strip, mic_hip_strip_crop_stats *stats,
                                          const mic_hip_out_spec *spec);
+/* RGB files: channels = 3, 8 bits, nsources = nfiles; CHANNELS_FIRST gives n x 3 x ch x cw */
+int mic_hip_rgb_read_crops_as(const mic_hip_rgb_file *files, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                              void *d_out, size_t out_cap, int32_t *status, int32_t *failed_plane, mic_hip_rgb_crop_stats *stats,
+                              const mic_hip_out_spec *spec);
+int mic_hip_session_rgb_read_crops_as(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets,
+                                      const mic_hip_rgb_image *imgs, int nfiles, const int32_t *xyf, int n, int cw, int ch,
+                                      void *d_out, size_t out_cap, int32_t *status, int32_t *failed_plane, mic_hip_rgb_crop_stats *stats,
+                                      const mic_hip_out_spec *spec);
 
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);

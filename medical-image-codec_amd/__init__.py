@@ -196,6 +196,16 @@ class StripCropStats(C.Structure):
     _fields_ = [("strips_decoded", C.c_uint64), ("strips_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class RgbFile(C.Structure):
+    """mic_hip_rgb_file"""
+    _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("width", C.c_int32), ("height", C.c_int32), ("container", C.c_int32)]
+
+
+class RgbCropStats(C.Structure):
+    """mic_hip_rgb_crop_stats"""
+    _fields_ = [("planes_decoded", C.c_uint64), ("planes_total", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
+
+
 class Unit(C.Structure):
     _fields_ = [("px_offset", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32),
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
@@ -218,6 +228,7 @@ ABI_SYMBOLS = [
     "mic_hip_mic2_compress_batch", "mic_hip_mic2_decompress_batch", "mic_hip_mic2_batch_plan",
     "mic_hip_session_mic2_encode", "mic_hip_session_mic2_decode",
     "mic_hip_strips_crop_plan", "mic_hip_strips_read_crops", "mic_hip_session_strips_read_crops",
+    "mic_hip_rgb_crop_plan", "mic_hip_rgb_read_crops", "mic_hip_session_rgb_read_crops",
     "mic_hip_wavelet_v2_compress", "mic_hip_wavelet_v2_compress_batch", "mic_hip_wavelet_v2_decompress_batch", "mic_hip_wavelet_v2_info", "mic_hip_wavelet_v2_decompress",
     "mic_hip_wavelet_v2_level_info", "mic_hip_wavelet_v2_decompress_level", "mic_hip_wavelet_v2_decompress_level_batch",
     "mic_hip_wavelet_v2_compress_jobs", "mic_hip_wavelet_v2_decompress_jobs", "mic_hip_wavelet_v2_batch_plan",
@@ -258,6 +269,8 @@ ABI_SYMBOLS = [
     "mic_hip_session_mic2_multi_read_crops_as",
     "mic_hip_strips_read_crops_as",
     "mic_hip_session_strips_read_crops_as",
+    "mic_hip_rgb_read_crops_as",
+    "mic_hip_session_rgb_read_crops_as",
 ]
 
 # the readers of many rectangles per call; each has an _as twin that takes a trailing mic_hip_out_spec (OutSpec)
@@ -437,6 +450,11 @@ def lib() -> C.CDLL:
                                            C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     L.mic_hip_strips_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + _strip_crop_args
     L.mic_hip_session_strips_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + _strip_crop_args
+    _rgb_crop_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(RgbCropStats)]
+    L.mic_hip_rgb_crop_plan.argtypes = [C.POINTER(RgbFile), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.mic_hip_rgb_read_crops.argtypes = [C.POINTER(RgbFile), C.c_int] + _rgb_crop_args
+    L.mic_hip_session_rgb_read_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RgbImage), C.c_int] + _rgb_crop_args
     L.mic_hip_wavelet_v2_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mic_hip_wavelet_v2_compress_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint16, C.c_int, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
@@ -1176,6 +1194,70 @@ def strips_read_crops(files, xyf, cw: int, ch: int, d_out: int, out_cap: int, sp
         ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, cw, ch, d, cap, s, b, p), xyf, d_out, out_cap)
     if rc:
         _raise(rc, "strips_read_crops")
+    return st, bad, stats
+
+
+# ------------------------------------------------------------------ single-frame RGB files: many crops per call
+def rgb_files(files):
+    """The mic_hip_rgb_file table of a list of RGB files, and the arrays that keep their bytes alive.  An entry is a MICR file
+    (bytes-like: its header names the size), a CompressRGB blob as (blob, width, height), or (data, width, height, container)
+    as the C struct has it; data None is a NULL pointer."""
+    tab, keep = (RgbFile * max(len(files), 1))(), []
+    for i, f in enumerate(files):
+        data, w, h, c = (f, 0, 0, 1) if not isinstance(f, tuple) else (f[0], f[1], f[2], f[3] if len(f) > 3 else 0)
+        a = None if data is None else _bytes_arr(data)
+        keep.append(a)
+        tab[i].data = None if a is None else a.ctypes.data
+        tab[i].len = 0 if a is None else a.size
+        tab[i].width, tab[i].height, tab[i].container = int(w), int(h), int(c)
+    return tab, keep
+
+
+def rgb_crop_plan(files, xyf, cw: int, ch: int, cap: Optional[int] = None):
+    """mic_hip_rgb_crop_plan: (uint32 array of the files whose planes the crops need decoded -- ascending, each once --, their
+    mode-2 planes, the crops with non-empty overlap, int32 status of each file).  files: as rgb_files takes them.  Needs no
+    device.  cap: room for that many files (default: as many as it takes); too few raises MicError (MIC_ERR_CAPACITY) whose
+    ``nfiles``, ``planes_coded``, ``pieces`` and ``file_status`` attributes are the counts and the files' codes."""
+    tab, keep = rgb_files(files)
+    a = _crop_xyf(xyf)
+    nf, npl, npc = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    fs = np.zeros(max(len(files), 1), dtype=np.int32)
+    if cap is None:
+        rc = lib().mic_hip_rgb_crop_plan(tab, len(files), a.ctypes.data, len(a), cw, ch, None, 0,
+                                         C.byref(nf), C.byref(npl), C.byref(npc), fs.ctypes.data)
+        if rc not in (MIC_OK, MIC_ERR_CAPACITY):
+            _raise(rc, "rgb_crop_plan")
+        cap = nf.value
+    file_of = np.zeros(max(cap, 1), dtype=np.uint32)
+    rc = lib().mic_hip_rgb_crop_plan(tab, len(files), a.ctypes.data, len(a), cw, ch, file_of.ctypes.data, cap,
+                                     C.byref(nf), C.byref(npl), C.byref(npc), fs.ctypes.data)
+    if rc:
+        e = MicError(rc, "rgb_crop_plan")
+        e.nfiles, e.planes_coded, e.pieces, e.file_status = nf.value, npl.value, npc.value, fs[: len(files)].copy()
+        raise e
+    return file_of[: nf.value].copy(), npl.value, npc.value, fs[: len(files)].copy()
+
+
+def _read_rgb_crops(call, xyf, d_out: int, out_cap: int):
+    a = _crop_xyf(xyf)
+    st = np.zeros(len(a), dtype=np.int32)
+    bad = np.full(len(a), -1, dtype=np.int32)
+    cs = RgbCropStats()
+    rc = call(a.ctypes.data, len(a), int(d_out) or None, int(out_cap), st.ctypes.data, bad.ctypes.data, C.byref(cs))
+    return rc, st, bad, dict(planes_decoded=cs.planes_decoded, planes_total=cs.planes_total, pieces=cs.pieces, slabs=cs.slabs)
+
+
+def rgb_read_crops(files, xyf, cw: int, ch: int, d_out: int, out_cap: int, spec=None):
+    """mic_hip_rgb_read_crops: the cw x ch crops at the (x, y, file) triples `xyf` of the CompressRGB blobs / MICR files `files`
+    (as rgb_files takes them; file = an index into the list), into the caller's device tensor d_out (an int:
+    ``torch.empty((n, ch, cw, 3), dtype=torch.uint8, device="cuda").data_ptr()``, or pinned host memory) of out_cap bytes.
+    Samples outside an image are 0.  Only the files some crop overlaps are uploaded and decoded, and only their coded planes.
+    -> (status per crop, failed plane per crop (-1: none), dict(planes_decoded, planes_total, pieces, slabs))."""
+    tab, keep = rgb_files(files)
+    rc, st, bad, stats = _read_rgb_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_rgb_read_crops", spec)(
+        tab, len(files), a, n, cw, ch, d, cap, s, b, p), xyf, d_out, out_cap)
+    if rc:
+        _raise(rc, "rgb_read_crops")
     return st, bad, stats
 
 
@@ -2154,6 +2236,20 @@ class Session:
         if rc:
             _raise(rc, "session_rgb_decode")
         return st, fp
+
+    def rgb_read_crops(self, d_blobs: int, offsets: np.ndarray, images, xyf, cw: int, ch: int, d_out: int, out_cap: int, spec=None):
+        """rgb_read_crops of CompressRGB blobs that lie on the session's device as rgb_encode leaves them: file f at
+        d_blobs + offsets[f] .. offsets[f + 1], images = make_rgb_images(...) (or the tuples; only width and height are read).
+        The heads of the named blobs are read by a kernel and the blobs go device to device."""
+        tab = images if isinstance(images, C.Array) else self.make_rgb_images(images)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.size < len(tab) + 1:
+            raise ValueError("rgb_read_crops: offsets must hold len(images) + 1 entries")
+        rc, st, bad, stats = _read_rgb_crops(lambda a, n, d, cap, s, b, p: _door("mic_hip_session_rgb_read_crops", spec)(
+            self._h, int(d_blobs) or None, offs.ctypes.data, tab, len(tab), a, n, cw, ch, d, cap, s, b, p), xyf, d_out, out_cap)
+        if rc:
+            _raise(rc, "session_rgb_read_crops")
+        return st, bad, stats
 
     # ---- WaveletV2 on device-resident frames (waveletfsecompressu16.go:303-534) -------------------------------------------
     def wavelet_v2_encode(self, d_frames: int, nframes: int, rows: int, cols: int, levels: int = 5):

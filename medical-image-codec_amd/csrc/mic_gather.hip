@@ -1,9 +1,9 @@
 // mic_gather.hip -- what the readers of many rectangles per call share (MIC3 patches: mic_api_ext.hip, MIC2 crops: mic_mic2_crops.hip,
-// strip-file crops: mic_strip_crops.hip).  Each of them plans on the host, decodes the touched units in sub-batches into a slab and
-// copies the pieces, the (rectangle, unit) overlaps, out of the slab into the output tensor.  Here: the kernels that copy and their
-// launcher, the judgement of the output pointer, the crop doors' way to a session, and the packing of a sub-batch's streams; and
-// the typed output of the _as doors (mic_hip_out_spec): its one judgement, the typed gather kernels, the pad fill and the convert
-// kernel of the MIC2 temporal staging tensor.
+// strip-file crops: mic_strip_crops.hip, RGB file crops: mic_rgb_crops.hip).  Each of them plans on the host, decodes the touched
+// units in sub-batches into a slab and copies the pieces, the (rectangle, unit) overlaps, out of the slab into the output tensor.
+// Here: the kernels that copy and their launcher, the judgement of the output pointer, the crop doors' way to a session, and the
+// packing of a sub-batch's streams; and the typed output of the _as doors (mic_hip_out_spec): its one judgement, the typed gather
+// kernels, the pad fill and the convert kernel of the MIC2 temporal staging tensor.
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
 #include <cmath>
@@ -34,29 +34,74 @@ __global__ void __launch_bounds__(256) k_gather_pieces(const uint16_t *slab, con
     }
 }
 
-// YCoCgRInverse of the piece's pixels, as k_wsi_planes_to_rgb does it; three byte stores per pixel at whatever byte offset the
-// tensor's row has.  src: the piece in plane 0, the other two pstride samples on each; out: u8, three a pixel.  Lanes along x of a
-// piece row: a wave reads 64 neighbouring samples of each plane and writes 192 neighbouring bytes.
-__global__ void __launch_bounds__(256) k_gather_pieces_rgb(const uint16_t *slab, const GatherPiece *pieces, uint8_t *out) {
-    const GatherPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
-    const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
-    const mic_gp<uint8_t> o = mic_g(out + pc.dst * 3);
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const size_t si = (size_t)y * pc.sstride, di = (size_t)y * pc.dstride * 3;
-        for (int x = ln.col; x < pc.w; x += ln.lw) {
-            const int yv = py[si + x];
-            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
-            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, deltazigzagcompressu16.go:113-116
-            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
-            const int t = yv - (cg >> 1);                                                   // YCoCgRInverse, asm_amd64.go:106-121
-            const int g = cg + t;
-            const int b = t - (co >> 1);
-            const int r = co + b;
-            const size_t d = di + (size_t)x * 3;
-            o[d] = (uint8_t)r; o[d + 1] = (uint8_t)g; o[d + 2] = (uint8_t)b;
+// ---- the RGB gathers: the planes a piece's pixels come from, one row loop, the pixel's arithmetic ---------------------------------
+// The three planes of a piece in a slab of whole units: the piece in plane 0, the other two pstride samples on each.
+struct SlabPlanes {
+    mic_gp<const uint16_t> py, pco, pcg;
+    __device__ __forceinline__ SlabPlanes(const uint16_t *slab, const GatherPiece &pc) : py(mic_g(slab + pc.src)), pco(py + pc.pstride), pcg(pco + pc.pstride) {}
+    __device__ __forceinline__ uint32_t y(size_t i) const { return py[i]; }
+    __device__ __forceinline__ uint32_t co(size_t i) const { return pco[i]; }
+    __device__ __forceinline__ uint32_t cg(size_t i) const { return pcg[i]; }
+};
+// The three planes of a piece by its record (RgbPlaneSrc): each the decoded plane in the slab, a constant, or the blob's raw samples
+// in `raw` -- little-endian at any byte address (a Y plane's always start at an odd one), two byte loads a sample as k_rgb_batch_fill
+// reads them.  The kind is the whole piece's, so a block's branches on it are uniform.
+struct ModePlanes {
+    struct Plane { mic_gp<const uint16_t> slab; mic_gp<const uint8_t> raw; uint32_t kind, value; };
+    Plane p[3];
+    __device__ __forceinline__ ModePlanes(const uint16_t *slab, const uint8_t *raw, const RgbPlaneSrc &r) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            p[k].kind = r.kind[k]; p[k].value = r.value[k];
+            p[k].slab = mic_g(slab) + (r.kind[k] == kPlaneSlab ? r.at[k] : 0);
+            p[k].raw = mic_g(raw) + (r.kind[k] == kPlaneRaw ? r.at[k] : 0);
         }
     }
+    __device__ __forceinline__ uint32_t sample(const Plane &q, size_t i) const {
+        if (q.kind == kPlaneSlab) return q.slab[i];
+        if (q.kind == kPlaneRaw) return (uint32_t)q.raw[2 * i] | ((uint32_t)q.raw[2 * i + 1] << 8);
+        return q.value;
+    }
+    __device__ __forceinline__ uint32_t y(size_t i) const { return sample(p[0], i); }
+    __device__ __forceinline__ uint32_t co(size_t i) const { return sample(p[1], i); }
+    __device__ __forceinline__ uint32_t cg(size_t i) const { return sample(p[2], i); }
+};
+// UnZigZag of Co and Cg (deltazigzagcompressu16.go:113-116) and YCoCgRInverse (asm_amd64.go:106-121), as k_wsi_planes_to_rgb does
+// them: the pixel every RGB gather writes (its channels' low bytes)
+struct RgbPx { int r, g, b; };
+__device__ __forceinline__ RgbPx ycocg_rgb(int yv, uint32_t uco, uint32_t ucg) {
+    const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));
+    const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
+    const int t = yv - (cg >> 1);
+    const int g = cg + t;
+    const int b = t - (co >> 1);
+    return RgbPx{ co + b, g, b };
+}
+// The piece's pixels through put(d, pixel), d = y * dstride + x * px samples from the piece's place in the tensor.  Lanes along x of
+// a piece row: a wave reads 64 neighbouring samples of each plane and writes 64 neighbouring pixels.
+template <class Planes, class Put>
+__device__ __forceinline__ void gather_rgb_rows(const GatherPiece &pc, const Planes &pl, size_t dstride, int px, Put &&put) {
+    const PieceLanes ln = piece_lanes(pc.w);
+    for (int y = ln.row; y < pc.h; y += ln.rstep) {
+        const size_t si = (size_t)y * pc.sstride, di = (size_t)y * dstride;
+        for (int x = ln.col; x < pc.w; x += ln.lw) put(di + (size_t)x * px, ycocg_rgb((int)pl.y(si + x), pl.co(si + x), pl.cg(si + x)));
+    }
+}
+// out: u8, three a pixel: three byte stores per pixel at whatever byte offset the tensor's row has, 192 neighbouring bytes a wave
+template <class Planes>
+__device__ __forceinline__ void gather_rgb_native(const GatherPiece &pc, const Planes &pl, uint8_t *out) {
+    const mic_gp<uint8_t> o = mic_g(out + pc.dst * 3);
+    gather_rgb_rows(pc, pl, (size_t)pc.dstride * 3, 3, [&](size_t d, RgbPx v) { o[d] = (uint8_t)v.r; o[d + 1] = (uint8_t)v.g; o[d + 2] = (uint8_t)v.b; });
+}
+
+__global__ void __launch_bounds__(256) k_gather_pieces_rgb(const uint16_t *slab, const GatherPiece *pieces, uint8_t *out) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    gather_rgb_native(pc, SlabPlanes(slab, pc), out);
+}
+// ... of RGB files (CompressRGB blobs), whose slab holds the coded planes alone: no plane is filled in for a constant or a raw one
+__global__ void __launch_bounds__(256) k_gather_modes_rgb(const uint16_t *slab, const uint8_t *raw, const GatherPiece *pieces, const RgbPlaneSrc *srcs, uint8_t *out) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    gather_rgb_native(pc, ModePlanes(slab, raw, srcs[blockIdx.x]), out);
 }
 
 // ---- typed output (mic_hip_out_spec) ------------------------------------------------------------------------------------------
@@ -112,31 +157,27 @@ __global__ void __launch_bounds__(256) k_gather_typed(const uint16_t *slab, cons
 // k_gather_pieces_rgb for a typed tensor: the same YCoCg-R inverse, then r, g and b through their channel's pair to the pixel's
 // three places, o.plane samples apart: 1 in the interleaved tensor (pc.dst: the pixel's first sample), ph * pw in the
 // channels-first one (pc.dst: the piece's place in plane 0, rows dstride samples apart).
-template <int DT>
-__global__ void __launch_bounds__(256) k_gather_typed_rgb(const uint16_t *slab, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+template <int DT, class Planes>
+__device__ __forceinline__ void gather_rgb_typed(const GatherPiece &pc, const Planes &pl, typename OutBits<DT>::type *out, const OutParams &o) {
     typedef typename OutBits<DT>::type T;
-    const GatherPiece pc = pieces[blockIdx.x];
-    const PieceLanes ln = piece_lanes(pc.w);
     const size_t a0 = (size_t)pc.source * o.src_mul;
     const Pair ar = out_pair(o, a0), ag = out_pair(o, a0 + o.ch_step), ab = out_pair(o, a0 + 2 * o.ch_step);
-    const mic_gp<const uint16_t> py = mic_g(slab + pc.src), pco = py + pc.pstride, pcg = pco + pc.pstride;
     const mic_gp<T> dr = mic_g(out + pc.dst), dg = dr + o.plane, db = dg + o.plane;
-    const int px = o.plane == 1 ? 3 : 1;                                                    // samples from a pixel to the next of its row
-    for (int y = ln.row; y < pc.h; y += ln.rstep) {
-        const size_t si = (size_t)y * pc.sstride, di = (size_t)y * pc.dstride;
-        for (int x = ln.col; x < pc.w; x += ln.lw) {
-            const int yv = py[si + x];
-            const uint32_t uco = pco[si + x], ucg = pcg[si + x];
-            const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));       // UnZigZag, deltazigzagcompressu16.go:113-116
-            const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
-            const int t = yv - (cg >> 1);                                                   // YCoCgRInverse, asm_amd64.go:106-121
-            const int g = cg + t;
-            const int b = t - (co >> 1);
-            const int r = co + b;
-            const size_t d = di + (size_t)x * px;
-            dr[d] = out_sample<DT>((uint8_t)r, ar, o); dg[d] = out_sample<DT>((uint8_t)g, ag, o); db[d] = out_sample<DT>((uint8_t)b, ab, o);
-        }
-    }
+    gather_rgb_rows(pc, pl, (size_t)pc.dstride, o.plane == 1 ? 3 : 1, [&](size_t d, RgbPx v) {   // (px: samples from a pixel to the next of its row)
+        dr[d] = out_sample<DT>((uint8_t)v.r, ar, o); dg[d] = out_sample<DT>((uint8_t)v.g, ag, o); db[d] = out_sample<DT>((uint8_t)v.b, ab, o);
+    });
+}
+template <int DT>
+__global__ void __launch_bounds__(256) k_gather_typed_rgb(const uint16_t *slab, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    gather_rgb_typed<DT>(pc, SlabPlanes(slab, pc), out, o);
+}
+// k_gather_modes_rgb for a typed tensor
+template <int DT>
+__global__ void __launch_bounds__(256) k_gather_typed_modes_rgb(const uint16_t *slab, const uint8_t *raw, const GatherPiece *pieces, const RgbPlaneSrc *srcs,
+                                                                typename OutBits<DT>::type *out, const OutParams o) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    gather_rgb_typed<DT>(pc, ModePlanes(slab, raw, srcs[blockIdx.x]), out, o);
 }
 
 // MIC2 temporal volumes: run = a crop's footprint, w x h samples of d slices from `at` of the u16 staging tensor (slices of ch x cw)
@@ -246,13 +287,21 @@ void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table,
 }
 
 void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out,
-                   int dtype, const OutParams &op) {
+                   int dtype, const OutParams &op, const RgbModeArgs &modes) {
     constexpr size_t kMaxGridX = 0x7FFFFFFF;
     const unsigned gy = row_chunks(mw, mh);
     for (size_t q = 0; q < np; q += kMaxGridX) {
         const dim3 grid((unsigned)std::min(np - q, kMaxGridX), gy), block(256);
         const GatherPiece *pq = pieces + q;
-        if (dtype == MIC_HIP_OUT_NATIVE) {
+        const RgbPlaneSrc *sq = modes.srcs + q;
+        if (kind == kGatherRGBModes) switch (dtype) {
+            case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL(k_gather_modes_rgb, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint8_t *)out); break;
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_U8>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_U16>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_F16>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_BF16>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_F32>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint32_t *)out, op); break;
+        } else if (dtype == MIC_HIP_OUT_NATIVE) {
             if (kind == kGatherRGB) hipLaunchKernelGGL(k_gather_pieces_rgb, grid, block, 0, stream, slab, pq, (uint8_t *)out);
             else if (kind == kGatherU16) hipLaunchKernelGGL(k_gather_pieces<uint16_t>, grid, block, 0, stream, slab, pq, (uint16_t *)out);
             else hipLaunchKernelGGL(k_gather_pieces<uint8_t>, grid, block, 0, stream, slab, pq, (uint8_t *)out);
@@ -292,7 +341,7 @@ int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t nee
     if (!*s) { if ((rc = lease.acquire())) return rc; *s = cur_default(); }
     else if ((rc = (*s)->activate())) return rc;
     rc = patch_pointer(*s, d_out, need);                                                    // judged before anything is launched
-    if (rc == MIC_ERR_CAPACITY || (o.typed() ? !out_aligned(o, *d_out) : ((size_t)*d_out & 1) != 0)) rc = MIC_ERR_ARGS;
+    if (rc == MIC_ERR_CAPACITY || (o.typed() ? !out_aligned(o, *d_out) : ((o.sample & 1) == 0 && ((size_t)*d_out & 1) != 0))) rc = MIC_ERR_ARGS;   // (u8 RGB: any address)
     return rc;
 }
 

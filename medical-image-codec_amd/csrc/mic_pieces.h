@@ -33,6 +33,15 @@ inline unsigned row_chunks(int w, int h) {
 // typed kernels read, to pick the affine pair.
 struct GatherPiece { uint64_t src, dst; int32_t sstride, dstride, w, h, pstride, source; };
 
+// Where the mode-aware RGB gather (RGB file crops: mic_rgb_crops.hip) finds the three planes of piece q: record q of the reader's
+// own records, which lie behind the gather list.  A plane is the decoded one in the slab (at: samples from the slab's start to the
+// piece's first sample), a constant that nobody materialises (value), or the raw little-endian samples of the blob where they lie in
+// the compressed-input buffer (at: bytes from that buffer's start to the piece's first sample, any alignment).  Rows are the piece's
+// sstride samples apart in both; the kernel reads neither src nor pstride of the piece.
+enum RgbPlaneKind : uint8_t { kPlaneConst = 0, kPlaneSlab = 1, kPlaneRaw = 2 };
+struct RgbPlaneSrc { uint64_t at[3]; uint16_t value[3]; uint8_t kind[3]; uint8_t pad[7]; };
+static_assert(sizeof(RgbPlaneSrc) == 40, "the records travel as five u64 per piece");
+
 // What the typed kernels (mic_gather.hip) read of a call's output description: the pair of (source, channel) is
 // pair source * src_mul + channel * ch_step of affine (a, b each); plane: samples between the channels of a pixel's destination (1: interleaved,
 // ph * pw: channels first), multiplied out by the host.
@@ -65,13 +74,17 @@ int fill_pad(hipStream_t stream, const OutFormat &o, void *d_out, size_t bytes);
 struct ConvertRun { uint64_t at; int32_t w, h, d, source; };
 void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table, const uint16_t *stage, const ConvertRun *runs, size_t n,
                     int mw, int mh, int md, int cw, int ch, void *out);
-// what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), or three YCoCg-R planes' RGB bytes
-enum GatherKind { kGatherU16, kGatherU8, kGatherRGB };
+// what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), three YCoCg-R planes' RGB bytes, or the same
+// from planes of three kinds (RgbPlaneSrc)
+enum GatherKind { kGatherU16, kGatherU8, kGatherRGB, kGatherRGBModes };
+// what kGatherRGBModes reads beside the slab: the buffer the raw planes lie in and the pieces' records (device; record q is piece q's)
+struct RgbModeArgs { const uint8_t *raw; const RgbPlaneSrc *srcs; };
 // np pieces (device) of a slab -> out, behind what `stream` holds; mw x mh: the largest of them.  The one place that picks the
 // kernel, cuts the rows of tall pieces over grid y (row_chunks) and the pieces over launches of at most 2^31 - 1.  dtype
 // MIC_HIP_OUT_NATIVE: the native kernels, which read nothing of op; else the typed ones (one plane: kGatherU16 and kGatherU8 alike).
+// modes: what kGatherRGBModes reads further, cut over the launches with the pieces.
 void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out,
-                   int dtype = 0, const OutParams &op = OutParams{ nullptr, 0, 0, 0, 0, 0, 1 });
+                   int dtype = 0, const OutParams &op = OutParams{ nullptr, 0, 0, 0, 0, 0, 1 }, const RgbModeArgs &modes = RgbModeArgs{ nullptr, nullptr });
 // d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
 // pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
 // *d_out becomes the address the device uses.

@@ -1,7 +1,8 @@
 // mic_rects.h -- the host core of the readers of many rectangles per call (MIC3 patches: mic_api_ext.hip; strip-file crops:
-// mic_strip_crops.hip; MIC2 crops: mic_mic2_crops.hip), written once.  A reader plans for itself -- the units to entropy-decode and
-// the (rectangle, unit) overlaps, pieces -- and decodes a sub-batch its own way; around that it calls, in this order: rect_batches,
-// upload_gather; per sub-batch gather_units behind the decode; after the call's one synchronise fold_unit_status and container_codes.
+// mic_strip_crops.hip; MIC2 crops: mic_mic2_crops.hip; RGB file crops: mic_rgb_crops.hip), written once.  A reader plans for
+// itself -- the units to entropy-decode and the (rectangle, unit) overlaps, pieces -- and decodes a sub-batch its own way; around
+// that it calls, in this order: rect_batches, upload_gather; per sub-batch gather_units behind the decode; after the call's one
+// synchronise fold_unit_status and container_codes.
 #pragma once
 #include "mic_session.h"
 #include "mic_pieces.h"
@@ -72,14 +73,16 @@ inline int upload_gather(mic_hip_session *s, const RectBatches &B, const OutForm
     return rc;
 }
 // the pieces of sub-batch b out of its decoded slab into d_out, timed as `label`; the caller resets the timer before and marks "end" behind.
-// plane: the samples of one rectangle's plane (ch x cw), which a channels-first tensor's kernel steps by.
+// plane: the samples of one rectangle's plane (ch x cw), which a channels-first tensor's kernel steps by.  raw (kGatherRGBModes): the
+// buffer the raw planes lie in; the pieces' RgbPlaneSrc records are the first thing behind the list.
 inline void gather_units(mic_hip_session *s, const char *label, GatherKind kind, const void *slab, const RectBatches &B, size_t b, void *d_out,
-                         const OutFormat &o, size_t plane, size_t behind = 0) {
+                         const OutFormat &o, size_t plane, size_t behind = 0, const void *raw = nullptr) {
     const size_t p0 = B.first[B.cuts[b]], np = B.first[B.cuts[b + 1]] - p0;
     if (!np) return;
     s->timer.mark(label);
     launch_gather(s->stream, kind, (const uint16_t *)slab, (const GatherPiece *)s->pieces.p + p0, np, B.mw[b], B.mh[b], d_out, o.dtype,
-                  o.params(out_table(s, B, behind), plane));
+                  o.params(out_table(s, B, behind), plane),
+                  RgbModeArgs{ (const uint8_t *)raw, (const RgbPlaneSrc *)((const char *)s->pieces.p + gather_bytes(B)) + p0 });
 }
 
 // status[r] / failed[r] (may be NULL) of rectangle r = piece.rect / per of n: MIC_OK / -1, or its first failing unit's in piece order / label(it)

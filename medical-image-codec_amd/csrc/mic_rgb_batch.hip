@@ -18,10 +18,9 @@ constexpr size_t kRgbMaxPx = (size_t)1 << 26;        // as mic_hip_rgb_compress
 constexpr int kRgbMaxImages = 65535 / 3;             // an image's three units: a launch's grid y in the unit codec
 
 // An image of a sub-batch: RGB at rgb + rgb_off (any byte alignment), its Y plane at planes + plane_off, Co and Cg rgb_stride(w * h)
-// u16 behind it each; chunk0 = the chunks of the images before it; slot: where its statistics go.
+// u16 behind it each (mic_session.h); chunk0 = the chunks of the images before it; slot: where its statistics go.
 struct RgbDesc { uint64_t rgb_off, plane_off; int32_t w, h; uint32_t chunk0, slot; };
 static_assert(sizeof(RgbDesc) == 32, "the table travels as four u64 per image");
-__host__ __device__ inline size_t rgb_stride(size_t npx) { return (npx + 7) & ~(size_t)7; }       // planes start 16-byte aligned
 
 typedef uint16_t rgb_u16x4 __attribute__((ext_vector_type(4)));
 typedef rgb_u16x4 RgbQ __attribute__((aligned(2)));                    // (a group of four pixels starts at any even address: gfx950 stores it unaligned)
@@ -198,14 +197,15 @@ __global__ void __launch_bounds__(256) k_rgb_batch_assemble(const RgbAsm *recs, 
     }
 }
 
-// RgbHead of every blob of a device buffer (micapi::rgb_head_of, on the device): one thread per blob, offs[i] .. offs[i + 1] its bytes.
+// RgbHead of every blob of a device buffer (micapi::rgb_head_of, on the device): one thread per blob, begins[i] .. ends[i] its bytes
+// (blobs that lie back to back: ends = begins + 1).
 // BOUNDS: a byte is read only at an index below the blob's length.
-__global__ void __launch_bounds__(256) k_rgb_batch_heads(const uint8_t *blobs, const uint64_t *offs, int n, RgbHead *heads) {
+__global__ void __launch_bounds__(256) k_rgb_batch_heads(const uint8_t *blobs, const uint64_t *begins, const uint64_t *ends, int n, RgbHead *heads) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i >= n) return;
     RgbHead h;
     memset(&h, 0, sizeof h);
-    const uint64_t b0 = offs[i], bl = offs[i + 1] >= b0 ? offs[i + 1] - b0 : 0;
+    const uint64_t b0 = begins[i], bl = ends[i] >= b0 ? ends[i] - b0 : 0;
     const uint8_t *c = blobs + b0;
     if (bl >= 12) {
         uint64_t off = 12;
@@ -233,6 +233,13 @@ void rgb_head_of(const uint8_t *c, uint64_t bl, RgbHead &h) {
         for (uint32_t k = 0; k < 3; k++) if (k < h.len[p] && off + k < bl) h.b[p][k] = c[off + k];
         off += h.len[p];
     }
+}
+
+int rgb_heads_enqueue(hipStream_t stream, const uint8_t *d_blobs, const uint64_t *d_begins, const uint64_t *d_ends, int n, RgbHead *d_heads) {
+    if (n <= 0) return MIC_OK;
+    hipLaunchKernelGGL(k_rgb_batch_heads, dim3((unsigned)(n + 255) / 256), dim3(256), 0, stream, d_blobs, d_begins, d_ends, n, d_heads);
+    HIP_TRY(hipGetLastError());
+    return MIC_OK;
 }
 
 int rgb_parse_head(const RgbHead &h, uint64_t bl, size_t npx, RgbPlaneRec pl[3], int32_t *failed_plane) {
@@ -486,8 +493,7 @@ int mic_hip_session_rgb_decode(mic_hip_session *s, const uint8_t *d_blobs, const
     RgbHead *d_heads = (RgbHead *)((char *)s->rgb_aux.p + offs_b);
     if (total) HIP_TRY(hipMemcpyAsync(s->io_comp.p, d_blobs + b0, (size_t)total, hipMemcpyDeviceToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(d_offs, h_rel, offs_b, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_rgb_batch_heads, dim3((unsigned)(n + 255) / 256), dim3(256), 0, s->stream, (const uint8_t *)s->io_comp.p, (const uint64_t *)d_offs, n, d_heads);
-    HIP_TRY(hipGetLastError());
+    if ((rc = rgb_heads_enqueue(s->stream, (const uint8_t *)s->io_comp.p, d_offs, d_offs + 1, n, d_heads))) return rc;
     HIP_TRY(hipMemcpyAsync(h_heads, d_heads, head_b, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     std::vector<RgbBlob> bl((size_t)n);

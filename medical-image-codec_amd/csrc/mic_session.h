@@ -397,7 +397,7 @@ int pack_streams(mic_hip_session *s, int nb, const std::function<uint64_t(int)> 
                  std::vector<uint64_t> &begins, std::vector<uint64_t> &ends);
 // What a crop door does once it has a plan: the session -- *s, made current, or when NULL one leased here --, then d_out judged for a
 // tensor of `need` bytes in o's type (patch_pointer; an allocation that ends before the tensor does and an address that is not
-// aligned to the sample -- u16 for the native format -- are MIC_ERR_ARGS: out_cap held the tensor).
+// aligned to the sample -- u16 for the native format, no demand on the u8 RGB one -- are MIC_ERR_ARGS: out_cap held the tensor).
 struct OutFormat;                 // (mic_pieces.h)
 int crop_door(mic_hip_session **s, DefaultLease &lease, void **d_out, size_t need, const OutFormat &o);
 // MIC2 crops (mic_mic2_crops.hip).  A piece is one (crop, frame) overlap: w x h samples from (sx, sy) of frame `frame` to (dx, dy) of
@@ -459,6 +459,10 @@ struct RgbBlob { uint64_t blob_off, blob_len, rgb_off; int32_t w, h; int32_t sta
 // what the host needs of a blob to check it: the three plane lengths and the first three bytes of each plane (zero where the blob ends before)
 struct RgbHead { uint32_t len[3]; uint8_t b[3][3]; uint8_t pad[3]; };
 void rgb_head_of(const uint8_t *blob, uint64_t bl, RgbHead &h);
+// ... of n blobs of a device buffer, blob i at d_begins[i] .. d_ends[i] of d_blobs (device arrays), behind what `stream` holds (k_rgb_batch_heads)
+int rgb_heads_enqueue(hipStream_t stream, const uint8_t *d_blobs, const uint64_t *d_begins, const uint64_t *d_ends, int n, RgbHead *d_heads);
+// u16 samples from a plane of an image of npx pixels to the next in a slab of YCoCg-R planes
+__host__ __device__ inline size_t rgb_stride(size_t npx) { return (npx + 7) & ~(size_t)7; }       // planes start 16-byte aligned
 // decompressRGBTileBlob's checks (wsicompress.go:431-461) + decompressWSIPlane's for every plane: the blob's status, the plane it names
 int rgb_parse_head(const RgbHead &h, uint64_t bl, size_t npx, RgbPlaneRec pl[3], int32_t *failed_plane);
 // images [i0, return) of the next sub-batch of images [.., n), npx(i) pixels each: their three units a launch's grid y and under the
