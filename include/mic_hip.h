@@ -1133,6 +1133,63 @@ int mic_hip_session_set_timing(mic_hip_session *s, int enabled);
  * names[i] / ms[i], returns the number of entries written (<= cap). */
 int mic_hip_session_last_timings(mic_hip_session *s, const char **names, float *ms, int cap);
 
+/* ---- MIC3: a cache of decoded tiles in device memory --------------------------------------------- */
+/* A sampler draws patches of the same slides call after call, and every patch call entropy-decodes the tiles it touches.  A
+ * tile cache keeps decoded tiles on the device: a reader or a session that has one attached decodes only the tiles that are not
+ * resident, pulls only their blobs through the callback, and gathers hits and fresh tiles alike out of the cache.  It serves
+ * mic_hip_wsi_reader_read_patches, mic_hip_session_wsi_read_patches, mic_hip_wsi_readers_read_patches and their _as twins; the
+ * flat-file doors and _reader_decompress_tile / _region never use it, and a caller who attaches none runs the code it ran before.
+ *
+ * A cache has nslots slots for tiles of one format (tile size, channels, bits per sample; the format checks are
+ * mic_hip_wsi_compress_ex's, tile_w / tile_h 0 = 256).  A slot holds one tile as pixels of the slide's sample format -- tile_w x
+ * tile_h x channels samples of u8, or u16 for 16-bit greyscale, the YCoCg-R inverse already done -- padded to a multiple of 256
+ * bytes: mic_hip_tile_cache_slot_bytes.  nslots = 0 is a valid cache that keeps nothing.  create, set_cache, clear, destroy,
+ * get_stats and plan need no device: the arena (nslots * slot_bytes, one allocation) is made by the first patch call that uses the
+ * cache, on that call's session's device; if that allocation fails the call returns its code and the cache stays empty.  A later
+ * call whose session is on another device runs without the cache, each of its tiles counted as bypassed.
+ *
+ * An entry's key is (owner, global tile index = level.first + ty * tiles_x + tx, as mic_hip_wsi_multi_patch_plan counts).  An
+ * owner is a reader, or one store generation of a session: two readers of one file are two owners, and every
+ * mic_hip_session_wsi_encode drops the session's old entries.
+ *
+ * Replacement.  Each call that uses the cache gets the next call number.  (1) The call's tiles are walked in plan order (slide,
+ * then global tile index); a resident one is a hit and is stamped with the call number.  (2) Each miss, in plan order, takes the
+ * lowest-numbered free slot; else the entry with the smallest stamp below the call's number, ties to the lowest slot, which is
+ * evicted; else -- every slot is stamped by this call -- the tile is bypassed: decoded into the session's slab and gathered
+ * from there.  (3) A tile whose decode reports a status is released when the call has its statuses: a failed tile is never
+ * resident (it counts as bypassed).  (4) A call that returns an error undoes everything: no entry added, none evicted, stamps and
+ * counters as before.  mic_hip_tile_cache_plan runs this policy alone, on the host, over a trace -- the same code.
+ *
+ * Locking.  One mutex per cache, held by a call from its planning to its final stream synchronise: threads that share a cache
+ * SERIALISE on it.  Lock order: readers first, in address order, then caches in address order.
+ *
+ * With a cache attached the stats of a patch call read: tiles_decoded = tiles this call entropy-decoded (misses + bypassed);
+ * pieces = the planner's count; slabs = decode chains run, 0 for a call that only hit. */
+typedef struct mic_hip_tile_cache mic_hip_tile_cache;
+/* slots: as given at create; resident: entries now; hits, misses (decoded and kept), bypassed (decoded and not kept), evictions,
+ * calls: cumulative; device_bytes: 0 until the arena is allocated */
+typedef struct { uint64_t slots, resident, hits, misses, bypassed, evictions, calls, device_bytes; } mic_hip_tile_cache_stats;
+int mic_hip_tile_cache_slot_bytes(int tile_w, int tile_h, int channels, int bits_per_sample, uint64_t *bytes);
+int mic_hip_tile_cache_create(int tile_w, int tile_h, int channels, int bits_per_sample, uint64_t nslots, mic_hip_tile_cache **c);
+/* drops every entry; owners stay attached.  NULL: MIC_OK */
+int mic_hip_tile_cache_clear(mic_hip_tile_cache *c);
+int mic_hip_tile_cache_get_stats(const mic_hip_tile_cache *c, mic_hip_tile_cache_stats *st);
+/* MIC_ERR_ARGS, and nothing freed, while a reader or session is attached.  NULL: MIC_OK */
+int mic_hip_tile_cache_destroy(mic_hip_tile_cache *c);
+/* c = NULL detaches and drops the reader's entries; a slide whose tile size or sample format is not the cache's: MIC_ERR_ARGS;
+ * the cache the reader already has: nothing happens.  mic_hip_wsi_reader_close detaches. */
+int mic_hip_wsi_reader_set_cache(mic_hip_wsi_reader *r, mic_hip_tile_cache *c);
+/* resident[i] = 1 when global tile index tiles[i] of this owner is resident, else 0; changes no state */
+int mic_hip_wsi_reader_cache_probe(mic_hip_wsi_reader *r, const uint64_t *tiles, size_t n, uint8_t *resident);
+/* the cache then serves mic_hip_session_wsi_read_patches{,_as}; the format is checked against the store when there is one, and
+ * by each mic_hip_session_wsi_encode (a store of another format detaches the cache).  mic_hip_session_destroy detaches. */
+int mic_hip_session_set_tile_cache(mic_hip_session *s, mic_hip_tile_cache *c);
+int mic_hip_session_tile_cache_probe(mic_hip_session *s, const uint64_t *tiles, size_t n, uint8_t *resident);
+/* The policy over a trace: keys = the calls' keys back to back (each call's distinct and ascending), call_len[k] = the length of
+ * call k; outcome[i] = 0 hit, 1 miss (kept), 2 bypassed; *evictions = their total (may be NULL). */
+int mic_hip_tile_cache_plan(uint64_t nslots, const uint64_t *keys, const uint32_t *call_len, int ncalls,
+                            uint8_t *outcome, uint64_t *evictions);
+
 #ifdef __cplusplus
 }
 #endif

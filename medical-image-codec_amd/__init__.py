@@ -130,6 +130,11 @@ class PatchStats(C.Structure):
     _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64)]
 
 
+class TileCacheStats(C.Structure):
+    """mic_hip_tile_cache_stats"""
+    _fields_ = [(f_, C.c_uint64) for f_ in ("slots", "resident", "hits", "misses", "bypassed", "evictions", "calls", "device_bytes")]
+
+
 class MultiPatchStats(C.Structure):
     """mic_hip_multi_patch_stats"""
     _fields_ = [("tiles_decoded", C.c_uint64), ("pieces", C.c_uint64), ("slabs", C.c_uint64), ("slides_read", C.c_uint64)]
@@ -271,6 +276,9 @@ ABI_SYMBOLS = [
     "mic_hip_session_strips_read_crops_as",
     "mic_hip_rgb_read_crops_as",
     "mic_hip_session_rgb_read_crops_as",
+    "mic_hip_tile_cache_slot_bytes", "mic_hip_tile_cache_create", "mic_hip_tile_cache_clear", "mic_hip_tile_cache_get_stats",
+    "mic_hip_tile_cache_destroy", "mic_hip_tile_cache_plan",
+    "mic_hip_wsi_reader_set_cache", "mic_hip_wsi_reader_cache_probe", "mic_hip_session_set_tile_cache", "mic_hip_session_tile_cache_probe",
 ]
 
 # the readers of many rectangles per call; each has an _as twin that takes a trailing mic_hip_out_spec (OutSpec)
@@ -514,6 +522,16 @@ def lib() -> C.CDLL:
     L.mic_hip_out_spec_check.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     L.mic_hip_session_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.mic_hip_session_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
+    L.mic_hip_tile_cache_slot_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_uint64)]
+    L.mic_hip_tile_cache_create.argtypes = [C.c_int] * 4 + [C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mic_hip_tile_cache_clear.argtypes = [C.c_void_p]
+    L.mic_hip_tile_cache_get_stats.argtypes = [C.c_void_p, C.POINTER(TileCacheStats)]
+    L.mic_hip_tile_cache_destroy.argtypes = [C.c_void_p]
+    L.mic_hip_wsi_reader_set_cache.argtypes = [C.c_void_p, C.c_void_p]
+    L.mic_hip_wsi_reader_cache_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.mic_hip_session_set_tile_cache.argtypes = [C.c_void_p, C.c_void_p]
+    L.mic_hip_session_tile_cache_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.mic_hip_tile_cache_plan.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -1750,6 +1768,85 @@ def _read_source(source, file_len: Optional[int], where: str):
     return get, int(file_len)
 
 
+def tile_cache_slot_bytes(tile_w: int, tile_h: int, channels: int = 3, bits_per_sample: int = 8) -> int:
+    """mic_hip_tile_cache_slot_bytes: device bytes of one slot of a TileCache of that format (a multiple of 256).  No device."""
+    nb = C.c_uint64(0)
+    rc = lib().mic_hip_tile_cache_slot_bytes(tile_w, tile_h, channels, bits_per_sample, C.byref(nb))
+    if rc:
+        _raise(rc, "tile_cache_slot_bytes")
+    return nb.value
+
+
+def tile_cache_plan(nslots: int, calls) -> Tuple[List[np.ndarray], int]:
+    """mic_hip_tile_cache_plan: the cache's replacement policy alone, over a trace.  calls: a sequence of calls, each the ascending,
+    distinct keys (global tile indices) of its tiles.  -> (per call a uint8 array: 0 hit, 1 miss (kept), 2 bypassed; evictions in
+    all).  No device."""
+    calls = [np.ascontiguousarray(np.asarray(c, dtype=np.uint64).reshape(-1)) for c in calls]
+    keys = np.concatenate(calls) if calls else np.zeros(0, dtype=np.uint64)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    lens = np.asarray([len(c) for c in calls], dtype=np.uint32)
+    out = np.zeros(max(len(keys), 1), dtype=np.uint8)
+    ev = C.c_uint64(0)
+    rc = lib().mic_hip_tile_cache_plan(int(nslots), keys.ctypes.data, lens.ctypes.data, len(calls), out.ctypes.data, C.byref(ev))
+    if rc:
+        _raise(rc, "tile_cache_plan")
+    cuts = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+    return [out[cuts[k]: cuts[k + 1]].copy() for k in range(len(calls))], ev.value
+
+
+class TileCache:
+    """mic_hip_tile_cache: decoded MIC3 tiles kept in device memory, `slots` of them, for readers and sessions whose slides have
+    this tile size and sample format (WsiReader.set_cache, Session.set_tile_cache).  A patch call of an owner with a cache decodes
+    only the tiles that are not resident.  The arena (slots * tile_cache_slot_bytes) is allocated by the first call that uses it.
+    Threads that share a cache serialise on it.  close() fails (MIC_ERR_ARGS) while a reader or session is still attached."""
+
+    def __init__(self, tile_w: int, tile_h: int, channels: int = 3, bits_per_sample: int = 8, slots: int = 0):
+        self._h = C.c_void_p()
+        rc = lib().mic_hip_tile_cache_create(tile_w, tile_h, channels, bits_per_sample, int(slots), C.byref(self._h))
+        if rc:
+            _raise(rc, "TileCache")
+
+    def stats(self) -> dict:
+        st = TileCacheStats()
+        rc = lib().mic_hip_tile_cache_get_stats(self._h, C.byref(st))
+        if rc:
+            _raise(rc, "TileCache.stats")
+        return {f_: int(getattr(st, f_)) for f_, _ in TileCacheStats._fields_}
+
+    def clear(self) -> None:
+        rc = lib().mic_hip_tile_cache_clear(self._h)
+        if rc:
+            _raise(rc, "TileCache.clear")
+
+    def close(self) -> None:
+        if self._h:
+            rc = lib().mic_hip_tile_cache_destroy(self._h)
+            if rc:
+                _raise(rc, "TileCache.close")
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _cache_probe(call, tiles) -> np.ndarray:
+    t = np.ascontiguousarray(np.asarray(tiles, dtype=np.uint64).reshape(-1))
+    res = np.zeros(max(len(t), 1), dtype=np.uint8)
+    rc = call(t.ctypes.data, len(t), res.ctypes.data)
+    if rc:
+        _raise(rc, "cache_probe")
+    return res[: len(t)].astype(bool)
+
+
 class WsiReader:
     """MIC3 random-access reader (mic_hip_wsi_reader_*): reads the header and tile index at open, then only the blobs of the
     tiles a tile() or region() covers.  source: a binary file object (seek + read), bytes, or a callable (offset, n) -> bytes."""
@@ -1793,10 +1890,24 @@ class WsiReader:
         self._cb.check(rc, "WsiReader.read_patches")
         return st, stats
 
+    def set_cache(self, cache: Optional["TileCache"]) -> None:
+        """mic_hip_wsi_reader_set_cache: read_patches (and wsi_readers_read_patches) then decode only the tiles that are not
+        resident in `cache`, and read only their blobs; None detaches and drops this reader's entries.  A cache of another tile
+        size or sample format raises MicError(MIC_ERR_ARGS)."""
+        rc = lib().mic_hip_wsi_reader_set_cache(self._h, cache._h if cache is not None else None)
+        if rc:
+            _raise(rc, "WsiReader.set_cache")
+        self._cache = cache                            # (kept alive while attached)
+
+    def cache_probe(self, tiles) -> np.ndarray:
+        """bool per global tile index (level.first + ty * tiles_x + tx): resident in this reader's cache; changes no state"""
+        return _cache_probe(lambda t, n, r: lib().mic_hip_wsi_reader_cache_probe(self._h, t, n, r), tiles)
+
     def close(self) -> None:
         if self._h:
             lib().mic_hip_wsi_reader_close(self._h)
             self._h = C.c_void_p()
+            self._cache = None
 
     def __enter__(self):
         return self
@@ -2365,6 +2476,18 @@ class Session:
         if rc:
             _raise(rc, "session_wsi_read_patches")
         return st, stats
+
+    def set_tile_cache(self, cache: Optional["TileCache"]) -> None:
+        """mic_hip_session_set_tile_cache: wsi_read_patches then decodes only the tiles that are not resident in `cache`; every
+        wsi_encode drops the session's entries (its slide is replaced).  None detaches."""
+        rc = lib().mic_hip_session_set_tile_cache(self._h, cache._h if cache is not None else None)
+        if rc:
+            _raise(rc, "session_set_tile_cache")
+        self._tile_cache = cache
+
+    def tile_cache_probe(self, tiles) -> np.ndarray:
+        """bool per global tile index of the session's slide: resident in its tile cache; changes no state"""
+        return _cache_probe(lambda t, n, r: lib().mic_hip_session_tile_cache_probe(self._h, t, n, r), tiles)
 
     def mic2_read_crops(self, head, d_file: int, file_len: int, xyz, cw: int, ch: int, cd: int, d_out: int, out_cap: int, spec=None):
         """mic2_read_crops of a MIC2 file that lies on the session's device: head = its first 20 + 8 * nframes bytes (host),

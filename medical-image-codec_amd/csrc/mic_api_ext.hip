@@ -11,6 +11,7 @@
 #include "mic_session.h"
 #include "mic_wave.h"
 #include "mic_rects.h"
+#include "mic_tile_cache.h"
 
 #include <memory>
 
@@ -827,22 +828,133 @@ typedef std::function<size_t(size_t npx)> SlabCeiling;
 // ... for blobs through the unit codec's workspace (tiles are a launch's grid y)
 SlabCeiling blob_ceiling(size_t P) { return [P](size_t npx) { return std::min<size_t>(kMaxGridY / P, batch_units_for(npx, P)); }; }
 
+// ---- the tile cache in a patch call (mic_tile_cache.h) ----------------------------------------------------------------------------
+// What a door with caches attached hands the core instead of its plan.  split() locks the caches of the call (address order, behind
+// the readers' locks), lets each index judge its tiles -- hit, miss or bypassed -- and cuts the plan in two: `decode`, the units to
+// entropy-decode (misses, bypassed, and tiles of owners without a cache) with the pieces of those that are NOT kept, which the core
+// gathers from the slab as ever; and per cache the pieces of its hits and misses, gathered out of the arena in one launch behind
+// the sub-batches.  A miss's planes go into its slot by one k_wsi_cache_fill launch behind its sub-batch's decode.  The locks are held
+// until the object dies, which is behind the call's final synchronise; a call that fails before finish() is undone there.
+struct CacheOwner { mic_hip_tile_cache *c; uint64_t owner; uint64_t first; };               // first: added to a unit's tile to make the global tile index
+struct CachePlan {
+    struct Use {
+        mic_hip_tile_cache *c; bool usable = false, planned = false;
+        std::vector<SlotIndex::Key> keys; std::vector<size_t> units;                        // its units of the full plan, plan order
+        std::vector<uint8_t> outcome; std::vector<uint32_t> slot;
+        std::vector<GatherPiece> pieces; int mw = 1, mh = 1;
+        std::vector<uint32_t> written;                                                      // slots a fill launch of this call has been queued for
+    };
+    std::vector<Use> uses;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    PatchPlan decode;
+    std::vector<size_t> full_of;                                                            // decode unit -> unit of the full plan
+    struct Kept { int32_t use; uint32_t slot; };                                            // use -1: not kept
+    std::vector<Kept> kept;                                                                 // per decode unit
+    std::vector<CacheFill> fills; std::vector<size_t> fill_first;                           // fills[fill_first[d] .. fill_first[d + 1]): decode unit d's (0 or 1)
+    GatherKind kind = kGatherPxU8;
+    mic_hip_session *s = nullptr; bool launched = false, done = false;
+    size_t cached_pieces() const { size_t n = 0; for (const Use &u : uses) n += u.pieces.size(); return n; }
+    size_t behind_bytes() const { return cached_pieces() * sizeof(GatherPiece) + fills.size() * sizeof(CacheFill); }
+
+    // um[u]: unit u's header; who(u): its owner's cache (c NULL: none)
+    template <class Who>
+    int split(mic_hip_session *ses, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const OutFormat &o, Who &&who) {
+        s = ses;
+        const size_t nu = plan.units.size();
+        std::vector<mic_hip_tile_cache *> cs;
+        std::vector<CacheOwner> ow(nu);
+        for (size_t u = 0; u < nu; u++) { ow[u] = who(u); if (ow[u].c) cs.push_back(ow[u].c); }
+        std::sort(cs.begin(), cs.end(), std::less<mic_hip_tile_cache *>());
+        cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+        uses.resize(cs.size());
+        locks.reserve(cs.size());
+        for (size_t k = 0; k < cs.size(); k++) { uses[k].c = cs[k]; locks.emplace_back(cs[k]->mu); }
+        int rc;
+        for (Use &us : uses) if ((rc = us.c->ensure_arena(s->device, &us.usable))) return rc;
+        std::vector<int32_t> use_of(nu, -1); std::vector<size_t> at(nu, 0);
+        for (size_t u = 0; u < nu; u++) {
+            if (!ow[u].c) continue;
+            const int32_t k = (int32_t)(std::lower_bound(cs.begin(), cs.end(), ow[u].c, std::less<mic_hip_tile_cache *>()) - cs.begin());
+            use_of[u] = k; at[u] = uses[(size_t)k].units.size();
+            uses[(size_t)k].units.push_back(u);
+            uses[(size_t)k].keys.push_back(SlotIndex::Key{ ow[u].owner, ow[u].first + plan.units[u].tile });
+        }
+        for (Use &us : uses) {
+            us.outcome.assign(us.keys.size(), SlotIndex::kBypass); us.slot.assign(us.keys.size(), SlotIndex::kNoSlot);
+            if (us.usable) us.c->index.plan(us.keys.data(), us.keys.size(), us.outcome.data(), us.slot.data());
+            else us.c->index.bypass_all(us.keys.size());
+            us.planned = true;
+        }
+        if (!uses.empty()) kind = uses[0].c->channels == 3 ? kGatherPxRGB : uses[0].c->bps == 16 ? kGatherPxU16 : kGatherPxU8;
+        // the plan in two
+        std::vector<size_t> dec_of(nu, ~(size_t)0);
+        fill_first.assign(1, 0);
+        for (size_t u = 0; u < nu; u++) {
+            const int32_t k = use_of[u];
+            const uint8_t oc = k < 0 ? (uint8_t)SlotIndex::kBypass : uses[(size_t)k].outcome[at[u]];
+            if (oc == SlotIndex::kHit) continue;
+            dec_of[u] = decode.units.size();
+            decode.units.push_back(plan.units[u]);
+            full_of.push_back(u);
+            kept.push_back(oc == SlotIndex::kMiss ? Kept{ k, uses[(size_t)k].slot[at[u]] } : Kept{ -1, SlotIndex::kNoSlot });
+            if (oc == SlotIndex::kMiss) {
+                const mic_hip_tile_cache *c = uses[(size_t)k].c;
+                fills.push_back(CacheFill{ 0, (uint64_t)(uintptr_t)c->arena + (uint64_t)kept.back().slot * c->slot_bytes, (uint32_t)((size_t)um[u]->tw * um[u]->th), 0 });
+            }
+            fill_first.push_back(fills.size());
+        }
+        for (const RectPiece &p : plan.pieces) {
+            const size_t u = p.unit;
+            const int32_t k = use_of[u];
+            const uint8_t oc = k < 0 ? (uint8_t)SlotIndex::kBypass : uses[(size_t)k].outcome[at[u]];
+            if (oc == SlotIndex::kBypass) { decode.pieces.push_back(p); decode.pieces.back().unit = (uint32_t)dec_of[u]; continue; }
+            Use &us = uses[(size_t)k];
+            const uint64_t bpp = um[u]->bpp();
+            const PieceDst pd = piece_dst(p, pw, ph, o);
+            us.pieces.push_back(GatherPiece{ (uint64_t)us.slot[at[u]] * us.c->slot_bytes + ((uint64_t)p.sy * (uint64_t)um[u]->tw + (uint64_t)p.sx) * bpp, pd.dst,
+                                             um[u]->tw, pd.dstride, p.w, p.h, 0, (int32_t)plan.units[u].slide });
+            us.mw = std::max(us.mw, p.w); us.mh = std::max(us.mh, p.h);
+        }
+        return MIC_OK;
+    }
+    // the call has its statuses (tile_status: per decode unit) and the stream is idle: a failed tile is not kept; the rest stands
+    void finish(const std::vector<int32_t> &tile_status) {
+        for (size_t d = 0; d < kept.size(); d++)
+            if (kept[d].use >= 0 && tile_status[d] != MIC_OK) {
+                Use &us = uses[(size_t)kept[d].use];
+                const size_t i = (size_t)(std::find(us.units.begin(), us.units.end(), full_of[d]) - us.units.begin());
+                us.c->index.release(us.keys[i]);
+            }
+        for (Use &us : uses) us.c->index.commit();
+        done = true;
+    }
+    ~CachePlan() {
+        if (done) return;
+        if (launched && s && s->stream) (void)hipStreamSynchronize(s->stream);             // (the slots are not let go while something may write them)
+        for (Use &us : uses) {
+            if (!us.planned) continue;
+            us.c->index.rollback();
+            for (uint32_t q : us.written) us.c->index.spoil(q);                             // (what a queued fill has overwritten is nobody's any more)
+        }
+    }
+};
+
 // The core of every patch call: the plan's pieces into d_out ([patch][ph][pw] pixels of the slides' format or of o's, an address s's
 // device can write: patch_pointer; what no piece covers is 0, or o's pad) on a session the caller holds.  um[u]: the header unit u's tile is coded
 // under (all of one sample format).  The skeleton is the one the strip and MIC2 crop readers run (mic_rects.h); here are the rule -- as
 // many tiles as `ceiling` allows of the largest, a tile P * tw * th samples of the slab -- and the decode (decode_plane_slab).
 // tile_status[u]: the source's code for the tile, else its first failing plane's; *nslab: sub-batches.
 int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int pw, int ph, const OutFormat &o, const SlabCeiling &ceiling,
-                 const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab) {
+                 const PatchSlabs &source, void *d_out, size_t need, std::vector<int32_t> &tile_status, uint64_t *nslab, CachePlan *cr = nullptr) {
     const size_t nu = plan.units.size();
     int rc;
     if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
     if ((rc = fill_pad(s->stream, o, d_out, need))) return rc;                              // outside the levels, refused slides and patches
     tile_status.assign(nu, MIC_OK);
     *nslab = 0;
-    if (nu == 0) { HIP_TRY(hipStreamSynchronize(s->stream)); return MIC_OK; }
-    const size_t P = (size_t)um[0]->planes();
-    const GatherKind kind = P == 3 ? kGatherRGB : um[0]->bps == 16 ? kGatherU16 : kGatherU8;
+    if (nu == 0 && !(cr && cr->cached_pieces())) { HIP_TRY(hipStreamSynchronize(s->stream)); if (cr) cr->finish(tile_status); return MIC_OK; }
+    const size_t P = nu ? (size_t)um[0]->planes() : 1;                                      // (cr: `plan` is what is left to decode, nothing when every tile hit)
+    const GatherKind kind = P == 3 ? kGatherRGB : (nu && um[0]->bps == 16) ? kGatherU16 : kGatherU8;
     std::vector<size_t> px(nu);
     for (size_t u = 0; u < nu; u++) px[u] = (size_t)um[u]->tw * um[u]->th;
     std::vector<std::pair<size_t, size_t>> caps;                                            // (tile size -> tiles a sub-batch holds: the ceiling is asked once per size)
@@ -855,7 +967,20 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
                                        [&](size_t u) { return P * px[u]; }, plan.pieces, pw, ph, [&](size_t u) { return UnitStride{ um[u]->tw, (int32_t)px[u] }; },
                                        [&](size_t u) { return plan.units[u].slide; }, o);
     if ((rc = s->wsi_planes.reserve(L.slab_max * 2 + 64))) return rc;
-    if ((rc = upload_gather(s, L, o))) return rc;
+    // with caches: behind the gather list lie the pieces of the cached tiles, cache by cache, and the fill records of the kept ones
+    const size_t behind = cr ? cr->behind_bytes() : 0;
+    if ((rc = upload_gather(s, L, o, behind))) return rc;
+    const GatherPiece *d_cached = (const GatherPiece *)((const char *)s->pieces.p + gather_bytes(L));
+    const CacheFill *d_fills = cr ? (const CacheFill *)(d_cached + cr->cached_pieces()) : nullptr;
+    if (cr) {
+        for (size_t d = 0; d < nu; d++) if (cr->kept[d].use >= 0) cr->fills[cr->fill_first[d]].src = L.slab_off[d];
+        const GatherPiece *at = d_cached;
+        for (const CachePlan::Use &us : cr->uses) {
+            if (!us.pieces.empty()) HIP_TRY(hipMemcpyAsync((void *)at, us.pieces.data(), us.pieces.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, s->stream));
+            at += us.pieces.size();
+        }
+        if (!cr->fills.empty()) HIP_TRY(hipMemcpyAsync((void *)d_fills, cr->fills.data(), cr->fills.size() * sizeof(CacheFill), hipMemcpyHostToDevice, s->stream));
+    }
     std::vector<WsiPlane> pl; std::vector<int32_t> pst;
     for (size_t b = 0; b < L.subs(); b++, ++*nslab) {
         const size_t u0 = L.cuts[b], nt = L.cuts[b + 1] - u0;
@@ -869,11 +994,34 @@ int read_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<co
             }, s->wsi_planes, L.slab_max, pst.data()))) return rc;
         for (size_t q = 0; q < nt * P; q++) if (tile_status[u0 + q / P] == MIC_OK) tile_status[u0 + q / P] = pst[q];
         s->timer.reset(s->stream);                                                          // (every unit has a piece; no more than 2^31 - 1 in all: plan_sort)
-        gather_units(s, "k_wsi_gather_patches", kind, s->wsi_planes.p, L, b, d_out, o, (size_t)ph * (size_t)pw);
+        if (cr && cr->fill_first[u0 + nt] > cr->fill_first[u0]) {                           // the kept tiles of this sub-batch into their slots
+            const size_t f0 = cr->fill_first[u0], nf = cr->fill_first[u0 + nt] - f0;
+            size_t max_px = 0;
+            for (size_t d = u0; d < u0 + nt; d++) if (cr->kept[d].use >= 0) { max_px = std::max(max_px, px[d]); cr->uses[(size_t)cr->kept[d].use].written.push_back(cr->kept[d].slot); }
+            cr->launched = true;
+            s->timer.mark("k_wsi_cache_fill");
+            launch_cache_fill(s->stream, cr->kind, (const uint16_t *)s->wsi_planes.p, d_fills + f0, nf, max_px);
+        }
+        gather_units(s, "k_wsi_gather_patches", kind, s->wsi_planes.p, L, b, d_out, o, (size_t)ph * (size_t)pw, behind);
         s->timer.mark("end");
         HIP_TRY(hipGetLastError());                                                         // (the next sub-batch follows on the stream; decode_plane_slab has waited for this one's bytes)
     }
+    if (cr && cr->cached_pieces()) {                                                        // hits and fresh tiles alike out of the arenas: one launch per cache
+        if (L.subs() == 0) s->timer.reset(s->stream);
+        const GatherPiece *at = d_cached;
+        s->timer.mark("k_wsi_gather_cached");
+        for (const CachePlan::Use &us : cr->uses) {
+            if (us.pieces.empty()) continue;
+            cr->launched = true;
+            launch_gather(s->stream, cr->kind, (const uint16_t *)us.c->arena, at, us.pieces.size(), us.mw, us.mh, d_out, o.dtype,
+                          o.params(out_table(s, L, behind), (size_t)ph * (size_t)pw));
+            at += us.pieces.size();
+        }
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (cr) cr->finish(tile_status);
     return MIC_OK;
 }
 
@@ -903,11 +1051,19 @@ PatchSlabs blob_slabs(mic_hip_session *s, const std::vector<const Mic3 *> &um, c
 // The plan of one level of `m` through the core.  status[i] (may be NULL): MIC_OK, or the first failing tile of patch i in tile
 // order, with the code mic_hip_wsi_decompress_tile has for it (the blob's, else its first failing plane's).
 int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<const Mic3 *> &um, int n, int pw, int ph, const OutFormat &o, const SlabCeiling &ceiling,
-                  const PatchSlabs &source, void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats) {
+                  const PatchSlabs &source, void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats,
+                  CachePlan *cr = nullptr, const PatchPlan *full = nullptr) {
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
-    const int rc = read_patches(s, plan, um, pw, ph, o, ceiling, source, d_out, need, tst, &nslab);
+    const int rc = read_patches(s, plan, um, pw, ph, o, ceiling, source, d_out, need, tst, &nslab, cr);
     if (rc) return rc;
+    if (cr) {                                                                               // plan: what was left to decode of *full; a hit is MIC_OK
+        std::vector<int32_t> all(full->units.size(), MIC_OK);
+        for (size_t d = 0; d < tst.size(); d++) all[cr->full_of[d]] = tst[d];
+        fold_unit_status(full->pieces, all, n, 1, status, nullptr, [](uint32_t) { return -1; });
+        if (stats) { stats->tiles_decoded = plan.units.size(); stats->pieces = full->pieces.size(); stats->slabs = nslab; }
+        return MIC_OK;
+    }
     fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
     if (stats) { stats->tiles_decoded = plan.units.size(); stats->pieces = plan.pieces.size(); stats->slabs = nslab; }
     return MIC_OK;
@@ -917,7 +1073,7 @@ int level_patches(mic_hip_session *s, const PatchPlan &plan, const std::vector<c
 // the union's tiles from `src` in ONE request (a reader then pulls those blobs only, contiguous ones in one read); a tile whose
 // index entry points outside the file fails the call with the source's code before anything is launched.
 int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const OutFormat &o, void *d_out, size_t need,
-                int32_t *status, mic_hip_patch_stats *stats) {
+                int32_t *status, mic_hip_patch_stats *stats, CacheOwner co = CacheOwner{ nullptr, 0, 0 }) {
     mic_hip_session *s = cur_default();
     const Level &L = m.lv[(size_t)level];
     int rc;
@@ -925,6 +1081,17 @@ int wsi_patches(const BlobSource &src, const Mic3 &m, int level, const int32_t *
     if (!out_aligned(o, d_out)) return MIC_ERR_ARGS;
     PatchPlan plan;
     if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
+    if (co.c) {                                                                             // the reader has a tile cache: only what is not resident is fetched and decoded
+        co.first = (uint64_t)L.first;
+        CachePlan cp;
+        if ((rc = cp.split(s, plan, std::vector<const Mic3 *>(plan.units.size(), &m), pw, ph, o, [&](size_t) { return co; }))) return rc;
+        std::vector<size_t> tiles(cp.decode.units.size());
+        for (size_t u = 0; u < tiles.size(); u++) tiles[u] = (size_t)L.first + (size_t)cp.decode.units[u].tile;
+        std::vector<TileBlob> blobs; std::vector<uint8_t> keep;
+        if (!tiles.empty() && (rc = src(tiles, blobs, keep))) return rc;
+        const std::vector<const Mic3 *> um(tiles.size(), &m);
+        return level_patches(s, cp.decode, um, n, pw, ph, o, blob_ceiling((size_t)m.planes()), blob_slabs(s, um, blobs), d_out, need, status, stats, &cp, &plan);
+    }
     std::vector<size_t> tiles(plan.units.size());
     for (size_t u = 0; u < tiles.size(); u++) tiles[u] = (size_t)L.first + (size_t)plan.units[u].tile;
     std::vector<TileBlob> blobs; std::vector<uint8_t> keep;
@@ -1015,7 +1182,8 @@ typedef std::function<int(uint32_t f, const std::vector<size_t> &tiles, std::vec
 
 // a door's call on a plan whose slides are set: arguments judged (multi_args), then the plan, n == 0, the pointer, the blobs, the core
 int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, int n, int pw, int ph, int channels, int bps, const OutFormat &o,
-               void *d_out, size_t need, int32_t *status, mic_hip_multi_patch_stats *stats) {
+               void *d_out, size_t need, int32_t *status, mic_hip_multi_patch_stats *stats,
+               const std::function<CacheOwner(uint32_t f)> &cache_of = nullptr) {
     int rc = multi_plan(plan, xysl, n, pw, ph, channels, bps);
     if (rc) return rc;
     if (stats) *stats = mic_hip_multi_patch_stats{ 0, 0, 0, 0 };
@@ -1026,16 +1194,29 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     mic_hip_session *s = cur_default();
     if ((rc = patch_pointer(s, &d_out, need))) return rc;                                   // judged before anything is launched
     if (o.typed() ? !out_aligned(o, d_out) : (bps == 16 && ((size_t)d_out & 1))) return MIC_ERR_ARGS;
-    const size_t nu = plan.units.size();
+    // readers with tile caches: what is resident is neither fetched nor decoded (dp: the units that are left)
+    std::unique_ptr<CachePlan> cp;
+    if (cache_of) {
+        bool any = false;
+        for (const PatchUnit &pu : plan.units) any = any || cache_of(pu.slide).c != nullptr;
+        if (any) {
+            std::vector<const Mic3 *> um_all(plan.units.size());
+            for (size_t u = 0; u < um_all.size(); u++) um_all[u] = &plan.slides[plan.units[u].slide].hdr();
+            cp.reset(new CachePlan());
+            if ((rc = cp->split(s, plan, um_all, pw, ph, o, [&](size_t u) { return cache_of(plan.units[u].slide); }))) return rc;
+        }
+    }
+    const PatchPlan &dp = cp ? cp->decode : (const PatchPlan &)plan;
+    const size_t nu = dp.units.size();
     std::vector<TileBlob> blobs; blobs.reserve(nu);
     std::vector<const Mic3 *> um(nu);
     std::vector<std::vector<uint8_t>> keep;
     std::vector<size_t> tiles;
     for (size_t u = 0; u < nu;) {                                                           // each slide's blobs in one request
-        const uint32_t f = plan.units[u].slide;
+        const uint32_t f = dp.units[u].slide;
         size_t v = u;
         tiles.clear();
-        for (; v < nu && plan.units[v].slide == f; v++) { tiles.push_back((size_t)plan.units[v].tile); um[v] = &plan.slides[f].hdr(); }
+        for (; v < nu && dp.units[v].slide == f; v++) { tiles.push_back((size_t)dp.units[v].tile); um[v] = &plan.slides[f].hdr(); }
         if (fetch) {
             std::vector<TileBlob> got;
             keep.emplace_back();
@@ -1053,7 +1234,12 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
     }
     std::vector<int32_t> tst;
     uint64_t nslab = 0;
-    if ((rc = read_patches(s, plan, um, pw, ph, o, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab))) return rc;
+    if ((rc = read_patches(s, dp, um, pw, ph, o, blob_ceiling(channels == 3 ? 3 : 1), blob_slabs(s, um, blobs), d_out, need, tst, &nslab, cp.get()))) return rc;
+    if (cp) {                                                                               // (a hit is MIC_OK)
+        std::vector<int32_t> all(plan.units.size(), MIC_OK);
+        for (size_t d = 0; d < tst.size(); d++) all[cp->full_of[d]] = tst[d];
+        tst.swap(all);
+    }
     fold_unit_status(plan.pieces, tst, n, 1, status, nullptr, [](uint32_t) { return -1; });
     container_codes(n, status, [&](int i) {                                                 // a refused slide's code; a level the slide does not have
         const MultiSlide &sl = plan.slides[(size_t)xysl[4 * (size_t)i + 2]]; const int32_t level = xysl[4 * (size_t)i + 3];
@@ -1390,6 +1576,11 @@ int mic_hip_session_wsi_encode(mic_hip_session *s, const uint8_t *d_pixels, int 
     if ((rc = s->activate())) return rc;
     if ((rc = s->ensure(1, (size_t)fmt.tw * fmt.th))) return rc;
     if (!s->wsi) s->wsi = new mic_hip_wsi_store();
+    if (s->tile_cache) {                                                                    // the store is replaced: its tiles in the cache are the old slide's
+        mic_hip_tile_cache *c = s->tile_cache;
+        if (c->tw != fmt.tw || c->th != fmt.th || c->channels != fmt.channels || c->bps != fmt.bps) { c->detach(s->tile_owner); s->tile_cache = nullptr; }
+        else { std::lock_guard<std::mutex> lk(c->mu); c->index.drop_owner(s->tile_owner); s->tile_owner = tile_cache_new_owner(); }
+    }
     mic_hip_wsi_store &W = *s->wsi;
     W.fmt = fmt; W.lv = plan_levels(width, height, fmt.tw, fmt.th, levels);
     W.fmt.nlev = (int)W.lv.size();
@@ -1516,16 +1707,48 @@ int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int
     const size_t P = (size_t)m.planes();
     PatchPlan plan;
     if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
+    // the records of units [u0, u0 + nt) of `dp`: the plan, or what a tile cache has left of it to decode
+    auto records = [&](const PatchPlan &dp) {
+        return [&, P](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
+            for (size_t k = 0; k < nt; k++) {
+                const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)dp.units[u0 + k].tile) * P;
+                pl.insert(pl.end(), rec, rec + P);
+            }
+            *base = (const uint8_t *)W.bytes.p;
+            return MIC_OK;
+        };
+    };
+    if (s->tile_cache) {
+        CachePlan cp;
+        const CacheOwner co{ s->tile_cache, s->tile_owner, (uint64_t)L.first };
+        if ((rc = cp.split(s, plan, std::vector<const Mic3 *>(plan.units.size(), &m), pw, ph, o, [&](size_t) { return co; }))) return rc;
+        const std::vector<const Mic3 *> um(cp.decode.units.size(), &m);
+        return level_patches(s, cp.decode, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); }, records(cp.decode), d_out, need, status, stats, &cp, &plan);
+    }
     const std::vector<const Mic3 *> um(plan.units.size(), &m);
-    return level_patches(s, plan, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); },
-                         [&](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
-        for (size_t k = 0; k < nt; k++) {
-            const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)plan.units[u0 + k].tile) * P;
-            pl.insert(pl.end(), rec, rec + P);
-        }
-        *base = (const uint8_t *)W.bytes.p;
-        return MIC_OK;
-    }, d_out, need, status, stats);
+    return level_patches(s, plan, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); }, records(plan), d_out, need, status, stats);
+} MIC_ABI_CATCH
+
+int mic_hip_session_set_tile_cache(mic_hip_session *s, mic_hip_tile_cache *c) try {
+    if (!s) return MIC_ERR_ARGS;
+    if (c == s->tile_cache) return MIC_OK;
+    if (c && s->wsi) {
+        const Mic3 &f = s->wsi->fmt;
+        if (c->tw != f.tw || c->th != f.th || c->channels != f.channels || c->bps != f.bps) return MIC_ERR_ARGS;
+    }
+    if (s->tile_cache) s->tile_cache->detach(s->tile_owner);
+    s->tile_cache = c;
+    if (c) { std::lock_guard<std::mutex> lk(c->mu); c->attached++; s->tile_owner = tile_cache_new_owner(); }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_session_tile_cache_probe(mic_hip_session *s, const uint64_t *tiles, size_t n, uint8_t *resident) try {
+    if (!s || (n && (!tiles || !resident))) return MIC_ERR_ARGS;
+    mic_hip_tile_cache *c = s->tile_cache;
+    if (!c) { for (size_t i = 0; i < n; i++) resident[i] = 0; return MIC_OK; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (size_t i = 0; i < n; i++) resident[i] = c->index.has(SlotIndex::Key{ s->tile_owner, tiles[i] }) ? 1 : 0;
+    return MIC_OK;
 } MIC_ABI_CATCH
 int mic_hip_session_wsi_read_patches(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
@@ -1739,6 +1962,7 @@ struct mic_hip_wsi_reader {
     uint64_t file_len = 0;
     Mic3 m;
     std::vector<uint8_t> head;              // header, level table, tile index
+    mic_hip_tile_cache *cache = nullptr; uint64_t owner = 0;   // mic_hip_wsi_reader_set_cache (guarded by mu): the patch calls' tile cache and this reader's owner number in it
     // the blobs of `tiles` through the callback: every entry checked against file_len first, then one read per run of contiguous blobs
     int fetch(const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
         std::vector<uint64_t> off(tiles.size()), len(tiles.size());
@@ -1938,8 +2162,30 @@ int mic_hip_wsi_reader_read_patches_as(mic_hip_wsi_reader *r, int level, const i
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
-    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, o, d_out, need, status, stats);
+    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, o, d_out, need, status, stats, CacheOwner{ r->cache, r->owner, 0 });
 } MIC_ABI_CATCH
+
+int mic_hip_wsi_reader_set_cache(mic_hip_wsi_reader *r, mic_hip_tile_cache *c) try {
+    if (!r) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (c == r->cache) return MIC_OK;
+    if (c && (!r->m.supported() || c->tw != r->m.tw || c->th != r->m.th || c->channels != r->m.channels || c->bps != r->m.bps)) return MIC_ERR_ARGS;
+    if (r->cache) r->cache->detach(r->owner);
+    r->cache = c;
+    if (c) { std::lock_guard<std::mutex> lc(c->mu); c->attached++; r->owner = tile_cache_new_owner(); }
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_wsi_reader_cache_probe(mic_hip_wsi_reader *r, const uint64_t *tiles, size_t n, uint8_t *resident) try {
+    if (!r || (n && (!tiles || !resident))) return MIC_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(r->mu);
+    mic_hip_tile_cache *c = r->cache;
+    if (!c) { for (size_t i = 0; i < n; i++) resident[i] = 0; return MIC_OK; }
+    std::lock_guard<std::mutex> lc(c->mu);
+    for (size_t i = 0; i < n; i++) resident[i] = c->index.has(SlotIndex::Key{ r->owner, tiles[i] }) ? 1 : 0;
+    return MIC_OK;
+} MIC_ABI_CATCH
+
 int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
                                     void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
     return mic_hip_wsi_reader_read_patches_as(r, level, xy, n, pw, ph, d_out, out_cap, status, stats, nullptr);
@@ -1975,7 +2221,8 @@ int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int 
     }
     return multi_call(plan, [&](uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
         return readers[f]->fetch(tiles, blobs, keep);
-    }, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats);
+    }, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats,
+    [&](uint32_t f) { return CacheOwner{ readers[f]->cache, readers[f]->owner, 0 }; });     // (each reader its own cache, shared, or none; a unit's reader is one of `named`)
 } MIC_ABI_CATCH
 int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
@@ -1983,6 +2230,9 @@ int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nre
     return mic_hip_wsi_readers_read_patches_as(readers, nreaders, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, nullptr);
 }
 
-void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) { delete r; }
+void mic_hip_wsi_reader_close(mic_hip_wsi_reader *r) {
+    if (r && r->cache) r->cache->detach(r->owner);                                          // (its entries go with it)
+    delete r;
+}
 
 }  // extern "C"

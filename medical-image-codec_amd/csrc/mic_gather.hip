@@ -3,12 +3,14 @@
 // units in sub-batches into a slab and copies the pieces, the (rectangle, unit) overlaps, out of the slab into the output tensor.
 // Here: the kernels that copy and their launcher, the judgement of the output pointer, the crop doors' way to a session, and the
 // packing of a sub-batch's streams; and the typed output of the _as doors (mic_hip_out_spec): its one judgement, the typed gather
-// kernels, the pad fill and the convert kernel of the MIC2 temporal staging tensor.
+// kernels, the pad fill and the convert kernel of the MIC2 temporal staging tensor; and the kernels of the MIC3 tile cache
+// (mic_tile_cache.h): the fill of freshly decoded tiles into pixel slots and the gathers that read pieces out of them.
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
 #include <cmath>
 #include "mic_session.h"
 #include "mic_pieces.h"
+#include "mic_px_copy.h"
 
 namespace {
 
@@ -34,7 +36,18 @@ __global__ void __launch_bounds__(256) k_gather_pieces(const uint16_t *slab, con
     }
 }
 
-// ---- the RGB gathers: the planes a piece's pixels come from, one row loop, the pixel's arithmetic ---------------------------------
+// ---- the RGB gathers: the pixel's arithmetic, the planes a piece's pixels come from, one row loop ---------------------------------
+// UnZigZag of Co and Cg (deltazigzagcompressu16.go:113-116) and YCoCgRInverse (asm_amd64.go:106-121), as k_wsi_planes_to_rgb does
+// them: the pixel every RGB gather writes (its channels' low bytes)
+struct RgbPx { int r, g, b; };
+__device__ __forceinline__ RgbPx ycocg_rgb(int yv, uint32_t uco, uint32_t ucg) {
+    const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));
+    const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
+    const int t = yv - (cg >> 1);
+    const int g = cg + t;
+    const int b = t - (co >> 1);
+    return RgbPx{ co + b, g, b };
+}
 // The three planes of a piece in a slab of whole units: the piece in plane 0, the other two pstride samples on each.
 struct SlabPlanes {
     mic_gp<const uint16_t> py, pco, pcg;
@@ -42,6 +55,7 @@ struct SlabPlanes {
     __device__ __forceinline__ uint32_t y(size_t i) const { return py[i]; }
     __device__ __forceinline__ uint32_t co(size_t i) const { return pco[i]; }
     __device__ __forceinline__ uint32_t cg(size_t i) const { return pcg[i]; }
+    __device__ __forceinline__ RgbPx px(size_t i) const { return ycocg_rgb((int)y(i), co(i), cg(i)); }
 };
 // The three planes of a piece by its record (RgbPlaneSrc): each the decoded plane in the slab, a constant, or the blob's raw samples
 // in `raw` -- little-endian at any byte address (a Y plane's always start at an odd one), two byte loads a sample as k_rgb_batch_fill
@@ -65,18 +79,15 @@ struct ModePlanes {
     __device__ __forceinline__ uint32_t y(size_t i) const { return sample(p[0], i); }
     __device__ __forceinline__ uint32_t co(size_t i) const { return sample(p[1], i); }
     __device__ __forceinline__ uint32_t cg(size_t i) const { return sample(p[2], i); }
+    __device__ __forceinline__ RgbPx px(size_t i) const { return ycocg_rgb((int)y(i), co(i), cg(i)); }
 };
-// UnZigZag of Co and Cg (deltazigzagcompressu16.go:113-116) and YCoCgRInverse (asm_amd64.go:106-121), as k_wsi_planes_to_rgb does
-// them: the pixel every RGB gather writes (its channels' low bytes)
-struct RgbPx { int r, g, b; };
-__device__ __forceinline__ RgbPx ycocg_rgb(int yv, uint32_t uco, uint32_t ucg) {
-    const int co = (int)(int16_t)((uco >> 1) ^ (uint16_t)(-(int)(uco & 1)));
-    const int cg = (int)(int16_t)((ucg >> 1) ^ (uint16_t)(-(int)(ucg & 1)));
-    const int t = yv - (cg >> 1);
-    const int g = cg + t;
-    const int b = t - (co >> 1);
-    return RgbPx{ co + b, g, b };
-}
+// The pixels of a piece in a slot of the tile cache: interleaved RGB bytes, the inverse transform done when the slot was filled.
+// pc.src: BYTES from the arena's start to the piece's first pixel; rows sstride pixels apart.
+struct SlotPixels {
+    mic_gp<const uint8_t> p;
+    __device__ __forceinline__ SlotPixels(const uint8_t *arena, const GatherPiece &pc) : p(mic_g(arena + pc.src)) {}
+    __device__ __forceinline__ RgbPx px(size_t i) const { return RgbPx{ p[3 * i], p[3 * i + 1], p[3 * i + 2] }; }
+};
 // The piece's pixels through put(d, pixel), d = y * dstride + x * px samples from the piece's place in the tensor.  Lanes along x of
 // a piece row: a wave reads 64 neighbouring samples of each plane and writes 64 neighbouring pixels.
 template <class Planes, class Put>
@@ -84,7 +95,7 @@ __device__ __forceinline__ void gather_rgb_rows(const GatherPiece &pc, const Pla
     const PieceLanes ln = piece_lanes(pc.w);
     for (int y = ln.row; y < pc.h; y += ln.rstep) {
         const size_t si = (size_t)y * pc.sstride, di = (size_t)y * dstride;
-        for (int x = ln.col; x < pc.w; x += ln.lw) put(di + (size_t)x * px, ycocg_rgb((int)pl.y(si + x), pl.co(si + x), pl.cg(si + x)));
+        for (int x = ln.col; x < pc.w; x += ln.lw) put(di + (size_t)x * px, pl.px(si + x));
     }
 }
 // out: u8, three a pixel: three byte stores per pixel at whatever byte offset the tensor's row has, 192 neighbouring bytes a wave
@@ -129,8 +140,8 @@ template <int DT> __device__ __forceinline__ typename OutBits<DT>::type out_samp
 // A row of w one-plane samples as DT: the lanes of piece_lanes.  2-byte outputs keep the native kernel's trick: a row whose
 // destination is 4-byte aligned stores packed pairs as dwords (the odd sample behind them as one 2-byte store), any other row
 // 2-byte samples; f32 is one dword per lane.
-template <int DT>
-__device__ __forceinline__ void typed_row(mic_gp<const uint16_t> s, mic_gp<typename OutBits<DT>::type> d, int w, const PieceLanes &ln, Pair ab, const OutParams &o) {
+template <int DT, typename S = uint16_t>
+__device__ __forceinline__ void typed_row(mic_gp<const S> s, mic_gp<typename OutBits<DT>::type> d, int w, const PieceLanes &ln, Pair ab, const OutParams &o) {
     typedef typename OutBits<DT>::type T;
     if (sizeof(T) == 2 && ((size_t)d & 3) == 0) {
         const mic_gp<uint32_t> d2 = (mic_gp<uint32_t>)d;
@@ -178,6 +189,54 @@ __global__ void __launch_bounds__(256) k_gather_typed_modes_rgb(const uint16_t *
                                                                 typename OutBits<DT>::type *out, const OutParams o) {
     const GatherPiece pc = pieces[blockIdx.x];
     gather_rgb_typed<DT>(pc, ModePlanes(slab, raw, srcs[blockIdx.x]), out, o);
+}
+
+// ---- gathers out of pixel slots (the MIC3 tile cache, mic_tile_cache.h) -----------------------------------------------------------
+// A slot holds a decoded tile as pixels of the slide's sample format, so a piece's src is a BYTE offset into the arena, its rows
+// sstride pixels apart; dst and dstride count as in the slab kernels.  Native output is then a copy of w * BPP bytes per row at any
+// byte alignment on both sides (mic_px_copy.h); typed output runs the arithmetic of the slab kernels on the slot's samples.
+template <int BPP>
+__global__ void __launch_bounds__(256) k_gather_px(const uint8_t *arena, const GatherPiece *pieces, uint8_t *out) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    const int nb = pc.w * BPP;
+    const PieceLanes ln = px_row_lanes(nb);
+    const uint8_t *src = arena + pc.src;
+    uint8_t *dst = out + pc.dst * BPP;
+    for (int y = ln.row; y < pc.h; y += ln.rstep)
+        px_row_dwords(mic_g(src + (size_t)y * pc.sstride * BPP), mic_g(dst + (size_t)y * pc.dstride * BPP), nb, ln);
+}
+// one plane of S samples (u8 or u16) to a typed tensor: k_gather_typed on a slot
+template <int DT, typename S>
+__global__ void __launch_bounds__(256) k_gather_px_typed(const uint8_t *arena, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    const PieceLanes ln = piece_lanes(pc.w);
+    const Pair ab = out_pair(o, (size_t)pc.source * o.src_mul);
+    const S *src = (const S *)(arena + pc.src);
+    typename OutBits<DT>::type *dst = out + pc.dst;
+    for (int y = ln.row; y < pc.h; y += ln.rstep)
+        typed_row<DT, S>(mic_g(src + (size_t)y * pc.sstride), mic_g(dst + (size_t)y * pc.dstride), pc.w, ln, ab, o);
+}
+// interleaved RGB bytes to a typed tensor: k_gather_typed_rgb on a slot
+template <int DT>
+__global__ void __launch_bounds__(256) k_gather_px_typed_rgb(const uint8_t *arena, const GatherPiece *pieces, typename OutBits<DT>::type *out, const OutParams o) {
+    const GatherPiece pc = pieces[blockIdx.x];
+    gather_rgb_typed<DT>(pc, SlotPixels(arena, pc), out, o);
+}
+
+// The planes of freshly decoded tiles into their slots, once, at insertion: tile blockIdx.x's npx pixels from its planes in the slab
+// (src samples in, the RGB planes npx apart) to dst, the slot's device address.  P3: the YCoCg-R inverse of k_wsi_planes_to_rgb;
+// else uint16ToBytes (T = u8) or the samples as they are (T = u16).  grid = (tiles, chunks).
+template <typename T, bool P3>
+__global__ void __launch_bounds__(256) k_cache_fill(const uint16_t *slab, const CacheFill *fills) {
+    const CacheFill f = fills[blockIdx.x];
+    const mic_gp<const uint16_t> p0 = mic_g(slab + f.src);
+    const mic_gp<T> d = mic_g((T *)(uintptr_t)f.dst);
+    for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < f.npx; i += gridDim.y * 256) {
+        if (P3) {
+            const RgbPx v = ycocg_rgb((int)p0[i], p0[(size_t)f.npx + i], p0[2 * (size_t)f.npx + i]);
+            d[3 * (size_t)i] = (T)v.r; d[3 * (size_t)i + 1] = (T)v.g; d[3 * (size_t)i + 2] = (T)v.b;
+        } else d[i] = (T)p0[i];
+    }
 }
 
 // MIC2 temporal volumes: run = a crop's footprint, w x h samples of d slices from `at` of the u16 staging tensor (slices of ch x cw)
@@ -294,7 +353,29 @@ void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, co
         const dim3 grid((unsigned)std::min(np - q, kMaxGridX), gy), block(256);
         const GatherPiece *pq = pieces + q;
         const RgbPlaneSrc *sq = modes.srcs + q;
-        if (kind == kGatherRGBModes) switch (dtype) {
+        const uint8_t *arena = (const uint8_t *)slab;
+        if (kind == kGatherPxRGB) switch (dtype) {
+            case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL(k_gather_px<3>, grid, block, 0, stream, arena, pq, (uint8_t *)out); break;
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_gather_px_typed_rgb<MIC_HIP_OUT_U8>, grid, block, 0, stream, arena, pq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_gather_px_typed_rgb<MIC_HIP_OUT_U16>, grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL(k_gather_px_typed_rgb<MIC_HIP_OUT_F16>, grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_gather_px_typed_rgb<MIC_HIP_OUT_BF16>, grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL(k_gather_px_typed_rgb<MIC_HIP_OUT_F32>, grid, block, 0, stream, arena, pq, (uint32_t *)out, op); break;
+        } else if (kind == kGatherPxU16) switch (dtype) {
+            case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL(k_gather_px<2>, grid, block, 0, stream, arena, pq, (uint8_t *)out); break;
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_U8, uint16_t>), grid, block, 0, stream, arena, pq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_U16, uint16_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_F16, uint16_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_BF16, uint16_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_F32, uint16_t>), grid, block, 0, stream, arena, pq, (uint32_t *)out, op); break;
+        } else if (kind == kGatherPxU8) switch (dtype) {
+            case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL(k_gather_px<1>, grid, block, 0, stream, arena, pq, (uint8_t *)out); break;
+            case MIC_HIP_OUT_U8: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_U8, uint8_t>), grid, block, 0, stream, arena, pq, (uint8_t *)out, op); break;
+            case MIC_HIP_OUT_U16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_U16, uint8_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_F16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_F16, uint8_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            case MIC_HIP_OUT_BF16: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_BF16, uint8_t>), grid, block, 0, stream, arena, pq, (uint16_t *)out, op); break;
+            default: hipLaunchKernelGGL((k_gather_px_typed<MIC_HIP_OUT_F32, uint8_t>), grid, block, 0, stream, arena, pq, (uint32_t *)out, op); break;
+        } else if (kind == kGatherRGBModes) switch (dtype) {
             case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL(k_gather_modes_rgb, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint8_t *)out); break;
             case MIC_HIP_OUT_U8: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_U8>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint8_t *)out, op); break;
             case MIC_HIP_OUT_U16: hipLaunchKernelGGL(k_gather_typed_modes_rgb<MIC_HIP_OUT_U16>, grid, block, 0, stream, slab, modes.raw, pq, sq, (uint16_t *)out, op); break;
@@ -318,6 +399,17 @@ void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, co
             case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_BF16>, grid, block, 0, stream, slab, pq, (uint16_t *)out, op); break;
             default: hipLaunchKernelGGL(k_gather_typed<MIC_HIP_OUT_F32>, grid, block, 0, stream, slab, pq, (uint32_t *)out, op); break;
         }
+    }
+}
+
+void launch_cache_fill(hipStream_t stream, GatherKind kind, const uint16_t *slab, const CacheFill *fills, size_t n, size_t max_px) {
+    constexpr size_t kMaxGridX = 0x7FFFFFFF;
+    const unsigned gy = (unsigned)std::min<size_t>(32, std::max<size_t>(1, (max_px + 2047) / 2048));   // (eight pixels a lane at least)
+    for (size_t q = 0; q < n; q += kMaxGridX) {
+        const dim3 grid((unsigned)std::min(n - q, kMaxGridX), gy), block(256);
+        if (kind == kGatherPxRGB) hipLaunchKernelGGL((k_cache_fill<uint8_t, true>), grid, block, 0, stream, slab, fills + q);
+        else if (kind == kGatherPxU16) hipLaunchKernelGGL((k_cache_fill<uint16_t, false>), grid, block, 0, stream, slab, fills + q);
+        else hipLaunchKernelGGL((k_cache_fill<uint8_t, false>), grid, block, 0, stream, slab, fills + q);
     }
 }
 

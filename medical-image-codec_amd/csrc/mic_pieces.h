@@ -31,7 +31,12 @@ inline unsigned row_chunks(int w, int h) {
 // depth x rows x columns passes 2^31); the kernels multiply nothing but y * stride.
 // source: the rectangle's source as the multi doors index it (slide, volume, strip file; 0 in the one-source doors), which only the
 // typed kernels read, to pick the affine pair.
+// A piece of a tile the MIC3 tile cache holds (the kGatherPx kinds) has its source in a pixel slot instead: src is then a BYTE
+// offset into the cache's arena -- slot * slot bytes + the overlap's first pixel --, sstride the tile's width in pixels, pstride unused.
 struct GatherPiece { uint64_t src, dst; int32_t sstride, dstride, w, h, pstride, source; };
+// A freshly decoded tile on its way into a slot of the tile cache: its planes src samples into the slab (npx each, back to back),
+// the slot at device address dst.
+struct CacheFill { uint64_t src, dst; uint32_t npx, pad; };
 
 // Where the mode-aware RGB gather (RGB file crops: mic_rgb_crops.hip) finds the three planes of piece q: record q of the reader's
 // own records, which lie behind the gather list.  A plane is the decoded one in the slab (at: samples from the slab's start to the
@@ -76,7 +81,8 @@ void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table,
                     int mw, int mh, int md, int cw, int ch, void *out);
 // what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), three YCoCg-R planes' RGB bytes, or the same
 // from planes of three kinds (RgbPlaneSrc)
-enum GatherKind { kGatherU16, kGatherU8, kGatherRGB, kGatherRGBModes };
+// ; or, out of pixel slots of the tile cache (`slab` is then the arena): u8, u16 or interleaved RGB pixels as they are
+enum GatherKind { kGatherU16, kGatherU8, kGatherRGB, kGatherRGBModes, kGatherPxU8, kGatherPxU16, kGatherPxRGB };
 // what kGatherRGBModes reads beside the slab: the buffer the raw planes lie in and the pieces' records (device; record q is piece q's)
 struct RgbModeArgs { const uint8_t *raw; const RgbPlaneSrc *srcs; };
 // np pieces (device) of a slab -> out, behind what `stream` holds; mw x mh: the largest of them.  The one place that picks the
@@ -85,6 +91,9 @@ struct RgbModeArgs { const uint8_t *raw; const RgbPlaneSrc *srcs; };
 // modes: what kGatherRGBModes reads further, cut over the launches with the pieces.
 void launch_gather(hipStream_t stream, GatherKind kind, const uint16_t *slab, const GatherPiece *pieces, size_t np, int mw, int mh, void *out,
                    int dtype = 0, const OutParams &op = OutParams{ nullptr, 0, 0, 0, 0, 0, 1 }, const RgbModeArgs &modes = RgbModeArgs{ nullptr, nullptr });
+// n freshly decoded tiles (device records) of a slab into their slots, in one launch behind what `stream` holds; kind: the kGatherPx
+// kind of the cache's pixels; max_px: the largest tile's pixels
+void launch_cache_fill(hipStream_t stream, GatherKind kind, const uint16_t *slab, const CacheFill *fills, size_t n, size_t max_px);
 // d_out of the patch and crop calls must be memory the session's device can write `need` bytes of: an allocation of that device, or
 // pinned host memory (mic_hip_host_alloc, hipHostMalloc / hipHostRegister).  Asked of the runtime before anything is launched;
 // *d_out becomes the address the device uses.

@@ -29,7 +29,15 @@ struct RectBatches {
     std::vector<size_t> cuts{ 0 }, first; std::vector<uint64_t> slab_off; size_t slab_max = 0;
     std::vector<GatherPiece> list; std::vector<int> mw, mh;  size_t subs() const { return cuts.size() - 1; }
 };
-struct UnitStride { int32_t row, plane; };            // samples between a unit's rows in the slab, and between its planes (RGB tiles; else 0)
+// A piece's place in a tensor of rectangles of ch x cw laid out as o says, and the samples between its rows there: a typed RGB tensor
+// counts in samples, not pixels -- interleaved, three a pixel; channels first, three planes of ch x cw a rectangle and the place the
+// one in plane 0.  Multiplied out in 64 bits.
+struct PieceDst { uint64_t dst; int32_t dstride; };
+inline PieceDst piece_dst(const RectPiece &p, int cw, int ch, const OutFormat &o) {
+    const uint64_t per_px = o.typed() && !o.planar() ? (uint64_t)o.channels : 1, per_rect = o.planar() ? (uint64_t)o.channels : 1;
+    return PieceDst{ (((uint64_t)p.rect * per_rect * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx) * per_px, (int32_t)(cw * (int)per_px) };
+}
+struct UnitStride { int32_t row, plane; };          // samples between a unit's rows in the slab, and between its planes (RGB tiles; else 0)
 // nu units: next(i0) ends the sub-batch that starts at i0 (next_sub_batch under the reader's rule); samples(u) is what unit u takes of
 // the slab (P planes of a tile, a strip, a frame; 0: not decoded into it).  A piece's two places are multiplied out in 64 bits.
 // source(u): the source unit u belongs to, which a piece carries to the typed kernels.  o: the tensor's layout -- a typed RGB tensor
@@ -38,7 +46,6 @@ struct UnitStride { int32_t row, plane; };            // samples between a unit'
 template <class Next, class Samples, class Stride, class Source>
 RectBatches rect_batches(size_t nu, Next &&next, Samples &&samples, const std::vector<RectPiece> &pieces, int cw, int ch, Stride &&stride,
                          Source &&source, const OutFormat &o) {
-    const uint64_t per_px = o.typed() && !o.planar() ? (uint64_t)o.channels : 1, per_rect = o.planar() ? (uint64_t)o.channels : 1;
     RectBatches B;
     B.slab_off.resize(nu); B.first.assign(nu + 1, 0); B.list.resize(pieces.size());
     while (B.cuts.back() < nu) {
@@ -53,9 +60,9 @@ RectBatches rect_batches(size_t nu, Next &&next, Samples &&samples, const std::v
         const RectPiece &p = pieces[q];
         while (p.unit >= B.cuts[b + 1]) b++;
         const UnitStride st = stride((size_t)p.unit);
-        B.list[q] = GatherPiece{ B.slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)st.row + (uint64_t)p.sx,
-                                 (((uint64_t)p.rect * per_rect * (uint64_t)ch + (uint64_t)p.dy) * (uint64_t)cw + (uint64_t)p.dx) * per_px, st.row,
-                                 (int32_t)(cw * (int)per_px), p.w, p.h, st.plane, (int32_t)source((size_t)p.unit) };
+        const PieceDst pd = piece_dst(p, cw, ch, o);
+        B.list[q] = GatherPiece{ B.slab_off[p.unit] + (uint64_t)p.sy * (uint64_t)st.row + (uint64_t)p.sx, pd.dst, st.row,
+                                 pd.dstride, p.w, p.h, st.plane, (int32_t)source((size_t)p.unit) };
         B.first[(size_t)p.unit + 1]++;
         B.mw[b] = std::max(B.mw[b], p.w); B.mh[b] = std::max(B.mh[b], p.h);
     }

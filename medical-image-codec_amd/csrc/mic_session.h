@@ -149,6 +149,8 @@ using namespace micapi;
 
 struct mic_hip_wsi_store;                       // MIC3 store of a device-resident slide (mic_api_ext.hip)
 void mic_wsi_store_free(mic_hip_wsi_store *w);
+struct mic_hip_tile_cache;                      // MIC3 tile cache (mic_tile_cache.h)
+void mic_tile_cache_detach(mic_hip_tile_cache *c, uint64_t owner);
 
 struct mic_hip_session {
     int device = 0;                         // the HIP device this session's stream and workspace live on (mic_hip_session_create_on)
@@ -175,6 +177,7 @@ struct mic_hip_session {
     struct WvTabHeld { std::vector<uint8_t> key; std::vector<uint32_t> spans; uint64_t gen = ~0ull; } wv_tab_held[2];   // ... and what each holds: the frame records it was built from, its work lists, the allocation
     mic_hip_wsi_store *wsi = nullptr;      // mic_hip_session_wsi_*: coded planes of a slide, on the device
     DevBuf wsi_planes, wsi_stats, wsi_payload, wsi_recs; std::vector<DevBuf> wsi_pyr;
+    mic_hip_tile_cache *tile_cache = nullptr; uint64_t tile_owner = 0;   // mic_hip_session_set_tile_cache: the cache of decoded tiles the store's patch calls use, and the store generation's owner number in it
     DevBuf pieces;                         // patch and crop calls: the call's piece list (GatherPiece, mic_pieces.h; MIC2 temporal: its footprints)
     DevBuf crop_stage;                     // MIC2 crops into a typed tensor: the u16 tensor the temporal volumes' running sums live in (mic_mic2_crops.hip)
     DevBuf wsi_fills;                      // MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
@@ -349,6 +352,7 @@ public:
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
         if (wsi) { mic_wsi_store_free(wsi); wsi = nullptr; }
+        if (tile_cache) { mic_tile_cache_detach(tile_cache, tile_owner); tile_cache = nullptr; }
         h_units.release(); pin_off.release(); pica_pin[0].release(); pica_pin[1].release(); rgb_pin.release();
         readback_queued = pack_queued = false;
         if (stream) (void)hipStreamDestroy(stream);
