@@ -252,7 +252,8 @@ int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs);
 /* Replaces CompressParallelStripsAdaptive (parallelstripsadaptive.go:54): strip boundaries by equal-cost partition of the rows'
  * summed |vertical delta| (adaptiveStripBoundaries, :222-289, float64 like the reference), every strip coded with both the avg
  * and the gradient-adaptive predictor (CompressSingleFrame / CompressSingleFrameGrad, two-state FSE) and the smaller kept, ties to
- * the gradient one (:97-105).  num_strips must be given (the reference's default is GOMAXPROCS). */
+ * the gradient one (:97-105).  num_strips must be given (the reference's default is GOMAXPROCS).  Either predictor is kept at any
+ * width: mic_hip_pica_decompress reads gradient strips wider than 32768 columns too (see MIC_HIP_PRED_GRAD). */
 int mic_hip_pica_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips,
                           uint8_t *out, size_t out_cap, size_t *out_len);
 /* The same with the index of the strip the error belongs to (the reference wraps it: "pica: strip %d: %w",
@@ -871,7 +872,10 @@ typedef struct mic_hip_unit {
 } mic_hip_unit;
 /* OR'ed into mic_hip_unit.nstates: the unit uses the gradient-adaptive predictor of CompressSingleFrameGrad /
  * DecompressSingleFrameGrad (multiframecompress.go:111-142, deltagradrlecompressu16.go) instead of avg(left, top).  The
- * stream does not record its predictor (PICA keeps it in the strip's flags word), so decode units must carry it too. */
+ * stream does not record its predictor (PICA keeps it in the strip's flags word), so decode units must carry it too.
+ * Width: like the reference, no limit of its own (a unit's pixel count is bounded as for every unit).  Up to 32768 columns the
+ * decoder hands rows from band to band through LDS; wider units take the row from the output frame instead, bit for bit the
+ * same pixels at a lower rate. */
 #define MIC_HIP_PRED_GRAD 0x200
 /* OR'ed into mic_hip_unit.nstates: the unit is a gap-removal stream (mic_hip_compress_frame_gap's bytes).  Decode units must carry it
  * too; with MIC_HIP_PRED_GRAD it is MIC_ERR_ARGS (the reference has no such codec). */

@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
     // steps ahead so the L2 round trip is off the step's critical path.
     // Frames up to PR_MAX_W columns leave here: k_dec_predict does this phase one wave per unit.
     if (W <= PR_MAX_W) return;
-    if (u.pred) { if (tid == 0) u.status = MICD_ERR_UNSUPPORTED; return; }   // the gradient predictor has no in-group wavefront
+    if (u.pred) return;                                           // k_dec_predict_grad<true>: the gradient predictor has no in-group wavefront
     const int ngrp = (W + PX_K - 1) / PX_K;
     for (int rb = 0; rb < H; rb += PX_THREADS) {
         const int y = rb + (int)tid;
@@ -783,14 +783,17 @@ __global__ void __launch_bounds__(128) k_dec_predict2(MicUnit *units, int w_lo, 
 // 768 XR strips of 2577 x 256 the kernel takes 4.27 / 4.28 / 4.42 / 4.77 ms at 1 / 2 / 4 / 8 steps (profiles/pica_batch.json) -- a unit is
 // one wave of nq + 63 dependent steps per band, bound by that wave's own instruction issue, not by its loads (DESIGN.md "PICA").
 // The row buffer is sized by the launch's width class (8 KiB, 16 KiB, PR_MAX_W columns), and only the classes the batch's widths
-// call for are launched.
+// call for are launched.  FRAME_ROW: the class of frames wider than PR_MAX_W (the reference has no width limit) keeps no row buffer:
+// the previous band's last row is in px_out by the time the next band starts, and lane 0 reads it from there -- one L2 round trip
+// per step on the wave's critical path, which only these frames pay.
 #define PG_Q 4
 #define PG_AHEAD 1
+template <bool FRAME_ROW>
 __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_lo, int w_hi) {
     MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK || u.mode != 0 || !u.pred) return;
     const int W = u.w, H = u.h;
-    if (W <= w_lo || W > w_hi) return;                           // row-buffer class of this launch (wider than PR_MAX_W: k_dec_pixels_wg has flagged it)
+    if (W <= w_lo || W > w_hi) return;                           // row-buffer class of this launch
     extern __shared__ uint16_t s_grow[];                         // the last row of the previous band (+ PG_Q slack)
     const uint32_t lane = threadIdx.x;
     const int32_t thr = (int32_t)u.dec_thr;
@@ -798,7 +801,7 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
     const __attribute__((address_space(1))) uint32_t *flags = (const __attribute__((address_space(1))) uint32_t *)u.flags;
     const int nq = (W + PG_Q - 1) / PG_Q;                        // groups per row
     const uint32_t npx = (uint32_t)W * (uint32_t)H;
-    for (int x = (int)lane; x < nq * PG_Q + PG_Q; x += 64) s_grow[x] = 0;
+    if (!FRAME_ROW) for (int x = (int)lane; x < nq * PG_Q + PG_Q; x += 64) s_grow[x] = 0;
     __builtin_amdgcn_s_waitcnt(0xC07F);
     struct Grp { uint32_t v[PG_Q]; uint32_t raw; };              // symbols of a group and the raw bits of its pixels
     for (int y0 = 0; y0 < H; y0 += 64) {
@@ -841,7 +844,9 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
             {
                 const int qc = min(max(q, 0), nq - 1);
                 uint32_t rb0 = 0, rb1 = 0;
-                if (lane == 0) { const uint2 r = *(const uint2 *)(s_grow + qc * PG_Q); rb0 = r.x; rb1 = r.y; }
+                if (FRAME_ROW) {                                 // (columns W .. W + 2 of the row above are this band's first pixels: never used)
+                    if (lane == 0 && y0) { const pr_v2 r = *(const __attribute__((address_space(1))) PrD *)(px + (rowp - (uint32_t)W) + (uint32_t)qc * PG_Q); rb0 = r.x; rb1 = r.y; }
+                } else if (lane == 0) { const uint2 r = *(const uint2 *)(s_grow + qc * PG_Q); rb0 = r.x; rb1 = r.y; }
                 const uint32_t m0 = mine[0] | (mine[1] << 16), m1 = mine[2] | (mine[3] << 16);
                 const uint32_t t0 = __builtin_amdgcn_update_dpp(rb0, m0, 0x138, 0xF, 0xF, false);   // wave_shr:1
                 const uint32_t t1 = __builtin_amdgcn_update_dpp(rb1, m1, 0x138, 0xF, 0xF, false);
@@ -868,7 +873,8 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
             // column 3: NE is the first pixel lane r - 1 has just produced for ITS group (one group further right)
             {
                 uint32_t rb = 0;
-                if (lane == 0) rb = s_grow[min(q + 1, nq) * PG_Q];
+                if (FRAME_ROW) { if (lane == 0 && y0) rb = px[(rowp - (uint32_t)W) + (uint32_t)min(q + 1, nq) * PG_Q]; }
+                else if (lane == 0) rb = s_grow[min(q + 1, nq) * PG_Q];
                 const uint32_t ne_in = __builtin_amdgcn_update_dpp(rb, res[0], 0x138, 0xF, 0xF, false);
                 const uint32_t x = x0 + 3u;
                 pixel(3, (x + 1 < (uint32_t)W) ? ne_in : up[2]);
@@ -880,13 +886,14 @@ __global__ void __launch_bounds__(64) k_dec_predict_grad(MicUnit *units, int w_l
                 const uint32_t d0 = res[0] | (res[1] << 16), d1 = res[2] | (res[3] << 16);
                 if (cnt == PG_Q) { pr_v2 d; d.x = d0; d.y = d1; *(__attribute__((address_space(1))) PrD *)(px + p) = d; }
                 else for (int k = 0; k < cnt; k++) px[p + (uint32_t)k] = (uint16_t)res[k];
-                if (lane == 63) *(uint2 *)(s_grow + q * PG_Q) = make_uint2(d0, d1);   // the next band's row above (read 63 steps ahead of this write)
+                if (!FRAME_ROW && lane == 63) *(uint2 *)(s_grow + q * PG_Q) = make_uint2(d0, d1);   // the next band's row above (read 63 steps ahead of this write)
             }
 #pragma unroll
             for (int k = 0; k < PG_Q; k++) mine[k] = act ? res[k] : mine[k];
             if (!act) { left = 0; if (q < 0) nw = 0; }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);                        // wave-private LDS: lane 63's row is in before the next band reads it
+        if (FRAME_ROW) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // lane 63's stores to px_out are done before lane 0 loads them (one wave, one L1)
+        else __builtin_amdgcn_s_waitcnt(0xC07F);                   // wave-private LDS: lane 63's row is in before the next band reads it
     }
 }
 
@@ -916,14 +923,16 @@ void mic_launch_decode_pixels(MicUnit *d_units, int n, hipStream_t stream, MicTi
     if (any_grad) {
         if (t) t->mark("k_dec_predict_grad");
         static MicPerDeviceOnce once;
-        once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_predict_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (PR_MAX_W + 2 * PG_Q) * 2); });
+        once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_predict_grad<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (PR_MAX_W + 2 * PG_Q) * 2); });
         // row-buffer classes by width, as above: 8 KiB up to 4088 columns, 16 KiB up to 8184, then the wide one -- launched when the
         // batch has a width of the class (pred_mask speaks for all units, gradient or not: a class without gradient units exits at once)
         if (pred_mask & (0x7Fu | MIC_PRED_NARROW | MIC_PRED_WAVE2))
-            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), 4096 * 2, stream, d_units, 0, 4096 - 2 * PG_Q);
+            hipLaunchKernelGGL(k_dec_predict_grad<false>, dim3(n), dim3(64), 4096 * 2, stream, d_units, 0, 4096 - 2 * PG_Q);
         if (pred_mask & (MIC_PRED_WAVE2 | MIC_PRED_WIDE))
-            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), 8192 * 2, stream, d_units, 4096 - 2 * PG_Q, 8192 - 2 * PG_Q);
-        if (pred_mask & MIC_PRED_WIDE)
-            hipLaunchKernelGGL(k_dec_predict_grad, dim3(n), dim3(64), (PR_MAX_W + 2 * PG_Q) * 2, stream, d_units, 8192 - 2 * PG_Q, PR_MAX_W);
+            hipLaunchKernelGGL(k_dec_predict_grad<false>, dim3(n), dim3(64), 8192 * 2, stream, d_units, 4096 - 2 * PG_Q, 8192 - 2 * PG_Q);
+        if (pred_mask & MIC_PRED_WIDE) {
+            hipLaunchKernelGGL(k_dec_predict_grad<false>, dim3(n), dim3(64), (PR_MAX_W + 2 * PG_Q) * 2, stream, d_units, 8192 - 2 * PG_Q, PR_MAX_W);
+            hipLaunchKernelGGL(k_dec_predict_grad<true>, dim3(n), dim3(64), 0, stream, d_units, PR_MAX_W, INT_MAX);   // no row buffer: any width
+        }
     }
 }
