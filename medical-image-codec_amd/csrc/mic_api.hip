@@ -712,6 +712,27 @@ int mic_hip_debug_split4_config(mic_hip_session *s, uint32_t min_tokens4) try {
     s->dec_classes = mic_hip_session::ClsMemory{};
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): the eight-part instance's record of unit i after a decode's *_finish -- out[0]: MIC_SPLIT_*,
+// out[1..7]: I_1 .. I_7, out[8]: W, out[9]: R (0: not an eight-part unit -- one it handed back carries the four-part instance's
+// record), out[10]: the failing boundary, out[11]: parts; of any other unit out[1..7], out[9] and out[10] are 0
+int mic_hip_debug_split8(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    const MicUnit &u = s->h_units[(size_t)i];
+    const uint32_t *r = u.split;
+    const uint32_t m = r[7] == 8u ? ~0u : 0u;
+    out[0] = r[0]; out[1] = r[1] & m; out[2] = r[3] & m; out[3] = r[4] & m;
+    for (int k = 0; k < 4; k++) out[4 + k] = u.split_hi[k] & m;
+    out[8] = r[2]; out[9] = r[5] & m; out[10] = r[6] & m; out[11] = r[7];
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug setter (not in the public header): the length from which on a unit of the four-part list goes to the eight-part instance
+// (MicSplitCfg::min_tokens8); a zero keeps the value.  The session forgets its launch masks, as above.
+int mic_hip_debug_split8_config(mic_hip_session *s, uint32_t min_tokens8) try {
+    if (!s) return MIC_ERR_ARGS;
+    if (min_tokens8) s->split_cfg.min_tokens8 = min_tokens8;
+    s->dec_classes = mic_hip_session::ClsMemory{};
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py
 // holds its own restatement against it, value by value)
 int mic_hip_debug_dec_cls(uint32_t flavour, uint32_t table_log, uint32_t zero_bits) { return mic_dec_cls(flavour, table_log, zero_bits); }

@@ -90,9 +90,12 @@ __device__ __forceinline__ uint64_t ls_rl64(uint64_t v, int lane) {
 // per token; list LS_RETRY_LIST is filled by that kernel with what it hands back, its count starts at zero here.
 // List LS_SPLIT4_LIST holds those of them that have at least min_tokens4 tokens: k_dec_tans_ls_parts<4> takes them, and hands back
 // to the same retry list.
+// List LS_SPLIT8_LIST holds those of at least max(min_tokens8, min_tokens4) tokens: k_dec_tans_ls_parts<8> takes them, and appends
+// what it hands back to the four-part list, which the four-part instance, launched behind it, judges afresh.
 #define LS_SPLIT_LIST MIC_CLS_CLASSES
 #define LS_RETRY_LIST (MIC_CLS_CLASSES + 1)
 #define LS_SPLIT4_LIST (MIC_CLS_CLASSES + 2)
+#define LS_SPLIT8_LIST (MIC_CLS_CLASSES + 3)
 #define LS_LISTS MIC_CLS_LISTS                     // lists this kernel counts (the retry list takes no unit here)
 __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, int *list, int *count, int split, MicSplitCfg cfg) {
     __shared__ uint32_t s_w[16][LS_LISTS];
@@ -114,7 +117,8 @@ __global__ void __launch_bounds__(1024) k_dec_classify(MicUnit *units, int n, in
                     if (u.comp_in[u.comp_len - 1] == 0) u.status = MICD_ERR_CORRUPT;
                     else {
                         cls = mic_dec_cls(flav, tl, u.zero_bits);
-                        if (cls == 0 && split && mic_split_gate(u, cfg)) cls = u.count >= cfg.min_tokens4 ? LS_SPLIT4_LIST : LS_SPLIT_LIST;
+                        if (cls == 0 && split && mic_split_gate(u, cfg))
+                            cls = u.count >= max(cfg.min_tokens8, cfg.min_tokens4) ? LS_SPLIT8_LIST : u.count >= cfg.min_tokens4 ? LS_SPLIT4_LIST : LS_SPLIT_LIST;
                     }
                 }
             }
@@ -552,7 +556,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 }
 
 // ==========================================================================================
-// The split instances: two states, tableLog 13, no 0-bit entries, and every long stream decoded as PARTS (two or four) parts by as
+// The split instances: two states, tableLog 13, no 0-bit entries, and every long stream decoded as PARTS (two, four or eight) parts by as
 // many decoders that share the stream's table.  A tANS decoder that starts at a wrong bit position with wrong
 // states falls in with the true one after a few thousand symbols when a symbol replaces most of a state's bits with stream bits
 // (9.6 of 13 on the headline's strips).  So part 0 starts at the true start and writes true states to tok; part p >= 1 starts
@@ -560,7 +564,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // slab, idle between the table stage and k_dec_translate.  Part p >= 1 hands its position and states after W symbols to part
 // p - 1, which runs until it has passed that position; once it reaches it with the same two states, role by role, everything
 // part p decoded from there on is the stream's.
-//   * lane 2 PARTS g + 2 part + k holds state k of part `part` of the wave's stream g (12 or 24 state lanes a wave); the other
+//   * lane 2 PARTS g + 2 part + k holds state k of part `part` of the wave's stream g (12, 24 or 48 state lanes a wave); the other
 //     lanes clone lane k of stream 0's part 0 (same addresses, same values);
 //   * a part has its own ring (4 blocks of B = 64 / PARTS dwords), mirror and stage: a chunk is 128 / PARTS symbols of the same
 //     hand-scheduled round as the unsplit instance (LS_CHUNK2_N);
@@ -570,8 +574,10 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // reads are three dwords from the dword of p - 32 on for every position p of the chunk, its last included: with D the dword of the
 // chunk's first position, in block b, they span dwords D - 13 B / 16 - 1 ... D + 1 (B = 32: D - 27, B = 16: D - 14);
 // D - 13 B / 16 - 1 >= B b - 13 B / 16 - 1 = B (b - 1) + 3 B / 16 - 1 (+ 5, + 2), inside block b - 1, and D + 1 inside block b + 1 at
-// the most: the three stored blocks.  The block in flight (b - 2) takes the slot of block b + 2 at the chunk's end, which no chunk
-// from here on reads.  The position behind the two initial states is at most 26 bits below the start, so the same three blocks
+// the most: the three stored blocks.  B = 8 has no dword to spare: a chunk of 16 symbols takes at most 208 bits = 6.5 dwords, the
+// lowest read starts at the dword of p0 - 208 - 32 for a first position p0 >= 32 D, which is floor(D - 7.5) = D - 8 >= 8 (b - 1):
+// exactly the first dword of block b - 1 when D is block b's first, and 6.5 < 8 keeps a chunk from crossing two blocks.  The block
+// in flight (b - 2) takes the slot of block b + 2 at the chunk's end, which no chunk from here on reads.  The position behind the two initial states is at most 26 bits below the start, so the same three blocks
 // hold what the initial states read.
 // Where the parts start: Lb the stream's bits, Wb = W symbols' worth of bits at the mean rate, x = (Lb + (PARTS - 1) Wb) / PARTS;
 // part p >= 1 starts at bit (PARTS - p) x - (PARTS - 1 - p) Wb, so that every part covers about x bits, W symbols of them under its
@@ -586,6 +592,11 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // it must decode count - I_last + W steps without reading below bit 0).  The first boundary that fails names the outcome, and the
 // whole unit -- no meeting, no room, a cut or damaged stream -- goes to the retry list, which the unsplit instance decodes and
 // reports as it always has.
+// Eight parts differ in three things (the third is the cache policy, LsParts::AUX).  A region holds a part's steps from W on (step j >= W at region offset j - W): the W steps in
+// front are the overlap, which k_dec_translate never reads and the joins do not need, so seven regions of a seventh of the slab
+// hold the parts of a full strip; the room checks are e_p - W <= R and j_end - W <= R, and tokens [I_p, I_p+1) lie at
+// sym[(p - 1) R + i - I_p].  And what the instance hands back goes to the end of the four-part list, not to the retry list: a miss
+// then costs a four-part chain instead of an unsplit one; the four-part instance, launched behind it, judges the unit afresh.
 // LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop, summed over the chunks, into dbg[] of the
 // wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over, snapshot and ballot;
 // dbg[5] chunks, dbg[6] parts per stream
@@ -598,21 +609,31 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 #define LS_ST_OUT(parts_) do { } while (0)
 #endif
 template <int PARTS> struct LsParts {
-    static_assert(PARTS == 2 || PARTS == 4, "eight parts do not fit the sym slab (DESIGN.md section 4)");
+    static_assert(PARTS == 2 || PARTS == 4 || PARTS == 8, "a part needs a ring block of at least 8 dwords: a chunk of 128 / PARTS symbols must not cross two");
     static constexpr int TL = 13, SPW = 3, WAVES = 3;
-    static constexpr int CHUNK = 128 / PARTS;                               // symbols of a chunk of one part: 64 | 32
-    static constexpr int BLK = 64 / PARTS, BLK_SHIFT = PARTS == 2 ? 5 : 4;  // dwords of a ring block = upkeep lanes of a part: 32 | 16
+    static constexpr int CHUNK = 128 / PARTS;                               // symbols of a chunk of one part: 64 | 32 | 16
+    static constexpr int BLK = 64 / PARTS, BLK_SHIFT = PARTS == 2 ? 5 : PARTS == 4 ? 4 : 3;   // dwords of a ring block = upkeep lanes of a part: 32 | 16 | 8
     static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = BLK_SHIFT + 2;
     static constexpr uint32_t MIRROR = 4u * BLK * RING_BLOCKS;              // two mirror dwords + two pad dwords
     static constexpr uint32_t STAGE = MIRROR + 16u;                         // CHUNK u16 states of a chunk
-    static constexpr uint32_t PART_BYTES = STAGE + 2u * CHUNK;              // 656 | 336
+    static constexpr uint32_t PART_BYTES = STAGE + 2u * CHUNK;              // 656 | 336 | 176
     static constexpr uint32_t TAB = (uint32_t)PARTS * PART_BYTES;           // the parts in front of the stream's table
-    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696 | 17 728
-    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264 | 159 552
+    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696 | 17 728 | 17 792
+    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264 | 159 552 | 160 128
     static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
+    // Eight parts: a region holds a part's steps from W on only (step j at region offset j - W) -- the first W are the overlap, which
+    // nothing reads: the joins are stepped from register snapshots.  Two and four parts keep the layout they were measured with
+    static constexpr bool SKIP_W = PARTS == 8;
+    // Cache policy of the chunk loop's buffer loads and state stores.  Two and four parts stream them (nt): a store instruction
+    // writes segments of 128 and 64 bytes.  Eight parts write 32-byte segments, four chunks to a cache line about 2000 cycles apart:
+    // streamed, the wait for the ring's loads stood behind those stores' acknowledgements for 800 cycles a chunk, 2400 in all (vmcnt
+    // counts in order), and fetching two chunks ahead did not move it; left to the L2 to combine it is 310, 1940 in all, and
+    // k_dec_translate finds part of the states there (profiles/tans2_split8_ab.json)
+    static constexpr int AUX = PARTS == 8 ? 0 : 2;
     // R, the tokens of one of the PARTS - 1 scratch regions, in whole chunks.  Recorded, and every NO_ROOM outcome depends on it, so
     // each instance keeps its rule: two parts' one region is the slab, clamped by the stream's length (part 1 never has to hold
-    // more); four parts' is a third of the slab whatever the stream's length (the sym slab is at least a tok slab)
+    // more); four parts' is a third of the slab whatever the stream's length (the sym slab is at least a tok slab), eight parts' a
+    // seventh
     static __device__ __forceinline__ uint32_t region(uint32_t sym_cap, uint32_t tok_cap, uint32_t T) {
         const uint32_t slab = min(sym_cap, tok_cap);
         return (PARTS == 2 ? min(slab, T) : slab / (uint32_t)(PARTS - 1)) & ~(uint32_t)(CHUNK - 1);
@@ -696,7 +717,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
         return (__builtin_amdgcn_ds_bpermute((int)((LP * (uint32_t)j + 2u * up) << 2), qq) >> 5) >> G::BLK_SHIFT;
     };
     auto load_blk = [&](int j, int32_t b) -> uint32_t {                    // dword lb of block b of stream j, zero outside the stream
-        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], (b * (int32_t)BLK + (int32_t)lb) * 4, 0, 2);
+        return __builtin_amdgcn_raw_buffer_load_b32(rs_in[j], (b * (int32_t)BLK + (int32_t)lb) * 4, 0, G::AUX);
     };
     auto store_blk = [&](int j, int32_t b, uint32_t v) {
         const uint32_t rb = (wv * LS_SPW + (uint32_t)j) * SB + up * PB;
@@ -764,7 +785,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
         asm volatile("" : "+v"(sn_q), "+v"(sn_st), "+v"(sn_ch));            // (taken here: sunk behind the chunk, the selects keep the old q and st alive across it)
         if (ch >= ch_cap || !__any(on & real & have)) break;                // one wave-uniform test per chunk
         LS_T(4);
-        if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else LS_CHUNK2_N("8", "64");
+        if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else if constexpr (PARTS == 4) LS_CHUNK2_N("8", "64"); else LS_CHUNK2_N("4", "32");
         LS_T(0);
         // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
 #pragma unroll
@@ -780,11 +801,13 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
 #pragma unroll
             for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + lb * 4);
             const uint32_t off = ch * 2u * CH;                              // (part 0 runs on into a descriptor that ends at its last whole chunk)
+            // eight parts: a region starts at step W, and the chunks in front of it are not stored (both terms below are wave-uniform)
+            const uint32_t ch0 = G::SKIP_W ? Wc : 0u, soff = (ch - ch0) * 2u * CH;
 #pragma unroll
             for (int j = 0; j < LS_SPW; j++) {
-                const bool fits = (ch + 1u) * CH <= s_R[j];                 // (a part that runs on past its region must not write into its neighbour's)
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, 2);   // (out of range + off < 2^32: still out of range)
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + off : LS_OOB), 0, 2);
+                const bool fits = ch >= ch0 && (ch + 1u - ch0) * CH <= s_R[j];   // (a part that runs on past its region must not write into its neighbour's)
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, G::AUX);   // (out of range + off < 2^32: still out of range)
+                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + soff : LS_OOB), 0, G::AUX);
             }
         }
         LS_T(3);
@@ -835,7 +858,12 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
     if (!(real && have && lane == l0)) return;
     // boundary b = 1 .. PARTS - 1: met, then room -- I_1 inside tok's whole chunks, part b - 1's last step e inside its region; then
     // the stream's end (PARTS): the last part's room and its count.  (Two parts: I_2 = I_3 = ~0, "no bound" to k_dec_translate)
-    uint32_t outcome = MIC_SPLIT_DONE, fail = 0, I[3] = { 0u, PARTS > 2 ? 0u : ~0u, PARTS > 2 ? 0u : ~0u };
+    // Eight parts: a region holds steps from W on, so the room is e - W <= R and j_end - W <= R (e >= W: the join's i_min)
+    constexpr int NI = PARTS > 4 ? PARTS - 1 : 3;
+    uint32_t outcome = MIC_SPLIT_DONE, fail = 0, I[NI];
+#pragma unroll
+    for (int b = 0; b < NI; b++) I[b] = b && PARTS == 2 ? ~0u : 0u;
+    const uint32_t dead = G::SKIP_W ? W : 0u;                               // a part's steps that its region does not hold
     {
         uint32_t at = 0;
 #pragma unroll
@@ -844,7 +872,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
             if (!mets[b]) { outcome = MIC_SPLIT_NOT_MET; fail = (uint32_t)b + 1u; break; }
             at = b ? at + es[b] - W : es[0];
             I[b] = at;
-            if (b ? es[b] > R : at > (T / CH) * CH) { outcome = MIC_SPLIT_NO_ROOM; fail = (uint32_t)b + 1u; }
+            if (b ? es[b] - dead > R : at > (T / CH) * CH) { outcome = MIC_SPLIT_NO_ROOM; fail = (uint32_t)b + 1u; }
         }
     }
     if (outcome == MIC_SPLIT_DONE) {
@@ -852,7 +880,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
         if (I[PARTS - 2] > T) outcome = MIC_SPLIT_BAD_COUNT;                 // (the parts in front hold more than the stream's symbols)
         else {
             const uint32_t j_end = T - I[PARTS - 2] + W, js = pl_ch * CH;   // the last part must hold steps [W, j_end)
-            if (j_end > R) outcome = MIC_SPLIT_NO_ROOM;
+            if (j_end - dead > R) outcome = MIC_SPLIT_NO_ROOM;
             else if (j_end > ch_end * CH) outcome = MIC_SPLIT_BAD_COUNT;    // (the loop ended: the last part was out of bits with symbols to go)
             else if (j_end > js) {
                 // the over-read rule at the stream's last symbol: the last part's position behind step j_end - 1, from its last chunk start with bits left
@@ -869,10 +897,11 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
     MicUnit &uo = units[unit_i];
     uo.split[0] = outcome; uo.split[1] = I[0]; uo.split[2] = W; uo.split[3] = I[1]; uo.split[4] = I[2];
     uo.split[5] = R; uo.split[6] = fail; uo.split[7] = (uint32_t)PARTS;
+    if constexpr (PARTS == 8) { uo.split_hi[0] = I[3]; uo.split_hi[1] = I[4]; uo.split_hi[2] = I[5]; uo.split_hi[3] = I[6]; }
     if (outcome == MIC_SPLIT_DONE) {
         uo.dec_kernel = 1u;                                                 // class 0, as the unsplit instance reports it
         uo.ntok = T; uo.dec_stage = MIC_STAGE_STATES;                // tok and sym hold STATES: k_dec_translate joins and translates them
-    } else retry_list[atomicAdd(retry_count, 1)] = unit_i;
+    } else retry_list[atomicAdd(retry_count, 1)] = unit_i;                  // (eight parts: the four-part list, behind what k_dec_classify put there)
 }
 
 // ==========================================================================================
@@ -915,12 +944,21 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
     // they are read from there and written, translated, to tok -- everything behind this pass sees an ordinary tok.  Up to three
     // bounds b1 <= b2 <= b3 (none: ~0, which is what a two-part unit's record holds for I_2 and I_3) and, for the tokens from bound p
     // on, the offset o_p from token index to scratch index (modulo 2^32)
-    const bool sp = TRTL == 13 && u.split[0] == MIC_SPLIT_DONE;
-    const uint32_t sp_R = u.split[5], sp_W = u.split[2];
+    // An eight-part unit (split[7] = 8) has four more bounds in split_hi, and its regions hold no steps in front of W:
+    // sym[(p - 1) R + i - I_p].  All of this is uniform per unit
+    const bool sp = TRTL == 13 && u.split[0] == MIC_SPLIT_DONE, sp8 = sp && u.split[7] == 8u;
+    const uint32_t sp_R = u.split[5], sp_W = sp8 ? 0u : u.split[2];
     const uint32_t b1 = sp ? u.split[1] : ~0u, b2 = sp ? u.split[3] : ~0u, b3 = sp ? u.split[4] : ~0u;
+    const uint32_t b4 = sp8 ? u.split_hi[0] : ~0u, b5 = sp8 ? u.split_hi[1] : ~0u, b6 = sp8 ? u.split_hi[2] : ~0u, b7 = sp8 ? u.split_hi[3] : ~0u;
     const uint32_t o1 = sp_W - b1, o2 = sp_R + sp_W - b2, o3 = 2u * sp_R + sp_W - b3;
-    auto seg_of = [&](uint32_t i) -> uint32_t { return (uint32_t)(i >= b1) + (uint32_t)(i >= b2) + (uint32_t)(i >= b3); };
-    auto scr_of = [&](uint32_t p, uint32_t i) -> uint32_t { return i + (p == 1u ? o1 : p == 2u ? o2 : o3); };
+    const uint32_t o4 = 3u * sp_R - b4, o5 = 4u * sp_R - b5, o6 = 5u * sp_R - b6, o7 = 6u * sp_R - b7;
+    auto seg_of = [&](uint32_t i) -> uint32_t {
+        return (uint32_t)(i >= b1) + (uint32_t)(i >= b2) + (uint32_t)(i >= b3) + (uint32_t)(i >= b4) + (uint32_t)(i >= b5) + (uint32_t)(i >= b6) +
+               (uint32_t)(i >= b7);
+    };
+    auto scr_of = [&](uint32_t p, uint32_t i) -> uint32_t {
+        return i + (p == 1u ? o1 : p == 2u ? o2 : p == 3u ? o3 : p == 4u ? o4 : p == 5u ? o5 : p == 6u ? o6 : o7);
+    };
     const uint16_t *scr = u.sym;
     const bool frame = u.mode == 0 && u.seg != nullptr;
     // (a length-prefixed RLE stream, walk_mode 1 -- a whole WaveletV2 frame -- is one unit of millions of tokens: walking it here would
@@ -943,8 +981,9 @@ __global__ void __launch_bounds__(TR_THREADS) k_dec_translate(MicUnit *units) {
                 if (pseg == 0u) v = __builtin_nontemporal_load((const tr_v4 *)(tok + i0));
                 else {
                     // behind a join of a split unit: eight states from the scratch slab, 2-byte aligned only -- five aligned dwords and
-                    // a funnel shift by the source's parity (the u16 in front of and behind the eight are inside the slab: W >= 32,
-                    // and the slab is 64 tokens longer than what the parts may write)
+                    // a funnel shift by the source's parity (the u16 in front of and behind the eight are inside the slab: W >= 32
+                    // -- an eight-part unit's index is at least 0, and rounding it down to even stays there --, and the slab is 64
+                    // tokens longer than what the parts may write)
                     const uint32_t sj = scr_of(pseg, i0);
                     const uint32_t *d = (const uint32_t *)(scr + (sj & ~1u));
                     const uint32_t sh = (sj & 1u) * 16u;
@@ -1091,16 +1130,17 @@ static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *
     const unsigned groups = (unsigned)((n + per - 1) / per);
     hipLaunchKernelGGL((k_dec_tans_ls<N, ZB, TL>), dim3(groups), dim3(64 * LsGeom<TL>::WAVES), LsGeom<TL>::LDS, stream, d_units, list, count);
 }
-// a split instance on list `from`; what it hands back goes to the retry list
+// a split instance on list `from`; what it hands back goes to the end of list `to` (the groups cover n units: an instance launched
+// behind it on `to` sees them)
 template <int PARTS>
-static void launch_ls_parts(MicUnit *d_units, int n, int *d_list, int *d_count, int from, hipStream_t stream, uint32_t overlap) {
+static void launch_ls_parts(MicUnit *d_units, int n, int *d_list, int *d_count, int from, int to, hipStream_t stream, uint32_t overlap) {
     using G = LsParts<PARTS>;
     constexpr int per = G::WAVES * G::SPW;
     static MicPerDeviceOnce once;
     once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_parts<PARTS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS); });
     const unsigned groups = (unsigned)((n + per - 1) / per);
     hipLaunchKernelGGL((k_dec_tans_ls_parts<PARTS>), dim3(groups), dim3(64 * G::WAVES), G::LDS, stream, d_units, d_list + (size_t)from * (size_t)n,
-                       d_count + from, d_list + (size_t)LS_RETRY_LIST * (size_t)n, d_count + LS_RETRY_LIST, overlap);
+                       d_count + from, d_list + (size_t)to * (size_t)n, d_count + to, overlap);
 }
 template <int TL>
 static void launch_ls_tl(MicUnit *d_units, int n, const int *d_list, const int *d_count, hipStream_t stream, bool skip_first, uint32_t m) {
@@ -1119,13 +1159,15 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
     if (t) t->mark("k_dec_classify");
     hipLaunchKernelGGL(k_dec_classify, dim3(1), dim3(1024), 0, stream, d_units, n, d_list, d_count, split ? 1 : 0, sc);
     if (split) {
-        // the split instances first (the longest kernels of the chain, the four-part one with the longest units in front), then what
+        // the split instances first (the longest kernels of the chain, the one with the longest units in front), then what
         // they hand back: an empty list in the normal case, and the unsplit instance's blocks leave at once.  (Without the retry
-        // launch k_dec_tans_gl would take those units: slower, not wrong.)
+        // launch k_dec_tans_gl would take those units: slower, not wrong.)  The eight-part instance hands back to the four-part one.
+        if (t) t->mark("k_dec_tans_ls_split8<13>");
+        launch_ls_parts<8>(d_units, n, d_list, d_count, LS_SPLIT8_LIST, LS_SPLIT4_LIST, stream, sc.overlap & ~63u);
         if (t) t->mark("k_dec_tans_ls_split4<13>");
-        launch_ls_parts<4>(d_units, n, d_list, d_count, LS_SPLIT4_LIST, stream, sc.overlap & ~63u);
+        launch_ls_parts<4>(d_units, n, d_list, d_count, LS_SPLIT4_LIST, LS_RETRY_LIST, stream, sc.overlap & ~63u);
         if (t) t->mark("k_dec_tans_ls_split<13>");
-        launch_ls_parts<2>(d_units, n, d_list, d_count, LS_SPLIT_LIST, stream, sc.overlap & ~63u);
+        launch_ls_parts<2>(d_units, n, d_list, d_count, LS_SPLIT_LIST, LS_RETRY_LIST, stream, sc.overlap & ~63u);
         if (cls_mask & MIC_CLS_RETRY) {
             if (t) t->mark("k_dec_tans_ls<2,false,13> retry");
             launch_ls_list<2, false, 13>(d_units, n, d_list + (size_t)LS_RETRY_LIST * (size_t)n, d_count + LS_RETRY_LIST, stream);

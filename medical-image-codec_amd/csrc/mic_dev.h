@@ -46,6 +46,9 @@ struct MicSplitCfg {
     uint32_t min_bits16 = 144u;        // G: 16 x the mean bits per token from which on a wrong start is forgotten inside W
     uint32_t min_tokens4 = 262144u;    // units that pass the gate above and are at least this long go to the four-part instance
                                        // (the others to the two-part one); mic_hip_debug_split4_config sets it, mic_hip_debug_split_config does not
+    uint32_t min_tokens8 = 393216u;    // ... and those of at least max(min_tokens8, min_tokens4) tokens to the eight-part instance, whose regions
+                                       // hold a part's steps from W on only: break-even against four parts is about 5.3 W, twelve W is the
+                                       // default; mic_hip_debug_split8_config sets it
 };
 // MicUnit.enc_kernel: 1 + the bit index of the MIC_ENC_CLS_* class (mic_launch.h) whose k_enc_tans_wg instance gave the unit its tANS
 // verdict (1 .. 7), or MIC_ENC_BY_SERIAL; MIC_ENC_HANDED is set beside it when the two-state instance had handed the unit over first
@@ -183,6 +186,9 @@ struct MicUnit {
                               // scratch region), 6 the failing boundary (1 .. parts - 1: the join of parts p - 1 and p, parts: the stream's
                               // end, 0: none), 7 parts.  Read by mic_hip_debug_split and mic_hip_debug_split4, predicted by
                               // tests/tans_split_model.py.  Cleared with the other results
+    uint32_t split_hi[4];     // ... of the eight-part instance (split[7] = 8): I_4 .. I_7, and its regions hold no dead steps -- tokens
+                              // [I_p, I_p+1) are the states sym[(p - 1) R + i - I_p].  Read by mic_hip_debug_split8, predicted by
+                              // tests/tans_split8_model.py
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }

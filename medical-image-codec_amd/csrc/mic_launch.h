@@ -71,10 +71,10 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
 // d_cls: per-session scratch of MIC_CLS_INTS(n) ints for the per-class unit lists of the lane-per-state tANS decoder (mic_decode_ls.hip)
 #define MIC_CLS_HEAD 64                 // the lists' counts (MIC_CLS_LISTS of them) stand in front of the lists
 #define MIC_CLS_CLASSES 30
-#define MIC_CLS_LISTS 33                // the classes' lists, the split list, the retry list and the four-part split list (mic_decode_ls.hip)
+#define MIC_CLS_LISTS 34                // the classes' lists, the split list, the retry list, the four-part and the eight-part split list (mic_decode_ls.hip)
 #define MIC_CLS_INTS(n) (MIC_CLS_HEAD + MIC_CLS_LISTS * (size_t)(n))
 // cls_mask beside the 30 classes: the split instances of class 0 are launched (and k_dec_classify fills their lists: the mask has
-// no bit left, so the four-part launch rides the two-part one's); the unsplit instance is launched behind them over what they hand back
+// no bit left, so the four- and eight-part launches ride the two-part one's); the unsplit instance is launched behind them over what they hand back
 #define MIC_CLS_SPLIT 0x40000000u
 #define MIC_CLS_RETRY 0x80000000u
 // pred_mask: predictor classes by frame width (mic_pred_bit); cls_mask: bit c = lane-per-state class c of mic_decode_ls.hip (MIC_CLS_CLASSES of them)

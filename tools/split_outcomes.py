@@ -1,6 +1,8 @@
-"""Diagnostic: what the split instances of the two-state tANS chain (k_dec_tans_ls_parts<4>, k_dec_tans_ls_parts<2>) make of the headline
-step's strips -- per step the count of units by instance and MicUnit.split outcome (not tried / split / handed back and why, for
-four-part units with the boundary that failed), and the spread of the first join.
+"""Diagnostic: what the split instances of the two-state tANS chain (k_dec_tans_ls_parts<8>, <4> and <2>) make of the headline
+step's strips -- per step the count of units by the instance whose record they carry and MicUnit.split outcome (not tried / split /
+handed back and why, for four- and eight-part records with the boundary that failed), and the spread of the first join.  A unit the
+eight-part instance hands back carries the four-part instance's record: with every headline strip on the eight-part list, any
+four-part record is such a unit.
 usage: tools/split_outcomes.py [frames=288] [steps=20]"""
 import ctypes as C, os, sys, importlib, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +17,7 @@ W, H, S = 2577, 2048, 8
 NAMES = {0: "not tried", 1: "split", 2: "handed back: no meeting", 3: "handed back: count", 4: "handed back: no room"}
 L = mic.lib()
 L.mic_hip_debug_split4.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+L.mic_hip_debug_split8.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 sh = (H + S - 1) // S
 units = mic.Session.make_units([(b * W * H + y0 * W, W, min(H, y0 + sh) - y0, 4095, 2) for b in range(B) for y0 in range(0, H, sh)])
 sess = mic.Session(B * S, W * sh)
@@ -38,12 +41,15 @@ for step in range(STEPS):
     for i in range(B * S):
         out = (C.c_uint32 * 8)()                                        # outcome, I_1, I_2, I_3, W, R (0: a two-part unit), failing boundary
         assert L.mic_hip_debug_split4(sess._h, i, out) == 0
-        four = out[5] != 0
-        seen[(4 if four else 2, int(out[0]), int(out[6]))] += 1
-        if out[0] == 1: first.append(int(out[1]) if four else None)
+        o8 = (C.c_uint32 * 12)()                                        # outcome, I_1 .. I_7, W, R (0: not an eight-part record), failing boundary, parts
+        assert L.mic_hip_debug_split8(sess._h, i, o8) == 0
+        four, eight = out[5] != 0, o8[9] != 0
+        seen[(8 if eight else 4 if four else 2, int(out[0]), int(o8[10]) if eight else int(out[6]))] += 1
+        if out[0] == 1: first.append(int(o8[1]) if eight else int(out[1]) if four else None)
     first = [v for v in first if v is not None]
     total += seen
     print(f"step {step}: " + ", ".join(f"{name(k)} {v}" for k, v in sorted(seen.items())) +
           (f"; I_1 {min(first)} .. {max(first)}" if first else ""), flush=True)
 print("all steps: " + ", ".join(f"{name(k)} {v}" for k, v in sorted(total.items())))
 print("handed back: %d of %d" % (sum(v for k, v in total.items() if k[1] >= 2), sum(total.values())))
+print("four-part records (the eight-part instance's hand-backs when min_tokens8 is below every strip): %d" % sum(v for k, v in total.items() if k[0] == 4))

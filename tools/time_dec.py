@@ -1,7 +1,9 @@
 """Timing of the decode kernels on the bench workload, ignoring decode status (for ablation builds whose output is wrong).
-usage: python tools/time_dec.py [frames] [nstates] [noise] [min_tokens4]   (noise: a number, or "published" for the headline's level
--- the streams the split instances take; default: xr_like's own.  min_tokens4: the session's four-part threshold; one above the
-strips' length, 1000000 say, sends every headline strip to the two-part instance, mark k_dec_tans_ls_split<13>)"""
+usage: python tools/time_dec.py [frames] [nstates] [noise] [min_tokens4] [min_tokens8]   (noise: a number, or "published" for the
+headline's level -- the streams the split instances take; default: xr_like's own.  min_tokens4: the session's four-part threshold;
+one above the strips' length, 1000000 say, sends every headline strip to the two-part instance, mark k_dec_tans_ls_split<13>.
+min_tokens8: the eight-part threshold; 1000000 keeps the headline strips with the four-part instance, mark k_dec_tans_ls_split4<13>,
+the default sends them to the eight-part one, mark k_dec_tans_ls_split8<13>.  0 keeps a value)"""
 import ctypes, os, sys, importlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +25,8 @@ units = [(b * W * H + y0 * W, W, min(H, y0 + sh) - y0, 4095, NS) for b in range(
 sess = mic.Session(len(units), W * sh)
 if len(sys.argv) > 4:
     assert mic.lib().mic_hip_debug_split4_config(sess._h, ctypes.c_uint32(int(sys.argv[4]))) == 0
+if len(sys.argv) > 5:
+    assert mic.lib().mic_hip_debug_split8_config(sess._h, ctypes.c_uint32(int(sys.argv[5]))) == 0
 cu = mic.Session.make_units(units)
 sess.encode_enqueue(d_px.data_ptr(), cu)
 d_blobs, offs, st, ns = sess.encode_finish()
