@@ -1131,6 +1131,59 @@ int mic_hip_session_rgb_read_crops_as(mic_hip_session *s, const uint8_t *d_blobs
                                       void *d_out, size_t out_cap, int32_t *status, int32_t *failed_plane, mic_hip_rgb_crop_stats *stats,
                                       const mic_hip_out_spec *spec);
 
+/* ---- MIC3 patches at any magnification, resampled on the device ---------------------------------- */
+/* The pyramid stores powers of two of the scanner's resolution; a sampler asks for a target resolution (0.5 um per pixel of a
+ * slide scanned at 0.23).  The five MIC3 patch readers each have a _scaled twin below: the arguments of the _as form and a
+ * trailing scale_num, scale_den -- an output pixel is scale_num / scale_den level pixels wide and high -- so that the tensor a
+ * model consumes still comes out of the one call (no reference counterpart).
+ * One scale per call, reduced by its gcd at the door; behind that 1 <= den <= num, num <= 16 * den and num <= 1024, anything else is
+ * MIC_ERR_ARGS.  Slides that differ by a power of two in resolution meet at one scale through the per-patch level of the multi
+ * doors; a scale per slide, and magnification (a scale below 1), are out of scope.
+ * The value, exact in integers, which a host reference reproduces bit for bit.  Patch i at (x, y) of its level has pw x ph output
+ * pixels.  In units of 1 / den of a level pixel, measured from the patch origin, output pixel (j, r) covers [j * num, (j + 1) * num)
+ * x [r * num, (r + 1) * num) and level pixel (x + k, y + l) covers [k * den, (k + 1) * den) x [l * den, (l + 1) * den); wx(j, k)
+ * and wy(r, l) are the lengths of the two overlaps (0 .. den); p(., c) is the decoded sample of channel c -- of an RGB slide the R,
+ * G or B byte behind the YCoCg-R inverse --, 0 outside the level.  Per channel
+ *     S = sum_l wy(r, l) * sum_k wx(j, k) * p(x + k, y + l, c),    v = (S + num^2 / 2) / num^2    (integer division: half rounds up).
+ * At 2 / 1 that is (a + b + c + d + 2) / 4, the rule the pyramid is built by: a scaled read at 2 / 1 from level L at even origins
+ * equals the native read from level L + 1 wherever that level came from whole 2 x 2 blocks.
+ * v is the sample in the slide's own format, which the native spec (spec NULL or dtype NATIVE) writes; a typed spec applies the rule of
+ * mic_hip_out_spec to x = v, unchanged.  pad (0 in the native format) goes to every output sample whose footprint lies wholly outside
+ * the level, and to all samples of a patch the native door would zero (a refused slide, a bad level); a footprint partly outside
+ * is averaged over the zero-extended level, with no renormalisation.
+ * The source rectangle of a patch is sw x sh = ceil(pw * num / den) x ceil(ph * num / den) level pixels at (x, y)
+ * (mic_hip_wsi_scaled_extent).  status[i]: the first failing tile among the tiles that rectangle touches, in tile-index order, with
+ * the native door's codes; stats counts that plan's tiles and pieces -- feed mic_hip_wsi_patch_plan, mic_hip_wsi_multi_patch_plan and
+ * mic_hip_tile_cache_plan with sw x sh.
+ * How it runs: the door's own native call reads the n source rectangles into a staging tensor of native samples in the session's
+ * workspace (at most a quarter of the workspace ceiling), and one resample kernel writes every sample of d_out.  Attached tile
+ * caches work as they do in the native call.  Patches whose staging tensor does not fit go as consecutive groups, each one native
+ * call and one resample launch: stats.slabs sums over the groups, tiles_decoded and pieces stay the whole call's plan counts (with
+ * a tile cache attached tiles_decoded is what the groups really decoded).
+ * The checks come in the native door's order with the scale judged right behind pw, ph and n; a scale of 1 / 1 (6 / 6) is the
+ * _as door itself: same bytes, statuses, stats and kernels, no staging. */
+/* The one judgement of a scale, and the source extent of a pw x ph patch under it.  MIC_ERR_ARGS for pw, ph, num or den <= 0 and
+ * for a scale outside the limits above; MIC_ERR_UNSUPPORTED where (pw + 1) * num or (ph + 1) * num (reduced) passes 2^31 - 1.  sw, sh
+ * may be NULL.  Needs no device. */
+int mic_hip_wsi_scaled_extent(int pw, int ph, int scale_num, int scale_den, int *sw, int *sh);
+int mic_hip_wsi_read_patches_scaled(const uint8_t *compressed, size_t compressed_len, int level, const int32_t *xy, int n, int pw, int ph,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                    int scale_num, int scale_den);
+int mic_hip_wsi_reader_read_patches_scaled(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                           void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                           int scale_num, int scale_den);
+int mic_hip_session_wsi_read_patches_scaled(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                            void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                            int scale_num, int scale_den);
+int mic_hip_wsi_multi_read_patches_scaled(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                          const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                          void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats,
+                                          const mic_hip_out_spec *spec, int scale_num, int scale_den);
+int mic_hip_wsi_readers_read_patches_scaled(mic_hip_wsi_reader *const *readers, int nreaders,
+                                            const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                            void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats,
+                                            const mic_hip_out_spec *spec, int scale_num, int scale_den);
+
 /* Enables (1) / disables (0) per-kernel HIP-event timing of the enqueue calls. */
 int mic_hip_session_set_timing(mic_hip_session *s, int enabled);
 /* Per-kernel device time (ms, HIP events on the session stream) of the last enqueue:

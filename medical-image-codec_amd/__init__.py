@@ -276,6 +276,12 @@ ABI_SYMBOLS = [
     "mic_hip_session_strips_read_crops_as",
     "mic_hip_rgb_read_crops_as",
     "mic_hip_session_rgb_read_crops_as",
+    "mic_hip_wsi_scaled_extent",
+    "mic_hip_wsi_read_patches_scaled",
+    "mic_hip_wsi_reader_read_patches_scaled",
+    "mic_hip_session_wsi_read_patches_scaled",
+    "mic_hip_wsi_multi_read_patches_scaled",
+    "mic_hip_wsi_readers_read_patches_scaled",
     "mic_hip_tile_cache_slot_bytes", "mic_hip_tile_cache_create", "mic_hip_tile_cache_clear", "mic_hip_tile_cache_get_stats",
     "mic_hip_tile_cache_destroy", "mic_hip_tile_cache_plan",
     "mic_hip_wsi_reader_set_cache", "mic_hip_wsi_reader_cache_probe", "mic_hip_session_set_tile_cache", "mic_hip_session_tile_cache_probe",
@@ -520,6 +526,10 @@ def lib() -> C.CDLL:
     for name in _RECT_DOORS:
         getattr(L, name + "_as").argtypes = getattr(L, name).argtypes + [C.c_void_p]
     L.mic_hip_out_spec_check.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    for name in _RECT_DOORS:
+        if hasattr(L, name + "_scaled"):                                                     # the MIC3 patch readers: spec, scale_num, scale_den
+            getattr(L, name + "_scaled").argtypes = getattr(L, name).argtypes + [C.c_void_p, C.c_int, C.c_int]
+    L.mic_hip_wsi_scaled_extent.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mic_hip_session_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.mic_hip_session_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.mic_hip_tile_cache_slot_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_uint64)]
@@ -588,8 +598,13 @@ def out_spec_check(spec: OutSpec, channels: int = 1, bits_per_sample: int = 16, 
     return nb.value
 
 
-def _door(name: str, spec: Optional[OutSpec]):
-    """the C entry point of a rectangle reader: the native symbol, or with a spec its _as twin with the spec bound as last argument"""
+def _door(name: str, spec: Optional[OutSpec], scale=None):
+    """the C entry point of a rectangle reader: the native symbol, or with a spec its _as twin with the spec bound as last argument;
+    with scale=(num, den) (the MIC3 patch readers) its _scaled twin with the spec, or NULL, and the scale bound behind the rest"""
+    if scale is not None:
+        num, den = (int(v) for v in scale)
+        twin = getattr(lib(), name + "_scaled")
+        return lambda *a: twin(*a, spec.ref() if spec is not None else None, num, den)
     if spec is None:
         return getattr(lib(), name)
     twin = getattr(lib(), name + "_as")
@@ -1582,6 +1597,17 @@ def wsi_patch_plan(level_w: int, level_h: int, tile_w: int, tile_h: int, xy, pw:
     return tiles[: nt.value].copy(), npc.value
 
 
+def wsi_scaled_extent(pw: int, ph: int, scale) -> Tuple[int, int]:
+    """mic_hip_wsi_scaled_extent: (sw, sh), the level pixels a pw x ph patch covers at scale = (num, den) -- what to plan a scaled
+    call with (wsi_patch_plan, wsi_multi_patch_plan, tile_cache_plan); MicError(MIC_ERR_ARGS) for a scale the doors refuse.  Needs
+    no device."""
+    sw, sh = C.c_int(0), C.c_int(0)
+    rc = lib().mic_hip_wsi_scaled_extent(pw, ph, int(scale[0]), int(scale[1]), C.byref(sw), C.byref(sh))
+    if rc:
+        _raise(rc, "wsi_scaled_extent")
+    return sw.value, sh.value
+
+
 def _read_patches(where: str, call, xy, d_out: int, out_cap: int):
     a = _patch_xy(xy)
     st = np.zeros(len(a), dtype=np.int32)
@@ -1590,12 +1616,14 @@ def _read_patches(where: str, call, xy, d_out: int, out_cap: int):
     return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs)
 
 
-def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
+def wsi_read_patches(compressed, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None, scale=None):
     """mic_hip_wsi_read_patches: the pw x ph patches at the (x, y) origins `xy` of one level, into the caller's device tensor
     d_out (an int: ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit
-    greyscale) of out_cap bytes.  Pixels outside the level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs))."""
+    greyscale) of out_cap bytes.  Pixels outside the level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs)).
+    scale=(num, den): mic_hip_wsi_read_patches_scaled -- every output pixel is the exact area average of num / den x num / den
+    level pixels (1 <= num / den <= 16), resampled on the device; the patch covers wsi_scaled_extent(pw, ph, scale) level pixels."""
     c = _bytes_arr(compressed)
-    rc, st, stats = _read_patches("wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_read_patches", spec)(
+    rc, st, stats = _read_patches("wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_read_patches", spec, scale)(
         c.ctypes.data, c.size, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
     if rc:
         _raise(rc, "wsi_read_patches")
@@ -1639,14 +1667,16 @@ def _read_multi_patches(call, xysl, d_out: int, out_cap: int):
     return rc, st, dict(tiles_decoded=ps.tiles_decoded, pieces=ps.pieces, slabs=ps.slabs, slides_read=ps.slides_read)
 
 
-def wsi_multi_read_patches(files, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None):
+def wsi_multi_read_patches(files, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None,
+                           scale=None):
     """mic_hip_wsi_multi_read_patches: the pw x ph patches (x, y, slide, level) `xysl` of the MIC3 files `files` (host buffers;
     slide = an index into the list), into the caller's device tensor d_out (an int:
     ``torch.empty((n, ph, pw, C), dtype=torch.uint8, device="cuda").data_ptr()``; torch.uint16 for 16-bit greyscale; or pinned host
     memory) of out_cap bytes.  Every file must have the call's sample format; one that has not, or does not parse, fails alone.
-    Pixels outside a level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs, slides_read))."""
+    Pixels outside a level are 0.  -> (status per patch, dict(tiles_decoded, pieces, slabs, slides_read)).
+    scale=(num, den): as in wsi_read_patches, one scale for the call."""
     arrs, ptrs, lens = _file_table(files)
-    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_multi_read_patches", spec)(
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_multi_read_patches", spec, scale)(
         ptrs.ctypes.data, lens.ctypes.data, len(arrs), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
     if rc:
         _raise(rc, "wsi_multi_read_patches")
@@ -1883,9 +1913,9 @@ class WsiReader:
                                                                   C.byref(ow), C.byref(oh)), "WsiReader.region")
         return _wsi_shape(self.info, out, ow.value, oh.value)
 
-    def read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
+    def read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None, scale=None):
         """as wsi_read_patches on the whole file; only the blobs of the tiles the patches touch are read, each once"""
-        rc, st, stats = _read_patches("WsiReader.read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_reader_read_patches", spec)(
+        rc, st, stats = _read_patches("WsiReader.read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_wsi_reader_read_patches", spec, scale)(
             self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
         self._cb.check(rc, "WsiReader.read_patches")
         return st, stats
@@ -1922,12 +1952,13 @@ class WsiReader:
             pass
 
 
-def wsi_readers_read_patches(readers, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None):
+def wsi_readers_read_patches(readers, xysl, pw: int, ph: int, d_out: int, out_cap: int, channels: int = 3, bits_per_sample: int = 8, spec=None,
+                             scale=None):
     """mic_hip_wsi_readers_read_patches: wsi_multi_read_patches over a sequence of WsiReader (slide = an index into it; an entry
     no patch names may be None and is never read).  Only the blobs of the tiles the patches touch are read, each once."""
     readers = list(readers)
     hs = np.asarray([(r._h.value or 0) if r is not None else 0 for r in readers], dtype=np.uintp)
-    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_readers_read_patches", spec)(
+    rc, st, stats = _read_multi_patches(lambda a, n, d, cap, s, p: _door("mic_hip_wsi_readers_read_patches", spec, scale)(
         hs.ctypes.data, len(readers), a, n, pw, ph, channels, bits_per_sample, d, cap, s, p), xysl, d_out, out_cap)
     for r in readers:                                  # an exception a source raised comes first
         if r is not None and r._cb.exc is not None:
@@ -2469,9 +2500,9 @@ class Session:
         if rc:
             _raise(rc, "session_wsi_decode_level")
 
-    def wsi_read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None):
+    def wsi_read_patches(self, level: int, xy, pw: int, ph: int, d_out: int, out_cap: int, spec=None, scale=None):
         """wsi_read_patches from the slide wsi_encode left in the session (it stays in HBM); d_out on the session's device"""
-        rc, st, stats = _read_patches("session_wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_session_wsi_read_patches", spec)(
+        rc, st, stats = _read_patches("session_wsi_read_patches", lambda a, n, d, cap, s, p: _door("mic_hip_session_wsi_read_patches", spec, scale)(
             self._h, level, a, n, pw, ph, d, cap, s, p), xy, d_out, out_cap)
         if rc:
             _raise(rc, "session_wsi_read_patches")

@@ -807,10 +807,32 @@ int plan_patches(int level_w, int level_h, int tw, int th, const int32_t *xy, in
     return MIC_OK;
 }
 
+// ---- scaled patches: the judgement of a scale -----------------------------------------------------------------------------------
+// The scale of a _scaled door's call, num / den of a level pixel an output pixel: as the caller gave it, and behind judge() reduced,
+// with sw x sh, the source rectangle of a pw x ph patch.  unit(): 1 / 1, the _as door itself.
+struct Scale {
+    int num = 1, den = 1, sw = 0, sh = 0;
+    bool unit() const { return num == den; }
+    // mic_hip_wsi_scaled_extent: the only place a scale is judged
+    int judge(int pw, int ph) {
+        if (pw <= 0 || ph <= 0 || num <= 0 || den <= 0) return MIC_ERR_ARGS;
+        int a = num, b = den;
+        while (b) { const int t = a % b; a = b; b = t; }
+        num /= a; den /= a;
+        if (den > num || (int64_t)num > 16 * (int64_t)den || num > 1024) return MIC_ERR_ARGS;
+        // (the kernel's j * num, j <= pw, is 32 bits wide; a tensor that wide is nobody's patch)
+        if (((int64_t)pw + 1) * num > 0x7FFFFFFF || ((int64_t)ph + 1) * num > 0x7FFFFFFF) return MIC_ERR_UNSUPPORTED;
+        sw = (int)(((int64_t)pw * num + den - 1) / den); sh = (int)(((int64_t)ph * num + den - 1) / den);
+        return MIC_OK;
+    }
+};
+
 // What the three one-slide patch entry points check of their arguments before a device is touched; o = the output description,
-// *need = bytes of the patch tensor.
-int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const mic_hip_out_spec *spec, OutFormat &o, size_t out_cap, size_t *need) {
+// *need = bytes of the patch tensor.  sc (the _scaled doors): the call's scale, judged right behind pw, ph and n.
+int patch_args(const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const mic_hip_out_spec *spec, OutFormat &o, size_t out_cap, size_t *need,
+               Scale *sc = nullptr) {
     if (level < 0 || level >= m.nlev || pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xy)) return MIC_ERR_ARGS;
+    if (sc) { const int src = sc->judge(pw, ph); if (src) return src; }
     if (!m.supported()) return MIC_ERR_UNSUPPORTED;
     const int orc = o.make(spec, m.channels, m.bps, 1);
     if (orc) return orc;
@@ -1169,8 +1191,9 @@ int multi_plan(MultiPlan &plan, const int32_t *q, int n, int pw, int ph, int cha
 // what the entry points check before a file is looked at; o = the output description of a call on nsources slides, *need = bytes of
 // the patch tensor
 int multi_args(const int32_t *xysl, int n, int pw, int ph, int channels, int bps, const mic_hip_out_spec *spec, int nsources, OutFormat &o,
-               size_t out_cap, size_t *need) {
+               size_t out_cap, size_t *need, Scale *sc = nullptr) {
     if (pw <= 0 || ph <= 0 || n < 0 || (n > 0 && !xysl)) return MIC_ERR_ARGS;
+    if (sc) { const int src = sc->judge(pw, ph); if (src) return src; }
     if (!((channels == 3 && bps == 8) || (channels == 1 && (bps == 8 || bps == 16)))) return MIC_ERR_UNSUPPORTED;   // (Mic3::supported)
     const int rc = o.make(spec, channels, bps, nsources);
     if (rc) return rc;
@@ -1250,6 +1273,144 @@ int multi_call(MultiPlan &plan, const MultiFetch &fetch, const int32_t *xysl, in
         for (const MultiSlide &sl : plan.slides) read += sl.header_ok ? 1 : 0;
         *stats = mic_hip_multi_patch_stats{ nu, plan.pieces.size(), nslab, read };
     }
+    return MIC_OK;
+}
+
+// ---- scaled patches: groups of source rectangles through the native core, then the resample -----------------------------------------
+// A call of a _scaled door whose scale is not 1 / 1, on a session the caller holds, d_out and its alignment judged.  An output
+// pixel's footprint straddles tiles that may sit in different sub-batches or in cache slots, so the gather cannot average in one pass
+// and stay exact; as with the MIC2 temporal crops there is a staging tensor instead: the door's own native call (`group`: plan,
+// sub-batches, cache split, gather -- unchanged) reads the n rectangles of sw x sh into s->wsi_stage, and one launch of
+// k_resample_patches writes every sample of d_out.  The staging tensor may take a quarter of the workspace ceiling; n patches that
+// need more go as consecutive groups, each one native call and one resample launch.
+// group(i0, ng, d_stage, bytes, status, t, recs): patches [i0, i0 + ng) into d_stage, their statuses, the native call's stats, and
+// their records (what of each source rectangle lies inside its level; empty where the native door zeroes the patch).
+// whole(t): the plan counts of the whole call at sw x sh (host only), asked when the call was cut: pieces and slides are the plan's;
+// so are the tiles unless a tile cache is in play (cached), where they stay what the groups really decoded.
+struct ScaledTotals { uint64_t tiles = 0, pieces = 0, slabs = 0, slides = 0; };
+typedef std::function<int(int i0, int ng, void *d_stage, size_t bytes, int32_t *status, ScaledTotals &t, ScaledPatch *recs)> ScaledGroup;
+typedef std::function<int(ScaledTotals &t)> ScaledWhole;
+
+int scaled_patches(mic_hip_session *s, const Scale &sc, int channels, int bps, int n, int pw, int ph, const OutFormat &o, void *d_out,
+                   int32_t *status, bool cached, const ScaledGroup &group, const ScaledWhole &whole, ScaledTotals &tot) {
+    const size_t spx = (size_t)channels * (bps == 16 ? 2 : 1);                              // bytes of a native pixel
+    const unsigned __int128 pb128 = (unsigned __int128)(unsigned)sc.sw * (unsigned)sc.sh * spx;
+    if (pb128 > ((size_t)1 << 40)) return MIC_ERR_CAPACITY;                                  // (one source rectangle that no device holds)
+    const size_t pb = (size_t)pb128;
+    const size_t gmax = std::min<size_t>((size_t)n, std::max<size_t>(1, workspace_budget() / 4 / pb));
+    const size_t stage_bytes = align_up(gmax * pb, 16), rec_bytes = align_up(gmax * sizeof(ScaledPatch), 16);
+    int rc;
+    if ((rc = s->ensure(1, 1))) return rc;                                                  // (the session's stream)
+    if ((rc = s->wsi_stage.reserve(stage_bytes + rec_bytes + o.table_bytes() + 64))) return rc;
+    char *base = (char *)s->wsi_stage.p;
+    ScaledPatch *d_recs = (ScaledPatch *)(base + stage_bytes);
+    void *d_table = base + stage_bytes + rec_bytes;
+    if (o.typed()) HIP_TRY(hipMemcpyAsync(d_table, o.table.data(), o.table_bytes(), hipMemcpyHostToDevice, s->stream));
+    std::vector<ScaledPatch> recs((size_t)n);                                               // (lives until the synchronise below)
+    const ScaledGeom g{ pw, ph, sc.sw, sc.sh, sc.num, sc.den, o.pad_bits() };
+    tot = ScaledTotals();
+    size_t groups = 0;
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += gmax, groups++) {
+        const size_t ng = std::min(gmax, (size_t)n - i0);
+        ScaledTotals t;
+        s->timer.reset(s->stream);                                                          // (a native call that launches nothing marks nothing)
+        if ((rc = group((int)i0, (int)ng, base, ng * pb, status ? status + i0 : nullptr, t, recs.data() + i0))) return rc;
+        tot.tiles += t.tiles; tot.pieces += t.pieces; tot.slabs += t.slabs; tot.slides = std::max(tot.slides, t.slides);
+        HIP_TRY(hipMemcpyAsync(d_recs, recs.data() + i0, ng * sizeof(ScaledPatch), hipMemcpyHostToDevice, s->stream));
+        s->timer.mark("k_wsi_resample");                                                    // behind the marks of the native call's last sub-batch
+        launch_resample(s->stream, channels, bps, o, d_table, base, d_recs, ng, g, (char *)d_out + i0 * (size_t)ph * (size_t)pw * o.pixel());
+        s->timer.mark("end");
+        HIP_TRY(hipGetLastError());                                                         // (the next group's native call follows on the stream)
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (groups > 1) {
+        ScaledTotals w;
+        if ((rc = whole(w))) return rc;
+        tot.pieces = w.pieces; tot.slides = w.slides;
+        if (!cached) tot.tiles = w.tiles;
+    }
+    return MIC_OK;
+}
+// a patch's record: what of its source rectangle at (x, y) lies inside a level of lw x lh
+ScaledPatch scaled_record(const Scale &sc, int64_t x, int64_t y, int64_t lw, int64_t lh, int32_t source) {
+    const int64_t x0 = std::max<int64_t>(0, -x), x1 = std::min<int64_t>(sc.sw, lw - x), y0 = std::max<int64_t>(0, -y), y1 = std::min<int64_t>(sc.sh, lh - y);
+    if (x0 >= x1 || y0 >= y1) return ScaledPatch{ 0, 0, 0, 0, source, 0 };
+    return ScaledPatch{ (int32_t)x0, (int32_t)x1, (int32_t)y0, (int32_t)y1, source, 0 };
+}
+
+// The one-slide doors' scaled call on a parsed header: `native` is the door's own core call (wsi_patches on its source, or the
+// session store's) for rectangles of sw x sh in the slide's format.
+typedef std::function<int(const int32_t *xy, int n, void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats)> NativePatches;
+int scaled_level(mic_hip_session *s, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const Scale &sc, const OutFormat &o, void *d_out,
+                 int32_t *status, mic_hip_patch_stats *stats, bool cached, const NativePatches &native) {
+    const Level &L = m.lv[(size_t)level];
+    ScaledTotals tot;
+    const int rc = scaled_patches(s, sc, m.channels, m.bps, n, pw, ph, o, d_out, status, cached,
+        [&](int i0, int ng, void *d_stage, size_t bytes, int32_t *st, ScaledTotals &t, ScaledPatch *recs) -> int {
+            mic_hip_patch_stats ps{ 0, 0, 0 };
+            const int r = native(xy + 2 * (size_t)i0, ng, d_stage, bytes, st, &ps);
+            if (r) return r;
+            t.tiles = ps.tiles_decoded; t.pieces = ps.pieces; t.slabs = ps.slabs;
+            for (int i = 0; i < ng; i++) recs[i] = scaled_record(sc, xy[2 * ((size_t)i0 + i)], xy[2 * ((size_t)i0 + i) + 1], L.w, L.h, 0);
+            return MIC_OK;
+        },
+        [&](ScaledTotals &t) -> int {
+            PatchPlan plan;
+            const int r = plan_patches(L.w, L.h, m.tw, m.th, xy, n, sc.sw, sc.sh, plan);
+            t.tiles = plan.units.size(); t.pieces = plan.pieces.size();
+            return r;
+        }, tot);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_patch_stats{ tot.tiles, tot.pieces, tot.slabs };
+    return MIC_OK;
+}
+
+// The multi doors' scaled call, behind multi_args: what multi_call judges, in its order -- the slide indices, n == 0, the pointer --,
+// then multi_call itself group by group on a fresh plan each (slides(plan) sets the plan's slides as the door does).
+int multi_call_scaled(const std::function<void(MultiPlan &)> &slides, int nslides, const MultiFetch &fetch, const int32_t *xysl, int n, int pw, int ph,
+                      int channels, int bps, const Scale &sc, const OutFormat &o, void *d_out, size_t need, int32_t *status, mic_hip_multi_patch_stats *stats,
+                      const std::function<CacheOwner(uint32_t f)> &cache_of, bool cached) {
+    for (int i = 0; i < n; i++) if (xysl[4 * (size_t)i + 2] < 0 || xysl[4 * (size_t)i + 2] >= nslides) return MIC_ERR_ARGS;
+    if (stats) *stats = mic_hip_multi_patch_stats{ 0, 0, 0, 0 };
+    if (n == 0) return MIC_OK;
+    if (!d_out) return MIC_ERR_ARGS;
+    DefaultLease lease;
+    int rc;
+    if ((rc = lease.acquire())) return rc;
+    mic_hip_session *s = cur_default();
+    if ((rc = patch_pointer(s, &d_out, need))) return rc;
+    if (o.typed() ? !out_aligned(o, d_out) : (bps == 16 && ((size_t)d_out & 1))) return MIC_ERR_ARGS;
+    OutFormat on;
+    if ((rc = on.make(nullptr, channels, bps, 1))) return rc;
+    auto heads = [](const MultiPlan &plan) { uint64_t k = 0; for (const MultiSlide &sl : plan.slides) k += sl.header_ok ? 1 : 0; return k; };
+    ScaledTotals tot;
+    rc = scaled_patches(s, sc, channels, bps, n, pw, ph, o, d_out, status, cached,
+        [&](int i0, int ng, void *d_stage, size_t bytes, int32_t *st, ScaledTotals &t, ScaledPatch *recs) -> int {
+            MultiPlan plan;
+            slides(plan);
+            mic_hip_multi_patch_stats ms{ 0, 0, 0, 0 };
+            const int32_t *q = xysl + 4 * (size_t)i0;
+            const int r = multi_call(plan, fetch, q, ng, sc.sw, sc.sh, channels, bps, on, d_stage, bytes, st, &ms, cache_of);
+            if (r) return r;
+            t.tiles = ms.tiles_decoded; t.pieces = ms.pieces; t.slabs = ms.slabs; t.slides = ms.slides_read;
+            for (int i = 0; i < ng; i++) {                                                  // a refused slide, a level it does not have: all pad
+                const int32_t f = q[4 * (size_t)i + 2], level = q[4 * (size_t)i + 3];
+                const MultiSlide &sl = plan.slides[(size_t)f];
+                if (sl.status != MIC_OK || level < 0 || level >= (int)sl.hdr().lv.size()) { recs[i] = ScaledPatch{ 0, 0, 0, 0, f, 0 }; continue; }
+                const Level &L = sl.hdr().lv[(size_t)level];
+                recs[i] = scaled_record(sc, q[4 * (size_t)i], q[4 * (size_t)i + 1], L.w, L.h, f);
+            }
+            return MIC_OK;
+        },
+        [&](ScaledTotals &t) -> int {
+            MultiPlan plan;
+            slides(plan);
+            const int r = multi_plan(plan, xysl, n, sc.sw, sc.sh, channels, bps);
+            t.tiles = plan.units.size(); t.pieces = plan.pieces.size(); t.slides = heads(plan);
+            return r;
+        }, tot);
+    if (rc) return rc;
+    if (stats) *stats = mic_hip_multi_patch_stats{ tot.tiles, tot.pieces, tot.slabs, tot.slides };
     return MIC_OK;
 }
 }  // namespace
@@ -1457,21 +1618,58 @@ int mic_hip_wsi_patch_plan(int level_w, int level_h, int tile_w, int tile_h, con
     return MIC_OK;
 } MIC_ABI_CATCH
 
-// n patches of one level of a MIC3 file in host memory, into a tensor on the default session's device
-int mic_hip_wsi_read_patches_as(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
-                                void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+// mic_hip_wsi_scaled_extent: Scale::judge; needs no device
+int mic_hip_wsi_scaled_extent(int pw, int ph, int scale_num, int scale_den, int *sw, int *sh) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    const int rc = sc.judge(pw, ph);
+    if (rc) return rc;
+    if (sw) *sw = sc.sw;
+    if (sh) *sh = sc.sh;
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+// The scaled call of the file and reader doors on the session the thread holds: d_out judged as wsi_patches judges it, then the
+// door's own native call group by group (scaled_level).
+static int wsi_patches_scaled(const BlobSource &src, const Mic3 &m, int level, const int32_t *xy, int n, int pw, int ph, const Scale &sc, const OutFormat &o,
+                              void *d_out, size_t need, int32_t *status, mic_hip_patch_stats *stats, CacheOwner co = CacheOwner{ nullptr, 0, 0 }) {
+    mic_hip_session *s = cur_default();
+    int rc;
+    if ((rc = patch_pointer(s, &d_out, need))) return rc;
+    if (!out_aligned(o, d_out)) return MIC_ERR_ARGS;
+    OutFormat on;
+    if ((rc = on.make(nullptr, m.channels, m.bps, 1))) return rc;
+    return scaled_level(s, m, level, xy, n, pw, ph, sc, o, d_out, status, stats, co.c != nullptr,
+                        [&](const int32_t *q, int ng, void *d_stage, size_t bytes, int32_t *st, mic_hip_patch_stats *ps) {
+                            return wsi_patches(src, m, level, q, ng, sc.sw, sc.sh, on, d_stage, bytes, st, ps, co);
+                        });
+}
+
+// n patches of one level of a MIC3 file in host memory, into a tensor on the default session's device (sc: the _scaled door's scale)
+static int wsi_read_patches_door(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                                 void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec, Scale *sc) {
     if (!c) return MIC_ERR_ARGS;
     Mic3 m; int rc = parse_mic3(c, len, m);
     if (rc) return rc;
     size_t need = 0;
     OutFormat o;
-    if ((rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need))) return rc;
+    if ((rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need, sc))) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
+    if (sc && !sc->unit()) return wsi_patches_scaled(flat_source(c, len, m), m, level, xy, n, pw, ph, *sc, o, d_out, need, status, stats);
     return wsi_patches(flat_source(c, len, m), m, level, xy, n, pw, ph, o, d_out, need, status, stats);
+}
+int mic_hip_wsi_read_patches_as(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                                void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+    return wsi_read_patches_door(c, len, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_wsi_read_patches_scaled(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
+                                    void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                    int scale_num, int scale_den) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    return wsi_read_patches_door(c, len, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, &sc);
 } MIC_ABI_CATCH
 int mic_hip_wsi_read_patches(const uint8_t *c, size_t len, int level, const int32_t *xy, int n, int pw, int ph,
                              void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats) {
@@ -1501,18 +1699,35 @@ int mic_hip_wsi_multi_patch_plan(const uint8_t *const *files, const size_t *lens
 } MIC_ABI_CATCH
 
 // n patches of many MIC3 files in host memory, any levels, into a tensor on the default session's device
-int mic_hip_wsi_multi_read_patches_as(const uint8_t *const *files, const size_t *lens, int nfiles,
-                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
-                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
+static int wsi_multi_read_patches_door(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                       const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec, Scale *sc) {
     if (nfiles < 0 || (nfiles > 0 && (!files || !lens))) return MIC_ERR_ARGS;
     size_t need = 0;
     OutFormat o;
-    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nfiles, o, out_cap, &need);
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nfiles, o, out_cap, &need, sc);
     if (rc) return rc;
+    auto slides = [&](MultiPlan &plan) {
+        plan.slides.resize((size_t)nfiles);
+        for (int f = 0; f < nfiles; f++) { plan.slides[(size_t)f].head = files[f]; plan.slides[(size_t)f].file_len = lens[f]; }
+    };
+    if (sc && !sc->unit())
+        return multi_call_scaled(slides, nfiles, nullptr, xysl, n, pw, ph, channels, bits_per_sample, *sc, o, d_out, need, status, stats, nullptr, false);
     MultiPlan plan;
-    plan.slides.resize((size_t)nfiles);
-    for (int f = 0; f < nfiles; f++) { plan.slides[(size_t)f].head = files[f]; plan.slides[(size_t)f].file_len = lens[f]; }
+    slides(plan);
     return multi_call(plan, nullptr, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats);
+}
+int mic_hip_wsi_multi_read_patches_as(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                      void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
+    return wsi_multi_read_patches_door(files, lens, nfiles, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, spec, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_wsi_multi_read_patches_scaled(const uint8_t *const *files, const size_t *lens, int nfiles,
+                                          const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                          void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec,
+                                          int scale_num, int scale_den) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    return wsi_multi_read_patches_door(files, lens, nfiles, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, spec, &sc);
 } MIC_ABI_CATCH
 int mic_hip_wsi_multi_read_patches(const uint8_t *const *files, const size_t *lens, int nfiles,
                                    const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
@@ -1689,14 +1904,14 @@ int mic_hip_session_wsi_decode_level(mic_hip_session *s, int level, uint8_t *d_p
 
 // n patches of one level from the store: the plane records of the union's tiles as they stand (no blob is put together or parsed),
 // their bytes where mic_hip_session_wsi_encode left them
-int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
-                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+static int session_wsi_read_patches_door(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                         void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec, Scale *sc) {
     if (!s || !s->wsi) return MIC_ERR_ARGS;
     mic_hip_wsi_store &W = *s->wsi;
     Mic3 m = W.fmt; m.lv = W.lv; m.nlev = (int)W.lv.size();
     size_t need = 0;
     OutFormat o;
-    int rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need);
+    int rc = patch_args(m, level, xy, n, pw, ph, spec, o, out_cap, &need, sc);
     if (rc) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
@@ -1705,28 +1920,51 @@ int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int
     if (!out_aligned(o, d_out)) return MIC_ERR_ARGS;
     const Level &L = m.lv[(size_t)level];
     const size_t P = (size_t)m.planes();
-    PatchPlan plan;
-    if ((rc = plan_patches(L.w, L.h, m.tw, m.th, xy, n, pw, ph, plan))) return rc;
-    // the records of units [u0, u0 + nt) of `dp`: the plan, or what a tile cache has left of it to decode
-    auto records = [&](const PatchPlan &dp) {
-        return [&, P](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
-            for (size_t k = 0; k < nt; k++) {
-                const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)dp.units[u0 + k].tile) * P;
-                pl.insert(pl.end(), rec, rec + P);
-            }
-            *base = (const uint8_t *)W.bytes.p;
-            return MIC_OK;
+    // n patches of pw x ph at xy through the core into d_out as o says (the scaled call: its source rectangles into the staging tensor)
+    auto native = [&](const int32_t *q, int k, int w, int h, const OutFormat &of, void *dst, size_t bytes, int32_t *st, mic_hip_patch_stats *ps) -> int {
+        PatchPlan plan;
+        int r;
+        if ((r = plan_patches(L.w, L.h, m.tw, m.th, q, k, w, h, plan))) return r;
+        // the records of units [u0, u0 + nt) of `dp`: the plan, or what a tile cache has left of it to decode
+        auto records = [&](const PatchPlan &dp) {
+            return [&, P](size_t u0, size_t nt, const uint8_t **base, std::vector<WsiPlane> &pl, int32_t *) -> int {
+                for (size_t t = 0; t < nt; t++) {
+                    const WsiPlane *rec = W.planes.data() + ((size_t)L.first + (size_t)dp.units[u0 + t].tile) * P;
+                    pl.insert(pl.end(), rec, rec + P);
+                }
+                *base = (const uint8_t *)W.bytes.p;
+                return MIC_OK;
+            };
         };
+        if (s->tile_cache) {
+            CachePlan cp;
+            const CacheOwner co{ s->tile_cache, s->tile_owner, (uint64_t)L.first };
+            if ((r = cp.split(s, plan, std::vector<const Mic3 *>(plan.units.size(), &m), w, h, of, [&](size_t) { return co; }))) return r;
+            const std::vector<const Mic3 *> um(cp.decode.units.size(), &m);
+            return level_patches(s, cp.decode, um, k, w, h, of, [&](size_t) { return session_slab_tiles(m); }, records(cp.decode), dst, bytes, st, ps, &cp, &plan);
+        }
+        const std::vector<const Mic3 *> um(plan.units.size(), &m);
+        return level_patches(s, plan, um, k, w, h, of, [&](size_t) { return session_slab_tiles(m); }, records(plan), dst, bytes, st, ps);
     };
-    if (s->tile_cache) {
-        CachePlan cp;
-        const CacheOwner co{ s->tile_cache, s->tile_owner, (uint64_t)L.first };
-        if ((rc = cp.split(s, plan, std::vector<const Mic3 *>(plan.units.size(), &m), pw, ph, o, [&](size_t) { return co; }))) return rc;
-        const std::vector<const Mic3 *> um(cp.decode.units.size(), &m);
-        return level_patches(s, cp.decode, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); }, records(cp.decode), d_out, need, status, stats, &cp, &plan);
+    if (sc && !sc->unit()) {
+        OutFormat on;
+        if ((rc = on.make(nullptr, m.channels, m.bps, 1))) return rc;
+        return scaled_level(s, m, level, xy, n, pw, ph, *sc, o, d_out, status, stats, s->tile_cache != nullptr,
+                            [&](const int32_t *q, int ng, void *d_stage, size_t bytes, int32_t *st, mic_hip_patch_stats *ps) {
+                                return native(q, ng, sc->sw, sc->sh, on, d_stage, bytes, st, ps);
+                            });
     }
-    const std::vector<const Mic3 *> um(plan.units.size(), &m);
-    return level_patches(s, plan, um, n, pw, ph, o, [&](size_t) { return session_slab_tiles(m); }, records(plan), d_out, need, status, stats);
+    return native(xy, n, pw, ph, o, d_out, need, status, stats);
+}
+int mic_hip_session_wsi_read_patches_as(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+    return session_wsi_read_patches_door(s, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_session_wsi_read_patches_scaled(mic_hip_session *s, int level, const int32_t *xy, int n, int pw, int ph,
+                                            void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                            int scale_num, int scale_den) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    return session_wsi_read_patches_door(s, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, &sc);
 } MIC_ABI_CATCH
 
 int mic_hip_session_set_tile_cache(mic_hip_session *s, mic_hip_tile_cache *c) try {
@@ -2149,20 +2387,32 @@ int mic_hip_wsi_reader_decompress_region(mic_hip_wsi_reader *r, int level, int x
     return wsi_region(r->source(), r->m, level, x, y, w, h, out, out_cap, out_w, out_h);
 } MIC_ABI_CATCH
 
-int mic_hip_wsi_reader_read_patches_as(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
-                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+static int wsi_reader_read_patches_door(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec, Scale *sc) {
     if (!r) return MIC_ERR_ARGS;
     std::lock_guard<std::mutex> lk(r->mu);
     size_t need = 0;
     OutFormat o;
-    int rc = patch_args(r->m, level, xy, n, pw, ph, spec, o, out_cap, &need);
+    int rc = patch_args(r->m, level, xy, n, pw, ph, spec, o, out_cap, &need, sc);
     if (rc) return rc;
     if (stats) *stats = mic_hip_patch_stats{ 0, 0, 0 };
     if (n == 0) return MIC_OK;
     if (!d_out) return MIC_ERR_ARGS;
     DefaultLease lease;
     if ((rc = lease.acquire())) return rc;
-    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, o, d_out, need, status, stats, CacheOwner{ r->cache, r->owner, 0 });
+    const CacheOwner co{ r->cache, r->owner, 0 };
+    if (sc && !sc->unit()) return wsi_patches_scaled(r->source(), r->m, level, xy, n, pw, ph, *sc, o, d_out, need, status, stats, co);
+    return wsi_patches(r->source(), r->m, level, xy, n, pw, ph, o, d_out, need, status, stats, co);
+}
+int mic_hip_wsi_reader_read_patches_as(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                       void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec) try {
+    return wsi_reader_read_patches_door(r, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_wsi_reader_read_patches_scaled(mic_hip_wsi_reader *r, int level, const int32_t *xy, int n, int pw, int ph,
+                                           void *d_out, size_t out_cap, int32_t *status, mic_hip_patch_stats *stats, const mic_hip_out_spec *spec,
+                                           int scale_num, int scale_den) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    return wsi_reader_read_patches_door(r, level, xy, n, pw, ph, d_out, out_cap, status, stats, spec, &sc);
 } MIC_ABI_CATCH
 
 int mic_hip_wsi_reader_set_cache(mic_hip_wsi_reader *r, mic_hip_tile_cache *c) try {
@@ -2193,13 +2443,13 @@ int mic_hip_wsi_reader_read_patches(mic_hip_wsi_reader *r, int level, const int3
 
 // mic_hip_wsi_multi_read_patches through readers.  Only the readers some patch names are touched: each distinct one is locked once,
 // in address order (one order for every caller), and asked for its blobs in one fetch.
-int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int nreaders,
-                                        const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
-                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
+static int wsi_readers_read_patches_door(mic_hip_wsi_reader *const *readers, int nreaders,
+                                         const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                         void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec, Scale *sc) {
     if (nreaders < 0 || (nreaders > 0 && !readers)) return MIC_ERR_ARGS;
     size_t need = 0;
     OutFormat o;
-    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nreaders, o, out_cap, &need);
+    const int rc = multi_args(xysl, n, pw, ph, channels, bits_per_sample, spec, nreaders, o, out_cap, &need, sc);
     if (rc) return rc;
     std::vector<mic_hip_wsi_reader *> named;
     for (int i = 0; i < n; i++) {
@@ -2212,17 +2462,39 @@ int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int 
     std::vector<std::unique_lock<std::mutex>> locks;
     locks.reserve(named.size());
     for (mic_hip_wsi_reader *r : named) locks.emplace_back(r->mu);
-    MultiPlan plan;
-    plan.slides.resize((size_t)nreaders);
-    for (int i = 0; i < n; i++) {
-        const size_t f = (size_t)xysl[4 * (size_t)i + 2];
-        mic_hip_wsi_reader *r = readers[f];
-        if (r) { plan.slides[f].head = r->head.data(); plan.slides[f].file_len = r->file_len; plan.slides[f].m = &r->m; }
-    }
-    return multi_call(plan, [&](uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
+    auto slides = [&](MultiPlan &plan) {
+        plan.slides.resize((size_t)nreaders);
+        for (int i = 0; i < n; i++) {
+            const size_t f = (size_t)xysl[4 * (size_t)i + 2];
+            mic_hip_wsi_reader *r = readers[f];
+            if (r) { plan.slides[f].head = r->head.data(); plan.slides[f].file_len = r->file_len; plan.slides[f].m = &r->m; }
+        }
+    };
+    const MultiFetch fetch = [&](uint32_t f, const std::vector<size_t> &tiles, std::vector<TileBlob> &blobs, std::vector<uint8_t> &keep) {
         return readers[f]->fetch(tiles, blobs, keep);
-    }, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats,
-    [&](uint32_t f) { return CacheOwner{ readers[f]->cache, readers[f]->owner, 0 }; });     // (each reader its own cache, shared, or none; a unit's reader is one of `named`)
+    };
+    // (each reader its own cache, shared, or none; a unit's reader is one of `named`)
+    const std::function<CacheOwner(uint32_t)> cache_of = [&](uint32_t f) { return CacheOwner{ readers[f]->cache, readers[f]->owner, 0 }; };
+    if (sc && !sc->unit()) {
+        bool cached = false;
+        for (mic_hip_wsi_reader *r : named) cached = cached || r->cache != nullptr;
+        return multi_call_scaled(slides, nreaders, fetch, xysl, n, pw, ph, channels, bits_per_sample, *sc, o, d_out, need, status, stats, cache_of, cached);
+    }
+    MultiPlan plan;
+    slides(plan);
+    return multi_call(plan, fetch, xysl, n, pw, ph, channels, bits_per_sample, o, d_out, need, status, stats, cache_of);
+}
+int mic_hip_wsi_readers_read_patches_as(mic_hip_wsi_reader *const *readers, int nreaders,
+                                        const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                        void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec) try {
+    return wsi_readers_read_patches_door(readers, nreaders, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, spec, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_wsi_readers_read_patches_scaled(mic_hip_wsi_reader *const *readers, int nreaders,
+                                            const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,
+                                            void *d_out, size_t out_cap, int32_t *status, mic_hip_multi_patch_stats *stats, const mic_hip_out_spec *spec,
+                                            int scale_num, int scale_den) try {
+    Scale sc; sc.num = scale_num; sc.den = scale_den;
+    return wsi_readers_read_patches_door(readers, nreaders, xysl, n, pw, ph, channels, bits_per_sample, d_out, out_cap, status, stats, spec, &sc);
 } MIC_ABI_CATCH
 int mic_hip_wsi_readers_read_patches(mic_hip_wsi_reader *const *readers, int nreaders,
                                      const int32_t *xysl, int n, int pw, int ph, int channels, int bits_per_sample,

@@ -4,10 +4,12 @@
 // Here: the kernels that copy and their launcher, the judgement of the output pointer, the crop doors' way to a session, and the
 // packing of a sub-batch's streams; and the typed output of the _as doors (mic_hip_out_spec): its one judgement, the typed gather
 // kernels, the pad fill and the convert kernel of the MIC2 temporal staging tensor; and the kernels of the MIC3 tile cache
-// (mic_tile_cache.h): the fill of freshly decoded tiles into pixel slots and the gathers that read pieces out of them.
+// (mic_tile_cache.h): the fill of freshly decoded tiles into pixel slots and the gathers that read pieces out of them; and the
+// resample kernel of the scaled MIC3 patch doors, which area-averages a staging tensor of native patches into the output tensor.
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
 #include <cmath>
+#include <type_traits>
 #include "mic_session.h"
 #include "mic_pieces.h"
 #include "mic_px_copy.h"
@@ -255,6 +257,86 @@ __global__ void __launch_bounds__(256) k_convert_runs(const uint16_t *stage, con
         }
 }
 
+// ---- scaled MIC3 patches: the staging tensor's native pixels, area-averaged, to the tensor -----------------------------------------
+// The value (include/mic_hip.h): output pixel (x, y) of a patch covers [x * num, (x + 1) * num) x [y * num, (y + 1) * num) in units of
+// 1 / den of a source pixel, source pixel (k, l) covers [k * den, (k + 1) * den) x [l * den, (l + 1) * den); per channel
+// S = sum_l wy * sum_k wx * p(k, l) over the overlaps' lengths and v = (S + num^2 / 2) / num^2.  The footprint's columns are k0 =
+// x * num / den .. k1 = ((x + 1) * num - 1) / den: the first weighs (k0 + 1) * den - x * num, the last (x + 1) * num - k1 * den, every
+// one between den (num >= den: a footprint never lies inside one source pixel unless it IS that pixel, num == den); rows alike.
+// A row's sum stays below 1024 * 65535 < 2^26; S reaches 1024^2 * 65535 < 2^36, so 16-bit sources sum in 64 bits, 8-bit ones
+// (below 2^28) in 32.  One division per output sample.
+// grid = (patches, row chunks), the lanes of a piece (piece_lanes(pw)): lanes along output x.  Adjacent lanes' footprints are adjacent
+// in the source row, so step t of the column loop reads addresses num / den pixels apart across the wave and the wave's whole
+// span of each source row, 64 * num / den pixels, within k1 - k0 + 1 <= 17 steps: every byte of every line it touches is used, out of L1
+// from the second step on.  The 3-byte source reads its bytes one by one: a lane's pixels are num / den * 3 bytes from its
+// neighbour's, so no dword holds what two lanes need, and px_row_dwords' skewed dwords would be assembled per lane and pixel for
+// three bytes each.  A pixel whose footprint misses the patch's part of the level is pad; the staging tensor is 0 where the level is not.
+template <int DT, typename S> struct ScaledOut { typedef typename OutBits<DT>::type type; };
+template <typename S> struct ScaledOut<MIC_HIP_OUT_NATIVE, S> { typedef S type; };
+struct Footprint { int first, last, w_first, w_last; };     // source columns (rows) first .. last; the weights of the two ends (last > first)
+__device__ __forceinline__ Footprint footprint(int j, int num, int den) {
+    const int a = j * num, k0 = a / den, k1 = (a + num - 1) / den;
+    return Footprint{ k0, k1, min((k0 + 1) * den, a + num) - a, a + num - k1 * den };
+}
+template <int DT, typename S, int C>
+__global__ void __launch_bounds__(256) k_resample_patches(const S *stage, const ScaledPatch *recs, typename ScaledOut<DT, S>::type *out, const ScaledGeom g, const OutParams o) {
+    typedef typename ScaledOut<DT, S>::type T;
+    typedef typename std::conditional<sizeof(S) == 2, uint64_t, uint32_t>::type Acc;
+    const ScaledPatch rp = recs[blockIdx.x];
+    const PieceLanes ln = piece_lanes(g.pw);
+    const mic_gp<const S> src = mic_g(stage + (size_t)blockIdx.x * (size_t)g.sh * (size_t)g.sw * C);
+    const size_t area = (size_t)g.ph * (size_t)g.pw;
+    const mic_gp<T> dst = mic_g(out + (size_t)blockIdx.x * area * C);
+    const bool planar = C > 1 && DT != MIC_HIP_OUT_NATIVE && o.plane != 1;
+    const size_t cstep = planar ? area : 1;
+    Pair ab[C];
+    if (DT != MIC_HIP_OUT_NATIVE) {
+#pragma unroll
+        for (int c = 0; c < C; c++) ab[c] = out_pair(o, (size_t)rp.source * o.src_mul + (size_t)c * o.ch_step);
+    }
+    const Acc nn = (Acc)g.num * (Acc)g.num, half = nn / 2;
+    for (int x = ln.col; x < g.pw; x += ln.lw) {
+        const Footprint fx = footprint(x, g.num, g.den);
+        const bool x_in = fx.last >= rp.x0 && fx.first < rp.x1;
+        for (int y = ln.row; y < g.ph; y += ln.rstep) {
+            const Footprint fy = footprint(y, g.num, g.den);
+            const size_t di = ((size_t)y * g.pw + x) * (planar ? 1 : C);
+            if (!(x_in && fy.last >= rp.y0 && fy.first < rp.y1)) {
+#pragma unroll
+                for (int c = 0; c < C; c++) dst[di + c * cstep] = (T)g.pad_bits;
+                continue;
+            }
+            Acc sum[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) sum[c] = 0;
+            for (int l = fy.first; l <= fy.last; l++) {
+                const uint32_t wy = l == fy.first ? (uint32_t)fy.w_first : l == fy.last ? (uint32_t)fy.w_last : (uint32_t)g.den;
+                const mic_gp<const S> row = src + ((size_t)l * g.sw + fx.first) * C;
+                uint32_t mid[C], ends[C];
+#pragma unroll
+                for (int c = 0; c < C; c++) { ends[c] = (uint32_t)fx.w_first * row[c]; mid[c] = 0; }
+                const int nk = fx.last - fx.first;
+                for (int k = 1; k < nk; k++) {
+#pragma unroll
+                    for (int c = 0; c < C; c++) mid[c] += row[k * C + c];
+                }
+                if (nk > 0) {
+#pragma unroll
+                    for (int c = 0; c < C; c++) ends[c] += (uint32_t)fx.w_last * row[nk * C + c];
+                }
+#pragma unroll
+                for (int c = 0; c < C; c++) sum[c] += (Acc)wy * (Acc)(ends[c] + mid[c] * (uint32_t)g.den);
+            }
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const uint32_t v = (uint32_t)((sum[c] + half) / nn);
+                if (DT == MIC_HIP_OUT_NATIVE) dst[di + c * cstep] = (T)v;
+                else dst[di + c * cstep] = (T)out_sample<DT>(v, ab[c], o);
+            }
+        }
+    }
+}
+
 // n dwords of `bits` from d (4-byte aligned)
 __global__ void __launch_bounds__(256) k_fill_dwords(uint32_t *d, size_t n, uint32_t bits) {
     const mic_gp<uint32_t> g = mic_g(d);
@@ -342,6 +424,39 @@ void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table,
         case MIC_HIP_OUT_BF16: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_BF16>, grid, block, 0, stream, stage, runs + q, (uint16_t *)out, cw, ch, op); break;
         default: hipLaunchKernelGGL(k_convert_runs<MIC_HIP_OUT_F32>, grid, block, 0, stream, stage, runs + q, (uint32_t *)out, cw, ch, op); break;
         }
+    }
+}
+
+namespace {
+// the launches of one source format: S samples, C a pixel
+template <typename S, int C>
+void resample_as(hipStream_t stream, const dim3 &grid, int dtype, const OutParams &op, const void *stage, const ScaledPatch *recs, const ScaledGeom &g, void *out) {
+    const dim3 block(256);
+    const S *st = (const S *)stage;
+    switch (dtype) {
+    case MIC_HIP_OUT_NATIVE: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_NATIVE, S, C>), grid, block, 0, stream, st, recs, (S *)out, g, op); break;
+    case MIC_HIP_OUT_U8: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_U8, S, C>), grid, block, 0, stream, st, recs, (uint8_t *)out, g, op); break;
+    case MIC_HIP_OUT_U16: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_U16, S, C>), grid, block, 0, stream, st, recs, (uint16_t *)out, g, op); break;
+    case MIC_HIP_OUT_F16: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_F16, S, C>), grid, block, 0, stream, st, recs, (uint16_t *)out, g, op); break;
+    case MIC_HIP_OUT_BF16: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_BF16, S, C>), grid, block, 0, stream, st, recs, (uint16_t *)out, g, op); break;
+    default: hipLaunchKernelGGL((k_resample_patches<MIC_HIP_OUT_F32, S, C>), grid, block, 0, stream, st, recs, (uint32_t *)out, g, op); break;
+    }
+}
+}  // namespace
+
+void launch_resample(hipStream_t stream, int channels, int bits_per_sample, const OutFormat &o, const void *d_table, const void *stage,
+                     const ScaledPatch *recs, size_t n, const ScaledGeom &g, void *out) {
+    constexpr size_t kMaxGridX = 0x7FFFFFFF;
+    const unsigned gy = row_chunks(g.pw, g.ph);
+    const OutParams op = o.params(d_table, (size_t)g.ph * (size_t)g.pw);
+    const size_t spx = (size_t)channels * (bits_per_sample == 16 ? 2 : 1);                 // bytes of a staged pixel
+    for (size_t q = 0; q < n; q += kMaxGridX) {
+        const dim3 grid((unsigned)std::min(n - q, kMaxGridX), gy);
+        const void *st = (const char *)stage + q * (size_t)g.sh * (size_t)g.sw * spx;
+        void *dq = (char *)out + q * (size_t)g.ph * (size_t)g.pw * o.pixel();
+        if (channels == 3) resample_as<uint8_t, 3>(stream, grid, o.dtype, op, st, recs + q, g, dq);
+        else if (bits_per_sample == 16) resample_as<uint16_t, 1>(stream, grid, o.dtype, op, st, recs + q, g, dq);
+        else resample_as<uint8_t, 1>(stream, grid, o.dtype, op, st, recs + q, g, dq);
     }
 }
 

@@ -79,6 +79,16 @@ int fill_pad(hipStream_t stream, const OutFormat &o, void *d_out, size_t bytes);
 struct ConvertRun { uint64_t at; int32_t w, h, d, source; };
 void launch_convert(hipStream_t stream, const OutFormat &o, const void *d_table, const uint16_t *stage, const ConvertRun *runs, size_t n,
                     int mw, int mh, int md, int cw, int ch, void *out);
+// Scaled MIC3 patches (the _scaled doors, mic_api_ext.hip): patch i of a group lies as sh x sw native pixels, zero outside the level,
+// at pixel i * sh * sw of the staging tensor.  Its record: the part of the source rectangle inside the level, [x0, x1) x [y0, y1) in
+// source coordinates (empty: a patch that is all pad), and the source whose affine pair it takes.
+struct ScaledPatch { int32_t x0, x1, y0, y1, source, pad; };
+// one call's geometry: pw x ph output pixels a patch out of sw x sh source pixels at num / den; pad_bits: OutFormat::pad_bits
+struct ScaledGeom { int32_t pw, ph, sw, sh, num, den; uint32_t pad_bits; };
+// n patches of the staging tensor (channels x bits_per_sample: the slides' sample format) area-averaged into `out`, patch after patch
+// as o lays them out, behind what `stream` holds: one launch per 2^31 - 1 patches
+void launch_resample(hipStream_t stream, int channels, int bits_per_sample, const OutFormat &o, const void *d_table, const void *stage,
+                     const ScaledPatch *recs, size_t n, const ScaledGeom &g, void *out);
 // what a piece's samples become in the tensor: u16 as they are, u8 (uint16ToBytes), three YCoCg-R planes' RGB bytes, or the same
 // from planes of three kinds (RgbPlaneSrc)
 // ; or, out of pixel slots of the tile cache (`slab` is then the arena): u8, u16 or interleaved RGB pixels as they are

@@ -180,6 +180,7 @@ struct mic_hip_session {
     mic_hip_tile_cache *tile_cache = nullptr; uint64_t tile_owner = 0;   // mic_hip_session_set_tile_cache: the cache of decoded tiles the store's patch calls use, and the store generation's owner number in it
     DevBuf pieces;                         // patch and crop calls: the call's piece list (GatherPiece, mic_pieces.h; MIC2 temporal: its footprints)
     DevBuf crop_stage;                     // MIC2 crops into a typed tensor: the u16 tensor the temporal volumes' running sums live in (mic_mic2_crops.hip)
+    DevBuf wsi_stage;                      // MIC3 scaled patches: a group's native source rectangles, its patch records and the affine table (mic_api_ext.hip)
     DevBuf wsi_fills;                      // MIC3 decode: a slab's constant-plane spans (mic_api_ext.hip)
     std::vector<uint8_t> wsi_host_bytes;   // MIC3 patches from blobs: a sub-batch's stream bytes on their way up; kept, so that a loop of calls touches the same pages
     DevBuf rgb_planes, rgb_aux;            // RGB batches: a sub-batch's YCoCg-R planes; its tables, statistics and records (mic_rgb_batch.hip)
@@ -341,13 +342,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
