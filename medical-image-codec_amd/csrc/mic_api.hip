@@ -158,6 +158,7 @@ static int encode_enqueue_tier(mic_hip_session *s, const uint16_t *d_pixels, con
     for (int i = 0; i < n; i++) {
         if ((size_t)units[i].width * (size_t)units[i].height <= 131072u) enc_hint |= MIC_ENC_CLS_SMALL12 | MIC_ENC_CLS_SMALL13;
         if (units[i].max_value >= 2048u) enc_hint |= MIC_ENC_CLS_TL14 | MIC_ENC_CLS_TL15 | MIC_ENC_CLS_TL16;
+        if (units[i].max_value < 4096u) enc_hint |= MIC_ENC_TBL_C4K;                 // (tokens of a frame of up to 12 bits stay below 4096: the compact table instance)
     }
     const int variant = s->variant | MIC_VARIANT_FRAMES | (any_grad ? MIC_VARIANT_GRAD : 0) | (narrow ? MIC_VARIANT_NARROW : 0) | (any_gap ? MIC_VARIANT_GAP : 0);
     if ((rc = s->run_encode([&] {
@@ -262,6 +263,7 @@ static void learn_classes(mic_hip_session *s, int n) {
             const MicUnit &u = s->h_units[(size_t)i];
             const uint32_t tl = u.table_log;
             if (tl < MIC_MIN_TABLELOG || tl > MIC_MAX_TABLELOG) continue;                 // (the chain stopped in front of the tANS stage)
+            if (tl <= 13 && u.symbol_len <= 4096u && u.nstates != 108) seen |= MIC_ENC_TBL_C4K;   // tb_is_c4k, mic_tables.hip: by the rule, whichever instance ran
             if (tl == 14) seen |= MIC_ENC_CLS_TL14;
             else if (tl == 15) seen |= MIC_ENC_CLS_TL15;
             else if (tl == 16) seen |= MIC_ENC_CLS_TL16;
@@ -733,6 +735,13 @@ int mic_hip_debug_split8_config(mic_hip_session *s, uint32_t min_tokens8) try {
     s->dec_classes = mic_hip_session::ClsMemory{};
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): how far the chain behind the tables brought unit i (MicUnit.dec_stage: MIC_STAGE_*,
+// mic_dev.h; 4 = k_dec_rows_tok made its pixels) after a decode's *_finish
+int mic_hip_debug_dec_stage(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    *out = s->h_units[(size_t)i].dec_stage;
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py
 // holds its own restatement against it, value by value)
 int mic_hip_debug_dec_cls(uint32_t flavour, uint32_t table_log, uint32_t zero_bits) { return mic_dec_cls(flavour, table_log, zero_bits); }
@@ -760,6 +769,13 @@ int mic_hip_debug_fetch_tok(mic_hip_session *s, int i, void *dst, size_t n) try 
 int mic_hip_debug_tab_route(mic_hip_session *s, int i, uint32_t *out) try {
     if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
     *out = s->h_units[(size_t)i].tb_route;
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug probe (not in the public header): which instance of the table kernel built unit i's tables (MicUnit.tb_inst: MIC_TBI_*,
+// mic_dev.h; 0: neither) after a *_finish
+int mic_hip_debug_tab_inst(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    *out = s->h_units[(size_t)i].tb_inst;
     return MIC_OK;
 } MIC_ABI_CATCH
 // debug probe (not in the public header): which tANS encode kernel decided unit i (MicUnit.enc_kernel, mic_dev.h) after an encode's

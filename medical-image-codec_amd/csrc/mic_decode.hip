@@ -267,7 +267,8 @@ void mic_launch_decode(MicUnit *d_units, int n, hipStream_t stream, int variant,
     const bool any_grad = (variant & MIC_VARIANT_GRAD) != 0, gap = (variant & MIC_VARIANT_GAP) != 0;
     if (gap) mic_launch_dec_gap_map(d_units, n, stream, t);
     if (t) t->mark("k_dec_tables_wg");
-    mic_launch_dec_tables(d_units, n, stream);
+    // (classes 0-5: tableLog 13, 24-29: tableLog <= 12 -- what the compact table instance can take; a mask of all ones: unknown)
+    mic_launch_dec_tables(d_units, n, stream, (cls_mask & (0x3F00003Fu | MIC_CLS_SPLIT)) != 0);
     if (gap) mic_launch_dec_gap_expand(d_units, n, stream, t);
     // lane-per-state kernels over compacted per-class lists (mic_decode_ls.hip): every table size has its class; what they leave
     // (a tableLog-16 table with 0-bit entries, 1-state streams) falls through to the kernels below, which skip decoded units

@@ -88,6 +88,10 @@ struct MicSplitCfg {
 #define MIC_TBR_P_BIG_STAGE     (1u << 13)   // parsed by k_dec_parse<true> from its 40 KiB stage
 #define MIC_TBR_P_BIG_HBM       (1u << 14)   // parsed by k_dec_parse<true> starting over from HBM
 #define MIC_TBR_P_WINDOW        (1u << 15)   // the window loop of mic_read_ncount read at least one field (clear: the byte-wise loop read them all)
+// MicUnit.tb_inst: the instance of the table kernel that took the unit (mic_tables.hip).  A word of its own, not a seventeenth route
+// bit: tb_route's upper half is the big-symbol count, and its value is compared as a whole with the model of tests/table_routes.py
+#define MIC_TBI_STD             1u           // the standard instance: one work-group per CU, any alphabet, rANS, HBM scratch
+#define MIC_TBI_C4K             2u           // the compact instance: tANS, at most 4096 symbols, tableLog <= 13; two work-groups per CU
 
 // MicUnit.dec_stage: a decode unit's place in the chain behind the tANS kernels (DESIGN.md section 4 has the table).  Device code only;
 // every enqueue starts at NONE (lay_out: MicUnit{}).  The chain's other two hand-off signals: ntok != 0 ("decoded"), and wv_slow.
@@ -189,6 +193,9 @@ struct MicUnit {
     uint32_t split_hi[4];     // ... of the eight-part instance (split[7] = 8): I_4 .. I_7, and its regions hold no dead steps -- tokens
                               // [I_p, I_p+1) are the states sym[(p - 1) R + i - I_p].  Read by mic_hip_debug_split8, predicted by
                               // tests/tans_split8_model.py
+    uint32_t tb_inst;         // which instance of k_enc_tables_wg / k_dec_tables_wg took the unit (MIC_TBI_*; 0: neither -- the unit failed in
+                              // front of the table stage).  Thread 0 writes it; on encode it is also what keeps the standard instance
+                              // off a unit the compact one has built.  Read by mic_hip_debug_tab_inst.  Cleared with the other results
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }

@@ -1441,7 +1441,7 @@ void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant,
     const bool gap = (variant & MIC_VARIANT_GAP) != 0;
     if (gap) mic_launch_enc_gap(d_units, n, stream, t);
     if (t) t->mark("k_enc_tables_wg");
-    mic_launch_enc_tables(d_units, n, stream);
+    mic_launch_enc_tables(d_units, n, stream, (enc_mask & MIC_ENC_TBL_C4K) != 0);
     if (gap) mic_launch_enc_gap_remap(d_units, n, stream, t);
     static MicPerDeviceOnce once;
     once.run([] {

@@ -67,6 +67,8 @@ struct MicTimer {
 #define MIC_ENC_CLS_TL14    0x10u
 #define MIC_ENC_CLS_TL15    0x20u
 #define MIC_ENC_CLS_TL16    0x40u
+// (in the same mask, and no tANS class -- MicUnit.enc_kernel never names it:)
+#define MIC_ENC_TBL_C4K     0x80u       // k_enc_tables_wg<true>, the table kernel's compact instance (mic_tables.hip); the standard one is always launched
 void mic_launch_encode(MicUnit *d_units, int n, hipStream_t stream, int variant, MicTimer *t, uint32_t enc_mask = ~0u);
 // d_cls: per-session scratch of MIC_CLS_INTS(n) ints for the per-class unit lists of the lane-per-state tANS decoder (mic_decode_ls.hip)
 #define MIC_CLS_HEAD 64                 // the lists' counts (MIC_CLS_LISTS of them) stand in front of the lists
@@ -123,7 +125,9 @@ __host__ __device__ inline bool mic_split_gate(const MicUnit &u, const MicSplitC
     return u.flavour == 2 && u.table_log == 13 && !u.zero_bits && mic_sym_ceiling(u, u.count) == u.count && u.count >= cfg.min_tokens &&
            u.count >= 128u && 128ull * (uint64_t)(u.comp_len - u.bits_off) >= (uint64_t)cfg.min_bits16 * (uint64_t)u.count;
 }
-void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream);
+// c4k: launch the compact instance too (encode: MIC_ENC_TBL_C4K of the mask; decode: the batch may hold a class of tableLog <= 13).
+// The standard instance is the catch-all: it takes every unit the compact one did not, so a wrong `false` costs time, never correctness.
+void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream, bool c4k = true);
 // gap removal (mic_gap.hip): encode -- map and compact histogram behind the tokeniser, token remap in front of the tANS encoder, the
 // header's bytes added to blob_len behind it; decode -- map parse in front of k_dec_parse, expansion of tab_sym behind the tables
 void mic_launch_enc_gap(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
@@ -131,4 +135,4 @@ void mic_launch_enc_gap_remap(MicUnit *d_units, int n, hipStream_t stream, MicTi
 void mic_launch_enc_gap_len(MicUnit *d_units, int n, hipStream_t stream);
 void mic_launch_dec_gap_map(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
 void mic_launch_dec_gap_expand(MicUnit *d_units, int n, hipStream_t stream, MicTimer *t);
-void mic_launch_dec_tables(MicUnit *d_units, int n, hipStream_t stream);
+void mic_launch_dec_tables(MicUnit *d_units, int n, hipStream_t stream, bool c4k = true);

@@ -10,9 +10,19 @@
 // numbering are data-parallel (mic_tables_par.h); the NCount header is a variable-width bit
 // packing whose 32-bit accumulator wraps exactly like the reference's (fsecompressu16.go:260-262)
 // and stays on one lane, reading norm[] from LDS.  "Small" units (alphabet <= 8192 symbols,
-// tableLog <= 13: every 8..12-bit image) keep all scratch in 70 KiB of LDS as 16-bit values, two
-// work-groups per CU; anything larger (16-bit CT: 65536 symbols, tableLog 16) uses the unit's
-// HBM scratch slabs through the same code.
+// tableLog <= 13: every 8..12-bit image) keep all scratch in LDS as 16-bit values; anything
+// larger (16-bit CT: 65536 symbols, tableLog 16) uses the unit's HBM scratch slabs through the
+// same code.
+//
+// Each kernel comes in two instances (TbLds below).  The compact one takes the small tANS units of
+// at most 4096 symbols -- the tokens of every frame of up to 12 bits -- with a carve-up of 68.5 KiB
+// and at most 64 VGPRs: two work-groups per CU, which cover each other's barrier and LDS stalls.
+// The standard one (96.4 KiB, one work-group per CU) takes everything else: larger alphabets,
+// tableLog above 13, rANS, the HBM scratch path -- and every unit the compact one did not take.
+// The compact one is launched first, over the whole batch, when the launch masks say the batch may
+// hold such a unit (mic_launch.h: what the host knows and what the session remembers; a wrong
+// guess costs time, never correctness); a group returns at once for a unit that is not its own,
+// and MicUnit.tb_inst says which instance built a unit's tables.
 #include "mic_dev.h"
 #include "mic_fse_tables.h"
 #include "mic_tables_par.h"
@@ -21,17 +31,33 @@
 
 #define TB_SMALL_SYMS 8192
 #define TB_SMALL_TL 13
+#define TB_C4K_SYMS 4096                     // the compact instance's alphabet
 
-// LDS carve-up shared by both kernels (bytes)
-#define TB_OFF_NORM   0                      // int16[8192]
-#define TB_OFF_FIRST  (16 * 1024)            // uint16[8192]
-#define TB_OFF_CUM    (32 * 1024)            // uint16[8192]
-#define TB_OFF_VISIT  (48 * 1024)            // uint16[8192]           (small units only)
-#define TB_OFF_BITMAP (64 * 1024)            // uint32[2048 + 1]
-#define TB_OFF_WPREF  (64 * 1024 + 8256)     // uint32[2048 + 1]
-#define TB_OFF_BIG    (64 * 1024 + 16512)    // uint32[4096 + 2]
-#define TB_OFF_TMP    (64 * 1024 + 32960)    // uint32[128]
-#define TB_LDS_BYTES  (64 * 1024 + 32960 + 512)    // ~96.4 KiB  (1 group / CU; the small path alone would fit 2)
+// LDS carve-up shared by both kernels (bytes), per instance.  The small path of tp_build ranks its big symbols by waves: wave w
+// owns words [256 w, 256 w + 256) from BITMAP on (16 KiB, running on into WPREF) and 256 16-bit prefixes from word 1024 of BIG
+// on (8 KiB behind a list of at most 2^13 / 17 symbols) -- all the compact instance keeps of the three areas.
+template <bool C4K> struct TbLds {
+    static constexpr uint32_t SYMS   = C4K ? TB_C4K_SYMS : TB_SMALL_SYMS;
+    static constexpr uint32_t NORM   = 0;                                 // int16[SYMS]
+    static constexpr uint32_t FIRST  = 2 * SYMS;                          // uint16[SYMS]
+    static constexpr uint32_t CUM    = 4 * SYMS;                          // uint16[SYMS]
+    static constexpr uint32_t VISIT  = 6 * SYMS;                          // uint16[8192]: 2^13 table positions  (small units only)
+    static constexpr uint32_t BITMAP = VISIT + 16 * 1024;                 // uint32[2048 + 1]
+    static constexpr uint32_t WPREF  = BITMAP + 8256;                     // uint32[2048 + 1]
+    static constexpr uint32_t BIG    = BITMAP + 16512;                    // uint32[4096 + 2]; compact: uint32[1024] + uint16[16 * 256]
+    static constexpr uint32_t TMP    = BIG + (C4K ? 12288 : 16448);       // uint32[128]
+    static constexpr uint32_t BYTES  = TMP + 512;                         // standard ~96.4 KiB: 1 group / CU; compact 68.5 KiB: 2
+    static_assert(WPREF - BITMAP >= 4 * (2048 + 1) && BIG - WPREF >= 4 * (2048 + 1) && BIG - BITMAP >= 4 * 256 * TP_WAVES, "bitmap, prefixes; a wave's 256 words");
+    static_assert(TMP - BIG >= (C4K ? 4 * 1024 + 2 * 256 * TP_WAVES : 4 * (4096 + 2)) && (1 << TB_SMALL_TL) / (TP_SMALLV + 1) < 1024, "big list (and the waves' prefixes behind it)");
+    static_assert((((SYMS * TB_SMALL_TL) >> 3) + 3 + 8 + 3) / 4 * 4 <= BITMAP - VISIT, "the NCount bit buffer of a small unit fits the visit area");
+    static_assert(BYTES % 16 == 0, "");
+};
+#define TB_STATIC_LDS 512                    // bound on what a kernel declares beside the carve-up (s_misc, the vote words)
+static_assert(TbLds<false>::BYTES == 64 * 1024 + 32960 + 512 && TbLds<false>::BYTES + TB_STATIC_LDS <= 160 * 1024, "the standard instance: one group per CU");
+static_assert(TbLds<true>::BYTES <= 80 * 1024 && 2 * (TbLds<true>::BYTES + TB_STATIC_LDS) <= 160 * 1024, "the compact instance: two groups per CU");
+__host__ __device__ inline bool tb_is_c4k(uint32_t symbol_len, uint32_t tl, uint32_t flavour) {
+    return symbol_len <= TB_C4K_SYMS && tl <= TB_SMALL_TL && flavour != 108;
+}
 
 // ------------------------------------------------------------------------------------------
 // writeCount (fsecompressu16.go:191-289) on the whole group, for tableLog <= 14 (a field is at most
@@ -147,7 +173,7 @@ __device__ int tb_write_ncount_par(const NormT *norm, uint32_t symbol_len, uint3
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename NormT, typename IdxT>
+template <typename NormT, typename IdxT, bool RANS>   // RANS: the instance takes rANS units (nstates 108)
 __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT *cum_all, uint16_t *visit_pos,
                                 uint32_t *bitmap, uint32_t *wprefix, uint32_t *big_list, uint32_t *s_tmp,
                                 uint32_t *s_misc, uint32_t n, uint32_t symbol_len, uint32_t tl) {
@@ -215,8 +241,9 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
                 if (lane == 0) { s_tmp[wave] = a; s_t64[wave] = b; }
                 __syncthreads();
                 uint32_t ta = 0; uint64_t tb = 0;
+#pragma unroll 4                                                    // (sixteen partials read at once are 48 vector registers)
                 for (int w = 0; w < TP_WAVES; w++) { ta += s_tmp[w]; tb += s_t64[w]; }
-                ra = ta; rb = tb;
+                ra = mic_uniform(ta); rb = mic_uniform(tb);                    // (scalar: the compact instance lives on 64 vector registers)
             };
             uint32_t total = n;
             const uint32_t low_threshold2 = total >> tl;
@@ -259,7 +286,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
             if (rc2 == MICD_OK && !serial) {
                 const uint64_t v_step_log = 62 - (uint64_t)tl;
                 const uint64_t midv = (1ull << (v_step_log - 1)) - 1;
-                const uint64_t r_step = (((1ull << v_step_log) * (uint64_t)to_distribute) + midv) / (uint64_t)total;
+                const uint64_t r_step = mic_uniform((uint64_t)((((1ull << v_step_log) * (uint64_t)to_distribute) + midv) / (uint64_t)total));
                 uint64_t carry = midv;
                 uint32_t badw = 0;
                 for (uint32_t base = 0; base < symbol_len; base += TP_THREADS) {
@@ -271,6 +298,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
                     if (lane == 63) s_t64[wave] = incl;
                     __syncthreads();
                     uint64_t off = 0, tot = 0;
+#pragma unroll 4
                     for (int w = 0; w < TP_WAVES; w++) { const uint64_t x = s_t64[w]; if ((uint32_t)w < wave) off += x; tot += x; }
                     if (ny) {
                         const uint64_t start = carry + off + incl - val, end = start + val;
@@ -278,7 +306,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
                         if (weight < 1) badw = 1;
                         norm[s2] = (NormT)(int32_t)weight;
                     }
-                    carry += tot;
+                    carry += mic_uniform(tot);
                 }
                 if (__syncthreads_or((int)badw)) rc2 = MICD_ERR_INTERNAL;
             }
@@ -330,7 +358,7 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     __syncthreads();
     if ((int)s_misc[3] != MICD_OK) { if (tid == 0) u.status = (int)s_misc[3]; return; }
     MIC_STAMP_AT(u, 6);
-    if (u.nstates == 108) {
+    if (RANS && u.nstates == 108) {
         // buildRansEncTable (ransu16.go:139-180): bias = cumulative frequency, positives in symbol order, then the
         // low-probability symbols; record = freq | k0 << 20 in tt_nb, bias in tt_find.  No state table.
         uint32_t carry_pos = 0, carry_low = 0;
@@ -384,13 +412,21 @@ __device__ void enc_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     MIC_STAMP_AT(u, 7);
 }
 
-__global__ void __launch_bounds__(TP_THREADS) k_enc_tables_wg(MicUnit *units) {
+// C4K: the compact instance (two groups per CU: sixteen waves each, eight per SIMD, 64 VGPRs).  It is launched first, when it is
+// launched at all (mic_launch_enc_tables), and builds nothing for a unit that is not its own; a unit that fails a histogram gate
+// (USE_RLE, INCOMPRESSIBLE: known before the class is) gets its status, max_count and symbol_len from whichever instance scans it
+// first, tb_inst stays 0 and the other instance skips it by its status.  The standard instance takes every unit that does not
+// carry the compact one's mark.
+template <bool C4K>
+__global__ void __launch_bounds__(TP_THREADS, C4K ? 8 : 4) k_enc_tables_wg(MicUnit *units) {
+    typedef TbLds<C4K> L;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ uint32_t s_misc[8];
     MicUnit &u = units[blockIdx.x];
     if (u.status != MICD_OK) return;
+    if (C4K ? u.nstates == 108 : u.tb_inst == MIC_TBI_C4K) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t *s_tmp = (uint32_t *)(s_raw + TB_OFF_TMP);
+    uint32_t *s_tmp = (uint32_t *)(s_raw + L::TMP);
     // ---- histogram scan: symbolLen and maxCount (fsecompressu16.go:438-462) -------------------------
     uint32_t m = 0, sl = 0;
     const uint32_t hist_hi = min(u.tab_cap, (u.hist_hi >= 1 && u.hist_hi <= MIC_MAXSYM) ? u.hist_hi : MIC_MAXSYM + 1u);   // (the tokeniser's bound on what it counted)
@@ -405,7 +441,6 @@ __global__ void __launch_bounds__(TP_THREADS) k_enc_tables_wg(MicUnit *units) {
         uint32_t mm = 0, ss = 0;
         for (int w = 0; w < TP_WAVES; w++) { mm = max(mm, s_tmp[w]); ss = max(ss, s_tmp[16 + w]); }
         const uint32_t n = u.ntok;
-        u.max_count = mm; u.symbol_len = ss;
         int rc = MICD_OK;
         // gate order of FSECompressU16* (fse2state.go:23-42); the flavour's length gate is applied in k_enc_tans_wg
         // (a bare FSE call has no fallback chain: its own flavour's length gate comes before the histogram gates, fse8state.go:32-34)
@@ -414,31 +449,34 @@ __global__ void __launch_bounds__(TP_THREADS) k_enc_tables_wg(MicUnit *units) {
         else if (mm == n) rc = MICD_ERR_USE_RLE;
         else if (mm == 1 || mm < (n >> 15)) rc = MICD_ERR_INCOMPRESSIBLE;
         uint32_t tl = 0;
-        if (rc == MICD_OK) { tl = mic_optimal_table_log(n, ss, u.req_tl); u.table_log = tl; }
-        if (rc == MICD_OK && (1u << tl) > u.tab_cap) rc = MICD_INT_GROW;      // (tier 1: the table slabs hold 8192 states)
-        if (rc != MICD_OK) u.status = rc;
+        if (rc == MICD_OK) tl = mic_optimal_table_log(n, ss, u.req_tl);
+        if (C4K && rc == MICD_OK && !tb_is_c4k(ss, tl, u.nstates)) rc = MICD_ERR_UNSUPPORTED;   // (the standard instance's: nothing is written)
+        else {
+            u.max_count = mm; u.symbol_len = ss;
+            if (rc == MICD_OK) { u.table_log = tl; u.tb_inst = C4K ? MIC_TBI_C4K : MIC_TBI_STD; }
+            if (rc == MICD_OK && (1u << tl) > u.tab_cap) rc = MICD_INT_GROW;  // (tier 1: the table slabs hold 8192 states)
+            if (rc != MICD_OK) u.status = rc;
+        }
         s_misc[0] = (uint32_t)rc; s_misc[1] = tl; s_misc[4] = ss; s_misc[5] = n;
     }
     __syncthreads();
     if ((int)s_misc[0] != MICD_OK) return;
-    const uint32_t tl = s_misc[1], symbol_len = s_misc[4], n = s_misc[5];
-    uint32_t *bitmap = (uint32_t *)(s_raw + TB_OFF_BITMAP), *wprefix = (uint32_t *)(s_raw + TB_OFF_WPREF), *big = (uint32_t *)(s_raw + TB_OFF_BIG);
-    if (symbol_len <= TB_SMALL_SYMS && tl <= TB_SMALL_TL) {
-        enc_tables_body<int16_t, uint16_t>(u, (int16_t *)(s_raw + TB_OFF_NORM), (uint16_t *)(s_raw + TB_OFF_FIRST),
-                                           (uint16_t *)(s_raw + TB_OFF_CUM), (uint16_t *)(s_raw + TB_OFF_VISIT),
-                                           bitmap, wprefix, big, s_tmp, s_misc, n, symbol_len, tl);
-    } else {
+    const uint32_t tl = mic_uniform(s_misc[1]), symbol_len = mic_uniform(s_misc[4]), n = mic_uniform(s_misc[5]);
+    uint32_t *bitmap = (uint32_t *)(s_raw + L::BITMAP), *wprefix = (uint32_t *)(s_raw + L::WPREF), *big = (uint32_t *)(s_raw + L::BIG);
+    if (C4K || (symbol_len <= TB_SMALL_SYMS && tl <= TB_SMALL_TL)) {
+        enc_tables_body<int16_t, uint16_t, !C4K>(u, (int16_t *)(s_raw + L::NORM), (uint16_t *)(s_raw + L::FIRST),
+                                                 (uint16_t *)(s_raw + L::CUM), (uint16_t *)(s_raw + L::VISIT),
+                                                 bitmap, wprefix, big, s_tmp, s_misc, n, symbol_len, tl);
+    } else if (!C4K) {
         // HBM scratch: norm[] itself, cumul[] for the first visits, hist[] (dead after normalisation) for cum_all,
         // tab_sym[] for the visit sequence
-        enc_tables_body<int32_t, uint32_t>(u, u.norm, (uint32_t *)u.cumul, (uint32_t *)u.hist, u.tab_sym,
-                                           bitmap, wprefix, big, s_tmp, s_misc, n, symbol_len, tl);
+        enc_tables_body<int32_t, uint32_t, true>(u, u.norm, (uint32_t *)u.cumul, (uint32_t *)u.hist, u.tab_sym,
+                                                 bitmap, wprefix, big, s_tmp, s_misc, n, symbol_len, tl);
     }
 }
 
 // ------------------------------------------------------------------------------------------
-#define DT_STAGE 8192     // bytes of the blob staged in LDS for the header parse (aliases the visit/bitmap area)
-
-template <typename NormT, typename IdxT>
+template <typename NormT, typename IdxT, bool RANS>
 __device__ void dec_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT *cum_all, uint16_t *visit_pos,
                                 uint32_t *bitmap, uint32_t *wprefix, uint32_t *big_list, uint32_t *s_tmp,
                                 uint32_t symbol_len, uint32_t tl, uint32_t flavour) {
@@ -449,7 +487,7 @@ __device__ void dec_tables_body(MicUnit &u, NormT *norm, IdxT *first_visit, IdxT
     uint32_t route = sizeof(NormT) == 2 ? MIC_TBR_SMALL : MIC_TBR_HBM;
     const int32_t large_limit = (int32_t)(size >> 1);
     for (uint32_t s = tid; s < symbol_len; s += TP_THREADS) if ((int32_t)norm[s] >= large_limit) zb = 1;   // fsedecompressu16.go:214-216
-    if (flavour == 108) {
+    if (RANS && flavour == 108) {
         // buildRansDecTable (ransu16.go:77-135): slots filled in symbol order, positives first, then the -1 symbols
         route |= MIC_TBR_RANS;
         uint32_t carry_pos = 0, carry_low = 0;
@@ -586,38 +624,52 @@ __global__ void __launch_bounds__(64) k_dec_parse(MicUnit *units) {
     }
 }
 
-__global__ void __launch_bounds__(TP_THREADS) k_dec_tables_wg(MicUnit *units) {
+// (the parse has left the unit's class in its descriptor: each instance takes its own units; c4k_launched = 0: the compact
+// instance is not in this chain and the standard one takes every unit)
+template <bool C4K>
+__global__ void __launch_bounds__(TP_THREADS, C4K ? 8 : 4) k_dec_tables_wg(MicUnit *units, int c4k_launched) {
+    typedef TbLds<C4K> L;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     MicUnit &u = units[blockIdx.x];
     const uint32_t tid = threadIdx.x;
     if (u.status != MICD_OK) return;                                      // k_dec_parse already failed this unit
-    int16_t *norm16 = (int16_t *)(s_raw + TB_OFF_NORM);
-    uint32_t *s_tmp = (uint32_t *)(s_raw + TB_OFF_TMP);
     const uint32_t tl = u.table_log, symbol_len = u.symbol_len, flavour = u.flavour;
-    const bool small = symbol_len <= TB_SMALL_SYMS && tl <= TB_SMALL_TL;
+    if (C4K ? !tb_is_c4k(symbol_len, tl, flavour) : (c4k_launched && tb_is_c4k(symbol_len, tl, flavour))) return;
+    if (tid == 0) u.tb_inst = C4K ? MIC_TBI_C4K : MIC_TBI_STD;
+    int16_t *norm16 = (int16_t *)(s_raw + L::NORM);
+    uint32_t *s_tmp = (uint32_t *)(s_raw + L::TMP);
+    const bool small = C4K || (symbol_len <= TB_SMALL_SYMS && tl <= TB_SMALL_TL);
     if (small) for (uint32_t s2 = tid; s2 < symbol_len; s2 += TP_THREADS) norm16[s2] = (int16_t)u.norm[s2];
     __syncthreads();
-    uint32_t *bitmap = (uint32_t *)(s_raw + TB_OFF_BITMAP), *wprefix = (uint32_t *)(s_raw + TB_OFF_WPREF), *big = (uint32_t *)(s_raw + TB_OFF_BIG);
+    uint32_t *bitmap = (uint32_t *)(s_raw + L::BITMAP), *wprefix = (uint32_t *)(s_raw + L::WPREF), *big = (uint32_t *)(s_raw + L::BIG);
     if (small) {
-        dec_tables_body<int16_t, uint16_t>(u, norm16, (uint16_t *)(s_raw + TB_OFF_FIRST), (uint16_t *)(s_raw + TB_OFF_CUM),
-                                           (uint16_t *)(s_raw + TB_OFF_VISIT), bitmap, wprefix, big, s_tmp, symbol_len, tl, flavour);
-    } else {
+        dec_tables_body<int16_t, uint16_t, !C4K>(u, norm16, (uint16_t *)(s_raw + L::FIRST), (uint16_t *)(s_raw + L::CUM),
+                                                 (uint16_t *)(s_raw + L::VISIT), bitmap, wprefix, big, s_tmp, symbol_len, tl, flavour);
+    } else if (!C4K) {
         // HBM scratch: cumul[] first visits, tt_find[] cum_all (not hist[]: the encode side keeps that slab zero between calls),
         // state_tab[] (u32, first half used as u16) visit sequence
-        dec_tables_body<int32_t, uint32_t>(u, u.norm, (uint32_t *)u.cumul, (uint32_t *)u.tt_find, (uint16_t *)u.state_tab,
-                                           bitmap, wprefix, big, s_tmp, symbol_len, tl, flavour);
+        dec_tables_body<int32_t, uint32_t, true>(u, u.norm, (uint32_t *)u.cumul, (uint32_t *)u.tt_find, (uint16_t *)u.state_tab,
+                                                 bitmap, wprefix, big, s_tmp, symbol_len, tl, flavour);
     }
 }
 
-void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream) {
+void mic_launch_enc_tables(MicUnit *d_units, int n, hipStream_t stream, bool c4k) {
     static MicPerDeviceOnce once;
-    once.run([] { (void)hipFuncSetAttribute((const void *)k_enc_tables_wg, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_BYTES); });
-    hipLaunchKernelGGL(k_enc_tables_wg, dim3(n), dim3(TP_THREADS), TB_LDS_BYTES, stream, d_units);
+    once.run([] {
+        (void)hipFuncSetAttribute((const void *)k_enc_tables_wg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TbLds<true>::BYTES);
+        (void)hipFuncSetAttribute((const void *)k_enc_tables_wg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TbLds<false>::BYTES);
+    });
+    if (c4k) hipLaunchKernelGGL(k_enc_tables_wg<true>, dim3(n), dim3(TP_THREADS), TbLds<true>::BYTES, stream, d_units);
+    hipLaunchKernelGGL(k_enc_tables_wg<false>, dim3(n), dim3(TP_THREADS), TbLds<false>::BYTES, stream, d_units);
 }
-void mic_launch_dec_tables(MicUnit *d_units, int n, hipStream_t stream) {
+void mic_launch_dec_tables(MicUnit *d_units, int n, hipStream_t stream, bool c4k) {
     static MicPerDeviceOnce once;
-    once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tables_wg, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_BYTES); });
+    once.run([] {
+        (void)hipFuncSetAttribute((const void *)k_dec_tables_wg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TbLds<true>::BYTES);
+        (void)hipFuncSetAttribute((const void *)k_dec_tables_wg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TbLds<false>::BYTES);
+    });
     hipLaunchKernelGGL(k_dec_parse<false>, dim3(n), dim3(64), 0, stream, d_units);
     hipLaunchKernelGGL(k_dec_parse<true>, dim3(n), dim3(64), 0, stream, d_units);
-    hipLaunchKernelGGL(k_dec_tables_wg, dim3(n), dim3(TP_THREADS), TB_LDS_BYTES, stream, d_units);
+    if (c4k) hipLaunchKernelGGL(k_dec_tables_wg<true>, dim3(n), dim3(TP_THREADS), TbLds<true>::BYTES, stream, d_units, 1);
+    hipLaunchKernelGGL(k_dec_tables_wg<false>, dim3(n), dim3(TP_THREADS), TbLds<false>::BYTES, stream, d_units, c4k ? 1 : 0);
 }

@@ -33,6 +33,10 @@ __device__ __forceinline__ uint32_t mic_wave_incl_max(uint32_t v) {
     return v;
 }
 
+// A value that is the same in every lane, said so to the compiler: it moves to scalar registers.
+__device__ __forceinline__ uint32_t mic_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t mic_uniform(uint64_t v) { return (uint64_t)mic_uniform((uint32_t)v) | ((uint64_t)mic_uniform((uint32_t)(v >> 32)) << 32); }
+
 // The value of the lane d below (lanes 0 .. d-1: their own), 32 or 64 bits.
 __device__ __forceinline__ uint32_t mic_lane_up(uint32_t v, int d) { return (uint32_t)__shfl_up((int)v, d); }
 __device__ __forceinline__ uint64_t mic_lane_up(uint64_t v, int d) { return (uint64_t)__shfl_up((long long)v, d); }
