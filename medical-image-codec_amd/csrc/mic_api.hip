@@ -735,6 +735,21 @@ int mic_hip_debug_split8_config(mic_hip_session *s, uint32_t min_tokens8) try {
     s->dec_classes = mic_hip_session::ClsMemory{};
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): who did the eight-part instance's per-chunk upkeep for unit i after a decode's *_finish --
+// out[0]: 0 the chain wave, 1 a partner wave, out[1]: chunks the partner served, out[2]: chunks the chain wave found its partner not
+// ready for, out[3]: stalled (MicUnit.partner; zeros of a unit the eight-part instance did not run)
+int mic_hip_debug_partner(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    for (int k = 0; k < 4; k++) out[k] = s->h_units[(size_t)i].partner[k];
+    return MIC_OK;
+} MIC_ABI_CATCH
+// debug setter (not in the public header): polls a chain wave of the eight-part instance waits for its partner wave before it gives
+// up (MicSplitCfg::partner_bound; 1: at once); a zero puts the default back
+int mic_hip_debug_partner_config(mic_hip_session *s, uint32_t bound) try {
+    if (!s) return MIC_ERR_ARGS;
+    s->split_cfg.partner_bound = bound ? bound : MicSplitCfg{}.partner_bound;
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): how far the chain behind the tables brought unit i (MicUnit.dec_stage: MIC_STAGE_*,
 // mic_dev.h; 4 = k_dec_rows_tok made its pixels) after a decode's *_finish
 int mic_hip_debug_dec_stage(mic_hip_session *s, int i, uint32_t *out) try {

@@ -599,7 +599,9 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // then costs a four-part chain instead of an unsplit one; the four-part instance, launched behind it, judges the unit afresh.
 // LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop, summed over the chunks, into dbg[] of the
 // wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over, snapshot and ballot;
-// dbg[5] chunks, dbg[6] parts per stream
+// dbg[5] chunks, dbg[6] parts per stream.  The partner instance (eight parts): the chain wave's 0 rounds, 1 publish, 2 the wait for its
+// partner, 4 as above (3 stays 0: the upkeep is not there), and the partner wave's own period in dbg[8 ..]: 8 waiting for the chunk, 9
+// positions, ring fills and loads, 10 stage, served and state stores, dbg[11] its chunks
 #ifdef LS_STAMP
 #define LS_ST_DECL uint64_t stamp[5] = { 0, 0, 0, 0, 0 }, t_prev = __builtin_amdgcn_s_memtime()
 #define LS_ST_OUT(parts_) do { if (lane == 0) { MicUnit &ud = units[unit_i]; for (int i_ = 0; i_ < 5; i_++) ud.dbg[i_] = (uint32_t)(stamp[i_] >> 4); \
@@ -616,11 +618,26 @@ template <int PARTS> struct LsParts {
     static constexpr int RING_BLOCKS = 4, DEPTH = 2, RING_BITS = BLK_SHIFT + 2;
     static constexpr uint32_t MIRROR = 4u * BLK * RING_BLOCKS;              // two mirror dwords + two pad dwords
     static constexpr uint32_t STAGE = MIRROR + 16u;                         // CHUNK u16 states of a chunk
-    static constexpr uint32_t PART_BYTES = STAGE + 2u * CHUNK;              // 656 | 336 | 176
+    // Eight parts: the per-chunk upkeep (ring fills, state stores) is done by a PARTNER wave per chain wave (wave WAVES + w serves
+    // chain wave w), which needs the chunk's stage twice, by chunk parity, and a mailbox per chain wave (protocol: above the kernel)
+    static constexpr bool PARTNER = PARTS == 8;
+    static constexpr int GROUP_WAVES = PARTNER ? 2 * WAVES : WAVES;
+    static constexpr uint32_t STAGE_BYTES = 2u * CHUNK;
+    static constexpr uint32_t PART_BYTES = STAGE + (PARTNER ? 2u : 1u) * STAGE_BYTES;   // 656 | 336 | 208
     static constexpr uint32_t TAB = (uint32_t)PARTS * PART_BYTES;           // the parts in front of the stream's table
-    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696 | 17 728 | 17 792
-    static constexpr uint32_t LDS = WAVES * SPW * STREAM_BYTES;             // 159 264 | 159 552 | 160 128
+    static constexpr uint32_t STREAM_BYTES = TAB + (2u << TL);              // 17 696 | 17 728 | 18 048
+    static constexpr uint32_t MAILBOX = WAVES * SPW * STREAM_BYTES;         // behind the streams: MB_BYTES per chain wave
+    static constexpr uint32_t MB_BYTES = PARTNER ? 256u : 0u;               // two halves (chunk parity) of 32 words: SPW * PARTS positions, then the words below
+    static constexpr uint32_t MB_HALF = 128u;
+    static constexpr uint32_t MB_DONE = 24u * 4u, MB_SERVED = 25u * 4u, MB_BAIL = 26u * 4u, MB_OWN = 27u * 4u;   // (in half 0; MB_OWN: SPW words)
+    static constexpr uint32_t MB_FIN = 0x80000000u;                         // in the DONE word: the chain wave has left its loop
+    static constexpr uint32_t LDS = MAILBOX + WAVES * MB_BYTES;             // 159 264 | 159 552 | 163 200
     static_assert(LDS <= 160 * 1024, "one group must fit a CU's LDS");
+    static_assert(!PARTNER || SPW * PARTS <= 24, "the mailbox's words lie behind the positions");
+    // Polls the partner waits for its chain wave's next chunk before it gives up: the chain wave's own bound (MicSplitCfg::partner_bound,
+    // the longest it can stand still in front of a chunk) is added to it in the kernel.  Its own share covers the chain wave's start
+    // (three tables, 48 KiB through one wave: some 10^4 cycles) and a chunk (some 10^3) 10^4 times over at 200 cycles a poll
+    static constexpr uint32_t PARTNER_POLLS = 1u << 20;
     // Eight parts: a region holds a part's steps from W on only (step j at region offset j - W) -- the first W are the overlap, which
     // nothing reads: the joins are stepped from register snapshots.  Two and four parts keep the layout they were measured with
     static constexpr bool SKIP_W = PARTS == 8;
@@ -640,16 +657,57 @@ template <int PARTS> struct LsParts {
     }
 };
 
+// a mailbox word (LsParts::PARTNER): every lane reads the same address, or one lane writes; volatile, and fenced against the compiler
+// moving the ring and stage accesses across it -- the LDS itself serves a wave's operations in the order it issued them
+__device__ __forceinline__ uint32_t ls_mb_get(uint32_t a) {
+    asm volatile("" ::: "memory");
+    const uint32_t v = *(volatile __attribute__((address_space(3))) uint32_t *)(uintptr_t)a;
+    asm volatile("" ::: "memory");
+    return v;
+}
+__device__ __forceinline__ void ls_mb_put(uint32_t a, uint32_t v) {
+    asm volatile("" ::: "memory");
+    *(volatile __attribute__((address_space(3))) uint32_t *)(uintptr_t)a = v;
+    asm volatile("" ::: "memory");
+}
+
+// The partner protocol (eight parts).  The group has six waves: waves 0-2 are the chain waves with today's roles and lanes, wave 3 + w
+// is the partner of chain wave w and does its per-chunk upkeep: it fills the parts' rings and sends the chunks' states out.  The two
+// talk through chain wave w's mailbox in LDS, and through nothing else:
+//   chain wave, behind chunk c:   the parts' positions into half c & 1 of the mailbox, then DONE = c + 1 (chunks run), then a read of
+//                                 SERVED that nothing waits for: the loop test of the next chunk runs in its shadow;
+//   chain wave, in front of c:    SERVED >= c - 1, by one compare on that read; else it polls (counted: MicUnit.partner[2]);
+//   partner, for c = 0, 1, ...:   waits for DONE > c; reads the positions of half c & 1; where a part's position has reached a new block b,
+//                                 puts block b - 2 into the ring from its register queue (and loads a block further down); reads stage
+//                                 half c & 1; SERVED = c + 1; sends the states out with the same two stores per stream as ever.
+// Deadline (tests/tans_partner_model.py states it and tests/test_tans_partner_cpu.py checks it on the fastest consumers found): chunk c + 2
+// starts in block b or b - 1 when b is the block of the position behind chunk c, and reads no lower than the block under its own, b - 2:
+// the fill for chunk c.  That block takes the slot of b + 2, and chunk c + 1, which may be running, reads b + 1 .. b - 1.  Chunk c + 2 is
+// also the next to write stage half c & 1 and mailbox half c & 1.  So SERVED >= c - 1 in front of chunk c is all a chain wave needs, and
+// the partner has a whole chunk's time for work that touches LDS only: its loads run two blocks ahead of the ring.  The chain wave
+// fills the four blocks b + 1 .. b - 2 of its first position itself, so chunks 0 and 1 wait for nobody.
+// Ends: a chain wave that leaves its loop sets MB_FIN in DONE; the partner serves what is outstanding and leaves.  Every wait is a poll
+// with s_sleep and a bound (the chain wave's: MicSplitCfg::partner_bound, some 400 cycles a poll: the default is 10^8 cycles, 10^4 times
+// a partner's worst chunk -- three loads that miss to HBM, some 10^4 cycles; the partner's: LsParts::PARTNER_POLLS on top of that); a
+// bound that runs out sets BAIL, the other side leaves at its next poll, and the wave's units are handed to the four-part list as
+// MIC_SPLIT_STALLED.  The partner of a chain wave without units returns with it, before either touches the mailbox again.
 template <int PARTS>
-__global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_parts(MicUnit *units, const int *list, const int *count_p, int *retry_list,
-                                                                                int *retry_count, uint32_t overlap) {
+__global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_ls_parts(MicUnit *units, const int *list, const int *count_p, int *retry_list,
+                                                                                      int *retry_count, uint32_t overlap, uint32_t wait_bound) {
     using G = LsParts<PARTS>;
     constexpr int LS_SPW = G::SPW, LS_RBITS = G::RING_BITS, LS_DEPTH = G::DEPTH;
     constexpr bool ZB = false;
     constexpr uint32_t tl = G::TL, size = 1u << tl, SB = G::STREAM_BYTES, PB = G::PART_BYTES, CH = G::CHUNK, BLK = G::BLK, LP = 2u * PARTS;
     extern __shared__ uint32_t s_mem[];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63, wv_g = threadIdx.x >> 6;
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_mem != 0u) return;   // layout assumes dynamic LDS at 0
+    const bool partner = G::PARTNER && wv_g >= (uint32_t)G::WAVES;         // (wave-uniform)
+    const uint32_t wv = partner ? wv_g - (uint32_t)G::WAVES : wv_g;        // the chain wave: its own number, or the one this partner serves
+    const uint32_t mb = G::MAILBOX + wv * G::MB_BYTES;
+    if constexpr (G::PARTNER) {                                             // the one barrier: zeroed mailboxes, in front of every return
+        if (!partner) *(ls_l32)(uintptr_t)(mb + lane * 4u) = 0u;
+        __syncthreads();
+    }
     const int n_cls = *count_p;
     const int slot0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * G::WAVES + (int)wv) * LS_SPW);
     if (slot0 >= n_cls) return;                                             // waves share nothing and never meet at a barrier
@@ -669,7 +727,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
     // ---- tables, as in k_dec_tans_ls: one per stream, all parts read it ----
 #pragma unroll 1
     for (int j = 0; j < LS_SPW; j++) {
-        if (slot0 + j >= n_cls) break;
+        if (slot0 + j >= n_cls || partner) break;
         const uint32_t *dt = (const uint32_t *)(uintptr_t)ls_rl64((uint64_t)(uintptr_t)u.tt_nb, (int)LP * j);
         const uint32_t tb = (wv * LS_SPW + (uint32_t)j) * SB + G::TAB;
         for (uint32_t p = lane * 4; p < size; p += 256) {
@@ -729,6 +787,15 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
 #pragma unroll
     for (int j = 0; j < LS_SPW; j++) {
         const int32_t b = blk_of(j, q - (int32_t)(2 * tl));                 // block of the position BEHIND the initial states
+        if constexpr (G::PARTNER) {
+            // the chain wave fills all four slots, b + 1 .. b - 2; the partner's queue starts with the block under them
+            pfb[j] = b - LS_DEPTH - 1;
+            if (!partner) {
+#pragma unroll
+                for (int dd = -1; dd <= LS_DEPTH; dd++) store_blk(j, b - dd, load_blk(j, b - dd));
+            }
+            continue;
+        }
 #pragma unroll
         for (int dd = -1; dd < LS_DEPTH; dd++) store_blk(j, b - dd, load_blk(j, b - dd));
         pfb[j] = b - LS_DEPTH;
@@ -737,7 +804,7 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
     __builtin_amdgcn_s_waitcnt(0xC07F);                                     // wave-private LDS: the writes above are in before the reads below
     // ---- chain state ----
     const uint32_t ringb = vbase;
-    const uint32_t stgb = vbase + G::STAGE + 2u * k;                        // stage16[r * 2 + k] = state k of round r
+    uint32_t stgb = vbase + G::STAGE + 2u * k;                              // stage16[r * 2 + k] = state k of round r (eight parts: of stage half chunk & 1)
     const uint32_t cb = tbase - 2u * size;
     const uint32_t C = 31u - tl;
     auto window = [&](int32_t qq) -> uint32_t {
@@ -765,12 +832,99 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
 #pragma unroll
     for (int j = 0; j < LS_SPW; j++) scr0[j] = up ? (PARTS > 2 ? (up - 1u) * s_R[j] * 2u : 0u) + lb * 4u : LS_OOB;
     const uint32_t tok0 = up ? LS_OOB : lb * 4u;
+    // one chunk's states of this lane's part of every stream, out of the stage at byte offset `half`, to tok and the scratch regions
+    auto send_states = [&](uint32_t c, uint32_t half) {
+        uint32_t s2[LS_SPW];
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + half + lb * 4);
+        if constexpr (G::PARTNER) { if (lane == 0) ls_mb_put(mb + G::MB_SERVED, c + 1u); }   // behind the ring stores and the stage reads: the LDS keeps a wave's order
+        const uint32_t off = c * 2u * CH;                                   // (part 0 runs on into a descriptor that ends at its last whole chunk)
+        // eight parts: a region starts at step W, and the chunks in front of it are not stored (both terms below are wave-uniform)
+        const uint32_t ch0 = G::SKIP_W ? Wc : 0u, soff = (c - ch0) * 2u * CH;
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) {
+            const bool fits = c >= ch0 && (c + 1u - ch0) * CH <= s_R[j];    // (a part that runs on past its region must not write into its neighbour's)
+            __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, G::AUX);   // (out of range + off < 2^32: still out of range)
+            __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + soff : LS_OOB), 0, G::AUX);
+        }
+    };
+    if constexpr (G::PARTNER) if (partner) {
+        // ---- the partner wave: lanes BLK p .. BLK p + BLK - 1 serve part p of each of the chain wave's streams ----
+        // Two blocks per part wait in registers: pfa = block pfb, what the ring takes next, and pfn = the one under it, loaded a chunk
+        // ago at the least.  The loop's loads are asm: the value is not there when the statement is done, and the one wait that covers
+        // them, at the top of a chunk's service, names what may still be out behind them (vmcnt counts in order)
+        uint32_t pfa[LS_SPW], pfn[LS_SPW], touch = 0;
+#pragma unroll
+        for (int j = 0; j < LS_SPW; j++) { pfa[j] = load_blk(j, pfb[j]); pfn[j] = load_blk(j, pfb[j] - 1); }
+        const uint32_t polls = G::PARTNER_POLLS + min(wait_bound, 1u << 30);
+        uint32_t c = 0, fin = 0;
+        bool bail = false;
+#ifdef LS_STAMP
+        uint64_t pst[3] = { 0, 0, 0 }, pt = __builtin_amdgcn_s_memtime();
+#define LS_PT(i) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); pst[i] += t_ - pt; pt = t_; } while (0)
+#else
+#define LS_PT(i) do { } while (0)
+#endif
+        for (;; c++) {
+            for (uint32_t tries = 0;; tries++) {                            // chunk c: run and published?
+                const uint32_t dn = (uint32_t)__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_DONE));
+                fin = dn & G::MB_FIN;
+                if ((dn & ~G::MB_FIN) > c) { fin = 0; break; }
+                if (fin) break;                                             // the chain wave has left its loop, and nothing is outstanding
+                if (__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_BAIL)) != 0 || tries >= polls) { bail = true; break; }
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (fin || bail) break;
+            LS_PT(0);
+            const uint32_t half = c & 1u;
+            int32_t qp[LS_SPW];
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) qp[j] = (int32_t)ls_mb_get(mb + half * G::MB_HALF + ((uint32_t)j * (uint32_t)PARTS + up) * 4u);
+            asm volatile("s_waitcnt vmcnt(9)" ::: "memory");                // the loads of the chunk before: not its three touches, not its six stores
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) {
+                const bool adv = ((qp[j] >> 5) >> G::BLK_SHIFT) - LS_DEPTH <= pfb[j];   // the part has reached a new block: one at most per chunk
+                if (adv) store_blk(j, pfb[j], pfa[j]);
+                pfa[j] = adv ? pfn[j] : pfa[j];
+                pfb[j] -= adv ? 1 : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) {                              // (the same block again for a part that stayed)
+                const int32_t off = ((pfb[j] - 1) * (int32_t)BLK + (int32_t)lb) * 4;
+                asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(pfn[j]) : [o] "v"(off), [r] "s"(rs_in[j]) : "memory");
+            }
+            // ... and a touch of the cache line under it (four blocks), behind the loads so that the wait above leaves it out: a block's
+            // own load, a few chunks on, then finds the line in the L2 -- from HBM it took longer than a chunk, and the partner set the pace
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) {
+                const int32_t off = ((pfb[j] - 1 - 128 / 4 / (int32_t)BLK) * (int32_t)BLK + (int32_t)lb) * 4;
+                asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(touch) : [o] "v"(off), [r] "s"(rs_in[j]) : "memory");
+            }
+            LS_PT(1);
+            send_states(c, half * G::STAGE_BYTES);
+            LS_PT(2);
+        }
+        if (bail) { if (lane == 0) ls_mb_put(mb + G::MB_BAIL, 1u); }
+        // chunks served, per unit: what the chain wave says the unit's own parts ran (MB_OWN, in front of MB_FIN), or what was served of it
+        if (lane < (uint32_t)LS_SPW && slot0 + (int)lane < n_cls) {
+            const uint32_t own = fin ? ls_mb_get(mb + G::MB_OWN + lane * 4u) : ~0u;
+            units[list[slot0 + (int)lane]].partner[1] = min(c, own);
+        }
+#ifdef LS_STAMP
+        if (lane == 0) { MicUnit &ud = units[list[slot0]]; for (int i = 0; i < 3; i++) ud.dbg[8 + i] = (uint32_t)(pst[i] >> 4); ud.dbg[11] = c; }
+#endif
+        return;
+    }
     bool handed = false;
     uint32_t m_ab = 0;                                                      // the next part's two states after Wc chunks, second << 16 (a state is below 2^14)
     int32_t qlim = last_part ? qz : INT32_MIN;                              // a part is on above it: nothing up to the hand-over, then the next part's
                                                                             // position after Wc chunks; the last part: bits left
     int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: the last chunk start above qlim
     uint32_t ch = 0;
+    // the partner instance: the lane's word of the mailbox half and its stage half of the chunk to come, and their sums over the halves
+    [[maybe_unused]] uint32_t mb_pos = mb + (g * (uint32_t)PARTS + part) * 4u, mb_sv = 0, not_ready = 0;
+    [[maybe_unused]] const uint32_t mb_pos_sum = 2u * mb_pos + G::MB_HALF, stg_sum = 2u * stgb + G::STAGE_BYTES;
+    [[maybe_unused]] bool stalled = false;
     LS_ST_DECL;
     for (;; ch++) {
         if (ch == Wc) {                                                     // (uniform, once)
@@ -785,34 +939,78 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
         asm volatile("" : "+v"(sn_q), "+v"(sn_st), "+v"(sn_ch));            // (taken here: sunk behind the chunk, the selects keep the old q and st alive across it)
         if (ch >= ch_cap || !__any(on & real & have)) break;                // one wave-uniform test per chunk
         LS_T(4);
-        if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else if constexpr (PARTS == 4) LS_CHUNK2_N("8", "64"); else LS_CHUNK2_N("4", "32");
-        LS_T(0);
-        // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
-#pragma unroll
-        for (int j = 0; j < LS_SPW; j++) store_blk(j, pfb[j], pf[j]);
-        LS_T(1);
-#pragma unroll
-        for (int j = 0; j < LS_SPW; j++) pfb[j] = blk_of(j, q) - LS_DEPTH;
-#pragma unroll
-        for (int j = 0; j < LS_SPW; j++) pf[j] = load_blk(j, pfb[j]);
-        LS_T(2);
-        {
-            uint32_t s2[LS_SPW];
-#pragma unroll
-            for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + lb * 4);
-            const uint32_t off = ch * 2u * CH;                              // (part 0 runs on into a descriptor that ends at its last whole chunk)
-            // eight parts: a region starts at step W, and the chunks in front of it are not stored (both terms below are wave-uniform)
-            const uint32_t ch0 = G::SKIP_W ? Wc : 0u, soff = (ch - ch0) * 2u * CH;
-#pragma unroll
-            for (int j = 0; j < LS_SPW; j++) {
-                const bool fits = ch >= ch0 && (ch + 1u - ch0) * CH <= s_R[j];   // (a part that runs on past its region must not write into its neighbour's)
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, G::AUX);   // (out of range + off < 2^32: still out of range)
-                __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + soff : LS_OOB), 0, G::AUX);
+        if constexpr (G::PARTNER) {
+            // SERVED as it was behind the last chunk (the read was issued there; everything from there to here ran in its shadow)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mb_sv) :: "memory");
+            uint32_t sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)mb_sv);
+            if (__builtin_expect(sv + 1u < ch, 0)) {                        // the partner is not ready: poll (the slow path)
+                not_ready++;
+                for (uint32_t tries = 0;; tries++) {
+                    sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_SERVED));
+                    if (sv + 1u >= ch) break;
+                    if (__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_BAIL)) != 0 || tries + 1u >= wait_bound) { stalled = true; break; }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                if (stalled) break;
             }
+            LS_T(2);
+            LS_CHUNK2_N("4", "32");
+            LS_T(0);
+            // publish: the positions (lanes of role 0 of the 24 parts), then DONE, then the read of SERVED for the next chunk's test
+            {
+                const uint64_t em_pos = 0x0000555555555555ull, em_one = 1ull;
+                const uint32_t dn = ch + 1u;
+                asm volatile("s_mov_b64 exec, %[ep]\n\t"
+                             "ds_write_b32 %[pa], %[q]\n\t"
+                             "s_mov_b64 exec, %[e1]\n\t"
+                             "ds_write_b32 %[da], %[dn]\n\t"
+                             "ds_read_b32 %[sv], %[da] offset:%[SO]\n\t"
+                             "s_mov_b64 exec, -1"
+                             : [sv] "=&v"(mb_sv)
+                             : [pa] "v"(mb_pos), [q] "v"(q), [da] "v"(mb + G::MB_DONE), [dn] "v"(dn), [ep] "s"(em_pos), [e1] "s"(em_one),
+                               [SO] "n"(G::MB_SERVED - G::MB_DONE)
+                             : "memory");
+                mb_pos = mb_pos_sum - mb_pos;                               // the other half
+                stgb = stg_sum - stgb;
+            }
+            LS_T(1);
+        } else {
+            if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else LS_CHUNK2_N("8", "64");
+            LS_T(0);
+            // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) store_blk(j, pfb[j], pf[j]);
+            LS_T(1);
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) pfb[j] = blk_of(j, q) - LS_DEPTH;
+#pragma unroll
+            for (int j = 0; j < LS_SPW; j++) pf[j] = load_blk(j, pfb[j]);
+            LS_T(2);
+            {
+                uint32_t s2[LS_SPW];
+#pragma unroll
+                for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + lb * 4);
+                const uint32_t off = ch * 2u * CH;                          // (part 0 runs on into a descriptor that ends at its last whole chunk)
+#pragma unroll
+                for (int j = 0; j < LS_SPW; j++) {
+                    const bool fits = (ch + 1u) * CH <= s_R[j];             // (a part that runs on past its region must not write into its neighbour's)
+                    __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_tok[j], (int)(tok0 + off), 0, G::AUX);   // (out of range + off < 2^32: still out of range)
+                    __builtin_amdgcn_raw_buffer_store_b32(s2[j], rs_scr[j], (int)(fits ? scr0[j] + off : LS_OOB), 0, G::AUX);
+                }
+            }
+            LS_T(3);
         }
-        LS_T(3);
     }
     const uint32_t ch_end = ch;                                             // chunks every part ran and stored
+    if constexpr (G::PARTNER) {
+        // the unit's own chunks (its parts' last chunk that was on, + 1: a longer neighbour keeps the wave going), for the partner's
+        // record, then MB_FIN beside the chunks run; a stalled wave sets BAIL instead.  Nothing below needs the partner, the rings or the stage
+        uint32_t own = real && have ? sn_ch + 1u : 0u;
+#pragma unroll
+        for (uint32_t d = 1; d < LP; d <<= 1) own = max(own, (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane ^ d) << 2), (int)own));
+        if (real && (lane & (LP - 1u)) == 0u) ls_mb_put(mb + G::MB_OWN + g * 4u, own);
+        if (lane == 0) ls_mb_put(stalled ? mb + G::MB_BAIL : mb + G::MB_DONE, stalled ? 1u : ch_end | G::MB_FIN);
+    }
     LS_ST_OUT((uint32_t)PARTS);
     // ---- the joins: boundary p | p + 1 by lane 0 of part p, those of a stream side by side ----
     const uint32_t sn_s1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane | 1u) << 2), (int)sn_st);
@@ -894,7 +1092,11 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::WAVES) k_dec_tans_ls_part
         }
         if (outcome == MIC_SPLIT_DONE) fail = 0u;
     }
+    if constexpr (G::PARTNER) {
+        if (stalled) { outcome = MIC_SPLIT_STALLED; fail = 0u; for (int b = 0; b < NI; b++) I[b] = 0u; }
+    }
     MicUnit &uo = units[unit_i];
+    if constexpr (G::PARTNER) { uo.partner[0] = 1u; uo.partner[2] = not_ready; uo.partner[3] = stalled ? 1u : 0u; }
     uo.split[0] = outcome; uo.split[1] = I[0]; uo.split[2] = W; uo.split[3] = I[1]; uo.split[4] = I[2];
     uo.split[5] = R; uo.split[6] = fail; uo.split[7] = (uint32_t)PARTS;
     if constexpr (PARTS == 8) { uo.split_hi[0] = I[3]; uo.split_hi[1] = I[4]; uo.split_hi[2] = I[5]; uo.split_hi[3] = I[6]; }
@@ -1133,14 +1335,15 @@ static void launch_ls_list(MicUnit *d_units, int n, const int *list, const int *
 // a split instance on list `from`; what it hands back goes to the end of list `to` (the groups cover n units: an instance launched
 // behind it on `to` sees them)
 template <int PARTS>
-static void launch_ls_parts(MicUnit *d_units, int n, int *d_list, int *d_count, int from, int to, hipStream_t stream, uint32_t overlap) {
+static void launch_ls_parts(MicUnit *d_units, int n, int *d_list, int *d_count, int from, int to, hipStream_t stream, uint32_t overlap,
+                            uint32_t wait_bound = 0) {
     using G = LsParts<PARTS>;
     constexpr int per = G::WAVES * G::SPW;
     static MicPerDeviceOnce once;
     once.run([] { (void)hipFuncSetAttribute((const void *)k_dec_tans_ls_parts<PARTS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS); });
     const unsigned groups = (unsigned)((n + per - 1) / per);
-    hipLaunchKernelGGL((k_dec_tans_ls_parts<PARTS>), dim3(groups), dim3(64 * G::WAVES), G::LDS, stream, d_units, d_list + (size_t)from * (size_t)n,
-                       d_count + from, d_list + (size_t)to * (size_t)n, d_count + to, overlap);
+    hipLaunchKernelGGL((k_dec_tans_ls_parts<PARTS>), dim3(groups), dim3(64 * G::GROUP_WAVES), G::LDS, stream, d_units, d_list + (size_t)from * (size_t)n,
+                       d_count + from, d_list + (size_t)to * (size_t)n, d_count + to, overlap, wait_bound ? wait_bound : 1u);
 }
 template <int TL>
 static void launch_ls_tl(MicUnit *d_units, int n, const int *d_list, const int *d_count, hipStream_t stream, bool skip_first, uint32_t m) {
@@ -1163,7 +1366,7 @@ void mic_launch_dec_tans_ls(MicUnit *d_units, int n, int *d_list, int *d_count, 
         // they hand back: an empty list in the normal case, and the unsplit instance's blocks leave at once.  (Without the retry
         // launch k_dec_tans_gl would take those units: slower, not wrong.)  The eight-part instance hands back to the four-part one.
         if (t) t->mark("k_dec_tans_ls_split8<13>");
-        launch_ls_parts<8>(d_units, n, d_list, d_count, LS_SPLIT8_LIST, LS_SPLIT4_LIST, stream, sc.overlap & ~63u);
+        launch_ls_parts<8>(d_units, n, d_list, d_count, LS_SPLIT8_LIST, LS_SPLIT4_LIST, stream, sc.overlap & ~63u, sc.partner_bound);
         if (t) t->mark("k_dec_tans_ls_split4<13>");
         launch_ls_parts<4>(d_units, n, d_list, d_count, LS_SPLIT4_LIST, LS_RETRY_LIST, stream, sc.overlap & ~63u);
         if (t) t->mark("k_dec_tans_ls_split<13>");

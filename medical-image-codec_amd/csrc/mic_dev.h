@@ -38,6 +38,8 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 #define MIC_SPLIT_NOT_MET       2u     // fell back to the unsplit instance: two neighbouring parts did not meet inside the overlap
 #define MIC_SPLIT_BAD_COUNT     3u     // fell back: the last part does not end with the stream's last symbol (cut or damaged stream)
 #define MIC_SPLIT_NO_ROOM       4u     // fell back: a part does not fit its scratch region, or the first two meet behind the last whole chunk
+#define MIC_SPLIT_STALLED       5u     // handed back by the eight-part instance: a chain wave and its partner wave gave each other up (a wait ran
+                                       // into its bound: MicSplitCfg::partner_bound); nothing is wrong with the stream
 // Which two-state tableLog-13 units are split, and how far the parts overlap.  Defaults below; a session's
 // values come from mic_hip_debug_split_config.
 struct MicSplitCfg {
@@ -49,6 +51,8 @@ struct MicSplitCfg {
     uint32_t min_tokens8 = 393216u;    // ... and those of at least max(min_tokens8, min_tokens4) tokens to the eight-part instance, whose regions
                                        // hold a part's steps from W on only: break-even against four parts is about 5.3 W, twelve W is the
                                        // default; mic_hip_debug_split8_config sets it
+    uint32_t partner_bound = 1u << 18; // eight parts: polls (about 400 cycles each) a chain wave waits for its partner wave before it gives the
+                                       // wave's units up as MIC_SPLIT_STALLED (k_dec_tans_ls_parts<8>); mic_hip_debug_partner_config sets it
 };
 // MicUnit.enc_kernel: 1 + the bit index of the MIC_ENC_CLS_* class (mic_launch.h) whose k_enc_tans_wg instance gave the unit its tANS
 // verdict (1 .. 7), or MIC_ENC_BY_SERIAL; MIC_ENC_HANDED is set beside it when the two-state instance had handed the unit over first
@@ -196,6 +200,10 @@ struct MicUnit {
     uint32_t tb_inst;         // which instance of k_enc_tables_wg / k_dec_tables_wg took the unit (MIC_TBI_*; 0: neither -- the unit failed in
                               // front of the table stage).  Thread 0 writes it; on encode it is also what keeps the standard instance
                               // off a unit the compact one has built.  Read by mic_hip_debug_tab_inst.  Cleared with the other results
+    uint32_t partner[4];      // decode, a unit the eight-part instance ran: 0 who did the per-chunk upkeep (0 the chain wave itself, 1 a partner
+                              // wave), 1 chunks of the unit the partner served, 2 chunks the chain wave found its partner not ready for (the
+                              // wave's count), 3 stalled (MIC_SPLIT_STALLED; kept when the four-part instance then takes the unit).  Read by
+                              // mic_hip_debug_partner, predicted by tests/tans_partner_model.py.  Cleared with the other results
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }

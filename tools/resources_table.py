@@ -7,7 +7,8 @@ FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("Scratc
           ("LDS Size [bytes/block]", "lds_bytes"), ("Occupancy [waves/SIMD]", "occupancy_waves_per_simd"))
 rows, cur = {}, {}                                                      # (cur per source: a side-by-side build interleaves the files' remarks)
 for line in open(sys.argv[1], errors="replace"):
-    m = re.match(r"(\S+?):\d+:\d+: remark:\s+(.*?) \[-Rpass-analysis=kernel-resource-usage\]", line)
+    m = (re.match(r"(\S+?):\d+:\d+: remark:\s+(.*?) \[-Rpass-analysis=kernel-resource-usage\]", line) or
+         re.match(r"remark: (\S+?):\d+:\d+:\s+(.*?) \[-Rpass-analysis=kernel-resource-usage\]", line))   # (newer compilers put the word first)
     if not m:
         continue
     src, text = m.groups()
