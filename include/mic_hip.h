@@ -40,6 +40,7 @@ extern "C" {
 #define MIC_ERR_UNSUPPORTED     -9
 #define MIC_ERR_INCOMPRESSIBLE -10   /* Go ErrIncompressible, fseu16.go:33; C: -4 / -10 */
 #define MIC_ERR_IO             -11   /* a read or write callback of the MIC3 streaming calls returned non-zero */
+#define MIC_ERR_MISMATCH       -12   /* decoded pixels differ from the reference pixels / from the expected CRC-32 (the verify calls) */
 
 /* FSE flavour requested from an encoder: the entry of the reference's fallback chain
  * (multiframecompress.go:15-93).  2 -> CompressSingleFrame (2-state, then 1-state),
@@ -215,6 +216,33 @@ typedef struct mic_hip_pics_dec_job {
 } mic_hip_pics_dec_job;
 int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs);
 int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs);
+
+/* ---- verified encode and CRC-32 digests ---------------------------------------------------------------- */
+/* The formats carry no checksum ("No checksums -- caller must verify integrity", fsedecompressu16.go:21-23).  The calls below
+ * prove on the device that a stream decodes to the pixels it was made from, and give every unit / image a digest that travels
+ * BESIDE the file (an index, a DICOM attribute): the IEEE CRC-32 -- zlib's crc32, Go's hash/crc32.ChecksumIEEE: reflected
+ * polynomial 0xEDB88320, init and final xor 0xFFFFFFFF -- of the pixels as little-endian u16 bytes in row-major order. */
+typedef struct mic_hip_verify_result {
+    int32_t  status;          /* MIC_OK: checked and equal; MIC_ERR_MISMATCH; anything else is the codec's own status: not checked */
+    uint32_t crc32;           /* CRC-32 of the REFERENCE pixels (the encoder's input); valid whenever the unit's arguments were */
+    uint64_t mismatches;      /* differing samples (0 unless status is MIC_ERR_MISMATCH) */
+    int64_t  first_mismatch;  /* smallest differing pixel index within the unit / image, -1: none */
+} mic_hip_verify_result;
+/* crc(A || B) from crc(A), crc(B) and B's length in bytes (zlib's crc32_combine).  Needs no device. */
+uint32_t mic_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* mic_hip_compress_batch / mic_hip_pics_compress_batch with the check: every sub-batch is decoded again on the device from the
+ * bytes that were just packed and compared with the pixels it came from, in front of the download.  Files, out_len, failed_strip,
+ * sub-batches and devices are those of the unverified calls, byte for byte.  res[j] describes job j as a whole (a PICS image: its
+ * strips' CRCs joined in order, mismatches summed, first_mismatch the image's pixel index).  A job that fails the check gets
+ * status MIC_ERR_MISMATCH in the job and in res[j] -- failed_strip names its first strip that differed --; its bytes are still
+ * delivered and out_len is set, so the caller can keep the evidence.  A job the codec refused keeps that status in both. */
+int mic_hip_compress_batch_verified(mic_hip_enc_job *jobs, int njobs, mic_hip_verify_result *res);
+int mic_hip_pics_compress_batch_verified(mic_hip_pics_enc_job *jobs, int njobs, mic_hip_verify_result *res);
+/* mic_hip_decompress_batch / mic_hip_pics_decompress_batch with the digest of what was decoded: crc[j] = the CRC-32 of job j's
+ * pixels, taken on the device in front of the download (0 for a job that did not decode).  expect (may be NULL): a decoded job
+ * whose CRC is not expect[j] gets status MIC_ERR_MISMATCH; its pixels are delivered all the same. */
+int mic_hip_decompress_batch_crc(mic_hip_dec_job *jobs, int njobs, const uint32_t *expect, uint32_t *crc);
+int mic_hip_pics_decompress_batch_crc(mic_hip_pics_dec_job *jobs, int njobs, const uint32_t *expect, uint32_t *crc);
 
 /* Replaces CompressSingleFrameGrad / DecompressSingleFrameGrad (multiframecompress.go:111-142): the unit codec with the
  * gradient-adaptive predictor (deltagradrlecompressu16.go) and the two-state -> one-state FSE chain. */
@@ -909,6 +937,22 @@ int mic_hip_session_decode_enqueue(mic_hip_session *s, const uint8_t *d_blobs,
                                    const uint64_t *h_offsets, const mic_hip_unit *units, int n,
                                    uint16_t *d_pixels_out);
 int mic_hip_session_decode_finish(mic_hip_session *s, int32_t *h_status);
+/* Digests and checks on device-resident units (mic_hip_verify_result and the CRC: above, "verified encode").  All three are
+ * synchronous with respect to the host; PICA pair batches are not served.
+ * digest: h_crc[i] = the CRC-32 of unit i's pixels at d_pixels + units[i].px_offset (max_value and nstates are not looked at).
+ * verify: the streams at d_blobs + h_offsets[i] .. h_offsets[i + 1] are decoded -- units as for mic_hip_session_decode -- into a
+ * scratch buffer of the session (sized to the batch's extent, counted by mic_hip_session_workspace_bytes) and compared with
+ * d_pixels_ref, unit i at units[i].px_offset: h_res[i].status is MIC_OK, MIC_ERR_MISMATCH, or the decoder's status (then nothing
+ * was compared: mismatches 0, first_mismatch -1); crc32 is the reference pixels' in every case.
+ * encode_verified: mic_hip_session_encode -- *d_blobs, h_offsets and h_nstates are that call's, byte for byte --, then verify of
+ * the packed streams against d_pixels.  A unit the encoder refused (MIC_ERR_USE_RLE, MIC_ERR_INCOMPRESSIBLE, ...) keeps that
+ * status in h_res[i], is not decoded, and still gets its CRC. */
+int mic_hip_session_digest(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, uint32_t *h_crc);
+int mic_hip_session_verify(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets, const mic_hip_unit *units, int n,
+                           const uint16_t *d_pixels_ref, mic_hip_verify_result *h_res);
+int mic_hip_session_encode_verified(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n,
+                                    const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *h_nstates,
+                                    mic_hip_verify_result *h_res);
 /* WaveletV2 on device-resident frames (BASELINE config 3 as bench.py times it): nframes frames of rows x cols u16, contiguous at
  * d_frames -> their streams WITHOUT the 11-byte file header (rows u32, cols u32, maxValue u16, levels u8,
  * waveletfsecompressu16.go:346-350 -- the caller holds those), packed back to back in the session: *d_streams,

@@ -34,6 +34,7 @@ MIC_HIP_PRED_GRAD = 0x200          # OR'ed into a session unit's nstates: gradie
 MIC_ERR_INCOMPRESSIBLE = -10
 MIC_ERR_IO = -11                   # a read / write callback of the MIC3 streaming calls failed
 MIC_HIP_GAP_REMOVAL = 0x800        # OR'ed into a session unit's nstates: a gap-removal stream (include/mic_hip.h)
+MIC_ERR_MISMATCH = -12             # the verify calls: decoded pixels differ from the reference pixels / the expected CRC-32
 
 _ERR_NAMES = {
     MIC_ERR_ARGS: "bad arguments", MIC_ERR_NOMEM: "out of memory",
@@ -42,6 +43,7 @@ _ERR_NAMES = {
     MIC_ERR_DEVICE: "no usable gfx950 device / HIP error", MIC_ERR_INTERNAL: "internal error",
     MIC_ERR_UNSUPPORTED: "unsupported", MIC_ERR_INCOMPRESSIBLE: "input is not compressible",  # fseu16.go:33
     MIC_ERR_IO: "read / write callback failed",
+    MIC_ERR_MISMATCH: "decoded pixels differ from the reference",
 }
 
 
@@ -216,6 +218,15 @@ class Unit(C.Structure):
                 ("max_value", C.c_uint16), ("nstates", C.c_uint16)]
 
 
+class VerifyResult(C.Structure):
+    """mic_hip_verify_result: status MIC_OK (checked and equal), MIC_ERR_MISMATCH, or the codec's own status (not checked);
+    crc32 of the reference pixels (zlib.crc32 of their little-endian bytes); differing samples; the first one's pixel index (-1)."""
+    _fields_ = [("status", C.c_int32), ("crc32", C.c_uint32), ("mismatches", C.c_uint64), ("first_mismatch", C.c_int64)]
+
+    def __repr__(self):
+        return f"VerifyResult(status={self.status}, crc32=0x{self.crc32:08x}, mismatches={self.mismatches}, first_mismatch={self.first_mismatch})"
+
+
 # every symbol include/mic_hip.h declares (tests/test_abi.py checks the .so exports them all)
 ABI_SYMBOLS = [
     "mic_hip_set_device", "mic_hip_set_devices", "mic_hip_get_devices", "mic_hip_shard_plan", "mic_hip_wsi_band_plan", "mic_hip_device_name", "mic_hip_version",
@@ -285,6 +296,9 @@ ABI_SYMBOLS = [
     "mic_hip_tile_cache_slot_bytes", "mic_hip_tile_cache_create", "mic_hip_tile_cache_clear", "mic_hip_tile_cache_get_stats",
     "mic_hip_tile_cache_destroy", "mic_hip_tile_cache_plan",
     "mic_hip_wsi_reader_set_cache", "mic_hip_wsi_reader_cache_probe", "mic_hip_session_set_tile_cache", "mic_hip_session_tile_cache_probe",
+    "mic_hip_crc32_combine", "mic_hip_compress_batch_verified", "mic_hip_pics_compress_batch_verified",
+    "mic_hip_decompress_batch_crc", "mic_hip_pics_decompress_batch_crc",
+    "mic_hip_session_digest", "mic_hip_session_verify", "mic_hip_session_encode_verified",
 ]
 
 # the readers of many rectangles per call; each has an _as twin that takes a trailing mic_hip_out_spec (OutSpec)
@@ -542,6 +556,17 @@ def lib() -> C.CDLL:
     L.mic_hip_session_set_tile_cache.argtypes = [C.c_void_p, C.c_void_p]
     L.mic_hip_session_tile_cache_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.mic_hip_tile_cache_plan.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mic_hip_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    L.mic_hip_crc32_combine.restype = C.c_uint32
+    L.mic_hip_compress_batch_verified.argtypes = [C.POINTER(EncJob), C.c_int, C.POINTER(VerifyResult)]
+    L.mic_hip_pics_compress_batch_verified.argtypes = [C.POINTER(PicsEncJob), C.c_int, C.POINTER(VerifyResult)]
+    L.mic_hip_decompress_batch_crc.argtypes = [C.POINTER(DecJob), C.c_int, C.c_void_p, C.c_void_p]
+    L.mic_hip_pics_decompress_batch_crc.argtypes = [C.POINTER(PicsDecJob), C.c_int, C.c_void_p, C.c_void_p]
+    L.mic_hip_session_digest.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Unit), C.c_int, C.c_void_p]
+    L.mic_hip_session_verify.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(Unit), C.c_int, C.c_void_p, C.POINTER(VerifyResult)]
+    L.mic_hip_session_encode_verified.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Unit), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_int32), C.POINTER(VerifyResult)]
+    L.mic_hip_debug_verify_geometry.argtypes = [C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -702,7 +727,7 @@ def _encode_batch(where: str, symbol: str, job_type, images, bound, outs=None, *
         for k, v in per.items():
             setattr(jobs[i], k, int(v[i]))
         jobs[i].out = outs[i].ctypes.data; jobs[i].out_cap = outs[i].size
-    rc = getattr(lib(), symbol)(jobs, n)
+    rc = (getattr(lib(), symbol) if isinstance(symbol, str) else symbol)(jobs, n)      # (a callable: a door with further arguments)
     if rc:
         _raise(rc, where)
     return jobs, outs
@@ -719,7 +744,7 @@ def _decode_batch(where: str, symbol: str, job_type, files, dims, outs=None):
     for i in range(n):
         jobs[i].compressed = cs[i].ctypes.data; jobs[i].compressed_len = cs[i].size
         jobs[i].pixels_out = outs[i].ctypes.data; jobs[i].width = dims[i][0]; jobs[i].height = dims[i][1]
-    rc = getattr(lib(), symbol)(jobs, n)
+    rc = (getattr(lib(), symbol) if isinstance(symbol, str) else symbol)(jobs, n)
     if rc:
         _raise(rc, where)
     return jobs, [o.reshape(h, w) for o, (w, h) in zip(outs, dims)]
@@ -860,6 +885,69 @@ def decompress_parallel_strips_batch(files: Sequence, dims: Sequence[Tuple[int, 
     """Many PICS files, one call (mic_hip_pics_decompress_batch): [(status, (height, width) uint16 pixels)]."""
     jobs, imgs = _decode_batch("decompress_parallel_strips_batch", "mic_hip_pics_decompress_batch", PicsDecJob, files, dims, outs)
     return [(j.status, im) for j, im in zip(jobs, imgs)]
+
+
+# ------------------------------------------------------------------ verified encode, CRC-32 digests
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """mic_hip_crc32_combine: zlib.crc32(A + B) from zlib.crc32(A), zlib.crc32(B) and len(B) in bytes.  Needs no device."""
+    return int(lib().mic_hip_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b)))
+
+
+def verify_geometry() -> Tuple[int, int, int]:
+    """mic_hip_debug_verify_geometry (a debug probe): the pixels a lane, a wave and a work-group of the digest kernel take"""
+    out = (C.c_uint32 * 3)()
+    rc = lib().mic_hip_debug_verify_geometry(out)
+    if rc:
+        _raise(rc, "verify_geometry")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _verified(where: str, symbol: str, job_type, images, bound, outs, **fields):
+    """_encode_batch through a _verified door: (jobs, outs, the VerifyResult per job)"""
+    res = (VerifyResult * max(len(images), 1))()
+    call = getattr(lib(), symbol)
+    jobs, outs = _encode_batch(where, lambda j, n: call(j, n, res), job_type, images, bound, outs, **fields)
+    return jobs, outs, [res[i] for i in range(len(images))]
+
+
+def compress_batch_verified(frames: Sequence[np.ndarray], max_values: Sequence[int], nstates: int = 2):
+    """compress_batch, every stream decoded again on the device and compared with its frame (mic_hip_compress_batch_verified):
+    [(status, blob, nstates_used, VerifyResult)].  A frame that fails the check has status MIC_ERR_MISMATCH and still its bytes."""
+    jobs, outs, res = _verified("compress_batch_verified", "mic_hip_compress_batch_verified", EncJob, frames,
+                                lambda i, a: _frame_bound(a.size), None, max_value=max_values, nstates=nstates)
+    return [(j.status, o[: j.out_len].tobytes(), j.nstates_used, r) for j, o, r in zip(jobs, outs, res)]
+
+
+def pics_compress_batch_verified(images: Sequence[np.ndarray], max_value: int, num_strips: int, nstates: int = 2,
+                                 outs: Optional[Sequence[np.ndarray]] = None):
+    """compress_parallel_strips_batch with the check (mic_hip_pics_compress_batch_verified): [(status, file bytes, VerifyResult of
+    the whole image, failed_strip)]."""
+    jobs, outs, res = _verified("pics_compress_batch_verified", "mic_hip_pics_compress_batch_verified", PicsEncJob, images,
+                                lambda i, a: pics_bound(a.shape[1], a.shape[0], num_strips), outs,
+                                max_value=max_value, nstates=nstates, num_strips=num_strips)
+    return [(j.status, o[: j.out_len], r, j.failed_strip) for j, o, r in zip(jobs, outs, res)]
+
+
+def _decode_crc(where: str, symbol: str, job_type, files, dims, expect, outs):
+    n = len(files)
+    crc = np.zeros(max(n, 1), dtype=np.uint32)
+    exp = None if expect is None else np.ascontiguousarray(expect, dtype=np.uint32)
+    if exp is not None and exp.size != n:
+        raise ValueError(where + ": expect must hold one CRC per file")
+    call = getattr(lib(), symbol)
+    jobs, imgs = _decode_batch(where, lambda j, k: call(j, k, None if exp is None else exp.ctypes.data, crc.ctypes.data), job_type, files, dims, outs)
+    return [(j.status, im, int(crc[i])) for i, (j, im) in enumerate(zip(jobs, imgs))]
+
+
+def decompress_batch_crc(blobs: Sequence[bytes], dims: Sequence[Tuple[int, int]], expect=None, outs=None):
+    """decompress_batch with the CRC-32 of every decoded frame, taken on the device (mic_hip_decompress_batch_crc):
+    [(status, pixels, crc32)].  expect: one CRC per blob; a frame whose CRC differs has status MIC_ERR_MISMATCH (and its pixels)."""
+    return _decode_crc("decompress_batch_crc", "mic_hip_decompress_batch_crc", DecJob, blobs, dims, expect, outs)
+
+
+def pics_decompress_batch_crc(files: Sequence, dims: Sequence[Tuple[int, int]], expect=None, outs=None):
+    """decompress_parallel_strips_batch with the CRC-32 of every decoded image (mic_hip_pics_decompress_batch_crc)."""
+    return _decode_crc("pics_decompress_batch_crc", "mic_hip_pics_decompress_batch_crc", PicsDecJob, files, dims, expect, outs)
 
 
 def host_alloc(nbytes: int, dtype=np.uint8) -> np.ndarray:
@@ -2342,6 +2430,50 @@ class Session:
         if rc:
             _raise(rc, "session_decode_finish")
         return st
+
+    # ---- digests, verify, verified encode (include/mic_hip.h, "verified encode") -----------------------------------------
+    def encode(self, d_pixels: int, units):
+        """encode_enqueue + encode_finish: (d_blobs, offsets, status, nstates)"""
+        self.encode_enqueue(d_pixels, units)
+        return self.encode_finish()
+
+    def decode(self, d_blobs: int, offsets: np.ndarray, units, d_pixels_out: int) -> np.ndarray:
+        """decode_enqueue + decode_finish: status per unit"""
+        self.decode_enqueue(d_blobs, offsets, units, d_pixels_out)
+        return self.decode_finish()
+
+    def digest(self, d_pixels: int, units) -> np.ndarray:
+        """mic_hip_session_digest: the CRC-32 (zlib.crc32 of the little-endian bytes) of every unit's pixels, taken on the device"""
+        crc = np.empty(len(units), dtype=np.uint32)
+        rc = lib().mic_hip_session_digest(self._h, d_pixels, units, len(units), crc.ctypes.data)
+        if rc:
+            _raise(rc, "session_digest")
+        return crc
+
+    def verify(self, d_blobs: int, offsets: np.ndarray, units, d_pixels_ref: int) -> List[VerifyResult]:
+        """mic_hip_session_verify: the streams decoded into the session's scratch and compared with the reference pixels"""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.size < len(units) + 1:
+            raise ValueError("verify: offsets must hold len(units) + 1 entries")
+        res = (VerifyResult * len(units))()
+        rc = lib().mic_hip_session_verify(self._h, d_blobs, offs.ctypes.data_as(C.POINTER(C.c_uint64)), units, len(units), d_pixels_ref, res)
+        if rc:
+            _raise(rc, "session_verify")
+        return list(res)
+
+    def encode_verified(self, d_pixels: int, units):
+        """mic_hip_session_encode_verified: encode, then the packed streams decoded and compared with d_pixels --
+        (d_blobs, offsets, nstates, [VerifyResult]); blobs, offsets and nstates are encode's, byte for byte."""
+        n = len(units)
+        offs = np.empty(n + 1, dtype=np.uint64); ns = np.empty(n, dtype=np.int32)
+        res = (VerifyResult * n)()
+        d = C.c_void_p()
+        rc = lib().mic_hip_session_encode_verified(self._h, d_pixels, units, n, C.byref(d), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   ns.ctypes.data_as(C.POINTER(C.c_int32)), res)
+        if rc:
+            _raise(rc, "session_encode_verified")
+        self._n = n
+        return d.value, offs, ns, list(res)
 
     # ---- RGB images on the device (rgbcompress.go:25-33) ----------------------------------------------------------------
     @staticmethod

@@ -368,6 +368,107 @@ int session_decode_finish(mic_hip_session *s, int32_t *h_status) {
     return MIC_OK;
 }
 
+// ---- digests and compares (mic_verify.hip) -------------------------------------------------------
+// The host's part: the chunk -> unit table of the flat grid (a unit's body is cut from its END, mic_verify.h), built the way the
+// readers build their piece lists; one upload, two launches, one download; the CRC's init and final xor once per unit.
+int session_digest_run(mic_hip_session *s, const uint16_t *d_ref, const uint16_t *d_dec, const mic_hip_unit *units, int n,
+                       const uint8_t *compare, mic_hip_verify_result *res) {
+    if (n <= 0) return MIC_ERR_ARGS;
+    for (int i = 0; i < n; i++) {
+        if (units[i].width <= 0 || units[i].height <= 0) return MIC_ERR_ARGS;
+        if ((size_t)units[i].width * (size_t)units[i].height > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;   // (a pixel index fits the kernels' 32 bits)
+    }
+    if (d_dec && (((uintptr_t)d_ref ^ (uintptr_t)d_dec) & 15u)) return MIC_ERR_INTERNAL;   // (the two copies share their 16-byte boundaries: mic_verify.h)
+    if (!s->stream) HIP_TRY(mic_stream_create(&s->stream));
+    const size_t units_bytes = align_up(sizeof(MicVerifyUnit) * (size_t)n, 16);
+    s->verify_up.resize(units_bytes);
+    std::vector<uint32_t> first_chunk((size_t)n + 1);
+    uint64_t nchunks = 0;
+    bool any_compare = false;
+    for (int i = 0; i < n; i++) {
+        const uint64_t npx = (uint64_t)units[i].width * (uint64_t)units[i].height;
+        const uint16_t *ref = d_ref + units[i].px_offset;
+        const uint64_t base = (uint64_t)(uintptr_t)ref;
+        const int64_t body = (int64_t)(((base + 2 * npx) & ~(uint64_t)15) - base);
+        const uint64_t nch = body > 0 ? ((uint64_t)body + MIC_VFY_CHUNK_BYTES - 1) / MIC_VFY_CHUNK_BYTES : 0;
+        const bool cmp = d_dec && (!compare || compare[i]);
+        any_compare |= cmp;
+        MicVerifyUnit vu{ ref, cmp ? d_dec + units[i].px_offset : nullptr, npx, (uint32_t)nchunks, (uint32_t)nch };
+        memcpy(s->verify_up.data() + sizeof(MicVerifyUnit) * (size_t)i, &vu, sizeof vu);
+        first_chunk[(size_t)i] = (uint32_t)nchunks;
+        nchunks += nch;
+        if (nchunks > 0x7FFFFFFFull) return MIC_ERR_UNSUPPORTED;           // (a launch's grid)
+    }
+    first_chunk[(size_t)n] = (uint32_t)nchunks;
+    const size_t table_bytes = align_up(4 * (size_t)nchunks, 16);
+    s->verify_up.resize(units_bytes + table_bytes);
+    uint32_t *tab = (uint32_t *)(s->verify_up.data() + units_bytes);
+    for (int i = 0; i < n; i++) std::fill(tab + first_chunk[(size_t)i], tab + first_chunk[(size_t)i + 1], (uint32_t)i);
+    // device layout: [unit records][chunk -> unit][chunk registers][mism n x u64][first n x u64][reg n x u32]
+    const size_t off_partial = units_bytes + table_bytes, off_mism = off_partial + table_bytes, off_first = off_mism + 8 * (size_t)n,
+                 off_reg = off_first + 8 * (size_t)n, total = off_reg + align_up(4 * (size_t)n, 8);
+    int rc = s->verify_tab.reserve(total);
+    if (rc) return rc;
+    char *d = (char *)s->verify_tab.p;
+    HIP_TRY(hipMemcpyAsync(d, s->verify_up.data(), units_bytes + table_bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(d + off_mism, 0, 8 * (size_t)n, s->stream));
+    HIP_TRY(hipMemsetAsync(d + off_first, 0xFF, 8 * (size_t)n, s->stream));
+    s->timer.stream = s->stream;
+    mic_launch_units_digest((const MicVerifyUnit *)d, n, (const uint32_t *)(d + units_bytes), (uint32_t)nchunks, any_compare, (uint32_t *)(d + off_partial),
+                            (uint32_t *)(d + off_reg), (unsigned long long *)(d + off_mism), (unsigned long long *)(d + off_first), s->stream, &s->timer);
+    HIP_TRY(hipGetLastError());
+    s->verify_down.resize((total - off_mism) / 8);
+    HIP_TRY(hipMemcpyAsync(s->verify_down.data(), d + off_mism, total - off_mism, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const uint64_t *mism = s->verify_down.data(), *first = mism + n;
+    const uint32_t *reg = (const uint32_t *)(first + n);
+    for (int i = 0; i < n; i++) {
+        const uint64_t bytes = 2 * (uint64_t)units[i].width * (uint64_t)units[i].height;
+        auto it = s->verify_init.find(bytes);
+        if (it == s->verify_init.end()) {
+            if (s->verify_init.size() > 4096) s->verify_init.clear();
+            it = s->verify_init.emplace(bytes, mic_crc_mul(0xFFFFFFFFu, mic_crc_xpow8(bytes))).first;
+        }
+        res[i].crc32 = reg[i] ^ it->second ^ 0xFFFFFFFFu;
+        res[i].mismatches = mism[i];
+        res[i].first_mismatch = first[i] == ~0ull ? -1 : (int64_t)first[i];
+    }
+    return MIC_OK;
+}
+
+int session_verify(mic_hip_session *s, const uint8_t *d_base, const uint64_t *begins, const uint64_t *ends, const mic_hip_unit *units, int n,
+                   const uint16_t *d_ref, const int32_t *skip, mic_hip_verify_result *res) {
+    if (n <= 0) return MIC_ERR_ARGS;
+    // the units that are decoded, in their order; each keeps its px_offset in the scratch buffer
+    std::vector<int> idx;
+    std::vector<mic_hip_unit> du; std::vector<uint64_t> b, e;
+    size_t extent = 0;
+    for (int i = 0; i < n; i++) {
+        if (units[i].width <= 0 || units[i].height <= 0) return MIC_ERR_ARGS;
+        res[i].status = skip ? skip[i] : MIC_OK;
+        if (res[i].status != MIC_OK) continue;
+        idx.push_back(i); du.push_back(units[i]); b.push_back(begins[i]); e.push_back(ends[i]);
+        extent = std::max(extent, (size_t)units[i].px_offset + (size_t)units[i].width * (size_t)units[i].height);
+    }
+    std::vector<uint8_t> cmp((size_t)n, 0);
+    uint16_t *d_dec = nullptr;
+    if (!idx.empty()) {
+        int rc = s->verify_px.reserve(extent * 2 + 16 + 64);
+        if (rc) return rc;
+        // (the scratch copy starts where the reference does modulo 16, whatever the caller's pointer: the compare kernel's 16-byte loads then serve both)
+        d_dec = (uint16_t *)((char *)s->verify_px.p + ((uintptr_t)d_ref & 15u));
+        std::vector<int32_t> st(idx.size());
+        if ((rc = session_decode_enqueue_spans(s, d_base, b.data(), e.data(), du.data(), (int)idx.size(), d_dec))) return rc;
+        // (the compare is launched behind the finish: a tier-1 chain that ran again in tier 2 wrote the pixels twice, and these are the run that counted)
+        if ((rc = session_decode_finish(s, st.data()))) return rc;
+        for (size_t k = 0; k < idx.size(); k++) { res[idx[k]].status = st[k]; cmp[(size_t)idx[k]] = st[k] == MIC_OK; }
+    }
+    const int rc = session_digest_run(s, d_ref, d_dec, units, n, cmp.data(), res);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) if (res[i].status == MIC_OK && res[i].mismatches) res[i].status = MIC_ERR_MISMATCH;
+    return MIC_OK;
+}
+
 // (the host-pointer batch and container entry points live in mic_host_io.hip)
 
 size_t unit_ws_bytes_tier(size_t px, int tier) {
@@ -667,6 +768,43 @@ int mic_hip_session_decode(mic_hip_session *s, const uint8_t *d_blobs, const uin
     int rc = mic_hip_session_decode_enqueue(s, d_blobs, h_offsets, units, n, d_pixels_out);
     if (rc) return rc;
     return mic_hip_session_decode_finish(s, h_status);
+} MIC_ABI_CATCH
+// ---- digests, verify, verified encode (session_digest_run / session_verify above)
+int mic_hip_session_digest(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n, uint32_t *h_crc) try {
+    if (!s || !d_pixels || !units || !h_crc || n <= 0) return MIC_ERR_ARGS;
+    { const int arc = s->activate(); if (arc) return arc; }
+    std::vector<mic_hip_verify_result> res((size_t)n);
+    s->timer.reset(s->stream);
+    const int rc = session_digest_run(s, d_pixels, nullptr, units, n, nullptr, res.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) h_crc[i] = res[(size_t)i].crc32;
+    return MIC_OK;
+} MIC_ABI_CATCH
+int mic_hip_session_verify(mic_hip_session *s, const uint8_t *d_blobs, const uint64_t *h_offsets, const mic_hip_unit *units, int n,
+                           const uint16_t *d_pixels_ref, mic_hip_verify_result *h_res) try {
+    if (!s || !d_blobs || !h_offsets || !units || !d_pixels_ref || !h_res || n <= 0) return MIC_ERR_ARGS;
+    { const int arc = s->activate(); if (arc) return arc; }
+    return session_verify(s, d_blobs, h_offsets, h_offsets + 1, units, n, d_pixels_ref, nullptr, h_res);
+} MIC_ABI_CATCH
+int mic_hip_session_encode_verified(mic_hip_session *s, const uint16_t *d_pixels, const mic_hip_unit *units, int n,
+                                    const uint8_t **d_blobs, uint64_t *h_offsets, int32_t *h_nstates, mic_hip_verify_result *h_res) try {
+    if (!s || !d_pixels || !units || !h_offsets || !h_res || n <= 0) return MIC_ERR_ARGS;
+    { const int arc = s->activate(); if (arc) return arc; }
+    std::vector<int32_t> st((size_t)n);
+    const uint8_t *packed = nullptr;
+    int rc = session_encode_enqueue(s, d_pixels, units, n);
+    if (rc == MIC_OK) rc = session_encode_finish(s, &packed, h_offsets, st.data(), h_nstates);
+    if (rc) return rc;
+    if (d_blobs) *d_blobs = packed;
+    // (the packed buffer is no slab of the workspace: it stands while the decode lays the workspace out anew)
+    return session_verify(s, packed, h_offsets, h_offsets + 1, units, n, d_pixels, st.data(), h_res);
+} MIC_ABI_CATCH
+// debug probe (not in the public header): the digest kernels' geometry in PIXELS -- out[0] a lane's run, out[1] a wave's, out[2] a
+// work-group's chunk (mic_verify.h); tests aim units at these seams
+int mic_hip_debug_verify_geometry(uint32_t *out) try {
+    if (!out) return MIC_ERR_ARGS;
+    out[0] = MIC_VFY_LANE_BYTES / 2; out[1] = MIC_VFY_WAVE_BYTES / 2; out[2] = MIC_VFY_CHUNK_BYTES / 2;
+    return MIC_OK;
 } MIC_ABI_CATCH
 // debug probe (not part of the public header): raw result fields of unit i after a *_finish
 int mic_hip_debug_unit(mic_hip_session *s, int i, uint32_t *out8) try {

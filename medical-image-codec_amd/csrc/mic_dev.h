@@ -27,6 +27,7 @@ __host__ __device__ inline uint32_t mic_gap_stride(uint32_t tab_cap) { return (2
 #define MICD_ERR_INTERNAL       -8
 #define MICD_ERR_UNSUPPORTED    -9
 #define MICD_ERR_INCOMPRESSIBLE -10
+#define MICD_ERR_MISMATCH      -12    // the verify calls: decoded pixels differ from the reference (mic_verify.hip; the host sets it)
 #define MICD_INT_GROW           -21    // internal: a tier-1 slab would overflow; the host runs the batch again in tier 2 (never surfaces)
 #define MICD_GAP_CHECK          -22    // internal: a gap-removal unit for k_dec_gap_check, the checking decode path (never surfaces)
 // MicUnit.dec_kernel behind the 30 lane-per-state classes (1 .. 30)

@@ -188,6 +188,7 @@ struct EncGroup {
 struct EncUnit {
     uint64_t px_off; int32_t w, h; uint16_t maxv, nstates; int group;
     int32_t status = MIC_OK, nstates_used = 0; size_t len = 0;
+    mic_hip_verify_result vr{ MIC_OK, 0, 0, -1 };     // the verified doors: what the check of this unit's stream said
 };
 struct DecGroup {
     const uint8_t *h_comp; uint16_t *h_px;
@@ -198,6 +199,7 @@ struct DecGroup {
 struct DecUnit {
     size_t comp_off, comp_len; uint64_t px_off; int32_t w, h; uint16_t flags; int group;
     int32_t status = MIC_OK;
+    uint32_t crc = 0;                                 // the _crc doors: CRC-32 of the unit's decoded pixels
 };
 
 inline bool unit_gap(const EncUnit &u) { return (u.nstates & MIC_HIP_GAP_REMOVAL) != 0; }
@@ -205,13 +207,15 @@ inline bool unit_gap(const DecUnit &u) { return (u.flags & MIC_HIP_GAP_REMOVAL) 
 // units [i0, i1) of the next sub-batch of units [.., n): under the workspace ceiling, and -- when the call is large enough to be worth a pipeline --
 // about `target` units (the kernels want a couple of thousand units per launch: the tANS decode chain takes as long for ten
 // streams as for 2304)
+// staging: bytes per pixel a unit holds beside its slabs -- two halves each of the pixels, the streams, the packed buffer; the verified
+// encode adds the pixels its streams decode to
 template <class U>
-int next_cut(const std::vector<U> &units, int i0, int n, size_t target) {
+int next_cut(const std::vector<U> &units, int i0, int n, size_t target, size_t staging = 12) {
     size_t max_px = 0, gap_x = 0, cap = 0;
     return (int)next_sub_batch((size_t)i0, (size_t)n, [&](size_t i) { return (size_t)units[i].w * (size_t)units[i].h; }, [&](size_t i, size_t mp) {
         // (a gap-removal unit holds a map slab beside the others: the tier-2 one is counted)
         const size_t gx = std::max(gap_x, unit_gap(units[i]) ? (size_t)mic_gap_stride(65536u) : (size_t)0);
-        if (mp != max_px || gx != gap_x || cap == 0) cap = batch_units_for(mp, 1, 12 * mp + gx);   // (+ the staging: two halves each of the pixels, the streams, the packed buffer)
+        if (mp != max_px || gx != gap_x || cap == 0) cap = batch_units_for(mp, 1, staging * mp + gx);
         max_px = mp; gap_x = gx;
         return cap;
     }, CutRule{ 65535, target });
@@ -229,13 +233,15 @@ inline size_t pipeline_target(size_t n_units, bool encode) {
 }
 
 // Groups [g0, g1) of the call -- their units are one range of U -- on session s; G and U are the caller's, every index is the call's.
-int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncUnit> &U, int g0, int g1) {
+// verify: every sub-batch's packed streams are decoded again and compared with its pixels, both still on the device (session_verify);
+// U[i].vr says what came of it.  Nothing else changes: a unit that fails the check is delivered like any other.
+int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncUnit> &U, int g0, int g1, bool verify = false) {
     if (g0 >= g1) return MIC_OK;
     const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
     if (u0 == n) return MIC_OK;
     const size_t target = pipeline_target((size_t)(n - u0), true);
     struct Sub { int i0, i1; std::vector<mic_hip_unit> units; size_t px; };
-    const std::vector<Sub> subs = staged_cut<Sub>(u0, n, [&](int i0) { return next_cut(U, i0, n, target); }, [&](int i0, int i1) {
+    const std::vector<Sub> subs = staged_cut<Sub>(u0, n, [&](int i0) { return next_cut(U, i0, n, target, verify ? 14 : 12); }, [&](int i0, int i1) {
         Sub sb{ i0, i1, std::vector<mic_hip_unit>((size_t)(i1 - i0)), 0 };
         for (int i = i0; i < i1; i++) {
             const EncUnit &u = U[(size_t)i];
@@ -270,6 +276,11 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
         const uint8_t *d_blobs = nullptr;
         int rc = session_encode_enqueue(s, (const uint16_t *)in[half]->p, sb.units.data(), nb);
         if (rc == MIC_OK) rc = session_encode_finish(s, &d_blobs, offs.data(), st.data(), ns.data());
+        if (rc == MIC_OK && verify) {                      // (the pixels are still in this half, the streams in s->packed)
+            std::vector<mic_hip_verify_result> vr((size_t)nb);
+            rc = session_verify(s, d_blobs, offs.data(), offs.data() + 1, sb.units.data(), nb, (const uint16_t *)in[half]->p, st.data(), vr.data());
+            for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) U[(size_t)i].vr = vr[(size_t)(i - sb.i0)];
+        }
         if (rc == MIC_OK) rc = keep_packed(s, prev);
         if (rc != MIC_OK) return rc;
         prev = &down;
@@ -296,7 +307,8 @@ int encode_groups(mic_hip_session *s, std::vector<EncGroup> &G, std::vector<EncU
     });
 }
 
-int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecUnit> &U, int g0, int g1) {
+// digest: U[i].crc = the CRC-32 of every unit's decoded pixels, taken on the device in front of the download
+int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecUnit> &U, int g0, int g1, bool digest = false) {
     if (g0 >= g1) return MIC_OK;
     const int u0 = G[(size_t)g0].first, n = G[(size_t)g1 - 1].first + G[(size_t)g1 - 1].n;
     if (u0 == n) return MIC_OK;
@@ -355,6 +367,12 @@ int decode_groups(mic_hip_session *s, std::vector<DecGroup> &G, std::vector<DecU
         if (rc == MIC_OK) rc = session_decode_enqueue_spans(s, (const uint8_t *)in[half]->p, sb.begins.data(), sb.ends.data(), sb.units.data(), nb, (uint16_t *)outb[half]->p);
         if (rc == MIC_OK) rc = session_decode_finish(s, st.data());
         mark("decoded", k);
+        if (rc == MIC_OK && digest) {                      // (a unit that failed to decode is hashed too -- its pixels lie inside the half -- and not reported)
+            std::vector<mic_hip_verify_result> vr((size_t)nb);
+            rc = session_digest_run(s, (const uint16_t *)outb[half]->p, nullptr, sb.units.data(), nb, nullptr, vr.data());
+            for (int i = sb.i0; i < sb.i1 && rc == MIC_OK; i++) U[(size_t)i].crc = vr[(size_t)(i - sb.i0)].crc32;
+            mark("digests", k);
+        }
         if (rc != MIC_OK) return rc;
         for (int i = sb.i0; i < sb.i1;) {
             DecGroup &g = G[(size_t)U[(size_t)i].group];
@@ -598,9 +616,12 @@ int pica_encode_run(mic_hip_session *s, std::vector<PicaRun> &J, int j0, int nj)
 // The batch decoder of both: a file is a header and one unit per strip.  info: the file's width, height and strip count;
 // entry(c, h, n, k): strip k as its header states it (pics_strip_entry / pica_strip_entry, mic_session.h); pica: the call is a PICA
 // one (-DMIC_PICA_TIMING builds time those).
+// crc (with it the call takes digests; null: not): crc[i] = the CRC-32 of job i's image, its strips' CRCs joined in order; expect
+// (nullable): a decoded job whose CRC differs becomes MIC_ERR_MISMATCH.
 template <class Job, class Info, class Entry>
-int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry entry) {
+int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry entry, const uint32_t *expect = nullptr, uint32_t *crc = nullptr) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    for (int i = 0; crc && i < njobs; i++) crc[i] = 0;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
     if (rc) return rc;
@@ -624,6 +645,7 @@ int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry en
         // pixels no strip writes come back as zeros, like the reference's make([]uint16, w*h) (parallelstrips.go:288,
         // parallelstripsadaptive.go:175): a header whose strips do not cover the image is accepted there
         if (covered < (size_t)w * (size_t)h) memset(j.pixels_out, 0, (size_t)w * (size_t)h * 2);
+        if (crc && covered != (size_t)w * (size_t)h) { U.resize(u0); j.status = MIC_ERR_UNSUPPORTED; continue; }   // (strips that leave holes or overlap: no fold of strip digests is the image's)
         G.push_back(DecGroup{ j.compressed, j.pixels_out, (int)u0, n });
         job_of.push_back(i);
     }
@@ -633,8 +655,18 @@ int strips_decompress_batch(Job *jobs, int njobs, bool pica, Info info, Entry en
     std::unique_ptr<PicaTimingScope> timing(pica ? new PicaTimingScope(lease.s, "decode") : nullptr);
 #endif
     if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
-                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1); }))) return rc;
+                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1, crc != nullptr); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) { jobs[job_of[k]].status = G[k].status; jobs[job_of[k]].failed_strip = G[k].failed; }   // "strip %d: %w", parallelstrips.go:316; "pica: strip %d: %w", :207
+    for (size_t k = 0; crc && k < G.size(); k++) {
+        if (G[k].status != MIC_OK) continue;
+        uint32_t c = 0;
+        for (int q = G[k].first; q < G[k].first + G[k].n; q++) {
+            const DecUnit &u = U[(size_t)q];
+            c = q == G[k].first ? u.crc : mic_hip_crc32_combine(c, u.crc, 2 * (uint64_t)u.w * (uint64_t)u.h);
+        }
+        crc[job_of[k]] = c;
+        if (expect && expect[job_of[k]] != c) jobs[job_of[k]].status = MIC_ERR_MISMATCH;
+    }
     return MIC_OK;
 }
 
@@ -1091,6 +1123,9 @@ extern "C" {
 
 // The cut of `n` weighted items into `shards` contiguous shards that the batch entry points use across the devices of
 // mic_hip_set_devices (first[0 .. shards]: item i belongs to shard k iff first[k] <= i < first[k + 1]); no device needed.
+// crc(A || B) = crc(A) * x^(8 |B|) xor crc(B): the init and final xor of the two finished CRCs cancel (mic_verify.h)
+uint32_t mic_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return mic_crc_mul(crc_a, mic_crc_xpow8(len_b)) ^ crc_b; }
+
 int mic_hip_shard_plan(const uint64_t *weights, int n, int shards, int *first) try {
     if (!weights || !first || n < 0 || shards <= 0) return MIC_ERR_ARGS;
     plan_shards(weights, n, shards, first);
@@ -1107,8 +1142,27 @@ void *mic_hip_host_alloc(size_t bytes) {
 }
 void mic_hip_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
-// flags: OR-ed into every unit's nstates (MIC_HIP_GAP_REMOVAL for the _gap entry points)
-static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
+// What the verified doors report of a group: its units' results joined in order -- the CRCs by mic_hip_crc32_combine (the units are
+// contiguous runs of the group's pixels), the mismatches summed, the first one as the group's pixel index.  *failed (nullable): the
+// first unit that mismatched, counted from the group's first.  status: the group's codec status, or MIC_ERR_MISMATCH.
+static mic_hip_verify_result group_verify_result(const EncGroup &g, const std::vector<EncUnit> &U, int *failed) {
+    mic_hip_verify_result r{ g.status, 0, 0, -1 };
+    for (int q = g.first; q < g.first + g.n; q++) {
+        const EncUnit &u = U[(size_t)q];
+        r.crc32 = q == g.first ? u.vr.crc32 : mic_hip_crc32_combine(r.crc32, u.vr.crc32, 2 * (uint64_t)u.w * (uint64_t)u.h);
+        if (u.vr.mismatches && r.mismatches == 0) {
+            r.first_mismatch = (int64_t)u.px_off - (int64_t)U[(size_t)g.first].px_off + u.vr.first_mismatch;
+            if (failed && g.status == MIC_OK) *failed = q - g.first;
+        }
+        r.mismatches += u.vr.mismatches;
+    }
+    if (g.status == MIC_OK && r.mismatches) r.status = MIC_ERR_MISMATCH;
+    if (g.status != MIC_OK) { r.mismatches = 0; r.first_mismatch = -1; }       // (the job was not delivered: what its other units said is no use)
+    return r;
+}
+
+// flags: OR-ed into every unit's nstates (MIC_HIP_GAP_REMOVAL for the _gap entry points); res (nullable): the verified door
+static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags, mic_hip_verify_result *res = nullptr) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
@@ -1117,6 +1171,7 @@ static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
     for (int i = 0; i < njobs; i++) {
         mic_hip_enc_job &j = jobs[i];
         j.out_len = 0; j.nstates_used = 0;
+        if (res) res[i] = mic_hip_verify_result{ MIC_ERR_ARGS, 0, 0, -1 };
         if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || (size_t)j.width * (size_t)j.height > ((size_t)1 << 28) ||
             !(j.nstates == 2 || j.nstates == 4 || j.nstates == 8)) { j.status = MIC_ERR_ARGS; continue; }
         G.push_back(EncGroup{ j.pixels, DestRun{ j.out, j.out_cap, 0 }, (int)U.size(), 1 });
@@ -1124,14 +1179,19 @@ static int compress_jobs(mic_hip_enc_job *jobs, int njobs, uint16_t flags) {
         job_of.push_back(i);
     }
     if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
-                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1); }))) return rc;
+                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1, res != nullptr); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) {
         mic_hip_enc_job &j = jobs[job_of[k]];
         j.status = G[k].status; j.nstates_used = U[k].nstates_used;
         j.out_len = G[k].status == MIC_OK ? G[k].dst.written : 0;
+        if (res) j.status = (res[job_of[k]] = group_verify_result(G[k], U, nullptr)).status;   // (MIC_ERR_MISMATCH: the bytes stand, out_len says how many)
     }
     return MIC_OK;
 }
+int mic_hip_compress_batch_verified(mic_hip_enc_job *jobs, int njobs, mic_hip_verify_result *res) try {
+    if (!res && njobs > 0) return MIC_ERR_ARGS;
+    return compress_jobs(jobs, njobs, 0, res);
+} MIC_ABI_CATCH
 int mic_hip_compress_batch(mic_hip_enc_job *jobs, int njobs) try {
     return compress_jobs(jobs, njobs, 0);
 } MIC_ABI_CATCH
@@ -1139,8 +1199,10 @@ int mic_hip_compress_batch_gap(mic_hip_enc_job *jobs, int njobs) try {
     return compress_jobs(jobs, njobs, MIC_HIP_GAP_REMOVAL);
 } MIC_ABI_CATCH
 
-static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
+// crc (with it the call takes digests), expect (nullable): as strips_decompress_batch's
+static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags, const uint32_t *expect = nullptr, uint32_t *crc = nullptr) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
+    for (int i = 0; crc && i < njobs; i++) crc[i] = 0;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
     if (rc) return rc;
@@ -1156,10 +1218,19 @@ static int decompress_jobs(mic_hip_dec_job *jobs, int njobs, uint16_t flags) {
         job_of.push_back(i);
     }
     if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
-                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1); }))) return rc;
-    for (size_t k = 0; k < G.size(); k++) jobs[job_of[k]].status = G[k].status;
+                           [&](mic_hip_session *s, int g0, int g1) { return decode_groups(s, G, U, g0, g1, crc != nullptr); }))) return rc;
+    for (size_t k = 0; k < G.size(); k++) {
+        jobs[job_of[k]].status = G[k].status;
+        if (!crc || G[k].status != MIC_OK) continue;
+        crc[job_of[k]] = U[k].crc;
+        if (expect && expect[job_of[k]] != U[k].crc) jobs[job_of[k]].status = MIC_ERR_MISMATCH;
+    }
     return MIC_OK;
 }
+int mic_hip_decompress_batch_crc(mic_hip_dec_job *jobs, int njobs, const uint32_t *expect, uint32_t *crc) try {
+    if (!crc && njobs > 0) return MIC_ERR_ARGS;
+    return decompress_jobs(jobs, njobs, 0, expect, crc);
+} MIC_ABI_CATCH
 int mic_hip_decompress_batch(mic_hip_dec_job *jobs, int njobs) try {
     return decompress_jobs(jobs, njobs, 0);
 } MIC_ABI_CATCH
@@ -1168,7 +1239,8 @@ int mic_hip_decompress_batch_gap(mic_hip_dec_job *jobs, int njobs) try {
 } MIC_ABI_CATCH
 
 // ---- PICS (parallelstrips.go) ----------------------------------------------------------------
-int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
+// res (nullable): the verified door
+static int pics_compress_jobs(mic_hip_pics_enc_job *jobs, int njobs, mic_hip_verify_result *res) {
     if (!jobs || njobs < 0) return MIC_ERR_ARGS;
     if (njobs == 0) return MIC_OK;
     int rc = ensure_device();
@@ -1179,11 +1251,12 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
     for (int i = 0; i < njobs; i++) {
         mic_hip_pics_enc_job &j = jobs[i];
         j.out_len = 0; j.failed_strip = -1;
+        if (res) res[i] = mic_hip_verify_result{ MIC_ERR_ARGS, 0, 0, -1 };
         if (!j.pixels || !j.out || j.width <= 0 || j.height <= 0 || j.num_strips <= 0 || !(j.nstates == 2 || j.nstates == 4 || j.nstates == 8)) { j.status = MIC_ERR_ARGS; continue; }
         int strip_h, actual; pics_geometry(j.height, j.num_strips, strip_h, actual);
         const size_t header = 20 + (size_t)actual * 8;
-        if ((size_t)j.width * (size_t)strip_h > ((size_t)1 << 28)) { j.status = MIC_ERR_UNSUPPORTED; continue; }
-        if (j.out_cap < header) { j.status = MIC_ERR_CAPACITY; continue; }
+        if ((size_t)j.width * (size_t)strip_h > ((size_t)1 << 28)) { j.status = MIC_ERR_UNSUPPORTED; if (res) res[i].status = j.status; continue; }
+        if (j.out_cap < header) { j.status = MIC_ERR_CAPACITY; if (res) res[i].status = j.status; continue; }
         G.push_back(EncGroup{ j.pixels, DestRun{ j.out, j.out_cap, header }, (int)U.size(), actual });
         for (int s = 0; s < actual; s++) {
             const int y0 = s * strip_h, y1 = std::min(j.height, y0 + strip_h);
@@ -1192,14 +1265,16 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
         job_of.push_back(i); geo.push_back(Geo{ strip_h, actual });
     }
     if ((rc = over_devices((int)G.size(), [&](int g) { return group_px(G[(size_t)g], U); },
-                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1); }))) return rc;
+                           [&](mic_hip_session *s, int g0, int g1) { return encode_groups(s, G, U, g0, g1, res != nullptr); }))) return rc;
     for (size_t k = 0; k < G.size(); k++) {
         mic_hip_pics_enc_job &j = jobs[job_of[k]];
         const EncGroup &g = G[k];
         j.status = g.status;                                                   // first failing strip, :95-99
         j.failed_strip = g.failed;                                             // "parallelstrips: strip %d: %w", :97
+        if (res) res[job_of[k]] = group_verify_result(g, U, &j.failed_strip);
         if (j.status != MIC_OK) continue;
-        if (g.dst.written > 0xFFFFFFFFull) { j.status = MIC_ERR_UNSUPPORTED; continue; }
+        if (g.dst.written > 0xFFFFFFFFull) { j.status = MIC_ERR_UNSUPPORTED; if (res) res[job_of[k]].status = j.status; continue; }
+        if (res) j.status = res[job_of[k]].status;                             // (MIC_ERR_MISMATCH: the file is written all the same)
         uint8_t *out = j.out;
         memcpy(out, "PICS", 4);
         put_u32(out + 4, (uint32_t)j.width); put_u32(out + 8, (uint32_t)j.height);
@@ -1214,6 +1289,13 @@ int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
         j.out_len = g.dst.hdr + g.dst.written;
     }
     return MIC_OK;
+}
+int mic_hip_pics_compress_batch(mic_hip_pics_enc_job *jobs, int njobs) try {
+    return pics_compress_jobs(jobs, njobs, nullptr);
+} MIC_ABI_CATCH
+int mic_hip_pics_compress_batch_verified(mic_hip_pics_enc_job *jobs, int njobs, mic_hip_verify_result *res) try {
+    if (!res && njobs > 0) return MIC_ERR_ARGS;
+    return pics_compress_jobs(jobs, njobs, res);
 } MIC_ABI_CATCH
 
 int mic_hip_pics_compress(const uint16_t *pixels, int width, int height, uint16_t max_value, int num_strips, int nstates,
@@ -1238,6 +1320,12 @@ int mic_hip_pics_compress_ex(const uint16_t *pixels, int width, int height, uint
 int mic_hip_pics_decompress_batch(mic_hip_pics_dec_job *jobs, int njobs) try {
     return strips_decompress_batch(jobs, njobs, false,
         [](const uint8_t *c, size_t len, int *w, int *h, int *n) { return mic_hip_pics_info(c, len, w, h, n, nullptr); }, pics_strip_entry);
+} MIC_ABI_CATCH
+
+int mic_hip_pics_decompress_batch_crc(mic_hip_pics_dec_job *jobs, int njobs, const uint32_t *expect, uint32_t *crc) try {
+    if (!crc && njobs > 0) return MIC_ERR_ARGS;
+    return strips_decompress_batch(jobs, njobs, false,
+        [](const uint8_t *c, size_t len, int *w, int *h, int *n) { return mic_hip_pics_info(c, len, w, h, n, nullptr); }, pics_strip_entry, expect, crc);
 } MIC_ABI_CATCH
 
 int mic_hip_pics_decompress(const uint8_t *c, size_t len, uint16_t *pixels_out, int width, int height) try {

@@ -18,6 +18,7 @@
 #include "../../include/mic_hip.h"
 #include "mic_dev.h"
 #include "mic_launch.h"
+#include "mic_verify.h"
 
 struct mic_hip_session;
 
@@ -187,6 +188,10 @@ struct mic_hip_session {
     DevBuf rgb_payload, rgb_payload2;      // ... and its assembled blobs: two halves, one goes down while the other is written
     DevBuf mic2_files, mic2_payload;       // mic_hip_session_mic2_encode: the call's MIC2 files back to back; the streams of its sub-batches until they are assembled (mic_mic2_batch.hip)
     PinnedU64 rgb_pin;                     // ... the host's copy of the plane statistics / the blob heads
+    DevBuf verify_px;                      // mic_hip_session_verify / _encode_verified: the pixels the checked streams decode to (empty until the first such call)
+    DevBuf verify_tab;                     // the digest kernels' unit records, chunk table, chunk registers and per-unit results (mic_verify.h)
+    std::vector<uint8_t> verify_up; std::vector<uint64_t> verify_down;   // ... their host copies on the way up and down
+    std::map<uint64_t, uint32_t> verify_init;                             // ... and 0xFFFFFFFF * x^(8 * bytes) per unit size seen (the CRC's init, carried to the unit's end)
     PinnedUnits h_units;
     std::vector<uint64_t> h_off;
     // what an enqueue has already put behind its chain (session_*_finish then only synchronises): the read-back of the descriptors;
@@ -342,13 +347,13 @@ private:
     }
 public:
     size_t reserved_bytes() const {
-        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        const DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload, &verify_px, &verify_tab };
         size_t t = 0;
         for (const DevBuf *b : all) t += b->cap;
         return t;
     }
     void release() {
-        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload };
+        DevBuf *all[] = { &units, &gap, &cls, &tok, &hist, &norm, &tt_nb, &tt_find, &state_tab, &tab_sym, &cumul, &blob, &packed, &offsets, &seg, &sym, &flags, &io_px, &io_comp, &io_px2, &io_comp2, &packed2, &pica_tab, &pica_cost, &pica_starts, &wv_a, &wv_b, &wv_tab_enc, &wv_tab_dec, &wsi_planes, &wsi_stats, &wsi_payload, &wsi_recs, &pieces, &crop_stage, &wsi_stage, &wsi_fills, &rgb_planes, &rgb_aux, &rgb_payload, &rgb_payload2, &mic2_files, &mic2_payload, &verify_px, &verify_tab };
         for (DevBuf *b : all) b->release();
         for (DevBuf &b : wsi_pyr) b.release();
         wsi_pyr.clear();
@@ -386,6 +391,15 @@ int session_decode_enqueue(mic_hip_session *s, const uint8_t *d_blobs, const uin
 int session_decode_enqueue_spans(mic_hip_session *s, const uint8_t *d_base, const uint64_t *begins, const uint64_t *ends,
                                  const mic_hip_unit *units, int n, uint16_t *d_pixels_out);
 int session_decode_finish(mic_hip_session *s, int32_t *h_status);
+// Digests and compares (mic_verify.hip).  session_digest_run: res[i].crc32 = the CRC-32 of unit i of d_ref; with d_dec, units whose
+// compare[i] is set (null: all) are compared with their counterparts in d_dec (same px_offset): res[i].mismatches / first_mismatch,
+// 0 / -1 for the others.  res[i].status is left alone.  Complete on return.
+int session_digest_run(mic_hip_session *s, const uint16_t *d_ref, const uint16_t *d_dec, const mic_hip_unit *units, int n,
+                       const uint8_t *compare, mic_hip_verify_result *res);
+// The streams d_base + begins[i] .. ends[i] decoded into the session's scratch and compared with d_ref: res[i] in full.  skip
+// (nullable): units whose skip[i] is not MIC_OK are not decoded -- res[i].status = skip[i], the CRC is still taken.
+int session_verify(mic_hip_session *s, const uint8_t *d_base, const uint64_t *begins, const uint64_t *ends, const mic_hip_unit *units, int n,
+                   const uint16_t *d_ref, const int32_t *skip, mic_hip_verify_result *res);
 size_t unit_ws_bytes(size_t px);
 size_t unit_ws_bytes_tier(size_t px, int tier);
 size_t batch_units_for(size_t px, size_t mult, size_t extra = 0);   // units per sub-batch of the tiered unit codec (mic_api.hip)
