@@ -367,8 +367,10 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
     // (a macro, not a lambda: clang does not capture through asm operands in a generic lambda)
     // DR_ double rounds, LIM_ = 4 * rounds: the stage offset behind which a round neither looks up nor reads (the split instances'
     // chunks are 32 and 16 rounds: LS_CHUNK2_N("16", "128"), LS_CHUNK2_N("8", "64"))
+    // STG_: the stage of the chunk's states (the eight-part instance names one of two by the chunk's parity)
 #define LS_CHUNK2() LS_CHUNK2_N("32", "256")
-#define LS_CHUNK2_N(DR_, LIM_) do { \
+#define LS_CHUNK2_N(DR_, LIM_) LS_CHUNK2_AT(DR_, LIM_, stgb)
+#define LS_CHUNK2_AT(DR_, LIM_, STG_) do { \
         uint32_t e, c, cp, m, hi, pre, at, a0, a1, lo, hh; \
         q -= 32; \
         asm volatile(".set ls_off, 4\n\t" \
@@ -387,7 +389,7 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
                      "s_waitcnt lgkmcnt(0)" \
                      : [st] "+v"(st), [q] "+v"(q), [e] "=&v"(e), [c] "=&v"(c), [cp] "=&v"(cp), [m] "=&v"(m), [hi] "=&v"(hi), [pre] "=&v"(pre), \
                        [at] "=&v"(at), [a0] "=&v"(a0), [a1] "=&v"(a1), [lo] "=&v"(lo), [hh] "=&v"(hh) \
-                     : [C] "v"(C), [mk1] "v"(mk1), [Ck] "v"(mk1 & C), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(stgb), [RW] "n"(LS_RBITS), \
+                     : [C] "v"(C), [mk1] "v"(mk1), [Ck] "v"(mk1 & C), [cb] "v"(cb), [ringb] "v"(ringb), [stg] "v"(STG_), [RW] "n"(LS_RBITS), \
                        [ZBF] "n"(ZB ? 1 : 0) \
                      : "memory", "vcc", "v60", "v61", "v62"); \
         q += 32; \
@@ -600,8 +602,9 @@ __global__ void __launch_bounds__(64 * LsGeom<TL>::WAVES) k_dec_tans_ls(MicUnit 
 // LS_STAMP builds (tools/time_dec.py): shader-clock ticks per phase of the chunk loop, summed over the chunks, into dbg[] of the
 // wave's first unit through ordinary stores -- 0 rounds, 1 ring stores, 2 loads, 3 state stores, 4 hand-over, snapshot and ballot;
 // dbg[5] chunks, dbg[6] parts per stream.  The partner instance (eight parts): the chain wave's 0 rounds, 1 publish, 2 the wait for its
-// partner, 4 as above (3 stays 0: the upkeep is not there), and the partner wave's own period in dbg[8 ..]: 8 waiting for the chunk, 9
-// positions, ring fills and loads, 10 stage, served and state stores, dbg[11] its chunks
+// partner, 4 as above (3 stays 0: the upkeep is not there; a pass has two of each phase and every slot keeps its per-chunk meaning), and
+// the partner wave's own period in dbg[8 ..]: 8 waiting for the chunk, 9 positions, stage, ring fills, served and loads, 10 state stores,
+// dbg[11] its chunks
 #ifdef LS_STAMP
 #define LS_ST_DECL uint64_t stamp[5] = { 0, 0, 0, 0, 0 }, t_prev = __builtin_amdgcn_s_memtime()
 #define LS_ST_OUT(parts_) do { if (lane == 0) { MicUnit &ud = units[unit_i]; for (int i_ = 0; i_ < 5; i_++) ud.dbg[i_] = (uint32_t)(stamp[i_] >> 4); \
@@ -677,9 +680,14 @@ __device__ __forceinline__ void ls_mb_put(uint32_t a, uint32_t v) {
 //   chain wave, behind chunk c:   the parts' positions into half c & 1 of the mailbox, then DONE = c + 1 (chunks run), then a read of
 //                                 SERVED that nothing waits for: the loop test of the next chunk runs in its shadow;
 //   chain wave, in front of c:    SERVED >= c - 1, by one compare on that read; else it polls (counted: MicUnit.partner[2]);
-//   partner, for c = 0, 1, ...:   waits for DONE > c; reads the positions of half c & 1; where a part's position has reached a new block b,
-//                                 puts block b - 2 into the ring from its register queue (and loads a block further down); reads stage
-//                                 half c & 1; SERVED = c + 1; sends the states out with the same two stores per stream as ever.
+//   partner, for c = 0, 1, ...:   waits for DONE > c; reads the positions and the stage of half c & 1; where a part's position has reached a
+//                                 new block b, puts block b - 2 into the ring from its register queue; SERVED = c + 1; then what goes to
+//                                 memory: the queue's loads, and the states with the same two stores per stream as ever.
+// A pass of either loop is two chunks, an even one and an odd one: the halves are immediates and fixed registers, and the chain wave has its
+// wave-uniform exit test in front of the even chunk only.  It may so run one chunk behind the last that any part is on for: nothing is on in
+// it, no snapshot moves, every record keeps its value; the chunk reads zeros below the stream, its states go where a shorter stream's go
+// beside a longer neighbour (behind every token that is read, or nowhere: `fits`, tok's descriptor), and the partner serves it like any other
+// (tests/tans_pairs_model.py).  The hand-over chunk is tested for in front of both chunks of a pass.
 // Deadline (tests/tans_partner_model.py states it and tests/test_tans_partner_cpu.py checks it on the fastest consumers found): chunk c + 2
 // starts in block b or b - 1 when b is the block of the position behind chunk c, and reads no lower than the block under its own, b - 2:
 // the fill for chunk c.  That block takes the slot of b + 2, and chunk c + 1, which may be running, reads b + 1 .. b - 1.  Chunk c + 2 is
@@ -832,12 +840,13 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
 #pragma unroll
     for (int j = 0; j < LS_SPW; j++) scr0[j] = up ? (PARTS > 2 ? (up - 1u) * s_R[j] * 2u : 0u) + lb * 4u : LS_OOB;
     const uint32_t tok0 = up ? LS_OOB : lb * 4u;
-    // one chunk's states of this lane's part of every stream, out of the stage at byte offset `half`, to tok and the scratch regions
-    auto send_states = [&](uint32_t c, uint32_t half) {
-        uint32_t s2[LS_SPW];
+    // (the partner instance) one chunk's states of this lane's part of every stream: out of the stage at byte offset `half` ...
+    auto take_stage = [&](uint32_t half, uint32_t (&s2)[LS_SPW]) {
 #pragma unroll
         for (int j = 0; j < LS_SPW; j++) s2[j] = *(ls_l32)(uintptr_t)((wv * LS_SPW + (uint32_t)j) * SB + up * PB + G::STAGE + half + lb * 4);
-        if constexpr (G::PARTNER) { if (lane == 0) ls_mb_put(mb + G::MB_SERVED, c + 1u); }   // behind the ring stores and the stage reads: the LDS keeps a wave's order
+    };
+    // ... and to tok and the scratch regions
+    auto send_states = [&](uint32_t c, const uint32_t (&s2)[LS_SPW]) {
         const uint32_t off = c * 2u * CH;                                   // (part 0 runs on into a descriptor that ends at its last whole chunk)
         // eight parts: a region starts at step W, and the chunks in front of it are not stored (both terms below are wave-uniform)
         const uint32_t ch0 = G::SKIP_W ? Wc : 0u, soff = (c - ch0) * 2u * CH;
@@ -850,12 +859,22 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
     };
     if constexpr (G::PARTNER) if (partner) {
         // ---- the partner wave: lanes BLK p .. BLK p + BLK - 1 serve part p of each of the chain wave's streams ----
-        // Two blocks per part wait in registers: pfa = block pfb, what the ring takes next, and pfn = the one under it, loaded a chunk
-        // ago at the least.  The loop's loads are asm: the value is not there when the statement is done, and the one wait that covers
-        // them, at the top of a chunk's service, names what may still be out behind them (vmcnt counts in order)
-        uint32_t pfa[LS_SPW], pfn[LS_SPW], touch = 0;
+        // Two blocks per part wait in registers, block pfb, what the ring takes next, and the one under it, each in the register of its
+        // parity: pfe the even one, pfo the odd one.  A block enters the queue when the part reaches a new block and enters the ring two
+        // such advances later, so its load has two chunks at the least to arrive, and no register is moved when the queue moves on: a
+        // move would have to wait for the newest load.  Whether a part advances in a chunk is the stream's business (a chunk takes 0 to
+        // 6.5 of a block's 8 dwords), so the roles are picked by a select on the block's parity and cannot be fixed per half of a pass.
+        // Every chunk loads both blocks of the queue again, each lane its own two: a block that is there already arrives as the same
+        // dwords, what is read meanwhile is right, and every load instruction has all its lanes, so the count below holds whatever the
+        // parts do.  The loop's loads are asm: the value is not there when the statement is done, and the one wait that covers them, at
+        // the top of a chunk's service, names what may still be out behind them (vmcnt counts in order)
+        uint32_t pfe[LS_SPW], pfo[LS_SPW], touch = 0;
 #pragma unroll
-        for (int j = 0; j < LS_SPW; j++) { pfa[j] = load_blk(j, pfb[j]); pfn[j] = load_blk(j, pfb[j] - 1); }
+        for (int j = 0; j < LS_SPW; j++) {
+            const uint32_t l0 = load_blk(j, pfb[j]), l1 = load_blk(j, pfb[j] - 1);
+            const bool odd = (pfb[j] & 1) != 0;
+            pfe[j] = odd ? l1 : l0; pfo[j] = odd ? l0 : l1;
+        }
         const uint32_t polls = G::PARTNER_POLLS + min(wait_bound, 1u << 30);
         uint32_t c = 0, fin = 0;
         bool bail = false;
@@ -865,7 +884,9 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
 #else
 #define LS_PT(i) do { } while (0)
 #endif
-        for (;; c++) {
+        // chunk c, of parity `half` (a literal at both calls: the mailbox half and the stage half are immediates) -> false: the chain
+        // wave has left its loop and nothing is outstanding, or one side has given up
+        auto serve = [&](const uint32_t half) __attribute__((always_inline)) -> bool {
             for (uint32_t tries = 0;; tries++) {                            // chunk c: run and published?
                 const uint32_t dn = (uint32_t)__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_DONE));
                 fin = dn & G::MB_FIN;
@@ -874,24 +895,30 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
                 if (__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_BAIL)) != 0 || tries >= polls) { bail = true; break; }
                 __builtin_amdgcn_s_sleep(2);
             }
-            if (fin || bail) break;
+            if (fin || bail) return false;
             LS_PT(0);
-            const uint32_t half = c & 1u;
             int32_t qp[LS_SPW];
 #pragma unroll
             for (int j = 0; j < LS_SPW; j++) qp[j] = (int32_t)ls_mb_get(mb + half * G::MB_HALF + ((uint32_t)j * (uint32_t)PARTS + up) * 4u);
-            asm volatile("s_waitcnt vmcnt(9)" ::: "memory");                // the loads of the chunk before: not its three touches, not its six stores
+            uint32_t s2[LS_SPW];
+            take_stage(half * G::STAGE_BYTES, s2);                          // (issued here: they arrive while the rings are filled)
+            // the loads of two chunks ago and everything older: a chunk is six loads, three touches and six stores, in this order, so what
+            // may stay out is the chunk before (15) and the touches and stores of the one before that (9)
+            asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
 #pragma unroll
             for (int j = 0; j < LS_SPW; j++) {
                 const bool adv = ((qp[j] >> 5) >> G::BLK_SHIFT) - LS_DEPTH <= pfb[j];   // the part has reached a new block: one at most per chunk
-                if (adv) store_blk(j, pfb[j], pfa[j]);
-                pfa[j] = adv ? pfn[j] : pfa[j];
+                if (adv) store_blk(j, pfb[j], (pfb[j] & 1) ? pfo[j] : pfe[j]);
                 pfb[j] -= adv ? 1 : 0;
             }
+            // SERVED, as soon as the chain wave may rely on it: behind the ring stores and the stage reads (the LDS keeps a wave's order),
+            // in front of everything that goes to memory -- the chain wave looks at it once, right behind its next chunk
+            if (lane == 0) ls_mb_put(mb + G::MB_SERVED, c + 1u);
 #pragma unroll
-            for (int j = 0; j < LS_SPW; j++) {                              // (the same block again for a part that stayed)
-                const int32_t off = ((pfb[j] - 1) * (int32_t)BLK + (int32_t)lb) * 4;
-                asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(pfn[j]) : [o] "v"(off), [r] "s"(rs_in[j]) : "memory");
+            for (int j = 0; j < LS_SPW; j++) {                              // blocks pfb and pfb - 1: the even one of the two, and the odd one
+                const int32_t off_e = ((pfb[j] & ~1) * (int32_t)BLK + (int32_t)lb) * 4, off_o = (((pfb[j] - 1) | 1) * (int32_t)BLK + (int32_t)lb) * 4;
+                asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(pfe[j]) : [o] "v"(off_e), [r] "s"(rs_in[j]) : "memory");
+                asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(pfo[j]) : [o] "v"(off_o), [r] "s"(rs_in[j]) : "memory");
             }
             // ... and a touch of the cache line under it (four blocks), behind the loads so that the wait above leaves it out: a block's
             // own load, a few chunks on, then finds the line in the L2 -- from HBM it took longer than a chunk, and the partner set the pace
@@ -901,9 +928,14 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
                 asm volatile("buffer_load_dword %[v], %[o], %[r], 0 offen" : [v] "+v"(touch) : [o] "v"(off), [r] "s"(rs_in[j]) : "memory");
             }
             LS_PT(1);
-            send_states(c, half * G::STAGE_BYTES);
+            send_states(c, s2);
             LS_PT(2);
-        }
+            c++;
+            return true;
+        };
+        // a pass is two chunks, as the chain wave's: an even one out of the first halves, an odd one out of the second; FIN or BAIL ends
+        // the loop in front of either
+        while (serve(0u) && serve(1u)) { }
         if (bail) { if (lane == 0) ls_mb_put(mb + G::MB_BAIL, 1u); }
         // chunks served, per unit: what the chain wave says the unit's own parts ran (MB_OWN, in front of MB_FIN), or what was served of it
         if (lane < (uint32_t)LS_SPW && slot0 + (int)lane < n_cls) {
@@ -921,60 +953,83 @@ __global__ void __launch_bounds__(64 * LsParts<PARTS>::GROUP_WAVES) k_dec_tans_l
                                                                             // position after Wc chunks; the last part: bits left
     int32_t sn_q = q; uint32_t sn_st = st, sn_ch = 0;                       // snapshot: the last chunk start above qlim
     uint32_t ch = 0;
-    // the partner instance: the lane's word of the mailbox half and its stage half of the chunk to come, and their sums over the halves
-    [[maybe_unused]] uint32_t mb_pos = mb + (g * (uint32_t)PARTS + part) * 4u, mb_sv = 0, not_ready = 0;
-    [[maybe_unused]] const uint32_t mb_pos_sum = 2u * mb_pos + G::MB_HALF, stg_sum = 2u * stgb + G::STAGE_BYTES;
+    // the partner instance: the lane's word of mailbox half 0, and the stage of the odd chunks (the halves of a chunk are immediates
+    // and fixed registers: a pass of the loop is an even chunk and an odd one)
+    [[maybe_unused]] const uint32_t mb_pos = mb + (g * (uint32_t)PARTS + part) * 4u, stgb1 = stgb + G::STAGE_BYTES;
+    [[maybe_unused]] uint32_t mb_sv = 0, not_ready = 0;
     [[maybe_unused]] bool stalled = false;
     LS_ST_DECL;
-    for (;; ch++) {
-        if (ch == Wc) {                                                     // (uniform, once)
-            const int32_t qn = __builtin_amdgcn_ds_bpermute((int)(nl << 2), q);
-            m_ab = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nl << 2), (int)st) |
-                   ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((nl | 1u) << 2), (int)st) << 16);
-            qlim = last_part ? qz : qn;
-            handed = true;
+    // in front of a chunk, per lane: the hand-over (uniform, once), and the snapshot -- the last chunk start above the limit
+#define LS_PARTS_FRONT() \
+        if (ch == Wc) {                                                     /* (uniform, once) */ \
+            const int32_t qn = __builtin_amdgcn_ds_bpermute((int)(nl << 2), q); \
+            m_ab = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nl << 2), (int)st) | \
+                   ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((nl | 1u) << 2), (int)st) << 16); \
+            qlim = last_part ? qz : qn; \
+            handed = true; \
+        } \
+        const bool on = own_chunk(ch) & (q > qlim);                         /* (selects, no branch) */ \
+        sn_q = on ? q : sn_q; sn_st = on ? st : sn_st; sn_ch = on ? ch : sn_ch; \
+        asm volatile("" : "+v"(sn_q), "+v"(sn_st), "+v"(sn_ch))             /* (taken here: sunk behind the chunk, the selects keep the old q and st alive across it) */
+    // The partner instance's chunk `ch` of parity HALF_ (a literal: stage, mailbox half and their offsets are immediates).  In front: SERVED
+    // as it was behind the last chunk (the read was issued there; everything from there to here ran in its shadow); a partner that is
+    // not ready is polled for (the slow path), and a bound that runs out leaves the loop (`break`: the macro stands in the loop's own
+    // body).  Behind: the positions (lanes of role 0 of the 24 parts), then DONE, then the read of SERVED for the next chunk's test
+#define LS_PARTNER_CHUNK(HALF_) \
+        { \
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mb_sv) :: "memory"); \
+            uint32_t sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)mb_sv); \
+            if (__builtin_expect(sv + 1u < ch, 0)) { \
+                not_ready++; \
+                for (uint32_t tries = 0;; tries++) { \
+                    sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_SERVED)); \
+                    if (sv + 1u >= ch) break; \
+                    if (__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_BAIL)) != 0 || tries + 1u >= wait_bound) { stalled = true; break; } \
+                    __builtin_amdgcn_s_sleep(1); \
+                } \
+                if (stalled) break; \
+            } \
+            LS_T(2); \
+            if constexpr ((HALF_) != 0) LS_CHUNK2_AT("4", "32", stgb1); else LS_CHUNK2_AT("4", "32", stgb); \
+            LS_T(0); \
+            const uint64_t em_pos = 0x0000555555555555ull, em_one = 1ull; \
+            const uint32_t dn = ch + 1u; \
+            asm volatile("s_mov_b64 exec, %[ep]\n\t" \
+                         "ds_write_b32 %[pa], %[q] offset:%[HO]\n\t" \
+                         "s_mov_b64 exec, %[e1]\n\t" \
+                         "ds_write_b32 %[da], %[dn]\n\t" \
+                         "ds_read_b32 %[sv], %[da] offset:%[SO]\n\t" \
+                         "s_mov_b64 exec, -1" \
+                         : [sv] "=&v"(mb_sv) \
+                         : [pa] "v"(mb_pos), [q] "v"(q), [da] "v"(mb + G::MB_DONE), [dn] "v"(dn), [ep] "s"(em_pos), [e1] "s"(em_one), \
+                           [SO] "n"(G::MB_SERVED - G::MB_DONE), [HO] "n"((HALF_) * G::MB_HALF) \
+                         : "memory"); \
+            LS_T(1); \
         }
-        const bool on = own_chunk(ch) & (q > qlim);                         // (selects, no branch)
-        sn_q = on ? q : sn_q; sn_st = on ? st : sn_st; sn_ch = on ? ch : sn_ch;
-        asm volatile("" : "+v"(sn_q), "+v"(sn_st), "+v"(sn_ch));            // (taken here: sunk behind the chunk, the selects keep the old q and st alive across it)
-        if (ch >= ch_cap || !__any(on & real & have)) break;                // one wave-uniform test per chunk
-        LS_T(4);
-        if constexpr (G::PARTNER) {
-            // SERVED as it was behind the last chunk (the read was issued there; everything from there to here ran in its shadow)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mb_sv) :: "memory");
-            uint32_t sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)mb_sv);
-            if (__builtin_expect(sv + 1u < ch, 0)) {                        // the partner is not ready: poll (the slow path)
-                not_ready++;
-                for (uint32_t tries = 0;; tries++) {
-                    sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_SERVED));
-                    if (sv + 1u >= ch) break;
-                    if (__builtin_amdgcn_readfirstlane((int)ls_mb_get(mb + G::MB_BAIL)) != 0 || tries + 1u >= wait_bound) { stalled = true; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                if (stalled) break;
-            }
-            LS_T(2);
-            LS_CHUNK2_N("4", "32");
-            LS_T(0);
-            // publish: the positions (lanes of role 0 of the 24 parts), then DONE, then the read of SERVED for the next chunk's test
+    if constexpr (G::PARTNER) {
+        // A pass is two chunks, an even one and an odd one, and the wave-uniform exit test stands in front of the even one only: the
+        // wave runs at most one chunk more than its last part that is on needs.  In front of that chunk no lane is on (on only ever
+        // goes off: q falls, the limit rises once, own_chunk ends), so the snapshots, and with them every record, keep their values;
+        // its states go where a shorter stream's go beside a longer neighbour -- behind the tokens anything reads, or nowhere (`fits`,
+        // tok's descriptor) --, its ring reads below the stream are zeros, and the partner serves it like any other.  ch <= ch_cap + 1
+        for (;;) {
             {
-                const uint64_t em_pos = 0x0000555555555555ull, em_one = 1ull;
-                const uint32_t dn = ch + 1u;
-                asm volatile("s_mov_b64 exec, %[ep]\n\t"
-                             "ds_write_b32 %[pa], %[q]\n\t"
-                             "s_mov_b64 exec, %[e1]\n\t"
-                             "ds_write_b32 %[da], %[dn]\n\t"
-                             "ds_read_b32 %[sv], %[da] offset:%[SO]\n\t"
-                             "s_mov_b64 exec, -1"
-                             : [sv] "=&v"(mb_sv)
-                             : [pa] "v"(mb_pos), [q] "v"(q), [da] "v"(mb + G::MB_DONE), [dn] "v"(dn), [ep] "s"(em_pos), [e1] "s"(em_one),
-                               [SO] "n"(G::MB_SERVED - G::MB_DONE)
-                             : "memory");
-                mb_pos = mb_pos_sum - mb_pos;                               // the other half
-                stgb = stg_sum - stgb;
+                LS_PARTS_FRONT();
+                if (ch >= ch_cap || !__any(on & real & have)) break;        // one wave-uniform test per pass
             }
-            LS_T(1);
-        } else {
+            LS_T(4);
+            LS_PARTNER_CHUNK(0)
+            ch++;
+            { LS_PARTS_FRONT(); }
+            LS_T(4);
+            LS_PARTNER_CHUNK(1)
+            ch++;
+        }
+    } else {
+        for (;; ch++) {
+            LS_PARTS_FRONT();
+            if (ch >= ch_cap || !__any(on & real & have)) break;            // one wave-uniform test per chunk
+            LS_T(4);
             if constexpr (PARTS == 2) LS_CHUNK2_N("16", "128"); else LS_CHUNK2_N("8", "64");
             LS_T(0);
             // upkeep, in the order of k_dec_tans_ls: consumers of last chunk's prefetch, then the loads, then the stores

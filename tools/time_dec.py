@@ -52,7 +52,7 @@ for i in (0, 9, 900):
         p = [out[16 + 8 + k] * 16 for k in range(3)]
         print("unit", i, "%d parts, chain wave, cycles per chunk: rounds %.0f  publish %.0f  handshake wait %.0f  loop test %.0f  sum %.0f  (chunks %d)"
               % (out[16 + 6], d[0] / n, d[1] / n, d[2] / n, d[4] / n, sum(d) / n, n))
-        print("unit", i, "         partner wave, cycles per chunk: waiting for the chunk %.0f  positions, ring fills, loads %.0f  stage, served, state stores %.0f  "
+        print("unit", i, "         partner wave, cycles per chunk: waiting for the chunk %.0f  positions, stage, ring fills, served, loads %.0f  state stores %.0f  "
               "busy %.0f of %.0f  (chunks %d)" % (p[0] / m, p[1] / m, p[2] / m, (p[1] + p[2]) / m, sum(p) / m, m))
     elif out[16 + 6]:                                                   # a split instance's stamps: five phases, chunks, parts per stream
         n = out[16 + 5]
