@@ -895,6 +895,13 @@ int mic_hip_debug_dec_stage(mic_hip_session *s, int i, uint32_t *out) try {
     *out = s->h_units[(size_t)i].dec_stage;
     return MIC_OK;
 } MIC_ABI_CATCH
+// debug probe (not in the public header): which forks of the tokens-to-pixels stage unit i took (MicUnit.px_paths: MIC_PXP_* bits,
+// mic_dev.h -- k_dec_rows_tok's of a unit it made the pixels of, else k_dec_pixels_wg's) after a decode's *_finish
+int mic_hip_debug_px_paths(mic_hip_session *s, int i, uint32_t *out) try {
+    if (!s || !out || i < 0 || i >= s->n_last) return MIC_ERR_ARGS;
+    *out = s->h_units[(size_t)i].px_paths;
+    return MIC_OK;
+} MIC_ABI_CATCH
 // debug probe (not in the public header): mic_dec_cls as this build compiled it, gates and all (tests/test_decode_classes_cpu.py
 // holds its own restatement against it, value by value)
 int mic_hip_debug_dec_cls(uint32_t flavour, uint32_t table_log, uint32_t zero_bits) { return mic_dec_cls(flavour, table_log, zero_bits); }

@@ -50,18 +50,22 @@ __device__ __noinline__ void dec_tans_serial_body(MicUnit &u) {
     if (u.flavour == 1) {
         // decompress(), fsedecompressu16.go:267-377: run until the bits are used up and the
         // current state needs more; a non-zero final state contributes one more symbol.
+        // (a one-state stream does not say how many tokens it holds: the token slab is found full only here.  Tier 1's holds what a
+        // well-formed frame of few escapes needs; a frame of more tokens -- two per escaped pixel, or one of many short segments -- runs
+        // again in tier 2 like a stream of the other flavours whose count says so, mic_tables.hip)
+        const int32_t full = u.tier == 1 ? MICD_INT_GROW : MICD_ERR_CORRUPT;
         uint32_t state = br.get(tl);
         uint32_t n = 0;
         for (;;) {
             uint32_t e = dt[state];
             uint32_t nb = e >> 16;
             if (br.cursor == 0 && nb > 0) {
-                if (state != 0) { if (n >= u.tok_cap) { u.status = MICD_ERR_CORRUPT; return; } out[n++] = ds[state]; }
+                if (state != 0) { if (n >= u.tok_cap) { u.status = full; return; } out[n++] = ds[state]; }
                 break;
             }
             uint32_t low = br.get(nb);
             if (br.over) { u.status = MICD_ERR_CORRUPT; return; }
-            if (n >= u.tok_cap) { u.status = MICD_ERR_CORRUPT; return; }
+            if (n >= u.tok_cap) { u.status = full; return; }
             out[n++] = ds[state];
             state = (e & 0xFFFF) + low;
         }

@@ -276,12 +276,13 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
 #define RF_ROW(i) do { } while (0)
 #endif
     uint32_t spos = 1;                                                   // symbol 0 is the max value, not a pixel
+    uint32_t paths = 0;                                                  // MIC_PXP_ROW_*: the forks the unit's rows took (one value per wave: a scalar register)
     if (spos + (uint32_t)W > nsym) return;                               // tokens ran out (Go: panic): the other path's error
     int ar = issue(spos, (uint32_t)W);                                   // row 0
     if (ar == 0) return;
     for (int y = 0; y < H; y++) {
-        if (ar > 0) land();
-        else { RF_ROW(1); if (!assemble(spos, 0u, (uint32_t)W)) return; } // (more than eight pieces: piece by piece)
+        if (ar > 0) { land(); paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_ROW_GATHER); }
+        else { RF_ROW(1); paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_ROW_PIECEWISE); if (!assemble(spos, 0u, (uint32_t)W)) return; } // (more than eight pieces: piece by piece)
         // What lies behind the row's end in the row buffer (the next row's first symbols, or the results staged for the last store) is
         // computed along by the last lanes: there it must be the symbol that changes nothing, or a stale result would look like a
         // wrap-around to the predictor.  Fewer than 256 positions -- written here, after the row (LDS operations of a wave are in
@@ -309,7 +310,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
         const bool esc_row = __any(hasd != 0u);
         RF_T(4);
         if (esc_row) {
-            RF_ROW(2);
+            RF_ROW(2); paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_ROW_ESCAPE);
             // ---- escapes in this row: markers, pixel numbering, raw bits (k_dec_pixels_wg's scan, one wave) ----
             const uint32_t have = min((uint32_t)W + RF_SLACK, nsym - spos);
             __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -380,7 +381,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
         bool fine;
         if (y == 0) { RP::slow_row(tp, es, raw, true, thr, lane, g.nl); fine = true; }
         else fine = RP::fast_row(tp, es, raw, thr, lane, nv);
-        if (!fine) { RP::redo_row(tp, es, raw, thr, lane, g, px, y, W, npx); RF_ROW(3); }   // the wrap-around fired somewhere
+        if (!fine) { RP::redo_row(tp, es, raw, thr, lane, g, px, y, W, npx); RF_ROW(3); paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_ROW_REDO); }   // the wrap-around fired somewhere
         RF_T(2);
         put(y);
         RF_T(3);
@@ -390,7 +391,7 @@ __global__ void __launch_bounds__(256, 3) k_dec_rows_tok(MicUnit *units, int n_u
 #ifdef RF_STATS
     if (lane == 0) { for (int i = 0; i < 4; i++) { u.dbg[i] = st_rows[i]; u.dbg[4 + i] = (uint32_t)(st_t[i] >> 4); } u.dbg[1] = (uint32_t)(st_t[4] >> 4); u.dbg[2] = (uint32_t)(st_t[5] >> 4); }
 #endif
-    if (lane == 0) { u.dec_thr = thr; u.dec_stage = MIC_STAGE_PIXELS; }  // pixels done: the two-kernel path skips this unit
+    if (lane == 0) { u.dec_thr = thr; u.px_paths = paths; u.dec_stage = MIC_STAGE_PIXELS; }  // pixels done: the two-kernel path skips this unit
 }
 
 void mic_launch_decode_fused(MicUnit *d_units, int n, hipStream_t stream, uint32_t kmask) {

@@ -139,6 +139,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
         };
         // symbols of the NEXT tile, fetched while this one is scanned (valid when the table covered that tile)
         bool pre_cov = false; uint32_t p8[4] = { 0u, 0u, 0u, 0u }; uint32_t pre_bad = 0, pre_j = 0;
+        uint32_t paths = 0;              // MIC_PXP_*: the forks taken, every one a value of the whole group (a scalar register)
         MIC_STAMP_BEGIN();
         for (uint32_t base = 0; base < nsym && carry_px < npx; base += PX_T) {
             const uint32_t tile_end = min(base + PX_T, nsym);
@@ -154,6 +155,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             uint32_t my_seg = s_lo;                                      // segment this thread found (absolute index; hint for the next tile)
             uint32_t badm = 0;                                           // this thread's symbols behind the last token (fetch8)
             if (pre_cov) {
+                paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_PREFETCH);   // (inside the branch: named in front of it, the bit costs the kernel 20 bytes of scratch)
                 if (!got) {
 #pragma unroll
                     for (int k = 0; k < 4; k++) w8[k] = p8[k];
@@ -181,6 +183,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
                         my_seg = r0 + j; got = true;
                     }
                     if (!(cover_end < tile_end)) break;
+                    paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)MIC_PXP_TABLE_RELOAD);
                 }
             }
             {   // prefetch for the next tile, if the table in LDS already covers it
@@ -212,6 +215,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             // (A symbol behind the tokens that a pixel wants raises s_misc[3], read behind the last tile's barrier; zeros stand in till then.)
             const bool plain = !__syncthreads_or((int)(dmask != 0)) && carry_state == 0;
             s_lo = s_misc[5 + par];
+            paths |= (uint32_t)__builtin_amdgcn_readfirstlane((int)(plain ? MIC_PXP_PLAIN_TILE : carry_state ? MIC_PXP_SCAN_TILE | MIC_PXP_SCAN_ENTRY1 : MIC_PXP_SCAN_TILE));
             if (plain) {
                 const uint32_t z = (base == 0) ? 1u : 0u;                // symbol 0 is not a pixel
                 const uint32_t cnt_all = tile_end - base - z;
@@ -282,6 +286,7 @@ __global__ void __launch_bounds__(PX_THREADS, 8) k_dec_pixels_wg(MicUnit *units)
             __syncthreads();
             MIC_STAMP_AT(u, 3);
         }
+        if (tid == 0) u.px_paths = paths;
         if (carry_px < npx) { if (tid == 0) u.status = MICD_ERR_CORRUPT; return; }   // tokens ran out (Go: panic)
     }
     __threadfence_block();

@@ -98,6 +98,16 @@ struct MicSplitCfg {
 #define MIC_TBI_STD             1u           // the standard instance: one work-group per CU, any alphabet, rANS, HBM scratch
 #define MIC_TBI_C4K             2u           // the compact instance: tANS, at most 4096 symbols, tableLog <= 13; two work-groups per CU
 
+// MicUnit.px_paths: which forks of the tokens-to-pixels stage a decode unit took (tests/test_gpu_px_seams.py)
+#define MIC_PXP_PLAIN_TILE      (1u << 0)    // k_dec_pixels_wg: a tile without a delimiter, entered with marker state 0: no scan
+#define MIC_PXP_SCAN_TILE       (1u << 1)    // ... a tile that took the marker scan
+#define MIC_PXP_SCAN_ENTRY1     (1u << 2)    // ... and was entered with marker state 1 (its first symbol is the payload of the tile before's last)
+#define MIC_PXP_TABLE_RELOAD    (1u << 3)    // ... the LDS segment table did not reach a tile's end: a second round of the r0 loop inside one tile
+#define MIC_PXP_PREFETCH        (1u << 4)    // ... a tile took the symbols fetched while the tile before was scanned
+#define MIC_PXP_ROW_GATHER      (1u << 8)    // k_dec_rows_tok: a row of up to eight pieces, gathered
+#define MIC_PXP_ROW_PIECEWISE   (1u << 9)    // ... a row of nine pieces or more, copied piece by piece
+#define MIC_PXP_ROW_ESCAPE      (1u << 10)   // ... a row with a delimiter: the marker scan over the row and its slack
+#define MIC_PXP_ROW_REDO        (1u << 11)   // ... a row the 16-bit wrap-around fired in: done again lane by lane
 // MicUnit.dec_stage: a decode unit's place in the chain behind the tANS kernels (DESIGN.md section 4 has the table).  Device code only;
 // every enqueue starts at NONE (lay_out: MicUnit{}).  The chain's other two hand-off signals: ntok != 0 ("decoded"), and wv_slow.
 enum MicStage : uint32_t {
@@ -205,6 +215,10 @@ struct MicUnit {
                               // wave), 1 chunks of the unit the partner served, 2 chunks the chain wave found its partner not ready for (the
                               // wave's count), 3 stalled (MIC_SPLIT_STALLED; kept when the four-part instance then takes the unit).  Read by
                               // mic_hip_debug_partner, predicted by tests/tans_partner_model.py.  Cleared with the other results
+    uint32_t px_paths;        // decode: which forks the tokens-to-pixels kernel that made the unit's symbols or pixels took (MIC_PXP_* above): thread 0
+                              // of k_dec_pixels_wg writes it once behind the tile loop, lane 0 of k_dec_rows_tok next to dec_stage (a unit it
+                              // declines keeps the zero, and k_dec_pixels_wg's bits follow).  Read by mic_hip_debug_px_paths, predicted by
+                              // tests/px_seam_streams.py.  Cleared with the other results
 };
 // a prefix unit: the tANS chain stopped at the ceiling (tANS yields symbols in forward order, so the ntok it decoded are exact)
 __host__ __device__ inline bool mic_is_prefix(const MicUnit &u) { return u.sym_limit != 0 && u.ntok < u.count; }
