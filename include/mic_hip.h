@@ -1291,6 +1291,49 @@ int mic_hip_session_tile_cache_probe(mic_hip_session *s, const uint64_t *tiles, 
 int mic_hip_tile_cache_plan(uint64_t nslots, const uint64_t *keys, const uint32_t *call_len, int ncalls,
                             uint8_t *outcome, uint64_t *evictions);
 
+/* ---- MIC2: a cache of reconstructed frames in device memory -------------------------------------- */
+/* A 3-D sampler returns to the same volumes for a whole epoch, and every crop call of a reader entropy-decodes every frame its
+ * crops overlap -- for a temporal file every frame from 0 up to the last one a crop needs.  A frame cache is the tile cache above
+ * with slots of one frame each: width x height u16 samples, padded to a multiple of 256 bytes
+ * (mic_hip_frame_cache_slot_bytes).  mic_hip_frame_cache_create returns the same object type, so _clear, _get_stats, _destroy,
+ * mic_hip_tile_cache_plan and mic_hip_tile_cache_stats serve it unchanged; its limits are the crop doors' (sides > 0, at most
+ * 2^28 pixels), nslots = 0 keeps nothing, and no device is needed before the first call that uses it.
+ *
+ * It serves mic_hip_mic2_reader_read_crops{,_as} and mic_hip_mic2_readers_read_crops{,_as}: readers of one call may share a cache
+ * or hold different ones, and a reader without one is decoded inside the same call and keeps nothing.  The host-memory doors
+ * (mic_hip_mic2_read_crops, _multi_read_crops) and the session doors keep no identity between calls and never use a cache; a
+ * call none of whose readers has a cache runs the code it ran before.
+ *
+ * A slot always holds the RECONSTRUCTED frame, for independent and temporal files alike; the key is (owner, frame), each reader
+ * an owner of its own.  A call's keys are the frames some crop overlaps, ascending, reader after reader in the order of the
+ * readers' array (a reader listed twice once) -- for a temporal file the named frames themselves, not 0 .. last.  The policy
+ * is the tile cache's.  Independent files: only misses and bypassed frames are fetched through the callback and decoded.
+ * Temporal files: a resident frame is a key frame.  For a named frame f that is not a hit the anchor is the largest frame a < f
+ * resident for this owner once the call is planned -- a hit, an earlier miss of this call, or an entry no crop named -- and only
+ * the residual streams of frames a + 1 .. f are fetched and decoded (an interval several named frames share, once); with no
+ * resident frame below f the chain starts at frame 0's spatial stream.  Frames in between that no crop names are summed through
+ * and not stored.  The crops are gathered from whole frames, so a typed tensor needs no staging.
+ *
+ * Failure.  A frame whose decode reports a status is never resident, nor is any frame whose chain passes a failed residual
+ * (they count as bypassed); crops that depend on one get its code and failed_frame = the failing frame, as without a cache.  A
+ * call that returns an error (a failing callback, an allocation) leaves entries, stamps and counters as they were.
+ *
+ * Stats with a cache in the call: frames_decoded = the streams this call entropy-decoded; slabs = decode chains run, 0 for a
+ * call that only hit. */
+int mic_hip_frame_cache_slot_bytes(int width, int height, uint64_t *bytes);
+int mic_hip_frame_cache_create(int width, int height, uint64_t nslots, mic_hip_tile_cache **c);
+/* c = NULL detaches and drops the reader's entries; a cache whose format is not (the file's width, height, 1 channel, 16 bits):
+ * MIC_ERR_ARGS; the cache the reader already has: nothing happens.  mic_hip_mic2_reader_close detaches. */
+int mic_hip_mic2_reader_set_cache(mic_hip_mic2_reader *r, mic_hip_tile_cache *c);
+/* resident[i] = 1 when frame frames[i] of this reader is resident, else 0; changes no state */
+int mic_hip_mic2_reader_cache_probe(mic_hip_mic2_reader *r, const uint32_t *frames, size_t n, uint8_t *resident);
+/* The reader doors run on a default session, which has no handle to time.  enabled != 0: every mic_hip_mic2_reader_read_crops{,_as}
+ * of this reader then times its kernels as mic_hip_session_set_timing(s, 2) does on the session it runs on, summed over the call's
+ * launch chains, and _last_timings returns the last call's entries as mic_hip_session_last_timings does (names[i] / ms[i], the
+ * number written).  The frame kernel of a cached temporal call is the entry k_mic2_accumulate_frames. */
+int mic_hip_mic2_reader_set_timing(mic_hip_mic2_reader *r, int enabled);
+int mic_hip_mic2_reader_last_timings(mic_hip_mic2_reader *r, const char **names, float *ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,6 +296,8 @@ ABI_SYMBOLS = [
     "mic_hip_tile_cache_slot_bytes", "mic_hip_tile_cache_create", "mic_hip_tile_cache_clear", "mic_hip_tile_cache_get_stats",
     "mic_hip_tile_cache_destroy", "mic_hip_tile_cache_plan",
     "mic_hip_wsi_reader_set_cache", "mic_hip_wsi_reader_cache_probe", "mic_hip_session_set_tile_cache", "mic_hip_session_tile_cache_probe",
+    "mic_hip_frame_cache_slot_bytes", "mic_hip_frame_cache_create", "mic_hip_mic2_reader_set_cache", "mic_hip_mic2_reader_cache_probe",
+    "mic_hip_mic2_reader_set_timing", "mic_hip_mic2_reader_last_timings",
     "mic_hip_crc32_combine", "mic_hip_compress_batch_verified", "mic_hip_pics_compress_batch_verified",
     "mic_hip_decompress_batch_crc", "mic_hip_pics_decompress_batch_crc",
     "mic_hip_session_digest", "mic_hip_session_verify", "mic_hip_session_encode_verified",
@@ -549,6 +551,12 @@ def lib() -> C.CDLL:
     L.mic_hip_tile_cache_slot_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_uint64)]
     L.mic_hip_tile_cache_create.argtypes = [C.c_int] * 4 + [C.c_uint64, C.POINTER(C.c_void_p)]
     L.mic_hip_tile_cache_clear.argtypes = [C.c_void_p]
+    L.mic_hip_frame_cache_slot_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.mic_hip_frame_cache_create.argtypes = [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mic_hip_mic2_reader_set_cache.argtypes = [C.c_void_p, C.c_void_p]
+    L.mic_hip_mic2_reader_cache_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.mic_hip_mic2_reader_set_timing.argtypes = [C.c_void_p, C.c_int]
+    L.mic_hip_mic2_reader_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.mic_hip_tile_cache_get_stats.argtypes = [C.c_void_p, C.POINTER(TileCacheStats)]
     L.mic_hip_tile_cache_destroy.argtypes = [C.c_void_p]
     L.mic_hip_wsi_reader_set_cache.argtypes = [C.c_void_p, C.c_void_p]
@@ -1956,8 +1964,31 @@ class TileCache:
             pass
 
 
-def _cache_probe(call, tiles) -> np.ndarray:
-    t = np.ascontiguousarray(np.asarray(tiles, dtype=np.uint64).reshape(-1))
+def frame_cache_slot_bytes(width: int, height: int) -> int:
+    """mic_hip_frame_cache_slot_bytes: device bytes of one slot of a FrameCache for frames of width x height (a multiple of 256).
+    No device."""
+    nb = C.c_uint64(0)
+    rc = lib().mic_hip_frame_cache_slot_bytes(width, height, C.byref(nb))
+    if rc:
+        _raise(rc, "frame_cache_slot_bytes")
+    return nb.value
+
+
+class FrameCache(TileCache):
+    """mic_hip_frame_cache_create: reconstructed MIC2 frames of width x height kept in device memory, `slots` of them, for readers
+    of files of that frame size (Mic2Reader.set_cache).  A crop call of a reader with a cache decodes only the frames that are
+    not resident; for a temporal file a resident frame is a key frame, and only the residuals behind the nearest one below a
+    wanted frame are decoded.  The same object as a TileCache: stats, clear and close are its."""
+
+    def __init__(self, width: int, height: int, slots: int = 0):
+        self._h = C.c_void_p()
+        rc = lib().mic_hip_frame_cache_create(width, height, int(slots), C.byref(self._h))
+        if rc:
+            _raise(rc, "FrameCache")
+
+
+def _cache_probe(call, tiles, dtype=np.uint64) -> np.ndarray:
+    t = np.ascontiguousarray(np.asarray(tiles, dtype=dtype).reshape(-1))
     res = np.zeros(max(len(t), 1), dtype=np.uint8)
     rc = call(t.ctypes.data, len(t), res.ctypes.data)
     if rc:
@@ -2086,10 +2117,35 @@ class Mic2Reader:
         self._cb.check(rc, "Mic2Reader.read_crops")
         return st, stats
 
+    def set_cache(self, cache: Optional["FrameCache"]) -> None:
+        """mic_hip_mic2_reader_set_cache: read_crops (and mic2_readers_read_crops) then decode only the frames that are not
+        resident in `cache`, and read only their streams; None detaches and drops this reader's entries.  A cache of another
+        frame size raises MicError(MIC_ERR_ARGS)."""
+        rc = lib().mic_hip_mic2_reader_set_cache(self._h, cache._h if cache is not None else None)
+        if rc:
+            _raise(rc, "Mic2Reader.set_cache")
+        self._cache = cache                            # (kept alive while attached)
+
+    def cache_probe(self, frames) -> np.ndarray:
+        """bool per frame index: resident in this reader's cache; changes no state"""
+        return _cache_probe(lambda t, n, r: lib().mic_hip_mic2_reader_cache_probe(self._h, t, n, r), frames, np.uint32)
+
+    def set_timing(self, on) -> None:
+        """mic_hip_mic2_reader_set_timing: read_crops then times its kernels (HIP events on the session it runs on)"""
+        lib().mic_hip_mic2_reader_set_timing(self._h, int(bool(on)))
+
+    def last_timings(self):
+        """[(kernel name, device ms)] of the last timed read_crops, summed over its launch chains"""
+        names = (C.c_char_p * 96)()
+        ms = (C.c_float * 96)()
+        k = lib().mic_hip_mic2_reader_last_timings(self._h, names, ms, 96)
+        return [(names[i].decode(), float(ms[i])) for i in range(k)]
+
     def close(self) -> None:
         if self._h:
             lib().mic_hip_mic2_reader_close(self._h)
             self._h = C.c_void_p()
+            self._cache = None
 
     def __enter__(self):
         return self

@@ -1,4 +1,5 @@
-// mic_tile_cache.h -- a cache of decoded units in device memory (MIC3 tiles today: mic_api_ext.hip).  Two things live here:
+// mic_tile_cache.h -- a cache of decoded units in device memory (MIC3 tiles: mic_api_ext.hip; reconstructed MIC2 frames:
+// mic_mic2_crops.hip).  Two things live here:
 // SlotIndex, the host-side index and replacement policy, which knows nothing of containers or devices (a key is an owner and a unit
 // number), and mic_hip_tile_cache, the object behind the C ABI: one SlotIndex, one arena of equal slots, one mutex.
 //
@@ -29,6 +30,7 @@ public:
     uint64_t resident() const { return map_.size(); }
     const Counters &counters() const { return cnt_; }
     bool has(const Key &k) const { return map_.find(k) != map_.end(); }
+    uint32_t slot_of(const Key &k) const { const auto it = map_.find(k); return it == map_.end() ? kNoSlot : it->second; }   // (changes no state)
 
     // One call: n distinct keys in the caller's order -> outcome[i] and, for a hit or a miss, slot[i] (kNoSlot for a bypass).
     // What it changes is journalled until commit() or rollback().

@@ -66,6 +66,25 @@ int mic_hip_tile_cache_create(int tile_w, int tile_h, int channels, int bits_per
     return MIC_OK;
 } MIC_ABI_CATCH
 
+// a cache of reconstructed MIC2 frames: the same object, a slot one frame of width x height u16 samples (mic2_crop_args' limits)
+int mic_hip_frame_cache_slot_bytes(int width, int height, uint64_t *bytes) try {
+    if (!bytes || width <= 0 || height <= 0) return MIC_ERR_ARGS;
+    if ((size_t)width * (size_t)height > ((size_t)1 << 28)) return MIC_ERR_UNSUPPORTED;
+    *bytes = ((uint64_t)width * (uint64_t)height * 2 + 255) / 256 * 256;
+    return MIC_OK;
+} MIC_ABI_CATCH
+
+int mic_hip_frame_cache_create(int width, int height, uint64_t nslots, mic_hip_tile_cache **c) try {
+    if (!c) return MIC_ERR_ARGS;
+    *c = nullptr;
+    uint64_t sb = 0;
+    const int rc = mic_hip_frame_cache_slot_bytes(width, height, &sb);
+    if (rc) return rc;
+    if (nslots >= micapi::SlotIndex::kNoSlot || (nslots && sb > (uint64_t)SIZE_MAX / nslots)) return MIC_ERR_UNSUPPORTED;
+    *c = new mic_hip_tile_cache(width, height, 1, 16, sb, nslots);
+    return MIC_OK;
+} MIC_ABI_CATCH
+
 int mic_hip_tile_cache_clear(mic_hip_tile_cache *c) try {
     if (!c) return MIC_OK;
     std::lock_guard<std::mutex> lk(c->mu);
